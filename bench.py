@@ -42,6 +42,8 @@ BLOCK = 65536
 PARAMS = (8, 30, 32)  # the reference CLI's fixed Parameters::new(8, 30, 32) (src/main.rs:108)
 SEED = 0x5EED0001
 HBM_PEAK = 8.0e12
+DUMP_LIMIT = 64 << 20      # --dump-outputs writes at most this many bytes
+DUMP_SAMPLE_BLOCKS = 128   # ... of which the block streams of this many blocks, chosen by a fixed seed
 
 
 def host_cores():
@@ -60,6 +62,29 @@ def host_cores():
         except Exception:
             pass
     return n
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: writes each array as <dirname>/<name>.npy (float32 / float64 only, DUMP_LIMIT bytes in all), so that two
+    builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    if not os.path.isdir(dirname):
+        os.makedirs(dirname)
+        with open(os.path.join(dirname, ".gitignore"), "w") as f:  # a dump made inside a checkout leaves `git status` clean
+            f.write("*\n")
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench.py: wrote {len(arrays)} arrays ({total} bytes) to {dirname}", file=sys.stderr)
+
+
+def dump_sample_blocks(nblocks):
+    """The blocks whose streams --dump-outputs writes: a fixed seeded choice, the same for every build and run."""
+    import numpy as np
+    k = min(DUMP_SAMPLE_BLOCKS, nblocks)
+    return np.sort(np.random.default_rng(SEED).choice(nblocks, size=k, replace=False))
 
 
 def launch_command(n, argv, port=None):
@@ -154,6 +179,10 @@ def file_workload(args, rx, torch, dist, rank, world, dev):
                 assert [h64(d[int(o[i]): int(o[i + 1])].tobytes()) for i in range(nblocks)] == gold["block_hashes"], \
                     "streams differ from tests/golden/blocks.json"
                 golden = "every block's size and blake2b-64 equal tests/golden/blocks.json"
+        if args.dump_outputs:
+            # the last timed round trip, whole: compressed stream, its offsets table, the decoded file
+            dump_outputs(args.dump_outputs, {"stream": d.astype("float32"), "offsets": o.astype("float64"),
+                                             "decoded": back.cpu().numpy().astype("float32")})
         per = (nblocks + world - 1) // world
         line = {
             "metric": "encode MB/s (whole node), per-block bitstream bit-exact",
@@ -182,7 +211,7 @@ def file_workload(args, rx, torch, dist, rank, world, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)  # the chip's clocks settle only after ~0.2 s of load
     ap.add_argument("--blocks", type=int, default=65536, help="blocks per GPU (default: the config's 65,536)")
     ap.add_argument("--workload", default="iid",
@@ -197,7 +226,13 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks share cuda:0 and rendezvous over gloo: exercises the multi-rank code path on a one-GPU box "
                          "(the line says so; not a scaling measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB): iid / zipf: offsets, status, summary and the streams of a fixed seeded sample of "
+                         f"{DUMP_SAMPLE_BLOCKS} blocks (stream_sample, blocks listed in stream_sample_blocks); file: stream, offsets, decoded")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # Plain `python bench.py --gpus N`: this process becomes the launcher.  It has made no HIP
@@ -277,6 +312,19 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+
+    if args.dump_outputs:
+        import numpy as np
+        offs_h = enc.offsets[: nblocks + 1].cpu().numpy()
+        pick = dump_sample_blocks(nblocks)
+        stream = torch.cat([enc.out[int(offs_h[b]): int(offs_h[b + 1])] for b in pick]).cpu().numpy()
+        dump_outputs(args.dump_outputs, {
+            "offsets": offs_h.astype(np.float64),
+            "status": enc.status[:nblocks].cpu().numpy().astype(np.float32),
+            "summary": enc.summary.cpu().numpy().astype(np.float32),
+            "stream_sample": stream.astype(np.float32),
+            "stream_sample_blocks": pick.astype(np.float64),
+        })
 
     total_in = n * world
     value = total_in / elapsed * args.steps / 1e6

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,3 +63,27 @@ def test_main_with_gpus_2_launches_before_importing_torch(tmp_path):
     assert json.loads(p.stdout.strip().splitlines()[-1])["n_gpus"] == 2   # rank 0's line passes through
     argv = json.load(open(rec))
     assert "--nproc-per-node=2" in argv and "--rehearse-on-one-gpu" in argv and "--gpus" in argv
+
+
+def test_steps_below_one_is_refused_before_any_work():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
+def test_dump_outputs_writes_float_arrays_into_a_self_ignoring_directory(tmp_path):
+    import numpy as np
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), {"a": np.arange(3, dtype=np.float32), "b": np.zeros(2, dtype=np.float64)})
+    assert sorted(os.listdir(d)) == [".gitignore", "a.npy", "b.npy"] and (d / ".gitignore").read_text() == "*\n"
+    assert np.load(d / "a.npy").tolist() == [0, 1, 2] and np.load(d / "b.npy").dtype == np.float64
+    for bad in ({"u8": np.zeros(2, dtype=np.uint8)}, {"big": np.zeros((bench.DUMP_LIMIT >> 3) + 1, dtype=np.float64)}):
+        with pytest.raises(AssertionError):
+            bench.dump_outputs(str(d), bad)
+        assert not (d / (list(bad)[0] + ".npy")).exists()
+
+
+def test_dump_sample_is_fixed_and_inside_the_launch():
+    a, b = bench.dump_sample_blocks(65536), bench.dump_sample_blocks(65536)
+    assert len(a) == bench.DUMP_SAMPLE_BLOCKS and (a == b).all() and len(set(a.tolist())) == len(a) and a.max() < 65536
+    assert sorted(bench.dump_sample_blocks(5).tolist()) == [0, 1, 2, 3, 4]

@@ -1003,6 +1003,42 @@ def test_bench_self_launch_two_ranks_on_one_gpu(rx):
     assert line["roundtrip_equal"] and line["golden"] and all(line["phases"][k] >= 0 for k in ("scatter_ms", "encode_ms", "gather_ms", "decode_ms"))
 
 
+def test_bench_dump_outputs_are_the_last_steps_streams(rx, tmp_path):
+    """`bench.py --dump-outputs DIR`: the timed path's offsets, statuses and the streams of the sampled blocks, equal to the
+    CPU oracle on the same (seeded) input and identical in a second run; `--steps` is the number of timed steps."""
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(GOLDEN))
+    nblocks = 300
+
+    def run(d, steps):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--blocks", str(nblocks), "--steps",
+                            str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-decode", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        names = sorted(f[:-4] for f in os.listdir(d) if f.endswith(".npy"))
+        assert names == ["offsets", "status", "stream_sample", "stream_sample_blocks", "summary"]
+        arrs = {k: np.load(os.path.join(d, k + ".npy")) for k in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        return arrs
+
+    a = run(tmp_path / "a", 3)
+    offs = a["offsets"].astype(np.int64)
+    pick = a["stream_sample_blocks"].astype(np.int64)
+    assert len(offs) == nblocks + 1 and offs[0] == 0 and (np.diff(offs) > 0).all()
+    assert not a["status"].any() and a["summary"].tolist() == [0, 0] and pick.tolist() == bench.dump_sample_blocks(nblocks).tolist()
+    host = rx.gen_iid(nblocks * BLOCK).cpu().numpy()
+    want = b"".join(ox.compress(host[b * BLOCK:(b + 1) * BLOCK].tobytes(), (8, 30, 32))[0] for b in pick)
+    assert a["stream_sample"].astype(np.uint8).tobytes() == want
+    assert len(want) == int((offs[pick + 1] - offs[pick]).sum())
+    b = run(tmp_path / "b", 2)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_host_abi_pipeline_many_chunks(rx):
     """The host-pointer calls cut the work into chunks of whole blocks that run on several streams
     (redux_amd/csrc/redux_host.hpp).  Inputs that span several chunks, with a ragged tail, at three
