@@ -281,6 +281,51 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
                                    uint64_t out_cap, void *d_out_sizes, void *d_block_status, void *d_summary,
                                    void *stream);
 
+/* ---- byte-plane layout of typed data ("shuffle" filter) ----------------------------------------
+ * An order-0 byte model sees the bytes of bf16 / fp32 / int64 data interleaved: the skewed exponent byte is mixed with
+ * mantissa bytes that are close to uniform.  These calls put a byte transform in front of the coder that makes each BLOCK
+ * hold one byte plane.  E = element_size, one of 1, 2, 4, 8 (1 = no layout: results identical to the plain calls);
+ * B = block_size.
+ *   - The input is cut into frames of E*B bytes; only the last may be shorter.  A frame of L bytes holds N = L / E
+ *     elements; byte p of element i moves to frame offset p*N + i; the L - N*E trailing bytes stay at the end unchanged.
+ *   - So a full frame is exactly E blocks, block j of the frame being plane j of B elements.  The block cut, the streams
+ *     and the container are then exactly those of the plain calls applied to the transformed bytes:
+ *     stream_E(x)[b] == redux_encode_blocks(planes_E(x))[b].
+ * (The adaptive model's cost of a block is the same for any order of its bytes: shuffling INSIDE a block gains nothing.)
+ * Not available for the `_v` calls, redux_compress / redux_decompress and the static-table model.
+ *
+ * redux_planes_check          OK for 1, 2, 4, 8, else INVALID_INPUT.
+ * redux_planes_dev            the transform (inverse = 0) or its inverse (inverse != 0) of len bytes, d_src -> d_dst (device
+ *                             buffers that must not overlap), stream-ordered.
+ * redux_encode_planes_dev     redux_encode_blocks_dev of the transformed input.  The transformed copy is carved from the
+ *                             FRONT of the workspace (redux_encode_planes_workspace_bytes; E = 1: the plain call's workspace).
+ * redux_decode_planes_dev     the inverse: nblocks = redux_block_count(out_len, block_size) streams, block b must decode to
+ *                             min(block_size, out_len - b*block_size) bytes -- one that comes back OK with another size is
+ *                             reported INVALID_INPUT (and counted in d_summary) --, the blocks decode into a plane buffer in
+ *                             the workspace and the inverse transform writes d_out[0 .. out_len); no byte outside that
+ *                             range is written, for damaged streams too.  Every frame whose blocks are all OK holds the
+ *                             original bytes.  d_out_sizes / d_block_status: nblocks entries.
+ * redux_encode_blocks_planes  host-pointer forms through the same chunk pipeline as redux_encode_blocks /
+ * redux_decode_blocks_planes  redux_decode_blocks (chunks are whole 64-block waves, so whole frames: the output depends on
+ *                             neither the chunk size nor the devices of redux_host_set_devices); decode writes out[0 .. out_len).
+ */
+int      redux_planes_check(uint32_t element_size);
+int      redux_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                          void *stream);
+uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                            void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status);
+int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

@@ -135,14 +135,25 @@ def _ptr(a):
 
 
 # ---- block API, host buffers ------------------------------------------------------------
-def compress_blocks(data, block_size, params=(8, 30, 32)):
+def _check_element_size(element_size):
+    """1 (no layout), 2, 4 or 8; anything else is InvalidInput (redux_planes_check)."""
+    if not isinstance(element_size, (int, np.integer)) or not 0 < element_size < 1 << 32 \
+            or _lib.lib().redux_planes_check(int(element_size)) != _lib.OK:
+        raise InvalidInput()
+    return int(element_size)
+
+
+def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
-    offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block."""
+    offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
+    element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
+    layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes."""
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
     cp = P._c()
     _raise(L.redux_device_supports(C.byref(cp)))
+    E = _check_element_size(element_size)
     if block_size <= 0:
         raise InvalidInput()
     nb = L.redux_block_count(len(a), block_size)
@@ -150,15 +161,27 @@ def compress_blocks(data, block_size, params=(8, 30, 32)):
     out = np.empty(cap, dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
-    st = L.redux_encode_blocks(C.byref(cp), _ptr(a), len(a), block_size, out.ctypes.data, cap, offs.ctypes.data,
-                               status.ctypes.data)
+    if E == 1:
+        st = L.redux_encode_blocks(C.byref(cp), _ptr(a), len(a), block_size, out.ctypes.data, cap, offs.ctypes.data,
+                                   status.ctypes.data)
+    else:
+        st = L.redux_encode_blocks_planes(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
+                                          offs.ctypes.data, status.ctypes.data)
     _raise(st)
     return out[: int(offs[-1])], offs, status
 
 
-def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True):
+def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
-    sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]]."""
+    sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
+    With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
+    required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
+    (frames with a damaged block hold undefined bytes; their blocks' status says which)."""
+    E = _check_element_size(element_size)
+    if E > 1 and length is None:
+        raise InvalidInput()
+    if length is not None:
+        return _decompress_blocks_planes(streams, offsets, block_size, params, check, E, int(length))
     P = _params_of(params)
     a = _u8(streams)
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -176,6 +199,27 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     if check:
         _raise(st)
     return out, sizes, status
+
+
+def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, length):
+    P = _params_of(params)
+    a = _u8(streams)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    L = _lib.lib()
+    if block_size <= 0 or length < 0 or len(offs) != L.redux_block_count(length, block_size) + 1 or int(offs[-1]) > len(a) \
+            or bool((offs[1:] < offs[:-1]).any()):
+        raise InvalidInput()
+    cp = P._c()
+    _raise(L.redux_device_supports(C.byref(cp)))
+    nb = len(offs) - 1
+    out = np.empty(max(length, 1), dtype=np.uint8)
+    sizes = np.zeros(nb, dtype=np.uint32)
+    status = np.zeros(nb, dtype=np.int32)
+    st = L.redux_decode_blocks_planes(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
+                                      sizes.ctypes.data, status.ctypes.data)
+    if check:
+        _raise(st)
+    return out[:length], sizes, status
 
 
 # ---- several GPUs behind the host-pointer calls ------------------------------------------------
@@ -347,16 +391,18 @@ class DeviceEncoder:
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
     on torch's current stream."""
 
-    def __init__(self, params, block_size, max_in_len, device="cuda:0"):
+    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1):
         torch = _torch()
         self.P = _params_of(params)
         self.cp = self.P._c()
         L = _lib.lib()
         _raise(L.redux_device_supports(C.byref(self.cp)))
+        self.element_size = _check_element_size(element_size)  # > 1: the byte-plane layout in front of the coder
         self.block_size = int(block_size)
         self.max_in_len = int(max_in_len)
         self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        self.ws_bytes = L.redux_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size)
+        self.ws_bytes = L.redux_encode_planes_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size,
+                                                              self.element_size)
         self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
         self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
@@ -373,6 +419,8 @@ class DeviceEncoder:
     def encode_slots(self, d_in):
         """Phase 1 only: the coder kernel (padded slots + sizes inside the workspace)."""
         torch = _torch()
+        if self.element_size != 1:
+            raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout)
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
         st = _lib.lib().redux_encode_slots_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
@@ -384,6 +432,8 @@ class DeviceEncoder:
     def compact(self, n):
         """Phase 2 only: scan + gather into the dense output."""
         torch = _torch()
+        if self.element_size != 1:
+            raise Unsupported()
         self.summary.zero_()
         st = _lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, C.c_void_p(self.out.data_ptr()),
                                                 self.out_cap, C.c_void_p(self.offsets.data_ptr()),
@@ -400,28 +450,41 @@ class DeviceEncoder:
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
         self.summary.zero_()
-        st = _lib.lib().redux_encode_blocks_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
-                                                C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                _stream_ptr(torch))
+        if self.element_size == 1:
+            st = _lib.lib().redux_encode_blocks_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
+                                                    C.c_void_p(self.out.data_ptr()), self.out_cap,
+                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+                                                    _stream_ptr(torch))
+        else:
+            st = _lib.lib().redux_encode_planes_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
+                                                    self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
+                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+                                                    _stream_ptr(torch))
         _raise(st)
         nb = _lib.lib().redux_block_count(n, self.block_size)
         return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
 
 
 class DeviceDecoder:
-    """Reusable decoder for up to max_blocks blocks resident in HBM."""
+    """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
+    layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes."""
 
-    def __init__(self, params, block_size, max_blocks, device="cuda:0"):
+    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1):
         torch = _torch()
         self.P = _params_of(params)
         self.cp = self.P._c()
         L = _lib.lib()
         _raise(L.redux_device_supports(C.byref(self.cp)))
+        self.element_size = _check_element_size(element_size)
         self.block_size = int(block_size)
         self.max_blocks = int(max_blocks)
-        self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
+        if self.element_size == 1:
+            self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
+        else:
+            self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
+                                                                  self.block_size, self.element_size)
         self.device = torch.device(device)
         self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
         self.ws_off = (-self.ws.data_ptr()) % 256
@@ -431,10 +494,32 @@ class DeviceDecoder:
         self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
 
     @_on_device
-    def decode(self, d_streams, d_offsets):
+    def decode(self, d_streams, d_offsets, length=None):
+        """length: bytes of the original input; required with element_size > 1 (d_offsets then holds
+        redux_block_count(length, block_size) + 1 entries), and the result is out[:length]."""
         torch = _torch()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
+        if self.element_size > 1 and length is None:
+            raise InvalidInput()
+        if length is not None:
+            L = _lib.lib()
+            if length < 0 or L.redux_block_count(int(length), self.block_size) != nb:
+                raise InvalidInput()
+            if self.element_size == 1 and self.ws_bytes < L.redux_decode_planes_workspace_bytes(
+                    C.byref(self.cp), int(length), self.block_size, 1):
+                self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
+                                                                      self.block_size, 1)
+                self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
+                self.ws_off = (-self.ws.data_ptr()) % 256
+            self.summary.zero_()
+            st = L.redux_decode_planes_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
+                                           C.c_void_p(d_offsets.data_ptr()), int(length), self.block_size, self.element_size,
+                                           C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
+                                           C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
+                                           C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
+            _raise(st)
+            return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
         self.summary.zero_()
         st = _lib.lib().redux_decode_blocks_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
                                                 C.c_void_p(d_offsets.data_ptr()), nb, self.block_size,
@@ -506,6 +591,24 @@ class DeviceStaticCoder:
             C.c_void_p(self.dec_summary.data_ptr()), _stream_ptr(torch))
         _raise(st)
         return self.dec_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+
+
+# ---- byte-plane layout of typed data ----------------------------------------------------------
+def planes(d_src, element_size, block_size, inverse=False, out=None):
+    """The byte-plane layout (include/redux_hip.h) of a uint8 device tensor, or its inverse: redux_planes_dev on torch's
+    current stream.  out: a uint8 tensor of the same length on the same device (allocated when None)."""
+    torch = _torch()
+    E = _check_element_size(element_size)
+    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
+    if block_size <= 0:
+        raise InvalidInput()
+    n = d_src.numel()
+    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
+    with torch.cuda.device(t.device):
+        _raise(_lib.lib().redux_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
+                                           1 if inverse else 0, _stream_ptr(torch)))
+    return t
 
 
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------

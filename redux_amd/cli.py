@@ -1,29 +1,31 @@
 """Command line with the reference's interface (src/main.rs):
 
-    python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N]
+    python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
 `--block-size 0` (the default) produces / expects the reference's raw single stream -- one
 coder, so one GPU lane; any other value cuts the input into independent blocks coded in
 parallel and wraps them in the container of redux_amd/container.py.  All coding runs on the
-GPU: there is no CPU path.
+GPU: there is no CPU path.  `--element-size 2|4|8` (with a block size) codes typed data -- bf16 / fp16, fp32 / int32,
+fp64 / int64 -- in the byte-plane layout (container version 2); decoding reads the element size from the container.
+A raw reference stream has no place to record it: `--element-size` above 1 with `--block-size 0` is a usage error.
 """
 import io
 import sys
 
-USAGE = "Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>]"
+USAGE = "Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>]"
 
 
 def parse(argv):
-    opts = {"compress": None, "input": None, "output": None, "block_size": 0}
+    opts = {"compress": None, "input": None, "output": None, "block_size": 0}  # (+ "element_size" when given)
     it = iter(argv)
     for arg in it:
         if arg == "-c":
             opts["compress"] = True
         elif arg == "-d":
             opts["compress"] = False
-        elif arg in ("-i", "-o", "--block-size"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size"):
             val = next(it, None)
             if val is None:
                 return None
@@ -31,6 +33,10 @@ def parse(argv):
                 opts["input"] = val
             elif arg == "-o":
                 opts["output"] = val
+            elif arg == "--element-size":
+                if val not in ("1", "2", "4", "8"):
+                    return None
+                opts["element_size"] = int(val)
             else:
                 try:
                     opts["block_size"] = int(val)
@@ -40,6 +46,8 @@ def parse(argv):
                     return None
         else:
             return None
+    if opts.get("element_size", 1) > 1 and opts["block_size"] == 0:
+        return None  # a raw reference stream has no place to record the element size
     return None if opts["compress"] is None else opts
 
 
@@ -68,7 +76,7 @@ def main(argv=None):
                 i_n, o_n = api.compress(io.BytesIO(data), o, api.AdaptiveTreeModel.new(params))
                 sink.write(o.getvalue())
             else:
-                blob = container.compress_bytes(data, opts["block_size"], params)
+                blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -6,14 +6,18 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 
 Layout (little-endian):
     0   4  magic  b"RDXB"
-    4   1  version (1)
+    4   1  version (1; 2 = byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
-   12   4  reserved (0)
+   12   4  version 1: reserved (0); version 2: element size E, one of 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
    32  4*nblocks   compressed size of each block
    ..  payloads, concatenated in block order
+
+Version 2 is the same layout for data coded with the byte-plane layout of typed data (include/redux_hip.h): the payloads
+are the streams of the transformed bytes, and decoding undoes the layout.  Element size 1 (no layout) writes version 1,
+byte for byte what this module wrote before version 2 existed.
 """
 import struct
 
@@ -23,6 +27,8 @@ from . import api
 
 MAGIC = b"RDXB"
 VERSION = 1
+VERSION_PLANES = 2
+ELEMENT_SIZES = (2, 4, 8)  # what version 2 may record
 HEADER = struct.Struct("<4sBBBBIIQQ")
 # A header field, not a promise: a crafted 40-byte file must not make the decoder allocate
 # gigabytes.  The container never holds blocks above 1 GiB (the CLI refuses larger ones), and
@@ -30,14 +36,18 @@ HEADER = struct.Struct("<4sBBBBIIQQ")
 MAX_BLOCK_SIZE = 1 << 30
 
 
-def pack(streams, offsets, params, block_size, total_len):
-    """streams: dense uint8 array; offsets: uint64[nblocks+1]."""
+def pack(streams, offsets, params, block_size, total_len, element_size=1):
+    """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
+    byte-plane layout (version 2)."""
+    if element_size != 1 and element_size not in ELEMENT_SIZES:
+        raise api.InvalidInput()
     P = api._params_of(params)
     offs = np.asarray(offsets, dtype=np.uint64)
     sizes = np.diff(offs.astype(np.int64))
     if (sizes < 0).any() or (sizes > 0xFFFFFFFF).any():
         raise api.InvalidInput()
-    head = HEADER.pack(MAGIC, VERSION, P.symbol_bits, P.freq_bits, P.code_bits, block_size, 0, len(sizes), total_len)
+    ver, res = (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
+    head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     return head + sizes.astype("<u4").tobytes() + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
 
@@ -47,8 +57,10 @@ def unpack(buf):
     b = memoryview(buf)
     if len(b) < HEADER.size:
         raise api.Eof()
-    magic, ver, sb, fb, cb, block_size, _res, nblocks, total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or ver != VERSION or block_size == 0 or block_size > MAX_BLOCK_SIZE:
+    magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
+    if magic != MAGIC or ver not in (VERSION, VERSION_PLANES) or block_size == 0 or block_size > MAX_BLOCK_SIZE:
+        raise api.InvalidInput()
+    if ver == VERSION_PLANES and res not in ELEMENT_SIZES:
         raise api.InvalidInput()
     P = api.Parameters(sb, fb, cb)
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
@@ -65,6 +77,18 @@ def unpack(buf):
     return P, block_size, total, offsets, payload
 
 
+def element_size(buf):
+    """Element size of the byte-plane layout a container records: 1 for version 1, E for version 2.  Malformed headers
+    raise InvalidInput, truncated ones Eof."""
+    b = memoryview(buf)
+    if len(b) < HEADER.size:
+        raise api.Eof()
+    magic, ver, _sb, _fb, _cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
+    if magic != MAGIC or ver not in (VERSION, VERSION_PLANES) or (ver == VERSION_PLANES and res not in ELEMENT_SIZES):
+        raise api.InvalidInput()
+    return 1 if ver == VERSION else res
+
+
 def header_is_wellformed(buf):
     """True when the first 32 bytes are a consistent container header: magic, version, a triple
     Parameters::new accepts, a block size in range and a block count that matches the declared
@@ -75,7 +99,9 @@ def header_is_wellformed(buf):
     if len(b) < HEADER.size:
         return False
     magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or ver != VERSION or res != 0 or not 0 < block_size <= MAX_BLOCK_SIZE:
+    if magic != MAGIC or not 0 < block_size <= MAX_BLOCK_SIZE:
+        return False
+    if not ((ver == VERSION and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)):
         return False
     try:
         api.Parameters.new(sb, fb, cb)
@@ -84,12 +110,15 @@ def header_is_wellformed(buf):
     return nblocks == (1 if total == 0 else (total + block_size - 1) // block_size)
 
 
-def compress_bytes(data, block_size=65536, params=(8, 30, 32)):
-    """bytes -> container bytes (every block coded on the GPU)."""
-    if not 0 < block_size <= MAX_BLOCK_SIZE:
+def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1):
+    """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2."""
+    if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES):
         raise api.InvalidInput()
-    out, offs, _ = api.compress_blocks(data, block_size, params)
-    return pack(out, offs, params, block_size, len(data))
+    if element_size == 1:
+        out, offs, _ = api.compress_blocks(data, block_size, params)
+    else:
+        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size)
+    return pack(out, offs, params, block_size, len(data), element_size)
 
 
 def decompress_bytes(buf):
@@ -101,6 +130,16 @@ def decompress_bytes(buf):
     nb = len(offsets) - 1
     if len(payload) < nb:
         raise api.InvalidInput()
+    E = element_size(buf)
+    if E > 1:  # (frames are E * block_size bytes: the blocks decode at their real size, into out[0 .. total))
+        try:
+            out, sizes, _ = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total)
+        except MemoryError:
+            raise api.InvalidInput()
+        expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]
+        if [int(x) for x in sizes] != expect:
+            raise api.InvalidInput()
+        return out.tobytes()
     cap = max(1, min(block_size, total))  # one short block never needs block_size bytes of capacity
     try:
         out, sizes, _ = api.decompress_blocks(payload, offsets, cap, P)

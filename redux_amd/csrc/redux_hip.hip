@@ -11,6 +11,7 @@
 //   redux_decode_cells.hpp  k_decode_cells: their decoder, the tree as cells of four levels
 //   redux_synth.hpp    k_gen_iid / k_gen_zipf
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
+//   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -28,6 +29,7 @@
 #include "redux_coop.hpp"
 #include "redux_synth.hpp"
 #include "redux_static.hpp"
+#include "redux_planes.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -440,6 +442,42 @@ static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, ui
 #include "redux_host.hpp"
 
 using namespace redux;
+
+// the byte-plane layout (redux_planes.hpp): the fast kernel over the full frames when it applies, the byte kernel for the rest
+template <int E>
+static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
+{
+    PlanesArgs a;
+    a.src          = (const uint8_t *)d_src;
+    a.dst          = (uint8_t *)d_dst;
+    a.block_size   = block_size;
+    a.frame_groups = block_size / 16;
+    a.len          = len;
+    a.first        = 0;
+    a.groups       = 0;
+    const uint64_t frame = (uint64_t)E * block_size, nfull = len / frame;
+    if (block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 && nfull) {
+        a.groups = nfull * a.frame_groups;
+        const uint64_t wgs = (a.groups + 255) / 256;
+        if (wgs > 0x7FFFFFFFull)
+            return REDUX_UNSUPPORTED;
+        if (inverse)
+            k_planes<E, true><<<(uint32_t)wgs, 256, 0, s>>>(a);
+        else
+            k_planes<E, false><<<(uint32_t)wgs, 256, 0, s>>>(a);
+        a.first = nfull * frame;
+    }
+    if (a.first < len) { // the short last frame, or everything the fast kernel cannot take
+        const uint64_t n = len - a.first, wgs = (n + 255) / 256;
+        const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
+        if (inverse)
+            k_planes_bytes<E, true><<<grid, 256, 0, s>>>(a);
+        else
+            k_planes_bytes<E, false><<<grid, 256, 0, s>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
 
 extern "C" {
 
@@ -1428,6 +1466,128 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
         k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
+}
+
+// ---- byte-plane layout (redux_planes.hpp) ---------------------------------------------------------
+int redux_planes_check(uint32_t element_size)
+{
+    return (element_size == 1 || element_size == 2 || element_size == 4 || element_size == 8) ? REDUX_OK : REDUX_INVALID_INPUT;
+}
+
+int redux_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                     void *stream)
+{
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place: the transform reads bytes another thread writes)
+        return REDUX_INVALID_INPUT;
+    hipStream_t s = (hipStream_t)stream;
+    switch (element_size) {
+    case 2: return launch_planes<2>(d_src, d_dst, len, block_size, inverse != 0, s);
+    case 4: return launch_planes<4>(d_src, d_dst, len, block_size, inverse != 0, s);
+    case 8: return launch_planes<8>(d_src, d_dst, len, block_size, inverse != 0, s);
+    default: HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s)); return REDUX_OK;
+    }
+}
+
+uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_planes_check(element_size) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    if (ws == 0 || element_size == 1) // (E = 1: the plain call, on the caller's buffer)
+        return ws;
+    return planes_copy_bytes(in_len) + ws;
+}
+
+uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0)
+        return 0;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const uint64_t ws      = redux_decode_workspace_bytes(p, nblocks, block_size);
+    return ws ? planes_copy_bytes(nblocks * (uint64_t)block_size) + ws : 0;
+}
+
+// the transformed copy at the front of the workspace, the plain encoder behind it with what is left
+int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    if (element_size == 1)
+        return redux_encode_blocks_dev(p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary,
+                                       d_workspace, workspace_bytes, stream);
+    const uint64_t copy = planes_copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *t = (uint8_t *)d_workspace;
+    if ((st = redux_planes_dev(d_in, t, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+        return st;
+    return redux_encode_blocks_dev(p, t, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, t + copy,
+                                   workspace_bytes - copy, stream);
+}
+
+// the blocks decode into a plane buffer at the front of the workspace (block_size bytes of room each, so a damaged stream
+// writes nothing outside it); their sizes are checked against the layout; the inverse transform writes d_out[0 .. out_len)
+int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes ||
+        !d_block_status || (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
+    if (workspace_bytes < redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *t = (uint8_t *)d_workspace;
+    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
+                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr);
+    if (st != REDUX_OK)
+        return st;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
+                                                                        (int32_t *)d_summary, nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    return redux_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream);
+}
+
+int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(p, in, in_len, block_size, out, out_cap, out_offsets, block_status, element_size); // redux_host.hpp
+}
+
+int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !in_offsets || !out_sizes || (out_len && !out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    if (in_offsets[nblocks] && !in)
+        return REDUX_INVALID_INPUT;
+    return host::decode_blocks(p, in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, nullptr,
+                               decode_blocks_dev_impl, element_size, out_len); // redux_host.hpp
 }
 
 int redux_host_release(void) { return host::ctx_release_all(); }

@@ -463,6 +463,7 @@ struct EncCall {
     uint64_t            out_cap;
     uint64_t           *out_offsets;
     int32_t            *block_status;
+    uint32_t            element_size; // > 1: the byte-plane layout in front of the coder (redux_encode_planes_dev)
     uint64_t            nblocks, cb, nchunks, ws_bytes, bound, chunk_in;
 };
 
@@ -580,8 +581,11 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
                     return r;
                 HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
                 uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-                r = redux_encode_blocks_dev(E.p, s.d_in.p, len, E.block_size, s.d_out.p, E.bound, s.d_off.p, s.d_st.p, s.d_sum.p, ws,
-                                            E.ws_bytes, st);
+                // (a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64)
+                r = E.element_size > 1 ? redux_encode_planes_dev(E.p, s.d_in.p, len, E.block_size, E.element_size, s.d_out.p, E.bound,
+                                                                 s.d_off.p, s.d_st.p, s.d_sum.p, ws, E.ws_bytes, st)
+                                       : redux_encode_blocks_dev(E.p, s.d_in.p, len, E.block_size, s.d_out.p, E.bound, s.d_off.p, s.d_st.p,
+                                                                 s.d_sum.p, ws, E.ws_bytes, st);
                 if (r != REDUX_OK)
                     return r;
                 // (the small result arrays are fetched by the drain thread once the event has fired: a D2H
@@ -616,7 +620,7 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
 }
 
 static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out,
-                         uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+                         uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t element_size = 1)
 {
     std::vector<Ctx *> ctx;
     std::vector<std::unique_lock<std::mutex>> locks;
@@ -628,7 +632,7 @@ static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_l
 
     EncCall E;
     E.p = p; E.in = in; E.in_len = in_len; E.block_size = block_size; E.out = out; E.out_cap = out_cap;
-    E.out_offsets = out_offsets; E.block_status = block_status;
+    E.out_offsets = out_offsets; E.block_status = block_status; E.element_size = element_size;
     E.nblocks  = redux_block_count(in_len, block_size);
     E.cb       = chunk_blocks_for(E.nblocks, block_size, kEncChunkMax, ctx.size());
     E.nchunks  = (E.nblocks + E.cb - 1) / E.cb;
@@ -636,6 +640,8 @@ static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_l
     E.ws_bytes = redux_encode_workspace_bytes(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
     if (E.nchunks > 1) // several chunks in flight keep the chip busy: no pairs area, so the chunks run on the pair kernel (encode_slots_impl)
         E.ws_bytes = geometry(p, E.chunk_in, block_size, false, false).total;
+    if (element_size > 1) // the transformed copy of a chunk goes in front (redux_encode_planes_dev)
+        E.ws_bytes += planes_copy_bytes(E.chunk_in < in_len ? E.chunk_in : in_len);
     E.bound    = redux_encode_bound(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
     Job J;
     J.total.assign(E.nchunks, 0);
@@ -678,7 +684,15 @@ struct DecCall {
     int32_t            *block_status;
     uint64_t           *in_used;
     DecodeDevCall       dev_call;
+    uint32_t            element_size; // > 0: redux_decode_planes_dev, whose output is out[0 .. out_len) exactly
+    uint64_t            out_len;
     uint64_t            cb, nchunks, wsb, max_in;
+
+    uint64_t chunk_out(uint64_t b0, uint64_t nb) const // bytes a chunk's blocks write into out
+    {
+        const uint64_t full = nb * (uint64_t)block_size, o = b0 * (uint64_t)block_size;
+        return element_size ? (out_len - o < full ? out_len - o : full) : full;
+    }
 };
 
 static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint64_t stride)
@@ -726,7 +740,8 @@ static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint
             if (!err) {
                 if (((const int32_t *)s.h_sum.p)[0] != REDUX_OK)
                     J.note_bad(k, ((const int32_t *)s.h_sum.p)[0]);
-                err = drain_d2h(c, D.out + b0 * (uint64_t)D.block_size, s.d_out.p, nb * (uint64_t)D.block_size);
+                const uint64_t n = D.chunk_out(b0, nb);
+                err = n ? drain_d2h(c, D.out + b0 * (uint64_t)D.block_size, s.d_out.p, n) : REDUX_OK;
             }
             if (!err) {
                 memcpy(D.out_sizes + b0, s.h_sz.p, nb * 4);
@@ -784,8 +799,10 @@ static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint
                     return r;
                 HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
                 uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-                r = D.dev_call(D.p, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p, nb * (uint64_t)D.block_size, s.d_sz.p, s.d_st.p,
-                               s.d_sum.p, ws, D.wsb, st, D.in_used ? s.d_used.p : nullptr, nullptr, false, 0);
+                r = D.element_size ? redux_decode_planes_dev(D.p, s.d_in.p, s.d_off.p, D.chunk_out(b0, nb), D.block_size, D.element_size,
+                                                             s.d_out.p, s.d_sz.p, s.d_st.p, s.d_sum.p, ws, D.wsb, st)
+                                   : D.dev_call(D.p, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p, nb * (uint64_t)D.block_size, s.d_sz.p,
+                                                s.d_st.p, s.d_sum.p, ws, D.wsb, st, D.in_used ? s.d_used.p : nullptr, nullptr, false, 0);
                 if (r != REDUX_OK)
                     return r;
                 HOST_TRY(hipEventRecord(s.done, st)); // (small result arrays: fetched by the drain thread, see encode_on_ctx)
@@ -818,7 +835,7 @@ static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint
 
 static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
                          uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
-                         uint64_t *in_used, DecodeDevCall dev_call)
+                         uint64_t *in_used, DecodeDevCall dev_call, uint32_t element_size = 0, uint64_t out_len = 0)
 {
     (void)out_cap;
     std::vector<Ctx *> ctx;
@@ -832,9 +849,11 @@ static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_
     DecCall D;
     D.p = p; D.in = in; D.in_offsets = in_offsets; D.nblocks = nblocks; D.block_size = block_size; D.out = out;
     D.out_sizes = out_sizes; D.block_status = block_status; D.in_used = in_used; D.dev_call = dev_call;
+    D.element_size = element_size; D.out_len = out_len;
     D.cb      = chunk_blocks_for(nblocks, block_size, kDecChunkMax, ctx.size());
     D.nchunks = (nblocks + D.cb - 1) / D.cb;
-    D.wsb     = redux_decode_workspace_bytes(p, D.cb, block_size);
+    D.wsb     = element_size ? redux_decode_planes_workspace_bytes(p, D.cb * (uint64_t)block_size, block_size, element_size)
+                             : redux_decode_workspace_bytes(p, D.cb, block_size);
     D.max_in  = 0;
     for (uint64_t k = 0; k < D.nchunks; k++) {
         const uint64_t b0 = k * D.cb, b1 = (b0 + D.cb <= nblocks ? b0 + D.cb : nblocks);

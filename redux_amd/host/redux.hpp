@@ -12,6 +12,7 @@
 //   redux::decompress(istream, ostream, model)              src/lib.rs:113
 //   redux::hip::compress_blocks / decompress_blocks         the block API the GPU path adds
 //   redux::hip::compress_blocks_v / decompress_blocks_v     many independent inputs in one launch (tests/corpora.rs:32-85)
+//   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
 //
 // Every stream byte is produced by the gfx950 kernels; there is no CPU coder in this header.
 #pragma once
@@ -154,6 +155,44 @@ inline std::vector<std::uint8_t> decompress_blocks(const Blocks &streams, std::u
                               sz.data(), nullptr));
     if (sizes)
         *sizes = sz;
+    return out;
+}
+
+// Typed data in the byte-plane layout (include/redux_hip.h): element_size 2, 4 or 8 (1 = no layout, compress_blocks'
+// streams); frames of element_size * block_size bytes are transformed so that each block holds one byte plane.
+inline Blocks compress_blocks_planes(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                     const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_planes(&cp, in, len, block_size, element_size, b.data.data(), b.data.size(), b.offsets.data(), nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_planes(const Blocks &streams, std::uint64_t len, std::uint32_t block_size,
+                                                          std::uint32_t element_size, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT); // (the C call reads data[offsets[b] .. offsets[b + 1]) from caller memory)
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_planes(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
+                                     sizes.data(), nullptr));
+    out.resize(len);
     return out;
 }
 

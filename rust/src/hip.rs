@@ -52,6 +52,11 @@ extern "C" {
                       out_cap: u64, bytes_in: *mut u64, bytes_out: *mut u64) -> c_int;
     fn redux_decompress(p: *const ReduxParams, input: *const u8, in_len: u64, out: *mut u8,
                         out_cap: u64, bytes_in: *mut u64, bytes_out: *mut u64) -> c_int;
+    fn redux_encode_blocks_planes(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                  out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32) -> c_int;
+    fn redux_decode_blocks_planes(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                  block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
+                                  block_status: *mut i32) -> c_int;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
@@ -133,6 +138,49 @@ pub fn decompress_blocks(streams: &[u8], offsets: &[u64], block_size: u32, p: &P
         try!(status(redux_decode_blocks(&cp, streams.as_ptr(), offsets.as_ptr(), nb as u64, block_size,
                                         out.as_mut_ptr(), out.len() as u64, sizes.as_mut_ptr(), ptr::null_mut())));
         Ok((out, sizes))
+    }
+}
+
+/// `compress_blocks` of typed data in the byte-plane layout (include/redux_hip.h): `element_size` 2, 4 or 8 (bf16 / fp16,
+/// fp32 / i32, f64 / i64; 1 = no layout, the same streams as `compress_blocks`).  Frames of `element_size * block_size`
+/// bytes are transformed so that each block holds one byte plane, then coded exactly as `compress_blocks` codes them.
+pub fn compress_blocks_planes(data: &[u8], block_size: u32, element_size: u32, p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_planes(&cp, data.as_ptr(), data.len() as u64, block_size, element_size,
+                                               out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_planes`: `len` is the original byte count; returns the original bytes.
+pub fn decompress_blocks_planes(streams: &[u8], offsets: &[u64], len: u64, block_size: u32, element_size: u32,
+                                p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_planes(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size,
+                                               out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
     }
 }
 
