@@ -344,6 +344,12 @@ const char *redux_decode_kernel_name(const redux_params *p, const void *d_out, u
  * nblocks = blocks (or table entries) of the launch; 0 = a grid that fills the chip, which is what
  * redux_decode_kernel_name answers for. */
 const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out, uint32_t block_size, uint64_t nblocks);
+/* The same for redux_static_encode_blocks_dev / redux_static_decode_blocks_dev: the choice depends on the table total
+ * (>= 2^17: quotient fix-up; <= 2^16: lookup-table decoder; between: lock-step decoder), on code_bits (32 or less) and on
+ * whether the launch has at most one wave (64 blocks) per SIMD of HIP's current device.  Alignment is decided inside
+ * the kernels.  "" for arguments the _dev call rejects, and for nblocks == 0 (the decode call launches nothing). */
+const char *redux_static_encode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t in_len, uint32_t block_size);
+const char *redux_static_decode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t nblocks);
 
 /* Diagnostic, used by the parity tests only: *max_err = max over the integers x in [lo, hi] of
  * |v_rcp_f64(x) * x - 1| evaluated on the device.  The decoder's code-value division

@@ -1312,6 +1312,66 @@ static int static_check(const redux_params *p, const uint32_t *cum)
     return REDUX_OK;
 }
 
+// which static kernel a call runs: ONE decision, used by the launch code and reported by
+// redux_static_encode_kernel_name / redux_static_decode_kernel_name.  "solo": at most one wave per SIMD
+enum class StaticEncKernel { Fixup, Cb32Solo, Cb32, Narrow };
+enum class StaticDecKernel { Fixup, LutCb32Solo, LutSolo, LutCb32, Lut, LockCb32Solo, LockCb32, LockSolo, Lock };
+
+static bool static_solo(uint64_t nblocks) { return (nblocks + 63) / 64 <= 4ull * cu_count(); }
+
+static StaticEncKernel pick_static_encode_kernel(const redux_params *p, uint32_t total, uint64_t nblocks)
+{
+    if (total >= (1u << 17))
+        return StaticEncKernel::Fixup;
+    if (p->code_bits == 32)
+        return static_solo(nblocks) ? StaticEncKernel::Cb32Solo : StaticEncKernel::Cb32;
+    return StaticEncKernel::Narrow;
+}
+
+static StaticDecKernel pick_static_decode_kernel(const redux_params *p, uint32_t total, uint64_t nblocks)
+{
+    if (total >= (1u << 17))
+        return StaticDecKernel::Fixup;
+    const bool solo = static_solo(nblocks), cb32 = p->code_bits == 32;
+    if (total <= 65536u) // get_symbol by direct lookup
+        return solo ? (cb32 ? StaticDecKernel::LutCb32Solo : StaticDecKernel::LutSolo) : (cb32 ? StaticDecKernel::LutCb32 : StaticDecKernel::Lut);
+    return solo ? (cb32 ? StaticDecKernel::LockCb32Solo : StaticDecKernel::LockSolo) : (cb32 ? StaticDecKernel::LockCb32 : StaticDecKernel::Lock);
+}
+
+const char *redux_static_encode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t in_len, uint32_t block_size)
+{
+    if (static_check(p, cum) != REDUX_OK || block_size == 0)
+        return "";
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (64ull * g.slot_bytes >= (1ull << 32) || 64ull * block_size >= (1ull << 32)) // as redux_static_encode_blocks_dev
+        return "";
+    switch (pick_static_encode_kernel(p, cum[kStaticEntries - 1], g.nblocks)) {
+    case StaticEncKernel::Fixup: return "k_encode_static<true, false> (total >= 2^17: quotient fix-up)";
+    case StaticEncKernel::Cb32Solo: return "k_encode_static<false, true, true> (code_bits 32, one wave per SIMD)";
+    case StaticEncKernel::Cb32: return "k_encode_static<false, true> (code_bits 32)";
+    case StaticEncKernel::Narrow: return "k_encode_static<false, false> (code_bits < 32)";
+    }
+    return "";
+}
+
+const char *redux_static_decode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t nblocks)
+{
+    if (static_check(p, cum) != REDUX_OK || nblocks == 0) // (no blocks: the call launches nothing)
+        return "";
+    switch (pick_static_decode_kernel(p, cum[kStaticEntries - 1], nblocks)) {
+    case StaticDecKernel::Fixup: return "k_decode_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)";
+    case StaticDecKernel::LutCb32Solo: return "k_decode_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)";
+    case StaticDecKernel::LutSolo: return "k_decode_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)";
+    case StaticDecKernel::LutCb32: return "k_decode_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)";
+    case StaticDecKernel::Lut: return "k_decode_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)";
+    case StaticDecKernel::LockCb32Solo: return "k_decode_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)";
+    case StaticDecKernel::LockCb32: return "k_decode_static_lock<true, false> (lock-step, code_bits 32)";
+    case StaticDecKernel::LockSolo: return "k_decode_static_lock<false, true> (lock-step, one wave per SIMD)";
+    case StaticDecKernel::Lock: return "k_decode_static_lock<false, false> (lock-step)";
+    }
+    return "";
+}
+
 static double static_rc(uint32_t total)
 {
     double  r = 1.0 / (double)total;
@@ -1374,15 +1434,12 @@ int redux_static_encode_blocks_dev(const redux_params *p, const uint32_t *cum, c
     a.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
     memcpy(a.tab.cum, cum, sizeof a.tab.cum);
     const uint32_t grid = (uint32_t)((g.nblocks + 63) / 64);
-    const bool     solo = grid <= 4u * cu_count(); // as k_decode_static_lock: one wave per SIMD, not two on some
-    if (cum[kStaticEntries - 1] >= (1u << 17))
-        k_encode_static<true, false><<<grid, 64, 0, s>>>(a);
-    else if (p->code_bits == 32 && solo)
-        k_encode_static<false, true, true><<<grid, 64, 0, s>>>(a);
-    else if (p->code_bits == 32)
-        k_encode_static<false, true><<<grid, 64, 0, s>>>(a);
-    else
-        k_encode_static<false, false><<<grid, 64, 0, s>>>(a);
+    switch (pick_static_encode_kernel(p, cum[kStaticEntries - 1], g.nblocks)) { // solo as k_decode_static_lock: one wave per SIMD, not two on some
+    case StaticEncKernel::Fixup: k_encode_static<true, false><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32Solo: k_encode_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32: k_encode_static<false, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Narrow: k_encode_static<false, false><<<grid, 64, 0, s>>>(a); break;
+    }
     HIP_TRY(hipGetLastError());
     return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
@@ -1414,8 +1471,9 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
     a.code_bits  = p->code_bits;
     a.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
     memcpy(a.tab.cum, cum, sizeof a.tab.cum);
-    const uint32_t grid = (uint32_t)((nblocks + 63) / 64);
-    if (cum[kStaticEntries - 1] >= (1u << 17))
+    const uint32_t        grid = (uint32_t)((nblocks + 63) / 64);
+    const StaticDecKernel k    = pick_static_decode_kernel(p, cum[kStaticEntries - 1], nblocks);
+    if (k == StaticDecKernel::Fixup)
         k_decode_static<true><<<grid, 64, 0, s>>>(a);
     else {
         StaticLockArgs la;
@@ -1437,29 +1495,16 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
         la.d.table      = nullptr;
         la.rc           = a.rc;
         la.tab          = a.tab;
-        const bool solo = grid <= 4u * cu_count(); // at most one wave per SIMD: keep the dispatcher from doubling them up
-        if (cum[kStaticEntries - 1] <= 65536u) { // get_symbol by direct lookup
-            if (solo) {
-                if (p->code_bits == 32)
-                    k_decode_static_lut<true, 4><<<(grid + 3) / 4, 256, 0, s>>>(la);
-                else
-                    k_decode_static_lut<false, 4><<<(grid + 3) / 4, 256, 0, s>>>(la);
-            } else {
-                if (p->code_bits == 32)
-                    k_decode_static_lut<true, 8><<<(grid + 7) / 8, 512, 0, s>>>(la);
-                else
-                    k_decode_static_lut<false, 8><<<(grid + 7) / 8, 512, 0, s>>>(la);
-            }
-        } else if (p->code_bits == 32) {
-            if (solo)
-                k_decode_static_lock<true, true><<<grid, 64, 0, s>>>(la);
-            else
-                k_decode_static_lock<true, false><<<grid, 64, 0, s>>>(la);
-        } else {
-            if (solo)
-                k_decode_static_lock<false, true><<<grid, 64, 0, s>>>(la);
-            else
-                k_decode_static_lock<false, false><<<grid, 64, 0, s>>>(la);
+        switch (k) { // solo: at most one wave per SIMD, to keep the dispatcher from doubling them up
+        case StaticDecKernel::LutCb32Solo: k_decode_static_lut<true, 4><<<(grid + 3) / 4, 256, 0, s>>>(la); break;
+        case StaticDecKernel::LutSolo: k_decode_static_lut<false, 4><<<(grid + 3) / 4, 256, 0, s>>>(la); break;
+        case StaticDecKernel::LutCb32: k_decode_static_lut<true, 8><<<(grid + 7) / 8, 512, 0, s>>>(la); break;
+        case StaticDecKernel::Lut: k_decode_static_lut<false, 8><<<(grid + 7) / 8, 512, 0, s>>>(la); break;
+        case StaticDecKernel::LockCb32Solo: k_decode_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
+        case StaticDecKernel::LockCb32: k_decode_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
+        case StaticDecKernel::LockSolo: k_decode_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
+        case StaticDecKernel::Lock: k_decode_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
+        case StaticDecKernel::Fixup: break;
         }
     }
     if (d_summary)
