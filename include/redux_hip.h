@@ -281,6 +281,47 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
                                    uint64_t out_cap, void *d_out_sizes, void *d_block_status, void *d_summary,
                                    void *stream);
 
+/* ---- semi-static coding: the static table built from the data ---------------------------------
+ * The rule that turns byte counts c[0..255] into cum[0..=257] for a target total T.  The host function, the device kernel
+ * and every binding agree on it bit for bit:
+ *   - 257 <= T <= freq_max (else INVALID_INPUT); N = sum c; R = T - 257.  N R >= 2^64, or N >= 2^64, is
+ *     UNSUPPORTED (at T = 2^16: inputs of 256 TiB or more).  Parameters the static coder does not take
+ *     (symbol_bits != 8, code_bits > 32) return what redux_static_table_check returns for them.
+ *   - EOF (symbol 256) always has frequency 1.  N = 0: every frequency is 1 and the total is 257.
+ *   - Otherwise f[s] = 1 + floor(c[s] R / N) with remainder r[s] = c[s] R mod N; D = T - sum f (EOF included) lies in
+ *     [0, 255], and the D bytes with the largest r[s] get one more (equal remainders: the lower symbol first).  Then
+ *     sum f = T exactly.  cum[0] = 0, cum[i+1] = cum[i] + f[i].
+ * Callers above the C ABI default to T = min(2^16, freq_max): such a table decodes on the lookup decoder.
+ *
+ * redux_static_table_from_counts  the rule on the host; needs no GPU.
+ * redux_histogram_workspace_bytes workspace redux_histogram_dev needs for in_len bytes: 0 = none (pass NULL, 0).
+ * redux_histogram_dev             ADDS the byte counts of d_in[0 .. in_len) (any length, any alignment) to d_counts, u64[256]
+ *                                 on the device, stream-ordered: a buffer can be counted in pieces.  Zero the counts first.
+ * redux_static_table_dev          the rule on the device: one workgroup reads d_counts (u64[256]) and writes d_cum
+ *                                 (u32[258]), stream-ordered.  The parameter and total checks are made before the launch;
+ *                                 N R >= 2^64 cannot be seen then, and the kernel writes a table of zeros instead, which
+ *                                 redux_static_table_check rejects.
+ * redux_static_table              host pointers: counts `in` on the CURRENT device (chunks staged through the host
+ *                                 pipeline's pinned ring; redux_host_set_devices is ignored by this call), applies the rule
+ *                                 and returns cum in host memory.
+ * redux_static_encode_blocks      redux_encode_blocks / redux_decode_blocks under the table cum, through the same chunk
+ * redux_static_decode_blocks      pipeline (fleet included).  Block b's stream is that of redux_static_encode_blocks_dev; the
+ *                                 streams depend on neither the chunk size nor the devices.  No byte-plane form: each plane
+ *                                 would need its own table. */
+int      redux_static_table_from_counts(const redux_params *p, const uint64_t *counts, uint32_t total, uint32_t *cum);
+uint64_t redux_histogram_workspace_bytes(uint64_t in_len);
+int      redux_histogram_dev(const void *d_in, uint64_t in_len, void *d_counts /* u64[256], ADDED to */, void *d_workspace,
+                             uint64_t workspace_bytes, void *stream);
+int      redux_static_table_dev(const redux_params *p, const void *d_counts, uint32_t total, void *d_cum /* u32[258] */,
+                                void *stream);
+int      redux_static_table(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t total, uint32_t *cum);
+int      redux_static_encode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                    uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                    int32_t *block_status);
+int      redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in,
+                                    const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
+                                    uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status);
+
 /* ---- byte-plane layout of typed data ("shuffle" filter) ----------------------------------------
  * An order-0 byte model sees the bytes of bf16 / fp32 / int64 data interleaved: the skewed exponent byte is mixed with
  * mantissa bytes that are close to uniform.  These calls put a byte transform in front of the coder that makes each BLOCK

@@ -107,8 +107,36 @@ class AdaptiveTreeModel:
         return self.params
 
 
+class StaticModel:
+    """The static-table model (include/redux_hip.h, "static-table model"): Parameters plus a fixed table cum[0..=257].
+    StaticModel.from_data builds the table from the data by the rule of "semi-static coding".  compress_blocks and
+    decompress_blocks take it where they take Parameters."""
+
+    def __init__(self, params, cum):
+        self.params = _params_of(params)
+        c = np.ascontiguousarray(cum, dtype=np.int64)
+        if c.shape != (258,) or (c < 0).any() or (c > 0xFFFFFFFF).any():
+            raise InvalidInput()
+        self.cum = c.astype(np.uint32)
+        cp = self.params._c()
+        _raise(_lib.lib().redux_static_table_check(C.byref(cp), self.cum.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    @classmethod
+    def from_data(cls, data, params=(8, 30, 32), total=None):
+        return cls(params, static_table(data, params, total))
+
+    def parameters(self):
+        return self.params
+
+    def total(self):
+        return int(self.cum[-1])
+
+    def _cum_ptr(self):
+        return self.cum.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 def _params_of(model_or_params):
-    if isinstance(model_or_params, AdaptiveTreeModel):
+    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel)):
         return model_or_params.params
     if isinstance(model_or_params, Parameters):
         return model_or_params
@@ -134,6 +162,67 @@ def _ptr(a):
     return a.ctypes.data if a.size else None
 
 
+# ---- semi-static coding: the static table built from the data ------------------------------
+def default_total(params):
+    """The table total used when none is given: min(2^16, freq_max), so the table decodes on the lookup decoder."""
+    return min(1 << 16, _params_of(params).freq_max)
+
+
+def _total_of(params, total):
+    T = default_total(params) if total is None else total
+    if not isinstance(T, (int, np.integer)) or not 0 <= T < 1 << 32:
+        raise InvalidInput()
+    return int(T)
+
+
+def static_table_from_counts(counts, params=(8, 30, 32), total=None):
+    """redux_static_table_from_counts: the rule (include/redux_hip.h, "semi-static coding") on u64[256] counts, on the
+    host.  Returns np.uint32[258]."""
+    P = _params_of(params)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.shape != (256,):
+        raise InvalidInput()
+    cum = np.zeros(258, dtype=np.uint32)
+    cp = P._c()
+    _raise(_lib.lib().redux_static_table_from_counts(C.byref(cp), c.ctypes.data, _total_of(P, total), cum.ctypes.data))
+    return cum
+
+
+def static_table(data, params=(8, 30, 32), total=None):
+    """The static table of `data`: np.uint32[258].  Host data (bytes-like, numpy) goes through redux_static_table; a torch
+    uint8 device tensor is counted where it lies (redux_histogram_dev + redux_static_table_dev, one read-back)."""
+    P = _params_of(params)
+    T = _total_of(P, total)
+    cp = P._c()
+    L = _lib.lib()
+    if not _is_device_tensor(data):
+        a = _u8(data)
+        cum = np.zeros(258, dtype=np.uint32)
+        _raise(L.redux_static_table(C.byref(cp), _ptr(a), len(a), T, cum.ctypes.data))
+        return cum
+    torch = _torch()
+    assert data.dtype == torch.uint8 and data.is_contiguous()
+    with torch.cuda.device(data.device):
+        counts = torch.zeros(256, dtype=torch.int64, device=data.device)
+        d_cum = torch.zeros(258, dtype=torch.int32, device=data.device)
+        s = _stream_ptr(torch)
+        _raise(L.redux_histogram_dev(C.c_void_p(data.data_ptr()) if data.numel() else None, data.numel(),
+                                     C.c_void_p(counts.data_ptr()), None, 0, s))
+        _raise(L.redux_static_table_dev(C.byref(cp), C.c_void_p(counts.data_ptr()), T, C.c_void_p(d_cum.data_ptr()), s))
+        cum = d_cum.cpu().numpy().view(np.uint32).copy()
+    if not cum.any():  # the kernel's mark for N * R >= 2^64
+        raise Unsupported()
+    return cum
+
+
+def _is_device_tensor(x):
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
 # ---- block API, host buffers ------------------------------------------------------------
 def _check_element_size(element_size):
     """1 (no layout), 2, 4 or 8; anything else is InvalidInput (redux_planes_check)."""
@@ -147,7 +236,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
-    layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes."""
+    layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
+    params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks); no element_size."""
+    if isinstance(params, StaticModel):
+        return _compress_blocks_static(data, block_size, params, element_size)
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
@@ -171,12 +263,53 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
     return out[: int(offs[-1])], offs, status
 
 
+def _compress_blocks_static(data, block_size, model, element_size):
+    if _check_element_size(element_size) != 1:
+        raise InvalidInput()  # (each byte plane would need its own table)
+    a = _u8(data)
+    L = _lib.lib()
+    cp = model.params._c()
+    if block_size <= 0:
+        raise InvalidInput()
+    nb = L.redux_block_count(len(a), block_size)
+    cap = L.redux_static_encode_bound(C.byref(cp), len(a), block_size)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    offs = np.zeros(nb + 1, dtype=np.uint64)
+    status = np.zeros(nb, dtype=np.int32)
+    _raise(L.redux_static_encode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data, cap,
+                                        offs.ctypes.data, status.ctypes.data))
+    return out[: int(offs[-1])], offs, status
+
+
+def _decompress_blocks_static(streams, offsets, block_size, model, check, element_size, length):
+    if _check_element_size(element_size) != 1 or length is not None:
+        raise InvalidInput()
+    a = _u8(streams)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nb = len(offs) - 1
+    if nb < 0 or block_size <= 0 or int(offs[-1]) > len(a) or bool((offs[1:] < offs[:-1]).any()):
+        raise InvalidInput()
+    L = _lib.lib()
+    cp = model.params._c()
+    out = np.empty(nb * block_size, dtype=np.uint8)
+    sizes = np.zeros(nb, dtype=np.uint32)
+    status = np.zeros(nb, dtype=np.int32)
+    st = L.redux_static_decode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
+                                      out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data)
+    if check:
+        _raise(st)
+    return out, sizes, status
+
+
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
     required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
-    (frames with a damaged block hold undefined bytes; their blocks' status says which)."""
+    (frames with a damaged block hold undefined bytes; their blocks' status says which).
+    params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks)."""
+    if isinstance(params, StaticModel):
+        return _decompress_blocks_static(streams, offsets, block_size, params, check, element_size, length)
     E = _check_element_size(element_size)
     if E > 1 and length is None:
         raise InvalidInput()
@@ -557,6 +690,11 @@ class DeviceStaticCoder:
         self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
         self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
         self.dec_out = None
+
+    @classmethod
+    def from_data(cls, d_in, params, block_size, max_in_len, total=None):
+        """A coder whose table is built from d_in (a uint8 device tensor) on the device (static_table)."""
+        return cls(params, static_table(d_in, params, total), block_size, max_in_len, device=d_in.device)
 
     @_on_device
     def encode(self, d_in):

@@ -1,6 +1,7 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
+                            [--model adaptive|static]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -10,22 +11,26 @@ parallel and wraps them in the container of redux_amd/container.py.  All coding 
 GPU: there is no CPU path.  `--element-size 2|4|8` (with a block size) codes typed data -- bf16 / fp16, fp32 / int32,
 fp64 / int64 -- in the byte-plane layout (container version 2); decoding reads the element size from the container.
 A raw reference stream has no place to record it: `--element-size` above 1 with `--block-size 0` is a usage error.
+`--model static` (with a block size, element size 1) builds one static frequency table from the whole input and codes
+every block under it (container version 3, which records the table); `--model adaptive`, the default, is the
+reference's model.  Decoding reads the model from the container.
 """
 import io
 import sys
 
-USAGE = "Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>]"
+USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
+         "[--model <adaptive|static>]")
 
 
 def parse(argv):
-    opts = {"compress": None, "input": None, "output": None, "block_size": 0}  # (+ "element_size" when given)
+    opts = {"compress": None, "input": None, "output": None, "block_size": 0}  # (+ "element_size", "model" when given)
     it = iter(argv)
     for arg in it:
         if arg == "-c":
             opts["compress"] = True
         elif arg == "-d":
             opts["compress"] = False
-        elif arg in ("-i", "-o", "--block-size", "--element-size"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model"):
             val = next(it, None)
             if val is None:
                 return None
@@ -37,6 +42,10 @@ def parse(argv):
                 if val not in ("1", "2", "4", "8"):
                     return None
                 opts["element_size"] = int(val)
+            elif arg == "--model":
+                if val not in ("adaptive", "static"):
+                    return None
+                opts["model"] = val
             else:
                 try:
                     opts["block_size"] = int(val)
@@ -48,6 +57,8 @@ def parse(argv):
             return None
     if opts.get("element_size", 1) > 1 and opts["block_size"] == 0:
         return None  # a raw reference stream has no place to record the element size
+    if opts.get("model") == "static" and (opts["block_size"] == 0 or opts.get("element_size", 1) != 1):
+        return None  # the table lives in the container (not in a raw stream), and there is one table, not one per plane
     return None if opts["compress"] is None else opts
 
 
@@ -76,7 +87,8 @@ def main(argv=None):
                 i_n, o_n = api.compress(io.BytesIO(data), o, api.AdaptiveTreeModel.new(params))
                 sink.write(o.getvalue())
             else:
-                blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1))
+                blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
+                                                opts.get("model", "adaptive"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -6,18 +6,23 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 
 Layout (little-endian):
     0   4  magic  b"RDXB"
-    4   1  version (1; 2 = byte-plane layout)
+    4   1  version (1; 2 = byte-plane layout; 3 = static-table model)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
-   12   4  version 1: reserved (0); version 2: element size E, one of 2, 4, 8
+   12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
-   32  4*nblocks   compressed size of each block
+   (version 3 only) 4*258  the static table cum[0..=257], u32
+   ..  4*nblocks   compressed size of each block
    ..  payloads, concatenated in block order
 
 Version 2 is the same layout for data coded with the byte-plane layout of typed data (include/redux_hip.h): the payloads
 are the streams of the transformed bytes, and decoding undoes the layout.  Element size 1 (no layout) writes version 1,
 byte for byte what this module wrote before version 2 existed.
+
+Version 3 holds streams of the static-table model (include/redux_hip.h, "static-table model" and "semi-static coding"):
+the header is followed by the table the blocks were coded under, and decoding uses it.  A table that
+redux_static_table_check rejects is InvalidInput, a truncated one Eof.
 """
 import struct
 
@@ -28,6 +33,8 @@ from . import api
 MAGIC = b"RDXB"
 VERSION = 1
 VERSION_PLANES = 2
+VERSION_STATIC = 3
+TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
 ELEMENT_SIZES = (2, 4, 8)  # what version 2 may record
 HEADER = struct.Struct("<4sBBBBIIQQ")
 # A header field, not a promise: a crafted 40-byte file must not make the decoder allocate
@@ -38,17 +45,26 @@ MAX_BLOCK_SIZE = 1 << 30
 
 def pack(streams, offsets, params, block_size, total_len, element_size=1):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
-    byte-plane layout (version 2)."""
+    byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1)."""
     if element_size != 1 and element_size not in ELEMENT_SIZES:
+        raise api.InvalidInput()
+    static = isinstance(params, api.StaticModel)
+    if static and element_size != 1:
         raise api.InvalidInput()
     P = api._params_of(params)
     offs = np.asarray(offsets, dtype=np.uint64)
     sizes = np.diff(offs.astype(np.int64))
     if (sizes < 0).any() or (sizes > 0xFFFFFFFF).any():
         raise api.InvalidInput()
-    ver, res = (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
+    ver, res = (VERSION_STATIC, 0) if static else (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
+    if static:
+        head += params.cum.astype("<u4").tobytes()
     return head + sizes.astype("<u4").tobytes() + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
+
+
+def _version_ok(ver, res):
+    return (ver in (VERSION, VERSION_STATIC) and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)
 
 
 def unpack(buf):
@@ -58,17 +74,19 @@ def unpack(buf):
     if len(b) < HEADER.size:
         raise api.Eof()
     magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or ver not in (VERSION, VERSION_PLANES) or block_size == 0 or block_size > MAX_BLOCK_SIZE:
-        raise api.InvalidInput()
-    if ver == VERSION_PLANES and res not in ELEMENT_SIZES:
+    if magic != MAGIC or not _version_ok(ver, res) or block_size == 0 or block_size > MAX_BLOCK_SIZE:
         raise api.InvalidInput()
     P = api.Parameters(sb, fb, cb)
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
-    end_sizes = HEADER.size + 4 * nblocks
+    start = HEADER.size
+    if ver == VERSION_STATIC:
+        _table(b, P)
+        start += TABLE
+    end_sizes = start + 4 * nblocks
     if len(b) < end_sizes:
         raise api.Eof()
-    sizes = np.frombuffer(b, dtype="<u4", count=nblocks, offset=HEADER.size).astype(np.uint64)
+    sizes = np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint64)
     offsets = np.zeros(nblocks + 1, dtype=np.uint64)
     offsets[1:] = np.cumsum(sizes)
     if len(b) < end_sizes + int(offsets[-1]):
@@ -84,9 +102,34 @@ def element_size(buf):
     if len(b) < HEADER.size:
         raise api.Eof()
     magic, ver, _sb, _fb, _cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or ver not in (VERSION, VERSION_PLANES) or (ver == VERSION_PLANES and res not in ELEMENT_SIZES):
+    if magic != MAGIC or not _version_ok(ver, res):
         raise api.InvalidInput()
-    return 1 if ver == VERSION else res
+    return res if ver == VERSION_PLANES else 1
+
+
+def _table(b, P):
+    """the version 3 table after the header of b, checked against P"""
+    if len(b) < HEADER.size + TABLE:
+        raise api.Eof()
+    cum = np.frombuffer(b, dtype="<u4", count=258, offset=HEADER.size).astype(np.uint32)
+    try:
+        return api.StaticModel(P, cum).cum
+    except api.Error:  # (redux_static_table_check: a bad table, or parameters the static coder does not take)
+        raise api.InvalidInput()
+
+
+def static_table(buf):
+    """The static table (np.uint32[258]) a version 3 container records; None for versions 1 and 2.  Malformed headers
+    or tables raise InvalidInput, truncated ones Eof."""
+    b = memoryview(buf)
+    if len(b) < HEADER.size:
+        raise api.Eof()
+    magic, ver, sb, fb, cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
+    if magic != MAGIC or not _version_ok(ver, res):
+        raise api.InvalidInput()
+    if ver != VERSION_STATIC:
+        return None
+    return _table(b, api.Parameters(sb, fb, cb))
 
 
 def header_is_wellformed(buf):
@@ -101,7 +144,7 @@ def header_is_wellformed(buf):
     magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
     if magic != MAGIC or not 0 < block_size <= MAX_BLOCK_SIZE:
         return False
-    if not ((ver == VERSION and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)):
+    if not _version_ok(ver, res):
         return False
     try:
         api.Parameters.new(sb, fb, cb)
@@ -110,10 +153,16 @@ def header_is_wellformed(buf):
     return nblocks == (1 if total == 0 else (total + block_size - 1) // block_size)
 
 
-def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1):
-    """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2."""
-    if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES):
+def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive"):
+    """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
+    model "static": the static table of the data (api.static_table, default total) codes every block, version 3."""
+    if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
+            or model not in ("adaptive", "static") or (model == "static" and element_size != 1):
         raise api.InvalidInput()
+    if model == "static":
+        m = api.StaticModel.from_data(data, params)
+        out, offs, _ = api.compress_blocks(data, block_size, m)
+        return pack(out, offs, m, block_size, len(data))
     if element_size == 1:
         out, offs, _ = api.compress_blocks(data, block_size, params)
     else:
@@ -131,6 +180,8 @@ def decompress_bytes(buf):
     if len(payload) < nb:
         raise api.InvalidInput()
     E = element_size(buf)
+    cum = static_table(buf)
+    model = P if cum is None else api.StaticModel(P, cum)
     if E > 1:  # (frames are E * block_size bytes: the blocks decode at their real size, into out[0 .. total))
         try:
             out, sizes, _ = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total)
@@ -142,7 +193,7 @@ def decompress_bytes(buf):
         return out.tobytes()
     cap = max(1, min(block_size, total))  # one short block never needs block_size bytes of capacity
     try:
-        out, sizes, _ = api.decompress_blocks(payload, offsets, cap, P)
+        out, sizes, _ = api.decompress_blocks(payload, offsets, cap, model)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
         raise api.InvalidInput()
     expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]

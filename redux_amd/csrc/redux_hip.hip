@@ -12,6 +12,7 @@
 //   redux_synth.hpp    k_gen_iid / k_gen_zipf
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
+//   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -30,6 +31,7 @@
 #include "redux_synth.hpp"
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
+#include "redux_hist.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -1511,6 +1513,154 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
         k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
+}
+
+// ---- semi-static coding (redux_hist.hpp) ------------------------------------------------------------
+// the parameter and total checks of the rule: what static_check says about the parameters, then 257 <= total <= freq_max
+static int static_total_check(const redux_params *p, uint32_t total)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p))
+        return REDUX_UNSUPPORTED;
+    if (total < kStaticEntries - 1 || (uint64_t)total > (1ull << p->freq_bits) - 1)
+        return REDUX_INVALID_INPUT;
+    return REDUX_OK;
+}
+
+int redux_static_table_from_counts(const redux_params *p, const uint64_t *counts, uint32_t total, uint32_t *cum)
+{
+    int st = static_total_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!counts || !cum)
+        return REDUX_INVALID_INPUT;
+    unsigned __int128 n128 = 0;
+    for (int s = 0; s < 256; s++)
+        n128 += counts[s];
+    const uint64_t N = (uint64_t)n128, R = total - 257ull;
+    if ((n128 >> 64) || (unsigned __int128)N * R >> 64)
+        return REDUX_UNSUPPORTED;
+    uint32_t f[257];
+    uint64_t r[256];
+    uint64_t sum = 1; // EOF
+    for (int s = 0; s < 256; s++) {
+        f[s] = 1;
+        r[s] = 0;
+        if (N) {
+            const uint64_t cr = counts[s] * R;
+            f[s] += (uint32_t)(cr / N);
+            r[s] = cr % N;
+        }
+        sum += f[s];
+    }
+    f[256] = 1;
+    if (N) {
+        const uint64_t D = total - sum; // in [0, 255]
+        for (int s = 0; s < 256; s++) {
+            uint64_t rank = 0;
+            for (int j = 0; j < 256; j++)
+                rank += (r[j] > r[s] || (r[j] == r[s] && j < s)) ? 1 : 0;
+            if (rank < D)
+                f[s]++;
+        }
+    }
+    cum[0] = 0;
+    for (int s = 0; s < 257; s++)
+        cum[s + 1] = cum[s] + f[s];
+    return REDUX_OK;
+}
+
+uint64_t redux_histogram_workspace_bytes(uint64_t in_len)
+{
+    (void)in_len; // (k_byte_hist keeps everything in LDS and registers)
+    return 0;
+}
+
+int redux_histogram_dev(const void *d_in, uint64_t in_len, void *d_counts, void *d_workspace, uint64_t workspace_bytes,
+                        void *stream)
+{
+    (void)d_workspace;
+    (void)workspace_bytes;
+    if (!d_counts || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    if (in_len == 0)
+        return REDUX_OK;
+    HistArgs a;
+    a.in     = (const uint8_t *)d_in;
+    a.counts = (unsigned long long *)d_counts;
+    const uint64_t lead = (16 - ((uintptr_t)d_in & 15)) & 15;
+    if (lead >= in_len) {
+        a.head = in_len;
+        a.nvec = 0;
+        a.tail = 0;
+    } else {
+        a.head = lead;
+        a.nvec = (in_len - lead) / 16;
+        a.tail = in_len - lead - a.nvec * 16;
+    }
+    const uint64_t rows = (a.nvec + 63) / 64, per = rows / kHistUnroll; // (rows per workgroup-step)
+    const uint64_t cap  = (uint64_t)kHistWgsPerCu * cu_count();
+    const uint32_t grid = (uint32_t)(per < 1 ? 1 : per < cap ? per : cap);
+    k_byte_hist<<<grid, 64, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_static_table_dev(const redux_params *p, const void *d_counts, uint32_t total, void *d_cum, void *stream)
+{
+    int st = static_total_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_counts || !d_cum)
+        return REDUX_INVALID_INPUT;
+    k_static_table<<<1, 256, 0, (hipStream_t)stream>>>((const unsigned long long *)d_counts, total, (uint32_t *)d_cum);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_static_table(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t total, uint32_t *cum)
+{
+    int st = static_total_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!cum || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    uint64_t counts[256];
+    if ((st = host::byte_histogram(in, in_len, counts)) != REDUX_OK) // redux_host.hpp
+        return st;
+    return redux_static_table_from_counts(p, counts, total, cum);
+}
+
+int redux_static_encode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                               uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    int st = static_check(p, cum);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(p, in, in_len, block_size, out, out_cap, out_offsets, block_status, 1, cum); // redux_host.hpp
+}
+
+int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
+                               uint64_t nblocks, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
+                               int32_t *block_status)
+{
+    int st = static_check(p, cum);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !in_offsets || !out_sizes || (nblocks && !out))
+        return REDUX_INVALID_INPUT;
+    if (nblocks == 0)
+        return REDUX_OK;
+    if (out_cap < nblocks * (uint64_t)block_size)
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (in_offsets[nblocks] && !in)
+        return REDUX_INVALID_INPUT;
+    return host::decode_blocks(p, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr,
+                               decode_blocks_dev_impl, 0, 0, cum); // redux_host.hpp
 }
 
 // ---- byte-plane layout (redux_planes.hpp) ---------------------------------------------------------

@@ -149,6 +149,7 @@ struct Ctx {
     Slot        slot[kSlots];
     void       *piece[kPieces] = {};      // input staging ring
     hipEvent_t  piece_free[kPieces] = {};
+    Buf         d_counts;   // u64[256]: byte_histogram
     uint64_t    allocs = 0; // hipMalloc / hipHostMalloc calls so far (redux_host_allocations)
     // timeline of the last call, seconds since its start: per chunk {staging begins, device work enqueued,
     // kernels done (drain thread saw the event), results in caller memory}; trace[0..3] of chunk 0 etc.
@@ -262,6 +263,7 @@ static void ctx_teardown_locked(Ctx &c)
         if (s.done) (void)hipEventDestroy(s.done);
         s.done = nullptr;
     }
+    free_buf_dev(c.d_counts);
     for (int i = 0; i < kPieces; i++) {
         if (c.piece[i]) (void)hipHostFree(c.piece[i]);
         if (c.piece_free[i]) (void)hipEventDestroy(c.piece_free[i]);
@@ -464,6 +466,7 @@ struct EncCall {
     uint64_t           *out_offsets;
     int32_t            *block_status;
     uint32_t            element_size; // > 1: the byte-plane layout in front of the coder (redux_encode_planes_dev)
+    const uint32_t     *cum;          // not null: the static-table model (redux_static_encode_blocks_dev)
     uint64_t            nblocks, cb, nchunks, ws_bytes, bound, chunk_in;
 };
 
@@ -582,7 +585,9 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
                 HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
                 uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
                 // (a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64)
-                r = E.element_size > 1 ? redux_encode_planes_dev(E.p, s.d_in.p, len, E.block_size, E.element_size, s.d_out.p, E.bound,
+                r = E.cum               ? redux_static_encode_blocks_dev(E.p, E.cum, s.d_in.p, len, E.block_size, s.d_out.p, E.bound,
+                                                                         s.d_off.p, s.d_st.p, s.d_sum.p, ws, E.ws_bytes, st)
+                    : E.element_size > 1 ? redux_encode_planes_dev(E.p, s.d_in.p, len, E.block_size, E.element_size, s.d_out.p, E.bound,
                                                                  s.d_off.p, s.d_st.p, s.d_sum.p, ws, E.ws_bytes, st)
                                        : redux_encode_blocks_dev(E.p, s.d_in.p, len, E.block_size, s.d_out.p, E.bound, s.d_off.p, s.d_st.p,
                                                                  s.d_sum.p, ws, E.ws_bytes, st);
@@ -620,7 +625,8 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
 }
 
 static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out,
-                         uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t element_size = 1)
+                         uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t element_size = 1,
+                         const uint32_t *cum = nullptr)
 {
     std::vector<Ctx *> ctx;
     std::vector<std::unique_lock<std::mutex>> locks;
@@ -632,7 +638,7 @@ static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_l
 
     EncCall E;
     E.p = p; E.in = in; E.in_len = in_len; E.block_size = block_size; E.out = out; E.out_cap = out_cap;
-    E.out_offsets = out_offsets; E.block_status = block_status; E.element_size = element_size;
+    E.out_offsets = out_offsets; E.block_status = block_status; E.element_size = element_size; E.cum = cum;
     E.nblocks  = redux_block_count(in_len, block_size);
     E.cb       = chunk_blocks_for(E.nblocks, block_size, kEncChunkMax, ctx.size());
     E.nchunks  = (E.nblocks + E.cb - 1) / E.cb;
@@ -643,6 +649,10 @@ static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_l
     if (element_size > 1) // the transformed copy of a chunk goes in front (redux_encode_planes_dev)
         E.ws_bytes += planes_copy_bytes(E.chunk_in < in_len ? E.chunk_in : in_len);
     E.bound    = redux_encode_bound(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
+    if (cum) { // the static coder: its own workspace and bound for the largest chunk (its streams do not depend on either)
+        E.ws_bytes = redux_static_encode_workspace_bytes(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
+        E.bound    = redux_static_encode_bound(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
+    }
     Job J;
     J.total.assign(E.nchunks, 0);
     J.known.assign(E.nchunks, 0);
@@ -686,6 +696,7 @@ struct DecCall {
     DecodeDevCall       dev_call;
     uint32_t            element_size; // > 0: redux_decode_planes_dev, whose output is out[0 .. out_len) exactly
     uint64_t            out_len;
+    const uint32_t     *cum;          // not null: the static-table model (redux_static_decode_blocks_dev, no workspace)
     uint64_t            cb, nchunks, wsb, max_in;
 
     uint64_t chunk_out(uint64_t b0, uint64_t nb) const // bytes a chunk's blocks write into out
@@ -799,7 +810,9 @@ static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint
                     return r;
                 HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
                 uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-                r = D.element_size ? redux_decode_planes_dev(D.p, s.d_in.p, s.d_off.p, D.chunk_out(b0, nb), D.block_size, D.element_size,
+                r = D.cum          ? redux_static_decode_blocks_dev(D.p, D.cum, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p,
+                                                                    nb * (uint64_t)D.block_size, s.d_sz.p, s.d_st.p, s.d_sum.p, st)
+                  : D.element_size ? redux_decode_planes_dev(D.p, s.d_in.p, s.d_off.p, D.chunk_out(b0, nb), D.block_size, D.element_size,
                                                              s.d_out.p, s.d_sz.p, s.d_st.p, s.d_sum.p, ws, D.wsb, st)
                                    : D.dev_call(D.p, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p, nb * (uint64_t)D.block_size, s.d_sz.p,
                                                 s.d_st.p, s.d_sum.p, ws, D.wsb, st, D.in_used ? s.d_used.p : nullptr, nullptr, false, 0);
@@ -835,7 +848,8 @@ static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint
 
 static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
                          uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
-                         uint64_t *in_used, DecodeDevCall dev_call, uint32_t element_size = 0, uint64_t out_len = 0)
+                         uint64_t *in_used, DecodeDevCall dev_call, uint32_t element_size = 0, uint64_t out_len = 0,
+                         const uint32_t *cum = nullptr)
 {
     (void)out_cap;
     std::vector<Ctx *> ctx;
@@ -849,10 +863,11 @@ static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_
     DecCall D;
     D.p = p; D.in = in; D.in_offsets = in_offsets; D.nblocks = nblocks; D.block_size = block_size; D.out = out;
     D.out_sizes = out_sizes; D.block_status = block_status; D.in_used = in_used; D.dev_call = dev_call;
-    D.element_size = element_size; D.out_len = out_len;
+    D.element_size = element_size; D.out_len = out_len; D.cum = cum;
     D.cb      = chunk_blocks_for(nblocks, block_size, kDecChunkMax, ctx.size());
     D.nchunks = (nblocks + D.cb - 1) / D.cb;
-    D.wsb     = element_size ? redux_decode_planes_workspace_bytes(p, D.cb * (uint64_t)block_size, block_size, element_size)
+    D.wsb     = cum ? 0
+              : element_size ? redux_decode_planes_workspace_bytes(p, D.cb * (uint64_t)block_size, block_size, element_size)
                              : redux_decode_workspace_bytes(p, D.cb, block_size);
     D.max_in  = 0;
     for (uint64_t k = 0; k < D.nchunks; k++) {
@@ -880,6 +895,61 @@ static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_
     if (J.error != REDUX_OK)
         return J.error;
     return J.bad_status;
+}
+
+// ================================================================================================
+// byte histogram of host memory (redux_static_table)
+//
+// The input is staged chunk by chunk through the pinned ring into the slots of the CURRENT device's context (the fleet of
+// redux_host_set_devices is not used: the result is 2 KiB, there is nothing to spread), and k_byte_hist of each chunk adds
+// into one u64[256] on the device.  Chunk j runs on stream j % kStreams and slot j % kSlots, so the staging of a chunk
+// into a slot is ordered after the kernel that read the slot's previous chunk.  One read-back at the end.
+// ================================================================================================
+static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
+{
+    Ctx *cp  = nullptr;
+    int  dev = 0;
+    int  rc  = ctx_of_current_device(&cp, &dev);
+    if (rc != REDUX_OK)
+        return rc;
+    Ctx                        &c = *cp;
+    std::lock_guard<std::mutex> l(c.mu);
+    c.want = dev;
+    if ((rc = ctx_init_locked(c)) != REDUX_OK)
+        return rc;
+    const uint64_t lo = g_chunk_min.load() ? g_chunk_min.load() : kChunkMin;
+    const uint64_t hi = g_chunk_max.load() ? g_chunk_max.load() : kEncChunkMax;
+    uint64_t chunk = (in_len + kSlots - 1) / kSlots;
+    chunk = chunk < lo ? lo : chunk > hi ? hi : chunk;
+    chunk = (chunk + 65535) / 65536 * 65536; // (whole 64 KiB: the test hook's 1-byte chunks become 64 KiB)
+    const uint64_t nchunks = (in_len + chunk - 1) / chunk;
+    const int      nslots  = (int)(nchunks < (uint64_t)kSlots ? nchunks : (uint64_t)kSlots);
+    if ((rc = grow_dev(c, c.d_counts, 256 * 8)) != REDUX_OK)
+        return rc;
+    for (int i = 0; i < nslots; i++)
+        if ((rc = grow_dev(c, c.slot[i].d_in, chunk + 16)) != REDUX_OK)
+            return rc;
+    HOST_TRY(hipMemsetAsync(c.d_counts.p, 0, 256 * 8, c.stream[0]));
+    HOST_TRY(hipStreamSynchronize(c.stream[0])); // (the other streams do not wait for stream 0)
+    {
+        CopyPool pool(kCopyThreads - 1);
+        uint64_t piece_no = 0;
+        for (uint64_t j = 0; j < nchunks && rc == REDUX_OK; j++) {
+            const uint64_t o = j * chunk, n = in_len - o < chunk ? in_len - o : chunk;
+            hipStream_t    st = c.stream[j % kStreams];
+            void          *d  = c.slot[j % kSlots].d_in.p;
+            rc = stage_h2d(c, pool, piece_no, d, in + o, n, st);
+            if (rc == REDUX_OK)
+                rc = redux_histogram_dev(d, n, c.d_counts.p, nullptr, 0, st);
+        }
+    }
+    for (int i = 0; i < kStreams; i++) // nothing of this call stays in flight
+        if (hipStreamSynchronize(c.stream[i]) != hipSuccess && rc == REDUX_OK)
+            rc = REDUX_IO_ERROR;
+    if (rc == REDUX_OK && hipMemcpy(counts, c.d_counts.p, 256 * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = REDUX_IO_ERROR;
+    ctx_trim_locked(c);
+    return rc;
 }
 
 // ================================================================================================

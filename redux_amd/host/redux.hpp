@@ -13,6 +13,7 @@
 //   redux::hip::compress_blocks / decompress_blocks         the block API the GPU path adds
 //   redux::hip::compress_blocks_v / decompress_blocks_v     many independent inputs in one launch (tests/corpora.rs:32-85)
 //   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
+//   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
 //
 // Every stream byte is produced by the gfx950 kernels; there is no CPU coder in this header.
 #pragma once
@@ -193,6 +194,64 @@ inline std::vector<std::uint8_t> decompress_blocks_planes(const Blocks &streams,
     check(redux_decode_blocks_planes(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
                                      sizes.data(), nullptr));
     out.resize(len);
+    return out;
+}
+
+// Semi-static coding (include/redux_hip.h): the static table of `in` by the documented rule, total 0 = the default
+// min(2^16, freq_max); the table is cum[0..=257].
+inline std::vector<std::uint32_t> static_table(const std::uint8_t *in, std::uint64_t len, const model::Parameters &p,
+                                               std::uint32_t total = 0)
+{
+    const redux_params cp = p.c_abi();
+    if (total == 0) {
+        const std::uint64_t fmax = (1ull << p.freq_bits) - 1;
+        total = (std::uint32_t)(fmax < 65536 ? fmax : 65536);
+    }
+    std::vector<std::uint32_t> cum(258);
+    check(redux_static_table(&cp, in, len, total, cum.data()));
+    return cum;
+}
+
+// every block coded under the fixed table cum
+inline Blocks compress_blocks_static(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size,
+                                     const model::Parameters &p, const std::vector<std::uint32_t> &cum)
+{
+    const redux_params cp = p.c_abi();
+    if (cum.size() != 258)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    check(redux_static_table_check(&cp, cum.data()));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_static_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_static_encode_blocks(&cp, cum.data(), in, len, block_size, b.data.data(), b.data.size(), b.offsets.data(), nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: block b of the result is data[b*block_size .. b*block_size + sizes[b])
+inline std::vector<std::uint8_t> decompress_blocks_static(const Blocks &streams, std::uint32_t block_size, const model::Parameters &p,
+                                                          const std::vector<std::uint32_t> &cum,
+                                                          std::vector<std::uint32_t> *sizes = nullptr)
+{
+    const redux_params cp = p.c_abi();
+    if (cum.size() != 258)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    check(redux_static_table_check(&cp, cum.data()));
+    if (streams.offsets.empty() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    const std::uint64_t        nb = streams.offsets.size() - 1;
+    std::vector<std::uint8_t>  out(nb * (std::uint64_t)block_size);
+    std::vector<std::uint32_t> sz(nb);
+    check(redux_static_decode_blocks(&cp, cum.data(), streams.data.data(), streams.offsets.data(), nb, block_size, out.data(),
+                                     out.size(), sz.data(), nullptr));
+    if (sizes)
+        *sizes = sz;
     return out;
 }
 

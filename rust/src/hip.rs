@@ -57,6 +57,15 @@ extern "C" {
     fn redux_decode_blocks_planes(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                   block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
                                   block_status: *mut i32) -> c_int;
+    fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
+    fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
+    fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
+    fn redux_static_table(p: *const ReduxParams, input: *const u8, in_len: u64, total: u32, cum: *mut u32) -> c_int;
+    fn redux_static_encode_blocks(p: *const ReduxParams, cum: *const u32, input: *const u8, in_len: u64, block_size: u32,
+                                  out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32) -> c_int;
+    fn redux_static_decode_blocks(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
+                                  nblocks: u64, block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32,
+                                  block_status: *mut i32) -> c_int;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
@@ -181,6 +190,69 @@ pub fn decompress_blocks_planes(streams: &[u8], offsets: &[u64], len: u64, block
                                                out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
+    }
+}
+
+/// The table total used when none is given: `min(2^16, freq_max)`, which keeps the table on the lookup decoder.
+pub fn default_static_total(p: &Parameters) -> u32 {
+    std::cmp::min(1u64 << 16, (1u64 << p.freq_bits) - 1) as u32
+}
+
+/// Semi-static coding (include/redux_hip.h): the static table `cum[0..=257]` of 256 byte counts by the documented rule,
+/// computed on the host (no GPU).
+pub fn static_table_from_counts(counts: &[u64; 256], total: u32, p: &Parameters) -> Result<Vec<u32>> {
+    let cp = c_params(p);
+    let mut cum = vec![0u32; 258];
+    unsafe {
+        try!(status(redux_static_table_from_counts(&cp, counts.as_ptr(), total, cum.as_mut_ptr())));
+    }
+    Ok(cum)
+}
+
+/// The static table of `data`: its bytes are counted on the current GPU, then the rule is applied.
+pub fn static_table(data: &[u8], total: u32, p: &Parameters) -> Result<Vec<u32>> {
+    let cp = c_params(p);
+    let mut cum = vec![0u32; 258];
+    unsafe {
+        try!(status(redux_static_table(&cp, data.as_ptr(), data.len() as u64, total, cum.as_mut_ptr())));
+    }
+    Ok(cum)
+}
+
+/// `compress_blocks` under the fixed table `cum` (258 entries, e.g. from `static_table`) instead of the adaptive model.
+pub fn compress_blocks_static(data: &[u8], block_size: u32, cum: &[u32], p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 || cum.len() != 258 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_static_table_check(&cp, cum.as_ptr())));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_static_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_static_encode_blocks(&cp, cum.as_ptr(), data.as_ptr(), data.len() as u64, block_size,
+                                               out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_static`: block `b` of the result is `out[b * block_size..][..sizes[b]]`.
+pub fn decompress_blocks_static(streams: &[u8], offsets: &[u64], block_size: u32, cum: &[u32],
+                                p: &Parameters) -> Result<(Vec<u8>, Vec<u32>)> {
+    if block_size == 0 || cum.len() != 258 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    let nb = offsets.len() - 1;
+    unsafe {
+        try!(status(redux_static_table_check(&cp, cum.as_ptr())));
+        let mut out = vec![0u8; nb * block_size as usize];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_static_decode_blocks(&cp, cum.as_ptr(), streams.as_ptr(), offsets.as_ptr(), nb as u64, block_size,
+                                               out.as_mut_ptr(), out.len() as u64, sizes.as_mut_ptr(), ptr::null_mut())));
+        Ok((out, sizes))
     }
 }
 
