@@ -445,6 +445,48 @@ static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, ui
 
 using namespace redux;
 
+// ---- the encoders of the chunked host calls (redux_host.hpp: EncodeCoder) --------------------------------------------
+static host::EncodeCoder adaptive_encoder(const redux_params *p, uint32_t block_size)
+{
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                // several chunks in flight keep the chip busy: no pairs area, so the chunks run on the pair kernel (encode_slots_impl)
+                ws    = several ? geometry(p, max_in, block_size, false, false).total : redux_encode_workspace_bytes(p, max_in, block_size);
+                bound = redux_encode_bound(p, max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_encode_blocks_dev(p, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p, s.d_sum.p, ws,
+                                               ws_bytes, st);
+            }};
+}
+
+// the transformed copy of a chunk goes in front of the adaptive coder's workspace (redux_encode_planes_dev); a chunk is whole
+// 64-block waves, so whole frames of the layout for every element size that divides 64
+static host::EncodeCoder planes_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                plain.size(max_in, several, ws, bound);
+                ws += planes_copy_bytes(max_in);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_encode_planes_dev(p, s.d_in.p, len, block_size, element_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                               s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
+// the static coder: its own workspace and bound for the largest chunk (its streams do not depend on either)
+static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
+{
+    return {[=](uint64_t max_in, bool, uint64_t &ws, uint64_t &bound) {
+                ws    = redux_static_encode_workspace_bytes(p, max_in, block_size);
+                bound = redux_static_encode_bound(p, max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_static_encode_blocks_dev(p, cum, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                                      s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
 // the byte-plane layout (redux_planes.hpp): the fast kernel over the full frames when it applies, the byte kernel for the rest
 template <int E>
 static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
@@ -959,7 +1001,7 @@ int redux_encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_le
         return st;
     if (block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    return host::encode_blocks(p, in, in_len, block_size, out, out_cap, out_offsets, block_status); // redux_host.hpp
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, adaptive_encoder(p, block_size)); // redux_host.hpp
 }
 
 int redux_compress(const redux_params *p, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
@@ -1245,34 +1287,64 @@ int redux_decode_blocks_v(const redux_params *p, const uint8_t *in, const uint64
         return REDUX_INVALID_INPUT;
     if (is_any(p))
         return REDUX_UNSUPPORTED;
-    return host::decode_blocks_v(p, in, in_offsets, out, out_off, out_len, ninputs, block_size, out_sizes, block_status,
-                                 decode_blocks_dev_impl);
+    return host::decode_blocks_v(p, in, in_offsets, out, out_off, out_len, ninputs, block_size, out_sizes, block_status);
 }
 
-static int decode_blocks_host(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
-                              uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
-                              int32_t *block_status, uint64_t *in_used)
+// the decoders of the chunked host calls (redux_host.hpp: DecodeCoder)
+static host::DecodeCoder adaptive_decoder(const redux_params *p, uint32_t block_size)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (block_size == 0 || !in_offsets || !out_sizes || (nblocks && !out))
+    return {[=](uint64_t cb) { return redux_decode_workspace_bytes(p, cb, block_size); },
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *d_in_used, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return decode_blocks_dev_impl(p, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes, s.d_sz.p, s.d_st.p,
+                                              s.d_sum.p, ws, ws_bytes, st, d_in_used);
+            }};
+}
+
+// decodes exactly the chunk's share of out_len (redux_decode_planes_dev)
+static host::DecodeCoder planes_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    return {[=](uint64_t cb) { return redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_decode_planes_dev(p, s.d_in.p, s.d_off.p, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
+                                               s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
+// the static decoder takes no workspace
+static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
+{
+    return {[](uint64_t) { return (uint64_t)0; },
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *, uint64_t, hipStream_t st) {
+                return redux_static_decode_blocks_dev(p, cum, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes, s.d_sz.p,
+                                                      s.d_st.p, s.d_sum.p, st);
+            }};
+}
+
+// The host-pointer decoders: `params` is the status of the entry's own parameter checks, then the checks they share.  The
+// blocks decode to out_len bytes (nblocks * block_size, or exactly out_len in the planes layout) in out[0 .. out_cap).
+static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
+                              uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
+                              uint64_t *in_used, const host::DecodeCoder &coder)
+{
+    if (params != REDUX_OK)
+        return params;
+    if (block_size == 0 || !in_offsets || !out_sizes || (out_len && !out))
         return REDUX_INVALID_INPUT;
     if (nblocks == 0)
         return REDUX_OK;
-    if (out_cap < nblocks * (uint64_t)block_size)
+    if (out_cap < out_len)
         return REDUX_OUTPUT_TOO_SMALL;
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
-    return host::decode_blocks(p, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, in_used,
-                               decode_blocks_dev_impl); // redux_host.hpp
+    return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder); // redux_host.hpp
 }
 
 int redux_decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
                         uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
                         int32_t *block_status)
 {
-    return decode_blocks_host(p, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr);
+    return decode_blocks_host(check_params(p), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
+                              out_sizes, block_status, nullptr, adaptive_decoder(p, block_size));
 }
 
 int redux_decompress(const redux_params *p, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
@@ -1284,7 +1356,8 @@ int redux_decompress(const redux_params *p, const uint8_t *in, uint64_t in_len, 
     uint32_t  sz      = 0;
     int32_t   st      = 0;
     uint64_t  used    = 0;
-    const int rc = decode_blocks_host(p, in, offs, 1, (uint32_t)out_cap, out, out_cap, &sz, &st, &used);
+    const int rc = decode_blocks_host(check_params(p), in, offs, 1, (uint32_t)out_cap, out, out_cap, out_cap, &sz, &st, &used,
+                                      adaptive_decoder(p, (uint32_t)out_cap));
     if (rc == REDUX_OK) {
         if (bytes_out)
             *bytes_out = sz;
@@ -1641,26 +1714,15 @@ int redux_static_encode_blocks(const redux_params *p, const uint32_t *cum, const
         return st;
     if (block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    return host::encode_blocks(p, in, in_len, block_size, out, out_cap, out_offsets, block_status, 1, cum); // redux_host.hpp
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, static_encoder(p, cum, block_size)); // redux_host.hpp
 }
 
 int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
                                uint64_t nblocks, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
                                int32_t *block_status)
 {
-    int st = static_check(p, cum);
-    if (st != REDUX_OK)
-        return st;
-    if (block_size == 0 || !in_offsets || !out_sizes || (nblocks && !out))
-        return REDUX_INVALID_INPUT;
-    if (nblocks == 0)
-        return REDUX_OK;
-    if (out_cap < nblocks * (uint64_t)block_size)
-        return REDUX_OUTPUT_TOO_SMALL;
-    if (in_offsets[nblocks] && !in)
-        return REDUX_INVALID_INPUT;
-    return host::decode_blocks(p, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr,
-                               decode_blocks_dev_impl, 0, 0, cum); // redux_host.hpp
+    return decode_blocks_host(static_check(p, cum), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
+                              out_sizes, block_status, nullptr, static_decoder(p, cum, block_size));
 }
 
 // ---- byte-plane layout (redux_planes.hpp) ---------------------------------------------------------
@@ -1767,22 +1829,18 @@ int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_
         return st;
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    return host::encode_blocks(p, in, in_len, block_size, out, out_cap, out_offsets, block_status, element_size); // redux_host.hpp
+    const host::EncodeCoder coder = element_size > 1 ? planes_encoder(p, block_size, element_size) : adaptive_encoder(p, block_size);
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder); // redux_host.hpp
 }
 
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
 {
     int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !in_offsets || !out_sizes || (out_len && !out))
-        return REDUX_INVALID_INPUT;
-    const uint64_t nblocks = redux_block_count(out_len, block_size);
-    if (in_offsets[nblocks] && !in)
-        return REDUX_INVALID_INPUT;
-    return host::decode_blocks(p, in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, nullptr,
-                               decode_blocks_dev_impl, element_size, out_len); // redux_host.hpp
+    if (st == REDUX_OK && redux_planes_check(element_size) != REDUX_OK)
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, planes_decoder(p, block_size, element_size));
 }
 
 int redux_host_release(void) { return host::ctx_release_all(); }
@@ -1826,8 +1884,8 @@ uint64_t redux_host_resident_bytes(void)
         if (!c.ready)
             continue;
         for (host::Slot &s : c.slot)
-            for (const host::Buf *b : {&s.d_in, &s.d_ws, &s.d_out, &s.d_off, &s.d_sz, &s.d_st, &s.d_sum, &s.d_used, &s.d_tab})
-                n += b->cap;
+            for (const host::Buf *b : s.bufs())
+                n += b->pinned ? 0 : b->cap;
     }
     return n;
 }

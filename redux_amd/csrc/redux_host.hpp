@@ -23,20 +23,26 @@
 //     chunk k+8.  Nothing that depends on a running kernel is ever put into a copy queue: the SDMA
 //     queues are in order, and a 16 KiB result copy waiting for its kernel blocks every copy behind it.
 //
-// Included by redux_hip.hip (one translation unit) after the _dev entry points it drives.
+// Included by redux_hip.hip (one translation unit), whose ABI entry points choose the coder a call runs (EncodeCoder,
+// DecodeCoder).
 #pragma once
 
 #include "../../include/redux_hip.h"
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
+#include <initializer_list>
 #include <mutex>
+#include <optional>
 #include <stdint.h>
 #include <string.h>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace redux {
@@ -127,14 +133,20 @@ public:
 
 // ---- persistent per-device context -----------------------------------------------------------
 struct Buf {
-    void  *p = nullptr;
-    size_t cap = 0;
+    bool   pinned = false; // hipHostMalloc'd (a pinned mirror of a device array), else hipMalloc'd
+    void  *p      = nullptr;
+    size_t cap    = 0;
 };
 
 struct Slot {          // one chunk in flight
-    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab; // device
-    Buf h_off, h_sz, h_st, h_sum, h_used, h_tab;                    // pinned mirrors of the small arrays
-    hipEvent_t done = nullptr;                               // recorded after the chunk's kernels and small D2H copies
+    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab;                  // device
+    Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}; // pinned mirrors of the small arrays
+    hipEvent_t done = nullptr;                                                       // recorded after the chunk's kernels
+
+    std::array<Buf *, 15> bufs()
+    {
+        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab};
+    }
 };
 
 struct Ctx {
@@ -174,31 +186,35 @@ static Ctx g_ctx[16];
         }                                                                                              \
     } while (0)
 
-static int grow_dev(Ctx &c, Buf &b, size_t need)
+static void free_buf(Buf &b)
+{
+    if (b.p)
+        (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
+    b.p = nullptr; b.cap = 0;
+}
+
+static int grow_buf(Ctx &c, Buf &b, size_t need)
 {
     if (b.cap >= need)
         return REDUX_OK;
     if (b.p)
-        HOST_TRY(hipFree(b.p));
+        HOST_TRY(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
     b.p = nullptr; b.cap = 0;
     const size_t cap = (need + need / 8 + 4095) & ~(size_t)4095;
-    HOST_TRY(hipMalloc(&b.p, cap));
+    HOST_TRY(b.pinned ? hipHostMalloc(&b.p, cap, hipHostMallocDefault) : hipMalloc(&b.p, cap));
     c.allocs++;
     b.cap = cap;
     return REDUX_OK;
 }
 
-static int grow_pinned(Ctx &c, Buf &b, size_t need)
+// every (buffer, bytes) pair in turn; the first failure ends it
+static int grow_bufs(Ctx &c, std::initializer_list<std::pair<Buf *, uint64_t>> need)
 {
-    if (b.cap >= need)
-        return REDUX_OK;
-    if (b.p)
-        HOST_TRY(hipHostFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    const size_t cap = (need + need / 8 + 4095) & ~(size_t)4095;
-    HOST_TRY(hipHostMalloc(&b.p, cap, hipHostMallocDefault));
-    c.allocs++;
-    b.cap = cap;
+    for (const auto &n : need) {
+        const int rc = grow_buf(c, *n.first, n.second);
+        if (rc != REDUX_OK)
+            return rc;
+    }
     return REDUX_OK;
 }
 
@@ -244,9 +260,6 @@ static int ctx_init_locked(Ctx &c)
     return REDUX_OK;
 }
 
-static void free_buf_dev(Buf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-static void free_buf_pin(Buf &b) { if (b.p) (void)hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
-
 // frees everything the context holds on the device it was built for (c.mu is held)
 static void ctx_teardown_locked(Ctx &c)
 {
@@ -256,14 +269,12 @@ static void ctx_teardown_locked(Ctx &c)
     for (int i = 0; i < kStreams; i++) // (a call in flight holds c.mu, so these are idle: belt and braces)
         if (c.stream[i]) (void)hipStreamSynchronize(c.stream[i]);
     for (Slot &s : c.slot) {
-        free_buf_dev(s.d_in); free_buf_dev(s.d_ws); free_buf_dev(s.d_out); free_buf_dev(s.d_off); free_buf_dev(s.d_sz);
-        free_buf_dev(s.d_st); free_buf_dev(s.d_sum); free_buf_dev(s.d_used); free_buf_dev(s.d_tab);
-        free_buf_pin(s.h_off); free_buf_pin(s.h_sz); free_buf_pin(s.h_st); free_buf_pin(s.h_sum); free_buf_pin(s.h_used);
-        free_buf_pin(s.h_tab);
+        for (Buf *b : s.bufs())
+            free_buf(*b);
         if (s.done) (void)hipEventDestroy(s.done);
         s.done = nullptr;
     }
-    free_buf_dev(c.d_counts);
+    free_buf(c.d_counts);
     for (int i = 0; i < kPieces; i++) {
         if (c.piece[i]) (void)hipHostFree(c.piece[i]);
         if (c.piece_free[i]) (void)hipEventDestroy(c.piece_free[i]);
@@ -289,33 +300,28 @@ static void ctx_trim_locked(Ctx &c)
     for (Slot &s : c.slot)
         for (Buf *b : {&s.d_in, &s.d_ws, &s.d_out})
             if (b->cap > kTrimBytes)
-                free_buf_dev(*b);
+                free_buf(*b);
 }
+
+struct CallerDevice { // HIP's current device when the scope began, made current again when it ends
+    int d = -1;
+    CallerDevice() { (void)hipGetDevice(&d); }
+    ~CallerDevice()
+    {
+        if (d >= 0)
+            (void)hipSetDevice(d);
+    }
+};
 
 static int ctx_release_all()
 {
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev); // restored below: freeing another device's context must not move the caller
-    struct Restore {
-        int d;
-        ~Restore() { if (d >= 0) (void)hipSetDevice(d); }
-    } restore{caller_dev};
+    CallerDevice caller; // freeing another device's context must not move the caller
     for (Ctx &c : g_ctx) {
         std::lock_guard<std::mutex> lc(c.mu); // waits for a call in flight on that device
         ctx_teardown_locked(c);
     }
     return REDUX_OK;
 }
-
-// ---- hand-over between the issuing thread and the drain thread -----------------------------------
-struct Handover {
-    std::mutex              m;
-    std::condition_variable cv;
-    uint64_t                issued = 0;  // chunks whose device work has been enqueued
-    uint64_t                drained = 0; // chunks whose results are in the caller's memory
-    int                     error = REDUX_OK;
-    bool                    abort = false;
-};
 
 // stage `len` host bytes into the slot's device input at byte offset 0, through the pinned ring, on `s`
 static int stage_h2d(Ctx &c, CopyPool &pool, uint64_t &piece_no, void *d_dst, const uint8_t *src, uint64_t len, hipStream_t s)
@@ -409,32 +415,40 @@ static int set_devices(const int32_t *ids, uint32_t n)
     return REDUX_OK;
 }
 
+// `bytes` within [kChunkMin, chunk_max], or within the test hook's bounds where it sets them
+static uint64_t clamp_chunk_bytes(uint64_t bytes, uint64_t chunk_max)
+{
+    const uint64_t lo = g_chunk_min.load() ? g_chunk_min.load() : kChunkMin;
+    const uint64_t hi = g_chunk_max.load() ? g_chunk_max.load() : chunk_max;
+    return bytes < lo ? lo : bytes > hi ? hi : bytes;
+}
+
 // blocks per chunk: whole 64-block waves; an eighth of a context's share of the call (eight chunks in flight per
 // context), within [kChunkMin, chunk_max] bytes of payload
 static uint64_t chunk_blocks_for(uint64_t nblocks, uint32_t block_size, uint64_t chunk_max, size_t nctx)
 {
-    const uint64_t lo = g_chunk_min.load() ? g_chunk_min.load() : kChunkMin;
-    const uint64_t hi = g_chunk_max.load() ? g_chunk_max.load() : chunk_max;
-    uint64_t bytes = (nblocks * (uint64_t)block_size + kSlots * nctx - 1) / (kSlots * nctx);
-    bytes = bytes < lo ? lo : bytes > hi ? hi : bytes;
+    const uint64_t bytes = clamp_chunk_bytes((nblocks * (uint64_t)block_size + kSlots * nctx - 1) / (kSlots * nctx), chunk_max);
     uint64_t cb = (bytes + block_size - 1) / block_size;
     cb = (cb + 63) / 64 * 64;
     return cb < nblocks ? cb : nblocks;
 }
 
-// what the contexts of one call share
-struct Job {
+// ---- what the contexts of one call share ---------------------------------------------------------
+// A call's units are its chunks (redux_encode_blocks ...) or its groups of inputs (the `_v` calls), in block order.  The
+// ledger keeps the call's first error, the first unit with a non-OK block, and -- encode -- where each unit's streams go in
+// the dense output: known once every earlier unit's size is, whichever context coded it.
+struct Ledger {
     std::mutex              m;
     std::condition_variable cv;
     bool                    abort = false;
     int                     error = REDUX_OK;
-    uint64_t                bad_chunk = ~0ull; // first chunk (in block order) with a non-OK block, and that status
+    uint64_t                bad_unit = ~0ull; // first unit (in block order) with a non-OK block, and that status
     int                     bad_status = REDUX_OK;
-    // encode only: where a chunk's streams go in the dense output is known once every earlier chunk's size is
-    std::vector<uint64_t> total, prefix; // prefix[k] = sum of total[0..k): valid for k <= prefix_n
-    std::vector<char>     known;
-    uint64_t              prefix_n = 0;
+    std::vector<uint64_t>   size, prefix; // prefix[k] = sum of size[0..k): valid for k <= prefix_n
+    std::vector<char>       known;
+    uint64_t                prefix_n = 0;
 
+    explicit Ledger(uint64_t nunits) : size(nunits, 0), prefix(nunits + 1, 0), known(nunits, 0) {}
     void fail(int rc)
     {
         std::lock_guard<std::mutex> l(m);
@@ -443,114 +457,148 @@ struct Job {
         abort = true;
         cv.notify_all();
     }
-    void note_bad(uint64_t chunk, int st)
+    bool aborted()
     {
         std::lock_guard<std::mutex> l(m);
-        if (chunk < bad_chunk) {
-            bad_chunk  = chunk;
+        return abort;
+    }
+    void publish(uint64_t k, uint64_t bytes)
+    {
+        std::lock_guard<std::mutex> l(m);
+        size[k]  = bytes;
+        known[k] = 1;
+        while (prefix_n < size.size() && known[prefix_n]) {
+            prefix[prefix_n + 1] = prefix[prefix_n] + size[prefix_n];
+            prefix_n++;
+        }
+        cv.notify_all();
+    }
+    // bytes of all units before k, once they are all published; nothing if the call fails meanwhile
+    std::optional<uint64_t> base_of(uint64_t k)
+    {
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return abort || prefix_n >= k; });
+        if (abort)
+            return std::nullopt;
+        return prefix[k];
+    }
+    void note_bad(uint64_t k, int st)
+    {
+        std::lock_guard<std::mutex> l(m);
+        if (k < bad_unit) {
+            bad_unit   = k;
             bad_status = st;
         }
     }
+    int result() const { return error != REDUX_OK ? error : bad_status; }
 };
 
-// ================================================================================================
-// encode
-// ================================================================================================
-struct EncCall {
-    const redux_params *p;
-    const uint8_t      *in;
-    uint64_t            in_len;
-    uint32_t            block_size;
-    uint8_t            *out;
-    uint64_t            out_cap;
-    uint64_t           *out_offsets;
-    int32_t            *block_status;
-    uint32_t            element_size; // > 1: the byte-plane layout in front of the coder (redux_encode_planes_dev)
-    const uint32_t     *cum;          // not null: the static-table model (redux_static_encode_blocks_dev)
-    uint64_t            nblocks, cb, nchunks, ws_bytes, bound, chunk_in;
+// ---- one call over its contexts ------------------------------------------------------------------
+// Takes the call's contexts (take_contexts), sizes the call for their number -- plan(nctx, &nunits) -- and runs
+// work(ctx, ledger, first, stride) for the units first, first + stride, ... of each context: context 0 on the calling thread,
+// every other on a thread of its own.  Returns the call's error, or failing that the first non-OK unit status in block order.
+template <typename Plan, typename Work>
+static int run_fleet(Plan &&plan, Work &&work)
+{
+    std::vector<Ctx *> ctx;
+    std::vector<std::unique_lock<std::mutex>> locks;
+    int rc = take_contexts(ctx, locks);
+    if (rc != REDUX_OK)
+        return rc;
+    CallerDevice caller; // (every context makes its own device current on the thread that drives it)
+    uint64_t     nunits = 0;
+    if ((rc = plan(ctx.size(), nunits)) != REDUX_OK)
+        return rc;
+    Ledger L(nunits);
+    const uint64_t nctx = ctx.size() < nunits ? ctx.size() : nunits; // (a call of one unit uses one context)
+    std::vector<std::thread> th;
+    for (uint64_t d = 1; d < nctx; d++)
+        th.emplace_back([&, d] { work(*ctx[d], L, d, nctx); });
+    work(*ctx[0], L, 0, nctx);
+    for (auto &t : th)
+        t.join();
+    for (Ctx *c : ctx) {
+        if (c->ready)
+            (void)hipSetDevice(c->device);
+        ctx_trim_locked(*c);
+    }
+    return L.result();
+}
+
+// ---- the chunk pipeline of one context -----------------------------------------------------------
+// What became of a chunk's results: rc (REDUX_OK: in caller memory), or `aborted`: not placed because the call failed
+// elsewhere (its error is that failure's).
+struct Placed {
+    int  rc      = REDUX_OK;
+    bool aborted = false;
 };
 
-// the chunks first, first + stride, ... of the call on context c (the calling thread of the call holds c.mu)
-static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint64_t stride)
+// hand-over between the issuing thread and the drain thread of one context
+struct Handover {
+    std::mutex              m;
+    std::condition_variable cv;
+    uint64_t                issued = 0;  // chunks whose device work has been enqueued
+    uint64_t                drained = 0; // chunks whose results are in the caller's memory
+    bool                    abort = false;
+};
+
+static void *slot_ws(const Slot &s) { return (void *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255); }
+
+// a small result array -> its pinned mirror, on the chunk's stream
+static bool fetch_small(Buf &h, const Buf &d, uint64_t bytes, hipStream_t s)
+{
+    return hipMemcpyAsync(h.p, d.p, bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+}
+
+// The chunks first, first + stride, ... of the call on context c (the calling thread of the call holds c.mu).  What differs by
+// direction is the Op's (EncodeChunks, DecodeChunks): grow (what a slot holds), stage and launch (chunk k's H2D and kernels),
+// fetch (its small result arrays) and place (its results -> caller memory).
+template <typename Op>
+static void run_chunks_on_ctx(Ctx &c, const Op &op, Ledger &L, uint64_t first, uint64_t stride)
 {
     int rc = ctx_init_locked(c); // (makes c.want HIP's current device on this thread)
     if (rc != REDUX_OK)
-        return J.fail(rc);
-    const uint64_t mine = first < E.nchunks ? (E.nchunks - first + stride - 1) / stride : 0; // chunks of this context
-    const uint64_t first_len = E.chunk_in < E.in_len ? E.chunk_in : E.in_len;
+        return L.fail(rc);
+    const uint64_t mine   = first < op.nchunks ? (op.nchunks - first + stride - 1) / stride : 0; // chunks of this context
     const int      nslots = (int)(mine < (uint64_t)kSlots ? mine : (uint64_t)kSlots);
-    for (int i = 0; i < nslots; i++) {
-        Slot &s = c.slot[i];
-        if ((rc = grow_dev(c, s.d_in, first_len + 16)) || (rc = grow_dev(c, s.d_ws, E.ws_bytes + 256)) || (rc = grow_dev(c, s.d_out, E.bound + 16)) ||
-            (rc = grow_dev(c, s.d_off, (E.cb + 1) * 8)) || (rc = grow_dev(c, s.d_st, E.cb * 4)) || (rc = grow_dev(c, s.d_sum, 8)) ||
-            (rc = grow_pinned(c, s.h_off, (E.cb + 1) * 8)) || (rc = grow_pinned(c, s.h_st, E.cb * 4)) || (rc = grow_pinned(c, s.h_sum, 8)))
-            return J.fail(rc);
-    }
+    for (int i = 0; i < nslots; i++)
+        if ((rc = op.grow(c, c.slot[i])) != REDUX_OK)
+            return L.fail(rc);
     c.trace.assign(mine * 4, 0.0);
     c.t0 = now_s();
-    Handover H; // between this context's issuing thread and its drain thread; j = ordinal of a chunk within this context
+    Handover H; // j = ordinal of a chunk within this context: slot and stream j % 8
     // ---- drain thread: results of chunk k -> caller memory -------------------------------------
     std::thread drain([&] {
         (void)hipSetDevice(c.device);
         for (uint64_t j = 0; j < mine; j++) {
-            const uint64_t k = first + j * stride;
             {
                 std::unique_lock<std::mutex> l(H.m);
                 H.cv.wait(l, [&] { return H.issued > j || H.abort; });
                 if (H.abort)
                     return;
             }
+            const uint64_t k = first + j * stride, b0 = k * op.cb, nb = (b0 + op.cb <= op.nblocks ? op.cb : op.nblocks - b0);
             Slot          &s  = c.slot[j % kSlots];
-            const uint64_t b0 = k * E.cb, nb = (b0 + E.cb <= E.nblocks ? E.cb : E.nblocks - b0);
-            int            err = REDUX_OK;
-            hipStream_t st = c.stream[j % kStreams]; // idle once the chunk's event has fired
-            if (hipEventSynchronize(s.done) != hipSuccess ||
-                hipMemcpyAsync(s.h_off.p, s.d_off.p, (nb + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(s.h_st.p, s.d_st.p, nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(s.h_sum.p, s.d_sum.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                err = REDUX_IO_ERROR;
+            hipStream_t    st = c.stream[j % kStreams]; // idle once the chunk's event has fired
+            Placed         r;
+            if (hipEventSynchronize(s.done) != hipSuccess || !op.fetch(s, st, nb) || hipStreamSynchronize(st) != hipSuccess)
+                r.rc = REDUX_IO_ERROR;
             c.trace[j * 4 + 2] = now_s() - c.t0;
-            const uint64_t *ho    = (const uint64_t *)s.h_off.p;
-            const uint64_t  total = err ? 0 : ho[nb];
-            uint64_t        base  = 0;
-            if (!err) {
+            if (r.rc == REDUX_OK) {
                 if (((const int32_t *)s.h_sum.p)[0] != REDUX_OK)
-                    J.note_bad(k, ((const int32_t *)s.h_sum.p)[0]);
-                // publish this chunk's size, then wait for the sizes of all earlier chunks (other contexts' included)
-                std::unique_lock<std::mutex> l(J.m);
-                J.total[k] = total;
-                J.known[k] = 1;
-                while (J.prefix_n < E.nchunks && J.known[J.prefix_n]) {
-                    J.prefix[J.prefix_n + 1] = J.prefix[J.prefix_n] + J.total[J.prefix_n];
-                    J.prefix_n++;
-                }
-                J.cv.notify_all();
-                J.cv.wait(l, [&] { return J.abort || J.prefix_n >= k; });
-                if (J.abort)
-                    err = -1; // (another context failed: its error is the call's)
-                else
-                    base = J.prefix[k];
-            }
-            if (!err && base + total > E.out_cap)
-                err = REDUX_OUTPUT_TOO_SMALL;
-            if (!err && total)
-                err = drain_d2h(c, E.out + base, s.d_out.p, total);
-            if (!err) {
-                for (uint64_t i = 0; i <= nb; i++)
-                    E.out_offsets[b0 + i] = base + ho[i]; // (entry b0 + nb is written again, with the same value, by the next chunk)
-                if (E.block_status)
-                    memcpy(E.block_status + b0, s.h_st.p, nb * 4);
+                    L.note_bad(k, ((const int32_t *)s.h_sum.p)[0]);
+                r = op.place(c, s, k, b0, nb, L);
             }
             c.trace[j * 4 + 3] = now_s() - c.t0;
-            if (err > 0)
-                J.fail(err);
+            if (r.rc != REDUX_OK)
+                L.fail(r.rc);
+            const bool stop = r.rc != REDUX_OK || r.aborted;
             std::lock_guard<std::mutex> l(H.m);
             H.drained = j + 1;
-            if (err)
+            if (stop)
                 H.abort = true;
             H.cv.notify_all();
-            if (err)
+            if (stop)
                 return;
         }
     });
@@ -560,38 +608,24 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
         CopyPool pool(kCopyThreads - 1);
         uint64_t piece_no = 0;
         for (uint64_t j = 0; j < mine; j++) {
-            const uint64_t k = first + j * stride;
             {
                 std::unique_lock<std::mutex> l(H.m); // the slot's previous chunk must be in the caller's memory
                 H.cv.wait(l, [&] { return H.abort || j < (uint64_t)kSlots || H.drained + kSlots > j; });
                 if (H.abort)
                     break;
             }
-            {
-                std::lock_guard<std::mutex> l(J.m);
-                if (J.abort)
-                    break;
-            }
+            if (L.aborted())
+                break;
             c.trace[j * 4 + 0] = now_s() - c.t0;
+            const uint64_t k = first + j * stride, b0 = k * op.cb, nb = (b0 + op.cb <= op.nblocks ? op.cb : op.nblocks - b0);
             Slot          &s  = c.slot[j % kSlots];
             hipStream_t    st = c.stream[j % kStreams];
-            const uint64_t b0 = k * E.cb, nb = (b0 + E.cb <= E.nblocks ? E.cb : E.nblocks - b0);
-            const uint64_t o0 = b0 * (uint64_t)E.block_size;
-            const uint64_t len = (o0 + nb * (uint64_t)E.block_size <= E.in_len) ? nb * (uint64_t)E.block_size : E.in_len - o0;
             auto issue = [&]() -> int {
-                int r = stage_h2d(c, pool, piece_no, s.d_in.p, E.in + o0, len, st);
+                int r = op.stage(c, s, st, b0, nb, pool, piece_no);
                 if (r != REDUX_OK)
                     return r;
                 HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
-                uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-                // (a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64)
-                r = E.cum               ? redux_static_encode_blocks_dev(E.p, E.cum, s.d_in.p, len, E.block_size, s.d_out.p, E.bound,
-                                                                         s.d_off.p, s.d_st.p, s.d_sum.p, ws, E.ws_bytes, st)
-                    : E.element_size > 1 ? redux_encode_planes_dev(E.p, s.d_in.p, len, E.block_size, E.element_size, s.d_out.p, E.bound,
-                                                                 s.d_off.p, s.d_st.p, s.d_sum.p, ws, E.ws_bytes, st)
-                                       : redux_encode_blocks_dev(E.p, s.d_in.p, len, E.block_size, s.d_out.p, E.bound, s.d_off.p, s.d_st.p,
-                                                                 s.d_sum.p, ws, E.ws_bytes, st);
-                if (r != REDUX_OK)
+                if ((r = op.launch(s, st, b0, nb)) != REDUX_OK)
                     return r;
                 // (the small result arrays are fetched by the drain thread once the event has fired: a D2H
                 // enqueued here would sit in the in-order SDMA queue until this chunk's kernels end, with
@@ -602,7 +636,7 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
             rc = issue();
             c.trace[j * 4 + 1] = now_s() - c.t0;
             if (rc != REDUX_OK)
-                J.fail(rc);
+                L.fail(rc);
             std::lock_guard<std::mutex> l(H.m);
             if (rc != REDUX_OK)
                 H.abort = true;
@@ -624,281 +658,192 @@ static void encode_on_ctx(Ctx &c, const EncCall &E, Job &J, uint64_t first, uint
         (void)hipStreamSynchronize(c.stream[i]);
 }
 
-static int encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out,
-                         uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t element_size = 1,
-                         const uint32_t *cum = nullptr)
+template <typename Op>
+static int run_chunks(Op &op)
 {
-    std::vector<Ctx *> ctx;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    int rc = take_contexts(ctx, locks);
-    if (rc != REDUX_OK)
-        return rc;
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-
-    EncCall E;
-    E.p = p; E.in = in; E.in_len = in_len; E.block_size = block_size; E.out = out; E.out_cap = out_cap;
-    E.out_offsets = out_offsets; E.block_status = block_status; E.element_size = element_size; E.cum = cum;
-    E.nblocks  = redux_block_count(in_len, block_size);
-    E.cb       = chunk_blocks_for(E.nblocks, block_size, kEncChunkMax, ctx.size());
-    E.nchunks  = (E.nblocks + E.cb - 1) / E.cb;
-    E.chunk_in = E.cb * (uint64_t)block_size; // bytes of a full chunk
-    E.ws_bytes = redux_encode_workspace_bytes(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
-    if (E.nchunks > 1) // several chunks in flight keep the chip busy: no pairs area, so the chunks run on the pair kernel (encode_slots_impl)
-        E.ws_bytes = geometry(p, E.chunk_in, block_size, false, false).total;
-    if (element_size > 1) // the transformed copy of a chunk goes in front (redux_encode_planes_dev)
-        E.ws_bytes += planes_copy_bytes(E.chunk_in < in_len ? E.chunk_in : in_len);
-    E.bound    = redux_encode_bound(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
-    if (cum) { // the static coder: its own workspace and bound for the largest chunk (its streams do not depend on either)
-        E.ws_bytes = redux_static_encode_workspace_bytes(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
-        E.bound    = redux_static_encode_bound(p, E.chunk_in < in_len ? E.chunk_in : in_len, block_size);
-    }
-    Job J;
-    J.total.assign(E.nchunks, 0);
-    J.known.assign(E.nchunks, 0);
-    J.prefix.assign(E.nchunks + 1, 0);
-    const uint64_t nctx = ctx.size() < E.nchunks ? ctx.size() : E.nchunks; // (a call of one chunk uses one context)
-    std::vector<std::thread> th;
-    for (uint64_t d = 1; d < nctx; d++)
-        th.emplace_back([&, d] { encode_on_ctx(*ctx[d], E, J, d, nctx); });
-    encode_on_ctx(*ctx[0], E, J, 0, nctx);
-    for (auto &t : th)
-        t.join();
-    for (Ctx *c : ctx) {
-        if (c->ready)
-            (void)hipSetDevice(c->device);
-        ctx_trim_locked(*c);
-    }
-    if (caller_dev >= 0)
-        (void)hipSetDevice(caller_dev);
-    if (J.error != REDUX_OK)
-        return J.error;
-    return J.bad_status;
+    return run_fleet([&](size_t nctx, uint64_t &nunits) { return op.plan(nctx, nunits); },
+                     [&](Ctx &c, Ledger &L, uint64_t first, uint64_t stride) { run_chunks_on_ctx(c, op, L, first, stride); });
 }
 
-// ================================================================================================
-// decode
-// ================================================================================================
-// decode_blocks_dev_impl of redux_hip.hip (defined after this header is included)
-typedef int (*DecodeDevCall)(const redux_params *, const void *, const void *, uint64_t, uint32_t, void *, uint64_t, void *, void *,
-                             void *, void *, uint64_t, void *, void *, const redux_block *, bool, uint64_t);
+// ---- the coder of a chunked call ---------------------------------------------------------------
+// Chosen by the call's ABI entry point (redux_hip.hip): the workspace and stream room a chunk needs, and the launch of one
+// chunk's kernels on its stream, between the slot's buffers.
+struct EncodeCoder {
+    // workspace and stream-area bytes for chunks of at most max_in input bytes (`several`: the call has more than one chunk)
+    std::function<void(uint64_t max_in, bool several, uint64_t &ws_bytes, uint64_t &bound)> size;
+    // len bytes in s.d_in -> streams in s.d_out (room: bound), s.d_off, s.d_st, s.d_sum
+    std::function<int(Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st)> launch;
+};
 
-struct DecCall {
-    const redux_params *p;
-    const uint8_t      *in;
-    const uint64_t     *in_offsets;
-    uint64_t            nblocks;
-    uint32_t            block_size;
-    uint8_t            *out;
-    uint32_t           *out_sizes;
-    int32_t            *block_status;
-    uint64_t           *in_used;
-    DecodeDevCall       dev_call;
-    uint32_t            element_size; // > 0: redux_decode_planes_dev, whose output is out[0 .. out_len) exactly
-    uint64_t            out_len;
-    const uint32_t     *cum;          // not null: the static-table model (redux_static_decode_blocks_dev, no workspace)
-    uint64_t            cb, nchunks, wsb, max_in;
+struct DecodeCoder {
+    std::function<uint64_t(uint64_t cb)> workspace; // bytes for chunks of at most cb blocks
+    // nb streams in s.d_in (offsets s.d_off) -> out_bytes bytes in s.d_out, s.d_sz, s.d_st, s.d_sum; d_in_used may be null
+    std::function<int(Slot &s, uint64_t nb, uint64_t out_bytes, void *d_in_used, void *ws, uint64_t ws_bytes, hipStream_t st)> launch;
+};
 
-    uint64_t chunk_out(uint64_t b0, uint64_t nb) const // bytes a chunk's blocks write into out
+// ================================================================================================
+// encode: chunk k = blocks [k * cb, k * cb + nb) of the input -> its streams at their place in the dense output
+// ================================================================================================
+struct EncodeChunks {
+    const uint8_t     *in;
+    uint64_t           in_len;
+    uint32_t           block_size;
+    uint8_t           *out;
+    uint64_t           out_cap;
+    uint64_t          *out_offsets;
+    int32_t           *block_status;
+    const EncodeCoder &coder;
+    uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
+
+    int plan(size_t nctx, uint64_t &n)
     {
-        const uint64_t full = nb * (uint64_t)block_size, o = b0 * (uint64_t)block_size;
-        return element_size ? (out_len - o < full ? out_len - o : full) : full;
+        nblocks = redux_block_count(in_len, block_size);
+        cb      = chunk_blocks_for(nblocks, block_size, kEncChunkMax, nctx);
+        nchunks = n = (nblocks + cb - 1) / cb;
+        max_in  = cb * (uint64_t)block_size < in_len ? cb * (uint64_t)block_size : in_len; // bytes of the largest chunk
+        coder.size(max_in, nchunks > 1, ws_bytes, bound);
+        return REDUX_OK;
+    }
+    uint64_t len_of(uint64_t b0, uint64_t nb) const // input bytes of a chunk
+    {
+        const uint64_t o0 = b0 * (uint64_t)block_size;
+        return o0 + nb * (uint64_t)block_size <= in_len ? nb * (uint64_t)block_size : in_len - o0;
+    }
+    int grow(Ctx &c, Slot &s) const
+    {
+        return grow_bufs(c, {{&s.d_in, max_in + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (cb + 1) * 8},
+                             {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
+    }
+    int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
+    {
+        return stage_h2d(c, pool, piece_no, s.d_in.p, in + b0 * (uint64_t)block_size, len_of(b0, nb), st);
+    }
+    int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
+    {
+        return coder.launch(s, len_of(b0, nb), bound, slot_ws(s), ws_bytes, st);
+    }
+    bool fetch(Slot &s, hipStream_t st, uint64_t nb) const
+    {
+        return fetch_small(s.h_off, s.d_off, (nb + 1) * 8, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
+               fetch_small(s.h_sum, s.d_sum, 8, st);
+    }
+    Placed place(Ctx &c, Slot &s, uint64_t k, uint64_t b0, uint64_t nb, Ledger &L) const
+    {
+        const uint64_t *ho    = (const uint64_t *)s.h_off.p;
+        const uint64_t  total = ho[nb];
+        L.publish(k, total); // then wait for the sizes of all earlier chunks (other contexts' included)
+        const std::optional<uint64_t> base = L.base_of(k);
+        if (!base)
+            return {REDUX_OK, true};
+        if (*base + total > out_cap)
+            return {REDUX_OUTPUT_TOO_SMALL};
+        const int rc = total ? drain_d2h(c, out + *base, s.d_out.p, total) : REDUX_OK;
+        if (rc != REDUX_OK)
+            return {rc};
+        for (uint64_t i = 0; i <= nb; i++)
+            out_offsets[b0 + i] = *base + ho[i]; // (entry b0 + nb is written again, with the same value, by the next chunk)
+        if (block_status)
+            memcpy(block_status + b0, s.h_st.p, nb * 4);
+        return {};
     }
 };
 
-static void decode_on_ctx(Ctx &c, const DecCall &D, Job &J, uint64_t first, uint64_t stride)
+static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
+                         uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder)
 {
-    int rc = ctx_init_locked(c); // (makes c.want HIP's current device on this thread)
-    if (rc != REDUX_OK)
-        return J.fail(rc);
-    const uint64_t mine   = first < D.nchunks ? (D.nchunks - first + stride - 1) / stride : 0;
-    const int      nslots = (int)(mine < (uint64_t)kSlots ? mine : (uint64_t)kSlots);
-    for (int i = 0; i < nslots; i++) {
-        Slot &s = c.slot[i];
-        if ((rc = grow_dev(c, s.d_in, D.max_in + 32)) || (rc = grow_dev(c, s.d_ws, D.wsb + 256)) ||
-            (rc = grow_dev(c, s.d_out, D.cb * (uint64_t)D.block_size + 16)) || (rc = grow_dev(c, s.d_off, (D.cb + 1) * 8)) ||
-            (rc = grow_dev(c, s.d_sz, D.cb * 4)) || (rc = grow_dev(c, s.d_st, D.cb * 4)) || (rc = grow_dev(c, s.d_sum, 8)) ||
-            (rc = grow_dev(c, s.d_used, D.in_used ? D.cb * 8 : 8)) || (rc = grow_pinned(c, s.h_off, (D.cb + 1) * 8)) ||
-            (rc = grow_pinned(c, s.h_sz, D.cb * 4)) || (rc = grow_pinned(c, s.h_st, D.cb * 4)) || (rc = grow_pinned(c, s.h_sum, 8)) ||
-            (rc = grow_pinned(c, s.h_used, D.in_used ? D.cb * 8 : 8)))
-            return J.fail(rc);
-    }
-    c.trace.assign(mine * 4, 0.0);
-    c.t0 = now_s();
-    Handover H;
-    std::thread drain([&] {
-        (void)hipSetDevice(c.device);
-        for (uint64_t j = 0; j < mine; j++) {
-            const uint64_t k = first + j * stride;
-            {
-                std::unique_lock<std::mutex> l(H.m);
-                H.cv.wait(l, [&] { return H.issued > j || H.abort; });
-                if (H.abort)
-                    return;
-            }
-            Slot          &s  = c.slot[j % kSlots];
-            const uint64_t b0 = k * D.cb, nb = (b0 + D.cb <= D.nblocks ? D.cb : D.nblocks - b0);
-            int            err = REDUX_OK;
-            hipStream_t st = c.stream[j % kStreams];
-            if (hipEventSynchronize(s.done) != hipSuccess ||
-                hipMemcpyAsync(s.h_sz.p, s.d_sz.p, nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(s.h_st.p, s.d_st.p, nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(s.h_sum.p, s.d_sum.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                (D.in_used && hipMemcpyAsync(s.h_used.p, s.d_used.p, nb * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-                hipStreamSynchronize(st) != hipSuccess)
-                err = REDUX_IO_ERROR;
-            c.trace[j * 4 + 2] = now_s() - c.t0;
-            if (!err) {
-                if (((const int32_t *)s.h_sum.p)[0] != REDUX_OK)
-                    J.note_bad(k, ((const int32_t *)s.h_sum.p)[0]);
-                const uint64_t n = D.chunk_out(b0, nb);
-                err = n ? drain_d2h(c, D.out + b0 * (uint64_t)D.block_size, s.d_out.p, n) : REDUX_OK;
-            }
-            if (!err) {
-                memcpy(D.out_sizes + b0, s.h_sz.p, nb * 4);
-                if (D.block_status)
-                    memcpy(D.block_status + b0, s.h_st.p, nb * 4);
-                if (D.in_used)
-                    memcpy(D.in_used + b0, s.h_used.p, nb * 8);
-            }
-            c.trace[j * 4 + 3] = now_s() - c.t0;
-            if (err)
-                J.fail(err);
-            std::lock_guard<std::mutex> l(H.m);
-            H.drained = j + 1;
-            if (err)
-                H.abort = true;
-            H.cv.notify_all();
-            if (err)
-                return;
-        }
-    });
-
-    {
-        CopyPool pool(kCopyThreads - 1);
-        uint64_t piece_no = 0;
-        for (uint64_t j = 0; j < mine; j++) {
-            const uint64_t k = first + j * stride;
-            {
-                std::unique_lock<std::mutex> l(H.m);
-                H.cv.wait(l, [&] { return H.abort || j < (uint64_t)kSlots || H.drained + kSlots > j; });
-                if (H.abort)
-                    break;
-            }
-            {
-                std::lock_guard<std::mutex> l(J.m);
-                if (J.abort)
-                    break;
-            }
-            c.trace[j * 4 + 0] = now_s() - c.t0;
-            Slot          &s  = c.slot[j % kSlots];
-            hipStream_t    st = c.stream[j % kStreams];
-            const uint64_t b0 = k * D.cb, nb = (b0 + D.cb <= D.nblocks ? D.cb : D.nblocks - b0);
-            const uint64_t i0 = D.in_offsets[b0], len = D.in_offsets[b0 + nb] - i0;
-            auto issue = [&]() -> int {
-                // the chunk's offsets, rebased to the chunk's first byte (the pinned mirror of the previous
-                // chunk in this slot has been consumed: that chunk is drained)
-                uint64_t *ho = (uint64_t *)s.h_off.p;
-                for (uint64_t i = 0; i <= nb; i++) {
-                    if (D.in_offsets[b0 + i] < i0 || (i && D.in_offsets[b0 + i] < D.in_offsets[b0 + i - 1]))
-                        return REDUX_INVALID_INPUT;
-                    ho[i] = D.in_offsets[b0 + i] - i0;
-                }
-                HOST_TRY(hipMemcpyAsync(s.d_off.p, ho, (nb + 1) * 8, hipMemcpyHostToDevice, st));
-                int r = stage_h2d(c, pool, piece_no, s.d_in.p, D.in + i0, len, st);
-                if (r != REDUX_OK)
-                    return r;
-                HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
-                uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-                r = D.cum          ? redux_static_decode_blocks_dev(D.p, D.cum, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p,
-                                                                    nb * (uint64_t)D.block_size, s.d_sz.p, s.d_st.p, s.d_sum.p, st)
-                  : D.element_size ? redux_decode_planes_dev(D.p, s.d_in.p, s.d_off.p, D.chunk_out(b0, nb), D.block_size, D.element_size,
-                                                             s.d_out.p, s.d_sz.p, s.d_st.p, s.d_sum.p, ws, D.wsb, st)
-                                   : D.dev_call(D.p, s.d_in.p, s.d_off.p, nb, D.block_size, s.d_out.p, nb * (uint64_t)D.block_size, s.d_sz.p,
-                                                s.d_st.p, s.d_sum.p, ws, D.wsb, st, D.in_used ? s.d_used.p : nullptr, nullptr, false, 0);
-                if (r != REDUX_OK)
-                    return r;
-                HOST_TRY(hipEventRecord(s.done, st)); // (small result arrays: fetched by the drain thread, see encode_on_ctx)
-                return REDUX_OK;
-            };
-            rc = issue();
-            c.trace[j * 4 + 1] = now_s() - c.t0;
-            if (rc != REDUX_OK)
-                J.fail(rc);
-            std::lock_guard<std::mutex> l(H.m);
-            if (rc != REDUX_OK)
-                H.abort = true;
-            else
-                H.issued = j + 1;
-            H.cv.notify_all();
-            if (rc != REDUX_OK)
-                break;
-        }
-        {
-            std::lock_guard<std::mutex> l(H.m);
-            if (H.issued < mine)
-                H.abort = true;
-            H.cv.notify_all();
-        }
-    }
-    drain.join();
-    for (int i = 0; i < kStreams; i++)
-        (void)hipStreamSynchronize(c.stream[i]);
-}
-
-static int decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
-                         uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
-                         uint64_t *in_used, DecodeDevCall dev_call, uint32_t element_size = 0, uint64_t out_len = 0,
-                         const uint32_t *cum = nullptr)
-{
-    (void)out_cap;
-    std::vector<Ctx *> ctx;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    int rc = take_contexts(ctx, locks);
-    if (rc != REDUX_OK)
-        return rc;
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-
-    DecCall D;
-    D.p = p; D.in = in; D.in_offsets = in_offsets; D.nblocks = nblocks; D.block_size = block_size; D.out = out;
-    D.out_sizes = out_sizes; D.block_status = block_status; D.in_used = in_used; D.dev_call = dev_call;
-    D.element_size = element_size; D.out_len = out_len; D.cum = cum;
-    D.cb      = chunk_blocks_for(nblocks, block_size, kDecChunkMax, ctx.size());
-    D.nchunks = (nblocks + D.cb - 1) / D.cb;
-    D.wsb     = cum ? 0
-              : element_size ? redux_decode_planes_workspace_bytes(p, D.cb * (uint64_t)block_size, block_size, element_size)
-                             : redux_decode_workspace_bytes(p, D.cb, block_size);
-    D.max_in  = 0;
-    for (uint64_t k = 0; k < D.nchunks; k++) {
-        const uint64_t b0 = k * D.cb, b1 = (b0 + D.cb <= nblocks ? b0 + D.cb : nblocks);
-        if (in_offsets[b1] < in_offsets[b0])
-            return REDUX_INVALID_INPUT;
-        const uint64_t n = in_offsets[b1] - in_offsets[b0];
-        D.max_in = n > D.max_in ? n : D.max_in;
-    }
-    Job J;
-    const uint64_t nctx = ctx.size() < D.nchunks ? ctx.size() : D.nchunks;
-    std::vector<std::thread> th;
-    for (uint64_t d = 1; d < nctx; d++)
-        th.emplace_back([&, d] { decode_on_ctx(*ctx[d], D, J, d, nctx); });
-    decode_on_ctx(*ctx[0], D, J, 0, nctx);
-    for (auto &t : th)
-        t.join();
-    for (Ctx *c : ctx) {
-        if (c->ready)
-            (void)hipSetDevice(c->device);
-        ctx_trim_locked(*c);
-    }
-    if (caller_dev >= 0)
-        (void)hipSetDevice(caller_dev);
-    if (J.error != REDUX_OK)
-        return J.error;
-    return J.bad_status;
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder};
+    return run_chunks(op);
 }
 
 // ================================================================================================
-// byte histogram of host memory (redux_static_table)
+// decode: chunk k = blocks [k * cb, k * cb + nb) -> out[k * cb * block_size ..), chunk_out bytes of it
+// ================================================================================================
+struct DecodeChunks {
+    const uint8_t     *in;
+    const uint64_t    *in_offsets;
+    uint64_t           nblocks;
+    uint32_t           block_size;
+    uint8_t           *out;
+    uint64_t           out_len; // bytes the call writes: nblocks * block_size, or out[0 .. out_len) exactly in the planes layout
+    uint32_t          *out_sizes;
+    int32_t           *block_status;
+    uint64_t          *in_used;
+    const DecodeCoder &coder;
+    uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
+
+    int plan(size_t nctx, uint64_t &n)
+    {
+        cb       = chunk_blocks_for(nblocks, block_size, kDecChunkMax, nctx);
+        nchunks  = n = (nblocks + cb - 1) / cb;
+        ws_bytes = coder.workspace(cb);
+        for (uint64_t k = 0; k < nchunks; k++) {
+            const uint64_t b0 = k * cb, b1 = (b0 + cb <= nblocks ? b0 + cb : nblocks);
+            if (in_offsets[b1] < in_offsets[b0])
+                return REDUX_INVALID_INPUT;
+            const uint64_t len = in_offsets[b1] - in_offsets[b0];
+            max_in = len > max_in ? len : max_in;
+        }
+        return REDUX_OK;
+    }
+    uint64_t chunk_out(uint64_t b0, uint64_t nb) const // bytes a chunk's blocks write into out
+    {
+        const uint64_t full = nb * (uint64_t)block_size, o = b0 * (uint64_t)block_size;
+        return out_len - o < full ? out_len - o : full;
+    }
+    int grow(Ctx &c, Slot &s) const
+    {
+        const uint64_t used = in_used ? cb * 8 : 8;
+        return grow_bufs(c, {{&s.d_in, max_in + 32}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, cb * (uint64_t)block_size + 16},
+                             {&s.d_off, (cb + 1) * 8}, {&s.d_sz, cb * 4}, {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.d_used, used},
+                             {&s.h_off, (cb + 1) * 8}, {&s.h_sz, cb * 4}, {&s.h_st, cb * 4}, {&s.h_sum, 8}, {&s.h_used, used}});
+    }
+    int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
+    {
+        // the chunk's offsets, rebased to the chunk's first byte (the pinned mirror of the previous
+        // chunk in this slot has been consumed: that chunk is drained)
+        const uint64_t i0 = in_offsets[b0];
+        uint64_t      *ho = (uint64_t *)s.h_off.p;
+        for (uint64_t i = 0; i <= nb; i++) {
+            if (in_offsets[b0 + i] < i0 || (i && in_offsets[b0 + i] < in_offsets[b0 + i - 1]))
+                return REDUX_INVALID_INPUT;
+            ho[i] = in_offsets[b0 + i] - i0;
+        }
+        HOST_TRY(hipMemcpyAsync(s.d_off.p, ho, (nb + 1) * 8, hipMemcpyHostToDevice, st));
+        return stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
+    }
+    int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
+    {
+        return coder.launch(s, nb, chunk_out(b0, nb), in_used ? s.d_used.p : nullptr, slot_ws(s), ws_bytes, st);
+    }
+    bool fetch(Slot &s, hipStream_t st, uint64_t nb) const
+    {
+        return fetch_small(s.h_sz, s.d_sz, nb * 4, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
+               fetch_small(s.h_sum, s.d_sum, 8, st) && (!in_used || fetch_small(s.h_used, s.d_used, nb * 8, st));
+    }
+    Placed place(Ctx &c, Slot &s, uint64_t, uint64_t b0, uint64_t nb, Ledger &) const
+    {
+        const uint64_t n  = chunk_out(b0, nb);
+        const int      rc = n ? drain_d2h(c, out + b0 * (uint64_t)block_size, s.d_out.p, n) : REDUX_OK;
+        if (rc != REDUX_OK)
+            return {rc};
+        memcpy(out_sizes + b0, s.h_sz.p, nb * 4);
+        if (block_status)
+            memcpy(block_status + b0, s.h_st.p, nb * 4);
+        if (in_used)
+            memcpy(in_used + b0, s.h_used.p, nb * 8);
+        return {};
+    }
+};
+
+static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
+                         uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder)
+{
+    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder};
+    return run_chunks(op);
+}
+
+// ================================================================================================
+// byte histogram of host memory (the frequency table of the static model)
 //
 // The input is staged chunk by chunk through the pinned ring into the slots of the CURRENT device's context (the fleet of
 // redux_host_set_devices is not used: the result is 2 KiB, there is nothing to spread), and k_byte_hist of each chunk adds
@@ -917,17 +862,14 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
     c.want = dev;
     if ((rc = ctx_init_locked(c)) != REDUX_OK)
         return rc;
-    const uint64_t lo = g_chunk_min.load() ? g_chunk_min.load() : kChunkMin;
-    const uint64_t hi = g_chunk_max.load() ? g_chunk_max.load() : kEncChunkMax;
-    uint64_t chunk = (in_len + kSlots - 1) / kSlots;
-    chunk = chunk < lo ? lo : chunk > hi ? hi : chunk;
+    uint64_t chunk = clamp_chunk_bytes((in_len + kSlots - 1) / kSlots, kEncChunkMax);
     chunk = (chunk + 65535) / 65536 * 65536; // (whole 64 KiB: the test hook's 1-byte chunks become 64 KiB)
     const uint64_t nchunks = (in_len + chunk - 1) / chunk;
     const int      nslots  = (int)(nchunks < (uint64_t)kSlots ? nchunks : (uint64_t)kSlots);
-    if ((rc = grow_dev(c, c.d_counts, 256 * 8)) != REDUX_OK)
+    if ((rc = grow_buf(c, c.d_counts, 256 * 8)) != REDUX_OK)
         return rc;
     for (int i = 0; i < nslots; i++)
-        if ((rc = grow_dev(c, c.slot[i].d_in, chunk + 16)) != REDUX_OK)
+        if ((rc = grow_buf(c, c.slot[i].d_in, chunk + 16)) != REDUX_OK)
             return rc;
     HOST_TRY(hipMemsetAsync(c.d_counts.p, 0, 256 * 8, c.stream[0]));
     HOST_TRY(hipStreamSynchronize(c.stream[0])); // (the other streams do not wait for stream 0)
@@ -964,21 +906,6 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
 // ================================================================================================
 constexpr uint64_t kVGroupBytes = 512ull << 20;
 
-struct DeviceScope { // makes `dev` HIP's current device for a scope and puts the caller's back
-    int prev = -1;
-    explicit DeviceScope(int dev)
-    {
-        (void)hipGetDevice(&prev);
-        if (dev != prev)
-            (void)hipSetDevice(dev);
-    }
-    ~DeviceScope()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
 // One group of consecutive inputs = one launch.  first_block = number of its first block; nb its blocks.
 struct VGroup {
     uint64_t i0, i1, first_block, nb;
@@ -1004,55 +931,6 @@ static std::vector<VGroup> v_groups(const uint64_t *len, uint64_t ninputs, uint3
     return g;
 }
 
-// What the contexts of one `_v` call share: the groups are dealt round-robin (group k on context k mod n, each context
-// taking its groups in order), and -- encode only -- a group's place in the dense output is known once every earlier
-// group's size is.
-struct VJob {
-    std::mutex              m;
-    std::condition_variable cv;
-    std::vector<uint64_t>   total;
-    std::vector<char>       known;
-    std::vector<int>        bad;   // first non-OK block status of each group
-    int                     error = REDUX_OK;
-    bool                    abort = false;
-
-    explicit VJob(size_t n) : total(n, 0), known(n, 0), bad(n, REDUX_OK) {}
-    void fail(int rc)
-    {
-        std::lock_guard<std::mutex> l(m);
-        if (error == REDUX_OK)
-            error = rc;
-        abort = true;
-        cv.notify_all();
-    }
-    void publish(size_t g, uint64_t t)
-    {
-        std::lock_guard<std::mutex> l(m);
-        total[g] = t;
-        known[g] = 1;
-        cv.notify_all();
-    }
-    // bytes of all groups before g, once they are all known; false if the call was aborted meanwhile
-    bool base_of(size_t g, uint64_t &base)
-    {
-        std::unique_lock<std::mutex> l(m);
-        cv.wait(l, [&] {
-            if (abort)
-                return true;
-            for (size_t h = 0; h < g; h++)
-                if (!known[h])
-                    return false;
-            return true;
-        });
-        if (abort)
-            return false;
-        base = 0;
-        for (size_t h = 0; h < g; h++)
-            base += total[h];
-        return true;
-    }
-};
-
 struct EncVCall {
     const redux_params *p;
     const uint8_t      *in;
@@ -1064,7 +942,7 @@ struct EncVCall {
     int32_t            *block_status;
 };
 
-static int encode_v_group(Ctx &c, const EncVCall &E, const VGroup &G, size_t gi, VJob &J, CopyPool &pool, uint64_t &piece_no)
+static int encode_v_group(Ctx &c, const EncVCall &E, const VGroup &G, uint64_t gi, Ledger &L, CopyPool &pool, uint64_t &piece_no)
 {
     int         rc;
     Slot       &s  = c.slot[0];
@@ -1083,10 +961,9 @@ static int encode_v_group(Ctx &c, const EncVCall &E, const VGroup &G, size_t gi,
     redux_block_table_v(doff.data(), E.in_len + G.i0, G.i1 - G.i0, E.block_size, tbl.data());
     const uint64_t ws_bytes = redux_encode_workspace_bytes(E.p, ne * (uint64_t)E.block_size, E.block_size);
     const uint64_t bound    = nb * redux_encode_slot_bytes(E.p, E.block_size);
-    if ((rc = grow_dev(c, s.d_in, pos + 16)) || (rc = grow_dev(c, s.d_ws, ws_bytes + 256)) || (rc = grow_dev(c, s.d_out, bound + 16)) ||
-        (rc = grow_dev(c, s.d_off, (nb + 1) * 8)) || (rc = grow_dev(c, s.d_st, nb * 4)) || (rc = grow_dev(c, s.d_sum, 8)) ||
-        (rc = grow_dev(c, s.d_tab, ne * sizeof(redux_block))) || (rc = grow_pinned(c, s.h_off, (nb + 1) * 8)) ||
-        (rc = grow_pinned(c, s.h_st, nb * 4)) || (rc = grow_pinned(c, s.h_sum, 8)) || (rc = grow_pinned(c, s.h_tab, ne * sizeof(redux_block))))
+    if ((rc = grow_bufs(c, {{&s.d_in, pos + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (nb + 1) * 8},
+                            {&s.d_st, nb * 4}, {&s.d_sum, 8}, {&s.d_tab, ne * sizeof(redux_block)}, {&s.h_off, (nb + 1) * 8},
+                            {&s.h_st, nb * 4}, {&s.h_sum, 8}, {&s.h_tab, ne * sizeof(redux_block)}})))
         return rc;
     memcpy(s.h_tab.p, tbl.data(), ne * sizeof(redux_block));
     HOST_TRY(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, ne * sizeof(redux_block), hipMemcpyHostToDevice, st));
@@ -1095,9 +972,8 @@ static int encode_v_group(Ctx &c, const EncVCall &E, const VGroup &G, size_t gi,
             (rc = stage_h2d(c, pool, piece_no, (uint8_t *)s.d_in.p + doff[k], E.in + E.in_off[G.i0 + k], E.in_len[G.i0 + k], st)))
             return rc;
     HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
-    uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
     if ((rc = redux_encode_blocks_v_dev(E.p, s.d_in.p, pos, s.d_tab.p, ne, nb, E.block_size, REDUX_V_ALIGNED16, s.d_out.p, bound, s.d_off.p,
-                                        s.d_st.p, s.d_sum.p, ws, ws_bytes, st)))
+                                        s.d_st.p, s.d_sum.p, slot_ws(s), ws_bytes, st)))
         return rc;
     HOST_TRY(hipMemcpyAsync(s.h_off.p, s.d_off.p, (nb + 1) * 8, hipMemcpyDeviceToHost, st));
     HOST_TRY(hipMemcpyAsync(s.h_st.p, s.d_st.p, nb * 4, hipMemcpyDeviceToHost, st));
@@ -1105,84 +981,21 @@ static int encode_v_group(Ctx &c, const EncVCall &E, const VGroup &G, size_t gi,
     HOST_TRY(hipStreamSynchronize(st));
     const uint64_t *ho    = (const uint64_t *)s.h_off.p;
     const uint64_t  total = ho[nb];
-    J.publish(gi, total);
-    uint64_t out_base = 0;
-    if (!J.base_of(gi, out_base)) // (another group failed)
+    L.publish(gi, total);
+    const std::optional<uint64_t> out_base = L.base_of(gi);
+    if (!out_base) // (another group failed)
         return REDUX_OK;
-    if (out_base + total > E.out_cap)
+    if (*out_base + total > E.out_cap)
         return REDUX_OUTPUT_TOO_SMALL;
-    if (total && (rc = drain_d2h(c, E.out + out_base, s.d_out.p, total)))
+    if (total && (rc = drain_d2h(c, E.out + *out_base, s.d_out.p, total)))
         return rc;
     for (uint64_t i = 0; i <= nb; i++) // (entry nb is also the next group's entry 0: the same value from either side)
-        E.out_offsets[G.first_block + i] = out_base + ho[i];
+        E.out_offsets[G.first_block + i] = *out_base + ho[i];
     if (E.block_status)
         memcpy(E.block_status + G.first_block, s.h_st.p, nb * 4);
-    J.bad[gi] = ((const int32_t *)s.h_sum.p)[0];
+    if (((const int32_t *)s.h_sum.p)[0] != REDUX_OK)
+        L.note_bad(gi, ((const int32_t *)s.h_sum.p)[0]);
     return REDUX_OK;
-}
-
-// runs fn(group index) for the groups first, first + stride, ... on context c (whose mutex the call holds)
-template <typename F>
-static void v_on_ctx(Ctx &c, size_t ngroups, size_t first, size_t stride, VJob &J, F &&fn)
-{
-    int rc = ctx_init_locked(c); // (makes c.want HIP's current device on this thread)
-    if (rc != REDUX_OK)
-        return J.fail(rc);
-    CopyPool pool(kCopyThreads - 1);
-    uint64_t piece_no = 0;
-    for (size_t g = first; g < ngroups; g += stride) {
-        {
-            std::lock_guard<std::mutex> l(J.m);
-            if (J.abort)
-                break;
-        }
-        if ((rc = fn(c, g, pool, piece_no)) != REDUX_OK)
-            return J.fail(rc);
-    }
-    (void)hipStreamSynchronize(c.stream[0]);
-}
-
-template <typename F>
-static int v_deal(size_t ngroups, VJob &J, F &&fn)
-{
-    std::vector<Ctx *> ctx;
-    std::vector<std::unique_lock<std::mutex>> locks;
-    int rc = take_contexts(ctx, locks);
-    if (rc != REDUX_OK)
-        return rc;
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-    const size_t nctx = ctx.size() < ngroups ? ctx.size() : ngroups; // (the reference's corpus is one group: one context)
-    std::vector<std::thread> th;
-    for (size_t d = 1; d < nctx; d++)
-        th.emplace_back([&, d] { v_on_ctx(*ctx[d], ngroups, d, nctx, J, fn); });
-    v_on_ctx(*ctx[0], ngroups, 0, nctx, J, fn);
-    for (auto &t : th)
-        t.join();
-    for (Ctx *c : ctx) {
-        if (c->ready)
-            (void)hipSetDevice(c->device);
-        ctx_trim_locked(*c);
-    }
-    if (caller_dev >= 0)
-        (void)hipSetDevice(caller_dev);
-    if (J.error != REDUX_OK)
-        return J.error;
-    for (int b : J.bad) // the first group (in block order) with a non-OK block decides
-        if (b != REDUX_OK)
-            return b;
-    return REDUX_OK;
-}
-
-static int encode_blocks_v(const redux_params *p, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t ninputs,
-                           uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
-{
-    const std::vector<VGroup> groups = v_groups(in_len, ninputs, block_size);
-    EncVCall E{p, in, in_off, in_len, block_size, out, out_cap, out_offsets, block_status};
-    VJob     J(groups.size());
-    return v_deal(groups.size(), J, [&](Ctx &c, size_t g, CopyPool &pool, uint64_t &piece_no) {
-        return encode_v_group(c, E, groups[g], g, J, pool, piece_no);
-    });
 }
 
 struct DecVCall {
@@ -1194,10 +1007,9 @@ struct DecVCall {
     uint32_t            block_size;
     uint32_t           *out_sizes;
     int32_t            *block_status;
-    DecodeDevCall       dev_call;
 };
 
-static int decode_v_group(Ctx &c, const DecVCall &D, const VGroup &G, size_t gi, VJob &J, CopyPool &pool, uint64_t &piece_no)
+static int decode_v_group(Ctx &c, const DecVCall &D, const VGroup &G, uint64_t gi, Ledger &L, CopyPool &pool, uint64_t &piece_no)
 {
     int         rc;
     Slot       &s  = c.slot[0];
@@ -1220,11 +1032,10 @@ static int decode_v_group(Ctx &c, const DecVCall &D, const VGroup &G, size_t gi,
     if (len_in && !D.in)
         return REDUX_INVALID_INPUT;
     const uint64_t wsb = redux_decode_workspace_bytes(D.p, ne, D.block_size);
-    if ((rc = grow_dev(c, s.d_in, len_in + 32)) || (rc = grow_dev(c, s.d_ws, wsb + 256)) || (rc = grow_dev(c, s.d_out, pos + 16)) ||
-        (rc = grow_dev(c, s.d_off, (nb + 1) * 8)) || (rc = grow_dev(c, s.d_sz, nb * 4)) || (rc = grow_dev(c, s.d_st, nb * 4)) ||
-        (rc = grow_dev(c, s.d_sum, 8)) || (rc = grow_dev(c, s.d_tab, ne * sizeof(redux_block))) ||
-        (rc = grow_pinned(c, s.h_off, (nb + 1) * 8)) || (rc = grow_pinned(c, s.h_sz, nb * 4)) || (rc = grow_pinned(c, s.h_st, nb * 4)) ||
-        (rc = grow_pinned(c, s.h_sum, 8)) || (rc = grow_pinned(c, s.h_tab, ne * sizeof(redux_block))))
+    if ((rc = grow_bufs(c, {{&s.d_in, len_in + 32}, {&s.d_ws, wsb + 256}, {&s.d_out, pos + 16}, {&s.d_off, (nb + 1) * 8},
+                            {&s.d_sz, nb * 4}, {&s.d_st, nb * 4}, {&s.d_sum, 8}, {&s.d_tab, ne * sizeof(redux_block)},
+                            {&s.h_off, (nb + 1) * 8}, {&s.h_sz, nb * 4}, {&s.h_st, nb * 4}, {&s.h_sum, 8},
+                            {&s.h_tab, ne * sizeof(redux_block)}})))
         return rc;
     uint64_t *ho = (uint64_t *)s.h_off.p;
     for (uint64_t i = 0; i <= nb; i++)
@@ -1235,9 +1046,8 @@ static int decode_v_group(Ctx &c, const DecVCall &D, const VGroup &G, size_t gi,
     if (len_in && (rc = stage_h2d(c, pool, piece_no, s.d_in.p, D.in + sb0, len_in, st)))
         return rc;
     HOST_TRY(hipMemsetAsync(s.d_sum.p, 0, 8, st));
-    uint8_t *ws = (uint8_t *)(((uintptr_t)s.d_ws.p + 255) & ~(uintptr_t)255);
-    if ((rc = D.dev_call(D.p, s.d_in.p, s.d_off.p, ne, D.block_size, s.d_out.p, pos, s.d_sz.p, s.d_st.p, s.d_sum.p, ws, wsb, st, nullptr,
-                         (const redux_block *)s.d_tab.p, true, nb)))
+    if ((rc = redux_decode_blocks_v_dev(D.p, s.d_in.p, s.d_off.p, s.d_tab.p, ne, nb, D.block_size, REDUX_V_ALIGNED16, s.d_out.p, pos,
+                                        s.d_sz.p, s.d_st.p, s.d_sum.p, slot_ws(s), wsb, st)))
         return rc;
     HOST_TRY(hipMemcpyAsync(s.h_sz.p, s.d_sz.p, nb * 4, hipMemcpyDeviceToHost, st));
     HOST_TRY(hipMemcpyAsync(s.h_st.p, s.d_st.p, nb * 4, hipMemcpyDeviceToHost, st));
@@ -1267,19 +1077,47 @@ static int decode_v_group(Ctx &c, const DecVCall &D, const VGroup &G, size_t gi,
     memcpy(D.out_sizes + blk_base, hs, nb * 4);
     if (D.block_status)
         memcpy(D.block_status + blk_base, s.h_st.p, nb * 4);
-    J.bad[gi] = ((const int32_t *)s.h_sum.p)[0];
+    if (((const int32_t *)s.h_sum.p)[0] != REDUX_OK)
+        L.note_bad(gi, ((const int32_t *)s.h_sum.p)[0]);
     return REDUX_OK;
 }
 
+// group_fn(c, g, ledger, pool, piece_no) for every group, the groups dealt round-robin over the call's contexts; each context
+// runs its groups one after the other, on its first slot and stream
+template <typename F>
+static int run_groups(uint64_t ngroups, F &&group_fn)
+{
+    return run_fleet([&](size_t, uint64_t &nunits) { nunits = ngroups; return REDUX_OK; },
+                     [&](Ctx &c, Ledger &L, uint64_t first, uint64_t stride) {
+                         int rc = ctx_init_locked(c); // (makes c.want HIP's current device on this thread)
+                         if (rc != REDUX_OK)
+                             return L.fail(rc);
+                         CopyPool pool(kCopyThreads - 1);
+                         uint64_t piece_no = 0;
+                         for (uint64_t g = first; g < ngroups && !L.aborted(); g += stride)
+                             if ((rc = group_fn(c, g, L, pool, piece_no)) != REDUX_OK)
+                                 return L.fail(rc);
+                         (void)hipStreamSynchronize(c.stream[0]);
+                     });
+}
+
+static int encode_blocks_v(const redux_params *p, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t ninputs,
+                           uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    const std::vector<VGroup> groups = v_groups(in_len, ninputs, block_size);
+    const EncVCall            E{p, in, in_off, in_len, block_size, out, out_cap, out_offsets, block_status};
+    return run_groups(groups.size(), [&](Ctx &c, uint64_t g, Ledger &L, CopyPool &pool, uint64_t &piece_no) {
+        return encode_v_group(c, E, groups[g], g, L, pool, piece_no);
+    });
+}
+
 static int decode_blocks_v(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint8_t *out, const uint64_t *out_off,
-                           const uint64_t *out_len, uint64_t ninputs, uint32_t block_size, uint32_t *out_sizes, int32_t *block_status,
-                           DecodeDevCall dev_call)
+                           const uint64_t *out_len, uint64_t ninputs, uint32_t block_size, uint32_t *out_sizes, int32_t *block_status)
 {
     const std::vector<VGroup> groups = v_groups(out_len, ninputs, block_size);
-    DecVCall D{p, in, in_offsets, out, out_off, out_len, block_size, out_sizes, block_status, dev_call};
-    VJob     J(groups.size());
-    return v_deal(groups.size(), J, [&](Ctx &c, size_t g, CopyPool &pool, uint64_t &piece_no) {
-        return decode_v_group(c, D, groups[g], g, J, pool, piece_no);
+    const DecVCall            D{p, in, in_offsets, out, out_off, out_len, block_size, out_sizes, block_status};
+    return run_groups(groups.size(), [&](Ctx &c, uint64_t g, Ledger &L, CopyPool &pool, uint64_t &piece_no) {
+        return decode_v_group(c, D, groups[g], g, L, pool, piece_no);
     });
 }
 
