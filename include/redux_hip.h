@@ -367,6 +367,51 @@ int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status);
 
+/* ---- per-block CRC-32 checksums ---------------------------------------------------------------
+ * crc[b] = CRC-32/ISO-HDLC -- the zlib / gzip / PNG CRC (reflected polynomial 0xEDB88320, init and xorout 0xFFFFFFFF),
+ * zlib.crc32 -- of the ORIGINAL, uncompressed bytes x[b*B .. min((b+1)*B, len)), B = block_size.  The same for every model
+ * and layout: with the byte-plane layout block b of the checksum is an original-order range, not plane b.  An empty input
+ * is one empty block with CRC 0.  Computed on the device (k_crc32, redux_amd/csrc/redux_crc.hpp) from the linearity of the
+ * CRC over GF(2): the terms of a block's pieces are combined by XOR in any order.  Any block size, any alignment.
+ *
+ * redux_crc32_blocks_dev    crc[b] of d_in[0 .. in_len) in blocks of block_size: redux_block_count(in_len, block_size)
+ *                           entries in d_crc (u32, device).  Stream-ordered, never allocates, never synchronises.
+ * redux_crc32_sizes_dev     the layout redux_decode_blocks_dev writes: block b = d_in[b*B .. b*B + min(sizes[b], B)),
+ *                           d_sizes u32[nblocks] on the device.
+ * redux_crc32_combine       zlib's crc32_combine, on the host: the CRC of A || B from crc(A), crc(B) and |B| (a whole file's
+ *                           CRC from its block CRCs).
+ * redux_crc32_blocks        host pointers: chunks staged through the host pipeline's pinned ring on the CURRENT device (as
+ *                           redux_static_table; redux_host_set_devices is ignored), crc[] in host memory.
+ * The `_crc` coding calls take their sibling's arguments plus block_crc (u32[nblocks], host memory):
+ *   - encode: crc[b] of the input, computed on each chunk's staged input in HBM before any transform;
+ *   - decode: the CRC of what block b decoded to (planes: the original-order range after the inverse transform), computed
+ *     on each chunk's output in HBM; unspecified for a block whose status is not OK.
+ * Their CRCs cost no extra PCIe traffic (4 bytes per block travel with the chunk's other small arrays) and depend on
+ * neither the chunk size nor the devices.  The sibling calls are these with block_crc = NULL.  A caller that finds a
+ * mismatch reports INVALID_INPUT (there is no status code of its own). */
+int      redux_crc32_blocks_dev(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_crc /* u32[nblocks] */, void *stream);
+int      redux_crc32_sizes_dev(const void *d_in, uint64_t nblocks, uint32_t block_size, const void *d_sizes /* u32[nblocks] */,
+                               void *d_crc /* u32[nblocks] */, void *stream);
+uint32_t redux_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
+int      redux_crc32_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t *crc);
+int      redux_encode_blocks_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out,
+                                 uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc);
+int      redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
+                                 uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
+                                 uint32_t *block_crc);
+int      redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                        uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                        int32_t *block_status, uint32_t *block_crc);
+int      redux_decode_blocks_planes_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                                        uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes,
+                                        int32_t *block_status, uint32_t *block_crc);
+int      redux_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                        uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                        int32_t *block_status, uint32_t *block_crc);
+int      redux_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in,
+                                        const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
+                                        uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

@@ -232,14 +232,26 @@ def _check_element_size(element_size):
     return int(element_size)
 
 
-def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
+def _crc_out(block_crc, nb):
+    """the caller's block_crc= array (np.uint32[nblocks], filled in place) -> its pointer; None -> NULL"""
+    if block_crc is None:
+        return None
+    if not isinstance(block_crc, np.ndarray) or block_crc.dtype != np.uint32 or block_crc.shape != (nb,) \
+            or not block_crc.flags.c_contiguous or not block_crc.flags.writeable:
+        raise InvalidInput()
+    return block_crc.ctypes.data if nb else None
+
+
+def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
     layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
-    params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks); no element_size."""
+    params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks); no element_size.
+    block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 (zlib.crc32) of every input block, in original
+    byte order for every layout (the `_crc` calls of include/redux_hip.h)."""
     if isinstance(params, StaticModel):
-        return _compress_blocks_static(data, block_size, params, element_size)
+        return _compress_blocks_static(data, block_size, params, element_size, block_crc)
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
@@ -253,7 +265,11 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
     out = np.empty(cap, dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
-    if E == 1:
+    crc = _crc_out(block_crc, nb)
+    if block_crc is not None:
+        st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
+                                              offs.ctypes.data, status.ctypes.data, crc)
+    elif E == 1:
         st = L.redux_encode_blocks(C.byref(cp), _ptr(a), len(a), block_size, out.ctypes.data, cap, offs.ctypes.data,
                                    status.ctypes.data)
     else:
@@ -263,7 +279,7 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1):
     return out[: int(offs[-1])], offs, status
 
 
-def _compress_blocks_static(data, block_size, model, element_size):
+def _compress_blocks_static(data, block_size, model, element_size, block_crc=None):
     if _check_element_size(element_size) != 1:
         raise InvalidInput()  # (each byte plane would need its own table)
     a = _u8(data)
@@ -276,12 +292,16 @@ def _compress_blocks_static(data, block_size, model, element_size):
     out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
-    _raise(L.redux_static_encode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data, cap,
-                                        offs.ctypes.data, status.ctypes.data))
+    if block_crc is not None:
+        _raise(L.redux_static_encode_blocks_crc(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
+                                                cap, offs.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb)))
+    else:
+        _raise(L.redux_static_encode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data, cap,
+                                            offs.ctypes.data, status.ctypes.data))
     return out[: int(offs[-1])], offs, status
 
 
-def _decompress_blocks_static(streams, offsets, block_size, model, check, element_size, length):
+def _decompress_blocks_static(streams, offsets, block_size, model, check, element_size, length, block_crc=None):
     if _check_element_size(element_size) != 1 or length is not None:
         raise InvalidInput()
     a = _u8(streams)
@@ -294,27 +314,35 @@ def _decompress_blocks_static(streams, offsets, block_size, model, check, elemen
     out = np.empty(nb * block_size, dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
-    st = L.redux_static_decode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
-                                      out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data)
+    if block_crc is not None:
+        st = L.redux_static_decode_blocks_crc(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
+                                              out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data,
+                                              _crc_out(block_crc, nb))
+    else:
+        st = L.redux_static_decode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
+                                          out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data)
     if check:
         _raise(st)
     return out, sizes, status
 
 
-def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None):
+def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
+                      block_crc=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
     required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
     (frames with a damaged block hold undefined bytes; their blocks' status says which).
-    params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks)."""
+    params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks).
+    block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
+    order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK."""
     if isinstance(params, StaticModel):
-        return _decompress_blocks_static(streams, offsets, block_size, params, check, element_size, length)
+        return _decompress_blocks_static(streams, offsets, block_size, params, check, element_size, length, block_crc)
     E = _check_element_size(element_size)
     if E > 1 and length is None:
         raise InvalidInput()
     if length is not None:
-        return _decompress_blocks_planes(streams, offsets, block_size, params, check, E, int(length))
+        return _decompress_blocks_planes(streams, offsets, block_size, params, check, E, int(length), block_crc)
     P = _params_of(params)
     a = _u8(streams)
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -327,14 +355,18 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     out = np.empty(nb * block_size, dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
-    st = L.redux_decode_blocks(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
-                               sizes.ctypes.data, status.ctypes.data)
+    if block_crc is not None:
+        st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
+                                       sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
+    else:
+        st = L.redux_decode_blocks(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
+                                   sizes.ctypes.data, status.ctypes.data)
     if check:
         _raise(st)
     return out, sizes, status
 
 
-def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, length):
+def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, length, block_crc=None):
     P = _params_of(params)
     a = _u8(streams)
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -348,8 +380,12 @@ def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, le
     out = np.empty(max(length, 1), dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
-    st = L.redux_decode_blocks_planes(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
-                                      sizes.ctypes.data, status.ctypes.data)
+    if block_crc is not None:
+        st = L.redux_decode_blocks_planes_crc(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
+                                              sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
+    else:
+        st = L.redux_decode_blocks_planes(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
+                                          sizes.ctypes.data, status.ctypes.data)
     if check:
         _raise(st)
     return out[:length], sizes, status
@@ -747,6 +783,49 @@ def planes(d_src, element_size, block_size, inverse=False, out=None):
         _raise(_lib.lib().redux_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
                                            1 if inverse else 0, _stream_ptr(torch)))
     return t
+
+
+# ---- per-block CRC-32 checksums -----------------------------------------------------------------
+def crc32_blocks(data, block_size, sizes=None):
+    """CRC-32 (zlib.crc32) of every block of block_size bytes of `data` (the last may be shorter; empty data: one block,
+    CRC 0) -> np.uint32[nblocks].  Host data (bytes-like, numpy) goes through redux_crc32_blocks; a uint8 device tensor is
+    checksummed where it lies (redux_crc32_blocks_dev, one read-back).  sizes (device tensors only: an int32 / uint32
+    device tensor of nblocks entries, as DeviceDecoder.decode returns): block b is then data[b*B : b*B + min(sizes[b], B)),
+    the layout of a decoder's output (redux_crc32_sizes_dev)."""
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    L = _lib.lib()
+    if not _is_device_tensor(data):
+        if sizes is not None:
+            raise InvalidInput()
+        a = _u8(data)
+        crc = np.zeros(L.redux_block_count(len(a), block_size), dtype=np.uint32)
+        _raise(L.redux_crc32_blocks(_ptr(a), len(a), block_size, crc.ctypes.data))
+        return crc
+    torch = _torch()
+    assert data.dtype == torch.uint8 and data.is_contiguous()
+    with torch.cuda.device(data.device):
+        s = _stream_ptr(torch)
+        if sizes is None:
+            n = data.numel()
+            d_crc = torch.empty(L.redux_block_count(n, block_size), dtype=torch.int32, device=data.device)
+            _raise(L.redux_crc32_blocks_dev(C.c_void_p(data.data_ptr()) if n else None, n, block_size,
+                                            C.c_void_p(d_crc.data_ptr()), s))
+        else:
+            assert sizes.is_cuda and sizes.device == data.device and sizes.element_size() == 4 and sizes.is_contiguous()
+            nb = sizes.numel()
+            if nb * block_size > data.numel():  # (the kernel may read any byte of every block's room)
+                raise InvalidInput()
+            d_crc = torch.empty(max(nb, 1), dtype=torch.int32, device=data.device)
+            _raise(L.redux_crc32_sizes_dev(C.c_void_p(data.data_ptr()), nb, block_size, C.c_void_p(sizes.data_ptr()),
+                                           C.c_void_p(d_crc.data_ptr()), s))
+            d_crc = d_crc[:nb]
+        return d_crc.cpu().numpy().view(np.uint32).copy()
+
+
+def crc32_combine(crc1, crc2, len2):
+    """zlib's crc32_combine (redux_crc32_combine, on the host): the CRC of A || B from crc32(A), crc32(B) and len(B)."""
+    return int(_lib.lib().redux_crc32_combine(int(crc1) & 0xFFFFFFFF, int(crc2) & 0xFFFFFFFF, int(len2)))
 
 
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------

@@ -1,7 +1,7 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
-                            [--model adaptive|static]
+                            [--model adaptive|static] [--checksum]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -14,12 +14,16 @@ A raw reference stream has no place to record it: `--element-size` above 1 with 
 `--model static` (with a block size, element size 1) builds one static frequency table from the whole input and codes
 every block under it (container version 3, which records the table); `--model adaptive`, the default, is the
 reference's model.  Decoding reads the model from the container.
+`--checksum` (with -c and a block size) records the CRC-32 (zlib.crc32) of every block's uncompressed bytes in the container
+(version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
+damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
+table: `--checksum` with `--block-size 0` is a usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static>]")
+         "[--model <adaptive|static>] [--checksum]")
 
 
 def parse(argv):
@@ -28,6 +32,8 @@ def parse(argv):
     for arg in it:
         if arg == "-c":
             opts["compress"] = True
+        elif arg == "--checksum":
+            opts["checksum"] = True
         elif arg == "-d":
             opts["compress"] = False
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model"):
@@ -59,6 +65,8 @@ def parse(argv):
         return None  # a raw reference stream has no place to record the element size
     if opts.get("model") == "static" and (opts["block_size"] == 0 or opts.get("element_size", 1) != 1):
         return None  # the table lives in the container (not in a raw stream), and there is one table, not one per plane
+    if opts.get("checksum") and opts["compress"] and opts["block_size"] == 0:
+        return None  # the table lives in the container (-d verifies whatever table a container has)
     return None if opts["compress"] is None else opts
 
 
@@ -88,7 +96,7 @@ def main(argv=None):
                 sink.write(o.getvalue())
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
-                                                opts.get("model", "adaptive"))
+                                                opts.get("model", "adaptive"), opts.get("checksum", False))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -14,6 +14,7 @@ Layout (little-endian):
    24   8  total uncompressed length
    (version 3 only) 4*258  the static table cum[0..=257], u32
    ..  4*nblocks   compressed size of each block
+   (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
    ..  payloads, concatenated in block order
 
 Version 2 is the same layout for data coded with the byte-plane layout of typed data (include/redux_hip.h): the payloads
@@ -23,6 +24,13 @@ byte for byte what this module wrote before version 2 existed.
 Version 3 holds streams of the static-table model (include/redux_hip.h, "static-table model" and "semi-static coding"):
 the header is followed by the table the blocks were coded under, and decoding uses it.  A table that
 redux_static_table_check rejects is InvalidInput, a truncated one Eof.
+
+Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13: versions 1 / 2 / 3 with checksums) means a table of nblocks
+CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
+every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
+block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
+right length and is caught only here.  Any other high bit is InvalidInput, a truncated table Eof.  Without checksums the
+writers emit exactly the bytes they emitted before the flag existed.
 """
 import struct
 
@@ -35,6 +43,7 @@ VERSION = 1
 VERSION_PLANES = 2
 VERSION_STATIC = 3
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
+CRC_FLAG = 0x10  # version bit: a table of per-block CRC-32 values follows the size table
 ELEMENT_SIZES = (2, 4, 8)  # what version 2 may record
 HEADER = struct.Struct("<4sBBBBIIQQ")
 # A header field, not a promise: a crafted 40-byte file must not make the decoder allocate
@@ -43,9 +52,10 @@ HEADER = struct.Struct("<4sBBBBIIQQ")
 MAX_BLOCK_SIZE = 1 << 30
 
 
-def pack(streams, offsets, params, block_size, total_len, element_size=1):
+def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
-    byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1)."""
+    byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
+    block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table."""
     if element_size != 1 and element_size not in ELEMENT_SIZES:
         raise api.InvalidInput()
     static = isinstance(params, api.StaticModel)
@@ -57,14 +67,27 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1):
     if (sizes < 0).any() or (sizes > 0xFFFFFFFF).any():
         raise api.InvalidInput()
     ver, res = (VERSION_STATIC, 0) if static else (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
+    crc = b""
+    if block_crc is not None:
+        c = np.asarray(block_crc)
+        if c.shape != (len(sizes),):
+            raise api.InvalidInput()
+        ver |= CRC_FLAG
+        crc = c.astype("<u4").tobytes()
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if static:
         head += params.cum.astype("<u4").tobytes()
-    return head + sizes.astype("<u4").tobytes() + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
+    return head + sizes.astype("<u4").tobytes() + crc + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
 
 def _version_ok(ver, res):
+    ver &= ~CRC_FLAG
     return (ver in (VERSION, VERSION_STATIC) and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)
+
+
+def _layout(ver):
+    """the version without its checksum flag"""
+    return ver & ~CRC_FLAG
 
 
 def unpack(buf):
@@ -80,7 +103,7 @@ def unpack(buf):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     start = HEADER.size
-    if ver == VERSION_STATIC:
+    if _layout(ver) == VERSION_STATIC:
         _table(b, P)
         start += TABLE
     end_sizes = start + 4 * nblocks
@@ -89,10 +112,27 @@ def unpack(buf):
     sizes = np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint64)
     offsets = np.zeros(nblocks + 1, dtype=np.uint64)
     offsets[1:] = np.cumsum(sizes)
+    if ver & CRC_FLAG:
+        end_sizes += 4 * nblocks
+        if len(b) < end_sizes:
+            raise api.Eof()
     if len(b) < end_sizes + int(offsets[-1]):
         raise api.Eof()
     payload = np.frombuffer(b, dtype=np.uint8, count=int(offsets[-1]), offset=end_sizes)
     return P, block_size, total, offsets, payload
+
+
+def block_crcs(buf):
+    """The per-block CRC-32 table (np.uint32[nblocks]) a flagged container (0x11 / 0x12 / 0x13) records; None without
+    the flag.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    b = memoryview(buf)
+    unpack(b)  # (every check of the layout, the table's extent included)
+    ver = b[4]
+    if not ver & CRC_FLAG:
+        return None
+    nblocks = HEADER.unpack_from(b, 0)[7]
+    start = HEADER.size + (TABLE if _layout(ver) == VERSION_STATIC else 0) + 4 * nblocks
+    return np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint32)
 
 
 def element_size(buf):
@@ -104,7 +144,7 @@ def element_size(buf):
     magic, ver, _sb, _fb, _cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
     if magic != MAGIC or not _version_ok(ver, res):
         raise api.InvalidInput()
-    return res if ver == VERSION_PLANES else 1
+    return res if _layout(ver) == VERSION_PLANES else 1
 
 
 def _table(b, P):
@@ -127,7 +167,7 @@ def static_table(buf):
     magic, ver, sb, fb, cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
     if magic != MAGIC or not _version_ok(ver, res):
         raise api.InvalidInput()
-    if ver != VERSION_STATIC:
+    if _layout(ver) != VERSION_STATIC:
         return None
     return _table(b, api.Parameters(sb, fb, cb))
 
@@ -153,21 +193,30 @@ def header_is_wellformed(buf):
     return nblocks == (1 if total == 0 else (total + block_size - 1) // block_size)
 
 
-def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive"):
+def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
-    model "static": the static table of the data (api.static_table, default total) codes every block, version 3."""
+    model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
+    checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call."""
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
             or model not in ("adaptive", "static") or (model == "static" and element_size != 1):
         raise api.InvalidInput()
+    crc = np.zeros(max(1, -(-len(data) // block_size)), dtype=np.uint32) if checksum else None
+    kw = {} if crc is None else {"block_crc": crc}
     if model == "static":
         m = api.StaticModel.from_data(data, params)
-        out, offs, _ = api.compress_blocks(data, block_size, m)
-        return pack(out, offs, m, block_size, len(data))
+        out, offs, _ = api.compress_blocks(data, block_size, m, **kw)
+        return pack(out, offs, m, block_size, len(data), block_crc=crc)
     if element_size == 1:
-        out, offs, _ = api.compress_blocks(data, block_size, params)
+        out, offs, _ = api.compress_blocks(data, block_size, params, **kw)
     else:
-        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size)
-    return pack(out, offs, params, block_size, len(data), element_size)
+        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size, **kw)
+    return pack(out, offs, params, block_size, len(data), element_size, block_crc=crc)
+
+
+def _verify(want, got, status):
+    """a checksummed container: every OK block must decode to the recorded CRC"""
+    if want is not None and bool(((got != want) & (np.asarray(status) == 0)).any()):
+        raise api.InvalidInput()
 
 
 def decompress_bytes(buf):
@@ -181,24 +230,29 @@ def decompress_bytes(buf):
         raise api.InvalidInput()
     E = element_size(buf)
     cum = static_table(buf)
+    want = block_crcs(buf)
+    got = None if want is None else np.zeros(nb, dtype=np.uint32)
+    kw = {} if got is None else {"block_crc": got}
     model = P if cum is None else api.StaticModel(P, cum)
     if E > 1:  # (frames are E * block_size bytes: the blocks decode at their real size, into out[0 .. total))
         try:
-            out, sizes, _ = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total)
+            out, sizes, status = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total, **kw)
         except MemoryError:
             raise api.InvalidInput()
         expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]
         if [int(x) for x in sizes] != expect:
             raise api.InvalidInput()
+        _verify(want, got, status)
         return out.tobytes()
     cap = max(1, min(block_size, total))  # one short block never needs block_size bytes of capacity
     try:
-        out, sizes, _ = api.decompress_blocks(payload, offsets, cap, model)
+        out, sizes, status = api.decompress_blocks(payload, offsets, cap, model, **kw)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
         raise api.InvalidInput()
     expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]
     if [int(x) for x in sizes] != expect:
         raise api.InvalidInput()
+    _verify(want, got, status)
     if total == nb * cap:
         return out.tobytes()
     return b"".join(out[b * cap: b * cap + int(sizes[b])].tobytes() for b in range(nb))

@@ -32,6 +32,7 @@
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
 #include "redux_hist.hpp"
+#include "redux_crc.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -523,6 +524,48 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
     return REDUX_OK;
 }
 
+// per-block CRC-32 (redux_crc.hpp): G lanes per block, the widest power of two up to 64 that leaves every lane at least
+// 16 chunks; blocks above kCrcSeg in segments (XORed into a zeroed d_crc)
+static uint32_t crc_group(uint32_t block_size)
+{
+    uint32_t G = 1;
+    while (G < 64 && 512ull * G <= block_size)
+        G *= 2;
+    return G;
+}
+
+static int launch_crc32(const void *d_in, uint64_t in_len, const void *d_sizes, uint64_t nblocks, uint32_t block_size, void *d_crc,
+                        hipStream_t s)
+{
+    if (nblocks == 0)
+        return REDUX_OK;
+    CrcArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.sizes      = (const uint32_t *)d_sizes;
+    a.nblocks    = nblocks;
+    a.block_size = block_size;
+    a.nseg       = block_size > kCrcSeg ? (uint32_t)((block_size + kCrcSeg - 1) / kCrcSeg) : 1;
+    a.nitems     = nblocks * a.nseg;
+    a.crc        = (uint32_t *)d_crc;
+    const uint32_t G    = crc_group(block_size);
+    const uint64_t per  = kCrcThreads / G, wgs = (a.nitems + per - 1) / per, cap = 4ull * cu_count(); // (32 KiB of LDS each)
+    const uint32_t grid = (uint32_t)(wgs < cap ? wgs : cap);
+    if (a.nseg > 1)
+        HIP_TRY(hipMemsetAsync(d_crc, 0, nblocks * 4, s));
+    switch (G) {
+    case 1: k_crc32<1><<<grid, kCrcThreads, 0, s>>>(a); break;
+    case 2: k_crc32<2><<<grid, kCrcThreads, 0, s>>>(a); break;
+    case 4: k_crc32<4><<<grid, kCrcThreads, 0, s>>>(a); break;
+    case 8: k_crc32<8><<<grid, kCrcThreads, 0, s>>>(a); break;
+    case 16: k_crc32<16><<<grid, kCrcThreads, 0, s>>>(a); break;
+    case 32: k_crc32<32><<<grid, kCrcThreads, 0, s>>>(a); break;
+    default: k_crc32<64><<<grid, kCrcThreads, 0, s>>>(a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
 extern "C" {
 
 const char *redux_version(void) { return "redux_hip 0.3.0 gfx950"; }
@@ -993,15 +1036,22 @@ int redux_encode_blocks_v(const redux_params *p, const uint8_t *in, const uint64
     return host::encode_blocks_v(p, in, in_off, in_len, ninputs, block_size, out, out_cap, out_offsets, block_status);
 }
 
-int redux_encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
-                        uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+int redux_encode_blocks_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                            uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
     if (block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, adaptive_encoder(p, block_size)); // redux_host.hpp
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, adaptive_encoder(p, block_size),
+                               block_crc); // redux_host.hpp
+}
+
+int redux_encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                        uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    return redux_encode_blocks_crc(p, in, in_len, block_size, out, out_cap, out_offsets, block_status, nullptr);
 }
 
 int redux_compress(const redux_params *p, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
@@ -1307,7 +1357,8 @@ static host::DecodeCoder planes_decoder(const redux_params *p, uint32_t block_si
             [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
                 return redux_decode_planes_dev(p, s.d_in.p, s.d_off.p, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
                                                s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
-            }};
+            },
+            true};
 }
 
 // the static decoder takes no workspace
@@ -1324,7 +1375,7 @@ static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *c
 // blocks decode to out_len bytes (nblocks * block_size, or exactly out_len in the planes layout) in out[0 .. out_cap).
 static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
-                              uint64_t *in_used, const host::DecodeCoder &coder)
+                              uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr)
 {
     if (params != REDUX_OK)
         return params;
@@ -1336,15 +1387,23 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
         return REDUX_OUTPUT_TOO_SMALL;
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
-    return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder); // redux_host.hpp
+    return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
+                               block_crc); // redux_host.hpp
+}
+
+int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
+                            uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
+                            int32_t *block_status, uint32_t *block_crc)
+{
+    return decode_blocks_host(check_params(p), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
+                              out_sizes, block_status, nullptr, adaptive_decoder(p, block_size), block_crc);
 }
 
 int redux_decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
                         uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
                         int32_t *block_status)
 {
-    return decode_blocks_host(check_params(p), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
-                              out_sizes, block_status, nullptr, adaptive_decoder(p, block_size));
+    return redux_decode_blocks_crc(p, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr);
 }
 
 int redux_decompress(const redux_params *p, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
@@ -1706,23 +1765,38 @@ int redux_static_table(const redux_params *p, const uint8_t *in, uint64_t in_len
     return redux_static_table_from_counts(p, counts, total, cum);
 }
 
-int redux_static_encode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
-                               uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+int redux_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                   uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                                   uint32_t *block_crc)
 {
     int st = static_check(p, cum);
     if (st != REDUX_OK)
         return st;
     if (block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, static_encoder(p, cum, block_size)); // redux_host.hpp
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, static_encoder(p, cum, block_size),
+                               block_crc); // redux_host.hpp
+}
+
+int redux_static_encode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                               uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    return redux_static_encode_blocks_crc(p, cum, in, in_len, block_size, out, out_cap, out_offsets, block_status, nullptr);
+}
+
+int redux_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
+                                   uint64_t nblocks, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
+                                   int32_t *block_status, uint32_t *block_crc)
+{
+    return decode_blocks_host(static_check(p, cum), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
+                              out_sizes, block_status, nullptr, static_decoder(p, cum, block_size), block_crc);
 }
 
 int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
                                uint64_t nblocks, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
                                int32_t *block_status)
 {
-    return decode_blocks_host(static_check(p, cum), in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap,
-                              out_sizes, block_status, nullptr, static_decoder(p, cum, block_size));
+    return redux_static_decode_blocks_crc(p, cum, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr);
 }
 
 // ---- byte-plane layout (redux_planes.hpp) ---------------------------------------------------------
@@ -1821,8 +1895,9 @@ int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void 
     return redux_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream);
 }
 
-int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
-                               uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+int redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                   uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                                   uint32_t *block_crc)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
@@ -1830,17 +1905,65 @@ int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
     const host::EncodeCoder coder = element_size > 1 ? planes_encoder(p, block_size, element_size) : adaptive_encoder(p, block_size);
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder); // redux_host.hpp
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc); // redux_host.hpp
 }
 
-int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
-                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
+int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status)
+{
+    return redux_encode_blocks_planes_crc(p, in, in_len, block_size, element_size, out, out_cap, out_offsets, block_status, nullptr);
+}
+
+int redux_decode_blocks_planes_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                                   uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                                   uint32_t *block_crc)
 {
     int st = check_params(p);
     if (st == REDUX_OK && redux_planes_check(element_size) != REDUX_OK)
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, planes_decoder(p, block_size, element_size));
+                              block_status, nullptr, planes_decoder(p, block_size, element_size), block_crc);
+}
+
+int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
+{
+    return redux_decode_blocks_planes_crc(p, in, in_offsets, out_len, block_size, element_size, out, out_sizes, block_status, nullptr);
+}
+
+// ---- per-block CRC-32 (redux_crc.hpp) -------------------------------------------------------------
+int redux_crc32_blocks_dev(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_crc, void *stream)
+{
+    if (block_size == 0 || !d_crc || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    return launch_crc32(d_in, in_len, nullptr, redux_block_count(in_len, block_size), block_size, d_crc, (hipStream_t)stream);
+}
+
+int redux_crc32_sizes_dev(const void *d_in, uint64_t nblocks, uint32_t block_size, const void *d_sizes, void *d_crc, void *stream)
+{
+    if (block_size == 0 || (nblocks && (!d_in || !d_sizes || !d_crc)))
+        return REDUX_INVALID_INPUT;
+    return launch_crc32(d_in, 0, d_sizes, nblocks, block_size, d_crc, (hipStream_t)stream);
+}
+
+uint32_t redux_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2)
+{
+    uint32_t p = 0x80000000u, sq = 0x80000000u; // x^0; then sq = x^(8 * 2^k)
+    for (int i = 0; i < 8; i++)
+        sq = crc_mulx(sq);
+    for (; len2; len2 >>= 1) {
+        if (len2 & 1)
+            p = crc_mulmod(sq, p);
+        sq = crc_mulmod(sq, sq);
+    }
+    return crc_mulmod(p, crc1) ^ crc2;
+}
+
+int redux_crc32_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t *crc)
+{
+    if (block_size == 0 || !crc || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::crc32_blocks(in, in_len, block_size, crc); // redux_host.hpp
 }
 
 int redux_host_release(void) { return host::ctx_release_all(); }

@@ -139,13 +139,14 @@ struct Buf {
 };
 
 struct Slot {          // one chunk in flight
-    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab;                  // device
-    Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}; // pinned mirrors of the small arrays
-    hipEvent_t done = nullptr;                                                       // recorded after the chunk's kernels
+    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab, d_crc;                       // device
+    Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}, h_crc{true}; // pinned mirrors of the small arrays
+    hipEvent_t done = nullptr;                                                                    // recorded after the chunk's kernels
 
-    std::array<Buf *, 15> bufs()
+    std::array<Buf *, 17> bufs()
     {
-        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab};
+        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &d_crc,
+                &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab, &h_crc};
     }
 };
 
@@ -679,6 +680,9 @@ struct DecodeCoder {
     std::function<uint64_t(uint64_t cb)> workspace; // bytes for chunks of at most cb blocks
     // nb streams in s.d_in (offsets s.d_off) -> out_bytes bytes in s.d_out, s.d_sz, s.d_st, s.d_sum; d_in_used may be null
     std::function<int(Slot &s, uint64_t nb, uint64_t out_bytes, void *d_in_used, void *ws, uint64_t ws_bytes, hipStream_t st)> launch;
+    // where block b of s.d_out is: false = at b * block_size, s.d_sz[b] bytes; true = out_bytes of original-order bytes, cut
+    // into blocks of block_size (the byte-plane layout, after its inverse transform)
+    bool original_order = false;
 };
 
 // ================================================================================================
@@ -693,6 +697,7 @@ struct EncodeChunks {
     uint64_t          *out_offsets;
     int32_t           *block_status;
     const EncodeCoder &coder;
+    uint32_t          *block_crc; // may be null: CRC-32 of each input block (redux_crc.hpp), on the staged chunk
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -711,8 +716,9 @@ struct EncodeChunks {
     }
     int grow(Ctx &c, Slot &s) const
     {
-        return grow_bufs(c, {{&s.d_in, max_in + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (cb + 1) * 8},
-                             {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
+        const int rc = grow_bufs(c, {{&s.d_in, max_in + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (cb + 1) * 8},
+                                     {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
+        return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
     {
@@ -720,12 +726,17 @@ struct EncodeChunks {
     }
     int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
     {
+        if (block_crc) { // the staged input, before any transform
+            const int rc = redux_crc32_blocks_dev(s.d_in.p, len_of(b0, nb), block_size, s.d_crc.p, st);
+            if (rc != REDUX_OK)
+                return rc;
+        }
         return coder.launch(s, len_of(b0, nb), bound, slot_ws(s), ws_bytes, st);
     }
     bool fetch(Slot &s, hipStream_t st, uint64_t nb) const
     {
         return fetch_small(s.h_off, s.d_off, (nb + 1) * 8, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
-               fetch_small(s.h_sum, s.d_sum, 8, st);
+               fetch_small(s.h_sum, s.d_sum, 8, st) && (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st));
     }
     Placed place(Ctx &c, Slot &s, uint64_t k, uint64_t b0, uint64_t nb, Ledger &L) const
     {
@@ -744,14 +755,16 @@ struct EncodeChunks {
             out_offsets[b0 + i] = *base + ho[i]; // (entry b0 + nb is written again, with the same value, by the next chunk)
         if (block_status)
             memcpy(block_status + b0, s.h_st.p, nb * 4);
+        if (block_crc)
+            memcpy(block_crc + b0, s.h_crc.p, nb * 4);
         return {};
     }
 };
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
-                         uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder)
+                         uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr)
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc};
     return run_chunks(op);
 }
 
@@ -769,6 +782,7 @@ struct DecodeChunks {
     int32_t           *block_status;
     uint64_t          *in_used;
     const DecodeCoder &coder;
+    uint32_t          *block_crc; // may be null: CRC-32 of what each block decoded to (redux_crc.hpp), on the chunk's output
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -793,9 +807,10 @@ struct DecodeChunks {
     int grow(Ctx &c, Slot &s) const
     {
         const uint64_t used = in_used ? cb * 8 : 8;
-        return grow_bufs(c, {{&s.d_in, max_in + 32}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, cb * (uint64_t)block_size + 16},
-                             {&s.d_off, (cb + 1) * 8}, {&s.d_sz, cb * 4}, {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.d_used, used},
-                             {&s.h_off, (cb + 1) * 8}, {&s.h_sz, cb * 4}, {&s.h_st, cb * 4}, {&s.h_sum, 8}, {&s.h_used, used}});
+        const int      rc   = grow_bufs(c, {{&s.d_in, max_in + 32}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, cb * (uint64_t)block_size + 16},
+                                            {&s.d_off, (cb + 1) * 8}, {&s.d_sz, cb * 4}, {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.d_used, used},
+                                            {&s.h_off, (cb + 1) * 8}, {&s.h_sz, cb * 4}, {&s.h_st, cb * 4}, {&s.h_sum, 8}, {&s.h_used, used}});
+        return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
     {
@@ -813,12 +828,17 @@ struct DecodeChunks {
     }
     int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
     {
-        return coder.launch(s, nb, chunk_out(b0, nb), in_used ? s.d_used.p : nullptr, slot_ws(s), ws_bytes, st);
+        const int rc = coder.launch(s, nb, chunk_out(b0, nb), in_used ? s.d_used.p : nullptr, slot_ws(s), ws_bytes, st);
+        if (rc != REDUX_OK || !block_crc)
+            return rc;
+        return coder.original_order ? redux_crc32_blocks_dev(s.d_out.p, chunk_out(b0, nb), block_size, s.d_crc.p, st)
+                                    : redux_crc32_sizes_dev(s.d_out.p, nb, block_size, s.d_sz.p, s.d_crc.p, st);
     }
     bool fetch(Slot &s, hipStream_t st, uint64_t nb) const
     {
         return fetch_small(s.h_sz, s.d_sz, nb * 4, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
-               fetch_small(s.h_sum, s.d_sum, 8, st) && (!in_used || fetch_small(s.h_used, s.d_used, nb * 8, st));
+               fetch_small(s.h_sum, s.d_sum, 8, st) && (!in_used || fetch_small(s.h_used, s.d_used, nb * 8, st)) &&
+               (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st));
     }
     Placed place(Ctx &c, Slot &s, uint64_t, uint64_t b0, uint64_t nb, Ledger &) const
     {
@@ -831,14 +851,17 @@ struct DecodeChunks {
             memcpy(block_status + b0, s.h_st.p, nb * 4);
         if (in_used)
             memcpy(in_used + b0, s.h_used.p, nb * 8);
+        if (block_crc)
+            memcpy(block_crc + b0, s.h_crc.p, nb * 4);
         return {};
     }
 };
 
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
-                         uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder)
+                         uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
+                         uint32_t *block_crc = nullptr)
 {
-    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder};
+    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc};
     return run_chunks(op);
 }
 
@@ -890,6 +913,55 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
             rc = REDUX_IO_ERROR;
     if (rc == REDUX_OK && hipMemcpy(counts, c.d_counts.p, 256 * 8, hipMemcpyDeviceToHost) != hipSuccess)
         rc = REDUX_IO_ERROR;
+    ctx_trim_locked(c);
+    return rc;
+}
+
+// ================================================================================================
+// per-block CRC-32 of host memory (redux_crc32_blocks)
+//
+// As byte_histogram: the CURRENT device's context, chunks of whole blocks staged through the pinned ring, chunk j on stream
+// and slot j % kSlots (stream order keeps a slot's staging behind the kernel that read its previous chunk), each chunk's
+// k_crc32 into the slot's d_crc and its CRCs copied straight into the caller's array on the same stream.
+// ================================================================================================
+static int crc32_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t *crc)
+{
+    Ctx *cp  = nullptr;
+    int  dev = 0;
+    int  rc  = ctx_of_current_device(&cp, &dev);
+    if (rc != REDUX_OK)
+        return rc;
+    Ctx                        &c = *cp;
+    std::lock_guard<std::mutex> l(c.mu);
+    c.want = dev;
+    if ((rc = ctx_init_locked(c)) != REDUX_OK)
+        return rc;
+    const uint64_t nblocks = redux_block_count(in_len, block_size);
+    uint64_t       cb      = clamp_chunk_bytes((in_len + kSlots - 1) / kSlots, kEncChunkMax) / block_size;
+    cb                     = cb < 1 ? 1 : cb;
+    const uint64_t nchunks = (nblocks + cb - 1) / cb, chunk = cb * block_size;
+    const int      nslots  = (int)(nchunks < (uint64_t)kSlots ? nchunks : (uint64_t)kSlots);
+    for (int i = 0; i < nslots; i++)
+        if ((rc = grow_bufs(c, {{&c.slot[i].d_in, (chunk < in_len ? chunk : in_len) + 16}, {&c.slot[i].d_crc, cb * 4}})) != REDUX_OK)
+            return rc;
+    {
+        CopyPool pool(kCopyThreads - 1);
+        uint64_t piece_no = 0;
+        for (uint64_t j = 0; j < nchunks && rc == REDUX_OK; j++) {
+            const uint64_t o = j * chunk, n = in_len - o < chunk ? in_len - o : chunk, b0 = j * cb;
+            const uint64_t nb = nblocks - b0 < cb ? nblocks - b0 : cb;
+            hipStream_t    st = c.stream[j % kStreams];
+            Slot          &s  = c.slot[j % kSlots];
+            rc = stage_h2d(c, pool, piece_no, s.d_in.p, in + o, n, st);
+            if (rc == REDUX_OK)
+                rc = redux_crc32_blocks_dev(s.d_in.p, n, block_size, s.d_crc.p, st);
+            if (rc == REDUX_OK && hipMemcpyAsync(crc + b0, s.d_crc.p, nb * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+                rc = REDUX_IO_ERROR;
+        }
+    }
+    for (int i = 0; i < kStreams; i++) // nothing of this call stays in flight
+        if (hipStreamSynchronize(c.stream[i]) != hipSuccess && rc == REDUX_OK)
+            rc = REDUX_IO_ERROR;
     ctx_trim_locked(c);
     return rc;
 }

@@ -66,6 +66,25 @@ extern "C" {
     fn redux_static_decode_blocks(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
                                   nblocks: u64, block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32,
                                   block_status: *mut i32) -> c_int;
+    fn redux_crc32_combine(crc1: u32, crc2: u32, len2: u64) -> u32;
+    fn redux_crc32_blocks(input: *const u8, in_len: u64, block_size: u32, crc: *mut u32) -> c_int;
+    fn redux_encode_blocks_crc(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, out: *mut u8,
+                               out_cap: u64, out_offsets: *mut u64, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_crc(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, nblocks: u64,
+                               block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32, block_status: *mut i32,
+                               block_crc: *mut u32) -> c_int;
+    fn redux_encode_blocks_planes_crc(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32,
+                                      element_size: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                      block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_planes_crc(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                      block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
+                                      block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_static_encode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_len: u64,
+                                      block_size: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                      block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_static_decode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
+                                      nblocks: u64, block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32,
+                                      block_status: *mut i32, block_crc: *mut u32) -> c_int;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
