@@ -367,6 +367,49 @@ int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status);
 
+/* ---- stored blocks -----------------------------------------------------------------------------
+ * A block whose stream does not shrink it can travel as its raw bytes instead (zstd raw blocks, deflate stored blocks).
+ * Block b has L_b = min(B, len - b*B) bytes of coder input x' (the input for element_size 1, its byte-plane layout for
+ * E = 2, 4, 8: a stored plane is plane bytes) and a stream of s_b bytes.  With store_ratio t, 0 <= t <= 65536:
+ *     stored_b  <=>  status_b == OK  and  s_b * 65536 >= t * L_b      (exact, 64-bit)
+ * and payload_b = x'[b*B .. b*B + L_b) if stored_b, else the stream the plain / planes call writes, unchanged.  So
+ * t = 65536 stores exactly the blocks that do not shrink (the output is never larger than the input plus its tables, and
+ * costs no ratio on any input), t = 0 stores every block (an empty input's one block: a 0-byte payload).  t > 65536 is
+ * INVALID_INPUT.  Flags are u8, 0 (coded) or 1 (stored), one per block.  Streams and flags depend on neither the chunk
+ * size nor the devices.
+ * Coverage: the adaptive model with symbol_bits 8 and code_bits <= 32 (the parameters of the `_v` calls); other valid
+ * parameters are UNSUPPORTED.  Not available for the static-table model, the `_v` calls and redux_compress / decompress.
+ *
+ * redux_encode_stored_workspace_bytes  what redux_encode_stored_dev needs (the planes call's workspace); 0 if unsupported.
+ * redux_decode_stored_workspace_bytes  what redux_decode_stored_dev needs for out_len bytes; 0 if unsupported.
+ * redux_encode_stored_dev   the coder over x', then the rule (k_store_select): d_stored[b] is written, a stored block's
+ *                           payload is x' itself and d_out_offsets counts its L_b bytes.  out_cap as in the plain call
+ *                           (a block that does not fit is reported OUTPUT_TOO_SMALL and never written).
+ * redux_decode_stored_dev   the inverse: nblocks = redux_block_count(out_len, B); out[0 .. out_len) in original order.  The
+ *                           coded blocks decode through the table form of the adaptive decoders, the stored payloads are
+ *                           copied.  Block b must come back as L_b bytes (for E > 1: its place in the frame layout): an OK
+ *                           block of another length is INVALID_INPUT, a stored payload longer than L_b OUTPUT_TOO_SMALL
+ *                           (size 0, nothing written), a flag other than 0 / 1 INVALID_INPUT.  d_summary (if given) is
+ *                           overwritten with the failing blocks only.  out_cap must be >= out_len.
+ * redux_encode_blocks_stored / redux_decode_blocks_stored  host-pointer forms through the chunk pipeline; the flags
+ *                           travel per chunk as the CRCs do (block_crc may be NULL, as in the `_crc` calls). */
+uint64_t redux_encode_stored_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_stored_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            uint32_t store_ratio, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                            void *d_stored /* u8[nblocks] */, void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */,
+                            const void *d_stored /* u8[nblocks] */, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_sizes /* u32[nblocks] */, void *d_block_status,
+                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_stored(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint32_t store_ratio, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, uint8_t *stored,
+                               int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_stored(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *stored,
+                               uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                               uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* ---- per-block CRC-32 checksums ---------------------------------------------------------------
  * crc[b] = CRC-32/ISO-HDLC -- the zlib / gzip / PNG CRC (reflected polynomial 0xEDB88320, init and xorout 0xFFFFFFFF),
  * zlib.crc32 -- of the ORIGINAL, uncompressed bytes x[b*B .. min((b+1)*B, len)), B = block_size.  The same for every model

@@ -10,5 +10,5 @@ from .api import (  # noqa: F401
     compress, decompress, compress_blocks, decompress_blocks, compress_blocks_v, decompress_blocks_v, block_table_v, BLOCK_DTYPE, BLOCK_IDLE,
     host_set_devices, host_chunk_plan, host_set_chunk_bytes,
     DeviceEncoder, DeviceDecoder, DeviceStaticCoder, planes, gen_iid, gen_zipf, zipf_thresholds, version,
-    crc32_blocks, crc32_combine,
+    crc32_blocks, crc32_combine, STORE_RATIO,
 )

@@ -85,6 +85,12 @@ SIGNATURES = {
     "redux_decode_blocks_planes_crc": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_static_encode_blocks_crc": (C.c_int, [_PP, C.POINTER(_U32), _V, _U64, _U32, _V, _U64, _V, _V, _V]),
     "redux_static_decode_blocks_crc": (C.c_int, [_PP, C.POINTER(_U32), _V, _V, _U64, _U32, _V, _U64, _V, _V, _V]),
+    "redux_encode_stored_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_stored_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_stored_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _V, _U64, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_stored_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_stored": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _V, _U64, _V, _V, _V, _V]),
+    "redux_decode_blocks_stored": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_planes_check": (C.c_int, [_U32]),
     "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

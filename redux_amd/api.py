@@ -242,15 +242,32 @@ def _crc_out(block_crc, nb):
     return block_crc.ctypes.data if nb else None
 
 
-def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None):
+STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
+
+
+def _stored_arg(stored, nb, writable):
+    """the caller's stored= flags (np.uint8[nblocks]; filled in place on encode) -> its pointer"""
+    if not isinstance(stored, np.ndarray) or stored.dtype != np.uint8 or stored.shape != (nb,) \
+            or not stored.flags.c_contiguous or (writable and not stored.flags.writeable):
+        raise InvalidInput()
+    return stored.ctypes.data
+
+
+def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
+                    store_ratio=STORE_RATIO):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
     layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
     params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks); no element_size.
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 (zlib.crc32) of every input block, in original
-    byte order for every layout (the `_crc` calls of include/redux_hip.h)."""
+    byte order for every layout (the `_crc` calls of include/redux_hip.h).
+    stored: a np.uint8[nblocks] the same call fills with the stored-block flags (include/redux_hip.h, "stored blocks"):
+    passing it turns stored blocks on, and block b's payload is then its raw (planes: plane) bytes wherever its stream
+    is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it."""
     if isinstance(params, StaticModel):
+        if stored is not None:
+            raise InvalidInput()  # (the static decoder has no table form)
         return _compress_blocks_static(data, block_size, params, element_size, block_crc)
     P = _params_of(params)
     a = _u8(data)
@@ -266,7 +283,12 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
     crc = _crc_out(block_crc, nb)
-    if block_crc is not None:
+    if stored is not None:
+        if not isinstance(store_ratio, (int, np.integer)) or not 0 <= store_ratio < 1 << 32:
+            raise InvalidInput()
+        st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
+                                          offs.ctypes.data, _stored_arg(stored, nb, True), status.ctypes.data, crc)
+    elif block_crc is not None:
         st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
                                               offs.ctypes.data, status.ctypes.data, crc)
     elif E == 1:
@@ -327,7 +349,7 @@ def _decompress_blocks_static(streams, offsets, block_size, model, check, elemen
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None):
+                      block_crc=None, stored=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -335,7 +357,14 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     (frames with a damaged block hold undefined bytes; their blocks' status says which).
     params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks).
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
-    order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK."""
+    order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK.
+    stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
+    uint8[length] in original order, as with element_size > 1."""
+    if stored is not None:
+        if isinstance(params, StaticModel) or length is None:
+            raise InvalidInput()
+        return _decompress_blocks_stored(streams, offsets, block_size, params, check, _check_element_size(element_size),
+                                         int(length), block_crc, stored)
     if isinstance(params, StaticModel):
         return _decompress_blocks_static(streams, offsets, block_size, params, check, element_size, length, block_crc)
     E = _check_element_size(element_size)
@@ -386,6 +415,28 @@ def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, le
     else:
         st = L.redux_decode_blocks_planes(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
                                           sizes.ctypes.data, status.ctypes.data)
+    if check:
+        _raise(st)
+    return out[:length], sizes, status
+
+
+def _decompress_blocks_stored(streams, offsets, block_size, params, check, E, length, block_crc, stored):
+    P = _params_of(params)
+    a = _u8(streams)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    L = _lib.lib()
+    if block_size <= 0 or length < 0 or len(offs) != L.redux_block_count(length, block_size) + 1 or int(offs[-1]) > len(a) \
+            or bool((offs[1:] < offs[:-1]).any()):
+        raise InvalidInput()
+    cp = P._c()
+    _raise(L.redux_device_supports(C.byref(cp)))
+    nb = len(offs) - 1
+    flags = _stored_arg(stored, nb, False)
+    out = np.empty(max(length, 1), dtype=np.uint8)
+    sizes = np.zeros(nb, dtype=np.uint32)
+    status = np.zeros(nb, dtype=np.int32)
+    st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
+                                      out.size, sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
     if check:
         _raise(st)
     return out[:length], sizes, status

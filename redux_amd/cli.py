@@ -1,7 +1,7 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
-                            [--model adaptive|static] [--checksum]
+                            [--model adaptive|static] [--checksum] [--stored]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -18,12 +18,15 @@ reference's model.  Decoding reads the model from the container.
 (version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
 damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
 table: `--checksum` with `--block-size 0` is a usage error.
+`--stored` (with -c and a block size, adaptive model) writes a block whose stream would not be smaller than the block as
+its raw bytes (container flag 0x40): incompressible data then costs no more than its own size plus the tables, and
+decodes as a copy.  -d reads any stored container.  `--stored` with `--block-size 0` or `--model static` is a usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static>] [--checksum]")
+         "[--model <adaptive|static>] [--checksum] [--stored]")
 
 
 def parse(argv):
@@ -34,6 +37,8 @@ def parse(argv):
             opts["compress"] = True
         elif arg == "--checksum":
             opts["checksum"] = True
+        elif arg == "--stored":
+            opts["stored"] = True
         elif arg == "-d":
             opts["compress"] = False
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model"):
@@ -67,6 +72,8 @@ def parse(argv):
         return None  # the table lives in the container (not in a raw stream), and there is one table, not one per plane
     if opts.get("checksum") and opts["compress"] and opts["block_size"] == 0:
         return None  # the table lives in the container (-d verifies whatever table a container has)
+    if opts.get("stored") and opts["compress"] and (opts["block_size"] == 0 or opts.get("model") == "static"):
+        return None  # the bitmap lives in the container, and the static decoder has no table form
     return None if opts["compress"] is None else opts
 
 
@@ -96,7 +103,8 @@ def main(argv=None):
                 sink.write(o.getvalue())
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
-                                                opts.get("model", "adaptive"), opts.get("checksum", False))
+                                                opts.get("model", "adaptive"), opts.get("checksum", False),
+                                                opts.get("stored", False))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

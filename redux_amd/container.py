@@ -15,6 +15,7 @@ Layout (little-endian):
    (version 3 only) 4*258  the static table cum[0..=257], u32
    ..  4*nblocks   compressed size of each block
    (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
+   (flag 0x40 only) ceil(nblocks/8)  stored-block bitmap: bit b % 8 of byte b // 8 (LSB first) = block b is stored
    ..  payloads, concatenated in block order
 
 Version 2 is the same layout for data coded with the byte-plane layout of typed data (include/redux_hip.h): the payloads
@@ -31,6 +32,12 @@ every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_by
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
 right length and is caught only here.  Any other high bit is InvalidInput, a truncated table Eof.  Without checksums the
 writers emit exactly the bytes they emitted before the flag existed.
+
+Bit 0x40 (versions 0x41 / 0x42, with checksums 0x51 / 0x52) means stored blocks (include/redux_hip.h, "stored blocks"): a
+bitmap of the blocks whose payload is their raw coder input -- the bytes themselves, or for version 2 their plane -- follows
+the size table and the CRC table.  A stored block's size entry must be its raw length min(B, total - b*B), and the bitmap's
+padding bits must be 0 (else InvalidInput); a truncated bitmap is Eof.  The static-table model (version 3) has no stored
+blocks.  Without stored=True the writers emit exactly the bytes they emitted before the flag existed.
 """
 import struct
 
@@ -44,6 +51,7 @@ VERSION_PLANES = 2
 VERSION_STATIC = 3
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
 CRC_FLAG = 0x10  # version bit: a table of per-block CRC-32 values follows the size table
+STORED_FLAG = 0x40  # version bit: a stored-block bitmap follows the size table (and the CRC table)
 ELEMENT_SIZES = (2, 4, 8)  # what version 2 may record
 HEADER = struct.Struct("<4sBBBBIIQQ")
 # A header field, not a promise: a crafted 40-byte file must not make the decoder allocate
@@ -52,10 +60,17 @@ HEADER = struct.Struct("<4sBBBBIIQQ")
 MAX_BLOCK_SIZE = 1 << 30
 
 
-def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None):
+def _raw_lengths(nblocks, block_size, total):
+    """L_b = min(B, total - b*B): the bytes of each block (0 for an empty input's one block)"""
+    o = np.arange(nblocks, dtype=np.int64) * block_size
+    return np.clip(total - o, 0, block_size)
+
+
+def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
-    block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table."""
+    block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
+    stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap."""
     if element_size != 1 and element_size not in ELEMENT_SIZES:
         raise api.InvalidInput()
     static = isinstance(params, api.StaticModel)
@@ -74,20 +89,30 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
             raise api.InvalidInput()
         ver |= CRC_FLAG
         crc = c.astype("<u4").tobytes()
+    bitmap = b""
+    if stored is not None:
+        f = np.asarray(stored)
+        if static or f.shape != (len(sizes),) or bool((f > 1).any()) \
+                or bool((sizes[f == 1] != _raw_lengths(len(sizes), block_size, total_len)[f == 1]).any()):
+            raise api.InvalidInput()
+        ver |= STORED_FLAG
+        bitmap = np.packbits(f.astype(np.uint8), bitorder="little").tobytes()
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if static:
         head += params.cum.astype("<u4").tobytes()
-    return head + sizes.astype("<u4").tobytes() + crc + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
+    return head + sizes.astype("<u4").tobytes() + crc + bitmap + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
 
 def _version_ok(ver, res):
-    ver &= ~CRC_FLAG
+    if ver & STORED_FLAG and _layout(ver) not in (VERSION, VERSION_PLANES):
+        return False
+    ver = _layout(ver)
     return (ver in (VERSION, VERSION_STATIC) and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)
 
 
 def _layout(ver):
-    """the version without its checksum flag"""
-    return ver & ~CRC_FLAG
+    """the version without its checksum and stored-block flags"""
+    return ver & ~(CRC_FLAG | STORED_FLAG)
 
 
 def unpack(buf):
@@ -116,6 +141,18 @@ def unpack(buf):
         end_sizes += 4 * nblocks
         if len(b) < end_sizes:
             raise api.Eof()
+    if ver & STORED_FLAG:
+        nbytes = (nblocks + 7) // 8
+        if len(b) < end_sizes + nbytes:
+            raise api.Eof()
+        bits = np.frombuffer(b, dtype=np.uint8, count=nbytes, offset=end_sizes)
+        flags = np.unpackbits(bits, bitorder="little")
+        if bool(flags[nblocks:].any()):  # padding bits
+            raise api.InvalidInput()
+        flags = flags[:nblocks].astype(bool)
+        if bool((sizes[flags] != _raw_lengths(nblocks, block_size, total)[flags].astype(np.uint64)).any()):
+            raise api.InvalidInput()
+        end_sizes += nbytes
     if len(b) < end_sizes + int(offsets[-1]):
         raise api.Eof()
     payload = np.frombuffer(b, dtype=np.uint8, count=int(offsets[-1]), offset=end_sizes)
@@ -133,6 +170,20 @@ def block_crcs(buf):
     nblocks = HEADER.unpack_from(b, 0)[7]
     start = HEADER.size + (TABLE if _layout(ver) == VERSION_STATIC else 0) + 4 * nblocks
     return np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint32)
+
+
+def block_stored(buf):
+    """The stored-block flags (np.uint8[nblocks] of 0 / 1) a flagged container (0x41 / 0x42 / 0x51 / 0x52) records; None
+    without the flag.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    b = memoryview(buf)
+    unpack(b)  # (every check of the bitmap included)
+    ver = b[4]
+    if not ver & STORED_FLAG:
+        return None
+    nblocks = HEADER.unpack_from(b, 0)[7]
+    start = HEADER.size + 4 * nblocks * (2 if ver & CRC_FLAG else 1)
+    bits = np.frombuffer(b, dtype=np.uint8, count=(nblocks + 7) // 8, offset=start)
+    return np.unpackbits(bits, bitorder="little")[:nblocks].astype(np.uint8)
 
 
 def element_size(buf):
@@ -193,15 +244,22 @@ def header_is_wellformed(buf):
     return nblocks == (1 if total == 0 else (total + block_size - 1) // block_size)
 
 
-def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False):
+def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
+                   stored=False):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
-    checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call."""
+    checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
+    stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with model "static"."""
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
-            or model not in ("adaptive", "static") or (model == "static" and element_size != 1):
+            or model not in ("adaptive", "static") or (model == "static" and (element_size != 1 or stored)):
         raise api.InvalidInput()
-    crc = np.zeros(max(1, -(-len(data) // block_size)), dtype=np.uint32) if checksum else None
+    nb = max(1, -(-len(data) // block_size))
+    crc = np.zeros(nb, dtype=np.uint32) if checksum else None
     kw = {} if crc is None else {"block_crc": crc}
+    if stored:
+        flags = np.zeros(nb, dtype=np.uint8)
+        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size, stored=flags, **kw)
+        return pack(out, offs, params, block_size, len(data), element_size, block_crc=crc, stored=flags)
     if model == "static":
         m = api.StaticModel.from_data(data, params)
         out, offs, _ = api.compress_blocks(data, block_size, m, **kw)
@@ -226,15 +284,18 @@ def decompress_bytes(buf):
     # so only the declared total bounds the capacity; but every block's stream has at least one
     # byte, so a header that declares more blocks than there are payload bytes is malformed.
     nb = len(offsets) - 1
-    if len(payload) < nb:
+    flags = block_stored(buf)
+    if len(payload) < nb - (0 if flags is None else int(flags.sum())):  # (a stored block may be empty; a stream is not)
         raise api.InvalidInput()
     E = element_size(buf)
     cum = static_table(buf)
     want = block_crcs(buf)
     got = None if want is None else np.zeros(nb, dtype=np.uint32)
     kw = {} if got is None else {"block_crc": got}
+    if flags is not None:
+        kw["stored"] = flags
     model = P if cum is None else api.StaticModel(P, cum)
-    if E > 1:  # (frames are E * block_size bytes: the blocks decode at their real size, into out[0 .. total))
+    if E > 1 or flags is not None:  # (the blocks decode at their real size, into out[0 .. total))
         try:
             out, sizes, status = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total, **kw)
         except MemoryError:

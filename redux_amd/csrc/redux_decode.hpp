@@ -115,6 +115,8 @@ __global__ void __launch_bounds__(64) k_decode(DecArgs a)
     const uint32_t lane = threadIdx.x;
     const uint64_t slot = (uint64_t)blockIdx.x * 64 + lane;
     const bool     live = slot < a.nblocks && !(a.table && a.table[slot].index == 0xFFFFFFFFu /* idle entry */);
+    if (a.table && __builtin_amdgcn_ballot_w64(live) == 0) // a wave of idle entries (a stored-block table's end) does nothing
+        return;
     uint64_t       blk = slot, dst_off = slot * (uint64_t)a.block_size;
     uint32_t       capn = a.block_size;
     if (a.table && live) { // block table: see DecArgs

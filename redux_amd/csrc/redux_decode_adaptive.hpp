@@ -152,6 +152,8 @@ __device__ __forceinline__ void decode_adaptive_body(const DecArgs &a, uint32_t 
     const uint32_t lane = threadIdx.x;
     const uint64_t slot = (uint64_t)blockIdx.x * 64 + lane;
     const bool     live = slot < a.nblocks && !(a.table && a.table[slot].index == 0xFFFFFFFFu /* idle entry */);
+    if (a.table && __builtin_amdgcn_ballot_w64(live) == 0) // a wave of idle entries (a stored-block table's end) does nothing
+        return;
 
     AdTree A;
     A.init(lds, lane);

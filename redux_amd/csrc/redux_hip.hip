@@ -13,6 +13,7 @@
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
+//   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -33,6 +34,7 @@
 #include "redux_planes.hpp"
 #include "redux_hist.hpp"
 #include "redux_crc.hpp"
+#include "redux_store.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -879,7 +881,8 @@ int redux_encode_slots_dev(const redux_params *p, const void *d_in, uint64_t in_
 // scan + gather of the slots a coder kernel left in the workspace laid out by g
 static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status,
                         void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream,
-                        const redux_block *d_table = nullptr, uint64_t nblocks_real = 0)
+                        const redux_block *d_table = nullptr, uint64_t nblocks_real = 0, const uint8_t *d_stored = nullptr,
+                        const void *d_raw = nullptr, uint32_t block_size = 0)
 {
     if (!d_workspace || !d_block_status || !d_out_offsets || !d_out)
         return REDUX_INVALID_INPUT;
@@ -911,6 +914,9 @@ static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *
     ca.mode       = (const uint32_t *)(ws + g.off_mode);
     ca.cap_rows   = (uint32_t)(g.slot_bytes / 4);
     ca.table      = d_table;
+    ca.stored     = d_stored;
+    ca.raw        = (const uint8_t *)d_raw;
+    ca.block_size = block_size;
     k_compact<<<(uint32_t)g.nblocks, 256, 0, s>>>(ca);
     if (!g.any && !g.gen && (g.u16 || g.coop)) { // (every launch that may have left row-major group areas: the kernel reads the mode word)
         const uint32_t tiles = (ca.cap_rows + kTileRows - 1) / kTileRows + 1;
@@ -1100,7 +1106,8 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
                                   uint32_t block_size, void *d_out, uint64_t out_cap, void *d_out_sizes,
                                   void *d_block_status, void *d_summary, void *d_workspace,
                                   uint64_t workspace_bytes, void *stream, void *d_in_used,
-                                  const redux_block *d_table = nullptr, bool tbl_aligned16 = false, uint64_t nblocks_real = 0)
+                                  const redux_block *d_table = nullptr, bool tbl_aligned16 = false, uint64_t nblocks_real = 0,
+                                  bool table_trusted = false)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
@@ -1216,7 +1223,7 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
     const uint32_t rc_n = dec_rc_entries(g);
     k_fill_rc<<<(rc_n + 255) / 256, 256, 0, s>>>((double *)d_workspace, rc_n);
     const uint32_t *table_failed = nullptr;
-    if (d_table) { // caller data: the kernels read a checked copy (redux_table.hpp)
+    if (d_table && !table_trusted) { // caller data: the kernels read a checked copy (redux_table.hpp)
         uint8_t *wt = (uint8_t *)d_workspace + align_up((uint64_t)rc_n * 8, 256);
         TableCheckArgs ta;
         ta.in         = d_table;
@@ -1375,7 +1382,8 @@ static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *c
 // blocks decode to out_len bytes (nblocks * block_size, or exactly out_len in the planes layout) in out[0 .. out_cap).
 static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
-                              uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr)
+                              uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr,
+                              const uint8_t *stored = nullptr)
 {
     if (params != REDUX_OK)
         return params;
@@ -1388,7 +1396,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
     return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
-                               block_crc); // redux_host.hpp
+                               block_crc, stored); // redux_host.hpp
 }
 
 int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
@@ -1929,6 +1937,188 @@ int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const u
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
 {
     return redux_decode_blocks_planes_crc(p, in, in_offsets, out_len, block_size, element_size, out, out_sizes, block_status, nullptr);
+}
+
+// ---- stored blocks (redux_store.hpp) --------------------------------------------------------------
+// the adaptive model with 8-bit symbols and code_bits <= 32: the coders whose decoders have the table form
+static int stored_check(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0)
+        return REDUX_INVALID_INPUT;
+    return is_any(p) ? REDUX_UNSUPPORTED : REDUX_OK;
+}
+
+uint64_t redux_encode_stored_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (stored_check(p, block_size, element_size) != REDUX_OK)
+        return 0;
+    return redux_encode_planes_workspace_bytes(p, in_len, block_size, element_size);
+}
+
+// [plane buffer (E > 1)] [the coded blocks' table] [the adaptive decoder's workspace]
+static uint64_t store_table_bytes(uint64_t nblocks) { return align_up(nblocks * sizeof(redux_block), 256); }
+
+uint64_t redux_decode_stored_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    if (stored_check(p, block_size, element_size) != REDUX_OK)
+        return 0;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    return (element_size > 1 ? planes_copy_bytes(nblocks * (uint64_t)block_size) : 0) + store_table_bytes(nblocks) +
+           redux_decode_workspace_bytes(p, nblocks, block_size);
+}
+
+// the plain coder over x' (the input, or its layout at the front of the workspace), then the rule, then the scan and the
+// compaction, which copies x' for the stored blocks
+int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            uint32_t store_ratio, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_stored,
+                            void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = stored_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (store_ratio > kStoreRatioOne || !d_workspace || !d_stored || !d_block_status || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    hipStream_t    s    = (hipStream_t)stream;
+    const uint64_t copy = element_size > 1 ? planes_copy_bytes(in_len) : 0;
+    if (workspace_bytes < copy) // (the coder checks the rest: a workspace without the small-grid pairs area will do, geometry_ws)
+        return REDUX_OUTPUT_TOO_SMALL;
+    const void    *x    = d_in;
+    if (element_size > 1) {
+        if ((st = redux_planes_dev(d_in, d_workspace, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+            return st;
+        x = d_workspace;
+    }
+    uint8_t       *ws  = (uint8_t *)d_workspace + copy;
+    const uint64_t wsb = workspace_bytes - copy;
+    if ((st = encode_slots_impl(p, x, in_len, block_size, nullptr, 0, false, d_block_status, ws, wsb, stream)) != REDUX_OK)
+        return st;
+    const Geometry  g = geometry_ws(p, in_len, block_size, wsb);
+    StoreSelectArgs sa;
+    sa.status     = (const int32_t *)d_block_status;
+    sa.sizes      = (uint32_t *)(ws + g.off_sizes);
+    sa.stored     = (uint8_t *)d_stored;
+    sa.nblocks    = g.nblocks;
+    sa.in_len     = in_len;
+    sa.block_size = block_size;
+    sa.ratio      = store_ratio;
+    const uint64_t wgs = (g.nblocks + 255) / 256;
+    k_store_select<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>(sa);
+    HIP_TRY(hipGetLastError());
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, wsb, stream, nullptr, 0,
+                        (const uint8_t *)d_stored, x, block_size);
+}
+
+// coded blocks through the table form of the adaptive decoders, stored ones copied, into T (d_out, or the plane buffer);
+// then the length rule, the inverse layout and the summary
+int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_stored,
+                            uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap,
+                            void *d_out_sizes, void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes,
+                            void *stream)
+{
+    int st = stored_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_workspace || !d_in_offsets || !d_stored || !d_out_sizes || !d_block_status || (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    if (out_cap < out_len || workspace_bytes < redux_decode_stored_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (((uintptr_t)d_workspace) & 255)
+        return REDUX_INVALID_INPUT;
+    hipStream_t    s       = (hipStream_t)stream;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const uint64_t copy    = element_size > 1 ? planes_copy_bytes(nblocks * (uint64_t)block_size) : 0;
+    uint8_t       *t       = element_size > 1 ? (uint8_t *)d_workspace : (uint8_t *)d_out;
+    redux_block   *table   = (redux_block *)((uint8_t *)d_workspace + copy);
+    uint8_t       *dws     = (uint8_t *)table + store_table_bytes(nblocks);
+
+    StoreTableArgs ta;
+    ta.stored     = (const uint8_t *)d_stored;
+    ta.table      = table;
+    ta.nblocks    = nblocks;
+    ta.out_len    = out_len;
+    ta.block_size = block_size;
+    k_store_table<<<1, 1024, 0, s>>>(ta);
+    HIP_TRY(hipGetLastError());
+    // (the library's own table, coded blocks first: no k_table_check, whose "a block no entry codes" rule is wrong here)
+    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, out_len, d_out_sizes, d_block_status, nullptr, dws,
+                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr, table,
+                                (block_size & 15) == 0, nblocks, true);
+    if (st != REDUX_OK)
+        return st;
+    StoreUnpackArgs ua;
+    ua.in         = (const uint8_t *)d_in;
+    ua.in_offsets = (const uint64_t *)d_in_offsets;
+    ua.stored     = (const uint8_t *)d_stored;
+    ua.out        = t;
+    ua.out_sizes  = (uint32_t *)d_out_sizes;
+    ua.status     = (int32_t *)d_block_status;
+    ua.nblocks    = nblocks;
+    ua.out_len    = out_len;
+    ua.block_size = block_size;
+    k_store_unpack<<<(uint32_t)nblocks, 256, 0, s>>>(ua);
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
+                                                                        nullptr, nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    if (element_size > 1 && (st = redux_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
+        return st;
+    if (d_summary) {
+        HIP_TRY(hipMemsetAsync(d_summary, 0, 8, s));
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+        HIP_TRY(hipGetLastError());
+    }
+    return REDUX_OK;
+}
+
+// the chunked host calls: flags travel in the slot's d_stf (redux_host.hpp)
+static host::EncodeCoder stored_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size, uint32_t store_ratio)
+{
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                plain.size(max_in, several, ws, bound);
+                ws += element_size > 1 ? planes_copy_bytes(max_in) : 0;
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_encode_stored_dev(p, s.d_in.p, len, block_size, element_size, store_ratio, s.d_out.p, bound, s.d_off.p,
+                                               s.d_stf.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
+static host::DecodeCoder stored_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    return {[=](uint64_t cb) { return redux_decode_stored_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_decode_stored_dev(p, s.d_in.p, s.d_off.p, s.d_stf.p, out_bytes, block_size, element_size, s.d_out.p,
+                                               out_bytes, s.d_sz.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            },
+            true};
+}
+
+int redux_encode_blocks_stored(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint32_t store_ratio, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, uint8_t *stored,
+                               int32_t *block_status, uint32_t *block_crc)
+{
+    int st = stored_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (store_ratio > kStoreRatioOne || !out || !out_offsets || !stored || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               stored_encoder(p, block_size, element_size, store_ratio), block_crc, stored); // redux_host.hpp
+}
+
+int redux_decode_blocks_stored(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *stored,
+                               uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                               uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = stored_check(p, block_size, element_size);
+    if (st == REDUX_OK && !stored)
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_cap, out_sizes,
+                              block_status, nullptr, stored_decoder(p, block_size, element_size), block_crc, stored);
 }
 
 // ---- per-block CRC-32 (redux_crc.hpp) -------------------------------------------------------------

@@ -139,14 +139,15 @@ struct Buf {
 };
 
 struct Slot {          // one chunk in flight
-    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab, d_crc;                       // device
-    Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}, h_crc{true}; // pinned mirrors of the small arrays
-    hipEvent_t done = nullptr;                                                                    // recorded after the chunk's kernels
+    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab, d_crc, d_stf;                              // device
+    Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}, h_crc{true}, h_stf{true}; // pinned mirrors of the small arrays
+    hipEvent_t done = nullptr; // recorded after the chunk's kernels
+    // (d_stf / h_stf: the stored-block flags, u8 per block)
 
-    std::array<Buf *, 17> bufs()
+    std::array<Buf *, 19> bufs()
     {
-        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &d_crc,
-                &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab, &h_crc};
+        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &d_crc, &d_stf,
+                &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab, &h_crc, &h_stf};
     }
 };
 
@@ -698,6 +699,7 @@ struct EncodeChunks {
     int32_t           *block_status;
     const EncodeCoder &coder;
     uint32_t          *block_crc; // may be null: CRC-32 of each input block (redux_crc.hpp), on the staged chunk
+    uint8_t           *stored;    // may be null: the stored-block flags the coder leaves in s.d_stf (redux_store.hpp)
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -718,6 +720,11 @@ struct EncodeChunks {
     {
         const int rc = grow_bufs(c, {{&s.d_in, max_in + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (cb + 1) * 8},
                                      {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
+        if (rc == REDUX_OK && stored) {
+            const int r2 = grow_bufs(c, {{&s.d_stf, cb}, {&s.h_stf, cb}});
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
@@ -736,7 +743,8 @@ struct EncodeChunks {
     bool fetch(Slot &s, hipStream_t st, uint64_t nb) const
     {
         return fetch_small(s.h_off, s.d_off, (nb + 1) * 8, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
-               fetch_small(s.h_sum, s.d_sum, 8, st) && (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st));
+               fetch_small(s.h_sum, s.d_sum, 8, st) && (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st)) &&
+               (!stored || fetch_small(s.h_stf, s.d_stf, nb, st));
     }
     Placed place(Ctx &c, Slot &s, uint64_t k, uint64_t b0, uint64_t nb, Ledger &L) const
     {
@@ -757,14 +765,17 @@ struct EncodeChunks {
             memcpy(block_status + b0, s.h_st.p, nb * 4);
         if (block_crc)
             memcpy(block_crc + b0, s.h_crc.p, nb * 4);
+        if (stored)
+            memcpy(stored + b0, s.h_stf.p, nb);
         return {};
     }
 };
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
-                         uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr)
+                         uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr,
+                         uint8_t *stored = nullptr)
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored};
     return run_chunks(op);
 }
 
@@ -783,6 +794,7 @@ struct DecodeChunks {
     uint64_t          *in_used;
     const DecodeCoder &coder;
     uint32_t          *block_crc; // may be null: CRC-32 of what each block decoded to (redux_crc.hpp), on the chunk's output
+    const uint8_t     *stored;    // may be null: stored-block flags, staged to s.d_stf with the chunk's offsets (redux_store.hpp)
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -810,6 +822,11 @@ struct DecodeChunks {
         const int      rc   = grow_bufs(c, {{&s.d_in, max_in + 32}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, cb * (uint64_t)block_size + 16},
                                             {&s.d_off, (cb + 1) * 8}, {&s.d_sz, cb * 4}, {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.d_used, used},
                                             {&s.h_off, (cb + 1) * 8}, {&s.h_sz, cb * 4}, {&s.h_st, cb * 4}, {&s.h_sum, 8}, {&s.h_used, used}});
+        if (rc == REDUX_OK && stored) {
+            const int r2 = grow_bufs(c, {{&s.d_stf, cb}, {&s.h_stf, cb}});
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
@@ -824,6 +841,10 @@ struct DecodeChunks {
             ho[i] = in_offsets[b0 + i] - i0;
         }
         HOST_TRY(hipMemcpyAsync(s.d_off.p, ho, (nb + 1) * 8, hipMemcpyHostToDevice, st));
+        if (stored) {
+            memcpy(s.h_stf.p, stored + b0, nb);
+            HOST_TRY(hipMemcpyAsync(s.d_stf.p, s.h_stf.p, nb, hipMemcpyHostToDevice, st));
+        }
         return stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
     }
     int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
@@ -859,9 +880,9 @@ struct DecodeChunks {
 
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                          uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
-                         uint32_t *block_crc = nullptr)
+                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr)
 {
-    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc};
+    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored};
     return run_chunks(op);
 }
 

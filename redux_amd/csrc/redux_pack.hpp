@@ -5,12 +5,14 @@
 //                    k_scan_sizes_coalesced for whole chunks of 4096 blocks (the headline shape)
 //   k_compact        slot b [0, size_b) -> out + offsets[b], 16-byte stores with byte realignment
 //   k_compact_rows   the same from row-major group areas (what k_encode_pair leaves)
+//   (stored blocks, redux_store.hpp: k_compact copies their raw bytes whatever the mode; k_compact_rows skips them)
 //
 // Included by redux_hip.hip (one translation unit).
 #pragma once
 
 #include "redux_coder.hpp"
 #include "redux_encode.hpp"
+#include "redux_store.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -257,18 +259,24 @@ struct CompactArgs {
                               // bit 1: every aligned dword of a slot is byte-reversed (kSwapped, redux_coder.hpp)
     uint32_t        cap_rows; // rows of a group area
     const redux_block *table; // block table (null: slot b holds block b): slot b holds the block numbered table[b].index
+    const uint8_t  *stored;   // null, or u8[nblocks]: block b is stored (k_store_select), its bytes are raw + b * block_size
+    const uint8_t  *raw;
+    uint32_t        block_size;
 };
 
 __global__ void __launch_bounds__(256) k_compact(CompactArgs a)
 {
     const uint64_t b = blockIdx.x;
     const uint32_t mode = *a.mode;
-    if (b >= a.nblocks || (mode & 1u))
+    if (b >= a.nblocks || ((mode & 1u) && !a.stored))
         return;
     const uint32_t bx  = (mode & 2u) ? 3u : 0u;                   // slot byte that holds stream byte i: i ^ bx
     const uint32_t sel = (mode & 2u) ? 0x00010203u : 0x03020100u; // v_perm selector that restores stream order
     const uint64_t lb = a.table ? a.table[b].index : b;
     if (lb == kIdleEntry) // an idle table entry: nothing was coded in this slot
+        return;
+    const bool raw = a.stored && a.stored[lb];
+    if ((mode & 1u) && !raw) // (row-major group areas: k_compact_rows places the coded streams)
         return;
     const uint64_t o0 = a.offsets[lb], o1 = a.offsets[lb + 1];
     const uint32_t tid = threadIdx.x;
@@ -286,6 +294,10 @@ __global__ void __launch_bounds__(256) k_compact(CompactArgs a)
     const uint32_t n   = (uint32_t)(o1 - o0);
     const uint8_t *src = a.slots + b * a.slot_bytes; // 16-byte aligned
     uint8_t       *dst = a.out + o0;
+    if (raw) { // a stored block: its coder input, at any alignment
+        store_copy(a.raw + lb * a.block_size, dst, n, tid, 256);
+        return;
+    }
 
     // head: bytes up to the first 16-byte boundary of dst
     uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
@@ -354,7 +366,7 @@ __global__ void __launch_bounds__(256) k_compact_rows(CompactArgs a)
         uint64_t       d = 0;
         uint32_t       n = 0, sh = 0;
         const uint64_t lb = b < a.nblocks ? (a.table ? a.table[b].index : b) : kIdleEntry;
-        if (lb != kIdleEntry) {
+        if (lb != kIdleEntry && !(a.stored && a.stored[lb])) { // (stored blocks: k_compact)
             const uint64_t o0 = a.offsets[lb], o1 = a.offsets[lb + 1];
             if (o1 <= a.out_cap) {
                 n  = (uint32_t)(o1 - o0);

@@ -85,6 +85,12 @@ extern "C" {
     fn redux_static_decode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
                                       nblocks: u64, block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32,
                                       block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_encode_blocks_stored(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                  store_ratio: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64, stored: *mut u8,
+                                  block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_stored(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, stored: *const u8,
+                                  out_len: u64, block_size: u32, element_size: u32, out: *mut u8, out_cap: u64,
+                                  out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
