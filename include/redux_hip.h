@@ -106,7 +106,10 @@ int redux_encode_blocks(const redux_params *p, const uint8_t *in, uint64_t in_le
  *   out              block b is written at out + b*block_size (at most block_size bytes)
  *   out_sizes        nblocks entries: decoded length of each block
  * Per-block status: EOF for a truncated stream, INVALID_INPUT for a code value outside the
- * model's total, OUTPUT_TOO_SMALL if a (corrupt) stream decodes past block_size. */
+ * model's total, OUTPUT_TOO_SMALL if a (corrupt) stream decodes past block_size.
+ * Block b's range [in_offsets[b], in_offsets[b+1]) may hold any number of bytes after its stream: they are
+ * ignored, as redux::decompress ignores what follows its stream.  This holds for every decode call here (the
+ * `_dev`, `_v`, `_crc`, planes, stored and static ones, and redux_decompress's in_len). */
 int redux_decode_blocks(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
                         uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
                         int32_t *block_status);

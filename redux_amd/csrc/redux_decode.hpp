@@ -47,6 +47,25 @@ struct DecArgs {
 };
 constexpr uint32_t kDecRcWindow = 1u << 20;
 
+// The part of a block's input range its decode can read.  A range may hold any number of bytes after its stream, which
+// the reader never reaches (redux::decompress ignores them, lib.rs:113-120); the decoders that count the stream's bits
+// in 32 bits read the range up to this bound instead.  Proof that a block with room for capn bytes of sb-bit symbols
+// never fetches a bit past it, at code_bits cb:
+//   * the first code value takes cb bits (codec.rs:124-127);
+//   * a decoded symbol leaves an interval of width >= 1 (count <= the code range, model/mod.rs:64); each renormalising
+//     shift doubles the width, which stays <= 2^cb, so a symbol pulls at most cb bits; EOF pulls none (codec.rs:136-138);
+//   * symbol i (from 0) is written unless a byte it completes lies past the block: it is written iff
+//     (i + 1) * sb <= 8 * capn + 7, so at most n = (8 capn + 7) / sb are, and the next one fails after its bits.
+// Hence at most cb * (n + 2) bits.  Lock-step blocks hold <= 4 MiB of >= 1-bit symbols at cb <= 32 (static ones <= 2^26 - 2
+// bytes of 8-bit symbols): the bound stays below 2^31 bits, as the 32-bit count-downs need.  Streams no longer than it
+// decode exactly as before.
+__device__ __forceinline__ uint64_t dec_range_bound(uint64_t size, uint32_t capn, uint32_t sb, uint32_t cb)
+{
+    const uint64_t n     = ((uint64_t)capn * 8 + 7) / sb;
+    const uint64_t bound = ((uint64_t)cb * (n + 2) + 7) / 8;
+    return size < bound ? size : bound;
+}
+
 // The reciprocal the coder multiplies with at update number `nup` (wave-uniform), count = count0 + nup: from the table
 // while it lasts, otherwise computed as k_fill_rc computes an entry -- the correctly rounded 1 / count, biased up 4 ulp
 // (scale_div's proof needs exactly that value) -- ~15 instructions of a step that has ~165.
@@ -505,7 +524,8 @@ __device__ __forceinline__ void decode_lock_body(const DecArgs &a, uint32_t *lds
         size              = a.in_offsets[blk + 1] - o0;
         sp                = a.in + o0;
     }
-    const uint32_t stream_bits = (uint32_t)(size * 8);
+    const uint64_t size_eff    = dec_range_bound(size, a.block_size, 8u, cb); // (bytes after the stream: never read)
+    const uint32_t stream_bits = (uint32_t)(size_eff * 8);
     uint8_t       *dst         = a.out + (live ? blk : 0) * (uint64_t)a.block_size;
     const uint32_t capn        = a.block_size;
     const bool     aligned4    = a.aligned4 != 0;
@@ -533,7 +553,7 @@ __device__ __forceinline__ void decode_lock_body(const DecArgs &a, uint32_t *lds
     const bool      has    = live && size > 0;
     const uintptr_t sp_abs = (uintptr_t)sp;
     const gptr      gin    = has ? (gptr)(sp_abs & ~(uintptr_t)3) : (gptr)(uintptr_t)a.in_offsets;
-    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
+    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size_eff + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
     const uint32_t  skip   = has ? (uint32_t)(sp_abs & 3) * 8 : 0u;
     const gptr      gsafe  = (gptr)(uintptr_t)a.in_offsets;
     auto rd = [&](uint32_t o) { return gin[o < rpo_last ? o : rpo_last]; };

@@ -176,7 +176,8 @@ __device__ __forceinline__ void decode_adaptive_body(const DecArgs &a, uint32_t 
         size              = a.in_offsets[blk + 1] - o0;
         sp                = a.in + o0;
     }
-    const uint32_t stream_bits = (uint32_t)(size * 8);
+    const uint64_t size_eff    = dec_range_bound(size, capn, 8u, cb); // (bytes after the stream: never read)
+    const uint32_t stream_bits = (uint32_t)(size_eff * 8);
     uint8_t       *dst         = a.out + (live ? dst_off : 0);
     const rc_ptr   rcp         = (rc_ptr)a.rc;
     const uint32_t nfreeze     = a.nfreeze;
@@ -197,7 +198,7 @@ __device__ __forceinline__ void decode_adaptive_body(const DecArgs &a, uint32_t 
     const bool      has      = live && size > 0;
     const uintptr_t sp_abs   = (uintptr_t)sp;
     const gptr      gin      = has ? (gptr)(sp_abs & ~(uintptr_t)3) : (gptr)(uintptr_t)a.in_offsets;
-    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
+    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size_eff + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
     const uint32_t  skip     = has ? (uint32_t)(sp_abs & 3) * 8 : 0u;
     const gptr      gsafe    = (gptr)(uintptr_t)a.in_offsets;
     const uint32_t  L4       = lane * 4u;

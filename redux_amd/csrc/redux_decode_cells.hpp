@@ -289,7 +289,8 @@ __global__ void __launch_bounds__(64) k_decode_cells(GenDecArgs a)
         size              = a.in_offsets[blk + 1] - o0;
         sp                = a.in + o0;
     }
-    const uint32_t stream_bits = (uint32_t)(size * 8);
+    const uint64_t size_eff    = dec_range_bound(size, a.block_size, SB, cb); // (bytes after the stream: never read)
+    const uint32_t stream_bits = (uint32_t)(size_eff * 8);
     uint8_t       *dst         = a.out + (live ? blk : 0) * (uint64_t)a.block_size;
     const uint32_t capn        = a.block_size; // bytes
     const uint32_t nfreeze     = a.nfreeze;
@@ -301,7 +302,7 @@ __global__ void __launch_bounds__(64) k_decode_cells(GenDecArgs a)
     const bool      has      = live && size > 0;
     const uintptr_t sp_abs   = (uintptr_t)sp;
     const gptr      gin      = has ? (gptr)(sp_abs & ~(uintptr_t)3) : (gptr)(uintptr_t)a.in_offsets;
-    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
+    const uint32_t  rpo_last = has ? (uint32_t)(((((sp_abs + size_eff + 3) & ~(uintptr_t)3) - (sp_abs & ~(uintptr_t)3)) >> 2) - 1) : 0u;
     const uint32_t  skip     = has ? (uint32_t)(sp_abs & 3) * 8 : 0u;
     const gptr      gsafe    = (gptr)(uintptr_t)a.in_offsets;
     char *const     ring     = reinterpret_cast<char *>(lds) + G::kRingBase + 4u * lane;

@@ -623,20 +623,30 @@ const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out,
     case DecKernel::GenericU16: return "k_decode<true, false> (u16 tree, per-lane control flow)";
     case DecKernel::GenericU16Fixup: return "k_decode<true, true> (u16 tree, quotient fix-up)";
     case DecKernel::GenericU32: return "k_decode<false, true> (u32 tree)";
-    case DecKernel::CellsFixup: // (the same kernels' instance for counts of 2^17 and more)
+    case DecKernel::CellsFixup: {
+        // lock-step, the tree as cells of four levels in LDS; the instance for counts of 2^17 and more (widths 1 ... 7)
+        static const char *const names[8] = {"", "k_decode_cells<1> (fix-up: count past 2^17)", "k_decode_cells<2> (fix-up: count past 2^17)",
+                                             "k_decode_cells<3> (fix-up: count past 2^17)", "k_decode_cells<4> (fix-up: count past 2^17)",
+                                             "k_decode_cells<5> (fix-up: count past 2^17)", "k_decode_cells<6> (fix-up: count past 2^17)",
+                                             "k_decode_cells<7> (fix-up: count past 2^17)"};
+        return p->symbol_bits < 8 ? names[p->symbol_bits] : "";
+    }
     case DecKernel::Cells:
     case DecKernel::CellsWorkspace: {
         // lock-step, the tree as cells of four levels: all of them in LDS (symbol_bits <= 10), or the bottom ones in the workspace
-        static const char *const names[13] = {"", "k_decode_cells<1>", "k_decode_cells<2>", "k_decode_cells<3>", "k_decode_cells<4>",
-                                               "k_decode_cells<5>", "k_decode_cells<6>", "k_decode_cells<7>", "", "k_decode_cells<9>",
-                                               "k_decode_cells<10>", "k_decode_cells<11>", "k_decode_cells<12>"};
+        static const char *const names[13] = {"", "k_decode_cells<1> (cells in LDS)", "k_decode_cells<2> (cells in LDS)",
+                                               "k_decode_cells<3> (cells in LDS)", "k_decode_cells<4> (cells in LDS)",
+                                               "k_decode_cells<5> (cells in LDS)", "k_decode_cells<6> (cells in LDS)",
+                                               "k_decode_cells<7> (cells in LDS)", "", "k_decode_cells<9> (cells in LDS)",
+                                               "k_decode_cells<10> (cells in LDS)", "k_decode_cells<11> (bottom cells in the workspace)",
+                                               "k_decode_cells<12> (bottom cells in the workspace)"};
         return names[p->symbol_bits];
     }
-    case DecKernel::Cells8:
-    case DecKernel::Cells8Fixup: return "k_decode_cells<8> (u32 cells, blocks above 64 KiB, one wave per 64 blocks)";
+    case DecKernel::Cells8: return "k_decode_cells<8> (u32 cells, blocks above 64 KiB, one wave per 64 blocks)";
+    case DecKernel::Cells8Fixup: return "k_decode_cells<8> (u32 cells, blocks above 64 KiB, one wave per 64 blocks; fix-up: count past 2^17)";
     case DecKernel::Any: return "k_decode_any (general parameters, one lane per block)";
-    case DecKernel::Wave:
-    case DecKernel::WaveFixup: return "k_decode_wave (one block per wave, cumulative table across the lanes)";
+    case DecKernel::Wave: return "k_decode_wave (one block per wave, cumulative table across the lanes)";
+    case DecKernel::WaveFixup: return "k_decode_wave (one block per wave, cumulative table across the lanes; fix-up: count past 2^17)";
     }
     return "";
 }
