@@ -232,25 +232,18 @@ def _check_element_size(element_size):
     return int(element_size)
 
 
-def _crc_out(block_crc, nb):
-    """the caller's block_crc= array (np.uint32[nblocks], filled in place) -> its pointer; None -> NULL"""
-    if block_crc is None:
-        return None
-    if not isinstance(block_crc, np.ndarray) or block_crc.dtype != np.uint32 or block_crc.shape != (nb,) \
-            or not block_crc.flags.c_contiguous or not block_crc.flags.writeable:
-        raise InvalidInput()
-    return block_crc.ctypes.data if nb else None
-
-
 STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
 
 
-def _stored_arg(stored, nb, writable):
-    """the caller's stored= flags (np.uint8[nblocks]; filled in place on encode) -> its pointer"""
-    if not isinstance(stored, np.ndarray) or stored.dtype != np.uint8 or stored.shape != (nb,) \
-            or not stored.flags.c_contiguous or (writable and not stored.flags.writeable):
+def _array_arg(a, dtype, nb, writable=True):
+    """the caller's block_crc= (np.uint32[nblocks], filled in place) or stored= array (np.uint8[nblocks]; filled in
+    place on encode) -> its pointer; None -> NULL"""
+    if a is None:
+        return None
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != (nb,) or not a.flags.c_contiguous \
+            or (writable and not a.flags.writeable):
         raise InvalidInput()
-    return stored.ctypes.data
+    return _ptr(a)
 
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
@@ -259,93 +252,51 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
     layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
-    params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks); no element_size.
+    params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks_crc); no element_size.
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 (zlib.crc32) of every input block, in original
     byte order for every layout (the `_crc` calls of include/redux_hip.h).
     stored: a np.uint8[nblocks] the same call fills with the stored-block flags (include/redux_hip.h, "stored blocks"):
     passing it turns stored blocks on, and block b's payload is then its raw (planes: plane) bytes wherever its stream
     is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it."""
-    if isinstance(params, StaticModel):
-        if stored is not None:
-            raise InvalidInput()  # (the static decoder has no table form)
-        return _compress_blocks_static(data, block_size, params, element_size, block_crc)
+    static = isinstance(params, StaticModel)
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
     cp = P._c()
     _raise(L.redux_device_supports(C.byref(cp)))
     E = _check_element_size(element_size)
-    if block_size <= 0:
+    # (a static model has one table for all byte planes, and its decoder has no table form for stored blocks)
+    if block_size <= 0 or (static and (E != 1 or stored is not None)) or (stored is not None and (
+            not isinstance(store_ratio, (int, np.integer)) or not 0 <= store_ratio < 1 << 32)):
         raise InvalidInput()
     nb = L.redux_block_count(len(a), block_size)
-    cap = L.redux_encode_bound(C.byref(cp), len(a), block_size)
-    out = np.empty(cap, dtype=np.uint8)
+    crc = _array_arg(block_crc, np.uint32, nb)
+    flags = _array_arg(stored, np.uint8, nb)
+    cap = (L.redux_static_encode_bound if static else L.redux_encode_bound)(C.byref(cp), len(a), block_size)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
-    crc = _crc_out(block_crc, nb)
     if stored is not None:
-        if not isinstance(store_ratio, (int, np.integer)) or not 0 <= store_ratio < 1 << 32:
-            raise InvalidInput()
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
-                                          offs.ctypes.data, _stored_arg(stored, nb, True), status.ctypes.data, crc)
-    elif block_crc is not None:
+                                          offs.ctypes.data, flags, status.ctypes.data, crc)
+    elif static:
+        st = L.redux_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
+                                              cap, offs.ctypes.data, status.ctypes.data, crc)
+    else:  # (element size 1 included: the coder without a layout)
         st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
                                               offs.ctypes.data, status.ctypes.data, crc)
-    elif E == 1:
-        st = L.redux_encode_blocks(C.byref(cp), _ptr(a), len(a), block_size, out.ctypes.data, cap, offs.ctypes.data,
-                                   status.ctypes.data)
-    else:
-        st = L.redux_encode_blocks_planes(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
-                                          offs.ctypes.data, status.ctypes.data)
     _raise(st)
     return out[: int(offs[-1])], offs, status
 
 
-def _compress_blocks_static(data, block_size, model, element_size, block_crc=None):
-    if _check_element_size(element_size) != 1:
-        raise InvalidInput()  # (each byte plane would need its own table)
-    a = _u8(data)
-    L = _lib.lib()
-    cp = model.params._c()
-    if block_size <= 0:
-        raise InvalidInput()
-    nb = L.redux_block_count(len(a), block_size)
-    cap = L.redux_static_encode_bound(C.byref(cp), len(a), block_size)
-    out = np.empty(max(cap, 1), dtype=np.uint8)
-    offs = np.zeros(nb + 1, dtype=np.uint64)
-    status = np.zeros(nb, dtype=np.int32)
-    if block_crc is not None:
-        _raise(L.redux_static_encode_blocks_crc(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
-                                                cap, offs.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb)))
-    else:
-        _raise(L.redux_static_encode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data, cap,
-                                            offs.ctypes.data, status.ctypes.data))
-    return out[: int(offs[-1])], offs, status
-
-
-def _decompress_blocks_static(streams, offsets, block_size, model, check, element_size, length, block_crc=None):
-    if _check_element_size(element_size) != 1 or length is not None:
-        raise InvalidInput()
-    a = _u8(streams)
+def _offsets_in(offsets, nbytes):
+    """the caller's offsets -> np.uint64[nblocks+1]; InvalidInput unless there is at least one entry and every stream
+    lies inside the nbytes of the streams, in order (the C calls read streams[offsets[b] .. offsets[b + 1]) from caller
+    memory)"""
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    nb = len(offs) - 1
-    if nb < 0 or block_size <= 0 or int(offs[-1]) > len(a) or bool((offs[1:] < offs[:-1]).any()):
+    if len(offs) == 0 or int(offs[-1]) > nbytes or bool((offs[1:] < offs[:-1]).any()):
         raise InvalidInput()
-    L = _lib.lib()
-    cp = model.params._c()
-    out = np.empty(nb * block_size, dtype=np.uint8)
-    sizes = np.zeros(nb, dtype=np.uint32)
-    status = np.zeros(nb, dtype=np.int32)
-    if block_crc is not None:
-        st = L.redux_static_decode_blocks_crc(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
-                                              out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data,
-                                              _crc_out(block_crc, nb))
-    else:
-        st = L.redux_static_decode_blocks(C.byref(cp), model._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
-                                          out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data)
-    if check:
-        _raise(st)
-    return out, sizes, status
+    return offs
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
@@ -355,91 +306,46 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
     required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
     (frames with a damaged block hold undefined bytes; their blocks' status says which).
-    params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks).
+    params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks_crc).
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
     order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK.
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
     uint8[length] in original order, as with element_size > 1."""
-    if stored is not None:
-        if isinstance(params, StaticModel) or length is None:
-            raise InvalidInput()
-        return _decompress_blocks_stored(streams, offsets, block_size, params, check, _check_element_size(element_size),
-                                         int(length), block_crc, stored)
-    if isinstance(params, StaticModel):
-        return _decompress_blocks_static(streams, offsets, block_size, params, check, element_size, length, block_crc)
+    static = isinstance(params, StaticModel)
     E = _check_element_size(element_size)
-    if E > 1 and length is None:
+    if block_size <= 0 or (static and (E != 1 or length is not None or stored is not None)) \
+            or (length is None and (E > 1 or stored is not None)):
         raise InvalidInput()
-    if length is not None:
-        return _decompress_blocks_planes(streams, offsets, block_size, params, check, E, int(length), block_crc)
     P = _params_of(params)
     a = _u8(streams)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    offs = _offsets_in(offsets, len(a))
     nb = len(offs) - 1
-    if nb < 0 or (nb >= 0 and len(offs) and (int(offs[-1]) > len(a) or bool((offs[1:] < offs[:-1]).any()))):
-        raise InvalidInput()  # (the C call reads streams[offsets[b] .. offsets[b + 1]) from caller memory)
     L = _lib.lib()
-    cp = P._c()
-    _raise(L.redux_device_supports(C.byref(cp)))
-    out = np.empty(nb * block_size, dtype=np.uint8)
-    sizes = np.zeros(nb, dtype=np.uint32)
-    status = np.zeros(nb, dtype=np.int32)
-    if block_crc is not None:
-        st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
-                                       sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
-    else:
-        st = L.redux_decode_blocks(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
-                                   sizes.ctypes.data, status.ctypes.data)
-    if check:
-        _raise(st)
-    return out, sizes, status
-
-
-def _decompress_blocks_planes(streams, offsets, block_size, params, check, E, length, block_crc=None):
-    P = _params_of(params)
-    a = _u8(streams)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    L = _lib.lib()
-    if block_size <= 0 or length < 0 or len(offs) != L.redux_block_count(length, block_size) + 1 or int(offs[-1]) > len(a) \
-            or bool((offs[1:] < offs[:-1]).any()):
+    length = None if length is None else int(length)
+    if length is not None and (length < 0 or nb != L.redux_block_count(length, block_size)):
         raise InvalidInput()
     cp = P._c()
     _raise(L.redux_device_supports(C.byref(cp)))
-    nb = len(offs) - 1
-    out = np.empty(max(length, 1), dtype=np.uint8)
+    crc = _array_arg(block_crc, np.uint32, nb)
+    flags = _array_arg(stored, np.uint8, nb, writable=False)
+    out = np.empty(nb * block_size if length is None else max(length, 1), dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
-    if block_crc is not None:
+    if stored is not None:
+        st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
+                                          out.size, sizes.ctypes.data, status.ctypes.data, crc)
+    elif static:
+        st = L.redux_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
+                                              out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data, crc)
+    elif length is not None:
         st = L.redux_decode_blocks_planes_crc(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
-                                              sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
+                                              sizes.ctypes.data, status.ctypes.data, crc)
     else:
-        st = L.redux_decode_blocks_planes(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
-                                          sizes.ctypes.data, status.ctypes.data)
+        st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
+                                       sizes.ctypes.data, status.ctypes.data, crc)
     if check:
         _raise(st)
-    return out[:length], sizes, status
-
-
-def _decompress_blocks_stored(streams, offsets, block_size, params, check, E, length, block_crc, stored):
-    P = _params_of(params)
-    a = _u8(streams)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    L = _lib.lib()
-    if block_size <= 0 or length < 0 or len(offs) != L.redux_block_count(length, block_size) + 1 or int(offs[-1]) > len(a) \
-            or bool((offs[1:] < offs[:-1]).any()):
-        raise InvalidInput()
-    cp = P._c()
-    _raise(L.redux_device_supports(C.byref(cp)))
-    nb = len(offs) - 1
-    flags = _stored_arg(stored, nb, False)
-    out = np.empty(max(length, 1), dtype=np.uint8)
-    sizes = np.zeros(nb, dtype=np.uint32)
-    status = np.zeros(nb, dtype=np.int32)
-    st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
-                                      out.size, sizes.ctypes.data, status.ctypes.data, _crc_out(block_crc, nb))
-    if check:
-        _raise(st)
-    return out[:length], sizes, status
+    return (out if length is None else out[:length]), sizes, status
 
 
 # ---- several GPUs behind the host-pointer calls ------------------------------------------------
@@ -515,15 +421,12 @@ def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32
     cp = P._c()
     _raise(L.redux_device_supports(C.byref(cp)))
     a = _u8(streams)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     lens = np.ascontiguousarray(lengths, dtype=np.uint64)
     if block_size <= 0 or len(lens) == 0:
         raise InvalidInput()
     nb = L.redux_block_count_v(lens.ctypes.data, len(lens), block_size)
-    if nb != len(offs) - 1:
-        raise InvalidInput()
-    # the C call copies streams[offsets[0] .. offsets[nb]) from caller memory: they must lie inside `streams`, in order
-    if int(offs[0]) != 0 or int(offs[-1]) > len(a) or bool((offs[1:] < offs[:-1]).any()):
+    offs = _offsets_in(offsets, len(a))
+    if nb != len(offs) - 1 or int(offs[0]) != 0:  # (the C call copies streams[offsets[0] .. offsets[nb]) in one piece)
         raise InvalidInput()
     out_off = np.zeros(len(lens), dtype=np.uint64)
     out_off[1:] = np.cumsum(lens)[:-1]
@@ -606,6 +509,12 @@ def _on_device(method):
     return wrapper
 
 
+def _workspace(torch, nbytes, device):
+    """(ws, ws_off): a uint8 device tensor with nbytes of room from the 256-byte boundary ws.data_ptr() + ws_off on"""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    return ws, (-ws.data_ptr()) % 256
+
+
 class DeviceEncoder:
     """Reusable encoder for inputs of up to max_in_len bytes already resident in HBM.
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
@@ -625,8 +534,7 @@ class DeviceEncoder:
                                                               self.element_size)
         self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
-        self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
-        self.ws_off = (-self.ws.data_ptr()) % 256
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
         self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
         self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
@@ -706,8 +614,7 @@ class DeviceDecoder:
             self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
                                                                   self.block_size, self.element_size)
         self.device = torch.device(device)
-        self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
-        self.ws_off = (-self.ws.data_ptr()) % 256
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
         self.out = torch.empty(self.max_blocks * self.block_size, dtype=torch.uint8, device=self.device)
         self.sizes = torch.zeros(self.max_blocks, dtype=torch.int32, device=self.device)
         self.status = torch.zeros(self.max_blocks, dtype=torch.int32, device=self.device)
@@ -718,20 +625,18 @@ class DeviceDecoder:
         """length: bytes of the original input; required with element_size > 1 (d_offsets then holds
         redux_block_count(length, block_size) + 1 entries), and the result is out[:length]."""
         torch = _torch()
+        L = _lib.lib()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
-        if self.element_size > 1 and length is None:
+        if (length is None and self.element_size > 1) \
+                or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)):
             raise InvalidInput()
         if length is not None:
-            L = _lib.lib()
-            if length < 0 or L.redux_block_count(int(length), self.block_size) != nb:
-                raise InvalidInput()
             if self.element_size == 1 and self.ws_bytes < L.redux_decode_planes_workspace_bytes(
                     C.byref(self.cp), int(length), self.block_size, 1):
                 self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
                                                                       self.block_size, 1)
-                self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
-                self.ws_off = (-self.ws.data_ptr()) % 256
+                self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
             self.summary.zero_()
             st = L.redux_decode_planes_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
                                            C.c_void_p(d_offsets.data_ptr()), int(length), self.block_size, self.element_size,
@@ -741,13 +646,11 @@ class DeviceDecoder:
             _raise(st)
             return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
         self.summary.zero_()
-        st = _lib.lib().redux_decode_blocks_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
-                                                C.c_void_p(d_offsets.data_ptr()), nb, self.block_size,
-                                                C.c_void_p(self.out.data_ptr()), self.out.numel(),
-                                                C.c_void_p(self.sizes.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                C.c_void_p(self.summary.data_ptr()),
-                                                C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes,
-                                                _stream_ptr(torch))
+        st = L.redux_decode_blocks_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()), C.c_void_p(d_offsets.data_ptr()),
+                                       nb, self.block_size, C.c_void_p(self.out.data_ptr()), self.out.numel(),
+                                       C.c_void_p(self.sizes.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                       C.c_void_p(self.summary.data_ptr()), C.c_void_p(self.ws.data_ptr() + self.ws_off),
+                                       self.ws_bytes, _stream_ptr(torch))
         _raise(st)
         return self.out[: nb * self.block_size], self.sizes[:nb], self.status[:nb], self.summary
 
@@ -770,8 +673,7 @@ class DeviceStaticCoder:
         self.ws_bytes = L.redux_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size)
         self.out_cap = L.redux_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
-        self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
-        self.ws_off = (-self.ws.data_ptr()) % 256
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
         self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
         self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)

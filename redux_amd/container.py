@@ -40,6 +40,7 @@ padding bits must be 0 (else InvalidInput); a truncated bitmap is Eof.  The stat
 blocks.  Without stored=True the writers emit exactly the bytes they emitted before the flag existed.
 """
 import struct
+from collections import namedtuple
 
 import numpy as np
 
@@ -71,10 +72,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap."""
-    if element_size != 1 and element_size not in ELEMENT_SIZES:
-        raise api.InvalidInput()
     static = isinstance(params, api.StaticModel)
-    if static and element_size != 1:
+    if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1):
         raise api.InvalidInput()
     P = api._params_of(params)
     offs = np.asarray(offsets, dtype=np.uint64)
@@ -103,124 +102,109 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     return head + sizes.astype("<u4").tobytes() + crc + bitmap + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
 
-def _version_ok(ver, res):
-    if ver & STORED_FLAG and _layout(ver) not in (VERSION, VERSION_PLANES):
-        return False
-    ver = _layout(ver)
-    return (ver in (VERSION, VERSION_STATIC) and res == 0) or (ver == VERSION_PLANES and res in ELEMENT_SIZES)
-
-
 def _layout(ver):
     """the version without its checksum and stored-block flags"""
     return ver & ~(CRC_FLAG | STORED_FLAG)
 
 
-def unpack(buf):
-    """-> (Parameters, block_size, total_len, offsets uint64[nblocks+1], payload uint8 array).
-    Malformed containers raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
-    b = memoryview(buf)
+def _version_ok(ver, res):
+    """a known layout, its reserved word, and no stored blocks with a static table"""
+    layout = _layout(ver)
+    return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
+        or (layout == VERSION_PLANES and res in ELEMENT_SIZES)
+
+
+# What _parse reads from a container: element_size 1, or E of version 2; static the StaticModel of a version 3 table;
+# offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
+# of 0 / 1.  static, crcs and stored are None where the container has no such section.
+_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored")
+
+
+def _header(b):
+    """-> (version, Parameters, block_size, element size, nblocks, total) of a consistent header; Eof if b is shorter
+    than a header, InvalidInput if it is not consistent"""
     if len(b) < HEADER.size:
         raise api.Eof()
     magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or not _version_ok(ver, res) or block_size == 0 or block_size > MAX_BLOCK_SIZE:
+    if magic != MAGIC or not _version_ok(ver, res) or not 0 < block_size <= MAX_BLOCK_SIZE:
         raise api.InvalidInput()
     P = api.Parameters(sb, fb, cb)
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
-    start = HEADER.size
-    if _layout(ver) == VERSION_STATIC:
-        _table(b, P)
-        start += TABLE
-    end_sizes = start + 4 * nblocks
-    if len(b) < end_sizes:
+    return ver, P, block_size, res if _layout(ver) == VERSION_PLANES else 1, nblocks, total
+
+
+def _take(b, at, dtype, count):
+    """(count items of dtype at b[at:], where the next section begins); Eof if b ends first"""
+    end = at + np.dtype(dtype).itemsize * count
+    if len(b) < end:
         raise api.Eof()
-    sizes = np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint64)
+    return np.frombuffer(b, dtype=dtype, count=count, offset=at), end
+
+
+def _parse(buf):
+    """every check of the layout, section by section: header, table, sizes, CRCs, bitmap, payload.  Malformed containers
+    raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
+    b = memoryview(buf)
+    ver, P, block_size, E, nblocks, total = _header(b)
+    static = crcs = stored = None
+    at = HEADER.size
+    if _layout(ver) == VERSION_STATIC:
+        cum, at = _take(b, at, "<u4", 258)
+        try:
+            static = api.StaticModel(P, cum)
+        except api.Error:  # (redux_static_table_check: a bad table, or parameters the static coder does not take)
+            raise api.InvalidInput()
+    sizes, at = _take(b, at, "<u4", nblocks)
+    sizes = sizes.astype(np.uint64)
     offsets = np.zeros(nblocks + 1, dtype=np.uint64)
     offsets[1:] = np.cumsum(sizes)
     if ver & CRC_FLAG:
-        end_sizes += 4 * nblocks
-        if len(b) < end_sizes:
-            raise api.Eof()
+        crcs, at = _take(b, at, "<u4", nblocks)
+        crcs = crcs.astype(np.uint32)
     if ver & STORED_FLAG:
-        nbytes = (nblocks + 7) // 8
-        if len(b) < end_sizes + nbytes:
-            raise api.Eof()
-        bits = np.frombuffer(b, dtype=np.uint8, count=nbytes, offset=end_sizes)
+        bits, at = _take(b, at, np.uint8, (nblocks + 7) // 8)
         flags = np.unpackbits(bits, bitorder="little")
         if bool(flags[nblocks:].any()):  # padding bits
             raise api.InvalidInput()
-        flags = flags[:nblocks].astype(bool)
-        if bool((sizes[flags] != _raw_lengths(nblocks, block_size, total)[flags].astype(np.uint64)).any()):
+        stored = flags[:nblocks].astype(np.uint8)
+        raw = stored == 1
+        if bool((sizes[raw] != _raw_lengths(nblocks, block_size, total)[raw].astype(np.uint64)).any()):
             raise api.InvalidInput()
-        end_sizes += nbytes
-    if len(b) < end_sizes + int(offsets[-1]):
-        raise api.Eof()
-    payload = np.frombuffer(b, dtype=np.uint8, count=int(offsets[-1]), offset=end_sizes)
-    return P, block_size, total, offsets, payload
+    payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
+    return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored)
+
+
+def unpack(buf):
+    """-> (Parameters, block_size, total_len, offsets uint64[nblocks+1], payload uint8 array).
+    Malformed containers raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
+    c = _parse(buf)
+    return c.params, c.block_size, c.total, c.offsets, c.payload
 
 
 def block_crcs(buf):
     """The per-block CRC-32 table (np.uint32[nblocks]) a flagged container (0x11 / 0x12 / 0x13) records; None without
     the flag.  Malformed containers raise InvalidInput, truncated ones Eof."""
-    b = memoryview(buf)
-    unpack(b)  # (every check of the layout, the table's extent included)
-    ver = b[4]
-    if not ver & CRC_FLAG:
-        return None
-    nblocks = HEADER.unpack_from(b, 0)[7]
-    start = HEADER.size + (TABLE if _layout(ver) == VERSION_STATIC else 0) + 4 * nblocks
-    return np.frombuffer(b, dtype="<u4", count=nblocks, offset=start).astype(np.uint32)
+    return _parse(buf).crcs
 
 
 def block_stored(buf):
     """The stored-block flags (np.uint8[nblocks] of 0 / 1) a flagged container (0x41 / 0x42 / 0x51 / 0x52) records; None
     without the flag.  Malformed containers raise InvalidInput, truncated ones Eof."""
-    b = memoryview(buf)
-    unpack(b)  # (every check of the bitmap included)
-    ver = b[4]
-    if not ver & STORED_FLAG:
-        return None
-    nblocks = HEADER.unpack_from(b, 0)[7]
-    start = HEADER.size + 4 * nblocks * (2 if ver & CRC_FLAG else 1)
-    bits = np.frombuffer(b, dtype=np.uint8, count=(nblocks + 7) // 8, offset=start)
-    return np.unpackbits(bits, bitorder="little")[:nblocks].astype(np.uint8)
+    return _parse(buf).stored
 
 
 def element_size(buf):
-    """Element size of the byte-plane layout a container records: 1 for version 1, E for version 2.  Malformed headers
-    raise InvalidInput, truncated ones Eof."""
-    b = memoryview(buf)
-    if len(b) < HEADER.size:
-        raise api.Eof()
-    magic, ver, _sb, _fb, _cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or not _version_ok(ver, res):
-        raise api.InvalidInput()
-    return res if _layout(ver) == VERSION_PLANES else 1
-
-
-def _table(b, P):
-    """the version 3 table after the header of b, checked against P"""
-    if len(b) < HEADER.size + TABLE:
-        raise api.Eof()
-    cum = np.frombuffer(b, dtype="<u4", count=258, offset=HEADER.size).astype(np.uint32)
-    try:
-        return api.StaticModel(P, cum).cum
-    except api.Error:  # (redux_static_table_check: a bad table, or parameters the static coder does not take)
-        raise api.InvalidInput()
+    """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for version 2.  Malformed
+    containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).element_size
 
 
 def static_table(buf):
-    """The static table (np.uint32[258]) a version 3 container records; None for versions 1 and 2.  Malformed headers
-    or tables raise InvalidInput, truncated ones Eof."""
-    b = memoryview(buf)
-    if len(b) < HEADER.size:
-        raise api.Eof()
-    magic, ver, sb, fb, cb, _bs, res, _nb, _total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or not _version_ok(ver, res):
-        raise api.InvalidInput()
-    if _layout(ver) != VERSION_STATIC:
-        return None
-    return _table(b, api.Parameters(sb, fb, cb))
+    """The static table (np.uint32[258]) a version 3 container records; None for versions 1 and 2.  Malformed containers
+    raise InvalidInput, truncated ones Eof."""
+    static = _parse(buf).static
+    return None if static is None else static.cum
 
 
 def header_is_wellformed(buf):
@@ -229,19 +213,11 @@ def header_is_wellformed(buf):
     length.  The CLI uses it to tell a container from a raw reference stream that happens to begin
     with the same four bytes: a well-formed header followed by a damaged or truncated body is a
     damaged CONTAINER (unpack's error is reported), not a raw stream."""
-    b = memoryview(buf)
-    if len(b) < HEADER.size:
-        return False
-    magic, ver, sb, fb, cb, block_size, res, nblocks, total = HEADER.unpack_from(b, 0)
-    if magic != MAGIC or not 0 < block_size <= MAX_BLOCK_SIZE:
-        return False
-    if not _version_ok(ver, res):
-        return False
     try:
-        api.Parameters.new(sb, fb, cb)
+        _header(memoryview(buf))
     except api.Error:
         return False
-    return nblocks == (1 if total == 0 else (total + block_size - 1) // block_size)
+    return True
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
@@ -255,65 +231,37 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         raise api.InvalidInput()
     nb = max(1, -(-len(data) // block_size))
     crc = np.zeros(nb, dtype=np.uint32) if checksum else None
-    kw = {} if crc is None else {"block_crc": crc}
-    if stored:
-        flags = np.zeros(nb, dtype=np.uint8)
-        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size, stored=flags, **kw)
-        return pack(out, offs, params, block_size, len(data), element_size, block_crc=crc, stored=flags)
-    if model == "static":
-        m = api.StaticModel.from_data(data, params)
-        out, offs, _ = api.compress_blocks(data, block_size, m, **kw)
-        return pack(out, offs, m, block_size, len(data), block_crc=crc)
-    if element_size == 1:
-        out, offs, _ = api.compress_blocks(data, block_size, params, **kw)
-    else:
-        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size, **kw)
-    return pack(out, offs, params, block_size, len(data), element_size, block_crc=crc)
-
-
-def _verify(want, got, status):
-    """a checksummed container: every OK block must decode to the recorded CRC"""
-    if want is not None and bool(((got != want) & (np.asarray(status) == 0)).any()):
-        raise api.InvalidInput()
+    flags = np.zeros(nb, dtype=np.uint8) if stored else None
+    m = api.StaticModel.from_data(data, params) if model == "static" else params
+    out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags)
+    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags)
 
 
 def decompress_bytes(buf):
     """container bytes -> original bytes."""
-    P, block_size, total, offsets, payload = unpack(buf)
+    c = _parse(buf)
     # A stream of s bytes can decode to far more than s bytes (64 KiB of one symbol is ~400 bytes),
     # so only the declared total bounds the capacity; but every block's stream has at least one
     # byte, so a header that declares more blocks than there are payload bytes is malformed.
-    nb = len(offsets) - 1
-    flags = block_stored(buf)
-    if len(payload) < nb - (0 if flags is None else int(flags.sum())):  # (a stored block may be empty; a stream is not)
+    nb = len(c.offsets) - 1
+    if len(c.payload) < nb - (0 if c.stored is None else int(c.stored.sum())):  # (a stored block may be empty)
         raise api.InvalidInput()
-    E = element_size(buf)
-    cum = static_table(buf)
-    want = block_crcs(buf)
-    got = None if want is None else np.zeros(nb, dtype=np.uint32)
-    kw = {} if got is None else {"block_crc": got}
-    if flags is not None:
-        kw["stored"] = flags
-    model = P if cum is None else api.StaticModel(P, cum)
-    if E > 1 or flags is not None:  # (the blocks decode at their real size, into out[0 .. total))
-        try:
-            out, sizes, status = api.decompress_blocks(payload, offsets, block_size, P, element_size=E, length=total, **kw)
-        except MemoryError:
-            raise api.InvalidInput()
-        expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]
-        if [int(x) for x in sizes] != expect:
-            raise api.InvalidInput()
-        _verify(want, got, status)
-        return out.tobytes()
-    cap = max(1, min(block_size, total))  # one short block never needs block_size bytes of capacity
+    got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
+    exact = c.element_size > 1 or c.stored is not None
+    cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
-        out, sizes, status = api.decompress_blocks(payload, offsets, cap, model, **kw)
+        if exact:  # (the blocks decode at their real size, into out[0 .. total))
+            out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size, c.params,
+                                                       element_size=c.element_size, length=c.total, block_crc=got,
+                                                       stored=c.stored)
+        else:  # (straight into out[b * cap ..], no plane buffer)
+            out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
         raise api.InvalidInput()
-    expect = [min(block_size, total - b * block_size) for b in range(nb)] if total else [0]
-    if [int(x) for x in sizes] != expect:
+    if not np.array_equal(sizes, _raw_lengths(nb, c.block_size, c.total)):
         raise api.InvalidInput()
-    _verify(want, got, status)
-    if total == nb * cap:
+    if c.crcs is not None and bool(((got != c.crcs) & (status == 0)).any()):  # (every OK block: its recorded CRC)
+        raise api.InvalidInput()
+    if exact or c.total == nb * cap:
         return out.tobytes()
     return b"".join(out[b * cap: b * cap + int(sizes[b])].tobytes() for b in range(nb))
