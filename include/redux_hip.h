@@ -309,8 +309,8 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
  *                                 and returns cum in host memory.
  * redux_static_encode_blocks      redux_encode_blocks / redux_decode_blocks under the table cum, through the same chunk
  * redux_static_decode_blocks      pipeline (fleet included).  Block b's stream is that of redux_static_encode_blocks_dev; the
- *                                 streams depend on neither the chunk size nor the devices.  No byte-plane form: each plane
- *                                 would need its own table. */
+ *                                 streams depend on neither the chunk size nor the devices.  The byte-plane form, a table
+ *                                 per plane, is "plane-static coding" below. */
 int      redux_static_table_from_counts(const redux_params *p, const uint64_t *counts, uint32_t total, uint32_t *cum);
 uint64_t redux_histogram_workspace_bytes(uint64_t in_len);
 int      redux_histogram_dev(const void *d_in, uint64_t in_len, void *d_counts /* u64[256], ADDED to */, void *d_workspace,
@@ -336,7 +336,8 @@ int      redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, 
  *     and the container are then exactly those of the plain calls applied to the transformed bytes:
  *     stream_E(x)[b] == redux_encode_blocks(planes_E(x))[b].
  * (The adaptive model's cost of a block is the same for any order of its bytes: shuffling INSIDE a block gains nothing.)
- * Not available for the `_v` calls, redux_compress / redux_decompress and the static-table model.
+ * Not available for the `_v` calls and redux_compress / redux_decompress; with the static-table model it is "plane-static
+ * coding" below.
  *
  * redux_planes_check          OK for 1, 2, 4, 8, else INVALID_INPUT.
  * redux_planes_dev            the transform (inverse = 0) or its inverse (inverse != 0) of len bytes, d_src -> d_dst (device
@@ -458,6 +459,71 @@ int      redux_static_decode_blocks_crc(const redux_params *p, const uint32_t *c
                                         const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                                         uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- plane-static coding: one static table per byte plane ----------------------------------------
+ * The byte-plane layout and the semi-static model together: typed data (bf16 / fp32 / int64) whose planes have very different
+ * statistics, coded by the static coder under a table per plane.  E = element_size, one of 1, 2, 4, 8; B = block_size;
+ * x' = the byte-plane layout of the input for E and B ("byte-plane layout" above; E = 1: the input itself); block b of x' is
+ * x'[b*B .. min((b+1)*B, len)).
+ * The rule:
+ *   1. Table t, 0 <= t < E, is the table of "semi-static coding" (redux_static_table_from_counts) of the counts of the bytes
+ *      of all blocks b of x' with b mod E == t.  For full frames that is plane t; the short last frame is not special-cased:
+ *      its blocks are counted, and coded, by their index like any other.  A t that owns no bytes (len <= t*B) gets the table
+ *      of N = 0: every frequency 1, total 257.
+ *   2. Block b is coded under table b mod E by the static coder:
+ *      stream[b] == redux_static_encode_blocks(block b of x', cum[b mod E]); E = 1 is the static-table model, stream for stream.
+ *   3. Every table has the same total (one `total` argument), so one launch runs one kernel instance; the table of a t that
+ *      owns no bytes keeps total 257, and the only block ever coded under one is the empty input's block 0.
+ * Tables are u32[E][258], table t at cum + 258 t.  On the device they are read from device memory (d_cum), and the kernels
+ * check the table they load: one that is not strictly increasing from 0 to `total` (or to 257) makes its blocks INVALID_INPUT.
+ * Not available for the `_v` calls, redux_compress / redux_decompress and stored blocks; one set of tables per call (none
+ * per chunk or block range).
+ *
+ * redux_plane_static_table_check        every table passes redux_static_table_check, and all totals are equal (a table of
+ *                                       total 257, what a t without bytes gets, goes with any).  E = 1: one table.
+ * redux_plane_static_total              the common total of checked tables (the largest cum[257]).
+ * redux_plane_static_tables_from_counts rule 1 on the host from u64[E][256] counts.
+ * redux_plane_histogram_dev             ADDS the counts of x' = d_in[0 .. in_len) (already in the layout) to d_counts,
+ *                                       u64[E][256]: block b's bytes go to table b mod E.  Any block size and alignment.  A
+ *                                       buffer can be counted in pieces that are whole frames of E*B bytes.  Workspace: none.
+ * redux_plane_static_tables_dev         redux_static_table_dev for each t: d_counts + 256 t -> d_cum + 258 t.
+ * redux_plane_static_tables             host pointers, input in ORIGINAL order: chunks of whole frames are staged through the
+ *                                       pinned ring on the current device (as redux_static_table), laid out and counted there.
+ * redux_plane_static_encode_dev         device pointers, input in original order: the layout into the front of the workspace,
+ * redux_plane_static_decode_dev         then rule 2; decode is redux_decode_planes_dev's procedure under the static decoders
+ *                                       (plane buffer in the workspace, an OK block of the wrong length is INVALID_INPUT,
+ *                                       nothing outside d_out[0 .. out_len) is written, the summary last).  E = 1: no copy.
+ * redux_plane_static_encode_blocks_crc  host pointers through the chunk pipeline (fleet included), block_crc nullable: the
+ * redux_plane_static_decode_blocks_crc  CRCs are those of the ORIGINAL bytes, as for every layout.  The streams depend on
+ *                                       neither the chunk size nor the devices. */
+int      redux_plane_static_table_check(const redux_params *p, const uint32_t *cum /* u32[E][258] */, uint32_t element_size);
+uint32_t redux_plane_static_total(const uint32_t *cum, uint32_t element_size);
+int      redux_plane_static_tables_from_counts(const redux_params *p, const uint64_t *counts /* u64[E][256] */, uint32_t element_size,
+                                               uint32_t total, uint32_t *cum);
+uint64_t redux_plane_histogram_workspace_bytes(uint64_t in_len);
+int      redux_plane_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                                   void *d_counts /* u64[E][256], ADDED to */, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int      redux_plane_static_tables_dev(const redux_params *p, const void *d_counts, uint32_t element_size, uint32_t total,
+                                       void *d_cum /* u32[E][258] */, void *stream);
+int      redux_plane_static_tables(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                                   uint32_t total, uint32_t *cum);
+uint64_t redux_plane_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size);
+uint64_t redux_plane_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_plane_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int      redux_plane_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                       uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap,
+                                       void *d_out_offsets /* u64[nblocks+1] */, void *d_block_status /* i32[nblocks] */,
+                                       void *d_summary /* i32[2] */, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int      redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in,
+                                       const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len, uint32_t block_size,
+                                       uint32_t element_size, void *d_out, void *d_out_sizes /* u32[nblocks] */, void *d_block_status,
+                                       void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int      redux_plane_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                                              uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc);
+int      redux_plane_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
+                                              uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                                              uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the
@@ -482,6 +548,11 @@ const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out,
  * the kernels.  "" for arguments the _dev call rejects, and for nblocks == 0 (the decode call launches nothing). */
 const char *redux_static_encode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t in_len, uint32_t block_size);
 const char *redux_static_decode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t nblocks);
+/* The same for redux_plane_static_encode_dev / redux_plane_static_decode_dev (the k_*_plane_static* instances): the launch has
+ * element_size * ceil(ceil(nblocks / element_size) / 64) waves. */
+const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
+                                                  uint32_t element_size);
+const char *redux_plane_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size);
 
 /* Diagnostic, used by the parity tests only: *max_err = max over the integers x in [lo, hi] of
  * |v_rcp_f64(x) * x - 1| evaluated on the device.  The decoder's code-value division

@@ -6,9 +6,9 @@ here computes a bitstream on the CPU.
 """
 from .api import (  # noqa: F401
     Error, Eof, InvalidInput, IoError, OutputTooSmall, Unsupported,
-    Parameters, AdaptiveTreeModel, StaticModel, static_table, static_table_from_counts,
+    Parameters, AdaptiveTreeModel, StaticModel, PlaneStaticModel, static_table, static_table_from_counts, plane_static_tables,
     compress, decompress, compress_blocks, decompress_blocks, compress_blocks_v, decompress_blocks_v, block_table_v, BLOCK_DTYPE, BLOCK_IDLE,
     host_set_devices, host_chunk_plan, host_set_chunk_bytes,
-    DeviceEncoder, DeviceDecoder, DeviceStaticCoder, planes, gen_iid, gen_zipf, zipf_thresholds, version,
+    DeviceEncoder, DeviceDecoder, DeviceStaticCoder, DevicePlaneStaticCoder, planes, gen_iid, gen_zipf, zipf_thresholds, version,
     crc32_blocks, crc32_combine, STORE_RATIO,
 )

@@ -135,8 +135,39 @@ class StaticModel:
         return self.cum.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
+class PlaneStaticModel:
+    """Plane-static coding (include/redux_hip.h, "plane-static coding"): Parameters plus one static table per byte plane,
+    cums of shape (E, 258), E = element_size in 2 / 4 / 8; block b of the byte-plane layout is coded under table b mod E.
+    PlaneStaticModel.from_data builds the tables from the data.  compress_blocks and decompress_blocks take it where they
+    take Parameters; the layout's element size is the model's."""
+
+    def __init__(self, params, cums):
+        self.params = _params_of(params)
+        c = np.ascontiguousarray(cums, dtype=np.int64)
+        if c.ndim != 2 or c.shape[0] not in (2, 4, 8) or c.shape[1] != 258 or (c < 0).any() or (c > 0xFFFFFFFF).any():
+            raise InvalidInput()
+        self.cums = c.astype(np.uint32)
+        self.element_size = int(c.shape[0])
+        cp = self.params._c()
+        _raise(_lib.lib().redux_plane_static_table_check(C.byref(cp), self.cums.ctypes.data, self.element_size))
+
+    @classmethod
+    def from_data(cls, data, element_size, block_size, params=(8, 30, 32), total=None):
+        return cls(params, plane_static_tables(data, element_size, block_size, params, total))
+
+    def parameters(self):
+        return self.params
+
+    def total(self):
+        """the tables' common total (a table without bytes keeps 257)"""
+        return int(self.cums[:, -1].max())
+
+    def _cum_ptr(self):
+        return self.cums.ctypes.data
+
+
 def _params_of(model_or_params):
-    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel)):
+    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel, PlaneStaticModel)):
         return model_or_params.params
     if isinstance(model_or_params, Parameters):
         return model_or_params
@@ -215,6 +246,42 @@ def static_table(data, params=(8, 30, 32), total=None):
     return cum
 
 
+def plane_static_tables(data, element_size, block_size, params=(8, 30, 32), total=None):
+    """The tables of plane-static coding for `data` in ORIGINAL byte order: np.uint32[E, 258].  Host data goes through
+    redux_plane_static_tables; a torch uint8 device tensor is laid out and counted where it lies (redux_planes_dev,
+    redux_plane_histogram_dev, redux_plane_static_tables_dev, one read-back)."""
+    P = _params_of(params)
+    T = _total_of(P, total)
+    E = _check_element_size(element_size)
+    if E == 1 or not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    cp = P._c()
+    L = _lib.lib()
+    if not _is_device_tensor(data):
+        a = _u8(data)
+        cums = np.zeros((E, 258), dtype=np.uint32)
+        _raise(L.redux_plane_static_tables(C.byref(cp), _ptr(a), len(a), int(block_size), E, T, cums.ctypes.data))
+        return cums
+    torch = _torch()
+    with torch.cuda.device(data.device):
+        d_cum = _device_plane_tables(torch, L, cp, planes(data, E, block_size), E, int(block_size), T)
+        cums = d_cum.cpu().numpy().view(np.uint32).reshape(E, 258).copy()
+    if not cums.any(axis=1).all():  # the kernel's mark for N * R >= 2^64
+        raise Unsupported()
+    return cums
+
+
+def _device_plane_tables(torch, L, cp, d_x, E, block_size, total):
+    """x' (a uint8 device tensor already in the byte-plane layout) -> its E tables as an int32[E * 258] device tensor"""
+    counts = torch.zeros(E * 256, dtype=torch.int64, device=d_x.device)
+    d_cum = torch.zeros(E * 258, dtype=torch.int32, device=d_x.device)
+    s = _stream_ptr(torch)
+    _raise(L.redux_plane_histogram_dev(C.c_void_p(d_x.data_ptr()) if d_x.numel() else None, d_x.numel(), block_size, E,
+                                       C.c_void_p(counts.data_ptr()), None, 0, s))
+    _raise(L.redux_plane_static_tables_dev(C.byref(cp), C.c_void_p(counts.data_ptr()), E, total, C.c_void_p(d_cum.data_ptr()), s))
+    return d_cum
+
+
 def _is_device_tensor(x):
     try:
         import torch
@@ -253,26 +320,30 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
     layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
     params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks_crc); no element_size.
+    params may be a PlaneStaticModel: the layout of the model's element size, block b under table b mod E
+    (redux_plane_static_encode_blocks_crc); element_size must be 1 (the default: the model's is used) or the model's.
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 (zlib.crc32) of every input block, in original
     byte order for every layout (the `_crc` calls of include/redux_hip.h).
     stored: a np.uint8[nblocks] the same call fills with the stored-block flags (include/redux_hip.h, "stored blocks"):
     passing it turns stored blocks on, and block b's payload is then its raw (planes: plane) bytes wherever its stream
     is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it."""
-    static = isinstance(params, StaticModel)
+    static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
     cp = P._c()
     _raise(L.redux_device_supports(C.byref(cp)))
     E = _check_element_size(element_size)
-    # (a static model has one table for all byte planes, and its decoder has no table form for stored blocks)
-    if block_size <= 0 or (static and (E != 1 or stored is not None)) or (stored is not None and (
+    # (a static model has one table for all byte planes, and its decoder has no table form for stored blocks; a
+    # plane-static model brings its own element size)
+    if block_size <= 0 or (static and (E != 1 or stored is not None)) \
+            or (plane and (E not in (1, params.element_size) or stored is not None)) or (stored is not None and (
             not isinstance(store_ratio, (int, np.integer)) or not 0 <= store_ratio < 1 << 32)):
         raise InvalidInput()
     nb = L.redux_block_count(len(a), block_size)
     crc = _array_arg(block_crc, np.uint32, nb)
     flags = _array_arg(stored, np.uint8, nb)
-    cap = (L.redux_static_encode_bound if static else L.redux_encode_bound)(C.byref(cp), len(a), block_size)
+    cap = (L.redux_static_encode_bound if static or plane else L.redux_encode_bound)(C.byref(cp), len(a), block_size)
     out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
@@ -282,6 +353,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     elif static:
         st = L.redux_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
                                               cap, offs.ctypes.data, status.ctypes.data, crc)
+    elif plane:
+        st = L.redux_plane_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size,
+                                                    params.element_size, out.ctypes.data, cap, offs.ctypes.data,
+                                                    status.ctypes.data, crc)
     else:  # (element size 1 included: the coder without a layout)
         st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
                                               offs.ctypes.data, status.ctypes.data, crc)
@@ -307,13 +382,16 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
     (frames with a damaged block hold undefined bytes; their blocks' status says which).
     params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks_crc).
+    params may be a PlaneStaticModel (redux_plane_static_decode_blocks_crc): length is required, element_size is 1 (the
+    model's is used) or the model's, and out is the original bytes as with element_size > 1.
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
     order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK.
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
     uint8[length] in original order, as with element_size > 1."""
-    static = isinstance(params, StaticModel)
+    static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     E = _check_element_size(element_size)
     if block_size <= 0 or (static and (E != 1 or length is not None or stored is not None)) \
+            or (plane and (E not in (1, params.element_size) or length is None or stored is not None)) \
             or (length is None and (E > 1 or stored is not None)):
         raise InvalidInput()
     P = _params_of(params)
@@ -337,6 +415,10 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif static:
         st = L.redux_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
                                               out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data, crc)
+    elif plane:
+        st = L.redux_plane_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, length, block_size,
+                                                    params.element_size, out.ctypes.data, sizes.ctypes.data, status.ctypes.data,
+                                                    crc)
     elif length is not None:
         st = L.redux_decode_blocks_planes_crc(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
                                               sizes.ctypes.data, status.ctypes.data, crc)
@@ -718,6 +800,93 @@ class DeviceStaticCoder:
             C.c_void_p(self.dec_summary.data_ptr()), _stream_ptr(torch))
         _raise(st)
         return self.dec_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+
+
+class DevicePlaneStaticCoder:
+    """Plane-static coding on device tensors (include/redux_hip.h, "plane-static coding"): d_cum, an int32[E * 258] device
+    tensor of E tables with the common total `total`, stays on the device.  Input and output are in original byte order."""
+
+    def __init__(self, params, d_cum, total, element_size, block_size, max_in_len):
+        torch = _torch()
+        self.P = _params_of(params)
+        self.cp = self.P._c()
+        L = _lib.lib()
+        self.E = _check_element_size(element_size)
+        assert d_cum.is_cuda and d_cum.dtype == torch.int32 and d_cum.is_contiguous() and d_cum.numel() == self.E * 258
+        self.d_cum = d_cum
+        self.total = int(total)
+        self.block_size = int(block_size)
+        self.max_in_len = int(max_in_len)
+        self.device = d_cum.device
+        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
+        self.ws_bytes = max(L.redux_plane_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E),
+                            L.redux_plane_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
+        if self.ws_bytes == 0:
+            raise InvalidInput()
+        self.out_cap = L.redux_plane_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
+        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.dec_out = None
+
+    @classmethod
+    def from_data(cls, d_in, params, element_size, block_size, max_in_len, total=None):
+        """A coder whose tables are built from d_in (a uint8 device tensor, original order) on the device; nothing is
+        read back."""
+        torch = _torch()
+        P = _params_of(params)
+        T = _total_of(P, total)
+        E = _check_element_size(element_size)
+        with torch.cuda.device(d_in.device):
+            d_x = planes(d_in, E, block_size) if E > 1 else d_in
+            d_cum = _device_plane_tables(torch, _lib.lib(), P._c(), d_x, E, int(block_size), T)
+        return cls(P, d_cum, T, E, block_size, max_in_len)
+
+    def tables(self):
+        """the tables on the host: np.uint32[E, 258]"""
+        return self.d_cum.cpu().numpy().view(np.uint32).reshape(self.E, 258).copy()
+
+    def _ws_ptr(self):
+        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
+
+    @_on_device
+    def encode(self, d_in):
+        torch = _torch()
+        n = d_in.numel()
+        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        self.summary.zero_()
+        st = _lib.lib().redux_plane_static_encode_dev(
+            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_in.data_ptr()) if n else None, n,
+            self.block_size, self.E, C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
+            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+            _stream_ptr(torch))
+        _raise(st)
+        nb = _lib.lib().redux_block_count(n, self.block_size)
+        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+
+    @_on_device
+    def decode(self, d_streams, d_offsets, length):
+        """-> (the original bytes uint8[length], sizes, status, summary)"""
+        torch = _torch()
+        nb = d_offsets.numel() - 1
+        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= length <= self.max_in_len
+        if nb != _lib.lib().redux_block_count(length, self.block_size):
+            raise InvalidInput()
+        if self.dec_out is None:
+            self.dec_out = torch.empty(max(self.max_in_len, 1), dtype=torch.uint8, device=self.device)
+            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.dec_summary.zero_()
+        st = _lib.lib().redux_plane_static_decode_dev(
+            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
+            C.c_void_p(d_offsets.data_ptr()), length, self.block_size, self.E, C.c_void_p(self.dec_out.data_ptr()),
+            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
+            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
+        _raise(st)
+        return self.dec_out[:length], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
 
 
 # ---- byte-plane layout of typed data ----------------------------------------------------------

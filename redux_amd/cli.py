@@ -1,7 +1,7 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
-                            [--model adaptive|static] [--checksum] [--stored]
+                            [--model adaptive|static|plane-static] [--checksum] [--stored]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -13,20 +13,23 @@ fp64 / int64 -- in the byte-plane layout (container version 2); decoding reads t
 A raw reference stream has no place to record it: `--element-size` above 1 with `--block-size 0` is a usage error.
 `--model static` (with a block size, element size 1) builds one static frequency table from the whole input and codes
 every block under it (container version 3, which records the table); `--model adaptive`, the default, is the
-reference's model.  Decoding reads the model from the container.
+reference's model.  `--model plane-static` (with a block size and `--element-size 2|4|8`) builds one static table per
+byte plane of the layout and codes each plane's blocks under its own (container version 4, which records the E tables);
+without a block size, with `--element-size` absent or 1, or with `--stored` it is a usage error.  Decoding reads the model
+from the container.
 `--checksum` (with -c and a block size) records the CRC-32 (zlib.crc32) of every block's uncompressed bytes in the container
 (version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
 damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
 table: `--checksum` with `--block-size 0` is a usage error.
 `--stored` (with -c and a block size, adaptive model) writes a block whose stream would not be smaller than the block as
 its raw bytes (container flag 0x40): incompressible data then costs no more than its own size plus the tables, and
-decodes as a copy.  -d reads any stored container.  `--stored` with `--block-size 0` or `--model static` is a usage error.
+decodes as a copy.  -d reads any stored container.  `--stored` with `--block-size 0` or a static model is a usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static>] [--checksum] [--stored]")
+         "[--model <adaptive|static|plane-static>] [--checksum] [--stored]")
 
 
 def parse(argv):
@@ -54,7 +57,7 @@ def parse(argv):
                     return None
                 opts["element_size"] = int(val)
             elif arg == "--model":
-                if val not in ("adaptive", "static"):
+                if val not in ("adaptive", "static", "plane-static"):
                     return None
                 opts["model"] = val
             else:
@@ -70,9 +73,11 @@ def parse(argv):
         return None  # a raw reference stream has no place to record the element size
     if opts.get("model") == "static" and (opts["block_size"] == 0 or opts.get("element_size", 1) != 1):
         return None  # the table lives in the container (not in a raw stream), and there is one table, not one per plane
+    if opts.get("model") == "plane-static" and (opts["block_size"] == 0 or opts.get("element_size", 1) == 1):
+        return None  # the tables live in the container, one per byte plane of the layout
     if opts.get("checksum") and opts["compress"] and opts["block_size"] == 0:
         return None  # the table lives in the container (-d verifies whatever table a container has)
-    if opts.get("stored") and opts["compress"] and (opts["block_size"] == 0 or opts.get("model") == "static"):
+    if opts.get("stored") and opts["compress"] and (opts["block_size"] == 0 or opts.get("model") in ("static", "plane-static")):
         return None  # the bitmap lives in the container, and the static decoder has no table form
     return None if opts["compress"] is None else opts
 

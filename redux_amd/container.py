@@ -6,13 +6,15 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 
 Layout (little-endian):
     0   4  magic  b"RDXB"
-    4   1  version (1; 2 = byte-plane layout; 3 = static-table model)
+    4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
-   12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8
+   12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
+           the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008)
    16   8  nblocks
    24   8  total uncompressed length
    (version 3 only) 4*258  the static table cum[0..=257], u32
+   (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    ..  4*nblocks   compressed size of each block
    (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
    (flag 0x40 only) ceil(nblocks/8)  stored-block bitmap: bit b % 8 of byte b // 8 (LSB first) = block b is stored
@@ -26,7 +28,11 @@ Version 3 holds streams of the static-table model (include/redux_hip.h, "static-
 the header is followed by the table the blocks were coded under, and decoding uses it.  A table that
 redux_static_table_check rejects is InvalidInput, a truncated one Eof.
 
-Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13: versions 1 / 2 / 3 with checksums) means a table of nblocks
+Version 4 holds streams of plane-static coding (include/redux_hip.h, "plane-static coding"): the byte-plane layout of
+version 2, block b coded by the static coder under table b mod E.  Tables that redux_plane_static_table_check rejects are
+InvalidInput, truncated ones Eof.  It has no stored blocks (no 0x44).
+
+Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14: versions 1 / 2 / 3 / 4 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -50,6 +56,7 @@ MAGIC = b"RDXB"
 VERSION = 1
 VERSION_PLANES = 2
 VERSION_STATIC = 3
+VERSION_PLANE_STATIC = 4
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
 CRC_FLAG = 0x10  # version bit: a table of per-block CRC-32 values follows the size table
 STORED_FLAG = 0x40  # version bit: a stored-block bitmap follows the size table (and the CRC table)
@@ -70,17 +77,22 @@ def _raw_lengths(nblocks, block_size, total):
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
+    params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap."""
-    static = isinstance(params, api.StaticModel)
-    if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1):
+    static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
+    if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1) \
+            or (plane and element_size not in (1, params.element_size)):
         raise api.InvalidInput()
+    if plane:
+        element_size = params.element_size
     P = api._params_of(params)
     offs = np.asarray(offsets, dtype=np.uint64)
     sizes = np.diff(offs.astype(np.int64))
     if (sizes < 0).any() or (sizes > 0xFFFFFFFF).any():
         raise api.InvalidInput()
-    ver, res = (VERSION_STATIC, 0) if static else (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
+    ver, res = (VERSION_STATIC, 0) if static else (VERSION_PLANE_STATIC, element_size << 16 | element_size) if plane \
+        else (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -91,7 +103,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     bitmap = b""
     if stored is not None:
         f = np.asarray(stored)
-        if static or f.shape != (len(sizes),) or bool((f > 1).any()) \
+        if static or plane or f.shape != (len(sizes),) or bool((f > 1).any()) \
                 or bool((sizes[f == 1] != _raw_lengths(len(sizes), block_size, total_len)[f == 1]).any()):
             raise api.InvalidInput()
         ver |= STORED_FLAG
@@ -99,6 +111,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if static:
         head += params.cum.astype("<u4").tobytes()
+    if plane:
+        head += params.cums.astype("<u4").tobytes()
     return head + sizes.astype("<u4").tobytes() + crc + bitmap + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
 
@@ -111,10 +125,12 @@ def _version_ok(ver, res):
     """a known layout, its reserved word, and no stored blocks with a static table"""
     layout = _layout(ver)
     return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
-        or (layout == VERSION_PLANES and res in ELEMENT_SIZES)
+        or (layout == VERSION_PLANES and res in ELEMENT_SIZES) \
+        or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF)
 
 
-# What _parse reads from a container: element_size 1, or E of version 2; static the StaticModel of a version 3 table;
+# What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
+# or the PlaneStaticModel of version 4's tables;
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
 # of 0 / 1.  static, crcs and stored are None where the container has no such section.
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored")
@@ -131,7 +147,7 @@ def _header(b):
     P = api.Parameters(sb, fb, cb)
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
-    return ver, P, block_size, res if _layout(ver) == VERSION_PLANES else 1, nblocks, total
+    return ver, P, block_size, res & 0xFFFF if _layout(ver) in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1, nblocks, total
 
 
 def _take(b, at, dtype, count):
@@ -154,6 +170,12 @@ def _parse(buf):
         try:
             static = api.StaticModel(P, cum)
         except api.Error:  # (redux_static_table_check: a bad table, or parameters the static coder does not take)
+            raise api.InvalidInput()
+    if _layout(ver) == VERSION_PLANE_STATIC:
+        cums, at = _take(b, at, "<u4", 258 * E)
+        try:
+            static = api.PlaneStaticModel(P, cums.reshape(E, 258))
+        except api.Error:  # (redux_plane_static_table_check)
             raise api.InvalidInput()
     sizes, at = _take(b, at, "<u4", nblocks)
     sizes = sizes.astype(np.uint64)
@@ -195,16 +217,23 @@ def block_stored(buf):
 
 
 def element_size(buf):
-    """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for version 2.  Malformed
+    """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for versions 2 and 4.  Malformed
     containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).element_size
 
 
 def static_table(buf):
-    """The static table (np.uint32[258]) a version 3 container records; None for versions 1 and 2.  Malformed containers
+    """The static table (np.uint32[258]) a version 3 container records; None for versions 1, 2 and 4.  Malformed
+    containers raise InvalidInput, truncated ones Eof."""
+    static = _parse(buf).static
+    return static.cum if isinstance(static, api.StaticModel) else None
+
+
+def plane_static_tables(buf):
+    """The tables (np.uint32[E, 258]) a version 4 container records; None for versions 1, 2 and 3.  Malformed containers
     raise InvalidInput, truncated ones Eof."""
     static = _parse(buf).static
-    return None if static is None else static.cum
+    return static.cums if isinstance(static, api.PlaneStaticModel) else None
 
 
 def header_is_wellformed(buf):
@@ -225,14 +254,18 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
-    stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with model "static"."""
+    model "plane-static" (element_size 2 / 4 / 8): a static table per byte plane, built from the data
+    (api.plane_static_tables, default total), version 4.
+    stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with a static model."""
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
-            or model not in ("adaptive", "static") or (model == "static" and (element_size != 1 or stored)):
+            or model not in ("adaptive", "static", "plane-static") or (model == "static" and (element_size != 1 or stored)) \
+            or (model == "plane-static" and (element_size == 1 or stored)):
         raise api.InvalidInput()
     nb = max(1, -(-len(data) // block_size))
     crc = np.zeros(nb, dtype=np.uint32) if checksum else None
     flags = np.zeros(nb, dtype=np.uint8) if stored else None
-    m = api.StaticModel.from_data(data, params) if model == "static" else params
+    m = api.StaticModel.from_data(data, params) if model == "static" \
+        else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" else params
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags)
 
@@ -251,7 +284,8 @@ def decompress_bytes(buf):
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if exact:  # (the blocks decode at their real size, into out[0 .. total))
-            out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size, c.params,
+            out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
+                                                       c.static if c.element_size > 1 and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
                                                        stored=c.stored)
         else:  # (straight into out[b * cap ..], no plane buffer)

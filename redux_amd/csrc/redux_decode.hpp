@@ -502,11 +502,13 @@ __device__ __forceinline__ void dec_commit_careful(DecLane &S, const DecFound &f
 template <bool CB32, int MODE>
 __device__ __forceinline__ void decode_lock_body(const DecArgs &a, uint32_t *lds, const uint32_t *cum, double rc_static,
                                                  uint32_t lane = threadIdx.x, uint64_t group = blockIdx.x,
-                                                 const uint8_t *lut = nullptr, const uint32_t *ctab = nullptr)
+                                                 const uint8_t *lut = nullptr, const uint32_t *ctab = nullptr,
+                                                 const uint32_t stride = 1, const uint32_t first = 0)
 {
     static_assert(MODE == 1 || MODE == 2, "static models only");
     constexpr uint32_t kModelBytes = MODE == 2 ? 0 : kStaticTreeDwords * 4;
-    const uint64_t blk  = group * 64 + lane;
+    // (stride E, first t: the blocks of table t, redux_plane_static.hpp; 1, 0: consecutive blocks)
+    const uint64_t blk  = (group * 64 + lane) * stride + first;
     const bool     live = blk < a.nblocks;
 
     if (MODE == 1) { // (MODE 2: tables filled by the caller, which also synchronises)

@@ -13,6 +13,7 @@
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
+//   redux_plane_static.hpp  k_plane_hist / k_*_plane_static*: the static coder with one table per byte plane
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
@@ -33,6 +34,7 @@
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
 #include "redux_hist.hpp"
+#include "redux_plane_static.hpp"
 #include "redux_crc.hpp"
 #include "redux_store.hpp"
 
@@ -41,6 +43,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1947,6 +1950,413 @@ int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const u
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
 {
     return redux_decode_blocks_planes_crc(p, in, in_offsets, out_len, block_size, element_size, out, out_sizes, block_status, nullptr);
+}
+
+// ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------
+// E tables, table b mod E for block b of the byte-plane layout.  The launch shape: table t's blocks are cut into wave slots
+// of 64, every table gets as many slots as table 0 (which owns the most blocks), and workgroup g serves t = g mod E.
+static uint64_t plane_slots(uint64_t nblocks, uint32_t E) { return ((nblocks + E - 1) / E + 63) / 64; } // wave slots per table
+
+static int plane_static_check(const redux_params *p, uint32_t element_size, uint32_t total)
+{
+    int st = static_total_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    return redux_planes_check(element_size);
+}
+
+int redux_plane_static_table_check(const redux_params *p, const uint32_t *cum, uint32_t element_size)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p))
+        return REDUX_UNSUPPORTED;
+    if (redux_planes_check(element_size) != REDUX_OK || !cum)
+        return REDUX_INVALID_INPUT;
+    uint32_t total = 0; // of the tables that own bytes; a table that owns none is all ones (total 257)
+    for (uint32_t t = 0; t < element_size; t++) {
+        const uint32_t *c = cum + kStaticEntries * t;
+        if ((st = static_check(p, c)) != REDUX_OK)
+            return st;
+        if (c[kStaticEntries - 1] == kStaticEntries - 1)
+            continue;
+        if (total && c[kStaticEntries - 1] != total)
+            return REDUX_INVALID_INPUT;
+        total = c[kStaticEntries - 1];
+    }
+    return REDUX_OK;
+}
+
+uint32_t redux_plane_static_total(const uint32_t *cum, uint32_t element_size)
+{
+    uint32_t total = kStaticEntries - 1;
+    for (uint32_t t = 0; cum && t < element_size; t++)
+        if (cum[kStaticEntries * t + kStaticEntries - 1] > total)
+            total = cum[kStaticEntries * t + kStaticEntries - 1];
+    return total;
+}
+
+int redux_plane_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint32_t element_size, uint32_t total,
+                                          uint32_t *cum)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!counts || !cum)
+        return REDUX_INVALID_INPUT;
+    for (uint32_t t = 0; t < element_size; t++)
+        if ((st = redux_static_table_from_counts(p, counts + 256 * t, total, cum + kStaticEntries * t)) != REDUX_OK)
+            return st;
+    return REDUX_OK;
+}
+
+uint64_t redux_plane_histogram_workspace_bytes(uint64_t in_len)
+{
+    (void)in_len; // (k_plane_hist keeps everything in LDS and registers)
+    return 0;
+}
+
+int redux_plane_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size, void *d_counts,
+                              void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    (void)d_workspace;
+    (void)workspace_bytes;
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !d_counts || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    if (in_len == 0)
+        return REDUX_OK;
+    PlaneHistArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.nfull      = in_len / block_size;
+    a.block_size = block_size;
+    a.E          = element_size;
+    a.vec        = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    const uint32_t V = block_size / 16;
+    a.vshift     = a.vec && (V & (V - 1)) == 0 ? (uint32_t)__builtin_ctz(V) : 0xFFFFFFFFu;
+    a.counts     = (unsigned long long *)d_counts;
+    // workgroups per table: as redux_histogram_dev over a table's share of the bytes
+    const uint64_t share = in_len / element_size, per = a.vec ? share / (16ull * 64 * kHistUnroll) : (share + block_size - 1) / block_size;
+    const uint64_t cap   = (uint64_t)kHistWgsPerCu * cu_count() / element_size;
+    a.wgs                = (uint32_t)(per < 1 ? 1 : per < cap ? per : cap < 1 ? 1 : cap);
+    k_plane_hist<<<a.wgs * element_size, 64, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_plane_static_tables_dev(const redux_params *p, const void *d_counts, uint32_t element_size, uint32_t total, void *d_cum,
+                                  void *stream)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_counts || !d_cum)
+        return REDUX_INVALID_INPUT;
+    for (uint32_t t = 0; t < element_size; t++)
+        k_static_table<<<1, 256, 0, (hipStream_t)stream>>>((const unsigned long long *)d_counts + 256 * t, total,
+                                                           (uint32_t *)d_cum + kStaticEntries * t);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_plane_static_tables(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                              uint32_t total, uint32_t *cum)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !cum || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    uint64_t counts[8 * 256];
+    if ((st = host::byte_histogram(in, in_len, counts, block_size, element_size)) != REDUX_OK) // redux_host.hpp
+        return st;
+    return redux_plane_static_tables_from_counts(p, counts, element_size, total, cum);
+}
+
+// 64 slots / blocks of one wave, E apart, within a 32-bit lane offset
+static bool plane_static_fits(const Geometry &g, uint32_t block_size, uint32_t E)
+{
+    return 64ull * E * g.slot_bytes < (1ull << 32) && 64ull * E * block_size < (1ull << 32);
+}
+
+static const char *plane_static_name(bool decode, int k)
+{
+    static const char *const enc[4] = {"k_encode_plane_static<true, false> (total >= 2^17: quotient fix-up)",
+                                       "k_encode_plane_static<false, true, true> (code_bits 32, one wave per SIMD)",
+                                       "k_encode_plane_static<false, true> (code_bits 32)",
+                                       "k_encode_plane_static<false, false> (code_bits < 32)"};
+    static const char *const dec[9] = {
+        "k_decode_plane_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)",
+        "k_decode_plane_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)",
+        "k_decode_plane_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)",
+        "k_decode_plane_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)",
+        "k_decode_plane_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)",
+        "k_decode_plane_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)",
+        "k_decode_plane_static_lock<true, false> (lock-step, code_bits 32)",
+        "k_decode_plane_static_lock<false, true> (lock-step, one wave per SIMD)",
+        "k_decode_plane_static_lock<false, false> (lock-step)"};
+    return decode ? dec[k] : enc[k];
+}
+
+const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
+                                                  uint32_t element_size)
+{
+    if (plane_static_check(p, element_size, total) != REDUX_OK || block_size == 0)
+        return "";
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (!plane_static_fits(g, block_size, element_size))
+        return "";
+    return plane_static_name(false, (int)pick_static_encode_kernel(p, total, 64 * element_size * plane_slots(g.nblocks, element_size)));
+}
+
+const char *redux_plane_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size)
+{
+    if (plane_static_check(p, element_size, total) != REDUX_OK || nblocks == 0)
+        return "";
+    return plane_static_name(true, (int)pick_static_decode_kernel(p, total, 64 * element_size * plane_slots(nblocks, element_size)));
+}
+
+uint64_t redux_plane_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
+{
+    return redux_static_encode_bound(p, in_len, block_size);
+}
+
+uint64_t redux_plane_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_planes_check(element_size) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_static_encode_workspace_bytes(p, in_len, block_size);
+    return ws == 0 || element_size == 1 ? ws : planes_copy_bytes(in_len) + ws;
+}
+
+uint64_t redux_plane_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    if (check_params(p) != REDUX_OK || is_any(p) || redux_planes_check(element_size) != REDUX_OK || block_size == 0)
+        return 0;
+    return planes_copy_bytes(redux_block_count(out_len, block_size) * (uint64_t)block_size);
+}
+
+// the static coder over x' (d_x: the layout of the input, or the input itself for E = 1) under the tables at d_cum
+static int plane_static_encode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_x, uint64_t in_len,
+                                 uint32_t block_size, uint32_t E, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                                 void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (workspace_bytes < g.total)
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (!plane_static_fits(g, block_size, E))
+        return REDUX_UNSUPPORTED;
+    hipStream_t s  = (hipStream_t)stream;
+    uint8_t    *ws = (uint8_t *)d_workspace;
+    HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
+    PlaneStaticEncArgs a;
+    a.c.in         = (const uint8_t *)d_x;
+    a.c.in_len     = in_len;
+    a.c.nblocks    = g.nblocks;
+    a.c.slots      = ws + g.off_slots;
+    a.c.slot_bytes = g.slot_bytes;
+    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
+    a.c.status     = (int32_t *)d_block_status;
+    a.c.rc         = static_rc(total);
+    a.c.block_size = block_size;
+    a.c.slot_cap   = g.slot_cap;
+    a.c.code_bits  = p->code_bits;
+    a.c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    a.t.cum        = (const uint32_t *)d_cum;
+    a.t.E          = E;
+    a.t.total      = total;
+    a.t.rc257      = static_rc(kStaticEntries - 1);
+    const uint64_t slots = plane_slots(g.nblocks, E);
+    const uint32_t grid  = (uint32_t)(slots * E);
+    switch (pick_static_encode_kernel(p, total, 64 * E * slots)) {
+    case StaticEncKernel::Fixup: k_encode_plane_static<true, false><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32Solo: k_encode_plane_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32: k_encode_plane_static<false, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Narrow: k_encode_plane_static<false, false><<<grid, 64, 0, s>>>(a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_plane_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                  uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                                  void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
+        return REDUX_INVALID_INPUT;
+    if (element_size == 1)
+        return plane_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, d_out, out_cap, d_out_offsets, d_block_status,
+                                     d_summary, d_workspace, workspace_bytes, stream);
+    const uint64_t copy = planes_copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *x = (uint8_t *)d_workspace;
+    if ((st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+        return st;
+    return plane_static_encode_x(p, d_cum, total, x, in_len, block_size, element_size, d_out, out_cap, d_out_offsets, d_block_status,
+                                 d_summary, x + copy, workspace_bytes - copy, stream);
+}
+
+// the static decoders under E tables: nblocks streams -> block b at d_planes + b * block_size
+static int plane_static_decode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                 uint64_t nblocks, uint32_t block_size, uint32_t E, void *d_planes, void *d_out_sizes,
+                                 void *d_block_status, hipStream_t s)
+{
+    PlaneStaticLockArgs la;
+    memset(&la, 0, sizeof la);
+    la.d.in         = (const uint8_t *)d_in;
+    la.d.in_offsets = (const uint64_t *)d_in_offsets;
+    la.d.nblocks    = nblocks;
+    la.d.out        = (uint8_t *)d_planes;
+    la.d.out_sizes  = (uint32_t *)d_out_sizes;
+    la.d.status     = (int32_t *)d_block_status;
+    la.d.block_size = block_size;
+    la.d.nfreeze    = 0xFFFFFFFFu;
+    la.d.code_bits  = p->code_bits;
+    la.d.aligned4   = ((((uintptr_t)d_planes) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    if (la.d.aligned4 && (((uintptr_t)d_planes) & 15) == 0 && (block_size & 15) == 0)
+        la.d.aligned4 = 2;
+    la.rc      = static_rc(total);
+    la.t.cum   = (const uint32_t *)d_cum;
+    la.t.E     = E;
+    la.t.total = total;
+    la.t.rc257 = static_rc(kStaticEntries - 1);
+    const uint64_t slots = plane_slots(nblocks, E);
+    const uint32_t grid  = (uint32_t)(slots * E), grid4 = (uint32_t)((slots + 3) / 4 * E), grid8 = (uint32_t)((slots + 7) / 8 * E);
+    switch (pick_static_decode_kernel(p, total, 64 * E * slots)) {
+    case StaticDecKernel::Fixup: {
+        PlaneStaticDecArgs a;
+        a.c.in         = la.d.in;
+        a.c.in_offsets = la.d.in_offsets;
+        a.c.nblocks    = nblocks;
+        a.c.out        = la.d.out;
+        a.c.out_sizes  = la.d.out_sizes;
+        a.c.status     = la.d.status;
+        a.c.rc         = la.rc;
+        a.c.block_size = block_size;
+        a.c.code_bits  = p->code_bits;
+        a.c.aligned4   = la.d.aligned4 ? 1 : 0;
+        a.t            = la.t;
+        k_decode_plane_static<true><<<grid, 64, 0, s>>>(a);
+        break;
+    }
+    case StaticDecKernel::LutCb32Solo: k_decode_plane_static_lut<true, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutSolo: k_decode_plane_static_lut<false, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutCb32: k_decode_plane_static_lut<true, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::Lut: k_decode_plane_static_lut<false, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32Solo: k_decode_plane_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32: k_decode_plane_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockSolo: k_decode_plane_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::Lock: k_decode_plane_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// the blocks decode into a plane buffer at the front of the workspace (block_size bytes of room each, so a damaged stream
+// writes nothing outside it); their sizes are checked against the layout; the inverse transform writes d_out[0 .. out_len);
+// the summary comes last
+int redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                  uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
+                                  void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status || (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    if (workspace_bytes < redux_plane_static_decode_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t    *x = (uint8_t *)d_workspace;
+    if ((st = plane_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, element_size, x, d_out_sizes,
+                                    d_block_status, s)) != REDUX_OK)
+        return st;
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
+                                                                        nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    if ((st = redux_planes_dev(x, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
+        return st;
+    if (d_summary)
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// The coders of the chunked host calls.  The tables travel to each chunk's device behind the coder's workspace (8 KiB at
+// most, stream-ordered).  A chunk is whole 64-block waves, so its first block is a multiple of every E and b mod E inside
+// the chunk is the global one: checked (a call of one chunk starts at block 0 whatever its size).
+static uint64_t plane_tables_bytes(uint32_t E) { return align_up((uint64_t)E * kStaticEntries * 4, 256); }
+
+static host::EncodeCoder plane_static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size, uint32_t E)
+{
+    const uint32_t total = redux_plane_static_total(cum, E);
+    auto           chunk = std::make_shared<uint64_t>(0); // bytes of a full chunk when the call has several
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                *chunk = several ? max_in : 0;
+                ws     = plane_tables_bytes(E) + redux_plane_static_encode_workspace_bytes(p, max_in, block_size, E);
+                bound  = redux_plane_static_encode_bound(p, max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                if (*chunk % ((uint64_t)E * block_size) != 0)
+                    return REDUX_UNSUPPORTED;
+                const uint64_t tb = plane_tables_bytes(E);
+                if (ws_bytes < tb)
+                    return REDUX_OUTPUT_TOO_SMALL;
+                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)E * kStaticEntries * 4, hipMemcpyHostToDevice, st));
+                return redux_plane_static_encode_dev(p, ws, total, s.d_in.p, len, block_size, E, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                                     s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+            }};
+}
+
+static host::DecodeCoder plane_static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size, uint32_t E)
+{
+    const uint32_t total = redux_plane_static_total(cum, E);
+    auto           cbs   = std::make_shared<uint64_t>(0); // blocks of a full chunk
+    return {[=](uint64_t cb) {
+                *cbs = cb;
+                return plane_tables_bytes(E) + redux_plane_static_decode_workspace_bytes(p, cb * (uint64_t)block_size, block_size, E);
+            },
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                if (*cbs % E != 0 && nb != *cbs) // (a chunk size that is no multiple of E: the call's only chunk)
+                    return REDUX_UNSUPPORTED;
+                const uint64_t tb = plane_tables_bytes(E);
+                if (ws_bytes < tb)
+                    return REDUX_OUTPUT_TOO_SMALL;
+                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)E * kStaticEntries * 4, hipMemcpyHostToDevice, st));
+                return redux_plane_static_decode_dev(p, ws, total, s.d_in.p, s.d_off.p, out_bytes, block_size, E, s.d_out.p, s.d_sz.p,
+                                                     s.d_st.p, s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+            },
+            true};
+}
+
+int redux_plane_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                         uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                                         uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = redux_plane_static_table_check(p, cum, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               plane_static_encoder(p, cum, block_size, element_size), block_crc); // redux_host.hpp
+}
+
+int redux_plane_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
+                                         uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                                         uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    const int st = redux_plane_static_table_check(p, cum, element_size);
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, plane_static_decoder(p, cum, block_size, st == REDUX_OK ? element_size : 1),
+                              block_crc);
 }
 
 // ---- stored blocks (redux_store.hpp) --------------------------------------------------------------

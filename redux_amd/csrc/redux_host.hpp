@@ -893,8 +893,11 @@ static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t
 // redux_host_set_devices is not used: the result is 2 KiB, there is nothing to spread), and k_byte_hist of each chunk adds
 // into one u64[256] on the device.  Chunk j runs on stream j % kStreams and slot j % kSlots, so the staging of a chunk
 // into a slot is ordered after the kernel that read the slot's previous chunk.  One read-back at the end.
+// E > 1 (redux_plane_static_tables): counts is u64[E][256], the counts of the byte-plane layout's blocks b by b mod E.  The
+// chunks are then whole frames of E * block_size bytes, so that a chunk's layout is its part of the whole input's and its
+// first block is a multiple of E; the layout of each chunk goes into the slot's workspace and k_plane_hist counts that.
 // ================================================================================================
-static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
+static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts, uint32_t block_size = 0, uint32_t E = 1)
 {
     Ctx *cp  = nullptr;
     int  dev = 0;
@@ -908,14 +911,22 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
         return rc;
     uint64_t chunk = clamp_chunk_bytes((in_len + kSlots - 1) / kSlots, kEncChunkMax);
     chunk = (chunk + 65535) / 65536 * 65536; // (whole 64 KiB: the test hook's 1-byte chunks become 64 KiB)
+    if (E > 1) {
+        const uint64_t frame = (uint64_t)E * block_size;
+        chunk = (chunk + frame - 1) / frame * frame;
+    }
     const uint64_t nchunks = (in_len + chunk - 1) / chunk;
     const int      nslots  = (int)(nchunks < (uint64_t)kSlots ? nchunks : (uint64_t)kSlots);
-    if ((rc = grow_buf(c, c.d_counts, 256 * 8)) != REDUX_OK)
+    const size_t   cbytes  = (size_t)E * 256 * 8;
+    if ((rc = grow_buf(c, c.d_counts, cbytes)) != REDUX_OK)
         return rc;
-    for (int i = 0; i < nslots; i++)
+    for (int i = 0; i < nslots; i++) {
         if ((rc = grow_buf(c, c.slot[i].d_in, chunk + 16)) != REDUX_OK)
             return rc;
-    HOST_TRY(hipMemsetAsync(c.d_counts.p, 0, 256 * 8, c.stream[0]));
+        if (E > 1 && (rc = grow_buf(c, c.slot[i].d_ws, chunk + 16)) != REDUX_OK)
+            return rc;
+    }
+    HOST_TRY(hipMemsetAsync(c.d_counts.p, 0, cbytes, c.stream[0]));
     HOST_TRY(hipStreamSynchronize(c.stream[0])); // (the other streams do not wait for stream 0)
     {
         CopyPool pool(kCopyThreads - 1);
@@ -925,14 +936,18 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts)
             hipStream_t    st = c.stream[j % kStreams];
             void          *d  = c.slot[j % kSlots].d_in.p;
             rc = stage_h2d(c, pool, piece_no, d, in + o, n, st);
-            if (rc == REDUX_OK)
+            if (rc == REDUX_OK && E > 1) {
+                void *x = c.slot[j % kSlots].d_ws.p;
+                if ((rc = redux_planes_dev(d, x, n, block_size, E, 0, st)) == REDUX_OK)
+                    rc = redux_plane_histogram_dev(x, n, block_size, E, c.d_counts.p, nullptr, 0, st);
+            } else if (rc == REDUX_OK)
                 rc = redux_histogram_dev(d, n, c.d_counts.p, nullptr, 0, st);
         }
     }
     for (int i = 0; i < kStreams; i++) // nothing of this call stays in flight
         if (hipStreamSynchronize(c.stream[i]) != hipSuccess && rc == REDUX_OK)
             rc = REDUX_IO_ERROR;
-    if (rc == REDUX_OK && hipMemcpy(counts, c.d_counts.p, 256 * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    if (rc == REDUX_OK && hipMemcpy(counts, c.d_counts.p, cbytes, hipMemcpyDeviceToHost) != hipSuccess)
         rc = REDUX_IO_ERROR;
     ctx_trim_locked(c);
     return rc;

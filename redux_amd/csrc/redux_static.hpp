@@ -38,7 +38,7 @@ struct StaticTable { // passed by value in the kernel arguments (1032 bytes)
     uint32_t cum[kStaticEntries];
 };
 
-struct StaticEncArgs {
+struct StaticEncCore { // everything but the table: shared with the E-table kernels of redux_plane_static.hpp
     const uint8_t *in;
     uint64_t       in_len;
     uint64_t       nblocks;
@@ -51,7 +51,10 @@ struct StaticEncArgs {
     uint32_t       slot_cap;
     uint32_t       code_bits;
     uint32_t       aligned16; // in and block_size are 16-byte multiples
-    StaticTable    tab;
+};
+
+struct StaticEncArgs : StaticEncCore {
+    StaticTable tab;
 };
 
 // Sixteen data symbols straight-line, all 64 lanes active, stores unchecked (the caller has
@@ -86,17 +89,14 @@ __device__ __forceinline__ void static_chunk(EncState &S, const uint32_t *tab, c
 template <bool SOLO>
 __device__ __forceinline__ void claim_the_simd();
 
-template <bool FIXUP, bool CB32, bool SOLO = false>
-__global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
+// The coder wave: lane l codes block blk0 + l * stride under the table in LDS (blk0 < nblocks).  stride 1 is the one-table
+// kernel below; the E-table kernels (redux_plane_static.hpp) pass stride E, so that a wave's 64 blocks share a table.
+template <bool FIXUP, bool CB32>
+__device__ __forceinline__ void static_encode_body(const StaticEncCore &a, const uint32_t *tab, const uint64_t blk0,
+                                                   const uint32_t stride = 1)
 {
-    __shared__ uint32_t tab[kStaticEntries + 2];
-    claim_the_simd<SOLO>();
     const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < kStaticEntries; i += 64)
-        tab[i] = a.tab.cum[i];
-    __syncthreads();
-    const uint64_t blk0 = (uint64_t)blockIdx.x * 64;
-    const uint64_t blk  = blk0 + lane;
+    const uint64_t blk  = blk0 + (uint64_t)lane * stride;
     const bool     live = blk < a.nblocks;
     uint32_t       len  = 0;
     if (live) {
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
     const uint8_t *src   = a.in + (live ? blk : blk0) * (uint64_t)a.block_size;
     uint8_t       *wdst  = a.slots + blk0 * a.slot_bytes;
     // dead lanes of the last wave own the spare slot behind the last real one (they store nothing)
-    const uint32_t off0  = live ? lane * (uint32_t)a.slot_bytes : (uint32_t)(a.nblocks - blk0) * (uint32_t)a.slot_bytes;
+    const uint32_t off0  = live ? lane * stride * (uint32_t)a.slot_bytes : (uint32_t)(a.nblocks - blk0) * (uint32_t)a.slot_bytes;
     const uint32_t limit = off0 + a.slot_cap;
     const uint32_t maxlen = __builtin_amdgcn_readfirstlane(wave_max(live ? len : 0u));
     const uint32_t sh     = 32 - a.code_bits;
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
         // every lane reads its block one whole 128-byte line at a time (ChunkQueue, redux_encode.hpp):
         // with 16 bytes per visit the line is evicted between visits and fetched eight times
         ChunkQueue Q;
-        Q.init(a.in + blk0 * (uint64_t)a.block_size, live ? lane * a.block_size : 0u, main_end);
+        Q.init(a.in + blk0 * (uint64_t)a.block_size, live ? lane * stride * a.block_size : 0u, main_end);
         constexpr uint32_t kChunkBudget = 16 * 4 + 32; // bytes a chunk may add without a per-store check
         for (; p < main_end; p += 16) {
             const uint4 cur = Q.pop();
@@ -153,7 +153,18 @@ __global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
     }
 }
 
-struct StaticDecArgs {
+template <bool FIXUP, bool CB32, bool SOLO = false>
+__global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
+{
+    __shared__ uint32_t tab[kStaticEntries + 2];
+    claim_the_simd<SOLO>();
+    for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
+        tab[i] = a.tab.cum[i];
+    __syncthreads();
+    static_encode_body<FIXUP, CB32>(a, tab, (uint64_t)blockIdx.x * 64);
+}
+
+struct StaticDecCore {
     const uint8_t  *in;
     const uint64_t *in_offsets; // nblocks + 1
     uint64_t        nblocks;
@@ -164,18 +175,16 @@ struct StaticDecArgs {
     uint32_t        block_size;
     uint32_t        code_bits;
     uint32_t        aligned4; // out and block_size are 4-byte multiples
-    StaticTable     tab;
 };
 
+struct StaticDecArgs : StaticDecCore {
+    StaticTable tab;
+};
+
+// one lane, one block (blk; not live past nblocks), the table in LDS
 template <bool FIXUP>
-__global__ void __launch_bounds__(64) k_decode_static(StaticDecArgs a)
+__device__ __forceinline__ void static_decode_body(const StaticDecCore &a, const uint32_t *tab, const uint64_t blk)
 {
-    __shared__ uint32_t tab[kStaticEntries + 2];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < kStaticEntries; i += 64)
-        tab[i] = a.tab.cum[i];
-    __syncthreads();
-    const uint64_t blk  = (uint64_t)blockIdx.x * 64 + lane;
     const bool     live = blk < a.nblocks;
     const uint32_t cb = a.code_bits, sh = 32 - cb;
     uint64_t       size = 0;
@@ -284,6 +293,16 @@ __global__ void __launch_bounds__(64) k_decode_static(StaticDecArgs a)
     }
 }
 
+template <bool FIXUP>
+__global__ void __launch_bounds__(64) k_decode_static(StaticDecArgs a)
+{
+    __shared__ uint32_t tab[kStaticEntries + 2];
+    for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
+        tab[i] = a.tab.cum[i];
+    __syncthreads();
+    static_decode_body<FIXUP>(a, tab, (uint64_t)blockIdx.x * 64 + threadIdx.x);
+}
+
 // The static decoder in k_decode_lock's form (redux_decode.hpp, decode_lock_body<CB32, true>): all 64 lanes in
 // lock-step, the table as its Fenwick form in LDS (1 KiB per workgroup, shared by the lanes), get_symbol as the
 // same carry-driven descent with speculative loads (two LDS round trips instead of nine dependent ones), stream
@@ -319,25 +338,32 @@ __global__ void __launch_bounds__(64) k_decode_static_lock(StaticLockArgs a)
 // Totals up to 2^16: get_symbol by direct lookup (dec_search_lut).  WAVES waves share one 64 KiB byte table lut[v] =
 // symbol and the plain cumulative table; each has its own 8 KiB stream ring: 4 waves = 97 KiB, one workgroup and one wave
 // per SIMD on a CU (the headline shape: 1024 groups of 64 blocks), 8 waves = 129 KiB for grids beyond that.
+// group: the workgroup's number among those of its table; its wave w decodes blocks ((group * WAVES + w) * 64 + lane) * stride + first
 template <bool CB32, int WAVES>
-__global__ void __launch_bounds__(64 * WAVES) k_decode_static_lut(StaticLockArgs a)
+__device__ __forceinline__ void static_lut_body(const DecArgs &d, const double rc, const uint32_t *cum, uint32_t *lds, const uint64_t group,
+                                                const uint32_t stride = 1, const uint32_t first = 0)
 {
     constexpr uint32_t kLutDwords = 65536 / 4, kTabDwords = 260;
-    __shared__ uint32_t lds[kLutDwords + kTabDwords + WAVES * 32 * 64];
     uint8_t  *lut  = reinterpret_cast<uint8_t *>(lds);
     uint32_t *ctab = lds + kLutDwords;
     const uint32_t t = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     for (uint32_t i = t; i < kStaticEntries; i += 64 * WAVES)
-        ctab[i] = a.tab.cum[i];
+        ctab[i] = cum[i];
     // symbol s fills [cum[s], cum[s+1]); the EOF symbol's range (and nothing beyond the total is ever looked up) gets 255
     for (uint32_t s = t; s < 257; s += 64 * WAVES) {
-        const uint32_t b = a.tab.cum[s], e = a.tab.cum[s + 1] < 65536u ? a.tab.cum[s + 1] : 65536u;
+        const uint32_t b = cum[s], e = cum[s + 1] < 65536u ? cum[s + 1] : 65536u;
         for (uint32_t i = b; i < e; i++)
             lut[i] = (uint8_t)(s < 256 ? s : 255);
     }
     __syncthreads();
-    decode_lock_body<CB32, 2>(a.d, ctab + kTabDwords + wave * (32 * 64), a.tab.cum, a.rc, t & 63u,
-                              (uint64_t)blockIdx.x * WAVES + wave, lut, ctab);
+    decode_lock_body<CB32, 2>(d, ctab + kTabDwords + wave * (32 * 64), cum, rc, t & 63u, group * WAVES + wave, lut, ctab, stride, first);
+}
+
+template <bool CB32, int WAVES>
+__global__ void __launch_bounds__(64 * WAVES) k_decode_static_lut(StaticLockArgs a)
+{
+    __shared__ uint32_t lds[65536 / 4 + 260 + WAVES * 32 * 64];
+    static_lut_body<CB32, WAVES>(a.d, a.rc, a.tab.cum, lds, blockIdx.x);
 }
 
 } // namespace redux
