@@ -536,6 +536,11 @@ const char *redux_source_hash(void);
  * roofline.kernel) instead of assuming the fast path was taken. */
 const char *redux_encode_kernel_name(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size);
 const char *redux_decode_kernel_name(const redux_params *p, const void *d_out, uint32_t block_size);
+/* The encoder's choice also depends on the workspace the call is GIVEN: a launch the small-grid kernels would take runs the
+ * full-grid kernels when workspace_bytes is below redux_encode_workspace_bytes' answer for its shape (no room for the pairs
+ * area: every chunk of a multi-chunk host call).  redux_encode_kernel_name answers for a workspace of that size or more. */
+const char *redux_encode_kernel_name_ws(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                        uint64_t workspace_bytes);
 /* The decoder also depends on the SIZE of the launch (blocks the lock-step decoder does not take -- above 64 KiB -- run one
  * per wave in launches of at most 1024 blocks, k_decode_wave, and on the cell decoder with u32 nodes, k_decode_cells<8>, in
  * larger ones; 11- and 12-bit symbols keep their bottom tree cells in LDS on small grids):

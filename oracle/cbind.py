@@ -117,6 +117,17 @@ def decompress(data, params=(8, 30, 32), model=TREE, cap=None):
     return out[: bo.value].tobytes(), (bi.value, bo.value)
 
 
+def decompress_raw(stream, cap, params=(8, 30, 32), model=TREE):
+    """ox_decompress without raising: (status, bytes written before the status was decided, bytes the reader fetched).
+    A full output reports IO_ERROR (the oracle's writer fails where the capacity ends)."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    bi, bo = C.c_uint64(), C.c_uint64()
+    st = lib().ox_decompress(a.ctypes.data if len(a) else None, len(a), out.ctypes.data, cap, params[0], params[1],
+                             params[2], model, C.byref(bi), C.byref(bo))
+    return st, out[: bo.value].tobytes(), bi.value
+
+
 def _static_call(fn, data, cum, params, cap):
     a = _as_u8(data)
     out = np.empty(cap, dtype=np.uint8)

@@ -29,6 +29,7 @@ SIGNATURES = {
     "redux_version": (C.c_char_p, []),
     "redux_source_hash": (C.c_char_p, []),
     "redux_encode_kernel_name": (C.c_char_p, [_PP, _V, _U64, _U32]),
+    "redux_encode_kernel_name_ws": (C.c_char_p, [_PP, _V, _U64, _U32, _U64]),
     "redux_decode_kernel_name": (C.c_char_p, [_PP, _V, _U32]),
     "redux_decode_kernel_name_n": (C.c_char_p, [_PP, _V, _U32, _U64]),
     "redux_static_encode_kernel_name": (C.c_char_p, [_PP, C.POINTER(_U32), _U64, _U32]),

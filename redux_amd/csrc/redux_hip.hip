@@ -374,8 +374,8 @@ static uint32_t cu_count()
 
 // ---- which kernel a call runs: ONE decision, used by the launch code and reported by
 // redux_encode_kernel_name / redux_decode_kernel_name (bench.py's roofline.kernel) ------------
-enum class EncKernel { PairCb32, Pair, SingleU16, SingleU16Fixup, SingleU32, Gen, GenPair, Any, CoopCb32, Coop };
-enum class DecKernel { LockCb32, Lock, GenericU16, GenericU16Fixup, GenericU32, Cells, CellsFixup, CellsWorkspace, Cells8, Cells8Fixup, Any, Wave, WaveFixup };
+enum class EncKernel { PairCb32, Pair, SingleU16, SingleU32, Gen, GenPair, Any, CoopCb32, Coop };
+enum class DecKernel { LockCb32, Lock, GenericU16, GenericU32, Cells, CellsFixup, CellsWorkspace, Cells8, Cells8Fixup, Any, Wave, WaveFixup };
 
 // 64 blocks per wave while 64 slots / 64 blocks stay within a 32-bit lane offset; otherwise
 // (giant blocks, whole-stream mode) one block per wave.
@@ -403,12 +403,10 @@ static EncKernel pick_encode_kernel(const Geometry &g, const redux_params *p, bo
     if (force && !strcmp(force, "single"))
         pair = false;
 #endif
-    // (a u16 tree means blocks of <= 65536 symbols, so count < 2^17: the pair kernel never needs FIXUP)
-    if (pair && !g.fixup)
+    // (a u16 tree means blocks of <= 65536 symbols, so count <= 257 + 65536 < 2^17: no u16 kernel ever needs FIXUP)
+    if (pair)
         return p->code_bits == 32 ? EncKernel::PairCb32 : EncKernel::Pair;
-    if (g.u16)
-        return g.fixup ? EncKernel::SingleU16Fixup : EncKernel::SingleU16;
-    return EncKernel::SingleU32;
+    return g.u16 ? EncKernel::SingleU16 : EncKernel::SingleU32;
 }
 
 // nslots: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice)
@@ -440,9 +438,7 @@ static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, ui
 #endif
     if (lock)
         return p->code_bits == 32 ? DecKernel::LockCb32 : DecKernel::Lock;
-    if (g.u16)
-        return g.fixup ? DecKernel::GenericU16Fixup : DecKernel::GenericU16;
-    return DecKernel::GenericU32;
+    return g.u16 ? DecKernel::GenericU16 : DecKernel::GenericU32; // (u16: count < 2^17, as for the encoders)
 }
 
 } // namespace redux
@@ -580,11 +576,8 @@ const char *redux_version(void) { return "redux_hip 0.3.0 gfx950"; }
 #endif
 const char *redux_source_hash(void) { return REDUX_SOURCE_HASH; }
 
-const char *redux_encode_kernel_name(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size)
+static const char *encode_kernel_name_of(const Geometry &g, const redux_params *p, const void *d_in, uint32_t block_size)
 {
-    if (check_params(p) != REDUX_OK || block_size == 0)
-        return "";
-    const Geometry g = geometry(p, in_len, block_size);
     const bool aligned16 = (((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0;
     switch (pick_encode_kernel(g, p, aligned16, block_size)) {
     case EncKernel::CoopCb32: return "k_coop_model + k_coop_chain<true> (small grid: model by 64 lanes per block, chain wave + bit-writer wave, code_bits 32)";
@@ -592,7 +585,6 @@ const char *redux_encode_kernel_name(const redux_params *p, const void *d_in, ui
     case EncKernel::PairCb32: return "k_encode_pair<false, true> (u16 tree, model wave + coder wave, code_bits 32)";
     case EncKernel::Pair: return "k_encode_pair<false, false> (u16 tree, model wave + coder wave)";
     case EncKernel::SingleU16: return "k_encode<true, false> (u16 tree, one wave per 64 blocks)";
-    case EncKernel::SingleU16Fixup: return "k_encode<true, true> (u16 tree, one wave per 64 blocks, quotient fix-up)";
     case EncKernel::SingleU32: return "k_encode<false, true> (u32 tree)";
     case EncKernel::Gen: {
         static const char *const names[8] = {"", "k_encode_gen<1>", "k_encode_gen<2>", "k_encode_gen<3>", "k_encode_gen<4>", "k_encode_gen<5>",
@@ -607,6 +599,20 @@ const char *redux_encode_kernel_name(const redux_params *p, const void *d_in, ui
     case EncKernel::Any: return "k_encode_any (general parameters, one lane per block)";
     }
     return "";
+}
+
+const char *redux_encode_kernel_name(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size)
+{
+    if (check_params(p) != REDUX_OK || block_size == 0)
+        return "";
+    return encode_kernel_name_of(geometry(p, in_len, block_size), p, d_in, block_size);
+}
+
+const char *redux_encode_kernel_name_ws(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint64_t workspace_bytes)
+{
+    if (check_params(p) != REDUX_OK || block_size == 0)
+        return "";
+    return encode_kernel_name_of(geometry_ws(p, in_len, block_size, workspace_bytes), p, d_in, block_size);
 }
 
 const char *redux_decode_kernel_name(const redux_params *p, const void *d_out, uint32_t block_size)
@@ -624,7 +630,6 @@ const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out,
     case DecKernel::LockCb32: return "k_decode_lock<true> (u16 tree, one wave per 64 blocks, code_bits 32)";
     case DecKernel::Lock: return "k_decode_lock<false> (u16 tree, one wave per 64 blocks)";
     case DecKernel::GenericU16: return "k_decode<true, false> (u16 tree, per-lane control flow)";
-    case DecKernel::GenericU16Fixup: return "k_decode<true, true> (u16 tree, quotient fix-up)";
     case DecKernel::GenericU32: return "k_decode<false, true> (u32 tree)";
     case DecKernel::CellsFixup: {
         // lock-step, the tree as cells of four levels in LDS; the instance for counts of 2^17 and more (widths 1 ... 7)
@@ -875,7 +880,6 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
     case EncKernel::PairCb32: k_encode_pair<false, true><<<grid, 128, 0, s>>>(a); break;
     case EncKernel::Pair: k_encode_pair<false, false><<<grid, 128, 0, s>>>(a); break;
     case EncKernel::SingleU16: k_encode<true, false><<<grid, 64, 0, s>>>(a); break;
-    case EncKernel::SingleU16Fixup: k_encode<true, true><<<grid, 64, 0, s>>>(a); break;
     case EncKernel::SingleU32: k_encode<false, true><<<grid, 64, 0, s>>>(a); break;
     case EncKernel::Gen:
     case EncKernel::GenPair:
@@ -1281,7 +1285,6 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
     case DecKernel::LockCb32: k_decode_lock<true><<<grid, 64, 0, s>>>(a); break;
     case DecKernel::Lock: k_decode_lock<false><<<grid, 64, 0, s>>>(a); break;
     case DecKernel::GenericU16: k_decode<true, false><<<grid, 64, 0, s>>>(a); break;
-    case DecKernel::GenericU16Fixup: k_decode<true, true><<<grid, 64, 0, s>>>(a); break;
     case DecKernel::GenericU32: k_decode<false, true><<<grid, 64, 0, s>>>(a); break;
     case DecKernel::Cells:
     case DecKernel::CellsFixup:

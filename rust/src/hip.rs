@@ -14,7 +14,7 @@
 //! checks every declaration against `include/redux_hip.h` (name, arity, pointer-vs-integer and
 //! integer width of each argument and of the return type).
 use std::io;
-use std::os::raw::c_int;
+use std::os::raw::{c_char, c_int, c_void};
 use std::ptr;
 
 use super::model::Parameters;
@@ -105,6 +105,9 @@ extern "C" {
     fn redux_decode_blocks_stored(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, stored: *const u8,
                                   out_len: u64, block_size: u32, element_size: u32, out: *mut u8, out_cap: u64,
                                   out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    #[allow(dead_code)] // declared for harnesses that print the kernel next to a timing; no wrapper here
+    fn redux_encode_kernel_name_ws(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32,
+                                   workspace_bytes: u64) -> *const c_char;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }

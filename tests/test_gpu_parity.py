@@ -160,9 +160,11 @@ def test_stress_patterns(rx, name):  # pending-run / carry and freeze corner cas
 
 
 def test_every_byte_value_in_both_lane_halves(rx):
-    """The pair kernel's model wave takes its dot-product masks from a table row per byte value (rows s and s + 1; row 256
-    is all zero, the node-256 term is added separately) and lanes l / l + 32 own the two halves of every tree dword:
-    128 blocks = two full waves in which every lane sees every byte value, runs of 255 and of 0, at its own phase."""
+    """128 blocks = two full waves in which every lane sees every byte value, runs of 255 and of 0, at its own phase.
+    Written for the pair kernel's mask table (a row per byte value, lanes l / l + 32 owning the halves of every tree
+    dword); a launch of 128 blocks runs the small-grid kernels today (k_coop_model + k_coop_chain: the model by 64 lanes
+    per block), whose per-symbol rows it exercises the same way.  The pair kernel gets these byte patterns' kin at its
+    own launch sizes in tests/test_adaptive_instances_gpu.py."""
     nb = 128
     i = np.arange(BLOCK, dtype=np.int64)
     blocks = []
@@ -224,13 +226,7 @@ def test_error_paths(rx):
 
 def _oracle_decode_raw(stream, cap, params):
     """ox_decompress without raising: (status, bytes written before the status was decided)."""
-    import ctypes as C
-    a = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
-    out = np.zeros(max(cap, 1), dtype=np.uint8)
-    bi, bo = C.c_uint64(), C.c_uint64()
-    st = ox.lib().ox_decompress(a.ctypes.data if len(a) else None, len(a), out.ctypes.data, cap, params[0], params[1],
-                                params[2], ox.TREE, C.byref(bi), C.byref(bo))
-    return st, out[: bo.value].tobytes()
+    return ox.decompress_raw(stream, cap, params)[:2]
 
 
 @pytest.mark.parametrize("params", [(8, 30, 32), (8, 14, 16)])
@@ -712,7 +708,10 @@ def _adversarial_cases():
 def test_adversarial_rare_paths(rx, name, params, data):
     """Forces the data-dependent rare paths: pending runs of hundreds of bits (flushed at EOF
     and, with a random tail, inside the unrolled loop) and low == high after narrowing
-    (k = code_bits).  Every lane of a wave gets the input so the wave-level ballots fire."""
+    (k = code_bits).  Six blocks per call: the inputs shorter than 1 KiB (pending_7f_*, pending_80_8_30_32) run
+    k_encode_pair in 6 lanes of one wave, the longer ones (pending_80_8_14_16, pending_80_8_22_24, width1_8_14_16) the
+    small-grid kernels (k_coop_model + k_coop_chain); tests/test_adaptive_instances_cpu.py asserts this split, and
+    tests/test_adaptive_instances_gpu.py runs every input on every instance at its own launch size."""
     blocks = data + bytes((-len(data)) % 16)           # 16-byte multiple so that all blocks are equal
     bs = len(blocks)
     many = blocks * 5 + data                            # 5 identical full blocks + the exact input as a ragged last one

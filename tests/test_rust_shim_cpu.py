@@ -12,9 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIP_RS = open(os.path.join(ROOT, "rust", "src", "hip.rs")).read()
 HEADER = open(os.path.join(ROOT, "include", "redux_hip.h")).read()
 
-RUST_TYPES = {"u8": ("int", 8), "u32": ("int", 32), "i32": ("int", 32), "u64": ("int", 64), "c_int": ("int", 32)}
+RUST_TYPES = {"u8": ("int", 8), "u32": ("int", 32), "i32": ("int", 32), "u64": ("int", 64), "c_int": ("int", 32),
+              "c_char": ("int", 8), "c_void": ("void", 0)}
 C_TYPES = {"uint8_t": ("int", 8), "uint32_t": ("int", 32), "int32_t": ("int", 32), "uint64_t": ("int", 64),
-           "int": ("int", 32)}
+           "int": ("int", 32), "char": ("int", 8), "void": ("void", 0)}
 
 
 def rust_kind(t):
@@ -64,7 +65,7 @@ def same(rk, ck):
         return False
     if rk[0] == "int":
         return rk[1] == ck[1]
-    # pointers: constness and pointee must agree (void* never appears in the bound subset)
+    # pointers: constness and pointee must agree (void * binds c_void only, char * binds c_char or u8)
     if rk[1] != ck[1]:
         return False
     rbase, cbase = rk[2], ck[2]

@@ -78,12 +78,8 @@ def dec_name(params, bs, nblocks):
 
 def oracle_decode(stream, cap, params):
     """ox_decompress without raising: (status as the device reports it, decoded bytes, bytes fetched)."""
-    a = np.ascontiguousarray(np.frombuffer(bytes(stream), dtype=np.uint8))
-    out = np.zeros(max(cap, 1), dtype=np.uint8)
-    bi, bo = C.c_uint64(), C.c_uint64()
-    st = ox.lib().ox_decompress(a.ctypes.data if len(a) else None, len(a), out.ctypes.data, cap, params[0], params[1],
-                                params[2], ox.TREE, C.byref(bi), C.byref(bo))
-    return (4 if st == ox.IO_ERROR else st), out[: bo.value].tobytes(), bi.value
+    st, out, fetched = ox.decompress_raw(stream, cap, params)
+    return (4 if st == ox.IO_ERROR else st), out, fetched
 
 
 @pytest.fixture(scope="module")
