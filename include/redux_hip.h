@@ -475,8 +475,8 @@ int      redux_static_decode_blocks_crc(const redux_params *p, const uint32_t *c
  *      owns no bytes keeps total 257, and the only block ever coded under one is the empty input's block 0.
  * Tables are u32[E][258], table t at cum + 258 t.  On the device they are read from device memory (d_cum), and the kernels
  * check the table they load: one that is not strictly increasing from 0 to `total` (or to 257) makes its blocks INVALID_INPUT.
- * Not available for the `_v` calls, redux_compress / redux_decompress and stored blocks; one set of tables per call (none
- * per chunk or block range).
+ * Not available for the `_v` calls, redux_compress / redux_decompress and stored blocks; one set of tables per call (tables
+ * per block range: "segment-static coding" below).
  *
  * redux_plane_static_table_check        every table passes redux_static_table_check, and all totals are equal (a table of
  *                                       total 257, what a t without bytes gets, goes with any).  E = 1: one table.
@@ -524,6 +524,82 @@ int      redux_plane_static_decode_blocks_crc(const redux_params *p, const uint3
                                               uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
                                               uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- segment-static coding: static tables per block range ------------------------------------------
+ * Plane-static coding with tables that follow the data: one table (or E, one per byte plane) covers a whole input, and loses
+ * where the statistics move (a checkpoint is a concatenation of tensors with different scales).  E = element_size, one of
+ * 1, 2, 4, 8; B = block_size; x' = the byte-plane layout of the input for E and B (E = 1: the input itself).
+ * The rule:
+ *   1. A segment is G = segment_blocks = 64 E k consecutive blocks of x', k >= 1 (G == 0 or not a multiple of 64 E:
+ *      INVALID_INPUT).  Segment s holds blocks [s G, (s+1) G); nseg = max(1, ceil(nblocks / G)).
+ *   2. Table (s, t), 0 <= t < E, is the table of "semi-static coding" (redux_static_table_from_counts, unchanged, one `total`
+ *      for the whole call) of the counts of the bytes of all blocks b of segment s with b mod E == t.  A pair (s, t) that owns
+ *      no bytes keeps the all-ones table (total 257), as in plane-static; the short last frame is not special-cased.
+ *   3. Block b is coded by the static coder under table (b / G) E + b mod E:
+ *      stream[b] == redux_static_encode_blocks(block b of x', cum[(b / G) E + b mod E]).
+ *   4. With G >= nblocks the tables and streams are those of plane-static coding (E > 1) or of the static-table model
+ *      (E = 1), bit for bit.
+ * Tables are u32[nseg][E][258], counts u64[nseg][E][256]: table (s, t) at cum + 258 (s E + t).  The kernels check the table
+ * they load, as in plane-static: a bad table makes only the blocks of the workgroup that loaded it INVALID_INPUT.  8-bit
+ * symbols and code_bits <= 32, as for plane-static; everything else is UNSUPPORTED.  Not available for the `_v` calls,
+ * redux_compress / redux_decompress and stored blocks.  Callers above the C ABI default to G = 64 E * 4.
+ *
+ * redux_segment_static_table_count        nseg E for nblocks blocks; 0 for an element size or G the rule does not take.
+ * redux_segment_static_table_check        ntables == redux_segment_static_table_count(nblocks, ...), every table passes
+ *                                         redux_static_table_check, and all totals are equal (a table of total 257 goes with any).
+ * redux_segment_static_total              the common total of checked tables (the largest cum[257]).
+ * redux_segment_static_tables_from_counts rule 2 on the host from u64[nseg][E][256] counts.
+ * redux_segment_histogram_dev             ADDS the counts of x' = d_in[0 .. in_len) (already in the layout) to d_counts,
+ *                                         u64[nseg][E][256] (k_segment_hist).  Any block size and alignment.
+ * redux_segment_static_tables_dev         rule 2 on the device, one launch for all tables (k_static_tables).
+ * redux_segment_static_encode_dev         device pointers, input in original order, as redux_plane_static_encode_dev /
+ * redux_segment_static_decode_dev         redux_plane_static_decode_dev with rule 3.
+ * redux_segment_static_build_encode_dev   the tables built from the buffer they code: the layout once, the histogram of that
+ *                                         copy, the tables (left in d_cum, u32[nseg][E][258]), the coder over the same copy.
+ *                                         Workspace: redux_segment_static_build_encode_workspace_bytes.
+ * redux_segment_static_encode_blocks_crc  host pointers through the chunk pipeline (fleet included), block_crc nullable.
+ * redux_segment_static_decode_blocks_crc  Chunks are whole segments; encode builds each chunk's tables from that chunk (one
+ *                                         pass over the input: no histogram of the whole input first) and writes them to cum,
+ *                                         u32[redux_segment_static_table_count][258] in host memory; decode sends each chunk
+ *                                         its own tables.  Streams and tables depend on neither the chunk size nor the devices. */
+uint64_t redux_segment_static_table_count(uint64_t nblocks, uint32_t element_size, uint32_t segment_blocks);
+int      redux_segment_static_table_check(const redux_params *p, const uint32_t *cum, uint64_t ntables, uint64_t nblocks,
+                                          uint32_t element_size, uint32_t segment_blocks);
+uint32_t redux_segment_static_total(const uint32_t *cum, uint64_t ntables);
+int      redux_segment_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint64_t nblocks, uint32_t element_size,
+                                                 uint32_t segment_blocks, uint32_t total, uint32_t *cum);
+int      redux_segment_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                                     uint32_t segment_blocks, void *d_counts /* u64[nseg][E][256], ADDED to */, void *stream);
+int      redux_segment_static_tables_dev(const redux_params *p, const void *d_counts, uint64_t nblocks, uint32_t element_size,
+                                         uint32_t segment_blocks, uint32_t total, void *d_cum /* u32[nseg][E][258] */, void *stream);
+uint64_t redux_segment_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size);
+uint64_t redux_segment_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_segment_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_segment_static_build_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size,
+                                                           uint32_t element_size, uint32_t segment_blocks);
+int      redux_segment_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                         uint32_t block_size, uint32_t element_size, uint32_t segment_blocks, void *d_out,
+                                         uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                                         void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */, void *d_workspace,
+                                         uint64_t workspace_bytes, void *stream);
+int      redux_segment_static_build_encode_dev(const redux_params *p, uint32_t total, const void *d_in, uint64_t in_len,
+                                               uint32_t block_size, uint32_t element_size, uint32_t segment_blocks,
+                                               void *d_cum /* u32[nseg][E][258], written */, void *d_out, uint64_t out_cap,
+                                               void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
+                                               uint64_t workspace_bytes, void *stream);
+int      redux_segment_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in,
+                                         const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len, uint32_t block_size,
+                                         uint32_t element_size, uint32_t segment_blocks, void *d_out,
+                                         void *d_out_sizes /* u32[nblocks] */, void *d_block_status, void *d_summary,
+                                         void *d_workspace, uint64_t workspace_bytes, void *stream);
+int      redux_segment_static_encode_blocks_crc(const redux_params *p, uint32_t total, const uint8_t *in, uint64_t in_len,
+                                                uint32_t block_size, uint32_t element_size, uint32_t segment_blocks,
+                                                uint32_t *cum /* written */, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                                int32_t *block_status, uint32_t *block_crc);
+int      redux_segment_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, uint64_t ntables, const uint8_t *in,
+                                                const uint64_t *in_offsets, uint64_t out_len, uint32_t block_size,
+                                                uint32_t element_size, uint32_t segment_blocks, uint8_t *out, uint32_t *out_sizes,
+                                                int32_t *block_status, uint32_t *block_crc);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the
@@ -558,6 +634,14 @@ const char *redux_static_decode_kernel_name(const redux_params *p, const uint32_
 const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
                                                   uint32_t element_size);
 const char *redux_plane_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size);
+
+/* The same for redux_segment_static_encode_dev / redux_segment_static_decode_dev (the k_*_segment_static* instances).  The
+ * lookup decoder's 4 or 8 waves share one table and so one segment: it runs where k = segment_blocks / (64 element_size) is a
+ * multiple of its wave count (8 not suiting, 4 is tried), and the lock-step decoder where neither suits. */
+const char *redux_segment_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
+                                                    uint32_t element_size, uint32_t segment_blocks);
+const char *redux_segment_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size,
+                                                    uint32_t segment_blocks);
 
 /* Diagnostic, used by the parity tests only: *max_err = max over the integers x in [lo, hi] of
  * |v_rcp_f64(x) * x - 1| evaluated on the device.  The decoder's code-value division

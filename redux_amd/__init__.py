@@ -11,4 +11,5 @@ from .api import (  # noqa: F401
     host_set_devices, host_chunk_plan, host_set_chunk_bytes,
     DeviceEncoder, DeviceDecoder, DeviceStaticCoder, DevicePlaneStaticCoder, planes, gen_iid, gen_zipf, zipf_thresholds, version,
     crc32_blocks, crc32_combine, STORE_RATIO,
+    SegmentStaticModel, segment_static_tables, segment_static_tables_from_counts, default_segment_blocks, DeviceSegmentStaticCoder,
 )

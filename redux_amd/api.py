@@ -166,8 +166,75 @@ class PlaneStaticModel:
         return self.cums.ctypes.data
 
 
+SEGMENT_K0 = 4  # default segment: G = 64 * E * SEGMENT_K0 blocks
+
+
+def default_segment_blocks(element_size):
+    """The segment length used when none is given: 64 * E * 4 blocks."""
+    return 64 * int(element_size) * SEGMENT_K0
+
+
+class SegmentStaticModel:
+    """Segment-static coding (include/redux_hip.h, "segment-static coding"): Parameters plus static tables per range of
+    segment_blocks = 64 * E * k blocks of the byte-plane layout, cums of shape (nseg * E, 258), E = element_size in
+    1 / 2 / 4 / 8; block b is coded under table (b // segment_blocks) * E + b % E.  The tables belong to one input: nseg is
+    checked against its block count when the model is used.  SegmentStaticModel.from_data codes the data while it builds
+    the tables, so compress_blocks(data, block_size, SegmentStaticModel.template(...)) is the one-pass way to get both."""
+
+    def __init__(self, params, cums, element_size, segment_blocks):
+        self.params = _params_of(params)
+        self.element_size = _check_element_size(element_size)
+        G = segment_blocks
+        if not isinstance(G, (int, np.integer)) or not 0 < G < 1 << 32 or G % (64 * self.element_size):
+            raise InvalidInput()
+        self.segment_blocks = int(G)
+        self._total = _total_of(self.params, None)  # what compress_blocks builds tables with while the model has none
+        self.cums = None
+        if cums is not None:
+            c = np.ascontiguousarray(cums, dtype=np.int64)
+            if c.ndim != 2 or c.shape[0] == 0 or c.shape[0] % self.element_size or c.shape[1] != 258 or (c < 0).any() \
+                    or (c > 0xFFFFFFFF).any():
+                raise InvalidInput()
+            self.cums = c.astype(np.uint32)
+            # (every count of blocks that gives this many tables passes the same check: the first of them)
+            nb = (c.shape[0] // self.element_size - 1) * self.segment_blocks + 1
+            self.check(nb)
+
+    @classmethod
+    def template(cls, params=(8, 30, 32), element_size=1, segment_blocks=None, total=None):
+        """A model without tables: compress_blocks builds them from the data it codes and returns them in the model."""
+        E = _check_element_size(element_size)
+        m = cls(params, None, E, default_segment_blocks(E) if segment_blocks is None else segment_blocks)
+        m._total = _total_of(m.params, total)
+        return m
+
+    @classmethod
+    def from_data(cls, data, element_size, block_size, params=(8, 30, 32), segment_blocks=None, total=None):
+        E = _check_element_size(element_size)
+        G = default_segment_blocks(E) if segment_blocks is None else segment_blocks
+        return cls(params, segment_static_tables(data, E, block_size, G, params, total), E, G)
+
+    def check(self, nblocks):
+        """redux_segment_static_table_check for an input of nblocks blocks"""
+        if self.cums is None:
+            raise InvalidInput()
+        cp = self.params._c()
+        _raise(_lib.lib().redux_segment_static_table_check(C.byref(cp), self.cums.ctypes.data, len(self.cums), int(nblocks),
+                                                            self.element_size, self.segment_blocks))
+
+    def parameters(self):
+        return self.params
+
+    def total(self):
+        """the tables' common total (a table without bytes keeps 257); a template's: the total it will build with"""
+        return int(self.cums[:, -1].max()) if self.cums is not None else self._total
+
+    def _cum_ptr(self):
+        return self.cums.ctypes.data
+
+
 def _params_of(model_or_params):
-    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel, PlaneStaticModel)):
+    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel, PlaneStaticModel, SegmentStaticModel)):
         return model_or_params.params
     if isinstance(model_or_params, Parameters):
         return model_or_params
@@ -282,6 +349,60 @@ def _device_plane_tables(torch, L, cp, d_x, E, block_size, total):
     return d_cum
 
 
+def segment_static_tables_from_counts(counts, nblocks, element_size, segment_blocks, params=(8, 30, 32), total=None):
+    """redux_segment_static_tables_from_counts: the rule on u64[nseg * E, 256] counts, on the host -> np.uint32[nseg * E, 258]."""
+    P = _params_of(params)
+    E = _check_element_size(element_size)
+    L = _lib.lib()
+    if not isinstance(segment_blocks, (int, np.integer)) or not 0 <= segment_blocks < 1 << 32:
+        raise InvalidInput()
+    n = L.redux_segment_static_table_count(int(nblocks), E, int(segment_blocks))
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if n == 0 or c.shape != (n, 256):
+        raise InvalidInput()
+    cums = np.zeros((n, 258), dtype=np.uint32)
+    cp = P._c()
+    _raise(L.redux_segment_static_tables_from_counts(C.byref(cp), c.ctypes.data, int(nblocks), E, int(segment_blocks),
+                                                     _total_of(P, total), cums.ctypes.data))
+    return cums
+
+
+def segment_static_tables(data, element_size, block_size, segment_blocks=None, params=(8, 30, 32), total=None):
+    """The tables of segment-static coding for `data` in ORIGINAL byte order: np.uint32[nseg * E, 258].  A torch uint8
+    device tensor is laid out and counted where it lies (redux_planes_dev, redux_segment_histogram_dev,
+    redux_segment_static_tables_dev, one read-back).  Host data: the tables are those the one-pass encode builds
+    (redux_segment_static_encode_blocks_crc), whose streams are dropped."""
+    P = _params_of(params)
+    T = _total_of(P, total)
+    E = _check_element_size(element_size)
+    G = default_segment_blocks(E) if segment_blocks is None else segment_blocks
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    m = SegmentStaticModel(P, None, E, G)  # (checks G)
+    m._total = T
+    if not _is_device_tensor(data):
+        compress_blocks(data, int(block_size), m)
+        return m.cums
+    torch = _torch()
+    L = _lib.lib()
+    cp = P._c()
+    with torch.cuda.device(data.device):
+        d_x = planes(data, E, block_size) if E > 1 else data
+        n = L.redux_segment_static_table_count(L.redux_block_count(d_x.numel(), int(block_size)), E, m.segment_blocks)
+        counts = torch.zeros(n * 256, dtype=torch.int64, device=d_x.device)
+        d_cum = torch.zeros(n * 258, dtype=torch.int32, device=d_x.device)
+        s = _stream_ptr(torch)
+        _raise(L.redux_segment_histogram_dev(C.c_void_p(d_x.data_ptr()) if d_x.numel() else None, d_x.numel(), int(block_size), E,
+                                             m.segment_blocks, C.c_void_p(counts.data_ptr()), s))
+        _raise(L.redux_segment_static_tables_dev(C.byref(cp), C.c_void_p(counts.data_ptr()),
+                                                 L.redux_block_count(d_x.numel(), int(block_size)), E, m.segment_blocks, T,
+                                                 C.c_void_p(d_cum.data_ptr()), s))
+        cums = d_cum.cpu().numpy().view(np.uint32).reshape(n, 258).copy()
+    if not cums.any(axis=1).all():  # the kernel's mark for N * R >= 2^64
+        raise Unsupported()
+    return cums
+
+
 def _is_device_tensor(x):
     try:
         import torch
@@ -322,12 +443,16 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks_crc); no element_size.
     params may be a PlaneStaticModel: the layout of the model's element size, block b under table b mod E
     (redux_plane_static_encode_blocks_crc); element_size must be 1 (the default: the model's is used) or the model's.
+    params may be a SegmentStaticModel (redux_segment_static_encode_blocks_crc): its tables are built from `data` as it is
+    coded, with the model's total, and the model holds them afterwards (tables it held before are replaced).
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 (zlib.crc32) of every input block, in original
     byte order for every layout (the `_crc` calls of include/redux_hip.h).
     stored: a np.uint8[nblocks] the same call fills with the stored-block flags (include/redux_hip.h, "stored blocks"):
     passing it turns stored blocks on, and block b's payload is then its raw (planes: plane) bytes wherever its stream
     is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
+    segment = isinstance(params, SegmentStaticModel)
+    plane = plane or segment  # (the checks of a model that brings its own element size)
     P = _params_of(params)
     a = _u8(data)
     L = _lib.lib()
@@ -347,7 +472,15 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
     status = np.zeros(nb, dtype=np.int32)
-    if stored is not None:
+    if segment:  # the tables are built from the data as it is coded, and left in the model
+        n = L.redux_segment_static_table_count(nb, params.element_size, params.segment_blocks)
+        cums = np.zeros((n, 258), dtype=np.uint32)
+        st = L.redux_segment_static_encode_blocks_crc(C.byref(cp), params.total(), _ptr(a), len(a), block_size, params.element_size,
+                                                      params.segment_blocks, cums.ctypes.data, out.ctypes.data, cap,
+                                                      offs.ctypes.data, status.ctypes.data, crc)
+        if st == _lib.OK or cums.any():
+            params.cums = cums
+    elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
     elif static:
@@ -384,11 +517,15 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks_crc).
     params may be a PlaneStaticModel (redux_plane_static_decode_blocks_crc): length is required, element_size is 1 (the
     model's is used) or the model's, and out is the original bytes as with element_size > 1.
+    params may be a SegmentStaticModel (redux_segment_static_decode_blocks_crc): as a PlaneStaticModel; its tables must be
+    those of an input of this many blocks.
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
     order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK.
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
     uint8[length] in original order, as with element_size > 1."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
+    segment = isinstance(params, SegmentStaticModel)
+    plane = plane or segment
     E = _check_element_size(element_size)
     if block_size <= 0 or (static and (E != 1 or length is not None or stored is not None)) \
             or (plane and (E not in (1, params.element_size) or length is None or stored is not None)) \
@@ -409,7 +546,13 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     out = np.empty(nb * block_size if length is None else max(length, 1), dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
-    if stored is not None:
+    if segment:
+        if params.cums is None:
+            raise InvalidInput()
+        st = L.redux_segment_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), len(params.cums), _ptr(a), offs.ctypes.data,
+                                                      length, block_size, params.element_size, params.segment_blocks,
+                                                      out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
+    elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
     elif static:
@@ -883,6 +1026,117 @@ class DevicePlaneStaticCoder:
         st = _lib.lib().redux_plane_static_decode_dev(
             C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
             C.c_void_p(d_offsets.data_ptr()), length, self.block_size, self.E, C.c_void_p(self.dec_out.data_ptr()),
+            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
+            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
+        _raise(st)
+        return self.dec_out[:length], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+
+
+class DeviceSegmentStaticCoder:
+    """Segment-static coding on device tensors (include/redux_hip.h, "segment-static coding").  encode_build(d_in) builds
+    the tables from d_in while it codes it (redux_segment_static_build_encode_dev: one layout pass) and leaves them in
+    d_cum, an int32[nseg * E * 258] device tensor; encode / decode run under the tables d_cum holds.  Input and output are
+    in original byte order."""
+
+    def __init__(self, params, element_size, block_size, max_in_len, segment_blocks=None, total=None, device="cuda:0"):
+        torch = _torch()
+        self.P = _params_of(params)
+        self.cp = self.P._c()
+        L = _lib.lib()
+        self.E = _check_element_size(element_size)
+        self.G = SegmentStaticModel(self.P, None, self.E,
+                                    default_segment_blocks(self.E) if segment_blocks is None else segment_blocks).segment_blocks
+        self.total = _total_of(self.P, total)
+        self.block_size = int(block_size)
+        self.max_in_len = int(max_in_len)
+        self.device = torch.device(device)
+        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
+        self.ntables_max = L.redux_segment_static_table_count(self.nblocks_max, self.E, self.G)
+        self.ws_bytes = max(L.redux_segment_static_build_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size,
+                                                                                self.E, self.G),
+                            L.redux_segment_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
+        if self.ws_bytes == 0:
+            raise InvalidInput()
+        self.out_cap = L.redux_segment_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
+        self.d_cum = torch.zeros(self.ntables_max * 258, dtype=torch.int32, device=self.device)
+        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.dec_out = None
+
+    @classmethod
+    def from_data(cls, d_in, params, element_size, block_size, max_in_len, segment_blocks=None, total=None):
+        """A coder whose tables are those of d_in (a uint8 device tensor, original order), built by encode_build: the
+        streams of d_in are in .out / .offsets, nothing is read back."""
+        c = cls(params, element_size, block_size, max_in_len, segment_blocks, total, d_in.device)
+        c.encode_build(d_in)
+        return c
+
+    def ntables(self, n):
+        L = _lib.lib()
+        return L.redux_segment_static_table_count(L.redux_block_count(n, self.block_size), self.E, self.G)
+
+    def tables(self, n):
+        """the tables of an n-byte input on the host: np.uint32[nseg * E, 258]"""
+        k = self.ntables(n)
+        return self.d_cum[: k * 258].cpu().numpy().view(np.uint32).reshape(k, 258).copy()
+
+    def set_tables(self, cums):
+        torch = _torch()
+        c = np.ascontiguousarray(cums, dtype=np.uint32).reshape(-1)
+        assert c.size <= self.d_cum.numel()
+        self.d_cum[: c.size] = torch.from_numpy(c.view(np.int32)).to(self.device)
+
+    def _ws_ptr(self):
+        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
+
+    def _encode(self, d_in, build):
+        torch = _torch()
+        n = d_in.numel()
+        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        self.summary.zero_()
+        L = _lib.lib()
+        tail = (C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
+                C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+                _stream_ptr(torch))
+        d_in_p = C.c_void_p(d_in.data_ptr()) if n else None
+        if build:
+            st = L.redux_segment_static_build_encode_dev(C.byref(self.cp), self.total, d_in_p, n, self.block_size, self.E, self.G,
+                                                         C.c_void_p(self.d_cum.data_ptr()), *tail)
+        else:
+            st = L.redux_segment_static_encode_dev(C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, d_in_p, n,
+                                                   self.block_size, self.E, self.G, *tail)
+        _raise(st)
+        nb = L.redux_block_count(n, self.block_size)
+        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+
+    @_on_device
+    def encode_build(self, d_in):
+        return self._encode(d_in, True)
+
+    @_on_device
+    def encode(self, d_in):
+        return self._encode(d_in, False)
+
+    @_on_device
+    def decode(self, d_streams, d_offsets, length):
+        """-> (the original bytes uint8[length], sizes, status, summary)"""
+        torch = _torch()
+        nb = d_offsets.numel() - 1
+        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= length <= self.max_in_len
+        if nb != _lib.lib().redux_block_count(length, self.block_size):
+            raise InvalidInput()
+        if self.dec_out is None:
+            self.dec_out = torch.empty(max(self.max_in_len, 1), dtype=torch.uint8, device=self.device)
+            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.dec_summary.zero_()
+        st = _lib.lib().redux_segment_static_decode_dev(
+            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
+            C.c_void_p(d_offsets.data_ptr()), length, self.block_size, self.E, self.G, C.c_void_p(self.dec_out.data_ptr()),
             C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
             C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
         _raise(st)

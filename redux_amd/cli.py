@@ -1,7 +1,7 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
-                            [--model adaptive|static|plane-static] [--checksum] [--stored]
+                            [--model adaptive|static|plane-static|segment-static] [--segment-blocks G] [--checksum] [--stored]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -17,6 +17,11 @@ reference's model.  `--model plane-static` (with a block size and `--element-siz
 byte plane of the layout and codes each plane's blocks under its own (container version 4, which records the E tables);
 without a block size, with `--element-size` absent or 1, or with `--stored` it is a usage error.  Decoding reads the model
 from the container.
+`--model segment-static` (with a block size and any `--element-size`) builds static tables per range of G blocks of the
+layout, `--segment-blocks G`, a multiple of 64 * element size (default 256 * element size), from each range as it is coded
+(container version 5, which records k = G / (64 E) and the tables): the model for large inputs whose statistics drift,
+such as checkpoints.  Without a block size, with `--stored`, with a G that is no such multiple, or `--segment-blocks` with
+another model, it is a usage error.
 `--checksum` (with -c and a block size) records the CRC-32 (zlib.crc32) of every block's uncompressed bytes in the container
 (version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
 damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
@@ -29,7 +34,7 @@ import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static|plane-static>] [--checksum] [--stored]")
+         "[--model <adaptive|static|plane-static|segment-static>] [--segment-blocks <G>] [--checksum] [--stored]")
 
 
 def parse(argv):
@@ -44,7 +49,7 @@ def parse(argv):
             opts["stored"] = True
         elif arg == "-d":
             opts["compress"] = False
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks"):
             val = next(it, None)
             if val is None:
                 return None
@@ -57,9 +62,13 @@ def parse(argv):
                     return None
                 opts["element_size"] = int(val)
             elif arg == "--model":
-                if val not in ("adaptive", "static", "plane-static"):
+                if val not in ("adaptive", "static", "plane-static", "segment-static"):
                     return None
                 opts["model"] = val
+            elif arg == "--segment-blocks":
+                if not val.isdigit() or not 0 < int(val) < 1 << 32:
+                    return None
+                opts["segment_blocks"] = int(val)
             else:
                 try:
                     opts["block_size"] = int(val)
@@ -75,6 +84,12 @@ def parse(argv):
         return None  # the table lives in the container (not in a raw stream), and there is one table, not one per plane
     if opts.get("model") == "plane-static" and (opts["block_size"] == 0 or opts.get("element_size", 1) == 1):
         return None  # the tables live in the container, one per byte plane of the layout
+    if opts.get("model") == "segment-static" and (opts["block_size"] == 0 or opts.get("stored")):
+        return None  # the tables live in the container, and the static decoder has no table form for stored blocks
+    if "segment_blocks" in opts:
+        k, r = divmod(opts["segment_blocks"], 64 * opts.get("element_size", 1))
+        if opts.get("model") != "segment-static" or r or not 1 <= k < 1 << 24:
+            return None  # whole wave slots of every plane: G = 64 E k, and k must fit the container's field
     if opts.get("checksum") and opts["compress"] and opts["block_size"] == 0:
         return None  # the table lives in the container (-d verifies whatever table a container has)
     if opts.get("stored") and opts["compress"] and (opts["block_size"] == 0 or opts.get("model") in ("static", "plane-static")):
@@ -109,7 +124,7 @@ def main(argv=None):
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
-                                                opts.get("stored", False))
+                                                opts.get("stored", False), opts.get("segment_blocks"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

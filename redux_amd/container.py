@@ -6,15 +6,18 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 
 Layout (little-endian):
     0   4  magic  b"RDXB"
-    4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane)
+    4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
+           5 = segment-static: static tables per block range)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
-           the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008)
+           the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
+           0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks
    16   8  nblocks
    24   8  total uncompressed length
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
+   (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
    ..  4*nblocks   compressed size of each block
    (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
    (flag 0x40 only) ceil(nblocks/8)  stored-block bitmap: bit b % 8 of byte b // 8 (LSB first) = block b is stored
@@ -32,7 +35,12 @@ Version 4 holds streams of plane-static coding (include/redux_hip.h, "plane-stat
 version 2, block b coded by the static coder under table b mod E.  Tables that redux_plane_static_table_check rejects are
 InvalidInput, truncated ones Eof.  It has no stored blocks (no 0x44).
 
-Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14: versions 1 / 2 / 3 / 4 with checksums) means a table of nblocks
+Version 5 holds streams of segment-static coding (include/redux_hip.h, "segment-static coding"): the layout of version 2
+(none for E = 1), block b coded by the static coder under table (b // G) E + b mod E, G = 64 E k.  The marker nibble 5 of
+the word at offset 12 is required: no other version's word carries it.  Tables that redux_segment_static_table_check
+rejects are InvalidInput, truncated ones Eof.  It has no stored blocks (no 0x45 / 0x55).
+
+Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14 / 0x15: versions 1 / 2 / 3 / 4 / 5 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -57,6 +65,8 @@ VERSION = 1
 VERSION_PLANES = 2
 VERSION_STATIC = 3
 VERSION_PLANE_STATIC = 4
+VERSION_SEGMENT_STATIC = 5
+SEGMENT_MARK = 0x50000000  # version 5's word at offset 12: SEGMENT_MARK | k << 4 | E
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
 CRC_FLAG = 0x10  # version bit: a table of per-block CRC-32 values follows the size table
 STORED_FLAG = 0x40  # version bit: a stored-block bitmap follows the size table (and the CRC table)
@@ -78,13 +88,15 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
+    params a SegmentStaticModel: streams of segment-static coding (version 5; element_size as for version 4).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap."""
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
+    segment = isinstance(params, api.SegmentStaticModel)
     if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1) \
-            or (plane and element_size not in (1, params.element_size)):
+            or ((plane or segment) and element_size not in (1, params.element_size)):
         raise api.InvalidInput()
-    if plane:
+    if plane or segment:
         element_size = params.element_size
     P = api._params_of(params)
     offs = np.asarray(offsets, dtype=np.uint64)
@@ -93,6 +105,12 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         raise api.InvalidInput()
     ver, res = (VERSION_STATIC, 0) if static else (VERSION_PLANE_STATIC, element_size << 16 | element_size) if plane \
         else (VERSION, 0) if element_size == 1 else (VERSION_PLANES, element_size)
+    if segment:
+        k = params.segment_blocks // (64 * element_size)
+        if not 1 <= k < 1 << 24:
+            raise api.InvalidInput()
+        params.check(len(sizes))  # (the table count against this many blocks)
+        ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -103,7 +121,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     bitmap = b""
     if stored is not None:
         f = np.asarray(stored)
-        if static or plane or f.shape != (len(sizes),) or bool((f > 1).any()) \
+        if static or plane or segment or f.shape != (len(sizes),) or bool((f > 1).any()) \
                 or bool((sizes[f == 1] != _raw_lengths(len(sizes), block_size, total_len)[f == 1]).any()):
             raise api.InvalidInput()
         ver |= STORED_FLAG
@@ -111,7 +129,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if static:
         head += params.cum.astype("<u4").tobytes()
-    if plane:
+    if plane or segment:
         head += params.cums.astype("<u4").tobytes()
     return head + sizes.astype("<u4").tobytes() + crc + bitmap + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
 
@@ -126,7 +144,9 @@ def _version_ok(ver, res):
     layout = _layout(ver)
     return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
         or (layout == VERSION_PLANES and res in ELEMENT_SIZES) \
-        or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF)
+        or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF) \
+        or (layout == VERSION_SEGMENT_STATIC and not ver & STORED_FLAG and res >> 28 == 5 and res & 0xF in (1,) + ELEMENT_SIZES
+            and res >> 4 & 0xFFFFFF >= 1)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
@@ -147,7 +167,14 @@ def _header(b):
     P = api.Parameters(sb, fb, cb)
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
-    return ver, P, block_size, res & 0xFFFF if _layout(ver) in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1, nblocks, total
+    layout = _layout(ver)
+    E = res & 0xF if layout == VERSION_SEGMENT_STATIC else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    return ver, P, block_size, E, nblocks, total
+
+
+def _segment_k(b):
+    """k of a version 5 header (already checked by _header)"""
+    return HEADER.unpack_from(b, 0)[6] >> 4 & 0xFFFFFF
 
 
 def _take(b, at, dtype, count):
@@ -176,6 +203,15 @@ def _parse(buf):
         try:
             static = api.PlaneStaticModel(P, cums.reshape(E, 258))
         except api.Error:  # (redux_plane_static_table_check)
+            raise api.InvalidInput()
+    if _layout(ver) == VERSION_SEGMENT_STATIC:
+        G = 64 * E * _segment_k(b)
+        nseg = max(1, -(-nblocks // G))  # (nseg follows from the header: a file with another table count reads as damaged)
+        cums, at = _take(b, at, "<u4", 258 * E * nseg)
+        try:
+            static = api.SegmentStaticModel(P, cums.reshape(E * nseg, 258), E, G)
+            static.check(nblocks)
+        except api.Error:  # (redux_segment_static_table_check)
             raise api.InvalidInput()
     sizes, at = _take(b, at, "<u4", nblocks)
     sizes = sizes.astype(np.uint64)
@@ -236,6 +272,13 @@ def plane_static_tables(buf):
     return static.cums if isinstance(static, api.PlaneStaticModel) else None
 
 
+def segment_static_tables(buf):
+    """(tables np.uint32[nseg * E, 258], segment_blocks) of a version 5 container; None for versions 1 to 4.  Malformed
+    containers raise InvalidInput, truncated ones Eof."""
+    static = _parse(buf).static
+    return (static.cums, static.segment_blocks) if isinstance(static, api.SegmentStaticModel) else None
+
+
 def header_is_wellformed(buf):
     """True when the first 32 bytes are a consistent container header: magic, version, a triple
     Parameters::new accepts, a block size in range and a block count that matches the declared
@@ -250,22 +293,27 @@ def header_is_wellformed(buf):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False):
+                   stored=False, segment_blocks=None):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
     model "plane-static" (element_size 2 / 4 / 8): a static table per byte plane, built from the data
     (api.plane_static_tables, default total), version 4.
-    stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with a static model."""
+    stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with a static model.
+    model "segment-static" (element_size 1 / 2 / 4 / 8): static tables per segment_blocks blocks (a multiple of
+    64 * element_size; None: api.default_segment_blocks), built from each range as it is coded, version 5."""
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
-            or model not in ("adaptive", "static", "plane-static") or (model == "static" and (element_size != 1 or stored)) \
-            or (model == "plane-static" and (element_size == 1 or stored)):
+            or model not in ("adaptive", "static", "plane-static", "segment-static") \
+            or (model == "static" and (element_size != 1 or stored)) \
+            or (model == "plane-static" and (element_size == 1 or stored)) or (model == "segment-static" and stored) \
+            or (model != "segment-static" and segment_blocks is not None):
         raise api.InvalidInput()
     nb = max(1, -(-len(data) // block_size))
     crc = np.zeros(nb, dtype=np.uint32) if checksum else None
     flags = np.zeros(nb, dtype=np.uint8) if stored else None
     m = api.StaticModel.from_data(data, params) if model == "static" \
-        else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" else params
+        else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" \
+        else api.SegmentStaticModel.template(params, element_size, segment_blocks) if model == "segment-static" else params
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags)
 
@@ -280,12 +328,13 @@ def decompress_bytes(buf):
     if len(c.payload) < nb - (0 if c.stored is None else int(c.stored.sum())):  # (a stored block may be empty)
         raise api.InvalidInput()
     got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
-    exact = c.element_size > 1 or c.stored is not None
+    segment = isinstance(c.static, api.SegmentStaticModel)
+    exact = c.element_size > 1 or c.stored is not None or segment
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if exact:  # (the blocks decode at their real size, into out[0 .. total))
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
-                                                       c.static if c.element_size > 1 and c.static is not None else c.params,
+                                                       c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
                                                        stored=c.stored)
         else:  # (straight into out[b * cap ..], no plane buffer)

@@ -14,6 +14,7 @@
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist / k_*_plane_static*: the static coder with one table per byte plane
+//   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
@@ -35,6 +36,7 @@
 #include "redux_planes.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
+#include "redux_segment_static.hpp"
 #include "redux_crc.hpp"
 #include "redux_store.hpp"
 
@@ -1399,7 +1401,7 @@ static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *c
 static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
                               uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr,
-                              const uint8_t *stored = nullptr)
+                              const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {})
 {
     if (params != REDUX_OK)
         return params;
@@ -1412,7 +1414,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
     return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
-                               block_crc, stored); // redux_host.hpp
+                               block_crc, stored, tables); // redux_host.hpp
 }
 
 int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
@@ -2360,6 +2362,457 @@ int redux_plane_static_decode_blocks_crc(const redux_params *p, const uint32_t *
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
                               block_status, nullptr, plane_static_decoder(p, cum, block_size, st == REDUX_OK ? element_size : 1),
                               block_crc);
+}
+
+// ---- segment-static coding (redux_segment_static.hpp) ----------------------------------------------
+// nseg * E tables, table (b / G) E + b mod E for block b of the byte-plane layout; G = 64 E k.  The launch shape is
+// plane-static's (plane_slots wave slots per plane, workgroup g serves t = g mod E); slot w lies in segment w / k.
+static int segment_static_check(const redux_params *p, uint32_t element_size, uint32_t segment_blocks, uint32_t total)
+{
+    int st = plane_static_check(p, element_size, total);
+    if (st != REDUX_OK)
+        return st;
+    return segment_blocks != 0 && segment_blocks % (64 * element_size) == 0 ? REDUX_OK : REDUX_INVALID_INPUT;
+}
+
+uint64_t redux_segment_static_table_count(uint64_t nblocks, uint32_t element_size, uint32_t segment_blocks)
+{
+    if (redux_planes_check(element_size) != REDUX_OK || segment_blocks == 0 || segment_blocks % (64 * element_size) != 0)
+        return 0;
+    const uint64_t nseg = nblocks / segment_blocks + (nblocks % segment_blocks ? 1 : 0);
+    return (nseg ? nseg : 1) * element_size;
+}
+
+int redux_segment_static_table_check(const redux_params *p, const uint32_t *cum, uint64_t ntables, uint64_t nblocks,
+                                     uint32_t element_size, uint32_t segment_blocks)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p))
+        return REDUX_UNSUPPORTED;
+    const uint64_t want = redux_segment_static_table_count(nblocks, element_size, segment_blocks);
+    if (want == 0 || ntables != want || !cum)
+        return REDUX_INVALID_INPUT;
+    uint32_t total = 0; // of the tables that own bytes; a table that owns none is all ones (total 257)
+    for (uint64_t i = 0; i < ntables; i++) {
+        const uint32_t *c = cum + kStaticEntries * i;
+        if ((st = static_check(p, c)) != REDUX_OK)
+            return st;
+        if (c[kStaticEntries - 1] == kStaticEntries - 1)
+            continue;
+        if (total && c[kStaticEntries - 1] != total)
+            return REDUX_INVALID_INPUT;
+        total = c[kStaticEntries - 1];
+    }
+    return REDUX_OK;
+}
+
+uint32_t redux_segment_static_total(const uint32_t *cum, uint64_t ntables)
+{
+    uint32_t total = kStaticEntries - 1;
+    for (uint64_t i = 0; cum && i < ntables; i++)
+        if (cum[kStaticEntries * i + kStaticEntries - 1] > total)
+            total = cum[kStaticEntries * i + kStaticEntries - 1];
+    return total;
+}
+
+int redux_segment_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint64_t nblocks, uint32_t element_size,
+                                            uint32_t segment_blocks, uint32_t total, uint32_t *cum)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!counts || !cum)
+        return REDUX_INVALID_INPUT;
+    const uint64_t n = redux_segment_static_table_count(nblocks, element_size, segment_blocks);
+    for (uint64_t i = 0; i < n; i++)
+        if ((st = redux_static_table_from_counts(p, counts + 256 * i, total, cum + kStaticEntries * i)) != REDUX_OK)
+            return st;
+    return REDUX_OK;
+}
+
+int redux_segment_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size, uint32_t segment_blocks,
+                                void *d_counts, void *stream)
+{
+    if (block_size == 0 || !d_counts || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    const uint64_t npairs = redux_segment_static_table_count(redux_block_count(in_len, block_size), element_size, segment_blocks);
+    if (npairs == 0)
+        return REDUX_INVALID_INPUT;
+    if (in_len == 0)
+        return REDUX_OK;
+    SegmentHistArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.nfull      = in_len / block_size;
+    a.npairs     = npairs;
+    a.block_size = block_size;
+    a.E          = element_size;
+    a.G          = segment_blocks;
+    a.vec        = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    const uint32_t V = block_size / 16;
+    a.vshift     = a.vec && (V & (V - 1)) == 0 ? (uint32_t)__builtin_ctz(V) : 0xFFFFFFFFu;
+    a.counts     = (unsigned long long *)d_counts;
+    // The grid: what the device holds (kHistWgsPerCu one-wave workgroups per CU), dealt over the pairs.  Few pairs: several
+    // workgroups walk one pair, as many as its bytes give a step's work to.  More pairs than that: one workgroup per pair, a
+    // pair after the other.
+    const uint64_t cap   = (uint64_t)kHistWgsPerCu * cu_count();
+    const uint64_t share = (uint64_t)(segment_blocks / element_size) * block_size; // bytes of a full pair
+    const uint64_t per   = a.vec ? share / (16ull * 64 * kHistUnroll) : segment_blocks / element_size;
+    uint64_t       wgs   = npairs >= cap ? 1 : cap / npairs;
+    wgs                  = wgs > per ? per : wgs;
+    a.wgs                = (uint32_t)(wgs < 1 ? 1 : wgs);
+    a.pstep              = npairs < cap ? npairs : cap;
+    k_segment_hist<<<(uint32_t)(a.pstep * a.wgs), 64, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_segment_static_tables_dev(const redux_params *p, const void *d_counts, uint64_t nblocks, uint32_t element_size,
+                                    uint32_t segment_blocks, uint32_t total, void *d_cum, void *stream)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_counts || !d_cum)
+        return REDUX_INVALID_INPUT;
+    const uint64_t n = redux_segment_static_table_count(nblocks, element_size, segment_blocks);
+    if (n > 0x7FFFFFFFull)
+        return REDUX_UNSUPPORTED;
+    k_static_tables<<<(uint32_t)n, 256, 0, (hipStream_t)stream>>>((const unsigned long long *)d_counts, total, (uint32_t *)d_cum);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// The lookup decoder's WAVES wave slots share a table, so they must share a segment: k a multiple of WAVES.  Where the
+// 8-wave instance does not suit, the 4-wave one is tried; where neither does (k = 1, 2, 3, 5, ...), the lock-step decoder.
+static StaticDecKernel pick_segment_decode_kernel(const redux_params *p, uint32_t total, uint64_t launch_blocks, uint32_t k)
+{
+    const StaticDecKernel d    = pick_static_decode_kernel(p, total, launch_blocks);
+    const bool            cb32 = p->code_bits == 32;
+    switch (d) {
+    case StaticDecKernel::LutCb32:
+    case StaticDecKernel::Lut:
+        if (k % 8 == 0)
+            return d;
+        if (k % 4 == 0)
+            return cb32 ? StaticDecKernel::LutCb32Solo : StaticDecKernel::LutSolo;
+        return cb32 ? StaticDecKernel::LockCb32 : StaticDecKernel::Lock;
+    case StaticDecKernel::LutCb32Solo:
+    case StaticDecKernel::LutSolo:
+        if (k % 4 == 0)
+            return d;
+        return cb32 ? StaticDecKernel::LockCb32Solo : StaticDecKernel::LockSolo;
+    default: return d;
+    }
+}
+
+static const char *segment_static_name(bool decode, int k)
+{
+    static const char *const enc[4] = {"k_encode_segment_static<true, false> (total >= 2^17: quotient fix-up)",
+                                       "k_encode_segment_static<false, true, true> (code_bits 32, one wave per SIMD)",
+                                       "k_encode_segment_static<false, true> (code_bits 32)",
+                                       "k_encode_segment_static<false, false> (code_bits < 32)"};
+    static const char *const dec[9] = {
+        "k_decode_segment_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)",
+        "k_decode_segment_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)",
+        "k_decode_segment_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)",
+        "k_decode_segment_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)",
+        "k_decode_segment_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)",
+        "k_decode_segment_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)",
+        "k_decode_segment_static_lock<true, false> (lock-step, code_bits 32)",
+        "k_decode_segment_static_lock<false, true> (lock-step, one wave per SIMD)",
+        "k_decode_segment_static_lock<false, false> (lock-step)"};
+    return decode ? dec[k] : enc[k];
+}
+
+const char *redux_segment_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
+                                                    uint32_t element_size, uint32_t segment_blocks)
+{
+    if (segment_static_check(p, element_size, segment_blocks, total) != REDUX_OK || block_size == 0)
+        return "";
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (!plane_static_fits(g, block_size, element_size))
+        return "";
+    return segment_static_name(false, (int)pick_static_encode_kernel(p, total, 64 * element_size * plane_slots(g.nblocks, element_size)));
+}
+
+const char *redux_segment_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size,
+                                                    uint32_t segment_blocks)
+{
+    if (segment_static_check(p, element_size, segment_blocks, total) != REDUX_OK || nblocks == 0)
+        return "";
+    return segment_static_name(true, (int)pick_segment_decode_kernel(p, total, 64 * element_size * plane_slots(nblocks, element_size),
+                                                                      segment_blocks / (64 * element_size)));
+}
+
+uint64_t redux_segment_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
+{
+    return redux_static_encode_bound(p, in_len, block_size);
+}
+
+uint64_t redux_segment_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_plane_static_encode_workspace_bytes(p, in_len, block_size, element_size);
+}
+
+uint64_t redux_segment_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_plane_static_decode_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+static uint64_t segment_counts_bytes(uint64_t ntables) { return align_up(ntables * 256 * 8, 256); }
+
+uint64_t redux_segment_static_build_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size,
+                                                           uint32_t element_size, uint32_t segment_blocks)
+{
+    if (block_size == 0)
+        return 0;
+    const uint64_t n  = redux_segment_static_table_count(redux_block_count(in_len, block_size), element_size, segment_blocks);
+    const uint64_t ws = redux_segment_static_encode_workspace_bytes(p, in_len, block_size, element_size);
+    return n && ws ? segment_counts_bytes(n) + ws : 0;
+}
+
+// the static coder over x' (d_x: the layout of the input, or the input itself for E = 1) under the tables at d_cum
+static int segment_static_encode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_x, uint64_t in_len,
+                                   uint32_t block_size, uint32_t E, uint32_t G, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                                   void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (workspace_bytes < g.total)
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (!plane_static_fits(g, block_size, E))
+        return REDUX_UNSUPPORTED;
+    hipStream_t s  = (hipStream_t)stream;
+    uint8_t    *ws = (uint8_t *)d_workspace;
+    HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
+    SegmentStaticEncArgs a;
+    a.c.in         = (const uint8_t *)d_x;
+    a.c.in_len     = in_len;
+    a.c.nblocks    = g.nblocks;
+    a.c.slots      = ws + g.off_slots;
+    a.c.slot_bytes = g.slot_bytes;
+    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
+    a.c.status     = (int32_t *)d_block_status;
+    a.c.rc         = static_rc(total);
+    a.c.block_size = block_size;
+    a.c.slot_cap   = g.slot_cap;
+    a.c.code_bits  = p->code_bits;
+    a.c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    a.t.p.cum      = (const uint32_t *)d_cum;
+    a.t.p.E        = E;
+    a.t.p.total    = total;
+    a.t.p.rc257    = static_rc(kStaticEntries - 1);
+    a.t.k          = G / (64 * E);
+    const uint64_t slots = plane_slots(g.nblocks, E);
+    const uint32_t grid  = (uint32_t)(slots * E);
+    switch (pick_static_encode_kernel(p, total, 64 * E * slots)) {
+    case StaticEncKernel::Fixup: k_encode_segment_static<true, false><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32Solo: k_encode_segment_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32: k_encode_segment_static<false, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Narrow: k_encode_segment_static<false, false><<<grid, 64, 0, s>>>(a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_segment_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                    uint32_t block_size, uint32_t element_size, uint32_t segment_blocks, void *d_out, uint64_t out_cap,
+                                    void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
+                                    uint64_t workspace_bytes, void *stream)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
+        return REDUX_INVALID_INPUT;
+    if (element_size == 1)
+        return segment_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, segment_blocks, d_out, out_cap, d_out_offsets,
+                                       d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+    const uint64_t copy = planes_copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *x = (uint8_t *)d_workspace;
+    if ((st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+        return st;
+    return segment_static_encode_x(p, d_cum, total, x, in_len, block_size, element_size, segment_blocks, d_out, out_cap, d_out_offsets,
+                                   d_block_status, d_summary, x + copy, workspace_bytes - copy, stream);
+}
+
+// Layout once, the histogram of that copy, the tables, the coder over the same copy.  The workspace: the counts, then what
+// redux_segment_static_encode_dev takes.
+int redux_segment_static_build_encode_dev(const redux_params *p, uint32_t total, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                          uint32_t element_size, uint32_t segment_blocks, void *d_cum, void *d_out, uint64_t out_cap,
+                                          void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
+                                          uint64_t workspace_bytes, void *stream)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(in_len, block_size);
+    const uint64_t cb      = segment_counts_bytes(redux_segment_static_table_count(nblocks, element_size, segment_blocks));
+    const uint64_t copy    = element_size > 1 ? planes_copy_bytes(in_len) : 0;
+    if (workspace_bytes < cb + copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    hipStream_t s      = (hipStream_t)stream;
+    uint8_t    *counts = (uint8_t *)d_workspace, *x = counts + cb;
+    HIP_TRY(hipMemsetAsync(counts, 0, cb, s));
+    if (element_size > 1 && (st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+        return st;
+    const void *d_x = element_size > 1 ? x : d_in;
+    if ((st = redux_segment_histogram_dev(d_x, in_len, block_size, element_size, segment_blocks, counts, stream)) != REDUX_OK)
+        return st;
+    if ((st = redux_segment_static_tables_dev(p, counts, nblocks, element_size, segment_blocks, total, d_cum, stream)) != REDUX_OK)
+        return st;
+    return segment_static_encode_x(p, d_cum, total, d_x, in_len, block_size, element_size, segment_blocks, d_out, out_cap, d_out_offsets,
+                                   d_block_status, d_summary, x + copy, workspace_bytes - cb - copy, stream);
+}
+
+// the static decoders under nseg * E tables: nblocks streams -> block b at d_planes + b * block_size
+static int segment_static_decode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                   uint64_t nblocks, uint32_t block_size, uint32_t E, uint32_t G, void *d_planes, void *d_out_sizes,
+                                   void *d_block_status, hipStream_t s)
+{
+    SegmentStaticLockArgs la;
+    memset(&la, 0, sizeof la);
+    la.d.in         = (const uint8_t *)d_in;
+    la.d.in_offsets = (const uint64_t *)d_in_offsets;
+    la.d.nblocks    = nblocks;
+    la.d.out        = (uint8_t *)d_planes;
+    la.d.out_sizes  = (uint32_t *)d_out_sizes;
+    la.d.status     = (int32_t *)d_block_status;
+    la.d.block_size = block_size;
+    la.d.nfreeze    = 0xFFFFFFFFu;
+    la.d.code_bits  = p->code_bits;
+    la.d.aligned4   = ((((uintptr_t)d_planes) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    if (la.d.aligned4 && (((uintptr_t)d_planes) & 15) == 0 && (block_size & 15) == 0)
+        la.d.aligned4 = 2;
+    la.rc        = static_rc(total);
+    la.t.p.cum   = (const uint32_t *)d_cum;
+    la.t.p.E     = E;
+    la.t.p.total = total;
+    la.t.p.rc257 = static_rc(kStaticEntries - 1);
+    la.t.k       = G / (64 * E);
+    const uint64_t slots = plane_slots(nblocks, E);
+    const uint32_t grid  = (uint32_t)(slots * E), grid4 = (uint32_t)((slots + 3) / 4 * E), grid8 = (uint32_t)((slots + 7) / 8 * E);
+    switch (pick_segment_decode_kernel(p, total, 64 * E * slots, la.t.k)) {
+    case StaticDecKernel::Fixup: {
+        SegmentStaticDecArgs a;
+        a.c.in         = la.d.in;
+        a.c.in_offsets = la.d.in_offsets;
+        a.c.nblocks    = nblocks;
+        a.c.out        = la.d.out;
+        a.c.out_sizes  = la.d.out_sizes;
+        a.c.status     = la.d.status;
+        a.c.rc         = la.rc;
+        a.c.block_size = block_size;
+        a.c.code_bits  = p->code_bits;
+        a.c.aligned4   = la.d.aligned4 ? 1 : 0;
+        a.t            = la.t;
+        k_decode_segment_static<true><<<grid, 64, 0, s>>>(a);
+        break;
+    }
+    case StaticDecKernel::LutCb32Solo: k_decode_segment_static_lut<true, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutSolo: k_decode_segment_static_lut<false, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutCb32: k_decode_segment_static_lut<true, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::Lut: k_decode_segment_static_lut<false, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32Solo: k_decode_segment_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32: k_decode_segment_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockSolo: k_decode_segment_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::Lock: k_decode_segment_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// redux_plane_static_decode_dev's procedure: plane buffer at the front of the workspace, sizes checked against the layout,
+// the inverse transform into d_out[0 .. out_len), the summary last
+int redux_segment_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                    uint64_t out_len, uint32_t block_size, uint32_t element_size, uint32_t segment_blocks, void *d_out,
+                                    void *d_out_sizes, void *d_block_status, void *d_summary, void *d_workspace,
+                                    uint64_t workspace_bytes, void *stream)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status || (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    if (workspace_bytes < redux_segment_static_decode_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t    *x = (uint8_t *)d_workspace;
+    if ((st = segment_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, element_size, segment_blocks, x,
+                                      d_out_sizes, d_block_status, s)) != REDUX_OK)
+        return st;
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
+                                                                        nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    if ((st = redux_planes_dev(x, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
+        return st;
+    if (d_summary)
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// The coders of the chunked host calls.  Chunks are whole segments (host::SegmentTablesIo), so a chunk's segment numbers are
+// the call's minus a constant and its tables are a contiguous run of the call's: encode builds them from the chunk into the
+// slot's d_tab, decode finds them staged there.
+static host::EncodeCoder segment_static_encoder(const redux_params *p, uint32_t total, uint32_t block_size, uint32_t E, uint32_t G)
+{
+    return {[=](uint64_t max_in, bool, uint64_t &ws, uint64_t &bound) {
+                ws    = redux_segment_static_build_encode_workspace_bytes(p, max_in, block_size, E, G);
+                bound = redux_segment_static_encode_bound(p, max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                return redux_segment_static_build_encode_dev(p, total, s.d_in.p, len, block_size, E, G, s.d_tab.p, s.d_out.p, bound,
+                                                             s.d_off.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
+static host::DecodeCoder segment_static_decoder(const redux_params *p, uint32_t total, uint32_t block_size, uint32_t E, uint32_t G)
+{
+    return {[=](uint64_t cb) { return redux_segment_static_decode_workspace_bytes(p, cb * (uint64_t)block_size, block_size, E); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                return redux_segment_static_decode_dev(p, s.d_tab.p, total, s.d_in.p, s.d_off.p, out_bytes, block_size, E, G, s.d_out.p,
+                                                       s.d_sz.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            },
+            true};
+}
+
+int redux_segment_static_encode_blocks_crc(const redux_params *p, uint32_t total, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                           uint32_t element_size, uint32_t segment_blocks, uint32_t *cum, uint8_t *out, uint64_t out_cap,
+                                           uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = segment_static_check(p, element_size, segment_blocks, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !cum || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               segment_static_encoder(p, total, block_size, element_size, segment_blocks), block_crc, nullptr,
+                               host::SegmentTablesIo{cum, element_size, segment_blocks}); // redux_host.hpp
+}
+
+int redux_segment_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, uint64_t ntables, const uint8_t *in,
+                                           const uint64_t *in_offsets, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                                           uint32_t segment_blocks, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                                           uint32_t *block_crc)
+{
+    if (block_size == 0)
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const int      st      = redux_segment_static_table_check(p, cum, ntables, nblocks, element_size, segment_blocks);
+    if (st != REDUX_OK)
+        return st;
+    return decode_blocks_host(st, in, in_offsets, nblocks, block_size, out, out_len, out_len, out_sizes, block_status, nullptr,
+                              segment_static_decoder(p, redux_segment_static_total(cum, ntables), block_size, element_size, segment_blocks),
+                              block_crc, nullptr, host::SegmentTablesIo{const_cast<uint32_t *>(cum), element_size, segment_blocks});
 }
 
 // ---- stored blocks (redux_store.hpp) --------------------------------------------------------------

@@ -6,7 +6,7 @@
 //                   of gfx950's 64, whatever the data: a buffer of one byte value costs what iid bytes cost.  The counters are
 //                   folded into 64-bit registers before any of them can reach 65,536, and each workgroup ends with one
 //                   global u64 atomic add per nonzero bin (integer adds: the result does not depend on their order).
-//   k_static_table  one workgroup of 256 threads: the counts -> cum[0..=257] by the rule of include/redux_hip.h
+//   k_static_table  one workgroup of 256 threads (static_table_build): the counts -> cum[0..=257] by the rule of include/redux_hip.h
 //                   ("semi-static coding"), bit for bit what redux_static_table_from_counts computes on the host.
 //
 // Included by redux_hip.hip (one translation unit).
@@ -149,7 +149,8 @@ __global__ void __launch_bounds__(64) k_byte_hist(HistArgs a)
 // thread s: byte s.  N = sum c, R = total - 257; f[s] = 1 + floor(c[s] R / N), r[s] = c[s] R mod N; the D = total - sum f
 // bytes with the largest r (ties: lower index first) get one more; EOF = 1.  N = 0: every frequency 1.  N R >= 2^64 (or
 // N itself >= 2^64): the table is all zeros, which redux_static_table_check rejects.
-__global__ void __launch_bounds__(256) k_static_table(const unsigned long long *counts, uint32_t total, uint32_t *cum)
+// (every thread of a 256-thread workgroup calls this: barriers)
+__device__ __forceinline__ void static_table_build(const unsigned long long *counts, uint32_t total, uint32_t *cum)
 {
     __shared__ unsigned long long s_lo[256], s_hi[256], s_r[256];
     __shared__ uint32_t           s_f[256];
@@ -212,6 +213,11 @@ __global__ void __launch_bounds__(256) k_static_table(const unsigned long long *
         cum[0] = 0;
     if (s == 255)
         cum[257] = s_f[255] + 1;
+}
+
+__global__ void __launch_bounds__(256) k_static_table(const unsigned long long *counts, uint32_t total, uint32_t *cum)
+{
+    static_table_build(counts, total, cum);
 }
 
 } // namespace redux

@@ -686,6 +686,24 @@ struct DecodeCoder {
     bool original_order = false;
 };
 
+// Segment-static coding (include/redux_hip.h): the call's tables, u32[nseg][E][258] in caller memory, travel per chunk through
+// the slot's d_tab / h_tab as the CRCs travel through d_crc / h_crc.  Chunks are whole segments of G blocks, so chunk
+// [b0, b0 + nb) owns the tables (b0 / G) E .. of the call: encode's coder leaves them in d_tab and they are fetched with the
+// chunk's small arrays; decode stages them to d_tab before its coder runs.  cum == null: the call has no tables.
+struct SegmentTablesIo {
+    uint32_t *cum = nullptr;
+    uint32_t  E = 1, G = 0;
+    uint64_t chunk_blocks(uint64_t cb, uint64_t nblocks) const // cb rounded up to whole segments
+    {
+        if (!cum || cb >= nblocks)
+            return cb;
+        cb = (cb + G - 1) / G * G;
+        return cb < nblocks ? cb : nblocks;
+    }
+    uint64_t bytes(uint64_t nb) const { return cum ? (nb + G - 1) / G * E * 258ull * 4 : 0; } // of a chunk's tables (nb >= 1)
+    uint32_t *at(uint64_t b0) const { return cum + b0 / G * E * 258ull; }
+};
+
 // ================================================================================================
 // encode: chunk k = blocks [k * cb, k * cb + nb) of the input -> its streams at their place in the dense output
 // ================================================================================================
@@ -700,12 +718,13 @@ struct EncodeChunks {
     const EncodeCoder &coder;
     uint32_t          *block_crc; // may be null: CRC-32 of each input block (redux_crc.hpp), on the staged chunk
     uint8_t           *stored;    // may be null: the stored-block flags the coder leaves in s.d_stf (redux_store.hpp)
+    SegmentTablesIo    tables;    // cum may be null: the segment tables the coder leaves in s.d_tab
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
     {
         nblocks = redux_block_count(in_len, block_size);
-        cb      = chunk_blocks_for(nblocks, block_size, kEncChunkMax, nctx);
+        cb      = tables.chunk_blocks(chunk_blocks_for(nblocks, block_size, kEncChunkMax, nctx), nblocks);
         nchunks = n = (nblocks + cb - 1) / cb;
         max_in  = cb * (uint64_t)block_size < in_len ? cb * (uint64_t)block_size : in_len; // bytes of the largest chunk
         coder.size(max_in, nchunks > 1, ws_bytes, bound);
@@ -722,6 +741,11 @@ struct EncodeChunks {
                                      {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
         if (rc == REDUX_OK && stored) {
             const int r2 = grow_bufs(c, {{&s.d_stf, cb}, {&s.h_stf, cb}});
+            if (r2 != REDUX_OK)
+                return r2;
+        }
+        if (rc == REDUX_OK && tables.cum) {
+            const int r2 = grow_bufs(c, {{&s.d_tab, tables.bytes(cb)}, {&s.h_tab, tables.bytes(cb)}});
             if (r2 != REDUX_OK)
                 return r2;
         }
@@ -744,7 +768,8 @@ struct EncodeChunks {
     {
         return fetch_small(s.h_off, s.d_off, (nb + 1) * 8, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
                fetch_small(s.h_sum, s.d_sum, 8, st) && (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st)) &&
-               (!stored || fetch_small(s.h_stf, s.d_stf, nb, st));
+               (!stored || fetch_small(s.h_stf, s.d_stf, nb, st)) &&
+               (!tables.cum || fetch_small(s.h_tab, s.d_tab, tables.bytes(nb), st));
     }
     Placed place(Ctx &c, Slot &s, uint64_t k, uint64_t b0, uint64_t nb, Ledger &L) const
     {
@@ -767,15 +792,17 @@ struct EncodeChunks {
             memcpy(block_crc + b0, s.h_crc.p, nb * 4);
         if (stored)
             memcpy(stored + b0, s.h_stf.p, nb);
+        if (tables.cum)
+            memcpy(tables.at(b0), s.h_tab.p, tables.bytes(nb));
         return {};
     }
 };
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr,
-                         uint8_t *stored = nullptr)
+                         uint8_t *stored = nullptr, SegmentTablesIo tables = {})
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables};
     return run_chunks(op);
 }
 
@@ -795,11 +822,12 @@ struct DecodeChunks {
     const DecodeCoder &coder;
     uint32_t          *block_crc; // may be null: CRC-32 of what each block decoded to (redux_crc.hpp), on the chunk's output
     const uint8_t     *stored;    // may be null: stored-block flags, staged to s.d_stf with the chunk's offsets (redux_store.hpp)
+    SegmentTablesIo    tables;    // cum may be null: the segment tables, staged to s.d_tab with the chunk's offsets
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
     {
-        cb       = chunk_blocks_for(nblocks, block_size, kDecChunkMax, nctx);
+        cb       = tables.chunk_blocks(chunk_blocks_for(nblocks, block_size, kDecChunkMax, nctx), nblocks);
         nchunks  = n = (nblocks + cb - 1) / cb;
         ws_bytes = coder.workspace(cb);
         for (uint64_t k = 0; k < nchunks; k++) {
@@ -827,6 +855,11 @@ struct DecodeChunks {
             if (r2 != REDUX_OK)
                 return r2;
         }
+        if (rc == REDUX_OK && tables.cum) {
+            const int r2 = grow_bufs(c, {{&s.d_tab, tables.bytes(cb)}, {&s.h_tab, tables.bytes(cb)}});
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
@@ -844,6 +877,10 @@ struct DecodeChunks {
         if (stored) {
             memcpy(s.h_stf.p, stored + b0, nb);
             HOST_TRY(hipMemcpyAsync(s.d_stf.p, s.h_stf.p, nb, hipMemcpyHostToDevice, st));
+        }
+        if (tables.cum) {
+            memcpy(s.h_tab.p, tables.at(b0), tables.bytes(nb));
+            HOST_TRY(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, tables.bytes(nb), hipMemcpyHostToDevice, st));
         }
         return stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
     }
@@ -880,9 +917,9 @@ struct DecodeChunks {
 
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                          uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
-                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr)
+                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {})
 {
-    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored};
+    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored, tables};
     return run_chunks(op);
 }
 

@@ -15,6 +15,7 @@
 //   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
 //   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
+//   redux::hip::compress_blocks_segment_static / decompress_blocks_segment_static   static tables per block range
 //
 // Every stream byte is produced by the gfx950 kernels; there is no CPU coder in this header.
 #pragma once
@@ -294,6 +295,58 @@ inline std::vector<std::uint8_t> decompress_blocks_static(const Blocks &streams,
                                      out.size(), sz.data(), nullptr));
     if (sizes)
         *sizes = sz;
+    return out;
+}
+
+// Segment-static coding (include/redux_hip.h): static tables per range of segment_blocks = 64 * element_size * k blocks of
+// the byte-plane layout, built from each range as it is coded (one pass).  tables: u32[nseg * element_size][258].
+struct SegmentBlocks {
+    Blocks                     blocks;
+    std::vector<std::uint32_t> tables;
+};
+inline SegmentBlocks compress_blocks_segment_static(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size,
+                                                    std::uint32_t element_size, std::uint32_t segment_blocks,
+                                                    const model::Parameters &p, std::uint32_t total = 0)
+{
+    const redux_params cp = p.c_abi();
+    if (total == 0) {
+        const std::uint64_t fmax = (1ull << p.freq_bits) - 1;
+        total = (std::uint32_t)(fmax < 65536 ? fmax : 65536);
+    }
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    const std::uint64_t nt = redux_segment_static_table_count(nb, element_size, segment_blocks);
+    if (nt == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    SegmentBlocks r;
+    r.tables.resize(nt * 258);
+    r.blocks.data.resize(redux_segment_static_encode_bound(&cp, len, block_size));
+    r.blocks.offsets.resize(nb + 1);
+    check(redux_segment_static_encode_blocks_crc(&cp, total, in, len, block_size, element_size, segment_blocks, r.tables.data(),
+                                                 r.blocks.data.data(), r.blocks.data.size(), r.blocks.offsets.data(), nullptr, nullptr));
+    r.blocks.data.resize(r.blocks.offsets[nb]);
+    return r;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_segment_static(const SegmentBlocks &s, std::uint64_t len, std::uint32_t block_size,
+                                                                  std::uint32_t element_size, std::uint32_t segment_blocks,
+                                                                  const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    const Blocks      &b  = s.blocks;
+    if (block_size == 0 || b.offsets.size() != redux_block_count(len, block_size) + 1 || b.offsets.back() > b.data.size() ||
+        s.tables.size() % 258)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < b.offsets.size(); i++)
+        if (b.offsets[i] < b.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t>  out(len ? len : 1);
+    std::vector<std::uint32_t> sz(b.offsets.size() - 1);
+    check(redux_segment_static_decode_blocks_crc(&cp, s.tables.data(), s.tables.size() / 258, b.data.data(), b.offsets.data(), len,
+                                                 block_size, element_size, segment_blocks, out.data(), sz.data(), nullptr, nullptr));
+    out.resize(len);
     return out;
 }
 

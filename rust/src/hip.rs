@@ -99,6 +99,24 @@ extern "C" {
     fn redux_plane_static_decode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
                                             out_len: u64, block_size: u32, element_size: u32, out: *mut u8,
                                             out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // segment-static coding: static tables per range of segment_blocks blocks (cum: u32[nseg * element_size][258])
+    fn redux_segment_static_table_count(nblocks: u64, element_size: u32, segment_blocks: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_segment_static_table_check(p: *const ReduxParams, cum: *const u32, ntables: u64, nblocks: u64, element_size: u32,
+                                        segment_blocks: u32) -> c_int;
+    #[allow(dead_code)]
+    fn redux_segment_static_total(cum: *const u32, ntables: u64) -> u32;
+    #[allow(dead_code)]
+    fn redux_segment_static_tables_from_counts(p: *const ReduxParams, counts: *const u64, nblocks: u64, element_size: u32,
+                                               segment_blocks: u32, total: u32, cum: *mut u32) -> c_int;
+    fn redux_segment_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
+    fn redux_segment_static_encode_blocks_crc(p: *const ReduxParams, total: u32, input: *const u8, in_len: u64, block_size: u32,
+                                              element_size: u32, segment_blocks: u32, cum: *mut u32, out: *mut u8, out_cap: u64,
+                                              out_offsets: *mut u64, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_segment_static_decode_blocks_crc(p: *const ReduxParams, cum: *const u32, ntables: u64, input: *const u8,
+                                              in_offsets: *const u64, out_len: u64, block_size: u32, element_size: u32,
+                                              segment_blocks: u32, out: *mut u8, out_sizes: *mut u32, block_status: *mut i32,
+                                              block_crc: *mut u32) -> c_int;
     fn redux_encode_blocks_stored(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
                                   store_ratio: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64, stored: *mut u8,
                                   block_status: *mut i32, block_crc: *mut u32) -> c_int;
@@ -295,6 +313,56 @@ pub fn decompress_blocks_static(streams: &[u8], offsets: &[u64], block_size: u32
         try!(status(redux_static_decode_blocks(&cp, cum.as_ptr(), streams.as_ptr(), offsets.as_ptr(), nb as u64, block_size,
                                                out.as_mut_ptr(), out.len() as u64, sizes.as_mut_ptr(), ptr::null_mut())));
         Ok((out, sizes))
+    }
+}
+
+/// Segment-static coding (include/redux_hip.h): static tables per range of `segment_blocks` = 64 * `element_size` * k blocks
+/// of the byte-plane layout, built from each range as it is coded.  Returns the dense streams, `nblocks + 1` offsets and the
+/// tables (`nseg * element_size * 258` entries).  `total` 0: min(2^16, freq_max).
+pub fn compress_blocks_segment_static(data: &[u8], block_size: u32, element_size: u32, segment_blocks: u32, total: u32,
+                                      p: &Parameters) -> Result<(Vec<u8>, Vec<u64>, Vec<u32>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    let fmax = (1u64 << cp.freq_bits) - 1;
+    let total = if total == 0 { if fmax < 65536 { fmax as u32 } else { 65536 } } else { total };
+    unsafe {
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let nt = redux_segment_static_table_count(nb as u64, element_size, segment_blocks) as usize;
+        if nt == 0 {
+            return Err(Error::InvalidInput);
+        }
+        let cap = redux_segment_static_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        let mut cum = vec![0u32; nt * 258];
+        try!(status(redux_segment_static_encode_blocks_crc(&cp, total, data.as_ptr(), data.len() as u64, block_size, element_size,
+                                                           segment_blocks, cum.as_mut_ptr(), out.as_mut_ptr(), cap as u64,
+                                                           offs.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs, cum))
+    }
+}
+
+/// Inverse of `compress_blocks_segment_static`: the original `len` bytes.
+pub fn decompress_blocks_segment_static(streams: &[u8], offsets: &[u64], cum: &[u32], len: u64, block_size: u32,
+                                        element_size: u32, segment_blocks: u32, p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || cum.len() % 258 != 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        if offsets.len() as u64 != redux_block_count(len, block_size) + 1 {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; if len == 0 { 1 } else { len as usize }];
+        let mut sizes = vec![0u32; offsets.len() - 1];
+        try!(status(redux_segment_static_decode_blocks_crc(&cp, cum.as_ptr(), (cum.len() / 258) as u64, streams.as_ptr(),
+                                                           offsets.as_ptr(), len, block_size, element_size, segment_blocks,
+                                                           out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
     }
 }
 
