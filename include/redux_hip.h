@@ -371,6 +371,54 @@ int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status);
 
+/* ---- delta filter for integer series -----------------------------------------------------------
+ * Typed data whose values are large but whose neighbours are close -- timestamps, sorted indices, offsets, counters, sampled
+ * signals -- has uniform low byte planes; the differences of neighbouring elements do not.  These calls put the delta
+ * filter in front of the byte-plane layout (Blosc, HDF5 and Zarr ship one next to their shuffle filter).  Strictly opt-in:
+ * floating-point data and plain bytes get LARGER with it.  E = element_size, one of 1, 2, 4, 8; B = block_size.
+ *   - The input is cut into the frames of the byte-plane layout: E*B bytes, only the last may be shorter (E = 1: a frame
+ *     is one block).  A frame of L bytes holds N = L / E little-endian unsigned elements x[0 .. N).
+ *   - The filter writes d[0] = x[0] and d[i] = x[i] - x[i-1] mod 2^(8E); the L - N*E trailing bytes are unchanged.
+ *   - The byte-plane layout above is then applied to the d's (E = 1: no layout).
+ *   - The inverse undoes the layout and takes the running sum mod 2^(8E) inside each frame.
+ * Every frame starts afresh: blocks of different frames stay independent, and a chunk boundary of the host calls changes
+ * nothing (chunks are whole 64-block waves, so whole frames).  Behind the transform is the plain adaptive coder:
+ *     stream_delta_E(x)[b] == redux_encode_blocks(planes_E(delta_E(x)))[b].
+ * Not available with the static-table models, stored blocks, the `_v` calls and redux_compress / redux_decompress.
+ *
+ * redux_delta_check          OK for 1, 2, 4, 8, else INVALID_INPUT.
+ * redux_delta_planes_dev     filter + layout (inverse = 0) or their inverse (inverse != 0) of len bytes, d_src -> d_dst
+ *                            (device buffers that must not overlap: INVALID_INPUT), stream-ordered, one read and one write.
+ * redux_encode_delta_dev     redux_encode_blocks_dev of the transformed input, the transformed copy carved from the FRONT of
+ *                            the workspace (redux_encode_delta_workspace_bytes: for E = 1 too, the filter changes the bytes).
+ * redux_decode_delta_dev     redux_decode_planes_dev's procedure: the blocks decode into a plane buffer in the workspace, a
+ *                            block that comes back OK with another size than its place gives it is reported INVALID_INPUT,
+ *                            the inverse writes d_out[0 .. out_len) and no byte outside it, for damaged streams too.  Every
+ *                            frame whose blocks are all OK holds the original bytes.
+ * redux_encode_blocks_delta  host-pointer forms on the chunk pipeline of redux_encode_blocks / redux_decode_blocks; the
+ * redux_decode_blocks_delta  output depends on neither the chunk size nor the devices of redux_host_set_devices.  block_crc
+ *                            may be null; else u32[nblocks], the CRC-32 of every block's ORIGINAL bytes ("per-block CRC-32
+ *                            checksums" below: decode fills it with the CRC of what the block's range of out holds).
+ */
+int      redux_delta_check(uint32_t element_size);
+int      redux_delta_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                                void *stream);
+uint64_t redux_encode_delta_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_delta_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                           void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                           void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                           void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_delta_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                           uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                           void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_delta(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                              uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                              uint32_t *block_crc);
+int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                              uint32_t *block_crc);
+
 /* ---- stored blocks -----------------------------------------------------------------------------
  * A block whose stream does not shrink it can travel as its raw bytes instead (zstd raw blocks, deflate stored blocks).
  * Block b has L_b = min(B, len - b*B) bytes of coder input x' (the input for element_size 1, its byte-plane layout for

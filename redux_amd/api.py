@@ -420,6 +420,17 @@ def _check_element_size(element_size):
     return int(element_size)
 
 
+def _check_filter(filter, allowed=True):
+    """filter=None, or "delta": the delta filter for integer series (include/redux_hip.h, "delta filter"); anything else,
+    and "delta" where it is not available (allowed false), is InvalidInput.  A check on the arguments alone: it comes
+    before any call into the library.  -> True for "delta"."""
+    if filter is None:
+        return False
+    if not isinstance(filter, str) or filter != "delta" or not allowed:
+        raise InvalidInput()
+    return True
+
+
 STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
 
 
@@ -435,7 +446,7 @@ def _array_arg(a, dtype, nb, writable=True):
 
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
-                    store_ratio=STORE_RATIO):
+                    store_ratio=STORE_RATIO, filter=None):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -449,9 +460,13 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     byte order for every layout (the `_crc` calls of include/redux_hip.h).
     stored: a np.uint8[nblocks] the same call fills with the stored-block flags (include/redux_hip.h, "stored blocks"):
     passing it turns stored blocks on, and block b's payload is then its raw (planes: plane) bytes wherever its stream
-    is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it."""
+    is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it.
+    filter="delta": the delta filter for integer series in front of the layout, for any element_size (include/redux_hip.h,
+    "delta filter": redux_encode_blocks_delta); decompress_blocks(..., element_size, length, filter="delta") undoes it.
+    Adaptive model only, and not with stored=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
+    delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     plane = plane or segment  # (the checks of a model that brings its own element size)
     P = _params_of(params)
     a = _u8(data)
@@ -480,6 +495,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
                                                       offs.ctypes.data, status.ctypes.data, crc)
         if st == _lib.OK or cums.any():
             params.cums = cums
+    elif delta:
+        st = L.redux_encode_blocks_delta(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
+                                         status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
@@ -508,7 +526,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None):
+                      block_crc=None, stored=None, filter=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -522,9 +540,14 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     block_crc: a np.uint32[nblocks] the same call fills with the CRC-32 of what each block decoded to (in original byte
     order: after the inverse byte-plane layout); unspecified for blocks whose status is not OK.
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
-    uint8[length] in original order, as with element_size > 1."""
+    uint8[length] in original order, as with element_size > 1.
+    filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
+    for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
+    delta = _check_filter(filter, not (static or plane or segment or stored is not None))
+    if delta and length is None:
+        raise InvalidInput()
     plane = plane or segment
     E = _check_element_size(element_size)
     if block_size <= 0 or (static and (E != 1 or length is not None or stored is not None)) \
@@ -552,6 +575,9 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
         st = L.redux_segment_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), len(params.cums), _ptr(a), offs.ctypes.data,
                                                       length, block_size, params.element_size, params.segment_blocks,
                                                       out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
+    elif delta:
+        st = L.redux_decode_blocks_delta(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
+                                         sizes.ctypes.data, status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
@@ -609,11 +635,12 @@ def block_table_v(offsets, lengths, block_size):
     return tab
 
 
-def compress_blocks_v(inputs, block_size, params=(8, 30, 32)):
+def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None):
     """redux::compress of every block of every input (a list of bytes-like objects), ONE launch for all of
     them; each input is cut into blocks on its own.  Returns (dense streams uint8, offsets
     uint64[nblocks+1], status int32[nblocks], first_block int64[len(inputs)+1]): input i owns blocks
-    first_block[i] .. first_block[i+1]-1."""
+    first_block[i] .. first_block[i+1]-1.  filter: None (the `_v` calls have no delta filter: "delta" is InvalidInput)."""
+    _check_filter(filter, False)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -638,9 +665,10 @@ def compress_blocks_v(inputs, block_size, params=(8, 30, 32)):
     return out[: int(offs[-1])], offs, status, first
 
 
-def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32), check=True):
+def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32), check=True, filter=None):
     """The inverse of compress_blocks_v: `lengths[i]` is the decoded size of input i.  Returns (list of
-    uint8 arrays, sizes uint32[nblocks], status int32[nblocks])."""
+    uint8 arrays, sizes uint32[nblocks], status int32[nblocks]).  filter: None ("delta" is InvalidInput)."""
+    _check_filter(filter, False)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -666,9 +694,11 @@ def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32
 
 
 # ---- src/lib.rs:102-120: whole-stream drop-ins --------------------------------------------
-def compress(istream, ostream, model):
+def compress(istream, ostream, model, filter=None):
     """redux::compress(istream, ostream, model) -> (bytes_in, bytes_out).  The whole input is
-    one block, so the stream equals the reference's; it is coded by one GPU lane."""
+    one block, so the stream equals the reference's; it is coded by one GPU lane.  filter: None (a raw reference stream
+    has no delta filter: "delta" is InvalidInput)."""
+    _check_filter(filter, False)
     P = _params_of(model)
     a = _u8(istream.read())
     L = _lib.lib()
@@ -682,8 +712,9 @@ def compress(istream, ostream, model):
     return (bi.value, bo.value)
 
 
-def decompress(istream, ostream, model, max_output=None):
-    """redux::decompress(istream, ostream, model) -> (bytes_in, bytes_out)."""
+def decompress(istream, ostream, model, max_output=None, filter=None):
+    """redux::decompress(istream, ostream, model) -> (bytes_in, bytes_out).  filter: None ("delta" is InvalidInput)."""
+    _check_filter(filter, False)
     P = _params_of(model)
     a = _u8(istream.read())
     L = _lib.lib()
@@ -745,7 +776,8 @@ class DeviceEncoder:
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
     on torch's current stream."""
 
-    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1):
+    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None):
+        self.delta = _check_filter(filter)  # the delta filter in front of the layout (encode() only)
         torch = _torch()
         self.P = _params_of(params)
         self.cp = self.P._c()
@@ -755,8 +787,8 @@ class DeviceEncoder:
         self.block_size = int(block_size)
         self.max_in_len = int(max_in_len)
         self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        self.ws_bytes = L.redux_encode_planes_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size,
-                                                              self.element_size)
+        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_planes_workspace_bytes
+        self.ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
         self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
         self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
@@ -772,8 +804,8 @@ class DeviceEncoder:
     def encode_slots(self, d_in):
         """Phase 1 only: the coder kernel (padded slots + sizes inside the workspace)."""
         torch = _torch()
-        if self.element_size != 1:
-            raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout)
+        if self.element_size != 1 or self.delta:
+            raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout and the filter)
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
         st = _lib.lib().redux_encode_slots_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
@@ -785,7 +817,7 @@ class DeviceEncoder:
     def compact(self, n):
         """Phase 2 only: scan + gather into the dense output."""
         torch = _torch()
-        if self.element_size != 1:
+        if self.element_size != 1 or self.delta:
             raise Unsupported()
         self.summary.zero_()
         st = _lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, C.c_void_p(self.out.data_ptr()),
@@ -803,7 +835,13 @@ class DeviceEncoder:
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
         self.summary.zero_()
-        if self.element_size == 1:
+        if self.delta:
+            st = _lib.lib().redux_encode_delta_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
+                                                   self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
+                                                   C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                                   C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+                                                   _stream_ptr(torch))
+        elif self.element_size == 1:
             st = _lib.lib().redux_encode_blocks_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
                                                     C.c_void_p(self.out.data_ptr()), self.out_cap,
                                                     C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
@@ -822,9 +860,11 @@ class DeviceEncoder:
 
 class DeviceDecoder:
     """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
-    layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes."""
+    layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes.  filter="delta": the
+    streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size."""
 
-    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1):
+    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None):
+        self.delta = _check_filter(filter)
         torch = _torch()
         self.P = _params_of(params)
         self.cp = self.P._c()
@@ -833,7 +873,7 @@ class DeviceDecoder:
         self.element_size = _check_element_size(element_size)
         self.block_size = int(block_size)
         self.max_blocks = int(max_blocks)
-        if self.element_size == 1:
+        if self.element_size == 1 and not self.delta:
             self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
         else:
             self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
@@ -853,7 +893,7 @@ class DeviceDecoder:
         L = _lib.lib()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
-        if (length is None and self.element_size > 1) \
+        if (length is None and (self.element_size > 1 or self.delta)) \
                 or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)):
             raise InvalidInput()
         if length is not None:
@@ -863,11 +903,12 @@ class DeviceDecoder:
                                                                       self.block_size, 1)
                 self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
             self.summary.zero_()
-            st = L.redux_decode_planes_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
-                                           C.c_void_p(d_offsets.data_ptr()), int(length), self.block_size, self.element_size,
-                                           C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
-                                           C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
-                                           C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
+            decode_dev = L.redux_decode_delta_dev if self.delta else L.redux_decode_planes_dev
+            st = decode_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
+                            C.c_void_p(d_offsets.data_ptr()), int(length), self.block_size, self.element_size,
+                            C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
+                            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
+                            C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
             _raise(st)
             return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
         self.summary.zero_()
@@ -1158,6 +1199,23 @@ def planes(d_src, element_size, block_size, inverse=False, out=None):
     with torch.cuda.device(t.device):
         _raise(_lib.lib().redux_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
                                            1 if inverse else 0, _stream_ptr(torch)))
+    return t
+
+
+def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
+    """The delta filter followed by the byte-plane layout (include/redux_hip.h, "delta filter") of a uint8 device tensor,
+    or their inverse: redux_delta_planes_dev on torch's current stream.  out: as for planes()."""
+    torch = _torch()
+    E = _check_element_size(element_size)
+    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
+    if block_size <= 0:
+        raise InvalidInput()
+    n = d_src.numel()
+    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
+    with torch.cuda.device(t.device):
+        _raise(_lib.lib().redux_delta_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
+                                                 1 if inverse else 0, _stream_ptr(torch)))
     return t
 
 

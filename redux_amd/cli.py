@@ -2,6 +2,7 @@
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static] [--segment-blocks G] [--checksum] [--stored]
+                            [--filter delta]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -29,12 +30,18 @@ table: `--checksum` with `--block-size 0` is a usage error.
 `--stored` (with -c and a block size, adaptive model) writes a block whose stream would not be smaller than the block as
 its raw bytes (container flag 0x40): incompressible data then costs no more than its own size plus the tables, and
 decodes as a copy.  -d reads any stored container.  `--stored` with `--block-size 0` or a static model is a usage error.
+`--filter delta` (with -c, a block size and any `--element-size`, adaptive model) codes the differences of neighbouring
+little-endian unsigned elements instead of the elements, frame by frame of the byte-plane layout (container version 6):
+for integer series whose values are large but close to their neighbours -- timestamps, sorted indices, offsets, counters,
+sampled signals.  Floating-point data and text get larger with it, so it is never chosen for you.  -d reads it from the
+container.  `--filter` with `--block-size 0`, `--stored` or a `--model` other than adaptive is a usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static|plane-static|segment-static>] [--segment-blocks <G>] [--checksum] [--stored]")
+         "[--model <adaptive|static|plane-static|segment-static>] [--segment-blocks <G>] [--checksum] [--stored] "
+         "[--filter <delta>]")
 
 
 def parse(argv):
@@ -49,7 +56,7 @@ def parse(argv):
             opts["stored"] = True
         elif arg == "-d":
             opts["compress"] = False
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter"):
             val = next(it, None)
             if val is None:
                 return None
@@ -65,6 +72,10 @@ def parse(argv):
                 if val not in ("adaptive", "static", "plane-static", "segment-static"):
                     return None
                 opts["model"] = val
+            elif arg == "--filter":
+                if val != "delta":
+                    return None
+                opts["filter"] = val
             elif arg == "--segment-blocks":
                 if not val.isdigit() or not 0 < int(val) < 1 << 32:
                     return None
@@ -94,6 +105,8 @@ def parse(argv):
         return None  # the table lives in the container (-d verifies whatever table a container has)
     if opts.get("stored") and opts["compress"] and (opts["block_size"] == 0 or opts.get("model") in ("static", "plane-static")):
         return None  # the bitmap lives in the container, and the static decoder has no table form
+    if "filter" in opts and (opts["block_size"] == 0 or opts.get("stored") or opts.get("model", "adaptive") != "adaptive"):
+        return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
     return None if opts["compress"] is None else opts
 
 
@@ -124,7 +137,7 @@ def main(argv=None):
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
-                                                opts.get("stored", False), opts.get("segment_blocks"))
+                                                opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -7,12 +7,13 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 Layout (little-endian):
     0   4  magic  b"RDXB"
     4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
-           5 = segment-static: static tables per block range)
+           5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
            the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
-           0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks
+           0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
+           0x60000000 | E with E one of 1, 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
    (version 3 only) 4*258  the static table cum[0..=257], u32
@@ -40,7 +41,13 @@ Version 5 holds streams of segment-static coding (include/redux_hip.h, "segment-
 the word at offset 12 is required: no other version's word carries it.  Tables that redux_segment_static_table_check
 rejects are InvalidInput, truncated ones Eof.  It has no stored blocks (no 0x45 / 0x55).
 
-Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14 / 0x15: versions 1 / 2 / 3 / 4 / 5 with checksums) means a table of nblocks
+Version 6 holds streams of the adaptive coder behind the delta filter for integer series (include/redux_hip.h, "delta
+filter"): the sections are version 2's, the payloads are the streams of the filtered bytes in the byte-plane layout (no
+layout for E = 1), and decoding undoes both.  The marker nibble 6 of the word at offset 12 is required: no other version's
+word carries it.  It has no stored blocks (no 0x46 / 0x56).  Without filter="delta" the writers emit exactly the bytes they
+emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14 / 0x15 / 0x16: versions 1 to 6 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -66,6 +73,8 @@ VERSION_PLANES = 2
 VERSION_STATIC = 3
 VERSION_PLANE_STATIC = 4
 VERSION_SEGMENT_STATIC = 5
+VERSION_DELTA = 6
+DELTA_MARK = 0x60000000  # version 6's word at offset 12: DELTA_MARK | E
 SEGMENT_MARK = 0x50000000  # version 5's word at offset 12: SEGMENT_MARK | k << 4 | E
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
 CRC_FLAG = 0x10  # version bit: a table of per-block CRC-32 values follows the size table
@@ -84,15 +93,17 @@ def _raw_lengths(nblocks, block_size, total):
     return np.clip(total - o, 0, block_size)
 
 
-def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None):
+def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
     params a SegmentStaticModel: streams of segment-static coding (version 5; element_size as for version 4).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
-    stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap."""
+    stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
+    filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored)."""
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
+    delta = api._check_filter(filter, not (static or plane or segment or stored is not None))
     if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1) \
             or ((plane or segment) and element_size not in (1, params.element_size)):
         raise api.InvalidInput()
@@ -111,6 +122,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
             raise api.InvalidInput()
         params.check(len(sizes))  # (the table count against this many blocks)
         ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
+    if delta:
+        ver, res = VERSION_DELTA, DELTA_MARK | element_size
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -146,14 +159,15 @@ def _version_ok(ver, res):
         or (layout == VERSION_PLANES and res in ELEMENT_SIZES) \
         or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF) \
         or (layout == VERSION_SEGMENT_STATIC and not ver & STORED_FLAG and res >> 28 == 5 and res & 0xF in (1,) + ELEMENT_SIZES
-            and res >> 4 & 0xFFFFFF >= 1)
+            and res >> 4 & 0xFFFFFF >= 1) \
+        or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
 # or the PlaneStaticModel of version 4's tables;
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
-# of 0 / 1.  static, crcs and stored are None where the container has no such section.
-_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored")
+# of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, else None.
+_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter")
 
 
 def _header(b):
@@ -168,7 +182,7 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout == VERSION_SEGMENT_STATIC else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -230,7 +244,8 @@ def _parse(buf):
         if bool((sizes[raw] != _raw_lengths(nblocks, block_size, total)[raw].astype(np.uint64)).any()):
             raise api.InvalidInput()
     payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
-    return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored)
+    return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored,
+                      "delta" if _layout(ver) == VERSION_DELTA else None)
 
 
 def unpack(buf):
@@ -256,6 +271,12 @@ def element_size(buf):
     """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for versions 2 and 4.  Malformed
     containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).element_size
+
+
+def filter(buf):
+    """"delta" for a version 6 container (the delta filter for integer series), None for versions 1 to 5.  Malformed
+    containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).filter
 
 
 def static_table(buf):
@@ -293,7 +314,7 @@ def header_is_wellformed(buf):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None):
+                   stored=False, segment_blocks=None, filter=None):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -301,7 +322,10 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     (api.plane_static_tables, default total), version 4.
     stored: blocks whose stream does not shrink them travel raw (flag 0x40, api.STORE_RATIO); not with a static model.
     model "segment-static" (element_size 1 / 2 / 4 / 8): static tables per segment_blocks blocks (a multiple of
-    64 * element_size; None: api.default_segment_blocks), built from each range as it is coded, version 5."""
+    64 * element_size; None: api.default_segment_blocks), built from each range as it is coded, version 5.
+    filter "delta" (element_size 1 / 2 / 4 / 8, model "adaptive", not stored): the delta filter for integer series in front of
+    the layout, version 6."""
+    api._check_filter(filter, model == "adaptive" and not stored)
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
             or model not in ("adaptive", "static", "plane-static", "segment-static") \
             or (model == "static" and (element_size != 1 or stored)) \
@@ -314,8 +338,8 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     m = api.StaticModel.from_data(data, params) if model == "static" \
         else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" \
         else api.SegmentStaticModel.template(params, element_size, segment_blocks) if model == "segment-static" else params
-    out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags)
-    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags)
+    out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter)
+    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter)
 
 
 def decompress_bytes(buf):
@@ -329,14 +353,14 @@ def decompress_bytes(buf):
         raise api.InvalidInput()
     got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
     segment = isinstance(c.static, api.SegmentStaticModel)
-    exact = c.element_size > 1 or c.stored is not None or segment
+    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if exact:  # (the blocks decode at their real size, into out[0 .. total))
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
-                                                       stored=c.stored)
+                                                       stored=c.stored, filter=c.filter)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes

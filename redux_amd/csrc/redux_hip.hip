@@ -12,6 +12,7 @@
 //   redux_synth.hpp    k_gen_iid / k_gen_zipf
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
+//   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist / k_*_plane_static*: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks
@@ -34,6 +35,7 @@
 #include "redux_synth.hpp"
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
+#include "redux_delta.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
 #include "redux_segment_static.hpp"
@@ -478,6 +480,20 @@ static host::EncodeCoder planes_encoder(const redux_params *p, uint32_t block_si
             }};
 }
 
+// the delta filter in front of the layout (redux_encode_delta_dev): the transformed copy for every element size, 1 included
+static host::EncodeCoder delta_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                plain.size(max_in, several, ws, bound);
+                ws += planes_copy_bytes(max_in);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_encode_delta_dev(p, s.d_in.p, len, block_size, element_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                              s.d_sum.p, ws, ws_bytes, st);
+            }};
+}
+
 // the static coder: its own workspace and bound for the largest chunk (its streams do not depend on either)
 static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
@@ -522,6 +538,45 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
             k_planes_bytes<E, true><<<grid, 256, 0, s>>>(a);
         else
             k_planes_bytes<E, false><<<grid, 256, 0, s>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// the delta filter (redux_delta.hpp): the fused kernels over the full frames when they apply, the element kernels for the rest
+template <int E>
+static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
+{
+    PlanesArgs a;
+    a.src          = (const uint8_t *)d_src;
+    a.dst          = (uint8_t *)d_dst;
+    a.block_size   = block_size;
+    a.frame_groups = block_size / 16;
+    a.len          = len;
+    a.first        = 0;
+    a.groups       = 0;
+    const uint64_t frame = (uint64_t)E * block_size, nfull = len / frame;
+    if (block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 && nfull) {
+        a.groups = nfull * a.frame_groups;
+        if (inverse) { // a workgroup per frame
+            k_delta_unplanes<E><<<(uint32_t)(nfull < (1u << 20) ? nfull : (1u << 20)), 256, 0, s>>>(a);
+        } else {
+            const uint64_t wgs = (a.groups + 255) / 256;
+            if (wgs > 0x7FFFFFFFull)
+                return REDUX_UNSUPPORTED;
+            k_delta_planes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
+        }
+        a.first = nfull * frame;
+    }
+    if (a.first < len) { // the short last frame, or everything the fused kernels cannot take
+        const uint64_t n = len - a.first;
+        if (inverse) {
+            const uint64_t nframes = (n + frame - 1) / frame;
+            k_delta_unplanes_bytes<E><<<(uint32_t)(nframes < (1u << 20) ? nframes : (1u << 20)), 256, 0, s>>>(a);
+        } else {
+            const uint64_t wgs = (n + 255) / 256;
+            k_delta_planes_bytes<E><<<(uint32_t)(wgs < 8192 ? wgs : 8192), 256, 0, s>>>(a);
+        }
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -1386,6 +1441,17 @@ static host::DecodeCoder planes_decoder(const redux_params *p, uint32_t block_si
             true};
 }
 
+// the same with the delta filter undone behind the layout (redux_decode_delta_dev)
+static host::DecodeCoder delta_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
+{
+    return {[=](uint64_t cb) { return redux_decode_delta_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_decode_delta_dev(p, s.d_in.p, s.d_off.p, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
+                                              s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            },
+            true};
+}
+
 // the static decoder takes no workspace
 static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
@@ -1955,6 +2021,114 @@ int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const u
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status)
 {
     return redux_decode_blocks_planes_crc(p, in, in_offsets, out_len, block_size, element_size, out, out_sizes, block_status, nullptr);
+}
+
+// ---- delta filter (redux_delta.hpp) ---------------------------------------------------------------
+int redux_delta_check(uint32_t element_size) { return redux_planes_check(element_size); }
+
+int redux_delta_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                           void *stream)
+{
+    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place, as redux_planes_dev)
+        return REDUX_INVALID_INPUT;
+    hipStream_t s = (hipStream_t)stream;
+    switch (element_size) {
+    case 1: return launch_delta<1>(d_src, d_dst, len, block_size, inverse != 0, s);
+    case 2: return launch_delta<2>(d_src, d_dst, len, block_size, inverse != 0, s);
+    case 4: return launch_delta<4>(d_src, d_dst, len, block_size, inverse != 0, s);
+    default: return launch_delta<8>(d_src, d_dst, len, block_size, inverse != 0, s);
+    }
+}
+
+// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
+uint64_t redux_encode_delta_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_delta_check(element_size) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    return ws ? planes_copy_bytes(in_len) + ws : 0;
+}
+
+uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+// redux_encode_planes_dev's procedure with the filter's transform
+int redux_encode_delta_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                           void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                           void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    const uint64_t copy = planes_copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *t = (uint8_t *)d_workspace;
+    if ((st = redux_delta_planes_dev(d_in, t, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+        return st;
+    return redux_encode_blocks_dev(p, t, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, t + copy,
+                                   workspace_bytes - copy, stream);
+}
+
+// redux_decode_planes_dev's procedure: the blocks decode into the plane buffer, k_planes_sizes checks their sizes, the
+// inverse writes d_out[0 .. out_len) and nothing else.  A frame's running sum never leaves the frame.
+int redux_decode_delta_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                           uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                           void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes ||
+        !d_block_status || (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
+    if (workspace_bytes < redux_decode_delta_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *t = (uint8_t *)d_workspace;
+    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
+                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr);
+    if (st != REDUX_OK)
+        return st;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
+                                                                        (int32_t *)d_summary, nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    return redux_delta_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream);
+}
+
+int redux_encode_blocks_delta(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               delta_encoder(p, block_size, element_size), block_crc); // redux_host.hpp
+}
+
+int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                              uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && redux_delta_check(element_size) != REDUX_OK)
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, delta_decoder(p, block_size, element_size), block_crc);
 }
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------

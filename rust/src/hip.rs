@@ -57,6 +57,13 @@ extern "C" {
     fn redux_decode_blocks_planes(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                   block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
                                   block_status: *mut i32) -> c_int;
+    // delta filter for integer series, in front of the byte-plane layout (block_crc may be null)
+    fn redux_encode_blocks_delta(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                 out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32,
+                                 block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_delta(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                 block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
+                                 block_status: *mut i32, block_crc: *mut u32) -> c_int;
     fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
     fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
     fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
@@ -248,6 +255,49 @@ pub fn decompress_blocks_planes(streams: &[u8], offsets: &[u64], len: u64, block
         let mut sizes = vec![0u32; nb];
         try!(status(redux_decode_blocks_planes(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size,
                                                out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks` of an integer series behind the delta filter (include/redux_hip.h, "delta filter"): `element_size` 1, 2,
+/// 4 or 8; the differences of neighbouring little-endian unsigned elements are coded, frame by frame of the byte-plane
+/// layout.  Opt-in: floating-point data and text get larger with it.
+pub fn compress_blocks_delta(data: &[u8], block_size: u32, element_size: u32, p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_delta(&cp, data.as_ptr(), data.len() as u64, block_size, element_size,
+                                              out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_delta`: `len` is the original byte count; returns the original bytes.
+pub fn decompress_blocks_delta(streams: &[u8], offsets: &[u64], len: u64, block_size: u32, element_size: u32,
+                               p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_delta(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size,
+                                              out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
