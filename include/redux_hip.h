@@ -671,6 +671,11 @@ const char *redux_encode_kernel_name_ws(const redux_params *p, const void *d_in,
  * nblocks = blocks (or table entries) of the launch; 0 = a grid that fills the chip, which is what
  * redux_decode_kernel_name answers for. */
 const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out, uint32_t block_size, uint64_t nblocks);
+/* The decoder of a launch that is given a block table (redux_decode_blocks_v_dev; redux_decode_stored_dev, whose table has
+ * one entry per block, so nentries = redux_block_count(out_len, block_size)): the cell decoder k_decode_cells<8> takes
+ * blocks in order and has no table form, so blocks above 64 KiB in launches too big for k_decode_wave run k_decode<false,
+ * true>.  "" for arguments the table form rejects (symbol_bits != 8 or code_bits > 32: UNSUPPORTED) and for nentries == 0. */
+const char *redux_decode_kernel_name_table(const redux_params *p, uint32_t block_size, uint64_t nentries);
 /* The same for redux_static_encode_blocks_dev / redux_static_decode_blocks_dev: the choice depends on the table total
  * (>= 2^17: quotient fix-up; <= 2^16: lookup-table decoder; between: lock-step decoder), on code_bits (32 or less) and on
  * whether the launch has at most one wave (64 blocks) per SIMD of HIP's current device.  Alignment is decided inside

@@ -32,6 +32,7 @@ SIGNATURES = {
     "redux_encode_kernel_name_ws": (C.c_char_p, [_PP, _V, _U64, _U32, _U64]),
     "redux_decode_kernel_name": (C.c_char_p, [_PP, _V, _U32]),
     "redux_decode_kernel_name_n": (C.c_char_p, [_PP, _V, _U32, _U64]),
+    "redux_decode_kernel_name_table": (C.c_char_p, [_PP, _U32, _U64]),
     "redux_static_encode_kernel_name": (C.c_char_p, [_PP, C.POINTER(_U32), _U64, _U32]),
     "redux_static_decode_kernel_name": (C.c_char_p, [_PP, C.POINTER(_U32), _U64]),
     "redux_debug_rcp_check": (C.c_int, [_U64, _U64, C.POINTER(C.c_double)]),

@@ -413,8 +413,12 @@ static EncKernel pick_encode_kernel(const Geometry &g, const redux_params *p, bo
     return g.u16 ? EncKernel::SingleU16 : EncKernel::SingleU32;
 }
 
-// nslots: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice)
-static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, uint64_t nslots = 0, uint32_t block_size = 0, bool table = false)
+// a decoder's geometry: no small-grid encoder, whose windows would size the reciprocal table
+static Geometry decode_geometry(const redux_params *p, uint32_t block_size) { return geometry(p, block_size, block_size, false, false); }
+
+// nslots: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice).  The one
+// call decode_blocks_dev_impl, redux_decode_kernel_name_n and redux_decode_kernel_name_table make.
+static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, uint64_t nslots, uint32_t block_size, bool table)
 {
     if (g.gen) {
         if (gen_needs_fixup(p, block_size))
@@ -677,13 +681,9 @@ const char *redux_decode_kernel_name(const redux_params *p, const void *d_out, u
     return redux_decode_kernel_name_n(p, d_out, block_size, 0);
 }
 
-const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out, uint32_t block_size, uint64_t nblocks)
+static const char *decode_kernel_name_of(DecKernel k, const redux_params *p)
 {
-    if (check_params(p) != REDUX_OK || block_size == 0)
-        return "";
-    (void)d_out; // every decoder takes any alignment (it only picks the store width inside the kernel)
-    const Geometry g = geometry(p, block_size, block_size, false, false); // (a decoder: no small-grid encoder, whose windows would size the reciprocal table)
-    switch (pick_decode_kernel(g, p, nblocks, block_size)) {
+    switch (k) {
     case DecKernel::LockCb32: return "k_decode_lock<true> (u16 tree, one wave per 64 blocks, code_bits 32)";
     case DecKernel::Lock: return "k_decode_lock<false> (u16 tree, one wave per 64 blocks)";
     case DecKernel::GenericU16: return "k_decode<true, false> (u16 tree, per-lane control flow)";
@@ -714,6 +714,25 @@ const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out,
     case DecKernel::WaveFixup: return "k_decode_wave (one block per wave, cumulative table across the lanes; fix-up: count past 2^17)";
     }
     return "";
+}
+
+const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out, uint32_t block_size, uint64_t nblocks)
+{
+    if (check_params(p) != REDUX_OK || block_size == 0)
+        return "";
+    (void)d_out; // every decoder takes any alignment (it only picks the store width inside the kernel)
+    return decode_kernel_name_of(pick_decode_kernel(decode_geometry(p, block_size), p, nblocks, block_size, false), p);
+}
+
+// the launch given a block table (decode_blocks_dev_impl with d_table: the `_v` calls, redux_decode_stored_dev)
+const char *redux_decode_kernel_name_table(const redux_params *p, uint32_t block_size, uint64_t nentries)
+{
+    if (check_params(p) != REDUX_OK || block_size == 0 || nentries == 0)
+        return "";
+    const Geometry g = decode_geometry(p, block_size);
+    if (g.gen || g.any) // (decode_blocks_dev_impl: UNSUPPORTED with a table)
+        return "";
+    return decode_kernel_name_of(pick_decode_kernel(g, p, nentries, block_size, true), p);
 }
 
 int redux_params_check(uint32_t symbol, uint32_t frequency, uint32_t code) /* model/mod.rs:64 */
@@ -1162,7 +1181,7 @@ uint64_t redux_decode_workspace_bytes(const redux_params *p, uint64_t nblocks, u
 {
     if (check_params(p) != REDUX_OK || block_size == 0)
         return 0;
-    const Geometry g = geometry(p, block_size, block_size, false, false); // (a decoder: no small-grid encoder, whose windows would size the reciprocal table)
+    const Geometry g = decode_geometry(p, block_size);
     if (g.gen) // (11- and 12-bit symbols: the bottom cells of the decoder's tree live in the workspace: gen_decode_in_workspace)
         return align_up((uint64_t)g.rc_n * 8, 256) +
                (gen_decode_cells(p, block_size) && gen_decode_in_workspace(p, nblocks) ? (nblocks + 63) / 64 * 64 * gen_decode_tree_bytes(p) : 0);
@@ -1192,11 +1211,12 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
         return REDUX_OK;
     if (!d_table && out_cap < nblocks * (uint64_t)block_size)
         return REDUX_OUTPUT_TOO_SMALL;
-    const Geometry g = geometry(p, block_size, block_size, false, false); // (a decoder: no small-grid encoder, whose windows would size the reciprocal table)
+    const Geometry g = decode_geometry(p, block_size);
     if (workspace_bytes < redux_decode_workspace_bytes(p, nblocks, block_size))
         return REDUX_OUTPUT_TOO_SMALL;
     if (d_table && (g.gen || g.any))
         return REDUX_UNSUPPORTED;
+    const DecKernel kernel = pick_decode_kernel(g, p, nblocks, block_size, d_table != nullptr);
     hipStream_t s = (hipStream_t)stream;
     if (g.gen) {
         GenDecArgs ga;
@@ -1214,7 +1234,7 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
         ga.code_bits  = p->code_bits;
         k_fill_rc_from<<<(g.rc_n + 255) / 256, 256, 0, s>>>((double *)d_workspace, g.rc_n, (1u << p->symbol_bits) + 1u);
         const uint32_t grid64 = (uint32_t)((nblocks + 63) / 64);
-        switch (pick_decode_kernel(g, p, nblocks, block_size)) {
+        switch (kernel) {
         case DecKernel::CellsFixup:
             switch (p->symbol_bits) {
 #define REDUX_GEN_DEC(SB) case SB: k_decode_cells<SB, 64, false, true><<<grid64, 64, 0, s>>>(ga); break;
@@ -1268,7 +1288,7 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
         HIP_TRY(hipGetLastError());
         return REDUX_OK;
     }
-    if (cells8_takes(p, block_size, nblocks, d_table != nullptr)) {
+    if (kernel == DecKernel::Cells8 || kernel == DecKernel::Cells8Fixup) {
         GenDecArgs ga;
         ga.in         = (const uint8_t *)d_in;
         ga.in_offsets = (const uint64_t *)d_in_offsets;
@@ -1285,7 +1305,7 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
         const uint32_t rc8 = cells8_rc_entries(p, block_size);
         k_fill_rc<<<(rc8 + 255) / 256, 256, 0, s>>>((double *)d_workspace, rc8);
         const uint32_t grid64 = (uint32_t)((nblocks + 63) / 64);
-        if (cells8_needs_fixup(p, block_size))
+        if (kernel == DecKernel::Cells8Fixup)
             k_decode_cells<8, 64, false, true><<<grid64, 64, 0, s>>>(ga);
         else
             k_decode_cells<8, 64, false, false><<<grid64, 64, 0, s>>>(ga);
@@ -1336,7 +1356,7 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
     a.table      = d_table;
     a.rc_n       = rc_n - 32; // (the last 32 entries are slack for the lock-step decoder's look-ahead)
     const uint32_t grid = (uint32_t)((nblocks + 63) / 64);
-    switch (pick_decode_kernel(g, p, nblocks)) {
+    switch (kernel) {
     case DecKernel::Wave: k_decode_wave<false><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
     case DecKernel::WaveFixup: k_decode_wave<true><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
     case DecKernel::LockCb32: k_decode_lock<true><<<grid, 64, 0, s>>>(a); break;

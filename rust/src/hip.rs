@@ -133,6 +133,8 @@ extern "C" {
     #[allow(dead_code)] // declared for harnesses that print the kernel next to a timing; no wrapper here
     fn redux_encode_kernel_name_ws(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32,
                                    workspace_bytes: u64) -> *const c_char;
+    #[allow(dead_code)] // the same for the decoder a stored launch runs (the table form)
+    fn redux_decode_kernel_name_table(p: *const ReduxParams, block_size: u32, nentries: u64) -> *const c_char;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
