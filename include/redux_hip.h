@@ -648,6 +648,73 @@ int      redux_segment_static_decode_blocks_crc(const redux_params *p, const uin
                                                 uint32_t element_size, uint32_t segment_blocks, uint8_t *out, uint32_t *out_sizes,
                                                 int32_t *block_status, uint32_t *block_crc);
 
+/* ---- context-static coding: a static table per preceding byte ----------------------------------------
+ * The static models above code a byte under a distribution that ignores the byte before it.  Here the table depends on the
+ * previous byte (an order-1 model): on text, logs and source code that is worth 20 % and more from about half a megabyte
+ * upward; below that the 256 tables cost more than they save.  Strictly opt-in.  8-bit symbols and code_bits <= 32;
+ * everything else is UNSUPPORTED.  B = block_size.
+ * The rule:
+ *   1. The context of byte i of a block is byte i-1 of the same block; the first byte of every block has context 0.  The EOF
+ *      symbol is coded under the context of the block's last byte (0 for an empty block).  Blocks stay independent.
+ *   2. counts[c][s], u64[256][256]: over all blocks, the number of bytes s whose context is c.  The pair across a block
+ *      boundary is not counted; each block's first byte counts under c = 0.
+ *   3. Table c is redux_static_table_from_counts(counts[c], total), unchanged, but for a context that owns no bytes: that one
+ *      is given a count of one for every byte value before the rule is applied.  EVERY table therefore has the same total,
+ *      and one reciprocal serves a launch.  (Plane-static's all-ones, total-257 table would not do: a caller may code data
+ *      under tables built from other data, and any context can then occur.)
+ *   4. total <= 2^16 and <= freq_max; a larger total is UNSUPPORTED, a smaller one than 257 INVALID_INPUT as for every static
+ *      table.  So every cum[1..256] fits 16 bits, 256 tables are exactly 128 KiB on the device, and the coder's quotient
+ *      needs no fix-up.
+ *   5. Block b's stream is what Codec::compress_stream writes with a model whose get_frequency(s) answers from table ctx and
+ *      then sets ctx = s; decode is the mirror through get_symbol.
+ *   6. Tables are u32[256][258], table c at cum + 258 c, each in the format of every other static call.
+ * On the device the tables are read from device memory (d_cum).  Every coder launch first checks them (strictly increasing
+ * from 0 to `total`, all 256): if one fails, every block is INVALID_INPUT and nothing else is written.
+ * Not available for the `_v` calls, redux_compress / redux_decompress, layouts, filters and stored blocks.
+ *
+ * redux_context_static_table_check        all 256 tables pass redux_static_table_check, and their totals are equal and <= 2^16.
+ * redux_context_static_total              the total of checked tables (cum[257]).
+ * redux_context_static_tables_from_counts rules 3 and 4 on the host from u64[256][256] counts.
+ * redux_context_histogram_dev             ADDS the pair counts of d_in[0 .. in_len), cut into blocks of block_size from its
+ *                                         start, to d_counts (u64[256][256]).  Any block size and alignment; a buffer can be
+ *                                         counted in pieces that are whole blocks.
+ * redux_context_static_tables_dev         rule 3 on the device, one launch for all 256: d_counts -> d_cum (u32[256][258]).
+ * redux_context_static_tables             host pointers: chunks of whole blocks are staged through the pinned ring on the
+ *                                         current device (as redux_static_table) and counted there.
+ * redux_context_static_encode_dev         device pointers, the procedure of redux_static_encode_blocks_dev /
+ * redux_context_static_decode_dev         redux_static_decode_blocks_dev (block b decodes to d_out + b*block_size; the summary
+ *                                         last; nothing outside the output is written) with the tables in device memory and a
+ *                                         workspace (256-byte aligned) that holds their checked image.
+ * redux_context_static_encode_blocks_crc  host pointers through the chunk pipeline (fleet included), one set of tables per
+ * redux_context_static_decode_blocks_crc  call, block_crc nullable.  Streams depend on neither the chunk size nor the devices. */
+int      redux_context_static_table_check(const redux_params *p, const uint32_t *cum /* u32[256][258] */);
+uint32_t redux_context_static_total(const uint32_t *cum);
+int      redux_context_static_tables_from_counts(const redux_params *p, const uint64_t *counts /* u64[256][256] */, uint32_t total,
+                                                 uint32_t *cum);
+int      redux_context_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size,
+                                     void *d_counts /* u64[256][256], ADDED to */, void *stream);
+int      redux_context_static_tables_dev(const redux_params *p, const void *d_counts, uint32_t total, void *d_cum /* u32[256][258] */,
+                                         void *stream);
+int      redux_context_static_tables(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t total,
+                                     uint32_t *cum);
+uint64_t redux_context_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size);
+uint64_t redux_context_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size);
+uint64_t redux_context_static_decode_workspace_bytes(const redux_params *p, uint64_t nblocks, uint32_t block_size);
+int      redux_context_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                         uint32_t block_size, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                                         void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */, void *d_workspace,
+                                         uint64_t workspace_bytes, void *stream);
+int      redux_context_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in,
+                                         const void *d_in_offsets /* u64[nblocks+1] */, uint64_t nblocks, uint32_t block_size,
+                                         void *d_out, uint64_t out_cap, void *d_out_sizes /* u32[nblocks] */, void *d_block_status,
+                                         void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int      redux_context_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                                uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                                int32_t *block_status, uint32_t *block_crc);
+int      redux_context_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in,
+                                                const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
+                                                uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

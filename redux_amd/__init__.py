@@ -11,5 +11,6 @@ from .api import (  # noqa: F401
     host_set_devices, host_chunk_plan, host_set_chunk_bytes,
     DeviceEncoder, DeviceDecoder, DeviceStaticCoder, DevicePlaneStaticCoder, planes, delta_planes, gen_iid, gen_zipf, zipf_thresholds, version,
     crc32_blocks, crc32_combine, STORE_RATIO,
+    ContextStaticModel, context_static_tables, context_static_tables_from_counts, DeviceContextStaticCoder,
     SegmentStaticModel, segment_static_tables, segment_static_tables_from_counts, default_segment_blocks, DeviceSegmentStaticCoder,
 )

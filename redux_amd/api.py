@@ -169,6 +169,35 @@ class PlaneStaticModel:
 SEGMENT_K0 = 4  # default segment: G = 64 * E * SEGMENT_K0 blocks
 
 
+class ContextStaticModel:
+    """Context-static coding (include/redux_hip.h, "context-static coding"): Parameters plus one static table per preceding
+    byte, cums of shape (256, 258), all of one total <= 2^16; a byte is coded under the table of the byte before it in
+    its block (0 at a block's start).  ContextStaticModel.from_data builds the tables from the data.  compress_blocks and
+    decompress_blocks take it where they take Parameters: element size 1, no filter, no stored blocks."""
+
+    def __init__(self, params, cums):
+        self.params = _params_of(params)
+        c = np.ascontiguousarray(cums, dtype=np.int64)
+        if c.shape != (256, 258) or (c < 0).any() or (c > 0xFFFFFFFF).any():
+            raise InvalidInput()
+        self.cums = c.astype(np.uint32)
+        cp = self.params._c()
+        _raise(_lib.lib().redux_context_static_table_check(C.byref(cp), self.cums.ctypes.data))
+
+    @classmethod
+    def from_data(cls, data, block_size, params=(8, 30, 32), total=None):
+        return cls(params, context_static_tables(data, block_size, params, total))
+
+    def parameters(self):
+        return self.params
+
+    def total(self):
+        return int(self.cums[0, -1])
+
+    def _cum_ptr(self):
+        return self.cums.ctypes.data
+
+
 def default_segment_blocks(element_size):
     """The segment length used when none is given: 64 * E * 4 blocks."""
     return 64 * int(element_size) * SEGMENT_K0
@@ -234,13 +263,20 @@ class SegmentStaticModel:
 
 
 def _params_of(model_or_params):
-    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel, PlaneStaticModel, SegmentStaticModel)):
+    if isinstance(model_or_params, (AdaptiveTreeModel, StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)):
         return model_or_params.params
     if isinstance(model_or_params, Parameters):
         return model_or_params
     if isinstance(model_or_params, (tuple, list)):
         return Parameters(*model_or_params)
     raise TypeError("expected Parameters, AdaptiveTreeModel or a (symbol, frequency, code) triple")
+
+
+def _adaptive_only(model_or_params):
+    """the `_v` calls and compress / decompress code under the adaptive model: a ContextStaticModel there is InvalidInput
+    (its tables would be ignored), before the library is touched"""
+    if isinstance(model_or_params, ContextStaticModel):
+        raise InvalidInput()
 
 
 MAX_BLOCK_BYTES = 0xFFFFFF00  # largest single block / whole stream the C ABI takes (redux_compress)
@@ -311,6 +347,55 @@ def static_table(data, params=(8, 30, 32), total=None):
     if not cum.any():  # the kernel's mark for N * R >= 2^64
         raise Unsupported()
     return cum
+
+
+def context_static_tables_from_counts(counts, params=(8, 30, 32), total=None):
+    """redux_context_static_tables_from_counts: the rule (include/redux_hip.h, "context-static coding") on u64[256][256]
+    pair counts, on the host.  Returns np.uint32[256, 258]."""
+    P = _params_of(params)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.shape != (256, 256):
+        raise InvalidInput()
+    cums = np.zeros((256, 258), dtype=np.uint32)
+    cp = P._c()
+    _raise(_lib.lib().redux_context_static_tables_from_counts(C.byref(cp), c.ctypes.data, _total_of(P, total), cums.ctypes.data))
+    return cums
+
+
+def context_static_tables(data, block_size, params=(8, 30, 32), total=None):
+    """The tables of context-static coding for `data` cut into blocks of block_size: np.uint32[256, 258].  Host data goes
+    through redux_context_static_tables; a torch uint8 device tensor is counted where it lies
+    (redux_context_histogram_dev, redux_context_static_tables_dev, one read-back)."""
+    P = _params_of(params)
+    T = _total_of(P, total)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    cp = P._c()
+    L = _lib.lib()
+    if not _is_device_tensor(data):
+        a = _u8(data)
+        cums = np.zeros((256, 258), dtype=np.uint32)
+        _raise(L.redux_context_static_tables(C.byref(cp), _ptr(a), len(a), int(block_size), T, cums.ctypes.data))
+        return cums
+    torch = _torch()
+    with torch.cuda.device(data.device):
+        d_cum = _device_context_tables(torch, L, cp, data, int(block_size), T)
+        cums = d_cum.cpu().numpy().view(np.uint32).reshape(256, 258).copy()
+    if not cums.any(axis=1).all():  # the kernel's mark for N * R >= 2^64
+        raise Unsupported()
+    return cums
+
+
+def _device_context_tables(torch, L, cp, d_in, block_size, total):
+    """a uint8 device tensor -> its 256 tables as an int32[256 * 258] device tensor"""
+    assert d_in.dtype == torch.uint8 and d_in.is_contiguous()
+    counts = torch.zeros(256 * 256, dtype=torch.int64, device=d_in.device)
+    d_cum = torch.zeros(256 * 258, dtype=torch.int32, device=d_in.device)
+    s = _stream_ptr(torch)
+    _raise(L.redux_context_histogram_dev(C.c_void_p(d_in.data_ptr()) if d_in.numel() else None, d_in.numel(), block_size,
+                                         C.c_void_p(counts.data_ptr()), s))
+    _raise(L.redux_context_static_tables_dev(C.byref(cp), C.c_void_p(counts.data_ptr()), total, C.c_void_p(d_cum.data_ptr()), s))
+    return d_cum
 
 
 def plane_static_tables(data, element_size, block_size, params=(8, 30, 32), total=None):
@@ -452,6 +537,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
     layout"): the streams are those of the transformed bytes, which decompress_blocks(..., element_size, length) undoes.
     params may be a StaticModel: the blocks are then coded under its table (redux_static_encode_blocks_crc); no element_size.
+    params may be a ContextStaticModel: every byte is coded under the table of the byte before it
+    (redux_context_static_encode_blocks_crc); no element_size, no stored=, no filter.
     params may be a PlaneStaticModel: the layout of the model's element size, block b under table b mod E
     (redux_plane_static_encode_blocks_crc); element_size must be 1 (the default: the model's is used) or the model's.
     params may be a SegmentStaticModel (redux_segment_static_encode_blocks_crc): its tables are built from `data` as it is
@@ -466,6 +553,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     Adaptive model only, and not with stored=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
+    context = isinstance(params, ContextStaticModel)
+    static = static or context  # (the same checks: element size 1, no stored blocks, no filter)
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     plane = plane or segment  # (the checks of a model that brings its own element size)
     P = _params_of(params)
@@ -501,6 +590,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
+    elif context:
+        st = L.redux_context_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
+                                                      cap, offs.ctypes.data, status.ctypes.data, crc)
     elif static:
         st = L.redux_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size, out.ctypes.data,
                                               cap, offs.ctypes.data, status.ctypes.data, crc)
@@ -533,6 +625,7 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     required, there must be redux_block_count(length, block_size) streams, and out is the original bytes, uint8[length]
     (frames with a damaged block hold undefined bytes; their blocks' status says which).
     params may be a StaticModel: the streams are then decoded under its table (redux_static_decode_blocks_crc).
+    params may be a ContextStaticModel (redux_context_static_decode_blocks_crc): as a StaticModel.
     params may be a PlaneStaticModel (redux_plane_static_decode_blocks_crc): length is required, element_size is 1 (the
     model's is used) or the model's, and out is the original bytes as with element_size > 1.
     params may be a SegmentStaticModel (redux_segment_static_decode_blocks_crc): as a PlaneStaticModel; its tables must be
@@ -545,6 +638,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
+    context = isinstance(params, ContextStaticModel)
+    static = static or context
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     if delta and length is None:
         raise InvalidInput()
@@ -581,6 +676,9 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
+    elif context:
+        st = L.redux_context_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
+                                                      out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data, crc)
     elif static:
         st = L.redux_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, nb, block_size,
                                               out.ctypes.data, out.size, sizes.ctypes.data, status.ctypes.data, crc)
@@ -640,6 +738,7 @@ def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None):
     them; each input is cut into blocks on its own.  Returns (dense streams uint8, offsets
     uint64[nblocks+1], status int32[nblocks], first_block int64[len(inputs)+1]): input i owns blocks
     first_block[i] .. first_block[i+1]-1.  filter: None (the `_v` calls have no delta filter: "delta" is InvalidInput)."""
+    _adaptive_only(params)
     _check_filter(filter, False)
     P = _params_of(params)
     L = _lib.lib()
@@ -668,6 +767,7 @@ def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None):
 def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32), check=True, filter=None):
     """The inverse of compress_blocks_v: `lengths[i]` is the decoded size of input i.  Returns (list of
     uint8 arrays, sizes uint32[nblocks], status int32[nblocks]).  filter: None ("delta" is InvalidInput)."""
+    _adaptive_only(params)
     _check_filter(filter, False)
     P = _params_of(params)
     L = _lib.lib()
@@ -698,6 +798,7 @@ def compress(istream, ostream, model, filter=None):
     """redux::compress(istream, ostream, model) -> (bytes_in, bytes_out).  The whole input is
     one block, so the stream equals the reference's; it is coded by one GPU lane.  filter: None (a raw reference stream
     has no delta filter: "delta" is InvalidInput)."""
+    _adaptive_only(model)
     _check_filter(filter, False)
     P = _params_of(model)
     a = _u8(istream.read())
@@ -714,6 +815,7 @@ def compress(istream, ostream, model, filter=None):
 
 def decompress(istream, ostream, model, max_output=None, filter=None):
     """redux::decompress(istream, ostream, model) -> (bytes_in, bytes_out).  filter: None ("delta" is InvalidInput)."""
+    _adaptive_only(model)
     _check_filter(filter, False)
     P = _params_of(model)
     a = _u8(istream.read())
@@ -984,6 +1086,90 @@ class DeviceStaticCoder:
             C.c_void_p(self.dec_summary.data_ptr()), _stream_ptr(torch))
         _raise(st)
         return self.dec_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+
+
+class DeviceContextStaticCoder:
+    """Context-static coding on device tensors (include/redux_hip.h, "context-static coding"): d_cum, an int32[256 * 258]
+    device tensor of 256 tables with the common total `total`, stays on the device; every call checks it there."""
+
+    def __init__(self, params, d_cum, total, block_size, max_in_len):
+        torch = _torch()
+        self.P = _params_of(params)
+        self.cp = self.P._c()
+        L = _lib.lib()
+        assert d_cum.is_cuda and d_cum.dtype == torch.int32 and d_cum.is_contiguous() and d_cum.numel() == 256 * 258
+        self.d_cum = d_cum
+        self.total = int(total)
+        self.block_size = int(block_size)
+        self.max_in_len = int(max_in_len)
+        self.device = d_cum.device
+        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
+        self.ws_bytes = max(L.redux_context_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size),
+                            L.redux_context_static_decode_workspace_bytes(C.byref(self.cp), self.nblocks_max, self.block_size))
+        if self.ws_bytes == 0:
+            raise InvalidInput()
+        self.out_cap = L.redux_context_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
+        self.out = torch.empty(max(self.out_cap, 1), dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.dec_out = None
+
+    @classmethod
+    def from_data(cls, d_in, params, block_size, max_in_len, total=None):
+        """A coder whose tables are built from d_in (a uint8 device tensor) on the device; nothing is read back."""
+        torch = _torch()
+        P = _params_of(params)
+        T = _total_of(P, total)
+        with torch.cuda.device(d_in.device):
+            d_cum = _device_context_tables(torch, _lib.lib(), P._c(), d_in, int(block_size), T)
+        return cls(P, d_cum, T, block_size, max_in_len)
+
+    def tables(self):
+        """the tables on the host: np.uint32[256, 258]"""
+        return self.d_cum.cpu().numpy().view(np.uint32).reshape(256, 258).copy()
+
+    def _ws_ptr(self):
+        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
+
+    @_on_device
+    def encode(self, d_in):
+        torch = _torch()
+        n = d_in.numel()
+        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        self.summary.zero_()
+        st = _lib.lib().redux_context_static_encode_dev(
+            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_in.data_ptr()) if n else None, n,
+            self.block_size, C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
+            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+            _stream_ptr(torch))
+        _raise(st)
+        nb = _lib.lib().redux_block_count(n, self.block_size)
+        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+
+    @_on_device
+    def decode(self, d_streams, d_offsets, out=None):
+        """-> (out uint8[nblocks * block_size], sizes, status, summary); block b occupies out[b * block_size:][:sizes[b]].
+        out: a uint8 device tensor of at least nblocks * block_size bytes to decode into (default: the coder's own)."""
+        torch = _torch()
+        nb = d_offsets.numel() - 1
+        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= nb <= self.nblocks_max
+        if self.dec_out is None:
+            self.dec_out = torch.empty(max(self.nblocks_max * self.block_size, 1), dtype=torch.uint8, device=self.device)
+            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        d_out = self.dec_out if out is None else out
+        assert d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= nb * self.block_size
+        self.dec_summary.zero_()
+        st = _lib.lib().redux_context_static_decode_dev(
+            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
+            C.c_void_p(d_offsets.data_ptr()), nb, self.block_size, C.c_void_p(d_out.data_ptr()), nb * self.block_size,
+            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
+            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
+        _raise(st)
+        return d_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
 
 
 class DevicePlaneStaticCoder:

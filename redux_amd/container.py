@@ -7,18 +7,21 @@ for one so that blocked output can be decoded again.  Every payload stays byte-i
 Layout (little-endian):
     0   4  magic  b"RDXB"
     4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
-           5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout)
+           5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
+           7 = context-static: a static table per preceding byte)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
            the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
-           0x60000000 | E with E one of 1, 2, 4, 8
+           0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000
    16   8  nblocks
    24   8  total uncompressed length
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
+   (version 7 only) 4  the tables' total; 32  presence mask, bit c % 8 of byte c // 8 (LSB first) = table c is recorded;
+           then for each recorded table, in order of c, 256 u16 frequencies of the byte values (EOF = 1 is implied)
    ..  4*nblocks   compressed size of each block
    (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
    (flag 0x40 only) ceil(nblocks/8)  stored-block bitmap: bit b % 8 of byte b // 8 (LSB first) = block b is stored
@@ -47,7 +50,14 @@ layout for E = 1), and decoding undoes both.  The marker nibble 6 of the word at
 word carries it.  It has no stored blocks (no 0x46 / 0x56).  Without filter="delta" the writers emit exactly the bytes they
 emitted before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 / 0x12 / 0x13 / 0x14 / 0x15 / 0x16: versions 1 to 6 with checksums) means a table of nblocks
+Version 7 holds streams of context-static coding (include/redux_hip.h, "context-static coding"): element size 1, a byte
+coded under the table of the byte before it in its block.  The sections are version 3's with the table section in the
+compact form above: a table equal to the one the rule gives a context without bytes (a count of one for every byte value)
+is not recorded, and reading rebuilds it, so text pays for its 60 to 100 contexts and not for 256.  A total outside
+257 .. min(2^16, freq_max), a frequency of 0, a row that does not sum to total - 1 and a section that ends early are
+InvalidInput.  The marker nibble 7 of the word at offset 12 is required.  It has no stored blocks (no 0x47 / 0x57).
+
+Bit 0x10 of the version byte (versions 0x11 to 0x17: versions 1 to 7 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -74,6 +84,8 @@ VERSION_STATIC = 3
 VERSION_PLANE_STATIC = 4
 VERSION_SEGMENT_STATIC = 5
 VERSION_DELTA = 6
+VERSION_CONTEXT_STATIC = 7
+CONTEXT_MARK = 0x70000000  # version 7's word at offset 12
 DELTA_MARK = 0x60000000  # version 6's word at offset 12: DELTA_MARK | E
 SEGMENT_MARK = 0x50000000  # version 5's word at offset 12: SEGMENT_MARK | k << 4 | E
 TABLE = 258 * 4  # version 3: cum[0..=257] as u32 after the header
@@ -98,13 +110,16 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
     params a SegmentStaticModel: streams of segment-static coding (version 5; element_size as for version 4).
+    params a ContextStaticModel: streams of context-static coding (version 7, element size 1; tables equal to the rule's
+    substitute for a context without bytes are dropped).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
     filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored)."""
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
-    delta = api._check_filter(filter, not (static or plane or segment or stored is not None))
-    if element_size not in (1,) + ELEMENT_SIZES or (static and element_size != 1) \
+    context = isinstance(params, api.ContextStaticModel)
+    delta = api._check_filter(filter, not (static or plane or segment or context or stored is not None))
+    if element_size not in (1,) + ELEMENT_SIZES or ((static or context) and element_size != 1) \
             or ((plane or segment) and element_size not in (1, params.element_size)):
         raise api.InvalidInput()
     if plane or segment:
@@ -124,6 +139,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
     if delta:
         ver, res = VERSION_DELTA, DELTA_MARK | element_size
+    if context:
+        ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -134,7 +151,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     bitmap = b""
     if stored is not None:
         f = np.asarray(stored)
-        if static or plane or segment or f.shape != (len(sizes),) or bool((f > 1).any()) \
+        if static or plane or segment or context or f.shape != (len(sizes),) or bool((f > 1).any()) \
                 or bool((sizes[f == 1] != _raw_lengths(len(sizes), block_size, total_len)[f == 1]).any()):
             raise api.InvalidInput()
         ver |= STORED_FLAG
@@ -144,7 +161,49 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         head += params.cum.astype("<u4").tobytes()
     if plane or segment:
         head += params.cums.astype("<u4").tobytes()
+    if context:
+        head += _pack_context_tables(params.cums)
     return head + sizes.astype("<u4").tobytes() + crc + bitmap + np.asarray(streams, dtype=np.uint8)[: int(offs[-1])].tobytes()
+
+
+def _substitute_freqs(total):
+    """the 256 byte frequencies of the table a context without bytes gets (include/redux_hip.h, "context-static coding",
+    rule 3): the semi-static rule on a count of one for every byte value"""
+    f = np.full(256, 1 + (total - 257) // 256, dtype=np.int64)
+    f[: total - 1 - int(f.sum())] += 1
+    return f
+
+
+def _pack_context_tables(cums):
+    """version 7's table section of np.uint32[256, 258] tables"""
+    c = np.asarray(cums, dtype=np.int64)
+    total = int(c[0, 257])
+    freqs = np.diff(c[:, :257], axis=1)  # [256, 256]: the byte values' frequencies (all <= 65,535: the total is <= 2^16)
+    present = (freqs != _substitute_freqs(total)).any(axis=1)
+    return struct.pack("<I", total) + np.packbits(present, bitorder="little").tobytes() + freqs[present].astype("<u2").tobytes()
+
+
+def _unpack_context_tables(b, at, P):
+    """(np.uint32[256, 258], where the next section begins) of version 7's table section at b[at:]; InvalidInput for
+    anything the rule cannot have written"""
+    try:
+        (total,), at = _take(b, at, "<u4", 1)
+        mask, at = _take(b, at, np.uint8, 32)
+        total = int(total)
+        if not 257 <= total <= min(1 << 16, P.freq_max):
+            raise api.InvalidInput()
+        present = np.unpackbits(mask, bitorder="little").astype(bool)
+        rows, at = _take(b, at, "<u2", 256 * int(present.sum()))
+    except api.Eof:
+        raise api.InvalidInput()
+    freqs = np.tile(_substitute_freqs(total), (256, 1))
+    freqs[present] = rows.reshape(-1, 256)
+    if bool((freqs == 0).any()) or bool((freqs.sum(axis=1) != total - 1).any()):
+        raise api.InvalidInput()
+    cums = np.zeros((256, 258), dtype=np.int64)
+    cums[:, 1:257] = np.cumsum(freqs, axis=1)
+    cums[:, 257] = total
+    return cums.astype(np.uint32), at
 
 
 def _layout(ver):
@@ -160,7 +219,8 @@ def _version_ok(ver, res):
         or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF) \
         or (layout == VERSION_SEGMENT_STATIC and not ver & STORED_FLAG and res >> 28 == 5 and res & 0xF in (1,) + ELEMENT_SIZES
             and res >> 4 & 0xFFFFFF >= 1) \
-        or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
+        or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
+        or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
@@ -226,6 +286,12 @@ def _parse(buf):
             static = api.SegmentStaticModel(P, cums.reshape(E * nseg, 258), E, G)
             static.check(nblocks)
         except api.Error:  # (redux_segment_static_table_check)
+            raise api.InvalidInput()
+    if _layout(ver) == VERSION_CONTEXT_STATIC:
+        cums, at = _unpack_context_tables(b, at, P)
+        try:
+            static = api.ContextStaticModel(P, cums)
+        except api.Error:  # (redux_context_static_table_check: parameters the static coder does not take)
             raise api.InvalidInput()
     sizes, at = _take(b, at, "<u4", nblocks)
     sizes = sizes.astype(np.uint64)
@@ -293,6 +359,13 @@ def plane_static_tables(buf):
     return static.cums if isinstance(static, api.PlaneStaticModel) else None
 
 
+def context_static_tables(buf):
+    """The tables (np.uint32[256, 258]) a version 7 container records, the dropped ones rebuilt; None for versions 1 to 6.
+    Malformed containers raise InvalidInput, truncated ones Eof."""
+    static = _parse(buf).static
+    return static.cums if isinstance(static, api.ContextStaticModel) else None
+
+
 def segment_static_tables(buf):
     """(tables np.uint32[nseg * E, 258], segment_blocks) of a version 5 container; None for versions 1 to 4.  Malformed
     containers raise InvalidInput, truncated ones Eof."""
@@ -324,11 +397,14 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     model "segment-static" (element_size 1 / 2 / 4 / 8): static tables per segment_blocks blocks (a multiple of
     64 * element_size; None: api.default_segment_blocks), built from each range as it is coded, version 5.
     filter "delta" (element_size 1 / 2 / 4 / 8, model "adaptive", not stored): the delta filter for integer series in front of
-    the layout, version 6."""
+    the layout, version 6.
+    model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
+    (api.context_static_tables, default total), version 7.  Nothing picks it for the caller: it pays from about half a
+    megabyte of text upward."""
     api._check_filter(filter, model == "adaptive" and not stored)
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
-            or model not in ("adaptive", "static", "plane-static", "segment-static") \
-            or (model == "static" and (element_size != 1 or stored)) \
+            or model not in ("adaptive", "static", "plane-static", "segment-static", "context-static") \
+            or (model in ("static", "context-static") and (element_size != 1 or stored)) \
             or (model == "plane-static" and (element_size == 1 or stored)) or (model == "segment-static" and stored) \
             or (model != "segment-static" and segment_blocks is not None):
         raise api.InvalidInput()
@@ -337,7 +413,8 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     flags = np.zeros(nb, dtype=np.uint8) if stored else None
     m = api.StaticModel.from_data(data, params) if model == "static" \
         else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" \
-        else api.SegmentStaticModel.template(params, element_size, segment_blocks) if model == "segment-static" else params
+        else api.SegmentStaticModel.template(params, element_size, segment_blocks) if model == "segment-static" \
+        else api.ContextStaticModel.from_data(data, block_size, params) if model == "context-static" else params
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter)
 

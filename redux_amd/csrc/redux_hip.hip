@@ -16,6 +16,7 @@
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist / k_*_plane_static*: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks
+//   redux_context_static.hpp  k_context_hist / k_*_context_static: the static coder with a table per preceding byte
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
@@ -39,6 +40,7 @@
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
 #include "redux_segment_static.hpp"
+#include "redux_context_static.hpp"
 #include "redux_crc.hpp"
 #include "redux_store.hpp"
 
@@ -3007,6 +3009,320 @@ int redux_segment_static_decode_blocks_crc(const redux_params *p, const uint32_t
     return decode_blocks_host(st, in, in_offsets, nblocks, block_size, out, out_len, out_len, out_sizes, block_status, nullptr,
                               segment_static_decoder(p, redux_segment_static_total(cum, ntables), block_size, element_size, segment_blocks),
                               block_crc, nullptr, host::SegmentTablesIo{const_cast<uint32_t *>(cum), element_size, segment_blocks});
+}
+
+// ---- context-static coding (redux_context_static.hpp) ----------------------------------------------
+// 256 tables, table c for the bytes that follow a byte c.  Every coder launch is k_context_image (the tables checked and
+// packed into the 128 KiB image at the front of the workspace) and then one persistent workgroup per CU.
+// Waves per workgroup.  The 128 KiB image allows one workgroup per CU, so the grid is first spread over the CUs and only then
+// deepened: W = the smallest built instance that holds ceil(wave slots / CUs), up to the largest (encode 8: sixteen waves
+// would be four per SIMD at 128 registers each, and the coder wave needs 132; decode 16).  65,536 blocks on 256 CUs are 1024
+// wave slots: 256 workgroups of 4 waves.  (REDUX_CTX_WAVES, variant builds only: one value for every launch, to measure the
+// values the rule does not choose.)
+constexpr uint64_t kCtxHead = kCtxImageBytes + 256; // the image and its flag, in front of a coder's own workspace
+
+static uint32_t context_waves(uint64_t nblocks, uint32_t max_waves)
+{
+#ifdef REDUX_CTX_WAVES
+    (void)nblocks;
+    return REDUX_CTX_WAVES < max_waves ? REDUX_CTX_WAVES : max_waves;
+#else
+    const uint64_t per_cu = ((nblocks + 63) / 64 + cu_count() - 1) / cu_count();
+    uint32_t       w      = 4;
+    while (w < max_waves && w < per_cu)
+        w *= 2;
+    return w;
+#endif
+}
+
+static int context_static_check(const redux_params *p, uint32_t total)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p) || total > kCtxTotalMax)
+        return REDUX_UNSUPPORTED;
+    return static_total_check(p, total);
+}
+
+int redux_context_static_table_check(const redux_params *p, const uint32_t *cum)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p))
+        return REDUX_UNSUPPORTED;
+    if (!cum)
+        return REDUX_INVALID_INPUT;
+    for (uint32_t c = 0; c < kCtxTables; c++) {
+        const uint32_t *t = cum + kStaticEntries * c;
+        if ((st = static_check(p, t)) != REDUX_OK)
+            return st;
+        if (t[kStaticEntries - 1] != cum[kStaticEntries - 1])
+            return REDUX_INVALID_INPUT;
+    }
+    return cum[kStaticEntries - 1] > kCtxTotalMax ? REDUX_UNSUPPORTED : REDUX_OK;
+}
+
+uint32_t redux_context_static_total(const uint32_t *cum) { return cum ? cum[kStaticEntries - 1] : 0; }
+
+int redux_context_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint32_t total, uint32_t *cum)
+{
+    int st = context_static_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!counts || !cum)
+        return REDUX_INVALID_INPUT;
+    uint64_t ones[256];
+    for (int s = 0; s < 256; s++)
+        ones[s] = 1;
+    for (uint32_t c = 0; c < kCtxTables; c++) {
+        const uint64_t *row = counts + 256 * c;
+        bool            any = false;
+        for (int s = 0; s < 256; s++)
+            any |= row[s] != 0;
+        if ((st = redux_static_table_from_counts(p, any ? row : ones, total, cum + kStaticEntries * c)) != REDUX_OK)
+            return st;
+    }
+    return REDUX_OK;
+}
+
+int redux_context_histogram_dev(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_counts, void *stream)
+{
+    if (block_size == 0 || !d_counts || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    if (in_len == 0)
+        return REDUX_OK;
+    ContextHistArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.block_size = block_size;
+    a.counts     = (unsigned long long *)d_counts;
+    const uint64_t lead = (16 - ((uintptr_t)d_in & 15)) & 15;
+    if (lead >= in_len) {
+        a.head = in_len;
+        a.nvec = 0;
+        a.tail = 0;
+    } else {
+        a.head = lead;
+        a.nvec = (in_len - lead) / 16;
+        a.tail = in_len - lead - a.nvec * 16;
+    }
+    const uint64_t rows = (a.nvec + kCtxHistThreads - 1) / kCtxHistThreads, cap = cu_count();
+    const uint32_t grid = (uint32_t)(rows < 1 ? 1 : rows < cap ? rows : cap);
+    k_context_hist<<<grid, kCtxHistThreads, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_context_static_tables_dev(const redux_params *p, const void *d_counts, uint32_t total, void *d_cum, void *stream)
+{
+    int st = context_static_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_counts || !d_cum)
+        return REDUX_INVALID_INPUT;
+    k_context_static_tables<<<kCtxTables, 256, 0, (hipStream_t)stream>>>((const unsigned long long *)d_counts, total, (uint32_t *)d_cum);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_context_static_tables(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t total,
+                                uint32_t *cum)
+{
+    int st = context_static_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !cum || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    std::vector<uint64_t> counts((size_t)kCtxTables * 256);
+    if ((st = host::byte_histogram(in, in_len, counts.data(), block_size, 1, true)) != REDUX_OK) // redux_host.hpp
+        return st;
+    return redux_context_static_tables_from_counts(p, counts.data(), total, cum);
+}
+
+uint64_t redux_context_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
+{
+    return redux_static_encode_bound(p, in_len, block_size);
+}
+
+uint64_t redux_context_static_encode_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size)
+{
+    const uint64_t ws = redux_static_encode_workspace_bytes(p, in_len, block_size);
+    return ws == 0 ? 0 : kCtxHead + ws;
+}
+
+uint64_t redux_context_static_decode_workspace_bytes(const redux_params *p, uint64_t nblocks, uint32_t block_size)
+{
+    (void)nblocks;
+    if (check_params(p) != REDUX_OK || is_any(p) || block_size == 0)
+        return 0;
+    return kCtxHead;
+}
+
+// the tables at d_cum -> the checked image and its flag at the front of the workspace
+static int context_image(const void *d_cum, uint32_t total, uint8_t *ws, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(ws + kCtxImageBytes, 0, 256, s));
+    k_context_image<<<kCtxTables, 256, 0, s>>>((const uint32_t *)d_cum, total, (uint16_t *)ws, (uint32_t *)(ws + kCtxImageBytes));
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+static void launch_context_encode(bool cb32, uint32_t waves, uint32_t grid, const ContextEncArgs &a, hipStream_t s)
+{
+    switch (waves * 2 + (cb32 ? 1 : 0)) {
+    case 8: k_encode_context_static<false, 4><<<grid, 256, 0, s>>>(a); break;
+    case 9: k_encode_context_static<true, 4><<<grid, 256, 0, s>>>(a); break;
+    case 17: k_encode_context_static<true, 8><<<grid, 512, 0, s>>>(a); break;
+    default: k_encode_context_static<false, 8><<<grid, 512, 0, s>>>(a); break;
+    }
+}
+
+int redux_context_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                    uint32_t block_size, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status,
+                                    void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = context_static_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
+        return REDUX_INVALID_INPUT;
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (workspace_bytes < kCtxHead + g.total)
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (64ull * g.slot_bytes >= (1ull << 32) || 64ull * block_size >= (1ull << 32)) // 64 slots / blocks within a 32-bit lane offset
+        return REDUX_UNSUPPORTED;
+    hipStream_t s    = (hipStream_t)stream;
+    uint8_t    *head = (uint8_t *)d_workspace, *ws = head + kCtxHead;
+    if ((st = context_image(d_cum, total, head, s)) != REDUX_OK)
+        return st;
+    HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
+    ContextEncArgs a;
+    a.c.in         = (const uint8_t *)d_in;
+    a.c.in_len     = in_len;
+    a.c.nblocks    = g.nblocks;
+    a.c.slots      = ws + g.off_slots;
+    a.c.slot_bytes = g.slot_bytes;
+    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
+    a.c.status     = (int32_t *)d_block_status;
+    a.c.rc         = static_rc(total);
+    a.c.block_size = block_size;
+    a.c.slot_cap   = g.slot_cap;
+    a.c.code_bits  = p->code_bits;
+    a.c.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    a.image        = (const uint16_t *)head;
+    a.bad          = (const uint32_t *)(head + kCtxImageBytes);
+    a.total        = total;
+    const uint32_t W      = context_waves(g.nblocks, 8);
+    const uint64_t groups = ((g.nblocks + 63) / 64 + W - 1) / W, cus = cu_count();
+    const uint32_t grid   = (uint32_t)(groups < cus ? groups : cus);
+    launch_context_encode(p->code_bits == 32, W, grid, a, s);
+    HIP_TRY(hipGetLastError());
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, workspace_bytes - kCtxHead, stream);
+}
+
+int redux_context_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                    uint64_t nblocks, uint32_t block_size, void *d_out, uint64_t out_cap, void *d_out_sizes,
+                                    void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = context_static_check(p, total);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !d_cum || !d_in_offsets || !d_out_sizes || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
+        return REDUX_INVALID_INPUT;
+    if (nblocks == 0)
+        return REDUX_OK;
+    if (out_cap < nblocks * (uint64_t)block_size || workspace_bytes < kCtxHead)
+        return REDUX_OUTPUT_TOO_SMALL;
+    hipStream_t s    = (hipStream_t)stream;
+    uint8_t    *head = (uint8_t *)d_workspace;
+    if ((st = context_image(d_cum, total, head, s)) != REDUX_OK)
+        return st;
+    ContextDecArgs a;
+    a.c.in         = (const uint8_t *)d_in;
+    a.c.in_offsets = (const uint64_t *)d_in_offsets;
+    a.c.nblocks    = nblocks;
+    a.c.out        = (uint8_t *)d_out;
+    a.c.out_sizes  = (uint32_t *)d_out_sizes;
+    a.c.status     = (int32_t *)d_block_status;
+    a.c.rc         = static_rc(total);
+    a.c.block_size = block_size;
+    a.c.code_bits  = p->code_bits;
+    a.c.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    a.image        = (const uint16_t *)head;
+    a.bad          = (const uint32_t *)(head + kCtxImageBytes);
+    a.total        = total;
+    const uint32_t W      = context_waves(nblocks, 16);
+    const uint64_t groups = ((nblocks + 63) / 64 + W - 1) / W, cus = cu_count();
+    const uint32_t grid   = (uint32_t)(groups < cus ? groups : cus);
+    switch (W) {
+    case 4: k_decode_context_static<4><<<grid, 256, 0, s>>>(a); break;
+    case 8: k_decode_context_static<8><<<grid, 512, 0, s>>>(a); break;
+    default: k_decode_context_static<16><<<grid, 1024, 0, s>>>(a); break;
+    }
+    if (d_summary)
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// The coders of the chunked host calls: the tables (258 KiB) travel to each chunk's device behind the coder's workspace,
+// stream-ordered.  Chunks are whole blocks and blocks are independent, so a chunk needs nothing from its neighbours.
+static uint64_t context_tables_bytes() { return align_up((uint64_t)kCtxTables * kStaticEntries * 4, 256); }
+
+static host::EncodeCoder context_static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
+{
+    const uint32_t total = redux_context_static_total(cum);
+    return {[=](uint64_t max_in, bool, uint64_t &ws, uint64_t &bound) {
+                ws    = context_tables_bytes() + redux_context_static_encode_workspace_bytes(p, max_in, block_size);
+                bound = redux_context_static_encode_bound(p, max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                const uint64_t tb = context_tables_bytes();
+                if (ws_bytes < tb)
+                    return REDUX_OUTPUT_TOO_SMALL;
+                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)kCtxTables * kStaticEntries * 4, hipMemcpyHostToDevice, st));
+                return redux_context_static_encode_dev(p, ws, total, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                                       s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+            }};
+}
+
+static host::DecodeCoder context_static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
+{
+    const uint32_t total = redux_context_static_total(cum);
+    return {[=](uint64_t cb) { return context_tables_bytes() + redux_context_static_decode_workspace_bytes(p, cb, block_size); },
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+                const uint64_t tb = context_tables_bytes();
+                if (ws_bytes < tb)
+                    return REDUX_OUTPUT_TOO_SMALL;
+                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)kCtxTables * kStaticEntries * 4, hipMemcpyHostToDevice, st));
+                return redux_context_static_decode_dev(p, ws, total, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes, s.d_sz.p,
+                                                       s.d_st.p, s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+            }};
+}
+
+int redux_context_static_encode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, uint64_t in_len,
+                                           uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                           int32_t *block_status, uint32_t *block_crc)
+{
+    int st = redux_context_static_table_check(p, cum);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, context_static_encoder(p, cum, block_size),
+                               block_crc); // redux_host.hpp
+}
+
+int redux_context_static_decode_blocks_crc(const redux_params *p, const uint32_t *cum, const uint8_t *in, const uint64_t *in_offsets,
+                                           uint64_t nblocks, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint32_t *out_sizes,
+                                           int32_t *block_status, uint32_t *block_crc)
+{
+    const int st = redux_context_static_table_check(p, cum);
+    if (st != REDUX_OK)
+        return st;
+    return decode_blocks_host(st, in, in_offsets, nblocks, block_size, out, nblocks * (uint64_t)block_size, out_cap, out_sizes,
+                              block_status, nullptr, context_static_decoder(p, cum, block_size), block_crc);
 }
 
 // ---- stored blocks (redux_store.hpp) --------------------------------------------------------------

@@ -933,8 +933,11 @@ static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t
 // E > 1 (redux_plane_static_tables): counts is u64[E][256], the counts of the byte-plane layout's blocks b by b mod E.  The
 // chunks are then whole frames of E * block_size bytes, so that a chunk's layout is its part of the whole input's and its
 // first block is a multiple of E; the layout of each chunk goes into the slot's workspace and k_plane_hist counts that.
+// pairs (redux_context_static_tables, E = 1): counts is u64[256][256], the (previous byte, byte) counts inside blocks of
+// block_size; the chunks are whole blocks and k_context_hist counts each.
 // ================================================================================================
-static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts, uint32_t block_size = 0, uint32_t E = 1)
+static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts, uint32_t block_size = 0, uint32_t E = 1,
+                          bool pairs = false)
 {
     Ctx *cp  = nullptr;
     int  dev = 0;
@@ -952,9 +955,14 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts, 
         const uint64_t frame = (uint64_t)E * block_size;
         chunk = (chunk + frame - 1) / frame * frame;
     }
+    if (pairs) {
+        chunk = (chunk + block_size - 1) / block_size * block_size;
+        if (chunk > in_len && in_len) // (one chunk: no more room than the input, whatever the block size)
+            chunk = in_len;
+    }
     const uint64_t nchunks = (in_len + chunk - 1) / chunk;
     const int      nslots  = (int)(nchunks < (uint64_t)kSlots ? nchunks : (uint64_t)kSlots);
-    const size_t   cbytes  = (size_t)E * 256 * 8;
+    const size_t   cbytes  = pairs ? (size_t)65536 * 8 : (size_t)E * 256 * 8;
     if ((rc = grow_buf(c, c.d_counts, cbytes)) != REDUX_OK)
         return rc;
     for (int i = 0; i < nslots; i++) {
@@ -977,7 +985,9 @@ static int byte_histogram(const uint8_t *in, uint64_t in_len, uint64_t *counts, 
                 void *x = c.slot[j % kSlots].d_ws.p;
                 if ((rc = redux_planes_dev(d, x, n, block_size, E, 0, st)) == REDUX_OK)
                     rc = redux_plane_histogram_dev(x, n, block_size, E, c.d_counts.p, nullptr, 0, st);
-            } else if (rc == REDUX_OK)
+            } else if (rc == REDUX_OK && pairs)
+                rc = redux_context_histogram_dev(d, n, block_size, c.d_counts.p, st);
+            else if (rc == REDUX_OK)
                 rc = redux_histogram_dev(d, n, c.d_counts.p, nullptr, 0, st);
         }
     }

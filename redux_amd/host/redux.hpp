@@ -17,6 +17,7 @@
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
 //   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
 //   redux::hip::compress_blocks_segment_static / decompress_blocks_segment_static   static tables per block range
+//   redux::hip::context_static_tables / compress_blocks_context_static / decompress_blocks_context_static   a table per preceding byte
 //
 // Every stream byte is produced by the gfx950 kernels; there is no CPU coder in this header.
 #pragma once
@@ -334,6 +335,62 @@ inline std::vector<std::uint8_t> decompress_blocks_static(const Blocks &streams,
     std::vector<std::uint32_t> sz(nb);
     check(redux_static_decode_blocks(&cp, cum.data(), streams.data.data(), streams.offsets.data(), nb, block_size, out.data(),
                                      out.size(), sz.data(), nullptr));
+    if (sizes)
+        *sizes = sz;
+    return out;
+}
+
+// Context-static coding (include/redux_hip.h): a static table per preceding byte.  tables: u32[256][258], all of one total
+// <= 2^16 (default: min(2^16, freq_max)), built from the data by context_static_tables.
+inline std::vector<std::uint32_t> context_static_tables(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size,
+                                                        const model::Parameters &p, std::uint32_t total = 0)
+{
+    const redux_params cp = p.c_abi();
+    if (total == 0)
+        total = p.freq_max < 65536 ? (std::uint32_t)p.freq_max : 65536u;
+    std::vector<std::uint32_t> cum(256 * 258);
+    check(redux_context_static_tables(&cp, in, len, block_size, total, cum.data()));
+    return cum;
+}
+
+inline Blocks compress_blocks_context_static(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size,
+                                             const model::Parameters &p, const std::vector<std::uint32_t> &tables)
+{
+    const redux_params cp = p.c_abi();
+    if (tables.size() != 256 * 258)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    check(redux_context_static_table_check(&cp, tables.data()));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_context_static_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_context_static_encode_blocks_crc(&cp, tables.data(), in, len, block_size, b.data.data(), b.data.size(), b.offsets.data(),
+                                                 nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: block b of the result is data[b*block_size .. b*block_size + sizes[b])
+inline std::vector<std::uint8_t> decompress_blocks_context_static(const Blocks &streams, std::uint32_t block_size,
+                                                                  const model::Parameters &p, const std::vector<std::uint32_t> &tables,
+                                                                  std::vector<std::uint32_t> *sizes = nullptr)
+{
+    const redux_params cp = p.c_abi();
+    if (tables.size() != 256 * 258)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    check(redux_context_static_table_check(&cp, tables.data()));
+    if (streams.offsets.empty() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    const std::uint64_t        nb = streams.offsets.size() - 1;
+    std::vector<std::uint8_t>  out(nb * (std::uint64_t)block_size);
+    std::vector<std::uint32_t> sz(nb);
+    check(redux_context_static_decode_blocks_crc(&cp, tables.data(), streams.data.data(), streams.offsets.data(), nb, block_size,
+                                                 out.data(), out.size(), sz.data(), nullptr, nullptr));
     if (sizes)
         *sizes = sz;
     return out;

@@ -124,6 +124,19 @@ extern "C" {
                                               in_offsets: *const u64, out_len: u64, block_size: u32, element_size: u32,
                                               segment_blocks: u32, out: *mut u8, out_sizes: *mut u32, block_status: *mut i32,
                                               block_crc: *mut u32) -> c_int;
+    // context-static coding: a static table per preceding byte (cum: u32[256][258])
+    fn redux_context_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
+    fn redux_context_static_total(cum: *const u32) -> u32;
+    fn redux_context_static_tables_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
+    fn redux_context_static_tables(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, total: u32,
+                                   cum: *mut u32) -> c_int;
+    fn redux_context_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
+    fn redux_context_static_encode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_len: u64,
+                                              block_size: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                              block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_context_static_decode_blocks_crc(p: *const ReduxParams, cum: *const u32, input: *const u8, in_offsets: *const u64,
+                                              nblocks: u64, block_size: u32, out: *mut u8, out_cap: u64, out_sizes: *mut u32,
+                                              block_status: *mut i32, block_crc: *mut u32) -> c_int;
     fn redux_encode_blocks_stored(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
                                   store_ratio: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64, stored: *mut u8,
                                   block_status: *mut i32, block_crc: *mut u32) -> c_int;
