@@ -749,8 +749,9 @@ const char *redux_decode_kernel_name_table(const redux_params *p, uint32_t block
  * the kernels.  "" for arguments the _dev call rejects, and for nblocks == 0 (the decode call launches nothing). */
 const char *redux_static_encode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t in_len, uint32_t block_size);
 const char *redux_static_decode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t nblocks);
-/* The same for redux_plane_static_encode_dev / redux_plane_static_decode_dev (the k_*_plane_static* instances): the launch has
- * element_size * ceil(ceil(nblocks / element_size) / 64) waves. */
+/* The same for redux_plane_static_encode_dev / redux_plane_static_decode_dev, which run the k_*_segment_static* instances with
+ * a single segment and report them under that name: the launch has element_size * ceil(ceil(nblocks / element_size) / 64)
+ * waves. */
 const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
                                                   uint32_t element_size);
 const char *redux_plane_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size);

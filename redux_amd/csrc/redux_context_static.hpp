@@ -19,10 +19,10 @@
 //                             coder launch on whatever d_cum the caller passed; with the flag up the coders write
 //                             INVALID_INPUT for every block and nothing else.
 //   k_encode_context_static   W waves per workgroup, one workgroup per CU, the image loaded into LDS once; every wave then
-//                             walks wave slots of 64 blocks, one lane per block, in static_encode_body's form with a ctx
-//                             register per lane
-//   k_decode_context_static   the inverse in static_decode_body's per-lane form; get_symbol tests EOF against the row's last
-//                             entry and then searches the lane's own row in 8 steps
+//                             walks wave slots of 64 blocks, one lane per block: static_encode_body (redux_static.hpp) under
+//                             a ContextModel, which is the image and a ctx register per lane
+//   k_decode_context_static   the inverse: static_decode_body under the same model; get_symbol tests EOF against the row's
+//                             last entry and then searches the lane's own row in 8 steps
 //
 // The lock-step and lookup-table decoder forms of redux_static.hpp are not built here: both share ONE table among the lanes of
 // a wave (a Fenwick tree, a 64 KiB lookup), and here every lane is in a row of its own.
@@ -180,111 +180,37 @@ struct ContextEncArgs {
     uint32_t        total;
 };
 
-// get_frequency(s) under the table of ctx: [row[s - 1], row[s]) with row[-1] = 0 (two ds_read_u16)
-__device__ __forceinline__ void context_range(const uint16_t *img, uint32_t ctx, uint32_t s, uint32_t &lo, uint32_t &hi)
-{
-    const uint16_t *e = img + ctx * 256u + s;
-    lo                = s ? (uint32_t)e[-1] : 0u;
-    hi                = (uint32_t)e[0];
-}
-
-// static_chunk (redux_static.hpp) with the lane's context: sixteen symbols straight-line, redone from the saved state and
-// context with the general encode_symbol if any lane needed more than one 32-bit append
-template <bool CB32>
-__device__ __forceinline__ void context_chunk(EncState &S, uint32_t &ctx, const uint16_t *img, const uint4 cur, uint32_t c, double rc,
-                                              uint32_t sh, uint8_t *wdst)
-{
-    const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-    const EncState S0   = S;
-    const uint32_t ctx0 = ctx;
-    SpecCarry      C    = spec_begin(S);
-    uint32_t       mx   = 0;
+// The model of a lane (redux_static.hpp): the table of the byte before, 0 at a block's start, in the image in LDS.  Row c of
+// the image is cum_c[1..256], so row[s - 1] = cum[s] with row[-1] = 0 (the pad in front of row 0 makes it readable).
+struct ContextModel {
+    const uint16_t *img;
+    uint32_t        tot; // every table's total
+    uint32_t        ctx;
+    __device__ __forceinline__ uint32_t total() const { return tot; }
+    // [row[s - 1], row[s]): two ds_read_u16
+    __device__ __forceinline__ uint2 range(uint32_t s) const
+    {
+        const uint16_t *e = img + ctx * 256u + s;
+        return make_uint2(s ? (uint32_t)e[-1] : 0u, (uint32_t)e[0]);
+    }
+    __device__ __forceinline__ uint32_t eof_lo() const { return img[ctx * 256u + 255u]; }
+    // EOF owns [cum[256], total); else the s in 0..255 with cum[s] <= v < cum[s + 1], in 8 steps over the lane's own row
+    __device__ __forceinline__ bool find(uint32_t v, uint32_t &s) const
+    {
+        const uint16_t *row = img + ctx * 256u;
+        if (v >= (uint32_t)row[255])
+            return true;
+        s = 0;
 #pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-        uint32_t lo, hi;
-        context_range(img, ctx, s, lo, hi);
-        const uint32_t m = encode_symbol_spec<false, CB32>(S, C, lo, hi, c, rc, sh, wdst);
-        mx               = m > mx ? m : mx;
-        ctx              = s;
-    }
-    spec_end(S, C);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx > 32u) != 0, 0)) {
-        S   = S0;
-        ctx = ctx0;
-#pragma unroll 1
-        for (int i = 0; i < 16; i++) {
-            const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-            uint32_t lo, hi;
-            context_range(img, ctx, s, lo, hi);
-            encode_symbol<false>(S, lo, hi, c, rc, sh, false, wdst, 0xFFFFFFFFu);
-            ctx = s;
+        for (int b = 7; b >= 0; b--) {
+            const uint32_t t = s | (1u << b);
+            if ((uint32_t)row[t - 1] <= v)
+                s = t;
         }
+        return false;
     }
-}
-
-// static_encode_body (redux_static.hpp) for one wave of a larger workgroup: lane l codes block blk0 + l (blk0 < nblocks)
-template <bool CB32>
-__device__ __forceinline__ void context_encode_body(const StaticEncCore &a, const uint16_t *img, const uint32_t c, const uint64_t blk0)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t blk  = blk0 + lane;
-    const bool     live = blk < a.nblocks;
-    uint32_t       len  = 0;
-    if (live) {
-        const uint64_t rem = a.in_len - blk * a.block_size;
-        len                = rem < a.block_size ? (uint32_t)rem : a.block_size;
-    }
-    const uint8_t *src   = a.in + (live ? blk : blk0) * (uint64_t)a.block_size;
-    uint8_t       *wdst  = a.slots + blk0 * a.slot_bytes;
-    // dead lanes of the last wave own the spare slot behind the last real one (they store nothing)
-    const uint32_t off0  = live ? lane * (uint32_t)a.slot_bytes : (uint32_t)(a.nblocks - blk0) * (uint32_t)a.slot_bytes;
-    const uint32_t limit = off0 + a.slot_cap;
-    const uint32_t maxlen = __builtin_amdgcn_readfirstlane(wave_max(live ? len : 0u));
-    const uint32_t sh     = 32 - a.code_bits;
-    const double   rc     = a.rc;
-
-    EncState S;
-    enc_init(S, off0);
-    uint32_t p = 0, ctx = 0;
-    const uint32_t minlen = __builtin_amdgcn_readfirstlane(wave_min(live ? len : 0xFFFFFFFFu));
-    if (a.aligned16 && minlen != 0xFFFFFFFFu && minlen >= 32) {
-        const uint32_t main_end = minlen & ~15u;
-        ChunkQueue Q;
-        Q.init(a.in + blk0 * (uint64_t)a.block_size, live ? lane * a.block_size : 0u, main_end);
-        constexpr uint32_t kChunkBudget = 16 * 4 + 32; // bytes a chunk may add without a per-store check
-        for (; p < main_end; p += 16) {
-            const uint4 cur = Q.pop();
-            if (__builtin_amdgcn_ballot_w64(S.off + kChunkBudget > limit)) { // a slot is nearly full: every store checked
-                const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll 1
-                for (int i = 0; i < 16; i++) {
-                    const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                    uint32_t lo, hi;
-                    context_range(img, ctx, s, lo, hi);
-                    encode_symbol<false>(S, lo, hi, c, rc, sh, false, wdst, limit);
-                    ctx = s;
-                }
-            } else
-                context_chunk<CB32>(S, ctx, img, cur, c, rc, sh, wdst);
-        }
-    }
-    for (; p <= maxlen; p++) {
-        if (live && p < len) {
-            const uint32_t s = src[p];
-            uint32_t lo, hi;
-            context_range(img, ctx, s, lo, hi);
-            encode_symbol<false>(S, lo, hi, c, rc, sh, false, wdst, limit); // get_frequency(s) under table ctx
-            ctx = s;
-        } else if (live && p == len) {
-            // EOF under the context of the block's last byte: [cum[256], total)
-            const uint32_t shifts = encode_symbol<false>(S, img[ctx * 256u + 255u], c, c, rc, sh, true, wdst, limit);
-            const uint32_t size   = encode_finish(S, shifts, a.code_bits, off0, wdst, limit);
-            a.sizes[blk]  = size;
-            a.status[blk] = size > a.slot_cap ? REDUX_OUTPUT_TOO_SMALL : REDUX_OK;
-        }
-    }
-}
+    __device__ __forceinline__ void advance(uint32_t s) { ctx = s; }
+};
 
 template <bool CB32, int W>
 __global__ void __launch_bounds__(64 * W) k_encode_context_static(ContextEncArgs a)
@@ -300,8 +226,10 @@ __global__ void __launch_bounds__(64 * W) k_encode_context_static(ContextEncArgs
         return;
     }
     const uint16_t *img = ctx_image_load(lds, a.image);
-    for (uint64_t slot = (uint64_t)blockIdx.x * W + wave; slot < nwaves; slot += (uint64_t)gridDim.x * W)
-        context_encode_body<CB32>(a.c, img, a.total, slot * 64);
+    for (uint64_t slot = (uint64_t)blockIdx.x * W + wave; slot < nwaves; slot += (uint64_t)gridDim.x * W) {
+        ContextModel m{img, a.total, 0};
+        static_encode_body<false, CB32>(a.c, m, slot * 64, threadIdx.x & 63u, 1);
+    }
 }
 
 // ---- decoder -----------------------------------------------------------------------------------------------------------
@@ -311,114 +239,6 @@ struct ContextDecArgs {
     const uint32_t *bad;
     uint32_t        total;
 };
-
-// static_decode_body (redux_static.hpp) with the lane's context: one lane, one block (blk; not live past nblocks)
-__device__ __forceinline__ void context_decode_body(const StaticDecCore &a, const uint16_t *img, const uint32_t c, const uint64_t blk)
-{
-    const bool     live = blk < a.nblocks;
-    const uint32_t cb = a.code_bits, sh = 32 - cb;
-    uint64_t       size = 0;
-    const uint8_t *sp   = a.in;
-    if (live) {
-        const uint64_t o0 = a.in_offsets[blk];
-        size              = a.in_offsets[blk + 1] - o0;
-        sp                = a.in + o0;
-    }
-    const uint64_t stream_bits = size * 8;
-    uint8_t       *dst         = a.out + (live ? blk : 0) * (uint64_t)a.block_size;
-    const uint32_t capn        = a.block_size;
-    const double   rc          = a.rc;
-
-    BitIn B;
-    B.init(sp, live ? size : 0);
-    uint32_t W        = B.take(cb) << sh;
-    uint64_t consumed = cb;
-    uint32_t low = 0, high = 0xFFFFFFFFu;
-    int32_t  st   = REDUX_OK;
-    bool     done = !live;
-    if (live && consumed > stream_bits) { // stream shorter than code_bits: Err(Eof) at once
-        st   = REDUX_EOF;
-        done = true;
-    }
-    uint32_t n_out = 0, obuf = 0, ctx = 0;
-    for (uint32_t p = 0;; p++) {
-        if (__builtin_amdgcn_readfirstlane(__ballot(!done) == 0))
-            break;
-        if (done)
-            continue;
-        const uint32_t R1  = (high - low) >> sh;
-        const uint32_t Vd  = (W - low) >> sh;
-        const uint64_t num = ((uint64_t)Vd + 1) * c - 1;
-        const double   xd  = (double)R1 + 1.0;
-        uint32_t       v   = (uint32_t)((double)num / xd);
-        {
-            const int64_t r = (int64_t)(num - ((uint64_t)v * R1 + v));
-            if (r < 0)
-                v--;
-            else if ((uint64_t)r > (uint64_t)R1)
-                v++;
-        }
-        // get_symbol under table ctx: EOF owns [cum[256], total); else the s in 0..255 with cum[s] <= v < cum[s + 1]
-        const uint16_t *row = img + ctx * 256u; // row[s - 1] = cum[s]
-        if (v >= (uint32_t)row[255]) {          // codec.rs:136-138: EOF returns before any renormalisation
-            done = true;
-            continue;
-        }
-        uint32_t s = 0;
-#pragma unroll
-        for (int b = 7; b >= 0; b--) {
-            const uint32_t t = s | (1u << b);
-            if ((uint32_t)row[t - 1] <= v)
-                s = t;
-        }
-        const uint32_t lo = s ? (uint32_t)row[s - 1] : 0u, hi = (uint32_t)row[s];
-        ctx = s;
-        const double   Y     = __builtin_fma((double)R1, rc, rc);
-        const uint32_t nlow  = low + (scale_div<false>(R1, Y, lo, c) << sh);
-        const uint32_t nhigh = low + (scale_div<false, true>(R1, Y, hi, c) << sh) - 1u;
-        const uint32_t xx    = nlow ^ nhigh;
-        const uint32_t k     = xx ? (uint32_t)__builtin_clz(xx) : 32u;
-        const uint32_t low2  = (uint32_t)((uint64_t)nlow << k);
-        const uint32_t ih2   = (uint32_t)((uint64_t)(~nhigh) << k);
-        const uint32_t t     = (low2 & ih2) << 1;
-        const uint32_t j     = (uint32_t)__builtin_clz(~t);
-        low                  = (low2 << j) & 0x7FFFFFFFu;
-        high                 = ~((ih2 << j) & 0x7FFFFFFFu);
-        const uint32_t n     = k + j; // bits pulled by get_bit (codec.rs:157)
-        consumed += n;
-        if (consumed > stream_bits) { // read_bits would hit Err(Eof) (bitio/mod.rs:107)
-            st   = REDUX_EOF;
-            done = true;
-            continue;
-        }
-        if (p >= capn) { // the symbol is decoded; writing it is what fails (codec.rs:171)
-            st   = REDUX_OUTPUT_TOO_SMALL;
-            done = true;
-            continue;
-        }
-        const uint32_t nb   = B.take(n);
-        const uint64_t comb = ((uint64_t)W << 32) | ((uint64_t)nb << (32 + sh - n));
-        const uint64_t c1   = comb << k;
-        const uint64_t c2   = c1 << j;
-        W = (((uint32_t)(c2 >> 32) & 0x7FFFFFFFu) | ((uint32_t)(c1 >> 32) & 0x80000000u)) & (0xFFFFFFFFu << sh);
-        if (a.aligned4) {
-            obuf |= s << (8 * (p & 3));
-            if ((p & 3) == 3) {
-                *reinterpret_cast<uint32_t *>(dst + (p & ~3u)) = obuf;
-                obuf = 0;
-            }
-        } else
-            dst[p] = (uint8_t)s;
-        n_out = p + 1;
-    }
-    if (live) {
-        if (a.aligned4)
-            for (uint32_t i = n_out & ~3u; i < n_out; i++)
-                dst[i] = (uint8_t)(obuf >> (8 * (i & 3)));
-        a.out_sizes[blk] = n_out;
-        a.status[blk]    = st;
-    }
-}
 
 template <int W>
 __global__ void __launch_bounds__(64 * W) k_decode_context_static(ContextDecArgs a)
@@ -434,8 +254,10 @@ __global__ void __launch_bounds__(64 * W) k_decode_context_static(ContextDecArgs
         return;
     }
     const uint16_t *img = ctx_image_load(lds, a.image);
-    for (uint64_t slot = (uint64_t)blockIdx.x * W + wave; slot < nwaves; slot += (uint64_t)gridDim.x * W)
-        context_decode_body(a.c, img, a.total, slot * 64 + (threadIdx.x & 63u));
+    for (uint64_t slot = (uint64_t)blockIdx.x * W + wave; slot < nwaves; slot += (uint64_t)gridDim.x * W) {
+        ContextModel m{img, a.total, 0};
+        static_decode_body<false>(a.c, m, slot * 64 + (threadIdx.x & 63u));
+    }
 }
 
 } // namespace redux

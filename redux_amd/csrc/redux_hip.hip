@@ -14,8 +14,8 @@
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
-//   redux_plane_static.hpp  k_plane_hist / k_*_plane_static*: the static coder with one table per byte plane
-//   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks
+//   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
+//   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
 //   redux_context_static.hpp  k_context_hist / k_*_context_static: the static coder with a table per preceding byte
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
@@ -2155,7 +2155,8 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------
 // E tables, table b mod E for block b of the byte-plane layout.  The launch shape: table t's blocks are cut into wave slots
-// of 64, every table gets as many slots as table 0 (which owns the most blocks), and workgroup g serves t = g mod E.
+// of 64, every table gets as many slots as table 0 (which owns the most blocks), and workgroup g serves t = g mod E.  The
+// coders are segment-static's with a single segment (the tables_static_* functions below, k = 0).
 static uint64_t plane_slots(uint64_t nblocks, uint32_t E) { return ((nblocks + E - 1) / E + 63) / 64; } // wave slots per table
 
 static int plane_static_check(const redux_params *p, uint32_t element_size, uint32_t total)
@@ -2164,6 +2165,35 @@ static int plane_static_check(const redux_params *p, uint32_t element_size, uint
     if (st != REDUX_OK)
         return st;
     return redux_planes_check(element_size);
+}
+
+// what the host-side check asks of a batch of tables: each one a static table, and one common total among those that own
+// bytes (a table that owns none is all ones: total 257)
+static int tables_check(const redux_params *p, const uint32_t *cum, uint64_t ntables)
+{
+    uint32_t total = 0;
+    for (uint64_t i = 0; i < ntables; i++) {
+        const uint32_t *c  = cum + kStaticEntries * i;
+        const int       st = static_check(p, c);
+        if (st != REDUX_OK)
+            return st;
+        if (c[kStaticEntries - 1] == kStaticEntries - 1)
+            continue;
+        if (total && c[kStaticEntries - 1] != total)
+            return REDUX_INVALID_INPUT;
+        total = c[kStaticEntries - 1];
+    }
+    return REDUX_OK;
+}
+
+// the largest last entry of a batch of tables
+static uint32_t tables_total(const uint32_t *cum, uint64_t ntables)
+{
+    uint32_t total = kStaticEntries - 1;
+    for (uint64_t i = 0; cum && i < ntables; i++)
+        if (cum[kStaticEntries * i + kStaticEntries - 1] > total)
+            total = cum[kStaticEntries * i + kStaticEntries - 1];
+    return total;
 }
 
 int redux_plane_static_table_check(const redux_params *p, const uint32_t *cum, uint32_t element_size)
@@ -2175,28 +2205,10 @@ int redux_plane_static_table_check(const redux_params *p, const uint32_t *cum, u
         return REDUX_UNSUPPORTED;
     if (redux_planes_check(element_size) != REDUX_OK || !cum)
         return REDUX_INVALID_INPUT;
-    uint32_t total = 0; // of the tables that own bytes; a table that owns none is all ones (total 257)
-    for (uint32_t t = 0; t < element_size; t++) {
-        const uint32_t *c = cum + kStaticEntries * t;
-        if ((st = static_check(p, c)) != REDUX_OK)
-            return st;
-        if (c[kStaticEntries - 1] == kStaticEntries - 1)
-            continue;
-        if (total && c[kStaticEntries - 1] != total)
-            return REDUX_INVALID_INPUT;
-        total = c[kStaticEntries - 1];
-    }
-    return REDUX_OK;
+    return tables_check(p, cum, element_size);
 }
 
-uint32_t redux_plane_static_total(const uint32_t *cum, uint32_t element_size)
-{
-    uint32_t total = kStaticEntries - 1;
-    for (uint32_t t = 0; cum && t < element_size; t++)
-        if (cum[kStaticEntries * t + kStaticEntries - 1] > total)
-            total = cum[kStaticEntries * t + kStaticEntries - 1];
-    return total;
-}
+uint32_t redux_plane_static_total(const uint32_t *cum, uint32_t element_size) { return tables_total(cum, element_size); }
 
 int redux_plane_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint32_t element_size, uint32_t total,
                                           uint32_t *cum)
@@ -2281,23 +2293,56 @@ static bool plane_static_fits(const Geometry &g, uint32_t block_size, uint32_t E
     return 64ull * E * g.slot_bytes < (1ull << 32) && 64ull * E * block_size < (1ull << 32);
 }
 
-static const char *plane_static_name(bool decode, int k)
+// The lookup decoder's WAVES wave slots share a table, so they must share a segment: k a multiple of WAVES (k = 0, a single
+// segment, is one).  Where the 8-wave instance does not suit, the 4-wave one is tried; where neither does (k = 1, 2, 3, 5,
+// ...), the lock-step decoder.
+static StaticDecKernel pick_segment_decode_kernel(const redux_params *p, uint32_t total, uint64_t launch_blocks, uint32_t k)
 {
-    static const char *const enc[4] = {"k_encode_plane_static<true, false> (total >= 2^17: quotient fix-up)",
-                                       "k_encode_plane_static<false, true, true> (code_bits 32, one wave per SIMD)",
-                                       "k_encode_plane_static<false, true> (code_bits 32)",
-                                       "k_encode_plane_static<false, false> (code_bits < 32)"};
+    const StaticDecKernel d    = pick_static_decode_kernel(p, total, launch_blocks);
+    const bool            cb32 = p->code_bits == 32;
+    switch (d) {
+    case StaticDecKernel::LutCb32:
+    case StaticDecKernel::Lut:
+        if (k % 8 == 0)
+            return d;
+        if (k % 4 == 0)
+            return cb32 ? StaticDecKernel::LutCb32Solo : StaticDecKernel::LutSolo;
+        return cb32 ? StaticDecKernel::LockCb32 : StaticDecKernel::Lock;
+    case StaticDecKernel::LutCb32Solo:
+    case StaticDecKernel::LutSolo:
+        if (k % 4 == 0)
+            return d;
+        return cb32 ? StaticDecKernel::LockCb32Solo : StaticDecKernel::LockSolo;
+    default: return d;
+    }
+}
+
+// the coders of redux_segment_static.hpp, which plane-static (k = 0) and segment-static (k = G / (64 E)) share
+static const char *tables_static_encode_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size, uint32_t E)
+{
+    static const char *const enc[4] = {"k_encode_segment_static<true, false> (total >= 2^17: quotient fix-up)",
+                                       "k_encode_segment_static<false, true, true> (code_bits 32, one wave per SIMD)",
+                                       "k_encode_segment_static<false, true> (code_bits 32)",
+                                       "k_encode_segment_static<false, false> (code_bits < 32)"};
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (!plane_static_fits(g, block_size, E))
+        return "";
+    return enc[(int)pick_static_encode_kernel(p, total, 64 * E * plane_slots(g.nblocks, E))];
+}
+
+static const char *tables_static_decode_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t E, uint32_t k)
+{
     static const char *const dec[9] = {
-        "k_decode_plane_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)",
-        "k_decode_plane_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)",
-        "k_decode_plane_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)",
-        "k_decode_plane_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)",
-        "k_decode_plane_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)",
-        "k_decode_plane_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)",
-        "k_decode_plane_static_lock<true, false> (lock-step, code_bits 32)",
-        "k_decode_plane_static_lock<false, true> (lock-step, one wave per SIMD)",
-        "k_decode_plane_static_lock<false, false> (lock-step)"};
-    return decode ? dec[k] : enc[k];
+        "k_decode_segment_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)",
+        "k_decode_segment_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)",
+        "k_decode_segment_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)",
+        "k_decode_segment_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)",
+        "k_decode_segment_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)",
+        "k_decode_segment_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)",
+        "k_decode_segment_static_lock<true, false> (lock-step, code_bits 32)",
+        "k_decode_segment_static_lock<false, true> (lock-step, one wave per SIMD)",
+        "k_decode_segment_static_lock<false, false> (lock-step)"};
+    return dec[(int)pick_segment_decode_kernel(p, total, 64 * E * plane_slots(nblocks, E), k)];
 }
 
 const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
@@ -2305,17 +2350,14 @@ const char *redux_plane_static_encode_kernel_name(const redux_params *p, uint32_
 {
     if (plane_static_check(p, element_size, total) != REDUX_OK || block_size == 0)
         return "";
-    const Geometry g = geometry(p, in_len, block_size, true);
-    if (!plane_static_fits(g, block_size, element_size))
-        return "";
-    return plane_static_name(false, (int)pick_static_encode_kernel(p, total, 64 * element_size * plane_slots(g.nblocks, element_size)));
+    return tables_static_encode_name(p, total, in_len, block_size, element_size);
 }
 
 const char *redux_plane_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size)
 {
     if (plane_static_check(p, element_size, total) != REDUX_OK || nblocks == 0)
         return "";
-    return plane_static_name(true, (int)pick_static_decode_kernel(p, total, 64 * element_size * plane_slots(nblocks, element_size)));
+    return tables_static_decode_name(p, total, nblocks, element_size, 0);
 }
 
 uint64_t redux_plane_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
@@ -2338,10 +2380,22 @@ uint64_t redux_plane_static_decode_workspace_bytes(const redux_params *p, uint64
     return planes_copy_bytes(redux_block_count(out_len, block_size) * (uint64_t)block_size);
 }
 
-// the static coder over x' (d_x: the layout of the input, or the input itself for E = 1) under the tables at d_cum
-static int plane_static_encode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_x, uint64_t in_len,
-                                 uint32_t block_size, uint32_t E, void *d_out, uint64_t out_cap, void *d_out_offsets,
-                                 void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+static SegmentTables segment_tables(const void *d_cum, uint32_t E, uint32_t k, uint32_t total)
+{
+    SegmentTables t;
+    t.p.cum   = (const uint32_t *)d_cum;
+    t.p.E     = E;
+    t.p.total = total;
+    t.p.rc257 = static_rc(kStaticEntries - 1);
+    t.k       = k;
+    return t;
+}
+
+// the static coder over x' (d_x: the layout of the input, or the input itself for E = 1) under the tables at d_cum; k wave
+// slots of a plane per segment, 0 for a single segment (SegmentTables)
+static int tables_static_encode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_x, uint64_t in_len,
+                                  uint32_t block_size, uint32_t E, uint32_t k, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                                  void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
     const Geometry g = geometry(p, in_len, block_size, true);
     if (workspace_bytes < g.total)
@@ -2351,7 +2405,7 @@ static int plane_static_encode_x(const redux_params *p, const void *d_cum, uint3
     hipStream_t s  = (hipStream_t)stream;
     uint8_t    *ws = (uint8_t *)d_workspace;
     HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
-    PlaneStaticEncArgs a;
+    SegmentStaticEncArgs a;
     a.c.in         = (const uint8_t *)d_x;
     a.c.in_len     = in_len;
     a.c.nblocks    = g.nblocks;
@@ -2364,20 +2418,36 @@ static int plane_static_encode_x(const redux_params *p, const void *d_cum, uint3
     a.c.slot_cap   = g.slot_cap;
     a.c.code_bits  = p->code_bits;
     a.c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
-    a.t.cum        = (const uint32_t *)d_cum;
-    a.t.E          = E;
-    a.t.total      = total;
-    a.t.rc257      = static_rc(kStaticEntries - 1);
+    a.t            = segment_tables(d_cum, E, k, total);
     const uint64_t slots = plane_slots(g.nblocks, E);
     const uint32_t grid  = (uint32_t)(slots * E);
     switch (pick_static_encode_kernel(p, total, 64 * E * slots)) {
-    case StaticEncKernel::Fixup: k_encode_plane_static<true, false><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Cb32Solo: k_encode_plane_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Cb32: k_encode_plane_static<false, true><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Narrow: k_encode_plane_static<false, false><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Fixup: k_encode_segment_static<true, false><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32Solo: k_encode_segment_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Cb32: k_encode_segment_static<false, true><<<grid, 64, 0, s>>>(a); break;
+    case StaticEncKernel::Narrow: k_encode_segment_static<false, false><<<grid, 64, 0, s>>>(a); break;
     }
     HIP_TRY(hipGetLastError());
     return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+// the layout of d_in at the front of the workspace (E > 1), then the coder over it
+static int tables_static_encode(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
+                                uint32_t block_size, uint32_t E, uint32_t k, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                                void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    if (E == 1)
+        return tables_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, k, d_out, out_cap, d_out_offsets, d_block_status,
+                                      d_summary, d_workspace, workspace_bytes, stream);
+    const uint64_t copy = planes_copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t  *x  = (uint8_t *)d_workspace;
+    const int st = redux_planes_dev(d_in, x, in_len, block_size, E, 0, stream);
+    if (st != REDUX_OK)
+        return st;
+    return tables_static_encode_x(p, d_cum, total, x, in_len, block_size, E, k, d_out, out_cap, d_out_offsets, d_block_status,
+                                  d_summary, x + copy, workspace_bytes - copy, stream);
 }
 
 int redux_plane_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
@@ -2389,25 +2459,16 @@ int redux_plane_static_encode_dev(const redux_params *p, const void *d_cum, uint
         return st;
     if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
         return REDUX_INVALID_INPUT;
-    if (element_size == 1)
-        return plane_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, d_out, out_cap, d_out_offsets, d_block_status,
-                                     d_summary, d_workspace, workspace_bytes, stream);
-    const uint64_t copy = planes_copy_bytes(in_len);
-    if (workspace_bytes < copy)
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t *x = (uint8_t *)d_workspace;
-    if ((st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
-        return st;
-    return plane_static_encode_x(p, d_cum, total, x, in_len, block_size, element_size, d_out, out_cap, d_out_offsets, d_block_status,
-                                 d_summary, x + copy, workspace_bytes - copy, stream);
+    return tables_static_encode(p, d_cum, total, d_in, in_len, block_size, element_size, 0, d_out, out_cap, d_out_offsets,
+                                d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
-// the static decoders under E tables: nblocks streams -> block b at d_planes + b * block_size
-static int plane_static_decode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
-                                 uint64_t nblocks, uint32_t block_size, uint32_t E, void *d_planes, void *d_out_sizes,
-                                 void *d_block_status, hipStream_t s)
+// the static decoders under the tables at d_cum (k as above): nblocks streams -> block b at d_planes + b * block_size
+static int tables_static_decode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                  uint64_t nblocks, uint32_t block_size, uint32_t E, uint32_t k, void *d_planes, void *d_out_sizes,
+                                  void *d_block_status, hipStream_t s)
 {
-    PlaneStaticLockArgs la;
+    SegmentStaticLockArgs la;
     memset(&la, 0, sizeof la);
     la.d.in         = (const uint8_t *)d_in;
     la.d.in_offsets = (const uint64_t *)d_in_offsets;
@@ -2421,16 +2482,13 @@ static int plane_static_decode_x(const redux_params *p, const void *d_cum, uint3
     la.d.aligned4   = ((((uintptr_t)d_planes) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
     if (la.d.aligned4 && (((uintptr_t)d_planes) & 15) == 0 && (block_size & 15) == 0)
         la.d.aligned4 = 2;
-    la.rc      = static_rc(total);
-    la.t.cum   = (const uint32_t *)d_cum;
-    la.t.E     = E;
-    la.t.total = total;
-    la.t.rc257 = static_rc(kStaticEntries - 1);
+    la.rc = static_rc(total);
+    la.t  = segment_tables(d_cum, E, k, total);
     const uint64_t slots = plane_slots(nblocks, E);
     const uint32_t grid  = (uint32_t)(slots * E), grid4 = (uint32_t)((slots + 3) / 4 * E), grid8 = (uint32_t)((slots + 7) / 8 * E);
-    switch (pick_static_decode_kernel(p, total, 64 * E * slots)) {
+    switch (pick_segment_decode_kernel(p, total, 64 * E * slots, k)) {
     case StaticDecKernel::Fixup: {
-        PlaneStaticDecArgs a;
+        SegmentStaticDecArgs a;
         a.c.in         = la.d.in;
         a.c.in_offsets = la.d.in_offsets;
         a.c.nblocks    = nblocks;
@@ -2442,17 +2500,17 @@ static int plane_static_decode_x(const redux_params *p, const void *d_cum, uint3
         a.c.code_bits  = p->code_bits;
         a.c.aligned4   = la.d.aligned4 ? 1 : 0;
         a.t            = la.t;
-        k_decode_plane_static<true><<<grid, 64, 0, s>>>(a);
+        k_decode_segment_static<true><<<grid, 64, 0, s>>>(a);
         break;
     }
-    case StaticDecKernel::LutCb32Solo: k_decode_plane_static_lut<true, 4><<<grid4, 256, 0, s>>>(la); break;
-    case StaticDecKernel::LutSolo: k_decode_plane_static_lut<false, 4><<<grid4, 256, 0, s>>>(la); break;
-    case StaticDecKernel::LutCb32: k_decode_plane_static_lut<true, 8><<<grid8, 512, 0, s>>>(la); break;
-    case StaticDecKernel::Lut: k_decode_plane_static_lut<false, 8><<<grid8, 512, 0, s>>>(la); break;
-    case StaticDecKernel::LockCb32Solo: k_decode_plane_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::LockCb32: k_decode_plane_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::LockSolo: k_decode_plane_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::Lock: k_decode_plane_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LutCb32Solo: k_decode_segment_static_lut<true, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutSolo: k_decode_segment_static_lut<false, 4><<<grid4, 256, 0, s>>>(la); break;
+    case StaticDecKernel::LutCb32: k_decode_segment_static_lut<true, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::Lut: k_decode_segment_static_lut<false, 8><<<grid8, 512, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32Solo: k_decode_segment_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockCb32: k_decode_segment_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::LockSolo: k_decode_segment_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
+    case StaticDecKernel::Lock: k_decode_segment_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -2461,6 +2519,30 @@ static int plane_static_decode_x(const redux_params *p, const void *d_cum, uint3
 // the blocks decode into a plane buffer at the front of the workspace (block_size bytes of room each, so a damaged stream
 // writes nothing outside it); their sizes are checked against the layout; the inverse transform writes d_out[0 .. out_len);
 // the summary comes last
+static int tables_static_decode(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
+                                uint64_t out_len, uint32_t block_size, uint32_t E, uint32_t k, void *d_out, void *d_out_sizes,
+                                void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    if (workspace_bytes < redux_plane_static_decode_workspace_bytes(p, out_len, block_size, E))
+        return REDUX_OUTPUT_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t    *x = (uint8_t *)d_workspace;
+    int st = tables_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, E, k, x, d_out_sizes, d_block_status, s);
+    if (st != REDUX_OK)
+        return st;
+    const uint64_t wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
+                                                                        nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    if ((st = redux_planes_dev(x, d_out, out_len, block_size, E, 1, stream)) != REDUX_OK)
+        return st;
+    if (d_summary)
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
 int redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
                                   uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
                                   void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
@@ -2470,24 +2552,8 @@ int redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint
         return st;
     if (block_size == 0 || !d_cum || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status || (out_len && !d_out))
         return REDUX_INVALID_INPUT;
-    const uint64_t nblocks = redux_block_count(out_len, block_size);
-    if (workspace_bytes < redux_plane_static_decode_workspace_bytes(p, out_len, block_size, element_size))
-        return REDUX_OUTPUT_TOO_SMALL;
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t    *x = (uint8_t *)d_workspace;
-    if ((st = plane_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, element_size, x, d_out_sizes,
-                                    d_block_status, s)) != REDUX_OK)
-        return st;
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
-                                                                        nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    if ((st = redux_planes_dev(x, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
-        return st;
-    if (d_summary)
-        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
+    return tables_static_decode(p, d_cum, total, d_in, d_in_offsets, out_len, block_size, element_size, 0, d_out, d_out_sizes,
+                                d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 // The coders of the chunked host calls.  The tables travel to each chunk's device behind the coder's workspace (8 KiB at
@@ -2590,28 +2656,10 @@ int redux_segment_static_table_check(const redux_params *p, const uint32_t *cum,
     const uint64_t want = redux_segment_static_table_count(nblocks, element_size, segment_blocks);
     if (want == 0 || ntables != want || !cum)
         return REDUX_INVALID_INPUT;
-    uint32_t total = 0; // of the tables that own bytes; a table that owns none is all ones (total 257)
-    for (uint64_t i = 0; i < ntables; i++) {
-        const uint32_t *c = cum + kStaticEntries * i;
-        if ((st = static_check(p, c)) != REDUX_OK)
-            return st;
-        if (c[kStaticEntries - 1] == kStaticEntries - 1)
-            continue;
-        if (total && c[kStaticEntries - 1] != total)
-            return REDUX_INVALID_INPUT;
-        total = c[kStaticEntries - 1];
-    }
-    return REDUX_OK;
+    return tables_check(p, cum, ntables);
 }
 
-uint32_t redux_segment_static_total(const uint32_t *cum, uint64_t ntables)
-{
-    uint32_t total = kStaticEntries - 1;
-    for (uint64_t i = 0; cum && i < ntables; i++)
-        if (cum[kStaticEntries * i + kStaticEntries - 1] > total)
-            total = cum[kStaticEntries * i + kStaticEntries - 1];
-    return total;
-}
+uint32_t redux_segment_static_total(const uint32_t *cum, uint64_t ntables) { return tables_total(cum, ntables); }
 
 int redux_segment_static_tables_from_counts(const redux_params *p, const uint64_t *counts, uint64_t nblocks, uint32_t element_size,
                                             uint32_t segment_blocks, uint32_t total, uint32_t *cum)
@@ -2681,57 +2729,12 @@ int redux_segment_static_tables_dev(const redux_params *p, const void *d_counts,
     return REDUX_OK;
 }
 
-// The lookup decoder's WAVES wave slots share a table, so they must share a segment: k a multiple of WAVES.  Where the
-// 8-wave instance does not suit, the 4-wave one is tried; where neither does (k = 1, 2, 3, 5, ...), the lock-step decoder.
-static StaticDecKernel pick_segment_decode_kernel(const redux_params *p, uint32_t total, uint64_t launch_blocks, uint32_t k)
-{
-    const StaticDecKernel d    = pick_static_decode_kernel(p, total, launch_blocks);
-    const bool            cb32 = p->code_bits == 32;
-    switch (d) {
-    case StaticDecKernel::LutCb32:
-    case StaticDecKernel::Lut:
-        if (k % 8 == 0)
-            return d;
-        if (k % 4 == 0)
-            return cb32 ? StaticDecKernel::LutCb32Solo : StaticDecKernel::LutSolo;
-        return cb32 ? StaticDecKernel::LockCb32 : StaticDecKernel::Lock;
-    case StaticDecKernel::LutCb32Solo:
-    case StaticDecKernel::LutSolo:
-        if (k % 4 == 0)
-            return d;
-        return cb32 ? StaticDecKernel::LockCb32Solo : StaticDecKernel::LockSolo;
-    default: return d;
-    }
-}
-
-static const char *segment_static_name(bool decode, int k)
-{
-    static const char *const enc[4] = {"k_encode_segment_static<true, false> (total >= 2^17: quotient fix-up)",
-                                       "k_encode_segment_static<false, true, true> (code_bits 32, one wave per SIMD)",
-                                       "k_encode_segment_static<false, true> (code_bits 32)",
-                                       "k_encode_segment_static<false, false> (code_bits < 32)"};
-    static const char *const dec[9] = {
-        "k_decode_segment_static<true> (total >= 2^17: quotient fix-up, per-lane control flow)",
-        "k_decode_segment_static_lut<true, 4> (total <= 2^16: lookup table, 4 waves per group, code_bits 32)",
-        "k_decode_segment_static_lut<false, 4> (total <= 2^16: lookup table, 4 waves per group)",
-        "k_decode_segment_static_lut<true, 8> (total <= 2^16: lookup table, 8 waves per group, code_bits 32)",
-        "k_decode_segment_static_lut<false, 8> (total <= 2^16: lookup table, 8 waves per group)",
-        "k_decode_segment_static_lock<true, true> (lock-step, code_bits 32, one wave per SIMD)",
-        "k_decode_segment_static_lock<true, false> (lock-step, code_bits 32)",
-        "k_decode_segment_static_lock<false, true> (lock-step, one wave per SIMD)",
-        "k_decode_segment_static_lock<false, false> (lock-step)"};
-    return decode ? dec[k] : enc[k];
-}
-
 const char *redux_segment_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size,
                                                     uint32_t element_size, uint32_t segment_blocks)
 {
     if (segment_static_check(p, element_size, segment_blocks, total) != REDUX_OK || block_size == 0)
         return "";
-    const Geometry g = geometry(p, in_len, block_size, true);
-    if (!plane_static_fits(g, block_size, element_size))
-        return "";
-    return segment_static_name(false, (int)pick_static_encode_kernel(p, total, 64 * element_size * plane_slots(g.nblocks, element_size)));
+    return tables_static_encode_name(p, total, in_len, block_size, element_size);
 }
 
 const char *redux_segment_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size,
@@ -2739,8 +2742,7 @@ const char *redux_segment_static_decode_kernel_name(const redux_params *p, uint3
 {
     if (segment_static_check(p, element_size, segment_blocks, total) != REDUX_OK || nblocks == 0)
         return "";
-    return segment_static_name(true, (int)pick_segment_decode_kernel(p, total, 64 * element_size * plane_slots(nblocks, element_size),
-                                                                      segment_blocks / (64 * element_size)));
+    return tables_static_decode_name(p, total, nblocks, element_size, segment_blocks / (64 * element_size));
 }
 
 uint64_t redux_segment_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
@@ -2770,49 +2772,6 @@ uint64_t redux_segment_static_build_encode_workspace_bytes(const redux_params *p
     return n && ws ? segment_counts_bytes(n) + ws : 0;
 }
 
-// the static coder over x' (d_x: the layout of the input, or the input itself for E = 1) under the tables at d_cum
-static int segment_static_encode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_x, uint64_t in_len,
-                                   uint32_t block_size, uint32_t E, uint32_t G, void *d_out, uint64_t out_cap, void *d_out_offsets,
-                                   void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
-{
-    const Geometry g = geometry(p, in_len, block_size, true);
-    if (workspace_bytes < g.total)
-        return REDUX_OUTPUT_TOO_SMALL;
-    if (!plane_static_fits(g, block_size, E))
-        return REDUX_UNSUPPORTED;
-    hipStream_t s  = (hipStream_t)stream;
-    uint8_t    *ws = (uint8_t *)d_workspace;
-    HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
-    SegmentStaticEncArgs a;
-    a.c.in         = (const uint8_t *)d_x;
-    a.c.in_len     = in_len;
-    a.c.nblocks    = g.nblocks;
-    a.c.slots      = ws + g.off_slots;
-    a.c.slot_bytes = g.slot_bytes;
-    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
-    a.c.status     = (int32_t *)d_block_status;
-    a.c.rc         = static_rc(total);
-    a.c.block_size = block_size;
-    a.c.slot_cap   = g.slot_cap;
-    a.c.code_bits  = p->code_bits;
-    a.c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
-    a.t.p.cum      = (const uint32_t *)d_cum;
-    a.t.p.E        = E;
-    a.t.p.total    = total;
-    a.t.p.rc257    = static_rc(kStaticEntries - 1);
-    a.t.k          = G / (64 * E);
-    const uint64_t slots = plane_slots(g.nblocks, E);
-    const uint32_t grid  = (uint32_t)(slots * E);
-    switch (pick_static_encode_kernel(p, total, 64 * E * slots)) {
-    case StaticEncKernel::Fixup: k_encode_segment_static<true, false><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Cb32Solo: k_encode_segment_static<false, true, true><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Cb32: k_encode_segment_static<false, true><<<grid, 64, 0, s>>>(a); break;
-    case StaticEncKernel::Narrow: k_encode_segment_static<false, false><<<grid, 64, 0, s>>>(a); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
-}
-
 int redux_segment_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
                                     uint32_t block_size, uint32_t element_size, uint32_t segment_blocks, void *d_out, uint64_t out_cap,
                                     void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
@@ -2823,17 +2782,8 @@ int redux_segment_static_encode_dev(const redux_params *p, const void *d_cum, ui
         return st;
     if (block_size == 0 || !d_cum || (!d_in && in_len) || !d_block_status || !d_workspace || (((uintptr_t)d_workspace) & 255))
         return REDUX_INVALID_INPUT;
-    if (element_size == 1)
-        return segment_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, segment_blocks, d_out, out_cap, d_out_offsets,
-                                       d_block_status, d_summary, d_workspace, workspace_bytes, stream);
-    const uint64_t copy = planes_copy_bytes(in_len);
-    if (workspace_bytes < copy)
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t *x = (uint8_t *)d_workspace;
-    if ((st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
-        return st;
-    return segment_static_encode_x(p, d_cum, total, x, in_len, block_size, element_size, segment_blocks, d_out, out_cap, d_out_offsets,
-                                   d_block_status, d_summary, x + copy, workspace_bytes - copy, stream);
+    return tables_static_encode(p, d_cum, total, d_in, in_len, block_size, element_size, segment_blocks / (64 * element_size), d_out,
+                                out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 // Layout once, the histogram of that copy, the tables, the coder over the same copy.  The workspace: the counts, then what
@@ -2863,69 +2813,10 @@ int redux_segment_static_build_encode_dev(const redux_params *p, uint32_t total,
         return st;
     if ((st = redux_segment_static_tables_dev(p, counts, nblocks, element_size, segment_blocks, total, d_cum, stream)) != REDUX_OK)
         return st;
-    return segment_static_encode_x(p, d_cum, total, d_x, in_len, block_size, element_size, segment_blocks, d_out, out_cap, d_out_offsets,
-                                   d_block_status, d_summary, x + copy, workspace_bytes - cb - copy, stream);
+    return tables_static_encode_x(p, d_cum, total, d_x, in_len, block_size, element_size, segment_blocks / (64 * element_size), d_out,
+                                  out_cap, d_out_offsets, d_block_status, d_summary, x + copy, workspace_bytes - cb - copy, stream);
 }
 
-// the static decoders under nseg * E tables: nblocks streams -> block b at d_planes + b * block_size
-static int segment_static_decode_x(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
-                                   uint64_t nblocks, uint32_t block_size, uint32_t E, uint32_t G, void *d_planes, void *d_out_sizes,
-                                   void *d_block_status, hipStream_t s)
-{
-    SegmentStaticLockArgs la;
-    memset(&la, 0, sizeof la);
-    la.d.in         = (const uint8_t *)d_in;
-    la.d.in_offsets = (const uint64_t *)d_in_offsets;
-    la.d.nblocks    = nblocks;
-    la.d.out        = (uint8_t *)d_planes;
-    la.d.out_sizes  = (uint32_t *)d_out_sizes;
-    la.d.status     = (int32_t *)d_block_status;
-    la.d.block_size = block_size;
-    la.d.nfreeze    = 0xFFFFFFFFu;
-    la.d.code_bits  = p->code_bits;
-    la.d.aligned4   = ((((uintptr_t)d_planes) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
-    if (la.d.aligned4 && (((uintptr_t)d_planes) & 15) == 0 && (block_size & 15) == 0)
-        la.d.aligned4 = 2;
-    la.rc        = static_rc(total);
-    la.t.p.cum   = (const uint32_t *)d_cum;
-    la.t.p.E     = E;
-    la.t.p.total = total;
-    la.t.p.rc257 = static_rc(kStaticEntries - 1);
-    la.t.k       = G / (64 * E);
-    const uint64_t slots = plane_slots(nblocks, E);
-    const uint32_t grid  = (uint32_t)(slots * E), grid4 = (uint32_t)((slots + 3) / 4 * E), grid8 = (uint32_t)((slots + 7) / 8 * E);
-    switch (pick_segment_decode_kernel(p, total, 64 * E * slots, la.t.k)) {
-    case StaticDecKernel::Fixup: {
-        SegmentStaticDecArgs a;
-        a.c.in         = la.d.in;
-        a.c.in_offsets = la.d.in_offsets;
-        a.c.nblocks    = nblocks;
-        a.c.out        = la.d.out;
-        a.c.out_sizes  = la.d.out_sizes;
-        a.c.status     = la.d.status;
-        a.c.rc         = la.rc;
-        a.c.block_size = block_size;
-        a.c.code_bits  = p->code_bits;
-        a.c.aligned4   = la.d.aligned4 ? 1 : 0;
-        a.t            = la.t;
-        k_decode_segment_static<true><<<grid, 64, 0, s>>>(a);
-        break;
-    }
-    case StaticDecKernel::LutCb32Solo: k_decode_segment_static_lut<true, 4><<<grid4, 256, 0, s>>>(la); break;
-    case StaticDecKernel::LutSolo: k_decode_segment_static_lut<false, 4><<<grid4, 256, 0, s>>>(la); break;
-    case StaticDecKernel::LutCb32: k_decode_segment_static_lut<true, 8><<<grid8, 512, 0, s>>>(la); break;
-    case StaticDecKernel::Lut: k_decode_segment_static_lut<false, 8><<<grid8, 512, 0, s>>>(la); break;
-    case StaticDecKernel::LockCb32Solo: k_decode_segment_static_lock<true, true><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::LockCb32: k_decode_segment_static_lock<true, false><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::LockSolo: k_decode_segment_static_lock<false, true><<<grid, 64, 0, s>>>(la); break;
-    case StaticDecKernel::Lock: k_decode_segment_static_lock<false, false><<<grid, 64, 0, s>>>(la); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
-}
-
-// redux_plane_static_decode_dev's procedure: plane buffer at the front of the workspace, sizes checked against the layout,
-// the inverse transform into d_out[0 .. out_len), the summary last
 int redux_segment_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
                                     uint64_t out_len, uint32_t block_size, uint32_t element_size, uint32_t segment_blocks, void *d_out,
                                     void *d_out_sizes, void *d_block_status, void *d_summary, void *d_workspace,
@@ -2936,24 +2827,9 @@ int redux_segment_static_decode_dev(const redux_params *p, const void *d_cum, ui
         return st;
     if (block_size == 0 || !d_cum || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status || (out_len && !d_out))
         return REDUX_INVALID_INPUT;
-    const uint64_t nblocks = redux_block_count(out_len, block_size);
-    if (workspace_bytes < redux_segment_static_decode_workspace_bytes(p, out_len, block_size, element_size))
-        return REDUX_OUTPUT_TOO_SMALL;
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t    *x = (uint8_t *)d_workspace;
-    if ((st = segment_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, element_size, segment_blocks, x,
-                                      d_out_sizes, d_block_status, s)) != REDUX_OK)
-        return st;
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
-                                                                        nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    if ((st = redux_planes_dev(x, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
-        return st;
-    if (d_summary)
-        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
+    return tables_static_decode(p, d_cum, total, d_in, d_in_offsets, out_len, block_size, element_size,
+                                segment_blocks / (64 * element_size), d_out, d_out_sizes, d_block_status, d_summary, d_workspace,
+                                workspace_bytes, stream);
 }
 
 // The coders of the chunked host calls.  Chunks are whole segments (host::SegmentTablesIo), so a chunk's segment numbers are

@@ -4,19 +4,15 @@
 // block size B; table t, 0 <= t < E, is the semi-static table of the bytes of all blocks b of x' with b mod E == t, and
 // block b is coded under table b mod E by the static coder of redux_static.hpp.
 //
-//   k_plane_hist                 counts x' into u64[E][256] (added to).  k_byte_hist's design (per-lane packed u16 counters
-//                                in LDS, folded before 65,536, one global u64 atomic per nonzero bin); a workgroup is bound
-//                                to one t and walks the blocks t, t + E, t + 2E, ... as contiguous B-byte runs
-//   k_encode_plane_static        k_encode_static / k_decode_static / k_decode_static_lock / k_decode_static_lut with their
-//   k_decode_plane_static        bodies unchanged; what differs is which block a lane owns and which table a workgroup
-//   k_decode_plane_static_lock   loads: workgroup g serves table t = g mod E, and wave slot w of that t owns the blocks
-//   k_decode_plane_static_lut    (64 w + lane) E + t.  Slots, sizes, status and offsets stay indexed by the real block
-//                                number, so the scan / compact kernels and the output addressing are untouched.
+//   k_plane_hist   counts x' into u64[E][256] (added to).  k_byte_hist's design (per-lane packed u16 counters in LDS, folded
+//                  before 65,536, one global u64 atomic per nonzero bin); a workgroup is bound to one t and walks the blocks
+//                  t, t + E, t + 2E, ... as contiguous B-byte runs
 //
-// The tables are read from device memory (u32[E][258]: eight tables are 8,256 bytes, more than a kernel's arguments should
-// carry) and are checked by the workgroup that loads them: a table that is not strictly increasing from 0 to the launch's
-// total makes every block of that workgroup INVALID_INPUT, so a table no host code has seen cannot break the coder's
-// invariants.
+// The coders are those of redux_segment_static.hpp with a single segment (SegmentTables::k == 0); what they share with this
+// file is the description of the tables and their device-side check.  The tables are read from device memory (u32[E][258]:
+// eight tables are 8,256 bytes, more than a kernel's arguments should carry) and are checked by the workgroup that loads
+// them: a table that is not strictly increasing from 0 to the launch's total makes every block of that workgroup
+// INVALID_INPUT, so a table no host code has seen cannot break the coder's invariants.
 //
 // Included by redux_hip.hip (one translation unit).
 #pragma once
@@ -137,7 +133,7 @@ __global__ void __launch_bounds__(64) k_plane_hist(PlaneHistArgs a)
             atomicAdd(counts + 2 * lane + 128 * (i >> 1) + (i & 1), acc[i]);
 }
 
-// ---- the coders with E tables ------------------------------------------------------------------------------------------
+// ---- the tables of the coders ---------------------------------------------------------------------------------------
 struct PlaneTables {
     const uint32_t *cum;   // u32[E][258], device memory
     uint32_t        E;
@@ -164,71 +160,6 @@ __device__ __forceinline__ double plane_table_rc(const uint32_t *cum, const Plan
     return cum[kStaticEntries - 1] == t.total ? rc : t.rc257;
 }
 
-struct PlaneStaticEncArgs {
-    StaticEncCore c;
-    PlaneTables   t;
-};
-
-template <bool FIXUP, bool CB32, bool SOLO = false>
-__global__ void __launch_bounds__(64) k_encode_plane_static(PlaneStaticEncArgs a)
-{
-    __shared__ uint32_t tab[kStaticEntries + 2];
-    claim_the_simd<SOLO>();
-    const uint32_t  t    = blockIdx.x % a.t.E;
-    const uint64_t  blk0 = (uint64_t)(blockIdx.x / a.t.E) * 64 * a.t.E + t; // lane 0's block
-    if (blk0 >= a.c.nblocks)
-        return;
-    const uint32_t *cum = a.t.cum + kStaticEntries * t;
-    const bool      ok  = plane_table_ok(cum, a.t.total);
-    if (!ok) {
-        const uint64_t blk = blk0 + (uint64_t)threadIdx.x * a.t.E;
-        if (blk < a.c.nblocks) {
-            a.c.sizes[blk]  = 0;
-            a.c.status[blk] = REDUX_INVALID_INPUT;
-        }
-        return;
-    }
-    for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
-        tab[i] = cum[i];
-    __syncthreads();
-    StaticEncCore c = a.c;
-    c.rc            = plane_table_rc(cum, a.t, a.c.rc);
-    static_encode_body<FIXUP, CB32>(c, tab, blk0, a.t.E);
-}
-
-struct PlaneStaticDecArgs {
-    StaticDecCore c;
-    PlaneTables   t;
-};
-
-template <bool FIXUP>
-__global__ void __launch_bounds__(64) k_decode_plane_static(PlaneStaticDecArgs a)
-{
-    __shared__ uint32_t tab[kStaticEntries + 2];
-    const uint32_t  t   = blockIdx.x % a.t.E;
-    const uint64_t  blk = ((uint64_t)(blockIdx.x / a.t.E) * 64 + threadIdx.x) * a.t.E + t;
-    const uint32_t *cum = a.t.cum + kStaticEntries * t;
-    if (!plane_table_ok(cum, a.t.total)) {
-        if (blk < a.c.nblocks) {
-            a.c.out_sizes[blk] = 0;
-            a.c.status[blk]    = REDUX_INVALID_INPUT;
-        }
-        return;
-    }
-    for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
-        tab[i] = cum[i];
-    __syncthreads();
-    StaticDecCore c = a.c;
-    c.rc            = plane_table_rc(cum, a.t, a.c.rc);
-    static_decode_body<FIXUP>(c, tab, blk);
-}
-
-struct PlaneStaticLockArgs {
-    DecArgs     d;
-    double      rc;
-    PlaneTables t;
-};
-
 // the blocks of a workgroup whose table failed the check: WAVES waves of 64 blocks from wave slot w0 of table t
 __device__ __forceinline__ void plane_static_refuse(const DecArgs &d, const PlaneTables &pt, uint64_t w0, uint32_t t)
 {
@@ -237,35 +168,6 @@ __device__ __forceinline__ void plane_static_refuse(const DecArgs &d, const Plan
         d.out_sizes[blk] = 0;
         d.status[blk]    = REDUX_INVALID_INPUT;
     }
-}
-
-template <bool CB32, bool SOLO>
-__global__ void __launch_bounds__(64) k_decode_plane_static_lock(PlaneStaticLockArgs a)
-{
-    __shared__ uint32_t lds[kStaticTreeDwords + 32 * 64];
-    claim_the_simd<SOLO>();
-    const uint32_t  t   = blockIdx.x % a.t.E;
-    const uint64_t  w   = blockIdx.x / a.t.E;
-    const uint32_t *cum = a.t.cum + kStaticEntries * t;
-    if (!plane_table_ok(cum, a.t.total)) {
-        plane_static_refuse(a.d, a.t, w, t);
-        return;
-    }
-    decode_lock_body<CB32, 1>(a.d, lds, cum, plane_table_rc(cum, a.t, a.rc), threadIdx.x, w, nullptr, nullptr, a.t.E, t);
-}
-
-template <bool CB32, int WAVES>
-__global__ void __launch_bounds__(64 * WAVES) k_decode_plane_static_lut(PlaneStaticLockArgs a)
-{
-    __shared__ uint32_t lds[65536 / 4 + 260 + WAVES * 32 * 64];
-    const uint32_t  t   = blockIdx.x % a.t.E;
-    const uint64_t  g   = blockIdx.x / a.t.E;
-    const uint32_t *cum = a.t.cum + kStaticEntries * t;
-    if (!plane_table_ok(cum, a.t.total)) {
-        plane_static_refuse(a.d, a.t, g * WAVES, t); // (threadIdx.x runs over the workgroup's WAVES * 64 blocks)
-        return;
-    }
-    static_lut_body<CB32, WAVES>(a.d, plane_table_rc(cum, a.t, a.rc), cum, lds, g, a.t.E, t);
 }
 
 } // namespace redux

@@ -7,10 +7,14 @@
 //   k_segment_hist                 counts x' into u64[nseg][E][256] (added to).  k_plane_hist's design; a workgroup is bound
 //                                  to one (s, t) at a time and walks that pair's blocks s G + t, s G + t + E, ...
 //   k_static_tables                k_static_table's body (static_table_build, redux_hist.hpp), one workgroup per table
-//   k_encode_segment_static        the k_*_plane_static* kernels with one more term in the table's address: wave slot w of
-//   k_decode_segment_static        plane t owns the blocks (64 w + lane) E + t, which all lie in segment w / k, so it loads
-//   k_decode_segment_static_lock   table (w / k) E + t.  The lookup decoder shares one table among WAVES wave slots: it is
-//   k_decode_segment_static_lut    launched only where k is a multiple of WAVES, so that those slots share a segment.
+//   k_encode_segment_static        k_encode_static / k_decode_static / k_decode_static_lock / k_decode_static_lut with their
+//   k_decode_segment_static        bodies unchanged; what differs is which block a lane owns and which table a workgroup
+//   k_decode_segment_static_lock   loads: workgroup g serves plane t = g mod E, and wave slot w of that t owns the blocks
+//   k_decode_segment_static_lut    (64 w + lane) E + t, which all lie in segment w / k, so it loads table (w / k) E + t.
+//                                  Slots, sizes, status and offsets stay indexed by the real block number, so the scan /
+//                                  compact kernels and the output addressing are untouched.  The lookup decoder shares one
+//                                  table among WAVES wave slots: it is launched only where k is a multiple of WAVES, so
+//                                  that those slots share a segment.  These are plane-static's coders too (k == 0, below).
 //
 // The tables are read from device memory and checked by the workgroup that loads them (plane_table_ok): a bad table makes
 // only that workgroup's blocks INVALID_INPUT.
@@ -127,15 +131,18 @@ __global__ void __launch_bounds__(256) k_static_tables(const unsigned long long 
 }
 
 // ---- the coders with nseg * E tables -------------------------------------------------------------------------------------
+// k == 0 stands for "one segment that holds every block": E tables, table t for every wave slot of plane t, which is
+// plane-static coding (redux_plane_static.hpp).  Nothing is divided by such a k, and the launch code's "k a multiple of
+// WAVES" holds for it, as it should: all wave slots of a plane share the one table.
 struct SegmentTables {
     PlaneTables p; // p.cum: u32[nseg][E][258], device memory
-    uint32_t    k; // wave slots of a plane per segment: G = 64 E k
+    uint32_t    k; // wave slots of a plane per segment: G = 64 E k; 0: a single segment
 };
 
 // the table of wave slot w of plane t (w: wave-uniform)
 __device__ __forceinline__ const uint32_t *segment_cum(const SegmentTables &s, uint64_t w, uint32_t t)
 {
-    return s.p.cum + (uint64_t)kStaticEntries * ((w / s.k) * s.p.E + t);
+    return s.p.cum + (uint64_t)kStaticEntries * ((s.k ? w / s.k : 0) * s.p.E + t);
 }
 
 struct SegmentStaticEncArgs {
@@ -167,7 +174,8 @@ __global__ void __launch_bounds__(64) k_encode_segment_static(SegmentStaticEncAr
     __syncthreads();
     StaticEncCore c = a.c;
     c.rc            = plane_table_rc(cum, a.t.p, a.c.rc);
-    static_encode_body<FIXUP, CB32>(c, tab, blk0, E);
+    TableModel m{tab};
+    static_encode_body<FIXUP, CB32>(c, m, blk0, threadIdx.x, E);
 }
 
 struct SegmentStaticDecArgs {
@@ -195,7 +203,8 @@ __global__ void __launch_bounds__(64) k_decode_segment_static(SegmentStaticDecAr
     __syncthreads();
     StaticDecCore c = a.c;
     c.rc            = plane_table_rc(cum, a.t.p, a.c.rc);
-    static_decode_body<FIXUP>(c, tab, blk);
+    TableModel m{tab};
+    static_decode_body<FIXUP>(c, m, blk);
 }
 
 struct SegmentStaticLockArgs {

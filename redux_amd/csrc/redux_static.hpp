@@ -38,7 +38,7 @@ struct StaticTable { // passed by value in the kernel arguments (1032 bytes)
     uint32_t cum[kStaticEntries];
 };
 
-struct StaticEncCore { // everything but the table: shared with the E-table kernels of redux_plane_static.hpp
+struct StaticEncCore { // everything but the table: shared with the E-table kernels of redux_segment_static.hpp
     const uint8_t *in;
     uint64_t       in_len;
     uint64_t       nblocks;
@@ -57,31 +57,66 @@ struct StaticEncArgs : StaticEncCore {
     StaticTable tab;
 };
 
+// The model of a lane: what the per-lane coder bodies below ask of it.  total() is total_frequency(); range(s) is
+// get_frequency(s) for a data symbol, (low, high) in .x and .y, and eof_lo() the low end of the EOF symbol's range, which
+// ends at the total; find(v, s) is get_symbol(v): true for EOF, else the symbol in s; advance(s) follows every data symbol
+// coded.  A model is a few registers: a body takes it by value, fresh for its block, and the 16-symbol stretch saves it
+// next to the coder state and restores both for a redo.  Results come back by value and find's search runs on a local:
+// with reference out-parameters written inside the unrolled code the compiler allocates up to six more VGPRs or four
+// fewer, and the encoders sit at occupancy boundaries.
+//
+// TableModel: one table for every symbol, cum[0..=257] in LDS.  The two table reads of a symbol are one ds_read2_b32.
+struct TableModel {
+    const uint32_t *tab;
+    __device__ __forceinline__ uint32_t total() const { return tab[kStaticEntries - 1]; }
+    __device__ __forceinline__ uint2    range(uint32_t s) const { return make_uint2(tab[s], tab[s + 1]); }
+    __device__ __forceinline__ uint32_t eof_lo() const { return tab[256]; }
+    // the s in 0..256 with cum[s] <= v < cum[s+1] (v < total)
+    __device__ __forceinline__ bool find(uint32_t v, uint32_t &s) const
+    {
+        uint32_t r = 0;
+#pragma unroll
+        for (int b = 8; b >= 0; b--) {
+            const uint32_t t = r | (1u << b);
+            if (t <= 256u && tab[t] <= v)
+                r = t;
+        }
+        s = r;
+        return r == 256u;
+    }
+    __device__ __forceinline__ void advance(uint32_t) {}
+};
+
 // Sixteen data symbols straight-line, all 64 lanes active, stores unchecked (the caller has
 // checked the chunk's budget): encode_symbol_spec as in the adaptive coder wave, with the same
 // "redo the stretch from the saved state with the general encode_symbol if any lane needed more
-// than one 32-bit append" rule.  The two table reads of a symbol are one ds_read2_b32.
-template <bool FIXUP, bool CB32>
-__device__ __forceinline__ void static_chunk(EncState &S, const uint32_t *tab, const uint4 cur, uint32_t c, double rc,
-                                             uint32_t sh, uint8_t *wdst)
+// than one 32-bit append" rule.
+template <bool FIXUP, bool CB32, class Model>
+__device__ __forceinline__ void static_chunk(EncState &S, Model &m, const uint4 cur, uint32_t c, double rc, uint32_t sh, uint8_t *wdst)
 {
     const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
     const EncState S0   = S;
+    const Model    m0   = m;
     SpecCarry      C    = spec_begin(S);
     uint32_t       mx   = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-        const uint32_t m = encode_symbol_spec<FIXUP, CB32>(S, C, tab[s], tab[s + 1], c, rc, sh, wdst);
-        mx               = m > mx ? m : mx;
+        const uint2    r = m.range(s);
+        const uint32_t n = encode_symbol_spec<FIXUP, CB32>(S, C, r.x, r.y, c, rc, sh, wdst);
+        mx               = n > mx ? n : mx;
+        m.advance(s);
     }
     spec_end(S, C);
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx > 32u) != 0, 0)) {
         S = S0;
+        m = m0;
 #pragma unroll 1
         for (int i = 0; i < 16; i++) {
             const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-            encode_symbol<FIXUP>(S, tab[s], tab[s + 1], c, rc, sh, false, wdst, 0xFFFFFFFFu);
+            const uint2    r = m.range(s);
+            encode_symbol<FIXUP>(S, r.x, r.y, c, rc, sh, false, wdst, 0xFFFFFFFFu);
+            m.advance(s);
         }
     }
 }
@@ -89,13 +124,13 @@ __device__ __forceinline__ void static_chunk(EncState &S, const uint32_t *tab, c
 template <bool SOLO>
 __device__ __forceinline__ void claim_the_simd();
 
-// The coder wave: lane l codes block blk0 + l * stride under the table in LDS (blk0 < nblocks).  stride 1 is the one-table
-// kernel below; the E-table kernels (redux_plane_static.hpp) pass stride E, so that a wave's 64 blocks share a table.
-template <bool FIXUP, bool CB32>
-__device__ __forceinline__ void static_encode_body(const StaticEncCore &a, const uint32_t *tab, const uint64_t blk0,
-                                                   const uint32_t stride = 1)
+// The coder wave: lane l of 64 codes block blk0 + l * stride under its model m, fresh for the block (blk0 < nblocks).
+// stride 1 is the one-table kernel below and the context kernels (redux_context_static.hpp); the E-table kernels
+// (redux_segment_static.hpp) pass stride E, so that a wave's 64 blocks share a table.
+template <bool FIXUP, bool CB32, class Model>
+__device__ __forceinline__ void static_encode_body(const StaticEncCore &a, Model m, const uint64_t blk0, const uint32_t lane,
+                                                   const uint32_t stride)
 {
-    const uint32_t lane = threadIdx.x;
     const uint64_t blk  = blk0 + (uint64_t)lane * stride;
     const bool     live = blk < a.nblocks;
     uint32_t       len  = 0;
@@ -110,7 +145,7 @@ __device__ __forceinline__ void static_encode_body(const StaticEncCore &a, const
     const uint32_t limit = off0 + a.slot_cap;
     const uint32_t maxlen = __builtin_amdgcn_readfirstlane(wave_max(live ? len : 0u));
     const uint32_t sh     = 32 - a.code_bits;
-    const uint32_t c      = tab[kStaticEntries - 1]; // total_frequency()
+    const uint32_t c      = m.total();
     const double   rc     = a.rc;
 
     EncState S;
@@ -133,19 +168,23 @@ __device__ __forceinline__ void static_encode_body(const StaticEncCore &a, const
 #pragma unroll 1
                 for (int i = 0; i < 16; i++) {
                     const uint32_t s = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                    encode_symbol<FIXUP>(S, tab[s], tab[s + 1], c, rc, sh, false, wdst, limit);
+                    const uint2    r = m.range(s);
+                    encode_symbol<FIXUP>(S, r.x, r.y, c, rc, sh, false, wdst, limit);
+                    m.advance(s);
                 }
             } else
-                static_chunk<FIXUP, CB32>(S, tab, cur, c, rc, sh, wdst);
+                static_chunk<FIXUP, CB32>(S, m, cur, c, rc, sh, wdst);
         }
     }
     for (; p <= maxlen; p++) {
         if (live && p < len) {
             const uint32_t s = src[p];
-            encode_symbol<FIXUP>(S, tab[s], tab[s + 1], c, rc, sh, false, wdst, limit); // get_frequency(s)
+            const uint2    r = m.range(s); // get_frequency(s)
+            encode_symbol<FIXUP>(S, r.x, r.y, c, rc, sh, false, wdst, limit);
+            m.advance(s);
         } else if (live && p == len) {
             // EOF symbol (codec.rs:108): [cum[256], total)
-            const uint32_t shifts = encode_symbol<FIXUP>(S, tab[256], c, c, rc, sh, true, wdst, limit);
+            const uint32_t shifts = encode_symbol<FIXUP>(S, m.eof_lo(), c, c, rc, sh, true, wdst, limit);
             const uint32_t size   = encode_finish(S, shifts, a.code_bits, off0, wdst, limit);
             a.sizes[blk]  = size;
             a.status[blk] = size > a.slot_cap ? REDUX_OUTPUT_TOO_SMALL : REDUX_OK;
@@ -161,7 +200,8 @@ __global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
     for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
         tab[i] = a.tab.cum[i];
     __syncthreads();
-    static_encode_body<FIXUP, CB32>(a, tab, (uint64_t)blockIdx.x * 64);
+    TableModel m{tab};
+    static_encode_body<FIXUP, CB32>(a, m, (uint64_t)blockIdx.x * 64, threadIdx.x, 1);
 }
 
 struct StaticDecCore {
@@ -181,9 +221,9 @@ struct StaticDecArgs : StaticDecCore {
     StaticTable tab;
 };
 
-// one lane, one block (blk; not live past nblocks), the table in LDS
-template <bool FIXUP>
-__device__ __forceinline__ void static_decode_body(const StaticDecCore &a, const uint32_t *tab, const uint64_t blk)
+// one lane, one block (blk; not live past nblocks) under its model m, fresh for the block
+template <bool FIXUP, class Model>
+__device__ __forceinline__ void static_decode_body(const StaticDecCore &a, Model m, const uint64_t blk)
 {
     const bool     live = blk < a.nblocks;
     const uint32_t cb = a.code_bits, sh = 32 - cb;
@@ -197,7 +237,7 @@ __device__ __forceinline__ void static_decode_body(const StaticDecCore &a, const
     const uint64_t stream_bits = size * 8;
     uint8_t       *dst         = a.out + (live ? blk : 0) * (uint64_t)a.block_size;
     const uint32_t capn        = a.block_size;
-    const uint32_t c           = tab[kStaticEntries - 1];
+    const uint32_t c           = m.total();
     const double   rc          = a.rc;
 
     BitIn B;
@@ -231,22 +271,16 @@ __device__ __forceinline__ void static_decode_body(const StaticDecCore &a, const
             else if ((uint64_t)r > (uint64_t)R1)
                 v++;
         }
-        // get_symbol: the s in 0..256 with cum[s] <= v < cum[s+1] (v < total)
-        uint32_t s = 0;
-#pragma unroll
-        for (int b = 8; b >= 0; b--) {
-            const uint32_t t = s | (1u << b);
-            if (t <= 256u && tab[t] <= v)
-                s = t;
-        }
-        if (s == 256u) { // codec.rs:136-138: EOF returns before any renormalisation
+        uint32_t s;
+        if (m.find(v, s)) { // get_symbol; codec.rs:136-138: EOF returns before any renormalisation
             done = true;
             continue;
         }
-        const uint32_t lo = tab[s], hi = tab[s + 1];
+        const uint2    r = m.range(s);
+        m.advance(s);
         const double   Y     = __builtin_fma((double)R1, rc, rc);
-        const uint32_t nlow  = low + (scale_div<FIXUP>(R1, Y, lo, c) << sh);
-        const uint32_t nhigh = low + (scale_div<FIXUP, true>(R1, Y, hi, c) << sh) - 1u;
+        const uint32_t nlow  = low + (scale_div<FIXUP>(R1, Y, r.x, c) << sh);
+        const uint32_t nhigh = low + (scale_div<FIXUP, true>(R1, Y, r.y, c) << sh) - 1u;
         const uint32_t xx    = nlow ^ nhigh;
         const uint32_t k     = xx ? (uint32_t)__builtin_clz(xx) : 32u;
         const uint32_t low2  = (uint32_t)((uint64_t)nlow << k);
@@ -300,7 +334,8 @@ __global__ void __launch_bounds__(64) k_decode_static(StaticDecArgs a)
     for (uint32_t i = threadIdx.x; i < kStaticEntries; i += 64)
         tab[i] = a.tab.cum[i];
     __syncthreads();
-    static_decode_body<FIXUP>(a, tab, (uint64_t)blockIdx.x * 64 + threadIdx.x);
+    TableModel m{tab};
+    static_decode_body<FIXUP>(a, m, (uint64_t)blockIdx.x * 64 + threadIdx.x);
 }
 
 // The static decoder in k_decode_lock's form (redux_decode.hpp, decode_lock_body<CB32, true>): all 64 lanes in

@@ -159,13 +159,13 @@ def test_every_kernel_instance(rx, lib):
                 cp = lib.Params(*params)
                 en = L.redux_plane_static_encode_kernel_name(C.byref(cp), total, n, B, E).decode()
                 dn = L.redux_plane_static_decode_kernel_name(C.byref(cp), total, nb, E).decode()
-                assert en.startswith("k_encode_plane_static<") and dn.startswith("k_decode_plane_static"), (en, dn)
+                assert en.startswith("k_encode_segment_static<") and dn.startswith("k_decode_segment_static"), (en, dn)  # (one segment)
                 # the instance is the one the one-table call picks for a launch of as many waves
                 waves = E * (((nb + E - 1) // E + 63) // 64)
                 ones = (C.c_uint32 * 258)(*([min(i, 256) * (total // 257) for i in range(257)] + [total]))
                 assert L.redux_static_table_check(C.byref(cp), ones) == lib.OK
-                assert en.replace("_plane_static", "_static") == L.redux_static_encode_kernel_name(C.byref(cp), ones, waves * 64 * B, B).decode()
-                assert dn.replace("_plane_static", "_static") == L.redux_static_decode_kernel_name(C.byref(cp), ones, waves * 64).decode()
+                assert en.replace("_segment_static", "_static") == L.redux_static_encode_kernel_name(C.byref(cp), ones, waves * 64 * B, B).decode()
+                assert dn.replace("_segment_static", "_static") == L.redux_static_decode_kernel_name(C.byref(cp), ones, waves * 64).decode()
                 assert ("fix-up" in en) == (total >= 1 << 17) and ("fix-up" in dn) == (total >= 1 << 17)
                 assert ("lut" in dn) == (total <= 1 << 16)
                 seen_enc.add(en)

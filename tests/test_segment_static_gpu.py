@@ -12,7 +12,7 @@ import pytest
 
 from conftest import ROOT
 from oracle import cbind as ox
-from test_plane_static_gpu import data_of, sp, to_dev
+from test_plane_static_gpu import data_of, device_counts as plane_device_counts, sp, to_dev
 from test_segment_static_cpu import mixed_bf16, nseg_of, segment_counts, segment_tables_ref
 from test_static_gpu import guarded, guards_intact, oracle_decode_raw
 
@@ -142,6 +142,44 @@ def test_one_segment_is_plane_static_and_static(rx, lib, E):
         assert torch.equal(s_offs, o_offs) and torch.equal(s_out[:end], o_out[:end])
 
 
+@pytest.mark.parametrize("B", [100, 4096])
+@pytest.mark.parametrize("E", [1, 2, 8])
+def test_one_segment_equals_plane_static_call_for_call(rx, lib, E, B):
+    """What lets plane-static run on the segment-static kernels: with one segment that holds every block, each segment call
+    gives what its plane call gives (counts, tables, offsets, statuses, stream bytes), and each decoder reads the other's
+    streams.  Once under the lookup decoder (total 2^16; its waves share a segment only if k % 4 == 0) and once under the
+    lock-step one (total 2^16 + 1)."""
+    import torch
+    L = lib.lib()
+    nb = 64 * E + 3
+    n = nb * B - 3
+    x = data_of("bf16", n, rx, seed=E)
+    d_in = to_dev(torch, x)
+    d_x = rx.planes(d_in, E, B) if E > 1 else d_in
+    cp = lib.Params(*P)
+    for total, k, form in ((1 << 16, 4, "_lut<"), ((1 << 16) + 1, 2, "_lock<")):
+        G = 64 * E * k
+        assert G >= nb
+        assert form in L.redux_segment_static_decode_kernel_name(C.byref(cp), total, nb, E, G).decode()
+        assert np.array_equal(device_counts(torch, lib, d_x, B, E, G), plane_device_counts(torch, lib, d_x, B, E))
+        old = rx.DevicePlaneStaticCoder.from_data(d_in, P, E, B, n, total=total)
+        cums = rx.segment_static_tables(d_in, E, B, G, P, total)
+        assert np.array_equal(cums, old.tables())
+        seg = rx.DeviceSegmentStaticCoder(P, E, B, n, G, total)
+        seg.set_tables(cums)
+        s_out, s_offs, s_st, s_sum = seg.encode(d_in)
+        o_out, o_offs, o_st, o_sum = old.encode(d_in)
+        torch.cuda.synchronize()
+        end = int(o_offs[-1])
+        assert torch.equal(s_offs, o_offs) and torch.equal(s_st, o_st) and s_sum.tolist() == o_sum.tolist() == [0, 0]
+        assert torch.equal(s_out[:end], o_out[:end])
+        for dec, (streams, offs) in ((seg, (o_out, o_offs)), (old, (s_out, s_offs))):
+            back, sizes, dst, dsum = dec.decode(streams[:end], offs, n)
+            torch.cuda.synchronize()
+            assert dsum.tolist() == [0, 0] and not bool(dst.any())
+            assert np.array_equal(back.cpu().numpy(), x), (E, B, total)
+
+
 # ---- every kernel instance -------------------------------------------------------------------------------------------
 def test_every_kernel_instance(rx, lib):
     import torch
@@ -159,7 +197,7 @@ def test_every_kernel_instance(rx, lib):
                     en = L.redux_segment_static_encode_kernel_name(C.byref(cp), total, n, B, E, G).decode()
                     dn = L.redux_segment_static_decode_kernel_name(C.byref(cp), total, nb, E, G).decode()
                     assert en.startswith("k_encode_segment_static<") and dn.startswith("k_decode_segment_static"), (en, dn)
-                    assert en.replace("_segment_static", "_plane_static") == L.redux_plane_static_encode_kernel_name(C.byref(cp), total, n, B, E).decode()
+                    assert en == L.redux_plane_static_encode_kernel_name(C.byref(cp), total, n, B, E).decode()
                     assert ("fix-up" in en) == (total >= 1 << 17) and ("fix-up" in dn) == (total >= 1 << 17)
                     # the lookup decoder's waves share a segment: 8 waves need k % 8 == 0, 4 waves k % 4 == 0
                     solo = nb < 4 * cus * 64

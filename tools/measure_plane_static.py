@@ -3,8 +3,9 @@
 
 Device-event times, medians of `--reps` runs, two alternating rounds of every comparison, device-resident blocks of 64 KiB:
   1. k_plane_hist (E = 2, 4) against k_byte_hist on the same x' buffer;
-  2. plane-static encode / decode (bf16 E = 2, fp32 E = 4) against (a) the one-table static calls on the same x' and
-     (b) the adaptive planes calls on the same input; compressed_over_input of each;
+  2. plane-static encode / decode (bf16 E = 2, fp32 E = 4: the k_*_segment_static* kernels with a single segment, as
+     the printed kernel names say) against (a) the one-table static calls on the same x' and (b) the adaptive planes
+     calls on the same input; compressed_over_input of each;
   3. semi-static end to end (layout + histogram + tables + encode) against adaptive planes encode;
   4. E = 1 through the one-table entry points (the existing static path).
 

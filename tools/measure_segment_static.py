@@ -5,10 +5,10 @@
 Shape: `blocks` x `block-size` bytes of mixed-sigma bf16 (E = 2: tensors of 2^19 to 2^22 elements, sigma log-uniform in
 [0.002, 0.5], the high halves of fp32) and of fp32 with the same sigmas (E = 4).  Timing: device events, medians of 5, two
 alternating rounds (every row is timed once per round, the rows in the same order; both medians are printed).  Rows: ratio,
-encode and decode GB/s for k in 1, 2, 4, 8 with the decoder instance each k selected; plane-static and the adaptive planes
-path on the same data; k_segment_hist against k_plane_hist on the same bytes; k_static_tables for the full table set;
-build_encode_dev end to end.  Last: the k0 the default rule picks (the smallest k whose decode rate is at least the adaptive
-planes decoder's)."""
+encode and decode GB/s for k in 1, 2, 4, 8 with the decoder instance each k selected; plane-static (the same kernels with a
+single segment) and the adaptive planes path on the same data; k_segment_hist against k_plane_hist on the same bytes;
+k_static_tables for the full table set; build_encode_dev end to end.  Last: the k0 the default rule picks (the smallest k
+whose decode rate is at least the adaptive planes decoder's)."""
 import argparse
 import ctypes as C
 import os
