@@ -471,35 +471,6 @@ static host::EncodeCoder adaptive_encoder(const redux_params *p, uint32_t block_
             }};
 }
 
-// the transformed copy of a chunk goes in front of the adaptive coder's workspace (redux_encode_planes_dev); a chunk is whole
-// 64-block waves, so whole frames of the layout for every element size that divides 64
-static host::EncodeCoder planes_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
-{
-    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
-    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
-                plain.size(max_in, several, ws, bound);
-                ws += planes_copy_bytes(max_in);
-            },
-            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return redux_encode_planes_dev(p, s.d_in.p, len, block_size, element_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
-                                               s.d_sum.p, ws, ws_bytes, st);
-            }};
-}
-
-// the delta filter in front of the layout (redux_encode_delta_dev): the transformed copy for every element size, 1 included
-static host::EncodeCoder delta_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
-{
-    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
-    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
-                plain.size(max_in, several, ws, bound);
-                ws += planes_copy_bytes(max_in);
-            },
-            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return redux_encode_delta_dev(p, s.d_in.p, len, block_size, element_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
-                                              s.d_sum.p, ws, ws_bytes, st);
-            }};
-}
-
 // the static coder: its own workspace and bound for the largest chunk (its streams do not depend on either)
 static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
@@ -513,21 +484,39 @@ static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *c
             }};
 }
 
-// the byte-plane layout (redux_planes.hpp): the fast kernel over the full frames when it applies, the byte kernel for the rest
+// ---- the transforms in front of a coder (redux_planes.hpp, redux_delta.hpp) -------------------------------------------
+// What the launches of the byte-plane layout and of the delta filter share: the arguments and the split of the bytes.  The
+// fast kernels take the `nfull` full frames when block size and pointers are 16-byte multiples (nfull = 0 otherwise, and
+// a.groups stays 0); the byte kernels take everything from `rest` on (a.first of their launch).
+struct PlanesSplit {
+    PlanesArgs a;
+    uint64_t   nfull, rest;
+};
+
+static PlanesSplit planes_split(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t E)
+{
+    PlanesSplit f;
+    f.a.src          = (const uint8_t *)d_src;
+    f.a.dst          = (uint8_t *)d_dst;
+    f.a.block_size   = block_size;
+    f.a.frame_groups = block_size / 16;
+    f.a.len          = len;
+    f.a.first        = 0;
+    f.a.groups       = 0;
+    const uint64_t frame = (uint64_t)E * block_size;
+    f.nfull = block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 ? len / frame : 0;
+    f.a.groups = f.nfull * f.a.frame_groups;
+    f.rest     = f.nfull * frame;
+    return f;
+}
+
+// the byte-plane layout: one workgroup per 256 groups of the full frames, the byte kernel for the rest
 template <int E>
 static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
 {
-    PlanesArgs a;
-    a.src          = (const uint8_t *)d_src;
-    a.dst          = (uint8_t *)d_dst;
-    a.block_size   = block_size;
-    a.frame_groups = block_size / 16;
-    a.len          = len;
-    a.first        = 0;
-    a.groups       = 0;
-    const uint64_t frame = (uint64_t)E * block_size, nfull = len / frame;
-    if (block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 && nfull) {
-        a.groups = nfull * a.frame_groups;
+    PlanesSplit f = planes_split(d_src, d_dst, len, block_size, E);
+    PlanesArgs &a = f.a;
+    if (f.nfull) {
         const uint64_t wgs = (a.groups + 255) / 256;
         if (wgs > 0x7FFFFFFFull)
             return REDUX_UNSUPPORTED;
@@ -535,8 +524,8 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
             k_planes<E, true><<<(uint32_t)wgs, 256, 0, s>>>(a);
         else
             k_planes<E, false><<<(uint32_t)wgs, 256, 0, s>>>(a);
-        a.first = nfull * frame;
     }
+    a.first = f.rest;
     if (a.first < len) { // the short last frame, or everything the fast kernel cannot take
         const uint64_t n = len - a.first, wgs = (n + 255) / 256;
         const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
@@ -549,33 +538,25 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
     return REDUX_OK;
 }
 
-// the delta filter (redux_delta.hpp): the fused kernels over the full frames when they apply, the element kernels for the rest
+// the delta filter: forward as the layout; the inverse a workgroup per frame (a frame's running sum), at most 2^20
 template <int E>
 static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
 {
-    PlanesArgs a;
-    a.src          = (const uint8_t *)d_src;
-    a.dst          = (uint8_t *)d_dst;
-    a.block_size   = block_size;
-    a.frame_groups = block_size / 16;
-    a.len          = len;
-    a.first        = 0;
-    a.groups       = 0;
-    const uint64_t frame = (uint64_t)E * block_size, nfull = len / frame;
-    if (block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 && nfull) {
-        a.groups = nfull * a.frame_groups;
-        if (inverse) { // a workgroup per frame
-            k_delta_unplanes<E><<<(uint32_t)(nfull < (1u << 20) ? nfull : (1u << 20)), 256, 0, s>>>(a);
+    PlanesSplit f = planes_split(d_src, d_dst, len, block_size, E);
+    PlanesArgs &a = f.a;
+    if (f.nfull) {
+        if (inverse) {
+            k_delta_unplanes<E><<<(uint32_t)(f.nfull < (1u << 20) ? f.nfull : (1u << 20)), 256, 0, s>>>(a);
         } else {
             const uint64_t wgs = (a.groups + 255) / 256;
             if (wgs > 0x7FFFFFFFull)
                 return REDUX_UNSUPPORTED;
             k_delta_planes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
         }
-        a.first = nfull * frame;
     }
+    a.first = f.rest;
     if (a.first < len) { // the short last frame, or everything the fused kernels cannot take
-        const uint64_t n = len - a.first;
+        const uint64_t n = len - a.first, frame = (uint64_t)E * block_size;
         if (inverse) {
             const uint64_t nframes = (n + frame - 1) / frame;
             k_delta_unplanes_bytes<E><<<(uint32_t)(nframes < (1u << 20) ? nframes : (1u << 20)), 256, 0, s>>>(a);
@@ -585,6 +566,102 @@ static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t b
         }
     }
     HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// redux_planes_dev and redux_delta_planes_dev: the checks, then the transform's launch for the element size
+static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+                         int inverse, void *stream)
+{
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place: the transform reads bytes another thread writes)
+        return REDUX_INVALID_INPUT;
+    hipStream_t s = (hipStream_t)stream;
+    const bool  inv = inverse != 0;
+    if (delta)
+        switch (element_size) {
+        case 1: return launch_delta<1>(d_src, d_dst, len, block_size, inv, s);
+        case 2: return launch_delta<2>(d_src, d_dst, len, block_size, inv, s);
+        case 4: return launch_delta<4>(d_src, d_dst, len, block_size, inv, s);
+        default: return launch_delta<8>(d_src, d_dst, len, block_size, inv, s);
+        }
+    switch (element_size) {
+    case 2: return launch_planes<2>(d_src, d_dst, len, block_size, inv, s);
+    case 4: return launch_planes<4>(d_src, d_dst, len, block_size, inv, s);
+    case 8: return launch_planes<8>(d_src, d_dst, len, block_size, inv, s);
+    default: HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s)); return REDUX_OK;
+    }
+}
+
+// ---- the layout stage of the layered calls ---------------------------------------------------------------------------
+// What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with the delta filter
+// in front of it or not.  The layout of single bytes is the identity; the filter over single bytes is not.
+struct Layout {
+    uint32_t E;
+    bool     delta;
+    bool     identity() const { return !delta && E == 1; }
+    // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
+    uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
+    int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
+    {
+        return transform_dev(delta, d_src, d_dst, len, block_size, E, 0, stream);
+    }
+    int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
+    {
+        return transform_dev(delta, d_src, d_dst, len, block_size, E, 1, stream);
+    }
+};
+
+// Encode side: the transformed copy x' of d_in goes to the front of the workspace (x' = d_in for the identity) and the coder
+// gets x' and what is left of the workspace behind the copy.
+struct Staged {
+    const void *x;
+    uint8_t    *ws;
+    uint64_t    ws_bytes;
+};
+
+static int layout_stage(Layout L, const void *d_in, uint64_t in_len, uint32_t block_size, void *d_workspace, uint64_t workspace_bytes,
+                        void *stream, Staged &o)
+{
+    const uint64_t copy = L.copy_bytes(in_len);
+    if (workspace_bytes < copy)
+        return REDUX_OUTPUT_TOO_SMALL;
+    o = {L.identity() ? d_in : d_workspace, (uint8_t *)d_workspace + copy, workspace_bytes - copy};
+    return L.identity() ? REDUX_OK : L.forward(d_in, d_workspace, in_len, block_size, stream);
+}
+
+// Decode side: the blocks were decoded to the plane buffer d_t at the front of the workspace, block_size bytes of room each,
+// so that a damaged stream writes nothing outside it (d_t null: to d_out in place, where the layout is the identity).  Their
+// sizes are checked against the layout of out_len bytes, the inverse writes d_out[0 .. out_len) and nothing else, and the
+// summary is taken.  Who writes d_summary differs by caller: the adaptive decoders have begun it and k_planes_sizes adds to
+// it (InSizes); the static decoders leave it to one k_summarize at the end (Summarize); the stored call zeroes it first
+// (ZeroSummarize).
+enum class TailSummary { InSizes, Summarize, ZeroSummarize };
+
+static int layout_decode_tail(Layout L, const void *d_t, void *d_out, uint64_t out_len, uint32_t block_size, void *d_out_sizes,
+                              void *d_block_status, void *d_summary, TailSummary how, void *stream)
+{
+    hipStream_t    s       = (hipStream_t)stream;
+    const uint64_t nblocks = redux_block_count(out_len, block_size), wgs = (nblocks + 255) / 256;
+    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
+                                                                        how == TailSummary::InSizes ? (int32_t *)d_summary : nullptr,
+                                                                        nblocks, out_len, block_size);
+    HIP_TRY(hipGetLastError());
+    if (d_t) {
+        const int st = L.inverse(d_t, d_out, out_len, block_size, stream);
+        if (st != REDUX_OK)
+            return st;
+    }
+    if (d_summary && how != TailSummary::InSizes) {
+        if (how == TailSummary::ZeroSummarize)
+            HIP_TRY(hipMemsetAsync(d_summary, 0, 8, s));
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
+        HIP_TRY(hipGetLastError());
+    }
     return REDUX_OK;
 }
 
@@ -1452,28 +1529,6 @@ static host::DecodeCoder adaptive_decoder(const redux_params *p, uint32_t block_
             }};
 }
 
-// decodes exactly the chunk's share of out_len (redux_decode_planes_dev)
-static host::DecodeCoder planes_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
-{
-    return {[=](uint64_t cb) { return redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
-            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return redux_decode_planes_dev(p, s.d_in.p, s.d_off.p, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
-                                               s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
-            },
-            true};
-}
-
-// the same with the delta filter undone behind the layout (redux_decode_delta_dev)
-static host::DecodeCoder delta_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size)
-{
-    return {[=](uint64_t cb) { return redux_decode_delta_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
-            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return redux_decode_delta_dev(p, s.d_in.p, s.d_off.p, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
-                                              s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
-            },
-            true};
-}
-
 // the static decoder takes no workspace
 static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
@@ -1586,12 +1641,18 @@ static StaticDecKernel pick_static_decode_kernel(const redux_params *p, uint32_t
     return solo ? (cb32 ? StaticDecKernel::LockCb32Solo : StaticDecKernel::LockSolo) : (cb32 ? StaticDecKernel::LockCb32 : StaticDecKernel::Lock);
 }
 
+// 64 slots / blocks of one wave, E apart (E = 1: the one-table and context-static coders), within a 32-bit lane offset
+static bool static_lanes_fit(const Geometry &g, uint32_t block_size, uint32_t E)
+{
+    return 64ull * E * g.slot_bytes < (1ull << 32) && 64ull * E * block_size < (1ull << 32);
+}
+
 const char *redux_static_encode_kernel_name(const redux_params *p, const uint32_t *cum, uint64_t in_len, uint32_t block_size)
 {
     if (static_check(p, cum) != REDUX_OK || block_size == 0)
         return "";
     const Geometry g = geometry(p, in_len, block_size, true);
-    if (64ull * g.slot_bytes >= (1ull << 32) || 64ull * block_size >= (1ull << 32)) // as redux_static_encode_blocks_dev
+    if (!static_lanes_fit(g, block_size, 1)) // as redux_static_encode_blocks_dev
         return "";
     switch (pick_static_encode_kernel(p, cum[kStaticEntries - 1], g.nblocks)) {
     case StaticEncKernel::Fixup: return "k_encode_static<true, false> (total >= 2^17: quotient fix-up)";
@@ -1630,6 +1691,63 @@ static double static_rc(uint32_t total)
     return r;
 }
 
+// what every static encoder kernel takes: x' in blocks -> linear slots and sizes in the workspace at ws
+static StaticEncCore static_enc_args(const Geometry &g, const redux_params *p, const void *d_x, uint64_t in_len, uint32_t block_size,
+                                     uint8_t *ws, void *d_block_status, uint32_t total)
+{
+    StaticEncCore c;
+    c.in         = (const uint8_t *)d_x;
+    c.in_len     = in_len;
+    c.nblocks    = g.nblocks;
+    c.slots      = ws + g.off_slots;
+    c.slot_bytes = g.slot_bytes;
+    c.sizes      = (uint32_t *)(ws + g.off_sizes);
+    c.status     = (int32_t *)d_block_status;
+    c.rc         = static_rc(total);
+    c.block_size = block_size;
+    c.slot_cap   = g.slot_cap;
+    c.code_bits  = p->code_bits;
+    c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    return c;
+}
+
+// what every per-lane static decoder kernel takes: nblocks streams -> block b at d_out + b * block_size
+static StaticDecCore static_dec_args(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t nblocks,
+                                     uint32_t block_size, void *d_out, void *d_out_sizes, void *d_block_status, uint32_t total)
+{
+    StaticDecCore c;
+    c.in         = (const uint8_t *)d_in;
+    c.in_offsets = (const uint64_t *)d_in_offsets;
+    c.nblocks    = nblocks;
+    c.out        = (uint8_t *)d_out;
+    c.out_sizes  = (uint32_t *)d_out_sizes;
+    c.status     = (int32_t *)d_block_status;
+    c.rc         = static_rc(total);
+    c.block_size = block_size;
+    c.code_bits  = p->code_bits;
+    c.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    return c;
+}
+
+// the same for the lock-step and lookup decoders, which take the adaptive decoders' DecArgs (no reciprocal table, no freeze,
+// no block table; aligned4 = 2 where output and block size are 16-byte multiples) and c.rc next to them
+static DecArgs lock_args_from(const StaticDecCore &c)
+{
+    DecArgs d;
+    memset(&d, 0, sizeof d);
+    d.in         = c.in;
+    d.in_offsets = c.in_offsets;
+    d.nblocks    = c.nblocks;
+    d.out        = c.out;
+    d.out_sizes  = c.out_sizes;
+    d.status     = c.status;
+    d.block_size = c.block_size;
+    d.nfreeze    = 0xFFFFFFFFu;
+    d.code_bits  = c.code_bits;
+    d.aligned4   = c.aligned4 && (((uintptr_t)c.out) & 15) == 0 && (c.block_size & 15) == 0 ? 2 : c.aligned4;
+    return d;
+}
+
 int redux_static_table_check(const redux_params *p, const uint32_t *cum) { return static_check(p, cum); }
 
 uint64_t redux_static_encode_bound(const redux_params *p, uint64_t in_len, uint32_t block_size)
@@ -1662,24 +1780,13 @@ int redux_static_encode_blocks_dev(const redux_params *p, const uint32_t *cum, c
     const Geometry g = geometry(p, in_len, block_size, true);
     if (workspace_bytes < g.total)
         return REDUX_OUTPUT_TOO_SMALL;
-    if (64ull * g.slot_bytes >= (1ull << 32) || 64ull * block_size >= (1ull << 32)) // 64 slots / blocks within a 32-bit lane offset
+    if (!static_lanes_fit(g, block_size, 1))
         return REDUX_UNSUPPORTED;
     hipStream_t s  = (hipStream_t)stream;
     uint8_t    *ws = (uint8_t *)d_workspace;
     HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
     StaticEncArgs a;
-    a.in         = (const uint8_t *)d_in;
-    a.in_len     = in_len;
-    a.nblocks    = g.nblocks;
-    a.slots      = ws + g.off_slots;
-    a.slot_bytes = g.slot_bytes;
-    a.sizes      = (uint32_t *)(ws + g.off_sizes);
-    a.status     = (int32_t *)d_block_status;
-    a.rc         = static_rc(cum[kStaticEntries - 1]);
-    a.block_size = block_size;
-    a.slot_cap   = g.slot_cap;
-    a.code_bits  = p->code_bits;
-    a.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    static_cast<StaticEncCore &>(a) = static_enc_args(g, p, d_in, in_len, block_size, ws, d_block_status, cum[kStaticEntries - 1]);
     memcpy(a.tab.cum, cum, sizeof a.tab.cum);
     const uint32_t grid = (uint32_t)((g.nblocks + 63) / 64);
     switch (pick_static_encode_kernel(p, cum[kStaticEntries - 1], g.nblocks)) { // solo as k_decode_static_lock: one wave per SIMD, not two on some
@@ -1708,16 +1815,8 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
         return REDUX_OUTPUT_TOO_SMALL;
     hipStream_t   s = (hipStream_t)stream;
     StaticDecArgs a;
-    a.in         = (const uint8_t *)d_in;
-    a.in_offsets = (const uint64_t *)d_in_offsets;
-    a.nblocks    = nblocks;
-    a.out        = (uint8_t *)d_out;
-    a.out_sizes  = (uint32_t *)d_out_sizes;
-    a.status     = (int32_t *)d_block_status;
-    a.rc         = static_rc(cum[kStaticEntries - 1]);
-    a.block_size = block_size;
-    a.code_bits  = p->code_bits;
-    a.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    static_cast<StaticDecCore &>(a) = static_dec_args(p, d_in, d_in_offsets, nblocks, block_size, d_out, d_out_sizes, d_block_status,
+                                                      cum[kStaticEntries - 1]);
     memcpy(a.tab.cum, cum, sizeof a.tab.cum);
     const uint32_t        grid = (uint32_t)((nblocks + 63) / 64);
     const StaticDecKernel k    = pick_static_decode_kernel(p, cum[kStaticEntries - 1], nblocks);
@@ -1726,23 +1825,9 @@ int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, c
     else {
         StaticLockArgs la;
         memset(&la, 0, sizeof la);
-        la.d.in         = a.in;
-        la.d.in_offsets = a.in_offsets;
-        la.d.nblocks    = nblocks;
-        la.d.out        = a.out;
-        la.d.out_sizes  = a.out_sizes;
-        la.d.status     = a.status;
-        la.d.rc         = nullptr;
-        la.d.block_size = block_size;
-        la.d.nfreeze    = 0xFFFFFFFFu;
-        la.d.code_bits  = p->code_bits;
-        la.d.aligned4   = a.aligned4;
-        if (a.aligned4 && (((uintptr_t)d_out) & 15) == 0 && (block_size & 15) == 0)
-            la.d.aligned4 = 2;
-        la.d.in_used    = nullptr;
-        la.d.table      = nullptr;
-        la.rc           = a.rc;
-        la.tab          = a.tab;
+        la.d   = lock_args_from(a);
+        la.rc  = a.rc;
+        la.tab = a.tab;
         switch (k) { // solo: at most one wave per SIMD, to keep the dispatcher from doubling them up
         case StaticDecKernel::LutCb32Solo: k_decode_static_lut<true, 4><<<(grid + 3) / 4, 256, 0, s>>>(la); break;
         case StaticDecKernel::LutSolo: k_decode_static_lut<false, 4><<<(grid + 3) / 4, 256, 0, s>>>(la); break;
@@ -1922,20 +2007,7 @@ int redux_planes_check(uint32_t element_size)
 int redux_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
                      void *stream)
 {
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
-        return REDUX_INVALID_INPUT;
-    if (len == 0)
-        return REDUX_OK;
-    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
-    if (s0 < d0 + len && d0 < s0 + len) // (not in place: the transform reads bytes another thread writes)
-        return REDUX_INVALID_INPUT;
-    hipStream_t s = (hipStream_t)stream;
-    switch (element_size) {
-    case 2: return launch_planes<2>(d_src, d_dst, len, block_size, inverse != 0, s);
-    case 4: return launch_planes<4>(d_src, d_dst, len, block_size, inverse != 0, s);
-    case 8: return launch_planes<8>(d_src, d_dst, len, block_size, inverse != 0, s);
-    default: HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s)); return REDUX_OK;
-    }
+    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream);
 }
 
 uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
@@ -1943,9 +2015,7 @@ uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_
     if (redux_planes_check(element_size) != REDUX_OK)
         return 0;
     const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    if (ws == 0 || element_size == 1) // (E = 1: the plain call, on the caller's buffer)
-        return ws;
-    return planes_copy_bytes(in_len) + ws;
+    return ws ? Layout{element_size, false}.copy_bytes(in_len) + ws : 0; // (E = 1: the plain call, on the caller's buffer)
 }
 
 uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -1957,56 +2027,86 @@ uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out
     return ws ? planes_copy_bytes(nblocks * (uint64_t)block_size) + ws : 0;
 }
 
-// the transformed copy at the front of the workspace, the plain encoder behind it with what is left
-int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
-                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+// the layered adaptive calls: the layout stage (layout_stage, layout_decode_tail), the plain coder behind it
+static int encode_layout_dev(Layout L, const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, void *d_out,
+                             uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
+                             uint64_t workspace_bytes, void *stream)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
+    if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
         return REDUX_INVALID_INPUT;
-    if (element_size == 1)
-        return redux_encode_blocks_dev(p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary,
-                                       d_workspace, workspace_bytes, stream);
-    const uint64_t copy = planes_copy_bytes(in_len);
-    if (workspace_bytes < copy)
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t *t = (uint8_t *)d_workspace;
-    if ((st = redux_planes_dev(d_in, t, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+    Staged x;
+    if ((st = layout_stage(L, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x)) != REDUX_OK)
         return st;
-    return redux_encode_blocks_dev(p, t, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, t + copy,
-                                   workspace_bytes - copy, stream);
+    return redux_encode_blocks_dev(p, x.x, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, x.ws,
+                                   x.ws_bytes, stream);
 }
 
-// the blocks decode into a plane buffer at the front of the workspace (block_size bytes of room each, so a damaged stream
-// writes nothing outside it); their sizes are checked against the layout; the inverse transform writes d_out[0 .. out_len)
-int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
-                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
-                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+// (the plane buffer for every element size, 1 included: the decoders never write a damaged stream's bytes to d_out)
+static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                             uint32_t block_size, void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary,
+                             void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes ||
-        !d_block_status || (out_len && !d_out))
+    if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status ||
+        (out_len && !d_out))
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
     const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
-    if (workspace_bytes < redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size))
+    if (workspace_bytes < redux_decode_planes_workspace_bytes(p, out_len, block_size, L.E))
         return REDUX_OUTPUT_TOO_SMALL;
     uint8_t *t = (uint8_t *)d_workspace;
     st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
                                 d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr);
     if (st != REDUX_OK)
         return st;
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
-                                                                        (int32_t *)d_summary, nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    return redux_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream);
+    return layout_decode_tail(L, t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary, TailSummary::InSizes, stream);
+}
+
+int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(Layout{element_size, false}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
+                             d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(Layout{element_size, false}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+// The coders of the chunked host calls (redux_host.hpp).  The transformed copy of a chunk goes in front of the adaptive
+// coder's workspace; a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64.
+static host::EncodeCoder layout_encoder(const redux_params *p, uint32_t block_size, Layout L)
+{
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                plain.size(max_in, several, ws, bound);
+                ws += L.copy_bytes(max_in);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return encode_layout_dev(L, p, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p, s.d_sum.p, ws,
+                                         ws_bytes, st);
+            }};
+}
+
+// decodes exactly the chunk's share of out_len
+static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_size, Layout L)
+{
+    return {[=](uint64_t cb) { return redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, L.E); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return decode_layout_dev(L, p, s.d_in.p, s.d_off.p, out_bytes, block_size, s.d_out.p, s.d_sz.p, s.d_st.p, s.d_sum.p,
+                                         ws, ws_bytes, st);
+            },
+            true};
 }
 
 int redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
@@ -2018,7 +2118,7 @@ int redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uin
         return st;
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
-    const host::EncodeCoder coder = element_size > 1 ? planes_encoder(p, block_size, element_size) : adaptive_encoder(p, block_size);
+    const host::EncodeCoder coder = element_size > 1 ? layout_encoder(p, block_size, Layout{element_size, false}) : adaptive_encoder(p, block_size);
     return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc); // redux_host.hpp
 }
 
@@ -2036,7 +2136,7 @@ int redux_decode_blocks_planes_crc(const redux_params *p, const uint8_t *in, con
     if (st == REDUX_OK && redux_planes_check(element_size) != REDUX_OK)
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, planes_decoder(p, block_size, element_size), block_crc);
+                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, false}), block_crc);
 }
 
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
@@ -2051,20 +2151,7 @@ int redux_delta_check(uint32_t element_size) { return redux_planes_check(element
 int redux_delta_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
                            void *stream)
 {
-    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
-        return REDUX_INVALID_INPUT;
-    if (len == 0)
-        return REDUX_OK;
-    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
-    if (s0 < d0 + len && d0 < s0 + len) // (not in place, as redux_planes_dev)
-        return REDUX_INVALID_INPUT;
-    hipStream_t s = (hipStream_t)stream;
-    switch (element_size) {
-    case 1: return launch_delta<1>(d_src, d_dst, len, block_size, inverse != 0, s);
-    case 2: return launch_delta<2>(d_src, d_dst, len, block_size, inverse != 0, s);
-    case 4: return launch_delta<4>(d_src, d_dst, len, block_size, inverse != 0, s);
-    default: return launch_delta<8>(d_src, d_dst, len, block_size, inverse != 0, s);
-    }
+    return transform_dev(true, d_src, d_dst, len, block_size, element_size, inverse, stream);
 }
 
 // (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
@@ -2073,7 +2160,7 @@ uint64_t redux_encode_delta_workspace_bytes(const redux_params *p, uint64_t in_l
     if (redux_delta_check(element_size) != REDUX_OK)
         return 0;
     const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? planes_copy_bytes(in_len) + ws : 0;
+    return ws ? Layout{element_size, true}.copy_bytes(in_len) + ws : 0;
 }
 
 uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2081,53 +2168,21 @@ uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_
     return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
 }
 
-// redux_encode_planes_dev's procedure with the filter's transform
+// (a frame's running sum never leaves the frame, so the inverse writes d_out[0 .. out_len) and nothing else)
 int redux_encode_delta_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
                            void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
-        return REDUX_INVALID_INPUT;
-    const uint64_t copy = planes_copy_bytes(in_len);
-    if (workspace_bytes < copy)
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t *t = (uint8_t *)d_workspace;
-    if ((st = redux_delta_planes_dev(d_in, t, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
-        return st;
-    return redux_encode_blocks_dev(p, t, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, t + copy,
-                                   workspace_bytes - copy, stream);
+    return encode_layout_dev(Layout{element_size, true}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
+                             d_summary, d_workspace, workspace_bytes, stream);
 }
 
-// redux_decode_planes_dev's procedure: the blocks decode into the plane buffer, k_planes_sizes checks their sizes, the
-// inverse writes d_out[0 .. out_len) and nothing else.  A frame's running sum never leaves the frame.
 int redux_decode_delta_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes ||
-        !d_block_status || (out_len && !d_out))
-        return REDUX_INVALID_INPUT;
-    const uint64_t nblocks = redux_block_count(out_len, block_size);
-    const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
-    if (workspace_bytes < redux_decode_delta_workspace_bytes(p, out_len, block_size, element_size))
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t *t = (uint8_t *)d_workspace;
-    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
-                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr);
-    if (st != REDUX_OK)
-        return st;
-    hipStream_t s = (hipStream_t)stream;
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
-                                                                        (int32_t *)d_summary, nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    return redux_delta_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream);
+    return decode_layout_dev(Layout{element_size, true}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_encode_blocks_delta(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
@@ -2139,7 +2194,7 @@ int redux_encode_blocks_delta(const redux_params *p, const uint8_t *in, uint64_t
     if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
         return REDUX_INVALID_INPUT;
     return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
-                               delta_encoder(p, block_size, element_size), block_crc); // redux_host.hpp
+                               layout_encoder(p, block_size, Layout{element_size, true}), block_crc); // redux_host.hpp
 }
 
 int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
@@ -2150,7 +2205,7 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
     if (st == REDUX_OK && redux_delta_check(element_size) != REDUX_OK)
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, delta_decoder(p, block_size, element_size), block_crc);
+                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, true}), block_crc);
 }
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------
@@ -2287,12 +2342,6 @@ int redux_plane_static_tables(const redux_params *p, const uint8_t *in, uint64_t
     return redux_plane_static_tables_from_counts(p, counts, element_size, total, cum);
 }
 
-// 64 slots / blocks of one wave, E apart, within a 32-bit lane offset
-static bool plane_static_fits(const Geometry &g, uint32_t block_size, uint32_t E)
-{
-    return 64ull * E * g.slot_bytes < (1ull << 32) && 64ull * E * block_size < (1ull << 32);
-}
-
 // The lookup decoder's WAVES wave slots share a table, so they must share a segment: k a multiple of WAVES (k = 0, a single
 // segment, is one).  Where the 8-wave instance does not suit, the 4-wave one is tried; where neither does (k = 1, 2, 3, 5,
 // ...), the lock-step decoder.
@@ -2325,7 +2374,7 @@ static const char *tables_static_encode_name(const redux_params *p, uint32_t tot
                                        "k_encode_segment_static<false, true> (code_bits 32)",
                                        "k_encode_segment_static<false, false> (code_bits < 32)"};
     const Geometry g = geometry(p, in_len, block_size, true);
-    if (!plane_static_fits(g, block_size, E))
+    if (!static_lanes_fit(g, block_size, E))
         return "";
     return enc[(int)pick_static_encode_kernel(p, total, 64 * E * plane_slots(g.nblocks, E))];
 }
@@ -2370,7 +2419,7 @@ uint64_t redux_plane_static_encode_workspace_bytes(const redux_params *p, uint64
     if (redux_planes_check(element_size) != REDUX_OK)
         return 0;
     const uint64_t ws = redux_static_encode_workspace_bytes(p, in_len, block_size);
-    return ws == 0 || element_size == 1 ? ws : planes_copy_bytes(in_len) + ws;
+    return ws ? Layout{element_size, false}.copy_bytes(in_len) + ws : 0;
 }
 
 uint64_t redux_plane_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2400,25 +2449,14 @@ static int tables_static_encode_x(const redux_params *p, const void *d_cum, uint
     const Geometry g = geometry(p, in_len, block_size, true);
     if (workspace_bytes < g.total)
         return REDUX_OUTPUT_TOO_SMALL;
-    if (!plane_static_fits(g, block_size, E))
+    if (!static_lanes_fit(g, block_size, E))
         return REDUX_UNSUPPORTED;
     hipStream_t s  = (hipStream_t)stream;
     uint8_t    *ws = (uint8_t *)d_workspace;
     HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
     SegmentStaticEncArgs a;
-    a.c.in         = (const uint8_t *)d_x;
-    a.c.in_len     = in_len;
-    a.c.nblocks    = g.nblocks;
-    a.c.slots      = ws + g.off_slots;
-    a.c.slot_bytes = g.slot_bytes;
-    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
-    a.c.status     = (int32_t *)d_block_status;
-    a.c.rc         = static_rc(total);
-    a.c.block_size = block_size;
-    a.c.slot_cap   = g.slot_cap;
-    a.c.code_bits  = p->code_bits;
-    a.c.aligned16  = ((((uintptr_t)d_x) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
-    a.t            = segment_tables(d_cum, E, k, total);
+    a.c = static_enc_args(g, p, d_x, in_len, block_size, ws, d_block_status, total);
+    a.t = segment_tables(d_cum, E, k, total);
     const uint64_t slots = plane_slots(g.nblocks, E);
     const uint32_t grid  = (uint32_t)(slots * E);
     switch (pick_static_encode_kernel(p, total, 64 * E * slots)) {
@@ -2431,23 +2469,17 @@ static int tables_static_encode_x(const redux_params *p, const void *d_cum, uint
     return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
-// the layout of d_in at the front of the workspace (E > 1), then the coder over it
+// the layout stage (layout_stage), then the coder over x'
 static int tables_static_encode(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
                                 uint32_t block_size, uint32_t E, uint32_t k, void *d_out, uint64_t out_cap, void *d_out_offsets,
                                 void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    if (E == 1)
-        return tables_static_encode_x(p, d_cum, total, d_in, in_len, block_size, 1, k, d_out, out_cap, d_out_offsets, d_block_status,
-                                      d_summary, d_workspace, workspace_bytes, stream);
-    const uint64_t copy = planes_copy_bytes(in_len);
-    if (workspace_bytes < copy)
-        return REDUX_OUTPUT_TOO_SMALL;
-    uint8_t  *x  = (uint8_t *)d_workspace;
-    const int st = redux_planes_dev(d_in, x, in_len, block_size, E, 0, stream);
+    Staged    x;
+    const int st = layout_stage(Layout{E, false}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x);
     if (st != REDUX_OK)
         return st;
-    return tables_static_encode_x(p, d_cum, total, x, in_len, block_size, E, k, d_out, out_cap, d_out_offsets, d_block_status,
-                                  d_summary, x + copy, workspace_bytes - copy, stream);
+    return tables_static_encode_x(p, d_cum, total, x.x, in_len, block_size, E, k, d_out, out_cap, d_out_offsets, d_block_status,
+                                  d_summary, x.ws, x.ws_bytes, stream);
 }
 
 int redux_plane_static_encode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, uint64_t in_len,
@@ -2468,38 +2500,19 @@ static int tables_static_decode_x(const redux_params *p, const void *d_cum, uint
                                   uint64_t nblocks, uint32_t block_size, uint32_t E, uint32_t k, void *d_planes, void *d_out_sizes,
                                   void *d_block_status, hipStream_t s)
 {
+    const StaticDecCore   c = static_dec_args(p, d_in, d_in_offsets, nblocks, block_size, d_planes, d_out_sizes, d_block_status, total);
     SegmentStaticLockArgs la;
     memset(&la, 0, sizeof la);
-    la.d.in         = (const uint8_t *)d_in;
-    la.d.in_offsets = (const uint64_t *)d_in_offsets;
-    la.d.nblocks    = nblocks;
-    la.d.out        = (uint8_t *)d_planes;
-    la.d.out_sizes  = (uint32_t *)d_out_sizes;
-    la.d.status     = (int32_t *)d_block_status;
-    la.d.block_size = block_size;
-    la.d.nfreeze    = 0xFFFFFFFFu;
-    la.d.code_bits  = p->code_bits;
-    la.d.aligned4   = ((((uintptr_t)d_planes) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
-    if (la.d.aligned4 && (((uintptr_t)d_planes) & 15) == 0 && (block_size & 15) == 0)
-        la.d.aligned4 = 2;
-    la.rc = static_rc(total);
+    la.d  = lock_args_from(c);
+    la.rc = c.rc;
     la.t  = segment_tables(d_cum, E, k, total);
     const uint64_t slots = plane_slots(nblocks, E);
     const uint32_t grid  = (uint32_t)(slots * E), grid4 = (uint32_t)((slots + 3) / 4 * E), grid8 = (uint32_t)((slots + 7) / 8 * E);
     switch (pick_segment_decode_kernel(p, total, 64 * E * slots, k)) {
     case StaticDecKernel::Fixup: {
         SegmentStaticDecArgs a;
-        a.c.in         = la.d.in;
-        a.c.in_offsets = la.d.in_offsets;
-        a.c.nblocks    = nblocks;
-        a.c.out        = la.d.out;
-        a.c.out_sizes  = la.d.out_sizes;
-        a.c.status     = la.d.status;
-        a.c.rc         = la.rc;
-        a.c.block_size = block_size;
-        a.c.code_bits  = p->code_bits;
-        a.c.aligned4   = la.d.aligned4 ? 1 : 0;
-        a.t            = la.t;
+        a.c = c;
+        a.t = la.t;
         k_decode_segment_static<true><<<grid, 64, 0, s>>>(a);
         break;
     }
@@ -2516,9 +2529,8 @@ static int tables_static_decode_x(const redux_params *p, const void *d_cum, uint
     return REDUX_OK;
 }
 
-// the blocks decode into a plane buffer at the front of the workspace (block_size bytes of room each, so a damaged stream
-// writes nothing outside it); their sizes are checked against the layout; the inverse transform writes d_out[0 .. out_len);
-// the summary comes last
+// the blocks decode into the plane buffer at the front of the workspace (for every E, 1 included), then the layout's decode
+// tail (layout_decode_tail); the summary comes last
 static int tables_static_decode(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
                                 uint64_t out_len, uint32_t block_size, uint32_t E, uint32_t k, void *d_out, void *d_out_sizes,
                                 void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
@@ -2526,21 +2538,12 @@ static int tables_static_decode(const redux_params *p, const void *d_cum, uint32
     const uint64_t nblocks = redux_block_count(out_len, block_size);
     if (workspace_bytes < redux_plane_static_decode_workspace_bytes(p, out_len, block_size, E))
         return REDUX_OUTPUT_TOO_SMALL;
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t    *x = (uint8_t *)d_workspace;
-    int st = tables_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, E, k, x, d_out_sizes, d_block_status, s);
+    const int st = tables_static_decode_x(p, d_cum, total, d_in, d_in_offsets, nblocks, block_size, E, k, d_workspace, d_out_sizes,
+                                          d_block_status, (hipStream_t)stream);
     if (st != REDUX_OK)
         return st;
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status, nullptr,
-                                                                        nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    if ((st = redux_planes_dev(x, d_out, out_len, block_size, E, 1, stream)) != REDUX_OK)
-        return st;
-    if (d_summary)
-        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
+    return layout_decode_tail(Layout{E, false}, d_workspace, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+                              TailSummary::Summarize, stream);
 }
 
 int redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
@@ -2556,49 +2559,65 @@ int redux_plane_static_decode_dev(const redux_params *p, const void *d_cum, uint
                                 d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
-// The coders of the chunked host calls.  The tables travel to each chunk's device behind the coder's workspace (8 KiB at
-// most, stream-ordered).  A chunk is whole 64-block waves, so its first block is a multiple of every E and b mod E inside
-// the chunk is the global one: checked (a call of one chunk starts at block 0 whatever its size).
-static uint64_t plane_tables_bytes(uint32_t E) { return align_up((uint64_t)E * kStaticEntries * 4, 256); }
+// The tables of a chunked static call travel to each chunk's device at the front of the chunk's workspace, stream-ordered:
+// `bytes` of them from the host at `cum`, in tables_bytes(bytes) of room.  The coder gets them at the workspace's old start
+// and its own workspace (ws, ws_bytes, moved on here) behind them.
+static uint64_t tables_bytes(uint64_t bytes) { return align_up(bytes, 256); }
 
+static int stage_tables(const uint32_t *cum, uint64_t bytes, uint8_t *&ws, uint64_t &ws_bytes, hipStream_t st)
+{
+    const uint64_t tb = tables_bytes(bytes);
+    if (ws_bytes < tb)
+        return REDUX_OUTPUT_TOO_SMALL;
+    HIP_TRY(hipMemcpyAsync(ws, cum, bytes, hipMemcpyHostToDevice, st));
+    ws += tb;
+    ws_bytes -= tb;
+    return REDUX_OK;
+}
+
+// The coders of the chunked host calls (8 KiB of tables at most).  A chunk is whole 64-block waves, so its first block is a
+// multiple of every E and b mod E inside the chunk is the global one: checked (a call of one chunk starts at block 0
+// whatever its size).
 static host::EncodeCoder plane_static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size, uint32_t E)
 {
     const uint32_t total = redux_plane_static_total(cum, E);
+    const uint64_t bytes = (uint64_t)E * kStaticEntries * 4;
     auto           chunk = std::make_shared<uint64_t>(0); // bytes of a full chunk when the call has several
     return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
                 *chunk = several ? max_in : 0;
-                ws     = plane_tables_bytes(E) + redux_plane_static_encode_workspace_bytes(p, max_in, block_size, E);
+                ws     = tables_bytes(bytes) + redux_plane_static_encode_workspace_bytes(p, max_in, block_size, E);
                 bound  = redux_plane_static_encode_bound(p, max_in, block_size);
             },
-            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *d_cum, uint64_t ws_bytes, hipStream_t st) -> int {
                 if (*chunk % ((uint64_t)E * block_size) != 0)
                     return REDUX_UNSUPPORTED;
-                const uint64_t tb = plane_tables_bytes(E);
-                if (ws_bytes < tb)
-                    return REDUX_OUTPUT_TOO_SMALL;
-                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)E * kStaticEntries * 4, hipMemcpyHostToDevice, st));
-                return redux_plane_static_encode_dev(p, ws, total, s.d_in.p, len, block_size, E, s.d_out.p, bound, s.d_off.p, s.d_st.p,
-                                                     s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+                uint8_t  *ws = (uint8_t *)d_cum;
+                const int rc = stage_tables(cum, bytes, ws, ws_bytes, st);
+                if (rc != REDUX_OK)
+                    return rc;
+                return redux_plane_static_encode_dev(p, d_cum, total, s.d_in.p, len, block_size, E, s.d_out.p, bound, s.d_off.p,
+                                                     s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
             }};
 }
 
 static host::DecodeCoder plane_static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size, uint32_t E)
 {
     const uint32_t total = redux_plane_static_total(cum, E);
+    const uint64_t bytes = (uint64_t)E * kStaticEntries * 4;
     auto           cbs   = std::make_shared<uint64_t>(0); // blocks of a full chunk
     return {[=](uint64_t cb) {
                 *cbs = cb;
-                return plane_tables_bytes(E) + redux_plane_static_decode_workspace_bytes(p, cb * (uint64_t)block_size, block_size, E);
+                return tables_bytes(bytes) + redux_plane_static_decode_workspace_bytes(p, cb * (uint64_t)block_size, block_size, E);
             },
-            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *d_cum, uint64_t ws_bytes, hipStream_t st) -> int {
                 if (*cbs % E != 0 && nb != *cbs) // (a chunk size that is no multiple of E: the call's only chunk)
                     return REDUX_UNSUPPORTED;
-                const uint64_t tb = plane_tables_bytes(E);
-                if (ws_bytes < tb)
-                    return REDUX_OUTPUT_TOO_SMALL;
-                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)E * kStaticEntries * 4, hipMemcpyHostToDevice, st));
-                return redux_plane_static_decode_dev(p, ws, total, s.d_in.p, s.d_off.p, out_bytes, block_size, E, s.d_out.p, s.d_sz.p,
-                                                     s.d_st.p, s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+                uint8_t  *ws = (uint8_t *)d_cum;
+                const int rc = stage_tables(cum, bytes, ws, ws_bytes, st);
+                if (rc != REDUX_OK)
+                    return rc;
+                return redux_plane_static_decode_dev(p, d_cum, total, s.d_in.p, s.d_off.p, out_bytes, block_size, E, s.d_out.p,
+                                                     s.d_sz.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
             },
             true};
 }
@@ -2800,21 +2819,20 @@ int redux_segment_static_build_encode_dev(const redux_params *p, uint32_t total,
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(in_len, block_size);
     const uint64_t cb      = segment_counts_bytes(redux_segment_static_table_count(nblocks, element_size, segment_blocks));
-    const uint64_t copy    = element_size > 1 ? planes_copy_bytes(in_len) : 0;
-    if (workspace_bytes < cb + copy)
+    const Layout   L{element_size, false};
+    if (workspace_bytes < cb + L.copy_bytes(in_len)) // (before the counts are cleared: layout_stage checks its share again)
         return REDUX_OUTPUT_TOO_SMALL;
-    hipStream_t s      = (hipStream_t)stream;
-    uint8_t    *counts = (uint8_t *)d_workspace, *x = counts + cb;
-    HIP_TRY(hipMemsetAsync(counts, 0, cb, s));
-    if (element_size > 1 && (st = redux_planes_dev(d_in, x, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
+    uint8_t *counts = (uint8_t *)d_workspace;
+    HIP_TRY(hipMemsetAsync(counts, 0, cb, (hipStream_t)stream));
+    Staged x;
+    if ((st = layout_stage(L, d_in, in_len, block_size, counts + cb, workspace_bytes - cb, stream, x)) != REDUX_OK)
         return st;
-    const void *d_x = element_size > 1 ? x : d_in;
-    if ((st = redux_segment_histogram_dev(d_x, in_len, block_size, element_size, segment_blocks, counts, stream)) != REDUX_OK)
+    if ((st = redux_segment_histogram_dev(x.x, in_len, block_size, element_size, segment_blocks, counts, stream)) != REDUX_OK)
         return st;
     if ((st = redux_segment_static_tables_dev(p, counts, nblocks, element_size, segment_blocks, total, d_cum, stream)) != REDUX_OK)
         return st;
-    return tables_static_encode_x(p, d_cum, total, d_x, in_len, block_size, element_size, segment_blocks / (64 * element_size), d_out,
-                                  out_cap, d_out_offsets, d_block_status, d_summary, x + copy, workspace_bytes - cb - copy, stream);
+    return tables_static_encode_x(p, d_cum, total, x.x, in_len, block_size, element_size, segment_blocks / (64 * element_size), d_out,
+                                  out_cap, d_out_offsets, d_block_status, d_summary, x.ws, x.ws_bytes, stream);
 }
 
 int redux_segment_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
@@ -3066,7 +3084,7 @@ int redux_context_static_encode_dev(const redux_params *p, const void *d_cum, ui
     const Geometry g = geometry(p, in_len, block_size, true);
     if (workspace_bytes < kCtxHead + g.total)
         return REDUX_OUTPUT_TOO_SMALL;
-    if (64ull * g.slot_bytes >= (1ull << 32) || 64ull * block_size >= (1ull << 32)) // 64 slots / blocks within a 32-bit lane offset
+    if (!static_lanes_fit(g, block_size, 1))
         return REDUX_UNSUPPORTED;
     hipStream_t s    = (hipStream_t)stream;
     uint8_t    *head = (uint8_t *)d_workspace, *ws = head + kCtxHead;
@@ -3074,18 +3092,7 @@ int redux_context_static_encode_dev(const redux_params *p, const void *d_cum, ui
         return st;
     HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256, s)); // linear slots, stream byte order
     ContextEncArgs a;
-    a.c.in         = (const uint8_t *)d_in;
-    a.c.in_len     = in_len;
-    a.c.nblocks    = g.nblocks;
-    a.c.slots      = ws + g.off_slots;
-    a.c.slot_bytes = g.slot_bytes;
-    a.c.sizes      = (uint32_t *)(ws + g.off_sizes);
-    a.c.status     = (int32_t *)d_block_status;
-    a.c.rc         = static_rc(total);
-    a.c.block_size = block_size;
-    a.c.slot_cap   = g.slot_cap;
-    a.c.code_bits  = p->code_bits;
-    a.c.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (block_size & 15) == 0) ? 1 : 0;
+    a.c            = static_enc_args(g, p, d_in, in_len, block_size, ws, d_block_status, total);
     a.image        = (const uint16_t *)head;
     a.bad          = (const uint32_t *)(head + kCtxImageBytes);
     a.total        = total;
@@ -3115,16 +3122,7 @@ int redux_context_static_decode_dev(const redux_params *p, const void *d_cum, ui
     if ((st = context_image(d_cum, total, head, s)) != REDUX_OK)
         return st;
     ContextDecArgs a;
-    a.c.in         = (const uint8_t *)d_in;
-    a.c.in_offsets = (const uint64_t *)d_in_offsets;
-    a.c.nblocks    = nblocks;
-    a.c.out        = (uint8_t *)d_out;
-    a.c.out_sizes  = (uint32_t *)d_out_sizes;
-    a.c.status     = (int32_t *)d_block_status;
-    a.c.rc         = static_rc(total);
-    a.c.block_size = block_size;
-    a.c.code_bits  = p->code_bits;
-    a.c.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+    a.c            = static_dec_args(p, d_in, d_in_offsets, nblocks, block_size, d_out, d_out_sizes, d_block_status, total);
     a.image        = (const uint16_t *)head;
     a.bad          = (const uint32_t *)(head + kCtxImageBytes);
     a.total        = total;
@@ -3142,38 +3140,38 @@ int redux_context_static_decode_dev(const redux_params *p, const void *d_cum, ui
     return REDUX_OK;
 }
 
-// The coders of the chunked host calls: the tables (258 KiB) travel to each chunk's device behind the coder's workspace,
-// stream-ordered.  Chunks are whole blocks and blocks are independent, so a chunk needs nothing from its neighbours.
-static uint64_t context_tables_bytes() { return align_up((uint64_t)kCtxTables * kStaticEntries * 4, 256); }
+// The coders of the chunked host calls: 258 KiB of tables in front of each chunk's workspace (stage_tables).  Chunks are whole
+// blocks and blocks are independent, so a chunk needs nothing from its neighbours.
+constexpr uint64_t kCtxTablesBytes = (uint64_t)kCtxTables * kStaticEntries * 4;
 
 static host::EncodeCoder context_static_encoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
     const uint32_t total = redux_context_static_total(cum);
     return {[=](uint64_t max_in, bool, uint64_t &ws, uint64_t &bound) {
-                ws    = context_tables_bytes() + redux_context_static_encode_workspace_bytes(p, max_in, block_size);
+                ws    = tables_bytes(kCtxTablesBytes) + redux_context_static_encode_workspace_bytes(p, max_in, block_size);
                 bound = redux_context_static_encode_bound(p, max_in, block_size);
             },
-            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
-                const uint64_t tb = context_tables_bytes();
-                if (ws_bytes < tb)
-                    return REDUX_OUTPUT_TOO_SMALL;
-                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)kCtxTables * kStaticEntries * 4, hipMemcpyHostToDevice, st));
-                return redux_context_static_encode_dev(p, ws, total, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
-                                                       s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *d_cum, uint64_t ws_bytes, hipStream_t st) -> int {
+                uint8_t  *ws = (uint8_t *)d_cum;
+                const int rc = stage_tables(cum, kCtxTablesBytes, ws, ws_bytes, st);
+                if (rc != REDUX_OK)
+                    return rc;
+                return redux_context_static_encode_dev(p, d_cum, total, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p,
+                                                       s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
             }};
 }
 
 static host::DecodeCoder context_static_decoder(const redux_params *p, const uint32_t *cum, uint32_t block_size)
 {
     const uint32_t total = redux_context_static_total(cum);
-    return {[=](uint64_t cb) { return context_tables_bytes() + redux_context_static_decode_workspace_bytes(p, cb, block_size); },
-            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) -> int {
-                const uint64_t tb = context_tables_bytes();
-                if (ws_bytes < tb)
-                    return REDUX_OUTPUT_TOO_SMALL;
-                HIP_TRY(hipMemcpyAsync(ws, cum, (size_t)kCtxTables * kStaticEntries * 4, hipMemcpyHostToDevice, st));
-                return redux_context_static_decode_dev(p, ws, total, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes, s.d_sz.p,
-                                                       s.d_st.p, s.d_sum.p, (uint8_t *)ws + tb, ws_bytes - tb, st);
+    return {[=](uint64_t cb) { return tables_bytes(kCtxTablesBytes) + redux_context_static_decode_workspace_bytes(p, cb, block_size); },
+            [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *, void *d_cum, uint64_t ws_bytes, hipStream_t st) -> int {
+                uint8_t  *ws = (uint8_t *)d_cum;
+                const int rc = stage_tables(cum, kCtxTablesBytes, ws, ws_bytes, st);
+                if (rc != REDUX_OK)
+                    return rc;
+                return redux_context_static_decode_dev(p, d_cum, total, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes,
+                                                       s.d_sz.p, s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
             }};
 }
 
@@ -3228,7 +3226,7 @@ uint64_t redux_decode_stored_workspace_bytes(const redux_params *p, uint64_t out
     if (stored_check(p, block_size, element_size) != REDUX_OK)
         return 0;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
-    return (element_size > 1 ? planes_copy_bytes(nblocks * (uint64_t)block_size) : 0) + store_table_bytes(nblocks) +
+    return Layout{element_size, false}.copy_bytes(nblocks * (uint64_t)block_size) + store_table_bytes(nblocks) +
            redux_decode_workspace_bytes(p, nblocks, block_size);
 }
 
@@ -3243,18 +3241,13 @@ int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in
         return st;
     if (store_ratio > kStoreRatioOne || !d_workspace || !d_stored || !d_block_status || (in_len && !d_in))
         return REDUX_INVALID_INPUT;
-    hipStream_t    s    = (hipStream_t)stream;
-    const uint64_t copy = element_size > 1 ? planes_copy_bytes(in_len) : 0;
-    if (workspace_bytes < copy) // (the coder checks the rest: a workspace without the small-grid pairs area will do, geometry_ws)
-        return REDUX_OUTPUT_TOO_SMALL;
-    const void    *x    = d_in;
-    if (element_size > 1) {
-        if ((st = redux_planes_dev(d_in, d_workspace, in_len, block_size, element_size, 0, stream)) != REDUX_OK)
-            return st;
-        x = d_workspace;
-    }
-    uint8_t       *ws  = (uint8_t *)d_workspace + copy;
-    const uint64_t wsb = workspace_bytes - copy;
+    hipStream_t s = (hipStream_t)stream;
+    Staged      staged; // (the coder checks the rest: a workspace without the small-grid pairs area will do, geometry_ws)
+    if ((st = layout_stage(Layout{element_size, false}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, staged)) != REDUX_OK)
+        return st;
+    const void    *x   = staged.x;
+    uint8_t       *ws  = staged.ws;
+    const uint64_t wsb = staged.ws_bytes;
     if ((st = encode_slots_impl(p, x, in_len, block_size, nullptr, 0, false, d_block_status, ws, wsb, stream)) != REDUX_OK)
         return st;
     const Geometry  g = geometry_ws(p, in_len, block_size, wsb);
@@ -3291,8 +3284,9 @@ int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void 
         return REDUX_INVALID_INPUT;
     hipStream_t    s       = (hipStream_t)stream;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
-    const uint64_t copy    = element_size > 1 ? planes_copy_bytes(nblocks * (uint64_t)block_size) : 0;
-    uint8_t       *t       = element_size > 1 ? (uint8_t *)d_workspace : (uint8_t *)d_out;
+    const Layout   L{element_size, false};
+    const uint64_t copy    = L.copy_bytes(nblocks * (uint64_t)block_size);
+    uint8_t       *t       = L.identity() ? (uint8_t *)d_out : (uint8_t *)d_workspace;
     redux_block   *table   = (redux_block *)((uint8_t *)d_workspace + copy);
     uint8_t       *dws     = (uint8_t *)table + store_table_bytes(nblocks);
 
@@ -3321,18 +3315,8 @@ int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void 
     ua.out_len    = out_len;
     ua.block_size = block_size;
     k_store_unpack<<<(uint32_t)nblocks, 256, 0, s>>>(ua);
-    const uint64_t wgs = (nblocks + 255) / 256;
-    k_planes_sizes<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>((const uint32_t *)d_out_sizes, (int32_t *)d_block_status,
-                                                                        nullptr, nblocks, out_len, block_size);
-    HIP_TRY(hipGetLastError());
-    if (element_size > 1 && (st = redux_planes_dev(t, d_out, out_len, block_size, element_size, 1, stream)) != REDUX_OK)
-        return st;
-    if (d_summary) {
-        HIP_TRY(hipMemsetAsync(d_summary, 0, 8, s));
-        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-        HIP_TRY(hipGetLastError());
-    }
-    return REDUX_OK;
+    return layout_decode_tail(L, L.identity() ? nullptr : t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+                              TailSummary::ZeroSummarize, stream);
 }
 
 // the chunked host calls: flags travel in the slot's d_stf (redux_host.hpp)
@@ -3341,7 +3325,7 @@ static host::EncodeCoder stored_encoder(const redux_params *p, uint32_t block_si
     const host::EncodeCoder plain = adaptive_encoder(p, block_size);
     return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
                 plain.size(max_in, several, ws, bound);
-                ws += element_size > 1 ? planes_copy_bytes(max_in) : 0;
+                ws += Layout{element_size, false}.copy_bytes(max_in);
             },
             [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
                 return redux_encode_stored_dev(p, s.d_in.p, len, block_size, element_size, store_ratio, s.d_out.p, bound, s.d_off.p,

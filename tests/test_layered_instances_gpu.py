@@ -523,3 +523,102 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     assert checked > 0
     del big_in, d_in, d_out, flat
     _free()
+
+
+# ---- 6. the summary of the four decode tails ------------------------------------------------------------------------------------
+TAILS = [PLANES, DELTA, STORED, "plane-static"]
+
+
+def _tables_coder(E, B, params, total, d_in, in_len):
+    """plane-static (the table-addressed static coders): the tables of the input on the device, and its streams."""
+    import torch
+    L = _lib()
+    lib, cp = L.lib(), L.Params(*params)
+    cum = np.zeros(E * 258, np.uint32)
+    host = d_in.cpu().numpy()
+    assert lib.redux_plane_static_tables(C.byref(cp), host.ctypes.data, in_len, B, E, total, cum.ctypes.data) == 0
+    d_cum = torch.from_numpy(cum).cuda()
+    nb = lib.redux_block_count(in_len, B)
+    cap = lib.redux_plane_static_encode_bound(C.byref(cp), in_len, B)
+    wsb = lib.redux_plane_static_encode_workspace_bytes(C.byref(cp), in_len, B, E)
+    wst, wsp = workspace(wsb)
+    out = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+    offs = torch.zeros(nb + 1, dtype=torch.int64, device="cuda:0")
+    status = torch.full((nb,), -7, dtype=torch.int32, device="cuda:0")
+    summ = torch.zeros(2, dtype=torch.int32, device="cuda:0")
+    rc = lib.redux_plane_static_encode_dev(C.byref(cp), _v(d_cum), total, _v(d_in), in_len, B, E, _v(out), cap, _v(offs), _v(status),
+                                           _v(summ), C.c_void_p(wsp), wsb, None)
+    torch.cuda.synchronize()
+    assert rc == 0 and summ.tolist() == [0, 0]
+    return d_cum, out, offs
+
+
+def _tables_decode(E, B, params, total, d_cum, d_streams, d_offs, out_len):
+    import torch
+    L = _lib()
+    lib, cp = L.lib(), L.Params(*params)
+    nb = lib.redux_block_count(out_len, B)
+    wsb = lib.redux_plane_static_decode_workspace_bytes(C.byref(cp), out_len, B, E)
+    wst, wsp = workspace(wsb)
+    big, out, lo = guarded(out_len)
+    sizes = torch.full((nb,), -7, dtype=torch.int32, device="cuda:0")
+    status = torch.full((nb,), -7, dtype=torch.int32, device="cuda:0")
+    summ = torch.zeros(2, dtype=torch.int32, device="cuda:0")
+    rc = lib.redux_plane_static_decode_dev(C.byref(cp), _v(d_cum), total, _v(d_streams), _v(d_offs), out_len, B, E, _v(out), _v(sizes),
+                                           _v(status), _v(summ), C.c_void_p(wsp), wsb, None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert guards_intact(big, lo, out_len)
+    return out, sizes, status, summ
+
+
+def _summary_is_the_statuses(status, summ, want_bad):
+    """d_summary = [the status of the first failing block, the number of failing blocks], from the returned statuses.  (Where
+    failing blocks differ in status, the device keeps the one whose workgroup came first: any of them.)"""
+    st = status.cpu().numpy()
+    bad = np.nonzero(st)[0]
+    assert bad.tolist() == want_bad, (bad.tolist(), want_bad)
+    first, count = summ.tolist()
+    assert count == len(bad)
+    assert first == int(st[bad[0]]) or (len(set(st[bad].tolist())) > 1 and first in st[bad].tolist()), (first, st[bad].tolist())
+
+
+@pytest.mark.parametrize("E", [1, 2, 4, 8])
+def test_summary_of_the_four_decode_tails(rx, E):
+    """67 blocks of 1,040 bytes and a last block of 5 (more than one 64-block wave, a block count no multiple of any E > 1, a
+    block size that is a multiple of 16 and not of 64, a ragged last block) through the planes, delta, stored and
+    table-addressed static decode calls: with two damaged streams, and with an out_len one byte short of what the streams
+    hold, d_summary is the first failing block's status and the count of failing blocks, as the returned statuses give them."""
+    import torch
+    params, B, nb, total = (8, 30, 32), 1040, 68, 4096
+    in_len = 67 * B + 5
+    rng = np.random.default_rng(140 + E)
+    d_in = torch.from_numpy(np.minimum(rng.standard_exponential(in_len) * 5, 255).astype(np.uint8)).cuda()   # (every block shrinks)
+    lib = _lib().lib()
+    for tail in TAILS:
+        if tail == "plane-static":
+            d_cum, out, offs = _tables_coder(E, B, params, total, d_in, in_len)
+            flags = None
+            decode = lambda s, n: _tables_decode(E, B, params, total, d_cum, s, offs, n)
+        else:
+            out, offs, status, summ, flags = encode_dev(tail, params, E, B, d_in, in_len, "own")
+            assert summ.tolist() == [0, 0]
+            decode = lambda s, n, tail=tail, flags=flags: decode_dev(tail, params, E, B, s, offs, flags, n)
+        assert lib.redux_block_count(in_len - 1, B) == nb
+        d_out, sizes, status, summ = decode(out, in_len)
+        assert summ.tolist() == [0, 0] and torch.equal(d_out, d_in), tail
+        # an out_len one byte short: the last block holds a byte too many
+        d_out, sizes, status, summ = decode(out, in_len - 1)
+        _summary_is_the_statuses(status, summ, [nb - 1])
+        assert torch.equal(d_out[: 67 * B - (67 % E) * B], d_in[: 67 * B - (67 % E) * B]), tail     # the frames without it
+        # two damaged streams, one in each 64-block wave: the last two thirds of the stream become 0xFF
+        o = offs.cpu().numpy()
+        picks = [b for b in (3, 65) if tail != STORED or int(flags[b]) == 0]
+        assert len(picks) == 2, "the skewed blocks are coded, not stored"
+        hurt = out.clone()
+        for b in picks:
+            n = int(o[b + 1] - o[b])
+            hurt[int(o[b]) + n // 3: int(o[b + 1])] = 0xFF
+        d_out, sizes, status, summ = decode(hurt, in_len)
+        _summary_is_the_statuses(status, summ, picks)
+    _free()
