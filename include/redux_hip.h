@@ -764,6 +764,14 @@ const char *redux_segment_static_encode_kernel_name(const redux_params *p, uint3
 const char *redux_segment_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks, uint32_t element_size,
                                                     uint32_t segment_blocks);
 
+/* The same for redux_context_static_encode_dev / redux_context_static_decode_dev (the k_*_context_static instances): one
+ * workgroup per CU holds the 128 KiB image, so the choice is the waves per workgroup, from the wave slots (64 blocks each) the
+ * launch has per CU of HIP's current device: 4 up to 4 slots per CU, 8 up to 8 (the encoder's largest, also by code_bits 32
+ * or less), 16 beyond (decoder only).  "" for arguments the _dev call rejects, and for nblocks == 0 (the decode call
+ * launches nothing). */
+const char *redux_context_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size);
+const char *redux_context_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks);
+
 /* Diagnostic, used by the parity tests only: *max_err = max over the integers x in [lo, hi] of
  * |v_rcp_f64(x) * x - 1| evaluated on the device.  The decoder's code-value division
  * (codec.rs:131) multiplies by the raw hardware reciprocal of `range` (an integer in [1, 2^32])

@@ -3062,9 +3062,49 @@ static int context_image(const void *d_cum, uint32_t total, uint8_t *ws, hipStre
     return REDUX_OK;
 }
 
-static void launch_context_encode(bool cb32, uint32_t waves, uint32_t grid, const ContextEncArgs &a, hipStream_t s)
+// which context-static kernel a call runs: ONE decision, used by the launch code and reported by
+// redux_context_static_encode_kernel_name / redux_context_static_decode_kernel_name
+struct ContextEncKernel {
+    uint32_t waves; // 4 or 8
+    bool     cb32;
+};
+
+static ContextEncKernel pick_context_encode_kernel(const redux_params *p, uint64_t nblocks)
 {
-    switch (waves * 2 + (cb32 ? 1 : 0)) {
+    return {context_waves(nblocks, 8), p->code_bits == 32};
+}
+
+static uint32_t pick_context_decode_kernel(uint64_t nblocks) { return context_waves(nblocks, 16); } // 4, 8 or 16 waves
+
+const char *redux_context_static_encode_kernel_name(const redux_params *p, uint32_t total, uint64_t in_len, uint32_t block_size)
+{
+    if (context_static_check(p, total) != REDUX_OK || block_size == 0)
+        return "";
+    const Geometry g = geometry(p, in_len, block_size, true);
+    if (!static_lanes_fit(g, block_size, 1)) // as redux_context_static_encode_dev
+        return "";
+    const ContextEncKernel k = pick_context_encode_kernel(p, g.nblocks);
+    if (k.waves == 4)
+        return k.cb32 ? "k_encode_context_static<true, 4> (code_bits 32, 4 waves per group)"
+                      : "k_encode_context_static<false, 4> (code_bits < 32, 4 waves per group)";
+    return k.cb32 ? "k_encode_context_static<true, 8> (code_bits 32, 8 waves per group)"
+                  : "k_encode_context_static<false, 8> (code_bits < 32, 8 waves per group)";
+}
+
+const char *redux_context_static_decode_kernel_name(const redux_params *p, uint32_t total, uint64_t nblocks)
+{
+    if (context_static_check(p, total) != REDUX_OK || nblocks == 0) // (no blocks: the call launches nothing)
+        return "";
+    switch (pick_context_decode_kernel(nblocks)) {
+    case 4: return "k_decode_context_static<4> (4 waves per group)";
+    case 8: return "k_decode_context_static<8> (8 waves per group)";
+    default: return "k_decode_context_static<16> (16 waves per group)";
+    }
+}
+
+static void launch_context_encode(const ContextEncKernel &k, uint32_t grid, const ContextEncArgs &a, hipStream_t s)
+{
+    switch (k.waves * 2 + (k.cb32 ? 1 : 0)) {
     case 8: k_encode_context_static<false, 4><<<grid, 256, 0, s>>>(a); break;
     case 9: k_encode_context_static<true, 4><<<grid, 256, 0, s>>>(a); break;
     case 17: k_encode_context_static<true, 8><<<grid, 512, 0, s>>>(a); break;
@@ -3096,10 +3136,10 @@ int redux_context_static_encode_dev(const redux_params *p, const void *d_cum, ui
     a.image        = (const uint16_t *)head;
     a.bad          = (const uint32_t *)(head + kCtxImageBytes);
     a.total        = total;
-    const uint32_t W      = context_waves(g.nblocks, 8);
-    const uint64_t groups = ((g.nblocks + 63) / 64 + W - 1) / W, cus = cu_count();
+    const ContextEncKernel k = pick_context_encode_kernel(p, g.nblocks);
+    const uint64_t groups = ((g.nblocks + 63) / 64 + k.waves - 1) / k.waves, cus = cu_count();
     const uint32_t grid   = (uint32_t)(groups < cus ? groups : cus);
-    launch_context_encode(p->code_bits == 32, W, grid, a, s);
+    launch_context_encode(k, grid, a, s);
     HIP_TRY(hipGetLastError());
     return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, workspace_bytes - kCtxHead, stream);
 }
@@ -3126,7 +3166,7 @@ int redux_context_static_decode_dev(const redux_params *p, const void *d_cum, ui
     a.image        = (const uint16_t *)head;
     a.bad          = (const uint32_t *)(head + kCtxImageBytes);
     a.total        = total;
-    const uint32_t W      = context_waves(nblocks, 16);
+    const uint32_t W      = pick_context_decode_kernel(nblocks);
     const uint64_t groups = ((nblocks + 63) / 64 + W - 1) / W, cus = cu_count();
     const uint32_t grid   = (uint32_t)(groups < cus ? groups : cus);
     switch (W) {

@@ -148,6 +148,10 @@ extern "C" {
                                    workspace_bytes: u64) -> *const c_char;
     #[allow(dead_code)] // the same for the decoder a stored launch runs (the table form)
     fn redux_decode_kernel_name_table(p: *const ReduxParams, block_size: u32, nentries: u64) -> *const c_char;
+    #[allow(dead_code)] // the same for the context-static coders: which of their seven instances a launch runs
+    fn redux_context_static_encode_kernel_name(p: *const ReduxParams, total: u32, in_len: u64, block_size: u32) -> *const c_char;
+    #[allow(dead_code)]
+    fn redux_context_static_decode_kernel_name(p: *const ReduxParams, total: u32, nblocks: u64) -> *const c_char;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }

@@ -16,6 +16,7 @@ import pytest
 from oracle import redux_ref as ref
 from test_context_static_cpu import (P, TOTAL, ContextStaticModel, corpus, encode_ref, ideal_bits, pair_counts, table_section_bytes,
                                      tables_ref)
+from test_context_static_instances_cpu import DEC, ENC, dec_name, enc_name
 
 pytestmark = pytest.mark.gpu
 
@@ -166,9 +167,11 @@ def test_text_streams(rx, B, params):
 
 @pytest.mark.parametrize("B,nblocks", [(64, 65), (257, 65), (4096, 65), (64, 64 * 8 + 1), (64, 64 * 16 + 1)])
 def test_wave_and_workgroup_boundaries(rx, B, nblocks):
-    """65 blocks: a second, nearly empty wave; 64 W + 1 blocks: a second workgroup's first lane (W = 8 encoder waves, 16
-    decoder waves); the last block is short"""
+    """65 blocks: a second, nearly empty wave; 64 * 8 + 1 and 64 * 16 + 1 blocks: a third and a fifth workgroup's first lane.
+    Every one of these shapes runs W = 4 waves per workgroup in both coders (a workgroup per CU comes before a deeper one;
+    tests/test_context_static_instances_gpu.py has the shapes of 8 and 16 waves); the last block is short"""
     x = np.resize(alice16k() if B > 64 else random64k(), nblocks * B - 3)
+    assert enc_name(P, len(x), B) == ENC[(True, 4)] and dec_name(P, nblocks) == DEC[4]
     check_streams(rx, x, B, tables_ref(pair_counts(x, B)))
 
 
@@ -199,6 +202,7 @@ def test_more_wave_slots_than_the_grid_holds(rx):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     nblocks = 64 * 16 * cus + 1
     x = np.resize(corpus("canterbury/alice29.txt"), nblocks * B - 5)
+    assert enc_name(P, len(x), B) == ENC[(True, 8)] and dec_name(P, nblocks) == DEC[16]
     cums = tables_ref(pair_counts(x, B))
     coder = rx.DeviceContextStaticCoder(P, d_tables(cums), TOTAL, B, len(x))
     d_in = dev(x)
