@@ -715,6 +715,43 @@ int      redux_context_static_decode_blocks_crc(const redux_params *p, const uin
                                                 const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                                                 uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- size estimates --------------------------------------------------------------------------------------
+ * What a block would cost under a model, from counts alone: every model here is exchangeable inside a block, so a block's
+ * ideal code length is a function of its byte counts, not of the order of its bytes.  A caller compares models without
+ * coding the input once per model.  Costs are in BITS, as doubles, and cross this boundary through pointers only.
+ *   - Adaptive model (8-bit symbols): a block starts at total 257 and every coded symbol adds 1, so a block with histogram h
+ *     and n bytes costs, the EOF symbol included,
+ *         A(h, n) = log2 G(n + 258) - log2 G(257) - sum_s log2 G(h[s] + 1)                    (G = the gamma function).
+ *     This holds while the model cannot freeze inside the block: 256 + n < freq_max.  A frozen model's cost depends on the
+ *     order of the bytes, so a longer block is UNSUPPORTED, as are symbol_bits != 8 and code_bits > 32.
+ *   - Static table cum[0..=257] with T = cum[257]: counts c cost sum_s c[s] (log2 T - log2(cum[s+1] - cum[s])), the
+ *     cross-entropy of the counts under the table.  Terms with c[s] == 0 are 0; the result is +inf when T == 0, or when a
+ *     frequency that is zero or negative meets a nonzero count.  EOF is NOT included: every table the library builds gives
+ *     EOF frequency 1, so a caller adds log2 T per block.  Nothing is indexed by table contents: any bytes may be passed.
+ *   - A stream is its ideal length plus the coder's termination: measured against the reference coder at (8, 30, 32),
+ *     len(stream) - (ceil(A / 8) + 2) lies in -1 .. +1 for the adaptive model and len(stream) - bits / 8 in 1.78 .. 2.87 for
+ *     static tables of total 2^16.
+ *
+ * redux_adaptive_cost_from_counts  A for n count rows, u64[n][256] -> bits[n], on the host; needs no GPU.  UNSUPPORTED
+ *                                  unless symbol_bits == 8, code_bits <= 32 and 256 + the largest row sum < freq_max.
+ * redux_table_cost_from_counts     the table rule for n rows, counts u64[n][256] and tables u32[n][258] -> bits[n], on the host.
+ * redux_block_cost_dev             A for every block of d_in[0 .. in_len) cut into blocks of block_size from its start
+ *                                  (k_block_cost): d_bits is f64[redux_block_count(in_len, block_size)] on the device.  Any
+ *                                  block_size 1 .. 2^30 (else INVALID_INPUT), any alignment of d_in, a short last block,
+ *                                  in_len == 0 (one empty block).  The UNSUPPORTED conditions above with block_size in
+ *                                  place of the row sum.  Stream-ordered, no workspace.
+ * redux_table_cost_dev             the table rule on the device (k_table_cost): d_counts u64[n][256] -- n = 1 what
+ *                                  redux_histogram_dev leaves, E rows redux_plane_histogram_dev, nseg E
+ *                                  redux_segment_histogram_dev, 256 redux_context_histogram_dev -- and d_cum u32[n][258]
+ *                                  -> d_bits f64[n].  Stream-ordered, no workspace. */
+int redux_adaptive_cost_from_counts(const redux_params *p, const uint64_t *counts /* u64[n][256] */, uint64_t n, double *bits);
+int redux_table_cost_from_counts(const uint64_t *counts /* u64[n][256] */, const uint32_t *cum /* u32[n][258] */, uint64_t n,
+                                 double *bits);
+int redux_block_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                         void *d_bits /* f64[nblocks] */, void *stream);
+int redux_table_cost_dev(const void *d_counts /* u64[n][256] */, const void *d_cum /* u32[n][258] */, uint64_t n,
+                         void *d_bits /* f64[n] */, void *stream);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

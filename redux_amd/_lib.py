@@ -141,6 +141,10 @@ SIGNATURES = {
     "redux_context_static_decode_blocks_crc": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _V, _U64, _V, _V, _V]),
     "redux_context_static_encode_kernel_name": (C.c_char_p, [_PP, _U32, _U64, _U32]),
     "redux_context_static_decode_kernel_name": (C.c_char_p, [_PP, _U32, _U64]),
+    "redux_adaptive_cost_from_counts": (C.c_int, [_PP, _V, _U64, C.POINTER(C.c_double)]),
+    "redux_table_cost_from_counts": (C.c_int, [_V, _V, _U64, C.POINTER(C.c_double)]),
+    "redux_block_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _V, _V]),
+    "redux_table_cost_dev": (C.c_int, [_V, _V, _U64, _V, _V]),
     "redux_planes_check": (C.c_int, [_U32]),
     "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

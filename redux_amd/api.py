@@ -1448,6 +1448,183 @@ def crc32_combine(crc1, crc2, len2):
     return int(_lib.lib().redux_crc32_combine(int(crc1) & 0xFFFFFFFF, int(crc2) & 0xFFFFFFFF, int(len2)))
 
 
+# ---- size estimates (include/redux_hip.h, "size estimates") ---------------------------------------
+MODELS = ("adaptive", "static", "plane-static", "segment-static", "context-static")  # (ties in an estimate go to the earlier)
+TERMINATION_BYTES = 2.5  # a stream's bytes beyond its ideal length: the midpoint of what DESIGN.md 6j measured
+
+
+def adaptive_cost_from_counts(counts, params=(8, 30, 32)):
+    """redux_adaptive_cost_from_counts: the adaptive model's ideal code length in bits, EOF included, of blocks with the
+    byte counts `counts` (u64[n, 256], or [256] for one block), on the host -> np.float64[n].  Unsupported where a block
+    could freeze the model."""
+    P = _params_of(params)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    c = c.reshape(1, 256) if c.shape == (256,) else c
+    if c.ndim != 2 or c.shape[1] != 256:
+        raise InvalidInput()
+    bits = np.zeros(len(c), dtype=np.float64)
+    cp = P._c()
+    _raise(_lib.lib().redux_adaptive_cost_from_counts(C.byref(cp), _ptr(c), len(c), bits.ctypes.data_as(C.POINTER(C.c_double))))
+    return bits
+
+
+def _cost_rows(counts, cums):
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    t = np.ascontiguousarray(cums, dtype=np.uint32)
+    c = c.reshape(1, 256) if c.shape == (256,) else c
+    t = t.reshape(1, 258) if t.shape == (258,) else t
+    if c.ndim != 2 or c.shape[1] != 256 or t.shape != (len(c), 258):
+        raise InvalidInput()
+    return c, t
+
+
+def table_cost_from_counts(counts, cums):
+    """redux_table_cost_from_counts: sum_s c[s] (log2 T - log2 f[s]) in bits for n count rows (u64[n, 256]) under n
+    static tables (u32[n, 258]), on the host -> np.float64[n].  EOF is not included (add log2 T per block); +inf for a
+    table that cannot code its row."""
+    c, t = _cost_rows(counts, cums)
+    bits = np.zeros(len(c), dtype=np.float64)
+    _raise(_lib.lib().redux_table_cost_from_counts(_ptr(c), _ptr(t), len(c), bits.ctypes.data_as(C.POINTER(C.c_double))))
+    return bits
+
+
+def _device_u8(torch, data):
+    """a uint8 device tensor is taken in place; host data (bytes-like, numpy) is uploaded to the current device"""
+    if _is_device_tensor(data):
+        assert data.dtype == torch.uint8 and data.is_contiguous()
+        return data
+    return torch.from_numpy(_u8(data).copy()).cuda()
+
+
+def block_cost(data, block_size, params=(8, 30, 32)):
+    """The adaptive model's ideal code length in bits, EOF included, of every block of block_size bytes of `data`
+    (redux_block_cost_dev: k_block_cost on torch's current stream, one read-back) -> np.float64[nblocks].  A uint8 device
+    tensor is read where it lies; host data is uploaded first."""
+    P = _params_of(params)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    torch = _torch()
+    d = _device_u8(torch, data)
+    L = _lib.lib()
+    cp = P._c()
+    with torch.cuda.device(d.device):
+        return _device_block_cost(torch, L, cp, d, int(block_size)).cpu().numpy()
+
+
+def _device_block_cost(torch, L, cp, d, block_size):
+    n = d.numel()
+    d_bits = torch.empty(L.redux_block_count(n, block_size), dtype=torch.float64, device=d.device)
+    _raise(L.redux_block_cost_dev(C.byref(cp), C.c_void_p(d.data_ptr()) if n else None, n, block_size,
+                                  C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits
+
+
+def table_cost(counts, cums):
+    """table_cost_from_counts on the device (redux_table_cost_dev: k_table_cost on torch's current stream, one read-back)
+    -> np.float64[n].  counts: an int64 device tensor of n * 256 entries, as the `_dev` histogram calls leave it, with cums
+    an int32 device tensor of n * 258; or host arrays of those shapes, which are uploaded first."""
+    torch = _torch()
+    if _is_device_tensor(counts) != _is_device_tensor(cums):
+        raise InvalidInput()
+    if _is_device_tensor(counts):
+        assert counts.element_size() == 8 and cums.element_size() == 4 and counts.is_contiguous() and cums.is_contiguous()
+        if counts.numel() % 256 or cums.numel() != counts.numel() // 256 * 258 or cums.device != counts.device:
+            raise InvalidInput()
+        d_c, d_t = counts, cums
+    else:
+        c, t = _cost_rows(counts, cums)
+        d_c, d_t = torch.from_numpy(c.view(np.int64).copy()).cuda(), torch.from_numpy(t.view(np.int32).copy()).cuda()
+    with torch.cuda.device(d_c.device):
+        return _device_table_cost(torch, _lib.lib(), d_c, d_t).cpu().numpy()
+
+
+def _device_table_cost(torch, L, d_counts, d_cum):
+    n = d_counts.numel() // 256
+    d_bits = torch.empty(n, dtype=torch.float64, device=d_counts.device)
+    _raise(L.redux_table_cost_dev(C.c_void_p(d_counts.data_ptr()) if n else None, C.c_void_p(d_cum.data_ptr()) if n else None, n,
+                                  C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits
+
+
+def estimate_candidates(element_size=1):
+    """The models an estimate covers for this element size, in MODELS order: adaptive and segment-static always, static and
+    context-static for element size 1, plane-static above."""
+    E = _check_element_size(element_size)
+    return tuple(m for m in MODELS if m in ("adaptive", "segment-static") or (m == "plane-static") == (E > 1))
+
+
+def estimate_payload(data, block_size, params=(8, 30, 32), element_size=1, segment_blocks=None, models=None):
+    """-> {model: estimated payload bytes}: what the streams of compress_blocks would add up to under each model of
+    `models` (None: estimate_candidates(element_size)), without coding anything.  One histogram pass per model on the device
+    (k_block_cost; the `_dev` histogram and table calls with the default total, then k_table_cost), on the byte-plane layout
+    for element_size > 1, as the coders run.  The estimate is ceil(sum bits / 8 + TERMINATION_BYTES * nblocks), every block's
+    EOF symbol included.  A uint8 device tensor is read where it lies; host data is uploaded once."""
+    return _estimate(data, block_size, params, element_size, segment_blocks, models)[0]
+
+
+def _estimate(data, block_size, params, element_size, segment_blocks, models):
+    """estimate_payload, and the context-static tables (np.uint32[256, 258]; None unless that model was estimated): the
+    container's overhead for them depends on which contexts occur"""
+    P = _params_of(params)
+    E = _check_element_size(element_size)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    B = int(block_size)
+    models = estimate_candidates(E) if models is None else tuple(models)
+    if any(m not in estimate_candidates(E) for m in models):
+        raise InvalidInput()
+    G = default_segment_blocks(E) if segment_blocks is None else segment_blocks
+    if "segment-static" in models:
+        G = SegmentStaticModel(P, None, E, G).segment_blocks  # (checks G)
+    T = _total_of(P, None)
+    torch = _torch()
+    L = _lib.lib()
+    cp = P._c()
+    d = _device_u8(torch, data)
+    out, context_cums = {}, None
+    with torch.cuda.device(d.device):
+        d_x = planes(d, E, B) if E > 1 else d
+        n = d_x.numel()
+        nb = L.redux_block_count(n, B)
+        x_ptr = C.c_void_p(d_x.data_ptr()) if n else None
+        s = _stream_ptr(torch)
+
+        def static_bits(nrows, table_of_block, histogram, tables):
+            """counts -> tables -> the rows' cross-entropy, plus log2(total) of its table for every block's EOF"""
+            counts = torch.zeros(nrows * 256, dtype=torch.int64, device=d_x.device)
+            d_cum = torch.zeros(nrows * 258, dtype=torch.int32, device=d_x.device)
+            _raise(histogram(C.c_void_p(counts.data_ptr())))
+            _raise(tables(C.c_void_p(counts.data_ptr()), C.c_void_p(d_cum.data_ptr())))
+            bits = _device_table_cost(torch, L, counts, d_cum).cpu().numpy()
+            cums = d_cum.cpu().numpy().view(np.uint32).reshape(nrows, 258)
+            if not cums.any(axis=1).all():  # the table kernel's mark for N * R >= 2^64
+                raise Unsupported()
+            eof = np.log2(cums[table_of_block(np.arange(nb, dtype=np.int64)), 257].astype(np.float64))
+            return float(bits.sum()) + float(eof.sum()), cums
+
+        for m in models:
+            if m == "adaptive":
+                total = float(_device_block_cost(torch, L, cp, d_x, B).sum().item())
+            elif m == "static":
+                total, _ = static_bits(1, lambda b: 0 * b,
+                                       lambda c: L.redux_histogram_dev(x_ptr, n, c, None, 0, s),
+                                       lambda c, t: L.redux_static_table_dev(C.byref(cp), c, T, t, s))
+            elif m == "plane-static":
+                total, _ = static_bits(E, lambda b: b % E,
+                                       lambda c: L.redux_plane_histogram_dev(x_ptr, n, B, E, c, None, 0, s),
+                                       lambda c, t: L.redux_plane_static_tables_dev(C.byref(cp), c, E, T, t, s))
+            elif m == "segment-static":
+                total, _ = static_bits(L.redux_segment_static_table_count(nb, E, G), lambda b: b // G * E + b % E,
+                                       lambda c: L.redux_segment_histogram_dev(x_ptr, n, B, E, G, c, s),
+                                       lambda c, t: L.redux_segment_static_tables_dev(C.byref(cp), c, nb, E, G, T, t, s))
+            else:  # context-static: a block's EOF is coded under its last byte's table; all 256 have one total
+                total, context_cums = static_bits(256, lambda b: 0 * b,
+                                                  lambda c: L.redux_context_histogram_dev(x_ptr, n, B, c, s),
+                                                  lambda c, t: L.redux_context_static_tables_dev(C.byref(cp), c, T, t, s))
+            out[m] = int(np.ceil(total / 8 + TERMINATION_BYTES * nb))
+    return out, context_cums
+
+
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------
 def gen_iid(nbytes, seed=0x5EED0001, first_byte=0, device="cuda:0", out=None):
     torch = _torch()

@@ -1,7 +1,8 @@
 """Command line with the reference's interface (src/main.rs):
 
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
-                            [--model adaptive|static|plane-static|segment-static|context-static] [--segment-blocks G] [--checksum] [--stored]
+                            [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
+                            [--stored]
                             [--filter delta]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -26,8 +27,14 @@ another model, it is a usage error.
 `--model context-static` (with a block size, element size 1) builds a static table per preceding byte -- an order-1
 model -- from the whole input and codes every byte under the table of the byte before it (container version 7, which
 records the tables of the contexts that occur).  It pays on text, logs and source code from about half a megabyte upward
-(bible.txt: 0.42 against 0.54) and costs up to 128 KiB of tables below that, so it is never chosen for you.  With
+(bible.txt: 0.42 against 0.54) and costs up to 128 KiB of tables below that, so only `--model auto` chooses it for you.  With
 `--block-size 0`, `--stored`, `--filter` or an `--element-size` other than 1 it is a usage error.
+`--model auto` (with a block size and any `--element-size`) estimates the container each model would write -- adaptive and
+segment-static always, static and context-static for element size 1, plane-static above -- from histograms of the input taken
+on the GPU, without coding it (redux_amd/container.py: estimate_bytes), and codes with the smallest; ties go to
+the earlier of adaptive, static, plane-static, segment-static, context-static.  The output is that model's container:
+nothing new for -d.  The filter and stored blocks are not chosen automatically: `--model auto` with `--block-size 0`,
+`--stored`, `--filter` or `--segment-blocks` is a usage error.
 `--checksum` (with -c and a block size) records the CRC-32 (zlib.crc32) of every block's uncompressed bytes in the container
 (version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
 damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
@@ -45,7 +52,7 @@ import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
-         "[--model <adaptive|static|plane-static|segment-static|context-static>] [--segment-blocks <G>] [--checksum] [--stored] "
+         "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
          "[--filter <delta>]")
 
 
@@ -74,7 +81,7 @@ def parse(argv):
                     return None
                 opts["element_size"] = int(val)
             elif arg == "--model":
-                if val not in ("adaptive", "static", "plane-static", "segment-static", "context-static"):
+                if val not in ("adaptive", "static", "plane-static", "segment-static", "context-static", "auto"):
                     return None
                 opts["model"] = val
             elif arg == "--filter":
@@ -104,6 +111,8 @@ def parse(argv):
         return None  # the tables live in the container, and the static decoder has no table form for stored blocks
     if opts.get("model") == "context-static" and (opts["block_size"] == 0 or opts.get("stored") or opts.get("element_size", 1) != 1):
         return None  # the tables live in the container; a table per preceding byte, of the bytes as they are
+    if opts.get("model") == "auto" and (opts["block_size"] == 0 or opts.get("stored") or "segment_blocks" in opts):
+        return None  # the choice is recorded as the chosen model's container; stored blocks and G are not chosen (nor the filter: below)
     if "segment_blocks" in opts:
         k, r = divmod(opts["segment_blocks"], 64 * opts.get("element_size", 1))
         if opts.get("model") != "segment-static" or r or not 1 <= k < 1 << 24:

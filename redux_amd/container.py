@@ -386,6 +386,42 @@ def header_is_wellformed(buf):
     return True
 
 
+def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False):
+    """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
+    table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
+    api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
+    because only the tables of contexts that occur are recorded."""
+    if model not in api.MODELS or nblocks < 1:
+        raise api.InvalidInput()
+    E = api._check_element_size(element_size)
+    n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
+    if model == "static":
+        n += TABLE
+    elif model == "plane-static":
+        n += E * TABLE
+    elif model == "segment-static":
+        G = api.default_segment_blocks(E) if segment_blocks is None else segment_blocks
+        n += max(1, -(-nblocks // G)) * E * TABLE
+    elif model == "context-static":
+        if context_cums is None:
+            raise api.InvalidInput()
+        n += len(_pack_context_tables(context_cums))
+    return n
+
+
+def estimate_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, segment_blocks=None, models=None, checksum=False):
+    """-> {model: estimated container bytes}: api.estimate_payload's estimate of the payloads plus overhead_bytes, which is
+    exact, for each model of `models` (None: api.estimate_candidates(element_size)).  Nothing is coded."""
+    payload, context_cums = api._estimate(data, block_size, params, element_size, segment_blocks, models)
+    nb = max(1, -(-len(data) // block_size))
+    return {m: payload[m] + overhead_bytes(m, nb, element_size, segment_blocks, context_cums, checksum) for m in payload}
+
+
+def choose_model(estimates):
+    """The model with the smallest estimate; ties go to the earlier of api.MODELS."""
+    return min(estimates, key=lambda m: (estimates[m], api.MODELS.index(m)))
+
+
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
                    stored=False, segment_blocks=None, filter=None):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
@@ -399,9 +435,16 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     filter "delta" (element_size 1 / 2 / 4 / 8, model "adaptive", not stored): the delta filter for integer series in front of
     the layout, version 6.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
-    (api.context_static_tables, default total), version 7.  Nothing picks it for the caller: it pays from about half a
-    megabyte of text upward."""
+    (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
+    only model "auto" picks it for the caller.
+    model "auto" (not stored, no filter, no segment_blocks): the model with the smallest estimate_bytes codes the data
+    (choose_model), and the container is that model's: no version of its own, nothing new to decode."""
     api._check_filter(filter, model == "adaptive" and not stored)
+    if model == "auto":
+        if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) or stored \
+                or segment_blocks is not None:
+            raise api.InvalidInput()
+        model = choose_model(estimate_bytes(data, block_size, params, element_size, checksum=checksum))
     if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) \
             or model not in ("adaptive", "static", "plane-static", "segment-static", "context-static") \
             or (model in ("static", "context-static") and (element_size != 1 or stored)) \

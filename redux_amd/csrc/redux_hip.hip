@@ -18,6 +18,7 @@
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
 //   redux_context_static.hpp  k_context_hist / k_*_context_static: the static coder with a table per preceding byte
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
+//   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -43,6 +44,7 @@
 #include "redux_context_static.hpp"
 #include "redux_crc.hpp"
 #include "redux_store.hpp"
+#include "redux_cost.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -3522,5 +3524,99 @@ int redux_gen_zipf_dev(void *d_out, uint64_t len, uint64_t first_byte, uint64_t 
 }
 
 const uint32_t *redux_zipf_thresholds(void) { return h_zipf; }
+
+// ---- size estimates (redux_cost.hpp) ---------------------------------------------------------------------------------
+// what the adaptive estimate needs of the parameters: the fast kernels' model (8-bit symbols, code_bits <= 32), and a block
+// of `longest` bytes that cannot freeze it: the total starts at 257 and grows by one per symbol, and a frozen model's cost
+// depends on the order of the bytes
+static int adaptive_cost_check(const redux_params *p, uint64_t longest)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (is_any(p) || 256 + longest >= (1ull << p->freq_bits) - 1)
+        return REDUX_UNSUPPORTED;
+    return REDUX_OK;
+}
+
+int redux_adaptive_cost_from_counts(const redux_params *p, const uint64_t *counts, uint64_t n, double *bits)
+{
+    if (!p || (n && (!counts || !bits)))
+        return REDUX_INVALID_INPUT;
+    uint64_t longest = 0;
+    for (uint64_t r = 0; r < n; r++) {
+        unsigned __int128 sum = 0;
+        for (int s = 0; s < 256; s++)
+            sum += counts[256 * r + s];
+        const uint64_t len = sum >> 62 ? 1ull << 62 : (uint64_t)sum; // (saturated: any such row freezes the model)
+        longest = len > longest ? len : longest;
+    }
+    int st = adaptive_cost_check(p, longest);
+    if (st != REDUX_OK)
+        return st;
+    int          sign;
+    const double lg257 = lgamma_r(257.0, &sign);
+    for (uint64_t r = 0; r < n; r++) {
+        uint64_t len = 0;
+        double   sum = 0;
+        for (int s = 0; s < 256; s++) {
+            const uint64_t c = counts[256 * r + s];
+            len += c;
+            if (c > 1)
+                sum += lgamma_r((double)c + 1.0, &sign);
+        }
+        bits[r] = (lgamma_r((double)len + 258.0, &sign) - lg257 - sum) * kInvLn2;
+    }
+    return REDUX_OK;
+}
+
+int redux_table_cost_from_counts(const uint64_t *counts, const uint32_t *cum, uint64_t n, double *bits)
+{
+    if (n && (!counts || !cum || !bits))
+        return REDUX_INVALID_INPUT;
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t *c = counts + 256 * r;
+        const uint32_t *t = cum + 258 * r;
+        const uint32_t  T = t[257];
+        const double    log2T = T ? log2((double)T) : 0.0;
+        double          sum = 0;
+        for (int s = 0; s < 256; s++)
+            sum += table_cost_term(c[s], t[s], t[s + 1], log2T);
+        bits[r] = T ? sum : INFINITY;
+    }
+    return REDUX_OK;
+}
+
+int redux_block_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, void *d_bits, void *stream)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || !d_bits || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    BlockCostArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.nblocks    = redux_block_count(in_len, block_size);
+    a.block_size = block_size;
+    a.bits       = (double *)d_bits;
+    const uint64_t cap  = (uint64_t)kHistWgsPerCu * cu_count();
+    const uint32_t grid = (uint32_t)(a.nblocks < cap ? a.nblocks : cap);
+    k_block_cost<<<grid, 64, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_table_cost_dev(const void *d_counts, const void *d_cum, uint64_t n, void *d_bits, void *stream)
+{
+    if (n && (!d_counts || !d_cum || !d_bits))
+        return REDUX_INVALID_INPUT;
+    if (n == 0)
+        return REDUX_OK;
+    k_table_cost<<<(uint32_t)(n < 65536 ? n : 65536), 64, 0, (hipStream_t)stream>>>((const unsigned long long *)d_counts,
+                                                                                   (const uint32_t *)d_cum, n, (double *)d_bits);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
 
 } // extern "C"
