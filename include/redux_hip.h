@@ -419,6 +419,61 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
                               uint32_t *block_crc);
 
+/* ---- XOR-against-base filter for series of snapshots -------------------------------------------
+ * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its
+ * base model, optimizer state, a KV cache against its earlier self -- differs from its predecessor only in the low mantissa
+ * bits.  These calls take a second buffer, the BASE, and code the bytewise XOR against it: equal sign, exponent and high
+ * mantissa bytes become zeros, which the adaptive coder writes in a fraction of a bit each.  XOR and not the modular
+ * difference of the elements: a small negative difference puts 0xFF into every upper byte, and XOR needs no element
+ * arithmetic.  Strictly opt-in, and only worth it when the base is related to the input; the decoder needs the same base.
+ * E = element_size, one of 1, 2, 4, 8; B = block_size; x = the input, len bytes; y = the base, base_len bytes, any length.
+ *   - y'[i] = y[i] for i < min(len, base_len) and 0 beyond: a base longer than the input is used up to len, a shorter one
+ *     leaves the rest of x as it is.
+ *   - d[i] = x[i] ^ y'[i] for every byte: no frames, no elements, the filter is bytewise.
+ *   - The byte-plane layout above is then applied to d (E = 1: no layout).
+ *   - The inverse undoes the layout and XORs with y' again.
+ * Blocks and frames stay independent, x == y gives all-zero coder input, and a chunk boundary of the host calls changes
+ * nothing (chunks are whole 64-block waves, so whole frames, and a chunk XORs its own share of the base).  Behind the
+ * transform is the plain adaptive coder:
+ *     stream_base_E(x, y)[b] == redux_encode_blocks(planes_E(x ^ y'))[b].
+ * Not available with the static-table models, stored blocks, the delta filter, the `_v` calls and redux_compress /
+ * redux_decompress.
+ *
+ * redux_base_check          OK for 1, 2, 4, 8, else INVALID_INPUT.
+ * redux_base_planes_dev     filter + layout (inverse = 0) or their inverse (inverse != 0) of len bytes, d_src -> d_dst, with
+ *                           d_base[0 .. base_len) (null only with base_len 0).  d_dst must overlap neither d_src nor the
+ *                           bytes of d_base that are read (INVALID_INPUT); stream-ordered, two reads and one write.
+ * redux_encode_base_dev     redux_encode_blocks_dev of the transformed input, the transformed copy carved from the FRONT of
+ *                           the workspace (redux_encode_base_workspace_bytes: for E = 1 too, the filter changes the bytes).
+ * redux_decode_base_dev     redux_decode_planes_dev's procedure: the blocks decode into a plane buffer in the workspace, a
+ *                           block that comes back OK with another size than its place gives it is reported INVALID_INPUT,
+ *                           the inverse writes d_out[0 .. out_len) and no byte outside it, for damaged streams too.  Every
+ *                           frame whose blocks are all OK holds the original bytes.
+ * redux_encode_blocks_base  host-pointer forms on the chunk pipeline of redux_encode_blocks / redux_decode_blocks: base is
+ * redux_decode_blocks_base  host memory, and a chunk's share of it travels to the device next to the chunk.  The output
+ *                           depends on neither the chunk size nor the devices of redux_host_set_devices.  block_crc may be
+ *                           null; else u32[nblocks], the CRC-32 of every block's ORIGINAL bytes, as for the delta filter.
+ */
+int      redux_base_check(uint32_t element_size);
+int      redux_base_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len,
+                               uint32_t block_size, uint32_t element_size, int inverse, void *stream);
+uint64_t redux_encode_base_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_base_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_base_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                          uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap,
+                          void *d_out_offsets /* u64[nblocks+1] */, void *d_block_status /* i32[nblocks] */,
+                          void *d_summary /* i32[2] */, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_base_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */,
+                          const void *d_base, uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                          void *d_out, void *d_out_sizes /* u32[nblocks] */, void *d_block_status, void *d_summary,
+                          void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_base(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                             uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                             int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_base(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                             uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                             uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* ---- stored blocks -----------------------------------------------------------------------------
  * A block whose stream does not shrink it can travel as its raw bytes instead (zstd raw blocks, deflate stored blocks).
  * Block b has L_b = min(B, len - b*B) bytes of coder input x' (the input for element_size 1, its byte-plane layout for

@@ -161,6 +161,14 @@ SIGNATURES = {
     "redux_decode_delta_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
     "redux_encode_blocks_delta": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_delta": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
+    "redux_base_check": (C.c_int, [_U32]),
+    "redux_base_planes_dev": (C.c_int, [_V, _V, _U64, _V, _U64, _U32, _U32, C.c_int, _V]),
+    "redux_encode_base_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_base_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_base_dev": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_base_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_base": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_base": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_gen_iid_dev": (C.c_int, [_V, _U64, _U64, _U64, _V]),
     "redux_gen_zipf_dev": (C.c_int, [_V, _U64, _U64, _U64, _V]),
     "redux_zipf_thresholds": (C.POINTER(_U32), []),

@@ -516,6 +516,17 @@ def _check_filter(filter, allowed=True):
     return True
 
 
+def _check_base(base, allowed=True):
+    """base=None, or the base of the XOR-against-base filter (include/redux_hip.h, "XOR-against-base filter"): a base where
+    the filter is not available (allowed false: a static model, stored blocks, the delta filter) is InvalidInput.  A check
+    on the arguments alone: it comes before any call into the library.  -> True when there is a base."""
+    if base is None:
+        return False
+    if not allowed:
+        raise InvalidInput()
+    return True
+
+
 STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
 
 
@@ -531,7 +542,7 @@ def _array_arg(a, dtype, nb, writable=True):
 
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
-                    store_ratio=STORE_RATIO, filter=None):
+                    store_ratio=STORE_RATIO, filter=None, base=None):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -550,11 +561,15 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     is >= store_ratio / 65536 of them.  decompress_blocks(..., stored=flags, length=...) undoes it.
     filter="delta": the delta filter for integer series in front of the layout, for any element_size (include/redux_hip.h,
     "delta filter": redux_encode_blocks_delta); decompress_blocks(..., element_size, length, filter="delta") undoes it.
-    Adaptive model only, and not with stored=."""
+    Adaptive model only, and not with stored=.
+    base: bytes-like of any length, an earlier snapshot of the same data; the XOR against it is coded, for any element_size
+    (include/redux_hip.h, "XOR-against-base filter": redux_encode_blocks_base); decompress_blocks(..., element_size, length,
+    base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context  # (the same checks: element size 1, no stored blocks, no filter)
+    xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     plane = plane or segment  # (the checks of a model that brings its own element size)
     P = _params_of(params)
@@ -587,6 +602,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     elif delta:
         st = L.redux_encode_blocks_delta(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
                                          status.ctypes.data, crc)
+    elif xbase:
+        y = _u8(base)
+        st = L.redux_encode_blocks_base(C.byref(cp), _ptr(a), len(a), _ptr(y), len(y), block_size, E, out.ctypes.data, cap,
+                                        offs.ctypes.data, status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
@@ -618,7 +637,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None):
+                      block_crc=None, stored=None, filter=None, base=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -635,13 +654,16 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
     uint8[length] in original order, as with element_size > 1.
     filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
-    for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=."""
+    for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.
+    base: the bytes compress_blocks(..., base=) was given (redux_decode_blocks_base); length is required for every
+    element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context
+    xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
-    if delta and length is None:
+    if (delta or xbase) and length is None:
         raise InvalidInput()
     plane = plane or segment
     E = _check_element_size(element_size)
@@ -673,6 +695,10 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif delta:
         st = L.redux_decode_blocks_delta(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
                                          sizes.ctypes.data, status.ctypes.data, crc)
+    elif xbase:
+        y = _u8(base)
+        st = L.redux_decode_blocks_base(C.byref(cp), _ptr(a), offs.ctypes.data, _ptr(y), len(y), length, block_size, E,
+                                        out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
@@ -873,14 +899,27 @@ def _workspace(torch, nbytes, device):
     return ws, (-ws.data_ptr()) % 256
 
 
+def _device_base(torch, base, device):
+    """base= of the device coder objects: None, or a contiguous uint8 tensor on the coder's device (else InvalidInput)"""
+    if base is None:
+        return None
+    if not isinstance(base, torch.Tensor) or not base.is_cuda or base.dtype != torch.uint8 or not base.is_contiguous() \
+            or torch.device(device).index not in (None, base.device.index):
+        raise InvalidInput()
+    return base
+
+
 class DeviceEncoder:
     """Reusable encoder for inputs of up to max_in_len bytes already resident in HBM.
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
-    on torch's current stream."""
+    on torch's current stream.  base: a uint8 device tensor of any length, an earlier snapshot of the data: encode() codes the
+    XOR against it (include/redux_hip.h, "XOR-against-base filter"); not together with filter=."""
 
-    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None):
+    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None):
+        _check_base(base, filter is None)   # (before the filter's own check: both together are refused whatever the filter)
         self.delta = _check_filter(filter)  # the delta filter in front of the layout (encode() only)
         torch = _torch()
+        self.base = _device_base(torch, base, device)  # the XOR-against-base filter in front of the layout (encode() only)
         self.P = _params_of(params)
         self.cp = self.P._c()
         L = _lib.lib()
@@ -889,7 +928,8 @@ class DeviceEncoder:
         self.block_size = int(block_size)
         self.max_in_len = int(max_in_len)
         self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_planes_workspace_bytes
+        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_base_workspace_bytes \
+            if self.base is not None else L.redux_encode_planes_workspace_bytes
         self.ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
         self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
@@ -906,7 +946,7 @@ class DeviceEncoder:
     def encode_slots(self, d_in):
         """Phase 1 only: the coder kernel (padded slots + sizes inside the workspace)."""
         torch = _torch()
-        if self.element_size != 1 or self.delta:
+        if self.element_size != 1 or self.delta or self.base is not None:
             raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout and the filter)
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
@@ -919,7 +959,7 @@ class DeviceEncoder:
     def compact(self, n):
         """Phase 2 only: scan + gather into the dense output."""
         torch = _torch()
-        if self.element_size != 1 or self.delta:
+        if self.element_size != 1 or self.delta or self.base is not None:
             raise Unsupported()
         self.summary.zero_()
         st = _lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, C.c_void_p(self.out.data_ptr()),
@@ -943,6 +983,13 @@ class DeviceEncoder:
                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
                                                    _stream_ptr(torch))
+        elif self.base is not None:
+            st = _lib.lib().redux_encode_base_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n,
+                                                  C.c_void_p(self.base.data_ptr()), self.base.numel(), self.block_size,
+                                                  self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
+                                                  C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
+                                                  C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
+                                                  _stream_ptr(torch))
         elif self.element_size == 1:
             st = _lib.lib().redux_encode_blocks_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
                                                     C.c_void_p(self.out.data_ptr()), self.out_cap,
@@ -963,11 +1010,14 @@ class DeviceEncoder:
 class DeviceDecoder:
     """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
     layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes.  filter="delta": the
-    streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size."""
+    streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size.  base: the uint8 device
+    tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=."""
 
-    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None):
+    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None):
+        _check_base(base, filter is None)
         self.delta = _check_filter(filter)
         torch = _torch()
+        self.base = _device_base(torch, base, device)
         self.P = _params_of(params)
         self.cp = self.P._c()
         L = _lib.lib()
@@ -975,7 +1025,7 @@ class DeviceDecoder:
         self.element_size = _check_element_size(element_size)
         self.block_size = int(block_size)
         self.max_blocks = int(max_blocks)
-        if self.element_size == 1 and not self.delta:
+        if self.element_size == 1 and not self.delta and self.base is None:
             self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
         else:
             self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
@@ -995,7 +1045,7 @@ class DeviceDecoder:
         L = _lib.lib()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
-        if (length is None and (self.element_size > 1 or self.delta)) \
+        if (length is None and (self.element_size > 1 or self.delta or self.base is not None)) \
                 or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)):
             raise InvalidInput()
         if length is not None:
@@ -1006,8 +1056,11 @@ class DeviceDecoder:
                 self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
             self.summary.zero_()
             decode_dev = L.redux_decode_delta_dev if self.delta else L.redux_decode_planes_dev
+            with_base = ()
+            if self.base is not None:
+                decode_dev, with_base = L.redux_decode_base_dev, (C.c_void_p(self.base.data_ptr()), self.base.numel())
             st = decode_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
-                            C.c_void_p(d_offsets.data_ptr()), int(length), self.block_size, self.element_size,
+                            C.c_void_p(d_offsets.data_ptr()), *with_base, int(length), self.block_size, self.element_size,
                             C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
                             C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
                             C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
@@ -1402,6 +1455,26 @@ def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
     with torch.cuda.device(t.device):
         _raise(_lib.lib().redux_delta_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
                                                  1 if inverse else 0, _stream_ptr(torch)))
+    return t
+
+
+def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None):
+    """The XOR against d_base followed by the byte-plane layout (include/redux_hip.h, "XOR-against-base filter") of a uint8
+    device tensor, or their inverse: redux_base_planes_dev on torch's current stream.  d_base: a uint8 tensor of any length
+    on the same device.  out: as for planes()."""
+    torch = _torch()
+    E = _check_element_size(element_size)
+    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
+    assert d_base.dtype == torch.uint8 and d_base.is_contiguous() and d_base.device == d_src.device
+    if block_size <= 0:
+        raise InvalidInput()
+    n = d_src.numel()
+    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
+    with torch.cuda.device(t.device):
+        _raise(_lib.lib().redux_base_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(d_base.data_ptr()) if d_base.numel() else None,
+                                                d_base.numel(), C.c_void_p(t.data_ptr()), n, block_size, E, 1 if inverse else 0,
+                                                _stream_ptr(torch)))
     return t
 
 

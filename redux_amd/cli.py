@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta]
+                            [--filter delta] [--base <base file>]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -47,13 +47,20 @@ little-endian unsigned elements instead of the elements, frame by frame of the b
 for integer series whose values are large but close to their neighbours -- timestamps, sorted indices, offsets, counters,
 sampled signals.  Floating-point data and text get larger with it, so it is never chosen for you.  -d reads it from the
 container.  `--filter` with `--block-size 0`, `--stored` or a `--model` other than adaptive is a usage error.
+`--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
+XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
+fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
+CRC-32).  A base of another length is fine: what lies past its end is coded as it is.  With -d, `--base FILE` supplies the
+base of a version 8 container: a missing, different or too short base, and a base given for any other input, is a
+decompression error (exit 3).  With -c, `--base` with `--block-size 0`, `--stored`, `--filter` or any `--model` other than
+adaptive (auto included: the base is never chosen for you) is a usage error; a base file that cannot be opened is exit 2.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>]")
+         "[--filter <delta>] [--base <base file>]")
 
 
 def parse(argv):
@@ -68,7 +75,7 @@ def parse(argv):
             opts["stored"] = True
         elif arg == "-d":
             opts["compress"] = False
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base"):
             val = next(it, None)
             if val is None:
                 return None
@@ -88,6 +95,8 @@ def parse(argv):
                 if val != "delta":
                     return None
                 opts["filter"] = val
+            elif arg == "--base":
+                opts["base"] = val
             elif arg == "--segment-blocks":
                 if not val.isdigit() or not 0 < int(val) < 1 << 32:
                     return None
@@ -123,6 +132,9 @@ def parse(argv):
         return None  # the bitmap lives in the container, and the static decoder has no table form
     if "filter" in opts and (opts["block_size"] == 0 or opts.get("stored") or opts.get("model", "adaptive") != "adaptive"):
         return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
+    if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
+                                               or opts.get("model", "adaptive") != "adaptive"):
+        return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only
     return None if opts["compress"] is None else opts
 
 
@@ -136,6 +148,13 @@ def main(argv=None):
     except OSError as e:
         print(f"Error while opening input file {opts['input']}: {e}", file=sys.stderr)
         return 2
+    base = None
+    if "base" in opts:
+        try:
+            base = open(opts["base"], "rb").read()
+        except OSError as e:
+            print(f"Error while opening base file {opts['base']}: {e}", file=sys.stderr)
+            return 2
     try:
         sink = sys.stdout.buffer if opts["output"] is None else open(opts["output"], "wb")
     except OSError as e:
@@ -153,7 +172,7 @@ def main(argv=None):
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
-                                                opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"))
+                                                opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base)
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)
@@ -163,10 +182,12 @@ def main(argv=None):
             # container: a truncated or damaged body is reported as such (exit 3), not decoded as garbage.
             is_container = container.header_is_wellformed(data)
             if is_container:
-                out = container.decompress_bytes(data)
+                out = container.decompress_bytes(data, base)
                 sink.write(out)
                 i_n, o_n = len(data), len(out)
             else:
+                if base is not None:  # (a raw reference stream was not written against a base)
+                    raise api.InvalidInput()
                 o = io.BytesIO()
                 i_n, o_n = api.decompress(io.BytesIO(data), o, api.AdaptiveTreeModel.new(params))
                 sink.write(o.getvalue())

@@ -8,15 +8,17 @@ Layout (little-endian):
     0   4  magic  b"RDXB"
     4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
            5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
-           7 = context-static: a static table per preceding byte)
+           7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
+           layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
            the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
-           0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000
+           0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
+   (version 8 only) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
@@ -57,7 +59,16 @@ is not recorded, and reading rebuilds it, so text pays for its 60 to 100 context
 257 .. min(2^16, freq_max), a frequency of 0, a row that does not sum to total - 1 and a section that ends early are
 InvalidInput.  The marker nibble 7 of the word at offset 12 is required.  It has no stored blocks (no 0x47 / 0x57).
 
-Bit 0x10 of the version byte (versions 0x11 to 0x17: versions 1 to 7 with checksums) means a table of nblocks
+Version 8 holds streams of the adaptive coder behind the XOR-against-base filter for series of snapshots
+(include/redux_hip.h, "XOR-against-base filter"): the header is followed by the base record, then come version 2's sections;
+the payloads are the streams of input ^ base in the byte-plane layout (no layout for E = 1), and decoding needs the same
+base: decompress_bytes(buf, base=...) refuses, before any GPU call, a missing base, one shorter than base_used and one whose
+first base_used bytes have another CRC-32 (InvalidInput); a longer one is fine.  The record's base_used above the total is
+InvalidInput, a truncated record Eof.  The marker nibble 8 of the word at offset 12 is required: no other version's word
+carries it.  It has no stored blocks (no 0x48 / 0x58).  Without base= the writers emit exactly the bytes they emitted
+before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x18: versions 1 to 8 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -71,6 +82,7 @@ padding bits must be 0 (else InvalidInput); a truncated bitmap is Eof.  The stat
 blocks.  Without stored=True the writers emit exactly the bytes they emitted before the flag existed.
 """
 import struct
+import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -85,6 +97,9 @@ VERSION_PLANE_STATIC = 4
 VERSION_SEGMENT_STATIC = 5
 VERSION_DELTA = 6
 VERSION_CONTEXT_STATIC = 7
+VERSION_BASE = 8
+BASE_MARK = 0x80000000  # version 8's word at offset 12: BASE_MARK | E
+BASE_RECORD = struct.Struct("<QI")  # version 8, after the header: base_used, CRC-32 of base[:base_used]
 CONTEXT_MARK = 0x70000000  # version 7's word at offset 12
 DELTA_MARK = 0x60000000  # version 6's word at offset 12: DELTA_MARK | E
 SEGMENT_MARK = 0x50000000  # version 5's word at offset 12: SEGMENT_MARK | k << 4 | E
@@ -105,7 +120,7 @@ def _raw_lengths(nblocks, block_size, total):
     return np.clip(total - o, 0, block_size)
 
 
-def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None):
+def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -114,11 +129,21 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     substitute for a context without bytes are dropped).
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
-    filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored)."""
+    filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored).
+    base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
+    zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter)."""
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
     context = isinstance(params, api.ContextStaticModel)
+    xbase = api._check_base(base, not (static or plane or segment or context or stored is not None or filter is not None))
     delta = api._check_filter(filter, not (static or plane or segment or context or stored is not None))
+    if xbase:
+        try:
+            base_used, base_crc = (int(v) for v in base)
+        except (TypeError, ValueError):
+            raise api.InvalidInput()
+        if not 0 <= base_used <= total_len or not 0 <= base_crc < 1 << 32:
+            raise api.InvalidInput()
     if element_size not in (1,) + ELEMENT_SIZES or ((static or context) and element_size != 1) \
             or ((plane or segment) and element_size not in (1, params.element_size)):
         raise api.InvalidInput()
@@ -141,6 +166,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_DELTA, DELTA_MARK | element_size
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
+    if xbase:
+        ver, res = VERSION_BASE, BASE_MARK | element_size
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -157,6 +184,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver |= STORED_FLAG
         bitmap = np.packbits(f.astype(np.uint8), bitorder="little").tobytes()
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
+    if xbase:
+        head += BASE_RECORD.pack(base_used, base_crc)
     if static:
         head += params.cum.astype("<u4").tobytes()
     if plane or segment:
@@ -220,14 +249,16 @@ def _version_ok(ver, res):
         or (layout == VERSION_SEGMENT_STATIC and not ver & STORED_FLAG and res >> 28 == 5 and res & 0xF in (1,) + ELEMENT_SIZES
             and res >> 4 & 0xFFFFFF >= 1) \
         or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK)
+        or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
+        or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
 # or the PlaneStaticModel of version 4's tables;
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
 # of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, else None.
-_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter")
+# base: (base_used, crc) of version 8's record, else None.
+_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base")
 
 
 def _header(b):
@@ -242,7 +273,7 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -264,8 +295,15 @@ def _parse(buf):
     raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
     b = memoryview(buf)
     ver, P, block_size, E, nblocks, total = _header(b)
-    static = crcs = stored = None
+    static = crcs = stored = base = None
     at = HEADER.size
+    if _layout(ver) == VERSION_BASE:
+        if len(b) < at + BASE_RECORD.size:
+            raise api.Eof()
+        base = BASE_RECORD.unpack_from(b, at)
+        at += BASE_RECORD.size
+        if base[0] > total:
+            raise api.InvalidInput()
     if _layout(ver) == VERSION_STATIC:
         cum, at = _take(b, at, "<u4", 258)
         try:
@@ -311,7 +349,7 @@ def _parse(buf):
             raise api.InvalidInput()
     payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
     return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored,
-                      "delta" if _layout(ver) == VERSION_DELTA else None)
+                      "delta" if _layout(ver) == VERSION_DELTA else None, base)
 
 
 def unpack(buf):
@@ -343,6 +381,12 @@ def filter(buf):
     """"delta" for a version 6 container (the delta filter for integer series), None for versions 1 to 5.  Malformed
     containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).filter
+
+
+def base(buf):
+    """(base_used, crc) of a version 8 container (the XOR-against-base filter): the bytes of the base the coder used and
+    the zlib.crc32 of them; None for versions 1 to 7.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).base
 
 
 def static_table(buf):
@@ -423,7 +467,7 @@ def choose_model(estimates):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None):
+                   stored=False, segment_blocks=None, filter=None, base=None):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -438,7 +482,10 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
     model "auto" (not stored, no filter, no segment_blocks): the model with the smallest estimate_bytes codes the data
-    (choose_model), and the container is that model's: no version of its own, nothing new to decode."""
+    (choose_model), and the container is that model's: no version of its own, nothing new to decode.
+    base (bytes-like of any length; any element_size, model "adaptive", not stored, no filter): an earlier snapshot of the
+    data; the XOR against it is coded, version 8, and decompress_bytes needs the same base."""
+    api._check_base(base, model == "adaptive" and not stored and filter is None)
     api._check_filter(filter, model == "adaptive" and not stored)
     if model == "auto":
         if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) or stored \
@@ -458,13 +505,27 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         else api.PlaneStaticModel.from_data(data, element_size, block_size, params) if model == "plane-static" \
         else api.SegmentStaticModel.template(params, element_size, segment_blocks) if model == "segment-static" \
         else api.ContextStaticModel.from_data(data, block_size, params) if model == "context-static" else params
-    out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter)
-    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter)
+    record = None
+    if base is not None:
+        base = api._u8(base)[: len(data)]  # (what the coder uses of it)
+        record = (len(base), zlib.crc32(base))
+    out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter,
+                                       base=base)
+    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record)
 
 
-def decompress_bytes(buf):
-    """container bytes -> original bytes."""
+def decompress_bytes(buf, base=None):
+    """container bytes -> original bytes.  base: the bytes a version 8 container was written against (at least its
+    base_used bytes of them; more is fine), and None for every other version: a missing, short or different base, and a base
+    given for another version, are InvalidInput before anything is decoded."""
     c = _parse(buf)
+    if (base is None) != (c.base is None):
+        raise api.InvalidInput()
+    if c.base is not None:
+        base = api._u8(base)
+        if len(base) < c.base[0] or zlib.crc32(base[: c.base[0]]) != c.base[1]:
+            raise api.InvalidInput()
+        base = base[: c.base[0]]
     # A stream of s bytes can decode to far more than s bytes (64 KiB of one symbol is ~400 bytes),
     # so only the declared total bounds the capacity; but every block's stream has at least one
     # byte, so a header that declares more blocks than there are payload bytes is malformed.
@@ -473,14 +534,14 @@ def decompress_bytes(buf):
         raise api.InvalidInput()
     got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
     segment = isinstance(c.static, api.SegmentStaticModel)
-    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None
+    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if exact:  # (the blocks decode at their real size, into out[0 .. total))
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
-                                                       stored=c.stored, filter=c.filter)
+                                                       stored=c.stored, filter=c.filter, base=base)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes

@@ -13,6 +13,7 @@
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
+//   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
@@ -38,6 +39,7 @@
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
 #include "redux_delta.hpp"
+#include "redux_base.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
 #include "redux_segment_static.hpp"
@@ -571,11 +573,61 @@ static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t b
     return REDUX_OK;
 }
 
-// redux_planes_dev and redux_delta_planes_dev: the checks, then the transform's launch for the element size
-static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
-                         int inverse, void *stream)
+// the base filter: the fused kernels take the full frames that lie inside the base when block size and all three pointers
+// are 16-byte multiples, one workgroup per 256 groups; the byte kernels take the rest up to the end of the frame the base
+// ends in (or of the input); whole frames past the base have nothing to XOR and go to the layout alone (launch_planes)
+template <int E>
+static int launch_base(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
+                       bool inverse, hipStream_t s)
 {
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+    const uint64_t frame = (uint64_t)E * block_size;
+    BaseArgs a;
+    a.src          = (const uint8_t *)d_src;
+    a.base         = (const uint8_t *)d_base;
+    a.dst          = (uint8_t *)d_dst;
+    a.block_size   = block_size;
+    a.frame_groups = block_size / 16;
+    a.len          = len;
+    a.base_len     = base_len < len ? base_len : len;
+    const bool     aligned = block_size % 16 == 0 && (((uintptr_t)d_src | (uintptr_t)d_base | (uintptr_t)d_dst) & 15) == 0;
+    const uint64_t nfast   = aligned ? a.base_len / frame : 0;
+    a.groups = nfast * a.frame_groups;
+    a.first  = nfast * frame;
+    a.end    = (a.base_len + frame - 1) / frame * frame; // the end of the frame the base ends in
+    a.end    = a.end < len ? a.end : len;
+    if (nfast) {
+        const uint64_t wgs = (a.groups + 255) / 256;
+        if (wgs > 0x7FFFFFFFull)
+            return REDUX_UNSUPPORTED;
+        if (inverse)
+            k_base_unplanes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
+        else
+            k_base_planes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
+    }
+    if (a.first < a.end) {
+        const uint64_t wgs  = (a.end - a.first + 255) / 256;
+        const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
+        if (inverse)
+            k_base_unplanes_bytes<E><<<grid, 256, 0, s>>>(a);
+        else
+            k_base_planes_bytes<E><<<grid, 256, 0, s>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    if (a.end < len) { // (a.end is a whole number of frames here: the layout of the rest is the rest of the layout)
+        if constexpr (E == 1)
+            HIP_TRY(hipMemcpyAsync(a.dst + a.end, a.src + a.end, len - a.end, hipMemcpyDeviceToDevice, s));
+        else
+            return launch_planes<E>(a.src + a.end, a.dst + a.end, len - a.end, block_size, inverse, s);
+    }
+    return REDUX_OK;
+}
+
+// redux_planes_dev, redux_delta_planes_dev and redux_base_planes_dev: the checks, then the transform's launch for the
+// element size.  base: the XOR-against-base filter with d_base[0 .. base_len) (not together with delta).
+static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+                         int inverse, void *stream, bool base = false, const void *d_base = nullptr, uint64_t base_len = 0)
+{
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
         return REDUX_INVALID_INPUT;
     if (len == 0)
         return REDUX_OK;
@@ -584,6 +636,18 @@ static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t le
         return REDUX_INVALID_INPUT;
     hipStream_t s = (hipStream_t)stream;
     const bool  inv = inverse != 0;
+    if (base) {
+        const uintptr_t y0 = (uintptr_t)d_base;
+        const uint64_t  used = base_len < len ? base_len : len;
+        if (used && y0 < d0 + len && d0 < y0 + used) // (nor may the destination lie over the bytes of the base that are read)
+            return REDUX_INVALID_INPUT;
+        switch (element_size) {
+        case 1: return launch_base<1>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        case 2: return launch_base<2>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        case 4: return launch_base<4>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        default: return launch_base<8>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        }
+    }
     if (delta)
         switch (element_size) {
         case 1: return launch_delta<1>(d_src, d_dst, len, block_size, inv, s);
@@ -601,20 +665,24 @@ static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t le
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
 // What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with the delta filter
-// in front of it or not.  The layout of single bytes is the identity; the filter over single bytes is not.
+// or the XOR-against-base filter in front of it, or neither.  The layout of single bytes is the identity; a filter over
+// single bytes is not.
 struct Layout {
-    uint32_t E;
-    bool     delta;
-    bool     identity() const { return !delta && E == 1; }
+    uint32_t    E;
+    bool        delta;
+    bool        xor_base = false;   // the base filter, with d_base[0 .. base_len) on the device (not together with delta)
+    const void *d_base   = nullptr;
+    uint64_t    base_len = 0;
+    bool        identity() const { return !delta && !xor_base && E == 1; }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(delta, d_src, d_dst, len, block_size, E, 0, stream);
+        return transform_dev(delta, d_src, d_dst, len, block_size, E, 0, stream, xor_base, d_base, base_len);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(delta, d_src, d_dst, len, block_size, E, 1, stream);
+        return transform_dev(delta, d_src, d_dst, len, block_size, E, 1, stream, xor_base, d_base, base_len);
     }
 };
 
@@ -1546,7 +1614,7 @@ static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *c
 static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
                               uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr,
-                              const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {})
+                              const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {}, host::BaseIo base = {})
 {
     if (params != REDUX_OK)
         return params;
@@ -1559,7 +1627,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
     return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
-                               block_crc, stored, tables); // redux_host.hpp
+                               block_crc, stored, tables, base); // redux_host.hpp
 }
 
 int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
@@ -2037,7 +2105,8 @@ static int encode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in))
+    if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in) ||
+        (L.xor_base && L.base_len && !L.d_base))
         return REDUX_INVALID_INPUT;
     Staged x;
     if ((st = layout_stage(L, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x)) != REDUX_OK)
@@ -2055,7 +2124,7 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
     if (st != REDUX_OK)
         return st;
     if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status ||
-        (out_len && !d_out))
+        (out_len && !d_out) || (L.xor_base && L.base_len && !L.d_base))
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
     const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
@@ -2087,6 +2156,16 @@ int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void 
 
 // The coders of the chunked host calls (redux_host.hpp).  The transformed copy of a chunk goes in front of the adaptive
 // coder's workspace; a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64.
+// The base filter's layout takes the chunk's share of the base from the slot (host::BaseIo).
+static Layout layout_of_slot(Layout L, const host::Slot &s)
+{
+    if (L.xor_base) {
+        L.d_base   = s.d_base.p;
+        L.base_len = s.base_len;
+    }
+    return L;
+}
+
 static host::EncodeCoder layout_encoder(const redux_params *p, uint32_t block_size, Layout L)
 {
     const host::EncodeCoder plain = adaptive_encoder(p, block_size);
@@ -2095,8 +2174,8 @@ static host::EncodeCoder layout_encoder(const redux_params *p, uint32_t block_si
                 ws += L.copy_bytes(max_in);
             },
             [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return encode_layout_dev(L, p, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p, s.d_sum.p, ws,
-                                         ws_bytes, st);
+                return encode_layout_dev(layout_of_slot(L, s), p, s.d_in.p, len, block_size, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                         s.d_sum.p, ws, ws_bytes, st);
             }};
 }
 
@@ -2105,8 +2184,8 @@ static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_si
 {
     return {[=](uint64_t cb) { return redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, L.E); },
             [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
-                return decode_layout_dev(L, p, s.d_in.p, s.d_off.p, out_bytes, block_size, s.d_out.p, s.d_sz.p, s.d_st.p, s.d_sum.p,
-                                         ws, ws_bytes, st);
+                return decode_layout_dev(layout_of_slot(L, s), p, s.d_in.p, s.d_off.p, out_bytes, block_size, s.d_out.p, s.d_sz.p, s.d_st.p,
+                                         s.d_sum.p, ws, ws_bytes, st);
             },
             true};
 }
@@ -2208,6 +2287,72 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
                               block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, true}), block_crc);
+}
+
+// ---- XOR-against-base filter (redux_base.hpp) ------------------------------------------------------
+int redux_base_check(uint32_t element_size) { return redux_planes_check(element_size); }
+
+int redux_base_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
+                          uint32_t element_size, int inverse, void *stream)
+{
+    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream, true, d_base, base_len);
+}
+
+// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
+uint64_t redux_encode_base_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_base_check(element_size) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    return ws ? Layout{element_size, false, true}.copy_bytes(in_len) + ws : 0;
+}
+
+uint64_t redux_decode_base_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+// (the inverse writes a byte of d_out for every byte of the plane buffer it reads, so d_out[0 .. out_len) and nothing else)
+int redux_encode_base_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                          uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                          void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(Layout{element_size, false, true, d_base, base_len}, p, d_in, in_len, block_size, d_out, out_cap,
+                             d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_base_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_base, uint64_t base_len,
+                          uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
+                          void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(Layout{element_size, false, true, d_base, base_len}, p, d_in, d_in_offsets, out_len, block_size, d_out,
+                             d_out_sizes, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_base(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                             uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                             int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_base_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) || (base_len && !base))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               layout_encoder(p, block_size, Layout{element_size, false, true}), block_crc, nullptr, {},
+                               host::BaseIo{base, base_len, true}); // redux_host.hpp
+}
+
+int redux_decode_blocks_base(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                             uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                             uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && (redux_base_check(element_size) != REDUX_OK || (base_len && !base)))
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, false, true}), block_crc, nullptr,
+                              {}, host::BaseIo{base, base_len, true});
 }
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------

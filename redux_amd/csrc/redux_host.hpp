@@ -139,14 +139,16 @@ struct Buf {
 };
 
 struct Slot {          // one chunk in flight
-    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab, d_crc, d_stf;                              // device
+    Buf d_in, d_ws, d_out, d_off, d_sz, d_st, d_sum, d_used, d_tab, d_crc, d_stf, d_base;                      // device
     Buf h_off{true}, h_sz{true}, h_st{true}, h_sum{true}, h_used{true}, h_tab{true}, h_crc{true}, h_stf{true}; // pinned mirrors of the small arrays
     hipEvent_t done = nullptr; // recorded after the chunk's kernels
     // (d_stf / h_stf: the stored-block flags, u8 per block)
+    // (d_base: the chunk's share of the base of the XOR-against-base filter, base_len bytes of it: BaseIo)
+    uint64_t base_len = 0;
 
-    std::array<Buf *, 19> bufs()
+    std::array<Buf *, 20> bufs()
     {
-        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &d_crc, &d_stf,
+        return {&d_in, &d_ws, &d_out, &d_off, &d_sz, &d_st, &d_sum, &d_used, &d_tab, &d_crc, &d_stf, &d_base,
                 &h_off, &h_sz, &h_st, &h_sum, &h_used, &h_tab, &h_crc, &h_stf};
     }
 };
@@ -300,7 +302,7 @@ static void ctx_trim_locked(Ctx &c)
     if (!c.ready)
         return;
     for (Slot &s : c.slot)
-        for (Buf *b : {&s.d_in, &s.d_ws, &s.d_out})
+        for (Buf *b : {&s.d_in, &s.d_ws, &s.d_out, &s.d_base})
             if (b->cap > kTrimBytes)
                 free_buf(*b);
 }
@@ -704,6 +706,22 @@ struct SegmentTablesIo {
     uint32_t *at(uint64_t b0) const { return cum + b0 / G * E * 258ull; }
 };
 
+// The XOR-against-base filter (include/redux_hip.h): the call's base, base_len bytes of caller memory next to its len bytes
+// of original data.  A chunk that holds original bytes [o0, o0 + n) owns base[o0 .. min(o0 + n, base_len)): it is staged
+// through the pinned ring into the slot's d_base, which only these calls allocate, and the chunk's coder finds it there with
+// its length in s.base_len.  on false: the call has no base.
+struct BaseIo {
+    const uint8_t *p   = nullptr;
+    uint64_t       len = 0;
+    bool           on  = false;
+    uint64_t share(uint64_t o0, uint64_t n) const { return !on || len <= o0 ? 0 : len - o0 < n ? len - o0 : n; }
+    int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t o0, uint64_t n, CopyPool &pool, uint64_t &piece_no) const
+    {
+        s.base_len = share(o0, n);
+        return s.base_len ? stage_h2d(c, pool, piece_no, s.d_base.p, p + o0, s.base_len, st) : REDUX_OK;
+    }
+};
+
 // ================================================================================================
 // encode: chunk k = blocks [k * cb, k * cb + nb) of the input -> its streams at their place in the dense output
 // ================================================================================================
@@ -719,6 +737,7 @@ struct EncodeChunks {
     uint32_t          *block_crc; // may be null: CRC-32 of each input block (redux_crc.hpp), on the staged chunk
     uint8_t           *stored;    // may be null: the stored-block flags the coder leaves in s.d_stf (redux_store.hpp)
     SegmentTablesIo    tables;    // cum may be null: the segment tables the coder leaves in s.d_tab
+    BaseIo             base;      // on: the chunk's share of the base, staged to s.d_base next to its input
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -749,11 +768,17 @@ struct EncodeChunks {
             if (r2 != REDUX_OK)
                 return r2;
         }
+        if (rc == REDUX_OK && base.on) {
+            const int r2 = grow_buf(c, s.d_base, max_in + 16);
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
     {
-        return stage_h2d(c, pool, piece_no, s.d_in.p, in + b0 * (uint64_t)block_size, len_of(b0, nb), st);
+        const int rc = stage_h2d(c, pool, piece_no, s.d_in.p, in + b0 * (uint64_t)block_size, len_of(b0, nb), st);
+        return rc != REDUX_OK || !base.on ? rc : base.stage(c, s, st, b0 * (uint64_t)block_size, len_of(b0, nb), pool, piece_no);
     }
     int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
     {
@@ -800,9 +825,9 @@ struct EncodeChunks {
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr,
-                         uint8_t *stored = nullptr, SegmentTablesIo tables = {})
+                         uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {})
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables, base};
     return run_chunks(op);
 }
 
@@ -823,6 +848,7 @@ struct DecodeChunks {
     uint32_t          *block_crc; // may be null: CRC-32 of what each block decoded to (redux_crc.hpp), on the chunk's output
     const uint8_t     *stored;    // may be null: stored-block flags, staged to s.d_stf with the chunk's offsets (redux_store.hpp)
     SegmentTablesIo    tables;    // cum may be null: the segment tables, staged to s.d_tab with the chunk's offsets
+    BaseIo             base;      // on: the share of the base that lies next to the chunk's output, staged to s.d_base
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -860,6 +886,11 @@ struct DecodeChunks {
             if (r2 != REDUX_OK)
                 return r2;
         }
+        if (rc == REDUX_OK && base.on) {
+            const int r2 = grow_buf(c, s.d_base, cb * (uint64_t)block_size + 16);
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         return rc != REDUX_OK || !block_crc ? rc : grow_bufs(c, {{&s.d_crc, cb * 4}, {&s.h_crc, cb * 4}});
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
@@ -882,7 +913,8 @@ struct DecodeChunks {
             memcpy(s.h_tab.p, tables.at(b0), tables.bytes(nb));
             HOST_TRY(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, tables.bytes(nb), hipMemcpyHostToDevice, st));
         }
-        return stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
+        const int rc = stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
+        return rc != REDUX_OK || !base.on ? rc : base.stage(c, s, st, b0 * (uint64_t)block_size, chunk_out(b0, nb), pool, piece_no);
     }
     int launch(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
     {
@@ -917,9 +949,10 @@ struct DecodeChunks {
 
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                          uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
-                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {})
+                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {})
 {
-    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored, tables};
+    DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored, tables,
+                    base};
     return run_chunks(op);
 }
 

@@ -14,6 +14,7 @@
 //   redux::hip::compress_blocks_v / decompress_blocks_v     many independent inputs in one launch (tests/corpora.rs:32-85)
 //   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
+//   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
 //   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
 //   redux::hip::compress_blocks_segment_static / decompress_blocks_segment_static   static tables per block range
@@ -237,6 +238,47 @@ inline std::vector<std::uint8_t> decompress_blocks_delta(const Blocks &streams, 
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_delta(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
                                     sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// A snapshot behind the XOR-against-base filter (include/redux_hip.h, "XOR-against-base filter"): base is an earlier
+// snapshot of the same data, of any length; the bytewise XOR against it is coded in the byte-plane layout of element_size
+// 1, 2, 4 or 8.  Opt-in, and the decoder needs the same base.
+inline Blocks compress_blocks_base(const std::uint8_t *in, std::uint64_t len, const std::uint8_t *base, std::uint64_t base_len,
+                                   std::uint32_t block_size, std::uint32_t element_size, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_base(&cp, in, len, base, base_len, block_size, element_size, b.data.data(), b.data.size(),
+                                   b.offsets.data(), nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse, with the same base: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_base(const Blocks &streams, const std::uint8_t *base, std::uint64_t base_len,
+                                                        std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                                        const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_base(&cp, streams.data.data(), streams.offsets.data(), base, base_len, len, block_size, element_size,
+                                   out.data(), sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }
