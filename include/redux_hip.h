@@ -437,7 +437,7 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
  * transform is the plain adaptive coder:
  *     stream_base_E(x, y)[b] == redux_encode_blocks(planes_E(x ^ y'))[b].
  * Not available with the static-table models, stored blocks, the delta filter, the `_v` calls and redux_compress /
- * redux_decompress.
+ * redux_decompress.  Constant blocks (below) can be skipped behind it.
  *
  * redux_base_check          OK for 1, 2, 4, 8, else INVALID_INPUT.
  * redux_base_planes_dev     filter + layout (inverse = 0) or their inverse (inverse != 0) of len bytes, d_src -> d_dst, with
@@ -516,6 +516,62 @@ int redux_encode_blocks_stored(const redux_params *p, const uint8_t *in, uint64_
 int redux_decode_blocks_stored(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *stored,
                                uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
                                uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
+/* ---- constant blocks ---------------------------------------------------------------------------
+ * A block whose bytes are all equal can travel as that one byte and skip the coder in both directions: behind the
+ * XOR-against-base filter every unchanged region of a snapshot is such a block, which the coder would still write in
+ * about 300 bytes per 64 KiB and at coder rate.  Strictly opt-in; stored blocks handle the incompressible end, this the
+ * other one.  x' is the coder input: the input itself for element_size 1, its byte-plane layout for E = 2, 4, 8, or the
+ * layout of x ^ base' when a base is given (the XOR-against-base filter above; base_len 0 means no base, d_base / base may
+ * then be null).  Block b has L_b = min(B, len - b*B) bytes of x'.
+ *     const_b  <=>  L_b >= 1  and  all L_b bytes of block b are equal      (a 1-byte block is constant; the empty
+ *                                                                           input's one empty block is not)
+ *   - If const_b, payload_b is that one byte and the size entry is 1.
+ *   - Otherwise payload_b is the stream the plain, planes or base call writes for block b, bit for bit.
+ *   - Flags are u8, 0 (coded) or 1 (constant), one per block.
+ *   - Streams and flags depend on neither the chunk size nor the devices.
+ * Coverage: the adaptive model with symbol_bits 8 and code_bits <= 32, as for stored blocks (other valid parameters are
+ * UNSUPPORTED); any element_size of 1, 2, 4, 8; with or without a base; with or without per-block CRCs (of the ORIGINAL
+ * bytes, as for the base calls).  Not available with stored blocks, the delta filter, the static-table models, the `_v`
+ * calls and redux_compress / redux_decompress.
+ *
+ * redux_const_blocks_dev    the detection alone (k_const_select) over any buffer: d_flags[b] for the nblocks =
+ *                           redux_block_count(in_len, B) blocks of d_in; one read of the buffer at most (a block is left at
+ *                           the first difference found), any alignment, stream-ordered.
+ * redux_encode_const_workspace_bytes  what redux_encode_const_dev needs, with or without a base; 0 if unsupported.
+ * redux_decode_const_workspace_bytes  what redux_decode_const_dev needs for out_len bytes; 0 if unsupported.
+ * redux_encode_const_dev    x' at the front of the workspace, the detection (d_const[b] is written), then the table form of
+ *                           the coder over the blocks that are left; a constant block gets size 1 and status OK, and its
+ *                           byte is copied from x'.  out_cap as in the plain call.  The table encoder's limit applies: an
+ *                           input of 4 GiB or more is UNSUPPORTED (the host-pointer form chunks far below it).
+ * redux_decode_const_dev    the inverse: nblocks = redux_block_count(out_len, B); d_out[0 .. out_len) in original order and
+ *                           no byte outside it.  The coded blocks decode through the table form of the adaptive decoders,
+ *                           a constant block is a fill of its L_b bytes.  d_const is untrusted: a flag other than 0 / 1, a
+ *                           constant block whose payload is not exactly 1 byte and a constant flag on a block with L_b = 0
+ *                           are INVALID_INPUT for that block (size 0, nothing written); an OK block of another length than
+ *                           its place is INVALID_INPUT as in the planes call.  d_summary (if given) is overwritten with
+ *                           the failing blocks only.
+ * redux_encode_blocks_const / redux_decode_blocks_const  host-pointer forms on the chunk pipeline; the flags travel per
+ *                           chunk as the stored flags do, a chunk's share of the base as in the base calls.  block_crc may
+ *                           be NULL. */
+int      redux_const_blocks_dev(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_flags /* u8[nblocks] */, void *stream);
+uint64_t redux_encode_const_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_const_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_const_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                           uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap,
+                           void *d_out_offsets /* u64[nblocks+1] */, void *d_const /* u8[nblocks] */,
+                           void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */, void *d_workspace,
+                           uint64_t workspace_bytes, void *stream);
+int redux_decode_const_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */,
+                           const void *d_const /* u8[nblocks] */, const void *d_base, uint64_t base_len, uint64_t out_len,
+                           uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                           void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_const(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                              uint8_t *const_flags, int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_const(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *const_flags,
+                              const uint8_t *base, uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                              uint8_t *out, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
 /* ---- per-block CRC-32 checksums ---------------------------------------------------------------
  * crc[b] = CRC-32/ISO-HDLC -- the zlib / gzip / PNG CRC (reflected polynomial 0xEDB88320, init and xorout 0xFFFFFFFF),

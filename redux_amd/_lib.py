@@ -169,6 +169,13 @@ SIGNATURES = {
     "redux_decode_base_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
     "redux_encode_blocks_base": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_base": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
+    "redux_const_blocks_dev": (C.c_int, [_V, _U64, _U32, _V, _V]),
+    "redux_encode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_const_dev": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_const_dev": (C.c_int, [_PP, _V, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_const": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V]),
+    "redux_decode_blocks_const": (C.c_int, [_PP, _V, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_gen_iid_dev": (C.c_int, [_V, _U64, _U64, _U64, _V]),
     "redux_gen_zipf_dev": (C.c_int, [_V, _U64, _U64, _U64, _V]),
     "redux_zipf_thresholds": (C.POINTER(_U32), []),

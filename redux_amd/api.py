@@ -527,6 +527,17 @@ def _check_base(base, allowed=True):
     return True
 
 
+def _check_constant(constant, allowed=True):
+    """constant=None / False, or the constant-block option (include/redux_hip.h, "constant blocks"): the option where it
+    is not available (allowed false: a static model, stored blocks, the delta filter, the `_v` calls) is InvalidInput.  A
+    check on the arguments alone: it comes before any call into the library.  -> True when the option is on."""
+    if constant is None or constant is False:
+        return False
+    if not allowed:
+        raise InvalidInput()
+    return True
+
+
 STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
 
 
@@ -542,7 +553,7 @@ def _array_arg(a, dtype, nb, writable=True):
 
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
-                    store_ratio=STORE_RATIO, filter=None, base=None):
+                    store_ratio=STORE_RATIO, filter=None, base=None, constant=None):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -564,11 +575,17 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     Adaptive model only, and not with stored=.
     base: bytes-like of any length, an earlier snapshot of the same data; the XOR against it is coded, for any element_size
     (include/redux_hip.h, "XOR-against-base filter": redux_encode_blocks_base); decompress_blocks(..., element_size, length,
-    base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=."""
+    base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=.
+    constant: a np.uint8[nblocks] the same call fills with the constant-block flags (include/redux_hip.h, "constant
+    blocks": redux_encode_blocks_const), or True: the flags are then allocated here and returned as a fourth value.  A block
+    of the coder's input whose bytes are all equal has that one byte as its payload and skips the coder;
+    decompress_blocks(..., element_size, length, constant=flags) undoes it.  With or without base=; adaptive model only, and
+    not with stored= or filter=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context  # (the same checks: element size 1, no stored blocks, no filter)
+    const = _check_constant(constant, not (static or plane or segment or stored is not None or filter is not None))
     xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     plane = plane or segment  # (the checks of a model that brings its own element size)
@@ -587,6 +604,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     nb = L.redux_block_count(len(a), block_size)
     crc = _array_arg(block_crc, np.uint32, nb)
     flags = _array_arg(stored, np.uint8, nb)
+    if const:
+        cflags = np.zeros(nb, dtype=np.uint8) if constant is True else constant
+        cptr = _array_arg(cflags, np.uint8, nb)
     cap = (L.redux_static_encode_bound if static or plane else L.redux_encode_bound)(C.byref(cp), len(a), block_size)
     out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nb + 1, dtype=np.uint64)
@@ -602,6 +622,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     elif delta:
         st = L.redux_encode_blocks_delta(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
                                          status.ctypes.data, crc)
+    elif const:
+        y = _u8(base) if xbase else _u8(b"")
+        st = L.redux_encode_blocks_const(C.byref(cp), _ptr(a), len(a), _ptr(y) if len(y) else None, len(y), block_size, E,
+                                         out.ctypes.data, cap, offs.ctypes.data, cptr, status.ctypes.data, crc)
     elif xbase:
         y = _u8(base)
         st = L.redux_encode_blocks_base(C.byref(cp), _ptr(a), len(a), _ptr(y), len(y), block_size, E, out.ctypes.data, cap,
@@ -623,6 +647,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
         st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
                                               offs.ctypes.data, status.ctypes.data, crc)
     _raise(st)
+    if constant is True:
+        return out[: int(offs[-1])], offs, status, cflags
     return out[: int(offs[-1])], offs, status
 
 
@@ -637,7 +663,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None):
+                      block_crc=None, stored=None, filter=None, base=None, constant=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -656,14 +682,18 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
     for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.
     base: the bytes compress_blocks(..., base=) was given (redux_decode_blocks_base); length is required for every
-    element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=."""
+    element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=.
+    constant: the np.uint8[nblocks] flags compress_blocks(..., constant=) wrote (redux_decode_blocks_const), with the
+    same base= if one was given; length is required for every element_size, and out is the original bytes.  Adaptive model
+    only, and not with stored= or filter=."""
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context
+    const = _check_constant(constant, not (static or plane or segment or stored is not None or filter is not None))
     xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
     delta = _check_filter(filter, not (static or plane or segment or stored is not None))
-    if (delta or xbase) and length is None:
+    if (delta or xbase or const) and length is None:
         raise InvalidInput()
     plane = plane or segment
     E = _check_element_size(element_size)
@@ -683,6 +713,7 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     _raise(L.redux_device_supports(C.byref(cp)))
     crc = _array_arg(block_crc, np.uint32, nb)
     flags = _array_arg(stored, np.uint8, nb, writable=False)
+    cptr = _array_arg(constant, np.uint8, nb, writable=False) if const else None
     out = np.empty(nb * block_size if length is None else max(length, 1), dtype=np.uint8)
     sizes = np.zeros(nb, dtype=np.uint32)
     status = np.zeros(nb, dtype=np.int32)
@@ -695,6 +726,10 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif delta:
         st = L.redux_decode_blocks_delta(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
                                          sizes.ctypes.data, status.ctypes.data, crc)
+    elif const:
+        y = _u8(base) if xbase else _u8(b"")
+        st = L.redux_decode_blocks_const(C.byref(cp), _ptr(a), offs.ctypes.data, cptr, _ptr(y) if len(y) else None, len(y),
+                                         length, block_size, E, out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
     elif xbase:
         y = _u8(base)
         st = L.redux_decode_blocks_base(C.byref(cp), _ptr(a), offs.ctypes.data, _ptr(y), len(y), length, block_size, E,
@@ -759,13 +794,14 @@ def block_table_v(offsets, lengths, block_size):
     return tab
 
 
-def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None):
+def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None, constant=None):
     """redux::compress of every block of every input (a list of bytes-like objects), ONE launch for all of
     them; each input is cut into blocks on its own.  Returns (dense streams uint8, offsets
     uint64[nblocks+1], status int32[nblocks], first_block int64[len(inputs)+1]): input i owns blocks
     first_block[i] .. first_block[i+1]-1.  filter: None (the `_v` calls have no delta filter: "delta" is InvalidInput)."""
     _adaptive_only(params)
     _check_filter(filter, False)
+    _check_constant(constant, False)  # (no constant blocks in the `_v` calls: InvalidInput)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -790,11 +826,12 @@ def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None):
     return out[: int(offs[-1])], offs, status, first
 
 
-def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32), check=True, filter=None):
+def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32), check=True, filter=None, constant=None):
     """The inverse of compress_blocks_v: `lengths[i]` is the decoded size of input i.  Returns (list of
     uint8 arrays, sizes uint32[nblocks], status int32[nblocks]).  filter: None ("delta" is InvalidInput)."""
     _adaptive_only(params)
     _check_filter(filter, False)
+    _check_constant(constant, False)  # (no constant blocks in the `_v` calls: InvalidInput)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -913,9 +950,13 @@ class DeviceEncoder:
     """Reusable encoder for inputs of up to max_in_len bytes already resident in HBM.
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
     on torch's current stream.  base: a uint8 device tensor of any length, an earlier snapshot of the data: encode() codes the
-    XOR against it (include/redux_hip.h, "XOR-against-base filter"); not together with filter=."""
+    XOR against it (include/redux_hip.h, "XOR-against-base filter"); not together with filter=.  constant=True: blocks of
+    the coder's input whose bytes are all equal skip the coder (include/redux_hip.h, "constant blocks"), with or without
+    base=, not together with filter=; encode() then returns the u8 flags as a fifth value."""
 
-    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None):
+    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False):
+        self.constant = _check_constant(constant, filter is None and not isinstance(
+            params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
         _check_base(base, filter is None)   # (before the filter's own check: both together are refused whatever the filter)
         self.delta = _check_filter(filter)  # the delta filter in front of the layout (encode() only)
         torch = _torch()
@@ -928,9 +969,12 @@ class DeviceEncoder:
         self.block_size = int(block_size)
         self.max_in_len = int(max_in_len)
         self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_base_workspace_bytes \
+        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_const_workspace_bytes \
+            if self.constant else L.redux_encode_base_workspace_bytes \
             if self.base is not None else L.redux_encode_planes_workspace_bytes
         self.ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
+        if self.constant and self.ws_bytes == 0:
+            raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
         self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
         self.device = torch.device(device)
         self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
@@ -938,6 +982,7 @@ class DeviceEncoder:
         self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
         self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.const_flags = torch.zeros(self.nblocks_max, dtype=torch.uint8, device=self.device) if self.constant else None
 
     def _ws_ptr(self):
         return C.c_void_p(self.ws.data_ptr() + self.ws_off)
@@ -946,7 +991,7 @@ class DeviceEncoder:
     def encode_slots(self, d_in):
         """Phase 1 only: the coder kernel (padded slots + sizes inside the workspace)."""
         torch = _torch()
-        if self.element_size != 1 or self.delta or self.base is not None:
+        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
             raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout and the filter)
         n = d_in.numel()
         assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
@@ -959,7 +1004,7 @@ class DeviceEncoder:
     def compact(self, n):
         """Phase 2 only: scan + gather into the dense output."""
         torch = _torch()
-        if self.element_size != 1 or self.delta or self.base is not None:
+        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
             raise Unsupported()
         self.summary.zero_()
         st = _lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, C.c_void_p(self.out.data_ptr()),
@@ -983,6 +1028,16 @@ class DeviceEncoder:
                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
                                                    _stream_ptr(torch))
+        elif self.constant:
+            nb = _lib.lib().redux_block_count(n, self.block_size)
+            base = (C.c_void_p(self.base.data_ptr()), self.base.numel()) if self.base is not None and self.base.numel() else (None, 0)
+            st = _lib.lib().redux_encode_const_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, *base, self.block_size,
+                                                   self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
+                                                   C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.const_flags.data_ptr()),
+                                                   C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
+                                                   self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
+            _raise(st)
+            return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary, self.const_flags[:nb]
         elif self.base is not None:
             st = _lib.lib().redux_encode_base_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n,
                                                   C.c_void_p(self.base.data_ptr()), self.base.numel(), self.block_size,
@@ -1011,9 +1066,12 @@ class DeviceDecoder:
     """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
     layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes.  filter="delta": the
     streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size.  base: the uint8 device
-    tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=."""
+    tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
+    streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags))."""
 
-    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None):
+    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False):
+        self.constant = _check_constant(constant, filter is None and not isinstance(
+            params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
         _check_base(base, filter is None)
         self.delta = _check_filter(filter)
         torch = _torch()
@@ -1025,7 +1083,12 @@ class DeviceDecoder:
         self.element_size = _check_element_size(element_size)
         self.block_size = int(block_size)
         self.max_blocks = int(max_blocks)
-        if self.element_size == 1 and not self.delta and self.base is None:
+        if self.constant:
+            self.ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
+                                                                 self.block_size, self.element_size)
+            if self.ws_bytes == 0:
+                raise Unsupported()
+        elif self.element_size == 1 and not self.delta and self.base is None:
             self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
         else:
             self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
@@ -1038,16 +1101,31 @@ class DeviceDecoder:
         self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
 
     @_on_device
-    def decode(self, d_streams, d_offsets, length=None):
+    def decode(self, d_streams, d_offsets, length=None, constant=None):
         """length: bytes of the original input; required with element_size > 1 (d_offsets then holds
-        redux_block_count(length, block_size) + 1 entries), and the result is out[:length]."""
+        redux_block_count(length, block_size) + 1 entries), and the result is out[:length].  constant: the uint8 device
+        tensor of nblocks flags the encoder returned, for a decoder made with constant=True (and only for one)."""
         torch = _torch()
         L = _lib.lib()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
-        if (length is None and (self.element_size > 1 or self.delta or self.base is not None)) \
-                or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)):
+        if (length is None and (self.element_size > 1 or self.delta or self.base is not None or self.constant)) \
+                or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)) \
+                or (constant is None) == self.constant:
             raise InvalidInput()
+        if self.constant:
+            if not isinstance(constant, torch.Tensor) or not constant.is_cuda or constant.dtype != torch.uint8 \
+                    or not constant.is_contiguous() or constant.numel() != nb:
+                raise InvalidInput()
+            self.summary.zero_()
+            base = (C.c_void_p(self.base.data_ptr()), self.base.numel()) if self.base is not None and self.base.numel() else (None, 0)
+            st = L.redux_decode_const_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()), C.c_void_p(d_offsets.data_ptr()),
+                                          C.c_void_p(constant.data_ptr()), *base, int(length), self.block_size,
+                                          self.element_size, C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
+                                          C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
+                                          C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
+            _raise(st)
+            return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
         if length is not None:
             if self.element_size == 1 and self.ws_bytes < L.redux_decode_planes_workspace_bytes(
                     C.byref(self.cp), int(length), self.block_size, 1):
@@ -1476,6 +1554,25 @@ def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None
                                                 d_base.numel(), C.c_void_p(t.data_ptr()), n, block_size, E, 1 if inverse else 0,
                                                 _stream_ptr(torch)))
     return t
+
+
+def constant_blocks(data, block_size):
+    """The constant-block flags (include/redux_hip.h, "constant blocks") of every block of block_size bytes of `data`:
+    1 where the block has at least one byte and all its bytes are equal, else 0.  A uint8 device tensor: redux_const_blocks_dev
+    on torch's current stream, -> a uint8 device tensor of nblocks flags.  Anything bytes-like: copied to cuda:0 first,
+    -> np.uint8[nblocks]."""
+    torch = _torch()
+    if block_size <= 0:
+        raise InvalidInput()
+    host = not isinstance(data, torch.Tensor)
+    d = torch.from_numpy(_u8(data).copy()).to("cuda:0") if host else data
+    assert d.dtype == torch.uint8 and d.is_contiguous() and d.is_cuda
+    nb = _lib.lib().redux_block_count(d.numel(), block_size)
+    flags = torch.empty(nb, dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        _raise(_lib.lib().redux_const_blocks_dev(C.c_void_p(d.data_ptr()) if d.numel() else None, d.numel(), block_size,
+                                                 C.c_void_p(flags.data_ptr()), _stream_ptr(torch)))
+    return flags.cpu().numpy() if host else flags
 
 
 # ---- per-block CRC-32 checksums -----------------------------------------------------------------

@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta] [--base <base file>]
+                            [--filter delta] [--base <base file>] [--skip-constant]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -54,13 +54,18 @@ CRC-32).  A base of another length is fine: what lies past its end is coded as i
 base of a version 8 container: a missing, different or too short base, and a base given for any other input, is a
 decompression error (exit 3).  With -c, `--base` with `--block-size 0`, `--stored`, `--filter` or any `--model` other than
 adaptive (auto included: the base is never chosen for you) is a usage error; a base file that cannot be opened is exit 2.
+`--skip-constant` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` and `--base` are allowed)
+leaves every block of the coder's input whose bytes are all equal out of the coder: it travels as one byte (container
+version 9) and is rebuilt by a fill.  Behind `--base` that is every unchanged region of a snapshot.  -d reads version 9
+with no flag.  `--skip-constant` with `--block-size 0`, `--stored`, `--filter` or any `--model` other than adaptive is a
+usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>] [--base <base file>]")
+         "[--filter <delta>] [--base <base file>] [--skip-constant]")
 
 
 def parse(argv):
@@ -75,6 +80,8 @@ def parse(argv):
             opts["stored"] = True
         elif arg == "-d":
             opts["compress"] = False
+        elif arg == "--skip-constant":
+            opts["skip_constant"] = True
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base"):
             val = next(it, None)
             if val is None:
@@ -135,6 +142,9 @@ def parse(argv):
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):
         return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only
+    if opts.get("skip_constant") and (not opts["compress"] or opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
+                                      or opts.get("model", "adaptive") != "adaptive"):
+        return None  # the bitmap lives in the container, and only the adaptive coder has the table form in both directions
     return None if opts["compress"] is None else opts
 
 
@@ -172,7 +182,8 @@ def main(argv=None):
             else:
                 blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
-                                                opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base)
+                                                opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
+                                                opts.get("skip_constant", False))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

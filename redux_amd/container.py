@@ -9,16 +9,17 @@ Layout (little-endian):
     4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
            5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
-           layout)
+           layout; 9 = constant blocks skipped, with or without the XOR-against-base filter)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
            the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
-           0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8
+           0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
+           version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0
    16   8  nblocks
    24   8  total uncompressed length
-   (version 8 only) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
+   (version 8, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
@@ -68,7 +69,16 @@ InvalidInput, a truncated record Eof.  The marker nibble 8 of the word at offset
 carries it.  It has no stored blocks (no 0x48 / 0x58).  Without base= the writers emit exactly the bytes they emitted
 before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x18: versions 1 to 8 with checksums) means a table of nblocks
+Version 9 holds streams of the adaptive coder with constant blocks skipped (include/redux_hip.h, "constant blocks"): a
+block of the coder's input -- the bytes, their byte-plane layout, or the layout of input ^ base -- whose bytes are all equal
+has that one byte as its payload.  The sections: header, version 8's base record if F is set, size table, CRC table (0x19),
+the constant bitmap of ceil(nblocks / 8) bytes (LSB first, padding bits 0), payloads.  A constant block's size entry other
+than 1 and set padding bits are InvalidInput, a truncated bitmap Eof; the base checks of version 8 apply when F = 1, and a
+base given for F = 0 is InvalidInput.  The marker nibble 9 of the word at offset 12 is required: no other version's word
+carries it.  It has no stored blocks (no 0x49 / 0x59), and 0x29 / 0x89 are InvalidInput as for every version.  Without
+skip_constant=True the writers emit exactly the bytes they emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x19: versions 1 to 9 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -98,6 +108,8 @@ VERSION_SEGMENT_STATIC = 5
 VERSION_DELTA = 6
 VERSION_CONTEXT_STATIC = 7
 VERSION_BASE = 8
+VERSION_CONST = 9
+CONST_MARK = 0x90000000  # version 9's word at offset 12: CONST_MARK | F << 4 | E, F = 1 with a base record
 BASE_MARK = 0x80000000  # version 8's word at offset 12: BASE_MARK | E
 BASE_RECORD = struct.Struct("<QI")  # version 8, after the header: base_used, CRC-32 of base[:base_used]
 CONTEXT_MARK = 0x70000000  # version 7's word at offset 12
@@ -120,7 +132,8 @@ def _raw_lengths(nblocks, block_size, total):
     return np.clip(total - o, 0, block_size)
 
 
-def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None):
+def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
+         constant=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -131,10 +144,13 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
     filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored).
     base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
-    zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter)."""
+    zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter).
+    constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
+    adaptive model, no stored, no filter); None: no bitmap."""
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
     context = isinstance(params, api.ContextStaticModel)
+    const = api._check_constant(constant, not (static or plane or segment or context or stored is not None or filter is not None))
     xbase = api._check_base(base, not (static or plane or segment or context or stored is not None or filter is not None))
     delta = api._check_filter(filter, not (static or plane or segment or context or stored is not None))
     if xbase:
@@ -168,6 +184,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if xbase:
         ver, res = VERSION_BASE, BASE_MARK | element_size
+    if const:
+        ver, res = VERSION_CONST, CONST_MARK | (1 if xbase else 0) << 4 | element_size
     crc = b""
     if block_crc is not None:
         c = np.asarray(block_crc)
@@ -182,6 +200,12 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
                 or bool((sizes[f == 1] != _raw_lengths(len(sizes), block_size, total_len)[f == 1]).any()):
             raise api.InvalidInput()
         ver |= STORED_FLAG
+        bitmap = np.packbits(f.astype(np.uint8), bitorder="little").tobytes()
+    if const:
+        f = np.asarray(constant)
+        if f.shape != (len(sizes),) or bool((f > 1).any()) or bool((sizes[f == 1] != 1).any()) \
+                or bool((_raw_lengths(len(sizes), block_size, total_len)[f == 1] == 0).any()):
+            raise api.InvalidInput()
         bitmap = np.packbits(f.astype(np.uint8), bitorder="little").tobytes()
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if xbase:
@@ -250,15 +274,17 @@ def _version_ok(ver, res):
             and res >> 4 & 0xFFFFFF >= 1) \
         or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
-        or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
+        or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
+        or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
 # or the PlaneStaticModel of version 4's tables;
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
 # of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, else None.
-# base: (base_used, crc) of version 8's record, else None.
-_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base")
+# base: (base_used, crc) of the record of version 8, or of version 9 with F = 1, else None.  constant: uint8[nblocks] of 0 / 1
+# for version 9, else None.
+_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant")
 
 
 def _header(b):
@@ -273,7 +299,7 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -295,9 +321,9 @@ def _parse(buf):
     raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
     b = memoryview(buf)
     ver, P, block_size, E, nblocks, total = _header(b)
-    static = crcs = stored = base = None
+    static = crcs = stored = base = constant = None
     at = HEADER.size
-    if _layout(ver) == VERSION_BASE:
+    if _layout(ver) == VERSION_BASE or (_layout(ver) == VERSION_CONST and HEADER.unpack_from(b, 0)[6] & 0x10):
         if len(b) < at + BASE_RECORD.size:
             raise api.Eof()
         base = BASE_RECORD.unpack_from(b, at)
@@ -347,9 +373,17 @@ def _parse(buf):
         raw = stored == 1
         if bool((sizes[raw] != _raw_lengths(nblocks, block_size, total)[raw].astype(np.uint64)).any()):
             raise api.InvalidInput()
+    if _layout(ver) == VERSION_CONST:
+        bits, at = _take(b, at, np.uint8, (nblocks + 7) // 8)
+        flags = np.unpackbits(bits, bitorder="little")
+        if bool(flags[nblocks:].any()):  # padding bits
+            raise api.InvalidInput()
+        constant = flags[:nblocks].astype(np.uint8)
+        if bool((sizes[constant == 1] != 1).any()):
+            raise api.InvalidInput()
     payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
     return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored,
-                      "delta" if _layout(ver) == VERSION_DELTA else None, base)
+                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant)
 
 
 def unpack(buf):
@@ -387,6 +421,12 @@ def base(buf):
     """(base_used, crc) of a version 8 container (the XOR-against-base filter): the bytes of the base the coder used and
     the zlib.crc32 of them; None for versions 1 to 7.  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).base
+
+
+def constant(buf):
+    """The constant-block flags (np.uint8[nblocks] of 0 / 1) a version 9 container records; None for versions 1 to 8.
+    Malformed containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).constant
 
 
 def static_table(buf):
@@ -467,7 +507,7 @@ def choose_model(estimates):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None):
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -484,7 +524,10 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     model "auto" (not stored, no filter, no segment_blocks): the model with the smallest estimate_bytes codes the data
     (choose_model), and the container is that model's: no version of its own, nothing new to decode.
     base (bytes-like of any length; any element_size, model "adaptive", not stored, no filter): an earlier snapshot of the
-    data; the XOR against it is coded, version 8, and decompress_bytes needs the same base."""
+    data; the XOR against it is coded, version 8, and decompress_bytes needs the same base.
+    skip_constant (any element_size, model "adaptive", not stored, no filter; with or without base): blocks of the coder's
+    input whose bytes are all equal travel as one byte and skip the coder in both directions, version 9."""
+    api._check_constant(skip_constant or None, model == "adaptive" and not stored and filter is None)
     api._check_base(base, model == "adaptive" and not stored and filter is None)
     api._check_filter(filter, model == "adaptive" and not stored)
     if model == "auto":
@@ -509,15 +552,18 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     if base is not None:
         base = api._u8(base)[: len(data)]  # (what the coder uses of it)
         record = (len(base), zlib.crc32(base))
+    cflags = np.zeros(nb, dtype=np.uint8) if skip_constant else None
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter,
-                                       base=base)
-    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record)
+                                       base=base, constant=cflags)
+    return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record,
+                constant=cflags)
 
 
 def decompress_bytes(buf, base=None):
-    """container bytes -> original bytes.  base: the bytes a version 8 container was written against (at least its
-    base_used bytes of them; more is fine), and None for every other version: a missing, short or different base, and a base
-    given for another version, are InvalidInput before anything is decoded."""
+    """container bytes -> original bytes.  base: the bytes a version 8 container, or a version 9 container with a base
+    record, was written against (at least its base_used bytes of them; more is fine), and None for every other container: a
+    missing, short or different base, and a base given for a container without a record, are InvalidInput before anything is
+    decoded."""
     c = _parse(buf)
     if (base is None) != (c.base is None):
         raise api.InvalidInput()
@@ -534,14 +580,15 @@ def decompress_bytes(buf, base=None):
         raise api.InvalidInput()
     got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
     segment = isinstance(c.static, api.SegmentStaticModel)
-    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None
+    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None \
+        or c.constant is not None
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if exact:  # (the blocks decode at their real size, into out[0 .. total))
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
-                                                       stored=c.stored, filter=c.filter, base=base)
+                                                       stored=c.stored, filter=c.filter, base=base, constant=c.constant)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes

@@ -19,6 +19,7 @@
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
 //   redux_context_static.hpp  k_context_hist / k_*_context_static: the static coder with a table per preceding byte
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
+//   redux_const.hpp    k_const_select / k_const_table / k_const_fill: constant blocks, one byte for a block of equal bytes
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
@@ -46,6 +47,7 @@
 #include "redux_context_static.hpp"
 #include "redux_crc.hpp"
 #include "redux_store.hpp"
+#include "redux_const.hpp"
 #include "redux_cost.hpp"
 
 #include "../../include/redux_hip.h"
@@ -3552,6 +3554,243 @@ int redux_decode_blocks_stored(const redux_params *p, const uint8_t *in, const u
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_cap, out_sizes,
                               block_status, nullptr, stored_decoder(p, block_size, element_size), block_crc, stored);
+}
+
+// ---- constant blocks (redux_const.hpp) ------------------------------------------------------------
+// the coders of stored blocks: the ones whose kernels have the table form in both directions
+static int const_check(const redux_params *p, uint32_t block_size, uint32_t element_size) { return stored_check(p, block_size, element_size); }
+
+// x' of a call: the byte-plane layout, behind the XOR against the base when there is one (base_len 0: no base)
+static Layout const_layout(uint32_t element_size, const void *d_base, uint64_t base_len)
+{
+    return base_len ? Layout{element_size, false, true, d_base, base_len} : Layout{element_size, false};
+}
+
+static int launch_const_select(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_flags, hipStream_t s)
+{
+    ConstSelectArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.flags      = (uint8_t *)d_flags;
+    a.nblocks    = redux_block_count(in_len, block_size);
+    a.in_len     = in_len;
+    a.block_size = block_size;
+    const uint64_t wgs = (a.nblocks + kConstWaves - 1) / kConstWaves;
+    k_const_select<<<(uint32_t)(wgs < (1u << 20) ? wgs : (1u << 20)), 64 * kConstWaves, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+int redux_const_blocks_dev(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_flags, void *stream)
+{
+    if (block_size == 0 || !d_flags || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    return launch_const_select(d_in, in_len, block_size, d_flags, (hipStream_t)stream);
+}
+
+static uint64_t const_front_bytes(uint64_t in_len, uint32_t block_size)
+{
+    return planes_copy_bytes(in_len) + store_table_bytes(redux_block_count(in_len, block_size));
+}
+
+// [x' (always: the size does not depend on whether a base is given)] [the coder blocks' table] [the adaptive encoder's
+// workspace for whole blocks: the table form sizes its launch by entries, redux_encode_blocks_v_dev]
+uint64_t redux_encode_const_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (const_check(p, block_size, element_size) != REDUX_OK)
+        return 0;
+    return const_front_bytes(in_len, block_size) +
+           redux_encode_workspace_bytes(p, redux_block_count(in_len, block_size) * (uint64_t)block_size, block_size);
+}
+
+// [plane buffer (always)] [the coder blocks' table] [the adaptive decoder's workspace]
+uint64_t redux_decode_const_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    if (const_check(p, block_size, element_size) != REDUX_OK)
+        return 0;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    return planes_copy_bytes(nblocks * (uint64_t)block_size) + store_table_bytes(nblocks) + redux_decode_workspace_bytes(p, nblocks, block_size);
+}
+
+// the layout, the detection, the table of the blocks that are left, the table form of the coder over it, then size 1 for
+// the constant blocks, the scan, the compaction of the coded streams and the constant blocks' bytes
+int redux_encode_const_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                           uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                           void *d_const, void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes,
+                           void *stream)
+{
+    int st = const_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_workspace || !d_const || !d_block_status || !d_out || !d_out_offsets || (in_len && !d_in) || (base_len && !d_base))
+        return REDUX_INVALID_INPUT;
+    if (in_len > 0xFFFFFFFFull) // the table encoder's lane offsets into x' are 32-bit
+        return REDUX_UNSUPPORTED;
+    if (workspace_bytes < const_front_bytes(in_len, block_size)) // (the coder checks its own part: geometry_ws)
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (((uintptr_t)d_workspace) & 255)
+        return REDUX_INVALID_INPUT;
+    hipStream_t  s = (hipStream_t)stream;
+    const Layout L = const_layout(element_size, d_base, base_len);
+    if (in_len == 0) { // one empty block, never constant: the call without the option
+        HIP_TRY(hipMemsetAsync(d_const, 0, 1, s));
+        return encode_layout_dev(L, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary,
+                                 d_workspace, workspace_bytes, stream);
+    }
+    const uint64_t nblocks = redux_block_count(in_len, block_size);
+    const uint64_t copy    = planes_copy_bytes(in_len);
+    const void    *x       = d_in;
+    if (!L.identity()) {
+        if ((st = L.forward(d_in, d_workspace, in_len, block_size, stream)) != REDUX_OK)
+            return st;
+        x = d_workspace;
+    }
+    redux_block   *table = (redux_block *)((uint8_t *)d_workspace + copy);
+    uint8_t       *ws    = (uint8_t *)table + store_table_bytes(nblocks);
+    const uint64_t wsb   = workspace_bytes - (uint64_t)(ws - (uint8_t *)d_workspace);
+    if ((st = launch_const_select(x, in_len, block_size, d_const, s)) != REDUX_OK)
+        return st;
+    StoreTableArgs ta;
+    ta.stored     = (const uint8_t *)d_const;
+    ta.table      = table;
+    ta.nblocks    = nblocks;
+    ta.out_len    = in_len;
+    ta.block_size = block_size;
+    k_const_table<<<1, 1024, 0, s>>>(ta);
+    HIP_TRY(hipGetLastError());
+    if ((st = encode_slots_impl(p, x, in_len, block_size, table, nblocks, (block_size & 15) == 0, d_block_status, ws, wsb, stream,
+                                nblocks)) != REDUX_OK)
+        return st;
+    const Geometry g = geometry_ws(p, nblocks * (uint64_t)block_size, block_size, wsb); // (as encode_slots_impl took it)
+    ConstPlaceArgs pa;
+    pa.flags      = (const uint8_t *)d_const;
+    pa.raw        = (const uint8_t *)x;
+    pa.sizes      = (uint32_t *)(ws + g.off_sizes);
+    pa.status     = (int32_t *)d_block_status;
+    pa.offsets    = (const uint64_t *)d_out_offsets;
+    pa.out        = (uint8_t *)d_out;
+    pa.out_cap    = out_cap;
+    pa.summary    = (int32_t *)d_summary;
+    pa.nblocks    = nblocks;
+    pa.block_size = block_size;
+    const uint64_t wgs  = (nblocks + 255) / 256;
+    const uint32_t grid = (uint32_t)(wgs < 1024 ? wgs : 1024);
+    k_const_sizes<<<grid, 256, 0, s>>>(pa);
+    HIP_TRY(hipGetLastError());
+    // (from here on the table is its checked copy in the coder's workspace)
+    if ((st = compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, wsb, stream,
+                           (const redux_block *)(ws + g.off_table), nblocks)) != REDUX_OK)
+        return st;
+    k_const_place<<<grid, 256, 0, s>>>(pa);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// coded blocks through the table form of the adaptive decoders, constant ones filled, into the plane buffer (d_out where
+// the layout is the identity); then the length rule, the inverse layout and filter, and the summary
+int redux_decode_const_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_const,
+                           const void *d_base, uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                           void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary, void *d_workspace,
+                           uint64_t workspace_bytes, void *stream)
+{
+    int st = const_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (!d_workspace || !d_in_offsets || !d_const || !d_out_sizes || !d_block_status || (out_len && !d_out) || (base_len && !d_base))
+        return REDUX_INVALID_INPUT;
+    if (workspace_bytes < redux_decode_const_workspace_bytes(p, out_len, block_size, element_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    if (((uintptr_t)d_workspace) & 255)
+        return REDUX_INVALID_INPUT;
+    hipStream_t    s       = (hipStream_t)stream;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const Layout   L       = const_layout(element_size, d_base, base_len);
+    const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
+    uint8_t       *t       = L.identity() ? (uint8_t *)d_out : (uint8_t *)d_workspace;
+    redux_block   *table   = (redux_block *)((uint8_t *)d_workspace + copy);
+    uint8_t       *dws     = (uint8_t *)table + store_table_bytes(nblocks);
+
+    StoreTableArgs ta;
+    ta.stored     = (const uint8_t *)d_const;
+    ta.table      = table;
+    ta.nblocks    = nblocks;
+    ta.out_len    = out_len;
+    ta.block_size = block_size;
+    k_const_table<<<1, 1024, 0, s>>>(ta);
+    HIP_TRY(hipGetLastError());
+    // (the library's own table, as in redux_decode_stored_dev: no k_table_check)
+    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, out_len, d_out_sizes, d_block_status, nullptr, dws,
+                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr, table,
+                                (block_size & 15) == 0, nblocks, true);
+    if (st != REDUX_OK)
+        return st;
+    ConstFillArgs fa;
+    fa.in         = (const uint8_t *)d_in;
+    fa.in_offsets = (const uint64_t *)d_in_offsets;
+    fa.flags      = (const uint8_t *)d_const;
+    fa.out        = t;
+    fa.out_sizes  = (uint32_t *)d_out_sizes;
+    fa.status     = (int32_t *)d_block_status;
+    fa.nblocks    = nblocks;
+    fa.out_len    = out_len;
+    fa.block_size = block_size;
+    k_const_fill<<<(uint32_t)nblocks, 256, 0, s>>>(fa);
+    HIP_TRY(hipGetLastError());
+    return layout_decode_tail(L, L.identity() ? nullptr : t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+                              TailSummary::ZeroSummarize, stream);
+}
+
+// the chunked host calls: flags travel in the slot's d_stf as the stored flags do, a chunk's share of the base in its d_base
+static host::EncodeCoder const_encoder(const redux_params *p, uint32_t block_size, uint32_t element_size, bool with_base)
+{
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+                plain.size(redux_block_count(max_in, block_size) * (uint64_t)block_size, several, ws, bound);
+                ws += const_front_bytes(max_in, block_size);
+            },
+            [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_encode_const_dev(p, s.d_in.p, len, with_base ? s.d_base.p : nullptr, with_base ? s.base_len : 0,
+                                              block_size, element_size, s.d_out.p, bound, s.d_off.p, s.d_stf.p, s.d_st.p, s.d_sum.p,
+                                              ws, ws_bytes, st);
+            }};
+}
+
+static host::DecodeCoder const_decoder(const redux_params *p, uint32_t block_size, uint32_t element_size, bool with_base)
+{
+    return {[=](uint64_t cb) { return redux_decode_const_workspace_bytes(p, cb * (uint64_t)block_size, block_size, element_size); },
+            [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
+                return redux_decode_const_dev(p, s.d_in.p, s.d_off.p, s.d_stf.p, with_base ? s.d_base.p : nullptr,
+                                              with_base ? s.base_len : 0, out_bytes, block_size, element_size, s.d_out.p, s.d_sz.p,
+                                              s.d_st.p, s.d_sum.p, ws, ws_bytes, st);
+            },
+            true};
+}
+
+int redux_encode_blocks_const(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                              uint8_t *const_flags, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = const_check(p, block_size, element_size);
+    if (st != REDUX_OK)
+        return st;
+    if (!out || !out_offsets || !const_flags || (in_len && !in) || (base_len && !base))
+        return REDUX_INVALID_INPUT;
+    const bool with_base = base_len != 0;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               const_encoder(p, block_size, element_size, with_base), block_crc, const_flags, {},
+                               host::BaseIo{base, base_len, with_base}); // redux_host.hpp
+}
+
+int redux_decode_blocks_const(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *const_flags,
+                              const uint8_t *base, uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                              uint8_t *out, uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = const_check(p, block_size, element_size);
+    if (st == REDUX_OK && (!const_flags || (base_len && !base)))
+        st = REDUX_INVALID_INPUT;
+    const bool with_base = base_len != 0;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, const_decoder(p, block_size, element_size, with_base), block_crc, const_flags, {},
+                              host::BaseIo{base, base_len, with_base});
 }
 
 // ---- per-block CRC-32 (redux_crc.hpp) -------------------------------------------------------------

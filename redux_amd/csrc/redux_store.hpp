@@ -114,9 +114,10 @@ struct StoreTableArgs {
 // Entry j < C (C = blocks flagged 0): the j-th coded block in block order, at b * block_size with room L_b; entries C ..
 // nblocks - 1 are IDLE, so every wave that holds one holds only IDLE entries after its coded ones.  A flag other than 0 / 1
 // is no coded block (k_store_unpack reports it).
-__global__ void __launch_bounds__(1024) k_store_table(StoreTableArgs a)
+// (the body, shared with k_const_table of redux_const.hpp: the flag array is either feature's, the predicate -- flag 0 is a
+// block the coder owns -- the same)
+__device__ __forceinline__ void flags_to_table(const StoreTableArgs &a, uint64_t *part)
 {
-    __shared__ uint64_t part[1024];
     const uint32_t tid = threadIdx.x;
     const uint64_t per = (a.nblocks + 1023) / 1024;
     const uint64_t b0  = per * tid < a.nblocks ? per * tid : a.nblocks;
@@ -144,6 +145,12 @@ __global__ void __launch_bounds__(1024) k_store_table(StoreTableArgs a)
     const redux_block idle = {0, 0, REDUX_BLOCK_IDLE};
     for (uint64_t k = part[1023] + tid; k < a.nblocks; k += 1024)
         a.table[k] = idle;
+}
+
+__global__ void __launch_bounds__(1024) k_store_table(StoreTableArgs a)
+{
+    __shared__ uint64_t part[1024];
+    flags_to_table(a, part);
 }
 
 struct StoreUnpackArgs {

@@ -16,6 +16,7 @@
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
+//   redux::hip::compress_blocks_const / decompress_blocks_const     constant blocks skipped, with or without a base
 //   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
 //   redux::hip::compress_blocks_segment_static / decompress_blocks_segment_static   static tables per block range
 //   redux::hip::context_static_tables / compress_blocks_context_static / decompress_blocks_context_static   a table per preceding byte
@@ -279,6 +280,50 @@ inline std::vector<std::uint8_t> decompress_blocks_base(const Blocks &streams, c
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_base(&cp, streams.data.data(), streams.offsets.data(), base, base_len, len, block_size, element_size,
                                    out.data(), sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// Constant blocks skipped (include/redux_hip.h, "constant blocks"): a block of the coder's input -- the bytes, their
+// byte-plane layout, or the layout of input ^ base when base_len is not 0 -- whose bytes are all equal travels as that one
+// byte; `constant` receives one 0 / 1 flag per block, which the decoder needs together with the same base.  Opt-in.
+inline Blocks compress_blocks_const(const std::uint8_t *in, std::uint64_t len, const std::uint8_t *base, std::uint64_t base_len,
+                                    std::uint32_t block_size, std::uint32_t element_size, const model::Parameters &p,
+                                    std::vector<std::uint8_t> &constant)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    constant.assign(nb, 0);
+    check(redux_encode_blocks_const(&cp, in, len, base, base_len, block_size, element_size, b.data.data(), b.data.size(),
+                                    b.offsets.data(), constant.data(), nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse, with the flags and the same base: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_const(const Blocks &streams, const std::vector<std::uint8_t> &constant,
+                                                         const std::uint8_t *base, std::uint64_t base_len, std::uint64_t len,
+                                                         std::uint32_t block_size, std::uint32_t element_size,
+                                                         const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        constant.size() + 1 != streams.offsets.size() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_const(&cp, streams.data.data(), streams.offsets.data(), constant.data(), base, base_len, len, block_size,
+                                    element_size, out.data(), sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }

@@ -72,6 +72,14 @@ extern "C" {
     fn redux_decode_blocks_base(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, base: *const u8,
                                 base_len: u64, out_len: u64, block_size: u32, element_size: u32, out: *mut u8,
                                 out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // constant blocks: a block of equal bytes travels as one byte (base null only with base_len 0: no base; block_crc may
+    // be null)
+    fn redux_encode_blocks_const(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
+                                 block_size: u32, element_size: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                 const_flags: *mut u8, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_const(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, const_flags: *const u8,
+                                 base: *const u8, base_len: u64, out_len: u64, block_size: u32, element_size: u32,
+                                 out: *mut u8, out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
     fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
     fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
     fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
@@ -370,6 +378,55 @@ pub fn decompress_blocks_base(streams: &[u8], offsets: &[u64], base: &[u8], len:
         try!(status(redux_decode_blocks_base(&cp, streams.as_ptr(), offsets.as_ptr(), base.as_ptr(), base.len() as u64, len,
                                              block_size, element_size, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
                                              ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks` with constant blocks skipped (include/redux_hip.h, "constant blocks"): a block of the coder's input --
+/// the bytes, their byte-plane layout of `element_size` 1, 2, 4 or 8, or the layout of data ^ base when `base` is not empty
+/// -- whose bytes are all equal has that one byte as its payload.  Returns (streams, offsets, flags); the decoder needs the
+/// flags and the same base.  Opt-in.
+pub fn compress_blocks_const(data: &[u8], base: &[u8], block_size: u32, element_size: u32, p: &Parameters)
+                             -> Result<(Vec<u8>, Vec<u64>, Vec<u8>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        let mut flags = vec![0u8; nb];
+        try!(status(redux_encode_blocks_const(&cp, data.as_ptr(), data.len() as u64, base.as_ptr(), base.len() as u64, block_size,
+                                              element_size, out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), flags.as_mut_ptr(),
+                                              ptr::null_mut(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs, flags))
+    }
+}
+
+/// Inverse of `compress_blocks_const`, with its flags and the same `base`: `len` is the original byte count; returns the
+/// original bytes.
+pub fn decompress_blocks_const(streams: &[u8], offsets: &[u64], flags: &[u8], base: &[u8], len: u64, block_size: u32,
+                               element_size: u32, p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() || nb != flags.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_const(&cp, streams.as_ptr(), offsets.as_ptr(), flags.as_ptr(), base.as_ptr(),
+                                              base.len() as u64, len, block_size, element_size, out.as_mut_ptr(),
+                                              sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
