@@ -916,6 +916,11 @@ def _stream_ptr(torch):
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _dptr(t):
+    """a device tensor's address for a void* parameter (ctypes converts the int); NULL for a tensor without bytes"""
+    return t.data_ptr() if t.numel() else None
+
+
 def _on_device(method):
     """The C ABI launches on HIP's CURRENT device and on the stream it is handed.  A coder object
     built for cuda:1 while cuda:0 is current would run its kernels on GPU 0 against GPU 1's memory,
@@ -930,12 +935,6 @@ def _on_device(method):
     return wrapper
 
 
-def _workspace(torch, nbytes, device):
-    """(ws, ws_off): a uint8 device tensor with nbytes of room from the 256-byte boundary ws.data_ptr() + ws_off on"""
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return ws, (-ws.data_ptr()) % 256
-
-
 def _device_base(torch, base, device):
     """base= of the device coder objects: None, or a contiguous uint8 tensor on the coder's device (else InvalidInput)"""
     if base is None:
@@ -946,7 +945,98 @@ def _device_base(torch, base, device):
     return base
 
 
-class DeviceEncoder:
+def _base_pair(base):
+    """the (base, base_len) arguments of the `_dev` entry points that take a base; (NULL, 0) without one or for an empty one"""
+    return (base.data_ptr(), base.numel()) if base is not None and base.numel() else (None, 0)
+
+
+class _DeviceCoder:
+    """What the device coder objects below share: the parameters and sizes, the workspace, the encode-side buffers (out,
+    offsets, status, summary), the decode-side buffers (dec_out, dec_sizes, dec_status, dec_summary, made on first use;
+    a subclass that decodes sets dec_out_bytes), and the trailing arguments every `_dev` entry point takes.  A subclass
+    adds its tables and its C entry points.  Every buffer is read when a call is made, so a caller may swap one."""
+
+    dec_out = None  # (until the first call that decodes)
+
+    def __init__(self, params, block_size, max_in_len, device, nblocks_max=None):
+        self.P = _params_of(params)
+        self.cp = self.P._c()
+        self.block_size = int(block_size)
+        self.max_in_len = int(max_in_len)
+        self.nblocks_max = _lib.lib().redux_block_count(self.max_in_len, self.block_size) if nblocks_max is None else nblocks_max
+        self.device = _torch().device(device)
+
+    def _alloc_workspace(self, nbytes):
+        """ws_bytes of room from the 256-byte boundary ws.data_ptr() + ws_off on"""
+        torch = _torch()
+        self.ws_bytes = nbytes
+        self.ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        self.ws_off = (-self.ws.data_ptr()) % 256
+
+    def _ws_ptr(self):
+        return self.ws.data_ptr() + self.ws_off
+
+    def _alloc_encode(self, out_cap):
+        torch = _torch()
+        self.out_cap = out_cap
+        self.out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=self.device)
+        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
+        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+
+    def _new_dec_buffers(self, out_bytes):
+        torch = _torch()
+        return (torch.empty(out_bytes, dtype=torch.uint8, device=self.device),
+                torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device),
+                torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device),
+                torch.zeros(2, dtype=torch.int32, device=self.device))
+
+    def _dec_buffers(self):
+        """(out, sizes, status, summary) of the decode side"""
+        if self.dec_out is None:
+            self.dec_out, self.dec_sizes, self.dec_status, self.dec_summary = self._new_dec_buffers(self.dec_out_bytes)
+        return self.dec_out, self.dec_sizes, self.dec_status, self.dec_summary
+
+    def _enc_tail(self):
+        """out, out_cap, offsets, status, summary, ws, ws_bytes, stream: how every encode entry point ends"""
+        return (self.out.data_ptr(), self.out_cap, self.offsets.data_ptr(), self.status.data_ptr(), self.summary.data_ptr(),
+                self._ws_ptr(), self.ws_bytes, _stream_ptr(_torch()))
+
+    def _dec_tail(self):
+        """sizes, status, summary, ws, ws_bytes, stream: how every decode entry point ends, after its output"""
+        _, sizes, status, summary = self._dec_buffers()
+        return (sizes.data_ptr(), status.data_ptr(), summary.data_ptr(), self._ws_ptr(), self.ws_bytes, _stream_ptr(_torch()))
+
+    def _check_input(self, d_in):
+        """-> the input's byte count"""
+        n = d_in.numel()
+        assert d_in.dtype == _torch().uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        return n
+
+    def _check_streams(self, d_streams, d_offsets, length=None):
+        """-> the number of streams; with a length, InvalidInput unless it is that of an input of `length` bytes"""
+        torch = _torch()
+        nb = d_offsets.numel() - 1
+        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
+        if length is None:
+            assert 0 <= nb <= self.nblocks_max
+        else:
+            assert 0 <= length <= self.max_in_len
+            if nb != _lib.lib().redux_block_count(length, self.block_size):
+                raise InvalidInput()
+        return nb
+
+    def _enc_result(self, n):
+        """what encoding n bytes returns: views of this object's buffers (valid until the next call)"""
+        nb = _lib.lib().redux_block_count(n, self.block_size)
+        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+
+    def _dec_result(self, nbytes, nb, out=None):
+        d_out, sizes, status, summary = self._dec_buffers()
+        return (d_out if out is None else out)[:nbytes], sizes[:nb], status[:nb], summary
+
+
+class DeviceEncoder(_DeviceCoder):
     """Reusable encoder for inputs of up to max_in_len bytes already resident in HBM.
     Allocates once (workspace, dense output, offsets, status); encode() only enqueues kernels
     on torch's current stream.  base: a uint8 device tensor of any length, an earlier snapshot of the data: encode() codes the
@@ -961,108 +1051,68 @@ class DeviceEncoder:
         self.delta = _check_filter(filter)  # the delta filter in front of the layout (encode() only)
         torch = _torch()
         self.base = _device_base(torch, base, device)  # the XOR-against-base filter in front of the layout (encode() only)
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        P = _params_of(params)
         L = _lib.lib()
-        _raise(L.redux_device_supports(C.byref(self.cp)))
-        self.element_size = _check_element_size(element_size)  # > 1: the byte-plane layout in front of the coder
-        self.block_size = int(block_size)
-        self.max_in_len = int(max_in_len)
-        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        ws_bytes = L.redux_encode_delta_workspace_bytes if self.delta else L.redux_encode_const_workspace_bytes \
-            if self.constant else L.redux_encode_base_workspace_bytes \
-            if self.base is not None else L.redux_encode_planes_workspace_bytes
-        self.ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
-        if self.constant and self.ws_bytes == 0:
+        _raise(L.redux_device_supports(C.byref(P._c())))
+        E = self.element_size = _check_element_size(element_size)  # > 1: the byte-plane layout in front of the coder
+        super().__init__(P, block_size, max_in_len, device)
+        B = self.block_size
+        # what encode() runs: the workspace size of the entry point, the entry point, and its arguments between
+        # (cp, d_in, n) and the tail
+        if self.delta:
+            ws_bytes, self._encode_dev, self._lead = L.redux_encode_delta_workspace_bytes, L.redux_encode_delta_dev, (B, E)
+        elif self.constant:  # (the tail then holds the flags as well)
+            ws_bytes, self._encode_dev = L.redux_encode_const_workspace_bytes, L.redux_encode_const_dev
+            self._lead = (*_base_pair(self.base), B, E)
+        elif self.base is not None:
+            ws_bytes, self._encode_dev = L.redux_encode_base_workspace_bytes, L.redux_encode_base_dev
+            self._lead = (*_base_pair(self.base), B, E)
+        else:  # (element size 1: the coder without a layout)
+            ws_bytes = L.redux_encode_planes_workspace_bytes
+            self._encode_dev, self._lead = (L.redux_encode_blocks_dev, (B,)) if E == 1 else (L.redux_encode_planes_dev, (B, E))
+        ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, E)
+        if self.constant and ws_bytes == 0:
             raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
-        self.out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.device = torch.device(device)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, B)
+        self._alloc_workspace(ws_bytes)
+        self._alloc_encode(out_cap)
         self.const_flags = torch.zeros(self.nblocks_max, dtype=torch.uint8, device=self.device) if self.constant else None
 
-    def _ws_ptr(self):
-        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
+    def _plain_only(self):
+        """the two phases are the plain coder's; encode() applies the layout and the filter"""
+        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
+            raise Unsupported()
 
     @_on_device
     def encode_slots(self, d_in):
         """Phase 1 only: the coder kernel (padded slots + sizes inside the workspace)."""
-        torch = _torch()
-        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
-            raise Unsupported()  # (the phases are the plain coder's; encode() applies the layout and the filter)
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
-        st = _lib.lib().redux_encode_slots_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
-                                               C.c_void_p(self.status.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                               _stream_ptr(torch))
-        _raise(st)
+        self._plain_only()
+        n = self._check_input(d_in)
+        _raise(_lib.lib().redux_encode_slots_dev(C.byref(self.cp), d_in.data_ptr(), n, self.block_size, self.status.data_ptr(),
+                                                 self._ws_ptr(), self.ws_bytes, _stream_ptr(_torch())))
 
     @_on_device
     def compact(self, n):
         """Phase 2 only: scan + gather into the dense output."""
-        torch = _torch()
-        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
-            raise Unsupported()
+        self._plain_only()
         self.summary.zero_()
-        st = _lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, C.c_void_p(self.out.data_ptr()),
-                                                self.out_cap, C.c_void_p(self.offsets.data_ptr()),
-                                                C.c_void_p(self.status.data_ptr()),
-                                                C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                _stream_ptr(torch))
-        _raise(st)
+        _raise(_lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, *self._enc_tail()))
 
     @_on_device
     def encode(self, d_in):
         """Full pass, stream-ordered: returns (out, offsets[nblocks+1], status, summary) views
         of this encoder's buffers (valid until the next call)."""
-        torch = _torch()
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        n = self._check_input(d_in)
         self.summary.zero_()
-        if self.delta:
-            st = _lib.lib().redux_encode_delta_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
-                                                   self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                   C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                   C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                   _stream_ptr(torch))
-        elif self.constant:
-            nb = _lib.lib().redux_block_count(n, self.block_size)
-            base = (C.c_void_p(self.base.data_ptr()), self.base.numel()) if self.base is not None and self.base.numel() else (None, 0)
-            st = _lib.lib().redux_encode_const_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, *base, self.block_size,
-                                                   self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                   C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.const_flags.data_ptr()),
-                                                   C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
-                                                   self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
-            _raise(st)
-            return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary, self.const_flags[:nb]
-        elif self.base is not None:
-            st = _lib.lib().redux_encode_base_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n,
-                                                  C.c_void_p(self.base.data_ptr()), self.base.numel(), self.block_size,
-                                                  self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                  C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                  C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                  _stream_ptr(torch))
-        elif self.element_size == 1:
-            st = _lib.lib().redux_encode_blocks_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
-                                                    C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                    _stream_ptr(torch))
-        else:
-            st = _lib.lib().redux_encode_planes_dev(C.byref(self.cp), C.c_void_p(d_in.data_ptr()), n, self.block_size,
-                                                    self.element_size, C.c_void_p(self.out.data_ptr()), self.out_cap,
-                                                    C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                                    C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                                                    _stream_ptr(torch))
-        _raise(st)
-        nb = _lib.lib().redux_block_count(n, self.block_size)
-        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+        tail = self._enc_tail()
+        if self.constant:  # (the flags go between the offsets and the status)
+            tail = tail[:3] + (self.const_flags.data_ptr(),) + tail[3:]
+        _raise(self._encode_dev(C.byref(self.cp), d_in.data_ptr(), n, *self._lead, *tail))
+        res = self._enc_result(n)
+        return res + (self.const_flags[: res[2].numel()],) if self.constant else res
 
 
-class DeviceDecoder:
+class DeviceDecoder(_DeviceCoder):
     """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
     layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes.  filter="delta": the
     streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size.  base: the uint8 device
@@ -1076,29 +1126,37 @@ class DeviceDecoder:
         self.delta = _check_filter(filter)
         torch = _torch()
         self.base = _device_base(torch, base, device)
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        P = _params_of(params)
         L = _lib.lib()
-        _raise(L.redux_device_supports(C.byref(self.cp)))
+        _raise(L.redux_device_supports(C.byref(P._c())))
         self.element_size = _check_element_size(element_size)
-        self.block_size = int(block_size)
         self.max_blocks = int(max_blocks)
-        if self.constant:
-            self.ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
-                                                                 self.block_size, self.element_size)
-            if self.ws_bytes == 0:
+        super().__init__(P, block_size, self.max_blocks * int(block_size), device, nblocks_max=self.max_blocks)
+        # what decode(..., length) runs: the entry point and its arguments between the offsets and the length
+        if self.constant:  # (the flags of the call come in front of them)
+            self._decode_dev, self._lead = L.redux_decode_const_dev, _base_pair(self.base)
+            ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
+            if ws_bytes == 0:
                 raise Unsupported()
-        elif self.element_size == 1 and not self.delta and self.base is None:
-            self.ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size)
-        else:
-            self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
-                                                                  self.block_size, self.element_size)
-        self.device = torch.device(device)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-        self.out = torch.empty(self.max_blocks * self.block_size, dtype=torch.uint8, device=self.device)
-        self.sizes = torch.zeros(self.max_blocks, dtype=torch.int32, device=self.device)
-        self.status = torch.zeros(self.max_blocks, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
+        elif self.delta:
+            self._decode_dev, self._lead, ws_bytes = L.redux_decode_delta_dev, (), self._layout_ws_bytes(self.max_in_len)
+        elif self.base is not None:
+            self._decode_dev, self._lead = L.redux_decode_base_dev, _base_pair(self.base)
+            ws_bytes = self._layout_ws_bytes(self.max_in_len)
+        else:  # (element size 1: decode() without a length needs less, and the first one with a length regrows it)
+            self._decode_dev, self._lead = L.redux_decode_planes_dev, ()
+            ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size) \
+                if self.element_size == 1 else self._layout_ws_bytes(self.max_in_len)
+        self._alloc_workspace(ws_bytes)
+        self.out, self.sizes, self.status, self.summary = self._new_dec_buffers(self.max_in_len)
+
+    def _dec_buffers(self):
+        """a decoder's buffers go by their plain names and are there from the start"""
+        return self.out, self.sizes, self.status, self.summary
+
+    def _layout_ws_bytes(self, nbytes):
+        """the workspace of the entry points that undo the layout, for an input of nbytes"""
+        return _lib.lib().redux_decode_planes_workspace_bytes(C.byref(self.cp), nbytes, self.block_size, self.element_size)
 
     @_on_device
     def decode(self, d_streams, d_offsets, length=None, constant=None):
@@ -1113,71 +1171,43 @@ class DeviceDecoder:
                 or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)) \
                 or (constant is None) == self.constant:
             raise InvalidInput()
+        flags = ()
         if self.constant:
             if not isinstance(constant, torch.Tensor) or not constant.is_cuda or constant.dtype != torch.uint8 \
                     or not constant.is_contiguous() or constant.numel() != nb:
                 raise InvalidInput()
-            self.summary.zero_()
-            base = (C.c_void_p(self.base.data_ptr()), self.base.numel()) if self.base is not None and self.base.numel() else (None, 0)
-            st = L.redux_decode_const_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()), C.c_void_p(d_offsets.data_ptr()),
-                                          C.c_void_p(constant.data_ptr()), *base, int(length), self.block_size,
-                                          self.element_size, C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
-                                          C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
-                                          C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
-            _raise(st)
-            return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
-        if length is not None:
-            if self.element_size == 1 and self.ws_bytes < L.redux_decode_planes_workspace_bytes(
-                    C.byref(self.cp), int(length), self.block_size, 1):
-                self.ws_bytes = L.redux_decode_planes_workspace_bytes(C.byref(self.cp), self.max_blocks * self.block_size,
-                                                                      self.block_size, 1)
-                self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-            self.summary.zero_()
-            decode_dev = L.redux_decode_delta_dev if self.delta else L.redux_decode_planes_dev
-            with_base = ()
-            if self.base is not None:
-                decode_dev, with_base = L.redux_decode_base_dev, (C.c_void_p(self.base.data_ptr()), self.base.numel())
-            st = decode_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()),
-                            C.c_void_p(d_offsets.data_ptr()), *with_base, int(length), self.block_size, self.element_size,
-                            C.c_void_p(self.out.data_ptr()), C.c_void_p(self.sizes.data_ptr()),
-                            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()),
-                            C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes, _stream_ptr(torch))
-            _raise(st)
-            return self.out[: int(length)], self.sizes[:nb], self.status[:nb], self.summary
+            flags = (constant.data_ptr(),)
+        if length is None:
+            nbytes = nb * self.block_size
+            decode_dev, args = L.redux_decode_blocks_dev, (nb, self.block_size, self.out.data_ptr(), self.out.numel())
+        else:
+            nbytes = int(length)
+            if self.element_size == 1 and not self.constant and self.ws_bytes < self._layout_ws_bytes(nbytes):
+                self._alloc_workspace(self._layout_ws_bytes(self.max_in_len))
+            decode_dev = self._decode_dev
+            args = (*flags, *self._lead, nbytes, self.block_size, self.element_size, self.out.data_ptr())
         self.summary.zero_()
-        st = L.redux_decode_blocks_dev(C.byref(self.cp), C.c_void_p(d_streams.data_ptr()), C.c_void_p(d_offsets.data_ptr()),
-                                       nb, self.block_size, C.c_void_p(self.out.data_ptr()), self.out.numel(),
-                                       C.c_void_p(self.sizes.data_ptr()), C.c_void_p(self.status.data_ptr()),
-                                       C.c_void_p(self.summary.data_ptr()), C.c_void_p(self.ws.data_ptr() + self.ws_off),
-                                       self.ws_bytes, _stream_ptr(torch))
-        _raise(st)
-        return self.out[: nb * self.block_size], self.sizes[:nb], self.status[:nb], self.summary
+        _raise(decode_dev(C.byref(self.cp), d_streams.data_ptr(), d_offsets.data_ptr(), *args, *self._dec_tail()))
+        return self._dec_result(nbytes, nb)
 
 
-class DeviceStaticCoder:
+class DeviceStaticCoder(_DeviceCoder):
     """The coder core under a fixed frequency table (include/redux_hip.h
     "static-table model").  cum: 258 cumulative frequencies, cum[0] = 0, strictly increasing,
     cum[257] = total <= freq_max; symbol 256 is EOF.  Same buffers as DeviceEncoder/DeviceDecoder."""
 
     def __init__(self, params, cum, block_size, max_in_len, device="cuda:0"):
-        torch = _torch()
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        _torch()
+        P = _params_of(params)
         L = _lib.lib()
         self.cum = (C.c_uint32 * 258)(*[int(x) for x in cum])
-        _raise(L.redux_static_table_check(C.byref(self.cp), self.cum))
-        self.block_size = int(block_size)
-        self.max_in_len = int(max_in_len)
-        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        self.ws_bytes = L.redux_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.out_cap = L.redux_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.device = torch.device(device)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_out = None
+        _raise(L.redux_static_table_check(C.byref(P._c()), self.cum))
+        super().__init__(P, block_size, max_in_len, device)
+        ws_bytes = L.redux_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size)
+        out_cap = L.redux_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self._alloc_workspace(ws_bytes)
+        self._alloc_encode(out_cap)
+        self.dec_out_bytes = self.nblocks_max * self.block_size
 
     @classmethod
     def from_data(cls, d_in, params, block_size, max_in_len, total=None):
@@ -1186,66 +1216,43 @@ class DeviceStaticCoder:
 
     @_on_device
     def encode(self, d_in):
-        torch = _torch()
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        n = self._check_input(d_in)
         self.summary.zero_()
-        st = _lib.lib().redux_static_encode_blocks_dev(
-            C.byref(self.cp), self.cum, C.c_void_p(d_in.data_ptr()), n, self.block_size, C.c_void_p(self.out.data_ptr()),
-            self.out_cap, C.c_void_p(self.offsets.data_ptr()), C.c_void_p(self.status.data_ptr()),
-            C.c_void_p(self.summary.data_ptr()), C.c_void_p(self.ws.data_ptr() + self.ws_off), self.ws_bytes,
-            _stream_ptr(torch))
-        _raise(st)
-        nb = _lib.lib().redux_block_count(n, self.block_size)
-        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+        _raise(_lib.lib().redux_static_encode_blocks_dev(C.byref(self.cp), self.cum, d_in.data_ptr(), n, self.block_size,
+                                                         *self._enc_tail()))
+        return self._enc_result(n)
 
     @_on_device
     def decode(self, d_streams, d_offsets):
-        torch = _torch()
-        nb = d_offsets.numel() - 1
-        assert nb <= self.nblocks_max and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
-        if self.dec_out is None:
-            self.dec_out = torch.empty(self.nblocks_max * self.block_size, dtype=torch.uint8, device=self.device)
-            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_summary.zero_()
-        st = _lib.lib().redux_static_decode_blocks_dev(
-            C.byref(self.cp), self.cum, C.c_void_p(d_streams.data_ptr()), C.c_void_p(d_offsets.data_ptr()), nb,
-            self.block_size, C.c_void_p(self.dec_out.data_ptr()), self.dec_out.numel(),
-            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
-            C.c_void_p(self.dec_summary.data_ptr()), _stream_ptr(torch))
-        _raise(st)
-        return self.dec_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+        nb = self._check_streams(d_streams, d_offsets)
+        d_out, _, _, summary = self._dec_buffers()
+        summary.zero_()
+        tail = self._dec_tail()  # (this entry point takes no workspace)
+        _raise(_lib.lib().redux_static_decode_blocks_dev(C.byref(self.cp), self.cum, d_streams.data_ptr(), d_offsets.data_ptr(), nb,
+                                                         self.block_size, d_out.data_ptr(), d_out.numel(), *tail[:3], tail[-1]))
+        return self._dec_result(nb * self.block_size, nb)
 
 
-class DeviceContextStaticCoder:
+class DeviceContextStaticCoder(_DeviceCoder):
     """Context-static coding on device tensors (include/redux_hip.h, "context-static coding"): d_cum, an int32[256 * 258]
     device tensor of 256 tables with the common total `total`, stays on the device; every call checks it there."""
 
     def __init__(self, params, d_cum, total, block_size, max_in_len):
         torch = _torch()
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        P = _params_of(params)
         L = _lib.lib()
         assert d_cum.is_cuda and d_cum.dtype == torch.int32 and d_cum.is_contiguous() and d_cum.numel() == 256 * 258
         self.d_cum = d_cum
         self.total = int(total)
-        self.block_size = int(block_size)
-        self.max_in_len = int(max_in_len)
-        self.device = d_cum.device
-        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        self.ws_bytes = max(L.redux_context_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size),
-                            L.redux_context_static_decode_workspace_bytes(C.byref(self.cp), self.nblocks_max, self.block_size))
-        if self.ws_bytes == 0:
+        super().__init__(P, block_size, max_in_len, d_cum.device)
+        ws_bytes = max(L.redux_context_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size),
+                       L.redux_context_static_decode_workspace_bytes(C.byref(self.cp), self.nblocks_max, self.block_size))
+        if ws_bytes == 0:
             raise InvalidInput()
-        self.out_cap = L.redux_context_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-        self.out = torch.empty(max(self.out_cap, 1), dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_out = None
+        out_cap = L.redux_context_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self._alloc_workspace(ws_bytes)
+        self._alloc_encode(out_cap)
+        self.dec_out_bytes = max(self.nblocks_max * self.block_size, 1)
 
     @classmethod
     def from_data(cls, d_in, params, block_size, max_in_len, total=None):
@@ -1261,76 +1268,51 @@ class DeviceContextStaticCoder:
         """the tables on the host: np.uint32[256, 258]"""
         return self.d_cum.cpu().numpy().view(np.uint32).reshape(256, 258).copy()
 
-    def _ws_ptr(self):
-        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
-
     @_on_device
     def encode(self, d_in):
-        torch = _torch()
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        n = self._check_input(d_in)
         self.summary.zero_()
-        st = _lib.lib().redux_context_static_encode_dev(
-            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_in.data_ptr()) if n else None, n,
-            self.block_size, C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
-            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-            _stream_ptr(torch))
-        _raise(st)
-        nb = _lib.lib().redux_block_count(n, self.block_size)
-        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+        _raise(_lib.lib().redux_context_static_encode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, _dptr(d_in), n,
+                                                          self.block_size, *self._enc_tail()))
+        return self._enc_result(n)
 
     @_on_device
     def decode(self, d_streams, d_offsets, out=None):
         """-> (out uint8[nblocks * block_size], sizes, status, summary); block b occupies out[b * block_size:][:sizes[b]].
         out: a uint8 device tensor of at least nblocks * block_size bytes to decode into (default: the coder's own)."""
-        torch = _torch()
-        nb = d_offsets.numel() - 1
-        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= nb <= self.nblocks_max
-        if self.dec_out is None:
-            self.dec_out = torch.empty(max(self.nblocks_max * self.block_size, 1), dtype=torch.uint8, device=self.device)
-            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        d_out = self.dec_out if out is None else out
-        assert d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= nb * self.block_size
-        self.dec_summary.zero_()
-        st = _lib.lib().redux_context_static_decode_dev(
-            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
-            C.c_void_p(d_offsets.data_ptr()), nb, self.block_size, C.c_void_p(d_out.data_ptr()), nb * self.block_size,
-            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
-            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
-        _raise(st)
-        return d_out[: nb * self.block_size], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+        nb = self._check_streams(d_streams, d_offsets)
+        d_out, _, _, summary = self._dec_buffers()
+        if out is not None:
+            d_out = out
+        assert d_out.dtype == _torch().uint8 and d_out.is_contiguous() and d_out.numel() >= nb * self.block_size
+        summary.zero_()
+        _raise(_lib.lib().redux_context_static_decode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, d_streams.data_ptr(),
+                                                          d_offsets.data_ptr(), nb, self.block_size, d_out.data_ptr(),
+                                                          nb * self.block_size, *self._dec_tail()))
+        return self._dec_result(nb * self.block_size, nb, out)
 
 
-class DevicePlaneStaticCoder:
+class DevicePlaneStaticCoder(_DeviceCoder):
     """Plane-static coding on device tensors (include/redux_hip.h, "plane-static coding"): d_cum, an int32[E * 258] device
     tensor of E tables with the common total `total`, stays on the device.  Input and output are in original byte order."""
 
     def __init__(self, params, d_cum, total, element_size, block_size, max_in_len):
         torch = _torch()
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        P = _params_of(params)
         L = _lib.lib()
         self.E = _check_element_size(element_size)
         assert d_cum.is_cuda and d_cum.dtype == torch.int32 and d_cum.is_contiguous() and d_cum.numel() == self.E * 258
         self.d_cum = d_cum
         self.total = int(total)
-        self.block_size = int(block_size)
-        self.max_in_len = int(max_in_len)
-        self.device = d_cum.device
-        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
-        self.ws_bytes = max(L.redux_plane_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E),
-                            L.redux_plane_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
-        if self.ws_bytes == 0:
+        super().__init__(P, block_size, max_in_len, d_cum.device)
+        ws_bytes = max(L.redux_plane_static_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E),
+                       L.redux_plane_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
+        if ws_bytes == 0:
             raise InvalidInput()
-        self.out_cap = L.redux_plane_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
-        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_out = None
+        out_cap = L.redux_plane_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self._alloc_workspace(ws_bytes)
+        self._alloc_encode(out_cap)
+        self.dec_out_bytes = max(self.max_in_len, 1)
 
     @classmethod
     def from_data(cls, d_in, params, element_size, block_size, max_in_len, total=None):
@@ -1349,48 +1331,27 @@ class DevicePlaneStaticCoder:
         """the tables on the host: np.uint32[E, 258]"""
         return self.d_cum.cpu().numpy().view(np.uint32).reshape(self.E, 258).copy()
 
-    def _ws_ptr(self):
-        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
-
     @_on_device
     def encode(self, d_in):
-        torch = _torch()
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        n = self._check_input(d_in)
         self.summary.zero_()
-        st = _lib.lib().redux_plane_static_encode_dev(
-            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_in.data_ptr()) if n else None, n,
-            self.block_size, self.E, C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
-            C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-            _stream_ptr(torch))
-        _raise(st)
-        nb = _lib.lib().redux_block_count(n, self.block_size)
-        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+        _raise(_lib.lib().redux_plane_static_encode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, _dptr(d_in), n,
+                                                        self.block_size, self.E, *self._enc_tail()))
+        return self._enc_result(n)
 
     @_on_device
     def decode(self, d_streams, d_offsets, length):
         """-> (the original bytes uint8[length], sizes, status, summary)"""
-        torch = _torch()
-        nb = d_offsets.numel() - 1
-        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= length <= self.max_in_len
-        if nb != _lib.lib().redux_block_count(length, self.block_size):
-            raise InvalidInput()
-        if self.dec_out is None:
-            self.dec_out = torch.empty(max(self.max_in_len, 1), dtype=torch.uint8, device=self.device)
-            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_summary.zero_()
-        st = _lib.lib().redux_plane_static_decode_dev(
-            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
-            C.c_void_p(d_offsets.data_ptr()), length, self.block_size, self.E, C.c_void_p(self.dec_out.data_ptr()),
-            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
-            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
-        _raise(st)
-        return self.dec_out[:length], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+        nb = self._check_streams(d_streams, d_offsets, length)
+        d_out, _, _, summary = self._dec_buffers()
+        summary.zero_()
+        _raise(_lib.lib().redux_plane_static_decode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, d_streams.data_ptr(),
+                                                        d_offsets.data_ptr(), length, self.block_size, self.E, d_out.data_ptr(),
+                                                        *self._dec_tail()))
+        return self._dec_result(length, nb)
 
 
-class DeviceSegmentStaticCoder:
+class DeviceSegmentStaticCoder(_DeviceCoder):
     """Segment-static coding on device tensors (include/redux_hip.h, "segment-static coding").  encode_build(d_in) builds
     the tables from d_in while it codes it (redux_segment_static_build_encode_dev: one layout pass) and leaves them in
     d_cum, an int32[nseg * E * 258] device tensor; encode / decode run under the tables d_cum holds.  Input and output are
@@ -1398,31 +1359,24 @@ class DeviceSegmentStaticCoder:
 
     def __init__(self, params, element_size, block_size, max_in_len, segment_blocks=None, total=None, device="cuda:0"):
         torch = _torch()
-        self.P = _params_of(params)
-        self.cp = self.P._c()
+        P = _params_of(params)
         L = _lib.lib()
         self.E = _check_element_size(element_size)
-        self.G = SegmentStaticModel(self.P, None, self.E,
+        self.G = SegmentStaticModel(P, None, self.E,
                                     default_segment_blocks(self.E) if segment_blocks is None else segment_blocks).segment_blocks
-        self.total = _total_of(self.P, total)
-        self.block_size = int(block_size)
-        self.max_in_len = int(max_in_len)
-        self.device = torch.device(device)
-        self.nblocks_max = L.redux_block_count(self.max_in_len, self.block_size)
+        self.total = _total_of(P, total)
+        super().__init__(P, block_size, max_in_len, device)
         self.ntables_max = L.redux_segment_static_table_count(self.nblocks_max, self.E, self.G)
-        self.ws_bytes = max(L.redux_segment_static_build_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size,
-                                                                                self.E, self.G),
-                            L.redux_segment_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
-        if self.ws_bytes == 0:
+        ws_bytes = max(L.redux_segment_static_build_encode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size,
+                                                                           self.E, self.G),
+                       L.redux_segment_static_decode_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.E))
+        if ws_bytes == 0:
             raise InvalidInput()
-        self.out_cap = L.redux_segment_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
-        self.ws, self.ws_off = _workspace(torch, self.ws_bytes, self.device)
+        out_cap = L.redux_segment_static_encode_bound(C.byref(self.cp), self.max_in_len, self.block_size)
+        self._alloc_workspace(ws_bytes)
         self.d_cum = torch.zeros(self.ntables_max * 258, dtype=torch.int32, device=self.device)
-        self.out = torch.empty(self.out_cap, dtype=torch.uint8, device=self.device)
-        self.offsets = torch.zeros(self.nblocks_max + 1, dtype=torch.int64, device=self.device)
-        self.status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-        self.summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_out = None
+        self._alloc_encode(out_cap)
+        self.dec_out_bytes = max(self.max_in_len, 1)
 
     @classmethod
     def from_data(cls, d_in, params, element_size, block_size, max_in_len, segment_blocks=None, total=None):
@@ -1447,28 +1401,17 @@ class DeviceSegmentStaticCoder:
         assert c.size <= self.d_cum.numel()
         self.d_cum[: c.size] = torch.from_numpy(c.view(np.int32)).to(self.device)
 
-    def _ws_ptr(self):
-        return C.c_void_p(self.ws.data_ptr() + self.ws_off)
-
     def _encode(self, d_in, build):
-        torch = _torch()
-        n = d_in.numel()
-        assert d_in.dtype == torch.uint8 and d_in.is_contiguous() and n <= self.max_in_len
+        n = self._check_input(d_in)
         self.summary.zero_()
         L = _lib.lib()
-        tail = (C.c_void_p(self.out.data_ptr()), self.out_cap, C.c_void_p(self.offsets.data_ptr()),
-                C.c_void_p(self.status.data_ptr()), C.c_void_p(self.summary.data_ptr()), self._ws_ptr(), self.ws_bytes,
-                _stream_ptr(torch))
-        d_in_p = C.c_void_p(d_in.data_ptr()) if n else None
+        data = (_dptr(d_in), n, self.block_size, self.E, self.G)
         if build:
-            st = L.redux_segment_static_build_encode_dev(C.byref(self.cp), self.total, d_in_p, n, self.block_size, self.E, self.G,
-                                                         C.c_void_p(self.d_cum.data_ptr()), *tail)
+            st = L.redux_segment_static_build_encode_dev(C.byref(self.cp), self.total, *data, self.d_cum.data_ptr(), *self._enc_tail())
         else:
-            st = L.redux_segment_static_encode_dev(C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, d_in_p, n,
-                                                   self.block_size, self.E, self.G, *tail)
+            st = L.redux_segment_static_encode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, *data, *self._enc_tail())
         _raise(st)
-        nb = L.redux_block_count(n, self.block_size)
-        return self.out, self.offsets[: nb + 1], self.status[:nb], self.summary
+        return self._enc_result(n)
 
     @_on_device
     def encode_build(self, d_in):
@@ -1481,79 +1424,51 @@ class DeviceSegmentStaticCoder:
     @_on_device
     def decode(self, d_streams, d_offsets, length):
         """-> (the original bytes uint8[length], sizes, status, summary)"""
-        torch = _torch()
-        nb = d_offsets.numel() - 1
-        assert d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8 and 0 <= length <= self.max_in_len
-        if nb != _lib.lib().redux_block_count(length, self.block_size):
-            raise InvalidInput()
-        if self.dec_out is None:
-            self.dec_out = torch.empty(max(self.max_in_len, 1), dtype=torch.uint8, device=self.device)
-            self.dec_sizes = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_status = torch.zeros(self.nblocks_max, dtype=torch.int32, device=self.device)
-            self.dec_summary = torch.zeros(2, dtype=torch.int32, device=self.device)
-        self.dec_summary.zero_()
-        st = _lib.lib().redux_segment_static_decode_dev(
-            C.byref(self.cp), C.c_void_p(self.d_cum.data_ptr()), self.total, C.c_void_p(d_streams.data_ptr()),
-            C.c_void_p(d_offsets.data_ptr()), length, self.block_size, self.E, self.G, C.c_void_p(self.dec_out.data_ptr()),
-            C.c_void_p(self.dec_sizes.data_ptr()), C.c_void_p(self.dec_status.data_ptr()),
-            C.c_void_p(self.dec_summary.data_ptr()), self._ws_ptr(), self.ws_bytes, _stream_ptr(torch))
-        _raise(st)
-        return self.dec_out[:length], self.dec_sizes[:nb], self.dec_status[:nb], self.dec_summary
+        nb = self._check_streams(d_streams, d_offsets, length)
+        d_out, _, _, summary = self._dec_buffers()
+        summary.zero_()
+        _raise(_lib.lib().redux_segment_static_decode_dev(C.byref(self.cp), self.d_cum.data_ptr(), self.total, d_streams.data_ptr(),
+                                                          d_offsets.data_ptr(), length, self.block_size, self.E, self.G,
+                                                          d_out.data_ptr(), *self._dec_tail()))
+        return self._dec_result(length, nb)
 
 
 # ---- byte-plane layout of typed data ----------------------------------------------------------
-def planes(d_src, element_size, block_size, inverse=False, out=None):
-    """The byte-plane layout (include/redux_hip.h) of a uint8 device tensor, or its inverse: redux_planes_dev on torch's
-    current stream.  out: a uint8 tensor of the same length on the same device (allocated when None)."""
+def _transform(name, d_src, element_size, block_size, inverse, out, d_base=None):
+    """planes / delta_planes / base_planes: the C entry point `name` from d_src into `out`, on torch's current stream"""
     torch = _torch()
     E = _check_element_size(element_size)
     assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
+    assert d_base is None or (d_base.dtype == torch.uint8 and d_base.is_contiguous() and d_base.device == d_src.device)
     if block_size <= 0:
         raise InvalidInput()
     n = d_src.numel()
     t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
+    base = () if d_base is None else _base_pair(d_base)
     with torch.cuda.device(t.device):
-        _raise(_lib.lib().redux_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
-                                           1 if inverse else 0, _stream_ptr(torch)))
+        _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, E, 1 if inverse else 0,
+                                         _stream_ptr(torch)))
     return t
+
+
+def planes(d_src, element_size, block_size, inverse=False, out=None):
+    """The byte-plane layout (include/redux_hip.h) of a uint8 device tensor, or its inverse: redux_planes_dev on torch's
+    current stream.  out: a uint8 tensor of the same length on the same device (allocated when None)."""
+    return _transform("redux_planes_dev", d_src, element_size, block_size, inverse, out)
 
 
 def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The delta filter followed by the byte-plane layout (include/redux_hip.h, "delta filter") of a uint8 device tensor,
     or their inverse: redux_delta_planes_dev on torch's current stream.  out: as for planes()."""
-    torch = _torch()
-    E = _check_element_size(element_size)
-    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
-    if block_size <= 0:
-        raise InvalidInput()
-    n = d_src.numel()
-    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
-    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
-    with torch.cuda.device(t.device):
-        _raise(_lib.lib().redux_delta_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(t.data_ptr()), n, block_size, E,
-                                                 1 if inverse else 0, _stream_ptr(torch)))
-    return t
+    return _transform("redux_delta_planes_dev", d_src, element_size, block_size, inverse, out)
 
 
 def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None):
     """The XOR against d_base followed by the byte-plane layout (include/redux_hip.h, "XOR-against-base filter") of a uint8
     device tensor, or their inverse: redux_base_planes_dev on torch's current stream.  d_base: a uint8 tensor of any length
     on the same device.  out: as for planes()."""
-    torch = _torch()
-    E = _check_element_size(element_size)
-    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
-    assert d_base.dtype == torch.uint8 and d_base.is_contiguous() and d_base.device == d_src.device
-    if block_size <= 0:
-        raise InvalidInput()
-    n = d_src.numel()
-    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
-    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
-    with torch.cuda.device(t.device):
-        _raise(_lib.lib().redux_base_planes_dev(C.c_void_p(d_src.data_ptr()), C.c_void_p(d_base.data_ptr()) if d_base.numel() else None,
-                                                d_base.numel(), C.c_void_p(t.data_ptr()), n, block_size, E, 1 if inverse else 0,
-                                                _stream_ptr(torch)))
-    return t
+    return _transform("redux_base_planes_dev", d_src, element_size, block_size, inverse, out, d_base)
 
 
 def constant_blocks(data, block_size):
@@ -1570,8 +1485,7 @@ def constant_blocks(data, block_size):
     nb = _lib.lib().redux_block_count(d.numel(), block_size)
     flags = torch.empty(nb, dtype=torch.uint8, device=d.device)
     with torch.cuda.device(d.device):
-        _raise(_lib.lib().redux_const_blocks_dev(C.c_void_p(d.data_ptr()) if d.numel() else None, d.numel(), block_size,
-                                                 C.c_void_p(flags.data_ptr()), _stream_ptr(torch)))
+        _raise(_lib.lib().redux_const_blocks_dev(_dptr(d), d.numel(), block_size, flags.data_ptr(), _stream_ptr(torch)))
     return flags.cpu().numpy() if host else flags
 
 
@@ -1599,16 +1513,14 @@ def crc32_blocks(data, block_size, sizes=None):
         if sizes is None:
             n = data.numel()
             d_crc = torch.empty(L.redux_block_count(n, block_size), dtype=torch.int32, device=data.device)
-            _raise(L.redux_crc32_blocks_dev(C.c_void_p(data.data_ptr()) if n else None, n, block_size,
-                                            C.c_void_p(d_crc.data_ptr()), s))
+            _raise(L.redux_crc32_blocks_dev(_dptr(data), n, block_size, d_crc.data_ptr(), s))
         else:
             assert sizes.is_cuda and sizes.device == data.device and sizes.element_size() == 4 and sizes.is_contiguous()
             nb = sizes.numel()
             if nb * block_size > data.numel():  # (the kernel may read any byte of every block's room)
                 raise InvalidInput()
             d_crc = torch.empty(max(nb, 1), dtype=torch.int32, device=data.device)
-            _raise(L.redux_crc32_sizes_dev(C.c_void_p(data.data_ptr()), nb, block_size, C.c_void_p(sizes.data_ptr()),
-                                           C.c_void_p(d_crc.data_ptr()), s))
+            _raise(L.redux_crc32_sizes_dev(data.data_ptr(), nb, block_size, sizes.data_ptr(), d_crc.data_ptr(), s))
             d_crc = d_crc[:nb]
         return d_crc.cpu().numpy().view(np.uint32).copy()
 
