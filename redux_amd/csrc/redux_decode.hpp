@@ -21,13 +21,17 @@ namespace redux {
 // ======================================================================================
 // decode
 // ======================================================================================
-struct DecArgs {
+// what every decoder kernel takes, first in its arguments: a stream per block -> the block, its size and its status
+struct DecCore {
     const uint8_t  *in;
     const uint64_t *in_offsets; // nblocks + 1
     uint64_t        nblocks;
     uint8_t        *out;        // block b at out + b*block_size
     uint32_t       *out_sizes;
     int32_t        *status;
+};
+
+struct DecArgs : DecCore {
     const double   *rc;
     uint32_t        block_size;
     uint32_t        nfreeze;
@@ -45,6 +49,7 @@ struct DecArgs {
     // workspace is bounded whatever the capacity.
     uint32_t rc_n;
 };
+static_assert(sizeof(DecCore) == 48 && sizeof(DecArgs) == 96, "kernarg layout");
 constexpr uint32_t kDecRcWindow = 1u << 20;
 
 // The part of a block's input range its decode can read.  A range may hold any number of bytes after its stream, which

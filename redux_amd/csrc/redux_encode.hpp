@@ -32,7 +32,8 @@ __global__ void k_fill_rc(double *rc, uint32_t n)
 // ======================================================================================
 // encode
 // ======================================================================================
-struct EncArgs {
+// what every encoder kernel takes, first in its arguments: the input in blocks -> a slot, a size and a status per block
+struct EncCore {
     const uint8_t *in;
     uint64_t       in_len;
     uint64_t       nblocks;
@@ -40,6 +41,9 @@ struct EncArgs {
     uint64_t       slot_bytes;
     uint32_t      *sizes;
     int32_t       *status;
+};
+
+struct EncArgs : EncCore {
     const double  *rc;
     uint32_t       block_size;
     uint32_t       slot_cap;  // usable bytes of a slot
@@ -61,6 +65,7 @@ struct EncArgs {
     double         rc_frozen;
     uint32_t      *cstate, *cbase;
 };
+static_assert(sizeof(EncCore) == 56 && sizeof(EncArgs) == 144, "kernarg layout");
 
 // A table entry with this index is an idle lane: redux_block_table_v pads the table with them so that blocks of very
 // different lengths do not share a wave (a wave runs its fast path for as long as its shortest block lasts).  Its

@@ -153,20 +153,14 @@ __device__ __forceinline__ uint32_t gen_symbol_decode(uint32_t raw, uint32_t k)
     return (raw >> (24u - SB - r)) & ((1u << SB) - 1u);
 }
 
-struct GenEncArgs {
-    const uint8_t *in;
-    uint64_t       in_len;
-    uint64_t       nblocks;
-    uint8_t       *slots;
-    uint64_t       slot_bytes;
-    uint32_t      *sizes;
-    int32_t       *status;
+struct GenEncArgs : EncCore {
     const double  *rc;       // rc[i] = 1 / (2^SB + 1 + i), bumped (k_fill_rc_from)
     uint32_t       block_size;
     uint32_t       slot_cap;
     uint32_t       nfreeze;  // freq_max - (2^SB + 1): updates before the freeze
     uint32_t       code_bits;
 };
+static_assert(sizeof(GenEncArgs) == 80, "kernarg layout");
 
 __global__ void k_fill_rc_from(double *rc, uint32_t n, uint32_t first)
 {
@@ -502,13 +496,7 @@ __global__ void __launch_bounds__(256) k_encode_gen_pair(GenEncArgs a)
     }
 }
 
-struct GenDecArgs {
-    const uint8_t  *in;
-    const uint64_t *in_offsets; // nblocks + 1
-    uint64_t        nblocks;
-    uint8_t        *out;        // block b at out + b*block_size
-    uint32_t       *out_sizes;
-    int32_t        *status;
+struct GenDecArgs : DecCore {
     const double   *rc;
     uint32_t       *trees;      // k_decode_cells<.., GLOBAL0>: the blocks' bottom cells (k_fill_cells16)
     uint64_t       *in_used;    // optional
@@ -516,6 +504,7 @@ struct GenDecArgs {
     uint32_t        nfreeze;
     uint32_t        code_bits;
 };
+static_assert(sizeof(GenDecArgs) == 88, "kernarg layout");
 
 // (the decoder of these widths is k_decode_cells, redux_decode_cells.hpp; rounds 2 and 3 had a per-level walk here, k_decode_gen)
 

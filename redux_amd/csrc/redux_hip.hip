@@ -68,18 +68,13 @@ namespace redux {
 // ======================================================================================
 // general parameters (redux_any.hpp): one lane per block, tree in the workspace
 // ======================================================================================
-struct AnyEncArgs {
-    const uint8_t *in;
-    uint64_t       in_len, nblocks;
-    uint8_t       *slots;
-    uint64_t       slot_bytes;
-    uint32_t      *sizes;
-    int32_t       *status;
+struct AnyEncArgs : EncCore {
     uint32_t      *trees;
     uint64_t       tree_words; // u32 entries per block
     uint32_t       block_size, slot_cap;
     uint32_t       sb, fb, cb;
 };
+static_assert(sizeof(AnyEncArgs) == 96, "kernarg layout");
 
 __global__ void __launch_bounds__(64) k_encode_any(AnyEncArgs a)
 {
@@ -97,19 +92,14 @@ __global__ void __launch_bounds__(64) k_encode_any(AnyEncArgs a)
     a.status[blk] = st;
 }
 
-struct AnyDecArgs {
-    const uint8_t  *in;
-    const uint64_t *in_offsets;
-    uint64_t        nblocks;
-    uint8_t        *out;
-    uint32_t       *out_sizes;
-    int32_t        *status;
+struct AnyDecArgs : DecCore {
     uint64_t       *in_used;
     uint32_t       *trees;
     uint64_t        tree_words;
     uint32_t        block_size;
     uint32_t        sb, fb, cb;
 };
+static_assert(sizeof(AnyDecArgs) == 88, "kernarg layout");
 
 __global__ void __launch_bounds__(64) k_decode_any(AnyDecArgs a)
 {
@@ -348,8 +338,8 @@ static Geometry geometry(const redux_params *p, uint64_t in_len, uint32_t block_
 
 // The layout a launch uses in the workspace it was GIVEN.  A workspace sized for a larger input, or for a pipeline of several
 // chunks, has no room for the small-grid kernels' pairs area: the launch then runs the full-grid kernels on the layout they
-// need (same bytes out, the small-launch speed-up forgone).  Both phases of a call -- the coder and the compaction -- must
-// take this decision the same way, so it is made here from (shape, workspace size) alone.
+// need (same bytes out, the small-launch speed-up forgone).  The decision is made from (shape, workspace size) alone: once per
+// call (encode_plan), and the same way by the two calls of the split pair redux_encode_slots_dev / redux_compact_slots_dev.
 static Geometry geometry_ws(const redux_params *p, uint64_t in_len, uint32_t block_size, uint64_t workspace_bytes)
 {
     Geometry g = geometry(p, in_len, block_size);
@@ -424,8 +414,8 @@ static EncKernel pick_encode_kernel(const Geometry &g, const redux_params *p, bo
 // a decoder's geometry: no small-grid encoder, whose windows would size the reciprocal table
 static Geometry decode_geometry(const redux_params *p, uint32_t block_size) { return geometry(p, block_size, block_size, false, false); }
 
-// nslots: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice).  The one
-// call decode_blocks_dev_impl, redux_decode_kernel_name_n and redux_decode_kernel_name_table make.
+// nslots: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice).  Called by
+// decode_layout alone, which decode_blocks_dev_impl, redux_decode_kernel_name_n and redux_decode_kernel_name_table read.
 static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, uint64_t nslots, uint32_t block_size, bool table)
 {
     if (g.gen) {
@@ -455,6 +445,45 @@ static DecKernel pick_decode_kernel(const Geometry &g, const redux_params *p, ui
     if (lock)
         return p->code_bits == 32 ? DecKernel::LockCb32 : DecKernel::Lock;
     return g.u16 ? DecKernel::GenericU16 : DecKernel::GenericU32; // (u16: count < 2^17, as for the encoders)
+}
+
+// entries of the decoders' reciprocal table: what the block capacity (or the freeze point) asks for, but at most
+// kDecRcWindow + slack -- a decoder of longer blocks computes the rest itself (rc_lookup, redux_decode.hpp)
+static uint32_t dec_rc_entries(const Geometry &g)
+{
+    return (g.gen || g.rc_n <= kDecRcWindow + 32) ? g.rc_n : kDecRcWindow + 32;
+}
+
+// A decode launch in its workspace: the kernel, then [reciprocal table] [checked copy of a block table] [its bitmap], or
+// [reciprocal table] [the cell decoder's bottom cells] (11- and 12-bit symbols: gen_decode_in_workspace), or the trees of the
+// general parameters alone.  The ONE place that decides it: the size, the launch and the kernel names read these fields.
+struct DecodeLayout {
+    DecKernel kernel;
+    uint32_t  rc_n; // reciprocal entries the launch fills
+    uint64_t  off_table, off_seen, off_trees, total;
+};
+
+// nblocks: blocks (or table entries) of the launch; 0 = unknown (redux_decode_kernel_name: the full-grid choice)
+static DecodeLayout decode_layout(const Geometry &g, const redux_params *p, uint64_t nblocks, uint32_t block_size, bool table)
+{
+    DecodeLayout L = {pick_decode_kernel(g, p, nblocks, block_size, table), 0, 0, 0, 0, 0};
+    if (g.gen) {
+        L.rc_n      = g.rc_n;
+        L.off_trees = align_up((uint64_t)g.rc_n * 8, 256);
+        L.total     = L.off_trees + (gen_decode_in_workspace(p, nblocks) ? (nblocks + 63) / 64 * 64 * gen_decode_tree_bytes(p) : 0);
+    } else if (g.any) {
+        L.total = (nblocks ? nblocks : 1) * g.tree_bytes;
+    } else {
+        // room for the table of either form of a call (the size is asked for without saying which): the cell decoder of 8-bit
+        // symbols, which takes no block table, fills at least as many entries as the others (cells8_rc_entries)
+        const bool     cells8 = L.kernel == DecKernel::Cells8 || L.kernel == DecKernel::Cells8Fixup;
+        const uint32_t room   = cells8_takes(p, block_size, nblocks ? nblocks : 1, false) ? cells8_rc_entries(p, block_size) : dec_rc_entries(g);
+        L.rc_n      = cells8 ? cells8_rc_entries(p, block_size) : dec_rc_entries(g);
+        L.off_table = align_up((uint64_t)room * 8, 256);
+        L.off_seen  = L.off_table + align_up(nblocks * sizeof(redux_block), 256);
+        L.total     = L.off_seen + align_up(table_seen_words(nblocks) * 4, 256);
+    }
+    return L;
 }
 
 } // namespace redux
@@ -872,7 +901,7 @@ const char *redux_decode_kernel_name_n(const redux_params *p, const void *d_out,
     if (check_params(p) != REDUX_OK || block_size == 0)
         return "";
     (void)d_out; // every decoder takes any alignment (it only picks the store width inside the kernel)
-    return decode_kernel_name_of(pick_decode_kernel(decode_geometry(p, block_size), p, nblocks, block_size, false), p);
+    return decode_kernel_name_of(decode_layout(decode_geometry(p, block_size), p, nblocks, block_size, false).kernel, p);
 }
 
 // the launch given a block table (decode_blocks_dev_impl with d_table: the `_v` calls, redux_decode_stored_dev)
@@ -883,7 +912,7 @@ const char *redux_decode_kernel_name_table(const redux_params *p, uint32_t block
     const Geometry g = decode_geometry(p, block_size);
     if (g.gen || g.any) // (decode_blocks_dev_impl: UNSUPPORTED with a table)
         return "";
-    return decode_kernel_name_of(pick_decode_kernel(g, p, nentries, block_size, true), p);
+    return decode_kernel_name_of(decode_layout(g, p, nentries, block_size, true).kernel, p);
 }
 
 int redux_params_check(uint32_t symbol, uint32_t frequency, uint32_t code) /* model/mod.rs:64 */
@@ -924,19 +953,163 @@ uint64_t redux_encode_workspace_bytes(const redux_params *p, uint64_t in_len, ui
     return geometry(p, in_len, block_size).total;
 }
 
-// d_table != null: the block table of redux_encode_blocks_v_dev (tbl_blocks entries; in_len = bytes of d_in)
-static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
-                             const redux_block *d_table, uint64_t tbl_blocks, bool tbl_aligned16, void *d_block_status,
-                             void *d_workspace, uint64_t workspace_bytes, void *stream, uint64_t nblocks_real = 0)
+// ---- the adaptive coder's launch layer ----------------------------------------------------------------------------------
+// The plan of an encode call: its Geometry, decided ONCE from (shape, workspace size) and handed to every stage of the
+// call -- the coder, the compaction and whatever the caller runs between them.  in_len is what sizes the launch: the input
+// bytes, or entries * block_size for the table form of a call.  Refuses what geometry() cannot take.
+static int encode_plan(const redux_params *p, uint64_t in_len, uint32_t block_size, uint64_t workspace_bytes, Geometry &g)
 {
-    int st = check_params(p);
+    const int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    if (block_size == 0 || !d_workspace || !d_block_status || (in_len && !d_in))
+    if (block_size == 0)
         return REDUX_INVALID_INPUT;
-    const Geometry g = geometry_ws(p, d_table ? tbl_blocks * (uint64_t)block_size : in_len, block_size, workspace_bytes);
-    if (d_table && (g.gen || g.any || in_len > 0xFFFFFFFFull || tbl_blocks == 0)) // lane offsets into d_in are 32-bit
-        return tbl_blocks == 0 ? REDUX_INVALID_INPUT : REDUX_UNSUPPORTED;
+    g = geometry_ws(p, in_len, block_size, workspace_bytes);
+    return REDUX_OK;
+}
+
+// The table form of a call (the `_v` calls, stored and constant blocks), in both directions: slot j of the launch takes the
+// block entries[j] names.  The launch counts entries; sizes, statuses and the summary are per block.  No entries: the plain
+// form, block b at b * block_size.
+struct BlockTable {
+    const redux_block *entries   = nullptr;
+    bool               aligned16 = false; // every entry's offset is a 16-byte multiple
+    uint64_t           nblocks   = 0;     // the blocks the entries name
+    bool               trusted   = false; // the library's own, or the checked copy of a caller's: the kernels may read it
+};
+
+// the raw bytes the compaction copies for the blocks flagged in `stored` (redux_store.hpp); none: every block is its stream
+struct RawCopy {
+    const uint8_t *stored     = nullptr;
+    const void    *raw        = nullptr;
+    uint32_t       block_size = 0;
+};
+
+// what the one filler of each argument core writes
+static EncCore enc_core(const Geometry &g, const void *d_in, uint64_t in_len, uint8_t *ws, void *d_block_status)
+{
+    EncCore c;
+    c.in         = (const uint8_t *)d_in;
+    c.in_len     = in_len;
+    c.nblocks    = g.nblocks;
+    c.slots      = ws + g.off_slots;
+    c.slot_bytes = g.slot_bytes;
+    c.sizes      = (uint32_t *)(ws + g.off_sizes);
+    c.status     = (int32_t *)d_block_status;
+    return c;
+}
+
+static DecCore dec_core(const void *d_in, const void *d_in_offsets, uint64_t nblocks, void *d_out, void *d_out_sizes, void *d_block_status)
+{
+    DecCore c;
+    c.in         = (const uint8_t *)d_in;
+    c.in_offsets = (const uint64_t *)d_in_offsets;
+    c.nblocks    = nblocks;
+    c.out        = (uint8_t *)d_out;
+    c.out_sizes  = (uint32_t *)d_out_sizes;
+    c.status     = (int32_t *)d_block_status;
+    return c;
+}
+
+// A caller's block table is caller data: the kernels read a checked copy (redux_table.hpp).  t: the table as given, nentries
+// of them over `bytes` bytes of blocks; the copy goes to `copy`, the bitmap of block numbers to `seen`, and what the check
+// finds to the per-block sizes and statuses.  Returns the copy and the word k_table_verdict reads after the call's summary.
+struct CheckedTable {
+    const redux_block *entries;
+    const uint32_t    *failed;
+};
+
+static CheckedTable table_check_stage(const BlockTable &t, uint64_t nentries, uint64_t bytes, uint32_t block_size, redux_block *copy,
+                                      uint32_t *seen, uint32_t *sizes, int32_t *status, hipStream_t s)
+{
+    TableCheckArgs ta;
+    ta.in         = t.entries;
+    ta.out        = copy;
+    ta.nentries   = nentries;
+    ta.nblocks    = t.nblocks;
+    ta.bytes      = bytes;
+    ta.block_size = block_size;
+    ta.aligned16  = t.aligned16 ? 1u : 0u;
+    ta.seen       = seen;
+    ta.sizes      = sizes;
+    ta.status     = status;
+    const uint64_t n0 = std::max(t.nblocks, table_seen_words(t.nblocks));
+    k_table_prepare<<<(uint32_t)((n0 + 255) / 256), 256, 0, s>>>(ta);
+    k_table_check<<<(uint32_t)((nentries + 255) / 256), 256, 0, s>>>(ta);
+    return {copy, seen + table_seen_words(t.nblocks) - 1};
+}
+
+// The small-grid encoder (redux_coop.hpp): a block's model by 64 lanes, its chain by one.  a: the launch's arguments as for
+// the full-grid kernels; longest: the longest block of the launch.  The instances, by [code_bits 32][fix-up]([linear slots]):
+typedef void (*CoopChainFn)(EncArgs, const uint2 *);
+typedef void (*CoopStepFn)(EncArgs, EncArgs, const uint2 *, uint2 *, uint32_t);
+static constexpr CoopChainFn kCoopChain[2][2] = {{k_coop_chain<false, false>, k_coop_chain<false, true>},
+                                                 {k_coop_chain<true, false>, k_coop_chain<true, true>}};
+static constexpr CoopChainFn kCoopLastChain[2][2][2] = {
+    {{k_coop_chain<false, false, false, true>, k_coop_chain<false, false, true, true>},
+     {k_coop_chain<false, true, false, true>, k_coop_chain<false, true, true, true>}},
+    {{k_coop_chain<true, false, false, true>, k_coop_chain<true, false, true, true>},
+     {k_coop_chain<true, true, false, true>, k_coop_chain<true, true, true, true>}}};
+static constexpr CoopStepFn kCoopStep[2][2][2] = {
+    {{k_coop_step<false, false, false>, k_coop_step<false, false, true>}, {k_coop_step<false, true, false>, k_coop_step<false, true, true>}},
+    {{k_coop_step<true, false, false>, k_coop_step<true, false, true>}, {k_coop_step<true, true, false>, k_coop_step<true, true, true>}}};
+
+static void launch_coop(const Geometry &g, EncArgs a, bool cb32, uint64_t longest, uint8_t *ws, hipStream_t s)
+{
+    uint2         *pairs = (uint2 *)(ws + g.off_pairs);
+    const uint32_t cgrid = (uint32_t)((g.nblocks + 63) / 64);
+    {
+        const double r = 1.0 / (double)(257ull + g.nfreeze); // the frozen model's reciprocal, biased as k_fill_rc's
+        uint64_t     u;
+        memcpy(&u, &r, 8);
+        u += 4;
+        memcpy(&a.rc_frozen, &u, 8);
+    }
+    a.winlen = g.coop_win;
+    a.cstate = !g.u16 ? (uint32_t *)(ws + g.off_cstate) : nullptr;
+    a.cbase  = a.cstate ? a.cstate + g.nblocks * 8 : nullptr;
+    if (g.u16) { // whole blocks
+        k_coop_model<false><<<(uint32_t)g.nblocks, 64, 0, s>>>(a, pairs);
+        const CoopChainFn chain = kCoopChain[cb32][g.fixup];
+        chain<<<cgrid, 128, 0, s>>>(a, pairs);
+        return;
+    }
+    // Blocks above 64 KiB, window by window.  Window w's chain runs in ONE launch with window w + 1's model (k_coop_step):
+    // two pairs buffers and two reciprocal tables, alternating.  The longest block of the launch decides the number of
+    // windows: its EOF symbol (symbol number `length`) is the last one coded.
+    const uint32_t rc_half   = g.rc_n / 2;
+    const uint64_t pair_half = g.nblocks * coop_block_pitch(g.coop_win);
+    double        *rcs[2]    = {(double *)(ws + g.off_rc), (double *)(ws + g.off_rc) + rc_half};
+    uint2         *prs[2]    = {pairs, pairs + pair_half};
+    const CoopStepFn  step = kCoopStep[cb32][g.fixup][g.coop_linear];
+    const CoopChainFn last = kCoopLastChain[cb32][g.fixup][g.coop_linear];
+    k_coop_model<true><<<(uint32_t)g.nblocks, 64, 0, s>>>(a, prs[0]); // (win0 = 0)
+    for (uint32_t w = 0; w < g.coop_nwin && (uint64_t)w * g.coop_win <= longest; w++) {
+        EncArgs ac = a, am = a;
+        ac.win0 = w * g.coop_win;
+        ac.rc   = rcs[w & 1];
+        am.win0 = (w + 1) * g.coop_win;
+        // (the table of the first window was filled by the caller, as k_fill_rc fills it, in the first half)
+        if (w)
+            k_fill_rc_from<<<(rc_half + 255) / 256, 256, 0, s>>>(rcs[w & 1], rc_half, 257u + ac.win0);
+        const bool more = w + 1 < g.coop_nwin && (uint64_t)am.win0 <= longest; // (a window that only holds EOF symbols has no model)
+        if (more)
+            step<<<cgrid + (uint32_t)g.nblocks, 128, 0, s>>>(ac, am, prs[w & 1], prs[(w + 1) & 1], cgrid);
+        else
+            last<<<cgrid, 128, 0, s>>>(ac, prs[w & 1]);
+    }
+}
+
+// The coder stage of a call planned as g: the blocks' streams into the slots of the workspace.  t: the table form (in_len is
+// then the bytes of d_in); a caller's table is checked here, and *checked says where its copy and the check's verdict are.
+static int encode_slots_impl(const Geometry &g, const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                             const BlockTable &t, void *d_block_status, void *d_workspace, uint64_t workspace_bytes, void *stream,
+                             CheckedTable *checked)
+{
+    if (!d_workspace || !d_block_status || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    if (t.entries && (g.gen || g.any || in_len > 0xFFFFFFFFull)) // lane offsets into d_in are 32-bit
+        return REDUX_UNSUPPORTED;
     if (workspace_bytes < g.total)
         return REDUX_OUTPUT_TOO_SMALL;
     if (((uintptr_t)d_workspace) & 255)
@@ -944,33 +1117,17 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
     hipStream_t s  = (hipStream_t)stream;
     uint8_t    *ws = (uint8_t *)d_workspace;
 
-    if (d_table) { // caller data: the kernels read a checked copy (redux_table.hpp)
-        TableCheckArgs ta;
-        ta.in         = d_table;
-        ta.out        = (redux_block *)(ws + g.off_table);
-        ta.nentries   = tbl_blocks;
-        ta.nblocks    = nblocks_real;
-        ta.bytes      = in_len;
-        ta.block_size = block_size;
-        ta.aligned16  = tbl_aligned16 ? 1u : 0u;
-        ta.seen       = (uint32_t *)(ws + g.off_seen);
-        ta.sizes      = (uint32_t *)(ws + g.off_sizes);
-        ta.status     = (int32_t *)d_block_status;
-        const uint64_t n0 = std::max(nblocks_real, table_seen_words(nblocks_real));
-        k_table_prepare<<<(uint32_t)((n0 + 255) / 256), 256, 0, s>>>(ta);
-        k_table_check<<<(uint32_t)((tbl_blocks + 255) / 256), 256, 0, s>>>(ta);
-        d_table = ta.out;
+    const redux_block *table = t.entries;
+    if (table && !t.trusted) {
+        *checked = table_check_stage(t, g.nblocks, in_len, block_size, (redux_block *)(ws + g.off_table), (uint32_t *)(ws + g.off_seen),
+                                     (uint32_t *)(ws + g.off_sizes), (int32_t *)d_block_status, s);
+        table    = checked->entries;
     }
     HIP_TRY(hipMemsetAsync(ws + g.off_mode, 0, 256 + kClaimWords * 4, s)); // linear slots unless the pair kernel runs (below); empty role book
+    const EncCore core = enc_core(g, d_in, in_len, ws, d_block_status);
     if (g.gen) {
         GenEncArgs ga;
-        ga.in         = (const uint8_t *)d_in;
-        ga.in_len     = in_len;
-        ga.nblocks    = g.nblocks;
-        ga.slots      = ws + g.off_slots;
-        ga.slot_bytes = g.slot_bytes;
-        ga.sizes      = (uint32_t *)(ws + g.off_sizes);
-        ga.status     = (int32_t *)d_block_status;
+        static_cast<EncCore &>(ga) = core;
         ga.rc         = (const double *)(ws + g.off_rc);
         ga.block_size = block_size;
         ga.slot_cap   = g.slot_cap;
@@ -994,13 +1151,7 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
     }
     if (g.any) {
         AnyEncArgs aa;
-        aa.in         = (const uint8_t *)d_in;
-        aa.in_len     = in_len;
-        aa.nblocks    = g.nblocks;
-        aa.slots      = ws + g.off_slots;
-        aa.slot_bytes = g.slot_bytes;
-        aa.sizes      = (uint32_t *)(ws + g.off_sizes);
-        aa.status     = (int32_t *)d_block_status;
+        static_cast<EncCore &>(aa) = core;
         aa.trees      = (uint32_t *)(ws + g.off_trees);
         aa.tree_words = g.tree_bytes / 4;
         aa.block_size = block_size;
@@ -1014,21 +1165,15 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
     k_fill_rc<<<(g.rc_n + 255) / 256, 256, 0, s>>>((double *)(ws + g.off_rc), g.rc_n);
 
     EncArgs a;
-    a.in         = (const uint8_t *)d_in;
-    a.in_len     = in_len;
-    a.nblocks    = g.nblocks;
-    a.slots      = ws + g.off_slots;
-    a.slot_bytes = g.slot_bytes;
-    a.sizes      = (uint32_t *)(ws + g.off_sizes);
-    a.status     = (int32_t *)d_block_status;
+    static_cast<EncCore &>(a) = core;
     a.rc         = (const double *)(ws + g.off_rc);
     a.block_size = block_size;
     a.slot_cap   = g.slot_cap;
     a.nfreeze    = g.nfreeze;
     a.code_bits  = p->code_bits;
-    a.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (d_table ? tbl_aligned16 : (block_size & 15) == 0)) ? 1 : 0;
+    a.aligned16  = ((((uintptr_t)d_in) & 15) == 0 && (table ? t.aligned16 : (block_size & 15) == 0)) ? 1 : 0;
     a.claims     = (uint32_t *)(ws + g.off_mode + 256);
-    a.table      = d_table;
+    a.table      = table;
     a.pair_width = g.pair_width;
     a.win0 = 0; a.winlen = block_size + 1; a.rc_frozen = 0.0; a.cstate = nullptr; a.cbase = nullptr;
     // 64 blocks per wave while 64 slots / 64 blocks stay within a 32-bit lane offset;
@@ -1036,74 +1181,16 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
     a.lanes = encode_lanes(g, block_size);
     const uint32_t grid = (uint32_t)((g.nblocks + a.lanes - 1) / a.lanes);
     const EncKernel which = pick_encode_kernel(g, p, a.aligned16 != 0, block_size);
+    const bool      coop  = which == EncKernel::CoopCb32 || which == EncKernel::Coop;
     // what the pair kernel leaves in the slots (CompactArgs::mode): byte 0x01 -> row-major group
     // areas, 0x02 -> linear slots whose dwords are byte-reversed
-    if (which == EncKernel::PairCb32 || which == EncKernel::Pair || which == EncKernel::CoopCb32 || which == EncKernel::Coop)
+    if (which == EncKernel::PairCb32 || which == EncKernel::Pair || coop)
         HIP_TRY(hipMemsetAsync(ws + g.off_mode, g.coop_linear ? 2 : (1 | 2), 4, s));
     switch (which) {
     case EncKernel::CoopCb32:
-    case EncKernel::Coop: {
-        uint2         *pairs = (uint2 *)(ws + g.off_pairs);
-        const uint32_t cgrid = (uint32_t)((g.nblocks + 63) / 64);
-        const bool     cb32  = which == EncKernel::CoopCb32;
-        {
-            const double r = 1.0 / (double)(257ull + g.nfreeze); // the frozen model's reciprocal, biased as k_fill_rc's
-            uint64_t     u;
-            memcpy(&u, &r, 8);
-            u += 4;
-            memcpy(&a.rc_frozen, &u, 8);
-        }
-        a.winlen = g.coop_win;
-        a.cstate = !g.u16 ? (uint32_t *)(ws + g.off_cstate) : nullptr;
-        a.cbase  = a.cstate ? a.cstate + g.nblocks * 8 : nullptr;
-        if (g.u16) { // whole blocks
-            k_coop_model<false><<<(uint32_t)g.nblocks, 64, 0, s>>>(a, pairs);
-            if (g.fixup) {
-                if (cb32) k_coop_chain<true, true><<<cgrid, 128, 0, s>>>(a, pairs);
-                else      k_coop_chain<false, true><<<cgrid, 128, 0, s>>>(a, pairs);
-            } else {
-                if (cb32) k_coop_chain<true, false><<<cgrid, 128, 0, s>>>(a, pairs);
-                else      k_coop_chain<false, false><<<cgrid, 128, 0, s>>>(a, pairs);
-            }
-            break;
-        }
-        // Blocks above 64 KiB, window by window.  Window w's chain runs in ONE launch with window w + 1's model (k_coop_step):
-        // two pairs buffers and two reciprocal tables, alternating.  The longest block of the launch decides the number of
-        // windows: its EOF symbol (symbol number `length`) is the last one coded.
-        const uint64_t longest = d_table ? block_size : (in_len < block_size ? in_len : block_size);
-        const uint32_t rc_half = g.rc_n / 2;
-        const uint64_t pair_half = g.nblocks * coop_block_pitch(g.coop_win);
-        double        *rcs[2] = {(double *)(ws + g.off_rc), (double *)(ws + g.off_rc) + rc_half};
-        uint2         *prs[2] = {pairs, pairs + pair_half};
-        k_coop_model<true><<<(uint32_t)g.nblocks, 64, 0, s>>>(a, prs[0]); // (win0 = 0)
-        for (uint32_t w = 0; w < g.coop_nwin && (uint64_t)w * g.coop_win <= longest; w++) {
-            EncArgs ac = a, am = a;
-            ac.win0 = w * g.coop_win;
-            ac.rc   = rcs[w & 1];
-            am.win0 = (w + 1) * g.coop_win;
-            // (the table of the first window was filled above, as k_fill_rc fills it, in the first half)
-            if (w)
-                k_fill_rc_from<<<(rc_half + 255) / 256, 256, 0, s>>>(rcs[w & 1], rc_half, 257u + ac.win0);
-            const bool more = w + 1 < g.coop_nwin && (uint64_t)am.win0 <= longest; // (a window that only holds EOF symbols has no model)
-            const uint2 *pc = prs[w & 1];
-            uint2       *pm = prs[(w + 1) & 1];
-            const uint32_t sgrid = cgrid + (uint32_t)g.nblocks;
-#define REDUX_COOP_LAUNCH(CB, FX, LIN)                                                                                 \
-    do {                                                                                                               \
-        if (more) k_coop_step<CB, FX, LIN><<<sgrid, 128, 0, s>>>(ac, am, pc, pm, cgrid);                               \
-        else      k_coop_chain<CB, FX, LIN, true><<<cgrid, 128, 0, s>>>(ac, pc);                                       \
-    } while (0)
-            if (g.coop_linear) {
-                if (g.fixup) { if (cb32) REDUX_COOP_LAUNCH(true, true, true); else REDUX_COOP_LAUNCH(false, true, true); }
-                else         { if (cb32) REDUX_COOP_LAUNCH(true, false, true); else REDUX_COOP_LAUNCH(false, false, true); }
-            } else {
-                if (g.fixup) { if (cb32) REDUX_COOP_LAUNCH(true, true, false); else REDUX_COOP_LAUNCH(false, true, false); }
-                else         { if (cb32) REDUX_COOP_LAUNCH(true, false, false); else REDUX_COOP_LAUNCH(false, false, false); }
-            }
-#undef REDUX_COOP_LAUNCH
-        }
+    case EncKernel::Coop:
+        launch_coop(g, a, which == EncKernel::CoopCb32, table ? block_size : (in_len < block_size ? in_len : block_size), ws, s);
         break;
-    }
     case EncKernel::PairCb32: k_encode_pair<false, true><<<grid, 128, 0, s>>>(a); break;
     case EncKernel::Pair: k_encode_pair<false, false><<<grid, 128, 0, s>>>(a); break;
     case EncKernel::SingleU16: k_encode<true, false><<<grid, 64, 0, s>>>(a); break;
@@ -1119,14 +1206,18 @@ static int encode_slots_impl(const redux_params *p, const void *d_in, uint64_t i
 int redux_encode_slots_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
                            void *d_block_status, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return encode_slots_impl(p, d_in, in_len, block_size, nullptr, 0, false, d_block_status, d_workspace, workspace_bytes, stream);
+    Geometry  g;
+    const int st = encode_plan(p, in_len, block_size, workspace_bytes, g);
+    if (st != REDUX_OK)
+        return st;
+    return encode_slots_impl(g, p, d_in, in_len, block_size, BlockTable{}, d_block_status, d_workspace, workspace_bytes, stream, nullptr);
 }
 
-// scan + gather of the slots a coder kernel left in the workspace laid out by g
+// The compaction stage: scan + gather of the slots a coder kernel left in the workspace laid out by g.  t: the (checked) table
+// the coder ran on; raw: the stored blocks' bytes.
 static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status,
-                        void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream,
-                        const redux_block *d_table = nullptr, uint64_t nblocks_real = 0, const uint8_t *d_stored = nullptr,
-                        const void *d_raw = nullptr, uint32_t block_size = 0)
+                        void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream, const BlockTable &t,
+                        const RawCopy &raw)
 {
     if (!d_workspace || !d_block_status || !d_out_offsets || !d_out)
         return REDUX_INVALID_INPUT;
@@ -1140,7 +1231,7 @@ static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *
     sa.status  = (const int32_t *)d_block_status;
     sa.offsets = (uint64_t *)d_out_offsets;
     sa.summary = (int32_t *)d_summary;
-    sa.nblocks = d_table ? nblocks_real : g.nblocks; // (g counts slots = table entries; sizes and status are per block)
+    sa.nblocks = t.entries ? t.nblocks : g.nblocks; // (g counts slots = table entries; sizes and status are per block)
     if (scan_is_coalesced(sa))
         k_scan_sizes_coalesced<<<1, 1024, 0, s>>>(sa);
     else
@@ -1157,10 +1248,10 @@ static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *
     ca.nblocks    = g.nblocks;
     ca.mode       = (const uint32_t *)(ws + g.off_mode);
     ca.cap_rows   = (uint32_t)(g.slot_bytes / 4);
-    ca.table      = d_table;
-    ca.stored     = d_stored;
-    ca.raw        = (const uint8_t *)d_raw;
-    ca.block_size = block_size;
+    ca.table      = t.entries;
+    ca.stored     = raw.stored;
+    ca.raw        = (const uint8_t *)raw.raw;
+    ca.block_size = raw.block_size;
     k_compact<<<(uint32_t)g.nblocks, 256, 0, s>>>(ca);
     if (!g.any && !g.gen && (g.u16 || g.coop)) { // (every launch that may have left row-major group areas: the kernel reads the mode word)
         const uint32_t tiles = (ca.cap_rows + kTileRows - 1) / kTileRows + 1;
@@ -1175,24 +1266,27 @@ int redux_compact_slots_dev(const redux_params *p, uint64_t in_len, uint32_t blo
                             uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
                             void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    int st = check_params(p);
+    Geometry  g;
+    const int st = encode_plan(p, in_len, block_size, workspace_bytes, g);
     if (st != REDUX_OK)
         return st;
-    if (block_size == 0)
-        return REDUX_INVALID_INPUT;
-    return compact_with(geometry_ws(p, in_len, block_size, workspace_bytes), d_out, out_cap, d_out_offsets, d_block_status, d_summary,
-                        d_workspace, workspace_bytes, stream);
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream, BlockTable{},
+                        RawCopy{});
 }
 
 int redux_encode_blocks_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
                             void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status,
                             void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    int st = redux_encode_slots_dev(p, d_in, in_len, block_size, d_block_status, d_workspace, workspace_bytes, stream);
+    Geometry g;
+    int      st = encode_plan(p, in_len, block_size, workspace_bytes, g);
     if (st != REDUX_OK)
         return st;
-    return redux_compact_slots_dev(p, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary,
-                                   d_workspace, workspace_bytes, stream);
+    st = encode_slots_impl(g, p, d_in, in_len, block_size, BlockTable{}, d_block_status, d_workspace, workspace_bytes, stream, nullptr);
+    if (st != REDUX_OK)
+        return st;
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream, BlockTable{},
+                        RawCopy{});
 }
 
 int redux_encode_blocks_v_dev(const redux_params *p, const void *d_in, uint64_t in_bytes, const void *d_table,
@@ -1204,18 +1298,20 @@ int redux_encode_blocks_v_dev(const redux_params *p, const void *d_in, uint64_t 
         return REDUX_INVALID_INPUT;
     if (nentries > 0xFFFFFFF0ull || nblocks > 0xFFFFFFF0ull || !d_block_status || !d_workspace)
         return REDUX_INVALID_INPUT;
-    int st = encode_slots_impl(p, d_in, in_bytes, block_size, (const redux_block *)d_table, nentries,
-                               (flags & REDUX_V_ALIGNED16) != 0, d_block_status, d_workspace, workspace_bytes, stream, nblocks);
+    Geometry g;
+    int      st = encode_plan(p, nentries * (uint64_t)block_size, block_size, workspace_bytes, g);
     if (st != REDUX_OK)
         return st;
-    // (from here on the table is its checked copy in the workspace)
-    const Geometry g = geometry_ws(p, nentries * (uint64_t)block_size, block_size, workspace_bytes);
+    const BlockTable given = {(const redux_block *)d_table, (flags & REDUX_V_ALIGNED16) != 0, nblocks, false};
+    CheckedTable     checked;
+    st = encode_slots_impl(g, p, d_in, in_bytes, block_size, given, d_block_status, d_workspace, workspace_bytes, stream, &checked);
+    if (st != REDUX_OK)
+        return st;
     st = compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream,
-                      (const redux_block *)((uint8_t *)d_workspace + g.off_table), nblocks);
+                      BlockTable{checked.entries, given.aligned16, nblocks, true}, RawCopy{});
     if (st != REDUX_OK)
         return st;
-    k_table_verdict<<<1, 1, 0, (hipStream_t)stream>>>((const uint32_t *)((uint8_t *)d_workspace + g.off_seen) + table_seen_words(nblocks) - 1,
-                                                      (int32_t *)d_summary);
+    k_table_verdict<<<1, 1, 0, (hipStream_t)stream>>>(checked.failed, (int32_t *)d_summary);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
 }
@@ -1321,37 +1417,19 @@ int redux_compress(const redux_params *p, const uint8_t *in, uint64_t in_len, ui
     return rc;
 }
 
-// entries of the decoders' reciprocal table: what the block capacity (or the freeze point) asks for, but at most
-// kDecRcWindow + slack -- a decoder of longer blocks computes the rest itself (rc_lookup, redux_decode.hpp)
-static uint32_t dec_rc_entries(const Geometry &g)
-{
-    return (g.gen || g.rc_n <= kDecRcWindow + 32) ? g.rc_n : kDecRcWindow + 32;
-}
-
 uint64_t redux_decode_workspace_bytes(const redux_params *p, uint64_t nblocks, uint32_t block_size)
 {
     if (check_params(p) != REDUX_OK || block_size == 0)
         return 0;
-    const Geometry g = decode_geometry(p, block_size);
-    if (g.gen) // (11- and 12-bit symbols: the bottom cells of the decoder's tree live in the workspace: gen_decode_in_workspace)
-        return align_up((uint64_t)g.rc_n * 8, 256) +
-               (gen_decode_cells(p, block_size) && gen_decode_in_workspace(p, nblocks) ? (nblocks + 63) / 64 * 64 * gen_decode_tree_bytes(p) : 0);
-    if (g.any)
-        return (nblocks ? nblocks : 1) * g.tree_bytes;
-    // the reciprocal table, then room for the checked copy of a block table and its bitmap (redux_table.hpp)
-    const uint64_t rc_n = cells8_takes(p, block_size, nblocks ? nblocks : 1, false) ? std::max<uint64_t>(cells8_rc_entries(p, block_size), dec_rc_entries(g))
-                                                                                  : dec_rc_entries(g);
-    return align_up(rc_n * 8, 256) + align_up(nblocks * sizeof(redux_block), 256) + align_up(table_seen_words(nblocks) * 4, 256);
+    return decode_layout(decode_geometry(p, block_size), p, nblocks, block_size, false).total;
 }
 
-// d_in_used (optional, u64[nblocks]): bytes of each stream the reader fetched; only
-// redux_decompress asks for it (the (u64, u64) of src/lib.rs:119)
+// The decoders.  t: the table form (nblocks counts its entries, out_cap the bytes of d_out they may name); d_in_used (optional,
+// u64[nblocks]): bytes of each stream the reader fetched; only redux_decompress asks for it (the (u64, u64) of src/lib.rs:119)
 static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t nblocks,
                                   uint32_t block_size, void *d_out, uint64_t out_cap, void *d_out_sizes,
                                   void *d_block_status, void *d_summary, void *d_workspace,
-                                  uint64_t workspace_bytes, void *stream, void *d_in_used,
-                                  const redux_block *d_table = nullptr, bool tbl_aligned16 = false, uint64_t nblocks_real = 0,
-                                  bool table_trusted = false)
+                                  uint64_t workspace_bytes, void *stream, void *d_in_used, const BlockTable &t)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
@@ -1360,171 +1438,106 @@ static int decode_blocks_dev_impl(const redux_params *p, const void *d_in, const
         return REDUX_INVALID_INPUT;
     if (nblocks == 0)
         return REDUX_OK;
-    if (!d_table && out_cap < nblocks * (uint64_t)block_size)
+    if (!t.entries && out_cap < nblocks * (uint64_t)block_size)
         return REDUX_OUTPUT_TOO_SMALL;
-    const Geometry g = decode_geometry(p, block_size);
-    if (workspace_bytes < redux_decode_workspace_bytes(p, nblocks, block_size))
+    const Geometry     g = decode_geometry(p, block_size);
+    const DecodeLayout L = decode_layout(g, p, nblocks, block_size, t.entries != nullptr);
+    if (workspace_bytes < L.total)
         return REDUX_OUTPUT_TOO_SMALL;
-    if (d_table && (g.gen || g.any))
+    if (t.entries && (g.gen || g.any))
         return REDUX_UNSUPPORTED;
-    const DecKernel kernel = pick_decode_kernel(g, p, nblocks, block_size, d_table != nullptr);
-    hipStream_t s = (hipStream_t)stream;
-    if (g.gen) {
-        GenDecArgs ga;
-        ga.in         = (const uint8_t *)d_in;
-        ga.in_offsets = (const uint64_t *)d_in_offsets;
-        ga.nblocks    = nblocks;
-        ga.out        = (uint8_t *)d_out;
-        ga.out_sizes  = (uint32_t *)d_out_sizes;
-        ga.status     = (int32_t *)d_block_status;
-        ga.rc         = (const double *)d_workspace;
-        ga.trees      = (uint32_t *)((uint8_t *)d_workspace + align_up((uint64_t)g.rc_n * 8, 256));
-        ga.in_used    = (uint64_t *)d_in_used;
-        ga.block_size = block_size;
-        ga.nfreeze    = g.nfreeze;
-        ga.code_bits  = p->code_bits;
-        k_fill_rc_from<<<(g.rc_n + 255) / 256, 256, 0, s>>>((double *)d_workspace, g.rc_n, (1u << p->symbol_bits) + 1u);
-        const uint32_t grid64 = (uint32_t)((nblocks + 63) / 64);
-        switch (kernel) {
-        case DecKernel::CellsFixup:
-            switch (p->symbol_bits) {
+    hipStream_t    s      = (hipStream_t)stream;
+    uint8_t       *ws     = (uint8_t *)d_workspace;
+    const DecCore  core   = dec_core(d_in, d_in_offsets, nblocks, d_out, d_out_sizes, d_block_status);
+    const uint32_t grid64 = (uint32_t)((nblocks + 63) / 64);
+    CheckedTable   table  = {t.entries, nullptr};
+
+    GenDecArgs ga; // the cell decoders, of every width
+    static_cast<DecCore &>(ga) = core;
+    ga.rc         = (const double *)ws;
+    ga.trees      = g.gen ? (uint32_t *)(ws + L.off_trees) : nullptr;
+    ga.in_used    = (uint64_t *)d_in_used;
+    ga.block_size = block_size;
+    ga.nfreeze    = g.nfreeze;
+    ga.code_bits  = p->code_bits;
+    if (g.gen)
+        k_fill_rc_from<<<(L.rc_n + 255) / 256, 256, 0, s>>>((double *)ws, L.rc_n, (1u << p->symbol_bits) + 1u);
+    else if (!g.any)
+        k_fill_rc<<<(L.rc_n + 255) / 256, 256, 0, s>>>((double *)ws, L.rc_n);
+
+    switch (L.kernel) {
+    case DecKernel::CellsFixup:
+        switch (p->symbol_bits) {
 #define REDUX_GEN_DEC(SB) case SB: k_decode_cells<SB, 64, false, true><<<grid64, 64, 0, s>>>(ga); break;
-                REDUX_GEN_DEC(1) REDUX_GEN_DEC(2) REDUX_GEN_DEC(3) REDUX_GEN_DEC(4) REDUX_GEN_DEC(5) REDUX_GEN_DEC(6) REDUX_GEN_DEC(7)
+            REDUX_GEN_DEC(1) REDUX_GEN_DEC(2) REDUX_GEN_DEC(3) REDUX_GEN_DEC(4) REDUX_GEN_DEC(5) REDUX_GEN_DEC(6) REDUX_GEN_DEC(7)
 #undef REDUX_GEN_DEC
-            default: return REDUX_UNSUPPORTED;
-            }
-            break;
-        case DecKernel::CellsWorkspace: {
-            // every tree starts at all-ones frequencies: a node = its lowbit
-            const uint64_t npieces = (uint64_t)grid64 * 64 * gen_decode_tree_bytes(p) / 16;
-            k_fill_cells16<<<(uint32_t)((npieces + 255) / 256), 256, 0, s>>>((cl_u32x4 *)ga.trees, npieces);
-            if (p->symbol_bits == 11)
-                k_decode_cells<11, 64, true><<<grid64, 64, 0, s>>>(ga);
-            else
-                k_decode_cells<12, 64, true><<<grid64, 64, 0, s>>>(ga);
-            break;
-        }
-        case DecKernel::Cells:
-            switch (p->symbol_bits) {
-#define REDUX_GEN_DEC(SB, LANES) case SB: k_decode_cells<SB, LANES, false><<<(uint32_t)((nblocks + LANES - 1) / LANES), LANES, 0, s>>>(ga); break;
-                REDUX_GEN_DEC(1, 64) REDUX_GEN_DEC(2, 64) REDUX_GEN_DEC(3, 64) REDUX_GEN_DEC(4, 64) REDUX_GEN_DEC(5, 64) REDUX_GEN_DEC(6, 64)
-                REDUX_GEN_DEC(7, 64) REDUX_GEN_DEC(9, 64) REDUX_GEN_DEC(10, 64)
-#undef REDUX_GEN_DEC
-            default: return REDUX_UNSUPPORTED;
-            }
-            break;
         default: return REDUX_UNSUPPORTED;
         }
-        if (d_summary)
-            k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-        HIP_TRY(hipGetLastError());
-        return REDUX_OK;
+        break;
+    case DecKernel::CellsWorkspace: {
+        // every tree starts at all-ones frequencies: a node = its lowbit
+        const uint64_t npieces = (uint64_t)grid64 * 64 * gen_decode_tree_bytes(p) / 16;
+        k_fill_cells16<<<(uint32_t)((npieces + 255) / 256), 256, 0, s>>>((cl_u32x4 *)ga.trees, npieces);
+        if (p->symbol_bits == 11)
+            k_decode_cells<11, 64, true><<<grid64, 64, 0, s>>>(ga);
+        else
+            k_decode_cells<12, 64, true><<<grid64, 64, 0, s>>>(ga);
+        break;
     }
-    if (g.any) {
+    case DecKernel::Cells:
+        switch (p->symbol_bits) {
+#define REDUX_GEN_DEC(SB) case SB: k_decode_cells<SB, 64, false><<<grid64, 64, 0, s>>>(ga); break;
+            REDUX_GEN_DEC(1) REDUX_GEN_DEC(2) REDUX_GEN_DEC(3) REDUX_GEN_DEC(4) REDUX_GEN_DEC(5) REDUX_GEN_DEC(6) REDUX_GEN_DEC(7)
+            REDUX_GEN_DEC(9) REDUX_GEN_DEC(10)
+#undef REDUX_GEN_DEC
+        default: return REDUX_UNSUPPORTED;
+        }
+        break;
+    case DecKernel::Cells8: k_decode_cells<8, 64, false, false><<<grid64, 64, 0, s>>>(ga); break;
+    case DecKernel::Cells8Fixup: k_decode_cells<8, 64, false, true><<<grid64, 64, 0, s>>>(ga); break;
+    case DecKernel::Any: {
         AnyDecArgs aa;
-        aa.in         = (const uint8_t *)d_in;
-        aa.in_offsets = (const uint64_t *)d_in_offsets;
-        aa.nblocks    = nblocks;
-        aa.out        = (uint8_t *)d_out;
-        aa.out_sizes  = (uint32_t *)d_out_sizes;
-        aa.status     = (int32_t *)d_block_status;
+        static_cast<DecCore &>(aa) = core;
         aa.in_used    = (uint64_t *)d_in_used;
-        aa.trees      = (uint32_t *)d_workspace;
+        aa.trees      = (uint32_t *)ws;
         aa.tree_words = g.tree_bytes / 4;
         aa.block_size = block_size;
         aa.sb = p->symbol_bits; aa.fb = p->freq_bits; aa.cb = p->code_bits;
-        k_decode_any<<<(uint32_t)((nblocks + 63) / 64), 64, 0, s>>>(aa);
-        if (d_summary)
-            k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-        HIP_TRY(hipGetLastError());
-        return REDUX_OK;
+        k_decode_any<<<grid64, 64, 0, s>>>(aa);
+        break;
     }
-    if (kernel == DecKernel::Cells8 || kernel == DecKernel::Cells8Fixup) {
-        GenDecArgs ga;
-        ga.in         = (const uint8_t *)d_in;
-        ga.in_offsets = (const uint64_t *)d_in_offsets;
-        ga.nblocks    = nblocks;
-        ga.out        = (uint8_t *)d_out;
-        ga.out_sizes  = (uint32_t *)d_out_sizes;
-        ga.status     = (int32_t *)d_block_status;
-        ga.rc         = (const double *)d_workspace;
-        ga.trees      = nullptr;
-        ga.in_used    = (uint64_t *)d_in_used;
-        ga.block_size = block_size;
-        ga.nfreeze    = g.nfreeze;
-        ga.code_bits  = p->code_bits;
-        const uint32_t rc8 = cells8_rc_entries(p, block_size);
-        k_fill_rc<<<(rc8 + 255) / 256, 256, 0, s>>>((double *)d_workspace, rc8);
-        const uint32_t grid64 = (uint32_t)((nblocks + 63) / 64);
-        if (kernel == DecKernel::Cells8Fixup)
-            k_decode_cells<8, 64, false, true><<<grid64, 64, 0, s>>>(ga);
-        else
-            k_decode_cells<8, 64, false, false><<<grid64, 64, 0, s>>>(ga);
-        if (d_summary)
-            k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, nblocks, (int32_t *)d_summary);
-        HIP_TRY(hipGetLastError());
-        return REDUX_OK;
+    default: { // the decoders of 8-bit symbols that take a block table
+        if (table.entries && !t.trusted)
+            table = table_check_stage(t, nblocks, out_cap, block_size, (redux_block *)(ws + L.off_table), (uint32_t *)(ws + L.off_seen),
+                                      (uint32_t *)d_out_sizes, (int32_t *)d_block_status, s);
+        DecArgs a;
+        static_cast<DecCore &>(a) = core;
+        a.rc         = (const double *)ws;
+        a.block_size = block_size;
+        a.nfreeze    = g.nfreeze;
+        a.code_bits  = p->code_bits;
+        a.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
+        if (a.aligned4 && (((uintptr_t)d_out) & 15) == 0 && (block_size & 15) == 0)
+            a.aligned4 = 2; // 16-byte aligned blocks: the lock-step decoder stages four dwords per store
+        if (table.entries) // where a block starts is the table's business: all of them 16-byte aligned, or nothing is assumed
+            a.aligned4 = (t.aligned16 && (((uintptr_t)d_out) & 15) == 0) ? 2 : 0;
+        a.in_used    = (uint64_t *)d_in_used;
+        a.table      = table.entries;
+        a.rc_n       = L.rc_n - 32; // (the last 32 entries are slack for the lock-step decoder's look-ahead)
+        switch (L.kernel) {
+        case DecKernel::Wave: k_decode_wave<false><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
+        case DecKernel::WaveFixup: k_decode_wave<true><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
+        case DecKernel::LockCb32: k_decode_lock<true><<<grid64, 64, 0, s>>>(a); break;
+        case DecKernel::Lock: k_decode_lock<false><<<grid64, 64, 0, s>>>(a); break;
+        case DecKernel::GenericU16: k_decode<true, false><<<grid64, 64, 0, s>>>(a); break;
+        default: k_decode<false, true><<<grid64, 64, 0, s>>>(a); break; // (GenericU32)
+        }
     }
-    const uint32_t rc_n = dec_rc_entries(g);
-    k_fill_rc<<<(rc_n + 255) / 256, 256, 0, s>>>((double *)d_workspace, rc_n);
-    const uint32_t *table_failed = nullptr;
-    if (d_table && !table_trusted) { // caller data: the kernels read a checked copy (redux_table.hpp)
-        uint8_t *wt = (uint8_t *)d_workspace + align_up((uint64_t)rc_n * 8, 256);
-        TableCheckArgs ta;
-        ta.in         = d_table;
-        ta.out        = (redux_block *)wt;
-        ta.nentries   = nblocks;
-        ta.nblocks    = nblocks_real;
-        ta.bytes      = out_cap;
-        ta.block_size = block_size;
-        ta.aligned16  = tbl_aligned16 ? 1u : 0u;
-        ta.seen       = (uint32_t *)(wt + align_up(nblocks * sizeof(redux_block), 256));
-        ta.sizes      = (uint32_t *)d_out_sizes;
-        ta.status     = (int32_t *)d_block_status;
-        const uint64_t n0 = std::max(nblocks_real, table_seen_words(nblocks_real));
-        k_table_prepare<<<(uint32_t)((n0 + 255) / 256), 256, 0, s>>>(ta);
-        k_table_check<<<(uint32_t)((nblocks + 255) / 256), 256, 0, s>>>(ta);
-        d_table      = ta.out;
-        table_failed = ta.seen + table_seen_words(nblocks_real) - 1;
-    }
-    DecArgs a;
-    a.in         = (const uint8_t *)d_in;
-    a.in_offsets = (const uint64_t *)d_in_offsets;
-    a.nblocks    = nblocks;
-    a.out        = (uint8_t *)d_out;
-    a.out_sizes  = (uint32_t *)d_out_sizes;
-    a.status     = (int32_t *)d_block_status;
-    a.rc         = (const double *)d_workspace;
-    a.block_size = block_size;
-    a.nfreeze    = g.nfreeze;
-    a.code_bits  = p->code_bits;
-    a.aligned4   = ((((uintptr_t)d_out) & 3) == 0 && (block_size & 3) == 0) ? 1 : 0;
-    if (a.aligned4 && (((uintptr_t)d_out) & 15) == 0 && (block_size & 15) == 0)
-        a.aligned4 = 2; // 16-byte aligned blocks: the lock-step decoder stages four dwords per store
-    if (d_table) // where a block starts is the table's business: all of them 16-byte aligned, or nothing is assumed
-        a.aligned4 = (tbl_aligned16 && (((uintptr_t)d_out) & 15) == 0) ? 2 : 0;
-    a.in_used    = (uint64_t *)d_in_used;
-    a.table      = d_table;
-    a.rc_n       = rc_n - 32; // (the last 32 entries are slack for the lock-step decoder's look-ahead)
-    const uint32_t grid = (uint32_t)((nblocks + 63) / 64);
-    switch (kernel) {
-    case DecKernel::Wave: k_decode_wave<false><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
-    case DecKernel::WaveFixup: k_decode_wave<true><<<(uint32_t)nblocks, 64, 0, s>>>(a); break;
-    case DecKernel::LockCb32: k_decode_lock<true><<<grid, 64, 0, s>>>(a); break;
-    case DecKernel::Lock: k_decode_lock<false><<<grid, 64, 0, s>>>(a); break;
-    case DecKernel::GenericU16: k_decode<true, false><<<grid, 64, 0, s>>>(a); break;
-    case DecKernel::GenericU32: k_decode<false, true><<<grid, 64, 0, s>>>(a); break;
-    case DecKernel::Cells:
-    case DecKernel::CellsFixup:
-    case DecKernel::CellsWorkspace:
-    case DecKernel::Cells8:
-    case DecKernel::Cells8Fixup:
-    case DecKernel::Any: break; // handled above
     }
     if (d_summary) // (with a block table nblocks counts its entries: statuses are per block)
-        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, d_table ? nblocks_real : nblocks, (int32_t *)d_summary);
-    if (table_failed)
-        k_table_verdict<<<1, 1, 0, s>>>(table_failed, (int32_t *)d_summary);
+        k_summarize<<<64, 256, 0, s>>>((const int32_t *)d_block_status, table.entries ? t.nblocks : nblocks, (int32_t *)d_summary);
+    if (table.failed)
+        k_table_verdict<<<1, 1, 0, s>>>(table.failed, (int32_t *)d_summary);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
 }
@@ -1562,7 +1575,7 @@ int redux_decode_blocks_dev(const redux_params *p, const void *d_in, const void 
                             void *stream)
 {
     return decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, d_out, out_cap, d_out_sizes,
-                                  d_block_status, d_summary, d_workspace, workspace_bytes, stream, nullptr);
+                                  d_block_status, d_summary, d_workspace, workspace_bytes, stream, nullptr, BlockTable{});
 }
 
 int redux_decode_blocks_v_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_table,
@@ -1573,8 +1586,8 @@ int redux_decode_blocks_v_dev(const redux_params *p, const void *d_in, const voi
     if (!d_table || nblocks == 0 || nentries < nblocks || !d_out || nentries > 0xFFFFFFF0ull)
         return REDUX_INVALID_INPUT;
     return decode_blocks_dev_impl(p, d_in, d_in_offsets, nentries, block_size, d_out, out_bytes, d_out_sizes, d_block_status,
-                                  d_summary, d_workspace, workspace_bytes, stream, nullptr, (const redux_block *)d_table,
-                                  (flags & REDUX_V_ALIGNED16) != 0, nblocks);
+                                  d_summary, d_workspace, workspace_bytes, stream, nullptr,
+                                  BlockTable{(const redux_block *)d_table, (flags & REDUX_V_ALIGNED16) != 0, nblocks, false});
 }
 
 int redux_decode_blocks_v(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint8_t *out,
@@ -1597,7 +1610,7 @@ static host::DecodeCoder adaptive_decoder(const redux_params *p, uint32_t block_
     return {[=](uint64_t cb) { return redux_decode_workspace_bytes(p, cb, block_size); },
             [=](host::Slot &s, uint64_t nb, uint64_t out_bytes, void *d_in_used, void *ws, uint64_t ws_bytes, hipStream_t st) {
                 return decode_blocks_dev_impl(p, s.d_in.p, s.d_off.p, nb, block_size, s.d_out.p, out_bytes, s.d_sz.p, s.d_st.p,
-                                              s.d_sum.p, ws, ws_bytes, st, d_in_used);
+                                              s.d_sum.p, ws, ws_bytes, st, d_in_used, BlockTable{});
             }};
 }
 
@@ -1768,13 +1781,7 @@ static StaticEncCore static_enc_args(const Geometry &g, const redux_params *p, c
                                      uint8_t *ws, void *d_block_status, uint32_t total)
 {
     StaticEncCore c;
-    c.in         = (const uint8_t *)d_x;
-    c.in_len     = in_len;
-    c.nblocks    = g.nblocks;
-    c.slots      = ws + g.off_slots;
-    c.slot_bytes = g.slot_bytes;
-    c.sizes      = (uint32_t *)(ws + g.off_sizes);
-    c.status     = (int32_t *)d_block_status;
+    static_cast<EncCore &>(c) = enc_core(g, d_x, in_len, ws, d_block_status);
     c.rc         = static_rc(total);
     c.block_size = block_size;
     c.slot_cap   = g.slot_cap;
@@ -1788,12 +1795,7 @@ static StaticDecCore static_dec_args(const redux_params *p, const void *d_in, co
                                      uint32_t block_size, void *d_out, void *d_out_sizes, void *d_block_status, uint32_t total)
 {
     StaticDecCore c;
-    c.in         = (const uint8_t *)d_in;
-    c.in_offsets = (const uint64_t *)d_in_offsets;
-    c.nblocks    = nblocks;
-    c.out        = (uint8_t *)d_out;
-    c.out_sizes  = (uint32_t *)d_out_sizes;
-    c.status     = (int32_t *)d_block_status;
+    static_cast<DecCore &>(c) = dec_core(d_in, d_in_offsets, nblocks, d_out, d_out_sizes, d_block_status);
     c.rc         = static_rc(total);
     c.block_size = block_size;
     c.code_bits  = p->code_bits;
@@ -1807,12 +1809,7 @@ static DecArgs lock_args_from(const StaticDecCore &c)
 {
     DecArgs d;
     memset(&d, 0, sizeof d);
-    d.in         = c.in;
-    d.in_offsets = c.in_offsets;
-    d.nblocks    = c.nblocks;
-    d.out        = c.out;
-    d.out_sizes  = c.out_sizes;
-    d.status     = c.status;
+    static_cast<DecCore &>(d) = c;
     d.block_size = c.block_size;
     d.nfreeze    = 0xFFFFFFFFu;
     d.code_bits  = c.code_bits;
@@ -1868,7 +1865,7 @@ int redux_static_encode_blocks_dev(const redux_params *p, const uint32_t *cum, c
     case StaticEncKernel::Narrow: k_encode_static<false, false><<<grid, 64, 0, s>>>(a); break;
     }
     HIP_TRY(hipGetLastError());
-    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream, BlockTable{}, RawCopy{});
 }
 
 int redux_static_decode_blocks_dev(const redux_params *p, const uint32_t *cum, const void *d_in,
@@ -2134,7 +2131,7 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
         return REDUX_OUTPUT_TOO_SMALL;
     uint8_t *t = (uint8_t *)d_workspace;
     st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
-                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr);
+                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr, BlockTable{});
     if (st != REDUX_OK)
         return st;
     return layout_decode_tail(L, t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary, TailSummary::InSizes, stream);
@@ -2615,7 +2612,7 @@ static int tables_static_encode_x(const redux_params *p, const void *d_cum, uint
     case StaticEncKernel::Narrow: k_encode_segment_static<false, false><<<grid, 64, 0, s>>>(a); break;
     }
     HIP_TRY(hipGetLastError());
-    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream, BlockTable{}, RawCopy{});
 }
 
 // the layout stage (layout_stage), then the coder over x'
@@ -3290,7 +3287,7 @@ int redux_context_static_encode_dev(const redux_params *p, const void *d_cum, ui
     const uint32_t grid   = (uint32_t)(groups < cus ? groups : cus);
     launch_context_encode(k, grid, a, s);
     HIP_TRY(hipGetLastError());
-    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, workspace_bytes - kCtxHead, stream);
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, workspace_bytes - kCtxHead, stream, BlockTable{}, RawCopy{});
 }
 
 int redux_context_static_decode_dev(const redux_params *p, const void *d_cum, uint32_t total, const void *d_in, const void *d_in_offsets,
@@ -3437,9 +3434,11 @@ int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in
     const void    *x   = staged.x;
     uint8_t       *ws  = staged.ws;
     const uint64_t wsb = staged.ws_bytes;
-    if ((st = encode_slots_impl(p, x, in_len, block_size, nullptr, 0, false, d_block_status, ws, wsb, stream)) != REDUX_OK)
+    Geometry       g;
+    if ((st = encode_plan(p, in_len, block_size, wsb, g)) != REDUX_OK)
         return st;
-    const Geometry  g = geometry_ws(p, in_len, block_size, wsb);
+    if ((st = encode_slots_impl(g, p, x, in_len, block_size, BlockTable{}, d_block_status, ws, wsb, stream, nullptr)) != REDUX_OK)
+        return st;
     StoreSelectArgs sa;
     sa.status     = (const int32_t *)d_block_status;
     sa.sizes      = (uint32_t *)(ws + g.off_sizes);
@@ -3451,8 +3450,8 @@ int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in
     const uint64_t wgs = (g.nblocks + 255) / 256;
     k_store_select<<<(uint32_t)(wgs < 1024 ? wgs : 1024), 256, 0, s>>>(sa);
     HIP_TRY(hipGetLastError());
-    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, wsb, stream, nullptr, 0,
-                        (const uint8_t *)d_stored, x, block_size);
+    return compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, wsb, stream, BlockTable{},
+                        RawCopy{(const uint8_t *)d_stored, x, block_size});
 }
 
 // coded blocks through the table form of the adaptive decoders, stored ones copied, into T (d_out, or the plane buffer);
@@ -3489,8 +3488,8 @@ int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void 
     HIP_TRY(hipGetLastError());
     // (the library's own table, coded blocks first: no k_table_check, whose "a block no entry codes" rule is wrong here)
     st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, out_len, d_out_sizes, d_block_status, nullptr, dws,
-                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr, table,
-                                (block_size & 15) == 0, nblocks, true);
+                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr,
+                                BlockTable{table, (block_size & 15) == 0, nblocks, true});
     if (st != REDUX_OK)
         return st;
     StoreUnpackArgs ua;
@@ -3657,10 +3656,13 @@ int redux_encode_const_dev(const redux_params *p, const void *d_in, uint64_t in_
     ta.block_size = block_size;
     k_const_table<<<1, 1024, 0, s>>>(ta);
     HIP_TRY(hipGetLastError());
-    if ((st = encode_slots_impl(p, x, in_len, block_size, table, nblocks, (block_size & 15) == 0, d_block_status, ws, wsb, stream,
-                                nblocks)) != REDUX_OK)
+    Geometry g; // (the table form sizes its launch by entries: here one per block)
+    if ((st = encode_plan(p, nblocks * (uint64_t)block_size, block_size, wsb, g)) != REDUX_OK)
         return st;
-    const Geometry g = geometry_ws(p, nblocks * (uint64_t)block_size, block_size, wsb); // (as encode_slots_impl took it)
+    const BlockTable left = {table, (block_size & 15) == 0, nblocks, false};
+    CheckedTable     checked;
+    if ((st = encode_slots_impl(g, p, x, in_len, block_size, left, d_block_status, ws, wsb, stream, &checked)) != REDUX_OK)
+        return st;
     ConstPlaceArgs pa;
     pa.flags      = (const uint8_t *)d_const;
     pa.raw        = (const uint8_t *)x;
@@ -3678,7 +3680,7 @@ int redux_encode_const_dev(const redux_params *p, const void *d_in, uint64_t in_
     HIP_TRY(hipGetLastError());
     // (from here on the table is its checked copy in the coder's workspace)
     if ((st = compact_with(g, d_out, out_cap, d_out_offsets, d_block_status, d_summary, ws, wsb, stream,
-                           (const redux_block *)(ws + g.off_table), nblocks)) != REDUX_OK)
+                           BlockTable{checked.entries, left.aligned16, nblocks, true}, RawCopy{})) != REDUX_OK)
         return st;
     k_const_place<<<grid, 256, 0, s>>>(pa);
     HIP_TRY(hipGetLastError());
@@ -3719,8 +3721,8 @@ int redux_decode_const_dev(const redux_params *p, const void *d_in, const void *
     HIP_TRY(hipGetLastError());
     // (the library's own table, as in redux_decode_stored_dev: no k_table_check)
     st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, out_len, d_out_sizes, d_block_status, nullptr, dws,
-                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr, table,
-                                (block_size & 15) == 0, nblocks, true);
+                                workspace_bytes - (uint64_t)(dws - (uint8_t *)d_workspace), stream, nullptr,
+                                BlockTable{table, (block_size & 15) == 0, nblocks, true});
     if (st != REDUX_OK)
         return st;
     ConstFillArgs fa;

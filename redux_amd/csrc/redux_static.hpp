@@ -38,14 +38,7 @@ struct StaticTable { // passed by value in the kernel arguments (1032 bytes)
     uint32_t cum[kStaticEntries];
 };
 
-struct StaticEncCore { // everything but the table: shared with the E-table kernels of redux_segment_static.hpp
-    const uint8_t *in;
-    uint64_t       in_len;
-    uint64_t       nblocks;
-    uint8_t       *slots;
-    uint64_t       slot_bytes;
-    uint32_t      *sizes;
-    int32_t       *status;
+struct StaticEncCore : EncCore { // everything but the table: shared with the E-table kernels of redux_segment_static.hpp
     double         rc;        // 1/total rounded, then bumped 4 ulp (as k_fill_rc)
     uint32_t       block_size;
     uint32_t       slot_cap;
@@ -56,6 +49,7 @@ struct StaticEncCore { // everything but the table: shared with the E-table kern
 struct StaticEncArgs : StaticEncCore {
     StaticTable tab;
 };
+static_assert(sizeof(StaticEncCore) == 80 && sizeof(StaticEncArgs) == 1112, "kernarg layout");
 
 // The model of a lane: what the per-lane coder bodies below ask of it.  total() is total_frequency(); range(s) is
 // get_frequency(s) for a data symbol, (low, high) in .x and .y, and eof_lo() the low end of the EOF symbol's range, which
@@ -204,22 +198,21 @@ __global__ void __launch_bounds__(64) k_encode_static(StaticEncArgs a)
     static_encode_body<FIXUP, CB32>(a, m, (uint64_t)blockIdx.x * 64, threadIdx.x, 1);
 }
 
-struct StaticDecCore {
-    const uint8_t  *in;
-    const uint64_t *in_offsets; // nblocks + 1
-    uint64_t        nblocks;
-    uint8_t        *out;        // block b at out + b*block_size
-    uint32_t       *out_sizes;
-    int32_t        *status;
+struct StaticDecCore : DecCore {
     double          rc;
     uint32_t        block_size;
     uint32_t        code_bits;
     uint32_t        aligned4; // out and block_size are 4-byte multiples
+    uint32_t        pad_;     // no tail padding: a derived struct's first member would move into it (StaticDecArgs::tab, from 72 to 68)
 };
 
 struct StaticDecArgs : StaticDecCore {
     StaticTable tab;
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(StaticDecCore) == 72 && sizeof(StaticDecArgs) == 1104 && offsetof(StaticDecArgs, tab) == 72, "kernarg layout");
+#pragma clang diagnostic pop
 
 // one lane, one block (blk; not live past nblocks) under its model m, fresh for the block
 template <bool FIXUP, class Model>
@@ -348,6 +341,7 @@ struct StaticLockArgs {
     double      rc;
     StaticTable tab;
 };
+static_assert(sizeof(StaticLockArgs) == 1136, "kernarg layout");
 
 // SOLO: the kernel claims more than half of a SIMD's 512 registers, so that no two of its waves share a SIMD.
 // A lock-step wave that has a SIMD to itself finishes a 64 KiB block in ~20 ms; the dispatcher, free to pack

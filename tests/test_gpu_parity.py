@@ -1694,3 +1694,47 @@ def test_hostile_block_tables_are_rejected_on_the_device(rx):
                 assert st[b] == 2 and sz[b] == 0
             else:
                 assert st[b] == 0 and sz[b] == BS and (dec[b * BS:(b + 1) * BS] == data[b * BS:(b + 1) * BS]).all(), (kind, b)
+
+
+def test_table_form_decodes_many_entries_of_blocks_past_a_mebibyte(rx):
+    """redux_decode_blocks_v_dev with a caller's table of more than 768 entries and blocks above 1 MiB: the one shape in which the
+    launch without a table would take the cell decoder, whose reciprocal table is longer than the one k_decode_wave fills
+    here, so the checked copy of the table does not start right behind the filled entries (decode_layout).  Two blocks
+    coded by the oracle among idle entries decode to their bytes, sizes and statuses; guard bands stay untouched."""
+    import ctypes as C
+    import torch
+    from redux_amd import _lib
+    L = _lib.lib()
+    BS, W, NE = (1 << 20) + 16, (8, 30, 32), 832
+    cp = _lib.Params(*W)
+    assert L.redux_decode_kernel_name_table(C.byref(cp), BS, NE).startswith(b"k_decode_wave")
+    assert L.redux_decode_kernel_name_n(C.byref(cp), None, BS, NE).startswith(b"k_decode_cells<8>")
+    z = rx.gen_zipf(BS + 300_001).cpu().numpy()
+    blocks = [z[:BS], z[BS:]]
+    streams = [ox.compress(b.tobytes(), W)[0] for b in blocks]
+    soffs = np.array([0, len(streams[0]), len(streams[0]) + len(streams[1])], dtype=np.int64)
+    tab = np.zeros(NE, dtype=rx.BLOCK_DTYPE)
+    tab["index"] = rx.BLOCK_IDLE
+    tab[70] = (0, BS, 0)            # (in two different waves, out of block order)
+    tab[3] = (BS, 300_001, 1)
+    G = 4096
+
+    def guarded(nbytes):
+        raw = torch.full((nbytes + 2 * G,), 0xAB, dtype=torch.uint8, device="cuda")
+        return raw, raw[G: G + nbytes]
+
+    wsb = L.redux_decode_workspace_bytes(C.byref(cp), NE, BS)
+    bufs = {k: guarded(n) for k, n in (("ws", wsb), ("out", len(z)), ("sz", 8), ("st", 8), ("sum", 8))}
+    bufs["sum"][1].zero_()
+    d_in = torch.from_numpy(np.frombuffer(b"".join(streams), dtype=np.uint8).copy()).cuda()
+    d_offs, d_tab = torch.from_numpy(soffs).cuda(), torch.from_numpy(tab.view(np.uint8).copy()).cuda()
+    p = lambda k: C.c_void_p(bufs[k][1].data_ptr())
+    r = L.redux_decode_blocks_v_dev(C.byref(cp), C.c_void_p(d_in.data_ptr()), C.c_void_p(d_offs.data_ptr()), C.c_void_p(d_tab.data_ptr()),
+                                    NE, 2, BS, 0, p("out"), len(z), p("sz"), p("st"), p("sum"), p("ws"), wsb,
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert r == 0
+    for raw, view in bufs.values():
+        assert bool((raw[:G] == 0xAB).all()) and bool((raw[G + view.numel():] == 0xAB).all())
+    assert bufs["sum"][1].view(torch.int32).tolist() == [0, 0] and bufs["st"][1].view(torch.int32).tolist() == [0, 0]
+    assert bufs["sz"][1].view(torch.int32).tolist() == [BS, 300_001] and bool((bufs["out"][1].cpu() == torch.from_numpy(z)).all())

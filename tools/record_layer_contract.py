@@ -1,10 +1,12 @@
 """The host contract of the layered calls, as data: every workspace and bound value, every kernel-name string and the return
 code of every refusal that is decided before any HIP call, for the planes, delta, stored, static, plane-static,
-segment-static and context-static families.
+segment-static and context-static families, and for the adaptive coder's own entry points under them: the plain, split,
+`_v`, base and const calls, over every parameter class (8-bit, the lock-step widths, general parameters).
 
     python tools/record_layer_contract.py [--lib PATH] > tests/golden/layer_contract.json
+    python tools/record_layer_contract.py [--lib PATH] --part adaptive > tests/golden/adaptive_contract.json
 
-records them from a library (the product's by default); tests/test_layer_contract_cpu.py runs the same collection on the
+record the two parts (the layered families; the adaptive coder's own calls) from a library (the product's by default); tests/test_layer_contract_cpu.py runs the same collection on the
 library under test and compares.  Record the fixture from the library of the commit whose behaviour is to be kept, never
 from the change that is being checked against it.
 
@@ -44,12 +46,28 @@ def lengths(bs):
     return [0, 1, bs, 67 * bs + 5, 4096 * bs]
 
 
+# the adaptive coder's own grid ("adaptive/..." rows): the 8-bit triples, a lock-step width below 8 and one above, general
+# parameters (code_bits > 32); a block above 64 KiB and one of 3 MiB, which the small-grid encoder codes in windows; lengths
+# on both sides of its limit of 2048 blocks
+APARAMS = PARAMS + [(4, 20, 24), (12, 20, 32), (8, 24, 40)]
+ABLOCKS = BLOCKS + [1 << 17, 3 << 20]
+AES = [1, 4]
+
+
+def alengths(bs):
+    return [0, 1, 67 * bs + 5, 2048 * bs, 2049 * bs, 4096 * bs]
+
+
 def table(total):
     return (C.c_uint32 * 258)(*(list(range(257)) + [total]))
 
 
-def sizes(L, decl):
-    """name -> values over PARAMS x BLOCKS x [ES] x lengths, in that nesting order."""
+def sizes(L, decl, part):
+    """name -> values over PARAMS x BLOCKS x [ES] x lengths, in that nesting order ("adaptive/" rows: the adaptive grid)."""
+    return adaptive_sizes(L, decl) if part == "adaptive" else layered_sizes(L, decl)
+
+
+def layered_sizes(L, decl):
     out = {}
     plain = ["redux_encode_bound", "redux_encode_workspace_bytes", "redux_static_encode_bound", "redux_static_encode_workspace_bytes",
              "redux_plane_static_encode_bound", "redux_segment_static_encode_bound", "redux_context_static_encode_bound",
@@ -74,8 +92,22 @@ def sizes(L, decl):
     return out
 
 
-def names(L, decl):
-    """name -> indices into `strings`, over PARAMS x TOTALS x BLOCKS x [ES] x lengths."""
+def adaptive_sizes(L, decl):
+    out = {}
+    agrid = [(decl.Params(*w), bs) for w in APARAMS for bs in ABLOCKS]
+    for n in ("redux_encode_bound", "redux_encode_workspace_bytes"):
+        out["adaptive/" + n] = [getattr(L, n)(C.byref(p), ln, bs) for p, bs in agrid for ln in alengths(bs)]
+    out["adaptive/redux_encode_slot_bytes"] = [L.redux_encode_slot_bytes(C.byref(p), bs) for p, bs in agrid]
+    out["adaptive/redux_decode_workspace_bytes"] = [L.redux_decode_workspace_bytes(C.byref(p), nb, bs) for p, bs in agrid
+                                                    for nb in [0] + [L.redux_block_count(ln, bs) for ln in alengths(bs)]]
+    for n in ("redux_encode_const_workspace_bytes", "redux_decode_const_workspace_bytes", "redux_encode_base_workspace_bytes",
+              "redux_decode_base_workspace_bytes"):
+        out["adaptive/" + n] = [getattr(L, n)(C.byref(p), ln, bs, E) for p, bs in agrid for E in AES for ln in alengths(bs)]
+    return out
+
+
+def names(L, decl, part):
+    """name -> indices into `strings`, over PARAMS x TOTALS x BLOCKS x [ES] x lengths ("adaptive/" rows: the adaptive grid)."""
     strings, out = [], {}
 
     def idx(b):
@@ -84,6 +116,11 @@ def names(L, decl):
             strings.append(s)
         return strings.index(s)
 
+    (adaptive_names if part == "adaptive" else layered_names)(L, decl, idx, out)
+    return {"strings": strings, "rows": out}
+
+
+def layered_names(L, decl, idx, out):
     grid = [(decl.Params(*w), t, bs) for w in PARAMS for t in TOTALS for bs in BLOCKS]
     out["redux_static_encode_kernel_name"] = [idx(L.redux_static_encode_kernel_name(C.byref(p), table(t), ln, bs))
                                               for p, t, bs in grid for ln in lengths(bs)]
@@ -104,7 +141,23 @@ def names(L, decl):
     out["giant blocks"] = [idx(L.redux_static_encode_kernel_name(C.byref(decl.Params(8, 30, 32)), table(4096), 1, bs)) for bs in (1 << 25, 1 << 26)] + \
                           [idx(L.redux_plane_static_encode_kernel_name(C.byref(decl.Params(8, 30, 32)), 4096, 1, bs, E))
                            for bs in (1 << 23, 1 << 24, 1 << 25, 1 << 26) for E in ES]
-    return {"strings": strings, "rows": out}
+
+
+def adaptive_names(L, decl, idx, out):
+    # input 16-byte aligned and not; a workspace that holds the small-grid pairs area and one a byte short
+    agrid = [(decl.Params(*w), bs) for w in APARAMS for bs in ABLOCKS]
+    for tag, d_in in (("", ptr(1)), ("/unaligned", ptr(1) + 4)):
+        out["adaptive/redux_encode_kernel_name" + tag] = [idx(L.redux_encode_kernel_name(C.byref(p), d_in, ln, bs))
+                                                          for p, bs in agrid for ln in alengths(bs)]
+    for tag, short in (("/fits", 0), ("/short", 1)):
+        out["adaptive/redux_encode_kernel_name_ws" + tag] = [
+            idx(L.redux_encode_kernel_name_ws(C.byref(p), ptr(1), ln, bs, L.redux_encode_workspace_bytes(C.byref(p), ln, bs) - short))
+            for p, bs in agrid for ln in alengths(bs)]
+    counts = lambda bs: [0] + [L.redux_block_count(ln, bs) for ln in alengths(bs)]
+    out["adaptive/redux_decode_kernel_name_n"] = [idx(L.redux_decode_kernel_name_n(C.byref(p), ptr(2), bs, nb))
+                                                  for p, bs in agrid for nb in counts(bs)]
+    out["adaptive/redux_decode_kernel_name_table"] = [idx(L.redux_decode_kernel_name_table(C.byref(p), bs, nb))
+                                                      for p, bs in agrid for nb in counts(bs)]
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------
@@ -121,9 +174,9 @@ def ptr(i):
     return (1 << 40) + (i << 32)       # dummy device pointers: 256-aligned, far apart
 
 
-def refusals(L, decl):
-    good, bad, anyp = decl.Params(8, 30, 32), decl.Params(8, 9, 16), decl.Params(12, 20, 32)
-    P = {"good": C.byref(good), "bad": C.byref(bad), "any": C.byref(anyp), "null": None}
+def refusals(L, decl, part):
+    good, bad, anyp, wide = decl.Params(8, 30, 32), decl.Params(8, 9, 16), decl.Params(12, 20, 32), decl.Params(8, 24, 40)
+    P = {"good": C.byref(good), "bad": C.byref(bad), "any": C.byref(anyp), "wide": C.byref(wide), "null": None}
     tab, badtab = table(4096), (C.c_uint32 * 258)(*([1] + list(range(1, 257)) + [4096]))
     T = {"good": tab, "bad": badtab, "null": None}
     dec_ws = L.redux_decode_planes_workspace_bytes(P["good"], LEN, BS, E0)
@@ -271,6 +324,8 @@ def refusals(L, decl):
              "workspace not 256-aligned and below the image": dict(d_ws=ptr(6) + 16, ws_bytes=CTX_HEAD - 1),
              "total 65537 and out_cap below out_len": dict(total=65537, out_cap=0)}),
     }
+    if part == "adaptive":
+        calls = adaptive_calls(L, P)
     out = {}
     for fn, (order, base, faults) in calls.items():
         out[fn] = {}
@@ -286,8 +341,123 @@ def refusals(L, decl):
     return out
 
 
-def collect(L, decl):
-    return {"sizes": sizes(L, decl), "names": names(L, decl), "refusals": refusals(L, decl)}
+def adaptive_calls(L, P):
+    """The adaptive coder's own entry points, in the form of refusals()'s `calls`.  `any` is a lock-step width (12-bit symbols),
+    `wide` general parameters (code_bits 40): the plain calls take both, the table forms and the const calls neither."""
+    dec_ws = L.redux_decode_workspace_bytes(P["good"], NB, BS)
+    const_front = COPY + (NB * 16 + 255) // 256 * 256           # x', then the table of the blocks that are left
+    const_dec_ws = L.redux_decode_const_workspace_bytes(P["good"], LEN, BS, E0)
+    base_dec_ws = L.redux_decode_base_workspace_bytes(P["good"], LEN, BS, E0)
+    slots = (["p", "d_in", "len", "bs", "d_st", "d_ws", "ws_bytes", "stream"],
+             dict(p="good", d_in=ptr(1), len=LEN, bs=BS, d_st=ptr(4), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+             {"bad params": dict(p="bad"), "null params": dict(p="null"), "block_size 0": dict(bs=0), "null workspace": dict(d_ws=None),
+              "null status": dict(d_st=None), "null input": dict(d_in=None), "no workspace bytes": dict(ws_bytes=0),
+              "4 KiB of workspace": dict(ws_bytes=4096), "workspace not 256-aligned": dict(d_ws=ptr(6) + 16),
+              "lock-step width: no workspace bytes": dict(p="any", ws_bytes=0), "general params: no workspace bytes": dict(p="wide", ws_bytes=0),
+              "bad params and null workspace": dict(p="bad", d_ws=None),
+              "no workspace bytes and workspace not 256-aligned": dict(ws_bytes=0, d_ws=ptr(6) + 16),
+              "null status and no workspace bytes": dict(d_st=None, ws_bytes=0)})
+    blocks = (["p", "d_in", "len", "bs", "d_out", "out_cap", "d_off", "d_st", "d_sum", "d_ws", "ws_bytes", "stream"],
+              dict(p="good", d_in=ptr(1), len=LEN, bs=BS, d_out=ptr(2), out_cap=BIG, d_off=ptr(3), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6),
+                   ws_bytes=BIG, stream=None),
+              slots[2])
+    v_faults = {"null table": dict(d_tab=None), "no blocks": dict(nblocks=0, nentries=0), "fewer entries than blocks": dict(nentries=NB - 1),
+                "2^32 entries": dict(nentries=1 << 32), "null status": dict(d_st=None), "null workspace": dict(d_ws=None),
+                "bad params": dict(p="bad"), "null params": dict(p="null"), "block_size 0": dict(bs=0),
+                "lock-step width": dict(p="any"), "general params": dict(p="wide"), "no workspace bytes": dict(ws_bytes=0),
+                "general params and no workspace bytes": dict(p="wide", ws_bytes=0), "null table and bad params": dict(d_tab=None, p="bad")}
+    return {
+        "redux_encode_slots_dev": slots,
+        "redux_compact_slots_dev": (
+            ["p", "len", "bs", "d_out", "out_cap", "d_off", "d_st", "d_sum", "d_ws", "ws_bytes", "stream"],
+            dict(p="good", len=LEN, bs=BS, d_out=ptr(2), out_cap=BIG, d_off=ptr(3), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG,
+                 stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "block_size 0": dict(bs=0), "null workspace": dict(d_ws=None),
+             "null status": dict(d_st=None), "null offsets": dict(d_off=None), "null output": dict(d_out=None),
+             "no workspace bytes": dict(ws_bytes=0), "general params: no workspace bytes": dict(p="wide", ws_bytes=0),
+             "bad params and null output": dict(p="bad", d_out=None), "null output and no workspace bytes": dict(d_out=None, ws_bytes=0)}),
+        "redux_encode_blocks_dev": blocks,
+        "redux_encode_blocks_v_dev": (
+            ["p", "d_in", "in_bytes", "d_tab", "nentries", "nblocks", "bs", "flags", "d_out", "out_cap", "d_off", "d_st", "d_sum", "d_ws",
+             "ws_bytes", "stream"],
+            dict(p="good", d_in=ptr(1), in_bytes=LEN, d_tab=ptr(9), nentries=2 * NB, nblocks=NB, bs=BS, flags=0, d_out=ptr(2), out_cap=BIG,
+                 d_off=ptr(3), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {**v_faults, "null input": dict(d_in=None), "input of 2^32 bytes": dict(in_bytes=1 << 32),
+             "workspace not 256-aligned": dict(d_ws=ptr(6) + 16), "input of 2^32 bytes and no workspace bytes": dict(in_bytes=1 << 32, ws_bytes=0),
+             "no workspace bytes and workspace not 256-aligned": dict(ws_bytes=0, d_ws=ptr(6) + 16)}),
+        "redux_decode_blocks_dev": (
+            ["p", "d_in", "d_off", "nblocks", "bs", "d_out", "out_cap", "d_sz", "d_st", "d_sum", "d_ws", "ws_bytes", "stream"],
+            dict(p="good", d_in=ptr(1), d_off=ptr(3), nblocks=NB, bs=BS, d_out=ptr(2), out_cap=NB * BS, d_sz=ptr(7), d_st=ptr(4), d_sum=ptr(5),
+                 d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "block_size 0": dict(bs=0), "null offsets": dict(d_off=None),
+             "null sizes": dict(d_sz=None), "null status": dict(d_st=None), "null workspace": dict(d_ws=None),
+             "out_cap below the blocks": dict(out_cap=NB * BS - 1), "below the full size": dict(ws_bytes=dec_ws - 1),
+             "lock-step width: no workspace bytes": dict(p="any", ws_bytes=0), "general params: no workspace bytes": dict(p="wide", ws_bytes=0),
+             "bad params and out_cap below the blocks": dict(p="bad", out_cap=0), "null sizes and out_cap below the blocks": dict(d_sz=None, out_cap=0),
+             "out_cap below the blocks and no workspace bytes": dict(out_cap=0, ws_bytes=0)}),
+        "redux_decode_blocks_v_dev": (
+            ["p", "d_in", "d_off", "d_tab", "nentries", "nblocks", "bs", "flags", "d_out", "out_bytes", "d_sz", "d_st", "d_sum", "d_ws",
+             "ws_bytes", "stream"],
+            dict(p="good", d_in=ptr(1), d_off=ptr(3), d_tab=ptr(9), nentries=2 * NB, nblocks=NB, bs=BS, flags=0, d_out=ptr(2), out_bytes=LEN,
+                 d_sz=ptr(7), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {**v_faults, "null output": dict(d_out=None), "null offsets": dict(d_off=None), "null sizes": dict(d_sz=None),
+             "below the full size": dict(ws_bytes=L.redux_decode_workspace_bytes(P["good"], 2 * NB, BS) - 1),
+             "null output and bad params": dict(d_out=None, p="bad")}),
+        "redux_encode_const_dev": (
+            ["p", "d_in", "len", "d_base", "base_len", "bs", "E", "d_out", "out_cap", "d_off", "d_const", "d_st", "d_sum", "d_ws", "ws_bytes",
+             "stream"],
+            dict(p="good", d_in=ptr(1), len=LEN, d_base=ptr(10), base_len=LEN, bs=BS, E=E0, d_out=ptr(2), out_cap=BIG, d_off=ptr(3),
+                 d_const=ptr(8), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "lock-step width": dict(p="any"), "general params": dict(p="wide"),
+             "E 3": dict(E=3), "block_size 0": dict(bs=0), "null workspace": dict(d_ws=None), "null flags": dict(d_const=None),
+             "null status": dict(d_st=None), "null output": dict(d_out=None), "null offsets": dict(d_off=None), "null input": dict(d_in=None),
+             "null base": dict(d_base=None), "input of 2^32 bytes": dict(len=1 << 32), "below the table": dict(ws_bytes=const_front - 1),
+             "no workspace bytes": dict(ws_bytes=0), "workspace not 256-aligned": dict(d_ws=ptr(6) + 16),
+             "input of 2^32 bytes and no workspace bytes": dict(len=1 << 32, ws_bytes=0),
+             "no workspace bytes and workspace not 256-aligned": dict(ws_bytes=0, d_ws=ptr(6) + 16),
+             "general params and E 3": dict(p="wide", E=3)}),
+        "redux_decode_const_dev": (
+            ["p", "d_in", "d_off", "d_const", "d_base", "base_len", "out_len", "bs", "E", "d_out", "d_sz", "d_st", "d_sum", "d_ws", "ws_bytes",
+             "stream"],
+            dict(p="good", d_in=ptr(1), d_off=ptr(3), d_const=ptr(8), d_base=ptr(10), base_len=LEN, out_len=LEN, bs=BS, E=E0, d_out=ptr(2),
+                 d_sz=ptr(7), d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "lock-step width": dict(p="any"), "general params": dict(p="wide"),
+             "E 3": dict(E=3), "block_size 0": dict(bs=0), "null workspace": dict(d_ws=None), "null offsets": dict(d_off=None),
+             "null flags": dict(d_const=None), "null sizes": dict(d_sz=None), "null status": dict(d_st=None), "null output": dict(d_out=None),
+             "null base": dict(d_base=None), "below the full size": dict(ws_bytes=const_dec_ws - 1), "no workspace bytes": dict(ws_bytes=0),
+             "workspace not 256-aligned": dict(d_ws=ptr(6) + 16),
+             "no workspace bytes and workspace not 256-aligned": dict(ws_bytes=0, d_ws=ptr(6) + 16),
+             "null flags and no workspace bytes": dict(d_const=None, ws_bytes=0)}),
+        "redux_base_planes_dev": (
+            ["src", "d_base", "base_len", "dst", "len", "bs", "E", "inverse", "stream"],
+            dict(src=ptr(1), d_base=ptr(10), base_len=LEN, dst=ptr(2), len=LEN, bs=BS, E=E0, inverse=0, stream=None),
+            {"null src": dict(src=None), "null dst": dict(dst=None), "null base": dict(d_base=None), "block_size 0": dict(bs=0),
+             "E 3": dict(E=3), "E 16": dict(E=16), "in place": dict(dst=ptr(1)), "overlap": dict(dst=ptr(1) + 16),
+             "destination over the base": dict(dst=ptr(10) + 16), "inverse in place": dict(dst=ptr(1), inverse=1),
+             "E 3 and len 0": dict(E=3, len=0), "null base and len 0": dict(d_base=None, len=0)}),
+        "redux_encode_base_dev": (
+            ["p", "d_in", "len", "d_base", "base_len", "bs", "E", "d_out", "out_cap", "d_off", "d_st", "d_sum", "d_ws", "ws_bytes", "stream"],
+            dict(p="good", d_in=ptr(1), len=LEN, d_base=ptr(10), base_len=LEN, bs=BS, E=E0, d_out=ptr(2), out_cap=BIG, d_off=ptr(3),
+                 d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "null workspace": dict(d_ws=None), "null input": dict(d_in=None),
+             "null base": dict(d_base=None), "block_size 0": dict(bs=0), "E 3": dict(E=3), "E 16": dict(E=16),
+             "below the copy": dict(ws_bytes=COPY - 1), "E 1: below the copy": dict(E=1, ws_bytes=COPY - 1),
+             "no workspace bytes": dict(ws_bytes=0), "E 3 and no workspace bytes": dict(E=3, ws_bytes=0),
+             "null base and no workspace bytes": dict(d_base=None, ws_bytes=0), "bad params and E 3": dict(p="bad", E=3)}),
+        "redux_decode_base_dev": (
+            ["p", "d_in", "d_off", "d_base", "base_len", "out_len", "bs", "E", "d_out", "d_sz", "d_st", "d_sum", "d_ws", "ws_bytes", "stream"],
+            dict(p="good", d_in=ptr(1), d_off=ptr(3), d_base=ptr(10), base_len=LEN, out_len=LEN, bs=BS, E=E0, d_out=ptr(2), d_sz=ptr(7),
+                 d_st=ptr(4), d_sum=ptr(5), d_ws=ptr(6), ws_bytes=BIG, stream=None),
+            {"bad params": dict(p="bad"), "null params": dict(p="null"), "null workspace": dict(d_ws=None), "null offsets": dict(d_off=None),
+             "null sizes": dict(d_sz=None), "null status": dict(d_st=None), "null output": dict(d_out=None), "null base": dict(d_base=None),
+             "block_size 0": dict(bs=0), "E 3": dict(E=3), "E 16": dict(E=16), "below the copy": dict(ws_bytes=DCOPY - 1),
+             "below the full size": dict(ws_bytes=base_dec_ws - 1), "E 3 and no workspace bytes": dict(E=3, ws_bytes=0),
+             "null base and no workspace bytes": dict(d_base=None, ws_bytes=0), "bad params and null sizes": dict(p="bad", d_sz=None)}),
+    }
+
+
+def collect(L, decl, part):
+    return {"sizes": sizes(L, decl, part), "names": names(L, decl, part), "refusals": refusals(L, decl, part)}
 
 
 def main():
@@ -295,7 +465,9 @@ def main():
     os.environ["ROCR_VISIBLE_DEVICES"] = "-1"
     path = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else None
     L, decl = load(path)
-    json.dump(collect(L, decl), sys.stdout, separators=(",", ":"), sort_keys=True)
+    part = sys.argv[sys.argv.index("--part") + 1] if "--part" in sys.argv else "layered"
+    assert part in ("layered", "adaptive"), part
+    json.dump(collect(L, decl, part), sys.stdout, separators=(",", ":"), sort_keys=True)
     sys.stdout.write("\n")
 
 
