@@ -863,6 +863,32 @@ int redux_block_cost_dev(const redux_params *p, const void *d_in, uint64_t in_le
 int redux_table_cost_dev(const void *d_counts /* u64[n][256] */, const void *d_cum /* u32[n][258] */, uint64_t n,
                          void *d_bits /* f64[n] */, void *stream);
 
+/* ---- layout estimates ------------------------------------------------------------------------------------
+ * The adaptive cost A (above) of every block of the input under each of the eight layouts a caller can put in front of the
+ * adaptive coder, so that the element size and the filter can be chosen without transforming or coding the input once per
+ * candidate.  Layout k = 4 F + log2 E: the byte-plane layout for elements of E = 1, 2, 4, 8 bytes ("byte-plane layout"
+ * above; E = 1: the bytes as they are), behind the delta filter when F = 1 ("delta filter" above; k = 4 is the filter over
+ * single bytes).  Every transformed input has the input's length, so all eight have redux_block_count(in_len, block_size)
+ * blocks.  Nothing about the layouts is new: bits[k][b] is what redux_block_cost_dev gives for block b of what
+ * redux_planes_dev / redux_delta_planes_dev write for (E, F) -- short last frame, trailing bytes and fresh starts of the
+ * frames included -- but it is counted from the untransformed bytes: no transformed copy, no workspace, and one read of
+ * the input per element size (the plain and the delta counts of a frame are taken by two waves of one workgroup).
+ *
+ * redux_layout_cost_dev             d_bits is f64[8][nblocks] on the device; row k is written only when bit k of `layouts`
+ *                                   is set.  Full frames go to k_layout_cost when block_size and d_in are multiples of 16,
+ *                                   everything else (the short last frame included) to k_layout_cost_bytes, which is right
+ *                                   for any alignment and block size but slow.  INVALID_INPUT for a block_size outside
+ *                                   1 .. 2^30, layouts == 0 or a bit above 7; UNSUPPORTED as redux_block_cost_dev.
+ *                                   in_len == 0: one empty block per row.  Stream-ordered, no workspace.
+ * redux_layout_cost_kernel_name     the kernels layout k (0 .. 7) of such a call runs on a 16-byte aligned d_in:
+ *                                   "k_layout_cost<E>", "k_layout_cost_bytes<E>", or both joined by " + " when full frames are
+ *                                   followed by a short one.  "" for a block_size or layout out of range.
+ * redux_layout_cost_kernel_name_at  the same for this d_in, which contributes its alignment only. */
+int         redux_layout_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                  uint32_t layouts /* bit k = layout k */, void *d_bits /* f64[8][nblocks] */, void *stream);
+const char *redux_layout_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t layout);
+const char *redux_layout_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layout);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

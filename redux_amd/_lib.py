@@ -145,6 +145,9 @@ SIGNATURES = {
     "redux_table_cost_from_counts": (C.c_int, [_V, _V, _U64, C.POINTER(C.c_double)]),
     "redux_block_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _V, _V]),
     "redux_table_cost_dev": (C.c_int, [_V, _V, _U64, _V, _V]),
+    "redux_layout_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V]),
+    "redux_layout_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
+    "redux_layout_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
     "redux_planes_check": (C.c_int, [_U32]),
     "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

@@ -1707,6 +1707,73 @@ def _estimate(data, block_size, params, element_size, segment_blocks, models):
     return out, context_cums
 
 
+# ---- layout estimates (include/redux_hip.h, "layout estimates") -----------------------------------
+LAYOUTS = tuple((E, f) for f in (None, "delta") for E in (1, 2, 4, 8))  # layout k = 4 F + log2 E; ties go to the earlier
+
+
+def layout_index(element_size, filter=None):
+    """k of (element_size, filter): 4 F + log2 E"""
+    try:
+        return LAYOUTS.index((element_size, filter))
+    except ValueError:
+        raise InvalidInput()
+
+
+def _layout_mask(layouts):
+    """None: all eight; an int: the bit mask itself; else an iterable of (element_size, filter) pairs or indices"""
+    if layouts is None:
+        return 0xFF
+    if isinstance(layouts, (int, np.integer)):
+        mask = int(layouts)
+    else:
+        mask = 0
+        for k in layouts:
+            k = layout_index(*k) if isinstance(k, tuple) else k
+            if not isinstance(k, (int, np.integer)) or not 0 <= k < 8:
+                raise InvalidInput()
+            mask |= 1 << int(k)
+    if not 0 < mask <= 0xFF:
+        raise InvalidInput()
+    return mask
+
+
+def layout_cost(data, block_size, params=(8, 30, 32), layouts=None):
+    """The adaptive model's ideal code length in bits, EOF included, of every block of each of the eight layouts of `data`
+    -- LAYOUTS[k]: the byte-plane layout for element size 1 / 2 / 4 / 8, then the same behind the delta filter -- counted
+    from the bytes as they are, with no transformed copy (redux_layout_cost_dev: k_layout_cost on torch's current stream, one
+    read-back) -> np.float64[8, nblocks].  layouts: None for all eight, or a bit mask, or (element_size, filter) pairs / layout
+    indices; rows that were not asked for are NaN.  A uint8 device tensor is read where it lies; host data is uploaded once."""
+    P = _params_of(params)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    mask = _layout_mask(layouts)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _device_layout_cost(torch, _lib.lib(), P._c(), d, int(block_size), mask).cpu().numpy()
+
+
+def _device_layout_cost(torch, L, cp, d, block_size, mask):
+    n = d.numel()
+    d_bits = torch.full((8, L.redux_block_count(n, block_size)), float("nan"), dtype=torch.float64, device=d.device)
+    _raise(L.redux_layout_cost_dev(C.byref(cp), C.c_void_p(d.data_ptr()) if n else None, n, block_size, mask,
+                                   C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits
+
+
+def estimate_layouts(data, block_size, params=(8, 30, 32), element_size=None):
+    """-> {(element_size, filter): estimated payload bytes}: what the streams of compress_blocks(..., element_size=,
+    filter=) would add up to under the adaptive model for each layout, without transforming or coding anything: one
+    layout_cost call, then ceil(sum bits / 8 + TERMINATION_BYTES * nblocks) as estimate_payload.  element_size None: all
+    eight layouts; 1 / 2 / 4 / 8: that element size's two, plain and delta."""
+    if element_size is not None:
+        _check_element_size(element_size)
+    want = [k for k in LAYOUTS if element_size is None or k[0] == element_size]
+    bits = layout_cost(data, block_size, params, want)
+    nb = bits.shape[1]
+    return {k: int(np.ceil(float(bits[LAYOUTS.index(k)].sum()) / 8 + TERMINATION_BYTES * nb)) for k in want}
+
+
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------
 def gen_iid(nbytes, seed=0x5EED0001, first_byte=0, device="cuda:0", out=None):
     torch = _torch()

@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta] [--base <base file>] [--skip-constant]
+                            [--filter delta] [--base <base file>] [--skip-constant] [--layout auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -33,8 +33,9 @@ records the tables of the contexts that occur).  It pays on text, logs and sourc
 segment-static always, static and context-static for element size 1, plane-static above -- from histograms of the input taken
 on the GPU, without coding it (redux_amd/container.py: estimate_bytes), and codes with the smallest; ties go to
 the earlier of adaptive, static, plane-static, segment-static, context-static.  The output is that model's container:
-nothing new for -d.  The filter and stored blocks are not chosen automatically: `--model auto` with `--block-size 0`,
-`--stored`, `--filter` or `--segment-blocks` is a usage error.
+nothing new for -d.  The filter and stored blocks are not chosen by it (the filter and the element size are `--layout auto`'s
+choice, under the adaptive model): `--model auto` with `--block-size 0`, `--stored`, `--filter` or `--segment-blocks` is a
+usage error.
 `--checksum` (with -c and a block size) records the CRC-32 (zlib.crc32) of every block's uncompressed bytes in the container
 (version flag 0x10); -d checks every block of such a container against it, and a block that decodes to other bytes -- a
 damaged, swapped or misplaced block -- is a decompression error (exit 3).  A raw reference stream has no room for the
@@ -45,8 +46,8 @@ decodes as a copy.  -d reads any stored container.  `--stored` with `--block-siz
 `--filter delta` (with -c, a block size and any `--element-size`, adaptive model) codes the differences of neighbouring
 little-endian unsigned elements instead of the elements, frame by frame of the byte-plane layout (container version 6):
 for integer series whose values are large but close to their neighbours -- timestamps, sorted indices, offsets, counters,
-sampled signals.  Floating-point data and text get larger with it, so it is never chosen for you.  -d reads it from the
-container.  `--filter` with `--block-size 0`, `--stored` or a `--model` other than adaptive is a usage error.
+sampled signals.  Floating-point data and text get larger with it, so only `--layout auto` chooses it for you.  -d reads it
+from the container.  `--filter` with `--block-size 0`, `--stored` or a `--model` other than adaptive is a usage error.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -59,13 +60,20 @@ leaves every block of the coder's input whose bytes are all equal out of the cod
 version 9) and is rebuilt by a fill.  Behind `--base` that is every unchanged region of a snapshot.  -d reads version 9
 with no flag.  `--skip-constant` with `--block-size 0`, `--stored`, `--filter` or any `--model` other than adaptive is a
 usage error.
+`--layout auto` (with -c and a block size, adaptive model; `--checksum` is allowed) estimates the container the adaptive
+coder would write behind each of the eight layouts -- element size 1, 2, 4, 8, each with and without the delta filter --
+from one pass over the input as it stands on the GPU, without transforming or coding it (redux_amd/container.py:
+estimate_layout_bytes), and codes with the smallest; ties go to the earlier of plain 1, 2, 4, 8, delta 1, 2, 4,
+8.  With `--element-size E` the choice is between plain and delta at that E.  The output is that layout's container (version
+1, 2 or 6): nothing new for -d.  `--layout auto` with `--block-size 0`, `--stored`, `--filter`, `--base`, `--skip-constant`,
+-d or any `--model` other than adaptive is a usage error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>] [--base <base file>] [--skip-constant]")
+         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto>]")
 
 
 def parse(argv):
@@ -82,7 +90,7 @@ def parse(argv):
             opts["compress"] = False
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout"):
             val = next(it, None)
             if val is None:
                 return None
@@ -104,6 +112,10 @@ def parse(argv):
                 opts["filter"] = val
             elif arg == "--base":
                 opts["base"] = val
+            elif arg == "--layout":
+                if val != "auto":
+                    return None
+                opts["layout"] = val
             elif arg == "--segment-blocks":
                 if not val.isdigit() or not 0 < int(val) < 1 << 32:
                     return None
@@ -145,6 +157,9 @@ def parse(argv):
     if opts.get("skip_constant") and (not opts["compress"] or opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                       or opts.get("model", "adaptive") != "adaptive"):
         return None  # the bitmap lives in the container, and only the adaptive coder has the table form in both directions
+    if "layout" in opts and (not opts["compress"] or opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
+                             or "base" in opts or opts.get("skip_constant") or opts.get("model", "adaptive") != "adaptive"):
+        return None  # the choice is recorded as the chosen layout's container, and it is made for the adaptive coder alone
     return None if opts["compress"] is None else opts
 
 
@@ -180,10 +195,12 @@ def main(argv=None):
                 i_n, o_n = api.compress(io.BytesIO(data), o, api.AdaptiveTreeModel.new(params))
                 sink.write(o.getvalue())
             else:
-                blob = container.compress_bytes(data, opts["block_size"], params, opts.get("element_size", 1),
+                # (--layout auto without --element-size: element size None, the choice among all eight layouts)
+                blob = container.compress_bytes(data, opts["block_size"], params,
+                                                opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
                                                 opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
-                                                opts.get("skip_constant", False))
+                                                opts.get("skip_constant", False), opts.get("layout"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

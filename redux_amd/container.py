@@ -470,13 +470,16 @@ def header_is_wellformed(buf):
     return True
 
 
-def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False):
+def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False,
+                   filter=None):
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
-    because only the tables of contexts that occur are recorded."""
+    because only the tables of contexts that occur are recorded.  filter "delta" (adaptive model, not stored): version 6,
+    which records the filter in the header's reserved word and adds no bytes."""
     if model not in api.MODELS or nblocks < 1:
         raise api.InvalidInput()
+    api._check_filter(filter, model == "adaptive" and not stored)
     E = api._check_element_size(element_size)
     n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
     if model == "static":
@@ -506,8 +509,25 @@ def choose_model(estimates):
     return min(estimates, key=lambda m: (estimates[m], api.MODELS.index(m)))
 
 
+LAYOUT_ORDER = api.LAYOUTS  # (1, None), (2, None), (4, None), (8, None), (1, "delta"), ... (8, "delta")
+
+
+def estimate_layout_bytes(data, block_size=65536, params=(8, 30, 32), element_size=None, checksum=False):
+    """-> {(element_size, filter): estimated container bytes} for the adaptive model behind each layout: api.estimate_layouts'
+    estimate of the payloads (one pass over the bytes as they are on the GPU; nothing is transformed or coded) plus
+    overhead_bytes, which is exact.  element_size None: all eight layouts; 1 / 2 / 4 / 8: plain and delta at that size."""
+    payload = api.estimate_layouts(data, block_size, params, element_size)
+    nb = max(1, -(-len(data) // block_size))
+    return {(E, f): payload[(E, f)] + overhead_bytes("adaptive", nb, E, checksum=checksum, filter=f) for E, f in payload}
+
+
+def choose_layout(estimates):
+    """The (element_size, filter) with the smallest estimate; ties go to the earlier of LAYOUT_ORDER."""
+    return min(estimates, key=lambda k: (estimates[k], LAYOUT_ORDER.index(k)))
+
+
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False):
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -526,7 +546,18 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     base (bytes-like of any length; any element_size, model "adaptive", not stored, no filter): an earlier snapshot of the
     data; the XOR against it is coded, version 8, and decompress_bytes needs the same base.
     skip_constant (any element_size, model "adaptive", not stored, no filter; with or without base): blocks of the coder's
-    input whose bytes are all equal travel as one byte and skip the coder in both directions, version 9."""
+    input whose bytes are all equal travel as one byte and skip the coder in both directions, version 9.
+    layout "auto" (model "adaptive", not stored, no filter, no base, no skip_constant): the element size and the filter
+    with the smallest estimate_layout_bytes code the data (choose_layout) -- of all eight layouts when element_size is None,
+    of plain and delta at that size when element_size is 1 / 2 / 4 / 8 (the default, 1, included: a caller who knows the dtype
+    says so, one who does not passes None) -- and the container is that layout's: version 1, 2 or 6, nothing new to
+    decode."""
+    if layout is not None:
+        if layout != "auto" or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
+                or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
+                or (element_size is not None and element_size != 1 and element_size not in ELEMENT_SIZES):
+            raise api.InvalidInput()
+        element_size, filter = choose_layout(estimate_layout_bytes(data, block_size, params, element_size, checksum))
     api._check_constant(skip_constant or None, model == "adaptive" and not stored and filter is None)
     api._check_base(base, model == "adaptive" and not stored and filter is None)
     api._check_filter(filter, model == "adaptive" and not stored)

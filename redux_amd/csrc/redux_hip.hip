@@ -21,6 +21,7 @@
 //   redux_store.hpp    k_store_select / k_store_table / k_store_unpack: stored blocks, the raw bytes of blocks that do not shrink
 //   redux_const.hpp    k_const_select / k_const_table / k_const_fill: constant blocks, one byte for a block of equal bytes
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
+//   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -49,6 +50,7 @@
 #include "redux_store.hpp"
 #include "redux_const.hpp"
 #include "redux_cost.hpp"
+#include "redux_layout_cost.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -807,6 +809,54 @@ static int launch_crc32(const void *d_in, uint64_t in_len, const void *d_sizes, 
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
 }
+
+// ---- layout estimates (redux_layout_cost.hpp) ------------------------------------------------------------------------
+// frames the fast kernel takes: all full ones when block size and buffer are 16-byte multiples, none otherwise
+static uint64_t layout_cost_full_frames(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t E)
+{
+    return block_size % 16 == 0 && ((uintptr_t)d_in & 15) == 0 ? in_len / ((uint64_t)E * block_size) : 0;
+}
+
+template <int E>
+static int launch_layout_cost(const void *d_in, uint64_t in_len, uint32_t block_size, bool plain, bool delta, double *bits,
+                              hipStream_t s)
+{
+    LayoutCostArgs a;
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.nblocks    = redux_block_count(in_len, block_size);
+    a.nfull      = layout_cost_full_frames(d_in, in_len, block_size, E);
+    a.block_size = block_size;
+    a.nfilt      = 0;
+    constexpr uint32_t log2E = E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : 3;
+    a.filt[1] = 0;
+    a.bits[1] = nullptr;
+    if (plain) {
+        a.filt[a.nfilt]   = 0;
+        a.bits[a.nfilt++] = bits + (uint64_t)log2E * a.nblocks;
+    }
+    if (delta) {
+        a.filt[a.nfilt]   = 1;
+        a.bits[a.nfilt++] = bits + (uint64_t)(4 + log2E) * a.nblocks;
+    }
+    if (a.nfull) { // four waves per CU: 160 KiB of LDS
+        const uint64_t cap  = (a.nfilt == 2 ? 2ull : 4ull) * cu_count();
+        const uint32_t grid = (uint32_t)(a.nfull < cap ? a.nfull : cap);
+        if (a.nfilt == 2)
+            k_layout_cost<E, 2><<<grid, 128, 0, s>>>(a);
+        else
+            k_layout_cost<E, 1><<<grid, 64, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t nrest = a.nblocks - a.nfull * E;
+    if (nrest) { // the short last frame, or everything the fast kernel cannot take
+        const uint64_t work = nrest * a.nfilt, cap = (uint64_t)kHistWgsPerCu * cu_count();
+        k_layout_cost_bytes<E><<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    return REDUX_OK;
+}
+
 
 extern "C" {
 
@@ -3991,6 +4041,49 @@ int redux_block_cost_dev(const redux_params *p, const void *d_in, uint64_t in_le
     k_block_cost<<<grid, 64, 0, (hipStream_t)stream>>>(a);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
+}
+
+int redux_layout_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layouts,
+                          void *d_bits, void *stream)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || layouts == 0 || layouts > 0xFF || !d_bits || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    hipStream_t s = (hipStream_t)stream;
+    for (uint32_t e = 0; e < 4 && st == REDUX_OK; e++) {
+        const bool plain = layouts >> e & 1, delta = layouts >> (4 + e) & 1;
+        if (!plain && !delta)
+            continue;
+        switch (e) {
+        case 0: st = launch_layout_cost<1>(d_in, in_len, block_size, plain, delta, (double *)d_bits, s); break;
+        case 1: st = launch_layout_cost<2>(d_in, in_len, block_size, plain, delta, (double *)d_bits, s); break;
+        case 2: st = launch_layout_cost<4>(d_in, in_len, block_size, plain, delta, (double *)d_bits, s); break;
+        default: st = launch_layout_cost<8>(d_in, in_len, block_size, plain, delta, (double *)d_bits, s); break;
+        }
+    }
+    return st;
+}
+
+const char *redux_layout_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layout)
+{
+    static const char *const names[4][3] = {
+        {"k_layout_cost<1>", "k_layout_cost<1> + k_layout_cost_bytes<1>", "k_layout_cost_bytes<1>"},
+        {"k_layout_cost<2>", "k_layout_cost<2> + k_layout_cost_bytes<2>", "k_layout_cost_bytes<2>"},
+        {"k_layout_cost<4>", "k_layout_cost<4> + k_layout_cost_bytes<4>", "k_layout_cost_bytes<4>"},
+        {"k_layout_cost<8>", "k_layout_cost<8> + k_layout_cost_bytes<8>", "k_layout_cost_bytes<8>"},
+    };
+    if (block_size == 0 || block_size > (1u << 30) || layout > 7)
+        return "";
+    const uint32_t e = layout & 3, E = 1u << e;
+    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
+    return names[e][nfull == 0 ? 2 : nfull * E < redux_block_count(in_len, block_size) ? 1 : 0];
+}
+
+const char *redux_layout_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t layout)
+{
+    return redux_layout_cost_kernel_name_at(nullptr, in_len, block_size, layout);
 }
 
 int redux_table_cost_dev(const void *d_counts, const void *d_cum, uint64_t n, void *d_bits, void *stream)
