@@ -889,6 +889,78 @@ int         redux_layout_cost_dev(const redux_params *p, const void *d_in, uint6
 const char *redux_layout_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t layout);
 const char *redux_layout_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layout);
 
+/* ---- mixed layouts --------------------------------------------------------------------------------------
+ * One layout per UNIT of the input instead of one per input, for files that hold several element types (bf16 weights next to
+ * fp32 state, int64 indices and text): the eight layouts of "layout estimates" above, chosen for every unit on its own.
+ *
+ * Unit         REDUX_MIXED_UNIT_BLOCKS (8) consecutive blocks, 8 * block_size bytes; only the last unit may be shorter;
+ *              nunits = ceil(nblocks / 8).  The unit size is not a parameter.  8 is a multiple of every element size, so
+ *              every unit boundary is a frame boundary of every layout.
+ * Unit table   u8[nunits], entry k = 4 F + log2 E in 0 .. 7: the layout index of redux_layout_cost_dev.
+ * Transform    the bytes of unit u of the result are the bytes of unit u of what redux_planes_dev (F = 0) or
+ *              redux_delta_planes_dev (F = 1) writes for the WHOLE buffer under layout table[u]; layout 0 is a copy.  Frames
+ *              start afresh and units are whole frames, so this is well defined, the short last unit with its short last
+ *              frame and trailing bytes included.  The inverse undoes it unit by unit.
+ * Choice       S[k][u] = the sum of bits[k][b] over the unit's blocks, added in f64 in ascending block order from 0.0;
+ *              table[u] = the lowest selected k with the smallest S[k][u].  No hysteresis.
+ *
+ * On the device a table byte is taken & 7: no table content makes a kernel read or write outside [0, len).  A table in HOST
+ * memory (the redux_*_blocks_mixed pair) with a byte above 7 is INVALID_INPUT before any launch.
+ *
+ * redux_mixed_unit_count            ceil(redux_block_count(in_len, block_size) / 8); 0 for block_size 0.
+ * redux_mixed_choose_dev            d_bits f64[8][nblocks] (redux_layout_cost_dev's; only the rows of layouts_mask are read)
+ *                                   -> d_table u8[ceil(nblocks / 8)] by the rule (k_mixed_choose).  d_sum_bits may be null:
+ *                                   one u64 that receives the sum over the units of the chosen S, in units of
+ *                                   2^-REDUX_MIXED_SUM_FRAC_BITS bit, each unit rounded to nearest.  INVALID_INPUT for
+ *                                   layouts_mask == 0 or a bit above 7, null d_bits or d_table, nblocks == 0.
+ * redux_mixed_layout_dev            the transform (inverse != 0: its inverse) of d_src[0 .. len) into d_dst, not in place.
+ *                                   Full units go to k_mixed_planes when block_size and both pointers are multiples of 16,
+ *                                   everything else (the short last unit included) to k_mixed_bytes, which is right for any
+ *                                   alignment and block size but slow.  INVALID_INPUT for a block_size outside 1 .. 2^30
+ *                                   or a null d_table.  Stream-ordered, no workspace.
+ * redux_encode_mixed_dev            layouts_mask != 0: the costs of those layouts (redux_layout_cost_dev, rows in the
+ *                                   workspace), the choice into d_table, the transform and the adaptive coder over it, all
+ *                                   stream-ordered with no host synchronisation.  layouts_mask == 0: d_table is used as given.
+ *                                   The rest as redux_encode_planes_dev.  INVALID_INPUT for a block_size outside 1 .. 2^30,
+ *                                   mask bits above 7 or a null d_table; UNSUPPORTED where redux_block_cost_dev is.
+ * redux_decode_mixed_dev            as redux_decode_planes_dev with the unit table in place of the element size: the blocks
+ *                                   decode into the plane buffer of the workspace, their sizes are checked, and the inverse
+ *                                   writes d_out[0 .. out_len) and nothing else.
+ * redux_encode_blocks_mixed / redux_decode_blocks_mixed   the host-pointer pair on the chunk pipeline; `table` is
+ *                                   u8[nunits] in host memory (written when layouts_mask != 0, read otherwise and by
+ *                                   decode); block_crc may be null: the CRC-32 of every block of the original bytes.  The
+ *                                   choice is per unit and chunks are whole units, so the result does not depend on the
+ *                                   chunking.
+ * redux_mixed_kernel_name           what redux_mixed_layout_dev runs on 16-byte aligned buffers: "k_mixed_planes<0>" (<1>:
+ *                                   inverse), "k_mixed_bytes<0>", or both joined by " + " when full units are followed by a
+ *                                   short one.  "" for a block_size out of range or len == 0.
+ * redux_mixed_kernel_name_at        the same for these pointers, which contribute their alignment only. */
+#define REDUX_MIXED_UNIT_BLOCKS 8
+#define REDUX_MIXED_SUM_FRAC_BITS 16
+uint64_t    redux_mixed_unit_count(uint64_t in_len, uint32_t block_size);
+int         redux_mixed_choose_dev(const void *d_bits /* f64[8][nblocks] */, uint64_t nblocks, uint32_t layouts_mask,
+                                   void *d_table /* u8[nunits] */, void *d_sum_bits /* u64, may be null */, void *stream);
+int         redux_mixed_layout_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size,
+                                   const void *d_table /* u8[nunits] */, int inverse, void *stream);
+uint64_t    redux_encode_mixed_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size);
+uint64_t    redux_decode_mixed_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size);
+int         redux_encode_mixed_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                   uint32_t layouts_mask, void *d_table /* u8[nunits] */, void *d_out, uint64_t out_cap,
+                                   void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
+                                   uint64_t workspace_bytes, void *stream);
+int         redux_decode_mixed_dev(const redux_params *p, const void *d_in, const void *d_in_offsets,
+                                   const void *d_table /* u8[nunits] */, uint64_t out_len, uint32_t block_size, void *d_out,
+                                   void *d_out_sizes, void *d_block_status, void *d_summary, void *d_workspace,
+                                   uint64_t workspace_bytes, void *stream);
+int         redux_encode_blocks_mixed(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                      uint32_t layouts_mask, uint8_t *table /* u8[nunits] */, uint8_t *out, uint64_t out_cap,
+                                      uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc);
+int         redux_decode_blocks_mixed(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets,
+                                      const uint8_t *table /* u8[nunits] */, uint64_t out_len, uint32_t block_size, uint8_t *out,
+                                      uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+const char *redux_mixed_kernel_name(uint64_t in_len, uint32_t block_size, int inverse);
+const char *redux_mixed_kernel_name_at(const void *d_src, const void *d_dst, uint64_t in_len, uint32_t block_size, int inverse);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

@@ -15,4 +15,5 @@ from .api import (  # noqa: F401
     SegmentStaticModel, segment_static_tables, segment_static_tables_from_counts, default_segment_blocks, DeviceSegmentStaticCoder,
     MODELS, adaptive_cost_from_counts, table_cost_from_counts, block_cost, table_cost, estimate_candidates, estimate_payload,
     LAYOUTS, layout_index, layout_cost, estimate_layouts,
+    mixed_units, choose_unit_layouts, mixed_layout,
 )

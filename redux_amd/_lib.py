@@ -148,6 +148,18 @@ SIGNATURES = {
     "redux_layout_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V]),
     "redux_layout_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
     "redux_layout_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
+    # mixed layouts: a layout per unit of 8 blocks
+    "redux_mixed_unit_count": (_U64, [_U64, _U32]),
+    "redux_mixed_choose_dev": (C.c_int, [_V, _U64, _U32, _V, _V, _V]),
+    "redux_mixed_layout_dev": (C.c_int, [_V, _V, _U64, _U32, _V, C.c_int, _V]),
+    "redux_encode_mixed_workspace_bytes": (_U64, [_PP, _U64, _U32]),
+    "redux_decode_mixed_workspace_bytes": (_U64, [_PP, _U64, _U32]),
+    "redux_encode_mixed_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_mixed_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_mixed": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_mixed": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _V, _V, _V, _V]),
+    "redux_mixed_kernel_name": (C.c_char_p, [_U64, _U32, C.c_int]),
+    "redux_mixed_kernel_name_at": (C.c_char_p, [_V, _V, _U64, _U32, C.c_int]),
     "redux_planes_check": (C.c_int, [_U32]),
     "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

@@ -552,8 +552,83 @@ def _array_arg(a, dtype, nb, writable=True):
     return _ptr(a)
 
 
+def _check_mixed(params, element_size=1, filter=None, stored=None, base=None, constant=None):
+    """the mixed layouts go with the adaptive model alone: a static model, an element size, a filter, stored blocks, a base
+    or the constant-block option next to them is InvalidInput.  A check on the arguments alone: it comes before any call
+    into the library."""
+    if isinstance(params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)) \
+            or not isinstance(element_size, (int, np.integer)) or element_size != 1 or filter is not None or stored is not None \
+            or base is not None or not (constant is None or constant is False):
+        raise InvalidInput()
+
+
+def _unit_table_arg(table, nunits):
+    """a caller's unit table -> a contiguous np.uint8[nunits] with every entry 0 .. 7 (else InvalidInput)"""
+    if not isinstance(table, np.ndarray) or table.dtype != np.uint8 or table.shape != (nunits,) or bool((table > 7).any()):
+        raise InvalidInput()
+    return np.ascontiguousarray(table)
+
+
+def mixed_units(nbytes, block_size):
+    """units of 8 blocks (include/redux_hip.h, "mixed layouts") of an input of nbytes: ceil(nblocks / 8)"""
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30 or nbytes < 0:
+        raise InvalidInput()
+    return int(_lib.lib().redux_mixed_unit_count(int(nbytes), int(block_size)))
+
+
+def _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc):
+    P = _params_of(params)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30:
+        raise InvalidInput()
+    choose = unit_layouts is True
+    mask = _layout_mask(layouts) if choose else 0
+    if not choose and layouts is not None:
+        raise InvalidInput()
+    a = _u8(data)
+    L = _lib.lib()
+    cp = P._c()
+    nunits = L.redux_mixed_unit_count(len(a), block_size)
+    table = np.zeros(nunits, dtype=np.uint8) if choose else _unit_table_arg(unit_layouts, nunits).copy()
+    _raise(L.redux_device_supports(C.byref(cp)))
+    nb = L.redux_block_count(len(a), block_size)
+    crc = _array_arg(block_crc, np.uint32, nb)
+    cap = L.redux_encode_bound(C.byref(cp), len(a), block_size)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    offs = np.zeros(nb + 1, dtype=np.uint64)
+    status = np.zeros(nb, dtype=np.int32)
+    _raise(L.redux_encode_blocks_mixed(C.byref(cp), _ptr(a), len(a), block_size, mask, table.ctypes.data, out.ctypes.data, cap,
+                                       offs.ctypes.data, status.ctypes.data, crc))
+    res = (out[: int(offs[-1])], offs, status)
+    return res + (table,) if choose else res
+
+
+def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc):
+    P = _params_of(params)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30 or length is None or int(length) < 0:
+        raise InvalidInput()
+    length = int(length)
+    a = _u8(streams)
+    offs = _offsets_in(offsets, len(a))
+    nb = len(offs) - 1
+    L = _lib.lib()
+    if nb != L.redux_block_count(length, block_size):
+        raise InvalidInput()
+    table = _unit_table_arg(unit_layouts, L.redux_mixed_unit_count(length, block_size))
+    cp = P._c()
+    _raise(L.redux_device_supports(C.byref(cp)))
+    crc = _array_arg(block_crc, np.uint32, nb)
+    out = np.empty(max(length, 1), dtype=np.uint8)
+    sizes = np.zeros(nb, dtype=np.uint32)
+    status = np.zeros(nb, dtype=np.int32)
+    st = L.redux_decode_blocks_mixed(C.byref(cp), _ptr(a), offs.ctypes.data, table.ctypes.data, length, block_size, out.ctypes.data,
+                                     sizes.ctypes.data, status.ctypes.data, crc)
+    if check:
+        _raise(st)
+    return out[:length], sizes, status
+
+
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
-                    store_ratio=STORE_RATIO, filter=None, base=None, constant=None):
+                    store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -580,7 +655,17 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     blocks": redux_encode_blocks_const), or True: the flags are then allocated here and returned as a fourth value.  A block
     of the coder's input whose bytes are all equal has that one byte as its payload and skips the coder;
     decompress_blocks(..., element_size, length, constant=flags) undoes it.  With or without base=; adaptive model only, and
-    not with stored= or filter=."""
+    not with stored= or filter=.
+    unit_layouts: the mixed layouts (include/redux_hip.h, "mixed layouts": redux_encode_blocks_mixed), a layout per unit of 8
+    blocks.  True: every unit's layout is chosen on the device among `layouts` (None: all eight; else as layout_cost's) and the
+    table, np.uint8[nunits], is returned as a fourth value.  A np.uint8[nunits]: the table is dictated; an entry above 7 is
+    InvalidInput.  decompress_blocks(..., unit_layouts=table, length=) undoes it.  Adaptive model only, and with none of
+    element_size, filter=, stored=, base= or constant=."""
+    if unit_layouts is not None:
+        _check_mixed(params, element_size, filter, stored, base, constant)
+        return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
+    if layouts is not None:
+        raise InvalidInput()
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
@@ -663,7 +748,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None, constant=None):
+                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -685,7 +770,12 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=.
     constant: the np.uint8[nblocks] flags compress_blocks(..., constant=) wrote (redux_decode_blocks_const), with the
     same base= if one was given; length is required for every element_size, and out is the original bytes.  Adaptive model
-    only, and not with stored= or filter=."""
+    only, and not with stored= or filter=.
+    unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
+    required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc."""
+    if unit_layouts is not None:
+        _check_mixed(params, element_size, filter, stored, base, constant)
+        return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
@@ -1044,7 +1134,14 @@ class DeviceEncoder(_DeviceCoder):
     the coder's input whose bytes are all equal skip the coder (include/redux_hip.h, "constant blocks"), with or without
     base=, not together with filter=; encode() then returns the u8 flags as a fifth value."""
 
-    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False):
+    def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
+                 mixed=False, layouts=None):
+        self.mixed = bool(mixed)
+        if self.mixed:  # (with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
+            _check_mixed(params, element_size, filter, None, base, constant)
+            self.mixed_mask = _layout_mask(layouts)
+        elif layouts is not None:
+            raise InvalidInput()
         self.constant = _check_constant(constant, filter is None and not isinstance(
             params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
         _check_base(base, filter is None)   # (before the filter's own check: both together are refused whatever the filter)
@@ -1059,7 +1156,13 @@ class DeviceEncoder(_DeviceCoder):
         B = self.block_size
         # what encode() runs: the workspace size of the entry point, the entry point, and its arguments between
         # (cp, d_in, n) and the tail
-        if self.delta:
+        if self.mixed:  # (encode() fills in the mask and the table)
+            if not 0 < B <= 1 << 30:
+                raise InvalidInput()
+            ws_bytes, self._encode_dev, self._lead = (lambda cp, n, b, e: L.redux_encode_mixed_workspace_bytes(cp, n, b)), \
+                L.redux_encode_mixed_dev, (B,)
+            self.unit_table = torch.zeros(max(L.redux_mixed_unit_count(self.max_in_len, B), 1), dtype=torch.uint8, device=self.device)
+        elif self.delta:
             ws_bytes, self._encode_dev, self._lead = L.redux_encode_delta_workspace_bytes, L.redux_encode_delta_dev, (B, E)
         elif self.constant:  # (the tail then holds the flags as well)
             ws_bytes, self._encode_dev = L.redux_encode_const_workspace_bytes, L.redux_encode_const_dev
@@ -1071,7 +1174,7 @@ class DeviceEncoder(_DeviceCoder):
             ws_bytes = L.redux_encode_planes_workspace_bytes
             self._encode_dev, self._lead = (L.redux_encode_blocks_dev, (B,)) if E == 1 else (L.redux_encode_planes_dev, (B, E))
         ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, E)
-        if self.constant and ws_bytes == 0:
+        if (self.constant or self.mixed) and ws_bytes == 0:
             raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
         out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, B)
         self._alloc_workspace(ws_bytes)
@@ -1080,7 +1183,7 @@ class DeviceEncoder(_DeviceCoder):
 
     def _plain_only(self):
         """the two phases are the plain coder's; encode() applies the layout and the filter"""
-        if self.element_size != 1 or self.delta or self.base is not None or self.constant:
+        if self.element_size != 1 or self.delta or self.base is not None or self.constant or self.mixed:
             raise Unsupported()
 
     @_on_device
@@ -1099,10 +1202,29 @@ class DeviceEncoder(_DeviceCoder):
         _raise(_lib.lib().redux_compact_slots_dev(C.byref(self.cp), n, self.block_size, *self._enc_tail()))
 
     @_on_device
-    def encode(self, d_in):
+    def encode(self, d_in, unit_layouts=None):
         """Full pass, stream-ordered: returns (out, offsets[nblocks+1], status, summary) views
-        of this encoder's buffers (valid until the next call)."""
+        of this encoder's buffers (valid until the next call).  An encoder made with mixed=True chooses a layout per unit of
+        8 blocks on the device (include/redux_hip.h, "mixed layouts") and returns the device table, uint8[nunits], as a fifth
+        value; unit_layouts: a uint8 device tensor of nunits entries that dictates the table instead (taken & 7)."""
         n = self._check_input(d_in)
+        if self.mixed:
+            L = _lib.lib()
+            nunits = L.redux_mixed_unit_count(n, self.block_size)
+            mask = self.mixed_mask
+            if unit_layouts is not None:
+                torch = _torch()
+                if not isinstance(unit_layouts, torch.Tensor) or not unit_layouts.is_cuda or unit_layouts.dtype != torch.uint8 \
+                        or not unit_layouts.is_contiguous() or unit_layouts.numel() != nunits:
+                    raise InvalidInput()
+                self.unit_table[:nunits].copy_(unit_layouts)
+                mask = 0
+            self.summary.zero_()
+            _raise(self._encode_dev(C.byref(self.cp), _dptr(d_in), n, self.block_size, mask, self.unit_table.data_ptr(),
+                                    *self._enc_tail()))
+            return self._enc_result(n) + (self.unit_table[:nunits],)
+        if unit_layouts is not None:
+            raise InvalidInput()
         self.summary.zero_()
         tail = self._enc_tail()
         if self.constant:  # (the flags go between the offsets and the status)
@@ -1119,7 +1241,11 @@ class DeviceDecoder(_DeviceCoder):
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
     streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags))."""
 
-    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False):
+    def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
+                 mixed=False):
+        self.mixed = bool(mixed)
+        if self.mixed:  # (the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
+            _check_mixed(params, element_size, filter, None, base, constant)
         self.constant = _check_constant(constant, filter is None and not isinstance(
             params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
         _check_base(base, filter is None)
@@ -1133,7 +1259,11 @@ class DeviceDecoder(_DeviceCoder):
         self.max_blocks = int(max_blocks)
         super().__init__(P, block_size, self.max_blocks * int(block_size), device, nblocks_max=self.max_blocks)
         # what decode(..., length) runs: the entry point and its arguments between the offsets and the length
-        if self.constant:  # (the flags of the call come in front of them)
+        if self.mixed:
+            if not 0 < self.block_size <= 1 << 30:
+                raise InvalidInput()
+            self._decode_dev, self._lead, ws_bytes = L.redux_decode_mixed_dev, (), self._layout_ws_bytes(self.max_in_len)
+        elif self.constant:  # (the flags of the call come in front of them)
             self._decode_dev, self._lead = L.redux_decode_const_dev, _base_pair(self.base)
             ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
             if ws_bytes == 0:
@@ -1159,14 +1289,28 @@ class DeviceDecoder(_DeviceCoder):
         return _lib.lib().redux_decode_planes_workspace_bytes(C.byref(self.cp), nbytes, self.block_size, self.element_size)
 
     @_on_device
-    def decode(self, d_streams, d_offsets, length=None, constant=None):
+    def decode(self, d_streams, d_offsets, length=None, constant=None, unit_layouts=None):
         """length: bytes of the original input; required with element_size > 1 (d_offsets then holds
         redux_block_count(length, block_size) + 1 entries), and the result is out[:length].  constant: the uint8 device
-        tensor of nblocks flags the encoder returned, for a decoder made with constant=True (and only for one)."""
+        tensor of nblocks flags the encoder returned, for a decoder made with constant=True (and only for one).
+        unit_layouts: the uint8 device tensor of nunits entries the encoder returned, for a decoder made with mixed=True (and
+        only for one); the length is then required."""
         torch = _torch()
         L = _lib.lib()
         nb = d_offsets.numel() - 1
         assert nb <= self.max_blocks and d_offsets.dtype == torch.int64 and d_streams.dtype == torch.uint8
+        if (unit_layouts is None) == self.mixed:
+            raise InvalidInput()
+        if self.mixed:
+            if length is None or length < 0 or L.redux_block_count(int(length), self.block_size) != nb \
+                    or not isinstance(unit_layouts, torch.Tensor) or not unit_layouts.is_cuda or unit_layouts.dtype != torch.uint8 \
+                    or not unit_layouts.is_contiguous() \
+                    or unit_layouts.numel() != L.redux_mixed_unit_count(int(length), self.block_size):
+                raise InvalidInput()
+            self.summary.zero_()
+            _raise(self._decode_dev(C.byref(self.cp), _dptr(d_streams), d_offsets.data_ptr(), unit_layouts.data_ptr(), int(length),
+                                    self.block_size, self.out.data_ptr(), *self._dec_tail()))
+            return self._dec_result(int(length), nb)
         if (length is None and (self.element_size > 1 or self.delta or self.base is not None or self.constant)) \
                 or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)) \
                 or (constant is None) == self.constant:
@@ -1462,6 +1606,45 @@ def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The delta filter followed by the byte-plane layout (include/redux_hip.h, "delta filter") of a uint8 device tensor,
     or their inverse: redux_delta_planes_dev on torch's current stream.  out: as for planes()."""
     return _transform("redux_delta_planes_dev", d_src, element_size, block_size, inverse, out)
+
+
+def _device_unit_table(torch, table, nunits, device):
+    """a unit table for a device call: a uint8 device tensor is taken as it is, host values (np.uint8, a list) are uploaded;
+    InvalidInput unless it has nunits entries.  Entries are taken & 7 on the device."""
+    if isinstance(table, torch.Tensor):
+        if not table.is_cuda or table.dtype != torch.uint8 or not table.is_contiguous() or table.device != device:
+            raise InvalidInput()
+        t = table
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(table, dtype=np.uint8).copy()).to(device)
+    if t.dim() != 1 or t.numel() != nunits:
+        raise InvalidInput()
+    return t
+
+
+def mixed_layout(d_src, table, block_size, inverse=False, out=None):
+    """The mixed transform (include/redux_hip.h, "mixed layouts") of a uint8 device tensor, or its inverse: unit u of 8 blocks
+    under layout table[u] & 7, redux_mixed_layout_dev on torch's current stream.  table: nunits entries, a uint8 device tensor
+    or host values.  out: as for planes()."""
+    torch = _torch()
+    assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30:
+        raise InvalidInput()
+    n = d_src.numel()
+    L = _lib.lib()
+    d_table = _device_unit_table(torch, table, L.redux_mixed_unit_count(n, int(block_size)), d_src.device)
+    t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
+    with torch.cuda.device(t.device):
+        _raise(L.redux_mixed_layout_dev(_dptr(d_src), _dptr(t), n, int(block_size), d_table.data_ptr(), 1 if inverse else 0,
+                                        _stream_ptr(torch)))
+    return t
+
+
+def mixed_kernel_name(d_src, d_dst, block_size, inverse=False):
+    """what mixed_layout runs between these two tensors: "k_mixed_planes<I>", "k_mixed_bytes<I>" or both joined by " + " """
+    return _lib.lib().redux_mixed_kernel_name_at(_dptr(d_src), _dptr(d_dst), d_src.numel(), int(block_size),
+                                                 1 if inverse else 0).decode()
 
 
 def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None):
@@ -1761,17 +1944,68 @@ def _device_layout_cost(torch, L, cp, d, block_size, mask):
     return d_bits
 
 
-def estimate_layouts(data, block_size, params=(8, 30, 32), element_size=None):
+MIXED_SUM_SCALE = 65536.0  # redux_mixed_choose_dev's sum counts 2^-16 bit (REDUX_MIXED_SUM_FRAC_BITS)
+
+
+def _device_choose(torch, L, d_bits, mask):
+    """d_bits f64[8][nblocks] on the device -> (device table uint8[nunits], device sum int64[1] in 2^-16 bit)"""
+    nb = d_bits.shape[1]
+    d_table = torch.zeros((nb + 7) // 8, dtype=torch.uint8, device=d_bits.device)
+    d_sum = torch.zeros(1, dtype=torch.int64, device=d_bits.device)
+    _raise(L.redux_mixed_choose_dev(d_bits.data_ptr(), nb, mask, d_table.data_ptr(), d_sum.data_ptr(), _stream_ptr(torch)))
+    return d_table, d_sum
+
+
+def choose_unit_layouts(bits, layouts=None):
+    """The choice of the mixed layouts (include/redux_hip.h, "mixed layouts") on the device: bits, float64[8, nblocks] as
+    layout_cost returns them (a numpy array is uploaded, a device tensor read where it lies) -> (np.uint8[nunits], the sum of
+    the chosen units' bits as a float).  table[u] is the lowest layout of `layouts` (None: all eight; else as layout_cost's)
+    with the smallest sum over the unit's blocks, added in ascending block order (redux_mixed_choose_dev: k_mixed_choose on
+    torch's current stream, one read-back).  Only the rows of `layouts` are read."""
+    mask = _layout_mask(layouts)
+    torch = _torch()
+    if isinstance(bits, torch.Tensor):
+        d_bits = bits
+        if not d_bits.is_cuda or d_bits.dtype != torch.float64 or not d_bits.is_contiguous():
+            raise InvalidInput()
+    else:
+        d_bits = torch.from_numpy(np.ascontiguousarray(bits, dtype=np.float64).copy()).cuda()
+    if d_bits.dim() != 2 or d_bits.shape[0] != 8 or d_bits.shape[1] == 0:
+        raise InvalidInput()
+    with torch.cuda.device(d_bits.device):
+        d_table, d_sum = _device_choose(torch, _lib.lib(), d_bits, mask)
+        return d_table.cpu().numpy(), int(d_sum.cpu()[0]) / MIXED_SUM_SCALE
+
+
+def estimate_layouts(data, block_size, params=(8, 30, 32), element_size=None, mixed=False):
     """-> {(element_size, filter): estimated payload bytes}: what the streams of compress_blocks(..., element_size=,
     filter=) would add up to under the adaptive model for each layout, without transforming or coding anything: one
     layout_cost call, then ceil(sum bits / 8 + TERMINATION_BYTES * nblocks) as estimate_payload.  element_size None: all
-    eight layouts; 1 / 2 / 4 / 8: that element size's two, plain and delta."""
+    eight layouts; 1 / 2 / 4 / 8: that element size's two, plain and delta.  mixed=True adds the key "mixed": the same for the
+    streams of compress_blocks(..., unit_layouts=True, layouts=those layouts), from the bits of the layout chosen for each
+    unit of 8 blocks (redux_mixed_choose_dev, on the cost rows where they lie)."""
     if element_size is not None:
         _check_element_size(element_size)
     want = [k for k in LAYOUTS if element_size is None or k[0] == element_size]
-    bits = layout_cost(data, block_size, params, want)
+    if not mixed:
+        bits = layout_cost(data, block_size, params, want)
+        nb = bits.shape[1]
+        return {k: int(np.ceil(float(bits[LAYOUTS.index(k)].sum()) / 8 + TERMINATION_BYTES * nb)) for k in want}
+    P = _params_of(params)
+    if not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    mask = _layout_mask(want)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    L = _lib.lib()
+    with torch.cuda.device(d.device):
+        d_bits = _device_layout_cost(torch, L, P._c(), d, int(block_size), mask)
+        _, d_sum = _device_choose(torch, L, d_bits, mask)
+        bits, chosen = d_bits.cpu().numpy(), int(d_sum.cpu()[0]) / MIXED_SUM_SCALE
     nb = bits.shape[1]
-    return {k: int(np.ceil(float(bits[LAYOUTS.index(k)].sum()) / 8 + TERMINATION_BYTES * nb)) for k in want}
+    est = {k: int(np.ceil(float(bits[LAYOUTS.index(k)].sum()) / 8 + TERMINATION_BYTES * nb)) for k in want}
+    est["mixed"] = int(np.ceil(chosen / 8 + TERMINATION_BYTES * nb))
+    return est
 
 
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------

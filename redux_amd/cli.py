@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta] [--base <base file>] [--skip-constant] [--layout auto]
+                            [--filter delta] [--base <base file>] [--skip-constant] [--layout auto|mixed]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -67,13 +67,19 @@ estimate_layout_bytes), and codes with the smallest; ties go to th
 8.  With `--element-size E` the choice is between plain and delta at that E.  The output is that layout's container (version
 1, 2 or 6): nothing new for -d.  `--layout auto` with `--block-size 0`, `--stored`, `--filter`, `--base`, `--skip-constant`,
 -d or any `--model` other than adaptive is a usage error.
+`--layout mixed` (with -c and a block size, adaptive model; `--checksum` is allowed) makes that choice for every unit of 8
+blocks on its own, on the GPU, and codes each unit behind its own layout (container version 10, which records a byte per
+unit): for files that hold several element types -- a checkpoint with bf16 weights next to fp32 state, int64
+indices and a text header -- where one layout for the whole file can only be the least bad.  A file of one type pays one byte
+per 8 blocks for it.  With `--element-size E` every unit is plain or delta at that E.  -d reads version 10 with no flag.
+The usage errors are those of `--layout auto`.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto>]")
+         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>]")
 
 
 def parse(argv):
@@ -113,7 +119,7 @@ def parse(argv):
             elif arg == "--base":
                 opts["base"] = val
             elif arg == "--layout":
-                if val != "auto":
+                if val not in ("auto", "mixed"):
                     return None
                 opts["layout"] = val
             elif arg == "--segment-blocks":
@@ -195,7 +201,7 @@ def main(argv=None):
                 i_n, o_n = api.compress(io.BytesIO(data), o, api.AdaptiveTreeModel.new(params))
                 sink.write(o.getvalue())
             else:
-                # (--layout auto without --element-size: element size None, the choice among all eight layouts)
+                # (--layout auto / mixed without --element-size: element size None, the choice among all eight layouts)
                 blob = container.compress_bytes(data, opts["block_size"], params,
                                                 opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),

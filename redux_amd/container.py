@@ -9,14 +9,16 @@ Layout (little-endian):
     4   1  version (1; 2 = byte-plane layout; 3 = static-table model; 4 = plane-static: a static table per byte plane;
            5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
-           layout; 9 = constant blocks skipped, with or without the XOR-against-base filter)
+           layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
+           per unit of 8 blocks)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
            the table count, which must equal E, in the high 16 bits (0x00020002, 0x00040004, 0x00080008); version 5:
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
            0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
-           version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0
+           version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
+           0xA0000000
    16   8  nblocks
    24   8  total uncompressed length
    (version 8, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
@@ -28,6 +30,7 @@ Layout (little-endian):
    ..  4*nblocks   compressed size of each block
    (flag 0x10 only) 4*nblocks  CRC-32 of each block's uncompressed bytes, u32
    (flag 0x40 only) ceil(nblocks/8)  stored-block bitmap: bit b % 8 of byte b // 8 (LSB first) = block b is stored
+   (version 10 only) ceil(nblocks/8)  the unit table: the layout k = 4 F + log2 E, 0 .. 7, of each unit of 8 blocks, u8
    ..  payloads, concatenated in block order
 
 Version 2 is the same layout for data coded with the byte-plane layout of typed data (include/redux_hip.h): the payloads
@@ -78,7 +81,14 @@ base given for F = 0 is InvalidInput.  The marker nibble 9 of the word at offset
 carries it.  It has no stored blocks (no 0x49 / 0x59), and 0x29 / 0x89 are InvalidInput as for every version.  Without
 skip_constant=True the writers emit exactly the bytes they emitted before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x19: versions 1 to 9 with checksums) means a table of nblocks
+Version 10 holds streams of the adaptive coder behind the mixed layouts (include/redux_hip.h, "mixed layouts"): every unit
+of 8 blocks has a layout of its own -- the byte-plane layout for elements of 1, 2, 4 or 8 bytes, with or without the delta
+filter -- recorded in the unit table, one byte per unit, which follows the size table and the CRC table (0x1A).  A table
+byte above 7 is InvalidInput, a truncated table Eof.  The marker nibble 0xA of the word at offset 12 is required: no other
+version's word carries it.  It has no stored blocks (no 0x4A / 0x5A).  Without layout="mixed" the writers emit exactly the
+bytes they emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1A: versions 1 to 10 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -109,6 +119,9 @@ VERSION_DELTA = 6
 VERSION_CONTEXT_STATIC = 7
 VERSION_BASE = 8
 VERSION_CONST = 9
+VERSION_MIXED = 10
+MIXED_MARK = 0xA0000000  # version 10's word at offset 12
+MIXED_UNIT_BLOCKS = 8  # blocks of a unit of the mixed layouts (REDUX_MIXED_UNIT_BLOCKS)
 CONST_MARK = 0x90000000  # version 9's word at offset 12: CONST_MARK | F << 4 | E, F = 1 with a base record
 BASE_MARK = 0x80000000  # version 8's word at offset 12: BASE_MARK | E
 BASE_RECORD = struct.Struct("<QI")  # version 8, after the header: base_used, CRC-32 of base[:base_used]
@@ -133,7 +146,7 @@ def _raw_lengths(nblocks, block_size, total):
 
 
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None):
+         constant=None, unit_layouts=None):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -146,7 +159,12 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
     zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter).
     constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
-    adaptive model, no stored, no filter); None: no bitmap."""
+    adaptive model, no stored, no filter); None: no bitmap.
+    unit_layouts: the ceil(nblocks / 8) layouts, 0 .. 7, of compress_blocks(..., unit_layouts=) (version 10; adaptive model,
+    element_size 1 and none of stored, filter, base and constant); None: no unit table."""
+    mixed = unit_layouts is not None
+    if mixed:
+        api._check_mixed(params, element_size, filter, stored, base, constant)
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
     context = isinstance(params, api.ContextStaticModel)
@@ -207,6 +225,13 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
                 or bool((_raw_lengths(len(sizes), block_size, total_len)[f == 1] == 0).any()):
             raise api.InvalidInput()
         bitmap = np.packbits(f.astype(np.uint8), bitorder="little").tobytes()
+    if mixed:
+        t = np.asarray(unit_layouts)
+        if t.shape != ((len(sizes) + MIXED_UNIT_BLOCKS - 1) // MIXED_UNIT_BLOCKS,) or t.dtype.kind not in "ui" \
+                or bool((t > 7).any()) or bool((t < 0).any()):
+            raise api.InvalidInput()
+        ver, res = VERSION_MIXED | (ver & CRC_FLAG), MIXED_MARK
+        bitmap = t.astype(np.uint8).tobytes()
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if xbase:
         head += BASE_RECORD.pack(base_used, base_crc)
@@ -275,7 +300,8 @@ def _version_ok(ver, res):
         or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
         or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES)
+        or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
+        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
@@ -283,8 +309,10 @@ def _version_ok(ver, res):
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
 # of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, else None.
 # base: (base_used, crc) of the record of version 8, or of version 9 with F = 1, else None.  constant: uint8[nblocks] of 0 / 1
-# for version 9, else None.
-_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant")
+# for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
+# None, as the table holds it unit by unit.
+_Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
+                        " unit_layouts", defaults=(None,))
 
 
 def _header(b):
@@ -321,7 +349,7 @@ def _parse(buf):
     raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
     b = memoryview(buf)
     ver, P, block_size, E, nblocks, total = _header(b)
-    static = crcs = stored = base = constant = None
+    static = crcs = stored = base = constant = units = None
     at = HEADER.size
     if _layout(ver) == VERSION_BASE or (_layout(ver) == VERSION_CONST and HEADER.unpack_from(b, 0)[6] & 0x10):
         if len(b) < at + BASE_RECORD.size:
@@ -381,9 +409,15 @@ def _parse(buf):
         constant = flags[:nblocks].astype(np.uint8)
         if bool((sizes[constant == 1] != 1).any()):
             raise api.InvalidInput()
+    if _layout(ver) == VERSION_MIXED:
+        units, at = _take(b, at, np.uint8, (nblocks + MIXED_UNIT_BLOCKS - 1) // MIXED_UNIT_BLOCKS)
+        units = units.copy()
+        if bool((units > 7).any()):
+            raise api.InvalidInput()
+        E = None
     payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
     return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored,
-                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant)
+                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant, units)
 
 
 def unpack(buf):
@@ -406,14 +440,14 @@ def block_stored(buf):
 
 
 def element_size(buf):
-    """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for versions 2 and 4.  Malformed
-    containers raise InvalidInput, truncated ones Eof."""
+    """Element size of the byte-plane layout a container records: 1 for versions 1 and 3, E for versions 2 and 4, None for
+    version 10 (unit_layouts holds it unit by unit).  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).element_size
 
 
 def filter(buf):
-    """"delta" for a version 6 container (the delta filter for integer series), None for versions 1 to 5.  Malformed
-    containers raise InvalidInput, truncated ones Eof."""
+    """"delta" for a version 6 container (the delta filter for integer series), None for every other version (version 10
+    records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).filter
 
 
@@ -427,6 +461,12 @@ def constant(buf):
     """The constant-block flags (np.uint8[nblocks] of 0 / 1) a version 9 container records; None for versions 1 to 8.
     Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).constant
+
+
+def unit_layouts(buf):
+    """The unit table (np.uint8[ceil(nblocks / 8)] of layouts 0 .. 7) a version 10 container records; None for versions 1 to
+    9.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).unit_layouts
 
 
 def static_table(buf):
@@ -471,17 +511,20 @@ def header_is_wellformed(buf):
 
 
 def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False,
-                   filter=None):
+                   filter=None, mixed=False):
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
     because only the tables of contexts that occur are recorded.  filter "delta" (adaptive model, not stored): version 6,
-    which records the filter in the header's reserved word and adds no bytes."""
-    if model not in api.MODELS or nblocks < 1:
+    which records the filter in the header's reserved word and adds no bytes.  mixed (adaptive model, element size 1, no
+    filter, not stored): version 10, whose unit table adds a byte per 8 blocks."""
+    if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)):
         raise api.InvalidInput()
     api._check_filter(filter, model == "adaptive" and not stored)
     E = api._check_element_size(element_size)
     n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
+    if mixed:
+        n += (nblocks + MIXED_UNIT_BLOCKS - 1) // MIXED_UNIT_BLOCKS
     if model == "static":
         n += TABLE
     elif model == "plane-static":
@@ -512,13 +555,17 @@ def choose_model(estimates):
 LAYOUT_ORDER = api.LAYOUTS  # (1, None), (2, None), (4, None), (8, None), (1, "delta"), ... (8, "delta")
 
 
-def estimate_layout_bytes(data, block_size=65536, params=(8, 30, 32), element_size=None, checksum=False):
+def estimate_layout_bytes(data, block_size=65536, params=(8, 30, 32), element_size=None, checksum=False, mixed=False):
     """-> {(element_size, filter): estimated container bytes} for the adaptive model behind each layout: api.estimate_layouts'
     estimate of the payloads (one pass over the bytes as they are on the GPU; nothing is transformed or coded) plus
-    overhead_bytes, which is exact.  element_size None: all eight layouts; 1 / 2 / 4 / 8: plain and delta at that size."""
-    payload = api.estimate_layouts(data, block_size, params, element_size)
+    overhead_bytes, which is exact.  element_size None: all eight layouts; 1 / 2 / 4 / 8: plain and delta at that size.
+    mixed=True adds the key "mixed": the version 10 container of compress_bytes(..., layout="mixed") among those layouts."""
+    payload = api.estimate_layouts(data, block_size, params, element_size, mixed=mixed)
     nb = max(1, -(-len(data) // block_size))
-    return {(E, f): payload[(E, f)] + overhead_bytes("adaptive", nb, E, checksum=checksum, filter=f) for E, f in payload}
+    est = {k: payload[k] + overhead_bytes("adaptive", nb, k[0], checksum=checksum, filter=k[1]) for k in payload if k != "mixed"}
+    if mixed:
+        est["mixed"] = payload["mixed"] + overhead_bytes("adaptive", nb, checksum=checksum, mixed=True)
+    return est
 
 
 def choose_layout(estimates):
@@ -551,12 +598,21 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     with the smallest estimate_layout_bytes code the data (choose_layout) -- of all eight layouts when element_size is None,
     of plain and delta at that size when element_size is 1 / 2 / 4 / 8 (the default, 1, included: a caller who knows the dtype
     says so, one who does not passes None) -- and the container is that layout's: version 1, 2 or 6, nothing new to
-    decode."""
+    decode.
+    layout "mixed" (the exclusions of "auto"): a layout per unit of 8 blocks, chosen on the device by its estimated cost --
+    among all eight when element_size is None, between plain and delta at that size when element_size is 1 / 2 / 4 / 8 --
+    version 10.  For files that hold several element types."""
     if layout is not None:
-        if layout != "auto" or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
+        if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
                 or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
                 or (element_size is not None and element_size != 1 and element_size not in ELEMENT_SIZES):
             raise api.InvalidInput()
+        if layout == "mixed":
+            want = [k for k in api.LAYOUTS if element_size is None or k[0] == element_size]
+            nb = max(1, -(-len(data) // block_size))
+            crc = np.zeros(nb, dtype=np.uint32) if checksum else None
+            out, offs, _, table = api.compress_blocks(data, block_size, params, block_crc=crc, unit_layouts=True, layouts=want)
+            return pack(out, offs, params, block_size, len(data), block_crc=crc, unit_layouts=table)
         element_size, filter = choose_layout(estimate_layout_bytes(data, block_size, params, element_size, checksum))
     api._check_constant(skip_constant or None, model == "adaptive" and not stored and filter is None)
     api._check_base(base, model == "adaptive" and not stored and filter is None)
@@ -611,11 +667,15 @@ def decompress_bytes(buf, base=None):
         raise api.InvalidInput()
     got = None if c.crcs is None else np.zeros(nb, dtype=np.uint32)
     segment = isinstance(c.static, api.SegmentStaticModel)
-    exact = c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None \
+    mixed = c.unit_layouts is not None
+    exact = mixed or c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None \
         or c.constant is not None
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
-        if exact:  # (the blocks decode at their real size, into out[0 .. total))
+        if mixed:
+            out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size, c.params, length=c.total, block_crc=got,
+                                                       unit_layouts=c.unit_layouts)
+        elif exact:  # (the blocks decode at their real size, into out[0 .. total))
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,

@@ -22,6 +22,7 @@
 //   redux_const.hpp    k_const_select / k_const_table / k_const_fill: constant blocks, one byte for a block of equal bytes
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 //   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
+//   redux_mixed.hpp    k_mixed_choose / k_mixed_planes: a layout per unit of 8 blocks, chosen from those costs on the device
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -51,6 +52,7 @@
 #include "redux_const.hpp"
 #include "redux_cost.hpp"
 #include "redux_layout_cost.hpp"
+#include "redux_mixed.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -856,6 +858,87 @@ static int launch_layout_cost(const void *d_in, uint64_t in_len, uint32_t block_
     }
     return REDUX_OK;
 }
+
+// ---- mixed layouts (redux_mixed.hpp) ----------------------------------------------------------------------------------
+// units the fast kernel takes: all full ones when block size and both buffers are 16-byte multiples, none otherwise
+static uint64_t mixed_full_units(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size)
+{
+    return block_size % 16 == 0 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0 ? len / ((uint64_t)kMixedUnit * block_size) : 0;
+}
+
+// the transform of d_src[0 .. len) under the device table: W workgroups per full unit (what E = 8 needs: the others loop),
+// the byte kernel for the rest -- forward a thread per byte, inverse a workgroup per unit, at most 2^20
+static int launch_mixed(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, const void *d_table, bool inverse,
+                        hipStream_t s)
+{
+    MixedArgs a;
+    a.src          = (const uint8_t *)d_src;
+    a.dst          = (uint8_t *)d_dst;
+    a.table        = (const uint8_t *)d_table;
+    a.block_size   = block_size;
+    a.frame_groups = block_size / 16;
+    a.nfull        = mixed_full_units(d_src, d_dst, len, block_size);
+    a.wgs          = (a.frame_groups + 255) / 256;
+    a.len          = len;
+    a.first        = a.nfull * kMixedUnit * block_size;
+    if (a.nfull) {
+        const uint64_t wgs = a.nfull * a.wgs;
+        if (wgs > 0x7FFFFFFFull)
+            return REDUX_UNSUPPORTED;
+        if (inverse)
+            k_mixed_planes<true><<<(uint32_t)wgs, 256, 0, s>>>(a);
+        else
+            k_mixed_planes<false><<<(uint32_t)wgs, 256, 0, s>>>(a);
+    }
+    if (a.first < len) { // the short last unit, or everything the fast kernel cannot take
+        const uint64_t n = len - a.first, unit = (uint64_t)kMixedUnit * block_size;
+        if (inverse) {
+            const uint64_t nunits = (n + unit - 1) / unit;
+            k_mixed_bytes<true><<<(uint32_t)(nunits < (1u << 20) ? nunits : (1u << 20)), 256, 0, s>>>(a);
+        } else {
+            const uint64_t wgs = (n + 255) / 256;
+            k_mixed_bytes<false><<<(uint32_t)(wgs < 8192 ? wgs : 8192), 256, 0, s>>>(a);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+static int mixed_layout_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, const void *d_table, int inverse,
+                            void *stream)
+{
+    if (block_size == 0 || block_size > (1u << 30) || !d_table || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place: the transform reads bytes another thread writes)
+        return REDUX_INVALID_INPUT;
+    return launch_mixed(d_src, d_dst, len, block_size, d_table, inverse != 0, (hipStream_t)stream);
+}
+
+static int mixed_choose_dev(const void *d_bits, uint64_t nblocks, uint32_t layouts_mask, void *d_table, void *d_sum_bits, void *stream)
+{
+    if (!d_bits || !d_table || nblocks == 0 || layouts_mask == 0 || layouts_mask > 0xFF)
+        return REDUX_INVALID_INPUT;
+    hipStream_t s = (hipStream_t)stream;
+    MixedChooseArgs a;
+    a.bits    = (const double *)d_bits;
+    a.nblocks = nblocks;
+    a.nunits  = (nblocks + kMixedUnit - 1) / kMixedUnit;
+    a.mask    = layouts_mask;
+    a.table   = (uint8_t *)d_table;
+    a.sum     = (unsigned long long *)d_sum_bits;
+    if (d_sum_bits)
+        HIP_TRY(hipMemsetAsync(d_sum_bits, 0, 8, s));
+    const uint64_t wgs = (a.nunits + 255) / 256;
+    k_mixed_choose<<<(uint32_t)(wgs < 4096 ? wgs : 4096), 256, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// bytes of the cost rows in the workspace of redux_encode_mixed_dev: f64[8][nblocks], a 256-byte multiple
+static uint64_t mixed_cost_bytes(uint64_t nblocks) { return (nblocks * 64 + 255) / 256 * 256; }
 
 
 extern "C" {
@@ -1679,7 +1762,8 @@ static host::DecodeCoder static_decoder(const redux_params *p, const uint32_t *c
 static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size,
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
                               uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr,
-                              const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {}, host::BaseIo base = {})
+                              const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {}, host::BaseIo base = {},
+                              host::UnitTableIo units = {})
 {
     if (params != REDUX_OK)
         return params;
@@ -1692,7 +1776,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
     return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
-                               block_crc, stored, tables, base); // redux_host.hpp
+                               block_crc, stored, tables, base, units); // redux_host.hpp
 }
 
 int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
@@ -4096,6 +4180,170 @@ int redux_table_cost_dev(const void *d_counts, const void *d_cum, uint64_t n, vo
                                                                                    (const uint32_t *)d_cum, n, (double *)d_bits);
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
+}
+
+// ---- mixed layouts (redux_mixed.hpp) ----------------------------------------------------------------
+uint64_t redux_mixed_unit_count(uint64_t in_len, uint32_t block_size)
+{
+    return (redux_block_count(in_len, block_size) + kMixedUnit - 1) / kMixedUnit;
+}
+
+int redux_mixed_choose_dev(const void *d_bits, uint64_t nblocks, uint32_t layouts_mask, void *d_table, void *d_sum_bits, void *stream)
+{
+    return mixed_choose_dev(d_bits, nblocks, layouts_mask, d_table, d_sum_bits, stream);
+}
+
+int redux_mixed_layout_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, const void *d_table, int inverse,
+                           void *stream)
+{
+    return mixed_layout_dev(d_src, d_dst, len, block_size, d_table, inverse, stream);
+}
+
+// the transformed copy, the cost rows, the coder's workspace
+uint64_t redux_encode_mixed_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size)
+{
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    return ws ? planes_copy_bytes(in_len) + mixed_cost_bytes(redux_block_count(in_len, block_size)) + ws : 0;
+}
+
+uint64_t redux_decode_mixed_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size)
+{
+    return redux_decode_planes_workspace_bytes(p, out_len, block_size, 1);
+}
+
+// ws_cost: the chunks of a multi-chunk host call run the coder on a workspace without the pairs area (adaptive_encoder)
+static int encode_mixed_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layouts_mask,
+                            void *d_table, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || layouts_mask > 0xFF || !d_table || !d_workspace || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    const uint64_t nblocks = redux_block_count(in_len, block_size);
+    const uint64_t copy = planes_copy_bytes(in_len), cost = mixed_cost_bytes(nblocks);
+    if (workspace_bytes < copy + cost)
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *x = (uint8_t *)d_workspace, *bits = x + copy;
+    if (layouts_mask) {
+        if ((st = redux_layout_cost_dev(p, d_in, in_len, block_size, layouts_mask, bits, stream)) != REDUX_OK)
+            return st;
+        if ((st = mixed_choose_dev(bits, nblocks, layouts_mask, d_table, nullptr, stream)) != REDUX_OK)
+            return st;
+    }
+    if ((st = mixed_layout_dev(d_in, x, in_len, block_size, d_table, 0, stream)) != REDUX_OK)
+        return st;
+    return redux_encode_blocks_dev(p, x, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status, d_summary, bits + cost,
+                                   workspace_bytes - copy - cost, stream);
+}
+
+int redux_encode_mixed_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layouts_mask,
+                           void *d_table, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                           void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_mixed_dev(p, d_in, in_len, block_size, layouts_mask, d_table, d_out, out_cap, d_out_offsets, d_block_status,
+                            d_summary, d_workspace, workspace_bytes, stream);
+}
+
+// the blocks decode into the plane buffer at the front of the workspace, then layout_decode_tail's sizes check and summary with
+// the mixed inverse in place of a single layout's (d_t null: the tail runs no inverse of its own)
+int redux_decode_mixed_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_table, uint64_t out_len,
+                           uint32_t block_size, void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary,
+                           void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (block_size == 0 || block_size > (1u << 30) || !d_table || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status ||
+        (out_len && !d_out))
+        return REDUX_INVALID_INPUT;
+    const uint64_t nblocks = redux_block_count(out_len, block_size);
+    const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
+    if (workspace_bytes < redux_decode_mixed_workspace_bytes(p, out_len, block_size))
+        return REDUX_OUTPUT_TOO_SMALL;
+    uint8_t *t = (uint8_t *)d_workspace;
+    st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
+                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr, BlockTable{});
+    if (st != REDUX_OK)
+        return st;
+    st = layout_decode_tail(Layout{1, false}, nullptr, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+                            TailSummary::InSizes, stream);
+    if (st != REDUX_OK)
+        return st;
+    return mixed_layout_dev(t, d_out, out_len, block_size, d_table, 1, stream);
+}
+
+// The host-pointer pair: a chunk is whole 64-block waves, hence whole units, so chunk [b0, b0 + nb) owns table bytes b0 / 8 ..;
+// they travel through the slot's d_stf / h_stf (host::UnitTableIo).
+static int mixed_table_check(const uint8_t *table, uint64_t nunits)
+{
+    for (uint64_t u = 0; u < nunits; u++)
+        if (table[u] > 7)
+            return REDUX_INVALID_INPUT;
+    return REDUX_OK;
+}
+
+int redux_encode_blocks_mixed(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t layouts_mask,
+                              uint8_t *table, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                              uint32_t *block_crc)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || layouts_mask > 0xFF || !table || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    if (!layouts_mask && (st = mixed_table_check(table, redux_mixed_unit_count(in_len, block_size))) != REDUX_OK)
+        return st;
+    const host::EncodeCoder plain = adaptive_encoder(p, block_size);
+    const host::EncodeCoder coder = {
+        [=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
+            plain.size(max_in, several, ws, bound);
+            ws += planes_copy_bytes(max_in) + mixed_cost_bytes(redux_block_count(max_in, block_size));
+        },
+        [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t stream) {
+            return encode_mixed_dev(p, s.d_in.p, len, block_size, layouts_mask, s.d_stf.p, s.d_out.p, bound, s.d_off.p, s.d_st.p,
+                                    s.d_sum.p, ws, ws_bytes, stream);
+        }};
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, nullptr, {}, {},
+                               host::UnitTableIo{table, layouts_mask == 0});
+}
+
+int redux_decode_blocks_mixed(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *table,
+                              uint64_t out_len, uint32_t block_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                              uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && (block_size == 0 || block_size > (1u << 30) || !table))
+        st = REDUX_INVALID_INPUT;
+    if (st == REDUX_OK)
+        st = mixed_table_check(table, redux_mixed_unit_count(out_len, block_size));
+    const host::DecodeCoder coder = {
+        [=](uint64_t cb) { return redux_decode_mixed_workspace_bytes(p, cb * (uint64_t)block_size, block_size); },
+        [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t stream) {
+            return redux_decode_mixed_dev(p, s.d_in.p, s.d_off.p, s.d_stf.p, out_bytes, block_size, s.d_out.p, s.d_sz.p, s.d_st.p,
+                                          s.d_sum.p, ws, ws_bytes, stream);
+        },
+        true};
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, coder, block_crc, nullptr, {}, {}, host::UnitTableIo{(uint8_t *)table, true});
+}
+
+const char *redux_mixed_kernel_name_at(const void *d_src, const void *d_dst, uint64_t in_len, uint32_t block_size, int inverse)
+{
+    static const char *const names[2][3] = {
+        {"k_mixed_planes<0>", "k_mixed_planes<0> + k_mixed_bytes<0>", "k_mixed_bytes<0>"},
+        {"k_mixed_planes<1>", "k_mixed_planes<1> + k_mixed_bytes<1>", "k_mixed_bytes<1>"},
+    };
+    if (block_size == 0 || block_size > (1u << 30) || in_len == 0)
+        return "";
+    const uint64_t nfull = mixed_full_units(d_src, d_dst, in_len, block_size);
+    return names[inverse != 0][nfull == 0 ? 2 : nfull * kMixedUnit * block_size < in_len ? 1 : 0];
+}
+
+const char *redux_mixed_kernel_name(uint64_t in_len, uint32_t block_size, int inverse)
+{
+    return redux_mixed_kernel_name_at(nullptr, nullptr, in_len, block_size, inverse);
 }
 
 } // extern "C"

@@ -722,6 +722,23 @@ struct BaseIo {
     }
 };
 
+// Mixed layouts (include/redux_hip.h): the call's unit table, u8 per unit of 8 blocks in caller memory, travels per chunk
+// through the slot's d_stf / h_stf as the stored flags do (the two never meet in one call).  Chunks are whole 64-block waves,
+// so chunk [b0, b0 + nb) owns table bytes b0 / 8 .. : encode fetches them with the chunk's small arrays when its coder chose
+// them (given false) and stages them in front of its coder when the caller dictates them (given true); decode stages them.
+struct UnitTableIo {
+    uint8_t *table = nullptr; // null: the call has no unit table
+    bool     given = false;
+    static uint64_t bytes(uint64_t nb) { return (nb + 7) / 8; }
+    uint8_t *at(uint64_t b0) const { return table + b0 / 8; }
+    int stage(Slot &s, hipStream_t st, uint64_t b0, uint64_t nb) const
+    {
+        memcpy(s.h_stf.p, at(b0), bytes(nb));
+        HOST_TRY(hipMemcpyAsync(s.d_stf.p, s.h_stf.p, bytes(nb), hipMemcpyHostToDevice, st));
+        return REDUX_OK;
+    }
+};
+
 // ================================================================================================
 // encode: chunk k = blocks [k * cb, k * cb + nb) of the input -> its streams at their place in the dense output
 // ================================================================================================
@@ -738,6 +755,7 @@ struct EncodeChunks {
     uint8_t           *stored;    // may be null: the stored-block flags the coder leaves in s.d_stf (redux_store.hpp)
     SegmentTablesIo    tables;    // cum may be null: the segment tables the coder leaves in s.d_tab
     BaseIo             base;      // on: the chunk's share of the base, staged to s.d_base next to its input
+    UnitTableIo        units;     // table may be null: the unit table of the mixed layouts, in s.d_stf
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -758,7 +776,7 @@ struct EncodeChunks {
     {
         const int rc = grow_bufs(c, {{&s.d_in, max_in + 16}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, bound + 16}, {&s.d_off, (cb + 1) * 8},
                                      {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.h_off, (cb + 1) * 8}, {&s.h_st, cb * 4}, {&s.h_sum, 8}});
-        if (rc == REDUX_OK && stored) {
+        if (rc == REDUX_OK && (stored || units.table)) {
             const int r2 = grow_bufs(c, {{&s.d_stf, cb}, {&s.h_stf, cb}});
             if (r2 != REDUX_OK)
                 return r2;
@@ -777,6 +795,11 @@ struct EncodeChunks {
     }
     int stage(Ctx &c, Slot &s, hipStream_t st, uint64_t b0, uint64_t nb, CopyPool &pool, uint64_t &piece_no) const
     {
+        if (units.table && units.given) {
+            const int r2 = units.stage(s, st, b0, nb);
+            if (r2 != REDUX_OK)
+                return r2;
+        }
         const int rc = stage_h2d(c, pool, piece_no, s.d_in.p, in + b0 * (uint64_t)block_size, len_of(b0, nb), st);
         return rc != REDUX_OK || !base.on ? rc : base.stage(c, s, st, b0 * (uint64_t)block_size, len_of(b0, nb), pool, piece_no);
     }
@@ -794,6 +817,7 @@ struct EncodeChunks {
         return fetch_small(s.h_off, s.d_off, (nb + 1) * 8, st) && fetch_small(s.h_st, s.d_st, nb * 4, st) &&
                fetch_small(s.h_sum, s.d_sum, 8, st) && (!block_crc || fetch_small(s.h_crc, s.d_crc, nb * 4, st)) &&
                (!stored || fetch_small(s.h_stf, s.d_stf, nb, st)) &&
+               (!units.table || units.given || fetch_small(s.h_stf, s.d_stf, units.bytes(nb), st)) &&
                (!tables.cum || fetch_small(s.h_tab, s.d_tab, tables.bytes(nb), st));
     }
     Placed place(Ctx &c, Slot &s, uint64_t k, uint64_t b0, uint64_t nb, Ledger &L) const
@@ -817,6 +841,8 @@ struct EncodeChunks {
             memcpy(block_crc + b0, s.h_crc.p, nb * 4);
         if (stored)
             memcpy(stored + b0, s.h_stf.p, nb);
+        if (units.table && !units.given)
+            memcpy(units.at(b0), s.h_stf.p, units.bytes(nb));
         if (tables.cum)
             memcpy(tables.at(b0), s.h_tab.p, tables.bytes(nb));
         return {};
@@ -825,9 +851,9 @@ struct EncodeChunks {
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr,
-                         uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {})
+                         uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {}, UnitTableIo units = {})
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables, base};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables, base, units};
     return run_chunks(op);
 }
 
@@ -849,6 +875,7 @@ struct DecodeChunks {
     const uint8_t     *stored;    // may be null: stored-block flags, staged to s.d_stf with the chunk's offsets (redux_store.hpp)
     SegmentTablesIo    tables;    // cum may be null: the segment tables, staged to s.d_tab with the chunk's offsets
     BaseIo             base;      // on: the share of the base that lies next to the chunk's output, staged to s.d_base
+    UnitTableIo        units;     // table may be null: the unit table of the mixed layouts, staged to s.d_stf
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
@@ -876,7 +903,7 @@ struct DecodeChunks {
         const int      rc   = grow_bufs(c, {{&s.d_in, max_in + 32}, {&s.d_ws, ws_bytes + 256}, {&s.d_out, cb * (uint64_t)block_size + 16},
                                             {&s.d_off, (cb + 1) * 8}, {&s.d_sz, cb * 4}, {&s.d_st, cb * 4}, {&s.d_sum, 8}, {&s.d_used, used},
                                             {&s.h_off, (cb + 1) * 8}, {&s.h_sz, cb * 4}, {&s.h_st, cb * 4}, {&s.h_sum, 8}, {&s.h_used, used}});
-        if (rc == REDUX_OK && stored) {
+        if (rc == REDUX_OK && (stored || units.table)) {
             const int r2 = grow_bufs(c, {{&s.d_stf, cb}, {&s.h_stf, cb}});
             if (r2 != REDUX_OK)
                 return r2;
@@ -912,6 +939,11 @@ struct DecodeChunks {
         if (tables.cum) {
             memcpy(s.h_tab.p, tables.at(b0), tables.bytes(nb));
             HOST_TRY(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, tables.bytes(nb), hipMemcpyHostToDevice, st));
+        }
+        if (units.table) {
+            const int r2 = units.stage(s, st, b0, nb);
+            if (r2 != REDUX_OK)
+                return r2;
         }
         const int rc = stage_h2d(c, pool, piece_no, s.d_in.p, in + i0, in_offsets[b0 + nb] - i0, st);
         return rc != REDUX_OK || !base.on ? rc : base.stage(c, s, st, b0 * (uint64_t)block_size, chunk_out(b0, nb), pool, piece_no);
@@ -949,10 +981,11 @@ struct DecodeChunks {
 
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                          uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
-                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {})
+                         uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {},
+                         UnitTableIo units = {})
 {
     DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored, tables,
-                    base};
+                    base, units};
     return run_chunks(op);
 }
 

@@ -243,6 +243,55 @@ inline std::vector<std::uint8_t> decompress_blocks_delta(const Blocks &streams, 
     return out;
 }
 
+// Files of several element types behind the mixed layouts (include/redux_hip.h, "mixed layouts"): every unit of 8 blocks is
+// coded behind the layout -- element size 1, 2, 4 or 8, with or without the delta filter -- that costs it least, chosen on the
+// device among the layouts of layouts_mask (bit k = layout 4 F + log2 E; 0xFF: all eight).  The unit table comes back next
+// to the streams, and the decoder needs it.
+struct MixedBlocks {
+    Blocks                    blocks;
+    std::vector<std::uint8_t> unit_layouts; // u8[redux_mixed_unit_count(len, block_size)], 0 .. 7
+};
+
+inline MixedBlocks compress_blocks_mixed(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size,
+                                         const model::Parameters &p, std::uint32_t layouts_mask = 0xFF)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || layouts_mask == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    MixedBlocks m;
+    Blocks &b = m.blocks;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    m.unit_layouts.resize(redux_mixed_unit_count(len, block_size));
+    check(redux_encode_blocks_mixed(&cp, in, len, block_size, layouts_mask, m.unit_layouts.data(), b.data.data(), b.data.size(),
+                                    b.offsets.data(), nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return m;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_mixed(const MixedBlocks &m, std::uint64_t len, std::uint32_t block_size,
+                                                         const model::Parameters &p)
+{
+    const Blocks &streams = m.blocks;
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        streams.offsets.back() > streams.data.size() || m.unit_layouts.size() != redux_mixed_unit_count(len, block_size))
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_mixed(&cp, streams.data.data(), streams.offsets.data(), m.unit_layouts.data(), len, block_size,
+                                    out.data(), sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
 // A snapshot behind the XOR-against-base filter (include/redux_hip.h, "XOR-against-base filter"): base is an earlier
 // snapshot of the same data, of any length; the bytewise XOR against it is coded in the byte-plane layout of element_size
 // 1, 2, 4 or 8.  Opt-in, and the decoder needs the same base.

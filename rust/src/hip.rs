@@ -168,6 +168,43 @@ extern "C" {
     fn redux_context_static_encode_kernel_name(p: *const ReduxParams, total: u32, in_len: u64, block_size: u32) -> *const c_char;
     #[allow(dead_code)]
     fn redux_context_static_decode_kernel_name(p: *const ReduxParams, total: u32, nblocks: u64) -> *const c_char;
+    // mixed layouts: a layout per unit of 8 blocks (table: u8[redux_mixed_unit_count]); declared for callers that keep
+    // their data on the device or write their own container, no wrapper here
+    #[allow(dead_code)]
+    fn redux_mixed_unit_count(in_len: u64, block_size: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_mixed_choose_dev(d_bits: *const c_void, nblocks: u64, layouts_mask: u32, d_table: *mut c_void,
+                              d_sum_bits: *mut c_void, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_mixed_layout_dev(d_src: *const c_void, d_dst: *mut c_void, len: u64, block_size: u32, d_table: *const c_void,
+                              inverse: c_int, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_encode_mixed_workspace_bytes(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_decode_mixed_workspace_bytes(p: *const ReduxParams, out_len: u64, block_size: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_encode_mixed_dev(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32, layouts_mask: u32,
+                              d_table: *mut c_void, d_out: *mut c_void, out_cap: u64, d_out_offsets: *mut c_void,
+                              d_block_status: *mut c_void, d_summary: *mut c_void, d_workspace: *mut c_void,
+                              workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_decode_mixed_dev(p: *const ReduxParams, d_in: *const c_void, d_in_offsets: *const c_void, d_table: *const c_void,
+                              out_len: u64, block_size: u32, d_out: *mut c_void, d_out_sizes: *mut c_void,
+                              d_block_status: *mut c_void, d_summary: *mut c_void, d_workspace: *mut c_void,
+                              workspace_bytes: u64, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_encode_blocks_mixed(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, layouts_mask: u32,
+                                 table: *mut u8, out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32,
+                                 block_crc: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn redux_decode_blocks_mixed(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, table: *const u8,
+                                 out_len: u64, block_size: u32, out: *mut u8, out_sizes: *mut u32, block_status: *mut i32,
+                                 block_crc: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn redux_mixed_kernel_name(in_len: u64, block_size: u32, inverse: c_int) -> *const c_char;
+    #[allow(dead_code)]
+    fn redux_mixed_kernel_name_at(d_src: *const c_void, d_dst: *const c_void, in_len: u64, block_size: u32,
+                                  inverse: c_int) -> *const c_char;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
