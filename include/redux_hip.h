@@ -1031,6 +1031,13 @@ int redux_debug_rcp_check(uint64_t lo, uint64_t hi, double *max_err);
 int redux_debug_role_book(const redux_params *p, uint64_t in_len, uint32_t block_size, uint64_t *offset,
                           uint64_t *bytes);
 
+/* Diagnostic, used by the tests only: the tile height of the encoder's row gather (k_compact_rows, which places the streams
+ * a pair or small-grid kernel left in row-major group areas).  The launch code takes tiles of 256 rows where a slot is at least
+ * four of them long (4 KiB) and tiles of 64 rows below; rows = 64 or 256 makes every later call of this process use that
+ * instance whatever the slot size, rows = 0 gives the choice back.  The dense output does not depend on it.  INVALID_INPUT
+ * for any other value. */
+int redux_debug_compact_tile_rows(uint32_t rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SIGNATURES = {
     "redux_static_decode_kernel_name": (C.c_char_p, [_PP, C.POINTER(_U32), _U64]),
     "redux_debug_rcp_check": (C.c_int, [_U64, _U64, C.POINTER(C.c_double)]),
     "redux_debug_role_book": (C.c_int, [_PP, _U64, _U32, C.POINTER(_U64), C.POINTER(_U64)]),
+    "redux_debug_compact_tile_rows": (C.c_int, [_U32]),
     "redux_params_check": (C.c_int, [_U32, _U32, _U32]),
     "redux_device_supports": (C.c_int, [_PP]),
     "redux_block_count": (_U64, [_U64, _U32]),

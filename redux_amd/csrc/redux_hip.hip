@@ -1346,6 +1346,27 @@ int redux_encode_slots_dev(const redux_params *p, const void *d_in, uint64_t in_
     return encode_slots_impl(g, p, d_in, in_len, block_size, BlockTable{}, d_block_status, d_workspace, workspace_bytes, stream, nullptr);
 }
 
+// The tile height k_compact_rows runs at (redux_pack.hpp): the tall tile where a group area is at least four of them tall,
+// the 64-row tile below that, so that small launches keep their workgroups.  redux_debug_compact_tile_rows dictates it.
+static std::atomic<uint32_t> g_compact_tile_rows{0};
+static uint32_t compact_tile_rows(uint32_t cap_rows)
+{
+    const uint32_t forced = g_compact_tile_rows.load(std::memory_order_relaxed);
+    if (forced)
+        return forced;
+    return cap_rows >= 4 * kTallTileRows ? kTallTileRows : kTileRows;
+}
+
+// Diagnostic (tests only): every later row gather of this process runs k_compact_rows at this tile height (64 or 256);
+// 0 gives the choice back to the launch code.
+int redux_debug_compact_tile_rows(uint32_t rows)
+{
+    if (rows != 0 && rows != kTileRows && rows != kTallTileRows)
+        return REDUX_INVALID_INPUT;
+    g_compact_tile_rows.store(rows, std::memory_order_relaxed);
+    return REDUX_OK;
+}
+
 // The compaction stage: scan + gather of the slots a coder kernel left in the workspace laid out by g.  t: the (checked) table
 // the coder ran on; raw: the stored blocks' bytes.
 static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status,
@@ -1387,9 +1408,12 @@ static int compact_with(const Geometry &g, void *d_out, uint64_t out_cap, void *
     ca.block_size = raw.block_size;
     k_compact<<<(uint32_t)g.nblocks, 256, 0, s>>>(ca);
     if (!g.any && !g.gen && (g.u16 || g.coop)) { // (every launch that may have left row-major group areas: the kernel reads the mode word)
-        const uint32_t tiles = (ca.cap_rows + kTileRows - 1) / kTileRows + 1;
-        const uint32_t groups = (uint32_t)((g.nblocks + 63) / 64);
-        k_compact_rows<<<(groups + 7) / 8 * 8 * tiles, 256, 0, s>>>(ca); // (whole sets of 8 groups: k_compact_rows' XCD-aware mapping)
+        const uint32_t rows   = compact_tile_rows(ca.cap_rows);
+        const uint32_t sets   = (uint32_t)((g.nblocks + 63) / 64 + 7) / 8 * 8; // (whole sets of 8 groups: k_compact_rows' XCD-aware mapping)
+        if (rows == kTallTileRows)
+            k_compact_rows<kTallTileRows><<<sets * compact_tiles(ca.cap_rows, kTallTileRows), 256, 0, s>>>(ca);
+        else
+            k_compact_rows<kTileRows><<<sets * compact_tiles(ca.cap_rows, kTileRows), 256, 0, s>>>(ca);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;

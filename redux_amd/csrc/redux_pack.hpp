@@ -331,48 +331,69 @@ __global__ void __launch_bounds__(256) k_compact(CompactArgs a)
 }
 
 // Row-major group areas: row r of group g holds dword r of its 64 streams
-// (slots + g * 64 * slot_bytes + 256 r + 4 l).  One workgroup gathers a tile of 64 rows: the
+// (slots + g * 64 * slot_bytes + 256 r + 4 l).  One workgroup gathers a tile of 64 rows (or 256): the
 // rows are read whole (coalesced) into LDS, then every stream's 64 dwords of the tile leave as
-// one 256-byte run of ALIGNED dwords of the dense output: output dword j of a stream that starts
+// one 256-byte run (four of them, end to end) of ALIGNED dwords of the dense output: output dword j of a stream that starts
 // at byte offset sh (0..3) inside its first aligned dword is the byte-funnel of source dwords
 // j-1 and j.  Only a stream's first and last output dword can be partial: those go bytewise.
-constexpr uint32_t kTileRows = 64;
+//
+//
+// The tile height is the template parameter, the workgroup is 256 threads whatever it is.  A tile of kTallTileRows = 256 rows
+// (67 KiB of LDS: two workgroups per CU, 16 loads in flight per thread) leaves every stream a 1 KiB run: a quarter of the
+// partial cache lines between neighbouring workgroups and a quarter of the prologues and barriers per byte, for a quarter of
+// the workgroups.  The host takes it where a group area is at least four such tiles tall (compact_tile_rows, redux_hip.hip)
+// and the 64-row tile below that.  Measured at 65,536 x 64 KiB (profiles/compact_rows.txt): 128 rows and 256 rows on 512
+// or 1024 threads are all slower than 256 rows on 256 threads, and 64 rows slowest.
+constexpr uint32_t kTileRows = 64, kTallTileRows = 256;
+constexpr uint32_t compact_tiles(uint32_t cap_rows, uint32_t rows) { return (cap_rows + rows - 1) / rows + 1; }
+template <uint32_t kRows>
 __global__ void __launch_bounds__(256) k_compact_rows(CompactArgs a)
 {
+    constexpr uint32_t kThreads = 256;
+    constexpr uint32_t kLoads   = kRows * 16 / kThreads; // uint4 loads per thread
+    constexpr uint32_t kStreams = 16;                    // streams a wave stores
+    constexpr uint32_t kChunks  = kRows / 64;            // runs of 16 quads (64 rows) per stream
+    static_assert(kRows % 64 == 0 && kLoads * kThreads == kRows * 16);
     const uint32_t mode = *a.mode;
     if ((mode & 1u) == 0)
         return;
     const uint32_t sel = (mode & 2u) ? 0x00010203u : 0x03020100u; // v_perm selector that restores stream order (kSwapped)
-    __shared__ uint32_t tile[(kTileRows + 1) * 65]; // +1 leading row (source dword j-1); pitch 65: conflict-free column reads
-    __shared__ uint64_t s_dst[64];                  // aligned dword that holds each stream's first byte (0: skip the stream)
+    __shared__ uint32_t tile[(kRows + 1) * 65]; // +1 leading row (source dword j-1); pitch 65: conflict-free column reads
+    __shared__ uint64_t s_dst[64];              // aligned dword that holds each stream's first byte (0: skip the stream)
     __shared__ uint32_t s_n[64], s_sh[64];
     __shared__ uint32_t s_maxj;
-    const uint32_t tiles = (a.cap_rows + kTileRows - 1) / kTileRows + 1;
+    const uint32_t tiles = compact_tiles(a.cap_rows, kRows);
     // XCD-aware mapping: workgroups are dealt to the 8 XCDs round-robin by blockIdx, and each XCD has its own L2.  A
-    // stream's consecutive 256-byte runs come from consecutive tiles of its group and share cache lines at their
+    // stream's consecutive runs come from consecutive tiles of its group and share cache lines at their
     // ends: all tiles of a group go to ONE XCD (blockIdx = 8 * (8-group block * tiles + tile) + group's slot), so the
     // partial lines merge in that L2 instead of leaving two L2s as two partial writes.
     const uint32_t y   = blockIdx.x >> 3;
     const uint64_t g   = (uint64_t)(y / tiles) * 8 + (blockIdx.x & 7u);
-    const uint32_t r0  = (y % tiles) * kTileRows;
+    const uint32_t r0  = (y % tiles) * kRows;
     if (g * 64 >= a.nblocks)
         return;
     const uint32_t tid   = threadIdx.x;
-    if (tid == 0)
-        s_maxj = 0;
-    __syncthreads();
-    if (tid < 64) { // where does each stream go, and how many output dwords does the longest one need?
+    // The tall tile forms the longest stream's dword count inside wave 0 and issues its tile loads without branches (below).
+    // The 64-row tile keeps its LDS atomicMax and its guarded loads: with both changes it measured 3 % and 11 % slower (its
+    // 16 KiB tiles already keep the CU's memory queues full; profiles/compact_rows.txt).
+    constexpr bool kTall = kRows > kTileRows;
+    if constexpr (!kTall) {
+        if (tid == 0)
+            s_maxj = 0;
+        __syncthreads();
+    }
+    if (tid < 64) { // wave 0: where does each stream go, and how many output dwords does the longest one need?
         const uint64_t b = g * 64 + tid;
         uint64_t       d = 0;
-        uint32_t       n = 0, sh = 0;
+        uint32_t       n = 0, sh = 0, need = 0;
         const uint64_t lb = b < a.nblocks ? (a.table ? a.table[b].index : b) : kIdleEntry;
         if (lb != kIdleEntry && !(a.stored && a.stored[lb])) { // (stored blocks: k_compact)
             const uint64_t o0 = a.offsets[lb], o1 = a.offsets[lb + 1];
             if (o1 <= a.out_cap) {
-                n  = (uint32_t)(o1 - o0);
-                sh = (uint32_t)((uintptr_t)(a.out + o0) & 3);
-                d  = (uint64_t)(uintptr_t)(a.out + o0) - sh;
-                atomicMax(&s_maxj, (sh + n + 3) >> 2);
+                n    = (uint32_t)(o1 - o0);
+                sh   = (uint32_t)((uintptr_t)(a.out + o0) & 3);
+                d    = (uint64_t)(uintptr_t)(a.out + o0) - sh;
+                need = (sh + n + 3) >> 2;
             } else if (r0 == 0) { // the dense buffer is too small for this block: report, never write
                 if (a.status[lb] == REDUX_OK)
                     a.status[lb] = REDUX_OUTPUT_TOO_SMALL;
@@ -385,23 +406,46 @@ __global__ void __launch_bounds__(256) k_compact_rows(CompactArgs a)
         s_dst[tid] = d;
         s_n[tid]   = n;
         s_sh[tid]  = sh;
+        if constexpr (!kTall) {
+            if (d)
+                atomicMax(&s_maxj, need);
+        } else {
+            // the whole wave is here and holds all 64 values: the maximum of each row of 16 lanes by four DPP moves (quad_perm
+            // [1,0,3,2] and [2,3,0,1], row_half_mirror, row_mirror), then of the four rows through SGPRs.  No LDS round trip,
+            // no second barrier: a tile behind the longest stream returns after one.
+            uint32_t m = need;
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, false));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, false));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, false));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, false));
+            m = max(max((uint32_t)__builtin_amdgcn_readlane((int)m, 0), (uint32_t)__builtin_amdgcn_readlane((int)m, 16)),
+                    max((uint32_t)__builtin_amdgcn_readlane((int)m, 32), (uint32_t)__builtin_amdgcn_readlane((int)m, 48)));
+            if (tid == 0)
+                s_maxj = m;
+        }
     }
     __syncthreads();
-    if (r0 >= s_maxj)
+    if (r0 >= s_maxj) // a tile behind the longest stream
         return;
     const uint4 *area = reinterpret_cast<const uint4 *>(a.slots + g * (64 * a.slot_bytes + 128));
-    // tile row i (0..64) = source row r0 - 1 + i; a row is 16 uint4.  All loads first, then the LDS writes.
-    uint4 v[4], lead = make_uint4(0, 0, 0, 0);
+    // tile row i (0..kRows) = source row r0 - 1 + i; a row is 16 uint4.  All loads first, then the LDS writes.
+    uint4 v[kLoads], lead = make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t e = tid + 256 * q, r = r0 + (e >> 4);
-        v[q] = r < a.cap_rows ? area[(uint64_t)r * 16 + (e & 15)] : make_uint4(0, 0, 0, 0);
+    for (uint32_t q = 0; q < kLoads; q++) {
+        const uint32_t e = tid + kThreads * q, r = r0 + (e >> 4);
+        if constexpr (kTall) { // no branch around a load, so that all of them issue back to back; rows behind the area read as zero
+            v[q] = area[(uint64_t)min(r, a.cap_rows - 1) * 16 + (e & 15)];
+            if (r >= a.cap_rows)
+                v[q] = make_uint4(0, 0, 0, 0);
+        } else {
+            v[q] = r < a.cap_rows ? area[(uint64_t)r * 16 + (e & 15)] : make_uint4(0, 0, 0, 0);
+        }
     }
     if (tid < 16 && r0 > 0)
         lead = area[(uint64_t)(r0 - 1) * 16 + tid];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t e = tid + 256 * q;
+    for (uint32_t q = 0; q < kLoads; q++) {
+        const uint32_t e = tid + kThreads * q;
         uint32_t      *w = &tile[((e >> 4) + 1) * 65 + (e & 15) * 4];
         w[0] = v[q].x; w[1] = v[q].y; w[2] = v[q].z; w[3] = v[q].w;
     }
@@ -412,10 +456,11 @@ __global__ void __launch_bounds__(256) k_compact_rows(CompactArgs a)
     __syncthreads();
     // thread -> (stream, four consecutive output dwords): one 16-byte store where the whole quad is inside the stream
     const uint32_t wave = tid >> 6, t = tid & 63;
+    // (a wave stores 16 consecutive quads of each of four streams per instruction: runs of 256 bytes)
 #pragma unroll 2
-    for (uint32_t it = 0; it < 4; it++) {
-        const uint32_t l  = wave * 16 + it * 4 + (t >> 4);
-        const uint32_t jq = (t & 15) * 4; // tile-relative first output dword
+    for (uint32_t it = 0; it < kStreams / 4 * kChunks; it++) {
+        const uint32_t l  = wave * kStreams + it / kChunks * 4 + (t >> 4);
+        const uint32_t jq = it % kChunks * 64 + (t & 15) * 4; // tile-relative first output dword
         const uint64_t d  = s_dst[l];
         const uint32_t n = s_n[l], sh = s_sh[l];
         const uint32_t j0 = r0 + jq;
