@@ -2,7 +2,8 @@
 //
 //   k_fill_rc            per-step reciprocal table 1/(257+i), biased up 4 ulp
 //   k_encode<U16,FIXUP>  one wave per 64 blocks (general form: u32 trees, unaligned input, giant blocks)
-//   k_encode_pair<..>    default: a model wave and a coder wave per 64 blocks, LDS ring between them
+//   k_encode_pair<..>    default: a model wave and a coder wave per 64 blocks, LDS ring between them; the coder wave
+//                        reads the input and hands it to the model wave through the ring as well (feed_slot)
 //
 // Included by redux_hip.hip (one translation unit); the host side launches these from
 // redux_encode_slots_dev.
@@ -263,7 +264,8 @@ __global__ void __launch_bounds__(64) k_encode(EncArgs a)
 // (tree query + update) does not depend on the coder's interval state, so a group is split
 // into a MODEL wave and a CODER wave that share the group's LDS:
 //   wave 0: input bytes -> get_frequency -> (low, high) pairs into an LDS ring
-//   wave 1: ring -> interval narrowing, renormalisation, bit output
+//   wave 1: ring -> interval narrowing, renormalisation, bit output; it also fetches the input, a line per visit, and
+//           passes it to wave 0 through a slot of the ring half it has just read (feed_slot)
 // Eight waves per CU = two per SIMD, so each SIMD always has a second instruction stream to
 // issue from.  (Measured, profiles/r01_ubench: a gfx950 SIMD retires the VOP3-type ops this
 // code is made of at ~4.5 cycles per wave-instruction however many waves feed it, so the two
@@ -275,7 +277,7 @@ __global__ void __launch_bounds__(64) k_encode(EncArgs a)
 // instruction in tools/ubench "40 VALU + barrier").)  The ring holds 2 x 8 symbols x 64 lanes x 8 B = 8 KiB (40 KiB per workgroup,
 // four workgroups = the CU's 160 KiB exactly); one s_barrier per 8 symbols hands a half over.
 // Only LDS traffic must be complete at the hand-off, so the barrier waits on lgkmcnt alone:
-// the coder's stores and the model's prefetch loads stay in flight across it.
+// the coder's stores and line loads and the model's mask loads stay in flight across it.
 // ======================================================================================
 constexpr uint32_t kRingSlots = 8;                               // symbols per hand-off
 constexpr uint32_t kRingBytes = 2 * kRingSlots * 64 * 8;         // two halves of uint2[8][64]
@@ -285,15 +287,25 @@ __device__ __forceinline__ void pair_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// Input path of the model wave: every lane reads its own block one whole 128-byte line at a
+// Input path: every lane reads its own block one whole 128-byte line at a
 // time (eight 16-byte loads issued back to back), so each line crosses the L2 <-> fabric
 // boundary once: FETCH_SIZE 2.14e6 KiB per 4 GiB pass, identical to a clean streaming read,
 // against 7.4e6-9.5e6 KiB with 16 bytes per visit (the line was evicted between visits), and
 // WRITE_SIZE drops 38 % as well (less L2 pollution).  c[] is the current line, n[] the next
 // one, already in flight; the chunk index is wave-uniform (the lanes advance in lock-step),
-// so pop() is a scalar switch.  Costs 2.8 % of kernel time (profiles/r01_traffic_matrix.txt);
-// (16 bytes per visit: 2.8 % faster, 2.4-3.2 x the traffic).
-struct ChunkQueue {
+// so pop() is a scalar switch.  In the model wave of the pair kernel, where it first lived, it
+// cost 2.8 % of kernel time (profiles/r01_traffic_matrix.txt; 16 bytes per visit: 2.8 % faster,
+// 2.4-3.2 x the traffic), and every mask-table load queued behind a line load waited out that
+// HBM miss (a wave's vector loads return in order).  The pair kernel's CODER wave owns it now
+// and hands the bytes to the model wave through the ring (feed_slot below,
+// profiles/coder_feeds_input.txt); the static coders (redux_static.hpp) use it as before.
+// PIN (the pair kernel): the copy of swap() is made to happen BEFORE the next line's loads.  Left to itself the compiler
+// issues the loads first, into spare registers, copies c[] <- n[] behind them (as the loop's closing register moves) and
+// then has to move the spare registers into n[] -- behind an s_waitcnt vmcnt(0) for the loads it has just issued: the wave
+// sits out a whole HBM miss per line (profiles/coder_feeds_input.txt).  Pinned, the loads write n[] itself and nothing
+// waits for them before the next swap(), a line-time later.
+template <bool PIN>
+struct ChunkQueueT {
     const uint8_t *base; // wave-uniform
     uint32_t       soff; // this lane's block offset
     uint32_t       last; // offset of the last 16-byte chunk the unrolled path reads
@@ -314,17 +326,34 @@ struct ChunkQueue {
     // current line <- prefetched line, then put the line after it in flight
     __device__ __forceinline__ void swap()
     {
+        // The pair kernel's coder wave has predicated stores, a number nobody knows, younger than the line's loads: it
+        // waits for everything, once per line (s_waitcnt vmcnt(0), expcnt and lgkmcnt left alone), and so relies on no
+        // order between the returns of loads and of stores.  The line was asked for a line-time ago.
+        if (PIN)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
 #pragma unroll
         for (int i = 0; i < 8; i++)
             c[i] = n[i];
+        if (PIN) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                u32x4 t = {c[i].x, c[i].y, c[i].z, c[i].w};
+                asm volatile("" : "+v"(t)); // c[i] is in registers of its own from here on
+                c[i] = make_uint4(t[0], t[1], t[2], t[3]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         idx = 0;
         prefetch();
     }
-    __device__ __forceinline__ void init(const uint8_t *b, uint32_t so, uint32_t e)
+    // e: end of the unrolled path (>= 16); first: the chunk (0..7, wave-uniform) that the first pop() returns
+    __device__ __forceinline__ void init(const uint8_t *b, uint32_t so, uint32_t e, uint32_t first = 0)
     {
         base = b; soff = so; last = e - 16; nextp = 0;
         prefetch();
         swap();
+        idx = first;
     }
     // the next 16 bytes of every lane's block
     __device__ __forceinline__ uint4 pop()
@@ -345,6 +374,7 @@ struct ChunkQueue {
         return r;
     }
 };
+using ChunkQueue = ChunkQueueT<false>;
 
 // The pair kernel writes ROW-major group areas -- row r = dword r of the group's 64 lanes -- so that the lanes of a wave,
 // whose dword counts stay within one or two of each other on iid bytes, fill whole 128-byte lines within a few symbols
@@ -358,9 +388,23 @@ __device__ __forceinline__ uint32_t ring_at(uint32_t i, uint32_t lane) // index 
 {
     return (i >> 1) * 128u + lane * 2u + (i & 1u);
 }
-// (Tried: the coder wave, which has the slack, pulling every input line into the L2 a line-time before the model wave asks
-// for it: 1.3 % faster, but the lines do not stay in the L2 until they are used and FETCH_SIZE doubles.  Not kept: the read
-// side stays at 1.00 x the input.)
+// The input reaches the model wave through the ring as well.  The coder wave reads the input (ChunkQueue) and, while it
+// codes the first half of chunk c, writes the 16 input bytes of chunk c + 2 into its lane's slot of that half: the place of
+// entries 0 and 1, which it has just read and which the model wave does not write again before the barrier that closes
+// chunk c (it is filling the second half).  Right after that barrier the model wave reads the slot back -- before its first
+// ring write of chunk c + 1, the pair (0, 1), and a wave's LDS operations complete in order -- as the `nxt` of chunk c + 1,
+// whose mask loads want those bytes from symbol 8 on.  No barrier is added: the coder's write is complete at its next
+// pair_barrier (lgkmcnt(0)), the one both waves meet at.  The model wave itself loads chunks 0 and 1 and puts chunk 1 into
+// the slot before its first chunk, so every chunk of either wave, of whatever kind, does the same: the coder wave one write
+// in its first half, the model wave one read at its top.  (The role book, the last 16 bytes of the ring, is far from the
+// slots, the first 1 KiB.)  The slot read is the OLDEST LDS operation of its chunk, so the lgkmcnt(N) counts of model_chunk,
+// which count the operations younger than the one waited for, stand as they were.
+// (Tried before this: the coder wave only touching each input line a line-time ahead of the model wave: 1.3 % faster, but
+// the lines do not stay in the L2 until they are used and FETCH_SIZE doubles.  The read side stays at 1.00 x the input.)
+__device__ __forceinline__ uint4 *feed_slot(uint2 *ring, uint32_t lane)
+{
+    return reinterpret_cast<uint4 *>(ring + ring_at(0, lane));
+}
 constexpr int kMaskAhead = 8; // symbols between a mask row's load and its use (4: 11.25 ms, 8: 11.01 ms when it was introduced)
 static_assert(kMaskAhead == 4 || kMaskAhead == 8, "prime() covers these");
 static_assert(16 % kMaskAhead == 0, "slot i % AHEAD must mean the same in every chunk");
@@ -491,8 +535,9 @@ __device__ __forceinline__ void model_chunk(const Tree<true> &T, uint2 *ring, ui
 // (SMEM shares lgkmcnt with LDS and returns out of order, so any LDS wait or ring barrier also
 // waits for every scalar load in flight; loaded at the top of the chunk, their miss latency sat
 // in front of the first barrier.  Sixteen at a time would need 64 SGPRs: spills.)
+// feed: the input bytes of the chunk after next, for the model wave (feed_slot).
 template <bool FIXUP, int MODE, bool CB32>
-__device__ __forceinline__ void coder_chunk(EncState &S, const uint2 *ring, uint32_t lane, uint32_t p,
+__device__ __forceinline__ void coder_chunk(EncState &S, uint2 *ring, uint32_t lane, uint32_t p, const uint4 feed,
                                             uint32_t nfreeze, rc_ptr rc, uint32_t sh, uint8_t *wdst, double (&r)[8])
 {
 #pragma unroll
@@ -505,6 +550,8 @@ __device__ __forceinline__ void coder_chunk(EncState &S, const uint2 *ring, uint
             lh[i]     = make_uint2(two.x, two.y);
             lh[i + 1] = make_uint2(two.z, two.w);
         }
+        if (h == 0)
+            *feed_slot(ring, lane) = feed; // behind the read of entries 0 and 1 (same address: the order is kept)
         double rn[8];
         if (MODE == 0) {
             uint32_t zero; // opaque 0 that "depends" on the ring data: pins the loads behind the LDS wait
@@ -551,13 +598,15 @@ __device__ __forceinline__ void coder_chunk(EncState &S, const uint2 *ring, uint
 
 // any chunk, rolled, every store checked against the slot limit
 template <bool FIXUP>
-__device__ __forceinline__ void coder_chunk_checked(EncState &S, const uint2 *ring, uint32_t lane, uint32_t p,
+__device__ __forceinline__ void coder_chunk_checked(EncState &S, uint2 *ring, uint32_t lane, uint32_t p, const uint4 feed,
                                                     uint32_t nfreeze, rc_ptr rc, uint32_t sh, uint8_t *wdst,
                                                     uint32_t limit)
 {
     for (uint32_t i = 0; i < 16; i++) {
         if ((i & 7) == 0)
             pair_barrier();
+        if (i == 2)
+            *feed_slot(ring, lane) = feed; // entries 0 and 1 have been read; complete at the barrier of i == 8
         const uint2    lh  = ring[ring_at(i, lane)];
         const uint32_t q   = p + i;
         const uint32_t nup = q < nfreeze ? q : nfreeze;
@@ -666,11 +715,13 @@ __global__ void __launch_bounds__(128) k_encode_pair(EncArgs a)
         __builtin_amdgcn_s_setprio(3);
         if (main_end) {
             uint32_t p = 0;
-            ChunkQueue Q;
-            Q.init(wsrc, soff, main_end);
-#define NEXT_CHUNK() Q.pop()
+            // Chunks 0 and 1 are this wave's own two loads; every later chunk comes from the coder wave through the
+            // ring (feed_slot), and chunk 1 takes the same way so that every chunk begins alike.  A chunk past the
+            // end re-reads the last one (never used), as the coder wave's queue does.
+            *feed_slot(ring, lane) = *reinterpret_cast<const uint4 *>(wsrc + soff + (main_end > 16 ? 16u : 0u));
+#define NEXT_CHUNK() (*feed_slot(ring, lane))
             // cur = the chunk at p, nxt the one after it (model_chunk loads masks a few symbols ahead, across the chunk boundary)
-            uint4    cur = NEXT_CHUNK(), nxt;
+            uint4    cur = *reinterpret_cast<const uint4 *>(wsrc + soff), nxt;
             MaskPipe mp;
             mp.prime(cur);
             uint32_t top = 0; // node 128 in this lane's half, as the LDS dword would hold it
@@ -680,6 +731,7 @@ __global__ void __launch_bounds__(128) k_encode_pair(EncArgs a)
             }
             T.add(T.A[7], top); // from here on (freeze-crossing chunk, frozen chunks, the coder wave's tail) the tree is read from LDS
             for (; p < m_end; p += 16) { // rolled: the update stops in the middle of this chunk
+                nxt = NEXT_CHUNK(); // (its own bytes it reads one by one from memory; the slot is taken as in every chunk)
                 for (uint32_t i = 0; i < 16; i++) {
                     const uint32_t q   = p + i;
                     const uint32_t nup = q < nfreeze ? q : nfreeze;
@@ -689,7 +741,7 @@ __global__ void __launch_bounds__(128) k_encode_pair(EncArgs a)
                     if ((i & 7) == 7)
                         pair_barrier();
                 }
-                cur = NEXT_CHUNK();
+                cur = nxt;
                 mp.prime(cur);
             }
             for (; p < main_end; p += 16, cur = nxt) {
@@ -703,19 +755,28 @@ __global__ void __launch_bounds__(128) k_encode_pair(EncArgs a)
         uint32_t p = 0;
         double   r[8];      // reciprocals of the first eight symbols of chunk r_at
         uint32_t r_at = ~0u;
+        // This wave owns the input stream (ChunkQueue: a line per visit, the next line in flight).  While it codes chunk p
+        // it hands the model wave the bytes of the chunk at p + 32 (feed_slot); taken from the queue BEFORE the chunk's
+        // first barrier, where this wave would otherwise only wait for the model wave.  A line was requested a line-time
+        // before its first use and is waited for once, where swap() copies it (s_waitcnt vmcnt(0): no order between the
+        // returns of its loads and of the stores below is relied on).
+        ChunkQueueT<true> Q;
+        if (main_end)
+            Q.init(wsrc, soff, main_end, 2);
         for (; p < main_end; p += 16) {
+            const uint4 feed = Q.pop();
             if (__builtin_amdgcn_ballot_w64(S.off + kChunkBudget > limit) || (p >= a_end && p < m_end))
-                coder_chunk_checked<FIXUP>(S, ring, lane, p, nfreeze, rc, sh, wdst, limit);
+                coder_chunk_checked<FIXUP>(S, ring, lane, p, feed, nfreeze, rc, sh, wdst, limit);
             else if (p < a_end) {
                 if (r_at != p) { // first chunk, or the previous one took the checked path
 #pragma unroll
                     for (int i = 0; i < 8; i++)
                         r[i] = rc[p + i];
                 }
-                coder_chunk<FIXUP, 0, CB32>(S, ring, lane, p, nfreeze, rc, sh, wdst, r);
+                coder_chunk<FIXUP, 0, CB32>(S, ring, lane, p, feed, nfreeze, rc, sh, wdst, r);
                 r_at = p + 16;
             } else
-                coder_chunk<FIXUP, 1, CB32>(S, ring, lane, p, nfreeze, rc, sh, wdst, r);
+                coder_chunk<FIXUP, 1, CB32>(S, ring, lane, p, feed, nfreeze, rc, sh, wdst, r);
         }
     }
     __syncthreads(); // the model wave's last updates are in LDS before the tail reads the tree
