@@ -961,6 +961,55 @@ int         redux_decode_blocks_mixed(const redux_params *p, const uint8_t *in, 
 const char *redux_mixed_kernel_name(uint64_t in_len, uint32_t block_size, int inverse);
 const char *redux_mixed_kernel_name_at(const void *d_src, const void *d_dst, uint64_t in_len, uint32_t block_size, int inverse);
 
+/* ---- range reads: decode only the blocks a byte range covers -----------------------------------------------------------
+ * Blocks are coded independently, and every layout in front of the coder is local to a short run of blocks, the GRANULE of
+ * g blocks: a frame of E blocks for the byte-plane layout, the delta filter, the XOR-against-base filter, stored and
+ * constant blocks and plane-static coding (table b mod E); a unit of 8 blocks for the mixed layouts; a segment of
+ * segment_blocks blocks for segment-static coding; one block (g = 1) where nothing sits in front of the coder.  Granule j of an
+ * input of `total` bytes in blocks of B is blocks [j g, min((j + 1) g, nblocks)) and bytes [j g B, min((j + 1) g B, total)); only
+ * the input's last granule can be short.
+ *
+ * Any run of whole granules -- its streams, its entries of the per-block tables (offsets rebased to 0, CRCs, stored and constant
+ * flags), its entries of the per-unit table, its segments' tables, its bytes of the base -- is a valid smaller input of the
+ * decode entry point of its layout, and so are several runs in ascending order, concatenated: the VIRTUAL INPUT.  The input's
+ * short last granule, if a run holds it, comes last there as well, and a base that covered a prefix of the input covers a
+ * prefix of the virtual input.  So reading R byte ranges is ONE decode call on the virtual input of the granules they cover,
+ * whatever R, and each range is then a slice of the result.
+ *
+ * redux_range_plan is that geometry (host arithmetic, no device call).  The ranges (starts[i], lens[i]) may come in any order,
+ * overlap and repeat.  Out: the union of the covered granules as disjoint ascending runs (run_first[r] the first granule,
+ * run_count[r] granules; touching and overlapping intervals are merged, *nruns <= nranges); *virt_len the bytes of the virtual
+ * input; virt_off[i] where range i begins in it.  A range without bytes covers no granule and gets virt_off 0 (starts[i] =
+ * total_len included).  INVALID_INPUT: starts[i] > total_len, starts[i] + lens[i] > total_len (a sum that overflows 64 bits
+ * included), block_size 0, granule_blocks 0. */
+int redux_range_plan(uint64_t total_len, uint32_t block_size, uint64_t granule_blocks, const uint64_t *starts,
+                     const uint64_t *lens, uint64_t nranges, uint64_t *run_first /* [nranges] */,
+                     uint64_t *run_count /* [nranges] */, uint64_t *nruns, uint64_t *virt_off /* [nranges] */,
+                     uint64_t *virt_len);
+
+/* The device piece: a segmented byte copy driven by a table, dst[segs[i].dst ..][: len] = src[segs[i].src ..][: len] for
+ * every i, both buffers at any byte alignment.  It gathers the covered streams of a compressed input kept in device memory
+ * into one compact stream buffer (and the covered bytes of a base), and scatters the requested bytes out of the decoded
+ * virtual input into the caller's tensor, without a host round trip.
+ *
+ * The segment table is HOST memory.  redux_segment_copy_dev checks it before any device call -- INVALID_INPUT for a segment
+ * that leaves its buffer (src + len > src_bytes or dst + len > dst_bytes, overflow included), for destination segments that
+ * overlap each other, and for buffers [d_src, d_src + src_bytes) and [d_dst, d_dst + dst_bytes) that overlap -- cuts the segments
+ * into tiles of at most 64 KiB, uploads the tile table to the front of the workspace and launches k_segment_copy once,
+ * stream-ordered (OUTPUT_TOO_SMALL for a workspace below redux_segment_copy_workspace_bytes).  No segments, or none with
+ * bytes: OK, nothing is launched.  redux_segment_tiles is the cut: a tile never straddles a segment, the tiles of a segment
+ * follow each other in order, and every tile but a segment's first starts at a 16-byte boundary of the destination (so only
+ * a segment's ends take the kernel's byte path).  It returns the number of tiles and writes them when `tiles` is not NULL. */
+typedef struct redux_segment {
+    uint64_t src, dst, len; /* byte offsets into d_src / d_dst, and the bytes to copy */
+} redux_segment;
+uint64_t    redux_segment_copy_workspace_bytes(const redux_segment *segs, uint64_t nsegs);
+uint64_t    redux_segment_tiles(const redux_segment *segs, uint64_t nsegs, redux_segment *tiles /* may be NULL */);
+int         redux_segment_copy_dev(const void *d_src, uint64_t src_bytes, void *d_dst, uint64_t dst_bytes,
+                                   const redux_segment *segs /* HOST memory */, uint64_t nsegs, void *d_workspace,
+                                   uint64_t workspace_bytes, void *stream);
+const char *redux_segment_copy_kernel_name(void);
+
 /* Library / build identification: "redux_hip <version> gfx950". */
 const char *redux_version(void);
 /* sha256 (first 16 hex digits) of the kernel sources + this header the library was built from ("unknown" when the

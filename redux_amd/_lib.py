@@ -161,6 +161,12 @@ SIGNATURES = {
     "redux_decode_blocks_mixed": (C.c_int, [_PP, _V, _V, _V, _U64, _U32, _V, _V, _V, _V]),
     "redux_mixed_kernel_name": (C.c_char_p, [_U64, _U32, C.c_int]),
     "redux_mixed_kernel_name_at": (C.c_char_p, [_V, _V, _U64, _U32, C.c_int]),
+    # range reads: the plan of the covered granules, and the segmented byte copy
+    "redux_range_plan": (C.c_int, [_U64, _U32, _U64, _V, _V, _U64, _V, _V, C.POINTER(_U64), _V, C.POINTER(_U64)]),
+    "redux_segment_copy_workspace_bytes": (_U64, [_V, _U64]),
+    "redux_segment_tiles": (_U64, [_V, _U64, _V]),
+    "redux_segment_copy_dev": (C.c_int, [_V, _U64, _V, _U64, _V, _U64, _V, _U64, _V]),
+    "redux_segment_copy_kernel_name": (C.c_char_p, []),
     "redux_planes_check": (C.c_int, [_U32]),
     "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

@@ -562,6 +562,9 @@ def _check_mixed(params, element_size=1, filter=None, stored=None, base=None, co
         raise InvalidInput()
 
 
+MIXED_UNIT_BLOCKS = 8  # REDUX_MIXED_UNIT_BLOCKS: blocks of a unit of the mixed layouts
+
+
 def _unit_table_arg(table, nunits):
     """a caller's unit table -> a contiguous np.uint8[nunits] with every entry 0 .. 7 (else InvalidInput)"""
     if not isinstance(table, np.ndarray) or table.dtype != np.uint8 or table.shape != (nunits,) or bool((table > 7).any()):
@@ -1025,6 +1028,90 @@ def _on_device(method):
     return wrapper
 
 
+# ---- range reads: the plan and the segmented copy (include/redux_hip.h, "range reads") -------
+SEGMENT_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u8")])  # redux_segment
+
+
+def _ranges_arg(ranges):
+    """the caller's (start, length) pairs -> (starts, lens) as np.uint64; InvalidInput for anything but pairs of integers
+    in [0, 2^64)"""
+    try:
+        pairs = [(int(s), int(n)) for s, n in ranges]
+    except (TypeError, ValueError):
+        raise InvalidInput()
+    if any(not 0 <= v < 1 << 64 for p in pairs for v in p):
+        raise InvalidInput()
+    a = np.array(pairs, dtype=np.uint64).reshape(-1, 2)
+    return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
+
+
+def range_plan(total, block_size, granule_blocks, ranges):
+    """redux_range_plan: the granules of granule_blocks blocks that the byte ranges (start, length) of an input of `total`
+    bytes cover.  -> (runs, virt_off, virt_len): runs the covered granules as ascending disjoint (first granule, count)
+    pairs, virt_len the bytes of their concatenation (the virtual input), virt_off[i] where range i begins in it (0 for a
+    range without bytes).  A range that leaves [0, total] is InvalidInput.  Host arithmetic: no GPU call."""
+    if not 0 <= total < 1 << 64 or not 0 < block_size < 1 << 32 or not 0 < granule_blocks < 1 << 64:
+        raise InvalidInput()
+    starts, lens = _ranges_arg(ranges)
+    n = len(starts)
+    first, count, off = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+    nruns, vlen = C.c_uint64(), C.c_uint64()
+    _raise(_lib.lib().redux_range_plan(total, block_size, granule_blocks, starts.ctypes.data, lens.ctypes.data, n, first.ctypes.data,
+                                       count.ctypes.data, C.byref(nruns), off.ctypes.data, C.byref(vlen)))
+    return ([(int(first[r]), int(count[r])) for r in range(nruns.value)], [int(v) for v in off[:n]], vlen.value)
+
+
+def _segments_arg(segments):
+    """(src, dst, len) triples, or an array of SEGMENT_DTYPE -> a contiguous array of SEGMENT_DTYPE"""
+    if isinstance(segments, np.ndarray) and segments.dtype == SEGMENT_DTYPE:
+        return np.ascontiguousarray(segments)
+    try:
+        rows = [(int(s), int(d), int(n)) for s, d, n in segments]
+    except (TypeError, ValueError):
+        raise InvalidInput()
+    if any(not 0 <= v < 1 << 64 for r in rows for v in r):
+        raise InvalidInput()
+    return np.array(rows, dtype=SEGMENT_DTYPE)
+
+
+def segment_tiles(segments):
+    """redux_segment_tiles: the tiles (an array of SEGMENT_DTYPE) the segmented copy cuts the segments into.  No GPU call."""
+    segs = _segments_arg(segments)
+    L = _lib.lib()
+    tiles = np.zeros(L.redux_segment_tiles(segs.ctypes.data, len(segs), None), dtype=SEGMENT_DTYPE)
+    L.redux_segment_tiles(segs.ctypes.data, len(segs), tiles.ctypes.data)
+    return tiles
+
+
+def _segment_copy(torch, d_src, d_dst, segs, ws=None):
+    """redux_segment_copy_dev on the current stream; ws: a uint8 device tensor to take the workspace from if it is large
+    enough (a new one otherwise)"""
+    L = _lib.lib()
+    need = L.redux_segment_copy_workspace_bytes(segs.ctypes.data, len(segs))
+    if ws is None or ws.numel() < need + 8:
+        ws = torch.empty(need + 8, dtype=torch.uint8, device=d_dst.device)
+    at = ws.data_ptr() + (-ws.data_ptr()) % 8
+    _raise(L.redux_segment_copy_dev(_dptr(d_src), d_src.numel(), _dptr(d_dst), d_dst.numel(), segs.ctypes.data, len(segs), at, need,
+                                    _stream_ptr(torch)))
+    return ws
+
+
+def segment_copy(d_src, d_dst, segments):
+    """d_dst[dst : dst + len] = d_src[src : src + len] for every (src, dst, len) of `segments`, in one launch of
+    k_segment_copy on torch's current stream.  d_src, d_dst: contiguous uint8 tensors on one device, at any byte alignment,
+    that do not overlap; the destination segments must not overlap each other (InvalidInput, before any GPU call).
+    Returns d_dst."""
+    torch = _torch()
+    for t in (d_src, d_dst):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise InvalidInput()
+    if d_src.device != d_dst.device:
+        raise InvalidInput()
+    with torch.cuda.device(d_dst.device):
+        _segment_copy(torch, d_src, d_dst, _segments_arg(segments))
+    return d_dst
+
+
 def _device_base(torch, base, device):
     """base= of the device coder objects: None, or a contiguous uint8 tensor on the coder's device (else InvalidInput)"""
     if base is None:
@@ -1263,15 +1350,15 @@ class DeviceDecoder(_DeviceCoder):
             if not 0 < self.block_size <= 1 << 30:
                 raise InvalidInput()
             self._decode_dev, self._lead, ws_bytes = L.redux_decode_mixed_dev, (), self._layout_ws_bytes(self.max_in_len)
-        elif self.constant:  # (the flags of the call come in front of them)
-            self._decode_dev, self._lead = L.redux_decode_const_dev, _base_pair(self.base)
+        elif self.constant:  # (the flags of the call come in front of the base pair, which is the call's: _takes_base)
+            self._decode_dev, self._lead, self._takes_base = L.redux_decode_const_dev, (), True
             ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
             if ws_bytes == 0:
                 raise Unsupported()
         elif self.delta:
             self._decode_dev, self._lead, ws_bytes = L.redux_decode_delta_dev, (), self._layout_ws_bytes(self.max_in_len)
         elif self.base is not None:
-            self._decode_dev, self._lead = L.redux_decode_base_dev, _base_pair(self.base)
+            self._decode_dev, self._lead, self._takes_base = L.redux_decode_base_dev, (), True
             ws_bytes = self._layout_ws_bytes(self.max_in_len)
         else:  # (element size 1: decode() without a length needs less, and the first one with a length regrows it)
             self._decode_dev, self._lead = L.redux_decode_planes_dev, ()
@@ -1288,6 +1375,9 @@ class DeviceDecoder(_DeviceCoder):
         """the workspace of the entry points that undo the layout, for an input of nbytes"""
         return _lib.lib().redux_decode_planes_workspace_bytes(C.byref(self.cp), nbytes, self.block_size, self.element_size)
 
+    _takes_base = False  # (the entry points of base= and constant=True take a (base, base_len) pair, whole or gathered)
+    _range_bufs = None   # (decode_ranges' buffers, made on its first call)
+
     @_on_device
     def decode(self, d_streams, d_offsets, length=None, constant=None, unit_layouts=None):
         """length: bytes of the original input; required with element_size > 1 (d_offsets then holds
@@ -1295,6 +1385,10 @@ class DeviceDecoder(_DeviceCoder):
         tensor of nblocks flags the encoder returned, for a decoder made with constant=True (and only for one).
         unit_layouts: the uint8 device tensor of nunits entries the encoder returned, for a decoder made with mixed=True (and
         only for one); the length is then required."""
+        return self._decode(d_streams, d_offsets, length, constant, unit_layouts, self.base)
+
+    def _decode(self, d_streams, d_offsets, length, constant, unit_layouts, base):
+        """decode()'s body; base: the uint8 device tensor the XOR is undone against, the decoder's own or a gathered one"""
         torch = _torch()
         L = _lib.lib()
         nb = d_offsets.numel() - 1
@@ -1329,10 +1423,102 @@ class DeviceDecoder(_DeviceCoder):
             if self.element_size == 1 and not self.constant and self.ws_bytes < self._layout_ws_bytes(nbytes):
                 self._alloc_workspace(self._layout_ws_bytes(self.max_in_len))
             decode_dev = self._decode_dev
-            args = (*flags, *self._lead, nbytes, self.block_size, self.element_size, self.out.data_ptr())
+            lead = _base_pair(base) if self._takes_base else self._lead
+            args = (*flags, *lead, nbytes, self.block_size, self.element_size, self.out.data_ptr())
         self.summary.zero_()
         _raise(decode_dev(C.byref(self.cp), d_streams.data_ptr(), d_offsets.data_ptr(), *args, *self._dec_tail()))
         return self._dec_result(nbytes, nb)
+
+    def _range_buffer(self, name, nbytes):
+        """a uint8 device buffer of at least nbytes that decode_ranges keeps between calls, next to the workspace"""
+        torch = _torch()
+        if self._range_bufs is None:
+            self._range_bufs = {}
+        t = self._range_bufs.get(name)
+        if t is None or t.numel() < nbytes:
+            t = self._range_bufs[name] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        return t
+
+    def _range_copy(self, d_src, d_dst, segs):
+        """the segmented copy with its tile table in the buffer decode_ranges keeps (the copies of a call follow each other on
+        one stream, so they can share it)"""
+        ws = _segment_copy(_torch(), d_src, d_dst, _segments_arg(segs), self._range_buffer("tiles", 0))
+        self._range_bufs["tiles"] = ws
+
+    @_on_device
+    def decode_ranges(self, d_streams, offsets, length, ranges, out=None, constant=None, unit_layouts=None):
+        """The bytes [start, start + n) of every (start, n) of `ranges` of the original input, from streams resident in
+        device memory, decoding only the granules the ranges cover (include/redux_hip.h, "range reads"): element_size blocks,
+        or 8 for a decoder made with mixed=True.  ONE decode launch whatever the number of ranges: the covered streams are
+        gathered into a compact buffer (k_segment_copy), with their entries of `constant` / `unit_layouts` and their bytes
+        of the base, decoded by the entry point decode() uses, and the requested bytes scattered into `out`
+        (k_segment_copy).
+        offsets: the nblocks + 1 stream offsets as a host array of integers, or the int64 device tensor the encoder returned,
+        which is copied to the host ONCE per call (a synchronisation: a caller who reads often keeps the host copy).
+        length: bytes of the original input.  constant / unit_layouts: as for decode(), for the WHOLE input.
+        out: a contiguous uint8 device tensor of sum(n) bytes at any alignment (a view into a larger one is fine); None: a
+        new one.  Returns (out, [where each range begins in out]).  A covered block that does not decode raises its status
+        (the decoder's summary is read: a synchronisation); ranges that leave [0, length], and covered granules of more than
+        max_blocks * block_size bytes, are InvalidInput.  Ranges without bytes make no GPU call."""
+        torch = _torch()
+        L = _lib.lib()
+        B = self.block_size
+        length = int(length)
+        offs = offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets)
+        if offs.ndim != 1 or offs.dtype.kind not in "ui" or length < 0 or len(offs) != L.redux_block_count(length, B) + 1 \
+                or d_streams.dtype != torch.uint8 or not d_streams.is_contiguous():
+            raise InvalidInput()
+        offs = _offsets_in(offs, d_streams.numel())
+        nb = len(offs) - 1
+        if (unit_layouts is None) == self.mixed or (constant is None) == self.constant:
+            raise InvalidInput()
+        g = MIXED_UNIT_BLOCKS if self.mixed else self.element_size
+        ranges = list(ranges)
+        runs, virt_off, virt_len = range_plan(length, B, g, ranges)
+        lens = [int(n) for _, n in ranges]
+        out_off = [int(v) for v in np.cumsum([0] + lens)[:-1]]
+        nout = sum(lens)
+        if out is None:
+            out = torch.empty(nout, dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() \
+                or out.numel() != nout or out.device != self.out.device:
+            raise InvalidInput()
+        if virt_len == 0:
+            return out, out_off
+        if virt_len > self.max_in_len:
+            raise InvalidInput()
+        for name, t, n in (("constant", constant, nb), ("unit_layouts", unit_layouts, L.redux_mixed_unit_count(length, B))):
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8
+                                  or not t.is_contiguous() or t.numel() != n):
+                raise InvalidInput()
+        # the covered blocks, run by run: their streams as segments, their sizes, their bytes of the base
+        blocks = [(f * g, min((f + c) * g, nb)) for f, c in runs]
+        sel = np.concatenate([np.arange(b0, b1, dtype=np.int64) for b0, b1 in blocks])
+        v_offs = np.zeros(len(sel) + 1, dtype=np.int64)
+        v_offs[1:] = np.cumsum((offs[sel + 1] - offs[sel]).astype(np.int64))
+        segs, at = [], 0
+        for b0, b1 in blocks:
+            segs.append((int(offs[b0]), at, int(offs[b1] - offs[b0])))
+            at += segs[-1][2]
+        d_v = self._range_buffer("streams", at)[:at]
+        self._range_copy(d_streams, d_v, segs)
+        d_voffs = torch.from_numpy(v_offs).to(self.device)
+        v_const = None if constant is None else constant[torch.from_numpy(sel).to(self.device)]
+        v_units = None if unit_layouts is None else unit_layouts[torch.from_numpy(np.unique(sel // MIXED_UNIT_BLOCKS)).to(self.device)]
+        v_base = self.base
+        if self._takes_base and self.base is not None and self.base.numel():
+            segs, at = [], 0
+            for b0, b1 in blocks:  # (what the base holds of each run: in ascending order a prefix of the virtual input)
+                lo, hi = min(b0 * B, self.base.numel()), min(b1 * B, length, self.base.numel())
+                segs.append((lo, at, hi - lo))
+                at += hi - lo
+            v_base = self._range_buffer("base", at)[:at]
+            self._range_copy(self.base, v_base, segs)
+        res = self._decode(d_v, d_voffs, virt_len, v_const, v_units, v_base)
+        st, _ = self.summary.tolist()
+        _raise(st)
+        self._range_copy(res[0], out, list(zip(virt_off, out_off, lens)))
+        return out, out_off
 
 
 class DeviceStaticCoder(_DeviceCoder):

@@ -4,6 +4,7 @@
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
                             [--filter delta] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--range START:LENGTH]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -73,13 +74,21 @@ unit): for files that hold several element types -- a checkpoint w
 indices and a text header -- where one layout for the whole file can only be the least bad.  A file of one type pays one byte
 per 8 blocks for it.  With `--element-size E` every unit is plain or delta at that E.  -d reads version 10 with no flag.
 The usage errors are those of `--layout auto`.
+`--range START:LENGTH` (with -d; both decimal, START + LENGTH at most the length of the data) writes only the bytes
+[START, START + LENGTH) of the original data, and decodes only the blocks that hold them (redux_amd/container.py: Reader;
+DESIGN.md 6o): one tensor out of a checkpoint.  With `-i FILE` the file is not read as a whole: the header and the tables are,
+then the streams of the covered blocks, so damage elsewhere in the file goes unnoticed; from stdin the input is read to its
+end first.  The summary line reports the bytes written and the bytes read from the input.  `--base FILE` works as for -d.  A
+raw reference stream has no random access, and a range may not leave the data: both are decompression errors (exit 3).
+`--range` with -c, without a value, or with a value that is not two non-negative decimal numbers around a colon, is a usage
+error.
 """
 import io
 import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>]")
+         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>]")
 
 
 def parse(argv):
@@ -96,7 +105,7 @@ def parse(argv):
             opts["compress"] = False
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range"):
             val = next(it, None)
             if val is None:
                 return None
@@ -118,6 +127,11 @@ def parse(argv):
                 opts["filter"] = val
             elif arg == "--base":
                 opts["base"] = val
+            elif arg == "--range":
+                start, colon, length = val.partition(":")
+                if not colon or not (start.isascii() and start.isdigit() and length.isascii() and length.isdigit()):
+                    return None
+                opts["range"] = (int(start), int(length))
             elif arg == "--layout":
                 if val not in ("auto", "mixed"):
                     return None
@@ -166,6 +180,8 @@ def parse(argv):
     if "layout" in opts and (not opts["compress"] or opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                              or "base" in opts or opts.get("skip_constant") or opts.get("model", "adaptive") != "adaptive"):
         return None  # the choice is recorded as the chosen layout's container, and it is made for the adaptive coder alone
+    if "range" in opts and opts["compress"] is not False:
+        return None  # a range is read, not written
     return None if opts["compress"] is None else opts
 
 
@@ -174,8 +190,10 @@ def main(argv=None):
     if opts is None:
         print(USAGE, file=sys.stderr)
         return 1
+    ranged = "range" in opts and opts["input"] is not None  # (the input file stays open and is read piece by piece)
     try:
-        data = sys.stdin.buffer.read() if opts["input"] is None else open(opts["input"], "rb").read()
+        data = sys.stdin.buffer.read() if opts["input"] is None else open(opts["input"], "rb") if ranged \
+            else open(opts["input"], "rb").read()
     except OSError as e:
         print(f"Error while opening input file {opts['input']}: {e}", file=sys.stderr)
         return 2
@@ -185,11 +203,15 @@ def main(argv=None):
             base = open(opts["base"], "rb").read()
         except OSError as e:
             print(f"Error while opening base file {opts['base']}: {e}", file=sys.stderr)
+            if ranged:
+                data.close()
             return 2
     try:
         sink = sys.stdout.buffer if opts["output"] is None else open(opts["output"], "wb")
     except OSError as e:
         print(f"Error while opening output file {opts['output']}: {e}", file=sys.stderr)
+        if ranged:
+            data.close()
         return 2
 
     from . import api, container
@@ -210,6 +232,14 @@ def main(argv=None):
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)
+        elif "range" in opts:
+            # (a raw reference stream has no random access: what is no container fails the header's checks here)
+            reader = container.Reader(data, base)
+            out = reader.read(*opts["range"])
+            sink.write(out)
+            i_n, o_n = reader.bytes_read, len(out)
+            ratio = (o_n / i_n) if i_n else float("nan")
+            print("Decompressed %d bytes from %d bytes read, ratio: %.3f" % (o_n, i_n, ratio), file=sys.stderr)
         else:
             # A container is recognised by a well-formed HEADER, not by its magic alone: a raw reference
             # stream may begin with the same four bytes.  Once the header is consistent the input IS a
@@ -233,6 +263,8 @@ def main(argv=None):
     finally:
         if opts["output"] is not None:
             sink.close()
+        if ranged:
+            data.close()
     return 0
 
 

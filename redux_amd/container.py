@@ -344,10 +344,10 @@ def _take(b, at, dtype, count):
     return np.frombuffer(b, dtype=dtype, count=count, offset=at), end
 
 
-def _parse(buf):
-    """every check of the layout, section by section: header, table, sizes, CRCs, bitmap, payload.  Malformed containers
-    raise InvalidInput, truncated ones Eof (src/lib.rs:57-64)."""
-    b = memoryview(buf)
+def _parse_index(b):
+    """every check of the layout before the payload, section by section: header, table, sizes, CRCs, bitmap.  -> (the
+    _Container without its payload, where the payload begins).  Malformed containers raise InvalidInput, truncated ones Eof
+    (src/lib.rs:57-64)."""
     ver, P, block_size, E, nblocks, total = _header(b)
     static = crcs = stored = base = constant = units = None
     at = HEADER.size
@@ -415,9 +415,16 @@ def _parse(buf):
         if bool((units > 7).any()):
             raise api.InvalidInput()
         E = None
-    payload, _ = _take(b, at, np.uint8, int(offsets[-1]))
-    return _Container(P, block_size, total, E, static, offsets, payload, crcs, stored,
-                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant, units)
+    return _Container(P, block_size, total, E, static, offsets, None, crcs, stored,
+                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant, units), at
+
+
+def _parse(buf):
+    """_parse_index, then the payload: a payload shorter than the size table says is Eof"""
+    b = memoryview(buf)
+    c, at = _parse_index(b)
+    payload, _ = _take(b, at, np.uint8, int(c.offsets[-1]))
+    return c._replace(payload=payload)
 
 
 def unpack(buf):
@@ -652,6 +659,12 @@ def decompress_bytes(buf, base=None):
     missing, short or different base, and a base given for a container without a record, are InvalidInput before anything is
     decoded."""
     c = _parse(buf)
+    return _decode_parsed(c, _checked_base(c, base))
+
+
+def _checked_base(c, base):
+    """the base a container's record asks for, cut to the bytes the coder used: InvalidInput for a missing, short or different
+    base, and for a base given to a container without a record"""
     if (base is None) != (c.base is None):
         raise api.InvalidInput()
     if c.base is not None:
@@ -659,6 +672,12 @@ def decompress_bytes(buf, base=None):
         if len(base) < c.base[0] or zlib.crc32(base[: c.base[0]]) != c.base[1]:
             raise api.InvalidInput()
         base = base[: c.base[0]]
+    return base
+
+
+def _decode_parsed(c, base):
+    """the bytes of a parsed container (base: _checked_base's): one decompress_blocks call, then every block's size against its
+    raw length and, with checksums, every OK block's CRC-32 against the recorded one"""
     # A stream of s bytes can decode to far more than s bytes (64 KiB of one symbol is ~400 bytes),
     # so only the declared total bounds the capacity; but every block's stream has at least one
     # byte, so a header that declares more blocks than there are payload bytes is malformed.
@@ -691,3 +710,131 @@ def decompress_bytes(buf, base=None):
     if exact or c.total == nb * cap:
         return out.tobytes()
     return b"".join(out[b * cap: b * cap + int(sizes[b])].tobytes() for b in range(nb))
+
+
+# ---- range reads: decode only the blocks a byte range covers (include/redux_hip.h, "range reads") ----------------------------
+CONTEXT_TABLES_MAX = 36 + 256 * 512  # version 7's table section at most: the total, the mask, 256 rows of 256 u16
+
+
+class _Source:
+    """the bytes of a container, fetched piece by piece: a bytes-like object, or a seekable binary file object.  bytes_read
+    counts what was fetched."""
+
+    def __init__(self, source):
+        self.bytes_read = 0
+        if hasattr(source, "read") and hasattr(source, "seek"):
+            self.file, self.view = source, None
+            self.size = source.seek(0, 2)
+        else:
+            self.file, self.view = None, memoryview(source).cast("B")
+            self.size = len(self.view)
+
+    def fetch(self, at, n):
+        """the bytes [at, at + n), fewer where the source ends first"""
+        n = max(0, min(n, self.size - at))
+        if self.view is not None:
+            got = self.view[at: at + n]
+        else:
+            self.file.seek(at)
+            got = self.file.read(n)
+        self.bytes_read += len(got)
+        return got
+
+
+def _index_rest_bytes(ver, nblocks):
+    """the bytes of the sections between the tables and the payload: sizes, CRCs, the bitmap or the unit table"""
+    n = 4 * nblocks + (4 * nblocks if ver & CRC_FLAG else 0) + ((nblocks + 7) // 8 if ver & STORED_FLAG else 0)
+    if _layout(ver) == VERSION_CONST:
+        n += (nblocks + 7) // 8
+    if _layout(ver) == VERSION_MIXED:
+        n += (nblocks + MIXED_UNIT_BLOCKS - 1) // MIXED_UNIT_BLOCKS
+    return n
+
+
+class Reader:
+    """Random access to a container's bytes: read(start, length) decodes only the granules the range covers (a frame of E
+    blocks; a unit of 8 blocks for version 10; a segment for version 5), and read_many(ranges) does so for any number of ranges
+    in ONE coder call.
+    source: the container as a bytes-like object, or a seekable binary file object, from which the header and the index
+    sections are read at open (every section's size follows from the header; of version 7's table section, whose size does
+    not, CONTEXT_TABLES_MAX bytes are read and then parsed) and later only the streams of covered blocks: the payload of
+    blocks no range covers is never read, so damage there -- a truncated file included -- does not matter to a range read.
+    base: as for decompress_bytes; it is checked against the container's record here, once.
+    total, block_size, nblocks, version, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
+    the source so far."""
+
+    def __init__(self, source, base=None):
+        self._src = src = _Source(source)
+        head = bytes(src.fetch(0, HEADER.size))
+        ver, P, _, E, nblocks, _ = _header(head)
+        res = HEADER.unpack_from(head, 0)[6]
+        layout = _layout(ver)
+        tables = BASE_RECORD.size if layout == VERSION_BASE or (layout == VERSION_CONST and res & 0x10) else 0
+        if layout == VERSION_STATIC:
+            tables += TABLE
+        elif layout == VERSION_PLANE_STATIC:
+            tables += E * TABLE
+        elif layout == VERSION_SEGMENT_STATIC:
+            tables += max(1, -(-nblocks // (64 * E * _segment_k(head)))) * E * TABLE
+        rest = _index_rest_bytes(ver, nblocks)
+        if layout == VERSION_CONTEXT_STATIC:  # (the table section says how long it is)
+            index = head + bytes(src.fetch(HEADER.size, CONTEXT_TABLES_MAX))
+            _, at = _unpack_context_tables(memoryview(index), HEADER.size, P)
+            index = index[: at + rest] + bytes(src.fetch(len(index), at + rest - len(index)))
+        else:
+            index = head + bytes(src.fetch(HEADER.size, tables + rest))
+        self._c, self.payload_offset = _parse_index(memoryview(index))
+        c = self._c
+        self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
+        self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
+            else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
+        self._base = _checked_base(c, base)
+
+    @property
+    def bytes_read(self):
+        return self._src.bytes_read
+
+    def read(self, start, length):
+        """the bytes [start, start + length) of the original data"""
+        return self.read_many([(start, length)])[0]
+
+    def read_many(self, ranges):
+        """-> [the bytes of each (start, length) of `ranges`], which may come in any order, overlap and repeat: the granules
+        they cover are decoded once, in one decompress_blocks call (none when no range has bytes), with every check
+        decompress_bytes makes applied to the covered blocks.  A range that leaves [0, total] is InvalidInput; a source that
+        ends inside a covered stream is Eof."""
+        c, g, B = self._c, self.granule_blocks, self.block_size
+        ranges = list(ranges)
+        runs, virt_off, virt_len = api.range_plan(c.total, B, g, ranges)
+        if virt_len == 0:
+            return [b""] * len(ranges)
+        blocks = [(f * g, min((f + n) * g, self.nblocks)) for f, n in runs]
+        parts = []
+        for b0, b1 in blocks:
+            o0, o1 = int(c.offsets[b0]), int(c.offsets[b1])
+            part = self._src.fetch(self.payload_offset + o0, o1 - o0)
+            if len(part) < o1 - o0:
+                raise api.Eof()
+            parts.append(np.frombuffer(part, dtype=np.uint8))
+        sel = np.concatenate([np.arange(b0, b1) for b0, b1 in blocks])
+        offsets = np.zeros(len(sel) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(c.offsets[sel + 1] - c.offsets[sel])
+        static, base = c.static, self._base
+        if isinstance(static, api.SegmentStaticModel):  # (a granule is a segment: the tables of the covered ones)
+            E = static.element_size
+            segs = np.concatenate([np.arange(f, f + n) for f, n in runs])
+            static = api.SegmentStaticModel(c.params, static.cums.reshape(-1, E, 258)[segs].reshape(-1, 258), E, g)
+        if base is not None:  # (what the base holds of each run: in ascending order a prefix of the virtual input)
+            base = np.concatenate([base[b0 * B: min(b1 * B, c.total)] for b0, b1 in blocks])
+        pick = lambda a: None if a is None else a[sel]
+        v = c._replace(total=virt_len, static=static, offsets=offsets, payload=np.concatenate(parts), crcs=pick(c.crcs),
+                       stored=pick(c.stored), constant=pick(c.constant),
+                       unit_layouts=None if c.unit_layouts is None else c.unit_layouts[np.unique(sel // MIXED_UNIT_BLOCKS)])
+        out = _decode_parsed(v, base)
+        return [out[o: o + int(n)] for o, (_, n) in zip(virt_off, ranges)]
+
+
+def decompress_range(buf, start, length, base=None):
+    """container bytes -> the bytes [start, start + length) of the original data, decoding only the blocks the range covers
+    (Reader(buf, base).read(start, length))."""
+    return Reader(buf, base).read(start, length)

@@ -23,6 +23,7 @@
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 //   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
 //   redux_mixed.hpp    k_mixed_choose / k_mixed_planes: a layout per unit of 8 blocks, chosen from those costs on the device
+//   redux_range.hpp    k_segment_copy: range reads, the plan of the covered granules and the segmented byte copy
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
 // extern "C" entry points.
 //
@@ -53,6 +54,7 @@
 #include "redux_cost.hpp"
 #include "redux_layout_cost.hpp"
 #include "redux_mixed.hpp"
+#include "redux_range.hpp"
 
 #include "../../include/redux_hip.h"
 
@@ -4369,5 +4371,53 @@ const char *redux_mixed_kernel_name(uint64_t in_len, uint32_t block_size, int in
 {
     return redux_mixed_kernel_name_at(nullptr, nullptr, in_len, block_size, inverse);
 }
+
+// ---- range reads (redux_range.hpp) ----------------------------------------------------------------------------------------
+int redux_range_plan(uint64_t total_len, uint32_t block_size, uint64_t granule_blocks, const uint64_t *starts, const uint64_t *lens,
+                     uint64_t nranges, uint64_t *run_first, uint64_t *run_count, uint64_t *nruns, uint64_t *virt_off,
+                     uint64_t *virt_len)
+{
+    return range_plan(total_len, block_size, granule_blocks, starts, lens, nranges, run_first, run_count, nruns, virt_off, virt_len);
+}
+
+uint64_t redux_segment_tiles(const redux_segment *segs, uint64_t nsegs, redux_segment *tiles)
+{
+    return segs ? segment_tiles(segs, nsegs, tiles) : 0;
+}
+
+uint64_t redux_segment_copy_workspace_bytes(const redux_segment *segs, uint64_t nsegs)
+{
+    return align_up(redux_segment_tiles(segs, nsegs, nullptr) * sizeof(redux_segment), 256);
+}
+
+int redux_segment_copy_dev(const void *d_src, uint64_t src_bytes, void *d_dst, uint64_t dst_bytes, const redux_segment *segs,
+                           uint64_t nsegs, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    const int st = segment_table_check(d_src, src_bytes, d_dst, dst_bytes, segs, nsegs);
+    if (st != REDUX_OK)
+        return st;
+    const uint64_t ntiles = segment_tiles(segs, nsegs, nullptr);
+    if (ntiles == 0)
+        return REDUX_OK;
+    if (!d_workspace || ((uintptr_t)d_workspace & 7))
+        return REDUX_INVALID_INPUT;
+    if (workspace_bytes < ntiles * sizeof(redux_segment))
+        return REDUX_OUTPUT_TOO_SMALL;
+    std::vector<redux_segment> tiles(ntiles);
+    segment_tiles(segs, nsegs, tiles.data());
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(d_workspace, tiles.data(), ntiles * sizeof(redux_segment), hipMemcpyHostToDevice, s));
+    SegmentCopyArgs a;
+    a.src    = (const uint8_t *)d_src;
+    a.dst    = (uint8_t *)d_dst;
+    a.tiles  = (const redux_segment *)d_workspace;
+    a.ntiles = ntiles;
+    const uint64_t cap = (uint64_t)cu_count() * 8; // eight workgroups of 256 per CU keep every wave slot busy; the rest is the stride
+    k_segment_copy<<<(uint32_t)(ntiles < cap ? ntiles : cap), kSegmentThreads, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+const char *redux_segment_copy_kernel_name(void) { return "k_segment_copy"; }
 
 } // extern "C"

@@ -205,6 +205,15 @@ extern "C" {
     #[allow(dead_code)]
     fn redux_mixed_kernel_name_at(d_src: *const c_void, d_dst: *const c_void, in_len: u64, block_size: u32,
                                   inverse: c_int) -> *const c_char;
+    // range reads: the plan of the granules a set of byte ranges covers (host arithmetic).  The segmented copy's calls
+    // (redux_segment_tiles, redux_segment_copy_workspace_bytes, redux_segment_copy_dev) take tables of the struct
+    // redux_segment and are for callers that keep streams in device memory: not bound here.
+    #[allow(dead_code)]
+    fn redux_range_plan(total_len: u64, block_size: u32, granule_blocks: u64, starts: *const u64, lens: *const u64,
+                        nranges: u64, run_first: *mut u64, run_count: *mut u64, nruns: *mut u64, virt_off: *mut u64,
+                        virt_len: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn redux_segment_copy_kernel_name() -> *const c_char;
     fn redux_host_release() -> c_int;
     fn redux_host_set_devices(device_ids: *const i32, n: u32) -> c_int;
 }
