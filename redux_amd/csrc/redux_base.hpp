@@ -2,15 +2,14 @@
 // fine-tuned model against its base), fused with the byte-plane layout (redux_planes.hpp): a byte transform in front of
 // the coder, next to k_planes and k_delta_planes, with a second input.
 //
-//   k_base_planes<E>          forward, full frames inside the base: k_planes's shape (16 elements per lane, the interleaved
-//                             side staged through LDS) with a second coalesced 16-byte load, from the base, XORed in on the
-//                             way into LDS, in front of planes_permute; E = 1: a plain 16-byte XOR stream, no LDS
-//   k_base_unplanes<E>        inverse, full frames inside the base: the plane loads, planes_permute inverse, the interleaved
-//                             side through LDS and XORed with the base's 16-byte chunk on the way out; no scan and no carry
-//                             along the frame, so k_planes's inverse shape
-//   k_base_planes_bytes<E>    one destination byte per thread, any alignment and block size: the short last frame, the frame
-//   k_base_unplanes_bytes<E>  the end of the base falls into, and everything when a pointer or the block size is no 16-byte
-//                             multiple
+//   k_base_planes<E>          forward, full frames inside the base: the forward tile (redux_planes.hpp) with a second
+//                             coalesced 16-byte load, from the base, XORed in by the stage-in hook on the way into LDS;
+//                             E = 1: a plain 16-byte XOR stream, no LDS
+//   k_base_unplanes<E>        inverse, full frames inside the base: the plain inverse tile, the base's chunks loaded ahead of
+//                             it and XORed in by the stage-out hook; no scan and no carry along the frame
+//   k_base_planes_bytes<E>    one destination byte per thread under the frame index rule, any alignment and block size: the
+//   k_base_unplanes_bytes<E>  short last frame, the frame the end of the base falls into, and everything when a pointer or
+//                             the block size is no 16-byte multiple
 //
 // Rule (E = element size, B = block size, x = the input of len bytes, y = the base of base_len bytes): y'[i] = y[i] for
 // i < min(len, base_len) and 0 beyond; d[i] = x[i] ^ y'[i] for every byte; the byte-plane layout of E is applied to d (none
@@ -41,7 +40,7 @@ struct BaseArgs {
 __device__ __forceinline__ uint4 base_xor(uint4 a, uint4 b) { return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w); }
 
 // Forward, full frames inside the base.  The wave's 1024*E contiguous bytes of the source and of the base are loaded with
-// the same coalesced 16-byte accesses and meet on the way into LDS; from there on it is planes_group's forward form.
+// the same coalesced 16-byte accesses and meet on the way into LDS.
 template <int E>
 __global__ void __launch_bounds__(256) k_base_planes(BaseArgs a)
 {
@@ -51,42 +50,13 @@ __global__ void __launch_bounds__(256) k_base_planes(BaseArgs a)
             ((uint4 *)a.dst)[g] = base_xor(((const uint4 *)a.src)[g], ((const uint4 *)a.base)[g]);
     } else {
         __shared__ uint4 lds[4 * 64 * E];
-        const uint32_t lane  = threadIdx.x & 63;
-        const uint64_t g0    = g - lane;
-        const bool     live  = g < a.groups;
-        const uint64_t f     = live ? g / a.frame_groups : 0;
-        const uint64_t i     = live ? g - f * a.frame_groups : 0;
-        const uint64_t fbase = f * (uint64_t)E * a.block_size;
-        const uint64_t left  = g0 < a.groups ? a.groups - g0 : 0;
-        const uint32_t wave_chunks = (uint32_t)((left < 64 ? left : 64) * E);
-        uint4 *wl = lds + (threadIdx.x >> 6) * 64 * E;
-
-        const uint4 *s = (const uint4 *)(a.src + g0 * 16 * E);
-        const uint4 *y = (const uint4 *)(a.base + g0 * 16 * E);
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            const uint32_t c = k * 64 + lane;
-            if (c < wave_chunks)
-                wl[planes_lds_slot<E>(c)] = base_xor(s[c], y[c]);
-        }
-        __syncthreads();
-        if (!live)
-            return;
-        uint32_t in[4 * E], out[4 * E];
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            const uint4 v = wl[planes_lds_slot<E>(lane * E + k)];
-            in[4 * k] = v.x; in[4 * k + 1] = v.y; in[4 * k + 2] = v.z; in[4 * k + 3] = v.w;
-        }
-        planes_permute<E, false>(in, out);
-#pragma unroll
-        for (int p = 0; p < E; p++)
-            *(uint4 *)(a.dst + fbase + (uint64_t)p * a.block_size + i * 16) = make_uint4(out[4 * p], out[4 * p + 1], out[4 * p + 2], out[4 * p + 3]);
+        const uint4 *y = (const uint4 *)(a.base + (g - (threadIdx.x & 63)) * 16 * E); // the wave's chunks of the base
+        tile_forward<E, PlainForward<E>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
+                                            [y](uint4 v, int, uint32_t c) { return base_xor(v, y[c]); });
     }
 }
 
-// Inverse, full frames inside the base: planes_group's inverse staged form, the base XORed in where the wave writes its
-// contiguous bytes.
+// Inverse, full frames inside the base: the base XORed in where the wave writes its contiguous bytes.
 template <int E>
 __global__ void __launch_bounds__(256) k_base_unplanes(BaseArgs a)
 {
@@ -96,63 +66,31 @@ __global__ void __launch_bounds__(256) k_base_unplanes(BaseArgs a)
             ((uint4 *)a.dst)[g] = base_xor(((const uint4 *)a.src)[g], ((const uint4 *)a.base)[g]);
     } else {
         __shared__ uint4 lds[4 * 64 * E];
-        const uint32_t lane  = threadIdx.x & 63;
-        const uint64_t g0    = g - lane;
-        const bool     live  = g < a.groups;
-        const uint64_t f     = live ? g / a.frame_groups : 0;
-        const uint64_t i     = live ? g - f * a.frame_groups : 0;
-        const uint64_t fbase = f * (uint64_t)E * a.block_size;
-        const uint64_t left  = g0 < a.groups ? a.groups - g0 : 0;
-        const uint32_t wave_chunks = (uint32_t)((left < 64 ? left : 64) * E);
-        uint4 *wl = lds + (threadIdx.x >> 6) * 64 * E;
-
         // the base's chunks first: they depend on nothing, and are in flight while the planes are permuted
-        const uint4 *y = (const uint4 *)(a.base + g0 * 16 * E);
+        const uint32_t lane = threadIdx.x & 63, wave_chunks = tile_wave_chunks<E, uint64_t>(a.groups, g - lane);
+        const uint4   *y    = (const uint4 *)(a.base + (g - lane) * 16 * E);
         uint4 yb[E];
 #pragma unroll
         for (int k = 0; k < E; k++) {
             const uint32_t c = k * 64 + lane;
             yb[k] = c < wave_chunks ? y[c] : make_uint4(0, 0, 0, 0);
         }
-        if (live) {
-            uint32_t in[4 * E], out[4 * E];
-#pragma unroll
-            for (int p = 0; p < E; p++) {
-                const uint4 v = *(const uint4 *)(a.src + fbase + (uint64_t)p * a.block_size + i * 16);
-                in[4 * p] = v.x; in[4 * p + 1] = v.y; in[4 * p + 2] = v.z; in[4 * p + 3] = v.w;
-            }
-            planes_permute<E, true>(in, out);
-#pragma unroll
-            for (int k = 0; k < E; k++)
-                wl[planes_lds_slot<E>(lane * E + k)] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
-        }
-        __syncthreads();
-        uint4 *d = (uint4 *)(a.dst + g0 * 16 * E);
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            const uint32_t c = k * 64 + lane;
-            if (c < wave_chunks)
-                d[c] = base_xor(wl[planes_lds_slot<E>(c)], yb[k]);
-        }
+        tile_inverse<E>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
+                        [&yb](uint4 v, int k, uint32_t) { return base_xor(v, yb[k]); });
     }
 }
 
-// Destination bytes [first, end) of the whole buffer, one per thread: k_planes_bytes's index rule; the base byte is the one
-// at the INTERLEAVED position (the source's forward, the destination's inverse), zero from base_len on.
+// Destination bytes [first, end) of the whole buffer, one per thread; the base byte is the one at the INTERLEAVED position
+// (the source's forward, the destination's inverse), zero from base_len on.
 template <int E, bool INVERSE>
 __device__ __forceinline__ void base_bytes(const BaseArgs &a)
 {
-    const uint64_t frame = (uint64_t)E * a.block_size;
     for (uint64_t o = a.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < a.end; o += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t f = o / frame, fb = f * frame, r = o - fb;
-        const uint64_t L = a.len - fb < frame ? a.len - fb : frame;
-        const uint64_t n = L / E; // elements of this frame
-        uint64_t s = r;           // trailing bytes: in place
-        if (r < n * E)
-            s = INVERSE ? (r % E) * n + r / E : (r % n) * E + r / n;
-        const uint64_t yi = INVERSE ? o : fb + s;
+        const FramePos f  = frame_pos(o, a.len, E, a.block_size);
+        const uint64_t s  = f.base + frame_src<INVERSE>(f, E);
+        const uint64_t yi = INVERSE ? o : s;
         const uint8_t  y  = yi < a.base_len ? a.base[yi] : (uint8_t)0;
-        a.dst[o] = a.src[fb + s] ^ y;
+        a.dst[o] = a.src[s] ^ y;
     }
 }
 

@@ -1,14 +1,13 @@
 // redux_delta.hpp -- the delta filter for integer series, fused with the byte-plane layout (redux_planes.hpp): a byte
 // transform in front of the coder, next to k_planes.
 //
-//   k_delta_planes<E>          forward, full frames: k_planes's shape (16 elements per lane, the interleaved side staged
-//                              through LDS) with one subtraction in front of planes_permute; one read and one write
-//   k_delta_unplanes<E>        inverse, full frames: one workgroup walks one frame, 256 lanes x 16 elements per iteration:
-//                              E plane loads, planes_permute inverse, a serial prefix over the lane's 16 elements in
-//                              registers, the lane totals scanned across the wave with __shfl_up, the wave totals carried
-//                              through LDS, a running carry along the frame, the interleaved side written through LDS
-//   k_delta_planes_bytes<E>    forward, one element per thread: the short last frame, unaligned buffers, blocks not a
-//   k_delta_unplanes_bytes<E>  multiple of 16; the inverse with one workgroup per frame and a scan of one element per lane
+//   k_delta_planes<E>          forward, full frames: the forward tile (redux_planes.hpp) with DeltaForward in front of the
+//                              permutation: the predecessor rule and one subtraction; one read and one write
+//   k_delta_unplanes<E>        inverse, full frames: one workgroup per frame, one row of 256 groups per iteration: the walk
+//                              of delta_inverse_walk (which the mixed kernel runs with 8 / E rows) with its own prefetch
+//   k_delta_planes_bytes<E>    the byte path, one element per thread: the short last frame, unaligned buffers, blocks not a
+//   k_delta_unplanes_bytes<E>  multiple of 16; bytes_forward (redux_planes.hpp), and bytes_inverse_frame with one workgroup
+//                              per frame
 //
 // Rule (E = element size, B = block size): the input is cut into the frames of the byte-plane layout (E*B bytes, only the
 // last may be shorter; E = 1: one block).  A frame of L bytes holds N = L / E little-endian unsigned elements x[0..N); the
@@ -143,62 +142,117 @@ __device__ __forceinline__ T delta_wave_scan(T x, uint32_t lane)
     return x;
 }
 
-// Forward, full frames: planes_group's forward staged form with the subtraction in front of the permutation.  A lane's
-// predecessor element is the end of the 16-byte chunk before its own in the wave's staged region; the wave's first lane
-// loads it from memory; at a frame start there is none.
+// The forward predecessor rule, as the forward tile's filter (PlainForward, redux_planes.hpp): a lane's predecessor element
+// is the end of the 16-byte chunk before its own in the wave's LDS row; the wave's first lane loads it from memory, ahead of
+// the barrier; a group that starts a frame has none (inside = false).
+template <int E>
+struct DeltaForward {
+    typedef typename DeltaSum<E>::T Pred;
+    __device__ __forceinline__ static Pred before(const uint8_t *src, uint64_t g, bool inside, uint32_t lane)
+    {
+        return inside && lane == 0 ? *(const Pred *)(src + g * 16 * E - sizeof(Pred)) : 0;
+    }
+    __device__ __forceinline__ static void apply(const uint4 *row, uint32_t lane, bool inside, Pred prev, uint32_t (&v)[4 * E])
+    {
+        if (inside && lane != 0) {
+            const uint4 *c = &row[planes_lds_slot<E>(lane * E - 1)];
+            if constexpr (E == 8)
+                prev = ((const uint64_t *)c)[1];
+            else
+                prev = ((const uint32_t *)c)[3];
+        }
+        uint32_t d[4 * E];
+        delta_diff<E>(v, prev, d);
+#pragma unroll
+        for (int q = 0; q < 4 * E; q++)
+            v[q] = d[q];
+    }
+};
+
+// Forward, full frames: the forward tile with the subtraction in front of the permutation; one read and one write.
 template <int E>
 __global__ void __launch_bounds__(256) k_delta_planes(PlanesArgs a)
 {
-    typedef typename DeltaSum<E>::T T;
     __shared__ uint4 lds[4 * 64 * E];
-    const uint64_t g     = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lane  = threadIdx.x & 63;
-    const uint64_t g0    = g - lane;
-    const bool     live  = g < a.groups;
-    const uint64_t f     = live ? g / a.frame_groups : 0;
-    const uint64_t i     = live ? g - f * a.frame_groups : 0;
-    const uint64_t fbase = f * (uint64_t)E * a.block_size;
-    const uint64_t left  = g0 < a.groups ? a.groups - g0 : 0;
-    const uint32_t wave_chunks = (uint32_t)((left < 64 ? left : 64) * E);
-    uint4 *wl = lds + (threadIdx.x >> 6) * 64 * E;
-
-    T prev = 0;
-    if (live && i != 0 && lane == 0) // (i != 0: the bytes before the wave's region belong to the same frame)
-        prev = *(const T *)(a.src + g * 16 * E - sizeof(T));
-    const uint4 *s = (const uint4 *)(a.src + g0 * 16 * E);
-#pragma unroll
-    for (int k = 0; k < E; k++) {
-        const uint32_t c = k * 64 + lane;
-        if (c < wave_chunks)
-            wl[planes_lds_slot<E>(c)] = s[c];
-    }
-    __syncthreads();
-    if (!live)
-        return;
-    uint32_t in[4 * E], d[4 * E], out[4 * E];
-#pragma unroll
-    for (int k = 0; k < E; k++) {
-        const uint4 v = wl[planes_lds_slot<E>(lane * E + k)];
-        in[4 * k] = v.x; in[4 * k + 1] = v.y; in[4 * k + 2] = v.z; in[4 * k + 3] = v.w;
-    }
-    if (i != 0 && lane != 0) {
-        const uint4 *c = &wl[planes_lds_slot<E>(lane * E - 1)];
-        if constexpr (E == 8)
-            prev = ((const uint64_t *)c)[1];
-        else
-            prev = ((const uint32_t *)c)[3];
-    }
-    delta_diff<E>(in, prev, d);
-    planes_permute<E, false>(d, out);
-#pragma unroll
-    for (int p = 0; p < E; p++)
-        *(uint4 *)(a.dst + fbase + (uint64_t)p * a.block_size + i * 16) = make_uint4(out[4 * p], out[4 * p + 1], out[4 * p + 2], out[4 * p + 3]);
+    tile_forward<E, DeltaForward<E>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
+                                        TileNoHook());
 }
 
-// Inverse, full frames: workgroup w walks frames w, w + gridDim.x, ...; an iteration takes 256 groups of 16 elements.
-// The plane loads of the next iteration are issued before this one's scan, so the dependency chain along the frame (scan,
-// two barriers) overlaps the memory latency.  The wave totals alternate between two LDS rows, so one barrier per
-// iteration orders them.
+// The frame walk of the inverse: the workgroup walks frames first, first + step, ... below count (src, dst: frame 0), R rows
+// of 256 groups per iteration and pair of barriers: the plane loads, planes_permute inverse, a serial prefix over the
+// lane's 16 elements in registers, the lane totals scanned across the wave, the wave totals through LDS, a running carry
+// along the frame, the interleaved side written through LDS.  The plane loads of the next iteration are issued before this
+// one's scan, so the dependency chain along the frame (scan, two barriers) overlaps the memory latency.  The wave totals
+// alternate between two LDS rows, so one barrier per iteration orders them.  Row r's running sum starts from the carry
+// behind rows 0 .. r - 1: the totals of every row's waves are in LDS after the first barrier.
+// lds: 4 waves x R rows x 64*E chunks.
+template <int E, int R, typename I>
+__device__ __forceinline__ void delta_inverse_walk(const uint8_t *src, uint8_t *dst, uint32_t frame_groups, uint32_t block_size, I first,
+                                                   I step, I count, uint4 *lds, typename DeltaSum<E>::T (*wtot)[R][4])
+{
+    typedef typename DeltaSum<E>::T T;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint4 *wl = lds + wave * 64 * E * R;
+    uint32_t row = 0;
+    for (I f = first; f < count; f += step) {
+        const uint64_t fbase = (uint64_t)f * E * block_size;
+        T        carry = 0; // the sum of the frame's elements before this iteration
+        uint32_t nxt[R][4 * E];
+        auto load = [&](uint32_t i0) { // rows i0 / 256 .. of the frame; a lane past the frame's end gets zeros (a total of 0)
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const uint32_t i = i0 + r * 256 + threadIdx.x;
+#pragma unroll
+                for (int q = 0; q < 4 * E; q++)
+                    nxt[r][q] = 0;
+                if (i < frame_groups)
+                    plane_load<E>(src + fbase, block_size, i, nxt[r]);
+            }
+        };
+        load(0);
+        for (uint32_t i0 = 0; i0 < frame_groups; i0 += 256 * R, row ^= 1) {
+            uint32_t v[R][4 * E];
+            T        total[R], incl[R];
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                planes_permute<E, true>(nxt[r], v[r]);
+            if (i0 + 256 * R < frame_groups) // the next iteration's loads are in flight while this one scans
+                load(i0 + 256 * R);
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                total[r] = delta_prefix<E>(v[r]);
+                incl[r]  = delta_wave_scan<T>(total[r], lane);
+                if (lane == 63)
+                    wtot[row][r][wave] = incl[r];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                T before = carry + incl[r] - total[r];
+#pragma unroll
+                for (uint32_t w = 0; w < 4; w++) {
+                    const T t = wtot[row][r][w];
+                    before += w < wave ? t : 0;
+                    carry += t;
+                }
+                delta_offset<E>(v[r], before);
+                if (i0 + r * 256 + threadIdx.x < frame_groups)
+                    tile_put<E>(wl + r * 64 * E, lane, v[r]);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const uint32_t w0 = i0 + r * 256 + threadIdx.x - lane; // the wave's first group of the row
+                tile_stage_out<E>(wl + r * 64 * E, (uint4 *)(dst + fbase + (uint64_t)w0 * 16 * E), tile_wave_chunks<E>(frame_groups, w0), lane,
+                                  TileNoHook());
+            }
+        }
+    }
+}
+
+// Inverse, full frames: workgroup w walks frames w, w + gridDim.x, ..., one row of 256 groups per iteration: the walk above
+// with R = 1, written out.  Through delta_inverse_walk<E, 1> the E = 8 instance measured 0.7 % slower (profiles/
+// layout_bodies.txt), so this kernel keeps its own loop, whose prefetch is decided per lane and issued ahead of the permutation.
 template <int E>
 __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
 {
@@ -216,13 +270,8 @@ __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
 #pragma unroll
         for (int q = 0; q < 4 * E; q++)
             nxt[q] = 0;
-        if (threadIdx.x < a.frame_groups) {
-#pragma unroll
-            for (int p = 0; p < E; p++) {
-                const uint4 v = *(const uint4 *)(a.src + fbase + (uint64_t)p * a.block_size + (uint64_t)threadIdx.x * 16);
-                nxt[4 * p] = v.x; nxt[4 * p + 1] = v.y; nxt[4 * p + 2] = v.z; nxt[4 * p + 3] = v.w;
-            }
-        }
+        if (threadIdx.x < a.frame_groups)
+            plane_load<E>(a.src + fbase, a.block_size, threadIdx.x, nxt);
         for (uint32_t i0 = 0; i0 < a.frame_groups; i0 += 256, row ^= 1) {
             const uint32_t i    = i0 + threadIdx.x;
             const bool     live = i < a.frame_groups;
@@ -231,11 +280,7 @@ __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
             for (int q = 0; q < 4 * E; q++)
                 in[q] = nxt[q];
             if ((uint64_t)i + 256 < a.frame_groups) {
-#pragma unroll
-                for (int p = 0; p < E; p++) {
-                    const uint4 x = *(const uint4 *)(a.src + fbase + (uint64_t)p * a.block_size + ((uint64_t)i + 256) * 16);
-                    nxt[4 * p] = x.x; nxt[4 * p + 1] = x.y; nxt[4 * p + 2] = x.z; nxt[4 * p + 3] = x.w;
-                }
+                plane_load<E>(a.src + fbase, a.block_size, (uint64_t)i + 256, nxt);
             } else {
 #pragma unroll
                 for (int q = 0; q < 4 * E; q++)
@@ -256,95 +301,74 @@ __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
             }
             delta_offset<E>(v, before);
             if (live)
-#pragma unroll
-                for (int k = 0; k < E; k++)
-                    wl[planes_lds_slot<E>(lane * E + k)] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+                tile_put<E>(wl, lane, v);
             __syncthreads();
             const uint32_t w0 = i0 + wave * 64; // the wave's first group of the frame
             if (w0 < a.frame_groups) {
-                const uint32_t left = a.frame_groups - w0, wave_chunks = (left < 64 ? left : 64) * E;
-                uint4 *d = (uint4 *)(a.dst + fbase + (uint64_t)w0 * 16 * E);
-#pragma unroll
-                for (int k = 0; k < E; k++) {
-                    const uint32_t c = k * 64 + lane;
-                    if (c < wave_chunks)
-                        d[c] = wl[planes_lds_slot<E>(c)];
-                }
+                const uint32_t left = a.frame_groups - w0;
+                tile_stage_out<E>(wl, (uint4 *)(a.dst + fbase + (uint64_t)w0 * 16 * E), (left < 64 ? left : 64) * E, lane, TileNoHook());
             }
         }
     }
 }
 
-// Forward, any alignment and block size: source bytes [first, len) of the whole buffer, the thread of an element's first
-// byte does the element, the threads of a frame's trailing bytes copy them.
+// Forward, any alignment and block size: source bytes [first, len) of the whole buffer, one per thread.
 template <int E>
 __global__ void __launch_bounds__(256) k_delta_planes_bytes(PlanesArgs a)
 {
-    const uint64_t frame = (uint64_t)E * a.block_size;
-    for (uint64_t o = a.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < a.len; o += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t f = o / frame, base = f * frame, r = o - base;
-        const uint64_t L = a.len - base < frame ? a.len - base : frame;
-        const uint64_t n = L / E;
-        if (r >= n * E) {
-            a.dst[o] = a.src[o];
-            continue;
-        }
-        if (r % E)
-            continue;
-        const uint64_t i = r / E;
-        uint64_t x = 0, p = 0;
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            x |= (uint64_t)a.src[o + k] << (8 * k);
-            if (i)
-                p |= (uint64_t)a.src[o - E + k] << (8 * k);
-        }
-        const uint64_t d = x - p;
-#pragma unroll
-        for (int k = 0; k < E; k++)
-            a.dst[base + (uint64_t)k * n + i] = (uint8_t)(d >> (8 * k));
-    }
+    for (uint64_t o = a.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < a.len; o += (uint64_t)gridDim.x * blockDim.x)
+        bytes_forward(a.src, a.dst, o, a.len, E, a.block_size, true);
 }
 
-// Inverse, any alignment and block size: workgroup w takes frames w, w + gridDim.x, ... of [first, len), 256 elements per
-// iteration, one per lane, summed in 64 bits (congruent mod 2^(8E)) by a wave scan and the wave totals in LDS.
-template <int E>
-__global__ void __launch_bounds__(256) k_delta_unplanes_bytes(PlanesArgs a)
+// The inverse of the byte path: the workgroup walks the frame of L bytes at `base`, 256 elements per iteration, one per
+// lane, summed in 64 bits (congruent mod 2^(8E)) by a wave scan and the wave totals in LDS; a plain layout skips the sum.
+// E, delta and L are uniform over the workgroup.  The rows of wtot alternate from one barrier to the next, across frames
+// too (row), so one barrier per iteration orders them.
+__device__ __forceinline__ void bytes_inverse_frame(const uint8_t *src, uint8_t *dst, uint64_t base, uint64_t L, uint32_t E, bool delta,
+                                                    uint64_t (*wtot)[4], uint32_t &row)
 {
-    __shared__ uint64_t wtot[2][4];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t frame = (uint64_t)E * a.block_size, nframes = (a.len - a.first + frame - 1) / frame;
-    uint32_t row = 0;
-    for (uint64_t fi = blockIdx.x; fi < nframes; fi += gridDim.x) {
-        const uint64_t base = a.first + fi * frame;
-        const uint64_t L = a.len - base < frame ? a.len - base : frame;
-        const uint64_t n = L / E;
-        if (n * E + threadIdx.x < L) // (at most E - 1 trailing bytes)
-            a.dst[base + n * E + threadIdx.x] = a.src[base + n * E + threadIdx.x];
-        uint64_t carry = 0;
-        for (uint64_t i0 = 0; i0 < n; i0 += 256, row ^= 1) {
-            const uint64_t i = i0 + threadIdx.x;
-            uint64_t d = 0;
-            if (i < n)
-#pragma unroll
-                for (int k = 0; k < E; k++)
-                    d |= (uint64_t)a.src[base + (uint64_t)k * n + i] << (8 * k);
+    const uint64_t n = L / E;
+    if (n * E + threadIdx.x < L) // (at most E - 1 trailing bytes)
+        dst[base + n * E + threadIdx.x] = src[base + n * E + threadIdx.x];
+    uint64_t carry = 0;
+    for (uint64_t i0 = 0; i0 < n; i0 += 256) {
+        const uint64_t i = i0 + threadIdx.x;
+        uint64_t d = 0;
+        if (i < n)
+            for (uint32_t q = 0; q < E; q++)
+                d |= (uint64_t)src[base + (uint64_t)q * n + i] << (8 * q);
+        uint64_t x = d;
+        if (delta) {
+            row ^= 1;
             const uint64_t incl = delta_wave_scan<uint64_t>(d, lane);
             if (lane == 63)
                 wtot[row][wave] = incl;
             __syncthreads();
-            uint64_t x = carry + incl;
+            x = carry + incl;
 #pragma unroll
             for (uint32_t w = 0; w < 4; w++) {
                 const uint64_t t = wtot[row][w];
                 x += w < wave ? t : 0;
                 carry += t;
             }
-            if (i < n)
-#pragma unroll
-                for (int k = 0; k < E; k++)
-                    a.dst[base + i * E + k] = (uint8_t)(x >> (8 * k));
         }
+        if (i < n)
+            for (uint32_t q = 0; q < E; q++)
+                dst[base + i * E + q] = (uint8_t)(x >> (8 * q));
+    }
+}
+
+// Inverse, any alignment and block size: workgroup w takes frames w, w + gridDim.x, ... of [first, len).
+template <int E>
+__global__ void __launch_bounds__(256) k_delta_unplanes_bytes(PlanesArgs a)
+{
+    __shared__ uint64_t wtot[2][4];
+    const uint64_t frame = (uint64_t)E * a.block_size, nframes = (a.len - a.first + frame - 1) / frame;
+    uint32_t row = 0;
+    for (uint64_t fi = blockIdx.x; fi < nframes; fi += gridDim.x) {
+        const uint64_t base = a.first + fi * frame;
+        bytes_inverse_frame(a.src, a.dst, base, a.len - base < frame ? a.len - base : frame, E, true, wtot, row);
     }
 }
 

@@ -61,11 +61,13 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace redux {
@@ -525,94 +527,100 @@ static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *c
             }};
 }
 
-// ---- the transforms in front of a coder (redux_planes.hpp, redux_delta.hpp) -------------------------------------------
-// What the launches of the byte-plane layout and of the delta filter share: the arguments and the split of the bytes.  The
-// fast kernels take the `nfull` full frames when block size and pointers are 16-byte multiples (nfull = 0 otherwise, and
-// a.groups stays 0); the byte kernels take everything from `rest` on (a.first of their launch).
-struct PlanesSplit {
-    PlanesArgs a;
-    uint64_t   nfull, rest;
+// ---- the transforms in front of a coder (redux_planes.hpp, redux_delta.hpp, redux_base.hpp, redux_mixed.hpp) ------------
+// The split every transform launch makes: the fast kernel takes the `nfull` whole granules (a frame of E*B bytes, a unit of
+// 8*B) of len bytes when the block size and every pointer are 16-byte multiples, and none otherwise; a byte kernel takes
+// everything from byte `rest` on.
+struct FastSplit {
+    uint64_t nfull, rest;
 };
 
-static PlanesSplit planes_split(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t E)
+static FastSplit fast_split(uint64_t len, uint64_t granule, uint32_t block_size, std::initializer_list<const void *> ptrs)
 {
-    PlanesSplit f;
-    f.a.src          = (const uint8_t *)d_src;
-    f.a.dst          = (uint8_t *)d_dst;
-    f.a.block_size   = block_size;
-    f.a.frame_groups = block_size / 16;
-    f.a.len          = len;
-    f.a.first        = 0;
-    f.a.groups       = 0;
-    const uint64_t frame = (uint64_t)E * block_size;
-    f.nfull = block_size % 16 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0 ? len / frame : 0;
-    f.a.groups = f.nfull * f.a.frame_groups;
-    f.rest     = f.nfull * frame;
-    return f;
+    uintptr_t bits = block_size;
+    for (const void *p : ptrs)
+        bits |= (uintptr_t)p;
+    const uint64_t nfull = bits & 15 ? 0 : len / granule;
+    return {nfull, nfull * granule};
+}
+
+// The three grid rules.  A workgroup per 256 groups, or W per unit: every workgroup has its own work, so a launch of more
+// than 2^31 - 1 is refused (false).  A thread per byte and a workgroup per frame (or unit) stride over their work.
+static bool grid_tiles(uint64_t wgs, uint32_t *grid)
+{
+    *grid = (uint32_t)wgs;
+    return wgs <= 0x7FFFFFFFull;
+}
+static uint32_t grid_bytes(uint64_t nbytes) { return (uint32_t)std::min<uint64_t>((nbytes + 255) / 256, 8192); }
+static uint32_t grid_frames(uint64_t nframes) { return (uint32_t)std::min<uint64_t>(nframes, 1u << 20); }
+
+static PlanesArgs planes_args(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, const FastSplit &f)
+{
+    PlanesArgs a;
+    a.src          = (const uint8_t *)d_src;
+    a.dst          = (uint8_t *)d_dst;
+    a.block_size   = block_size;
+    a.frame_groups = block_size / 16;
+    a.groups       = f.nfull * a.frame_groups;
+    a.first        = f.rest;
+    a.len          = len;
+    return a;
 }
 
 // the byte-plane layout: one workgroup per 256 groups of the full frames, the byte kernel for the rest
 template <int E>
 static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
 {
-    PlanesSplit f = planes_split(d_src, d_dst, len, block_size, E);
-    PlanesArgs &a = f.a;
+    const FastSplit  f = fast_split(len, (uint64_t)E * block_size, block_size, {d_src, d_dst});
+    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
     if (f.nfull) {
-        const uint64_t wgs = (a.groups + 255) / 256;
-        if (wgs > 0x7FFFFFFFull)
+        uint32_t grid;
+        if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
         if (inverse)
-            k_planes<E, true><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_planes<E, true><<<grid, 256, 0, s>>>(a);
         else
-            k_planes<E, false><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_planes<E, false><<<grid, 256, 0, s>>>(a);
     }
-    a.first = f.rest;
-    if (a.first < len) { // the short last frame, or everything the fast kernel cannot take
-        const uint64_t n = len - a.first, wgs = (n + 255) / 256;
-        const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
+    if (f.rest < len) { // the short last frame, or everything the fast kernel cannot take
         if (inverse)
-            k_planes_bytes<E, true><<<grid, 256, 0, s>>>(a);
+            k_planes_bytes<E, true><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
         else
-            k_planes_bytes<E, false><<<grid, 256, 0, s>>>(a);
+            k_planes_bytes<E, false><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
 }
 
-// the delta filter: forward as the layout; the inverse a workgroup per frame (a frame's running sum), at most 2^20
+// the delta filter: forward as the layout; the inverse a workgroup per frame (a frame's running sum)
 template <int E>
 static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
 {
-    PlanesSplit f = planes_split(d_src, d_dst, len, block_size, E);
-    PlanesArgs &a = f.a;
+    const uint64_t   frame = (uint64_t)E * block_size;
+    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
+    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
     if (f.nfull) {
-        if (inverse) {
-            k_delta_unplanes<E><<<(uint32_t)(f.nfull < (1u << 20) ? f.nfull : (1u << 20)), 256, 0, s>>>(a);
-        } else {
-            const uint64_t wgs = (a.groups + 255) / 256;
-            if (wgs > 0x7FFFFFFFull)
-                return REDUX_UNSUPPORTED;
-            k_delta_planes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
-        }
+        uint32_t grid;
+        if (inverse)
+            k_delta_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a);
+        else if (!grid_tiles((a.groups + 255) / 256, &grid))
+            return REDUX_UNSUPPORTED;
+        else
+            k_delta_planes<E><<<grid, 256, 0, s>>>(a);
     }
-    a.first = f.rest;
-    if (a.first < len) { // the short last frame, or everything the fused kernels cannot take
-        const uint64_t n = len - a.first, frame = (uint64_t)E * block_size;
-        if (inverse) {
-            const uint64_t nframes = (n + frame - 1) / frame;
-            k_delta_unplanes_bytes<E><<<(uint32_t)(nframes < (1u << 20) ? nframes : (1u << 20)), 256, 0, s>>>(a);
-        } else {
-            const uint64_t wgs = (n + 255) / 256;
-            k_delta_planes_bytes<E><<<(uint32_t)(wgs < 8192 ? wgs : 8192), 256, 0, s>>>(a);
-        }
+    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
+        if (inverse)
+            k_delta_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
+        else
+            k_delta_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
 }
 
-// the base filter: the fused kernels take the full frames that lie inside the base when block size and all three pointers
-// are 16-byte multiples, one workgroup per 256 groups; the byte kernels take the rest up to the end of the frame the base
-// ends in (or of the input); whole frames past the base have nothing to XOR and go to the layout alone (launch_planes)
+// the base filter: the fused kernels take the full frames that lie inside the base, one workgroup per 256 groups; the byte
+// kernels take the rest up to the end of the frame the base ends in (or of the input); whole frames past the base have
+// nothing to XOR and go to the layout alone (launch_planes)
 template <int E>
 static int launch_base(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
                        bool inverse, hipStream_t s)
@@ -626,28 +634,25 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
     a.frame_groups = block_size / 16;
     a.len          = len;
     a.base_len     = base_len < len ? base_len : len;
-    const bool     aligned = block_size % 16 == 0 && (((uintptr_t)d_src | (uintptr_t)d_base | (uintptr_t)d_dst) & 15) == 0;
-    const uint64_t nfast   = aligned ? a.base_len / frame : 0;
-    a.groups = nfast * a.frame_groups;
-    a.first  = nfast * frame;
+    const FastSplit f = fast_split(a.base_len, frame, block_size, {d_src, d_base, d_dst});
+    a.groups = f.nfull * a.frame_groups;
+    a.first  = f.rest;
     a.end    = (a.base_len + frame - 1) / frame * frame; // the end of the frame the base ends in
     a.end    = a.end < len ? a.end : len;
-    if (nfast) {
-        const uint64_t wgs = (a.groups + 255) / 256;
-        if (wgs > 0x7FFFFFFFull)
+    if (f.nfull) {
+        uint32_t grid;
+        if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
         if (inverse)
-            k_base_unplanes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_base_unplanes<E><<<grid, 256, 0, s>>>(a);
         else
-            k_base_planes<E><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_base_planes<E><<<grid, 256, 0, s>>>(a);
     }
     if (a.first < a.end) {
-        const uint64_t wgs  = (a.end - a.first + 255) / 256;
-        const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
         if (inverse)
-            k_base_unplanes_bytes<E><<<grid, 256, 0, s>>>(a);
+            k_base_unplanes_bytes<E><<<grid_bytes(a.end - a.first), 256, 0, s>>>(a);
         else
-            k_base_planes_bytes<E><<<grid, 256, 0, s>>>(a);
+            k_base_planes_bytes<E><<<grid_bytes(a.end - a.first), 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     if (a.end < len) { // (a.end is a whole number of frames here: the layout of the rest is the rest of the layout)
@@ -657,6 +662,18 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
             return launch_planes<E>(a.src + a.end, a.dst + a.end, len - a.end, block_size, inverse, s);
     }
     return REDUX_OK;
+}
+
+// f(std::integral_constant<int, E>) for a checked element size (redux_planes_check)
+template <typename F>
+static int for_element_size(uint32_t element_size, F &&f)
+{
+    switch (element_size) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
+    }
 }
 
 // redux_planes_dev, redux_delta_planes_dev and redux_base_planes_dev: the checks, then the transform's launch for the
@@ -671,33 +688,25 @@ static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t le
     const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
     if (s0 < d0 + len && d0 < s0 + len) // (not in place: the transform reads bytes another thread writes)
         return REDUX_INVALID_INPUT;
+    const uintptr_t y0 = (uintptr_t)d_base;
+    const uint64_t  used = base_len < len ? base_len : len;
+    if (base && used && y0 < d0 + len && d0 < y0 + used) // (nor may the destination lie over the bytes of the base that are read)
+        return REDUX_INVALID_INPUT;
     hipStream_t s = (hipStream_t)stream;
     const bool  inv = inverse != 0;
-    if (base) {
-        const uintptr_t y0 = (uintptr_t)d_base;
-        const uint64_t  used = base_len < len ? base_len : len;
-        if (used && y0 < d0 + len && d0 < y0 + used) // (nor may the destination lie over the bytes of the base that are read)
-            return REDUX_INVALID_INPUT;
-        switch (element_size) {
-        case 1: return launch_base<1>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        case 2: return launch_base<2>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        case 4: return launch_base<4>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        default: return launch_base<8>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+    return for_element_size(element_size, [&](auto e) -> int {
+        constexpr int E = decltype(e)::value;
+        if (base)
+            return launch_base<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        if (delta)
+            return launch_delta<E>(d_src, d_dst, len, block_size, inv, s);
+        if constexpr (E == 1) { // the layout of single bytes is the identity
+            HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s));
+            return REDUX_OK;
+        } else {
+            return launch_planes<E>(d_src, d_dst, len, block_size, inv, s);
         }
-    }
-    if (delta)
-        switch (element_size) {
-        case 1: return launch_delta<1>(d_src, d_dst, len, block_size, inv, s);
-        case 2: return launch_delta<2>(d_src, d_dst, len, block_size, inv, s);
-        case 4: return launch_delta<4>(d_src, d_dst, len, block_size, inv, s);
-        default: return launch_delta<8>(d_src, d_dst, len, block_size, inv, s);
-        }
-    switch (element_size) {
-    case 2: return launch_planes<2>(d_src, d_dst, len, block_size, inv, s);
-    case 4: return launch_planes<4>(d_src, d_dst, len, block_size, inv, s);
-    case 8: return launch_planes<8>(d_src, d_dst, len, block_size, inv, s);
-    default: HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s)); return REDUX_OK;
-    }
+    });
 }
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
@@ -862,45 +871,37 @@ static int launch_layout_cost(const void *d_in, uint64_t in_len, uint32_t block_
 }
 
 // ---- mixed layouts (redux_mixed.hpp) ----------------------------------------------------------------------------------
-// units the fast kernel takes: all full ones when block size and both buffers are 16-byte multiples, none otherwise
-static uint64_t mixed_full_units(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size)
-{
-    return block_size % 16 == 0 && (((uintptr_t)d_src | (uintptr_t)d_dst) & 15) == 0 ? len / ((uint64_t)kMixedUnit * block_size) : 0;
-}
-
 // the transform of d_src[0 .. len) under the device table: W workgroups per full unit (what E = 8 needs: the others loop),
-// the byte kernel for the rest -- forward a thread per byte, inverse a workgroup per unit, at most 2^20
+// the byte kernel for the rest -- forward a thread per byte, inverse a workgroup per unit
 static int launch_mixed(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, const void *d_table, bool inverse,
                         hipStream_t s)
 {
+    const uint64_t  unit = (uint64_t)kMixedUnit * block_size;
+    const FastSplit f = fast_split(len, unit, block_size, {d_src, d_dst});
     MixedArgs a;
     a.src          = (const uint8_t *)d_src;
     a.dst          = (uint8_t *)d_dst;
     a.table        = (const uint8_t *)d_table;
     a.block_size   = block_size;
     a.frame_groups = block_size / 16;
-    a.nfull        = mixed_full_units(d_src, d_dst, len, block_size);
+    a.nfull        = f.nfull;
     a.wgs          = (a.frame_groups + 255) / 256;
     a.len          = len;
-    a.first        = a.nfull * kMixedUnit * block_size;
-    if (a.nfull) {
-        const uint64_t wgs = a.nfull * a.wgs;
-        if (wgs > 0x7FFFFFFFull)
+    a.first        = f.rest;
+    if (f.nfull) {
+        uint32_t grid;
+        if (!grid_tiles(a.nfull * a.wgs, &grid))
             return REDUX_UNSUPPORTED;
         if (inverse)
-            k_mixed_planes<true><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_mixed_planes<true><<<grid, 256, 0, s>>>(a);
         else
-            k_mixed_planes<false><<<(uint32_t)wgs, 256, 0, s>>>(a);
+            k_mixed_planes<false><<<grid, 256, 0, s>>>(a);
     }
-    if (a.first < len) { // the short last unit, or everything the fast kernel cannot take
-        const uint64_t n = len - a.first, unit = (uint64_t)kMixedUnit * block_size;
-        if (inverse) {
-            const uint64_t nunits = (n + unit - 1) / unit;
-            k_mixed_bytes<true><<<(uint32_t)(nunits < (1u << 20) ? nunits : (1u << 20)), 256, 0, s>>>(a);
-        } else {
-            const uint64_t wgs = (n + 255) / 256;
-            k_mixed_bytes<false><<<(uint32_t)(wgs < 8192 ? wgs : 8192), 256, 0, s>>>(a);
-        }
+    if (f.rest < len) { // the short last unit, or everything the fast kernel cannot take
+        if (inverse)
+            k_mixed_bytes<true><<<grid_frames((len - f.rest + unit - 1) / unit), 256, 0, s>>>(a);
+        else
+            k_mixed_bytes<false><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -4363,8 +4364,8 @@ const char *redux_mixed_kernel_name_at(const void *d_src, const void *d_dst, uin
     };
     if (block_size == 0 || block_size > (1u << 30) || in_len == 0)
         return "";
-    const uint64_t nfull = mixed_full_units(d_src, d_dst, in_len, block_size);
-    return names[inverse != 0][nfull == 0 ? 2 : nfull * kMixedUnit * block_size < in_len ? 1 : 0];
+    const FastSplit f = fast_split(in_len, (uint64_t)kMixedUnit * block_size, block_size, {d_src, d_dst});
+    return names[inverse != 0][f.nfull == 0 ? 2 : f.rest < in_len ? 1 : 0];
 }
 
 const char *redux_mixed_kernel_name(uint64_t in_len, uint32_t block_size, int inverse)

@@ -76,18 +76,20 @@ def base_lengths(L, E, B):
 
 
 # ---- 1. the transform ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B", [1, 16, 48, 100, 1008, 4096])   # (1008: a frame ends inside a wave's turn of 64 groups)
+# (1008: a frame ends inside a wave's turn of 64 groups; 4688: 293 groups a frame, a row of 256 and a ragged wave, three frames)
+@pytest.mark.parametrize("B", [1, 16, 48, 100, 1008, 4096, 4688])
 @pytest.mark.parametrize("E", [1, 2, 4, 8])
 def test_base_planes_dev_matches_restatement(rx, E, B):
     rng = np.random.default_rng(E * 100003 + B)
     F = E * B
-    for L in (0, 1, F - 1, F, F + 1, 5 * F + 3 * E + 1):
+    last = (3 if B == 4688 else 5) * F + 3 * E + 1
+    for L in (0, 1, F - 1, F, F + 1, last):
         x = rng.integers(0, 256, L, dtype=np.uint8)
         for yl in base_lengths(L, E, B):
             y = rng.integers(0, 256, yl, dtype=np.uint8)
             check(rx, x, y, E, B)                    # all three on 16-byte boundaries: the fused kernels where B allows
             check(rx, x, y, E, B, 1, 1, 1)
-            if L == 5 * F + 3 * E + 1:               # each buffer alone, and all together, 1, 4 and 8 bytes off
+            if L == last:                            # each buffer alone, and all together, 1, 4 and 8 bytes off
                 for off in (1, 4, 8):
                     for so, yo, do in ((off, 0, 0), (0, off, 0), (0, 0, off), (off, off, off)):
                         check(rx, x, y, E, B, so, yo, do)

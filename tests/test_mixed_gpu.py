@@ -57,6 +57,21 @@ def splice(outs, table, n, B):
     return want
 
 
+def splice_and_back(rx, torch, x, d_x, outs, table, B):
+    """the transform under `table` is the splice, its inverse returns x, and neither writes outside its buffer"""
+    n = len(x)
+    want = splice(outs, table, n, B)
+    tg, d_y = guarded(torch, n)
+    rx.mixed_layout(d_x, table, B, out=d_y)
+    got = d_y.cpu().numpy()
+    assert np.array_equal(got, want), (B, n, table.tolist())
+    assert guards_intact(tg, n)
+    tg, d_back = guarded(torch, n)
+    rx.mixed_layout(d_y, torch.from_numpy(table).cuda(), B, inverse=True, out=d_back)
+    assert np.array_equal(d_back.cpu().numpy(), x), (B, n, table.tolist())
+    assert guards_intact(tg, n)
+
+
 # ---- the transform ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [16, 48, 256, 4096, 40, 1000])
 def test_mixed_layout_is_the_splice_of_the_whole_buffer_transforms(rx, lib, B):
@@ -75,19 +90,35 @@ def test_mixed_layout_is_the_splice_of_the_whole_buffer_transforms(rx, lib, B):
                 "k_mixed_planes<%d>" % i if n % (8 * B) == 0 else "k_mixed_planes<%d> + k_mixed_bytes<%d>" % (i, i)
             assert name == want_name, (n, B, inverse)
         for table in tables(nunits):
-            want = splice(outs, table, n, B)
-            tg, d_y = guarded(torch, n)
-            rx.mixed_layout(d_x, table, B, out=d_y)
-            got = d_y.cpu().numpy()
-            assert np.array_equal(got, want), (B, n, table.tolist())
-            assert guards_intact(tg, n)
-            tg, d_back = guarded(torch, n)
-            rx.mixed_layout(d_y, torch.from_numpy(table).cuda(), B, inverse=True, out=d_back)
-            assert np.array_equal(d_back.cpu().numpy(), x), (B, n, table.tolist())
-            assert guards_intact(tg, n)
+            splice_and_back(rx, torch, x, d_x, outs, table, B)
         if n == lengths(B)[-1]:  # the restatement of the rule agrees with the splice of the device's transforms
             t = tables(nunits)[8]
             assert np.array_equal(splice(outs, t, n, B), mixed_ref(x, t, B))
+
+
+def test_several_workgroups_per_unit_and_rows_past_the_frame_end(rx):
+    """B = 32816: 2051 groups per frame, 9 workgroups per unit; E = 1 behind the filter takes a second round of 8 rows of
+    which 3 groups are live, E = 8 nine iterations with a ragged last wave"""
+    import torch
+    B = 32816
+    for n in (8 * B, 2 * 8 * B, 2 * 8 * B + 5 * B + 7):
+        x = typed(n, seed=B + n % 7)
+        d_x = torch.from_numpy(x).cuda()
+        outs = whole(rx, torch, d_x, B)
+        for table in tables(rx.mixed_units(n, B)):
+            splice_and_back(rx, torch, x, d_x, outs, table, B)
+
+
+def test_sixteen_workgroups_per_unit(rx):
+    """B = 65536, the block size of the workload: 4096 groups per frame, 16 workgroups per unit"""
+    import torch
+    B = 65536
+    n = 2 * 8 * B
+    x = typed(n, seed=B)
+    d_x = torch.from_numpy(x).cuda()
+    outs = whole(rx, torch, d_x, B)
+    for table in tables(2)[8:10]:
+        splice_and_back(rx, torch, x, d_x, outs, table, B)
 
 
 @pytest.mark.parametrize("so,do", [(1, 0), (0, 15), (15, 1)])

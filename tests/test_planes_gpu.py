@@ -53,7 +53,7 @@ def guards_intact(t, n, offset=0):
 
 # ---- k_planes ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("E", [2, 4, 8])
-@pytest.mark.parametrize("B", [4, 16, 65536])
+@pytest.mark.parametrize("B", [4, 16, 65536, 4688])   # (4688: 293 groups a frame, a whole row of 256 and a ragged wave)
 def test_planes_dev_matches_restatement(rx, E, B):
     import torch
     rng = np.random.default_rng(E * 7 + B)
