@@ -419,6 +419,49 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
                               uint32_t *block_crc);
 
+/* ---- zigzag-folded delta filter for signed series ----------------------------------------------
+ * The delta filter's differences mod 2^(8E) put 0xFF into every upper byte when they are small and negative and 0x00 when
+ * they are small and positive, so a series that moves both ways -- a sampled signal, a random walk, offsets that go back and
+ * forth -- leaves each of the E - 1 upper byte planes an even mix of the two, about one bit per element per plane to a coder
+ * that sees one plane per block.  These calls are the delta filter with every difference folded so that small magnitudes of
+ * either sign become small unsigned numbers (Blosc, Parquet's DELTA_BINARY_PACKED and protobuf fold theirs the same way).
+ * Strictly opt-in, as the delta filter is; monotone series lose nothing by it, and E = 1 gains nothing.  E, B and the frames
+ * are the delta filter's.
+ *   - d[0] = x[0] and d[i] = x[i] - x[i-1] mod 2^(8E), as for the delta filter.
+ *   - z[i] = (d[i] << 1) ^ (0 - (d[i] >> (8E-1))) mod 2^(8E) for every i, 0 included: read as signed, d >= 0 maps to 2d and
+ *     d < 0 to -2d - 1.  The L - N*E trailing bytes of a frame are unchanged.
+ *   - The byte-plane layout above is then applied to the z's (E = 1: no layout).
+ *   - The inverse undoes the layout, unfolds with d = (z >> 1) ^ (0 - (z & 1)) and takes the running sum mod 2^(8E) inside
+ *     each frame.
+ * The fold is a bijection on E-byte words, so any input round-trips.  Behind the transform is the plain adaptive coder:
+ *     stream_zigzag_E(x)[b] == redux_encode_blocks(planes_E(zigzag_E(x)))[b].
+ * Not available with the static-table models, stored blocks, a base, constant blocks, the mixed layouts, the `_v` calls and
+ * redux_compress / redux_decompress.
+ *
+ * Every call is the shape of its delta namesake and keeps its promises: redux_zigzag_planes_dev is one read and one write;
+ * redux_decode_zigzag_dev writes no byte outside d_out[0 .. out_len), for damaged streams too, and every frame whose blocks
+ * are all OK holds the original bytes; the output of the host-pointer pair depends on neither the chunk size nor the
+ * devices, and block_crc is over the ORIGINAL bytes.
+ */
+int      redux_zigzag_check(uint32_t element_size);
+int      redux_zigzag_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                                 void *stream);
+uint64_t redux_encode_zigzag_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_zigzag_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_zigzag_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_zigzag_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                            void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_zigzag(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                               uint32_t *block_crc);
+int redux_decode_blocks_zigzag(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                               uint32_t *block_crc);
+
 /* ---- XOR-against-base filter for series of snapshots -------------------------------------------
  * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its
  * base model, optimizer state, a KV cache against its earlier self -- differs from its predecessor only in the low mantissa

@@ -183,6 +183,14 @@ SIGNATURES = {
     "redux_decode_delta_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
     "redux_encode_blocks_delta": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_delta": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
+    "redux_zigzag_check": (C.c_int, [_U32]),
+    "redux_zigzag_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
+    "redux_encode_zigzag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_zigzag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_zigzag_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_zigzag_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_zigzag": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_zigzag": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_base_check": (C.c_int, [_U32]),
     "redux_base_planes_dev": (C.c_int, [_V, _V, _U64, _V, _U64, _U32, _U32, C.c_int, _V]),
     "redux_encode_base_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

@@ -506,14 +506,21 @@ def _check_element_size(element_size):
 
 
 def _check_filter(filter, allowed=True):
-    """filter=None, or "delta": the delta filter for integer series (include/redux_hip.h, "delta filter"); anything else,
-    and "delta" where it is not available (allowed false), is InvalidInput.  A check on the arguments alone: it comes
-    before any call into the library.  -> True for "delta"."""
+    """filter=None, "delta": the delta filter for integer series (include/redux_hip.h, "delta filter"), or "zigzag": the
+    same with its differences folded (include/redux_hip.h, "zigzag-folded delta filter"); anything else, and a filter
+    where it is not available (allowed false), is InvalidInput.  A check on the arguments alone: it comes before any call
+    into the library.  -> False for None, True for "delta", "zigzag" for "zigzag": true wherever there is a filter, and
+    _zigzag() tells which."""
     if filter is None:
         return False
-    if not isinstance(filter, str) or filter != "delta" or not allowed:
+    if not isinstance(filter, str) or filter not in ("delta", "zigzag") or not allowed:
         raise InvalidInput()
-    return True
+    return True if filter == "delta" else filter
+
+
+def _zigzag(delta):
+    """of what _check_filter returned: is it the zigzag-folded filter"""
+    return delta == "zigzag"
 
 
 def _check_base(base, allowed=True):
@@ -651,6 +658,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     filter="delta": the delta filter for integer series in front of the layout, for any element_size (include/redux_hip.h,
     "delta filter": redux_encode_blocks_delta); decompress_blocks(..., element_size, length, filter="delta") undoes it.
     Adaptive model only, and not with stored=.
+    filter="zigzag": the delta filter with its differences folded, for series that move both ways (include/redux_hip.h,
+    "zigzag-folded delta filter": redux_encode_blocks_zigzag); accepted and refused exactly where "delta" is.
     base: bytes-like of any length, an earlier snapshot of the same data; the XOR against it is coded, for any element_size
     (include/redux_hip.h, "XOR-against-base filter": redux_encode_blocks_base); decompress_blocks(..., element_size, length,
     base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=.
@@ -708,8 +717,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
         if st == _lib.OK or cums.any():
             params.cums = cums
     elif delta:
-        st = L.redux_encode_blocks_delta(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
-                                         status.ctypes.data, crc)
+        encode = L.redux_encode_blocks_zigzag if _zigzag(delta) else L.redux_encode_blocks_delta
+        st = encode(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data, status.ctypes.data, crc)
     elif const:
         y = _u8(base) if xbase else _u8(b"")
         st = L.redux_encode_blocks_const(C.byref(cp), _ptr(a), len(a), _ptr(y) if len(y) else None, len(y), block_size, E,
@@ -768,7 +777,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     stored: the np.uint8[nblocks] flags compress_blocks(..., stored=) wrote; length is then required and out is
     uint8[length] in original order, as with element_size > 1.
     filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
-    for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.
+    for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.  filter="zigzag":
+    the same for compress_blocks(..., filter="zigzag")'s streams (redux_decode_blocks_zigzag).
     base: the bytes compress_blocks(..., base=) was given (redux_decode_blocks_base); length is required for every
     element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=.
     constant: the np.uint8[nblocks] flags compress_blocks(..., constant=) wrote (redux_decode_blocks_const), with the
@@ -817,8 +827,9 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
                                                       length, block_size, params.element_size, params.segment_blocks,
                                                       out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
     elif delta:
-        st = L.redux_decode_blocks_delta(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
-                                         sizes.ctypes.data, status.ctypes.data, crc)
+        decode = L.redux_decode_blocks_zigzag if _zigzag(delta) else L.redux_decode_blocks_delta
+        st = decode(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data, sizes.ctypes.data,
+                    status.ctypes.data, crc)
     elif const:
         y = _u8(base) if xbase else _u8(b"")
         st = L.redux_decode_blocks_const(C.byref(cp), _ptr(a), offs.ctypes.data, cptr, _ptr(y) if len(y) else None, len(y),
@@ -1232,7 +1243,7 @@ class DeviceEncoder(_DeviceCoder):
         self.constant = _check_constant(constant, filter is None and not isinstance(
             params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
         _check_base(base, filter is None)   # (before the filter's own check: both together are refused whatever the filter)
-        self.delta = _check_filter(filter)  # the delta filter in front of the layout (encode() only)
+        self.delta = _check_filter(filter)  # the delta filter, folded or not, in front of the layout (encode() only)
         torch = _torch()
         self.base = _device_base(torch, base, device)  # the XOR-against-base filter in front of the layout (encode() only)
         P = _params_of(params)
@@ -1250,7 +1261,9 @@ class DeviceEncoder(_DeviceCoder):
                 L.redux_encode_mixed_dev, (B,)
             self.unit_table = torch.zeros(max(L.redux_mixed_unit_count(self.max_in_len, B), 1), dtype=torch.uint8, device=self.device)
         elif self.delta:
-            ws_bytes, self._encode_dev, self._lead = L.redux_encode_delta_workspace_bytes, L.redux_encode_delta_dev, (B, E)
+            ws_bytes, self._encode_dev = (L.redux_encode_zigzag_workspace_bytes, L.redux_encode_zigzag_dev) if _zigzag(self.delta) \
+                else (L.redux_encode_delta_workspace_bytes, L.redux_encode_delta_dev)
+            self._lead = (B, E)
         elif self.constant:  # (the tail then holds the flags as well)
             ws_bytes, self._encode_dev = L.redux_encode_const_workspace_bytes, L.redux_encode_const_dev
             self._lead = (*_base_pair(self.base), B, E)
@@ -1324,7 +1337,8 @@ class DeviceEncoder(_DeviceCoder):
 class DeviceDecoder(_DeviceCoder):
     """Reusable decoder for up to max_blocks blocks resident in HBM.  element_size > 1: the streams are of the byte-plane
     layout (DeviceEncoder(..., element_size)) and decode(..., length) gives back the original bytes.  filter="delta": the
-    streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size.  base: the uint8 device
+    streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size; filter="zigzag": the same
+    for the delta filter with folded differences (include/redux_hip.h, "zigzag-folded delta filter").  base: the uint8 device
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
     streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags))."""
 
@@ -1356,7 +1370,8 @@ class DeviceDecoder(_DeviceCoder):
             if ws_bytes == 0:
                 raise Unsupported()
         elif self.delta:
-            self._decode_dev, self._lead, ws_bytes = L.redux_decode_delta_dev, (), self._layout_ws_bytes(self.max_in_len)
+            self._decode_dev = L.redux_decode_zigzag_dev if _zigzag(self.delta) else L.redux_decode_delta_dev
+            self._lead, ws_bytes = (), self._layout_ws_bytes(self.max_in_len)
         elif self.base is not None:
             self._decode_dev, self._lead, self._takes_base = L.redux_decode_base_dev, (), True
             ws_bytes = self._layout_ws_bytes(self.max_in_len)
@@ -1792,6 +1807,12 @@ def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The delta filter followed by the byte-plane layout (include/redux_hip.h, "delta filter") of a uint8 device tensor,
     or their inverse: redux_delta_planes_dev on torch's current stream.  out: as for planes()."""
     return _transform("redux_delta_planes_dev", d_src, element_size, block_size, inverse, out)
+
+
+def zigzag_planes(d_src, element_size, block_size, inverse=False, out=None):
+    """The zigzag-folded delta filter followed by the byte-plane layout (include/redux_hip.h, "zigzag-folded delta filter")
+    of a uint8 device tensor, or their inverse: redux_zigzag_planes_dev on torch's current stream.  out: as for planes()."""
+    return _transform("redux_zigzag_planes_dev", d_src, element_size, block_size, inverse, out)
 
 
 def _device_unit_table(torch, table, nunits, device):

@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -49,6 +49,12 @@ little-endian unsigned elements instead of the elements, frame by frame of the b
 for integer series whose values are large but close to their neighbours -- timestamps, sorted indices, offsets, counters,
 sampled signals.  Floating-point data and text get larger with it, so only `--layout auto` chooses it for you.  -d reads it
 from the container.  `--filter` with `--block-size 0`, `--stored` or a `--model` other than adaptive is a usage error.
+`--filter zigzag` (the rules of `--filter delta`; `--checksum` is allowed) folds every difference so that small magnitudes
+of either sign become small unsigned numbers (container version 11): for signed series that move both ways -- sampled
+signals, random walks, offsets that go back and forth -- whose small negative differences would otherwise put 0xFF into
+every upper byte plane; an int64 signal comes out at about half the size of `--filter delta`, a monotone series at the
+same size.  `--layout auto` does not choose it.  -d and -d `--range` read version 11 with no flag.  With `--block-size 0`,
+`--stored`, `--base`, `--skip-constant`, `--layout` or a `--model` other than adaptive it is a usage error.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -88,7 +94,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>]")
+         "[--filter <delta|zigzag>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>]")
 
 
 def parse(argv):
@@ -122,7 +128,7 @@ def parse(argv):
                     return None
                 opts["model"] = val
             elif arg == "--filter":
-                if val != "delta":
+                if val not in ("delta", "zigzag"):
                     return None
                 opts["filter"] = val
             elif arg == "--base":

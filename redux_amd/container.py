@@ -10,7 +10,7 @@ Layout (little-endian):
            5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
            layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
-           per unit of 8 blocks)
+           per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -18,7 +18,7 @@ Layout (little-endian):
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
            0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
            version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
-           0xA0000000
+           0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
    (version 8, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
@@ -88,7 +88,13 @@ byte above 7 is InvalidInput, a truncated table Eof.  The marker nibble 0xA of t
 version's word carries it.  It has no stored blocks (no 0x4A / 0x5A).  Without layout="mixed" the writers emit exactly the
 bytes they emitted before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x1A: versions 1 to 10 with checksums) means a table of nblocks
+Version 11 holds streams of the adaptive coder behind the zigzag-folded delta filter for signed series (include/redux_hip.h,
+"zigzag-folded delta filter"): version 6 with every difference folded, the same sections, and decoding undoes layout, fold
+and filter.  The word at offset 12 is 0xB0000000 | E: no other version takes that word, and version 11 takes no other.  It
+has no stored blocks (no 0x4B / 0x5B).  Without filter="zigzag" the writers emit exactly the bytes they emitted before the
+version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1B: versions 1 to 11 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -120,6 +126,8 @@ VERSION_CONTEXT_STATIC = 7
 VERSION_BASE = 8
 VERSION_CONST = 9
 VERSION_MIXED = 10
+VERSION_ZIGZAG = 11
+ZIGZAG_MARK = 0xB0000000  # version 11's word at offset 12: ZIGZAG_MARK | E
 MIXED_MARK = 0xA0000000  # version 10's word at offset 12
 MIXED_UNIT_BLOCKS = 8  # blocks of a unit of the mixed layouts (REDUX_MIXED_UNIT_BLOCKS)
 CONST_MARK = 0x90000000  # version 9's word at offset 12: CONST_MARK | F << 4 | E, F = 1 with a base record
@@ -156,6 +164,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     block_crc: nblocks CRC-32 values of the uncompressed blocks (the version gets flag 0x10); None: no table.
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
     filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored).
+    filter "zigzag": streams of compress_blocks(..., filter="zigzag") (version 11, as version 6).
     base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
     zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter).
     constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
@@ -197,7 +206,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         params.check(len(sizes))  # (the table count against this many blocks)
         ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
     if delta:
-        ver, res = VERSION_DELTA, DELTA_MARK | element_size
+        ver, res = (VERSION_ZIGZAG, ZIGZAG_MARK | element_size) if api._zigzag(delta) else (VERSION_DELTA, DELTA_MARK | element_size)
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if xbase:
@@ -301,13 +310,15 @@ def _version_ok(ver, res):
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
         or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK)
+        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK) \
+        or (layout == VERSION_ZIGZAG and not ver & STORED_FLAG and res >> 28 == 0xB and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
 # or the PlaneStaticModel of version 4's tables;
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
-# of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, else None.
+# of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, "zigzag"
+# for version 11, else None.
 # base: (base_used, crc) of the record of version 8, or of version 9 with F = 1, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
 # None, as the table holds it unit by unit.
@@ -327,7 +338,7 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST, VERSION_ZIGZAG) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -416,7 +427,7 @@ def _parse_index(b):
             raise api.InvalidInput()
         E = None
     return _Container(P, block_size, total, E, static, offsets, None, crcs, stored,
-                      "delta" if _layout(ver) == VERSION_DELTA else None, base, constant, units), at
+                      {VERSION_DELTA: "delta", VERSION_ZIGZAG: "zigzag"}.get(_layout(ver)), base, constant, units), at
 
 
 def _parse(buf):
@@ -453,8 +464,8 @@ def element_size(buf):
 
 
 def filter(buf):
-    """"delta" for a version 6 container (the delta filter for integer series), None for every other version (version 10
-    records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
+    """"delta" for a version 6 container (the delta filter for integer series), "zigzag" for a version 11 container (the same
+    with folded differences), None for every other version (version 10 records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).filter
 
 
@@ -522,8 +533,8 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
-    because only the tables of contexts that occur are recorded.  filter "delta" (adaptive model, not stored): version 6,
-    which records the filter in the header's reserved word and adds no bytes.  mixed (adaptive model, element size 1, no
+    because only the tables of contexts that occur are recorded.  filter "delta" or "zigzag" (adaptive model, not stored):
+    version 6 or 11, which record the filter in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
     filter, not stored): version 10, whose unit table adds a byte per 8 blocks."""
     if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)):
         raise api.InvalidInput()
@@ -592,6 +603,7 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     64 * element_size; None: api.default_segment_blocks), built from each range as it is coded, version 5.
     filter "delta" (element_size 1 / 2 / 4 / 8, model "adaptive", not stored): the delta filter for integer series in front of
     the layout, version 6.
+    filter "zigzag" (as "delta"): the delta filter with its differences folded, for series that move both ways, version 11.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
@@ -760,7 +772,7 @@ class Reader:
     not, CONTEXT_TABLES_MAX bytes are read and then parsed) and later only the streams of covered blocks: the payload of
     blocks no range covers is never read, so damage there -- a truncated file included -- does not matter to a range read.
     base: as for decompress_bytes; it is checked against the container's record here, once.
-    total, block_size, nblocks, version, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
+    total, block_size, nblocks, version, filter, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
     the source so far."""
 
     def __init__(self, source, base=None):
@@ -786,6 +798,7 @@ class Reader:
         self._c, self.payload_offset = _parse_index(memoryview(index))
         c = self._c
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
+        self.filter = c.filter
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
             else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
         self._base = _checked_base(c, base)

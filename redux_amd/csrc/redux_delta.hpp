@@ -323,9 +323,10 @@ __global__ void __launch_bounds__(256) k_delta_planes_bytes(PlanesArgs a)
 // The inverse of the byte path: the workgroup walks the frame of L bytes at `base`, 256 elements per iteration, one per
 // lane, summed in 64 bits (congruent mod 2^(8E)) by a wave scan and the wave totals in LDS; a plain layout skips the sum.
 // E, delta and L are uniform over the workgroup.  The rows of wtot alternate from one barrier to the next, across frames
-// too (row), so one barrier per iteration orders them.
+// too (row), so one barrier per iteration orders them.  fold (with delta): the elements are unfolded first
+// (redux_zigzag.hpp), sign-extended to 64 bits, which is congruent too; a lane past the frame's end keeps its 0.
 __device__ __forceinline__ void bytes_inverse_frame(const uint8_t *src, uint8_t *dst, uint64_t base, uint64_t L, uint32_t E, bool delta,
-                                                    uint64_t (*wtot)[4], uint32_t &row)
+                                                    uint64_t (*wtot)[4], uint32_t &row, bool fold = false)
 {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t n = L / E;
@@ -338,6 +339,8 @@ __device__ __forceinline__ void bytes_inverse_frame(const uint8_t *src, uint8_t 
         if (i < n)
             for (uint32_t q = 0; q < E; q++)
                 d |= (uint64_t)src[base + (uint64_t)q * n + i] << (8 * q);
+        if (fold)
+            d = d >> 1 ^ (0 - (d & 1));
         uint64_t x = d;
         if (delta) {
             row ^= 1;

@@ -13,6 +13,7 @@
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
+//   redux_zigzag.hpp   k_zigzag_planes / k_zigzag_unplanes: the delta filter with folded differences, for signed series
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
@@ -43,6 +44,7 @@
 #include "redux_static.hpp"
 #include "redux_planes.hpp"
 #include "redux_delta.hpp"
+#include "redux_zigzag.hpp"
 #include "redux_base.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
@@ -527,7 +529,7 @@ static host::EncodeCoder static_encoder(const redux_params *p, const uint32_t *c
             }};
 }
 
-// ---- the transforms in front of a coder (redux_planes.hpp, redux_delta.hpp, redux_base.hpp, redux_mixed.hpp) ------------
+// ---- the transforms in front of a coder (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_base.hpp, redux_mixed.hpp)
 // The split every transform launch makes: the fast kernel takes the `nfull` whole granules (a frame of E*B bytes, a unit of
 // 8*B) of len bytes when the block size and every pointer are 16-byte multiples, and none otherwise; a byte kernel takes
 // everything from byte `rest` on.
@@ -618,6 +620,32 @@ static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t b
     return REDUX_OK;
 }
 
+// the zigzag-folded delta filter: launch_delta's shape with the kernels of redux_zigzag.hpp
+template <int E>
+static int launch_zigzag(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
+{
+    const uint64_t   frame = (uint64_t)E * block_size;
+    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
+    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
+    if (f.nfull) {
+        uint32_t grid;
+        if (inverse)
+            k_zigzag_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a);
+        else if (!grid_tiles((a.groups + 255) / 256, &grid))
+            return REDUX_UNSUPPORTED;
+        else
+            k_zigzag_planes<E><<<grid, 256, 0, s>>>(a);
+    }
+    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
+        if (inverse)
+            k_zigzag_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
+        else
+            k_zigzag_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
 // the base filter: the fused kernels take the full frames that lie inside the base, one workgroup per 256 groups; the byte
 // kernels take the rest up to the end of the frame the base ends in (or of the input); whole frames past the base have
 // nothing to XOR and go to the layout alone (launch_planes)
@@ -676,9 +704,12 @@ static int for_element_size(uint32_t element_size, F &&f)
     }
 }
 
-// redux_planes_dev, redux_delta_planes_dev and redux_base_planes_dev: the checks, then the transform's launch for the
-// element size.  base: the XOR-against-base filter with d_base[0 .. base_len) (not together with delta).
-static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev and redux_base_planes_dev: the checks, then the
+// transform's launch for the element size.  delta: kNoDelta, kDelta or kZigzag (false / true: the first two).  base: the
+// XOR-against-base filter with d_base[0 .. base_len) (not together with delta).
+enum { kNoDelta = 0, kDelta = 1, kZigzag = 2 };
+
+static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
                          int inverse, void *stream, bool base = false, const void *d_base = nullptr, uint64_t base_len = 0)
 {
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
@@ -698,6 +729,8 @@ static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t le
         constexpr int E = decltype(e)::value;
         if (base)
             return launch_base<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        if (delta == kZigzag)
+            return launch_zigzag<E>(d_src, d_dst, len, block_size, inv, s);
         if (delta)
             return launch_delta<E>(d_src, d_dst, len, block_size, inv, s);
         if constexpr (E == 1) { // the layout of single bytes is the identity
@@ -711,24 +744,26 @@ static int transform_dev(bool delta, const void *d_src, void *d_dst, uint64_t le
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
 // What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with the delta filter
-// or the XOR-against-base filter in front of it, or neither.  The layout of single bytes is the identity; a filter over
-// single bytes is not.
+// (its differences folded or not) or the XOR-against-base filter in front of it, or neither.  The layout of single bytes
+// is the identity; a filter over single bytes is not.
 struct Layout {
     uint32_t    E;
     bool        delta;
     bool        xor_base = false;   // the base filter, with d_base[0 .. base_len) on the device (not together with delta)
     const void *d_base   = nullptr;
     uint64_t    base_len = 0;
+    bool        fold     = false;   // with delta: the zigzag fold of the differences (redux_zigzag.hpp)
+    int         filter() const { return delta ? (fold ? kZigzag : kDelta) : kNoDelta; }
     bool        identity() const { return !delta && !xor_base && E == 1; }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(delta, d_src, d_dst, len, block_size, E, 0, stream, xor_base, d_base, base_len);
+        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 0, stream, xor_base, d_base, base_len);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(delta, d_src, d_dst, len, block_size, E, 1, stream, xor_base, d_base, base_len);
+        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 1, stream, xor_base, d_base, base_len);
     }
 };
 
@@ -2447,6 +2482,71 @@ int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const ui
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
                               block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, true}), block_crc);
+}
+
+// ---- zigzag-folded delta filter (redux_zigzag.hpp) -------------------------------------------------
+static Layout zigzag_layout(uint32_t element_size) { return Layout{element_size, true, false, nullptr, 0, true}; }
+
+int redux_zigzag_check(uint32_t element_size) { return redux_planes_check(element_size); }
+
+int redux_zigzag_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                            void *stream)
+{
+    return transform_dev(kZigzag, d_src, d_dst, len, block_size, element_size, inverse, stream);
+}
+
+// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
+uint64_t redux_encode_zigzag_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    if (redux_zigzag_check(element_size) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    return ws ? zigzag_layout(element_size).copy_bytes(in_len) + ws : 0;
+}
+
+uint64_t redux_decode_zigzag_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+// (as for delta: a frame's running sum never leaves the frame, so the inverse writes d_out[0 .. out_len) and nothing else)
+int redux_encode_zigzag_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(zigzag_layout(element_size), p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
+                             d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_zigzag_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(zigzag_layout(element_size), p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_zigzag(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_zigzag_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               layout_encoder(p, block_size, zigzag_layout(element_size)), block_crc); // redux_host.hpp
+}
+
+int redux_decode_blocks_zigzag(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                               uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && redux_zigzag_check(element_size) != REDUX_OK)
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, layout_decoder(p, block_size, zigzag_layout(element_size)), block_crc);
 }
 
 // ---- XOR-against-base filter (redux_base.hpp) ------------------------------------------------------

@@ -1,5 +1,5 @@
 // redux_planes.hpp -- the byte-plane layout of typed data ("shuffle" filter), a byte transform in front of the coder, and
-// the pieces every layout transform is put together from (redux_delta.hpp, redux_base.hpp, redux_mixed.hpp).
+// the pieces every layout transform is put together from (redux_delta.hpp, redux_zigzag.hpp, redux_base.hpp, redux_mixed.hpp).
 //
 //   k_planes<E, INVERSE>        full frames: the forward tile / the plain inverse tile, one row of 256 groups per workgroup
 //   k_planes_bytes<E, INVERSE>  one byte per thread under the frame index rule: the short last frame, unaligned buffers,
@@ -146,7 +146,7 @@ __device__ __forceinline__ void plane_store(uint8_t *fbase, uint32_t block_size,
 
 // What a filter on the elements does in the forward tile: `before` runs ahead of the barrier and its result crosses it,
 // `apply` works on the lane's 16 elements in front of the permutation.  This one is no filter; DeltaForward
-// (redux_delta.hpp) is the other.
+// (redux_delta.hpp) and ZigzagForward (redux_zigzag.hpp) are the others.
 template <int E>
 struct PlainForward {
     struct Pred {};
@@ -243,9 +243,10 @@ __device__ __forceinline__ uint64_t frame_src(const FramePos &p, uint32_t E)
 }
 
 // Forward with or without the differences, for the thread of source byte o: the thread of an element's first byte does
-// the element, the threads of a frame's trailing bytes copy them.
+// the element, the threads of a frame's trailing bytes copy them.  fold (with delta): the zigzag fold of the difference
+// (redux_zigzag.hpp).
 __device__ __forceinline__ void bytes_forward(const uint8_t *src, uint8_t *dst, uint64_t o, uint64_t len, uint32_t E, uint32_t block_size,
-                                              bool delta)
+                                              bool delta, bool fold = false)
 {
     const FramePos f = frame_pos(o, len, E, block_size);
     if (f.r >= f.n * E) {
@@ -261,7 +262,9 @@ __device__ __forceinline__ void bytes_forward(const uint8_t *src, uint8_t *dst, 
         if (delta && i)
             p |= (uint64_t)src[o - E + q] << (8 * q);
     }
-    const uint64_t d = x - p;
+    uint64_t d = x - p;
+    if (fold) // (the bits above the element's 8*E are dropped below)
+        d = d << 1 ^ (0 - (d >> (8 * E - 1) & 1));
     for (uint32_t q = 0; q < E; q++)
         dst[f.base + (uint64_t)q * f.n + i] = (uint8_t)(d >> (8 * q));
 }

@@ -14,6 +14,7 @@
 //   redux::hip::compress_blocks_v / decompress_blocks_v     many independent inputs in one launch (tests/corpora.rs:32-85)
 //   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
+//   redux::hip::compress_blocks_zigzag / decompress_blocks_zigzag   signed series behind the zigzag-folded delta filter
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
 //   redux::hip::compress_blocks_const / decompress_blocks_const     constant blocks skipped, with or without a base
@@ -239,6 +240,45 @@ inline std::vector<std::uint8_t> decompress_blocks_delta(const Blocks &streams, 
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_delta(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
                                     sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// Signed series behind the zigzag-folded delta filter (include/redux_hip.h, "zigzag-folded delta filter"): compress_blocks_delta
+// with every difference folded, so that small differences of either sign leave the upper byte planes zero.
+inline Blocks compress_blocks_zigzag(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                     const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_zigzag(&cp, in, len, block_size, element_size, b.data.data(), b.data.size(), b.offsets.data(), nullptr,
+                                     nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_zigzag(const Blocks &streams, std::uint64_t len, std::uint32_t block_size,
+                                                          std::uint32_t element_size, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_zigzag(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
+                                     sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }

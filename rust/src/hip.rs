@@ -64,6 +64,13 @@ extern "C" {
     fn redux_decode_blocks_delta(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                  block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
                                  block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // zigzag-folded delta filter for signed series: the delta calls' shape
+    fn redux_encode_blocks_zigzag(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                  out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32,
+                                  block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_zigzag(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                  block_size: u32, element_size: u32, out: *mut u8, out_sizes: *mut u32,
+                                  block_status: *mut i32, block_crc: *mut u32) -> c_int;
     // XOR-against-base filter for series of snapshots, in front of the byte-plane layout (base null only with base_len 0;
     // block_crc may be null)
     fn redux_encode_blocks_base(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
@@ -379,6 +386,48 @@ pub fn decompress_blocks_delta(streams: &[u8], offsets: &[u64], len: u64, block_
         let mut sizes = vec![0u32; nb];
         try!(status(redux_decode_blocks_delta(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size,
                                               out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks_delta` with every difference zigzag-folded (include/redux_hip.h, "zigzag-folded delta filter"): for
+/// series that move both ways, whose small negative differences would otherwise fill the upper byte planes with 0xFF.
+pub fn compress_blocks_zigzag(data: &[u8], block_size: u32, element_size: u32, p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_zigzag(&cp, data.as_ptr(), data.len() as u64, block_size, element_size,
+                                               out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_zigzag`: `len` is the original byte count; returns the original bytes.
+pub fn decompress_blocks_zigzag(streams: &[u8], offsets: &[u64], len: u64, block_size: u32, element_size: u32,
+                                p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_zigzag(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size,
+                                               out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
