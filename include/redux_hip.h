@@ -517,6 +517,55 @@ int redux_decode_blocks_base(const redux_params *p, const uint8_t *in, const uin
                              uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
                              uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- folded difference against a base ------------------------------------------------------------
+ * A second operation for the base filter above, next to XOR and as opt-in as it is.  XOR is large where the input and the
+ * base lie on opposite sides of a carry: 0x3F7FFFFF against 0x3F800000 differ by 1 and XOR to 0x00FFFFFF.  The difference
+ * of the elements is small whenever the two are close as numbers, and the zigzag fold above takes away what spoke against
+ * it, the 0xFF a small negative difference puts into every upper byte.  E, B, the frames and the byte-plane layout are as
+ * above; x = the input, len bytes; y = the base, base_len bytes, any length; U = min(len, base_len), y'[i] = y[i] for i < U
+ * and 0 beyond.
+ *   - An element -- one of the N = L / E little-endian words of a frame of L bytes, counted from the frame's start -- is
+ *     COVERED when all E of its bytes lie below U.  A covered element becomes z = (d << 1) ^ (0 - (d >> (8E-1))) mod 2^(8E)
+ *     with d = x - y mod 2^(8E): read as signed, d >= 0 maps to 2d and d < 0 to -2d - 1.
+ *   - Every other byte is x ^ y': an element the base ends inside, the L - N*E trailing bytes of a frame, everything past
+ *     the base (which stays as it is).
+ *   - The byte-plane layout is then applied (E = 1: no layout; the filter over single bytes, fold(x - y mod 256), remains).
+ *   - The inverse undoes the layout, unfolds the covered elements with d = (z >> 1) ^ (0 - (z & 1)) and adds y; the other
+ *     bytes are XORed with y' again.
+ * x == y still gives all-zero coder input, whole frames past the base see the layout alone, and the rule is local to a frame
+ * and to a prefix of the base: blocks and frames stay as independent as the layout leaves them, and a chunk of the host
+ * calls works on its own share of the base.  The fold is a bijection, so any input round-trips.  Behind the transform is the
+ * plain adaptive coder:
+ *     stream_base_sub_E(x, y)[b] == redux_encode_blocks(planes_E(sub_E(x, y')))[b].
+ * Not available with the static-table models, stored blocks, the delta filters, constant blocks, the mixed layouts, the `_v`
+ * calls and redux_compress / redux_decompress.
+ *
+ * Every call has the signature of its base namesake and keeps its promises: redux_base_sub_planes_dev is two reads and one
+ * write, and d_dst must overlap neither d_src nor the bytes of d_base that are read (INVALID_INPUT);
+ * redux_decode_base_sub_dev writes no byte outside d_out[0 .. out_len), for damaged streams too, and every frame whose
+ * blocks are all OK holds the original bytes; the output of the host-pointer pair depends on neither the chunk size nor the
+ * devices, and block_crc is over the ORIGINAL bytes.  The workspaces are the base calls'.
+ */
+int      redux_base_sub_check(uint32_t element_size);
+int      redux_base_sub_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len,
+                                   uint32_t block_size, uint32_t element_size, int inverse, void *stream);
+uint64_t redux_encode_base_sub_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_base_sub_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_base_sub_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                              uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap,
+                              void *d_out_offsets /* u64[nblocks+1] */, void *d_block_status /* i32[nblocks] */,
+                              void *d_summary /* i32[2] */, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_base_sub_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */,
+                              const void *d_base, uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                              void *d_out, void *d_out_sizes /* u32[nblocks] */, void *d_block_status, void *d_summary,
+                              void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_base_sub(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                                 uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                 int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_base_sub(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                                 uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                                 uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* ---- stored blocks -----------------------------------------------------------------------------
  * A block whose stream does not shrink it can travel as its raw bytes instead (zstd raw blocks, deflate stored blocks).
  * Block b has L_b = min(B, len - b*B) bytes of coder input x' (the input for element_size 1, its byte-plane layout for

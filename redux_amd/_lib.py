@@ -199,6 +199,14 @@ SIGNATURES = {
     "redux_decode_base_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
     "redux_encode_blocks_base": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_base": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
+    "redux_base_sub_check": (C.c_int, [_U32]),
+    "redux_base_sub_planes_dev": (C.c_int, [_V, _V, _U64, _V, _U64, _U32, _U32, C.c_int, _V]),
+    "redux_encode_base_sub_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_base_sub_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_base_sub_dev": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_base_sub_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_base_sub": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_base_sub": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_const_blocks_dev": (C.c_int, [_V, _U64, _U32, _V, _V]),
     "redux_encode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
     "redux_decode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),

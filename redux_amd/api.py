@@ -534,6 +534,18 @@ def _check_base(base, allowed=True):
     return True
 
 
+def _check_base_op(base_op, base, constant=None):
+    """base_op="xor" (the default) or "sub": what the base filter does with the base, the bytewise XOR or the folded
+    difference of the elements (include/redux_hip.h, "folded difference against a base").  Any other value, "sub" without
+    a base and "sub" with the constant-block option are InvalidInput.  A check on the arguments alone: it comes before any
+    call into the library.  -> True for "sub"."""
+    if not isinstance(base_op, str) or base_op not in ("xor", "sub"):
+        raise InvalidInput()
+    if base_op == "sub" and (base is None or not (constant is None or constant is False)):
+        raise InvalidInput()
+    return base_op == "sub"
+
+
 def _check_constant(constant, allowed=True):
     """constant=None / False, or the constant-block option (include/redux_hip.h, "constant blocks"): the option where it
     is not available (allowed false: a static model, stored blocks, the delta filter, the `_v` calls) is InvalidInput.  A
@@ -638,7 +650,8 @@ def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length
 
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
-                    store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None):
+                    store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None,
+                    base_op="xor"):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -672,7 +685,11 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     blocks.  True: every unit's layout is chosen on the device among `layouts` (None: all eight; else as layout_cost's) and the
     table, np.uint8[nunits], is returned as a fourth value.  A np.uint8[nunits]: the table is dictated; an entry above 7 is
     InvalidInput.  decompress_blocks(..., unit_layouts=table, length=) undoes it.  Adaptive model only, and with none of
-    element_size, filter=, stored=, base= or constant=."""
+    element_size, filter=, stored=, base= or constant=.
+    base_op: "xor" (the default), or "sub" with base=: the folded difference of the elements against the base in place of
+    the XOR (include/redux_hip.h, "folded difference against a base": redux_encode_blocks_base_sub);
+    decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=."""
+    sub = _check_base_op(base_op, base, constant)
     if unit_layouts is not None:
         _check_mixed(params, element_size, filter, stored, base, constant)
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
@@ -725,8 +742,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
                                          out.ctypes.data, cap, offs.ctypes.data, cptr, status.ctypes.data, crc)
     elif xbase:
         y = _u8(base)
-        st = L.redux_encode_blocks_base(C.byref(cp), _ptr(a), len(a), _ptr(y), len(y), block_size, E, out.ctypes.data, cap,
-                                        offs.ctypes.data, status.ctypes.data, crc)
+        encode = L.redux_encode_blocks_base_sub if sub else L.redux_encode_blocks_base
+        st = encode(C.byref(cp), _ptr(a), len(a), _ptr(y), len(y), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
+                    status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
@@ -760,7 +778,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None):
+                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, base_op="xor"):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -785,7 +803,9 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     same base= if one was given; length is required for every element_size, and out is the original bytes.  Adaptive model
     only, and not with stored= or filter=.
     unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
-    required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc."""
+    required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
+    base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub)."""
+    sub = _check_base_op(base_op, base, constant)
     if unit_layouts is not None:
         _check_mixed(params, element_size, filter, stored, base, constant)
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
@@ -836,8 +856,9 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
                                          length, block_size, E, out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
     elif xbase:
         y = _u8(base)
-        st = L.redux_decode_blocks_base(C.byref(cp), _ptr(a), offs.ctypes.data, _ptr(y), len(y), length, block_size, E,
-                                        out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
+        decode = L.redux_decode_blocks_base_sub if sub else L.redux_decode_blocks_base
+        st = decode(C.byref(cp), _ptr(a), offs.ctypes.data, _ptr(y), len(y), length, block_size, E, out.ctypes.data,
+                    sizes.ctypes.data, status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
@@ -1230,10 +1251,13 @@ class DeviceEncoder(_DeviceCoder):
     on torch's current stream.  base: a uint8 device tensor of any length, an earlier snapshot of the data: encode() codes the
     XOR against it (include/redux_hip.h, "XOR-against-base filter"); not together with filter=.  constant=True: blocks of
     the coder's input whose bytes are all equal skip the coder (include/redux_hip.h, "constant blocks"), with or without
-    base=, not together with filter=; encode() then returns the u8 flags as a fifth value."""
+    base=, not together with filter=; encode() then returns the u8 flags as a fifth value.  base_op="sub" with base=: the
+    folded difference of the elements against the base in place of the XOR (include/redux_hip.h, "folded difference against a
+    base"); not together with constant=True."""
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, layouts=None):
+                 mixed=False, layouts=None, base_op="xor"):
+        self.base_sub = _check_base_op(base_op, base, constant)
         self.mixed = bool(mixed)
         if self.mixed:  # (with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
             _check_mixed(params, element_size, filter, None, base, constant)
@@ -1268,7 +1292,8 @@ class DeviceEncoder(_DeviceCoder):
             ws_bytes, self._encode_dev = L.redux_encode_const_workspace_bytes, L.redux_encode_const_dev
             self._lead = (*_base_pair(self.base), B, E)
         elif self.base is not None:
-            ws_bytes, self._encode_dev = L.redux_encode_base_workspace_bytes, L.redux_encode_base_dev
+            ws_bytes, self._encode_dev = (L.redux_encode_base_sub_workspace_bytes, L.redux_encode_base_sub_dev) if self.base_sub \
+                else (L.redux_encode_base_workspace_bytes, L.redux_encode_base_dev)
             self._lead = (*_base_pair(self.base), B, E)
         else:  # (element size 1: the coder without a layout)
             ws_bytes = L.redux_encode_planes_workspace_bytes
@@ -1340,10 +1365,12 @@ class DeviceDecoder(_DeviceCoder):
     streams are DeviceEncoder(..., filter="delta")'s; decode needs the length for every element size; filter="zigzag": the same
     for the delta filter with folded differences (include/redux_hip.h, "zigzag-folded delta filter").  base: the uint8 device
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
-    streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags))."""
+    streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags)).
+    base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s."""
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False):
+                 mixed=False, base_op="xor"):
+        self.base_sub = _check_base_op(base_op, base, constant)
         self.mixed = bool(mixed)
         if self.mixed:  # (the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
             _check_mixed(params, element_size, filter, None, base, constant)
@@ -1373,7 +1400,8 @@ class DeviceDecoder(_DeviceCoder):
             self._decode_dev = L.redux_decode_zigzag_dev if _zigzag(self.delta) else L.redux_decode_delta_dev
             self._lead, ws_bytes = (), self._layout_ws_bytes(self.max_in_len)
         elif self.base is not None:
-            self._decode_dev, self._lead, self._takes_base = L.redux_decode_base_dev, (), True
+            self._decode_dev = L.redux_decode_base_sub_dev if self.base_sub else L.redux_decode_base_dev
+            self._lead, self._takes_base = (), True
             ws_bytes = self._layout_ws_bytes(self.max_in_len)
         else:  # (element size 1: decode() without a length needs less, and the first one with a length regrows it)
             self._decode_dev, self._lead = L.redux_decode_planes_dev, ()
@@ -1861,6 +1889,13 @@ def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None
     return _transform("redux_base_planes_dev", d_src, element_size, block_size, inverse, out, d_base)
 
 
+def base_sub_planes(d_src, d_base, element_size, block_size, inverse=False, out=None):
+    """The folded difference against d_base followed by the byte-plane layout (include/redux_hip.h, "folded difference
+    against a base") of a uint8 device tensor, or their inverse: redux_base_sub_planes_dev on torch's current stream.
+    d_base and out: as for base_planes()."""
+    return _transform("redux_base_sub_planes_dev", d_src, element_size, block_size, inverse, out, d_base)
+
+
 def constant_blocks(data, block_size):
     """The constant-block flags (include/redux_hip.h, "constant blocks") of every block of block_size bytes of `data`:
     1 where the block has at least one byte and all its bytes are equal, else 0.  A uint8 device tensor: redux_const_blocks_dev
@@ -2097,8 +2132,36 @@ def _estimate(data, block_size, params, element_size, segment_blocks, models):
     return out, context_cums
 
 
+BASE_OPS = ("xor", "sub")  # what the base filter does with the base; ties go to the earlier
+
+
+def estimate_base_ops(data, base, block_size, params=(8, 30, 32), element_size=1):
+    """-> {"xor": bytes, "sub": bytes}: the estimated payload of the adaptive coder behind each operation of the base filter
+    (include/redux_hip.h, "XOR-against-base filter" and "folded difference against a base").  Each transform runs into one
+    scratch tensor (base_planes, base_sub_planes) and block_cost's kernel reads it; nothing is coded."""
+    P = _params_of(params)
+    E = _check_element_size(element_size)
+    if base is None or not isinstance(block_size, (int, np.integer)) or not 0 < block_size < 1 << 32:
+        raise InvalidInput()
+    B = int(block_size)
+    torch = _torch()
+    L = _lib.lib()
+    cp = P._c()
+    d = _device_u8(torch, data)
+    out = {}
+    with torch.cuda.device(d.device):
+        d_y = _device_u8(torch, base).to(d.device)
+        t = torch.empty_like(d)
+        nb = L.redux_block_count(d.numel(), B)
+        for op, transform in zip(BASE_OPS, (base_planes, base_sub_planes)):
+            if d.numel():
+                transform(d, d_y, E, B, out=t)
+            out[op] = int(np.ceil(float(_device_block_cost(torch, L, cp, t, B).sum().item()) / 8 + TERMINATION_BYTES * nb))
+    return out
+
+
 # ---- layout estimates (include/redux_hip.h, "layout estimates") -----------------------------------
-LAYOUTS = tuple((E, f) for f in (None, "delta") for E in (1, 2, 4, 8))  # layout k = 4 F + log2 E; ties go to the earlier
+LAYOUTS =tuple((E, f) for f in (None, "delta") for E in (1, 2, 4, 8))  # layout k = 4 F + log2 E; ties go to the earlier
 
 
 def layout_index(element_size, filter=None):

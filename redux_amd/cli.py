@@ -4,7 +4,7 @@
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
                             [--filter delta|zigzag] [--base <base file>] [--skip-constant] [--layout auto|mixed]
-                            [--range START:LENGTH]
+                            [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
 2 cannot open a file, 3 coding error) and the same summary line on stderr (main.rs:112,117).
@@ -62,6 +62,15 @@ CRC-32).  A base of another length is fine: what lies past its end is coded as i
 base of a version 8 container: a missing, different or too short base, and a base given for any other input, is a
 decompression error (exit 3).  With -c, `--base` with `--block-size 0`, `--stored`, `--filter` or any `--model` other than
 adaptive (auto included: the base is never chosen for you) is a usage error; a base file that cannot be opened is exit 2.
+`--base-op sub` (with -c and `--base`, so a block size, any `--element-size` and the adaptive model; `--checksum` is
+allowed) codes the folded difference of the little-endian elements against the base in place of the XOR (container version
+12, with version 8's base record): small where the input and the base are close as numbers, also across a carry, where XOR is
+not.  On synthetic fp32 pairs it comes out 4 to 6 % below XOR, on bf16 pairs 7 to 18 %, on unrelated pairs under 1 % above
+(no real checkpoint series was measured).  `--base-op auto` estimates the payload behind both operations on the
+GPU, without coding, and codes with the smaller (a tie goes to XOR); the output is that operation's container, version 8 or
+12.  `--base-op xor` is the default.  -d and -d `--range` read version 12 with `--base FILE` and no other flag.  `--base-op`
+with -d, without `--base` or with anything `--base` refuses is a usage error, and so is `--base-op sub` or `auto` with
+`--skip-constant`.
 `--skip-constant` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` and `--base` are allowed)
 leaves every block of the coder's input whose bytes are all equal out of the coder: it travels as one byte (container
 version 9) and is rebuilt by a fill.  Behind `--base` that is every unchanged region of a snapshot.  -d reads version 9
@@ -94,7 +103,8 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>]")
+         "[--filter <delta|zigzag>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--base-op <xor|sub|auto>]")
 
 
 def parse(argv):
@@ -111,7 +121,8 @@ def parse(argv):
             opts["compress"] = False
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
-        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range"):
+        elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range",
+                     "--base-op"):
             val = next(it, None)
             if val is None:
                 return None
@@ -133,6 +144,10 @@ def parse(argv):
                 opts["filter"] = val
             elif arg == "--base":
                 opts["base"] = val
+            elif arg == "--base-op":
+                if val not in ("xor", "sub", "auto"):
+                    return None
+                opts["base_op"] = val
             elif arg == "--range":
                 start, colon, length = val.partition(":")
                 if not colon or not (start.isascii() and start.isdigit() and length.isascii() and length.isdigit()):
@@ -180,6 +195,8 @@ def parse(argv):
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):
         return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only
+    if "base_op" in opts and (not opts["compress"] or "base" not in opts or (opts["base_op"] != "xor" and opts.get("skip_constant"))):
+        return None  # the operation is recorded as the container's version, and constant blocks go behind the XOR alone
     if opts.get("skip_constant") and (not opts["compress"] or opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                       or opts.get("model", "adaptive") != "adaptive"):
         return None  # the bitmap lives in the container, and only the adaptive coder has the table form in both directions
@@ -234,7 +251,7 @@ def main(argv=None):
                                                 opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
                                                 opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
-                                                opts.get("skip_constant", False), opts.get("layout"))
+                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("base_op", "xor"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -10,7 +10,8 @@ Layout (little-endian):
            5 = segment-static: static tables per block range; 6 = delta filter in front of the byte-plane layout;
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
            layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
-           per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout)
+           per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout; 12 = folded difference
+           against a base in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -18,10 +19,10 @@ Layout (little-endian):
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
            0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
            version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
-           0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8
+           0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8; version 12: 0xC0000000 | E with E one of 1, 2, 4, 8
    16   8  nblocks
    24   8  total uncompressed length
-   (version 8, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
+   (versions 8 and 12, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
@@ -94,7 +95,13 @@ and filter.  The word at offset 12 is 0xB0000000 | E: no other version takes tha
 has no stored blocks (no 0x4B / 0x5B).  Without filter="zigzag" the writers emit exactly the bytes they emitted before the
 version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x1B: versions 1 to 11 with checksums) means a table of nblocks
+Version 12 holds streams of the adaptive coder behind the folded difference against a base (include/redux_hip.h, "folded
+difference against a base"): version 8 with the other operation of the base filter, the same sections, base record included,
+and the same checks of the base before any GPU call.  The word at offset 12 is 0xC0000000 | E: no other version takes that
+word, and version 12 takes no other.  It has no stored blocks (no 0x4C / 0x5C).  Without base_op="sub" (or "auto") the writers
+emit exactly the bytes they emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1C: versions 1 to 12 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -127,6 +134,8 @@ VERSION_BASE = 8
 VERSION_CONST = 9
 VERSION_MIXED = 10
 VERSION_ZIGZAG = 11
+VERSION_BASE_SUB = 12
+BASE_SUB_MARK = 0xC0000000  # version 12's word at offset 12: BASE_SUB_MARK | E
 ZIGZAG_MARK = 0xB0000000  # version 11's word at offset 12: ZIGZAG_MARK | E
 MIXED_MARK = 0xA0000000  # version 10's word at offset 12
 MIXED_UNIT_BLOCKS = 8  # blocks of a unit of the mixed layouts (REDUX_MIXED_UNIT_BLOCKS)
@@ -154,7 +163,7 @@ def _raw_lengths(nblocks, block_size, total):
 
 
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None, unit_layouts=None):
+         constant=None, unit_layouts=None, base_op="xor"):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -170,7 +179,10 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
     adaptive model, no stored, no filter); None: no bitmap.
     unit_layouts: the ceil(nblocks / 8) layouts, 0 .. 7, of compress_blocks(..., unit_layouts=) (version 10; adaptive model,
-    element_size 1 and none of stored, filter, base and constant); None: no unit table."""
+    element_size 1 and none of stored, filter, base and constant); None: no unit table.
+    base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
+    version 8)."""
+    sub = api._check_base_op(base_op, base, constant)
     mixed = unit_layouts is not None
     if mixed:
         api._check_mixed(params, element_size, filter, stored, base, constant)
@@ -210,7 +222,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if xbase:
-        ver, res = VERSION_BASE, BASE_MARK | element_size
+        ver, res = (VERSION_BASE_SUB, BASE_SUB_MARK | element_size) if sub else (VERSION_BASE, BASE_MARK | element_size)
     if const:
         ver, res = VERSION_CONST, CONST_MARK | (1 if xbase else 0) << 4 | element_size
     crc = b""
@@ -311,7 +323,8 @@ def _version_ok(ver, res):
         or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK) \
-        or (layout == VERSION_ZIGZAG and not ver & STORED_FLAG and res >> 28 == 0xB and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
+        or (layout == VERSION_ZIGZAG and not ver & STORED_FLAG and res >> 28 == 0xB and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
+        or (layout == VERSION_BASE_SUB and not ver & STORED_FLAG and res >> 28 == 0xC and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
@@ -319,11 +332,12 @@ def _version_ok(ver, res):
 # offsets uint64[nblocks+1]; payload the uint8 streams; crcs (flag 0x10) uint32[nblocks]; stored (flag 0x40) uint8[nblocks]
 # of 0 / 1.  static, crcs and stored are None where the container has no such section.  filter: "delta" for version 6, "zigzag"
 # for version 11, else None.
-# base: (base_used, crc) of the record of version 8, or of version 9 with F = 1, else None.  constant: uint8[nblocks] of 0 / 1
+# base: (base_used, crc) of the record of version 8 or 12, or of version 9 with F = 1, else None; base_op: "xor" or "sub" where
+# there is a record, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
 # None, as the table holds it unit by unit.
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
-                        " unit_layouts", defaults=(None,))
+                        " unit_layouts base_op", defaults=(None, None))
 
 
 def _header(b):
@@ -338,7 +352,7 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST, VERSION_ZIGZAG) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST, VERSION_ZIGZAG, VERSION_BASE_SUB) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -362,7 +376,7 @@ def _parse_index(b):
     ver, P, block_size, E, nblocks, total = _header(b)
     static = crcs = stored = base = constant = units = None
     at = HEADER.size
-    if _layout(ver) == VERSION_BASE or (_layout(ver) == VERSION_CONST and HEADER.unpack_from(b, 0)[6] & 0x10):
+    if _layout(ver) in (VERSION_BASE, VERSION_BASE_SUB) or (_layout(ver) == VERSION_CONST and HEADER.unpack_from(b, 0)[6] & 0x10):
         if len(b) < at + BASE_RECORD.size:
             raise api.Eof()
         base = BASE_RECORD.unpack_from(b, at)
@@ -427,7 +441,8 @@ def _parse_index(b):
             raise api.InvalidInput()
         E = None
     return _Container(P, block_size, total, E, static, offsets, None, crcs, stored,
-                      {VERSION_DELTA: "delta", VERSION_ZIGZAG: "zigzag"}.get(_layout(ver)), base, constant, units), at
+                      {VERSION_DELTA: "delta", VERSION_ZIGZAG: "zigzag"}.get(_layout(ver)), base, constant, units,
+                      None if base is None else "sub" if _layout(ver) == VERSION_BASE_SUB else "xor"), at
 
 
 def _parse(buf):
@@ -470,9 +485,16 @@ def filter(buf):
 
 
 def base(buf):
-    """(base_used, crc) of a version 8 container (the XOR-against-base filter): the bytes of the base the coder used and
-    the zlib.crc32 of them; None for versions 1 to 7.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    """(base_used, crc) of a version 8 container (the XOR-against-base filter), of a version 12 container (the folded
+    difference against a base) and of a version 9 container with a base: the bytes of the base the coder used and the
+    zlib.crc32 of them; None for every other container.  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).base
+
+
+def base_op(buf):
+    """What the base filter of a container did with the base: "xor" for version 8 and for version 9 with a base, "sub" for
+    version 12, None for every other container.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).base_op
 
 
 def constant(buf):
@@ -529,20 +551,24 @@ def header_is_wellformed(buf):
 
 
 def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False,
-                   filter=None, mixed=False):
+                   filter=None, mixed=False, base=False):
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
     because only the tables of contexts that occur are recorded.  filter "delta" or "zigzag" (adaptive model, not stored):
     version 6 or 11, which record the filter in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
-    filter, not stored): version 10, whose unit table adds a byte per 8 blocks."""
-    if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)):
+    filter, not stored): version 10, whose unit table adds a byte per 8 blocks.  base (adaptive model, no filter, not stored, not
+    mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation."""
+    if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)) \
+            or (base and (model != "adaptive" or stored or filter is not None or mixed)):
         raise api.InvalidInput()
     api._check_filter(filter, model == "adaptive" and not stored)
     E = api._check_element_size(element_size)
     n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
     if mixed:
         n += (nblocks + MIXED_UNIT_BLOCKS - 1) // MIXED_UNIT_BLOCKS
+    if base:
+        n += BASE_RECORD.size
     if model == "static":
         n += TABLE
     elif model == "plane-static":
@@ -591,8 +617,13 @@ def choose_layout(estimates):
     return min(estimates, key=lambda k: (estimates[k], LAYOUT_ORDER.index(k)))
 
 
+def choose_base_op(estimates):
+    """The operation of the base filter with the smaller estimate (api.estimate_base_ops); a tie goes to "xor"."""
+    return min(estimates, key=lambda op: (estimates[op], api.BASE_OPS.index(op)))
+
+
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None):
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, base_op="xor"):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -620,7 +651,12 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     decode.
     layout "mixed" (the exclusions of "auto"): a layout per unit of 8 blocks, chosen on the device by its estimated cost --
     among all eight when element_size is None, between plain and delta at that size when element_size is 1 / 2 / 4 / 8 --
-    version 10.  For files that hold several element types."""
+    version 10.  For files that hold several element types.
+    base_op (with base, not with skip_constant): "sub" codes the folded difference of the elements against the base in place
+    of the XOR, version 12.  "auto": the operation with the smaller estimated payload codes the data (choose_base_op; a tie
+    goes to "xor"), and the container is that operation's, version 8 or 12: nothing new to decode.  Related pairs favour
+    "sub", unrelated ones "xor", and a caller cannot know in advance."""
+    api._check_base_op("sub" if base_op == "auto" else base_op, base, skip_constant or None)  # ("auto": the refusals of "sub")
     if layout is not None:
         if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
                 or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
@@ -658,15 +694,17 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     if base is not None:
         base = api._u8(base)[: len(data)]  # (what the coder uses of it)
         record = (len(base), zlib.crc32(base))
+    if base_op == "auto":
+        base_op = choose_base_op(api.estimate_base_ops(data, base, block_size, params, element_size))
     cflags = np.zeros(nb, dtype=np.uint8) if skip_constant else None
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter,
-                                       base=base, constant=cflags)
+                                       base=base, constant=cflags, base_op=base_op)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record,
-                constant=cflags)
+                constant=cflags, base_op=base_op)
 
 
 def decompress_bytes(buf, base=None):
-    """container bytes -> original bytes.  base: the bytes a version 8 container, or a version 9 container with a base
+    """container bytes -> original bytes.  base: the bytes a version 8 or 12 container, or a version 9 container with a base
     record, was written against (at least its base_used bytes of them; more is fine), and None for every other container: a
     missing, short or different base, and a base given for a container without a record, are InvalidInput before anything is
     decoded."""
@@ -710,7 +748,8 @@ def _decode_parsed(c, base):
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
-                                                       stored=c.stored, filter=c.filter, base=base, constant=c.constant)
+                                                       stored=c.stored, filter=c.filter, base=base, constant=c.constant,
+                                                       base_op=c.base_op or "xor")
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
@@ -772,7 +811,7 @@ class Reader:
     not, CONTEXT_TABLES_MAX bytes are read and then parsed) and later only the streams of covered blocks: the payload of
     blocks no range covers is never read, so damage there -- a truncated file included -- does not matter to a range read.
     base: as for decompress_bytes; it is checked against the container's record here, once.
-    total, block_size, nblocks, version, filter, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
+    total, block_size, nblocks, version, filter, base_op, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
     the source so far."""
 
     def __init__(self, source, base=None):
@@ -781,7 +820,7 @@ class Reader:
         ver, P, _, E, nblocks, _ = _header(head)
         res = HEADER.unpack_from(head, 0)[6]
         layout = _layout(ver)
-        tables = BASE_RECORD.size if layout == VERSION_BASE or (layout == VERSION_CONST and res & 0x10) else 0
+        tables = BASE_RECORD.size if layout in (VERSION_BASE, VERSION_BASE_SUB) or (layout == VERSION_CONST and res & 0x10) else 0
         if layout == VERSION_STATIC:
             tables += TABLE
         elif layout == VERSION_PLANE_STATIC:
@@ -798,7 +837,7 @@ class Reader:
         self._c, self.payload_offset = _parse_index(memoryview(index))
         c = self._c
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
-        self.filter = c.filter
+        self.filter, self.base_op = c.filter, c.base_op
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
             else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
         self._base = _checked_base(c, base)

@@ -15,6 +15,7 @@
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
 //   redux_zigzag.hpp   k_zigzag_planes / k_zigzag_unplanes: the delta filter with folded differences, for signed series
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
+//   redux_base_sub.hpp k_base_sub_planes / k_base_sub_unplanes: the base filter's folded difference, the same bodies
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
@@ -46,6 +47,7 @@
 #include "redux_delta.hpp"
 #include "redux_zigzag.hpp"
 #include "redux_base.hpp"
+#include "redux_base_sub.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
 #include "redux_segment_static.hpp"
@@ -648,8 +650,10 @@ static int launch_zigzag(const void *d_src, void *d_dst, uint64_t len, uint32_t 
 
 // the base filter: the fused kernels take the full frames that lie inside the base, one workgroup per 256 groups; the byte
 // kernels take the rest up to the end of the frame the base ends in (or of the input); whole frames past the base have
-// nothing to XOR and go to the layout alone (launch_planes)
-template <int E>
+// nothing to XOR and go to the layout alone (launch_planes).  SUB: the folded difference (redux_base_sub.hpp) in place of
+// the XOR, with the same split: its fused kernels too may only take full frames that lie inside the base, where every
+// element is covered
+template <int E, bool SUB = false>
 static int launch_base(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
                        bool inverse, hipStream_t s)
 {
@@ -671,16 +675,25 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
         uint32_t grid;
         if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
-        if (inverse)
+        if (SUB && inverse)
+            k_base_sub_unplanes<E><<<grid, 256, 0, s>>>(a);
+        else if (SUB)
+            k_base_sub_planes<E><<<grid, 256, 0, s>>>(a);
+        else if (inverse)
             k_base_unplanes<E><<<grid, 256, 0, s>>>(a);
         else
             k_base_planes<E><<<grid, 256, 0, s>>>(a);
     }
     if (a.first < a.end) {
-        if (inverse)
-            k_base_unplanes_bytes<E><<<grid_bytes(a.end - a.first), 256, 0, s>>>(a);
+        const uint32_t grid = grid_bytes(a.end - a.first);
+        if (SUB && inverse)
+            k_base_sub_unplanes_bytes<E><<<grid, 256, 0, s>>>(a);
+        else if (SUB)
+            k_base_sub_planes_bytes<E><<<grid, 256, 0, s>>>(a);
+        else if (inverse)
+            k_base_unplanes_bytes<E><<<grid, 256, 0, s>>>(a);
         else
-            k_base_planes_bytes<E><<<grid_bytes(a.end - a.first), 256, 0, s>>>(a);
+            k_base_planes_bytes<E><<<grid, 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     if (a.end < len) { // (a.end is a whole number of frames here: the layout of the rest is the rest of the layout)
@@ -690,6 +703,13 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
             return launch_planes<E>(a.src + a.end, a.dst + a.end, len - a.end, block_size, inverse, s);
     }
     return REDUX_OK;
+}
+
+template <int E>
+static int launch_base_sub(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
+                           bool inverse, hipStream_t s)
+{
+    return launch_base<E, true>(d_src, d_base, base_len, d_dst, len, block_size, inverse, s);
 }
 
 // f(std::integral_constant<int, E>) for a checked element size (redux_planes_check)
@@ -704,13 +724,15 @@ static int for_element_size(uint32_t element_size, F &&f)
     }
 }
 
-// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev and redux_base_planes_dev: the checks, then the
-// transform's launch for the element size.  delta: kNoDelta, kDelta or kZigzag (false / true: the first two).  base: the
-// XOR-against-base filter with d_base[0 .. base_len) (not together with delta).
+// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev, redux_base_planes_dev and redux_base_sub_planes_dev:
+// the checks, then the transform's launch for the element size.  delta: kNoDelta, kDelta or kZigzag (false / true: the
+// first two).  base: kNoBase, kXorBase or kSubBase (false / true: the first two): the base filter with
+// d_base[0 .. base_len), XOR or the folded difference (not together with delta).
 enum { kNoDelta = 0, kDelta = 1, kZigzag = 2 };
+enum { kNoBase = 0, kXorBase = 1, kSubBase = 2 };
 
 static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
-                         int inverse, void *stream, bool base = false, const void *d_base = nullptr, uint64_t base_len = 0)
+                         int inverse, void *stream, int base = kNoBase, const void *d_base = nullptr, uint64_t base_len = 0)
 {
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
         return REDUX_INVALID_INPUT;
@@ -727,6 +749,8 @@ static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len
     const bool  inv = inverse != 0;
     return for_element_size(element_size, [&](auto e) -> int {
         constexpr int E = decltype(e)::value;
+        if (base == kSubBase)
+            return launch_base_sub<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
         if (base)
             return launch_base<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
         if (delta == kZigzag)
@@ -744,8 +768,8 @@ static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
 // What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with the delta filter
-// (its differences folded or not) or the XOR-against-base filter in front of it, or neither.  The layout of single bytes
-// is the identity; a filter over single bytes is not.
+// (its differences folded or not) or the base filter (XOR or the folded difference) in front of it, or neither.  The
+// layout of single bytes is the identity; a filter over single bytes is not.
 struct Layout {
     uint32_t    E;
     bool        delta;
@@ -753,17 +777,19 @@ struct Layout {
     const void *d_base   = nullptr;
     uint64_t    base_len = 0;
     bool        fold     = false;   // with delta: the zigzag fold of the differences (redux_zigzag.hpp)
+    bool        sub_base = false;   // with xor_base: the folded difference in place of the XOR (redux_base_sub.hpp)
     int         filter() const { return delta ? (fold ? kZigzag : kDelta) : kNoDelta; }
+    int         base() const { return xor_base ? (sub_base ? kSubBase : kXorBase) : kNoBase; }
     bool        identity() const { return !delta && !xor_base && E == 1; }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 0, stream, xor_base, d_base, base_len);
+        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 0, stream, base(), d_base, base_len);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 1, stream, xor_base, d_base, base_len);
+        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 1, stream, base(), d_base, base_len);
     }
 };
 
@@ -2612,6 +2638,74 @@ int redux_decode_blocks_base(const redux_params *p, const uint8_t *in, const uin
         st = REDUX_INVALID_INPUT;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
                               block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, false, true}), block_crc, nullptr,
+                              {}, host::BaseIo{base, base_len, true});
+}
+
+// ---- folded difference against a base (redux_base_sub.hpp) ------------------------------------------
+// the base calls above with the other operation in the Layout; the workspaces are theirs
+static Layout base_sub_layout(uint32_t element_size, const void *d_base = nullptr, uint64_t base_len = 0)
+{
+    return Layout{element_size, false, true, d_base, base_len, false, true};
+}
+
+int redux_base_sub_check(uint32_t element_size) { return redux_base_check(element_size); }
+
+int redux_base_sub_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
+                              uint32_t element_size, int inverse, void *stream)
+{
+    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream, kSubBase, d_base, base_len);
+}
+
+uint64_t redux_encode_base_sub_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_encode_base_workspace_bytes(p, in_len, block_size, element_size);
+}
+
+uint64_t redux_decode_base_sub_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_decode_base_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+int redux_encode_base_sub_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
+                              uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                              void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(base_sub_layout(element_size, d_base, base_len), p, d_in, in_len, block_size, d_out, out_cap,
+                             d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_base_sub_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_base, uint64_t base_len,
+                              uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
+                              void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(base_sub_layout(element_size, d_base, base_len), p, d_in, d_in_offsets, out_len, block_size, d_out,
+                             d_out_sizes, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_base_sub(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
+                                 uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                 int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st != REDUX_OK)
+        return st;
+    if (redux_base_sub_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) ||
+        (base_len && !base))
+        return REDUX_INVALID_INPUT;
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
+                               layout_encoder(p, block_size, base_sub_layout(element_size)), block_crc, nullptr, {},
+                               host::BaseIo{base, base_len, true}); // redux_host.hpp
+}
+
+int redux_decode_blocks_base_sub(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                                 uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                                 uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && (redux_base_sub_check(element_size) != REDUX_OK || (base_len && !base)))
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, layout_decoder(p, block_size, base_sub_layout(element_size)), block_crc, nullptr,
                               {}, host::BaseIo{base, base_len, true});
 }
 

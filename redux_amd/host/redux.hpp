@@ -16,6 +16,7 @@
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
 //   redux::hip::compress_blocks_zigzag / decompress_blocks_zigzag   signed series behind the zigzag-folded delta filter
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
+//   redux::hip::compress_blocks_base_sub / decompress_blocks_base_sub   the same behind the folded difference against the base
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
 //   redux::hip::compress_blocks_const / decompress_blocks_const     constant blocks skipped, with or without a base
 //   redux::hip::static_table / compress_blocks_static / decompress_blocks_static   semi-static coding: one table from the data
@@ -369,6 +370,47 @@ inline std::vector<std::uint8_t> decompress_blocks_base(const Blocks &streams, c
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_base(&cp, streams.data.data(), streams.offsets.data(), base, base_len, len, block_size, element_size,
                                    out.data(), sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// A snapshot behind the folded difference against a base (include/redux_hip.h, "folded difference against a base"): the
+// base filter's other operation, the zigzag-folded difference of the little-endian elements in place of the XOR; the
+// arguments and the refusals of compress_blocks_base.  Opt-in, and the decoder needs the same base.
+inline Blocks compress_blocks_base_sub(const std::uint8_t *in, std::uint64_t len, const std::uint8_t *base, std::uint64_t base_len,
+                                       std::uint32_t block_size, std::uint32_t element_size, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_base_sub(&cp, in, len, base, base_len, block_size, element_size, b.data.data(), b.data.size(),
+                                       b.offsets.data(), nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse, with the same base: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_base_sub(const Blocks &streams, const std::uint8_t *base, std::uint64_t base_len,
+                                                            std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                                            const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_block_count(len, block_size) + 1 != streams.offsets.size() ||
+        streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_base_sub(&cp, streams.data.data(), streams.offsets.data(), base, base_len, len, block_size,
+                                       element_size, out.data(), sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }

@@ -79,6 +79,13 @@ extern "C" {
     fn redux_decode_blocks_base(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, base: *const u8,
                                 base_len: u64, out_len: u64, block_size: u32, element_size: u32, out: *mut u8,
                                 out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // folded difference against a base: the base filter's other operation, the arguments of the pair above
+    fn redux_encode_blocks_base_sub(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
+                                    block_size: u32, element_size: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                    block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_base_sub(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, base: *const u8,
+                                    base_len: u64, out_len: u64, block_size: u32, element_size: u32, out: *mut u8,
+                                    out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
     // constant blocks: a block of equal bytes travels as one byte (base null only with base_len 0: no base; block_crc may
     // be null)
     fn redux_encode_blocks_const(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
@@ -473,6 +480,52 @@ pub fn decompress_blocks_base(streams: &[u8], offsets: &[u64], base: &[u8], len:
         try!(status(redux_decode_blocks_base(&cp, streams.as_ptr(), offsets.as_ptr(), base.as_ptr(), base.len() as u64, len,
                                              block_size, element_size, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
                                              ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks` of a snapshot behind the folded difference against a base (include/redux_hip.h, "folded difference
+/// against a base"): `compress_blocks_base` with the zigzag-folded difference of the little-endian elements in place of the
+/// XOR.  Opt-in, and the decoder needs the same base.
+pub fn compress_blocks_base_sub(data: &[u8], base: &[u8], block_size: u32, element_size: u32, p: &Parameters)
+                                -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_base_sub(&cp, data.as_ptr(), data.len() as u64, base.as_ptr(), base.len() as u64,
+                                                 block_size, element_size, out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(),
+                                                 ptr::null_mut(), ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_base_sub`, with the same `base`: `len` is the original byte count; returns the original bytes.
+pub fn decompress_blocks_base_sub(streams: &[u8], offsets: &[u64], base: &[u8], len: u64, block_size: u32, element_size: u32,
+                                  p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_base_sub(&cp, streams.as_ptr(), offsets.as_ptr(), base.as_ptr(), base.len() as u64, len,
+                                                 block_size, element_size, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
+                                                 ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
