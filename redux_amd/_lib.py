@@ -84,8 +84,6 @@ SIGNATURES = {
     "redux_crc32_blocks": (C.c_int, [_V, _U64, _U32, _V]),
     "redux_encode_blocks_crc": (C.c_int, [_PP, _V, _U64, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_crc": (C.c_int, [_PP, _V, _V, _U64, _U32, _V, _U64, _V, _V, _V]),
-    "redux_encode_blocks_planes_crc": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
-    "redux_decode_blocks_planes_crc": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_static_encode_blocks_crc": (C.c_int, [_PP, C.POINTER(_U32), _V, _U64, _U32, _V, _U64, _V, _V, _V]),
     "redux_static_decode_blocks_crc": (C.c_int, [_PP, C.POINTER(_U32), _V, _V, _U64, _U32, _V, _U64, _V, _V, _V]),
     "redux_encode_stored_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
@@ -167,46 +165,8 @@ SIGNATURES = {
     "redux_segment_tiles": (_U64, [_V, _U64, _V]),
     "redux_segment_copy_dev": (C.c_int, [_V, _U64, _V, _U64, _V, _U64, _V, _U64, _V]),
     "redux_segment_copy_kernel_name": (C.c_char_p, []),
-    "redux_planes_check": (C.c_int, [_U32]),
-    "redux_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
-    "redux_encode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_decode_planes_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_encode_planes_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
-    "redux_decode_planes_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
     "redux_encode_blocks_planes": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V]),
     "redux_decode_blocks_planes": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V]),
-    "redux_delta_check": (C.c_int, [_U32]),
-    "redux_delta_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
-    "redux_encode_delta_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_decode_delta_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_encode_delta_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
-    "redux_decode_delta_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
-    "redux_encode_blocks_delta": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
-    "redux_decode_blocks_delta": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
-    "redux_zigzag_check": (C.c_int, [_U32]),
-    "redux_zigzag_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, _V]),
-    "redux_encode_zigzag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_decode_zigzag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_encode_zigzag_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
-    "redux_decode_zigzag_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
-    "redux_encode_blocks_zigzag": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
-    "redux_decode_blocks_zigzag": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _V, _V, _V, _V]),
-    "redux_base_check": (C.c_int, [_U32]),
-    "redux_base_planes_dev": (C.c_int, [_V, _V, _U64, _V, _U64, _U32, _U32, C.c_int, _V]),
-    "redux_encode_base_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_decode_base_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_encode_base_dev": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
-    "redux_decode_base_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
-    "redux_encode_blocks_base": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
-    "redux_decode_blocks_base": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
-    "redux_base_sub_check": (C.c_int, [_U32]),
-    "redux_base_sub_planes_dev": (C.c_int, [_V, _V, _U64, _V, _U64, _U32, _U32, C.c_int, _V]),
-    "redux_encode_base_sub_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_decode_base_sub_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
-    "redux_encode_base_sub_dev": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
-    "redux_decode_base_sub_dev": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
-    "redux_encode_blocks_base_sub": (C.c_int, [_PP, _V, _U64, _V, _U64, _U32, _U32, _V, _U64, _V, _V, _V]),
-    "redux_decode_blocks_base_sub": (C.c_int, [_PP, _V, _V, _V, _U64, _U64, _U32, _U32, _V, _V, _V, _V]),
     "redux_const_blocks_dev": (C.c_int, [_V, _U64, _U32, _V, _V]),
     "redux_encode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
     "redux_decode_const_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
@@ -218,6 +178,30 @@ SIGNATURES = {
     "redux_gen_zipf_dev": (C.c_int, [_V, _U64, _U64, _U64, _V]),
     "redux_zipf_thresholds": (C.POINTER(_U32), []),
 }
+
+
+
+def _family(infix, base, transform=None, blocks=None):
+    """The eight entry points of a filter in front of the byte-plane layout (include/redux_hip.h): the check, the transform,
+    the two workspace sizes, the `_dev` coder calls and the host-pointer ones.  base: they take a (base, base_len) pair
+    behind their input.  The layout's own family names its transform and its host-pointer calls differently."""
+    y = [_V, _U64] if base else []
+    blocks = blocks or infix
+    return {
+        "redux_%s_check" % infix: (C.c_int, [_U32]),
+        transform or "redux_%s_planes_dev" % infix: (C.c_int, [_V, *y, _V, _U64, _U32, _U32, C.c_int, _V]),
+        "redux_encode_%s_workspace_bytes" % infix: (_U64, [_PP, _U64, _U32, _U32]),
+        "redux_decode_%s_workspace_bytes" % infix: (_U64, [_PP, _U64, _U32, _U32]),
+        "redux_encode_%s_dev" % infix: (C.c_int, [_PP, _V, _U64, *y, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+        "redux_decode_%s_dev" % infix: (C.c_int, [_PP, _V, _V, *y, _U64, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+        "redux_encode_blocks_%s" % blocks: (C.c_int, [_PP, _V, _U64, *y, _U32, _U32, _V, _U64, _V, _V, _V]),
+        "redux_decode_blocks_%s" % blocks: (C.c_int, [_PP, _V, _V, *y, _U64, _U32, _U32, _V, _V, _V, _V]),
+    }
+
+
+SIGNATURES.update(_family("planes", False, transform="redux_planes_dev", blocks="planes_crc"))
+for _infix, _base in (("delta", False), ("zigzag", False), ("base", True), ("base_sub", True)):
+    SIGNATURES.update(_family(_infix, _base))
 
 _LIB = None
 

@@ -11,6 +11,7 @@ Reference surface (file:line under the reference checkout) and what stands for i
 Every byte of every stream is produced by the gfx950 kernels behind include/redux_hip.h.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -505,56 +506,66 @@ def _check_element_size(element_size):
     return int(element_size)
 
 
-def _check_filter(filter, allowed=True):
-    """filter=None, "delta": the delta filter for integer series (include/redux_hip.h, "delta filter"), or "zigzag": the
-    same with its differences folded (include/redux_hip.h, "zigzag-folded delta filter"); anything else, and a filter
-    where it is not available (allowed false), is InvalidInput.  A check on the arguments alone: it comes before any call
-    into the library.  -> False for None, True for "delta", "zigzag" for "zigzag": true wherever there is a filter, and
-    _zigzag() tells which."""
-    if filter is None:
-        return False
-    if not isinstance(filter, str) or filter not in ("delta", "zigzag") or not allowed:
+# The filter in front of the byte-plane layout, as the C entry points name it (include/redux_hip.h): the infix of
+# redux_{encode,decode}_{infix}_{dev,workspace_bytes}, redux_{encode,decode}_blocks_{infix} and redux_{infix}_planes_dev,
+# whether those take a (base, base_len) pair, and whether decoding needs the length for every element size.  A new filter
+# is a new row here (and a Filter value in redux_hip.hip, and a version row in container.py).
+_Front = namedtuple("_Front", "infix takes_base needs_length")
+_PLANES = _Front("planes", False, False)                                 # no filter: the layout alone (none for element size 1)
+_FILTERS = {"delta": _Front("delta", False, True),                       # filter="delta": the delta filter for integer series
+            "zigzag": _Front("zigzag", False, True)}                     # filter="zigzag": the same with folded differences
+_BASE_OPS = {"xor": _Front("base", True, True),                          # base=: the XOR against the base
+             "sub": _Front("base_sub", True, True)}                      # base=, base_op="sub": the folded difference
+
+# what _resolve_front makes of a call's options: the _Front, and whether the constant-block option / the mixed layouts are on
+_Resolved = namedtuple("_Resolved", "front constant mixed")
+
+_STATIC_MODELS = (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)
+
+
+def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor", constant=None, stored=None, unit_layouts=None,
+                   device=False):
+    """The one place that says which of filter=, base=, base_op=, constant=, stored=, unit_layouts= and the model's kind go
+    together; anything else is InvalidInput.  A check on the arguments alone: it touches neither the library nor torch,
+    so it comes before any call into either.  -> _Resolved.
+    filter: None, "delta" or "zigzag"; with the adaptive model only, and not with stored blocks.
+    base: None or a base; as a filter, and not together with one.  base_op: "xor" or "sub", "sub" only with a base and
+    without the constant-block option.
+    constant: None / False, or the option (True, or the flags); adaptive model only, with or without a base, not with a
+    filter or stored blocks.
+    unit_layouts: None, or the mixed layouts (any other value); adaptive model only, element size 1 and none of the above.
+    device: the device coder objects take a model for its parameters alone and have no stored blocks: only the
+    constant-block option and the mixed layouts look at the model's kind there."""
+    static = isinstance(params, _STATIC_MODELS)
+    const = not (constant is None or constant is False)
+    mixed = unit_layouts is not None
+    if not isinstance(base_op, str) or base_op not in _BASE_OPS or (base_op == "sub" and (base is None or const)):
         raise InvalidInput()
-    return True if filter == "delta" else filter
-
-
-def _zigzag(delta):
-    """of what _check_filter returned: is it the zigzag-folded filter"""
-    return delta == "zigzag"
-
-
-def _check_base(base, allowed=True):
-    """base=None, or the base of the XOR-against-base filter (include/redux_hip.h, "XOR-against-base filter"): a base where
-    the filter is not available (allowed false: a static model, stored blocks, the delta filter) is InvalidInput.  A check
-    on the arguments alone: it comes before any call into the library.  -> True when there is a base."""
-    if base is None:
-        return False
-    if not allowed:
+    if mixed and (static or not isinstance(element_size, (int, np.integer)) or element_size != 1 or filter is not None
+                  or stored is not None or base is not None or const):
         raise InvalidInput()
-    return True
-
-
-def _check_base_op(base_op, base, constant=None):
-    """base_op="xor" (the default) or "sub": what the base filter does with the base, the bytewise XOR or the folded
-    difference of the elements (include/redux_hip.h, "folded difference against a base").  Any other value, "sub" without
-    a base and "sub" with the constant-block option are InvalidInput.  A check on the arguments alone: it comes before any
-    call into the library.  -> True for "sub"."""
-    if not isinstance(base_op, str) or base_op not in ("xor", "sub"):
+    filtered = stored is None and not (static and not device)  # where a filter or a base may stand
+    if const and (static or stored is not None or filter is not None):
         raise InvalidInput()
-    if base_op == "sub" and (base is None or not (constant is None or constant is False)):
+    if base is not None and (not filtered or filter is not None):
         raise InvalidInput()
-    return base_op == "sub"
+    if filter is not None and (not filtered or not isinstance(filter, str) or filter not in _FILTERS):
+        raise InvalidInput()
+    front = _FILTERS[filter] if filter is not None else _BASE_OPS[base_op] if base is not None else _PLANES
+    return _Resolved(front, const, mixed)
 
 
-def _check_constant(constant, allowed=True):
-    """constant=None / False, or the constant-block option (include/redux_hip.h, "constant blocks"): the option where it
-    is not available (allowed false: a static model, stored blocks, the delta filter, the `_v` calls) is InvalidInput.  A
-    check on the arguments alone: it comes before any call into the library.  -> True when the option is on."""
-    if constant is None or constant is False:
-        return False
-    if not allowed:
+def _no_front(filter=None, constant=None):
+    """the calls that take no filter and no constant-block option at all: either is InvalidInput"""
+    r = _resolve_front(None, filter=filter, constant=constant)
+    if r.front is not _PLANES or r.constant:
         raise InvalidInput()
-    return True
+
+
+def _blocks_entry(L, direction, front):
+    """the host-pointer entry point of a _Front, redux_{direction}_blocks_{infix} (the layout's own family got its checksum
+    argument later, under a name of its own)"""
+    return getattr(L, "redux_%s_blocks_%s" % (direction, "planes_crc" if front is _PLANES else front.infix))
 
 
 STORE_RATIO = 65536  # stored blocks: store a block whose stream is >= 65536/65536 of its bytes (include/redux_hip.h)
@@ -569,16 +580,6 @@ def _array_arg(a, dtype, nb, writable=True):
             or (writable and not a.flags.writeable):
         raise InvalidInput()
     return _ptr(a)
-
-
-def _check_mixed(params, element_size=1, filter=None, stored=None, base=None, constant=None):
-    """the mixed layouts go with the adaptive model alone: a static model, an element size, a filter, stored blocks, a base
-    or the constant-block option next to them is InvalidInput.  A check on the arguments alone: it comes before any call
-    into the library."""
-    if isinstance(params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)) \
-            or not isinstance(element_size, (int, np.integer)) or element_size != 1 or filter is not None or stored is not None \
-            or base is not None or not (constant is None or constant is False):
-        raise InvalidInput()
 
 
 MIXED_UNIT_BLOCKS = 8  # REDUX_MIXED_UNIT_BLOCKS: blocks of a unit of the mixed layouts
@@ -689,9 +690,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     base_op: "xor" (the default), or "sub" with base=: the folded difference of the elements against the base in place of
     the XOR (include/redux_hip.h, "folded difference against a base": redux_encode_blocks_base_sub);
     decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=."""
-    sub = _check_base_op(base_op, base, constant)
-    if unit_layouts is not None:
-        _check_mixed(params, element_size, filter, stored, base, constant)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    if mixed:
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
     if layouts is not None:
         raise InvalidInput()
@@ -699,9 +699,6 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context  # (the same checks: element size 1, no stored blocks, no filter)
-    const = _check_constant(constant, not (static or plane or segment or stored is not None or filter is not None))
-    xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
-    delta = _check_filter(filter, not (static or plane or segment or stored is not None))
     plane = plane or segment  # (the checks of a model that brings its own element size)
     P = _params_of(params)
     a = _u8(data)
@@ -733,18 +730,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
                                                       offs.ctypes.data, status.ctypes.data, crc)
         if st == _lib.OK or cums.any():
             params.cums = cums
-    elif delta:
-        encode = L.redux_encode_blocks_zigzag if _zigzag(delta) else L.redux_encode_blocks_delta
-        st = encode(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap, offs.ctypes.data, status.ctypes.data, crc)
     elif const:
-        y = _u8(base) if xbase else _u8(b"")
+        y = _u8(base) if front.takes_base else _u8(b"")
         st = L.redux_encode_blocks_const(C.byref(cp), _ptr(a), len(a), _ptr(y) if len(y) else None, len(y), block_size, E,
                                          out.ctypes.data, cap, offs.ctypes.data, cptr, status.ctypes.data, crc)
-    elif xbase:
-        y = _u8(base)
-        encode = L.redux_encode_blocks_base_sub if sub else L.redux_encode_blocks_base
-        st = encode(C.byref(cp), _ptr(a), len(a), _ptr(y), len(y), block_size, E, out.ctypes.data, cap, offs.ctypes.data,
-                    status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_encode_blocks_stored(C.byref(cp), _ptr(a), len(a), block_size, E, int(store_ratio), out.ctypes.data, cap,
                                           offs.ctypes.data, flags, status.ctypes.data, crc)
@@ -758,9 +747,10 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
         st = L.redux_plane_static_encode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), len(a), block_size,
                                                     params.element_size, out.ctypes.data, cap, offs.ctypes.data,
                                                     status.ctypes.data, crc)
-    else:  # (element size 1 included: the coder without a layout)
-        st = L.redux_encode_blocks_planes_crc(C.byref(cp), _ptr(a), len(a), block_size, E, out.ctypes.data, cap,
-                                              offs.ctypes.data, status.ctypes.data, crc)
+    else:  # the adaptive coder behind the front's filter (none, and element size 1, included: the coder without a layout)
+        y = _u8(base) if front.takes_base else None
+        st = _blocks_entry(L, "encode", front)(C.byref(cp), _ptr(a), len(a), *((_ptr(y), len(y)) if front.takes_base else ()),
+                                               block_size, E, out.ctypes.data, cap, offs.ctypes.data, status.ctypes.data, crc)
     _raise(st)
     if constant is True:
         return out[: int(offs[-1])], offs, status, cflags
@@ -805,18 +795,14 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
     required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
     base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub)."""
-    sub = _check_base_op(base_op, base, constant)
-    if unit_layouts is not None:
-        _check_mixed(params, element_size, filter, stored, base, constant)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    if mixed:
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
     segment = isinstance(params, SegmentStaticModel)
     context = isinstance(params, ContextStaticModel)
     static = static or context
-    const = _check_constant(constant, not (static or plane or segment or stored is not None or filter is not None))
-    xbase = _check_base(base, not (static or plane or segment or stored is not None or filter is not None))
-    delta = _check_filter(filter, not (static or plane or segment or stored is not None))
-    if (delta or xbase or const) and length is None:
+    if (front.needs_length or const) and length is None:
         raise InvalidInput()
     plane = plane or segment
     E = _check_element_size(element_size)
@@ -846,19 +832,10 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
         st = L.redux_segment_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), len(params.cums), _ptr(a), offs.ctypes.data,
                                                       length, block_size, params.element_size, params.segment_blocks,
                                                       out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
-    elif delta:
-        decode = L.redux_decode_blocks_zigzag if _zigzag(delta) else L.redux_decode_blocks_delta
-        st = decode(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data, sizes.ctypes.data,
-                    status.ctypes.data, crc)
     elif const:
-        y = _u8(base) if xbase else _u8(b"")
+        y = _u8(base) if front.takes_base else _u8(b"")
         st = L.redux_decode_blocks_const(C.byref(cp), _ptr(a), offs.ctypes.data, cptr, _ptr(y) if len(y) else None, len(y),
                                          length, block_size, E, out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
-    elif xbase:
-        y = _u8(base)
-        decode = L.redux_decode_blocks_base_sub if sub else L.redux_decode_blocks_base
-        st = decode(C.byref(cp), _ptr(a), offs.ctypes.data, _ptr(y), len(y), length, block_size, E, out.ctypes.data,
-                    sizes.ctypes.data, status.ctypes.data, crc)
     elif stored is not None:
         st = L.redux_decode_blocks_stored(C.byref(cp), _ptr(a), offs.ctypes.data, flags, length, block_size, E, out.ctypes.data,
                                           out.size, sizes.ctypes.data, status.ctypes.data, crc)
@@ -872,9 +849,10 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
         st = L.redux_plane_static_decode_blocks_crc(C.byref(cp), params._cum_ptr(), _ptr(a), offs.ctypes.data, length, block_size,
                                                     params.element_size, out.ctypes.data, sizes.ctypes.data, status.ctypes.data,
                                                     crc)
-    elif length is not None:
-        st = L.redux_decode_blocks_planes_crc(C.byref(cp), _ptr(a), offs.ctypes.data, length, block_size, E, out.ctypes.data,
-                                              sizes.ctypes.data, status.ctypes.data, crc)
+    elif length is not None:  # the adaptive coder behind the front's filter, or behind the layout alone
+        y = _u8(base) if front.takes_base else None
+        st = _blocks_entry(L, "decode", front)(C.byref(cp), _ptr(a), offs.ctypes.data, *((_ptr(y), len(y)) if front.takes_base else ()),
+                                               length, block_size, E, out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
     else:
         st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
                                        sizes.ctypes.data, status.ctypes.data, crc)
@@ -925,8 +903,7 @@ def compress_blocks_v(inputs, block_size, params=(8, 30, 32), filter=None, const
     uint64[nblocks+1], status int32[nblocks], first_block int64[len(inputs)+1]): input i owns blocks
     first_block[i] .. first_block[i+1]-1.  filter: None (the `_v` calls have no delta filter: "delta" is InvalidInput)."""
     _adaptive_only(params)
-    _check_filter(filter, False)
-    _check_constant(constant, False)  # (no constant blocks in the `_v` calls: InvalidInput)
+    _no_front(filter, constant)  # (no filter and no constant blocks in the `_v` calls: InvalidInput)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -955,8 +932,7 @@ def decompress_blocks_v(streams, offsets, lengths, block_size, params=(8, 30, 32
     """The inverse of compress_blocks_v: `lengths[i]` is the decoded size of input i.  Returns (list of
     uint8 arrays, sizes uint32[nblocks], status int32[nblocks]).  filter: None ("delta" is InvalidInput)."""
     _adaptive_only(params)
-    _check_filter(filter, False)
-    _check_constant(constant, False)  # (no constant blocks in the `_v` calls: InvalidInput)
+    _no_front(filter, constant)  # (no filter and no constant blocks in the `_v` calls: InvalidInput)
     P = _params_of(params)
     L = _lib.lib()
     cp = P._c()
@@ -987,7 +963,7 @@ def compress(istream, ostream, model, filter=None):
     one block, so the stream equals the reference's; it is coded by one GPU lane.  filter: None (a raw reference stream
     has no delta filter: "delta" is InvalidInput)."""
     _adaptive_only(model)
-    _check_filter(filter, False)
+    _no_front(filter)
     P = _params_of(model)
     a = _u8(istream.read())
     L = _lib.lib()
@@ -1004,7 +980,7 @@ def compress(istream, ostream, model, filter=None):
 def decompress(istream, ostream, model, max_output=None, filter=None):
     """redux::decompress(istream, ostream, model) -> (bytes_in, bytes_out).  filter: None ("delta" is InvalidInput)."""
     _adaptive_only(model)
-    _check_filter(filter, False)
+    _no_front(filter)
     P = _params_of(model)
     a = _u8(istream.read())
     L = _lib.lib()
@@ -1257,17 +1233,13 @@ class DeviceEncoder(_DeviceCoder):
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
                  mixed=False, layouts=None, base_op="xor"):
-        self.base_sub = _check_base_op(base_op, base, constant)
-        self.mixed = bool(mixed)
-        if self.mixed:  # (with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
-            _check_mixed(params, element_size, filter, None, base, constant)
+        # (mixed: with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
+        self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
+                                                               unit_layouts=True if mixed else None, device=True)
+        if self.mixed:
             self.mixed_mask = _layout_mask(layouts)
         elif layouts is not None:
             raise InvalidInput()
-        self.constant = _check_constant(constant, filter is None and not isinstance(
-            params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
-        _check_base(base, filter is None)   # (before the filter's own check: both together are refused whatever the filter)
-        self.delta = _check_filter(filter)  # the delta filter, folded or not, in front of the layout (encode() only)
         torch = _torch()
         self.base = _device_base(torch, base, device)  # the XOR-against-base filter in front of the layout (encode() only)
         P = _params_of(params)
@@ -1284,20 +1256,15 @@ class DeviceEncoder(_DeviceCoder):
             ws_bytes, self._encode_dev, self._lead = (lambda cp, n, b, e: L.redux_encode_mixed_workspace_bytes(cp, n, b)), \
                 L.redux_encode_mixed_dev, (B,)
             self.unit_table = torch.zeros(max(L.redux_mixed_unit_count(self.max_in_len, B), 1), dtype=torch.uint8, device=self.device)
-        elif self.delta:
-            ws_bytes, self._encode_dev = (L.redux_encode_zigzag_workspace_bytes, L.redux_encode_zigzag_dev) if _zigzag(self.delta) \
-                else (L.redux_encode_delta_workspace_bytes, L.redux_encode_delta_dev)
-            self._lead = (B, E)
         elif self.constant:  # (the tail then holds the flags as well)
             ws_bytes, self._encode_dev = L.redux_encode_const_workspace_bytes, L.redux_encode_const_dev
             self._lead = (*_base_pair(self.base), B, E)
-        elif self.base is not None:
-            ws_bytes, self._encode_dev = (L.redux_encode_base_sub_workspace_bytes, L.redux_encode_base_sub_dev) if self.base_sub \
-                else (L.redux_encode_base_workspace_bytes, L.redux_encode_base_dev)
-            self._lead = (*_base_pair(self.base), B, E)
-        else:  # (element size 1: the coder without a layout)
-            ws_bytes = L.redux_encode_planes_workspace_bytes
-            self._encode_dev, self._lead = (L.redux_encode_blocks_dev, (B,)) if E == 1 else (L.redux_encode_planes_dev, (B, E))
+        elif self.front is _PLANES and E == 1:  # (the coder without a layout)
+            ws_bytes, self._encode_dev, self._lead = L.redux_encode_planes_workspace_bytes, L.redux_encode_blocks_dev, (B,)
+        else:  # the layered entry points of the front's family
+            ws_bytes = getattr(L, "redux_encode_%s_workspace_bytes" % self.front.infix)
+            self._encode_dev = getattr(L, "redux_encode_%s_dev" % self.front.infix)
+            self._lead = (*(_base_pair(self.base) if self.front.takes_base else ()), B, E)
         ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, E)
         if (self.constant or self.mixed) and ws_bytes == 0:
             raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
@@ -1308,7 +1275,7 @@ class DeviceEncoder(_DeviceCoder):
 
     def _plain_only(self):
         """the two phases are the plain coder's; encode() applies the layout and the filter"""
-        if self.element_size != 1 or self.delta or self.base is not None or self.constant or self.mixed:
+        if self.element_size != 1 or self.front is not _PLANES or self.constant or self.mixed:
             raise Unsupported()
 
     @_on_device
@@ -1370,14 +1337,9 @@ class DeviceDecoder(_DeviceCoder):
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
                  mixed=False, base_op="xor"):
-        self.base_sub = _check_base_op(base_op, base, constant)
-        self.mixed = bool(mixed)
-        if self.mixed:  # (the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
-            _check_mixed(params, element_size, filter, None, base, constant)
-        self.constant = _check_constant(constant, filter is None and not isinstance(
-            params, (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStaticModel)))
-        _check_base(base, filter is None)
-        self.delta = _check_filter(filter)
+        # (mixed: the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
+        self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
+                                                               unit_layouts=True if mixed else None, device=True)
         torch = _torch()
         self.base = _device_base(torch, base, device)
         P = _params_of(params)
@@ -1396,17 +1358,12 @@ class DeviceDecoder(_DeviceCoder):
             ws_bytes = L.redux_decode_const_workspace_bytes(C.byref(self.cp), self.max_in_len, self.block_size, self.element_size)
             if ws_bytes == 0:
                 raise Unsupported()
-        elif self.delta:
-            self._decode_dev = L.redux_decode_zigzag_dev if _zigzag(self.delta) else L.redux_decode_delta_dev
-            self._lead, ws_bytes = (), self._layout_ws_bytes(self.max_in_len)
-        elif self.base is not None:
-            self._decode_dev = L.redux_decode_base_sub_dev if self.base_sub else L.redux_decode_base_dev
-            self._lead, self._takes_base = (), True
-            ws_bytes = self._layout_ws_bytes(self.max_in_len)
-        else:  # (element size 1: decode() without a length needs less, and the first one with a length regrows it)
-            self._decode_dev, self._lead = L.redux_decode_planes_dev, ()
+        else:  # the front's family (element size 1 without a filter: decode() without a length needs less, and the first
+            # one with a length regrows it)
+            self._decode_dev = getattr(L, "redux_decode_%s_dev" % self.front.infix)
+            self._lead, self._takes_base = (), self.front.takes_base
             ws_bytes = L.redux_decode_workspace_bytes(C.byref(self.cp), self.max_blocks, self.block_size) \
-                if self.element_size == 1 else self._layout_ws_bytes(self.max_in_len)
+                if self.front is _PLANES and self.element_size == 1 else self._layout_ws_bytes(self.max_in_len)
         self._alloc_workspace(ws_bytes)
         self.out, self.sizes, self.status, self.summary = self._new_dec_buffers(self.max_in_len)
 
@@ -1448,7 +1405,7 @@ class DeviceDecoder(_DeviceCoder):
             _raise(self._decode_dev(C.byref(self.cp), _dptr(d_streams), d_offsets.data_ptr(), unit_layouts.data_ptr(), int(length),
                                     self.block_size, self.out.data_ptr(), *self._dec_tail()))
             return self._dec_result(int(length), nb)
-        if (length is None and (self.element_size > 1 or self.delta or self.base is not None or self.constant)) \
+        if (length is None and (self.element_size > 1 or self.front.needs_length or self.constant)) \
                 or (length is not None and (length < 0 or L.redux_block_count(int(length), self.block_size) != nb)) \
                 or (constant is None) == self.constant:
             raise InvalidInput()
@@ -1807,8 +1764,10 @@ class DeviceSegmentStaticCoder(_DeviceCoder):
 
 
 # ---- byte-plane layout of typed data ----------------------------------------------------------
-def _transform(name, d_src, element_size, block_size, inverse, out, d_base=None):
-    """planes / delta_planes / base_planes: the C entry point `name` from d_src into `out`, on torch's current stream"""
+def _transform(front, d_src, element_size, block_size, inverse, out, d_base=None):
+    """planes / delta_planes / base_planes ...: the transform of a _Front (redux_planes_dev, redux_{infix}_planes_dev) from
+    d_src into `out`, on torch's current stream"""
+    name = "redux_planes_dev" if front is _PLANES else "redux_%s_planes_dev" % front.infix
     torch = _torch()
     E = _check_element_size(element_size)
     assert d_src.dtype == torch.uint8 and d_src.is_contiguous()
@@ -1818,7 +1777,7 @@ def _transform(name, d_src, element_size, block_size, inverse, out, d_base=None)
     n = d_src.numel()
     t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
-    base = () if d_base is None else _base_pair(d_base)
+    base = _base_pair(d_base) if front.takes_base else ()
     with torch.cuda.device(t.device):
         _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, E, 1 if inverse else 0,
                                          _stream_ptr(torch)))
@@ -1828,19 +1787,19 @@ def _transform(name, d_src, element_size, block_size, inverse, out, d_base=None)
 def planes(d_src, element_size, block_size, inverse=False, out=None):
     """The byte-plane layout (include/redux_hip.h) of a uint8 device tensor, or its inverse: redux_planes_dev on torch's
     current stream.  out: a uint8 tensor of the same length on the same device (allocated when None)."""
-    return _transform("redux_planes_dev", d_src, element_size, block_size, inverse, out)
+    return _transform(_PLANES, d_src, element_size, block_size, inverse, out)
 
 
 def delta_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The delta filter followed by the byte-plane layout (include/redux_hip.h, "delta filter") of a uint8 device tensor,
     or their inverse: redux_delta_planes_dev on torch's current stream.  out: as for planes()."""
-    return _transform("redux_delta_planes_dev", d_src, element_size, block_size, inverse, out)
+    return _transform(_resolve_front(None, filter="delta").front, d_src, element_size, block_size, inverse, out)
 
 
 def zigzag_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The zigzag-folded delta filter followed by the byte-plane layout (include/redux_hip.h, "zigzag-folded delta filter")
     of a uint8 device tensor, or their inverse: redux_zigzag_planes_dev on torch's current stream.  out: as for planes()."""
-    return _transform("redux_zigzag_planes_dev", d_src, element_size, block_size, inverse, out)
+    return _transform(_resolve_front(None, filter="zigzag").front, d_src, element_size, block_size, inverse, out)
 
 
 def _device_unit_table(torch, table, nunits, device):
@@ -1886,14 +1845,14 @@ def base_planes(d_src, d_base, element_size, block_size, inverse=False, out=None
     """The XOR against d_base followed by the byte-plane layout (include/redux_hip.h, "XOR-against-base filter") of a uint8
     device tensor, or their inverse: redux_base_planes_dev on torch's current stream.  d_base: a uint8 tensor of any length
     on the same device.  out: as for planes()."""
-    return _transform("redux_base_planes_dev", d_src, element_size, block_size, inverse, out, d_base)
+    return _transform(_resolve_front(None, base=d_base).front, d_src, element_size, block_size, inverse, out, d_base)
 
 
 def base_sub_planes(d_src, d_base, element_size, block_size, inverse=False, out=None):
     """The folded difference against d_base followed by the byte-plane layout (include/redux_hip.h, "folded difference
     against a base") of a uint8 device tensor, or their inverse: redux_base_sub_planes_dev on torch's current stream.
     d_base and out: as for base_planes()."""
-    return _transform("redux_base_sub_planes_dev", d_src, element_size, block_size, inverse, out, d_base)
+    return _transform(_resolve_front(None, base=d_base, base_op="sub").front, d_src, element_size, block_size, inverse, out, d_base)
 
 
 def constant_blocks(data, block_size):

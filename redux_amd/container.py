@@ -155,6 +155,17 @@ HEADER = struct.Struct("<4sBBBBIIQQ")
 # the decode capacity is additionally capped by the total length the header declares.
 MAX_BLOCK_SIZE = 1 << 30
 
+# The versions that are version 2's sections behind a filter (version 2 itself: behind none): the marker nibble of the word
+# at offset 12, which is mark << 28 | E; the filter and the operation of the base filter a reader reports; whether the base
+# record follows the header.  pack, _version_ok, _header and _parse_index go by this table: a new filter is a new row.
+_FilterVersion = namedtuple("_FilterVersion", "mark filter base_op has_base")
+FILTER_VERSIONS = {VERSION_PLANES: _FilterVersion(0, None, None, False),
+                   VERSION_DELTA: _FilterVersion(DELTA_MARK >> 28, "delta", None, False),
+                   VERSION_BASE: _FilterVersion(BASE_MARK >> 28, None, "xor", True),
+                   VERSION_ZIGZAG: _FilterVersion(ZIGZAG_MARK >> 28, "zigzag", None, False),
+                   VERSION_BASE_SUB: _FilterVersion(BASE_SUB_MARK >> 28, None, "sub", True)}
+_VERSION_OF_FILTER = {(row.filter, row.base_op): ver for ver, row in FILTER_VERSIONS.items()}
+
 
 def _raw_lengths(nblocks, block_size, total):
     """L_b = min(B, total - b*B): the bytes of each block (0 for an empty input's one block)"""
@@ -182,16 +193,11 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     element_size 1 and none of stored, filter, base and constant); None: no unit table.
     base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
     version 8)."""
-    sub = api._check_base_op(base_op, base, constant)
-    mixed = unit_layouts is not None
-    if mixed:
-        api._check_mixed(params, element_size, filter, stored, base, constant)
+    front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    xbase = front.takes_base
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
     context = isinstance(params, api.ContextStaticModel)
-    const = api._check_constant(constant, not (static or plane or segment or context or stored is not None or filter is not None))
-    xbase = api._check_base(base, not (static or plane or segment or context or stored is not None or filter is not None))
-    delta = api._check_filter(filter, not (static or plane or segment or context or stored is not None))
     if xbase:
         try:
             base_used, base_crc = (int(v) for v in base)
@@ -217,12 +223,11 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
             raise api.InvalidInput()
         params.check(len(sizes))  # (the table count against this many blocks)
         ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
-    if delta:
-        ver, res = (VERSION_ZIGZAG, ZIGZAG_MARK | element_size) if api._zigzag(delta) else (VERSION_DELTA, DELTA_MARK | element_size)
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
-    if xbase:
-        ver, res = (VERSION_BASE_SUB, BASE_SUB_MARK | element_size) if sub else (VERSION_BASE, BASE_MARK | element_size)
+    if filter is not None or xbase:
+        ver = _VERSION_OF_FILTER[filter, base_op if xbase else None]
+        res = FILTER_VERSIONS[ver].mark << 28 | element_size
     if const:
         ver, res = VERSION_CONST, CONST_MARK | (1 if xbase else 0) << 4 | element_size
     crc = b""
@@ -313,18 +318,24 @@ def _layout(ver):
 def _version_ok(ver, res):
     """a known layout, its reserved word, and no stored blocks with a static table"""
     layout = _layout(ver)
+    row = FILTER_VERSIONS.get(layout)
+    if row is not None:  # (version 2 alone may have stored blocks, and has no element size 1: that is version 1)
+        plain = layout == VERSION_PLANES
+        return res >> 28 == row.mark and res & 0x0FFFFFFF in (() if plain else (1,)) + ELEMENT_SIZES \
+            and (plain or not ver & STORED_FLAG)
     return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
-        or (layout == VERSION_PLANES and res in ELEMENT_SIZES) \
         or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF) \
         or (layout == VERSION_SEGMENT_STATIC and not ver & STORED_FLAG and res >> 28 == 5 and res & 0xF in (1,) + ELEMENT_SIZES
             and res >> 4 & 0xFFFFFF >= 1) \
-        or (layout == VERSION_DELTA and not ver & STORED_FLAG and res >> 28 == 6 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
-        or (layout == VERSION_BASE and not ver & STORED_FLAG and res >> 28 == 8 and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK) \
-        or (layout == VERSION_ZIGZAG and not ver & STORED_FLAG and res >> 28 == 0xB and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_BASE_SUB and not ver & STORED_FLAG and res >> 28 == 0xC and res & 0x0FFFFFFF in (1,) + ELEMENT_SIZES)
+        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK)
+
+
+def _has_base_record(ver, res):
+    """of a checked header: does the base record follow it"""
+    row = FILTER_VERSIONS.get(_layout(ver))
+    return row.has_base if row is not None else _layout(ver) == VERSION_CONST and bool(res & 0x10)
 
 
 # What _parse reads from a container: element_size 1, or E of versions 2 and 4; static the StaticModel of a version 3 table
@@ -352,7 +363,8 @@ def _header(b):
     if nblocks != (1 if total == 0 else (total + block_size - 1) // block_size):
         raise api.InvalidInput()
     layout = _layout(ver)
-    E = res & 0xF if layout in (VERSION_SEGMENT_STATIC, VERSION_DELTA, VERSION_BASE, VERSION_CONST, VERSION_ZIGZAG, VERSION_BASE_SUB) else res & 0xFFFF if layout in (VERSION_PLANES, VERSION_PLANE_STATIC) else 1
+    E = res & 0xF if layout in FILTER_VERSIONS or layout in (VERSION_SEGMENT_STATIC, VERSION_CONST) \
+        else res & 0xFFFF if layout == VERSION_PLANE_STATIC else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -376,7 +388,7 @@ def _parse_index(b):
     ver, P, block_size, E, nblocks, total = _header(b)
     static = crcs = stored = base = constant = units = None
     at = HEADER.size
-    if _layout(ver) in (VERSION_BASE, VERSION_BASE_SUB) or (_layout(ver) == VERSION_CONST and HEADER.unpack_from(b, 0)[6] & 0x10):
+    if _has_base_record(ver, HEADER.unpack_from(b, 0)[6]):
         if len(b) < at + BASE_RECORD.size:
             raise api.Eof()
         base = BASE_RECORD.unpack_from(b, at)
@@ -440,9 +452,9 @@ def _parse_index(b):
         if bool((units > 7).any()):
             raise api.InvalidInput()
         E = None
-    return _Container(P, block_size, total, E, static, offsets, None, crcs, stored,
-                      {VERSION_DELTA: "delta", VERSION_ZIGZAG: "zigzag"}.get(_layout(ver)), base, constant, units,
-                      None if base is None else "sub" if _layout(ver) == VERSION_BASE_SUB else "xor"), at
+    row = FILTER_VERSIONS.get(_layout(ver))  # (version 9's record, where it has one, is the XOR's)
+    return _Container(P, block_size, total, E, static, offsets, None, crcs, stored, row.filter if row else None, base, constant,
+                      units, row.base_op if row else None if base is None else "xor"), at
 
 
 def _parse(buf):
@@ -562,7 +574,9 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)) \
             or (base and (model != "adaptive" or stored or filter is not None or mixed)):
         raise api.InvalidInput()
-    api._check_filter(filter, model == "adaptive" and not stored)
+    if filter is not None and (model != "adaptive" or stored):
+        raise api.InvalidInput()
+    api._resolve_front(None, filter=filter)
     E = api._check_element_size(element_size)
     n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
     if mixed:
@@ -656,7 +670,8 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     of the XOR, version 12.  "auto": the operation with the smaller estimated payload codes the data (choose_base_op; a tie
     goes to "xor"), and the container is that operation's, version 8 or 12: nothing new to decode.  Related pairs favour
     "sub", unrelated ones "xor", and a caller cannot know in advance."""
-    api._check_base_op("sub" if base_op == "auto" else base_op, base, skip_constant or None)  # ("auto": the refusals of "sub")
+    api._resolve_front(None, base=base, base_op="sub" if base_op == "auto" else base_op,
+                       constant=skip_constant or None)  # (base_op alone is judged here; "auto": the refusals of "sub")
     if layout is not None:
         if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
                 or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
@@ -669,9 +684,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
             out, offs, _, table = api.compress_blocks(data, block_size, params, block_crc=crc, unit_layouts=True, layouts=want)
             return pack(out, offs, params, block_size, len(data), block_crc=crc, unit_layouts=table)
         element_size, filter = choose_layout(estimate_layout_bytes(data, block_size, params, element_size, checksum))
-    api._check_constant(skip_constant or None, model == "adaptive" and not stored and filter is None)
-    api._check_base(base, model == "adaptive" and not stored and filter is None)
-    api._check_filter(filter, model == "adaptive" and not stored)
+    if (skip_constant or base is not None or filter is not None) and (model != "adaptive" or stored):
+        raise api.InvalidInput()
+    api._resolve_front(None, filter=filter, base=base, constant=skip_constant or None)  # (the model is a name here)
     if model == "auto":
         if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) or stored \
                 or segment_blocks is not None:
@@ -820,7 +835,7 @@ class Reader:
         ver, P, _, E, nblocks, _ = _header(head)
         res = HEADER.unpack_from(head, 0)[6]
         layout = _layout(ver)
-        tables = BASE_RECORD.size if layout in (VERSION_BASE, VERSION_BASE_SUB) or (layout == VERSION_CONST and res & 0x10) else 0
+        tables = BASE_RECORD.size if _has_base_record(ver, res) else 0
         if layout == VERSION_STATIC:
             tables += TABLE
         elif layout == VERSION_PLANE_STATIC:

@@ -1,11 +1,11 @@
 // redux_base_sub.hpp -- the folded difference against a base: the base filter's second operation (redux_base.hpp is the
-// first, XOR), fused with the byte-plane layout.  The kernels are redux_base.hpp's with another hook.
+// first, XOR), fused with the byte-plane layout.  The fused kernels are redux_base.hpp's with another operation.
 //
-//   k_base_sub_planes<E>          forward, full frames inside the base: k_base_planes' body, the stage-in hook subtracting
-//                                 the base's chunk from the source's and folding the 16 / E differences in registers;
-//                                 E = 1: a 16-byte stream kernel, no LDS
-//   k_base_sub_unplanes<E>        inverse, full frames inside the base: k_base_unplanes' body, the base's chunks loaded
-//                                 ahead, the stage-out hook unfolding and adding them
+//   k_base_planes<E, BaseSubFold<E>>    forward, full frames inside the base: the stage-in hook subtracts the base's chunk
+//                                       from the source's and folds the 16 / E differences in registers; E = 1: a 16-byte
+//                                       stream kernel, no LDS
+//   k_base_unplanes<E, BaseSubFold<E>>  inverse, full frames inside the base: the base's chunks loaded ahead, the
+//                                       stage-out hook unfolding and adding them
 //   k_base_sub_planes_bytes<E>    one element per thread under the frame index rule, any alignment and block size: the
 //   k_base_sub_unplanes_bytes<E>  short last frame, the frame the end of the base falls into, and everything when a pointer
 //                                 or the block size is no 16-byte multiple
@@ -27,7 +27,7 @@
 #pragma once
 
 #include "redux_base.hpp"
-#include "redux_zigzag.hpp"
+#include "redux_delta.hpp"
 
 namespace redux {
 
@@ -73,46 +73,12 @@ __device__ __forceinline__ uint4 base_sub_unfold(uint4 z, uint4 y)
     }
 }
 
-// Forward, full frames inside the base: k_base_planes with the subtraction and the fold where the two chunks meet.
+// the operation of k_base_planes / k_base_unplanes (redux_base.hpp)
 template <int E>
-__global__ void __launch_bounds__(256) k_base_sub_planes(BaseArgs a)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if constexpr (E == 1) { // no layout: group g is 16 bytes of the stream
-        if (g < a.groups)
-            ((uint4 *)a.dst)[g] = base_sub_fold<1>(((const uint4 *)a.src)[g], ((const uint4 *)a.base)[g]);
-    } else {
-        __shared__ uint4 lds[4 * 64 * E];
-        const uint4 *y = (const uint4 *)(a.base + (g - (threadIdx.x & 63)) * 16 * E); // the wave's chunks of the base
-        tile_forward<E, PlainForward<E>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
-                                            [y](uint4 v, int, uint32_t c) { return base_sub_fold<E>(v, y[c]); });
-    }
-}
-
-// Inverse, full frames inside the base: k_base_unplanes with the unfold and the addition where the wave writes its
-// contiguous bytes.
-template <int E>
-__global__ void __launch_bounds__(256) k_base_sub_unplanes(BaseArgs a)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if constexpr (E == 1) {
-        if (g < a.groups)
-            ((uint4 *)a.dst)[g] = base_sub_unfold<1>(((const uint4 *)a.src)[g], ((const uint4 *)a.base)[g]);
-    } else {
-        __shared__ uint4 lds[4 * 64 * E];
-        // the base's chunks first: they depend on nothing, and are in flight while the planes are permuted
-        const uint32_t lane = threadIdx.x & 63, wave_chunks = tile_wave_chunks<E, uint64_t>(a.groups, g - lane);
-        const uint4   *y    = (const uint4 *)(a.base + (g - lane) * 16 * E);
-        uint4 yb[E];
-#pragma unroll
-        for (int k = 0; k < E; k++) {
-            const uint32_t c = k * 64 + lane;
-            yb[k] = c < wave_chunks ? y[c] : make_uint4(0, 0, 0, 0);
-        }
-        tile_inverse<E>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
-                        [&yb](uint4 v, int k, uint32_t) { return base_sub_unfold<E>(v, yb[k]); });
-    }
-}
+struct BaseSubFold {
+    __device__ __forceinline__ static uint4 forward(uint4 x, uint4 y) { return base_sub_fold<E>(x, y); }
+    __device__ __forceinline__ static uint4 inverse(uint4 z, uint4 y) { return base_sub_unfold<E>(z, y); }
+};
 
 // Bytes [first, end) of the whole buffer by their INTERLEAVED position o (the source's forward, the destination's inverse),
 // one per thread: the thread of an element's first byte does the element, the threads of a frame's trailing bytes XOR them.

@@ -1,13 +1,17 @@
 // redux_delta.hpp -- the delta filter for integer series, fused with the byte-plane layout (redux_planes.hpp): a byte
 // transform in front of the coder, next to k_planes.
 //
-//   k_delta_planes<E>          forward, full frames: the forward tile (redux_planes.hpp) with DeltaForward in front of the
-//                              permutation: the predecessor rule and one subtraction; one read and one write
-//   k_delta_unplanes<E>        inverse, full frames: one workgroup per frame, one row of 256 groups per iteration: the walk
-//                              of delta_inverse_walk (which the mixed kernel runs with 8 / E rows) with its own prefetch
-//   k_delta_planes_bytes<E>    the byte path, one element per thread: the short last frame, unaligned buffers, blocks not a
-//   k_delta_unplanes_bytes<E>  multiple of 16; bytes_forward (redux_planes.hpp), and bytes_inverse_frame with one workgroup
-//                              per frame
+//   k_delta_planes<E, FOLD>          forward, full frames: the forward tile (redux_planes.hpp) with DeltaForward in front of
+//                                    the permutation: the predecessor rule and one subtraction; one read and one write
+//   k_delta_unplanes<E, FOLD>        inverse, full frames: one workgroup per frame, one row of 256 groups per iteration: the
+//                                    walk of delta_inverse_walk (which the mixed kernel runs with 8 / E rows) with its own
+//                                    prefetch
+//   k_delta_planes_bytes<E, FOLD>    the byte path, one element per thread: the short last frame, unaligned buffers, blocks
+//   k_delta_unplanes_bytes<E, FOLD>  not a multiple of 16; bytes_forward (redux_planes.hpp), and bytes_inverse_frame with
+//                                    one workgroup per frame
+//
+// FOLD: the zigzag-folded delta filter for signed series (redux_zigzag.hpp: its rule and its reasons): the fold of the
+// lane's 16 differences in registers behind the subtraction, the unfold between the permutation and the serial prefix.
 //
 // Rule (E = element size, B = block size): the input is cut into the frames of the byte-plane layout (E*B bytes, only the
 // last may be shorter; E = 1: one block).  A frame of L bytes holds N = L / E little-endian unsigned elements x[0..N); the
@@ -23,6 +27,7 @@
 #pragma once
 
 #include "redux_planes.hpp"
+#include "redux_zigzag.hpp"
 
 namespace redux {
 
@@ -144,8 +149,8 @@ __device__ __forceinline__ T delta_wave_scan(T x, uint32_t lane)
 
 // The forward predecessor rule, as the forward tile's filter (PlainForward, redux_planes.hpp): a lane's predecessor element
 // is the end of the 16-byte chunk before its own in the wave's LDS row; the wave's first lane loads it from memory, ahead of
-// the barrier; a group that starts a frame has none (inside = false).
-template <int E>
+// the barrier; a group that starts a frame has none (inside = false).  FOLD: the differences are then folded.
+template <int E, bool FOLD>
 struct DeltaForward {
     typedef typename DeltaSum<E>::T Pred;
     __device__ __forceinline__ static Pred before(const uint8_t *src, uint64_t g, bool inside, uint32_t lane)
@@ -166,16 +171,19 @@ struct DeltaForward {
 #pragma unroll
         for (int q = 0; q < 4 * E; q++)
             v[q] = d[q];
+        if constexpr (FOLD)
+            zigzag_fold<E>(v);
     }
 };
 
-// Forward, full frames: the forward tile with the subtraction in front of the permutation; one read and one write.
-template <int E>
+// Forward, full frames: the forward tile with the subtraction (and the fold) in front of the permutation; one read and one
+// write.
+template <int E, bool FOLD>
 __global__ void __launch_bounds__(256) k_delta_planes(PlanesArgs a)
 {
     __shared__ uint4 lds[4 * 64 * E];
-    tile_forward<E, DeltaForward<E>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
-                                        TileNoHook());
+    tile_forward<E, DeltaForward<E, FOLD>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size,
+                                              lds, TileNoHook());
 }
 
 // The frame walk of the inverse: the workgroup walks frames first, first + step, ... below count (src, dst: frame 0), R rows
@@ -253,7 +261,9 @@ __device__ __forceinline__ void delta_inverse_walk(const uint8_t *src, uint8_t *
 // Inverse, full frames: workgroup w walks frames w, w + gridDim.x, ..., one row of 256 groups per iteration: the walk above
 // with R = 1, written out.  Through delta_inverse_walk<E, 1> the E = 8 instance measured 0.7 % slower (profiles/
 // layout_bodies.txt), so this kernel keeps its own loop, whose prefetch is decided per lane and issued ahead of the permutation.
-template <int E>
+// FOLD: the unfold between the permutation and the prefix.  A lane past the frame's end holds zeros, their unfold is zeros, so
+// its total is still 0, which the scan relies on.
+template <int E, bool FOLD>
 __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
 {
     typedef typename DeltaSum<E>::T T;
@@ -287,6 +297,8 @@ __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
                     nxt[q] = 0;
             }
             planes_permute<E, true>(in, v); // (lanes past the frame: zeros, a total of 0)
+            if constexpr (FOLD)
+                zigzag_unfold<E>(v);
             const T total = delta_prefix<E>(v);
             const T incl  = delta_wave_scan<T>(total, lane);
             if (lane == 63)
@@ -313,11 +325,11 @@ __global__ void __launch_bounds__(256) k_delta_unplanes(PlanesArgs a)
 }
 
 // Forward, any alignment and block size: source bytes [first, len) of the whole buffer, one per thread.
-template <int E>
+template <int E, bool FOLD>
 __global__ void __launch_bounds__(256) k_delta_planes_bytes(PlanesArgs a)
 {
     for (uint64_t o = a.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < a.len; o += (uint64_t)gridDim.x * blockDim.x)
-        bytes_forward(a.src, a.dst, o, a.len, E, a.block_size, true);
+        bytes_forward(a.src, a.dst, o, a.len, E, a.block_size, true, FOLD);
 }
 
 // The inverse of the byte path: the workgroup walks the frame of L bytes at `base`, 256 elements per iteration, one per
@@ -363,7 +375,7 @@ __device__ __forceinline__ void bytes_inverse_frame(const uint8_t *src, uint8_t 
 }
 
 // Inverse, any alignment and block size: workgroup w takes frames w, w + gridDim.x, ... of [first, len).
-template <int E>
+template <int E, bool FOLD>
 __global__ void __launch_bounds__(256) k_delta_unplanes_bytes(PlanesArgs a)
 {
     __shared__ uint64_t wtot[2][4];
@@ -371,7 +383,7 @@ __global__ void __launch_bounds__(256) k_delta_unplanes_bytes(PlanesArgs a)
     uint32_t row = 0;
     for (uint64_t fi = blockIdx.x; fi < nframes; fi += gridDim.x) {
         const uint64_t base = a.first + fi * frame;
-        bytes_inverse_frame(a.src, a.dst, base, a.len - base < frame ? a.len - base : frame, E, true, wtot, row);
+        bytes_inverse_frame(a.src, a.dst, base, a.len - base < frame ? a.len - base : frame, E, true, wtot, row, FOLD);
     }
 }
 

@@ -13,9 +13,9 @@
 //   redux_static.hpp   k_encode_static / k_decode_static: the coder core under a fixed frequency table
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
-//   redux_zigzag.hpp   k_zigzag_planes / k_zigzag_unplanes: the delta filter with folded differences, for signed series
+//   redux_zigzag.hpp   the zigzag fold: k_delta_*<E, true> is the delta filter with folded differences, for signed series
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
-//   redux_base_sub.hpp k_base_sub_planes / k_base_sub_unplanes: the base filter's folded difference, the same bodies
+//   redux_base_sub.hpp BaseSubFold: the base filter's folded difference, the same kernels under another operation
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
@@ -596,8 +596,9 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
     return REDUX_OK;
 }
 
-// the delta filter: forward as the layout; the inverse a workgroup per frame (a frame's running sum)
-template <int E>
+// the delta filter, its differences folded (FOLD: the zigzag-folded filter) or not: forward as the layout; the inverse a
+// workgroup per frame (a frame's running sum)
+template <int E, bool FOLD>
 static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
 {
     const uint64_t   frame = (uint64_t)E * block_size;
@@ -606,43 +607,17 @@ static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t b
     if (f.nfull) {
         uint32_t grid;
         if (inverse)
-            k_delta_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a);
+            k_delta_unplanes<E, FOLD><<<grid_frames(f.nfull), 256, 0, s>>>(a);
         else if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
         else
-            k_delta_planes<E><<<grid, 256, 0, s>>>(a);
+            k_delta_planes<E, FOLD><<<grid, 256, 0, s>>>(a);
     }
     if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
         if (inverse)
-            k_delta_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
+            k_delta_unplanes_bytes<E, FOLD><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
         else
-            k_delta_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
-}
-
-// the zigzag-folded delta filter: launch_delta's shape with the kernels of redux_zigzag.hpp
-template <int E>
-static int launch_zigzag(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
-{
-    const uint64_t   frame = (uint64_t)E * block_size;
-    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
-    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
-    if (f.nfull) {
-        uint32_t grid;
-        if (inverse)
-            k_zigzag_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a);
-        else if (!grid_tiles((a.groups + 255) / 256, &grid))
-            return REDUX_UNSUPPORTED;
-        else
-            k_zigzag_planes<E><<<grid, 256, 0, s>>>(a);
-    }
-    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
-        if (inverse)
-            k_zigzag_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
-        else
-            k_zigzag_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
+            k_delta_planes_bytes<E, FOLD><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -653,7 +628,7 @@ static int launch_zigzag(const void *d_src, void *d_dst, uint64_t len, uint32_t 
 // nothing to XOR and go to the layout alone (launch_planes).  SUB: the folded difference (redux_base_sub.hpp) in place of
 // the XOR, with the same split: its fused kernels too may only take full frames that lie inside the base, where every
 // element is covered
-template <int E, bool SUB = false>
+template <int E, bool SUB>
 static int launch_base(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
                        bool inverse, hipStream_t s)
 {
@@ -675,14 +650,11 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
         uint32_t grid;
         if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
-        if (SUB && inverse)
-            k_base_sub_unplanes<E><<<grid, 256, 0, s>>>(a);
-        else if (SUB)
-            k_base_sub_planes<E><<<grid, 256, 0, s>>>(a);
-        else if (inverse)
-            k_base_unplanes<E><<<grid, 256, 0, s>>>(a);
+        typedef typename std::conditional<SUB, BaseSubFold<E>, BaseXor>::type OP;
+        if (inverse)
+            k_base_unplanes<E, OP><<<grid, 256, 0, s>>>(a);
         else
-            k_base_planes<E><<<grid, 256, 0, s>>>(a);
+            k_base_planes<E, OP><<<grid, 256, 0, s>>>(a);
     }
     if (a.first < a.end) {
         const uint32_t grid = grid_bytes(a.end - a.first);
@@ -705,13 +677,6 @@ static int launch_base(const void *d_src, const void *d_base, uint64_t base_len,
     return REDUX_OK;
 }
 
-template <int E>
-static int launch_base_sub(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
-                           bool inverse, hipStream_t s)
-{
-    return launch_base<E, true>(d_src, d_base, base_len, d_dst, len, block_size, inverse, s);
-}
-
 // f(std::integral_constant<int, E>) for a checked element size (redux_planes_check)
 template <typename F>
 static int for_element_size(uint32_t element_size, F &&f)
@@ -724,16 +689,19 @@ static int for_element_size(uint32_t element_size, F &&f)
     }
 }
 
-// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev, redux_base_planes_dev and redux_base_sub_planes_dev:
-// the checks, then the transform's launch for the element size.  delta: kNoDelta, kDelta or kZigzag (false / true: the
-// first two).  base: kNoBase, kXorBase or kSubBase (false / true: the first two): the base filter with
-// d_base[0 .. base_len), XOR or the folded difference (not together with delta).
-enum { kNoDelta = 0, kDelta = 1, kZigzag = 2 };
-enum { kNoBase = 0, kXorBase = 1, kSubBase = 2 };
+// The filter in front of the byte-plane layout: none; the delta filter, its differences plain or folded (redux_delta.hpp,
+// redux_zigzag.hpp); the base filter, the XOR or the folded difference (redux_base.hpp, redux_base_sub.hpp).  The one
+// name a filter has from the C entry points down to the kernel launch: a new filter is a new value here.
+enum class Filter { None, Delta, Zigzag, BaseXor, BaseSub };
 
-static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
-                         int inverse, void *stream, int base = kNoBase, const void *d_base = nullptr, uint64_t base_len = 0)
+static bool filter_has_base(Filter f) { return f == Filter::BaseXor || f == Filter::BaseSub; }
+
+// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev, redux_base_planes_dev and redux_base_sub_planes_dev:
+// the checks, then the transform's launch for the element size.  d_base[0 .. base_len): the base of a base filter.
+static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+                         int inverse, void *stream, const void *d_base = nullptr, uint64_t base_len = 0)
 {
+    const bool base = filter_has_base(filter);
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
         return REDUX_INVALID_INPUT;
     if (len == 0)
@@ -749,14 +717,13 @@ static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len
     const bool  inv = inverse != 0;
     return for_element_size(element_size, [&](auto e) -> int {
         constexpr int E = decltype(e)::value;
-        if (base == kSubBase)
-            return launch_base_sub<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        if (base)
-            return launch_base<E>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        if (delta == kZigzag)
-            return launch_zigzag<E>(d_src, d_dst, len, block_size, inv, s);
-        if (delta)
-            return launch_delta<E>(d_src, d_dst, len, block_size, inv, s);
+        switch (filter) {
+        case Filter::BaseSub: return launch_base<E, true>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        case Filter::BaseXor: return launch_base<E, false>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        case Filter::Zigzag: return launch_delta<E, true>(d_src, d_dst, len, block_size, inv, s);
+        case Filter::Delta: return launch_delta<E, false>(d_src, d_dst, len, block_size, inv, s);
+        case Filter::None: break;
+        }
         if constexpr (E == 1) { // the layout of single bytes is the identity
             HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s));
             return REDUX_OK;
@@ -767,29 +734,24 @@ static int transform_dev(int delta, const void *d_src, void *d_dst, uint64_t len
 }
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
-// What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with the delta filter
-// (its differences folded or not) or the base filter (XOR or the folded difference) in front of it, or neither.  The
-// layout of single bytes is the identity; a filter over single bytes is not.
+// What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with a filter in front
+// of it or none.  The layout of single bytes is the identity; a filter over single bytes is not.
 struct Layout {
     uint32_t    E;
-    bool        delta;
-    bool        xor_base = false;   // the base filter, with d_base[0 .. base_len) on the device (not together with delta)
-    const void *d_base   = nullptr;
+    Filter      filter   = Filter::None;
+    const void *d_base   = nullptr; // a base filter's base, d_base[0 .. base_len) on the device
     uint64_t    base_len = 0;
-    bool        fold     = false;   // with delta: the zigzag fold of the differences (redux_zigzag.hpp)
-    bool        sub_base = false;   // with xor_base: the folded difference in place of the XOR (redux_base_sub.hpp)
-    int         filter() const { return delta ? (fold ? kZigzag : kDelta) : kNoDelta; }
-    int         base() const { return xor_base ? (sub_base ? kSubBase : kXorBase) : kNoBase; }
-    bool        identity() const { return !delta && !xor_base && E == 1; }
+    bool        identity() const { return filter == Filter::None && E == 1; }
+    bool        has_base() const { return filter_has_base(filter); }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 0, stream, base(), d_base, base_len);
+        return transform_dev(filter, d_src, d_dst, len, block_size, E, 0, stream, d_base, base_len);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter(), d_src, d_dst, len, block_size, E, 1, stream, base(), d_base, base_len);
+        return transform_dev(filter, d_src, d_dst, len, block_size, E, 1, stream, d_base, base_len);
     }
 };
 
@@ -2289,26 +2251,29 @@ int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const
     return redux_static_decode_blocks_crc(p, cum, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr);
 }
 
-// ---- byte-plane layout (redux_planes.hpp) ---------------------------------------------------------
+// ---- the layered adaptive calls: byte-plane layout, delta, zigzag, base and base_sub ----------------------------------
+// Five families of eight entry points (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_base.hpp,
+// redux_base_sub.hpp), one Filter each: every body below the shared functions is one call into them.
 int redux_planes_check(uint32_t element_size)
 {
     return (element_size == 1 || element_size == 2 || element_size == 4 || element_size == 8) ? REDUX_OK : REDUX_INVALID_INPUT;
 }
+int redux_delta_check(uint32_t element_size) { return redux_planes_check(element_size); }
+int redux_zigzag_check(uint32_t element_size) { return redux_planes_check(element_size); }
+int redux_base_check(uint32_t element_size) { return redux_planes_check(element_size); }
+int redux_base_sub_check(uint32_t element_size) { return redux_planes_check(element_size); }
 
-int redux_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
-                     void *stream)
-{
-    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream);
-}
-
-uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+// (the copy for a filter at E = 1 too: it changes the bytes, so the coder needs the transformed copy; without one, E = 1 is
+// the plain call on the caller's buffer)
+static uint64_t encode_layout_workspace_bytes(Filter f, const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
     if (redux_planes_check(element_size) != REDUX_OK)
         return 0;
     const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? Layout{element_size, false}.copy_bytes(in_len) + ws : 0; // (E = 1: the plain call, on the caller's buffer)
+    return ws ? Layout{element_size, f}.copy_bytes(in_len) + ws : 0;
 }
 
+// (the same for every filter: the plane buffer for every element size, 1 included)
 uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
 {
     if (redux_planes_check(element_size) != REDUX_OK || block_size == 0)
@@ -2318,7 +2283,7 @@ uint64_t redux_decode_planes_workspace_bytes(const redux_params *p, uint64_t out
     return ws ? planes_copy_bytes(nblocks * (uint64_t)block_size) + ws : 0;
 }
 
-// the layered adaptive calls: the layout stage (layout_stage, layout_decode_tail), the plain coder behind it
+// the layout stage (layout_stage, layout_decode_tail), the plain coder behind it
 static int encode_layout_dev(Layout L, const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, void *d_out,
                              uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary, void *d_workspace,
                              uint64_t workspace_bytes, void *stream)
@@ -2327,7 +2292,7 @@ static int encode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
     if (st != REDUX_OK)
         return st;
     if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || (in_len && !d_in) ||
-        (L.xor_base && L.base_len && !L.d_base))
+        (L.has_base() && L.base_len && !L.d_base))
         return REDUX_INVALID_INPUT;
     Staged x;
     if ((st = layout_stage(L, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x)) != REDUX_OK)
@@ -2336,7 +2301,9 @@ static int encode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
                                    x.ws_bytes, stream);
 }
 
-// (the plane buffer for every element size, 1 included: the decoders never write a damaged stream's bytes to d_out)
+// (the plane buffer for every element size, 1 included: the decoders never write a damaged stream's bytes to d_out.  The
+// inverse writes d_out[0 .. out_len) and nothing else: a frame's running sum never leaves the frame, and a base filter writes
+// a byte for every byte of the plane buffer it reads)
 static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
                              uint32_t block_size, void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary,
                              void *d_workspace, uint64_t workspace_bytes, void *stream)
@@ -2345,7 +2312,7 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
     if (st != REDUX_OK)
         return st;
     if (redux_planes_check(L.E) != REDUX_OK || block_size == 0 || !d_workspace || !d_in_offsets || !d_out_sizes || !d_block_status ||
-        (out_len && !d_out) || (L.xor_base && L.base_len && !L.d_base))
+        (out_len && !d_out) || (L.has_base() && L.base_len && !L.d_base))
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
     const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
@@ -2359,28 +2326,12 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
     return layout_decode_tail(L, t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary, TailSummary::InSizes, stream);
 }
 
-int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
-                            void *d_workspace, uint64_t workspace_bytes, void *stream)
-{
-    return encode_layout_dev(Layout{element_size, false}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
-                             d_summary, d_workspace, workspace_bytes, stream);
-}
-
-int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
-                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
-                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
-{
-    return decode_layout_dev(Layout{element_size, false}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
-                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
-}
-
 // The coders of the chunked host calls (redux_host.hpp).  The transformed copy of a chunk goes in front of the adaptive
 // coder's workspace; a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64.
 // The base filter's layout takes the chunk's share of the base from the slot (host::BaseIo).
 static Layout layout_of_slot(Layout L, const host::Slot &s)
 {
-    if (L.xor_base) {
+    if (L.has_base()) {
         L.d_base   = s.d_base.p;
         L.base_len = s.base_len;
     }
@@ -2411,17 +2362,70 @@ static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_si
             true};
 }
 
-int redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
-                                   uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
-                                   uint32_t *block_crc)
+// the host-pointer calls (redux_host.hpp); base[0 .. base_len): a base filter's base, the chunks take their shares of it
+static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
+                                uint64_t base_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
+    const Layout L{element_size, f};
+    if (redux_planes_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) ||
+        (L.has_base() && base_len && !base))
         return REDUX_INVALID_INPUT;
-    const host::EncodeCoder coder = element_size > 1 ? layout_encoder(p, block_size, Layout{element_size, false}) : adaptive_encoder(p, block_size);
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc); // redux_host.hpp
+    const host::EncodeCoder coder = L.identity() ? adaptive_encoder(p, block_size) : layout_encoder(p, block_size, L);
+    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, nullptr, {},
+                               host::BaseIo{base, base_len, L.has_base()});
+}
+
+static int decode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                                uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                                uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    const Layout L{element_size, f};
+    int st = check_params(p);
+    if (st == REDUX_OK && (redux_planes_check(element_size) != REDUX_OK || (L.has_base() && base_len && !base)))
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, layout_decoder(p, block_size, L), block_crc, nullptr, {},
+                              host::BaseIo{base, base_len, L.has_base()});
+}
+
+// -- byte-plane layout
+int redux_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
+                     void *stream)
+{
+    return transform_dev(Filter::None, d_src, d_dst, len, block_size, element_size, inverse, stream);
+}
+
+uint64_t redux_encode_planes_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return encode_layout_workspace_bytes(Filter::None, p, in_len, block_size, element_size);
+}
+
+int redux_encode_planes_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(Layout{element_size}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
+                             d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_planes_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(Layout{element_size}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes, d_block_status,
+                             d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_planes_crc(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                   uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                                   uint32_t *block_crc)
+{
+    return encode_blocks_layout(Filter::None, p, in, in_len, nullptr, 0, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
 }
 
 int redux_encode_blocks_planes(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
@@ -2434,11 +2438,8 @@ int redux_decode_blocks_planes_crc(const redux_params *p, const uint8_t *in, con
                                    uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
                                    uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st == REDUX_OK && redux_planes_check(element_size) != REDUX_OK)
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, false}), block_crc);
+    return decode_blocks_layout(Filter::None, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc);
 }
 
 int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
@@ -2447,22 +2448,16 @@ int redux_decode_blocks_planes(const redux_params *p, const uint8_t *in, const u
     return redux_decode_blocks_planes_crc(p, in, in_offsets, out_len, block_size, element_size, out, out_sizes, block_status, nullptr);
 }
 
-// ---- delta filter (redux_delta.hpp) ---------------------------------------------------------------
-int redux_delta_check(uint32_t element_size) { return redux_planes_check(element_size); }
-
+// -- delta filter
 int redux_delta_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
-                           void *stream)
+                        void *stream)
 {
-    return transform_dev(true, d_src, d_dst, len, block_size, element_size, inverse, stream);
+    return transform_dev(Filter::Delta, d_src, d_dst, len, block_size, element_size, inverse, stream);
 }
 
-// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
 uint64_t redux_encode_delta_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
-    if (redux_delta_check(element_size) != REDUX_OK)
-        return 0;
-    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? Layout{element_size, true}.copy_bytes(in_len) + ws : 0;
+    return encode_layout_workspace_bytes(Filter::Delta, p, in_len, block_size, element_size);
 }
 
 uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2470,64 +2465,47 @@ uint64_t redux_decode_delta_workspace_bytes(const redux_params *p, uint64_t out_
     return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
 }
 
-// (a frame's running sum never leaves the frame, so the inverse writes d_out[0 .. out_len) and nothing else)
 int redux_encode_delta_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                           void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
-                           void *d_workspace, uint64_t workspace_bytes, void *stream)
+                        void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                        void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return encode_layout_dev(Layout{element_size, true}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
-                             d_summary, d_workspace, workspace_bytes, stream);
+    return encode_layout_dev(Layout{element_size, Filter::Delta}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_decode_delta_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
-                           uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
-                           void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                        uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                        void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return decode_layout_dev(Layout{element_size, true}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+    return decode_layout_dev(Layout{element_size, Filter::Delta}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
                              d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_encode_blocks_delta(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                              uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+                           uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_delta_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
-        return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
-                               layout_encoder(p, block_size, Layout{element_size, true}), block_crc); // redux_host.hpp
+    return encode_blocks_layout(Filter::Delta, p, in, in_len, nullptr, 0, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
 }
 
 int redux_decode_blocks_delta(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
-                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
-                              uint32_t *block_crc)
+                           uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                           uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st == REDUX_OK && redux_delta_check(element_size) != REDUX_OK)
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, true}), block_crc);
+    return decode_blocks_layout(Filter::Delta, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc);
 }
 
-// ---- zigzag-folded delta filter (redux_zigzag.hpp) -------------------------------------------------
-static Layout zigzag_layout(uint32_t element_size) { return Layout{element_size, true, false, nullptr, 0, true}; }
-
-int redux_zigzag_check(uint32_t element_size) { return redux_planes_check(element_size); }
-
+// -- zigzag-folded delta filter
 int redux_zigzag_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, int inverse,
-                            void *stream)
+                         void *stream)
 {
-    return transform_dev(kZigzag, d_src, d_dst, len, block_size, element_size, inverse, stream);
+    return transform_dev(Filter::Zigzag, d_src, d_dst, len, block_size, element_size, inverse, stream);
 }
 
-// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
 uint64_t redux_encode_zigzag_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
-    if (redux_zigzag_check(element_size) != REDUX_OK)
-        return 0;
-    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? zigzag_layout(element_size).copy_bytes(in_len) + ws : 0;
+    return encode_layout_workspace_bytes(Filter::Zigzag, p, in_len, block_size, element_size);
 }
 
 uint64_t redux_decode_zigzag_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2535,62 +2513,47 @@ uint64_t redux_decode_zigzag_workspace_bytes(const redux_params *p, uint64_t out
     return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
 }
 
-// (as for delta: a frame's running sum never leaves the frame, so the inverse writes d_out[0 .. out_len) and nothing else)
 int redux_encode_zigzag_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                            void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
-                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+                         void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                         void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return encode_layout_dev(zigzag_layout(element_size), p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets, d_block_status,
-                             d_summary, d_workspace, workspace_bytes, stream);
+    return encode_layout_dev(Layout{element_size, Filter::Zigzag}, p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_decode_zigzag_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len,
-                            uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
-                            void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                         uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes, void *d_block_status,
+                         void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return decode_layout_dev(zigzag_layout(element_size), p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+    return decode_layout_dev(Layout{element_size, Filter::Zigzag}, p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
                              d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_encode_blocks_zigzag(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
-                               uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+                            uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_zigzag_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in))
-        return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
-                               layout_encoder(p, block_size, zigzag_layout(element_size)), block_crc); // redux_host.hpp
+    return encode_blocks_layout(Filter::Zigzag, p, in, in_len, nullptr, 0, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
 }
 
 int redux_decode_blocks_zigzag(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
-                               uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
-                               uint32_t *block_crc)
+                            uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
+                            uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st == REDUX_OK && redux_zigzag_check(element_size) != REDUX_OK)
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, zigzag_layout(element_size)), block_crc);
+    return decode_blocks_layout(Filter::Zigzag, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc);
 }
 
-// ---- XOR-against-base filter (redux_base.hpp) ------------------------------------------------------
-int redux_base_check(uint32_t element_size) { return redux_planes_check(element_size); }
-
+// -- XOR-against-base filter
 int redux_base_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
-                          uint32_t element_size, int inverse, void *stream)
+                       uint32_t element_size, int inverse, void *stream)
 {
-    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream, true, d_base, base_len);
+    return transform_dev(Filter::BaseXor, d_src, d_dst, len, block_size, element_size, inverse, stream, d_base, base_len);
 }
 
-// (E = 1 too: the filter changes the bytes, so the coder needs the transformed copy)
 uint64_t redux_encode_base_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
-    if (redux_base_check(element_size) != REDUX_OK)
-        return 0;
-    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? Layout{element_size, false, true}.copy_bytes(in_len) + ws : 0;
+    return encode_layout_workspace_bytes(Filter::BaseXor, p, in_len, block_size, element_size);
 }
 
 uint64_t redux_decode_base_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2598,115 +2561,85 @@ uint64_t redux_decode_base_workspace_bytes(const redux_params *p, uint64_t out_l
     return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
 }
 
-// (the inverse writes a byte of d_out for every byte of the plane buffer it reads, so d_out[0 .. out_len) and nothing else)
 int redux_encode_base_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
-                          uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
-                          void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                       uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                       void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return encode_layout_dev(Layout{element_size, false, true, d_base, base_len}, p, d_in, in_len, block_size, d_out, out_cap,
+    return encode_layout_dev(Layout{element_size, Filter::BaseXor, d_base, base_len}, p, d_in, in_len, block_size, d_out, out_cap,
                              d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_decode_base_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_base, uint64_t base_len,
-                          uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
-                          void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                       uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
+                       void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return decode_layout_dev(Layout{element_size, false, true, d_base, base_len}, p, d_in, d_in_offsets, out_len, block_size, d_out,
+    return decode_layout_dev(Layout{element_size, Filter::BaseXor, d_base, base_len}, p, d_in, d_in_offsets, out_len, block_size, d_out,
                              d_out_sizes, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_encode_blocks_base(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
-                             uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
-                             int32_t *block_status, uint32_t *block_crc)
+                          uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                          int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_base_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) || (base_len && !base))
-        return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
-                               layout_encoder(p, block_size, Layout{element_size, false, true}), block_crc, nullptr, {},
-                               host::BaseIo{base, base_len, true}); // redux_host.hpp
+    return encode_blocks_layout(Filter::BaseXor, p, in, in_len, base, base_len, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
 }
 
 int redux_decode_blocks_base(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
-                             uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
-                             uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+                          uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                          uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st == REDUX_OK && (redux_base_check(element_size) != REDUX_OK || (base_len && !base)))
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, Layout{element_size, false, true}), block_crc, nullptr,
-                              {}, host::BaseIo{base, base_len, true});
+    return decode_blocks_layout(Filter::BaseXor, p, in, in_offsets, base, base_len, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc);
 }
 
-// ---- folded difference against a base (redux_base_sub.hpp) ------------------------------------------
-// the base calls above with the other operation in the Layout; the workspaces are theirs
-static Layout base_sub_layout(uint32_t element_size, const void *d_base = nullptr, uint64_t base_len = 0)
-{
-    return Layout{element_size, false, true, d_base, base_len, false, true};
-}
-
-int redux_base_sub_check(uint32_t element_size) { return redux_base_check(element_size); }
-
+// -- folded difference against a base
 int redux_base_sub_planes_dev(const void *d_src, const void *d_base, uint64_t base_len, void *d_dst, uint64_t len, uint32_t block_size,
-                              uint32_t element_size, int inverse, void *stream)
+                           uint32_t element_size, int inverse, void *stream)
 {
-    return transform_dev(false, d_src, d_dst, len, block_size, element_size, inverse, stream, kSubBase, d_base, base_len);
+    return transform_dev(Filter::BaseSub, d_src, d_dst, len, block_size, element_size, inverse, stream, d_base, base_len);
 }
 
 uint64_t redux_encode_base_sub_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
-    return redux_encode_base_workspace_bytes(p, in_len, block_size, element_size);
+    return encode_layout_workspace_bytes(Filter::BaseSub, p, in_len, block_size, element_size);
 }
 
 uint64_t redux_decode_base_sub_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
 {
-    return redux_decode_base_workspace_bytes(p, out_len, block_size, element_size);
+    return redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
 }
 
 int redux_encode_base_sub_dev(const redux_params *p, const void *d_in, uint64_t in_len, const void *d_base, uint64_t base_len,
-                              uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
-                              void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                           uint32_t block_size, uint32_t element_size, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                           void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return encode_layout_dev(base_sub_layout(element_size, d_base, base_len), p, d_in, in_len, block_size, d_out, out_cap,
+    return encode_layout_dev(Layout{element_size, Filter::BaseSub, d_base, base_len}, p, d_in, in_len, block_size, d_out, out_cap,
                              d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_decode_base_sub_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, const void *d_base, uint64_t base_len,
-                              uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
-                              void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+                           uint64_t out_len, uint32_t block_size, uint32_t element_size, void *d_out, void *d_out_sizes,
+                           void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
-    return decode_layout_dev(base_sub_layout(element_size, d_base, base_len), p, d_in, d_in_offsets, out_len, block_size, d_out,
+    return decode_layout_dev(Layout{element_size, Filter::BaseSub, d_base, base_len}, p, d_in, d_in_offsets, out_len, block_size, d_out,
                              d_out_sizes, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
 }
 
 int redux_encode_blocks_base_sub(const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base, uint64_t base_len,
-                                 uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
-                                 int32_t *block_status, uint32_t *block_crc)
+                              uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                              int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st != REDUX_OK)
-        return st;
-    if (redux_base_sub_check(element_size) != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) ||
-        (base_len && !base))
-        return REDUX_INVALID_INPUT;
-    return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status,
-                               layout_encoder(p, block_size, base_sub_layout(element_size)), block_crc, nullptr, {},
-                               host::BaseIo{base, base_len, true}); // redux_host.hpp
+    return encode_blocks_layout(Filter::BaseSub, p, in, in_len, base, base_len, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
 }
 
 int redux_decode_blocks_base_sub(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
-                                 uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
-                                 uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+                              uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
+                              uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
 {
-    int st = check_params(p);
-    if (st == REDUX_OK && (redux_base_sub_check(element_size) != REDUX_OK || (base_len && !base)))
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, base_sub_layout(element_size)), block_crc, nullptr,
-                              {}, host::BaseIo{base, base_len, true});
+    return decode_blocks_layout(Filter::BaseSub, p, in, in_offsets, base, base_len, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc);
 }
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------
@@ -2920,7 +2853,7 @@ uint64_t redux_plane_static_encode_workspace_bytes(const redux_params *p, uint64
     if (redux_planes_check(element_size) != REDUX_OK)
         return 0;
     const uint64_t ws = redux_static_encode_workspace_bytes(p, in_len, block_size);
-    return ws ? Layout{element_size, false}.copy_bytes(in_len) + ws : 0;
+    return ws ? Layout{element_size}.copy_bytes(in_len) + ws : 0;
 }
 
 uint64_t redux_plane_static_decode_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
@@ -2976,7 +2909,7 @@ static int tables_static_encode(const redux_params *p, const void *d_cum, uint32
                                 void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
 {
     Staged    x;
-    const int st = layout_stage(Layout{E, false}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x);
+    const int st = layout_stage(Layout{E}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, x);
     if (st != REDUX_OK)
         return st;
     return tables_static_encode_x(p, d_cum, total, x.x, in_len, block_size, E, k, d_out, out_cap, d_out_offsets, d_block_status,
@@ -3043,7 +2976,7 @@ static int tables_static_decode(const redux_params *p, const void *d_cum, uint32
                                           d_block_status, (hipStream_t)stream);
     if (st != REDUX_OK)
         return st;
-    return layout_decode_tail(Layout{E, false}, d_workspace, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+    return layout_decode_tail(Layout{E}, d_workspace, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
                               TailSummary::Summarize, stream);
 }
 
@@ -3320,7 +3253,7 @@ int redux_segment_static_build_encode_dev(const redux_params *p, uint32_t total,
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(in_len, block_size);
     const uint64_t cb      = segment_counts_bytes(redux_segment_static_table_count(nblocks, element_size, segment_blocks));
-    const Layout   L{element_size, false};
+    const Layout   L{element_size};
     if (workspace_bytes < cb + L.copy_bytes(in_len)) // (before the counts are cleared: layout_stage checks its share again)
         return REDUX_OUTPUT_TOO_SMALL;
     uint8_t *counts = (uint8_t *)d_workspace;
@@ -3767,7 +3700,7 @@ uint64_t redux_decode_stored_workspace_bytes(const redux_params *p, uint64_t out
     if (stored_check(p, block_size, element_size) != REDUX_OK)
         return 0;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
-    return Layout{element_size, false}.copy_bytes(nblocks * (uint64_t)block_size) + store_table_bytes(nblocks) +
+    return Layout{element_size}.copy_bytes(nblocks * (uint64_t)block_size) + store_table_bytes(nblocks) +
            redux_decode_workspace_bytes(p, nblocks, block_size);
 }
 
@@ -3784,7 +3717,7 @@ int redux_encode_stored_dev(const redux_params *p, const void *d_in, uint64_t in
         return REDUX_INVALID_INPUT;
     hipStream_t s = (hipStream_t)stream;
     Staged      staged; // (the coder checks the rest: a workspace without the small-grid pairs area will do, geometry_ws)
-    if ((st = layout_stage(Layout{element_size, false}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, staged)) != REDUX_OK)
+    if ((st = layout_stage(Layout{element_size}, d_in, in_len, block_size, d_workspace, workspace_bytes, stream, staged)) != REDUX_OK)
         return st;
     const void    *x   = staged.x;
     uint8_t       *ws  = staged.ws;
@@ -3827,7 +3760,7 @@ int redux_decode_stored_dev(const redux_params *p, const void *d_in, const void 
         return REDUX_INVALID_INPUT;
     hipStream_t    s       = (hipStream_t)stream;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
-    const Layout   L{element_size, false};
+    const Layout   L{element_size};
     const uint64_t copy    = L.copy_bytes(nblocks * (uint64_t)block_size);
     uint8_t       *t       = L.identity() ? (uint8_t *)d_out : (uint8_t *)d_workspace;
     redux_block   *table   = (redux_block *)((uint8_t *)d_workspace + copy);
@@ -3868,7 +3801,7 @@ static host::EncodeCoder stored_encoder(const redux_params *p, uint32_t block_si
     const host::EncodeCoder plain = adaptive_encoder(p, block_size);
     return {[=](uint64_t max_in, bool several, uint64_t &ws, uint64_t &bound) {
                 plain.size(max_in, several, ws, bound);
-                ws += Layout{element_size, false}.copy_bytes(max_in);
+                ws += Layout{element_size}.copy_bytes(max_in);
             },
             [=](host::Slot &s, uint64_t len, uint64_t bound, void *ws, uint64_t ws_bytes, hipStream_t st) {
                 return redux_encode_stored_dev(p, s.d_in.p, len, block_size, element_size, store_ratio, s.d_out.p, bound, s.d_off.p,
@@ -3917,7 +3850,7 @@ static int const_check(const redux_params *p, uint32_t block_size, uint32_t elem
 // x' of a call: the byte-plane layout, behind the XOR against the base when there is one (base_len 0: no base)
 static Layout const_layout(uint32_t element_size, const void *d_base, uint64_t base_len)
 {
-    return base_len ? Layout{element_size, false, true, d_base, base_len} : Layout{element_size, false};
+    return base_len ? Layout{element_size, Filter::BaseXor, d_base, base_len} : Layout{element_size};
 }
 
 static int launch_const_select(const void *d_in, uint64_t in_len, uint32_t block_size, void *d_flags, hipStream_t s)
@@ -4488,7 +4421,7 @@ int redux_decode_mixed_dev(const redux_params *p, const void *d_in, const void *
                                 d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr, BlockTable{});
     if (st != REDUX_OK)
         return st;
-    st = layout_decode_tail(Layout{1, false}, nullptr, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
+    st = layout_decode_tail(Layout{1}, nullptr, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary,
                             TailSummary::InSizes, stream);
     if (st != REDUX_OK)
         return st;

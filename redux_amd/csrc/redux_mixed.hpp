@@ -142,10 +142,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
         case 1: mixed_forward<2, PlainForward<2>>(src, dst, fg, B, wg, W, lds); break;
         case 2: mixed_forward<4, PlainForward<4>>(src, dst, fg, B, wg, W, lds); break;
         case 3: mixed_forward<8, PlainForward<8>>(src, dst, fg, B, wg, W, lds); break;
-        case 4: mixed_forward<1, DeltaForward<1>>(src, dst, fg, B, wg, W, lds); break;
-        case 5: mixed_forward<2, DeltaForward<2>>(src, dst, fg, B, wg, W, lds); break;
-        case 6: mixed_forward<4, DeltaForward<4>>(src, dst, fg, B, wg, W, lds); break;
-        default: mixed_forward<8, DeltaForward<8>>(src, dst, fg, B, wg, W, lds); break;
+        case 4: mixed_forward<1, DeltaForward<1, false>>(src, dst, fg, B, wg, W, lds); break;
+        case 5: mixed_forward<2, DeltaForward<2, false>>(src, dst, fg, B, wg, W, lds); break;
+        case 6: mixed_forward<4, DeltaForward<4, false>>(src, dst, fg, B, wg, W, lds); break;
+        default: mixed_forward<8, DeltaForward<8, false>>(src, dst, fg, B, wg, W, lds); break;
         }
     } else {
         switch (k) {

@@ -146,7 +146,7 @@ __device__ __forceinline__ void plane_store(uint8_t *fbase, uint32_t block_size,
 
 // What a filter on the elements does in the forward tile: `before` runs ahead of the barrier and its result crosses it,
 // `apply` works on the lane's 16 elements in front of the permutation.  This one is no filter; DeltaForward
-// (redux_delta.hpp) and ZigzagForward (redux_zigzag.hpp) are the others.
+// (redux_delta.hpp), with or without the fold, is the other.
 template <int E>
 struct PlainForward {
     struct Pred {};

@@ -1,13 +1,7 @@
-// redux_zigzag.hpp -- the zigzag-folded delta filter for signed series, fused with the byte-plane layout: the delta filter
-// (redux_delta.hpp) with every difference folded so that small magnitudes of either sign become small unsigned numbers.
-//
-//   k_zigzag_planes<E>          forward, full frames: the forward tile (redux_planes.hpp) with ZigzagForward in front of the
-//                               permutation: DeltaForward's predecessor rule and subtraction, then the fold of the lane's 16
-//                               elements in registers; one read and one write
-//   k_zigzag_unplanes<E>        inverse, full frames: the frame walk of k_delta_unplanes with the unfold between the
-//                               permutation and the serial prefix
-//   k_zigzag_planes_bytes<E>    the byte path, one element per thread: bytes_forward (redux_planes.hpp) and
-//   k_zigzag_unplanes_bytes<E>  bytes_inverse_frame (redux_delta.hpp) with the fold on
+// redux_zigzag.hpp -- the zigzag fold: every difference folded so that small magnitudes of either sign become small unsigned
+// numbers.  The arithmetic alone: the delta kernels (redux_delta.hpp) take it as their compile-time FOLD, which makes them
+// the zigzag-folded delta filter for signed series, and the folded difference against a base (redux_base_sub.hpp) folds
+// with it too.
 //
 // Rule (E, B and the frames as for the delta filter): d[0] = x[0], d[i] = x[i] - x[i-1] mod 2^(8E);
 // z[i] = (d[i] << 1) ^ (0 - (d[i] >> (8E-1))) mod 2^(8E) for every i, 0 included: read as signed, d >= 0 maps to 2d and
@@ -23,10 +17,10 @@
 // before the shift and the sign bit (fold) or low bit (unfold) spread into a whole-element mask, so nothing crosses an
 // element boundary; E = 8 is the same on 64-bit values.
 //
-// Included by redux_hip.hip (one translation unit).
+// Included by redux_delta.hpp.
 #pragma once
 
-#include "redux_delta.hpp"
+#include "redux_planes.hpp"
 
 namespace redux {
 
@@ -91,114 +85,6 @@ __device__ __forceinline__ void zigzag_unfold(uint32_t (&v)[4 * E])
 #pragma unroll
         for (int j = 0; j < 4 * E; j++)
             v[j] = zigzag_unfold_dword<E>(v[j]);
-    }
-}
-
-// The forward tile's filter: DeltaForward's predecessor rule and differences, then the fold.
-template <int E>
-struct ZigzagForward {
-    typedef typename DeltaForward<E>::Pred Pred;
-    __device__ __forceinline__ static Pred before(const uint8_t *src, uint64_t g, bool inside, uint32_t lane)
-    {
-        return DeltaForward<E>::before(src, g, inside, lane);
-    }
-    __device__ __forceinline__ static void apply(const uint4 *row, uint32_t lane, bool inside, Pred prev, uint32_t (&v)[4 * E])
-    {
-        DeltaForward<E>::apply(row, lane, inside, prev, v);
-        zigzag_fold<E>(v);
-    }
-};
-
-// Forward, full frames: the forward tile with the subtraction and the fold in front of the permutation.
-template <int E>
-__global__ void __launch_bounds__(256) k_zigzag_planes(PlanesArgs a)
-{
-    __shared__ uint4 lds[4 * 64 * E];
-    tile_forward<E, ZigzagForward<E>, 1>(a.src, a.dst, a.groups, (uint64_t)blockIdx.x * blockDim.x, a.frame_groups, a.block_size, lds,
-                                         TileNoHook());
-}
-
-// Inverse, full frames: k_delta_unplanes' frame walk (one workgroup per frame, one row of 256 groups per iteration, the
-// next row's plane loads in flight across the scan) with the unfold between the permutation and the prefix.  A lane past
-// the frame's end holds zeros, their unfold is zeros, so its total is still 0, which the scan relies on.
-template <int E>
-__global__ void __launch_bounds__(256) k_zigzag_unplanes(PlanesArgs a)
-{
-    typedef typename DeltaSum<E>::T T;
-    __shared__ uint4 lds[4 * 64 * E];
-    __shared__ T     wtot[2][4];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint4 *wl = lds + wave * 64 * E;
-    const uint64_t nframes = a.groups / a.frame_groups;
-    uint32_t row = 0;
-    for (uint64_t f = blockIdx.x; f < nframes; f += gridDim.x) {
-        const uint64_t fbase = f * (uint64_t)E * a.block_size;
-        T        carry = 0; // the sum of the frame's elements before this iteration
-        uint32_t nxt[4 * E];
-#pragma unroll
-        for (int q = 0; q < 4 * E; q++)
-            nxt[q] = 0;
-        if (threadIdx.x < a.frame_groups)
-            plane_load<E>(a.src + fbase, a.block_size, threadIdx.x, nxt);
-        for (uint32_t i0 = 0; i0 < a.frame_groups; i0 += 256, row ^= 1) {
-            const uint32_t i    = i0 + threadIdx.x;
-            const bool     live = i < a.frame_groups;
-            uint32_t in[4 * E], v[4 * E];
-#pragma unroll
-            for (int q = 0; q < 4 * E; q++)
-                in[q] = nxt[q];
-            if ((uint64_t)i + 256 < a.frame_groups) {
-                plane_load<E>(a.src + fbase, a.block_size, (uint64_t)i + 256, nxt);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4 * E; q++)
-                    nxt[q] = 0;
-            }
-            planes_permute<E, true>(in, v); // (lanes past the frame: zeros, unfolded to zeros, a total of 0)
-            zigzag_unfold<E>(v);
-            const T total = delta_prefix<E>(v);
-            const T incl  = delta_wave_scan<T>(total, lane);
-            if (lane == 63)
-                wtot[row][wave] = incl;
-            __syncthreads();
-            T before = carry + incl - total;
-#pragma unroll
-            for (uint32_t w = 0; w < 4; w++) {
-                const T t = wtot[row][w];
-                before += w < wave ? t : 0;
-                carry += t;
-            }
-            delta_offset<E>(v, before);
-            if (live)
-                tile_put<E>(wl, lane, v);
-            __syncthreads();
-            const uint32_t w0 = i0 + wave * 64; // the wave's first group of the frame
-            if (w0 < a.frame_groups) {
-                const uint32_t left = a.frame_groups - w0;
-                tile_stage_out<E>(wl, (uint4 *)(a.dst + fbase + (uint64_t)w0 * 16 * E), (left < 64 ? left : 64) * E, lane, TileNoHook());
-            }
-        }
-    }
-}
-
-// Forward, any alignment and block size: source bytes [first, len) of the whole buffer, one per thread.
-template <int E>
-__global__ void __launch_bounds__(256) k_zigzag_planes_bytes(PlanesArgs a)
-{
-    for (uint64_t o = a.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < a.len; o += (uint64_t)gridDim.x * blockDim.x)
-        bytes_forward(a.src, a.dst, o, a.len, E, a.block_size, true, true);
-}
-
-// Inverse, any alignment and block size: workgroup w takes frames w, w + gridDim.x, ... of [first, len).
-template <int E>
-__global__ void __launch_bounds__(256) k_zigzag_unplanes_bytes(PlanesArgs a)
-{
-    __shared__ uint64_t wtot[2][4];
-    const uint64_t frame = (uint64_t)E * a.block_size, nframes = (a.len - a.first + frame - 1) / frame;
-    uint32_t row = 0;
-    for (uint64_t fi = blockIdx.x; fi < nframes; fi += gridDim.x) {
-        const uint64_t base = a.first + fi * frame;
-        bytes_inverse_frame(a.src, a.dst, base, a.len - base < frame ? a.len - base : frame, E, true, wtot, row, true);
     }
 }
 

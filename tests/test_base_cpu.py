@@ -225,9 +225,11 @@ def test_python_api_refuses_the_base_where_it_is_not_available_before_any_librar
     for i, call in enumerate(calls):
         with pytest.raises(rx.InvalidInput):
             call()
-    assert api._check_base(None) is False and api._check_base(b"") is True and api._check_base(None, False) is False
+    flags = np.zeros(1, np.uint8)
+    assert api._resolve_front(None).front.takes_base is False and api._resolve_front(None, base=b"").front.takes_base is True \
+        and api._resolve_front(None, stored=flags).front.takes_base is False
     with pytest.raises(rx.InvalidInput):
-        api._check_base(b"", False)
+        api._resolve_front(None, base=b"", stored=flags)
 
 
 # ---- CLI -----------------------------------------------------------------------------------------------------------------

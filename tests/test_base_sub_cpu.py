@@ -328,8 +328,9 @@ def test_python_api_refuses_base_op_before_any_library_call(rx, monkeypatch):
     for i, call in enumerate(calls):
         with pytest.raises(rx.InvalidInput):
             call()
-    assert api._check_base_op("xor", None) is False and api._check_base_op("xor", y) is False and api._check_base_op("sub", y) is True
-    assert api._check_base_op("xor", y, True) is False and api._check_base_op("sub", y, False) is True
+    front = lambda op, base, constant=None: api._resolve_front(None, base=base, base_op=op, constant=constant).front.infix
+    assert front("xor", None) == "planes" and front("xor", y) == "base" and front("sub", y) == "base_sub"
+    assert front("xor", y, True) == "base" and front("sub", y, False) == "base_sub"
     # base_op is the last keyword wherever base= is taken
     import inspect
     for f in (rx.compress_blocks, rx.decompress_blocks, rx.DeviceEncoder.__init__, rx.DeviceDecoder.__init__, container.compress_bytes,

@@ -216,10 +216,11 @@ def test_python_api_refuses_the_option_where_it_is_not_available_before_any_libr
     for i, call in enumerate(calls):
         with pytest.raises(rx.InvalidInput):
             call()
-    assert api._check_constant(None) is False and api._check_constant(False) is False and api._check_constant(None, False) is False
-    assert api._check_constant(True) is True and api._check_constant(flags) is True
+    const = lambda constant, **kw: api._resolve_front(None, constant=constant, **kw).constant
+    assert const(None) is False and const(False) is False and const(None, stored=flags) is False
+    assert const(True) is True and const(flags) is True
     with pytest.raises(rx.InvalidInput):
-        api._check_constant(True, False)
+        const(True, stored=flags)
 
 
 # ---- CLI -----------------------------------------------------------------------------------------------------------------

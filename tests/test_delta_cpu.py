@@ -263,7 +263,7 @@ def test_python_api_refuses_the_filter_where_it_is_not_available_before_any_libr
     for i, call in enumerate(calls):
         with pytest.raises(rx.InvalidInput):
             call()
-    assert api._check_filter(None) is False and api._check_filter("delta") is True
+    assert api._resolve_front(None).front.infix == "planes" and api._resolve_front(None, filter="delta").front.infix == "delta"
 
 
 # ---- host-only ABI helpers -----------------------------------------------------------------------------------------------

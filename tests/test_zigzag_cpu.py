@@ -257,11 +257,12 @@ def test_python_api_refuses_the_filter_wherever_it_refuses_delta_before_any_libr
         with pytest.raises(rx.InvalidInput):
             rx.DeviceEncoder((8, 30, 32), 4096, 4096, filter=f)
         with pytest.raises(rx.InvalidInput):
-            api._check_filter(f)
-    assert api._check_filter(None) is False and api._check_filter("delta") is True
-    assert api._check_filter("zigzag") and api._zigzag(api._check_filter("zigzag")) and not api._zigzag(api._check_filter("delta"))
+            api._resolve_front(None, filter=f)
+    front = lambda f: api._resolve_front(None, filter=f).front.infix
+    assert front(None) == "planes" and front("delta") == "delta"
+    assert front("zigzag") == "zigzag" and front("zigzag") != front("delta")
     with pytest.raises(rx.InvalidInput):
-        api._check_filter("zigzag", False)
+        api._resolve_front(None, filter="zigzag", stored=flags)
 
 
 # ---- host-only ABI helpers -----------------------------------------------------------------------------------------------
