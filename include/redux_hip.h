@@ -462,6 +462,52 @@ int redux_decode_blocks_zigzag(const redux_params *p, const uint8_t *in, const u
                                uint32_t block_size, uint32_t element_size, uint8_t *out, uint32_t *out_sizes, int32_t *block_status,
                                uint32_t *block_crc);
 
+/* ---- lagged delta filter for interleaved channels and fixed-width records ----------------------
+ * Both delta filters take the difference to the element directly before.  Where several series are interleaved -- stereo or
+ * multi-channel PCM, IMU and ADC logs, (x, y, z) vertex arrays, RGB(A) pixels, row-major tables of fixed-width records --
+ * that element belongs to another channel and the difference is larger than the value; the right predecessor sits S
+ * elements back (TIFF's predictor, PNG's Sub filter with its bytes per pixel and FLAC's per-channel prediction are the same
+ * idea).  These calls are the zigzag-folded delta filter with a lag S, 1 <= S <= REDUX_LAG_MAX.  Strictly opt-in: a wrong
+ * lag costs bytes, and no call chooses one.  E, B and the frames are the delta filter's.
+ *   - d[i] = x[i] for i < S, d[i] = x[i] - x[i-S] mod 2^(8E) for i >= S.
+ *   - z[i] is the zigzag fold of d[i] (above), always: there is no unfolded form.  The L - N*E trailing bytes of a frame
+ *     are unchanged.
+ *   - The byte-plane layout is then applied to the z's (E = 1: no layout).
+ *   - The inverse undoes the layout, unfolds, then x[i] = d[i] + x[i-S]: S independent running sums per frame.
+ *   - Every frame starts afresh, so the blocks of different frames stay independent.  S >= N is legal: it folds every
+ *     element and subtracts nothing.  S = 1 is the zigzag filter, byte for byte.
+ * Behind the transform is the plain adaptive coder:
+ *     stream_lag_E_S(x)[b] == redux_encode_blocks(planes_E(lag_E_S(x)))[b].
+ * Not available where the zigzag filter is not.
+ *
+ * Every call is the shape of its zigzag namesake with `lag` after element_size, and keeps its promises:
+ * redux_decode_lag_dev writes no byte outside d_out[0 .. out_len), for damaged streams too, and every frame whose blocks are
+ * all OK holds the original bytes; the host-pointer pair cuts its chunks at frame boundaries, so its output depends on
+ * neither the chunk size nor the devices, and block_crc is over the ORIGINAL bytes.  A lag of 0 or above REDUX_LAG_MAX is
+ * REDUX_INVALID_INPUT wherever a bad element size is, and nothing is written.  The workspace calls take no lag and return
+ * their zigzag namesakes' values.  redux_lag_planes_dev reads the source once from memory and once more from cache, and
+ * reads no byte before a frame's first.
+ */
+#define REDUX_LAG_MAX 256
+int      redux_lag_check(uint32_t element_size, uint32_t lag);
+int      redux_lag_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, uint32_t lag,
+                              int inverse, void *stream);
+uint64_t redux_encode_lag_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_lag_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_lag_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                         uint32_t lag, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                         void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                         void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_lag_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                         uint32_t block_size, uint32_t element_size, uint32_t lag, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                         void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_lag(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                            uint32_t element_size, uint32_t lag, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                            int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_lag(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, uint32_t lag, uint8_t *out, uint32_t *out_sizes,
+                            int32_t *block_status, uint32_t *block_crc);
+
 /* ---- XOR-against-base filter for series of snapshots -------------------------------------------
  * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its
  * base model, optimizer state, a KV cache against its earlier self -- differs from its predecessor only in the low mantissa

@@ -202,6 +202,17 @@ def _family(infix, base, transform=None, blocks=None):
 SIGNATURES.update(_family("planes", False, transform="redux_planes_dev", blocks="planes_crc"))
 for _infix, _base in (("delta", False), ("zigzag", False), ("base", True), ("base_sub", True)):
     SIGNATURES.update(_family(_infix, _base))
+# the lagged delta filter: the zigzag family with the lag behind the element size (the workspace sizes take none)
+SIGNATURES.update({
+    "redux_lag_check": (C.c_int, [_U32, _U32]),
+    "redux_lag_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, _U32, C.c_int, _V]),
+    "redux_encode_lag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_lag_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_lag_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_lag_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_lag": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_lag": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _V, _V, _V, _V]),
+})
 
 _LIB = None
 

@@ -509,11 +509,14 @@ def _check_element_size(element_size):
 # The filter in front of the byte-plane layout, as the C entry points name it (include/redux_hip.h): the infix of
 # redux_{encode,decode}_{infix}_{dev,workspace_bytes}, redux_{encode,decode}_blocks_{infix} and redux_{infix}_planes_dev,
 # whether those take a (base, base_len) pair, and whether decoding needs the length for every element size.  A new filter
-# is a new row here (and a Filter value in redux_hip.hip, and a version row in container.py).
-_Front = namedtuple("_Front", "infix takes_base needs_length")
+# is a new row here (and a Filter value in redux_hip.hip, and a version row in container.py).  lag: the lag of the lagged
+# delta filter, which its entry points take behind the element size; None for every other front.
+_Front = namedtuple("_Front", "infix takes_base needs_length lag", defaults=(None,))
 _PLANES = _Front("planes", False, False)                                 # no filter: the layout alone (none for element size 1)
 _FILTERS = {"delta": _Front("delta", False, True),                       # filter="delta": the delta filter for integer series
-            "zigzag": _Front("zigzag", False, True)}                     # filter="zigzag": the same with folded differences
+            "zigzag": _Front("zigzag", False, True),                     # filter="zigzag": the same with folded differences
+            "lag": _Front("lag", False, True)}                           # filter="lag", lag=S: the predecessor S elements back
+LAG_MAX = 256  # REDUX_LAG_MAX
 _BASE_OPS = {"xor": _Front("base", True, True),                          # base=: the XOR against the base
              "sub": _Front("base_sub", True, True)}                      # base=, base_op="sub": the folded difference
 
@@ -524,11 +527,12 @@ _STATIC_MODELS = (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStat
 
 
 def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor", constant=None, stored=None, unit_layouts=None,
-                   device=False):
+                   device=False, lag=None):
     """The one place that says which of filter=, base=, base_op=, constant=, stored=, unit_layouts= and the model's kind go
     together; anything else is InvalidInput.  A check on the arguments alone: it touches neither the library nor torch,
     so it comes before any call into either.  -> _Resolved.
-    filter: None, "delta" or "zigzag"; with the adaptive model only, and not with stored blocks.
+    filter: None, "delta", "zigzag" or "lag"; with the adaptive model only, and not with stored blocks.
+    lag: with filter="lag" and only with it, an int in 1 .. LAG_MAX; the _Front returned carries it.
     base: None or a base; as a filter, and not together with one.  base_op: "xor" or "sub", "sub" only with a base and
     without the constant-block option.
     constant: None / False, or the option (True, or the flags); adaptive model only, with or without a base, not with a
@@ -539,6 +543,9 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     static = isinstance(params, _STATIC_MODELS)
     const = not (constant is None or constant is False)
     mixed = unit_layouts is not None
+    if (lag is not None) != (isinstance(filter, str) and filter == "lag") or (lag is not None and (
+            isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= LAG_MAX)):
+        raise InvalidInput()
     if not isinstance(base_op, str) or base_op not in _BASE_OPS or (base_op == "sub" and (base is None or const)):
         raise InvalidInput()
     if mixed and (static or not isinstance(element_size, (int, np.integer)) or element_size != 1 or filter is not None
@@ -552,6 +559,8 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     if filter is not None and (not filtered or not isinstance(filter, str) or filter not in _FILTERS):
         raise InvalidInput()
     front = _FILTERS[filter] if filter is not None else _BASE_OPS[base_op] if base is not None else _PLANES
+    if lag is not None:
+        front = front._replace(lag=int(lag))
     return _Resolved(front, const, mixed)
 
 
@@ -560,6 +569,11 @@ def _no_front(filter=None, constant=None):
     r = _resolve_front(None, filter=filter, constant=constant)
     if r.front is not _PLANES or r.constant:
         raise InvalidInput()
+
+
+def _lag_arg(front):
+    """what a _Front's entry points take behind the element size: the lag of the lagged delta filter, or nothing"""
+    return () if front.lag is None else (front.lag,)
 
 
 def _blocks_entry(L, direction, front):
@@ -652,7 +666,7 @@ def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
                     store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None,
-                    base_op="xor"):
+                    lag=None, base_op="xor"):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -674,6 +688,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     Adaptive model only, and not with stored=.
     filter="zigzag": the delta filter with its differences folded, for series that move both ways (include/redux_hip.h,
     "zigzag-folded delta filter": redux_encode_blocks_zigzag); accepted and refused exactly where "delta" is.
+    filter="lag", lag=S (1 .. 256): the zigzag filter with the predecessor S elements back, for S interleaved channels or
+    records of S columns (include/redux_hip.h, "lagged delta filter": redux_encode_blocks_lag); accepted and refused where
+    "zigzag" is.  A lag without filter="lag", or filter="lag" without one, is InvalidInput.
     base: bytes-like of any length, an earlier snapshot of the same data; the XOR against it is coded, for any element_size
     (include/redux_hip.h, "XOR-against-base filter": redux_encode_blocks_base); decompress_blocks(..., element_size, length,
     base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=.
@@ -690,7 +707,7 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     base_op: "xor" (the default), or "sub" with base=: the folded difference of the elements against the base in place of
     the XOR (include/redux_hip.h, "folded difference against a base": redux_encode_blocks_base_sub);
     decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=."""
-    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
     if mixed:
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
     if layouts is not None:
@@ -750,7 +767,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     else:  # the adaptive coder behind the front's filter (none, and element size 1, included: the coder without a layout)
         y = _u8(base) if front.takes_base else None
         st = _blocks_entry(L, "encode", front)(C.byref(cp), _ptr(a), len(a), *((_ptr(y), len(y)) if front.takes_base else ()),
-                                               block_size, E, out.ctypes.data, cap, offs.ctypes.data, status.ctypes.data, crc)
+                                               block_size, E, *_lag_arg(front), out.ctypes.data, cap, offs.ctypes.data,
+                                               status.ctypes.data, crc)
     _raise(st)
     if constant is True:
         return out[: int(offs[-1])], offs, status, cflags
@@ -768,7 +786,8 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, base_op="xor"):
+                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, lag=None,
+                      base_op="xor"):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -786,7 +805,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     uint8[length] in original order, as with element_size > 1.
     filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
     for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.  filter="zigzag":
-    the same for compress_blocks(..., filter="zigzag")'s streams (redux_decode_blocks_zigzag).
+    the same for compress_blocks(..., filter="zigzag")'s streams (redux_decode_blocks_zigzag).  filter="lag", lag=S: the
+    same for compress_blocks(..., filter="lag", lag=S)'s (redux_decode_blocks_lag).
     base: the bytes compress_blocks(..., base=) was given (redux_decode_blocks_base); length is required for every
     element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=.
     constant: the np.uint8[nblocks] flags compress_blocks(..., constant=) wrote (redux_decode_blocks_const), with the
@@ -795,7 +815,7 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
     required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
     base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub)."""
-    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
     if mixed:
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
@@ -852,7 +872,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif length is not None:  # the adaptive coder behind the front's filter, or behind the layout alone
         y = _u8(base) if front.takes_base else None
         st = _blocks_entry(L, "decode", front)(C.byref(cp), _ptr(a), offs.ctypes.data, *((_ptr(y), len(y)) if front.takes_base else ()),
-                                               length, block_size, E, out.ctypes.data, sizes.ctypes.data, status.ctypes.data, crc)
+                                               length, block_size, E, *_lag_arg(front), out.ctypes.data, sizes.ctypes.data,
+                                               status.ctypes.data, crc)
     else:
         st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
                                        sizes.ctypes.data, status.ctypes.data, crc)
@@ -1229,13 +1250,14 @@ class DeviceEncoder(_DeviceCoder):
     the coder's input whose bytes are all equal skip the coder (include/redux_hip.h, "constant blocks"), with or without
     base=, not together with filter=; encode() then returns the u8 flags as a fifth value.  base_op="sub" with base=: the
     folded difference of the elements against the base in place of the XOR (include/redux_hip.h, "folded difference against a
-    base"); not together with constant=True."""
+    base"); not together with constant=True.  filter="lag", lag=S: the lagged delta filter (include/redux_hip.h, "lagged delta
+    filter"), where filter="zigzag" may stand."""
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, layouts=None, base_op="xor"):
+                 mixed=False, layouts=None, lag=None, base_op="xor"):
         # (mixed: with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
-                                                               unit_layouts=True if mixed else None, device=True)
+                                                               unit_layouts=True if mixed else None, device=True, lag=lag)
         if self.mixed:
             self.mixed_mask = _layout_mask(layouts)
         elif layouts is not None:
@@ -1264,7 +1286,7 @@ class DeviceEncoder(_DeviceCoder):
         else:  # the layered entry points of the front's family
             ws_bytes = getattr(L, "redux_encode_%s_workspace_bytes" % self.front.infix)
             self._encode_dev = getattr(L, "redux_encode_%s_dev" % self.front.infix)
-            self._lead = (*(_base_pair(self.base) if self.front.takes_base else ()), B, E)
+            self._lead = (*(_base_pair(self.base) if self.front.takes_base else ()), B, E, *_lag_arg(self.front))
         ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, E)
         if (self.constant or self.mixed) and ws_bytes == 0:
             raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
@@ -1333,13 +1355,14 @@ class DeviceDecoder(_DeviceCoder):
     for the delta filter with folded differences (include/redux_hip.h, "zigzag-folded delta filter").  base: the uint8 device
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
     streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags)).
-    base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s."""
+    base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s.  filter="lag", lag=S: the streams are
+    DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"."""
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, base_op="xor"):
+                 mixed=False, lag=None, base_op="xor"):
         # (mixed: the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
-                                                               unit_layouts=True if mixed else None, device=True)
+                                                               unit_layouts=True if mixed else None, device=True, lag=lag)
         torch = _torch()
         self.base = _device_base(torch, base, device)
         P = _params_of(params)
@@ -1424,7 +1447,7 @@ class DeviceDecoder(_DeviceCoder):
                 self._alloc_workspace(self._layout_ws_bytes(self.max_in_len))
             decode_dev = self._decode_dev
             lead = _base_pair(base) if self._takes_base else self._lead
-            args = (*flags, *lead, nbytes, self.block_size, self.element_size, self.out.data_ptr())
+            args = (*flags, *lead, nbytes, self.block_size, self.element_size, *_lag_arg(self.front), self.out.data_ptr())
         self.summary.zero_()
         _raise(decode_dev(C.byref(self.cp), d_streams.data_ptr(), d_offsets.data_ptr(), *args, *self._dec_tail()))
         return self._dec_result(nbytes, nb)
@@ -1779,8 +1802,8 @@ def _transform(front, d_src, element_size, block_size, inverse, out, d_base=None
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
     base = _base_pair(d_base) if front.takes_base else ()
     with torch.cuda.device(t.device):
-        _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, E, 1 if inverse else 0,
-                                         _stream_ptr(torch)))
+        _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, E, *_lag_arg(front),
+                                         1 if inverse else 0, _stream_ptr(torch)))
     return t
 
 
@@ -1800,6 +1823,12 @@ def zigzag_planes(d_src, element_size, block_size, inverse=False, out=None):
     """The zigzag-folded delta filter followed by the byte-plane layout (include/redux_hip.h, "zigzag-folded delta filter")
     of a uint8 device tensor, or their inverse: redux_zigzag_planes_dev on torch's current stream.  out: as for planes()."""
     return _transform(_resolve_front(None, filter="zigzag").front, d_src, element_size, block_size, inverse, out)
+
+
+def lag_planes(d_src, element_size, block_size, lag, inverse=False, out=None):
+    """The lagged delta filter followed by the byte-plane layout (include/redux_hip.h, "lagged delta filter") of a uint8
+    device tensor, or their inverse: redux_lag_planes_dev on torch's current stream.  lag: 1 .. 256.  out: as for planes()."""
+    return _transform(_resolve_front(None, filter="lag", lag=lag).front, d_src, element_size, block_size, inverse, out)
 
 
 def _device_unit_table(torch, table, nunits, device):

@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag] [--lag S] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -55,6 +55,14 @@ signals, random walks, offsets that go back and forth -- whose small negative di
 every upper byte plane; an int64 signal comes out at about half the size of `--filter delta`, a monotone series at the
 same size.  `--layout auto` does not choose it.  -d and -d `--range` read version 11 with no flag.  With `--block-size 0`,
 `--stored`, `--base`, `--skip-constant`, `--layout` or a `--model` other than adaptive it is a usage error.
+`--filter lag --lag S` (the rules of `--filter zigzag`; S from 1 to 256) takes the folded difference to the element S back
+instead of the one directly before (container version 13, which records S): for S interleaved channels -- stereo or
+multi-channel PCM, IMU and ADC logs, (x, y, z) vertex arrays, RGB(A) pixels -- and row-major tables of records of S columns,
+where the element before belongs to another series and `--filter delta` or `zigzag` makes the file larger.  On interleaved
+int16 / int32 random walks it comes out at 0.54 to 0.65 of the best of plain, planes, delta and zigzag; a wrong lag costs up
+to 10 % over them, so nothing chooses it, or S, for you.  `--lag 1` is `--filter zigzag` under another version number.  -d
+and -d `--range` read version 13 with no flag.  `--lag` without `--filter lag`, `--filter lag` without `--lag`, and an S that
+is no decimal number from 1 to 256 are usage errors.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -103,7 +111,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag>] [--lag <1..256>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -122,7 +130,7 @@ def parse(argv):
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range",
-                     "--base-op"):
+                     "--base-op", "--lag"):
             val = next(it, None)
             if val is None:
                 return None
@@ -139,9 +147,13 @@ def parse(argv):
                     return None
                 opts["model"] = val
             elif arg == "--filter":
-                if val not in ("delta", "zigzag"):
+                if val not in ("delta", "zigzag", "lag"):
                     return None
                 opts["filter"] = val
+            elif arg == "--lag":
+                if not (val.isascii() and val.isdigit()) or not 1 <= int(val) <= 256:
+                    return None
+                opts["lag"] = int(val)
             elif arg == "--base":
                 opts["base"] = val
             elif arg == "--base-op":
@@ -192,6 +204,8 @@ def parse(argv):
         return None  # the bitmap lives in the container, and the static decoder has no table form
     if "filter" in opts and (opts["block_size"] == 0 or opts.get("stored") or opts.get("model", "adaptive") != "adaptive"):
         return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
+    if ("lag" in opts) != (opts.get("filter") == "lag"):
+        return None  # the lag is the lag filter's, and that filter has no default for it
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):
         return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only
@@ -251,7 +265,7 @@ def main(argv=None):
                                                 opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
                                                 opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
-                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("base_op", "xor"))
+                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("lag"), opts.get("base_op", "xor"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

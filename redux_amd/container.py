@@ -11,7 +11,7 @@ Layout (little-endian):
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
            layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
            per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout; 12 = folded difference
-           against a base in front of the byte-plane layout)
+           against a base in front of the byte-plane layout; 13 = lagged delta filter in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -19,7 +19,8 @@ Layout (little-endian):
            0x50000000 | k << 4 | E with E one of 1, 2, 4, 8 and 1 <= k < 2^24: segments of 64 E k blocks; version 6:
            0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
            version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
-           0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8; version 12: 0xC0000000 | E with E one of 1, 2, 4, 8
+           0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8; version 12: 0xC0000000 | E with E one of 1, 2, 4, 8;
+           version 13: 0xD0000000 | S << 4 | E with E one of 1, 2, 4, 8 and the lag S, 1 <= S <= 256
    16   8  nblocks
    24   8  total uncompressed length
    (versions 8 and 12, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
@@ -101,7 +102,13 @@ and the same checks of the base before any GPU call.  The word at offset 12 is 0
 word, and version 12 takes no other.  It has no stored blocks (no 0x4C / 0x5C).  Without base_op="sub" (or "auto") the writers
 emit exactly the bytes they emitted before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x1C: versions 1 to 12 with checksums) means a table of nblocks
+Version 13 holds streams of the adaptive coder behind the lagged delta filter for interleaved channels and fixed-width
+records (include/redux_hip.h, "lagged delta filter"): version 11 with the predecessor S elements back, the same sections, and
+decoding undoes layout, fold and filter with the lag the word records.  The word at offset 12 is 0xD0000000 | S << 4 | E: no
+other version takes that word, and version 13 takes no other; S = 0 and S > 256 are InvalidInput.  It has no stored blocks
+(no 0x4D / 0x5D).  Without filter="lag" the writers emit exactly the bytes they emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1D: versions 1 to 13 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -135,6 +142,9 @@ VERSION_CONST = 9
 VERSION_MIXED = 10
 VERSION_ZIGZAG = 11
 VERSION_BASE_SUB = 12
+VERSION_LAG = 13
+LAG_MARK = 0xD0000000  # version 13's word at offset 12: LAG_MARK | S << 4 | E
+LAG_MAX = api.LAG_MAX  # the largest lag S (REDUX_LAG_MAX)
 BASE_SUB_MARK = 0xC0000000  # version 12's word at offset 12: BASE_SUB_MARK | E
 ZIGZAG_MARK = 0xB0000000  # version 11's word at offset 12: ZIGZAG_MARK | E
 MIXED_MARK = 0xA0000000  # version 10's word at offset 12
@@ -157,13 +167,15 @@ MAX_BLOCK_SIZE = 1 << 30
 
 # The versions that are version 2's sections behind a filter (version 2 itself: behind none): the marker nibble of the word
 # at offset 12, which is mark << 28 | E; the filter and the operation of the base filter a reader reports; whether the base
-# record follows the header.  pack, _version_ok, _header and _parse_index go by this table: a new filter is a new row.
-_FilterVersion = namedtuple("_FilterVersion", "mark filter base_op has_base")
+# record follows the header; whether bits 4 .. 27 of the word hold the filter's lag (else they are 0).  pack, _version_ok,
+# _header and _parse_index go by this table: a new filter is a new row.
+_FilterVersion = namedtuple("_FilterVersion", "mark filter base_op has_base has_lag", defaults=(False,))
 FILTER_VERSIONS = {VERSION_PLANES: _FilterVersion(0, None, None, False),
                    VERSION_DELTA: _FilterVersion(DELTA_MARK >> 28, "delta", None, False),
                    VERSION_BASE: _FilterVersion(BASE_MARK >> 28, None, "xor", True),
                    VERSION_ZIGZAG: _FilterVersion(ZIGZAG_MARK >> 28, "zigzag", None, False),
-                   VERSION_BASE_SUB: _FilterVersion(BASE_SUB_MARK >> 28, None, "sub", True)}
+                   VERSION_BASE_SUB: _FilterVersion(BASE_SUB_MARK >> 28, None, "sub", True),
+                   VERSION_LAG: _FilterVersion(LAG_MARK >> 28, "lag", None, False, True)}
 _VERSION_OF_FILTER = {(row.filter, row.base_op): ver for ver, row in FILTER_VERSIONS.items()}
 
 
@@ -174,7 +186,7 @@ def _raw_lengths(nblocks, block_size, total):
 
 
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None, unit_layouts=None, base_op="xor"):
+         constant=None, unit_layouts=None, lag=None, base_op="xor"):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -185,6 +197,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     stored: nblocks 0 / 1 flags of compress_blocks(..., stored=) (the version gets flag 0x40); None: no bitmap.
     filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored).
     filter "zigzag": streams of compress_blocks(..., filter="zigzag") (version 11, as version 6).
+    filter "lag" with lag S: streams of compress_blocks(..., filter="lag", lag=S) (version 13, as version 11).
     base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
     zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter).
     constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
@@ -193,7 +206,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     element_size 1 and none of stored, filter, base and constant); None: no unit table.
     base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
     version 8)."""
-    front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts)
+    front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
     xbase = front.takes_base
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
@@ -227,7 +240,7 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if filter is not None or xbase:
         ver = _VERSION_OF_FILTER[filter, base_op if xbase else None]
-        res = FILTER_VERSIONS[ver].mark << 28 | element_size
+        res = FILTER_VERSIONS[ver].mark << 28 | (front.lag or 0) << 4 | element_size
     if const:
         ver, res = VERSION_CONST, CONST_MARK | (1 if xbase else 0) << 4 | element_size
     crc = b""
@@ -321,7 +334,9 @@ def _version_ok(ver, res):
     row = FILTER_VERSIONS.get(layout)
     if row is not None:  # (version 2 alone may have stored blocks, and has no element size 1: that is version 1)
         plain = layout == VERSION_PLANES
-        return res >> 28 == row.mark and res & 0x0FFFFFFF in (() if plain else (1,)) + ELEMENT_SIZES \
+        if row.has_lag and not 1 <= res >> 4 & 0xFFFFFF <= LAG_MAX:
+            return False
+        return res >> 28 == row.mark and res & (0xF if row.has_lag else 0x0FFFFFFF) in (() if plain else (1,)) + ELEMENT_SIZES \
             and (plain or not ver & STORED_FLAG)
     return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
         or (layout == VERSION_PLANE_STATIC and not ver & STORED_FLAG and res & 0xFFFF in ELEMENT_SIZES and res >> 16 == res & 0xFFFF) \
@@ -346,9 +361,9 @@ def _has_base_record(ver, res):
 # base: (base_used, crc) of the record of version 8 or 12, or of version 9 with F = 1, else None; base_op: "xor" or "sub" where
 # there is a record, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
-# None, as the table holds it unit by unit.
+# None, as the table holds it unit by unit.  lag: the lag S of version 13, else None.
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
-                        " unit_layouts base_op", defaults=(None, None))
+                        " unit_layouts base_op lag", defaults=(None, None, None))
 
 
 def _header(b):
@@ -454,7 +469,8 @@ def _parse_index(b):
         E = None
     row = FILTER_VERSIONS.get(_layout(ver))  # (version 9's record, where it has one, is the XOR's)
     return _Container(P, block_size, total, E, static, offsets, None, crcs, stored, row.filter if row else None, base, constant,
-                      units, row.base_op if row else None if base is None else "xor"), at
+                      units, row.base_op if row else None if base is None else "xor",
+                      HEADER.unpack_from(b, 0)[6] >> 4 & 0xFFFFFF if row and row.has_lag else None), at
 
 
 def _parse(buf):
@@ -492,8 +508,14 @@ def element_size(buf):
 
 def filter(buf):
     """"delta" for a version 6 container (the delta filter for integer series), "zigzag" for a version 11 container (the same
-    with folded differences), None for every other version (version 10 records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
+    with folded differences), "lag" for a version 13 container (the lagged delta filter: lag()), None for every other version (version 10 records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).filter
+
+
+def lag(buf):
+    """The lag S of a version 13 container (the lagged delta filter); None for every other version.  Malformed containers
+    raise InvalidInput, truncated ones Eof."""
+    return _parse(buf).lag
 
 
 def base(buf):
@@ -567,8 +589,8 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
-    because only the tables of contexts that occur are recorded.  filter "delta" or "zigzag" (adaptive model, not stored):
-    version 6 or 11, which record the filter in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
+    because only the tables of contexts that occur are recorded.  filter "delta", "zigzag" or "lag" (adaptive model, not stored):
+    version 6, 11 or 13, which record the filter (and the lag) in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
     filter, not stored): version 10, whose unit table adds a byte per 8 blocks.  base (adaptive model, no filter, not stored, not
     mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation."""
     if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)) \
@@ -576,7 +598,8 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
         raise api.InvalidInput()
     if filter is not None and (model != "adaptive" or stored):
         raise api.InvalidInput()
-    api._resolve_front(None, filter=filter)
+    if filter is not None and (not isinstance(filter, str) or filter not in api._FILTERS):
+        raise api.InvalidInput()
     E = api._check_element_size(element_size)
     n = HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0) + ((nblocks + 7) // 8 if stored else 0)
     if mixed:
@@ -637,7 +660,8 @@ def choose_base_op(estimates):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, base_op="xor"):
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, lag=None,
+                   base_op="xor"):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -649,6 +673,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     filter "delta" (element_size 1 / 2 / 4 / 8, model "adaptive", not stored): the delta filter for integer series in front of
     the layout, version 6.
     filter "zigzag" (as "delta"): the delta filter with its differences folded, for series that move both ways, version 11.
+    filter "lag" with lag S, 1 .. 256 (as "zigzag"; not with layout): the folded difference to the element S back, for S
+    interleaved channels or records of S columns, version 13.  A lag without filter "lag" is InvalidInput, and so is the filter
+    without one.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
@@ -672,6 +699,8 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     "sub", unrelated ones "xor", and a caller cannot know in advance."""
     api._resolve_front(None, base=base, base_op="sub" if base_op == "auto" else base_op,
                        constant=skip_constant or None)  # (base_op alone is judged here; "auto": the refusals of "sub")
+    if lag is not None or (isinstance(filter, str) and filter == "lag"):  # (a lag and its filter go together)
+        api._resolve_front(None, filter=filter, lag=lag)
     if layout is not None:
         if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
                 or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
@@ -686,7 +715,7 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         element_size, filter = choose_layout(estimate_layout_bytes(data, block_size, params, element_size, checksum))
     if (skip_constant or base is not None or filter is not None) and (model != "adaptive" or stored):
         raise api.InvalidInput()
-    api._resolve_front(None, filter=filter, base=base, constant=skip_constant or None)  # (the model is a name here)
+    api._resolve_front(None, filter=filter, base=base, constant=skip_constant or None, lag=lag)  # (the model is a name here)
     if model == "auto":
         if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) or stored \
                 or segment_blocks is not None:
@@ -713,9 +742,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         base_op = choose_base_op(api.estimate_base_ops(data, base, block_size, params, element_size))
     cflags = np.zeros(nb, dtype=np.uint8) if skip_constant else None
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter,
-                                       base=base, constant=cflags, base_op=base_op)
+                                       base=base, constant=cflags, base_op=base_op, lag=lag)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record,
-                constant=cflags, base_op=base_op)
+                constant=cflags, base_op=base_op, lag=lag)
 
 
 def decompress_bytes(buf, base=None):
@@ -764,7 +793,7 @@ def _decode_parsed(c, base):
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
                                                        stored=c.stored, filter=c.filter, base=base, constant=c.constant,
-                                                       base_op=c.base_op or "xor")
+                                                       base_op=c.base_op or "xor", lag=c.lag)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
@@ -826,7 +855,7 @@ class Reader:
     not, CONTEXT_TABLES_MAX bytes are read and then parsed) and later only the streams of covered blocks: the payload of
     blocks no range covers is never read, so damage there -- a truncated file included -- does not matter to a range read.
     base: as for decompress_bytes; it is checked against the container's record here, once.
-    total, block_size, nblocks, version, filter, base_op, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
+    total, block_size, nblocks, version, filter, lag, base_op, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
     the source so far."""
 
     def __init__(self, source, base=None):
@@ -852,7 +881,7 @@ class Reader:
         self._c, self.payload_offset = _parse_index(memoryview(index))
         c = self._c
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
-        self.filter, self.base_op = c.filter, c.base_op
+        self.filter, self.base_op, self.lag = c.filter, c.base_op, c.lag
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
             else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
         self._base = _checked_base(c, base)

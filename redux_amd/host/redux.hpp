@@ -15,6 +15,7 @@
 //   redux::hip::compress_blocks_planes / decompress_blocks_planes   typed data in the byte-plane layout
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
 //   redux::hip::compress_blocks_zigzag / decompress_blocks_zigzag   signed series behind the zigzag-folded delta filter
+//   redux::hip::compress_blocks_lag / decompress_blocks_lag         interleaved channels behind the lagged delta filter
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_base_sub / decompress_blocks_base_sub   the same behind the folded difference against the base
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
@@ -280,6 +281,46 @@ inline std::vector<std::uint8_t> decompress_blocks_zigzag(const Blocks &streams,
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_zigzag(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, out.data(),
                                      sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// Interleaved channels and fixed-width records behind the lagged delta filter (include/redux_hip.h, "lagged delta filter"):
+// compress_blocks_zigzag with the predecessor `lag` elements back, 1 <= lag <= REDUX_LAG_MAX.  Opt-in: a wrong lag costs
+// bytes, and the decoder needs the same one.
+inline Blocks compress_blocks_lag(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                  std::uint32_t lag, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_lag_check(element_size, lag) != REDUX_OK)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_lag(&cp, in, len, block_size, element_size, lag, b.data.data(), b.data.size(), b.offsets.data(),
+                                  nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_lag(const Blocks &streams, std::uint64_t len, std::uint32_t block_size,
+                                                       std::uint32_t element_size, std::uint32_t lag, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_lag_check(element_size, lag) != REDUX_OK ||
+        redux_block_count(len, block_size) + 1 != streams.offsets.size() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_lag(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, lag, out.data(),
+                                  sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }
