@@ -1027,6 +1027,40 @@ int         redux_layout_cost_dev(const redux_params *p, const void *d_in, uint6
 const char *redux_layout_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t layout);
 const char *redux_layout_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t layout);
 
+/* ---- lag estimates ---------------------------------------------------------------------------------------
+ * The adaptive cost A (above) of every block of the input behind the lagged delta filter ("lagged delta filter" above), for a
+ * list of lags in one call, so that the lag can be counted instead of known in advance or found by coding the input once per
+ * candidate.  Nothing about the filter is new: bits[j][b] is what redux_block_cost_dev gives for block b of what
+ * redux_lag_planes_dev writes for (element_size, block_size, lags[j]) -- the fresh start of every frame, d[i] = x[i] for
+ * i < S, the fold, S >= N, the short last frame and its trailing bytes included -- but it is counted from the untransformed
+ * bytes: no transformed copy and no workspace.
+ *
+ * Frame sampling.  With frame_step T only the frames 0, T, 2T, ... (of element_size * block_size bytes) are costed, and the
+ * output is compact: row j holds the blocks of the selected frames in order.  A selected full frame contributes
+ * element_size blocks, a selected short last frame the blocks it has.  T = 1 costs every block.
+ *
+ * redux_lag_cost_block_count     the blocks of a row: redux_block_count(in_len, block_size) for frame_step 1; 0 for a
+ *                                block_size or frame_step of 0 or an element size that is not 1, 2, 4, 8.
+ * redux_lag_cost_dev             d_bits is f64[nlags][redux_lag_cost_block_count(...)] on the device.  lags: nlags values on
+ *                                the HOST, consumed before the call returns (they travel in the kernels' arguments); repeated
+ *                                lags are legal, rows are independent.  Full frames go to k_lag_cost when block_size and d_in
+ *                                are multiples of 16, everything else (the short last frame included) to k_lag_cost_bytes,
+ *                                which is right for any alignment and block size but slow.  INVALID_INPUT for a block_size
+ *                                outside 1 .. 2^30, an element size other than 1, 2, 4, 8, nlags == 0 or above
+ *                                REDUX_LAG_MAX, a lag redux_lag_check refuses, frame_step == 0, or a null lags / d_bits;
+ *                                UNSUPPORTED as redux_block_cost_dev.  in_len == 0: one empty block per row.
+ *                                Stream-ordered, no workspace, no host synchronisation.
+ * redux_lag_cost_kernel_name     the kernels such a call with frame_step 1 runs on a 16-byte aligned d_in: "k_lag_cost<E>",
+ *                                "k_lag_cost_bytes<E>", or both joined by " + " when full frames are followed by a short
+ *                                one.  "" for a block_size or element size out of range.
+ * redux_lag_cost_kernel_name_at  the same for this d_in, which contributes its alignment only. */
+uint64_t    redux_lag_cost_block_count(uint64_t in_len, uint32_t block_size, uint32_t element_size, uint32_t frame_step);
+int         redux_lag_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, const uint32_t *lags /* host, nlags */, uint32_t nlags,
+                               uint32_t frame_step, void *d_bits /* f64[nlags][block_count] */, void *stream);
+const char *redux_lag_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size);
+const char *redux_lag_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+
 /* ---- mixed layouts --------------------------------------------------------------------------------------
  * One layout per UNIT of the input instead of one per input, for files that hold several element types (bf16 weights next to
  * fp32 state, int64 indices and text): the eight layouts of "layout estimates" above, chosen for every unit on its own.

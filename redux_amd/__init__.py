@@ -16,5 +16,6 @@ from .api import (  # noqa: F401
     MODELS, adaptive_cost_from_counts, table_cost_from_counts, block_cost, table_cost, estimate_candidates, estimate_payload,
     LAYOUTS, layout_index, layout_cost, estimate_layouts, BASE_OPS, estimate_base_ops,
     mixed_units, choose_unit_layouts, mixed_layout,
+    lag_cost, estimate_lags, choose_lag,
     range_plan, segment_copy, segment_tiles, SEGMENT_DTYPE,
 )

@@ -2266,6 +2266,125 @@ def estimate_layouts(data, block_size, params=(8, 30, 32), element_size=None, mi
     return est
 
 
+# ---- lag estimates (include/redux_hip.h, "lag estimates") ------------------------------------------
+LAG_SAMPLE_FRAMES = 64  # choose_lag's first pass counts about this many frames of a longer input
+LAG_FINALISTS = 3       # and its second pass the lags with the smallest sampled estimates, this many, plus lag 1
+
+
+def _lag_list(lags):
+    """None: 1 .. LAG_MAX; else 1 to LAG_MAX ints in 1 .. LAG_MAX, repeats allowed -> list of int"""
+    if lags is None:
+        return list(range(1, LAG_MAX + 1))
+    try:
+        lags = list(lags)
+    except TypeError:
+        raise InvalidInput()
+    if not 1 <= len(lags) <= LAG_MAX or any(isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= S <= LAG_MAX
+                                            for S in lags):
+        raise InvalidInput()
+    return [int(S) for S in lags]
+
+
+def _lag_cost_args(element_size, block_size, lags, frame_step):
+    """the argument checks of the lag estimates, on the arguments alone -> (E, B, lag list, T)"""
+    if not isinstance(element_size, (int, np.integer)) or isinstance(element_size, bool) or element_size not in (1, 2, 4, 8) \
+            or not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30 \
+            or isinstance(frame_step, bool) or not isinstance(frame_step, (int, np.integer)) or not 0 < frame_step < 1 << 32:
+        raise InvalidInput()
+    return int(element_size), int(block_size), _lag_list(lags), int(frame_step)
+
+
+def _device_lag_cost(torch, L, cp, d, E, B, lags, T):
+    """-> float64 device tensor [len(lags), redux_lag_cost_block_count]; the lag list is consumed by the call"""
+    n = d.numel()
+    d_bits = torch.empty((len(lags), L.redux_lag_cost_block_count(n, B, E, T)), dtype=torch.float64, device=d.device)
+    h_lags = np.asarray(lags, dtype=np.uint32)
+    _raise(L.redux_lag_cost_dev(C.byref(cp), C.c_void_p(d.data_ptr()) if n else None, n, B, E, h_lags.ctypes.data, len(lags), T,
+                                C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits
+
+
+def lag_cost(data, element_size, lags, block_size=65536, params=(8, 30, 32), frame_step=1):
+    """The adaptive model's ideal code length in bits, EOF included, of every block of `data` behind the lagged delta filter
+    (filter="lag") for each lag of `lags` (1 to 256 of them, each 1 .. LAG_MAX, repeats allowed), counted from the bytes as they
+    are, with no transformed copy (redux_lag_cost_dev: k_lag_cost on torch's current stream, one read-back)
+    -> np.float64[len(lags), block_count]: row j is block_cost(lag_planes(data, element_size, block_size, lags[j])).
+    frame_step T > 1 costs only the frames 0, T, 2T, ... (of element_size * block_size bytes) and returns their blocks in
+    order.  A uint8 device tensor is read where it lies; host data is uploaded once."""
+    E, B, lags, T = _lag_cost_args(element_size, block_size, lags, frame_step)  # (before the library is touched)
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _device_lag_cost(torch, _lib.lib(), P._c(), d, E, B, lags, T).cpu().numpy()
+
+
+def _lag_estimates(torch, L, cp, d, E, B, lags, T):
+    bits = _device_lag_cost(torch, L, cp, d, E, B, lags, T)
+    sums, nb = bits.sum(dim=1).cpu().numpy(), bits.shape[1]
+    out = {}
+    for j, S in enumerate(lags):
+        out.setdefault(S, int(np.ceil(float(sums[j]) / 8 + TERMINATION_BYTES * nb)))
+    return out
+
+
+def estimate_lags(data, element_size, block_size, lags=None, params=(8, 30, 32), frame_step=1):
+    """-> {S: estimated payload bytes}: what the streams of compress_blocks(..., element_size=, filter="lag", lag=S) would
+    add up to for each lag of `lags` (None: 1 .. LAG_MAX), without transforming or coding anything: one lag_cost call, then
+    ceil(sum bits / 8 + TERMINATION_BYTES * blocks) as estimate_payload, over the blocks of the selected frames (frame_step
+    1: all of them; a repeated lag keeps its first row)."""
+    E, B, lags, T = _lag_cost_args(element_size, block_size, lags, frame_step)  # (before the library is touched)
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _lag_estimates(torch, _lib.lib(), P._c(), d, E, B, lags, T)
+
+
+def lag_frame_step(nframes):
+    """the frame step of choose_lag's first pass: 1 up to LAG_SAMPLE_FRAMES frames (one exact pass), ceil(F / 64) above"""
+    return 1 if nframes <= LAG_SAMPLE_FRAMES else -(-nframes // LAG_SAMPLE_FRAMES)
+
+
+def lag_finalists(estimates):
+    """the lags of choose_lag's second pass, ascending: the LAG_FINALISTS smallest estimates (ties go to the smaller S), and
+    lag 1 always"""
+    return sorted(set(sorted(estimates, key=lambda S: (estimates[S], S))[:LAG_FINALISTS]) | {1})
+
+
+def best_lag(estimates):
+    """The lag with the smallest estimate; ties go to the smaller S."""
+    return min(estimates, key=lambda S: (estimates[S], S))
+
+
+def choose_lag(data, element_size, block_size, params=(8, 30, 32), estimate=None):
+    """-> (S, {S: estimated payload bytes}): the lag of the lagged delta filter with the smallest estimate_lags, counted on
+    the GPU and never guessed.  Up to LAG_SAMPLE_FRAMES (64) frames: one exact pass over all 256 lags.  Above: a first pass
+    over all 256 lags on every ceil(F / 64)-th frame, then an exact pass over every frame for the finalists alone -- the
+    LAG_FINALISTS (3) smallest sampled estimates and S = 1, which is always among them, so the chosen lag's estimate is never
+    above the zigzag filter's.  Ties go to the smaller S; there is no hysteresis.  The dict holds the estimates of the last
+    pass.  estimate: the rule alone, for a caller with costs of its own: a function (lags or None, frame_step) -> {S: bytes}
+    in place of the device."""
+    E, B, _, _ = _lag_cost_args(element_size, block_size, None, 1)  # (before the library is touched)
+    if estimate is None:
+        P = _params_of(params)
+        torch = _torch()
+        d = _device_u8(torch, data)
+        L, cp = _lib.lib(), P._c()
+        nbytes = d.numel()
+
+        def estimate(lags, T):
+            with torch.cuda.device(d.device):
+                return _lag_estimates(torch, L, cp, d, E, B, _lag_list(lags), T)
+    else:
+        nbytes = len(data)
+    T = lag_frame_step(max(1, -(-nbytes // (E * B))))
+    est = estimate(None, T)
+    if T > 1:
+        est = estimate(lag_finalists(est), 1)
+    return best_lag(est), est
+
+
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------
 def gen_iid(nbytes, seed=0x5EED0001, first_byte=0, device="cuda:0", out=None):
     torch = _torch()

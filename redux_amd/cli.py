@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag|lag] [--lag S] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag] [--lag S|auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -60,9 +60,15 @@ instead of the one directly before (container version 13, which records S): for 
 multi-channel PCM, IMU and ADC logs, (x, y, z) vertex arrays, RGB(A) pixels -- and row-major tables of records of S columns,
 where the element before belongs to another series and `--filter delta` or `zigzag` makes the file larger.  On interleaved
 int16 / int32 random walks it comes out at 0.54 to 0.65 of the best of plain, planes, delta and zigzag; a wrong lag costs up
-to 10 % over them, so nothing chooses it, or S, for you.  `--lag 1` is `--filter zigzag` under another version number.  -d
+to 10 % over them, so the filter stays opt-in: nothing chooses it for you, and `--layout auto` does not see it.  S can be
+counted: `--filter lag --lag auto` estimates the payload behind every lag from 1 to 256 on the GPU, from the input as it
+stands and without transforming or coding it (redux_amd/api.py: choose_lag), and codes with the smallest, ties
+to the smaller S.  Up to 64 frames (of element size times block size bytes) that is one exact pass; above, a first pass over
+about 64 evenly spaced frames, then an exact pass over every frame for the three best lags and S = 1 -- which is always among
+them, so the chosen lag is never estimated above `--filter zigzag`.  The output is that lag's container, version 13, which
+records it: nothing new for -d.  `--lag 1` is `--filter zigzag` under another version number.  -d
 and -d `--range` read version 13 with no flag.  `--lag` without `--filter lag`, `--filter lag` without `--lag`, and an S that
-is no decimal number from 1 to 256 are usage errors.
+is neither a decimal number from 1 to 256 nor the word `auto` are usage errors.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -111,7 +117,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag|lag>] [--lag <1..256>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -151,9 +157,12 @@ def parse(argv):
                     return None
                 opts["filter"] = val
             elif arg == "--lag":
-                if not (val.isascii() and val.isdigit()) or not 1 <= int(val) <= 256:
+                if val == "auto":
+                    opts["lag"] = val
+                elif not (val.isascii() and val.isdigit()) or not 1 <= int(val) <= 256:
                     return None
-                opts["lag"] = int(val)
+                else:
+                    opts["lag"] = int(val)
             elif arg == "--base":
                 opts["base"] = val
             elif arg == "--base-op":
@@ -205,7 +214,7 @@ def parse(argv):
     if "filter" in opts and (opts["block_size"] == 0 or opts.get("stored") or opts.get("model", "adaptive") != "adaptive"):
         return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
     if ("lag" in opts) != (opts.get("filter") == "lag"):
-        return None  # the lag is the lag filter's, and that filter has no default for it
+        return None  # the lag is the lag filter's, and that filter has no default for it (`--lag auto` asks for the count)
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):
         return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only

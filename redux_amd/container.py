@@ -649,6 +649,17 @@ def estimate_layout_bytes(data, block_size=65536, params=(8, 30, 32), element_si
     return est
 
 
+def estimate_lag_bytes(data, element_size, block_size=65536, lags=None, params=(8, 30, 32), checksum=False, frame_step=1):
+    """-> {S: estimated container bytes} for the adaptive model behind the lagged delta filter with each lag of `lags` (None:
+    1 .. LAG_MAX): api.estimate_lags' estimate of the payloads (counted from the bytes as they are on the GPU; nothing is
+    transformed or coded) plus overhead_bytes(..., filter="lag"), which is exact: directly comparable with
+    estimate_layout_bytes, for a caller who asks whether the filter pays at all.  frame_step above 1 estimates the selected
+    frames' payload only, under the whole container's overhead."""
+    payload = api.estimate_lags(data, element_size, block_size, lags, params, frame_step)
+    over = overhead_bytes("adaptive", max(1, -(-len(data) // block_size)), element_size, checksum=checksum, filter="lag")
+    return {S: payload[S] + over for S in payload}
+
+
 def choose_layout(estimates):
     """The (element_size, filter) with the smallest estimate; ties go to the earlier of LAYOUT_ORDER."""
     return min(estimates, key=lambda k: (estimates[k], LAYOUT_ORDER.index(k)))
@@ -675,7 +686,10 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     filter "zigzag" (as "delta"): the delta filter with its differences folded, for series that move both ways, version 11.
     filter "lag" with lag S, 1 .. 256 (as "zigzag"; not with layout): the folded difference to the element S back, for S
     interleaved channels or records of S columns, version 13.  A lag without filter "lag" is InvalidInput, and so is the filter
-    without one.
+    without one.  lag "auto" (with filter "lag"; here only, not in the block calls or the device coders): the lag with the
+    smallest estimate codes the data (api.choose_lag: counted on the GPU from the bytes as they are, exact on every frame for
+    the finalists, lag 1 always among them), and the container is that lag's, version 13, which records it: nothing new to
+    decode.  The filter itself stays opt-in.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
@@ -699,6 +713,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     "sub", unrelated ones "xor", and a caller cannot know in advance."""
     api._resolve_front(None, base=base, base_op="sub" if base_op == "auto" else base_op,
                        constant=skip_constant or None)  # (base_op alone is judged here; "auto": the refusals of "sub")
+    auto_lag = isinstance(lag, str) and lag == "auto"  # (the choice is made below, once nothing else refuses the call)
+    if auto_lag:
+        lag = 1
     if lag is not None or (isinstance(filter, str) and filter == "lag"):  # (a lag and its filter go together)
         api._resolve_front(None, filter=filter, lag=lag)
     if layout is not None:
@@ -727,6 +744,8 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
             or (model == "plane-static" and (element_size == 1 or stored)) or (model == "segment-static" and stored) \
             or (model != "segment-static" and segment_blocks is not None):
         raise api.InvalidInput()
+    if auto_lag:
+        lag = api.choose_lag(data, element_size, block_size, params)[0]
     nb = max(1, -(-len(data) // block_size))
     crc = np.zeros(nb, dtype=np.uint32) if checksum else None
     flags = np.zeros(nb, dtype=np.uint8) if stored else None

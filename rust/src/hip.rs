@@ -101,6 +101,17 @@ extern "C" {
     fn redux_decode_blocks_const(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, const_flags: *const u8,
                                  base: *const u8, base_len: u64, out_len: u64, block_size: u32, element_size: u32,
                                  out: *mut u8, out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // lag estimates: the adaptive cost of every block behind the lagged delta filter for a list of lags (device pointers;
+    // declared for callers that hold device buffers, not used by the host-slice functions below)
+    #[allow(dead_code)]
+    fn redux_lag_cost_block_count(in_len: u64, block_size: u32, element_size: u32, frame_step: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_lag_cost_dev(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32,
+                          lags: *const u32, nlags: u32, frame_step: u32, d_bits: *mut c_void, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_lag_cost_kernel_name(in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
+    #[allow(dead_code)]
+    fn redux_lag_cost_kernel_name_at(d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
     fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
     fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
     fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
