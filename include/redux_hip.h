@@ -508,6 +508,55 @@ int redux_decode_blocks_lag(const redux_params *p, const uint8_t *in, const uint
                             uint32_t block_size, uint32_t element_size, uint32_t lag, uint8_t *out, uint32_t *out_sizes,
                             int32_t *block_status, uint32_t *block_crc);
 
+/* ---- higher-order lagged differences -------------------------------------------------------------
+ * The lagged delta filter predicts an element by the one S back, the weakest predictor that interleaved sampled data can
+ * have.  A sampled, band-limited signal -- PCM, a vibration or IMU log, an ADC trace -- is locally a low-degree polynomial,
+ * and the K-th difference removes one of degree K - 1: FLAC's fixed predictors of order 2 and 3, and every "delta of delta"
+ * time-series codec.  These calls are the lagged delta filter applied K times, 1 <= K <= REDUX_LAG_ORDER_MAX.  Strictly
+ * opt-in, as the lag is: on a random walk order 1 is already optimal and a higher order costs bytes (5 to 16 % on generated
+ * walks, against a quarter to a third saved on generated tonal signals; no recorded signal was measured).  E, B, the frames
+ * and the lag S are the lagged delta filter's.  With x[j] = 0 for j < 0:
+ *   - d[i] = sum over j = 0 .. K of (-1)^j C(K, j) x[i - j S] mod 2^(8E):
+ *       K = 2: x[i] - 2 x[i-S] + x[i-2S],  K = 3: x[i] - 3 x[i-S] + 3 x[i-2S] - x[i-3S].
+ *     This is the lag-S difference applied K times, each application leaving its first S elements as they are.
+ *   - z[i] is the zigzag fold of d[i], always.  The L - N*E trailing bytes of a frame are unchanged.
+ *   - The byte-plane layout is then applied to the z's (E = 1: no layout).
+ *   - The inverse undoes the layout, unfolds, then takes the S running sums of the frame K times.
+ *   - Every frame starts afresh.  Any S and K are legal for any N: terms that fall before the frame are zero.  K = 1 is the
+ *     lagged delta filter, byte for byte.
+ * Behind the transform is the plain adaptive coder:
+ *     stream_lag_order_E_S_K(x)[b] == redux_encode_blocks(planes_E(lag_order_E_S_K(x)))[b].
+ * Not available where the lagged delta filter is not.
+ *
+ * Every call is the shape of its lag namesake with `order` directly after `lag`, and keeps its promises:
+ * redux_decode_lag_order_dev writes no byte outside d_out[0 .. out_len), for damaged streams too, and every frame whose
+ * blocks are all OK holds the original bytes; the host-pointer pair cuts its chunks at frame boundaries, and block_crc is
+ * over the ORIGINAL bytes.  An order of 0 or above REDUX_LAG_ORDER_MAX is REDUX_INVALID_INPUT wherever a bad lag is, and
+ * nothing is written; order 1 is accepted everywhere.  The workspace calls take neither lag nor order and return their zigzag
+ * namesakes' values.  redux_lag_order_planes_dev reads the source once from memory and K times more from cache, and reads no
+ * byte before a frame's first.
+ */
+#define REDUX_LAG_ORDER_MAX 3
+int      redux_lag_order_check(uint32_t element_size, uint32_t lag, uint32_t order);
+int      redux_lag_order_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+                                    uint32_t lag, uint32_t order, int inverse, void *stream);
+uint64_t redux_encode_lag_order_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_lag_order_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size);
+int redux_encode_lag_order_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint32_t lag, uint32_t order, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                               void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] */,
+                               void *d_workspace, uint64_t workspace_bytes, void *stream);
+int redux_decode_lag_order_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint32_t lag, uint32_t order, void *d_out,
+                               void *d_out_sizes /* u32[nblocks] */, void *d_block_status, void *d_summary, void *d_workspace,
+                               uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_lag_order(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                  uint32_t element_size, uint32_t lag, uint32_t order, uint8_t *out, uint64_t out_cap,
+                                  uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_lag_order(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                                  uint32_t block_size, uint32_t element_size, uint32_t lag, uint32_t order, uint8_t *out,
+                                  uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
+
 /* ---- XOR-against-base filter for series of snapshots -------------------------------------------
  * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its
  * base model, optimizer state, a KV cache against its earlier self -- differs from its predecessor only in the low mantissa

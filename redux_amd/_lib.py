@@ -217,6 +217,17 @@ SIGNATURES.update({
     "redux_encode_blocks_lag": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_lag": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _V, _V, _V, _V]),
 })
+# higher-order lagged differences: the lag family with the order behind the lag
+SIGNATURES.update({
+    "redux_lag_order_check": (C.c_int, [_U32, _U32, _U32]),
+    "redux_lag_order_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, _U32, _U32, C.c_int, _V]),
+    "redux_encode_lag_order_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_lag_order_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_lag_order_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _U32, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_lag_order_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_lag_order": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _U32, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_lag_order": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _U32, _V, _V, _V, _V]),
+})
 
 _LIB = None
 

@@ -510,13 +510,16 @@ def _check_element_size(element_size):
 # redux_{encode,decode}_{infix}_{dev,workspace_bytes}, redux_{encode,decode}_blocks_{infix} and redux_{infix}_planes_dev,
 # whether those take a (base, base_len) pair, and whether decoding needs the length for every element size.  A new filter
 # is a new row here (and a Filter value in redux_hip.hip, and a version row in container.py).  lag: the lag of the lagged
-# delta filter, which its entry points take behind the element size; None for every other front.
-_Front = namedtuple("_Front", "infix takes_base needs_length lag", defaults=(None,))
+# delta filter, which its entry points take behind the element size; None for every other front.  order: the order of
+# higher-order lagged differences, which their entry points take behind the lag; None for every other front.
+_Front = namedtuple("_Front", "infix takes_base needs_length lag order", defaults=(None, None))
 _PLANES = _Front("planes", False, False)                                 # no filter: the layout alone (none for element size 1)
 _FILTERS = {"delta": _Front("delta", False, True),                       # filter="delta": the delta filter for integer series
             "zigzag": _Front("zigzag", False, True),                     # filter="zigzag": the same with folded differences
             "lag": _Front("lag", False, True)}                           # filter="lag", lag=S: the predecessor S elements back
+_LAG_ORDER = _Front("lag_order", False, True)                            # filter="lag", lag=S, order=2 or 3: the lag filter K times
 LAG_MAX = 256  # REDUX_LAG_MAX
+LAG_ORDER_MAX = 3  # REDUX_LAG_ORDER_MAX
 _BASE_OPS = {"xor": _Front("base", True, True),                          # base=: the XOR against the base
              "sub": _Front("base_sub", True, True)}                      # base=, base_op="sub": the folded difference
 
@@ -527,12 +530,14 @@ _STATIC_MODELS = (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStat
 
 
 def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor", constant=None, stored=None, unit_layouts=None,
-                   device=False, lag=None):
+                   device=False, lag=None, order=None):
     """The one place that says which of filter=, base=, base_op=, constant=, stored=, unit_layouts= and the model's kind go
     together; anything else is InvalidInput.  A check on the arguments alone: it touches neither the library nor torch,
     so it comes before any call into either.  -> _Resolved.
     filter: None, "delta", "zigzag" or "lag"; with the adaptive model only, and not with stored blocks.
     lag: with filter="lag" and only with it, an int in 1 .. LAG_MAX; the _Front returned carries it.
+    order: None, or with filter="lag" an int in 1 .. LAG_ORDER_MAX.  None and 1 are the lag front itself; 2 and 3 the
+    lag_order front, which carries lag and order.
     base: None or a base; as a filter, and not together with one.  base_op: "xor" or "sub", "sub" only with a base and
     without the constant-block option.
     constant: None / False, or the option (True, or the flags); adaptive model only, with or without a base, not with a
@@ -545,6 +550,9 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     mixed = unit_layouts is not None
     if (lag is not None) != (isinstance(filter, str) and filter == "lag") or (lag is not None and (
             isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= LAG_MAX)):
+        raise InvalidInput()
+    if order is not None and (lag is None or isinstance(order, bool) or not isinstance(order, (int, np.integer))
+                              or not 1 <= order <= LAG_ORDER_MAX):
         raise InvalidInput()
     if not isinstance(base_op, str) or base_op not in _BASE_OPS or (base_op == "sub" and (base is None or const)):
         raise InvalidInput()
@@ -561,6 +569,8 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     front = _FILTERS[filter] if filter is not None else _BASE_OPS[base_op] if base is not None else _PLANES
     if lag is not None:
         front = front._replace(lag=int(lag))
+        if order is not None and order > 1:
+            front = _LAG_ORDER._replace(lag=int(lag), order=int(order))
     return _Resolved(front, const, mixed)
 
 
@@ -572,8 +582,9 @@ def _no_front(filter=None, constant=None):
 
 
 def _lag_arg(front):
-    """what a _Front's entry points take behind the element size: the lag of the lagged delta filter, or nothing"""
-    return () if front.lag is None else (front.lag,)
+    """what a _Front's entry points take behind the element size: the lag of the lagged delta filter, the lag and the order
+    of higher-order lagged differences, or nothing"""
+    return () if front.lag is None else (front.lag,) if front.order is None else (front.lag, front.order)
 
 
 def _blocks_entry(L, direction, front):
@@ -666,7 +677,7 @@ def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
                     store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None,
-                    lag=None, base_op="xor"):
+                    lag=None, order=None, base_op="xor"):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -691,6 +702,9 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     filter="lag", lag=S (1 .. 256): the zigzag filter with the predecessor S elements back, for S interleaved channels or
     records of S columns (include/redux_hip.h, "lagged delta filter": redux_encode_blocks_lag); accepted and refused where
     "zigzag" is.  A lag without filter="lag", or filter="lag" without one, is InvalidInput.
+    order=K (1 .. 3, with filter="lag" only): the lag-S difference applied K times, for sampled signals that are locally
+    polynomial (include/redux_hip.h, "higher-order lagged differences": redux_encode_blocks_lag_order).  None and 1 are the
+    lagged delta filter itself; on random walks a higher order costs bytes, so nothing chooses it for the caller.
     base: bytes-like of any length, an earlier snapshot of the same data; the XOR against it is coded, for any element_size
     (include/redux_hip.h, "XOR-against-base filter": redux_encode_blocks_base); decompress_blocks(..., element_size, length,
     base=the same bytes) undoes it.  Adaptive model only, and not with stored= or filter=.
@@ -707,7 +721,8 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     base_op: "xor" (the default), or "sub" with base=: the folded difference of the elements against the base in place of
     the XOR (include/redux_hip.h, "folded difference against a base": redux_encode_blocks_base_sub);
     decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=."""
-    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
+                                         order=order)
     if mixed:
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
     if layouts is not None:
@@ -787,7 +802,7 @@ def _offsets_in(offsets, nbytes):
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
                       block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, lag=None,
-                      base_op="xor"):
+                      order=None, base_op="xor"):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
     With element_size > 1 (or a length given) the byte-plane layout is undone: length, the original byte count, is then
@@ -806,7 +821,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     filter="delta": the streams are compress_blocks(..., filter="delta")'s (redux_decode_blocks_delta); length is required
     for every element_size, and out is the original bytes.  Adaptive model only, and not with stored=.  filter="zigzag":
     the same for compress_blocks(..., filter="zigzag")'s streams (redux_decode_blocks_zigzag).  filter="lag", lag=S: the
-    same for compress_blocks(..., filter="lag", lag=S)'s (redux_decode_blocks_lag).
+    same for compress_blocks(..., filter="lag", lag=S)'s (redux_decode_blocks_lag); with order=K the same for
+    compress_blocks(..., filter="lag", lag=S, order=K)'s (redux_decode_blocks_lag_order for K above 1).
     base: the bytes compress_blocks(..., base=) was given (redux_decode_blocks_base); length is required for every
     element_size, and out is the original bytes.  Adaptive model only, and not with stored= or filter=.
     constant: the np.uint8[nblocks] flags compress_blocks(..., constant=) wrote (redux_decode_blocks_const), with the
@@ -815,7 +831,8 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
     required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
     base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub)."""
-    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
+    front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
+                                         order=order)
     if mixed:
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
@@ -1251,13 +1268,15 @@ class DeviceEncoder(_DeviceCoder):
     base=, not together with filter=; encode() then returns the u8 flags as a fifth value.  base_op="sub" with base=: the
     folded difference of the elements against the base in place of the XOR (include/redux_hip.h, "folded difference against a
     base"); not together with constant=True.  filter="lag", lag=S: the lagged delta filter (include/redux_hip.h, "lagged delta
-    filter"), where filter="zigzag" may stand."""
+    filter"), where filter="zigzag" may stand; order=K (1 .. 3) with it: the difference applied K times (include/redux_hip.h,
+    "higher-order lagged differences")."""
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, layouts=None, lag=None, base_op="xor"):
+                 mixed=False, layouts=None, lag=None, order=None, base_op="xor"):
         # (mixed: with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
-                                                               unit_layouts=True if mixed else None, device=True, lag=lag)
+                                                               unit_layouts=True if mixed else None, device=True, lag=lag,
+                                                               order=order)
         if self.mixed:
             self.mixed_mask = _layout_mask(layouts)
         elif layouts is not None:
@@ -1356,13 +1375,14 @@ class DeviceDecoder(_DeviceCoder):
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
     streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags)).
     base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s.  filter="lag", lag=S: the streams are
-    DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"."""
+    DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"; order=K: the encoder's order."""
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, lag=None, base_op="xor"):
+                 mixed=False, lag=None, order=None, base_op="xor"):
         # (mixed: the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
-                                                               unit_layouts=True if mixed else None, device=True, lag=lag)
+                                                               unit_layouts=True if mixed else None, device=True, lag=lag,
+                                                               order=order)
         torch = _torch()
         self.base = _device_base(torch, base, device)
         P = _params_of(params)
@@ -1829,6 +1849,16 @@ def lag_planes(d_src, element_size, block_size, lag, inverse=False, out=None):
     """The lagged delta filter followed by the byte-plane layout (include/redux_hip.h, "lagged delta filter") of a uint8
     device tensor, or their inverse: redux_lag_planes_dev on torch's current stream.  lag: 1 .. 256.  out: as for planes()."""
     return _transform(_resolve_front(None, filter="lag", lag=lag).front, d_src, element_size, block_size, inverse, out)
+
+
+def lag_order_planes(d_src, element_size, block_size, lag, order, inverse=False, out=None):
+    """Higher-order lagged differences followed by the byte-plane layout (include/redux_hip.h, "higher-order lagged
+    differences") of a uint8 device tensor, or their inverse: redux_lag_order_planes_dev on torch's current stream, for order
+    1 too.  lag: 1 .. 256; order: 1 .. 3.  out: as for planes()."""
+    if order is None:  # (the resolver's "no order" is the lag filter; this call names the order)
+        raise InvalidInput()
+    _resolve_front(None, filter="lag", lag=lag, order=order)
+    return _transform(_LAG_ORDER._replace(lag=int(lag), order=int(order)), d_src, element_size, block_size, inverse, out)
 
 
 def _device_unit_table(torch, table, nunits, device):

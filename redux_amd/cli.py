@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag|lag] [--lag S|auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -69,6 +69,15 @@ them, so the chosen lag is never estimated above `--filter zigzag`.  The output 
 records it: nothing new for -d.  `--lag 1` is `--filter zigzag` under another version number.  -d
 and -d `--range` read version 13 with no flag.  `--lag` without `--filter lag`, `--filter lag` without `--lag`, and an S that
 is neither a decimal number from 1 to 256 nor the word `auto` are usage errors.
+`--order K` (with `--filter lag --lag S`; K is 1, 2 or 3; `--checksum` is allowed) applies the lag-S difference K times
+(container version 14, which records K and S): for sampled, band-limited signals -- PCM, vibration and IMU logs, ADC traces --
+which are locally a low-degree polynomial, as FLAC's fixed predictors of order 2 and 3 and every "delta of delta" codec
+assume.  On generated tonal signals (three sinusoids plus noise per channel) order 2 comes out at 0.72 to 0.77 and order 3 at
+0.67 to 0.73 of order 1; on generated random walks, for which order 1 is already optimal, they cost 5 and 13 to 16 % more,
+so the order stays opt-in and nothing chooses it for you.  No recorded signal was measured: the figures rest on generated
+data.  `--order 1` is `--filter lag --lag S` itself and writes version 13, byte for byte.  -d and -d `--range` read version
+14 with no flag.  `--order` without `--filter lag`, a K that is not the decimal 1, 2 or 3, and `--order 2` or `3` with
+`--lag auto` (the lag estimates count order 1 only) are usage errors.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -117,7 +126,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -136,7 +145,7 @@ def parse(argv):
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range",
-                     "--base-op", "--lag"):
+                     "--base-op", "--lag", "--order"):
             val = next(it, None)
             if val is None:
                 return None
@@ -163,6 +172,10 @@ def parse(argv):
                     return None
                 else:
                     opts["lag"] = int(val)
+            elif arg == "--order":
+                if val not in ("1", "2", "3"):
+                    return None
+                opts["order"] = int(val)
             elif arg == "--base":
                 opts["base"] = val
             elif arg == "--base-op":
@@ -215,6 +228,8 @@ def parse(argv):
         return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
     if ("lag" in opts) != (opts.get("filter") == "lag"):
         return None  # the lag is the lag filter's, and that filter has no default for it (`--lag auto` asks for the count)
+    if "order" in opts and (opts.get("filter") != "lag" or (opts["order"] > 1 and opts.get("lag") == "auto")):
+        return None  # the order is the lag filter's, and the lag estimates count order 1 only
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):
         return None  # the base record lives in the container, and the XOR sits in front of the adaptive coder only
@@ -274,7 +289,8 @@ def main(argv=None):
                                                 opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
                                                 opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
-                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("lag"), opts.get("base_op", "xor"))
+                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("lag"), opts.get("order"),
+                                                opts.get("base_op", "xor"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
             print("Compressed %d bytes into %d bytes, ratio: %.3f" % (i_n, o_n, i_n / o_n), file=sys.stderr)

@@ -11,7 +11,8 @@ Layout (little-endian):
            7 = context-static: a static table per preceding byte; 8 = XOR-against-base filter in front of the byte-plane
            layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
            per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout; 12 = folded difference
-           against a base in front of the byte-plane layout; 13 = lagged delta filter in front of the byte-plane layout)
+           against a base in front of the byte-plane layout; 13 = lagged delta filter in front of the byte-plane layout;
+           14 = higher-order lagged differences in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -20,7 +21,8 @@ Layout (little-endian):
            0x60000000 | E with E one of 1, 2, 4, 8; version 7: 0x70000000; version 8: 0x80000000 | E with E one of 1, 2, 4, 8;
            version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
            0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8; version 12: 0xC0000000 | E with E one of 1, 2, 4, 8;
-           version 13: 0xD0000000 | S << 4 | E with E one of 1, 2, 4, 8 and the lag S, 1 <= S <= 256
+           version 13: 0xD0000000 | S << 4 | E with E one of 1, 2, 4, 8 and the lag S, 1 <= S <= 256;
+           version 14: 0xE0000000 | K << 16 | S << 4 | E with E and S as in version 13 and the order K, 2 <= K <= 3
    16   8  nblocks
    24   8  total uncompressed length
    (versions 8 and 12, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
@@ -108,7 +110,15 @@ decoding undoes layout, fold and filter with the lag the word records.  The word
 other version takes that word, and version 13 takes no other; S = 0 and S > 256 are InvalidInput.  It has no stored blocks
 (no 0x4D / 0x5D).  Without filter="lag" the writers emit exactly the bytes they emitted before the version existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x1D: versions 1 to 13 with checksums) means a table of nblocks
+Version 14 holds streams of the adaptive coder behind higher-order lagged differences (include/redux_hip.h, "higher-order
+lagged differences"): version 13 with the lag-S difference applied K times, the same sections, and decoding undoes layout,
+fold and filter with the lag and the order the word records.  The word at offset 12 is 0xE0000000 | K << 16 | S << 4 | E: no
+other version takes that word, and version 14 takes no other; K outside 2 .. 3 and S outside 1 .. 256 are InvalidInput.  Order
+1 is the lagged delta filter and is always written as version 13, so a version 14 word with K = 1 is malformed.  It has no
+stored blocks (no 0x4E / 0x5E).  Without an order above 1 the writers emit exactly the bytes they emitted before the version
+existed.  One version number, 15, is left under the flag bits.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1E: versions 1 to 14 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -143,6 +153,9 @@ VERSION_MIXED = 10
 VERSION_ZIGZAG = 11
 VERSION_BASE_SUB = 12
 VERSION_LAG = 13
+VERSION_LAG_ORDER = 14
+LAG_ORDER_MARK = 0xE0000000  # version 14's word at offset 12: LAG_ORDER_MARK | K << 16 | S << 4 | E
+LAG_ORDER_MAX = api.LAG_ORDER_MAX  # the largest order K (REDUX_LAG_ORDER_MAX); version 14 records 2 .. LAG_ORDER_MAX
 LAG_MARK = 0xD0000000  # version 13's word at offset 12: LAG_MARK | S << 4 | E
 LAG_MAX = api.LAG_MAX  # the largest lag S (REDUX_LAG_MAX)
 BASE_SUB_MARK = 0xC0000000  # version 12's word at offset 12: BASE_SUB_MARK | E
@@ -167,16 +180,24 @@ MAX_BLOCK_SIZE = 1 << 30
 
 # The versions that are version 2's sections behind a filter (version 2 itself: behind none): the marker nibble of the word
 # at offset 12, which is mark << 28 | E; the filter and the operation of the base filter a reader reports; whether the base
-# record follows the header; whether bits 4 .. 27 of the word hold the filter's lag (else they are 0).  pack, _version_ok,
-# _header and _parse_index go by this table: a new filter is a new row.
-_FilterVersion = namedtuple("_FilterVersion", "mark filter base_op has_base has_lag", defaults=(False,))
+# record follows the header; whether bits 4 .. 27 of the word hold the filter's lag (else they are 0); whether bits 16 .. 27
+# hold the filter's order, which leaves the lag bits 4 .. 15.  pack, _version_ok, _header and _parse_index go by this table: a
+# new filter is a new row.
+_FilterVersion = namedtuple("_FilterVersion", "mark filter base_op has_base has_lag has_order", defaults=(False, False))
 FILTER_VERSIONS = {VERSION_PLANES: _FilterVersion(0, None, None, False),
                    VERSION_DELTA: _FilterVersion(DELTA_MARK >> 28, "delta", None, False),
                    VERSION_BASE: _FilterVersion(BASE_MARK >> 28, None, "xor", True),
                    VERSION_ZIGZAG: _FilterVersion(ZIGZAG_MARK >> 28, "zigzag", None, False),
                    VERSION_BASE_SUB: _FilterVersion(BASE_SUB_MARK >> 28, None, "sub", True),
-                   VERSION_LAG: _FilterVersion(LAG_MARK >> 28, "lag", None, False, True)}
-_VERSION_OF_FILTER = {(row.filter, row.base_op): ver for ver, row in FILTER_VERSIONS.items()}
+                   VERSION_LAG: _FilterVersion(LAG_MARK >> 28, "lag", None, False, True),
+                   VERSION_LAG_ORDER: _FilterVersion(LAG_ORDER_MARK >> 28, "lag", None, False, True, True)}
+# (the lag filter's version goes by its order: 13 for order 1, 14 above)
+_VERSION_OF_FILTER = {(row.filter, row.base_op): ver for ver, row in FILTER_VERSIONS.items() if not row.has_order}
+
+
+def _lag_word(row, res):
+    """(S, K) of the word at offset 12 of a version whose row has a lag; K is None where the row has no order"""
+    return (res >> 4 & 0xFFF, res >> 16 & 0xFFF) if row.has_order else (res >> 4 & 0xFFFFFF, None)
 
 
 def _raw_lengths(nblocks, block_size, total):
@@ -186,7 +207,7 @@ def _raw_lengths(nblocks, block_size, total):
 
 
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None, unit_layouts=None, lag=None, base_op="xor"):
+         constant=None, unit_layouts=None, lag=None, order=None, base_op="xor"):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -198,6 +219,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     filter "delta": streams of compress_blocks(..., filter="delta") (version 6, any element_size; adaptive model, no stored).
     filter "zigzag": streams of compress_blocks(..., filter="zigzag") (version 11, as version 6).
     filter "lag" with lag S: streams of compress_blocks(..., filter="lag", lag=S) (version 13, as version 11).
+    order K (with filter "lag"): streams of compress_blocks(..., filter="lag", lag=S, order=K) (version 14 for K = 2 or 3;
+    None and 1: version 13).
     base (base_used, crc): streams of compress_blocks(..., base=y) with base_used = min(len(y), total_len) and crc =
     zlib.crc32(y[:base_used]) (version 8, any element_size; adaptive model, no stored, no filter).
     constant: nblocks 0 / 1 flags of compress_blocks(..., constant=) (version 9, any element_size, with or without base;
@@ -206,7 +229,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     element_size 1 and none of stored, filter, base and constant); None: no unit table.
     base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
     version 8)."""
-    front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag)
+    front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
+                                             order=order)
     xbase = front.takes_base
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
@@ -239,8 +263,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if filter is not None or xbase:
-        ver = _VERSION_OF_FILTER[filter, base_op if xbase else None]
-        res = FILTER_VERSIONS[ver].mark << 28 | (front.lag or 0) << 4 | element_size
+        ver = VERSION_LAG_ORDER if front.order else _VERSION_OF_FILTER[filter, base_op if xbase else None]
+        res = FILTER_VERSIONS[ver].mark << 28 | (front.order or 0) << 16 | (front.lag or 0) << 4 | element_size
     if const:
         ver, res = VERSION_CONST, CONST_MARK | (1 if xbase else 0) << 4 | element_size
     crc = b""
@@ -334,8 +358,10 @@ def _version_ok(ver, res):
     row = FILTER_VERSIONS.get(layout)
     if row is not None:  # (version 2 alone may have stored blocks, and has no element size 1: that is version 1)
         plain = layout == VERSION_PLANES
-        if row.has_lag and not 1 <= res >> 4 & 0xFFFFFF <= LAG_MAX:
-            return False
+        if row.has_lag:
+            S, K = _lag_word(row, res)
+            if not 1 <= S <= LAG_MAX or (row.has_order and not 2 <= K <= LAG_ORDER_MAX):
+                return False
         return res >> 28 == row.mark and res & (0xF if row.has_lag else 0x0FFFFFFF) in (() if plain else (1,)) + ELEMENT_SIZES \
             and (plain or not ver & STORED_FLAG)
     return (res == 0 and (layout == VERSION or (layout == VERSION_STATIC and not ver & STORED_FLAG))) \
@@ -361,9 +387,10 @@ def _has_base_record(ver, res):
 # base: (base_used, crc) of the record of version 8 or 12, or of version 9 with F = 1, else None; base_op: "xor" or "sub" where
 # there is a record, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
-# None, as the table holds it unit by unit.  lag: the lag S of version 13, else None.
+# None, as the table holds it unit by unit.  lag: the lag S of version 13 or 14, else None.  order: the order K of version 14,
+# else None.
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
-                        " unit_layouts base_op lag", defaults=(None, None, None))
+                        " unit_layouts base_op lag order", defaults=(None, None, None, None))
 
 
 def _header(b):
@@ -470,7 +497,7 @@ def _parse_index(b):
     row = FILTER_VERSIONS.get(_layout(ver))  # (version 9's record, where it has one, is the XOR's)
     return _Container(P, block_size, total, E, static, offsets, None, crcs, stored, row.filter if row else None, base, constant,
                       units, row.base_op if row else None if base is None else "xor",
-                      HEADER.unpack_from(b, 0)[6] >> 4 & 0xFFFFFF if row and row.has_lag else None), at
+                      *(_lag_word(row, HEADER.unpack_from(b, 0)[6]) if row and row.has_lag else (None, None))), at
 
 
 def _parse(buf):
@@ -508,14 +535,21 @@ def element_size(buf):
 
 def filter(buf):
     """"delta" for a version 6 container (the delta filter for integer series), "zigzag" for a version 11 container (the same
-    with folded differences), "lag" for a version 13 container (the lagged delta filter: lag()), None for every other version (version 10 records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
+    with folded differences), "lag" for a version 13 or 14 container (the lagged delta filter: lag(), order()), None for every other version (version 10 records the filter unit by unit: unit_layouts).  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).filter
 
 
 def lag(buf):
-    """The lag S of a version 13 container (the lagged delta filter); None for every other version.  Malformed containers
-    raise InvalidInput, truncated ones Eof."""
+    """The lag S of a version 13 or 14 container (the lagged delta filter, at order 1 or above); None for every other
+    version.  Malformed containers raise InvalidInput, truncated ones Eof."""
     return _parse(buf).lag
+
+
+def order(buf):
+    """The order K of the lagged delta filter: 2 or 3 for a version 14 container (higher-order lagged differences), 1 for a
+    version 13 container; None for every other version.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    c = _parse(buf)
+    return c.order if c.order is not None else None if c.lag is None else 1
 
 
 def base(buf):
@@ -590,7 +624,7 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
     because only the tables of contexts that occur are recorded.  filter "delta", "zigzag" or "lag" (adaptive model, not stored):
-    version 6, 11 or 13, which record the filter (and the lag) in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
+    version 6, 11 or 13 (14 at an order above 1: the same size), which record the filter (and the lag and the order) in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
     filter, not stored): version 10, whose unit table adds a byte per 8 blocks.  base (adaptive model, no filter, not stored, not
     mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation."""
     if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)) \
@@ -672,7 +706,7 @@ def choose_base_op(estimates):
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
                    stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, lag=None,
-                   base_op="xor"):
+                   order=None, base_op="xor"):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
     checksum: record the CRC-32 of every block (flag 0x10), taken by the same coding call.
@@ -690,6 +724,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     smallest estimate codes the data (api.choose_lag: counted on the GPU from the bytes as they are, exact on every frame for
     the finalists, lag 1 always among them), and the container is that lag's, version 13, which records it: nothing new to
     decode.  The filter itself stays opt-in.
+    order K, 1 .. 3 (with filter "lag" only): the lag-S difference applied K times, for sampled signals that are locally
+    polynomial; version 14 for K = 2 or 3, which records K, and version 13, byte for byte, for K = 1.  On random walks a
+    higher order costs bytes, so nothing chooses it.  Not with lag "auto" above order 1: the lag estimates count order 1 only.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
@@ -716,8 +753,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     auto_lag = isinstance(lag, str) and lag == "auto"  # (the choice is made below, once nothing else refuses the call)
     if auto_lag:
         lag = 1
-    if lag is not None or (isinstance(filter, str) and filter == "lag"):  # (a lag and its filter go together)
-        api._resolve_front(None, filter=filter, lag=lag)
+    if lag is not None or order is not None or (isinstance(filter, str) and filter == "lag"):  # (a lag, its order and their filter go together)
+        if api._resolve_front(None, filter=filter, lag=lag, order=order).front.order and auto_lag:
+            raise api.InvalidInput()  # (choose_lag counts order-1 costs only)
     if layout is not None:
         if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
                 or base is not None or skip_constant or not 0 < block_size <= MAX_BLOCK_SIZE \
@@ -732,7 +770,7 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         element_size, filter = choose_layout(estimate_layout_bytes(data, block_size, params, element_size, checksum))
     if (skip_constant or base is not None or filter is not None) and (model != "adaptive" or stored):
         raise api.InvalidInput()
-    api._resolve_front(None, filter=filter, base=base, constant=skip_constant or None, lag=lag)  # (the model is a name here)
+    api._resolve_front(None, filter=filter, base=base, constant=skip_constant or None, lag=lag, order=order)  # (the model is a name here)
     if model == "auto":
         if not 0 < block_size <= MAX_BLOCK_SIZE or (element_size != 1 and element_size not in ELEMENT_SIZES) or stored \
                 or segment_blocks is not None:
@@ -761,9 +799,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
         base_op = choose_base_op(api.estimate_base_ops(data, base, block_size, params, element_size))
     cflags = np.zeros(nb, dtype=np.uint8) if skip_constant else None
     out, offs, _ = api.compress_blocks(data, block_size, m, element_size=element_size, block_crc=crc, stored=flags, filter=filter,
-                                       base=base, constant=cflags, base_op=base_op, lag=lag)
+                                       base=base, constant=cflags, base_op=base_op, lag=lag, order=order)
     return pack(out, offs, m, block_size, len(data), element_size, block_crc=crc, stored=flags, filter=filter, base=record,
-                constant=cflags, base_op=base_op, lag=lag)
+                constant=cflags, base_op=base_op, lag=lag, order=order)
 
 
 def decompress_bytes(buf, base=None):
@@ -812,7 +850,7 @@ def _decode_parsed(c, base):
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
                                                        stored=c.stored, filter=c.filter, base=base, constant=c.constant,
-                                                       base_op=c.base_op or "xor", lag=c.lag)
+                                                       base_op=c.base_op or "xor", lag=c.lag, order=c.order)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
@@ -874,7 +912,7 @@ class Reader:
     not, CONTEXT_TABLES_MAX bytes are read and then parsed) and later only the streams of covered blocks: the payload of
     blocks no range covers is never read, so damage there -- a truncated file included -- does not matter to a range read.
     base: as for decompress_bytes; it is checked against the container's record here, once.
-    total, block_size, nblocks, version, filter, lag, base_op, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
+    total, block_size, nblocks, version, filter, lag, order, base_op, granule_blocks, payload_offset: the container's; bytes_read: the bytes fetched from
     the source so far."""
 
     def __init__(self, source, base=None):
@@ -900,7 +938,7 @@ class Reader:
         self._c, self.payload_offset = _parse_index(memoryview(index))
         c = self._c
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
-        self.filter, self.base_op, self.lag = c.filter, c.base_op, c.lag
+        self.filter, self.base_op, self.lag, self.order = c.filter, c.base_op, c.lag, c.order
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
             else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
         self._base = _checked_base(c, base)

@@ -15,6 +15,7 @@
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
 //   redux_zigzag.hpp   the zigzag fold: k_delta_*<E, true> is the delta filter with folded differences, for signed series
 //   redux_lag.hpp      k_lag_planes / k_lag_unplanes: the lagged delta filter for interleaved channels, the predecessor S elements back
+//   redux_lag_order.hpp k_lag_order_planes / k_lag_order_unplanes: higher-order lagged differences, the lag filter applied K times
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_base_sub.hpp BaseSubFold: the base filter's folded difference, the same kernels under another operation
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
@@ -49,6 +50,7 @@
 #include "redux_delta.hpp"
 #include "redux_zigzag.hpp"
 #include "redux_lag.hpp"
+#include "redux_lag_order.hpp"
 #include "redux_base.hpp"
 #include "redux_base_sub.hpp"
 #include "redux_hist.hpp"
@@ -653,6 +655,33 @@ static int launch_lag(const void *d_src, void *d_dst, uint64_t len, uint32_t blo
     return REDUX_OK;
 }
 
+// higher-order lagged differences (redux_lag_order.hpp): launch_lag with the order a second kernel argument
+template <int E>
+static int launch_lag_order(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t lag, uint32_t order,
+                            bool inverse, hipStream_t s)
+{
+    const uint64_t   frame = (uint64_t)E * block_size;
+    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
+    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
+    if (f.nfull) {
+        uint32_t grid;
+        if (inverse)
+            k_lag_order_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a, lag, order);
+        else if (!grid_tiles((a.groups + 255) / 256, &grid))
+            return REDUX_UNSUPPORTED;
+        else
+            k_lag_order_planes<E><<<grid, 256, 0, s>>>(a, lag, order);
+    }
+    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
+        if (inverse)
+            k_lag_order_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a, lag, order);
+        else
+            k_lag_order_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a, lag, order);
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
 // the base filter: the fused kernels take the full frames that lie inside the base, one workgroup per 256 groups; the byte
 // kernels take the rest up to the end of the frame the base ends in (or of the input); whole frames past the base have
 // nothing to XOR and go to the layout alone (launch_planes).  SUB: the folded difference (redux_base_sub.hpp) in place of
@@ -720,27 +749,31 @@ static int for_element_size(uint32_t element_size, F &&f)
 }
 
 // The filter in front of the byte-plane layout: none; the delta filter, its differences plain or folded (redux_delta.hpp,
-// redux_zigzag.hpp); the lagged delta filter, whose lag travels next to the value (redux_lag.hpp); the base filter, the XOR
-// or the folded difference (redux_base.hpp, redux_base_sub.hpp).  The one name a filter has from the C entry points down to
+// redux_zigzag.hpp); the lagged delta filter, whose lag travels next to the value (redux_lag.hpp), and its higher orders,
+// whose order travels there too (redux_lag_order.hpp); the base filter, the XOR or the folded difference (redux_base.hpp,
+// redux_base_sub.hpp).  The one name a filter has from the C entry points down to
 // the kernel launch: a new filter is a new value here.
-enum class Filter { None, Delta, Zigzag, Lag, BaseXor, BaseSub };
+enum class Filter { None, Delta, Zigzag, Lag, LagOrder, BaseXor, BaseSub };
 
 static bool filter_has_base(Filter f) { return f == Filter::BaseXor || f == Filter::BaseSub; }
 
-// the element size's check, and the lag's where the filter has one
-static int filter_check(Filter f, uint32_t element_size, uint32_t lag)
+// the element size's check, and the lag's and the order's where the filter has them
+static int filter_check(Filter f, uint32_t element_size, uint32_t lag, uint32_t order)
 {
-    return f == Filter::Lag ? redux_lag_check(element_size, lag) : redux_planes_check(element_size);
+    return f == Filter::LagOrder ? redux_lag_order_check(element_size, lag, order)
+           : f == Filter::Lag    ? redux_lag_check(element_size, lag)
+                                 : redux_planes_check(element_size);
 }
 
-// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev, redux_lag_planes_dev, redux_base_planes_dev and
-// redux_base_sub_planes_dev: the checks, then the transform's launch for the element size.  d_base[0 .. base_len): the base of
-// a base filter; lag: the lag of the lagged delta filter.
+// redux_planes_dev, redux_delta_planes_dev, redux_zigzag_planes_dev, redux_lag_planes_dev, redux_lag_order_planes_dev,
+// redux_base_planes_dev and redux_base_sub_planes_dev: the checks, then the transform's launch for the element size.
+// d_base[0 .. base_len): the base of a base filter; lag: the lag of the lagged delta filter; order: that of its higher orders.
 static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
-                         int inverse, void *stream, const void *d_base = nullptr, uint64_t base_len = 0, uint32_t lag = 0)
+                         int inverse, void *stream, const void *d_base = nullptr, uint64_t base_len = 0, uint32_t lag = 0,
+                         uint32_t order = 0)
 {
     const bool base = filter_has_base(filter);
-    if (filter_check(filter, element_size, lag) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
+    if (filter_check(filter, element_size, lag, order) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)) || (base && base_len && !d_base))
         return REDUX_INVALID_INPUT;
     if (len == 0)
         return REDUX_OK;
@@ -758,6 +791,7 @@ static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t
         switch (filter) {
         case Filter::BaseSub: return launch_base<E, true>(d_src, d_base, used, d_dst, len, block_size, inv, s);
         case Filter::BaseXor: return launch_base<E, false>(d_src, d_base, used, d_dst, len, block_size, inv, s);
+        case Filter::LagOrder: return launch_lag_order<E>(d_src, d_dst, len, block_size, lag, order, inv, s);
         case Filter::Lag: return launch_lag<E>(d_src, d_dst, len, block_size, lag, inv, s);
         case Filter::Zigzag: return launch_delta<E, true>(d_src, d_dst, len, block_size, inv, s);
         case Filter::Delta: return launch_delta<E, false>(d_src, d_dst, len, block_size, inv, s);
@@ -781,18 +815,19 @@ struct Layout {
     const void *d_base   = nullptr; // a base filter's base, d_base[0 .. base_len) on the device
     uint64_t    base_len = 0;
     uint32_t    lag      = 0;       // the lagged delta filter's lag
-    int         check() const { return filter_check(filter, E, lag); }
+    uint32_t    order    = 0;       // the order of higher-order lagged differences
+    int         check() const { return filter_check(filter, E, lag, order); }
     bool        identity() const { return filter == Filter::None && E == 1; }
     bool        has_base() const { return filter_has_base(filter); }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter, d_src, d_dst, len, block_size, E, 0, stream, d_base, base_len, lag);
+        return transform_dev(filter, d_src, d_dst, len, block_size, E, 0, stream, d_base, base_len, lag, order);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter, d_src, d_dst, len, block_size, E, 1, stream, d_base, base_len, lag);
+        return transform_dev(filter, d_src, d_dst, len, block_size, E, 1, stream, d_base, base_len, lag, order);
     }
 };
 
@@ -2333,9 +2368,9 @@ int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const
     return redux_static_decode_blocks_crc(p, cum, in, in_offsets, nblocks, block_size, out, out_cap, out_sizes, block_status, nullptr);
 }
 
-// ---- the layered adaptive calls: byte-plane layout, delta, zigzag, lag, base and base_sub -----------------------------
-// Six families of eight entry points (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_lag.hpp, redux_base.hpp,
-// redux_base_sub.hpp), one Filter each: every body below the shared functions is one call into them.
+// ---- the layered adaptive calls: byte-plane layout, delta, zigzag, lag, lag_order, base and base_sub ------------------
+// Seven families of eight entry points (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_lag.hpp,
+// redux_lag_order.hpp, redux_base.hpp, redux_base_sub.hpp), one Filter each: every body below the shared functions is one call into them.
 int redux_planes_check(uint32_t element_size)
 {
     return (element_size == 1 || element_size == 2 || element_size == 4 || element_size == 8) ? REDUX_OK : REDUX_INVALID_INPUT;
@@ -2345,6 +2380,10 @@ int redux_zigzag_check(uint32_t element_size) { return redux_planes_check(elemen
 int redux_lag_check(uint32_t element_size, uint32_t lag)
 {
     return redux_planes_check(element_size) == REDUX_OK && lag >= 1 && lag <= REDUX_LAG_MAX ? REDUX_OK : REDUX_INVALID_INPUT;
+}
+int redux_lag_order_check(uint32_t element_size, uint32_t lag, uint32_t order)
+{
+    return redux_lag_check(element_size, lag) == REDUX_OK && order >= 1 && order <= REDUX_LAG_ORDER_MAX ? REDUX_OK : REDUX_INVALID_INPUT;
 }
 int redux_base_check(uint32_t element_size) { return redux_planes_check(element_size); }
 int redux_base_sub_check(uint32_t element_size) { return redux_planes_check(element_size); }
@@ -2451,12 +2490,13 @@ static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_si
 // the host-pointer calls (redux_host.hpp); base[0 .. base_len): a base filter's base, the chunks take their shares of it
 static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
                                 uint64_t base_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
-                                uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0)
+                                uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0,
+                                uint32_t order = 0)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    const Layout L{element_size, f, nullptr, 0, lag};
+    const Layout L{element_size, f, nullptr, 0, lag, order};
     if (L.check() != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) ||
         (L.has_base() && base_len && !base))
         return REDUX_INVALID_INPUT;
@@ -2467,9 +2507,10 @@ static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *
 
 static int decode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
                                 uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
-                                uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0)
+                                uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0,
+                                uint32_t order = 0)
 {
-    const Layout L{element_size, f, nullptr, 0, lag};
+    const Layout L{element_size, f, nullptr, 0, lag, order};
     int st = check_params(p);
     if (st == REDUX_OK && (L.check() != REDUX_OK || (L.has_base() && base_len && !base)))
         st = REDUX_INVALID_INPUT;
@@ -2677,6 +2718,55 @@ int redux_decode_blocks_lag(const redux_params *p, const uint8_t *in, const uint
 {
     return decode_blocks_layout(Filter::Lag, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
                                 block_status, block_crc, lag);
+}
+
+// -- higher-order lagged differences
+int redux_lag_order_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, uint32_t lag,
+                               uint32_t order, int inverse, void *stream)
+{
+    return transform_dev(Filter::LagOrder, d_src, d_dst, len, block_size, element_size, inverse, stream, nullptr, 0, lag, order);
+}
+
+uint64_t redux_encode_lag_order_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_encode_zigzag_workspace_bytes(p, in_len, block_size, element_size);
+}
+
+uint64_t redux_decode_lag_order_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_decode_zigzag_workspace_bytes(p, out_len, block_size, element_size);
+}
+
+int redux_encode_lag_order_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint32_t lag, uint32_t order, void *d_out, uint64_t out_cap, void *d_out_offsets,
+                               void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(Layout{element_size, Filter::LagOrder, nullptr, 0, lag, order}, p, d_in, in_len, block_size, d_out,
+                             out_cap, d_out_offsets, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_lag_order_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len, uint32_t block_size,
+                               uint32_t element_size, uint32_t lag, uint32_t order, void *d_out, void *d_out_sizes,
+                               void *d_block_status, void *d_summary, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(Layout{element_size, Filter::LagOrder, nullptr, 0, lag, order}, p, d_in, d_in_offsets, out_len, block_size,
+                             d_out, d_out_sizes, d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_lag_order(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                                  uint32_t element_size, uint32_t lag, uint32_t order, uint8_t *out, uint64_t out_cap,
+                                  uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc)
+{
+    return encode_blocks_layout(Filter::LagOrder, p, in, in_len, nullptr, 0, block_size, element_size, out, out_cap, out_offsets,
+                                block_status, block_crc, lag, order);
+}
+
+int redux_decode_blocks_lag_order(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                                  uint32_t block_size, uint32_t element_size, uint32_t lag, uint32_t order, uint8_t *out,
+                                  uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc)
+{
+    return decode_blocks_layout(Filter::LagOrder, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
+                                block_status, block_crc, lag, order);
 }
 
 // -- XOR-against-base filter

@@ -16,6 +16,7 @@
 //   redux::hip::compress_blocks_delta / decompress_blocks_delta     integer series behind the delta filter
 //   redux::hip::compress_blocks_zigzag / decompress_blocks_zigzag   signed series behind the zigzag-folded delta filter
 //   redux::hip::compress_blocks_lag / decompress_blocks_lag         interleaved channels behind the lagged delta filter
+//   redux::hip::compress_blocks_lag_order / decompress_blocks_lag_order   sampled signals behind higher-order lagged differences
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_base_sub / decompress_blocks_base_sub   the same behind the folded difference against the base
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
@@ -321,6 +322,48 @@ inline std::vector<std::uint8_t> decompress_blocks_lag(const Blocks &streams, st
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_lag(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, lag, out.data(),
                                   sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// Sampled signals behind higher-order lagged differences (include/redux_hip.h, "higher-order lagged differences"):
+// compress_blocks_lag with the lag-S difference applied `order` times, 1 <= order <= REDUX_LAG_ORDER_MAX; order 1 gives
+// compress_blocks_lag's streams.  Opt-in: on random walks a higher order costs bytes, and the decoder needs the same lag and
+// order.
+inline Blocks compress_blocks_lag_order(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size, std::uint32_t element_size,
+                                        std::uint32_t lag, std::uint32_t order, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_lag_order_check(element_size, lag, order) != REDUX_OK)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_lag_order(&cp, in, len, block_size, element_size, lag, order, b.data.data(), b.data.size(),
+                                        b.offsets.data(), nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_lag_order(const Blocks &streams, std::uint64_t len, std::uint32_t block_size,
+                                                             std::uint32_t element_size, std::uint32_t lag, std::uint32_t order,
+                                                             const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_lag_order_check(element_size, lag, order) != REDUX_OK ||
+        redux_block_count(len, block_size) + 1 != streams.offsets.size() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_lag_order(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, lag, order,
+                                        out.data(), sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }

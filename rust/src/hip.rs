@@ -78,6 +78,13 @@ extern "C" {
     fn redux_decode_blocks_lag(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                block_size: u32, element_size: u32, lag: u32, out: *mut u8, out_sizes: *mut u32,
                                block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // higher-order lagged differences: the lag calls' shape with the order behind the lag
+    fn redux_encode_blocks_lag_order(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                     lag: u32, order: u32, out: *mut u8, out_cap: u64, out_offsets: *mut u64,
+                                     block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_lag_order(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                     block_size: u32, element_size: u32, lag: u32, order: u32, out: *mut u8,
+                                     out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
     // XOR-against-base filter for series of snapshots, in front of the byte-plane layout (base null only with base_len 0;
     // block_crc may be null)
     fn redux_encode_blocks_base(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
@@ -495,6 +502,53 @@ pub fn decompress_blocks_lag(streams: &[u8], offsets: &[u64], len: u64, block_si
         let mut sizes = vec![0u32; nb];
         try!(status(redux_decode_blocks_lag(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size, lag,
                                             out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks_lag` with the lag-`lag` difference applied `order` times, 1 to 3 (include/redux_hip.h, "higher-order
+/// lagged differences"): for sampled signals that are locally polynomial.  Order 1 gives `compress_blocks_lag`'s streams.
+/// Opt-in: on random walks a higher order costs bytes.
+pub fn compress_blocks_lag_order(data: &[u8], block_size: u32, element_size: u32, lag: u32, order: u32,
+                                 p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_lag_order(&cp, data.as_ptr(), data.len() as u64, block_size, element_size, lag, order,
+                                                  out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut(),
+                                                  ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_lag_order` with the same `lag` and `order`: `len` is the original byte count; returns the
+/// original bytes.
+pub fn decompress_blocks_lag_order(streams: &[u8], offsets: &[u64], len: u64, block_size: u32, element_size: u32, lag: u32,
+                                   order: u32, p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_lag_order(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size, lag,
+                                                  order, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
+                                                  ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
