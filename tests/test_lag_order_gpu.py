@@ -131,6 +131,171 @@ def test_lag_order_planes_dev_rejects_bad_arguments(rx, lib):
         api.lag_order_planes(a, 3, 64, 2, 2, out=b)
 
 
+# ---- several frames per workgroup and per wave ------------------------------------------------------------------------
+# The tests above give every input two full frames and a short one: no workgroup of the inverse kernels walks on to a second
+# frame (carry[K][S], tot, last[K][2][256], par and the tile as the frame before left them), no wave of the forward kernel
+# holds more than two frames (gi % frame_groups), and a frame has 4, 256, 257 or 769 groups.
+def first_difference(got, want, E, B):
+    at = int(np.nonzero(got != want)[0][0])
+    return f"first difference at byte {at} (frame {at // (E * B)}, offset {at % (E * B)})"
+
+
+# Frames of 1, 3, 5, 63 and 65 groups (N = B elements).  The lags: 1, 2, 3 and 17 always; for the three small frames S, 2S
+# and 3S below, at (where N divides) and above N, up to S >= N where only the fold is left; for the two large ones 3S stays
+# below N (S <= 256), so the scan's last steps, 3S at either side of 256 and a 16-byte chunk.
+MANY_FRAMES_LAGS = {16: [1, 2, 3, 5, 6, 7, 8, 9, 15, 16, 17, 256], 48: [1, 2, 3, 15, 16, 17, 23, 24, 25, 47, 48, 49],
+                    80: [1, 2, 3, 17, 26, 27, 39, 40, 41, 79, 80, 81], 1008: [1, 2, 3, 16, 17, 85, 86, 255, 256],
+                    1040: [1, 2, 3, 16, 17, 85, 86, 255, 256]}
+
+
+def test_the_lags_of_the_short_frames_lie_on_every_side_of_the_frame():
+    for B, lags in MANY_FRAMES_LAGS.items():
+        assert {1, 2, 3, 17} <= set(lags) and all(1 <= S <= 256 for S in lags) and B % 16 == 0
+        for j in (1, 2, 3):
+            sides = {(j * S > B) - (j * S < B) for S in lags}
+            assert sides == ({-1} if 3 * 256 < B else {-1, 0, 1} if B % j == 0 else {-1, 1}), (B, j)
+    assert [B // 16 for B in MANY_FRAMES_LAGS] == [1, 3, 5, 63, 65]
+
+
+@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("E", [1, 2, 4, 8])
+@pytest.mark.parametrize("B", sorted(MANY_FRAMES_LAGS))
+def test_lag_order_kernels_at_many_short_frames(rx, E, B, K):
+    """203 full frames, a short one and E - 1 trailing bytes; frames of 1, 3 and 5 groups put up to 64 frames into one wave of
+    k_lag_order_planes, 63 and 65 groups let every wave start at another group of its frame; both directions."""
+    import torch
+    nf = 203
+    x = np.random.default_rng(E * 7 + B + K).integers(0, 256, nf * E * B + (B // 3 + 1) * E + (E - 1), dtype=np.uint8)
+    for S in MANY_FRAMES_LAGS[B]:
+        for inverse in (False, True):
+            want = lag_order_planes_ref(x, E, B, S, K, inverse=inverse)
+            got, intact = run_dev(torch, x, E, B, S, K, inverse)
+            assert np.array_equal(got, want), f"E={E} B={B} S={S} K={K} inverse={inverse}: " + first_difference(got, want, E, B)
+            assert intact, (E, B, S, K, inverse)
+
+
+@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("E", [1, 2, 4, 8])
+@pytest.mark.parametrize("B", [65520, 65552, 100_000, 1 << 20])
+def test_lag_order_kernels_at_frames_that_end_inside_a_turn(rx, E, B, K):
+    """Three full frames and a short one (a third of a frame, five elements and E - 1 trailing bytes), as for the order-1
+    kernels: uniform bytes, whose K-fold running sums wrap mod 2^(8E) every few elements, in the partial last turn of every
+    frame too; and all-0xFF bytes.  S = 3, 255 and 256, both directions."""
+    import torch
+    rng = np.random.default_rng(E * 1000 + B % 997 + K)
+    n = 3 * E * B + (B // 3 + 5) * E + E - 1
+    for x in (rng.integers(0, 256, n, dtype=np.uint8), np.full(n, 0xFF, np.uint8)):
+        for S in (3, 255, 256):
+            for inverse in (False, True):
+                want = lag_order_planes_ref(x, E, B, S, K, inverse=inverse)
+                got, intact = run_dev(torch, x, E, B, S, K, inverse)
+                assert np.array_equal(got, want), f"E={E} B={B} S={S} K={K} inverse={inverse}: " + first_difference(got, want, E, B)
+                assert intact, (E, B, S, K, inverse)
+
+
+def test_lag_order_kernels_at_one_very_long_frame(rx):
+    """B = 2^22 + 16, E = 2, S = 5, K = 3: a frame of 2^18 + 1 groups, 1025 rows of the fused kernels with one group in the last
+    row (the three carries and the tile are reused 1024 times inside one frame), then a short frame; both directions."""
+    import torch
+    E, B, S, K = 2, (1 << 22) + 16, 5, 3
+    assert B // 16 == 1024 * 256 + 1
+    x = np.random.default_rng(22).integers(0, 256, E * B + (B // 3 + 5) * E + 1, dtype=np.uint8)
+    for inverse in (False, True):
+        want = lag_order_planes_ref(x, E, B, S, K, inverse=inverse)
+        got, intact = run_dev(torch, x, E, B, S, K, inverse)
+        assert np.array_equal(got, want), f"inverse={inverse}: " + first_difference(got, want, E, B)
+        assert intact, inverse
+
+
+def on_device_poisoned(torch, n):
+    """poisoned() for an input too large to pass through the host: (whole buffer, view of n bytes) with FRONT bytes of FILL in
+    front and a guard band behind"""
+    t = torch.full((FRONT + n + GUARD + 16,), FILL, dtype=torch.uint8, device="cuda:0")
+    return t, t[FRONT: FRONT + n]
+
+
+def bands_intact(t, lo, n):
+    return bool((t[:lo] == FILL).all()) and bool((t[lo + n:] == FILL).all())
+
+
+@pytest.mark.parametrize("K", [2, 3])
+def test_fused_lag_order_inverse_with_more_frames_than_workgroups(rx, K):
+    """E = 1, B = 4112 (257 groups: two rows a frame, so the K carries are live), S = 3, 2^20 + 3 frames and a short one, past
+    2^32 bytes: the grid-stride loop of k_lag_order_unplanes, where three workgroups go on to a second frame with carry[][],
+    tot[][] and the tile as the first one left them.  The input is tiled on the device from 8 distinct frames in an aperiodic
+    order (no period that divides the grid or 4), the expected output is the same tiling of the per-frame restatement,
+    compared on the device; the forward kernel takes the result back to the input."""
+    import torch
+    from redux_amd import api
+    E, B, S, nf, short = 1, 4112, 3, (1 << 20) + 3, 1237
+    rng = np.random.default_rng(4112 + K)
+    frames = rng.integers(0, 256, (8, B), dtype=np.uint8)
+    last = rng.integers(0, 256, short, dtype=np.uint8)
+    f = torch.arange(nf, device="cuda:0")
+    idx = (f * f // 7 + f // 5 + f) % 8                                      # (no period)
+    assert len(set(np.diff(np.nonzero((idx[:4096] == 0).cpu().numpy())[0]).tolist())) > 4
+    assert len({int(idx[w]) for w in range(3)} | {int(idx[(1 << 20) + w]) for w in range(3)}) > 1
+    n = nf * B + short
+    assert n > 1 << 32
+    ts, src = on_device_poisoned(torch, n)
+    src[: nf * B].view(nf, B).copy_(torch.from_numpy(frames).cuda()[idx])
+    src[nf * B:].copy_(torch.from_numpy(last).cuda())
+    want = torch.from_numpy(np.stack([lag_order_planes_ref(fr, E, B, S, K, inverse=True) for fr in frames])).cuda()
+    want_last = torch.from_numpy(lag_order_planes_ref(last, E, B, S, K, inverse=True)).cuda()
+    td, dst = guarded(torch, n)
+    api.lag_order_planes(src, E, B, S, K, inverse=True, out=dst)
+    torch.cuda.synchronize()
+    assert bands_intact(td, GUARD, n) and bands_intact(ts, FRONT, n)
+    step = 1 << 17
+    for f0 in range(0, nf, step):
+        got = dst[f0 * B: min(f0 + step, nf) * B].view(-1, B)
+        bad = (got != want[idx[f0: f0 + step]]).any(1)
+        if bool(bad.any()):
+            fr = f0 + int(bad.nonzero()[0])
+            at = int((dst[fr * B: (fr + 1) * B] != want[idx[fr]]).nonzero()[0])
+            raise AssertionError(f"K={K}: frame {fr} (distinct frame {int(idx[fr])}) differs at byte {at}")
+    assert torch.equal(dst[nf * B:], want_last)
+    tb, back = guarded(torch, n)
+    api.lag_order_planes(dst, E, B, S, K, inverse=False, out=back)
+    torch.cuda.synchronize()
+    assert bands_intact(tb, GUARD, n) and bands_intact(td, GUARD, n)
+    assert torch.equal(back, src)
+    del ts, src, td, dst, tb, back, got, bad, want
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()                                                 # (three buffers of 4.3 GB)
+
+
+@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("S", [3, 256])
+def test_byte_lag_order_inverse_past_2_pow_20_frames(rx, S, K):
+    """E = 1, B = 400 (no multiple of 16: the byte kernels; two iterations of 256 elements a frame, so the chains' carries in
+    last[][][] are live, and par goes on from frame to frame), 2^20 + 3 frames and a short one of 77 bytes: the grid-stride
+    loop of k_lag_order_unplanes_bytes.  (Nearly all of the time is numpy over the 419 MB of the restatement, K passes.)"""
+    import torch
+    E, B, nf, short = 1, 400, (1 << 20) + 3, 77
+    x = np.random.default_rng(400 + S + K).integers(0, 256, nf * B + short, dtype=np.uint8)
+    # the restatement, vectorised over the full frames (the per-frame loop of lag_order_planes_ref takes minutes here) ...
+    body = x[: nf * B].reshape(nf, B)
+    r = (body >> 1) ^ np.negative(body & 1)                             # unfold: (z >> 1) ^ (0 - (z & 1)) mod 256
+    for _ in range(K):                                                   # the S running sums, K times
+        if S < B // 2:
+            for c in range(S):                                           # chain c: elements c, c + S, ...
+                r[:, c::S] = np.cumsum(r[:, c::S], axis=1, dtype=np.uint8)
+        else:
+            r[:, S:] += r[:, : B - S]                                    # (chains of two elements at the most)
+    want = np.concatenate([r.reshape(-1), lag_order_planes_ref(x[nf * B:], E, B, S, K, inverse=True)])
+    # ... checked against lag_order_planes_ref on both ends
+    k = 100 * B
+    assert np.array_equal(want[:k], lag_order_planes_ref(x[:k], E, B, S, K, inverse=True))
+    assert np.array_equal(want[-k - short:], lag_order_planes_ref(x[-k - short:], E, B, S, K, inverse=True))
+    assert not np.array_equal(want[:k], lag_order_planes_ref(x[:k], E, B, S, K - 1, inverse=True))
+    got, intact = run_dev(torch, x, E, B, S, K, True)
+    assert np.array_equal(got, want), f"S={S} K={K}: " + first_difference(got, want, E, B)
+    assert intact
+    back, intact = run_dev(torch, got, E, B, S, K, False)
+    assert intact and np.array_equal(back, x)
+
+
 # ---- streams: the plain coder on the transformed bytes, against the oracle ------------------------------------------------
 @pytest.mark.parametrize("K", [2, 3])
 @pytest.mark.parametrize("E", [2, 4])

@@ -1,6 +1,6 @@
 """Every layer in front of the adaptive coder on every coder instance below it (tests/test_layered_instances_gpu.py): the
 CPU side.  The layers: byte planes, the delta filter and stored blocks; then constant blocks, the mixed layouts and the
-zigzag, lag, base XOR and base folded-difference filters.
+zigzag, lag, base XOR and base folded-difference filters; then the higher-order lagged differences (lag order).
 
 Each layer's `_dev` calls are a few lines in front of encode_slots_impl / redux_encode_blocks_dev, and their decode calls
 in front of decode_blocks_dev_impl; what can go wrong is in the seams: which buffer the coder and the compaction read (the
@@ -21,6 +21,8 @@ table form, planned for nblocks * block_size bytes.  Here, without a GPU:
         mixed                        7 (MIXED_WHYS)                                (units of 8)  a dictated table of all 8 layouts
         zigzag, lag, base, base_sub  8 each (FILTER_WHYS)                          1, 2, 4, 8    lag 3, 2, 17, 256, 5, 64, 255, 16;
                                                                                                  base as const, once longer than x
+        lag_order                    8 (FILTER_WHYS)                               1, 2, 4, 8    the same lags; order 2, 3, 3, 2, 3, 2, 2, 3:
+                                                                                                 both orders at every element size
   * the table covers, per layer, every reason: removing a row fails test_the_table_covers_every_reason, which compares
     ROWS with a list written out per layer and asserts the encoders, decoders, element sizes, lags and kinds of base reached;
   * the table form of the decoders never names k_decode_cells<8> (redux_decode_kernel_name_table);
@@ -29,10 +31,11 @@ table form, planned for nblocks * block_size bytes.  Here, without a GPU:
   * the audit (run with -s): which instance each older GPU test of the layers runs today.
 Instance x layer pairs left out: the fix-up cell decoders of the widths below 8 (the plain table has them, the wrappers
 add nothing width-dependent); under constant blocks the general-symbol coders (UNSUPPORTED, asserted); under the mixed
-layouts and the four later filters the reasons that differ from a row of theirs only in the code width or in a decoder
-the same launch code reaches under delta (they share layout_stage and layout_decode_tail with it by construction: the
-sixteen reasons of delta stay delta's), and the decode-only launch of 4 MiB blocks."""
+layouts, the four later filters and the lag order the reasons that differ from a row of theirs only in the code width or
+in a decoder the same launch code reaches under delta (they share layout_stage and layout_decode_tail with it by
+construction: the sixteen reasons of delta stay delta's), and the decode-only launch of 4 MiB blocks."""
 import ctypes as C
+import zlib
 
 import numpy as np
 import pytest
@@ -42,8 +45,10 @@ from test_stream_ranges_cpu import ANY, CELLS8, CELLS8_FIX, GENERIC32, LOCK, WAV
 
 PLANES, DELTA, STORED = "planes", "delta", "stored"
 CONST, MIXED, ZIGZAG, LAG, BASE, BASE_SUB = "const", "mixed", "zigzag", "lag", "base", "base_sub"
+LAG_ORDER = "lag_order"                                   # (the infix of redux_encode_lag_order_workspace_bytes)
 FIRST_LAYERS = (PLANES, DELTA, STORED)
-FILTERS = (ZIGZAG, LAG, BASE, BASE_SUB)                   # the filters of layout_stage / layout_decode_tail behind delta
+FILTERS = (ZIGZAG, LAG, BASE, BASE_SUB, LAG_ORDER)        # the filters of layout_stage / layout_decode_tail behind delta
+WITH_LAG = (LAG, LAG_ORDER)                               # the calls that take a lag (the lag order: and an order behind it)
 WITH_BASE = (CONST, BASE, BASE_SUB)                       # the calls that take (d_base, base_len)
 LAYERS = FIRST_LAYERS + (CONST, MIXED) + FILTERS
 P32, P24, P16 = (8, 30, 32), (8, 22, 24), (8, 14, 16)
@@ -117,6 +122,7 @@ LATER_WHYS = {CONST: _STORED_WHYS, MIXED: MIXED_WHYS, **{f: FILTER_WHYS for f in
 MIXED_UNIT = 8                                             # REDUX_MIXED_UNIT_BLOCKS: a mixed row's "E" is the unit, in blocks
 ELEMENT.update({CONST: (1, 2, 4, 8), MIXED: (MIXED_UNIT,), **{f: (1, 2, 4, 8) for f in FILTERS}})
 LAGS = (3, 2, 17, 256, 5, 64, 255, 16)                     # by turn, from the first row of the lag filter on
+ORDERS = (2, 3, 3, 2, 3, 2, 2, 3)                          # by turn: with E = 1, 2, 4, 8 by turn every element size meets both
 # the base of a row, by turn: none (base_len 0), as long as the input, ending inside a frame at an odd byte; and one row
 # of each base filter with a base longer than the input
 BASE_KINDS = ("none", "full", "inside")
@@ -124,7 +130,7 @@ PINNED.update({(CONST, "single16_by_alignment"): (1, 4),   # E = 1 without a bas
                (CONST, "pair_by_blocks_cb32"): (1, 4)})    # ... the same shape WITH a base reads the copy: the pair kernel
 PINNED_BASE = {(CONST, "single16_by_alignment"): "none", (CONST, "pair_by_blocks_cb32"): "full",
                (BASE, "single32_by_workspace"): "longer", (BASE_SUB, "single32_by_workspace"): "longer"}
-# id -> (lag or None, kind of base or None)
+# id -> (lag or None, kind of base or None, order or None)
 EXTRA = {}
 for _layer in (CONST, MIXED) + FILTERS:
     for _turn, _why in enumerate(LATER_WHYS[_layer]):
@@ -135,7 +141,8 @@ for _layer in (CONST, MIXED) + FILTERS:
             _off = 0                                       # (as for stored: the caller's buffer is what the coder reads)
         _id = f"{_layer}_{_why}" if _layer == MIXED else f"{_layer}_e{_E}_{_why}"
         ROWS[_id] = (_layer, _p, _E, _bs, _nb, _off, _ws, _enc, _dec_t if _layer == CONST else _dec, _why)
-        EXTRA[_id] = (LAGS[_turn % len(LAGS)] if _layer == LAG else None, _base)
+        EXTRA[_id] = (LAGS[_turn % len(LAGS)] if _layer in WITH_LAG else None, _base,
+                      ORDERS[_turn % len(ORDERS)] if _layer == LAG_ORDER else None)
 
 
 def base_len_of(kind, in_len, E, bs):
@@ -237,7 +244,7 @@ def layer_dec_name(layer, params, bs, nb):
 @pytest.mark.parametrize("key", sorted(ROWS))
 def test_every_row_maps_to_its_instances(key):
     layer, params, E, bs, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base = EXTRA.get(key, (None, None))
+    lag, base, order = EXTRA.get(key, (None, None, None))
     in_len = input_len(params, bs, nb)
     L = _lib()
     plain = L.lib().redux_encode_workspace_bytes(C.byref(L.Params(*params)), coded_len(layer, bs, in_len), bs)
@@ -253,7 +260,7 @@ def test_every_row_maps_to_its_instances(key):
         assert table % 256 == 0 and table >= 8 * nb          # (an entry: at least an offset and a length)
     elif layer == MIXED:   # the copy and the cost rows f64[8][nblocks]
         assert copy == copy_bytes(DELTA, params, 1, bs, in_len) + (nb * 64 + 255) // 256 * 256
-    else:                  # the five filters: always a copy, of the planes call's size; lag, zigzag, base at E = 1 are no identity
+    else:                  # the filters: always a copy, of the planes call's size; lag, zigzag, base at E = 1 are no identity
         assert copy == copy_bytes(DELTA, params, E, bs, in_len) >= in_len
     if layer in WITH_BASE:
         n = base_len_of(base, in_len, E, bs)
@@ -261,7 +268,8 @@ def test_every_row_maps_to_its_instances(key):
                 "inside": 0 < n < in_len - E * bs and n % 2 == 1 and 0 < n % (E * bs) < E * bs - 1 and n % E == E - 1}[base]
     else:
         assert base is None
-    assert (1 <= lag <= 256) if layer == LAG else lag is None
+    assert (1 <= lag <= 256) if layer in WITH_LAG else lag is None
+    assert (order in (2, 3) and 3 * lag < bs) if layer == LAG_ORDER else order is None    # all K predecessors inside a frame
     if enc is not None:
         assert layer_enc_name(layer, params, E, bs, nb, off, ws, base=base) == enc
         if reads_copy(layer, E, base):       # the coder reads the copy: the caller's alignment selects nothing
@@ -287,16 +295,25 @@ _FILTER = ["coop_whole_cb16", "coop_windows_150k", "pair_by_blocks_cb32", "pair_
 WANT_ROWS = {PLANES: _TYPED, DELTA: _TYPED, STORED: _TABLE, CONST: _TABLE,
              MIXED: ["coop_whole_cb32", "coop_windows_100k", "pair_by_blocks_cb32", "pair_by_workspace", "single16_by_block_size",
                      "single32_by_workspace", "cells8"],
-             ZIGZAG: _FILTER, LAG: _FILTER, BASE: _FILTER, BASE_SUB: _FILTER}
-WANT_COUNT = {PLANES: 16, DELTA: 16, STORED: 12, CONST: 12, MIXED: 7, ZIGZAG: 8, LAG: 8, BASE: 8, BASE_SUB: 8}
+             ZIGZAG: _FILTER, LAG: _FILTER, BASE: _FILTER, BASE_SUB: _FILTER, LAG_ORDER: _FILTER}
+WANT_COUNT = {PLANES: 16, DELTA: 16, STORED: 12, CONST: 12, MIXED: 7, ZIGZAG: 8, LAG: 8, BASE: 8, BASE_SUB: 8, LAG_ORDER: 8}
+# the 95 rows the table held before the lag order came: none of their ids may change (CRC-32 of the sorted ids, one a line)
+OLD_IDS, OLD_IDS_CRC = 95, 1587991626
 
 
 def test_the_table_covers_every_reason():
-    """Per layer every reason of WANT_ROWS, once (16 + 16 + 12 rows of the first layers, 12 + 7 + 4 * 8 of the later ones);
-    and per layer every instance, element size, lag and kind of base."""
+    """Per layer every reason of WANT_ROWS, once (16 + 16 + 12 rows of the first layers, 12 + 7 + 4 * 8 of the later ones, 8
+    of the lag order); and per layer every instance, element size, lag, order and kind of base."""
     got = sorted((r[0], r[9]) for r in ROWS.values())
     want = sorted((layer, why) for layer in LAYERS for why in WANT_ROWS[layer])
-    assert got == want and len(ROWS) == len(want) == 44 + 12 + 7 + 32
+    assert got == want and len(ROWS) == len(want) == 44 + 12 + 7 + 32 + 8 == 103
+    # the 95 rows from before the lag order keep their ids (the checksum is of the sorted ids as they stood then) and lead the
+    # table; the new ids are the lag order's alone
+    old = sorted(k for k, r in ROWS.items() if r[0] != LAG_ORDER)
+    assert len(old) == OLD_IDS and zlib.crc32("\n".join(old).encode()) == OLD_IDS_CRC and set(old) <= set(ROWS)
+    assert sorted(list(ROWS)[:OLD_IDS]) == old
+    assert sorted(set(ROWS) - set(old)) == sorted(f"lag_order_e{(1, 2, 4, 8)[t % 4]}_{why}" for t, why in enumerate(FILTER_WHYS))
+    assert all(len(x) == 3 for x in EXTRA.values())
     assert {layer: sum(r[0] == layer for r in ROWS.values()) for layer in LAYERS} == WANT_COUNT
     assert sorted(EXTRA) == sorted(k for k, r in ROWS.items() if r[0] not in FIRST_LAYERS)
     common_enc = set(PAIR.values()) | set(COOP.values()) | {SINGLE16, SINGLE32}
@@ -329,7 +346,13 @@ def test_the_table_covers_every_reason():
             assert {r[3] for r in rows if r[7] in COOP.values()} >= {BS64, 100_000, 150_000}
             assert {(r[3], r[6]) for r in rows if r[7] in PAIR.values()} == {(4096, "own"), (BS64, "tight"), (1008, "own")}
         # the lags: the eight, once each; the bases: every kind, and for constant blocks every kind at E = 1 and above
-        assert sorted(x[0] for x in extra if x[0] is not None) == (sorted(LAGS) if layer == LAG else [])
+        assert sorted(x[0] for x in extra if x[0] is not None) == (sorted(LAGS) if layer in WITH_LAG else [])
+        # the orders: 2 and 3 at every element size of the lag order, none anywhere else; all K predecessors inside a frame
+        by = {(r[2], EXTRA[k][2]) for k, r in ROWS.items() if r[0] == layer and k in EXTRA}
+        assert by == ({(E, K) for E in (1, 2, 4, 8) for K in (2, 3)} if layer == LAG_ORDER
+                      else {(r[2], None) for r in rows if layer not in FIRST_LAYERS})
+        if layer == LAG_ORDER:
+            assert len(rows) == 8 and all(3 * EXTRA[k][0] < r[3] for k, r in ROWS.items() if r[0] == layer)
         kinds = {x[1] for x in extra} - {None}
         assert kinds == ({"none", "full", "inside"} if layer == CONST else {"none", "full", "inside", "longer"} if layer in (BASE, BASE_SUB)
                          else set())
@@ -337,6 +360,7 @@ def test_the_table_covers_every_reason():
             by = {(r[2] == 1, EXTRA[k][1]) for k, r in ROWS.items() if r[0] == CONST}
             assert by == {(e1, kind) for e1 in (True, False) for kind in BASE_KINDS}
     assert set(LAGS) == {3, 2, 17, 256, 5, 64, 255, 16} and len(LAGS) == 8
+    assert ORDERS == (2, 3, 3, 2, 3, 2, 2, 3) and len(ORDERS) == len(FILTER_WHYS)
     # the seam of the buffer: stored at E = 1 reads the caller's buffer, stored at E = 4 and delta at E = 1 the copy
     a, b, c = (ROWS[k] for k in ("stored_e1_single16_by_alignment", "stored_e4_pair_by_blocks_cb32", "delta_e1_pair_by_blocks_cb32"))
     assert a[3:7] == b[3:7] == c[3:7] and a[5] == 4 and (a[7], b[7], c[7]) == (SINGLE16, PAIR[True], PAIR[True])
@@ -488,7 +512,14 @@ def audit_rows():
         rows.append(row(LAG, "test_streams_equal_oracle_on_transformed_bytes", P32, E, 4096, 13))
     rows.append(row(LAG, "test_host_pipeline_over_several_chunks", P32, 4, 4096, 645))
     rows.append(row(LAG, "test_host_pipeline_over_several_chunks", P32, 4, 4096, 64, "tight"))
-    for layer in (ZIGZAG, LAG, BASE_SUB):
+    # the lag order (tests/test_lag_order_gpu.py): the lag filter's shapes; its container and CLI test codes 13 blocks at E = 2
+    for E in (2, 4):
+        rows.append(row(LAG_ORDER, "test_streams_equal_oracle_on_transformed_bytes", P32, E, 4096, 13))
+    rows.append(row(LAG_ORDER, "test_host_pipeline_over_several_chunks", P32, 4, 4096, 644))
+    rows.append(row(LAG_ORDER, "test_host_pipeline_over_several_chunks", P32, 4, 4096, 256, "tight"))
+    rows.append(row(LAG_ORDER, "test_damaged_stream_stays_in_bounds_and_spares_other_frames", P32, 2, 4096, 13))
+    rows.append(row(LAG_ORDER, "test_container_and_cli_with_the_order", P32, 2, 4096, 13))
+    for layer in (ZIGZAG, LAG, BASE_SUB, LAG_ORDER):
         for E in (1, 2, 4, 8):
             rows.append(row(layer, "test_device_encoder_decoder_roundtrip_and_ranges", P32, E, 4096, 4 * E + 4))
     for bs, E, nb in ((4096, 2, 389), (4096, 4, 389), (BS64, 1, 70), (BS64, 2, 70)):
@@ -504,7 +535,8 @@ def test_audit_of_the_older_layer_tests():
     (and one cell decoder); nothing above 64 KiB.  The later layers the same: constant blocks add the pair kernel and
     k_encode<true, false> at 48- and 1008-byte blocks, in launches of at most 45 blocks (less than one wave's 64 table
     entries), one of 71 and one of 300 without a constant block; code_bits 32 everywhere but for two filters' 4 to 20
-    blocks at 16."""
+    blocks at 16.  The lag order: the small-grid encoder (the pair kernel in the one chunked host call) and
+    k_decode_lock<true> in every one of its tests."""
     rows = audit_rows()
     for r in rows:
         print("%-8s %-52s %-52s %-44s %s" % (r[0], r[1][:52], r[2], r[3], r[4]))
@@ -525,3 +557,5 @@ def test_audit_of_the_older_layer_tests():
     full = [r for r in later if not r[3].startswith("k_coop") and "chunked" not in r[2]]
     assert {r[0] for r in full} == {CONST, MIXED} and all(" of 48" in r[2] or " of 100" in r[2] for r in full)
     assert {r[4] for r in later if r[0] in (CONST, MIXED, LAG, BASE)} == {"k_decode_lock<true>"}
+    assert {(r[3], r[4], "chunked" in r[2]) for r in rows if r[0] == LAG_ORDER} == {
+        ("k_coop_model + k_coop_chain<true>", "k_decode_lock<true>", False), ("k_encode_pair<false, true>", "k_decode_lock<true>", True)}

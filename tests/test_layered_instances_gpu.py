@@ -1,6 +1,6 @@
 """Every layer in front of the adaptive coder on every coder instance below it (the table:
 tests/test_layered_instances_cpu.py): byte planes, the delta filter and stored blocks; constant blocks, the mixed layouts,
-and the zigzag, lag, base XOR and base folded-difference filters.
+the zigzag, lag, base XOR and base folded-difference filters, and the lag order (higher-order lagged differences).
 
 One launch per row of ROWS, through the `_dev` calls.  A case first asserts, by name, that the coder below the wrapper runs
 the encode and decode instance the row promises, for the very pointer, length and workspace of the launch.  The input is
@@ -31,6 +31,9 @@ test_stream_ranges_gpu's own cannot).
     mixed_ref(x, the table the call returned).
   * base, base_sub: x = the base with sparse changes: bit flips; small numeric steps and one across a carry per frame.  The
     base by turn absent, as long as the input, ending inside a frame at an odd byte, and once longer than the input.
+  * lag_order: test_lag_order_cpu's interleaved tones (two frames) and test_lag_cpu's walks (one), as many channels as the
+    lag where that is <= 8, against lag_order_planes_ref; asserted from the reference before any device call: the
+    transformed bytes of every frame are neither the input's nor lag_planes_ref's (the order reaches the kernel).
   * one expected byte (constant blocks: also one flag) made wrong on the reference side fails the row of every later layer
     with a message that names the block and the unit.
 Then: the host-pointer forms with CRCs in at least three chunks against the `_dev` result (constant blocks on the caller's
@@ -39,8 +42,9 @@ lag kernels (S = 3, 255, 256) at block sizes whose frames end inside a wave's tu
 byte lag inverse past 2^20 frames (more frames than workgroups: what a workgroup keeps in LDS from frame to frame); the lag
 kernels at one frame of 1025 rows; k_const_select past its grid cap; damaged streams on the table forms of k_decode_wave and
 k_decode<false, true> and under planes / delta on k_decode_cells<8>.
-Left out: damaged streams under the later layers (the decoders' table forms are covered under stored, k_const_fill's
-refusals in test_const_gpu.py, and the filters share layout_decode_tail with delta)."""
+Left out: damaged streams under the later layers but for one lag-order row on k_decode_wave with the fix-up pass (the
+decoders' table forms are covered under stored, k_const_fill's refusals in test_const_gpu.py, and the filters share
+layout_decode_tail with delta).  The lag-order kernels with several frames per wave and per workgroup: test_lag_order_gpu.py."""
 import ctypes as C
 import zlib
 
@@ -54,7 +58,8 @@ from test_base_sub_cpu import base_sub_planes_ref
 from test_const_cpu import const_ref
 from test_delta_cpu import delta_planes_ref, sorted_i32, timestamps_i64, tones_i16
 from test_lag_cpu import channels, lag_planes_ref
-from test_layered_instances_cpu import (BASE, BASE_SUB, CONST, DELTA, EXTRA, LAG, MIXED, PLANES, ROWS, STORED, WITH_BASE, ZIGZAG,
+from test_lag_order_cpu import lag_order_planes_ref, tones
+from test_layered_instances_cpu import (BASE, BASE_SUB, CONST, DELTA, EXTRA, LAG, LAG_ORDER, MIXED, PLANES, ROWS, STORED, WITH_BASE, ZIGZAG,
                                         base_len_of, coded_len, copy_bytes, input_len, layer_dec_name, layer_enc_name,
                                         layer_ws_bytes, mixed_table, reads_copy, tail_len)
 from test_mixed_cpu import mixed_ref
@@ -90,9 +95,11 @@ def _free():
     torch.cuda.empty_cache()
 
 
-def transform(layer, x, E, B, inverse=False, lag=None, base=NONE, table=None):
+def transform(layer, x, E, B, inverse=False, lag=None, base=NONE, table=None, order=None):
     """The numpy restatement of what a layer's call puts in front of the coder (inverse: behind the decoder).  base: y, the
     bytes of the base that lie under x; table: the unit table of the mixed layouts."""
+    if layer == LAG_ORDER:
+        return lag_order_planes_ref(x, E, B, lag, order, inverse=inverse)
     if layer == DELTA:
         return delta_planes_ref(x, E, B, inverse=inverse)
     if layer == ZIGZAG:
@@ -155,6 +162,10 @@ def frames_of(layer, E, B, seed, lag=None):
     if layer == LAG:                                 # interleaved channels, as many as the lag where that is <= 8
         return {f"channels{k}": np.resize(channels(lag if lag <= 8 else 8, E, seed + k).view("<u%d" % E), B).view(np.uint8).copy()
                 for k in range(3)}, {}
+    if layer == LAG_ORDER:                           # two frames of tones and one of walks, interleaved as for the lag filter
+        ch = lag if lag <= 8 else 8
+        gens = {"tones0": tones(ch, E, seed), "tones1": tones(ch, E, seed + 1), "walks": channels(ch, E, seed + 2)}
+        return {n: np.resize(v.view("<u%d" % E), B).view(np.uint8).copy() for n, v in gens.items()}, {}
     if layer in (BASE, BASE_SUB):                    # x = y with sparse changes
         xs, ys = {}, {}
         for k in range(3):
@@ -207,9 +218,9 @@ class Launch:
     (name, variant) pair: the variant is how the base lies under the frame ("cov": all of it, "cut": the base ends inside,
     "unc": not at all, and so for every layer without a base) or, for the mixed layouts, the frame's (= unit's) layout."""
 
-    def __init__(self, layer, params, E, B, nb, seed, ragged="C", slot=None, lag=None, base=None, table=None, oracle=True):
+    def __init__(self, layer, params, E, B, nb, seed, ragged="C", slot=None, lag=None, base=None, table=None, oracle=True, order=None):
         import torch
-        self.layer, self.params, self.E, self.B, self.nb, self.lag = layer, params, E, B, nb, lag
+        self.layer, self.params, self.E, self.B, self.nb, self.lag, self.order = layer, params, E, B, nb, lag, order
         self.in_len = input_len(params, B, nb)
         F = E * B
         frames, y_frames = frames_of(layer, E, B, seed, lag)
@@ -293,7 +304,8 @@ class Launch:
         return self.frames[name] ^ pad(y, F), y
 
     def transformed(self, x, y, variant):
-        return transform(self.layer, x, self.E, self.B, lag=self.lag, base=y, table=[variant] if self.layer == MIXED else None)
+        return transform(self.layer, x, self.E, self.B, lag=self.lag, base=y, table=[variant] if self.layer == MIXED else None,
+                         order=self.order)
 
     def device_input(self, off):
         """(whole tensor, the input `off` bytes off a 16-byte boundary, its start in the tensor)"""
@@ -360,7 +372,7 @@ def _dev_fn(direction, layer):
     return getattr(_lib().lib(), f"redux_{direction}_{layer}_dev")
 
 
-def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, base_len=0, d_table=None, mask=0):
+def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, base_len=0, d_table=None, mask=0, order=None):
     """The layer's encode call between guard bands -> (out, offsets, statuses, summary, flags)"""
     import torch
     L = _lib()
@@ -386,6 +398,8 @@ def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, bas
         rc = fn(*x, B, mask, _v(d_table), *dst, *end)
     elif layer == LAG:
         rc = fn(*x, B, E, lag, *dst, *end)
+    elif layer == LAG_ORDER:
+        rc = fn(*x, B, E, lag, order, *dst, *end)
     elif layer in (BASE, BASE_SUB):
         rc = fn(*x, *y, B, E, *dst, *end)
     else:
@@ -396,7 +410,8 @@ def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, bas
     return out, offs, status, summ, flags
 
 
-def decode_dev(layer, params, E, B, d_streams, d_offs, d_flags, out_len, off=0, lag=None, d_base=None, base_len=0, d_table=None):
+def decode_dev(layer, params, E, B, d_streams, d_offs, d_flags, out_len, off=0, lag=None, d_base=None, base_len=0, d_table=None,
+               order=None):
     import torch
     L = _lib()
     lib, cp = L.lib(), L.Params(*params)
@@ -420,6 +435,8 @@ def decode_dev(layer, params, E, B, d_streams, d_offs, d_flags, out_len, off=0, 
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), _v(d_table), out_len, B, _v(out), *tail)
     elif layer == LAG:
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), out_len, B, E, lag, _v(out), *tail)
+    elif layer == LAG_ORDER:
+        rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), out_len, B, E, lag, order, _v(out), *tail)
     elif layer in (BASE, BASE_SUB):
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), *y, out_len, B, E, _v(out), *tail)
     else:
@@ -493,6 +510,19 @@ def const_launch_is_what_the_row_is_for(X, base):
         assert not under & {u for k, u in zip(X.keys, X.unit[::E]) if k[1] in ("cut", "unc")}
 
 
+def order_reaches_the_kernel(X):
+    """The lag order, from the reference alone: the transformed bytes of every distinct frame and of the ragged one are neither
+    the input's nor the lag filter's of it (order 1), so a call that dropped the order, or the filter, fails its row."""
+    E, B = X.E, X.B
+    assert X.order in (2, 3) and 3 * X.lag < B
+    xs = [X.x_of[src] for src in X.sources] + [X.last]
+    ts = [np.concatenate(X.t_blocks[k * E: (k + 1) * E]) for k in range(len(X.sources))] + [np.concatenate(X.t_blocks[len(X.sources) * E:])]
+    for x, t in zip(xs, ts):
+        assert len(t) == len(x) and not np.array_equal(t, x) and not np.array_equal(t, lag_planes_ref(x, E, B, X.lag))
+        if E > 1:
+            assert not np.array_equal(t, planes_ref(x, E, B))
+
+
 def layer_is_no_identity(X):
     return any(not np.array_equal(X.t_blocks[k * X.E], X.x_of[src][: X.B]) for k, src in enumerate(X.sources))
 
@@ -520,8 +550,8 @@ def spoil_reference(X, what):
 def run_row(key, ragged, spoil=None, mask=0):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base = EXTRA.get(key, (None, None))
-    X = Launch(layer, params, E, B, nb, _seed(key), ragged, lag=lag, base=base, oracle=not mask)
+    lag, base, order = EXTRA.get(key, (None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), ragged, lag=lag, base=base, oracle=not mask, order=order)
     in_len = X.in_len
     big_in, d_in, lo_in = X.device_input(off)
     assert d_in.data_ptr() % 16 == off
@@ -544,6 +574,8 @@ def run_row(key, ragged, spoil=None, mask=0):
         flag_pattern_holds(X, ragged)
     if layer == CONST:
         const_launch_is_what_the_row_is_for(X, base)
+    if layer == LAG_ORDER:
+        order_reaches_the_kernel(X)
     # the layer matters: the transformed bytes are not the input's (a base filter without a base at E = 1 still copies)
     assert layer_is_no_identity(X) or layer in FLAGGED or (layer in (BASE, BASE_SUB) and base == "none" and E == 1)
     if spoil:
@@ -556,7 +588,7 @@ def run_row(key, ragged, spoil=None, mask=0):
         assert L.lib().redux_encode_kernel_name_ws(C.byref(cp), x_ptr, coded_len(layer, B, in_len), B, wsb - front).decode() == enc
         assert layer_enc_name(layer, params, E, B, nb, off, ws, base=base) == enc
         if not mask:
-            out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, in_len, ws, lag, d_y, X.base_len, d_table)
+            out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, in_len, ws, lag, d_y, X.base_len, d_table, order=order)
         assert guards_intact(big_in, lo_in, in_len) and guards_intact(big_y, lo_y, X.base_len)
         assert summ.tolist() == [0, 0] and not bool(status.any())
         if layer in FLAGGED:
@@ -574,7 +606,7 @@ def run_row(key, ragged, spoil=None, mask=0):
     else:
         out, offs, flags = assemble(X, X.payload, X.flag)
     d_out, sizes, dstatus, dsum = decode_dev(layer, params, E, B, out, offs, flags if layer in FLAGGED else None, in_len, off, lag, d_y,
-                                             X.base_len, d_table)
+                                             X.base_len, d_table, order=order)
     assert dsum.tolist() == [0, 0] and not bool(dstatus.any())
     assert torch.equal(sizes.to(torch.int64), torch.from_numpy(X.block_lengths()).cuda())
     if not torch.equal(d_out, d_in):
@@ -598,7 +630,7 @@ def test_mixed_layouts_chosen_on_the_device(rx):
 
 SPOILED = [("const_e8_pair_below_coop_min", "flag"), ("const_e8_pair_below_coop_min", "byte"), ("mixed_pair_by_blocks_cb32", "byte"),
            ("zigzag_e8_pair_below_coop_min", "byte"), ("lag_e8_pair_below_coop_min", "byte"), ("base_e8_pair_below_coop_min", "byte"),
-           ("base_sub_e8_pair_below_coop_min", "byte")]
+           ("base_sub_e8_pair_below_coop_min", "byte"), ("lag_order_e8_pair_below_coop_min", "byte")]
 
 
 @pytest.mark.parametrize("key,what", SPOILED)
@@ -633,24 +665,26 @@ HOST_KEYS = ["planes_e2_coop_whole_cb32", "delta_e1_pair_by_blocks_cb32", "store
              # the later layers: constant blocks at E = 1 on the caller's buffer, and with a base that ends inside a chunk
              "const_e1_single16_by_alignment", "const_e2_pair_by_blocks_cb16", "mixed_pair_by_blocks_cb32",
              "zigzag_e4_pair_by_blocks_cb32", "lag_e4_pair_by_blocks_cb32", "base_e4_pair_by_blocks_cb32",
-             "base_sub_e2_single32_by_workspace"]
+             "base_sub_e2_single32_by_workspace", "lag_order_e4_pair_by_blocks_cb32"]
 
 
 @pytest.mark.parametrize("key", HOST_KEYS)
 def test_host_pointer_forms_with_crc_equal_the_dev_calls(rx, key):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base = EXTRA.get(key, (None, None))
-    X = Launch(layer, params, E, B, nb, _seed(key), "S", lag=lag, base=base)
+    lag, base, order = EXTRA.get(key, (None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), "S", lag=lag, base=base, order=order)
     big_in, d_in, lo_in = X.device_input(off)
     big_y, d_y, lo_y = X.device_base()
     d_table = torch.from_numpy(X.table).cuda() if layer == MIXED else None
-    out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, X.in_len, ws, lag, d_y, X.base_len, d_table)
+    out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, X.in_len, ws, lag, d_y, X.base_len, d_table, order=order)
     x = d_in.cpu().numpy()
     total = int(offs[-1])
     kw = {"unit_layouts": X.table} if layer == MIXED else {"element_size": E}
     if layer in (DELTA, ZIGZAG, LAG):
         kw["filter"] = layer
+    if layer == LAG_ORDER:
+        kw.update(filter="lag", lag=lag, order=order)
     if layer == LAG:
         kw["lag"] = lag
     if X.base_len:
@@ -873,7 +907,8 @@ def test_const_select_past_its_grid_cap(rx):
 
 
 # ---- 5. damaged streams on the new decode paths ---------------------------------------------------------------------------------
-DAMAGED_KEYS = ["stored_e1_coop_windows_100k", "stored_e4_table_generic32", "planes_e8_cells8", "delta_e2_cells8"]
+DAMAGED_KEYS = ["stored_e1_coop_windows_100k", "stored_e4_table_generic32", "planes_e8_cells8", "delta_e2_cells8",
+                "lag_order_e2_coop_windows_150k"]       # (k_decode_wave and the fix-up pass in front of the K-level inverse)
 
 
 @pytest.mark.parametrize("key", DAMAGED_KEYS)
@@ -884,7 +919,8 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
     assert layer_dec_name(layer, params, B, nb) == dec
-    X = Launch(layer, params, E, B, nb, _seed(key), "C")
+    lag, _, order = EXTRA.get(key, (None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), "C", lag=lag, order=order)
     rng = np.random.default_rng(_seed(key) + 1)
     coded = [b for b in range(nb - 1) if not X.flag[X.unit[b]]]
     picks = [coded[i] for i in (3, len(coded) // 5, len(coded) // 3, len(coded) // 2, len(coded) - 70, len(coded) - 2)]
@@ -910,7 +946,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     X.unit, X.d_unit = unit, torch.from_numpy(unit).cuda()
     flat, offs, flags = assemble(X, payload, flag)
     big_in, d_in, lo_in = X.device_input(0)
-    d_out, sizes, status, dsum = decode_dev(layer, params, E, B, flat, offs, flags, X.in_len, off)
+    d_out, sizes, status, dsum = decode_dev(layer, params, E, B, flat, offs, flags, X.in_len, off, lag, order=order)
     got_st, got_sz = status.cpu().numpy(), sizes.cpu().numpy()
     bad = np.nonzero((got_st != want_st) | (got_sz != want_sz))[0]
     assert not len(bad), (int(bad[0]), int(got_st[bad[0]]), int(got_sz[bad[0]]), int(want_st[bad[0]]), int(want_sz[bad[0]]))
@@ -929,7 +965,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     # inverse of the restated transform with d in place.  (E = 1 without a filter: the block's first len(d) bytes are d.)
     checked = 0
     for f in sorted({b // E for b in picks if b // E < len(X.plan)}):
-        t = transform(layer, X.frames[X.plan[f]], E, B).copy()
+        t = transform(layer, X.frames[X.plan[f]], E, B, lag=lag, order=order).copy()
         m = B
         for b in picks:
             if b // E == f:
@@ -937,7 +973,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
                 j = b % E
                 t[j * B: j * B + len(d)] = d
                 m = min(m, len(d))
-        want = transform(layer, t, E, B, inverse=True)[: m * E]
+        want = transform(layer, t, E, B, inverse=True, lag=lag, order=order)[: m * E]
         got = d_out[f * F: f * F + m * E].cpu().numpy()
         if not np.array_equal(got, want):
             at = int(np.nonzero(got != want)[0][0])

@@ -117,8 +117,12 @@ KINDS = {
     "v8": dict(E=2, element_size=2, base=True), "v9": dict(E=4, element_size=4, skip_constant=True),
     "v9base": dict(E=2, element_size=2, skip_constant=True, base=True), "v10": dict(E=1, layout="mixed", element_size=None),
     "0x41": dict(E=1, stored=True), "0x42": dict(E=2, element_size=2, stored=True),
+    # the frame-local prefix-sum filters that came after the sweep: zigzag, the folded difference against a base, lag, lag order
+    "v11": dict(E=2, element_size=2, filter="zigzag"), "v12": dict(E=4, element_size=4, base=True, base_op="sub"),
+    "v13": dict(E=2, element_size=2, filter="lag", lag=3), "v14": dict(E=8, element_size=8, filter="lag", lag=2, order=3),
 }
 ALL_KINDS = list(KINDS) + [k + "+crc" for k in KINDS]  # (0x41 + 0x10 = 0x51, ...)
+VERSION_BYTE = {"v11": 11, "v12": 12, "v13": 13, "v14": 14}  # (+crc: 0x1B, 0x1C, 0x1D, 0x1E)
 
 
 @functools.lru_cache(maxsize=None)
@@ -159,6 +163,8 @@ def test_every_container_kind_reads_by_range(rx, kind):
     blob, data, base, F, bs = made(kind)
     total = len(data)
     assert blob[4] & 0x10 == (0x10 if kind.endswith("+crc") else 0) and blob[4] & 0x40 == (0x40 if kind.startswith("0x4") else 0)
+    if kind.replace("+crc", "") in VERSION_BYTE:
+        assert blob[4] == VERSION_BYTE[kind.replace("+crc", "")] + (0x10 if kind.endswith("+crc") else 0)
     r = container.Reader(blob, base)
     assert (r.total, r.block_size, r.granule_blocks * bs) == (total, bs, F)
     ranges = the_ranges(total, F)
@@ -178,7 +184,7 @@ def test_every_container_kind_reads_by_range(rx, kind):
     assert container.decompress_range(blob, F - 1, 2, base=base) == data[F - 1: F + 1]
 
 
-@pytest.mark.parametrize("kind", ["v1+crc", "v2+crc", "v9base+crc", "v10+crc"])
+@pytest.mark.parametrize("kind", ["v1+crc", "v2+crc", "v9base+crc", "v10+crc", "v12+crc", "v14+crc"])
 def test_damage_matters_only_where_a_range_reads(rx, kind):
     from redux_amd import container
     blob, data, base, F, bs = made(kind)
@@ -202,7 +208,11 @@ def test_damage_matters_only_where_a_range_reads(rx, kind):
 # ---- streams resident in device memory ---------------------------------------------------------------------------------------
 MODES = {"plain": dict(E=1), "planes": dict(E=4, element_size=4), "delta": dict(E=8, element_size=8, filter="delta"),
          "base": dict(E=2, element_size=2, base=True), "constant": dict(E=2, element_size=2, constant=True),
-         "constant+base": dict(E=4, element_size=4, constant=True, base=True), "mixed": dict(E=1, mixed=True)}
+         "constant+base": dict(E=4, element_size=4, constant=True, base=True), "mixed": dict(E=1, mixed=True),
+         # the gathered virtual input (covered granules concatenated, a short last frame, the gathered prefix of a base that
+         # ends 100 bytes into a frame) behind the frame-local prefix-sum filters
+         "zigzag": dict(E=1, filter="zigzag"), "base_sub": dict(E=8, element_size=8, base=True, base_op="sub"),
+         "lag": dict(E=4, element_size=4, filter="lag", lag=5), "lag_order": dict(E=2, element_size=2, filter="lag", lag=3, order=2)}
 
 
 @pytest.mark.parametrize("mode", list(MODES))
