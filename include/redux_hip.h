@@ -1110,6 +1110,43 @@ int         redux_lag_cost_dev(const redux_params *p, const void *d_in, uint64_t
 const char *redux_lag_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size);
 const char *redux_lag_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size);
 
+/* ---- order estimates -------------------------------------------------------------------------------------
+ * The lag estimates above for higher-order lagged differences ("higher-order lagged differences" above): the adaptive cost A
+ * of every block of the input behind the lag filter at order K, for a list of (lag, order) candidates in one call, so that
+ * the order -- which pays on band-limited signals and costs bytes on random walks -- can be counted instead of guessed or
+ * found by coding the input three times.  Nothing about the filter is new: bits[c][b] is what redux_block_cost_dev gives for
+ * block b of what redux_lag_order_planes_dev writes for (element_size, block_size, lags[c], orders[c]) -- the fresh start of
+ * every frame, terms before the frame zero, the fold, the short last frame and its trailing bytes included -- counted from
+ * the untransformed bytes: no transformed copy and no workspace.  A candidate of order 1 gives redux_lag_cost_dev's row for
+ * its lag.  Frame sampling (frame_step) and the compact rows are those of the lag estimates, and so is the row length,
+ * redux_lag_cost_block_count.
+ *
+ * redux_lag_order_cost_dev             d_bits is f64[ncand][redux_lag_cost_block_count(...)] on the device.  lags, orders:
+ *                                      ncand values each on the HOST, consumed before the call returns (they travel in the
+ *                                      kernels' arguments); repeated candidates are legal, rows are independent.  The four
+ *                                      waves of a workgroup take four consecutive candidates and move at the pace of the
+ *                                      highest order among them: a list ordered by order first is the fastest (any order is
+ *                                      right).
+ *                                      Full frames go to k_lag_order_cost when block_size and d_in are multiples of 16,
+ *                                      everything else (the short last frame included) to k_lag_order_cost_bytes, which is
+ *                                      right for any alignment and block size but slow.  INVALID_INPUT where
+ *                                      redux_lag_cost_dev returns it, for ncand == 0 or above REDUX_LAG_ORDER_COST_MAX, a
+ *                                      null orders, or a pair redux_lag_order_check refuses; UNSUPPORTED as
+ *                                      redux_block_cost_dev.  in_len == 0: one empty block per row.  Stream-ordered, no
+ *                                      workspace, no host synchronisation.
+ * redux_lag_order_cost_kernel_name     the kernels such a call with frame_step 1 runs on a 16-byte aligned d_in:
+ *                                      "k_lag_order_cost<E>", "k_lag_order_cost_bytes<E>", or both joined by " + " when
+ *                                      full frames are followed by a short one.  "" for a block_size or element size out of
+ *                                      range.
+ * redux_lag_order_cost_kernel_name_at  the same for this d_in, which contributes its alignment only. */
+#define REDUX_LAG_ORDER_COST_MAX 256   /* candidates of one call */
+int         redux_lag_order_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                     uint32_t element_size, const uint32_t *lags /* host, ncand */,
+                                     const uint32_t *orders /* host, ncand */, uint32_t ncand, uint32_t frame_step,
+                                     void *d_bits /* f64[ncand][block_count] */, void *stream);
+const char *redux_lag_order_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size);
+const char *redux_lag_order_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+
 /* ---- mixed layouts --------------------------------------------------------------------------------------
  * One layout per UNIT of the input instead of one per input, for files that hold several element types (bf16 weights next to
  * fp32 state, int64 indices and text): the eight layouts of "layout estimates" above, chosen for every unit on its own.

@@ -17,5 +17,6 @@ from .api import (  # noqa: F401
     LAYOUTS, layout_index, layout_cost, estimate_layouts, BASE_OPS, estimate_base_ops,
     mixed_units, choose_unit_layouts, mixed_layout,
     lag_cost, estimate_lags, choose_lag,
+    lag_order_cost, estimate_lag_orders, choose_lag_order,
     range_plan, segment_copy, segment_tiles, SEGMENT_DTYPE,
 )

@@ -151,6 +151,10 @@ SIGNATURES = {
     "redux_lag_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _U32, _U32, _V, _V]),
     "redux_lag_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
     "redux_lag_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
+    # order estimates: the lag estimates for (lag, order) candidates
+    "redux_lag_order_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V, _U32, _U32, _V, _V]),
+    "redux_lag_order_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
+    "redux_lag_order_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
     # mixed layouts: a layout per unit of 8 blocks
     "redux_mixed_unit_count": (_U64, [_U64, _U32]),
     "redux_mixed_choose_dev": (C.c_int, [_V, _U64, _U32, _V, _V, _V]),

@@ -2415,6 +2415,128 @@ def choose_lag(data, element_size, block_size, params=(8, 30, 32), estimate=None
     return best_lag(est), est
 
 
+# ---- order estimates (include/redux_hip.h, "order estimates") --------------------------------------
+LAG_ORDER_COST_MAX = 256  # REDUX_LAG_ORDER_COST_MAX: the candidates of one call
+
+
+def _candidate_list(candidates):
+    """1 to LAG_ORDER_COST_MAX (S, K) pairs of ints, S in 1 .. LAG_MAX, K in 1 .. LAG_ORDER_MAX, repeats allowed
+    -> list of (int, int)"""
+    try:
+        cands = [tuple(c) for c in candidates]
+    except TypeError:
+        raise InvalidInput()
+    if not 1 <= len(cands) <= LAG_ORDER_COST_MAX:
+        raise InvalidInput()
+    for c in cands:
+        if len(c) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in c) \
+                or not 1 <= c[0] <= LAG_MAX or not 1 <= c[1] <= LAG_ORDER_MAX:
+            raise InvalidInput()
+    return [(int(S), int(K)) for S, K in cands]
+
+
+def _lag_order_cost_args(element_size, block_size, candidates, frame_step):
+    """the argument checks of the order estimates, on the arguments alone -> (E, B, candidate list, T)"""
+    E, B, _, T = _lag_cost_args(element_size, block_size, None, frame_step)
+    return E, B, _candidate_list(candidates), T
+
+
+def _device_lag_order_cost(torch, L, cp, d, E, B, cands, T):
+    """-> float64 device tensor [len(cands), redux_lag_cost_block_count]; both lists are consumed by the call"""
+    n = d.numel()
+    d_bits = torch.empty((len(cands), L.redux_lag_cost_block_count(n, B, E, T)), dtype=torch.float64, device=d.device)
+    h_lags = np.asarray([S for S, _ in cands], dtype=np.uint32)
+    h_orders = np.asarray([K for _, K in cands], dtype=np.uint32)
+    _raise(L.redux_lag_order_cost_dev(C.byref(cp), C.c_void_p(d.data_ptr()) if n else None, n, B, E, h_lags.ctypes.data,
+                                      h_orders.ctypes.data, len(cands), T, C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits
+
+
+def lag_order_cost(data, element_size, candidates, block_size=65536, params=(8, 30, 32), frame_step=1):
+    """The adaptive model's ideal code length in bits, EOF included, of every block of `data` behind the lag filter at a
+    higher order (filter="lag", lag=S, order=K) for each (S, K) of `candidates` (1 to 256 pairs, S in 1 .. LAG_MAX, K in 1 ..
+    LAG_ORDER_MAX, repeats allowed), counted from the bytes as they are, with no transformed copy (redux_lag_order_cost_dev:
+    k_lag_order_cost on torch's current stream, one read-back) -> np.float64[len(candidates), block_count]: row c is
+    block_cost(lag_order_planes(data, element_size, block_size, S, K)), and lag_cost's row of S for K = 1.  Four consecutive
+    candidates are counted side by side at the pace of the highest order among them: a list ordered by order first is the
+    fastest.  frame_step as for lag_cost.
+    A uint8 device tensor is read where it lies; host data is uploaded once."""
+    E, B, cands, T = _lag_order_cost_args(element_size, block_size, candidates, frame_step)  # (before the library is touched)
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _device_lag_order_cost(torch, _lib.lib(), P._c(), d, E, B, cands, T).cpu().numpy()
+
+
+def _lag_order_estimates(torch, L, cp, d, E, B, cands, T):
+    bits = _device_lag_order_cost(torch, L, cp, d, E, B, cands, T)
+    sums, nb = bits.sum(dim=1).cpu().numpy(), bits.shape[1]
+    out = {}
+    for j, c in enumerate(cands):
+        out.setdefault(c, int(np.ceil(float(sums[j]) / 8 + TERMINATION_BYTES * nb)))
+    return out
+
+
+def estimate_lag_orders(data, element_size, block_size, candidates, params=(8, 30, 32), frame_step=1):
+    """-> {(S, K): estimated payload bytes}: what the streams of compress_blocks(..., element_size=, filter="lag", lag=S,
+    order=K) would add up to for each pair of `candidates`, without transforming or coding anything: one lag_order_cost call,
+    then ceil(sum bits / 8 + TERMINATION_BYTES * blocks) as estimate_lags, over the blocks of the selected frames (frame_step
+    1: all of them; a repeated candidate keeps its first row)."""
+    E, B, cands, T = _lag_order_cost_args(element_size, block_size, candidates, frame_step)  # (before the library is touched)
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _lag_order_estimates(torch, _lib.lib(), P._c(), d, E, B, cands, T)
+
+
+def lag_order_candidates(lags):
+    """the candidates of choose_lag_order's exact pass: every order of every lag, by order first (the four waves of a
+    workgroup take consecutive candidates and move at the pace of the highest order among them)"""
+    return [(S, K) for K in range(1, LAG_ORDER_MAX + 1) for S in lags]
+
+
+def best_lag_order(estimates):
+    """The (S, K) with the smallest estimate; ties go to the smaller K, then to the smaller S."""
+    return min(estimates, key=lambda c: (estimates[c], c[1], c[0]))
+
+
+def choose_lag_order(data, element_size, block_size, lag=None, params=(8, 30, 32), estimate=None):
+    """-> ((S, K), {(S, K): estimated payload bytes}): the lag and the order of the lag filter with the smallest
+    estimate_lag_orders, counted on the GPU and never guessed.  With a lag S: one exact pass over (S, 1), (S, 2), (S, 3).
+    With lag None: choose_lag's first stage as it stands -- the order-1 estimates of all 256 lags, on about LAG_SAMPLE_FRAMES
+    frames of a longer input -- then lag_finalists (the LAG_FINALISTS smallest and S = 1), then one exact pass over every
+    order of every finalist, at most 12 candidates, by order first.  Ties go to the smaller K, then to the smaller S; there is no hysteresis.
+    (S, 1) of every finalist is among the candidates, so the chosen estimate is never above what choose_lag estimates for
+    its choice, nor above the zigzag filter's.  The dict holds the estimates of the exact pass.  estimate: the rule alone,
+    for a caller with costs of its own: a function (candidates or None, frame_step) in place of the device, which returns
+    {S: bytes} at order 1 for None (all 256 lags) and {(S, K): bytes} for a list of pairs."""
+    E, B, _, _ = _lag_cost_args(element_size, block_size, None, 1)  # (before the library is touched)
+    if lag is not None and (isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= LAG_MAX):
+        raise InvalidInput()
+    if estimate is None:
+        P = _params_of(params)
+        torch = _torch()
+        d = _device_u8(torch, data)
+        L, cp = _lib.lib(), P._c()
+        nbytes = d.numel()
+
+        def estimate(cands, T):
+            with torch.cuda.device(d.device):
+                if cands is None:
+                    return _lag_estimates(torch, L, cp, d, E, B, _lag_list(None), T)
+                return _lag_order_estimates(torch, L, cp, d, E, B, _candidate_list(cands), T)
+    else:
+        nbytes = len(data)
+    if lag is None:
+        lags = lag_finalists(estimate(None, lag_frame_step(max(1, -(-nbytes // (E * B))))))
+    else:
+        lags = [int(lag)]
+    est = estimate(lag_order_candidates(lags), 1)
+    return best_lag_order(est), est
+
+
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------
 def gen_iid(nbytes, seed=0x5EED0001, first_byte=0, device="cuda:0", out=None):
     torch = _torch()

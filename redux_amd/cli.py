@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--order-auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -78,6 +78,14 @@ so the order stays opt-in and nothing chooses it for you.  No recorded signal wa
 data.  `--order 1` is `--filter lag --lag S` itself and writes version 13, byte for byte.  -d and -d `--range` read version
 14 with no flag.  `--order` without `--filter lag`, a K that is not the decimal 1, 2 or 3, and `--order 2` or `3` with
 `--lag auto` (the lag estimates count order 1 only) are usage errors.
+`--order-auto` (with -c and `--filter lag --lag S` or `--lag auto`; a flag without a value) counts the order too: the payload
+behind orders 1, 2 and 3 is estimated on the GPU, from the input as it stands and without transforming or coding it
+(redux_amd/api.py: choose_lag_order) -- at lag S, or with `--lag auto` at each of that choice's finalists, at
+most 12 candidates in one exact pass -- and the smallest codes the data, ties to the smaller order, then to the smaller lag.
+Order 1 is always among the candidates, so the choice is never estimated above `--filter lag --lag S|auto` alone.  The output
+is that choice's ordinary container, version 13 for order 1 and version 14 above: nothing new for -d.  The figures behind it
+rest on generated data as well.  `--order-auto` together with `--order`, without `--filter lag --lag ...`, with -d, or with
+anything `--order 2` is refused with is a usage error.
 `--base FILE` (with -c, a block size and any `--element-size`, adaptive model; `--checksum` is allowed) codes the bytewise
 XOR of the input against FILE, an earlier snapshot of the same tensors -- the previous checkpoint, the base model of a
 fine-tune -- in the byte-plane layout (container version 8, which records how many bytes of the base were used and their
@@ -126,7 +134,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--order-auto] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -144,6 +152,10 @@ def parse(argv):
             opts["compress"] = False
         elif arg == "--skip-constant":
             opts["skip_constant"] = True
+        elif arg == "--order-auto":
+            if "order" in opts:
+                return None  # the order is given or counted, not both
+            opts["order"] = "auto"
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range",
                      "--base-op", "--lag", "--order"):
             val = next(it, None)
@@ -173,7 +185,7 @@ def parse(argv):
                 else:
                     opts["lag"] = int(val)
             elif arg == "--order":
-                if val not in ("1", "2", "3"):
+                if val not in ("1", "2", "3") or "order" in opts and opts["order"] == "auto":
                     return None
                 opts["order"] = int(val)
             elif arg == "--base":
@@ -228,7 +240,10 @@ def parse(argv):
         return None  # the filter is recorded in the container, and it sits in front of the adaptive coder only
     if ("lag" in opts) != (opts.get("filter") == "lag"):
         return None  # the lag is the lag filter's, and that filter has no default for it (`--lag auto` asks for the count)
-    if "order" in opts and (opts.get("filter") != "lag" or (opts["order"] > 1 and opts.get("lag") == "auto")):
+    if opts.get("order") == "auto":
+        if opts.get("filter") != "lag" or not opts["compress"]:
+            return None  # the counted order is the lag filter's, and it is counted where the data is coded
+    elif "order" in opts and (opts.get("filter") != "lag" or (opts["order"] > 1 and opts.get("lag") == "auto")):
         return None  # the order is the lag filter's, and the lag estimates count order 1 only
     if "base" in opts and opts["compress"] and (opts["block_size"] == 0 or opts.get("stored") or "filter" in opts
                                                or opts.get("model", "adaptive") != "adaptive"):

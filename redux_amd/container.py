@@ -694,6 +694,19 @@ def estimate_lag_bytes(data, element_size, block_size=65536, lags=None, params=(
     return {S: payload[S] + over for S in payload}
 
 
+def estimate_lag_order_bytes(data, element_size, block_size=65536, candidates=((1, 1), (1, 2), (1, 3)), params=(8, 30, 32), checksum=False,
+                             frame_step=1):
+    """-> {(S, K): estimated container bytes} for the adaptive model behind the lag filter at lag S and order K, for each pair
+    of `candidates`: api.estimate_lag_orders' estimate of the payloads (counted from the bytes as they are on the GPU; nothing
+    is transformed or coded) plus overhead_bytes(..., filter="lag"), which is exact for every order: version 13 (K = 1) and
+    version 14 (K = 2, 3) record lag and order in the header's reserved word and have the same sections, so their overhead is
+    the same size.  Directly comparable with estimate_lag_bytes and estimate_layout_bytes.  frame_step above 1 estimates the
+    selected frames' payload only, under the whole container's overhead."""
+    payload = api.estimate_lag_orders(data, element_size, block_size, candidates, params, frame_step)
+    over = overhead_bytes("adaptive", max(1, -(-len(data) // block_size)), element_size, checksum=checksum, filter="lag")
+    return {c: payload[c] + over for c in payload}
+
+
 def choose_layout(estimates):
     """The (element_size, filter) with the smallest estimate; ties go to the earlier of LAYOUT_ORDER."""
     return min(estimates, key=lambda k: (estimates[k], LAYOUT_ORDER.index(k)))
@@ -726,7 +739,11 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     decode.  The filter itself stays opt-in.
     order K, 1 .. 3 (with filter "lag" only): the lag-S difference applied K times, for sampled signals that are locally
     polynomial; version 14 for K = 2 or 3, which records K, and version 13, byte for byte, for K = 1.  On random walks a
-    higher order costs bytes, so nothing chooses it.  Not with lag "auto" above order 1: the lag estimates count order 1 only.
+    higher order costs bytes, so nothing chooses it unasked.  Not with lag "auto" above order 1: the lag estimates count order 1
+    only.  order "auto" (with filter "lag" and a lag S or "auto"; here only, not in the block calls or the device coders): the
+    order is counted too (api.choose_lag_order: one exact pass over orders 1, 2, 3 at lag S, or over the orders of every
+    finalist of lag "auto"; ties go to the smaller order, then to the smaller lag), and the container is that choice's ordinary
+    one, version 13 for order 1 and version 14 above: nothing new to decode.  Refused with everything order 2 is refused with.
     model "context-static" (element_size 1, not stored, no filter): a static table per preceding byte, built from the data
     (api.context_static_tables, default total), version 7.  It pays from about half a megabyte of text upward, and
     only model "auto" picks it for the caller.
@@ -753,8 +770,11 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     auto_lag = isinstance(lag, str) and lag == "auto"  # (the choice is made below, once nothing else refuses the call)
     if auto_lag:
         lag = 1
+    auto_order = isinstance(order, str) and order == "auto"  # (the same: until then it is refused where order 2 is)
+    if auto_order:
+        order = 2
     if lag is not None or order is not None or (isinstance(filter, str) and filter == "lag"):  # (a lag, its order and their filter go together)
-        if api._resolve_front(None, filter=filter, lag=lag, order=order).front.order and auto_lag:
+        if api._resolve_front(None, filter=filter, lag=lag, order=order).front.order and auto_lag and not auto_order:
             raise api.InvalidInput()  # (choose_lag counts order-1 costs only)
     if layout is not None:
         if layout not in ("auto", "mixed") or model != "adaptive" or stored or segment_blocks is not None or filter is not None \
@@ -782,7 +802,9 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
             or (model == "plane-static" and (element_size == 1 or stored)) or (model == "segment-static" and stored) \
             or (model != "segment-static" and segment_blocks is not None):
         raise api.InvalidInput()
-    if auto_lag:
+    if auto_order:
+        lag, order = api.choose_lag_order(data, element_size, block_size, None if auto_lag else lag, params)[0]
+    elif auto_lag:
         lag = api.choose_lag(data, element_size, block_size, params)[0]
     nb = max(1, -(-len(data) // block_size))
     crc = np.zeros(nb, dtype=np.uint32) if checksum else None

@@ -27,6 +27,7 @@
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 //   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
 //   redux_lag_cost.hpp  k_lag_cost: the adaptive cost of every block behind the lagged delta filter, for a list of lags
+//   redux_lag_order_cost.hpp  k_lag_order_cost: the same behind higher-order lagged differences, for (lag, order) candidates
 //   redux_mixed.hpp    k_mixed_choose / k_mixed_planes: a layout per unit of 8 blocks, chosen from those costs on the device
 //   redux_range.hpp    k_segment_copy: range reads, the plan of the covered granules and the segmented byte copy
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
@@ -63,6 +64,8 @@
 #include "redux_cost.hpp"
 #include "redux_layout_cost.hpp"
 #include "redux_lag_cost.hpp"
+#include "redux_lag_order_cost.hpp"
+#include "redux_lag_order_cost_list.hpp"
 #include "redux_mixed.hpp"
 #include "redux_range.hpp"
 
@@ -1005,6 +1008,36 @@ static int launch_lag_cost(const void *d_in, uint64_t in_len, uint32_t block_siz
     if (nrest) { // a selected short last frame, or everything the fast kernel cannot take
         const uint64_t work = nrest * nlags, cap = (uint64_t)kHistWgsPerCu * cu_count();
         k_lag_cost_bytes<E><<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    return REDUX_OK;
+}
+
+// ---- order estimates (redux_lag_order_cost.hpp) -------------------------------------------------------------------------
+// (a.lags and a.orders are filled by the caller: redux_lag_order_cost_dev)
+template <int E>
+static int launch_lag_order_cost(LagOrderCostArgs &a, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t ncand,
+                                 uint32_t frame_step, double *bits, hipStream_t s)
+{
+    a.in         = (const uint8_t *)d_in;
+    a.in_len     = in_len;
+    a.nblocks    = redux_block_count(in_len, block_size);
+    a.bits       = bits;
+    a.block_size = block_size;
+    a.frame_step = frame_step;
+    a.ncand      = ncand;
+    lag_cost_selected(a.nblocks, E, frame_step, &a.row_blocks);
+    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
+    a.nsel_fast  = (nfull + frame_step - 1) / frame_step;
+    if (a.nsel_fast) { // one workgroup of four waves per CU: 160 KiB of LDS
+        const uint64_t jobs = a.nsel_fast * ((ncand + kLagCostWaves - 1) / kLagCostWaves), cap = cu_count();
+        k_lag_order_cost<E><<<(uint32_t)(jobs < cap ? jobs : cap), 64 * kLagCostWaves, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint64_t nrest = a.row_blocks - a.nsel_fast * E;
+    if (nrest) { // a selected short last frame, or everything the fast kernel cannot take
+        const uint64_t work = nrest * ncand, cap = (uint64_t)kHistWgsPerCu * cu_count();
+        k_lag_order_cost_bytes<E><<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
     }
     return REDUX_OK;
@@ -4594,6 +4627,45 @@ const char *redux_lag_cost_kernel_name_at(const void *d_in, uint64_t in_len, uin
 const char *redux_lag_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
     return redux_lag_cost_kernel_name_at(nullptr, in_len, block_size, element_size);
+}
+
+int redux_lag_order_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                             const uint32_t *lags, const uint32_t *orders, uint32_t ncand, uint32_t frame_step, void *d_bits,
+                             void *stream)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK || frame_step == 0 ||
+        !d_bits || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    LagOrderCostArgs a; // (the lists travel in the kernels' arguments: consumed before the call returns)
+    if (!lag_order_cost_list(element_size, lags, orders, ncand, REDUX_LAG_ORDER_COST_MAX, a.lags, a.orders, redux_lag_order_check))
+        return REDUX_INVALID_INPUT;
+    const int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    return for_element_size(element_size, [&](auto e) -> int {
+        return launch_lag_order_cost<decltype(e)::value>(a, d_in, in_len, block_size, ncand, frame_step, (double *)d_bits,
+                                                         (hipStream_t)stream);
+    });
+}
+
+const char *redux_lag_order_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    static const char *const names[4][3] = {
+        {"k_lag_order_cost<1>", "k_lag_order_cost<1> + k_lag_order_cost_bytes<1>", "k_lag_order_cost_bytes<1>"},
+        {"k_lag_order_cost<2>", "k_lag_order_cost<2> + k_lag_order_cost_bytes<2>", "k_lag_order_cost_bytes<2>"},
+        {"k_lag_order_cost<4>", "k_lag_order_cost<4> + k_lag_order_cost_bytes<4>", "k_lag_order_cost_bytes<4>"},
+        {"k_lag_order_cost<8>", "k_lag_order_cost<8> + k_lag_order_cost_bytes<8>", "k_lag_order_cost_bytes<8>"},
+    };
+    if (block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK)
+        return "";
+    const uint32_t E = element_size, e = E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : 3;
+    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
+    return names[e][nfull == 0 ? 2 : nfull * E < redux_block_count(in_len, block_size) ? 1 : 0];
+}
+
+const char *redux_lag_order_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return redux_lag_order_cost_kernel_name_at(nullptr, in_len, block_size, element_size);
 }
 
 int redux_table_cost_dev(const void *d_counts, const void *d_cum, uint64_t n, void *d_bits, void *stream)

@@ -119,6 +119,15 @@ extern "C" {
     fn redux_lag_cost_kernel_name(in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
     #[allow(dead_code)]
     fn redux_lag_cost_kernel_name_at(d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
+    // order estimates: the same for a list of (lag, order) candidates of higher-order lagged differences
+    #[allow(dead_code)]
+    fn redux_lag_order_cost_dev(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32,
+                                lags: *const u32, orders: *const u32, ncand: u32, frame_step: u32, d_bits: *mut c_void,
+                                stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_lag_order_cost_kernel_name(in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
+    #[allow(dead_code)]
+    fn redux_lag_order_cost_kernel_name_at(d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
     fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
     fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
     fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
