@@ -557,6 +557,59 @@ int redux_decode_blocks_lag_order(const redux_params *p, const uint8_t *in, cons
                                   uint32_t block_size, uint32_t element_size, uint32_t lag, uint32_t order, uint8_t *out,
                                   uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- record layout for fixed-width structs ---------------------------------------------------------
+ * A table of fixed-width records -- a packed C struct dump, a numpy structured array, a row-major page of a columnar store --
+ * holds one distribution per byte column of the record.  The lag filter at element size 1 differences every byte against the
+ * same byte of the record before, but leaves all R columns in the same blocks.  These calls are the byte-plane layout with a
+ * record size R, 2 <= R <= REDUX_RECORD_MAX, in place of an element size (the HDF5 / Blosc "shuffle" with an arbitrary type
+ * size), so that every block holds one byte column, with an optional byte delta against the record before.  Strictly opt-in;
+ * adaptive model only.  B = block_size:
+ *   - the input is cut into frames of R*B bytes, only the last may be shorter; a frame of L bytes holds N = L / R records;
+ *   - delta != 0: d[i][p] = x[i][p] - x[i-1][p] mod 256 for i >= 1, d[0][p] = x[0][p]; every frame starts afresh; no fold
+ *     (the adaptive model's cost of a block does not depend on a bijection of its byte values); delta == 0: d = x;
+ *   - byte p of record i moves to frame offset p*N + i; the L - N*R trailing bytes stay where they are.
+ *   Without the delta this is the byte-plane layout's rule with E = R, and for R = 2, 4, 8 redux_planes_dev's bytes.
+ *     stream_record_R_F(x)[b] == redux_encode_blocks(record_R_F(x))[b].
+ *
+ * Every call is the shape of its lag namesake with (record_size, delta) in place of (element_size, lag), and keeps its
+ * promises: redux_decode_record_dev writes no byte outside d_out[0 .. out_len), for damaged streams too, and every frame whose
+ * blocks are intact decodes right; block_crc is over the ORIGINAL bytes.  A record size outside 2 .. REDUX_RECORD_MAX or a
+ * delta other than 0 / 1 is REDUX_INVALID_INPUT, and nothing is written; the workspace calls take no delta, return 0 for such a
+ * record size and otherwise what the lag family's return for element size 1.  redux_record_planes_dev: full frames go to
+ * k_record_planes / k_record_unplanes when block_size, d_src and d_dst are multiples of 16, everything else (the short last
+ * frame included) to k_record_planes_bytes / k_record_unplanes_bytes; d_src and d_dst must not overlap; no workspace.  The
+ * host-pointer pair runs on the chunk pipeline with chunks rounded up to whole frames of R blocks; streams depend on neither
+ * the chunk size nor the devices.
+ * redux_host_chunk_plan_record   redux_host_chunk_plan for these calls: the chunk a multiple of record_size blocks.
+ * redux_record_kernel_name       the kernels redux_record_planes_dev runs on 16-byte aligned buffers, joined by " + " when
+ *                                full frames are followed by a short one; "" for arguments the call refuses.
+ * redux_record_kernel_name_at    the same for these buffers, which contribute their alignment only. */
+#define REDUX_RECORD_MAX 256
+int      redux_record_check(uint32_t record_size, int delta);
+int      redux_record_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t record_size, int delta,
+                                 int inverse, void *stream);
+uint64_t redux_encode_record_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t record_size);
+uint64_t redux_decode_record_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t record_size);
+int redux_encode_record_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t record_size,
+                            int delta, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] or NULL */, void *d_workspace,
+                            uint64_t workspace_bytes, void *stream);
+int redux_decode_record_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                            uint32_t block_size, uint32_t record_size, int delta, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] or NULL */, void *d_workspace,
+                            uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_record(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t record_size,
+                               int delta, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                               uint32_t *block_crc);
+int redux_decode_blocks_record(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t record_size, int delta, uint8_t *out, uint32_t *out_sizes,
+                               int32_t *block_status, uint32_t *block_crc);
+int redux_host_chunk_plan_record(uint64_t nblocks, uint32_t block_size, uint32_t record_size, uint32_t ncontexts, int decode,
+                                 uint64_t *chunk_blocks, uint64_t *nchunks);
+const char *redux_record_kernel_name(uint64_t len, uint32_t block_size, uint32_t record_size, int inverse);
+const char *redux_record_kernel_name_at(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size,
+                                        uint32_t record_size, int inverse);
+
 /* ---- XOR-against-base filter for series of snapshots -------------------------------------------
  * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its
  * base model, optimizer state, a KV cache against its earlier self -- differs from its predecessor only in the low mantissa

@@ -232,6 +232,20 @@ SIGNATURES.update({
     "redux_encode_blocks_lag_order": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U32, _U32, _V, _U64, _V, _V, _V]),
     "redux_decode_blocks_lag_order": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U32, _U32, _V, _V, _V, _V]),
 })
+# the record layout: the lag family with (record size, delta flag) in place of (element size, lag)
+SIGNATURES.update({
+    "redux_record_check": (C.c_int, [_U32, C.c_int]),
+    "redux_record_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, C.c_int, C.c_int, _V]),
+    "redux_encode_record_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_record_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_encode_record_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, C.c_int, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_record_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, C.c_int, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_record": (C.c_int, [_PP, _V, _U64, _U32, _U32, C.c_int, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_record": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, C.c_int, _V, _V, _V, _V]),
+    "redux_host_chunk_plan_record": (C.c_int, [_U64, _U32, _U32, _U32, C.c_int, C.POINTER(_U64), C.POINTER(_U64)]),
+    "redux_record_kernel_name": (C.c_char_p, [_U64, _U32, _U32, C.c_int]),
+    "redux_record_kernel_name_at": (C.c_char_p, [_V, _V, _U64, _U32, _U32, C.c_int]),
+})
 
 _LIB = None
 

@@ -511,8 +511,9 @@ def _check_element_size(element_size):
 # whether those take a (base, base_len) pair, and whether decoding needs the length for every element size.  A new filter
 # is a new row here (and a Filter value in redux_hip.hip, and a version row in container.py).  lag: the lag of the lagged
 # delta filter, which its entry points take behind the element size; None for every other front.  order: the order of
-# higher-order lagged differences, which their entry points take behind the lag; None for every other front.
-_Front = namedtuple("_Front", "infix takes_base needs_length lag order", defaults=(None, None))
+# higher-order lagged differences, which their entry points take behind the lag; None for every other front.  record: the
+# (record size, delta flag) of the record layout, which its entry points take in place of the element size; None elsewhere.
+_Front = namedtuple("_Front", "infix takes_base needs_length lag order record", defaults=(None, None, None))
 _PLANES = _Front("planes", False, False)                                 # no filter: the layout alone (none for element size 1)
 _FILTERS = {"delta": _Front("delta", False, True),                       # filter="delta": the delta filter for integer series
             "zigzag": _Front("zigzag", False, True),                     # filter="zigzag": the same with folded differences
@@ -520,6 +521,8 @@ _FILTERS = {"delta": _Front("delta", False, True),                       # filte
 _LAG_ORDER = _Front("lag_order", False, True)                            # filter="lag", lag=S, order=2 or 3: the lag filter K times
 LAG_MAX = 256  # REDUX_LAG_MAX
 LAG_ORDER_MAX = 3  # REDUX_LAG_ORDER_MAX
+_RECORD = _Front("record", False, True)                                  # record_size=R: the record layout; filter="delta": its byte delta
+RECORD_MAX = 256  # REDUX_RECORD_MAX
 _BASE_OPS = {"xor": _Front("base", True, True),                          # base=: the XOR against the base
              "sub": _Front("base_sub", True, True)}                      # base=, base_op="sub": the folded difference
 
@@ -530,7 +533,7 @@ _STATIC_MODELS = (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStat
 
 
 def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor", constant=None, stored=None, unit_layouts=None,
-                   device=False, lag=None, order=None):
+                   device=False, record_size=None, lag=None, order=None):
     """The one place that says which of filter=, base=, base_op=, constant=, stored=, unit_layouts= and the model's kind go
     together; anything else is InvalidInput.  A check on the arguments alone: it touches neither the library nor torch,
     so it comes before any call into either.  -> _Resolved.
@@ -544,8 +547,19 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     filter or stored blocks.
     unit_layouts: None, or the mixed layouts (any other value); adaptive model only, element size 1 and none of the above.
     device: the device coder objects take a model for its parameters alone and have no stored blocks: only the
-    constant-block option and the mixed layouts look at the model's kind there."""
+    constant-block option and the mixed layouts look at the model's kind there.
+    record_size: None, or the record layout (include/redux_hip.h, "record layout"): an int in 2 .. RECORD_MAX; adaptive
+    model only, element size 1, filter None or "delta" (the byte delta against the record before), and none of lag=,
+    order=, base=, constant=, stored= or unit_layouts=; the _Front returned carries (record size, delta flag)."""
     static = isinstance(params, _STATIC_MODELS)
+    if record_size is not None:
+        if isinstance(record_size, bool) or not isinstance(record_size, (int, np.integer)) or not 2 <= record_size <= RECORD_MAX \
+                or static or not isinstance(element_size, (int, np.integer)) or isinstance(element_size, bool) or element_size != 1 \
+                or not (filter is None or (isinstance(filter, str) and filter == "delta")) \
+                or any(x is not None for x in (lag, order, base, stored, unit_layouts)) \
+                or not (constant is None or constant is False):
+            raise InvalidInput()
+        return _Resolved(_RECORD._replace(record=(int(record_size), 1 if filter is not None else 0)), False, False)
     const = not (constant is None or constant is False)
     mixed = unit_layouts is not None
     if (lag is not None) != (isinstance(filter, str) and filter == "lag") or (lag is not None and (
@@ -585,6 +599,12 @@ def _lag_arg(front):
     """what a _Front's entry points take behind the element size: the lag of the lagged delta filter, the lag and the order
     of higher-order lagged differences, or nothing"""
     return () if front.lag is None else (front.lag,) if front.order is None else (front.lag, front.order)
+
+
+def _elem_args(front, E):
+    """what a _Front's entry points take behind the block size: the element size and the lag arguments, or the record
+    layout's record size and delta flag"""
+    return front.record if front.record is not None else (E, *_lag_arg(front))
 
 
 def _blocks_entry(L, direction, front):
@@ -677,7 +697,7 @@ def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
                     store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None,
-                    lag=None, order=None, base_op="xor"):
+                    record_size=None, lag=None, order=None, base_op="xor"):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -720,9 +740,14 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     element_size, filter=, stored=, base= or constant=.
     base_op: "xor" (the default), or "sub" with base=: the folded difference of the elements against the base in place of
     the XOR (include/redux_hip.h, "folded difference against a base": redux_encode_blocks_base_sub);
-    decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=."""
+    decompress_blocks(..., base=, base_op="sub") undoes it.  Not with constant=.
+    record_size=R (2 .. 256): the record layout for fixed-width structs (include/redux_hip.h, "record layout":
+    redux_encode_blocks_record): every block then holds one byte column of B records of R bytes.  filter="delta" with it is
+    the byte delta against the record before (not the integer delta filter).  Adaptive model only, element_size 1, and with
+    none of lag=, order=, base=, constant=, stored= or unit_layouts=; decompress_blocks(..., length, record_size=R, filter=)
+    undoes it."""
     front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                         order=order)
+                                         order=order, record_size=record_size)
     if mixed:
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
     if layouts is not None:
@@ -782,7 +807,7 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     else:  # the adaptive coder behind the front's filter (none, and element size 1, included: the coder without a layout)
         y = _u8(base) if front.takes_base else None
         st = _blocks_entry(L, "encode", front)(C.byref(cp), _ptr(a), len(a), *((_ptr(y), len(y)) if front.takes_base else ()),
-                                               block_size, E, *_lag_arg(front), out.ctypes.data, cap, offs.ctypes.data,
+                                               block_size, *_elem_args(front, E), out.ctypes.data, cap, offs.ctypes.data,
                                                status.ctypes.data, crc)
     _raise(st)
     if constant is True:
@@ -801,7 +826,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, lag=None,
+                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, record_size=None, lag=None,
                       order=None, base_op="xor"):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
@@ -830,9 +855,11 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     only, and not with stored= or filter=.
     unit_layouts: the np.uint8[nunits] table of compress_blocks(..., unit_layouts=) (redux_decode_blocks_mixed); length is
     required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
-    base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub)."""
+    base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub).
+    record_size=R, with the filter= the streams were made with: the streams are compress_blocks(..., record_size=R)'s
+    (redux_decode_blocks_record); length is required, and out is the original bytes."""
     front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                         order=order)
+                                         order=order, record_size=record_size)
     if mixed:
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
@@ -889,7 +916,7 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     elif length is not None:  # the adaptive coder behind the front's filter, or behind the layout alone
         y = _u8(base) if front.takes_base else None
         st = _blocks_entry(L, "decode", front)(C.byref(cp), _ptr(a), offs.ctypes.data, *((_ptr(y), len(y)) if front.takes_base else ()),
-                                               length, block_size, E, *_lag_arg(front), out.ctypes.data, sizes.ctypes.data,
+                                               length, block_size, *_elem_args(front, E), out.ctypes.data, sizes.ctypes.data,
                                                status.ctypes.data, crc)
     else:
         st = L.redux_decode_blocks_crc(C.byref(cp), _ptr(a), offs.ctypes.data, nb, block_size, out.ctypes.data, out.size,
@@ -907,10 +934,15 @@ def host_set_devices(device_ids):
     _raise(_lib.lib().redux_host_set_devices(ids.ctypes.data if ids.size else None, int(ids.size)))
 
 
-def host_chunk_plan(nblocks, block_size, ncontexts=1, decode=False):
-    """(blocks per chunk, number of chunks) a host-pointer call uses; chunk k runs on context k % ncontexts."""
+def host_chunk_plan(nblocks, block_size, ncontexts=1, decode=False, record_size=None):
+    """(blocks per chunk, number of chunks) a host-pointer call uses; chunk k runs on context k % ncontexts.  record_size:
+    the plan of the record layout's calls, whose chunks are whole frames of record_size blocks."""
     cb, nc = C.c_uint64(), C.c_uint64()
-    _raise(_lib.lib().redux_host_chunk_plan(nblocks, block_size, ncontexts, 1 if decode else 0, C.byref(cb), C.byref(nc)))
+    if record_size is None:
+        _raise(_lib.lib().redux_host_chunk_plan(nblocks, block_size, ncontexts, 1 if decode else 0, C.byref(cb), C.byref(nc)))
+    else:
+        _raise(_lib.lib().redux_host_chunk_plan_record(nblocks, block_size, record_size, ncontexts, 1 if decode else 0,
+                                                       C.byref(cb), C.byref(nc)))
     return cb.value, nc.value
 
 
@@ -1269,14 +1301,15 @@ class DeviceEncoder(_DeviceCoder):
     folded difference of the elements against the base in place of the XOR (include/redux_hip.h, "folded difference against a
     base"); not together with constant=True.  filter="lag", lag=S: the lagged delta filter (include/redux_hip.h, "lagged delta
     filter"), where filter="zigzag" may stand; order=K (1 .. 3) with it: the difference applied K times (include/redux_hip.h,
-    "higher-order lagged differences")."""
+    "higher-order lagged differences").  record_size=R: the record layout for fixed-width structs (include/redux_hip.h, "record
+    layout"), with filter=None or "delta", its byte delta; element size 1 and none of the other options."""
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, layouts=None, lag=None, order=None, base_op="xor"):
+                 mixed=False, layouts=None, record_size=None, lag=None, order=None, base_op="xor"):
         # (mixed: with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
                                                                unit_layouts=True if mixed else None, device=True, lag=lag,
-                                                               order=order)
+                                                               order=order, record_size=record_size)
         if self.mixed:
             self.mixed_mask = _layout_mask(layouts)
         elif layouts is not None:
@@ -1305,8 +1338,8 @@ class DeviceEncoder(_DeviceCoder):
         else:  # the layered entry points of the front's family
             ws_bytes = getattr(L, "redux_encode_%s_workspace_bytes" % self.front.infix)
             self._encode_dev = getattr(L, "redux_encode_%s_dev" % self.front.infix)
-            self._lead = (*(_base_pair(self.base) if self.front.takes_base else ()), B, E, *_lag_arg(self.front))
-        ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, E)
+            self._lead = (*(_base_pair(self.base) if self.front.takes_base else ()), B, *_elem_args(self.front, E))
+        ws_bytes = ws_bytes(C.byref(self.cp), self.max_in_len, B, _elem_args(self.front, E)[0])
         if (self.constant or self.mixed) and ws_bytes == 0:
             raise Unsupported()  # (the adaptive model with 8-bit symbols and code_bits <= 32 only)
         out_cap = L.redux_encode_bound(C.byref(self.cp), self.max_in_len, B)
@@ -1375,14 +1408,16 @@ class DeviceDecoder(_DeviceCoder):
     tensor DeviceEncoder(..., base=) was given; decode needs the length; not together with filter=.  constant=True: the
     streams are DeviceEncoder(..., constant=True)'s; decode needs the length and the flags (decode(..., constant=flags)).
     base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s.  filter="lag", lag=S: the streams are
-    DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"; order=K: the encoder's order."""
+    DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"; order=K: the encoder's order.  record_size=R (with the
+    encoder's filter=): the streams are DeviceEncoder(..., record_size=R)'s; decode needs the length, and decode_ranges reads
+    whole frames of R blocks."""
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, lag=None, order=None, base_op="xor"):
+                 mixed=False, record_size=None, lag=None, order=None, base_op="xor"):
         # (mixed: the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
                                                                unit_layouts=True if mixed else None, device=True, lag=lag,
-                                                               order=order)
+                                                               order=order, record_size=record_size)
         torch = _torch()
         self.base = _device_base(torch, base, device)
         P = _params_of(params)
@@ -1467,7 +1502,7 @@ class DeviceDecoder(_DeviceCoder):
                 self._alloc_workspace(self._layout_ws_bytes(self.max_in_len))
             decode_dev = self._decode_dev
             lead = _base_pair(base) if self._takes_base else self._lead
-            args = (*flags, *lead, nbytes, self.block_size, self.element_size, *_lag_arg(self.front), self.out.data_ptr())
+            args = (*flags, *lead, nbytes, self.block_size, *_elem_args(self.front, self.element_size), self.out.data_ptr())
         self.summary.zero_()
         _raise(decode_dev(C.byref(self.cp), d_streams.data_ptr(), d_offsets.data_ptr(), *args, *self._dec_tail()))
         return self._dec_result(nbytes, nb)
@@ -1492,7 +1527,7 @@ class DeviceDecoder(_DeviceCoder):
     def decode_ranges(self, d_streams, offsets, length, ranges, out=None, constant=None, unit_layouts=None):
         """The bytes [start, start + n) of every (start, n) of `ranges` of the original input, from streams resident in
         device memory, decoding only the granules the ranges cover (include/redux_hip.h, "range reads"): element_size blocks,
-        or 8 for a decoder made with mixed=True.  ONE decode launch whatever the number of ranges: the covered streams are
+        record_size blocks for a decoder made with one, or 8 for a decoder made with mixed=True.  ONE decode launch whatever the number of ranges: the covered streams are
         gathered into a compact buffer (k_segment_copy), with their entries of `constant` / `unit_layouts` and their bytes
         of the base, decoded by the entry point decode() uses, and the requested bytes scattered into `out`
         (k_segment_copy).
@@ -1515,7 +1550,7 @@ class DeviceDecoder(_DeviceCoder):
         nb = len(offs) - 1
         if (unit_layouts is None) == self.mixed or (constant is None) == self.constant:
             raise InvalidInput()
-        g = MIXED_UNIT_BLOCKS if self.mixed else self.element_size
+        g = MIXED_UNIT_BLOCKS if self.mixed else self.front.record[0] if self.front.record else self.element_size
         ranges = list(ranges)
         runs, virt_off, virt_len = range_plan(length, B, g, ranges)
         lens = [int(n) for _, n in ranges]
@@ -1822,7 +1857,7 @@ def _transform(front, d_src, element_size, block_size, inverse, out, d_base=None
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
     base = _base_pair(d_base) if front.takes_base else ()
     with torch.cuda.device(t.device):
-        _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, E, *_lag_arg(front),
+        _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, *_elem_args(front, E),
                                          1 if inverse else 0, _stream_ptr(torch)))
     return t
 
@@ -1859,6 +1894,24 @@ def lag_order_planes(d_src, element_size, block_size, lag, order, inverse=False,
         raise InvalidInput()
     _resolve_front(None, filter="lag", lag=lag, order=order)
     return _transform(_LAG_ORDER._replace(lag=int(lag), order=int(order)), d_src, element_size, block_size, inverse, out)
+
+
+def record_planes(d_src, record_size, block_size, delta=False, inverse=False, out=None):
+    """The record layout for fixed-width structs (include/redux_hip.h, "record layout") of a uint8 device tensor, or its
+    inverse: redux_record_planes_dev on torch's current stream.  record_size: 2 .. RECORD_MAX.  delta: the byte delta
+    against the record before, in front of the layout.  out: as for planes()."""
+    front = _resolve_front(None, filter="delta" if delta else None, record_size=record_size).front
+    return _transform(front, d_src, 1, block_size, inverse, out)
+
+
+def record_kernel_name(nbytes, block_size, record_size, inverse=False, d_src=None, d_dst=None):
+    """The kernels record_planes runs for nbytes bytes (redux_record_kernel_name; with d_src and d_dst, device tensors,
+    redux_record_kernel_name_at: their alignment counts), joined by " + "; "" for arguments the call refuses."""
+    L = _lib.lib()
+    if d_src is None and d_dst is None:
+        return L.redux_record_kernel_name(nbytes, block_size, record_size, 1 if inverse else 0).decode()
+    return L.redux_record_kernel_name_at(d_src.data_ptr(), d_dst.data_ptr(), nbytes, block_size, record_size,
+                                         1 if inverse else 0).decode()
 
 
 def _device_unit_table(torch, table, nunits, device):

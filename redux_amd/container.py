@@ -12,7 +12,8 @@ Layout (little-endian):
            layout; 9 = constant blocks skipped, with or without the XOR-against-base filter; 10 = mixed layouts: a layout
            per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout; 12 = folded difference
            against a base in front of the byte-plane layout; 13 = lagged delta filter in front of the byte-plane layout;
-           14 = higher-order lagged differences in front of the byte-plane layout)
+           14 = higher-order lagged differences in front of the byte-plane layout; 15 = further layouts, told apart by a kind
+           field in the word at offset 12: kind 1 = record layout for fixed-width structs)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -22,7 +23,9 @@ Layout (little-endian):
            version 9: 0x90000000 | F << 4 | E with E one of 1, 2, 4, 8 and F 1 if a base was used, else 0; version 10:
            0xA0000000; version 11: 0xB0000000 | E with E one of 1, 2, 4, 8; version 12: 0xC0000000 | E with E one of 1, 2, 4, 8;
            version 13: 0xD0000000 | S << 4 | E with E one of 1, 2, 4, 8 and the lag S, 1 <= S <= 256;
-           version 14: 0xE0000000 | K << 16 | S << 4 | E with E and S as in version 13 and the order K, 2 <= K <= 3
+           version 14: 0xE0000000 | K << 16 | S << 4 | E with E and S as in version 13 and the order K, 2 <= K <= 3;
+           version 15: 0xF0000000 | kind << 24 | F << 12 | R with kind 1, the record size R, 2 <= R <= 256, in bits 0 to 8 and
+           F 1 for the byte delta, else 0
    16   8  nblocks
    24   8  total uncompressed length
    (versions 8 and 12, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
@@ -116,9 +119,18 @@ fold and filter with the lag and the order the word records.  The word at offset
 other version takes that word, and version 14 takes no other; K outside 2 .. 3 and S outside 1 .. 256 are InvalidInput.  Order
 1 is the lagged delta filter and is always written as version 13, so a version 14 word with K = 1 is malformed.  It has no
 stored blocks (no 0x4E / 0x5E).  Without an order above 1 the writers emit exactly the bytes they emitted before the version
-existed.  One version number, 15, is left under the flag bits.
+existed.
 
-Bit 0x10 of the version byte (versions 0x11 to 0x1E: versions 1 to 14 with checksums) means a table of nblocks
+Version 15 is the last version number under the flag bits, so it is not spent on one layout: bits 24 .. 27 of its word at
+offset 12 hold a KIND, and later layouts take kinds 2 .. 15 of version 15 rather than a version.  Kind 1 holds streams of
+the adaptive coder behind the record layout for fixed-width structs (include/redux_hip.h, "record layout"): the sections are
+version 2's, the payloads are the streams of the bytes in the layout of records of R bytes -- every block one byte column of
+B records -- behind the byte delta against the record before when F is set, and decoding undoes both.  The word is
+0xF0000000 | 1 << 24 | F << 12 | R: every other kind, any other set bit and R outside 2 .. 256 are InvalidInput; no other
+version takes that word, and version 15 takes no other.  It has no stored blocks (no 0x4F / 0x5F).  Without a record size the
+writers emit exactly the bytes they emitted before the version existed.
+
+Bit 0x10 of the version byte (versions 0x11 to 0x1F: versions 1 to 15 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
 block that is whole and correct but in the wrong place (swapped, duplicated, stitched in from another file) decodes to the
@@ -154,6 +166,10 @@ VERSION_ZIGZAG = 11
 VERSION_BASE_SUB = 12
 VERSION_LAG = 13
 VERSION_LAG_ORDER = 14
+VERSION_KINDS = 15
+KINDS_MARK = 0xF0000000  # version 15's word at offset 12: KINDS_MARK | kind << 24 | what the kind records
+KIND_RECORD = 1  # the record layout: KINDS_MARK | KIND_RECORD << 24 | F << 12 | R
+RECORD_MAX = api.RECORD_MAX  # the largest record size R (REDUX_RECORD_MAX)
 LAG_ORDER_MARK = 0xE0000000  # version 14's word at offset 12: LAG_ORDER_MARK | K << 16 | S << 4 | E
 LAG_ORDER_MAX = api.LAG_ORDER_MAX  # the largest order K (REDUX_LAG_ORDER_MAX); version 14 records 2 .. LAG_ORDER_MAX
 LAG_MARK = 0xD0000000  # version 13's word at offset 12: LAG_MARK | S << 4 | E
@@ -206,8 +222,16 @@ def _raw_lengths(nblocks, block_size, total):
     return np.clip(total - o, 0, block_size)
 
 
+def _record_word(res):
+    """(R, delta flag) of a well-formed version 15 word of kind 1, else None"""
+    R, F = res & 0x1FF, res >> 12 & 1
+    if res != (KINDS_MARK | KIND_RECORD << 24 | F << 12 | R) or not 2 <= R <= RECORD_MAX:
+        return None
+    return R, bool(F)
+
+
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None, unit_layouts=None, lag=None, order=None, base_op="xor"):
+         constant=None, unit_layouts=None, record_size=None, lag=None, order=None, base_op="xor"):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -228,9 +252,11 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     unit_layouts: the ceil(nblocks / 8) layouts, 0 .. 7, of compress_blocks(..., unit_layouts=) (version 10; adaptive model,
     element_size 1 and none of stored, filter, base and constant); None: no unit table.
     base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
-    version 8)."""
+    version 8).
+    record_size R (with filter None or "delta" only): streams of compress_blocks(..., record_size=R, filter=) (version 15,
+    kind 1; adaptive model, element_size 1 and none of the other options)."""
     front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                             order=order)
+                                             order=order, record_size=record_size)
     xbase = front.takes_base
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
@@ -262,7 +288,9 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_SEGMENT_STATIC, SEGMENT_MARK | k << 4 | element_size
     if context:
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
-    if filter is not None or xbase:
+    if front.record is not None:
+        ver, res = VERSION_KINDS, KINDS_MARK | KIND_RECORD << 24 | front.record[1] << 12 | front.record[0]
+    elif filter is not None or xbase:
         ver = VERSION_LAG_ORDER if front.order else _VERSION_OF_FILTER[filter, base_op if xbase else None]
         res = FILTER_VERSIONS[ver].mark << 28 | (front.order or 0) << 16 | (front.lag or 0) << 4 | element_size
     if const:
@@ -370,7 +398,8 @@ def _version_ok(ver, res):
             and res >> 4 & 0xFFFFFF >= 1) \
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
         or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
-        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK)
+        or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK) \
+        or (layout == VERSION_KINDS and not ver & STORED_FLAG and _record_word(res) is not None)
 
 
 def _has_base_record(ver, res):
@@ -388,9 +417,9 @@ def _has_base_record(ver, res):
 # there is a record, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
 # None, as the table holds it unit by unit.  lag: the lag S of version 13 or 14, else None.  order: the order K of version 14,
-# else None.
+# else None.  record: (R, delta) of version 15's record layout, else None; element_size is then 1 and filter None.
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
-                        " unit_layouts base_op lag order", defaults=(None, None, None, None))
+                        " unit_layouts base_op lag order record", defaults=(None, None, None, None, None))
 
 
 def _header(b):
@@ -497,7 +526,8 @@ def _parse_index(b):
     row = FILTER_VERSIONS.get(_layout(ver))  # (version 9's record, where it has one, is the XOR's)
     return _Container(P, block_size, total, E, static, offsets, None, crcs, stored, row.filter if row else None, base, constant,
                       units, row.base_op if row else None if base is None else "xor",
-                      *(_lag_word(row, HEADER.unpack_from(b, 0)[6]) if row and row.has_lag else (None, None))), at
+                      *(_lag_word(row, HEADER.unpack_from(b, 0)[6]) if row and row.has_lag else (None, None)),
+                      _record_word(HEADER.unpack_from(b, 0)[6]) if _layout(ver) == VERSION_KINDS else None), at
 
 
 def _parse(buf):
@@ -550,6 +580,13 @@ def order(buf):
     version 13 container; None for every other version.  Malformed containers raise InvalidInput, truncated ones Eof."""
     c = _parse(buf)
     return c.order if c.order is not None else None if c.lag is None else 1
+
+
+def record(buf):
+    """(R, delta) of a version 15 container of kind 1 (the record layout for fixed-width structs): the record size and whether
+    the byte delta against the record before was applied; None for every other container.  Malformed containers raise
+    InvalidInput, truncated ones Eof."""
+    return _parse(buf).record
 
 
 def base(buf):
@@ -619,14 +656,23 @@ def header_is_wellformed(buf):
 
 
 def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_cums=None, checksum=False, stored=False,
-                   filter=None, mixed=False, base=False):
+                   filter=None, mixed=False, base=False, record_size=None):
     """The bytes pack() writes besides the payloads for `model` (one of api.MODELS) and nblocks blocks: header, tables, size
     table, and the CRC table / stored-block bitmap when asked for.  segment-static: segment_blocks None is
     api.default_segment_blocks(element_size).  context-static: context_cums, the np.uint32[256, 258] tables, is required,
     because only the tables of contexts that occur are recorded.  filter "delta", "zigzag" or "lag" (adaptive model, not stored):
     version 6, 11 or 13 (14 at an order above 1: the same size), which record the filter (and the lag and the order) in the header's reserved word and add no bytes.  mixed (adaptive model, element size 1, no
     filter, not stored): version 10, whose unit table adds a byte per 8 blocks.  base (adaptive model, no filter, not stored, not
-    mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation."""
+    mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation.  record_size (adaptive model, element size 1,
+    filter None or "delta", not stored, not mixed, no base): version 15, which records the layout in the header's reserved word
+    and adds no bytes."""
+    if record_size is not None:
+        if model != "adaptive" or stored or mixed or base:
+            raise api.InvalidInput()
+        api._resolve_front(None, element_size, filter, record_size=record_size)
+        if nblocks < 1:
+            raise api.InvalidInput()
+        return HEADER.size + 4 * nblocks + (4 * nblocks if checksum else 0)
     if model not in api.MODELS or nblocks < 1 or (mixed and (model != "adaptive" or element_size != 1 or stored or filter is not None)) \
             or (base and (model != "adaptive" or stored or filter is not None or mixed)):
         raise api.InvalidInput()
@@ -654,9 +700,27 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     return n
 
 
-def estimate_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, segment_blocks=None, models=None, checksum=False):
+def estimate_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, segment_blocks=None, models=None, checksum=False,
+                   record_size=None, filter=None):
     """-> {model: estimated container bytes}: api.estimate_payload's estimate of the payloads plus overhead_bytes, which is
-    exact, for each model of `models` (None: api.estimate_candidates(element_size)).  Nothing is coded."""
+    exact, for each model of `models` (None: api.estimate_candidates(element_size)).  Nothing is coded.  record_size (with
+    filter None or "delta"; models None or ("adaptive",), no segment_blocks): the adaptive model behind the record layout,
+    estimated on the transformed bytes (api.record_planes: one transform on the GPU, nothing coded)."""
+    if record_size is not None or filter is not None:
+        if record_size is None or segment_blocks is not None or (models is not None and tuple(models) != ("adaptive",)) \
+                or not 0 < block_size <= MAX_BLOCK_SIZE:
+            raise api.InvalidInput()
+        front = api._resolve_front(None, element_size, filter, record_size=record_size).front
+        torch = api._torch()
+        a = api._u8(data)
+        nb = max(1, -(-len(a) // block_size))
+        over = overhead_bytes("adaptive", nb, checksum=checksum, filter=filter, record_size=record_size)
+        if len(a) == 0:
+            t = a
+        else:
+            t = api.record_planes(torch.from_numpy(a.copy()).cuda(), front.record[0], block_size, delta=bool(front.record[1])).cpu().numpy()
+        payload, _ = api._estimate(t, block_size, params, 1, None, ["adaptive"])
+        return {"adaptive": payload["adaptive"] + over}
     payload, context_cums = api._estimate(data, block_size, params, element_size, segment_blocks, models)
     nb = max(1, -(-len(data) // block_size))
     return {m: payload[m] + overhead_bytes(m, nb, element_size, segment_blocks, context_cums, checksum) for m in payload}
@@ -718,7 +782,7 @@ def choose_base_op(estimates):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, lag=None,
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, record_size=None, lag=None,
                    order=None, base_op="xor"):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
@@ -764,7 +828,18 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     base_op (with base, not with skip_constant): "sub" codes the folded difference of the elements against the base in place
     of the XOR, version 12.  "auto": the operation with the smaller estimated payload codes the data (choose_base_op; a tie
     goes to "xor"), and the container is that operation's, version 8 or 12: nothing new to decode.  Related pairs favour
-    "sub", unrelated ones "xor", and a caller cannot know in advance."""
+    "sub", unrelated ones "xor", and a caller cannot know in advance.
+    record_size R, 2 .. 256 (element_size 1, model "adaptive", filter None or "delta", and none of stored, segment_blocks,
+    base, skip_constant, layout, lag and order): the record layout for fixed-width structs, every block one byte column of
+    block_size records of R bytes; filter "delta" is then the byte delta against the record before.  Version 15, kind 1."""
+    if record_size is not None:
+        if layout is not None or model != "adaptive" or stored or segment_blocks is not None or skip_constant or base_op != "xor" \
+                or not 0 < block_size <= MAX_BLOCK_SIZE:
+            raise api.InvalidInput()
+        api._resolve_front(None, element_size, filter, base, lag=lag, order=order, record_size=record_size)
+        crc = np.zeros(max(1, -(-len(data) // block_size)), dtype=np.uint32) if checksum else None
+        out, offs, _ = api.compress_blocks(data, block_size, params, block_crc=crc, filter=filter, record_size=record_size)
+        return pack(out, offs, params, block_size, len(data), block_crc=crc, filter=filter, record_size=record_size)
     api._resolve_front(None, base=base, base_op="sub" if base_op == "auto" else base_op,
                        constant=skip_constant or None)  # (base_op alone is judged here; "auto": the refusals of "sub")
     auto_lag = isinstance(lag, str) and lag == "auto"  # (the choice is made below, once nothing else refuses the call)
@@ -861,7 +936,7 @@ def _decode_parsed(c, base):
     segment = isinstance(c.static, api.SegmentStaticModel)
     mixed = c.unit_layouts is not None
     exact = mixed or c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None \
-        or c.constant is not None
+        or c.constant is not None or c.record is not None
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if mixed:
@@ -871,8 +946,10 @@ def _decode_parsed(c, base):
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, c.block_size,
                                                        c.static if (c.element_size > 1 or segment) and c.static is not None else c.params,
                                                        element_size=c.element_size, length=c.total, block_crc=got,
-                                                       stored=c.stored, filter=c.filter, base=base, constant=c.constant,
-                                                       base_op=c.base_op or "xor", lag=c.lag, order=c.order)
+                                                       stored=c.stored, base=base, constant=c.constant,
+                                                       filter="delta" if c.record is not None and c.record[1] else c.filter,
+                                                       base_op=c.base_op or "xor", lag=c.lag, order=c.order,
+                                                       record_size=None if c.record is None else c.record[0])
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
@@ -927,7 +1004,7 @@ def _index_rest_bytes(ver, nblocks):
 
 class Reader:
     """Random access to a container's bytes: read(start, length) decodes only the granules the range covers (a frame of E
-    blocks; a unit of 8 blocks for version 10; a segment for version 5), and read_many(ranges) does so for any number of ranges
+    blocks; a unit of 8 blocks for version 10; a segment for version 5; a frame of R blocks for version 15's record layout), and read_many(ranges) does so for any number of ranges
     in ONE coder call.
     source: the container as a bytes-like object, or a seekable binary file object, from which the header and the index
     sections are read at open (every section's size follows from the header; of version 7's table section, whose size does
@@ -961,8 +1038,10 @@ class Reader:
         c = self._c
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
         self.filter, self.base_op, self.lag, self.order = c.filter, c.base_op, c.lag, c.order
+        self.record = c.record
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
-            else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) else c.element_size
+            else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) \
+            else c.record[0] if c.record is not None else c.element_size
         self._base = _checked_base(c, base)
 
     @property

@@ -16,6 +16,7 @@
 //   redux_zigzag.hpp   the zigzag fold: k_delta_*<E, true> is the delta filter with folded differences, for signed series
 //   redux_lag.hpp      k_lag_planes / k_lag_unplanes: the lagged delta filter for interleaved channels, the predecessor S elements back
 //   redux_lag_order.hpp k_lag_order_planes / k_lag_order_unplanes: higher-order lagged differences, the lag filter applied K times
+//   redux_record.hpp   k_record_planes / k_record_unplanes: the record layout for fixed-width structs, R bytes a record, with a byte delta
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_base_sub.hpp BaseSubFold: the base filter's folded difference, the same kernels under another operation
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
@@ -52,6 +53,7 @@
 #include "redux_zigzag.hpp"
 #include "redux_lag.hpp"
 #include "redux_lag_order.hpp"
+#include "redux_record.hpp"
 #include "redux_base.hpp"
 #include "redux_base_sub.hpp"
 #include "redux_hist.hpp"
@@ -685,6 +687,61 @@ static int launch_lag_order(const void *d_src, void *d_dst, uint64_t len, uint32
     return REDUX_OK;
 }
 
+// the record layout (redux_record.hpp): the record size and the byte delta are kernel arguments.  Forward: tiles of T
+// records, workgroups striding over them.  Inverse: a workgroup per (frame, column range); the columns are cut into ranges
+// only where the frames alone would leave CUs idle.
+static uint32_t record_lg_tile(uint32_t row, uint32_t items_row, uint32_t block_size)
+{
+    uint32_t lg = 4; // (a tile is at least the 16 records of a group)
+    while (lg < 12 && (2u << lg) * (row + (row & 1 ? 0 : 1)) <= kRecordLdsBytes && (2u << lg) * items_row <= 16 * kRecordItems &&
+           (1u << lg) < block_size)
+        lg++;
+    return lg;
+}
+
+static int launch_record(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t R, bool delta, bool inverse,
+                         hipStream_t s)
+{
+    const uint64_t  frame = (uint64_t)R * block_size;
+    const FastSplit f = fast_split(len, frame, block_size, {d_src, d_dst});
+    RecordArgs a;
+    a.src        = (const uint8_t *)d_src;
+    a.dst        = (uint8_t *)d_dst;
+    a.nfull      = f.nfull;
+    a.block_size = block_size;
+    a.R          = R;
+    a.delta      = delta;
+    a.lgT        = 4;
+    a.PC         = R;
+    a.first      = f.rest;
+    a.len        = len;
+    if (f.nfull) {
+        const uint64_t cus = cu_count();
+        if (inverse) {
+            if (f.nfull < 2 * cus && R > 64) { // few frames: ranges of columns, 16-byte multiples of at least 64
+                const uint64_t want = (2 * cus + f.nfull - 1) / f.nfull;
+                const uint32_t pc   = (uint32_t)(((R + want - 1) / want + 15) / 16 * 16);
+                a.PC = pc < 64 ? 64 : pc;
+            }
+            const uint32_t nr = (R + a.PC - 1) / a.PC;
+            a.lgT = record_lg_tile(nr > 1 ? a.PC : R, a.PC < R ? a.PC : R, block_size);
+            k_record_unplanes<<<(uint32_t)std::min<uint64_t>(f.nfull, 8 * cus) * nr, 256, 0, s>>>(a);
+        } else {
+            a.lgT = record_lg_tile(R, 0, block_size);
+            const uint64_t tiles = f.nfull * ((block_size + (1u << a.lgT) - 1) >> a.lgT);
+            k_record_planes<<<(uint32_t)std::min<uint64_t>(tiles, 8 * cus), 256, 0, s>>>(a);
+        }
+    }
+    if (f.rest < len) { // the short last frame, or everything the fast kernels cannot take
+        if (inverse)
+            k_record_unplanes_bytes<<<grid_bytes(delta ? (len - f.rest + frame - 1) / frame * R : len - f.rest), 256, 0, s>>>(a);
+        else
+            k_record_planes_bytes<<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
+    }
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
 // the base filter: the fused kernels take the full frames that lie inside the base, one workgroup per 256 groups; the byte
 // kernels take the rest up to the end of the frame the base ends in (or of the input); whole frames past the base have
 // nothing to XOR and go to the layout alone (launch_planes).  SUB: the folded difference (redux_base_sub.hpp) in place of
@@ -756,14 +813,17 @@ static int for_element_size(uint32_t element_size, F &&f)
 // whose order travels there too (redux_lag_order.hpp); the base filter, the XOR or the folded difference (redux_base.hpp,
 // redux_base_sub.hpp).  The one name a filter has from the C entry points down to
 // the kernel launch: a new filter is a new value here.
-enum class Filter { None, Delta, Zigzag, Lag, LagOrder, BaseXor, BaseSub };
+// RecordDelta is the byte delta of the record layout (redux_record.hpp) and goes with a record size only; the record layout
+// without it is Filter::None with a record size.
+enum class Filter { None, Delta, Zigzag, Lag, LagOrder, BaseXor, BaseSub, RecordDelta };
 
 static bool filter_has_base(Filter f) { return f == Filter::BaseXor || f == Filter::BaseSub; }
 
 // the element size's check, and the lag's and the order's where the filter has them
 static int filter_check(Filter f, uint32_t element_size, uint32_t lag, uint32_t order)
 {
-    return f == Filter::LagOrder ? redux_lag_order_check(element_size, lag, order)
+    return f == Filter::RecordDelta ? REDUX_INVALID_INPUT // (no element-size layout has it)
+           : f == Filter::LagOrder ? redux_lag_order_check(element_size, lag, order)
            : f == Filter::Lag    ? redux_lag_check(element_size, lag)
                                  : redux_planes_check(element_size);
 }
@@ -798,6 +858,7 @@ static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t
         case Filter::Lag: return launch_lag<E>(d_src, d_dst, len, block_size, lag, inv, s);
         case Filter::Zigzag: return launch_delta<E, true>(d_src, d_dst, len, block_size, inv, s);
         case Filter::Delta: return launch_delta<E, false>(d_src, d_dst, len, block_size, inv, s);
+        case Filter::RecordDelta: // (refused above)
         case Filter::None: break;
         }
         if constexpr (E == 1) { // the layout of single bytes is the identity
@@ -807,6 +868,20 @@ static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t
             return launch_planes<E>(d_src, d_dst, len, block_size, inv, s);
         }
     });
+}
+
+// redux_record_planes_dev: transform_dev's checks for the record layout, then its launch
+static int record_transform_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t record_size, int delta,
+                                int inverse, void *stream)
+{
+    if (redux_record_check(record_size, delta) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place)
+        return REDUX_INVALID_INPUT;
+    return launch_record(d_src, d_dst, len, block_size, record_size, delta != 0, inverse != 0, (hipStream_t)stream);
 }
 
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
@@ -819,20 +894,40 @@ struct Layout {
     uint64_t    base_len = 0;
     uint32_t    lag      = 0;       // the lagged delta filter's lag
     uint32_t    order    = 0;       // the order of higher-order lagged differences
-    int         check() const { return filter_check(filter, E, lag, order); }
-    bool        identity() const { return filter == Filter::None && E == 1; }
+    uint32_t    record   = 0;       // the record layout's record size (E is 1 then, and does not say how many blocks a frame has)
+    bool        record_delta() const { return filter == Filter::RecordDelta; }
+    int         check() const
+    {
+        if (record)
+            return E == 1 && (filter == Filter::None || record_delta()) ? redux_record_check(record, record_delta()) : REDUX_INVALID_INPUT;
+        return filter_check(filter, E, lag, order);
+    }
+    bool        identity() const { return filter == Filter::None && E == 1 && !record; }
     bool        has_base() const { return filter_has_base(filter); }
     // room for the transformed copy of len bytes (none for the identity: the coder reads the caller's buffer)
     uint64_t copy_bytes(uint64_t len) const { return identity() ? 0 : planes_copy_bytes(len); }
+    int transform(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, int inv, void *stream) const
+    {
+        if (record)
+            return record_transform_dev(d_src, d_dst, len, block_size, record, record_delta(), inv, stream);
+        return transform_dev(filter, d_src, d_dst, len, block_size, E, inv, stream, d_base, base_len, lag, order);
+    }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter, d_src, d_dst, len, block_size, E, 0, stream, d_base, base_len, lag, order);
+        return transform(d_src, d_dst, len, block_size, 0, stream);
     }
     int inverse(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
     {
-        return transform_dev(filter, d_src, d_dst, len, block_size, E, 1, stream, d_base, base_len, lag, order);
+        return transform(d_src, d_dst, len, block_size, 1, stream);
     }
 };
+
+static Layout record_layout(uint32_t record_size, int delta)
+{
+    Layout L{1, delta ? Filter::RecordDelta : Filter::None};
+    L.record = record_size ? record_size : ~0u; // (0 must not mean "no record size" here: the check refuses it)
+    return L;
+}
 
 // Encode side: the transformed copy x' of d_in goes to the front of the workspace (x' = d_in for the identity) and the coder
 // gets x' and what is left of the workspace behind the copy.
@@ -1963,7 +2058,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
                               uint8_t *out, uint64_t out_len, uint64_t out_cap, uint32_t *out_sizes, int32_t *block_status,
                               uint64_t *in_used, const host::DecodeCoder &coder, uint32_t *block_crc = nullptr,
                               const uint8_t *stored = nullptr, host::SegmentTablesIo tables = {}, host::BaseIo base = {},
-                              host::UnitTableIo units = {})
+                              host::UnitTableIo units = {}, uint32_t frame_blocks = 1)
 {
     if (params != REDUX_OK)
         return params;
@@ -1976,7 +2071,7 @@ static int decode_blocks_host(int params, const uint8_t *in, const uint64_t *in_
     if (in_offsets[nblocks] && !in)
         return REDUX_INVALID_INPUT;
     return host::decode_blocks(in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder,
-                               block_crc, stored, tables, base, units); // redux_host.hpp
+                               block_crc, stored, tables, base, units, frame_blocks); // redux_host.hpp
 }
 
 int redux_decode_blocks_crc(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks,
@@ -2485,7 +2580,8 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
 }
 
 // The coders of the chunked host calls (redux_host.hpp).  The transformed copy of a chunk goes in front of the adaptive
-// coder's workspace; a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64.
+// coder's workspace; a chunk is whole 64-block waves, so whole frames of the layout for every element size that divides 64,
+// and the record layout's chunks are rounded up to whole frames of its record size (host::chunk_blocks_framed).
 // The base filter's layout takes the chunk's share of the base from the slot (host::BaseIo).
 static Layout layout_of_slot(Layout L, const host::Slot &s)
 {
@@ -2521,21 +2617,40 @@ static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_si
 }
 
 // the host-pointer calls (redux_host.hpp); base[0 .. base_len): a base filter's base, the chunks take their shares of it
-static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
-                                uint64_t base_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
-                                uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0,
-                                uint32_t order = 0)
+static int encode_blocks_layout(Layout L, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
+                                uint64_t base_len, uint32_t block_size, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                                int32_t *block_status, uint32_t *block_crc)
 {
     int st = check_params(p);
     if (st != REDUX_OK)
         return st;
-    const Layout L{element_size, f, nullptr, 0, lag, order};
     if (L.check() != REDUX_OK || block_size == 0 || !out || !out_offsets || (in_len && !in) ||
         (L.has_base() && base_len && !base))
         return REDUX_INVALID_INPUT;
     const host::EncodeCoder coder = L.identity() ? adaptive_encoder(p, block_size) : layout_encoder(p, block_size, L);
     return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, nullptr, {},
-                               host::BaseIo{base, base_len, L.has_base()});
+                               host::BaseIo{base, base_len, L.has_base()}, {}, L.record);
+}
+
+static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
+                                uint64_t base_len, uint32_t block_size, uint32_t element_size, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_offsets, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0,
+                                uint32_t order = 0)
+{
+    return encode_blocks_layout(Layout{element_size, f, nullptr, 0, lag, order}, p, in, in_len, base, base_len, block_size, out,
+                                out_cap, out_offsets, block_status, block_crc);
+}
+
+static int decode_blocks_layout(Layout L, const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
+                                uint64_t base_len, uint64_t out_len, uint32_t block_size, uint8_t *out, uint32_t *out_sizes,
+                                int32_t *block_status, uint32_t *block_crc)
+{
+    int st = check_params(p);
+    if (st == REDUX_OK && (L.check() != REDUX_OK || (L.has_base() && base_len && !base)))
+        st = REDUX_INVALID_INPUT;
+    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
+                              block_status, nullptr, layout_decoder(p, block_size, L), block_crc, nullptr, {},
+                              host::BaseIo{base, base_len, L.has_base()}, {}, L.record);
 }
 
 static int decode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
@@ -2543,13 +2658,8 @@ static int decode_blocks_layout(Filter f, const redux_params *p, const uint8_t *
                                 uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc, uint32_t lag = 0,
                                 uint32_t order = 0)
 {
-    const Layout L{element_size, f, nullptr, 0, lag, order};
-    int st = check_params(p);
-    if (st == REDUX_OK && (L.check() != REDUX_OK || (L.has_base() && base_len && !base)))
-        st = REDUX_INVALID_INPUT;
-    return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
-                              block_status, nullptr, layout_decoder(p, block_size, L), block_crc, nullptr, {},
-                              host::BaseIo{base, base_len, L.has_base()});
+    return decode_blocks_layout(Layout{element_size, f, nullptr, 0, lag, order}, p, in, in_offsets, base, base_len, out_len, block_size,
+                                out, out_sizes, block_status, block_crc);
 }
 
 // -- byte-plane layout
@@ -2800,6 +2910,81 @@ int redux_decode_blocks_lag_order(const redux_params *p, const uint8_t *in, cons
 {
     return decode_blocks_layout(Filter::LagOrder, p, in, in_offsets, nullptr, 0, out_len, block_size, element_size, out, out_sizes,
                                 block_status, block_crc, lag, order);
+}
+
+// -- record layout (redux_record.hpp): a record size in place of an element size, the byte delta a flag
+int redux_record_check(uint32_t record_size, int delta)
+{
+    return record_size >= 2 && record_size <= REDUX_RECORD_MAX && (delta == 0 || delta == 1) ? REDUX_OK : REDUX_INVALID_INPUT;
+}
+
+int redux_record_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t record_size, int delta,
+                            int inverse, void *stream)
+{
+    return record_transform_dev(d_src, d_dst, len, block_size, record_size, delta, inverse, stream);
+}
+
+uint64_t redux_encode_record_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t record_size)
+{
+    if (redux_record_check(record_size, 0) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_encode_workspace_bytes(p, in_len, block_size);
+    return ws ? planes_copy_bytes(in_len) + ws : 0;
+}
+
+uint64_t redux_decode_record_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t record_size)
+{
+    return redux_record_check(record_size, 0) == REDUX_OK ? redux_decode_planes_workspace_bytes(p, out_len, block_size, 1) : 0;
+}
+
+int redux_encode_record_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t record_size,
+                            int delta, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(record_layout(record_size, delta), p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_record_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len, uint32_t block_size,
+                            uint32_t record_size, int delta, void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(record_layout(record_size, delta), p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_record(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t record_size,
+                               int delta, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                               uint32_t *block_crc)
+{
+    return encode_blocks_layout(record_layout(record_size, delta), p, in, in_len, nullptr, 0, block_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
+}
+
+int redux_decode_blocks_record(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t record_size, int delta, uint8_t *out, uint32_t *out_sizes,
+                               int32_t *block_status, uint32_t *block_crc)
+{
+    return decode_blocks_layout(record_layout(record_size, delta), p, in, in_offsets, nullptr, 0, out_len, block_size, out, out_sizes,
+                                block_status, block_crc);
+}
+
+const char *redux_record_kernel_name_at(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size, uint32_t record_size,
+                                        int inverse)
+{
+    static const char *const names[2][3] = {
+        {"k_record_planes", "k_record_planes + k_record_planes_bytes", "k_record_planes_bytes"},
+        {"k_record_unplanes", "k_record_unplanes + k_record_unplanes_bytes", "k_record_unplanes_bytes"},
+    };
+    if (block_size == 0 || redux_record_check(record_size, 0) != REDUX_OK)
+        return "";
+    const FastSplit f = fast_split(len, (uint64_t)record_size * block_size, block_size, {d_src, d_dst});
+    return names[inverse != 0][f.nfull == 0 ? 2 : f.rest < len ? 1 : 0];
+}
+
+const char *redux_record_kernel_name(uint64_t len, uint32_t block_size, uint32_t record_size, int inverse)
+{
+    return redux_record_kernel_name_at(nullptr, nullptr, len, block_size, record_size, inverse);
 }
 
 // -- XOR-against-base filter
@@ -4395,6 +4580,19 @@ int redux_host_chunk_plan(uint64_t nblocks, uint32_t block_size, uint32_t nconte
     if (nblocks == 0 || block_size == 0 || ncontexts == 0 || ncontexts > 16 || !chunk_blocks || !nchunks)
         return REDUX_INVALID_INPUT;
     *chunk_blocks = host::chunk_blocks_for(nblocks, block_size, decode ? host::kDecChunkMax : host::kEncChunkMax, ncontexts);
+    *nchunks      = (nblocks + *chunk_blocks - 1) / *chunk_blocks;
+    return REDUX_OK;
+}
+
+int redux_host_chunk_plan_record(uint64_t nblocks, uint32_t block_size, uint32_t record_size, uint32_t ncontexts, int decode,
+                                 uint64_t *chunk_blocks, uint64_t *nchunks)
+{
+    if (redux_record_check(record_size, 0) != REDUX_OK)
+        return REDUX_INVALID_INPUT;
+    const int st = redux_host_chunk_plan(nblocks, block_size, ncontexts, decode, chunk_blocks, nchunks);
+    if (st != REDUX_OK)
+        return st;
+    *chunk_blocks = host::chunk_blocks_framed(*chunk_blocks, nblocks, record_size);
     *nchunks      = (nblocks + *chunk_blocks - 1) / *chunk_blocks;
     return REDUX_OK;
 }

@@ -437,6 +437,17 @@ static uint64_t chunk_blocks_for(uint64_t nblocks, uint32_t block_size, uint64_t
     return cb < nblocks ? cb : nblocks;
 }
 
+// cb rounded up to whole frames of frame_blocks blocks, for the layouts whose frames do not divide a 64-block wave (the
+// record layout): a chunk's layout is then its part of the whole input's.  The chunk's last wave may be partly filled,
+// which the coders take.  A frame count that divides cb leaves it as it is.
+static uint64_t chunk_blocks_framed(uint64_t cb, uint64_t nblocks, uint32_t frame_blocks)
+{
+    if (frame_blocks <= 1 || cb >= nblocks)
+        return cb;
+    cb = (cb + frame_blocks - 1) / frame_blocks * frame_blocks;
+    return cb < nblocks ? cb : nblocks;
+}
+
 // ---- what the contexts of one call share ---------------------------------------------------------
 // A call's units are its chunks (redux_encode_blocks ...) or its groups of inputs (the `_v` calls), in block order.  The
 // ledger keeps the call's first error, the first unit with a non-OK block, and -- encode -- where each unit's streams go in
@@ -756,12 +767,14 @@ struct EncodeChunks {
     SegmentTablesIo    tables;    // cum may be null: the segment tables the coder leaves in s.d_tab
     BaseIo             base;      // on: the chunk's share of the base, staged to s.d_base next to its input
     UnitTableIo        units;     // table may be null: the unit table of the mixed layouts, in s.d_stf
+    uint32_t           frame_blocks = 1; // chunks are whole frames of so many blocks (chunk_blocks_framed)
     uint64_t           nblocks = 0, cb = 0, nchunks = 0, max_in = 0, ws_bytes = 0, bound = 0;
 
     int plan(size_t nctx, uint64_t &n)
     {
         nblocks = redux_block_count(in_len, block_size);
         cb      = tables.chunk_blocks(chunk_blocks_for(nblocks, block_size, kEncChunkMax, nctx), nblocks);
+        cb      = chunk_blocks_framed(cb, nblocks, frame_blocks);
         nchunks = n = (nblocks + cb - 1) / cb;
         max_in  = cb * (uint64_t)block_size < in_len ? cb * (uint64_t)block_size : in_len; // bytes of the largest chunk
         coder.size(max_in, nchunks > 1, ws_bytes, bound);
@@ -851,9 +864,11 @@ struct EncodeChunks {
 
 static int encode_blocks(const uint8_t *in, uint64_t in_len, uint32_t block_size, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_offsets, int32_t *block_status, const EncodeCoder &coder, uint32_t *block_crc = nullptr,
-                         uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {}, UnitTableIo units = {})
+                         uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {}, UnitTableIo units = {},
+                         uint32_t frame_blocks = 1)
 {
-    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables, base, units};
+    EncodeChunks op{in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, stored, tables, base, units,
+                    frame_blocks};
     return run_chunks(op);
 }
 
@@ -876,11 +891,13 @@ struct DecodeChunks {
     SegmentTablesIo    tables;    // cum may be null: the segment tables, staged to s.d_tab with the chunk's offsets
     BaseIo             base;      // on: the share of the base that lies next to the chunk's output, staged to s.d_base
     UnitTableIo        units;     // table may be null: the unit table of the mixed layouts, staged to s.d_stf
+    uint32_t           frame_blocks = 1; // chunks are whole frames of so many blocks (chunk_blocks_framed)
     uint64_t           cb = 0, nchunks = 0, ws_bytes = 0, max_in = 0;
 
     int plan(size_t nctx, uint64_t &n)
     {
         cb       = tables.chunk_blocks(chunk_blocks_for(nblocks, block_size, kDecChunkMax, nctx), nblocks);
+        cb       = chunk_blocks_framed(cb, nblocks, frame_blocks);
         nchunks  = n = (nblocks + cb - 1) / cb;
         ws_bytes = coder.workspace(cb);
         for (uint64_t k = 0; k < nchunks; k++) {
@@ -982,10 +999,10 @@ struct DecodeChunks {
 static int decode_blocks(const uint8_t *in, const uint64_t *in_offsets, uint64_t nblocks, uint32_t block_size, uint8_t *out,
                          uint64_t out_len, uint32_t *out_sizes, int32_t *block_status, uint64_t *in_used, const DecodeCoder &coder,
                          uint32_t *block_crc = nullptr, const uint8_t *stored = nullptr, SegmentTablesIo tables = {}, BaseIo base = {},
-                         UnitTableIo units = {})
+                         UnitTableIo units = {}, uint32_t frame_blocks = 1)
 {
     DecodeChunks op{in, in_offsets, nblocks, block_size, out, out_len, out_sizes, block_status, in_used, coder, block_crc, stored, tables,
-                    base, units};
+                    base, units, frame_blocks};
     return run_chunks(op);
 }
 

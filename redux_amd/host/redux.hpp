@@ -17,6 +17,7 @@
 //   redux::hip::compress_blocks_zigzag / decompress_blocks_zigzag   signed series behind the zigzag-folded delta filter
 //   redux::hip::compress_blocks_lag / decompress_blocks_lag         interleaved channels behind the lagged delta filter
 //   redux::hip::compress_blocks_lag_order / decompress_blocks_lag_order   sampled signals behind higher-order lagged differences
+//   redux::hip::compress_blocks_record / decompress_blocks_record   tables of fixed-width structs behind the record layout
 //   redux::hip::compress_blocks_base / decompress_blocks_base       a snapshot behind the XOR-against-base filter
 //   redux::hip::compress_blocks_base_sub / decompress_blocks_base_sub   the same behind the folded difference against the base
 //   redux::hip::compress_blocks_stored / decompress_blocks_stored   stored (raw) blocks for data that does not shrink
@@ -322,6 +323,46 @@ inline std::vector<std::uint8_t> decompress_blocks_lag(const Blocks &streams, st
     std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
     check(redux_decode_blocks_lag(&cp, streams.data.data(), streams.offsets.data(), len, block_size, element_size, lag, out.data(),
                                   sizes.data(), nullptr, nullptr));
+    out.resize(len);
+    return out;
+}
+
+// Tables of fixed-width structs behind the record layout (include/redux_hip.h, "record layout"): every block holds one byte
+// column of block_size records of record_size bytes, 2 <= record_size <= REDUX_RECORD_MAX; `delta`: the byte delta against the
+// record before, in front of the layout.  Opt-in, and the decoder needs the same record size and flag.
+inline Blocks compress_blocks_record(const std::uint8_t *in, std::uint64_t len, std::uint32_t block_size, std::uint32_t record_size,
+                                     bool delta, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_record_check(record_size, delta) != REDUX_OK)
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    Blocks b;
+    const std::uint64_t nb = redux_block_count(len, block_size);
+    b.data.resize(redux_encode_bound(&cp, len, block_size));
+    b.offsets.resize(nb + 1);
+    check(redux_encode_blocks_record(&cp, in, len, block_size, record_size, delta, b.data.data(), b.data.size(), b.offsets.data(),
+                                     nullptr, nullptr));
+    b.data.resize(b.offsets[nb]);
+    return b;
+}
+
+// inverse: the original len bytes
+inline std::vector<std::uint8_t> decompress_blocks_record(const Blocks &streams, std::uint64_t len, std::uint32_t block_size,
+                                                          std::uint32_t record_size, bool delta, const model::Parameters &p)
+{
+    const redux_params cp = p.c_abi();
+    check(redux_device_supports(&cp));
+    if (block_size == 0 || redux_record_check(record_size, delta) != REDUX_OK ||
+        redux_block_count(len, block_size) + 1 != streams.offsets.size() || streams.offsets.back() > streams.data.size())
+        throw Error::from_status(REDUX_INVALID_INPUT);
+    for (std::size_t i = 1; i < streams.offsets.size(); i++)
+        if (streams.offsets[i] < streams.offsets[i - 1])
+            throw Error::from_status(REDUX_INVALID_INPUT);
+    std::vector<std::uint8_t> out(len ? len : 1);
+    std::vector<std::uint32_t> sizes(streams.offsets.size() - 1);
+    check(redux_decode_blocks_record(&cp, streams.data.data(), streams.offsets.data(), len, block_size, record_size, delta, out.data(),
+                                     sizes.data(), nullptr, nullptr));
     out.resize(len);
     return out;
 }

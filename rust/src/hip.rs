@@ -85,6 +85,13 @@ extern "C" {
     fn redux_decode_blocks_lag_order(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                      block_size: u32, element_size: u32, lag: u32, order: u32, out: *mut u8,
                                      out_sizes: *mut u32, block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // record layout for fixed-width structs: the lag calls' shape with (record size, delta flag) in place of (element size, lag)
+    fn redux_encode_blocks_record(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, record_size: u32,
+                                  delta: c_int, out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32,
+                                  block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_record(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                  block_size: u32, record_size: u32, delta: c_int, out: *mut u8, out_sizes: *mut u32,
+                                  block_status: *mut i32, block_crc: *mut u32) -> c_int;
     // XOR-against-base filter for series of snapshots, in front of the byte-plane layout (base null only with base_len 0;
     // block_crc may be null)
     fn redux_encode_blocks_base(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
@@ -558,6 +565,53 @@ pub fn decompress_blocks_lag_order(streams: &[u8], offsets: &[u64], len: u64, bl
         try!(status(redux_decode_blocks_lag_order(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, element_size, lag,
                                                   order, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
                                                   ptr::null_mut())));
+        out.truncate(len as usize);
+        Ok(out)
+    }
+}
+
+/// `compress_blocks` behind the record layout for fixed-width structs (include/redux_hip.h, "record layout"): every block
+/// holds one byte column of `block_size` records of `record_size` bytes, 2 to 256; `delta`: the byte delta against the
+/// record before.  Opt-in.
+pub fn compress_blocks_record(data: &[u8], block_size: u32, record_size: u32, delta: bool,
+                              p: &Parameters) -> Result<(Vec<u8>, Vec<u64>)> {
+    if block_size == 0 {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(data.len() as u64, block_size) as usize;
+        let cap = redux_encode_bound(&cp, data.len() as u64, block_size) as usize;
+        let mut out = vec![0u8; cap];
+        let mut offs = vec![0u64; nb + 1];
+        try!(status(redux_encode_blocks_record(&cp, data.as_ptr(), data.len() as u64, block_size, record_size, delta as c_int,
+                                               out.as_mut_ptr(), cap as u64, offs.as_mut_ptr(), ptr::null_mut(),
+                                               ptr::null_mut())));
+        out.truncate(offs[nb] as usize);
+        Ok((out, offs))
+    }
+}
+
+/// Inverse of `compress_blocks_record` with the same `record_size` and `delta`: `len` is the original byte count; returns
+/// the original bytes.
+pub fn decompress_blocks_record(streams: &[u8], offsets: &[u64], len: u64, block_size: u32, record_size: u32, delta: bool,
+                                p: &Parameters) -> Result<Vec<u8>> {
+    if block_size == 0 || offsets.is_empty() || offsets[offsets.len() - 1] as usize > streams.len() {
+        return Err(Error::InvalidInput);
+    }
+    let cp = c_params(p);
+    unsafe {
+        try!(status(redux_device_supports(&cp)));
+        let nb = redux_block_count(len, block_size) as usize;
+        if nb + 1 != offsets.len() {
+            return Err(Error::InvalidInput);
+        }
+        let mut out = vec![0u8; std::cmp::max(len as usize, 1)];
+        let mut sizes = vec![0u32; nb];
+        try!(status(redux_decode_blocks_record(&cp, streams.as_ptr(), offsets.as_ptr(), len, block_size, record_size,
+                                               delta as c_int, out.as_mut_ptr(), sizes.as_mut_ptr(), ptr::null_mut(),
+                                               ptr::null_mut())));
         out.truncate(len as usize);
         Ok(out)
     }
