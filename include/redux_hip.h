@@ -583,7 +583,13 @@ int redux_decode_blocks_lag_order(const redux_params *p, const uint8_t *in, cons
  * redux_host_chunk_plan_record   redux_host_chunk_plan for these calls: the chunk a multiple of record_size blocks.
  * redux_record_kernel_name       the kernels redux_record_planes_dev runs on 16-byte aligned buffers, joined by " + " when
  *                                full frames are followed by a short one; "" for arguments the call refuses.
- * redux_record_kernel_name_at    the same for these buffers, which contribute their alignment only. */
+ * redux_record_kernel_name_at    the same for these buffers, which contribute their alignment only.
+ * redux_record_plan              the shape of that launch on 16-byte aligned buffers, from the function the launch itself
+ *                                takes it from; nothing is launched.  plan: four values, plan[0] = lgT (the fast kernel's tile is 1 << lgT
+ *                                records), plan[1] = PC (the inverse's byte columns per workgroup: record_size, or a multiple
+ *                                of 16 that is at least 64), plan[2] = the fast kernel's grid, plan[3] = the byte kernel's
+ *                                grid; a grid of 0: that kernel does not run.  cus: the CU count to plan for, 0 for the
+ *                                current device's.  REDUX_INVALID_INPUT for arguments the call refuses. */
 #define REDUX_RECORD_MAX 256
 int      redux_record_check(uint32_t record_size, int delta);
 int      redux_record_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t record_size, int delta,
@@ -609,6 +615,8 @@ int redux_host_chunk_plan_record(uint64_t nblocks, uint32_t block_size, uint32_t
 const char *redux_record_kernel_name(uint64_t len, uint32_t block_size, uint32_t record_size, int inverse);
 const char *redux_record_kernel_name_at(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size,
                                         uint32_t record_size, int inverse);
+int redux_record_plan(uint64_t len, uint32_t block_size, uint32_t record_size, int delta, int inverse, uint32_t cus,
+                      uint32_t *plan);
 
 /* ---- XOR-against-base filter for series of snapshots -------------------------------------------
  * A snapshot of tensors that were stored before -- checkpoint N against checkpoint N - 1, a fine-tuned model against its

@@ -18,6 +18,6 @@ from .api import (  # noqa: F401
     mixed_units, choose_unit_layouts, mixed_layout,
     lag_cost, estimate_lags, choose_lag,
     lag_order_cost, estimate_lag_orders, choose_lag_order,
-    record_planes, record_kernel_name, RECORD_MAX,
+    record_planes, record_kernel_name, record_plan, RECORD_MAX,
     range_plan, segment_copy, segment_tiles, SEGMENT_DTYPE,
 )

@@ -245,6 +245,7 @@ SIGNATURES.update({
     "redux_host_chunk_plan_record": (C.c_int, [_U64, _U32, _U32, _U32, C.c_int, C.POINTER(_U64), C.POINTER(_U64)]),
     "redux_record_kernel_name": (C.c_char_p, [_U64, _U32, _U32, C.c_int]),
     "redux_record_kernel_name_at": (C.c_char_p, [_V, _V, _U64, _U32, _U32, C.c_int]),
+    "redux_record_plan": (C.c_int, [_U64, _U32, _U32, C.c_int, C.c_int, _U32, C.POINTER(_U32)]),
 })
 
 _LIB = None

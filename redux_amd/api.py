@@ -1914,6 +1914,18 @@ def record_kernel_name(nbytes, block_size, record_size, inverse=False, d_src=Non
                                          1 if inverse else 0).decode()
 
 
+RecordPlan = namedtuple("RecordPlan", "lgT PC grid_fast grid_bytes")
+
+
+def record_plan(nbytes, block_size, record_size, delta=False, inverse=False, cus=0):
+    """The shape record_planes launches with for nbytes bytes on 16-byte aligned buffers (redux_record_plan; nothing is
+    launched) -> RecordPlan(lgT, PC, grid_fast, grid_bytes): the fast kernel's tile is 1 << lgT records, PC the inverse's byte
+    columns per workgroup, a grid of 0 a kernel that does not run.  cus: the CU count to plan for, 0: the current device's."""
+    plan = (C.c_uint32 * 4)()
+    _raise(_lib.lib().redux_record_plan(nbytes, block_size, record_size, 1 if delta else 0, 1 if inverse else 0, cus, plan))
+    return RecordPlan(*plan)
+
+
 def _device_unit_table(torch, table, nunits, device):
     """a unit table for a device call: a uint8 device tensor is taken as it is, host values (np.uint8, a list) are uploaded;
     InvalidInput unless it has nunits entries.  Entries are taken & 7 on the device."""

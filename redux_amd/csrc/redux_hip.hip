@@ -699,11 +699,43 @@ static uint32_t record_lg_tile(uint32_t row, uint32_t items_row, uint32_t block_
     return lg;
 }
 
+// The shape of a record launch, decided here alone: launch_record launches what it says and redux_record_plan reports it.
+// grid_fast / grid_rest are 0 where that kernel does not run.
+struct RecordPlan {
+    FastSplit f;
+    uint32_t  lgT, PC, grid_fast, grid_rest;
+};
+
+static RecordPlan record_plan(const FastSplit &f, uint64_t len, uint32_t block_size, uint32_t R, bool delta, bool inverse, uint64_t cus)
+{
+    const uint64_t frame = (uint64_t)R * block_size;
+    RecordPlan     p{f, 4, R, 0, 0};
+    if (f.nfull) {
+        if (inverse) {
+            if (f.nfull < 2 * cus && R > 64) { // few frames: ranges of columns, 16-byte multiples of at least 64
+                const uint64_t want = (2 * cus + f.nfull - 1) / f.nfull;
+                const uint32_t pc   = (uint32_t)(((R + want - 1) / want + 15) / 16 * 16);
+                p.PC = pc < 64 ? 64 : pc;
+            }
+            const uint32_t nr = (R + p.PC - 1) / p.PC;
+            p.lgT       = record_lg_tile(nr > 1 ? p.PC : R, p.PC < R ? p.PC : R, block_size);
+            p.grid_fast = (uint32_t)std::min<uint64_t>(f.nfull, 8 * cus) * nr;
+        } else {
+            p.lgT = record_lg_tile(R, 0, block_size);
+            const uint64_t tiles = f.nfull * ((block_size + (1u << p.lgT) - 1) >> p.lgT);
+            p.grid_fast = (uint32_t)std::min<uint64_t>(tiles, 8 * cus);
+        }
+    }
+    if (f.rest < len) // the short last frame, or everything the fast kernels cannot take
+        p.grid_rest = grid_bytes(inverse && delta ? (len - f.rest + frame - 1) / frame * R : len - f.rest);
+    return p;
+}
+
 static int launch_record(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t R, bool delta, bool inverse,
                          hipStream_t s)
 {
-    const uint64_t  frame = (uint64_t)R * block_size;
-    const FastSplit f = fast_split(len, frame, block_size, {d_src, d_dst});
+    const FastSplit  f = fast_split(len, (uint64_t)R * block_size, block_size, {d_src, d_dst});
+    const RecordPlan p = record_plan(f, len, block_size, R, delta, inverse, f.nfull ? cu_count() : 0);
     RecordArgs a;
     a.src        = (const uint8_t *)d_src;
     a.dst        = (uint8_t *)d_dst;
@@ -711,32 +743,21 @@ static int launch_record(const void *d_src, void *d_dst, uint64_t len, uint32_t 
     a.block_size = block_size;
     a.R          = R;
     a.delta      = delta;
-    a.lgT        = 4;
-    a.PC         = R;
+    a.lgT        = p.lgT;
+    a.PC         = p.PC;
     a.first      = f.rest;
     a.len        = len;
-    if (f.nfull) {
-        const uint64_t cus = cu_count();
-        if (inverse) {
-            if (f.nfull < 2 * cus && R > 64) { // few frames: ranges of columns, 16-byte multiples of at least 64
-                const uint64_t want = (2 * cus + f.nfull - 1) / f.nfull;
-                const uint32_t pc   = (uint32_t)(((R + want - 1) / want + 15) / 16 * 16);
-                a.PC = pc < 64 ? 64 : pc;
-            }
-            const uint32_t nr = (R + a.PC - 1) / a.PC;
-            a.lgT = record_lg_tile(nr > 1 ? a.PC : R, a.PC < R ? a.PC : R, block_size);
-            k_record_unplanes<<<(uint32_t)std::min<uint64_t>(f.nfull, 8 * cus) * nr, 256, 0, s>>>(a);
-        } else {
-            a.lgT = record_lg_tile(R, 0, block_size);
-            const uint64_t tiles = f.nfull * ((block_size + (1u << a.lgT) - 1) >> a.lgT);
-            k_record_planes<<<(uint32_t)std::min<uint64_t>(tiles, 8 * cus), 256, 0, s>>>(a);
-        }
-    }
-    if (f.rest < len) { // the short last frame, or everything the fast kernels cannot take
+    if (p.grid_fast) {
         if (inverse)
-            k_record_unplanes_bytes<<<grid_bytes(delta ? (len - f.rest + frame - 1) / frame * R : len - f.rest), 256, 0, s>>>(a);
+            k_record_unplanes<<<p.grid_fast, 256, 0, s>>>(a);
         else
-            k_record_planes_bytes<<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
+            k_record_planes<<<p.grid_fast, 256, 0, s>>>(a);
+    }
+    if (p.grid_rest) {
+        if (inverse)
+            k_record_unplanes_bytes<<<p.grid_rest, 256, 0, s>>>(a);
+        else
+            k_record_planes_bytes<<<p.grid_rest, 256, 0, s>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -2985,6 +3006,19 @@ const char *redux_record_kernel_name_at(const void *d_src, const void *d_dst, ui
 const char *redux_record_kernel_name(uint64_t len, uint32_t block_size, uint32_t record_size, int inverse)
 {
     return redux_record_kernel_name_at(nullptr, nullptr, len, block_size, record_size, inverse);
+}
+
+int redux_record_plan(uint64_t len, uint32_t block_size, uint32_t record_size, int delta, int inverse, uint32_t cus, uint32_t *plan)
+{
+    if (block_size == 0 || redux_record_check(record_size, delta) != REDUX_OK || !plan)
+        return REDUX_INVALID_INPUT;
+    const FastSplit  f = fast_split(len, (uint64_t)record_size * block_size, block_size, {});
+    const RecordPlan p = record_plan(f, len, block_size, record_size, delta != 0, inverse != 0, cus ? cus : cu_count());
+    plan[0] = p.lgT;
+    plan[1] = p.PC;
+    plan[2] = p.grid_fast;
+    plan[3] = p.grid_rest;
+    return REDUX_OK;
 }
 
 // -- XOR-against-base filter

@@ -1,6 +1,7 @@
 """Every layer in front of the adaptive coder on every coder instance below it (tests/test_layered_instances_gpu.py): the
 CPU side.  The layers: byte planes, the delta filter and stored blocks; then constant blocks, the mixed layouts and the
-zigzag, lag, base XOR and base folded-difference filters; then the higher-order lagged differences (lag order).
+zigzag, lag, base XOR and base folded-difference filters; then the higher-order lagged differences (lag order); then the
+record layout for fixed-width structs.
 
 Each layer's `_dev` calls are a few lines in front of encode_slots_impl / redux_encode_blocks_dev, and their decode calls
 in front of decode_blocks_dev_impl; what can go wrong is in the seams: which buffer the coder and the compaction read (the
@@ -23,6 +24,8 @@ table form, planned for nblocks * block_size bytes.  Here, without a GPU:
                                                                                                  base as const, once longer than x
         lag_order                    8 (FILTER_WHYS)                               1, 2, 4, 8    the same lags; order 2, 3, 3, 2, 3, 2, 2, 3:
                                                                                                  both orders at every element size
+        record                       8 (FILTER_WHYS)                               (record size) R = the eight lags by turn in place of E; the byte delta
+                                                                                                 off, off, on, on, ...: both at odd and even R
   * the table covers, per layer, every reason: removing a row fails test_the_table_covers_every_reason, which compares
     ROWS with a list written out per layer and asserts the encoders, decoders, element sizes, lags and kinds of base reached;
   * the table form of the decoders never names k_decode_cells<8> (redux_decode_kernel_name_table);
@@ -46,8 +49,9 @@ from test_stream_ranges_cpu import ANY, CELLS8, CELLS8_FIX, GENERIC32, LOCK, WAV
 PLANES, DELTA, STORED = "planes", "delta", "stored"
 CONST, MIXED, ZIGZAG, LAG, BASE, BASE_SUB = "const", "mixed", "zigzag", "lag", "base", "base_sub"
 LAG_ORDER = "lag_order"                                   # (the infix of redux_encode_lag_order_workspace_bytes)
+RECORD = "record"                                         # the record layout: a row's "E" is the record size, a frame E blocks
 FIRST_LAYERS = (PLANES, DELTA, STORED)
-FILTERS = (ZIGZAG, LAG, BASE, BASE_SUB, LAG_ORDER)        # the filters of layout_stage / layout_decode_tail behind delta
+FILTERS = (ZIGZAG, LAG, BASE, BASE_SUB, LAG_ORDER, RECORD)  # the filters of layout_stage / layout_decode_tail behind delta
 WITH_LAG = (LAG, LAG_ORDER)                               # the calls that take a lag (the lag order: and an order behind it)
 WITH_BASE = (CONST, BASE, BASE_SUB)                       # the calls that take (d_base, base_len)
 LAYERS = FIRST_LAYERS + (CONST, MIXED) + FILTERS
@@ -120,17 +124,21 @@ FILTER_WHYS = ["coop_whole_cb16", "coop_windows_150k", "pair_by_blocks_cb32", "p
                "single32_by_workspace", "gen_9_to_12", "cells8_fix"]
 LATER_WHYS = {CONST: _STORED_WHYS, MIXED: MIXED_WHYS, **{f: FILTER_WHYS for f in FILTERS}}
 MIXED_UNIT = 8                                             # REDUX_MIXED_UNIT_BLOCKS: a mixed row's "E" is the unit, in blocks
-ELEMENT.update({CONST: (1, 2, 4, 8), MIXED: (MIXED_UNIT,), **{f: (1, 2, 4, 8) for f in FILTERS}})
 LAGS = (3, 2, 17, 256, 5, 64, 255, 16)                     # by turn, from the first row of the lag filter on
+ELEMENT.update({CONST: (1, 2, 4, 8), MIXED: (MIXED_UNIT,), **{f: (1, 2, 4, 8) for f in FILTERS}, RECORD: LAGS})  # (record sizes)
 ORDERS = (2, 3, 3, 2, 3, 2, 2, 3)                          # by turn: with E = 1, 2, 4, 8 by turn every element size meets both
 # the base of a row, by turn: none (base_len 0), as long as the input, ending inside a frame at an odd byte; and one row
 # of each base filter with a base longer than the input
 BASE_KINDS = ("none", "full", "inside")
 PINNED.update({(CONST, "single16_by_alignment"): (1, 4),   # E = 1 without a base: the caller's buffer, 4 bytes off
                (CONST, "pair_by_blocks_cb32"): (1, 4)})    # ... the same shape WITH a base reads the copy: the pair kernel
+# the record layout: a row's "E" is its record size (LAGS by turn); these two keep their buffers aligned, so that the fast kernels
+# run the tiles of 63 groups in column ranges (R = 256, B = 1008) and the 147 tiles a frame of B = 150,000
+PINNED.update({(RECORD, "pair_below_coop_min"): (256, 0), (RECORD, "cells8_fix"): (16, 0)})
 PINNED_BASE = {(CONST, "single16_by_alignment"): "none", (CONST, "pair_by_blocks_cb32"): "full",
                (BASE, "single32_by_workspace"): "longer", (BASE_SUB, "single32_by_workspace"): "longer"}
-# id -> (lag or None, kind of base or None, order or None)
+# id -> (lag or None, kind of base or None, order or None, the record layout's delta flag or None).  The flag alternates every
+# two rows, so that the odd and the even record sizes (which alternate row by row) each meet both values
 EXTRA = {}
 for _layer in (CONST, MIXED) + FILTERS:
     for _turn, _why in enumerate(LATER_WHYS[_layer]):
@@ -139,10 +147,11 @@ for _layer in (CONST, MIXED) + FILTERS:
         _base = PINNED_BASE.get((_layer, _why), BASE_KINDS[_turn % 3]) if _layer in WITH_BASE else None
         if _layer == CONST and _E == 1 and _base == "none" and (_layer, _why) not in PINNED:
             _off = 0                                       # (as for stored: the caller's buffer is what the coder reads)
-        _id = f"{_layer}_{_why}" if _layer == MIXED else f"{_layer}_e{_E}_{_why}"
+        _id = f"{_layer}_{_why}" if _layer == MIXED else f"{_layer}_r{_E}_{_why}" if _layer == RECORD else f"{_layer}_e{_E}_{_why}"
         ROWS[_id] = (_layer, _p, _E, _bs, _nb, _off, _ws, _enc, _dec_t if _layer == CONST else _dec, _why)
         EXTRA[_id] = (LAGS[_turn % len(LAGS)] if _layer in WITH_LAG else None, _base,
-                      ORDERS[_turn % len(ORDERS)] if _layer == LAG_ORDER else None)
+                      ORDERS[_turn % len(ORDERS)] if _layer == LAG_ORDER else None,
+                      bool(_turn // 2 % 2) if _layer == RECORD else None)
 
 
 def base_len_of(kind, in_len, E, bs):
@@ -244,7 +253,7 @@ def layer_dec_name(layer, params, bs, nb):
 @pytest.mark.parametrize("key", sorted(ROWS))
 def test_every_row_maps_to_its_instances(key):
     layer, params, E, bs, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base, order = EXTRA.get(key, (None, None, None))
+    lag, base, order, delta = EXTRA.get(key, (None, None, None, None))
     in_len = input_len(params, bs, nb)
     L = _lib()
     plain = L.lib().redux_encode_workspace_bytes(C.byref(L.Params(*params)), coded_len(layer, bs, in_len), bs)
@@ -261,7 +270,8 @@ def test_every_row_maps_to_its_instances(key):
     elif layer == MIXED:   # the copy and the cost rows f64[8][nblocks]
         assert copy == copy_bytes(DELTA, params, 1, bs, in_len) + (nb * 64 + 255) // 256 * 256
     else:                  # the filters: always a copy, of the planes call's size; lag, zigzag, base at E = 1 are no identity
-        assert copy == copy_bytes(DELTA, params, E, bs, in_len) >= in_len
+        assert copy == copy_bytes(DELTA, params, 1 if layer == RECORD else E, bs, in_len) >= in_len   # (no element size there)
+    assert (delta in (False, True) and 2 <= E <= 256 and in_len > E * bs) if layer == RECORD else delta is None
     if layer in WITH_BASE:
         n = base_len_of(base, in_len, E, bs)
         assert {"none": n == 0, "full": n == in_len, "longer": n > in_len,
@@ -295,25 +305,54 @@ _FILTER = ["coop_whole_cb16", "coop_windows_150k", "pair_by_blocks_cb32", "pair_
 WANT_ROWS = {PLANES: _TYPED, DELTA: _TYPED, STORED: _TABLE, CONST: _TABLE,
              MIXED: ["coop_whole_cb32", "coop_windows_100k", "pair_by_blocks_cb32", "pair_by_workspace", "single16_by_block_size",
                      "single32_by_workspace", "cells8"],
-             ZIGZAG: _FILTER, LAG: _FILTER, BASE: _FILTER, BASE_SUB: _FILTER, LAG_ORDER: _FILTER}
-WANT_COUNT = {PLANES: 16, DELTA: 16, STORED: 12, CONST: 12, MIXED: 7, ZIGZAG: 8, LAG: 8, BASE: 8, BASE_SUB: 8, LAG_ORDER: 8}
+             ZIGZAG: _FILTER, LAG: _FILTER, BASE: _FILTER, BASE_SUB: _FILTER, LAG_ORDER: _FILTER, RECORD: _FILTER}
+WANT_COUNT = {PLANES: 16, DELTA: 16, STORED: 12, CONST: 12, MIXED: 7, ZIGZAG: 8, LAG: 8, BASE: 8, BASE_SUB: 8, LAG_ORDER: 8, RECORD: 8}
+# the record layout's rows, written out: (record size, delta flag, block size) by reason
+WANT_RECORD = {"coop_whole_cb16": (3, False, BS64), "coop_windows_150k": (2, False, 150_000), "pair_by_blocks_cb32": (17, True, 4096),
+               "pair_below_coop_min": (256, True, 1008), "single16_by_block_size": (5, False, 65528),
+               "single32_by_workspace": (64, False, 65552), "gen_9_to_12": (255, True, 4000), "cells8_fix": (16, True, 150_000)}
 # the 95 rows the table held before the lag order came: none of their ids may change (CRC-32 of the sorted ids, one a line)
 OLD_IDS, OLD_IDS_CRC = 95, 1587991626
 
 
 def test_the_table_covers_every_reason():
     """Per layer every reason of WANT_ROWS, once (16 + 16 + 12 rows of the first layers, 12 + 7 + 4 * 8 of the later ones, 8
-    of the lag order); and per layer every instance, element size, lag, order and kind of base."""
+    of the lag order, 8 of the record layout); and per layer every instance, element size, lag, order and kind of base, and
+    for the record layout every record size and both delta flags."""
     got = sorted((r[0], r[9]) for r in ROWS.values())
     want = sorted((layer, why) for layer in LAYERS for why in WANT_ROWS[layer])
-    assert got == want and len(ROWS) == len(want) == 44 + 12 + 7 + 32 + 8 == 103
+    assert got == want and len(ROWS) == len(want) == 44 + 12 + 7 + 32 + 8 + 8 == 111
     # the 95 rows from before the lag order keep their ids (the checksum is of the sorted ids as they stood then) and lead the
-    # table; the new ids are the lag order's alone
-    old = sorted(k for k, r in ROWS.items() if r[0] != LAG_ORDER)
+    # table; the new ids are the lag order's and, behind them, the record layout's
+    old = sorted(k for k, r in ROWS.items() if r[0] not in (LAG_ORDER, RECORD))
     assert len(old) == OLD_IDS and zlib.crc32("\n".join(old).encode()) == OLD_IDS_CRC and set(old) <= set(ROWS)
     assert sorted(list(ROWS)[:OLD_IDS]) == old
-    assert sorted(set(ROWS) - set(old)) == sorted(f"lag_order_e{(1, 2, 4, 8)[t % 4]}_{why}" for t, why in enumerate(FILTER_WHYS))
-    assert all(len(x) == 3 for x in EXTRA.values())
+    assert list(ROWS)[OLD_IDS:] == [f"lag_order_e{(1, 2, 4, 8)[t % 4]}_{why}" for t, why in enumerate(FILTER_WHYS)] + \
+        [f"record_r{R}_{why}" for why, (R, _, _) in WANT_RECORD.items()]
+    assert all(len(x) == 4 for x in EXTRA.values())
+    # the record layout: the rows written out in WANT_RECORD, the eight record sizes once each, both flags at odd and even sizes,
+    # the byte path, tiles of 63 groups, general 10-bit symbols; no other layer carries the flag
+    assert {r[9]: (r[2], EXTRA[k][3], r[3]) for k, r in ROWS.items() if r[0] == RECORD} == WANT_RECORD
+    assert sorted(R for R, _, _ in WANT_RECORD.values()) == sorted(LAGS)
+    assert {(R % 2, d) for R, d, _ in WANT_RECORD.values()} == {(o, d) for o in (0, 1) for d in (False, True)}
+    assert {bs % 16 for _, _, bs in WANT_RECORD.values()} == {0, 8} and WANT_RECORD["pair_below_coop_min"][2] // 16 == 63
+    assert ROWS["record_r255_gen_9_to_12"][1] == GEN_HI and all(reads_copy(RECORD, R) for R in LAGS)
+    assert all(x[3] is None for k, x in EXTRA.items() if ROWS[k][0] != RECORD)
+    # ... and which transform kernels a row's encode (caller's buffer -> workspace) and decode (workspace -> caller's buffer) run
+    names = {}
+    for k, r in ROWS.items():
+        if r[0] == RECORD:
+            n = input_len(r[1], r[3], r[4])
+            names[r[9]] = tuple(_lib().lib().redux_record_kernel_name_at(*((4096, 8192 + r[5]) if inv else (8192 + r[5], 4096)), n, r[3], r[2],
+                                                                         inv).decode().replace("k_record_", "") for inv in (0, 1))
+    fast, byte = ("planes + planes_bytes", "unplanes + unplanes_bytes"), ("planes_bytes", "unplanes_bytes")
+    assert names == {"coop_whole_cb16": fast, "coop_windows_150k": byte, "pair_by_blocks_cb32": fast, "pair_below_coop_min": fast,
+                     "single16_by_block_size": byte, "single32_by_workspace": byte, "gen_9_to_12": fast, "cells8_fix": fast}
+    from redux_amd import api
+    _, p, R, bs, nb, *_ = ROWS["record_r256_pair_below_coop_min"]     # one frame: column ranges of 64, tiles of 512 and of 31 groups
+    assert api.record_plan(input_len(p, bs, nb), bs, R, True, True, 256)[:2] == (9, 64) and bs % 512 // 16 == 31
+    _, p, R, bs, nb, *_ = ROWS["record_r16_cells8_fix"]
+    assert api.record_plan(input_len(p, bs, nb), bs, R, True, True, 256)[:2] == (10, 16) and -(-bs // 1024) == 147 and bs % 1024 // 16 == 31
     assert {layer: sum(r[0] == layer for r in ROWS.values()) for layer in LAYERS} == WANT_COUNT
     assert sorted(EXTRA) == sorted(k for k, r in ROWS.items() if r[0] not in FIRST_LAYERS)
     common_enc = set(PAIR.values()) | set(COOP.values()) | {SINGLE16, SINGLE32}
@@ -522,6 +561,14 @@ def audit_rows():
     for layer in (ZIGZAG, LAG, BASE_SUB, LAG_ORDER):
         for E in (1, 2, 4, 8):
             rows.append(row(layer, "test_device_encoder_decoder_roundtrip_and_ranges", P32, E, 4096, 4 * E + 4))
+    # the record layout (tests/test_record_gpu.py): "E" is the record size; 4096-byte blocks throughout
+    for R in (3, 23):
+        rows.append(row(RECORD, "test_streams_equal_oracle_on_transformed_bytes", P32, R, 4096, 2 * R + -(-(1000 * R + 2) // 4096)))
+    rows.append(row(RECORD, "test_host_pipeline_over_several_chunks", P32, 23, 4096, 280))
+    rows.append(row(RECORD, "test_host_pipeline_over_several_chunks", P32, 23, 4096, 69, "tight"))
+    rows.append(row(RECORD, "test_damaged_stream_stays_in_bounds_and_spares_other_frames", P32, 3, 4096, 13))
+    rows.append(row(RECORD, "test_device_encoder_decoder_roundtrip_and_ranges", P32, 23, 4096, 3 * 23 + 4))
+    rows.append(row(RECORD, "test_container_and_cli_end_to_end", P32, 23, 4096, 2 * 23 + 4))
     for bs, E, nb in ((4096, 2, 389), (4096, 4, 389), (BS64, 1, 70), (BS64, 2, 70)):
         rows.append(row(BASE, "test_encode_base_dev_equals_planes_call_on_xored_input_and_the_oracle", P32, E, bs, nb))
     rows.append(row(BASE, "test_device_coder_objects_with_a_base", P32, 4, 4096, 71))
@@ -535,8 +582,8 @@ def test_audit_of_the_older_layer_tests():
     (and one cell decoder); nothing above 64 KiB.  The later layers the same: constant blocks add the pair kernel and
     k_encode<true, false> at 48- and 1008-byte blocks, in launches of at most 45 blocks (less than one wave's 64 table
     entries), one of 71 and one of 300 without a constant block; code_bits 32 everywhere but for two filters' 4 to 20
-    blocks at 16.  The lag order: the small-grid encoder (the pair kernel in the one chunked host call) and
-    k_decode_lock<true> in every one of its tests."""
+    blocks at 16.  The lag order and the record layout: the small-grid encoder (the pair kernel in the one chunked host call)
+    and k_decode_lock<true> in every one of their tests."""
     rows = audit_rows()
     for r in rows:
         print("%-8s %-52s %-52s %-44s %s" % (r[0], r[1][:52], r[2], r[3], r[4]))
@@ -557,5 +604,6 @@ def test_audit_of_the_older_layer_tests():
     full = [r for r in later if not r[3].startswith("k_coop") and "chunked" not in r[2]]
     assert {r[0] for r in full} == {CONST, MIXED} and all(" of 48" in r[2] or " of 100" in r[2] for r in full)
     assert {r[4] for r in later if r[0] in (CONST, MIXED, LAG, BASE)} == {"k_decode_lock<true>"}
-    assert {(r[3], r[4], "chunked" in r[2]) for r in rows if r[0] == LAG_ORDER} == {
-        ("k_coop_model + k_coop_chain<true>", "k_decode_lock<true>", False), ("k_encode_pair<false, true>", "k_decode_lock<true>", True)}
+    for layer in (LAG_ORDER, RECORD):  # (the record layout: (8, 30, 32) at B = 4096 and at most 280 blocks, the same two)
+        assert {(r[3], r[4], "chunked" in r[2]) for r in rows if r[0] == layer} == {
+            ("k_coop_model + k_coop_chain<true>", "k_decode_lock<true>", False), ("k_encode_pair<false, true>", "k_decode_lock<true>", True)}

@@ -1,13 +1,14 @@
 """Every layer in front of the adaptive coder on every coder instance below it (the table:
 tests/test_layered_instances_cpu.py): byte planes, the delta filter and stored blocks; constant blocks, the mixed layouts,
-the zigzag, lag, base XOR and base folded-difference filters, and the lag order (higher-order lagged differences).
+the zigzag, lag, base XOR and base folded-difference filters, the lag order (higher-order lagged differences) and the record
+layout for fixed-width structs (a row's E is then the record size and a frame E blocks).
 
 One launch per row of ROWS, through the `_dev` calls.  A case first asserts, by name, that the coder below the wrapper runs
 the encode and decode instance the row promises, for the very pointer, length and workspace of the launch.  The input is
 tiled on the device from a few distinct FRAMES (E blocks of typed data; frames are independent under every layer; a unit
 of 8 blocks under the mixed layouts) and ends in a ragged frame whose last block has an odd length; every distinct block
 of the numpy restatement of the transform (planes_ref, delta_planes_ref, zigzag_planes_ref, lag_planes_ref,
-base_planes_ref + pad, base_sub_planes_ref, mixed_ref) is coded once by the oracle.  Checked for EVERY block of every
+base_planes_ref + pad, base_sub_planes_ref, mixed_ref, record_ref) is coded once by the oracle.  Checked for EVERY block of every
 launch (the count is the row's block count: 389, 1,093 or 2,565): offsets, statuses, the summary, the flags of stored and
 constant blocks, the stream bytes against the oracle's (a stored block: its transformed bytes; a constant block: its one
 byte); then the decode of the device's own output equals the input byte for byte and the sizes are the layout's.  Input,
@@ -34,6 +35,9 @@ test_stream_ranges_gpu's own cannot).
   * lag_order: test_lag_order_cpu's interleaved tones (two frames) and test_lag_cpu's walks (one), as many channels as the
     lag where that is <= 8, against lag_order_planes_ref; asserted from the reference before any device call: the
     transformed bytes of every frame are neither the input's nor lag_planes_ref's (the order reaches the kernel).
+  * record: packed records of R bytes whose columns are by turn a counter, a slowly moving value, noise and a constant,
+    three distinct frames of R blocks; the byte delta on or off as the row says; asserted from the reference before any
+    device call: the transformed bytes of every frame are not the input's, and those with the delta not those without.
   * one expected byte (constant blocks: also one flag) made wrong on the reference side fails the row of every later layer
     with a message that names the block and the unit.
 Then: the host-pointer forms with CRCs in at least three chunks against the `_dev` result (constant blocks on the caller's
@@ -42,7 +46,8 @@ lag kernels (S = 3, 255, 256) at block sizes whose frames end inside a wave's tu
 byte lag inverse past 2^20 frames (more frames than workgroups: what a workgroup keeps in LDS from frame to frame); the lag
 kernels at one frame of 1025 rows; k_const_select past its grid cap; damaged streams on the table forms of k_decode_wave and
 k_decode<false, true> and under planes / delta on k_decode_cells<8>.
-Left out: damaged streams under the later layers but for one lag-order row on k_decode_wave with the fix-up pass (the
+Left out: damaged streams under the later layers but for one lag-order row and one record row on k_decode_wave with the
+fix-up pass (the
 decoders' table forms are covered under stored, k_const_fill's refusals in test_const_gpu.py, and the filters share
 layout_decode_tail with delta).  The lag-order kernels with several frames per wave and per workgroup: test_lag_order_gpu.py."""
 import ctypes as C
@@ -59,12 +64,13 @@ from test_const_cpu import const_ref
 from test_delta_cpu import delta_planes_ref, sorted_i32, timestamps_i64, tones_i16
 from test_lag_cpu import channels, lag_planes_ref
 from test_lag_order_cpu import lag_order_planes_ref, tones
-from test_layered_instances_cpu import (BASE, BASE_SUB, CONST, DELTA, EXTRA, LAG, LAG_ORDER, MIXED, PLANES, ROWS, STORED, WITH_BASE, ZIGZAG,
+from test_layered_instances_cpu import (BASE, BASE_SUB, CONST, DELTA, EXTRA, LAG, LAG_ORDER, MIXED, PLANES, RECORD, ROWS, STORED, WITH_BASE, ZIGZAG,
                                         base_len_of, coded_len, copy_bytes, input_len, layer_dec_name, layer_enc_name,
                                         layer_ws_bytes, mixed_table, reads_copy, tail_len)
 from test_mixed_cpu import mixed_ref
 from test_planes_cpu import planes_ref
 from test_planes_gpu import typed
+from test_record_cpu import record_ref
 from test_stored_cpu import rule
 from test_zigzag_cpu import zigzag_planes_ref
 
@@ -95,9 +101,12 @@ def _free():
     torch.cuda.empty_cache()
 
 
-def transform(layer, x, E, B, inverse=False, lag=None, base=NONE, table=None, order=None):
+def transform(layer, x, E, B, inverse=False, lag=None, base=NONE, table=None, order=None, delta=None):
     """The numpy restatement of what a layer's call puts in front of the coder (inverse: behind the decoder).  base: y, the
-    bytes of the base that lie under x; table: the unit table of the mixed layouts."""
+    bytes of the base that lie under x; table: the unit table of the mixed layouts; the record layout: E is the record size,
+    delta its flag."""
+    if layer == RECORD:
+        return record_ref(x, E, B, bool(delta), inverse)
     if layer == LAG_ORDER:
         return lag_order_planes_ref(x, E, B, lag, order, inverse=inverse)
     if layer == DELTA:
@@ -162,6 +171,13 @@ def frames_of(layer, E, B, seed, lag=None):
     if layer == LAG:                                 # interleaved channels, as many as the lag where that is <= 8
         return {f"channels{k}": np.resize(channels(lag if lag <= 8 else 8, E, seed + k).view("<u%d" % E), B).view(np.uint8).copy()
                 for k in range(3)}, {}
+    if layer == RECORD:                              # packed records of E bytes: a counter, a slowly moving, a noisy and a
+        out = {}                                     # constant column, repeated across the record
+        for k in range(3):
+            i = np.arange(B, dtype=np.int64)
+            cols = [i + 11 * k, 100 + 37 * k + np.cumsum(rng.integers(-2, 3, B)), rng.integers(0, 256, B), np.full(B, 0x40 + k)]
+            out[f"records{k}"] = np.stack([cols[p % 4] + (p // 4) * 3 for p in range(E)], axis=1).astype(np.uint8).reshape(-1)
+        return out, {}
     if layer == LAG_ORDER:                           # two frames of tones and one of walks, interleaved as for the lag filter
         ch = lag if lag <= 8 else 8
         gens = {"tones0": tones(ch, E, seed), "tones1": tones(ch, E, seed + 1), "walks": channels(ch, E, seed + 2)}
@@ -218,9 +234,10 @@ class Launch:
     (name, variant) pair: the variant is how the base lies under the frame ("cov": all of it, "cut": the base ends inside,
     "unc": not at all, and so for every layer without a base) or, for the mixed layouts, the frame's (= unit's) layout."""
 
-    def __init__(self, layer, params, E, B, nb, seed, ragged="C", slot=None, lag=None, base=None, table=None, oracle=True, order=None):
+    def __init__(self, layer, params, E, B, nb, seed, ragged="C", slot=None, lag=None, base=None, table=None, oracle=True, order=None,
+                 delta=None):
         import torch
-        self.layer, self.params, self.E, self.B, self.nb, self.lag, self.order = layer, params, E, B, nb, lag, order
+        self.layer, self.params, self.E, self.B, self.nb, self.lag, self.order, self.delta = layer, params, E, B, nb, lag, order, delta
         self.in_len = input_len(params, B, nb)
         F = E * B
         frames, y_frames = frames_of(layer, E, B, seed, lag)
@@ -305,7 +322,7 @@ class Launch:
 
     def transformed(self, x, y, variant):
         return transform(self.layer, x, self.E, self.B, lag=self.lag, base=y, table=[variant] if self.layer == MIXED else None,
-                         order=self.order)
+                         order=self.order, delta=self.delta)
 
     def device_input(self, off):
         """(whole tensor, the input `off` bytes off a 16-byte boundary, its start in the tensor)"""
@@ -372,7 +389,7 @@ def _dev_fn(direction, layer):
     return getattr(_lib().lib(), f"redux_{direction}_{layer}_dev")
 
 
-def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, base_len=0, d_table=None, mask=0, order=None):
+def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, base_len=0, d_table=None, mask=0, order=None, delta=None):
     """The layer's encode call between guard bands -> (out, offsets, statuses, summary, flags)"""
     import torch
     L = _lib()
@@ -398,6 +415,8 @@ def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, bas
         rc = fn(*x, B, mask, _v(d_table), *dst, *end)
     elif layer == LAG:
         rc = fn(*x, B, E, lag, *dst, *end)
+    elif layer == RECORD:               # (block size, record size, delta flag)
+        rc = fn(*x, B, E, int(delta), *dst, *end)
     elif layer == LAG_ORDER:
         rc = fn(*x, B, E, lag, order, *dst, *end)
     elif layer in (BASE, BASE_SUB):
@@ -411,7 +430,7 @@ def encode_dev(layer, params, E, B, d_in, in_len, ws, lag=None, d_base=None, bas
 
 
 def decode_dev(layer, params, E, B, d_streams, d_offs, d_flags, out_len, off=0, lag=None, d_base=None, base_len=0, d_table=None,
-               order=None):
+               order=None, delta=None):
     import torch
     L = _lib()
     lib, cp = L.lib(), L.Params(*params)
@@ -435,6 +454,8 @@ def decode_dev(layer, params, E, B, d_streams, d_offs, d_flags, out_len, off=0, 
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), _v(d_table), out_len, B, _v(out), *tail)
     elif layer == LAG:
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), out_len, B, E, lag, _v(out), *tail)
+    elif layer == RECORD:
+        rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), out_len, B, E, int(delta), _v(out), *tail)
     elif layer == LAG_ORDER:
         rc = fn(C.byref(cp), _v(d_streams), _v(d_offs), out_len, B, E, lag, order, _v(out), *tail)
     elif layer in (BASE, BASE_SUB):
@@ -523,6 +544,17 @@ def order_reaches_the_kernel(X):
             assert not np.array_equal(t, planes_ref(x, E, B))
 
 
+def record_layout_reaches_the_kernel(X):
+    """The record layout, from the reference alone: the transformed bytes of every distinct frame and of the ragged one are not
+    the input's, and the bytes with the delta are not the bytes without it, so a call that dropped the layout, the record size's
+    frame or the flag fails its row."""
+    R, B = X.E, X.B
+    assert X.delta in (False, True) and len(X.last) % B % 2 == 1 and (len(X.last) > B or R == 2)   # a short frame of several blocks
+    for x in [X.x_of[src] for src in X.sources] + [X.last]:
+        t, other = record_ref(x, R, B, X.delta), record_ref(x, R, B, not X.delta)
+        assert len(t) == len(x) and not np.array_equal(t, x) and not np.array_equal(other, x) and not np.array_equal(t, other)
+
+
 def layer_is_no_identity(X):
     return any(not np.array_equal(X.t_blocks[k * X.E], X.x_of[src][: X.B]) for k, src in enumerate(X.sources))
 
@@ -550,8 +582,8 @@ def spoil_reference(X, what):
 def run_row(key, ragged, spoil=None, mask=0):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base, order = EXTRA.get(key, (None, None, None))
-    X = Launch(layer, params, E, B, nb, _seed(key), ragged, lag=lag, base=base, oracle=not mask, order=order)
+    lag, base, order, delta = EXTRA.get(key, (None, None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), ragged, lag=lag, base=base, oracle=not mask, order=order, delta=delta)
     in_len = X.in_len
     big_in, d_in, lo_in = X.device_input(off)
     assert d_in.data_ptr() % 16 == off
@@ -576,6 +608,8 @@ def run_row(key, ragged, spoil=None, mask=0):
         const_launch_is_what_the_row_is_for(X, base)
     if layer == LAG_ORDER:
         order_reaches_the_kernel(X)
+    if layer == RECORD:
+        record_layout_reaches_the_kernel(X)
     # the layer matters: the transformed bytes are not the input's (a base filter without a base at E = 1 still copies)
     assert layer_is_no_identity(X) or layer in FLAGGED or (layer in (BASE, BASE_SUB) and base == "none" and E == 1)
     if spoil:
@@ -588,7 +622,8 @@ def run_row(key, ragged, spoil=None, mask=0):
         assert L.lib().redux_encode_kernel_name_ws(C.byref(cp), x_ptr, coded_len(layer, B, in_len), B, wsb - front).decode() == enc
         assert layer_enc_name(layer, params, E, B, nb, off, ws, base=base) == enc
         if not mask:
-            out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, in_len, ws, lag, d_y, X.base_len, d_table, order=order)
+            out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, in_len, ws, lag, d_y, X.base_len, d_table, order=order,
+                                                        delta=delta)
         assert guards_intact(big_in, lo_in, in_len) and guards_intact(big_y, lo_y, X.base_len)
         assert summ.tolist() == [0, 0] and not bool(status.any())
         if layer in FLAGGED:
@@ -606,7 +641,7 @@ def run_row(key, ragged, spoil=None, mask=0):
     else:
         out, offs, flags = assemble(X, X.payload, X.flag)
     d_out, sizes, dstatus, dsum = decode_dev(layer, params, E, B, out, offs, flags if layer in FLAGGED else None, in_len, off, lag, d_y,
-                                             X.base_len, d_table, order=order)
+                                             X.base_len, d_table, order=order, delta=delta)
     assert dsum.tolist() == [0, 0] and not bool(dstatus.any())
     assert torch.equal(sizes.to(torch.int64), torch.from_numpy(X.block_lengths()).cuda())
     if not torch.equal(d_out, d_in):
@@ -630,7 +665,8 @@ def test_mixed_layouts_chosen_on_the_device(rx):
 
 SPOILED = [("const_e8_pair_below_coop_min", "flag"), ("const_e8_pair_below_coop_min", "byte"), ("mixed_pair_by_blocks_cb32", "byte"),
            ("zigzag_e8_pair_below_coop_min", "byte"), ("lag_e8_pair_below_coop_min", "byte"), ("base_e8_pair_below_coop_min", "byte"),
-           ("base_sub_e8_pair_below_coop_min", "byte"), ("lag_order_e8_pair_below_coop_min", "byte")]
+           ("base_sub_e8_pair_below_coop_min", "byte"), ("lag_order_e8_pair_below_coop_min", "byte"),
+           ("record_r256_pair_below_coop_min", "byte")]
 
 
 @pytest.mark.parametrize("key,what", SPOILED)
@@ -665,22 +701,25 @@ HOST_KEYS = ["planes_e2_coop_whole_cb32", "delta_e1_pair_by_blocks_cb32", "store
              # the later layers: constant blocks at E = 1 on the caller's buffer, and with a base that ends inside a chunk
              "const_e1_single16_by_alignment", "const_e2_pair_by_blocks_cb16", "mixed_pair_by_blocks_cb32",
              "zigzag_e4_pair_by_blocks_cb32", "lag_e4_pair_by_blocks_cb32", "base_e4_pair_by_blocks_cb32",
-             "base_sub_e2_single32_by_workspace", "lag_order_e4_pair_by_blocks_cb32"]
+             "base_sub_e2_single32_by_workspace", "lag_order_e4_pair_by_blocks_cb32", "record_r17_pair_by_blocks_cb32"]
 
 
 @pytest.mark.parametrize("key", HOST_KEYS)
 def test_host_pointer_forms_with_crc_equal_the_dev_calls(rx, key):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
-    lag, base, order = EXTRA.get(key, (None, None, None))
-    X = Launch(layer, params, E, B, nb, _seed(key), "S", lag=lag, base=base, order=order)
+    lag, base, order, delta = EXTRA.get(key, (None, None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), "S", lag=lag, base=base, order=order, delta=delta)
     big_in, d_in, lo_in = X.device_input(off)
     big_y, d_y, lo_y = X.device_base()
     d_table = torch.from_numpy(X.table).cuda() if layer == MIXED else None
-    out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, X.in_len, ws, lag, d_y, X.base_len, d_table, order=order)
+    out, offs, status, summ, flags = encode_dev(layer, params, E, B, d_in, X.in_len, ws, lag, d_y, X.base_len, d_table, order=order,
+                                                delta=delta)
     x = d_in.cpu().numpy()
     total = int(offs[-1])
-    kw = {"unit_layouts": X.table} if layer == MIXED else {"element_size": E}
+    kw = {"unit_layouts": X.table} if layer == MIXED else {"record_size": E} if layer == RECORD else {"element_size": E}
+    if layer == RECORD and delta:
+        kw["filter"] = "delta"
     if layer in (DELTA, ZIGZAG, LAG):
         kw["filter"] = layer
     if layer == LAG_ORDER:
@@ -908,7 +947,8 @@ def test_const_select_past_its_grid_cap(rx):
 
 # ---- 5. damaged streams on the new decode paths ---------------------------------------------------------------------------------
 DAMAGED_KEYS = ["stored_e1_coop_windows_100k", "stored_e4_table_generic32", "planes_e8_cells8", "delta_e2_cells8",
-                "lag_order_e2_coop_windows_150k"]       # (k_decode_wave and the fix-up pass in front of the K-level inverse)
+                "lag_order_e2_coop_windows_150k",       # (k_decode_wave and the fix-up pass in front of the K-level inverse)
+                "record_r2_coop_windows_150k"]          # (... and in front of the record layout's inverse)
 
 
 @pytest.mark.parametrize("key", DAMAGED_KEYS)
@@ -919,8 +959,8 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     import torch
     layer, params, E, B, nb, off, ws, enc, dec, _ = ROWS[key]
     assert layer_dec_name(layer, params, B, nb) == dec
-    lag, _, order = EXTRA.get(key, (None, None, None))
-    X = Launch(layer, params, E, B, nb, _seed(key), "C", lag=lag, order=order)
+    lag, _, order, delta = EXTRA.get(key, (None, None, None, None))
+    X = Launch(layer, params, E, B, nb, _seed(key), "C", lag=lag, order=order, delta=delta)
     rng = np.random.default_rng(_seed(key) + 1)
     coded = [b for b in range(nb - 1) if not X.flag[X.unit[b]]]
     picks = [coded[i] for i in (3, len(coded) // 5, len(coded) // 3, len(coded) // 2, len(coded) - 70, len(coded) - 2)]
@@ -946,7 +986,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     X.unit, X.d_unit = unit, torch.from_numpy(unit).cuda()
     flat, offs, flags = assemble(X, payload, flag)
     big_in, d_in, lo_in = X.device_input(0)
-    d_out, sizes, status, dsum = decode_dev(layer, params, E, B, flat, offs, flags, X.in_len, off, lag, order=order)
+    d_out, sizes, status, dsum = decode_dev(layer, params, E, B, flat, offs, flags, X.in_len, off, lag, order=order, delta=delta)
     got_st, got_sz = status.cpu().numpy(), sizes.cpu().numpy()
     bad = np.nonzero((got_st != want_st) | (got_sz != want_sz))[0]
     assert not len(bad), (int(bad[0]), int(got_st[bad[0]]), int(got_sz[bad[0]]), int(want_st[bad[0]]), int(want_sz[bad[0]]))
@@ -965,7 +1005,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
     # inverse of the restated transform with d in place.  (E = 1 without a filter: the block's first len(d) bytes are d.)
     checked = 0
     for f in sorted({b // E for b in picks if b // E < len(X.plan)}):
-        t = transform(layer, X.frames[X.plan[f]], E, B, lag=lag, order=order).copy()
+        t = transform(layer, X.frames[X.plan[f]], E, B, lag=lag, order=order, delta=delta).copy()
         m = B
         for b in picks:
             if b // E == f:
@@ -973,7 +1013,7 @@ def test_damaged_streams_on_the_new_decode_paths(rx, key):
                 j = b % E
                 t[j * B: j * B + len(d)] = d
                 m = min(m, len(d))
-        want = transform(layer, t, E, B, inverse=True, lag=lag, order=order)[: m * E]
+        want = transform(layer, t, E, B, inverse=True, lag=lag, order=order, delta=delta)[: m * E]
         got = d_out[f * F: f * F + m * E].cpu().numpy()
         if not np.array_equal(got, want):
             at = int(np.nonzero(got != want)[0][0])

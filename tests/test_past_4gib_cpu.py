@@ -25,6 +25,7 @@ from test_mixed_cpu import choose_ref, mixed_ref
 from test_mixed_gpu import typed
 from test_plane_static_cpu import plane_counts
 from test_planes_cpu import planes_ref
+from test_record_cpu import record_ref
 from test_segment_static_cpu import segment_counts
 from test_zigzag_cpu import zigzag_planes_ref
 
@@ -45,7 +46,35 @@ RESTATEMENTS = {"planes": planes_ref, "delta": delta_planes_ref, "zigzag": zigza
 TRANSFORMS = [("planes", 2, 4096), ("planes", 8, 65536),
               ("delta", 1, 4096), ("delta", 8, 65536), ("delta", 2, 4096),
               ("zigzag", 1, 4096), ("zigzag", 8, 65536), ("zigzag", 2, 4096)]
+# ... and the record layout, (name, R, B): the fast path with frames of 64 KiB; a frame that is a whole segment, far more
+# frames than 8 * CUs workgroups; B no multiple of 16, so the byte kernels take everything: forward more bytes than grid_bytes
+# has threads; at B = 2036 the delta inverse has more (frame, column) pairs than that too (at B = 4100 it has half as many);
+# R = 3 and 23, whose frames divide no power of two
+LAYOUT_NAMES = tuple(RESTATEMENTS)
+RESTATEMENTS["record"] = lambda x, R, B, inverse=False: record_ref(x, R, B, False, inverse)
+RESTATEMENTS["record_delta"] = lambda x, R, B, inverse=False: record_ref(x, R, B, True, inverse)
+RECORD_TRANSFORMS = [("record_delta", 16, 4096), ("record", 256, 2048), ("record_delta", 256, 2048),
+                     ("record", 4, 4100), ("record_delta", 4, 4100), ("record_delta", 4, 2036), ("record_delta", 3, 4096),
+                     ("record_delta", 23, 4096)]
+TRANSFORMS += RECORD_TRANSFORMS
 BASE_RESTATEMENTS = {"base": base_planes_ref, "base_sub": base_sub_planes_ref}
+
+
+def segment_length(granule):
+    """the segment a granule is tiled with: the shared one where the granule divides it, 32 granules where it does not"""
+    return SEG if SEG % granule == 0 else 32 * granule
+
+
+def segment_count(L=SEG):
+    """2^32 bytes of segments, rounded up, and three more"""
+    return -(-(1 << 32) // L) + 3
+
+
+def total_bytes(L=SEG):
+    return segment_count(L) * L + TAIL
+
+
+LARGEST = max(total_bytes(segment_length(R * B)) for _, R, B in RECORD_TRANSFORMS)   # what a buffer of the GPU file has to hold
 BASE_E, BASE_B = 4, 4096
 
 
@@ -56,10 +85,12 @@ def order(nseg):
 
 
 def constant_segment(L):
-    """L bytes (a multiple of 1024) in groups of four blocks of 1024 bytes: a group of one value (constant at B = 4096 too), a
-    group of noise, a group of four different constant blocks, a group of the NEXT group's value (equal neighbours); group 4 is
-    constant but for its last byte and group 8 but for byte 17"""
-    assert L % 1024 == 0
+    """L bytes in groups of four blocks of 1024 bytes: a group of one value (constant at B = 4096 too), a group of noise, a
+    group of four different constant blocks, a group of the NEXT group's value (equal neighbours); group 4 is constant but for
+    its last byte and group 8 but for byte 17.  (An L that is no multiple of 1024, as the record layout's segments at B = 4100
+    are: the first L bytes of the next multiple.)"""
+    if L % 1024:
+        return constant_segment(-(-L // 1024) * 1024)[:L].copy()
     rng = np.random.default_rng(1024)
     x = np.empty(L, dtype=np.uint8)
     value = lambda q: (q * 37 + 11) & 0xFF  # noqa: E731
@@ -227,6 +258,36 @@ def test_the_segments_are_what_the_cases_need():
     assert 0.05 < (x != y).mean() < 0.2
     assert base_length(8192, SEG) > 1 << 32 and base_length(8192, SEG) < N - SEG
     assert base_length(8192, SEG) % (BASE_E * BASE_B) == 7 and base_cover(8193, 8192, SEG) == SEG // 4 + 7
+
+
+def test_the_record_entries_and_their_segments():
+    """The record layout's entries against a list written out here (one removed fails this), and what each is there for: the
+    segment is whole frames, the frames lie past 2^32, the work outnumbers what the strided launches have, and every buffer
+    fits what the GPU file allocates."""
+    from redux_amd import api
+    assert TRANSFORMS[-8:] == [("record_delta", 16, 4096), ("record", 256, 2048), ("record_delta", 256, 2048), ("record", 4, 4100),
+                               ("record_delta", 4, 4100), ("record_delta", 4, 2036), ("record_delta", 3, 4096),
+                               ("record_delta", 23, 4096)] == RECORD_TRANSFORMS
+    assert len(TRANSFORMS) == 8 + 8 and LAYOUT_NAMES == ("planes", "delta", "zigzag")
+    assert [segment_length(R * B) for _, R, B in RECORD_TRANSFORMS] == [SEG, SEG, SEG, 524800, 524800, 260608, 32 * 3 * 4096, 32 * 23 * 4096]
+    assert segment_count() == NSEG and total_bytes() == N and LARGEST == total_bytes(32 * 23 * 4096) > N
+    cus = 256
+    for name, R, B in RECORD_TRANSFORMS:
+        L = segment_length(R * B)
+        n, delta = total_bytes(L), name == "record_delta"
+        assert L % (R * B) == 0 and (segment_count(L) - 3) * L >= 1 << 32 > (segment_count(L) - 4) * L and n <= LARGEST
+        assert 0 < TAIL // R < B and (TAIL % R > 0) == (R != 3)    # the tail: a short frame of whole records and, but for R = 3, trailing bytes
+        assert len(set(order(segment_count(L))[-3:].tolist()) | set(order(segment_count(L))[:4].tolist())) > 2
+        fwd, inv = api.record_plan(n, B, R, delta, False, cus), api.record_plan(n, B, R, delta, True, cus)
+        nframes = n // (R * B)
+        if B % 16:  # the byte kernels alone: 8,192 workgroups of 256 threads stride over the bytes, or the (frame, column) pairs
+            pairs = (nframes + 1) * R
+            assert (fwd.grid_fast, inv.grid_fast, fwd.grid_bytes) == (0, 0, 8192) and n > 8192 * 256
+            assert inv.grid_bytes == min(-(-(pairs if delta else n) // 256), 8192)
+            assert (pairs > 8192 * 256) == (B == 2036) and inv.grid_bytes == (8192 if B == 2036 or not delta else -(-pairs // 256))
+        else:       # the fast kernels, every workgroup on to further frames or tiles, and the byte kernels for the tail
+            assert fwd.grid_fast == inv.grid_fast == 8 * cus < nframes and fwd.grid_bytes and inv.grid_bytes and inv.PC == R
+    assert SEG // (256 * 2048) == 1 and N // SEG > 8 * 1024      # R = 256: a frame is a whole segment, more frames than 8 * CUs
 
 
 @pytest.mark.parametrize("name,E,B", TRANSFORMS)

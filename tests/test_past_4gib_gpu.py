@@ -1,4 +1,4 @@
-"""The transforms, the selectors and the estimates on an input of 4.3 GB: byte offsets past 2^32 and more work than every
+"""The transforms (the record layout among them), the selectors and the estimates on an input of 4.3 GB: byte offsets past 2^32 and more work than every
 strided launch has workgroups (grid_bytes 8,192; grid_frames and k_const_select 2^20; k_mixed_choose 4,096; the estimates, the
 CRC, the histograms and k_segment_copy a small multiple of the CU count), so that a workgroup goes on to a second frame, unit
 or block with its carry, its totals and its LDS tile as the first one left them.
@@ -52,16 +52,18 @@ def dev(a):
 
 
 class Buffers:
-    """three device buffers of N bytes between poison (on_device_poisoned), and what each one holds: the tiled input, the
-    tiled base, or nothing that a later test may count on"""
+    """three device buffers of N bytes (of T.LARGEST: the record layout's segments of 32 frames tile a few megabytes more)
+    between poison (on_device_poisoned), and what each one holds: the tiled input, the tiled base, or nothing that a later
+    test may count on.  L: the segment length of the tiling, the shared SEG unless a record size needs its own."""
 
     def __init__(self, torch):
         self.torch = torch
         self.idx = dev(ORDER)
-        self.raw = [on_device_poisoned(torch, N + 16)[0] for _ in range(3)]
+        self.raw = [on_device_poisoned(torch, T.LARGEST + 16)[0] for _ in range(3)]
         self.holds = [None] * 3
         self.parts = {"x": dev(T.segments()), "base": dev(T.base_segments())}
         self.tail = dev(T.tail_bytes())
+        self.orders = {SEG: (self.parts["x"], self.idx)}
 
     def view(self, i, offset=0, n=N):
         return self.raw[i][FRONT + offset: FRONT + offset + n]
@@ -75,18 +77,25 @@ class Buffers:
         self.raw[i].fill_(FILL)
         return self.view(i, offset, n)
 
-    def tiled(self, i, what="x", offset=0):
-        """buffer i holding the tiled input ("x": N bytes) or the base ("base": base_length bytes, no tail) -> its view"""
-        n = N if what == "x" else T.base_length(8192, SEG)
-        if self.holds[i] != (what, offset):
+    def order(self, L=SEG):
+        """(the distinct segments of length L, which of them lies at each position) on the device"""
+        if L not in self.orders:
+            self.orders[L] = (dev(T.segments(L)), dev(T.order(T.segment_count(L))))
+        return self.orders[L]
+
+    def tiled(self, i, what="x", offset=0, L=SEG):
+        """buffer i holding the tiled input ("x": T.total_bytes(L) bytes) or the base ("base": base_length bytes, no tail) -> its view"""
+        n = T.total_bytes(L) if what == "x" else T.base_length(8192, SEG)
+        if self.holds[i] != (what, offset, L):
             v = self.poisoned(i, offset, n)
-            parts, whole = self.parts[what], n // SEG
-            body = v[: whole * SEG].view(whole, SEG)
-            for f0 in range(0, whole, 1024):  # (slabs: a gather of the whole buffer would be a fourth one)
-                body[f0: f0 + 1024].copy_(parts[self.idx[f0: min(f0 + 1024, whole)]])
-            rest = self.tail if what == "x" else parts[self.idx[whole]][: n - whole * SEG]
-            v[whole * SEG:].copy_(rest)
-            self.holds[i] = (what, offset)
+            (parts, idx), whole = (self.order(L) if what == "x" else (self.parts[what], self.idx)), n // L
+            body = v[: whole * L].view(whole, L)
+            step = (512 << 20) // L  # (slabs: a gather of the whole buffer would be a fourth one)
+            for f0 in range(0, whole, step):
+                body[f0: f0 + step].copy_(parts[idx[f0: min(f0 + step, whole)]])
+            rest = self.tail if what == "x" else parts[idx[whole]][: n - whole * L]
+            v[whole * L:].copy_(rest)
+            self.holds[i] = (what, offset, L)
         return self.view(i, offset, n)
 
 
@@ -97,25 +106,27 @@ def bufs():
     assert len(set(np.diff(np.nonzero((b.idx[:4096] == 0).cpu().numpy())[0]).tolist())) > 4  # (no short period)
     assert N > 1 << 32
     yield b
-    del b.raw, b.parts, b
+    del b.raw, b.parts, b.orders, b
     torch.cuda.synchronize()
     torch.cuda.empty_cache()  # (three buffers of 4.3 GB)
 
 
-def mismatch(bufs, got, parts, granule, what, lo=0, hi=NSEG, tail=None):
-    """got (device bytes of the whole buffer) against parts[idx[f]] for the positions lo <= f < hi and, if given, `tail` behind
-    position NSEG - 1, on the device in slabs -> None, or what names the first wrong granule"""
-    torch, idx = bufs.torch, bufs.idx
-    step = 512
+def mismatch(bufs, got, parts, granule, what, lo=0, hi=None, tail=None, L=SEG, idx=None):
+    """got (device bytes of the whole buffer) against parts[idx[f]] for the positions lo <= f < hi (segments of L bytes) and, if
+    given, `tail` behind the last position, on the device in slabs -> None, or what names the first wrong granule"""
+    torch, idx = bufs.torch, bufs.idx if idx is None else idx
+    nseg = T.segment_count(L)
+    hi = nseg if hi is None else hi
+    step = (256 << 20) // L
     for f0 in range(lo, hi, step):
         f1 = min(f0 + step, hi)
-        g = got[f0 * SEG: f1 * SEG].view(-1, SEG)
+        g = got[f0 * L: f1 * L].view(-1, L)
         if not torch.equal(g, parts[idx[f0:f1]]):
             f = f0 + int((g != parts[idx[f0:f1]]).any(1).nonzero()[0])
-            at = f * SEG + int((got[f * SEG: (f + 1) * SEG] != parts[idx[f]]).nonzero()[0])
+            at = f * L + int((got[f * L: (f + 1) * L] != parts[idx[f]]).nonzero()[0])
             return f"{what} {at // granule} (position {f}, distinct segment {int(idx[f])}) differs at byte {at}"
-    if tail is not None and not torch.equal(got[NSEG * SEG:], tail):
-        at = NSEG * SEG + int((got[NSEG * SEG:] != tail).nonzero()[0])
+    if tail is not None and not torch.equal(got[nseg * L:], tail):
+        at = nseg * L + int((got[nseg * L:] != tail).nonzero()[0])
         return f"{what} {at // granule} (the tail) differs at byte {at}"
     return None
 
@@ -135,7 +146,16 @@ def tiled_rows(bufs, per, tail):
 def transform_refs():
     """{(name, E, B, inverse): (uint8[8, SEG], the tail's)}"""
     return {(name, E, B, inverse): per_segment(lambda x: T.RESTATEMENTS[name](x, E, B, inverse=inverse))
-            for name, E, B in T.TRANSFORMS for inverse in (False, True)}
+            for name, E, B in T.TRANSFORMS if name in T.LAYOUT_NAMES for inverse in (False, True)}
+
+
+@pytest.fixture(scope="module")
+def record_refs():
+    """{(name, R, B, inverse): (uint8[8, L], the tail's)} for the record layout, L the segment length of the entry"""
+    def per(fn, L):
+        return dev(np.stack([fn(s) for s in T.segments(L)])), dev(fn(T.tail_bytes()))
+    return {(name, R, B, inverse): per(lambda x: T.RESTATEMENTS[name](x, R, B, inverse=inverse), T.segment_length(R * B))
+            for name, R, B in T.RECORD_TRANSFORMS for inverse in (False, True)}
 
 
 @pytest.fixture(scope="module")
@@ -191,8 +211,8 @@ def count_refs():
 
 # ---- 1. planes, delta_planes, zigzag_planes -------------------------------------------------------------------------------
 # (name, E, B, offset of the source from a 16-byte boundary)
-TRANSFORM_CASES = [(name, E, B, 0) for name, E, B in T.TRANSFORMS if (E, B) != (2, 4096) or name == "planes"] + \
-                  [(name, 2, 4096, 1) for name in T.RESTATEMENTS] + [("delta", 1, 4096, 1), ("zigzag", 1, 4096, 1)]
+TRANSFORM_CASES = [(name, E, B, 0) for name, E, B in T.TRANSFORMS if name in T.LAYOUT_NAMES and ((E, B) != (2, 4096) or name == "planes")] + \
+                  [(name, 2, 4096, 1) for name in T.LAYOUT_NAMES] + [("delta", 1, 4096, 1), ("zigzag", 1, 4096, 1)]
 
 
 @pytest.mark.parametrize("name,E,B,off", TRANSFORM_CASES)
@@ -218,6 +238,41 @@ def test_layout_transforms(rx, bufs, transform_refs, name, E, B, off):
     call(dst, E, B, inverse=False, out=back)  # (dst: the inverse's result)
     assert bufs.intact(2) and bufs.intact(1)
     bad = mismatch(bufs, back, bufs.parts["x"], frame, "forward of the inverse: frame", tail=bufs.tail)
+    assert bad is None, bad
+
+
+# ---- 1b. record_planes ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,R,B", T.RECORD_TRANSFORMS)
+def test_record_layout(rx, bufs, record_refs, name, R, B):
+    """The record layout (T.RECORD_TRANSFORMS says what each entry is there for): fbase = f * R * B, p * B and frame_pos past
+    2^32; 8 * CUs workgroups of the fast kernels striding over 2^16 frames and more; at B = 4100 and 2036 the byte kernels from
+    byte 0, forward a thread per byte and the delta inverse a thread per (frame, column) striding from 8,192 workgroups.
+    Record sizes whose frames divide no power of two are tiled from segments of 32 frames.  Forward and inverse against the
+    tiled restatement, and the inverse's result through the forward kernel against the source."""
+    from redux_amd import api
+    delta = name == "record_delta"
+    L = T.segment_length(R * B)
+    n = T.total_bytes(L)
+    parts, idx = bufs.order(L)
+    tail = bufs.tail
+    src = bufs.tiled(0, "x", 0, L)
+    assert src.numel() == n > 1 << 32
+    for inverse in (False, True):
+        fast = api.record_plan(n, B, R, delta, inverse).grid_fast
+        kernel = "k_record_unplanes" if inverse else "k_record_planes"
+        assert api.record_kernel_name(n, B, R, inverse, d_src=src, d_dst=bufs.view(1, 0, n)) == \
+            (kernel + " + " + kernel + "_bytes" if fast else kernel + "_bytes")
+        assert bool(fast) == (B % 16 == 0)
+        dst = bufs.poisoned(1, 0, n)
+        api.record_planes(src, R, B, delta=delta, inverse=inverse, out=dst)
+        assert bufs.intact(1, 0, n) and bufs.intact(0, 0, n), (name, R, B, inverse)
+        want, want_tail = record_refs[name, R, B, inverse]
+        bad = mismatch(bufs, dst, want, R * B, "R=%d B=%d %s inverse=%s: frame" % (R, B, name, inverse), tail=want_tail, L=L, idx=idx)
+        assert bad is None, bad
+    back = bufs.poisoned(2, 0, n)
+    api.record_planes(dst, R, B, delta=delta, inverse=False, out=back)  # (dst: the inverse's result)
+    assert bufs.intact(2, 0, n) and bufs.intact(1, 0, n)
+    bad = mismatch(bufs, back, parts, R * B, "R=%d B=%d %s forward of the inverse: frame" % (R, B, name), tail=tail, L=L, idx=idx)
     assert bad is None, bad
 
 

@@ -311,3 +311,28 @@ def test_cli_parse_range():
         assert cli.parse(bad) is None, bad
     assert "--range" in cli.USAGE and "--range" in cli.__doc__
     assert cli.main(["-d", "--range"]) == 1
+
+
+def test_the_gpu_sweeps_hold_every_container_kind_and_mode():
+    """The tables of tests/test_range_gpu.py against lists written out here: a kind, a mode or a damaged kind that is removed
+    fails this test.  The record layout's kinds are container version 15 with and without the byte delta, their granule a
+    frame of record_size blocks, and the file's ranges reach its short last frame and that frame's trailing bytes."""
+    import test_range_gpu as G
+    kinds = ["v1", "v2", "v3", "v4", "v5", "v5e2", "v6", "v7", "v8", "v9", "v9base", "v10", "0x41", "0x42", "v11", "v12", "v13", "v14",
+             "v15", "v15plain"]
+    assert list(G.KINDS) == kinds and G.ALL_KINDS == kinds + [k + "+crc" for k in kinds]
+    assert list(G.MODES) == ["plain", "planes", "delta", "base", "constant", "constant+base", "mixed", "zigzag", "base_sub", "lag",
+                             "lag_order", "record"]
+    assert G.DAMAGED == ["v1+crc", "v2+crc", "v9base+crc", "v10+crc", "v12+crc", "v14+crc", "v15+crc", "v15plain+crc"]
+    assert G.KINDS["v15"] == dict(E=1, record_size=23, filter="delta") and G.KINDS["v15plain"] == dict(E=1, record_size=5)
+    assert G.MODES["record"] == dict(E=1, record_size=23, filter="delta")
+    assert G.VERSION_BYTE == {"v11": 11, "v12": 12, "v13": 13, "v14": 14, "v15": 15, "v15plain": 15}
+    for R in (23, 5):
+        F, total = R * G.B, 5 * R * G.B + G.B + 3
+        short = total - 5 * F                            # the short last frame: whole records and trailing bytes
+        assert 0 < short % R < short and short > G.B
+        ranges = G.the_ranges(total, F)
+        # (total - 5, 5) lies in the short frame and ends in its 5 (R = 23) or 4 (R = 5) trailing bytes; (0, total) reads its records
+        assert 0 < short % R <= 5 and (total - 5, 5) in ranges and (total - 1, 1) in ranges and (0, total) in ranges
+        runs, virt_off, virt_len = api.range_plan(total, G.B, R, [(total - 5, 5)])
+        assert [tuple(r) for r in runs] == [(5, 1)] and virt_len == short

@@ -120,9 +120,11 @@ KINDS = {
     # the frame-local prefix-sum filters that came after the sweep: zigzag, the folded difference against a base, lag, lag order
     "v11": dict(E=2, element_size=2, filter="zigzag"), "v12": dict(E=4, element_size=4, base=True, base_op="sub"),
     "v13": dict(E=2, element_size=2, filter="lag", lag=3), "v14": dict(E=8, element_size=8, filter="lag", lag=2, order=3),
+    # the record layout, with and without its byte delta: the granule is a frame of record_size blocks
+    "v15": dict(E=1, record_size=23, filter="delta"), "v15plain": dict(E=1, record_size=5),
 }
 ALL_KINDS = list(KINDS) + [k + "+crc" for k in KINDS]  # (0x41 + 0x10 = 0x51, ...)
-VERSION_BYTE = {"v11": 11, "v12": 12, "v13": 13, "v14": 14}  # (+crc: 0x1B, 0x1C, 0x1D, 0x1E)
+VERSION_BYTE = {"v11": 11, "v12": 12, "v13": 13, "v14": 14, "v15": 15, "v15plain": 15}  # (+crc: 0x1B, 0x1C, 0x1D, 0x1E, 0x1F)
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,7 +139,7 @@ def made(kind):
         F = kw["segment_blocks"] * bs
         data = typed(E, 2 * F + 9 * bs + 3, 7)  # two segments and a short third
     else:
-        F = E * bs
+        F = kw.get("record_size", E) * bs       # (the record layout: E is 1, a frame is record_size blocks)
         data = typed(E, 5 * F + bs + 3, E)      # a short last frame of more than one block, with trailing bytes
     if kind.startswith("0x4"):                  # (bytes that do not shrink, so that blocks are stored)
         data[F: 3 * F] = np.random.default_rng(3).integers(0, 256, 2 * F, dtype=np.uint8)
@@ -184,7 +186,10 @@ def test_every_container_kind_reads_by_range(rx, kind):
     assert container.decompress_range(blob, F - 1, 2, base=base) == data[F - 1: F + 1]
 
 
-@pytest.mark.parametrize("kind", ["v1+crc", "v2+crc", "v9base+crc", "v10+crc", "v12+crc", "v14+crc"])
+DAMAGED = ["v1+crc", "v2+crc", "v9base+crc", "v10+crc", "v12+crc", "v14+crc", "v15+crc", "v15plain+crc"]
+
+
+@pytest.mark.parametrize("kind", DAMAGED)
 def test_damage_matters_only_where_a_range_reads(rx, kind):
     from redux_amd import container
     blob, data, base, F, bs = made(kind)
@@ -212,7 +217,9 @@ MODES = {"plain": dict(E=1), "planes": dict(E=4, element_size=4), "delta": dict(
          # the gathered virtual input (covered granules concatenated, a short last frame, the gathered prefix of a base that
          # ends 100 bytes into a frame) behind the frame-local prefix-sum filters
          "zigzag": dict(E=1, filter="zigzag"), "base_sub": dict(E=8, element_size=8, base=True, base_op="sub"),
-         "lag": dict(E=4, element_size=4, filter="lag", lag=5), "lag_order": dict(E=2, element_size=2, filter="lag", lag=3, order=2)}
+         "lag": dict(E=4, element_size=4, filter="lag", lag=5), "lag_order": dict(E=2, element_size=2, filter="lag", lag=3, order=2),
+         # the record layout: frames of 23 blocks; the short last frame holds 178 records and 5 trailing bytes
+         "record": dict(E=1, record_size=23, filter="delta")}
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -220,8 +227,8 @@ def test_decode_ranges_equals_slices_of_decode(rx, mode):
     import torch
     kw = dict(MODES[mode])
     E = kw.pop("E")
-    x = mixed_data() if mode == "mixed" else typed(E, 5 * E * B + B + 3, 20 + E)
-    F = (8 if mode == "mixed" else E) * B
+    F = (8 if mode == "mixed" else kw.get("record_size", E)) * B
+    x = mixed_data() if mode == "mixed" else typed(E, 5 * F + B + 3, 20 + E)
     n = len(x)
     d_in = torch.from_numpy(x).cuda()
     if kw.pop("base", False):

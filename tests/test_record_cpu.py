@@ -5,6 +5,8 @@ pipeline and the C++ mirror's refusals.  No GPU call.
 
 The value claim rests on GENERATED data, two tables of packed structs (imu23, ticks20): nothing in the corpus fixtures
 consists of fixed-width records."""
+from collections import namedtuple
+
 import numpy as np
 import pytest
 
@@ -464,3 +466,210 @@ def test_cpp_mirror_refuses_bad_arguments_before_any_device_call(tmp_path):
     _lib.lib()
     out = subprocess.run([build_record_mirror_test(tmp_path), "--no-gpu"], capture_output=True, text=True)
     assert out.returncode == 0 and "record mirror host-side checks ok" in out.stdout, out.stdout + out.stderr
+
+
+# ---- the launch plan -------------------------------------------------------------------------------------------------
+# redux_record_plan reports the shape launch_record launches with, from the function the launch takes it from.  The
+# constants of redux_record.hpp, restated: the LDS tile's bytes, the inverse's work items (16 records of a column) a tile.
+LDS_BYTES, ITEMS = 33792, 2048
+LG_MAX = 12                       # record_lg_tile stops there: the largest tile is 4096 records (R up to 7)
+PCS = (64, 80, 96, 112, 128)      # the widths of a column range, besides R itself
+
+
+def tile_bytes(T, row):
+    """the LDS tile of T records of `row` bytes: for an even row every group of 16 records is followed by 16 bytes"""
+    return T * row + (T // 16) * (0 if row & 1 else 16)
+
+
+def plan_of(nfull, R, B, inverse, cus, delta=False, tail=0):
+    from redux_amd import api
+    return api.record_plan(nfull * R * B + tail, B, R, delta, inverse, cus)
+
+
+def max_tile(R, nfull, inverse, cus):
+    """the tile the plan takes where the block size does not hold it down"""
+    return 1 << plan_of(nfull, R, 1 << 16, inverse, cus).lgT
+
+
+# The sweep of tests/test_record_gpu.py: id -> (R, block size, full frames, a short frame and trailing bytes behind them,
+# what the row is there for).  A block size (d, k, a) is k * T + a for T the largest tile of the forward ("f") or the
+# inverse ("i") launch at this R and frame count; full frames ("pc", n): the fewest at which the inverse runs with PC = n;
+# ("cus", a, b): a * CUs + b.  The claims, checked against redux_record_plan by claims_hold: "lgT" / "ilgT" the forward /
+# inverse tile, "PC", "last" the columns of the last range, "G" the groups of the (forward, inverse) frame's last tile,
+# "tiles" the inverse's tiles a frame, "wrap": more frames than workgroups, "split": whether the columns are cut.
+SWEEP = {}
+GROUP_R = (3, 16, 23, 64, 255, 256)
+GROUP_B = (16, 32, 48, 80, 112, 1008, ("f", 1, 48))   # 1, 2, 3, 5, 7 and 63 groups; a full tile and 3 groups
+for _R in GROUP_R:
+    for _B in GROUP_B:
+        SWEEP["groups_r%d_b%s" % (_R, _B if isinstance(_B, int) else "T48")] = (_R, _B, 2, True, {})
+SWEEP["groups_r3_b16"][4]["lgT"] = 4
+SWEEP["groups_r3_b32"][4]["lgT"] = 5
+SWEEP["groups_r3_b48"][4].update(lgT=6, G=(3, 3))
+SWEEP["groups_r3_b112"][4].update(lgT=7, G=(7, 7))
+SWEEP["groups_r23_b80"][4].update(lgT=7, G=(5, 5))
+SWEEP["groups_r3_b1008"][4].update(lgT=10, G=(63, 63))
+SWEEP["groups_r64_b1008"][4].update(lgT=9, G=(31, 31))
+SWEEP["groups_r256_b1008"][4].update(lgT=7, G=(7, 31), split=True)        # forward: seven tiles of 128 records, then 7 groups
+SWEEP["groups_r3_bT48"][4].update(lgT=12, G=(3, 3), tiles=2)
+SWEEP["groups_r23_bT48"][4].update(lgT=10, G=(3, 3), tiles=2)
+SWEEP["groups_r64_bT48"][4].update(lgT=9, ilgT=9, G=(3, 3), tiles=2, split=False)
+SWEEP["groups_r255_bT48"][4].update(lgT=7, G=(3, 11), PC=64, last=63)
+for _id, _row in {
+    # the column ranges, one tile a frame and several with a ragged last one
+    "pc64_r255": (255, 64, 3, False, dict(PC=64, last=63, split=True)),
+    "pc64_r81": (81, 64, 3, False, dict(PC=64, last=17, split=True)),
+    "pc64_r65": (65, 64, 3, False, dict(PC=64, last=1, split=True)),
+    "pc0_r64": (64, 64, 3, False, dict(PC=64, split=False)),                      # R = 64 against 65 at the same frame count
+    "pc80_r200": (200, 64, ("pc", 80), False, dict(PC=80, last=40)),
+    "pc96_r256": (256, 64, ("pc", 96), False, dict(PC=96, last=64)),
+    "pc112_r200": (200, 64, ("pc", 112), False, dict(PC=112, last=88)),
+    "pc128_r256": (256, 64, ("pc", 128), False, dict(PC=128, last=128)),
+    "pc128_r256_below_2cus": (256, 64, ("cus", 2, -1), False, dict(PC=128, split=True)),
+    "pc0_r256_at_2cus": (256, 64, ("cus", 2, 0), False, dict(PC=256, split=False)),
+    "pc64_r65_tiles": (65, ("i", 2, 48), 3, False, dict(PC=64, last=1, ilgT=9, tiles=3, G=(None, 3))),
+    "pc64_r255_tiles": (255, ("i", 2, 48), 3, False, dict(PC=64, last=63, ilgT=9, tiles=3, G=(None, 3))),
+    "pc80_r200_tiles": (200, ("i", 2, 48), ("pc", 80), False, dict(PC=80, last=40, ilgT=8, tiles=3, G=(None, 3))),
+    "pc96_r256_tiles": (256, ("i", 2, 48), ("pc", 96), False, dict(PC=96, last=64, ilgT=8, tiles=3, G=(None, 3))),
+    "pc112_r200_tiles": (200, ("i", 2, 48), ("pc", 112), False, dict(PC=112, last=88, ilgT=8, tiles=3, G=(None, 3))),
+    "pc128_r256_tiles": (256, ("i", 2, 48), ("pc", 128), False, dict(PC=128, last=128, ilgT=8, tiles=3, G=(None, 3))),
+    # one full frame of a very large block and a short one: a last tile of one group, i0 * R and p * B far from small
+    "large_block_r17": (17, (1 << 22) + 16, 1, True, dict(lgT=10, ilgT=10, G=(1, 1), tiles=4097, split=False)),
+    # R = 13: tiles of 2048 records
+    "lg11_r13": (13, 4112, 2, True, dict(lgT=11, ilgT=11, G=(1, 1), tiles=3)),
+}.items():
+    SWEEP[_id] = _row
+Case = namedtuple("Case", "id R B nfull tail claims")
+
+
+def resolve(key, cus):
+    """the row with its block size and frame count worked out for `cus` CUs; None where no frame count reaches its PC"""
+    R, B, nfull, tail, claims = SWEEP[key]
+    if isinstance(nfull, tuple) and nfull[0] == "pc":
+        hits = [n for n in range(1, 2 * cus) if plan_of(n, R, 64, True, cus).PC == nfull[1]]
+        if not hits:
+            return None
+        nfull = hits[0]
+    elif isinstance(nfull, tuple):
+        nfull = nfull[1] * cus + nfull[2]
+    if isinstance(B, tuple):
+        B = B[1] * max_tile(R, nfull, B[0] == "i", cus) + B[2]
+    return Case(key, R, B, nfull, tail, claims)
+
+
+def tail_bytes(c):
+    """the short frame of B // 3 + 1 records and R - 1 trailing bytes behind the full frames of a row that has one"""
+    return (c.B // 3 + 1) * c.R + c.R - 1 if c.tail else 0
+
+
+def claims_hold(c, cus):
+    """the row's launches, by redux_record_plan for `cus` CUs (0: the device's), are what the row is there for"""
+    fwd = plan_of(c.nfull, c.R, c.B, False, cus, tail=tail_bytes(c))
+    inv = plan_of(c.nfull, c.R, c.B, True, cus, tail=tail_bytes(c))
+    assert fwd.grid_fast and inv.grid_fast and bool(fwd.grid_bytes) == bool(inv.grid_bytes) == c.tail, c
+    got = {"lgT": fwd.lgT, "ilgT": inv.lgT, "PC": inv.PC, "last": c.R - (-(-c.R // inv.PC) - 1) * inv.PC, "split": inv.PC < c.R,
+           "tiles": -(-c.B // (1 << inv.lgT))}
+    for k, v in c.claims.items():
+        if k == "G":
+            for want, p in zip(v, (fwd, inv)):
+                last = c.B % (1 << p.lgT) or min(c.B, 1 << p.lgT)
+                assert want is None or last // 16 == want, (c, k, last // 16)
+        else:
+            assert got[k] == v, (c, k, got[k])
+    assert fwd.PC == c.R and (inv.PC == c.R or (inv.PC % 16 == 0 and 64 <= inv.PC < c.R))
+    return fwd, inv
+
+
+@pytest.mark.parametrize("cus", [256, 8])
+def test_the_sweep_reaches_what_it_claims(rx, cus):
+    """Every row of SWEEP resolves for these CU counts and its claims hold; and the rows, compared with a list written out
+    here, between them reach every PC, every tile size, both sides of R > 64 and of nfull < 2 * CUs, last ranges of 1, 17, 63
+    and 88 columns, and last tiles of 3, 7 and 63 groups behind full ones."""
+    want = ["groups_r%d_b%s" % (R, B) for R in (3, 16, 23, 64, 255, 256) for B in ("16", "32", "48", "80", "112", "1008", "T48")]
+    want += ["pc64_r255", "pc64_r81", "pc64_r65", "pc0_r64", "pc80_r200", "pc96_r256", "pc112_r200", "pc128_r256",
+             "pc128_r256_below_2cus", "pc0_r256_at_2cus", "pc64_r65_tiles", "pc64_r255_tiles", "pc80_r200_tiles", "pc96_r256_tiles",
+             "pc112_r200_tiles", "pc128_r256_tiles", "large_block_r17", "lg11_r13"]
+    assert sorted(SWEEP) == sorted(want) and len(SWEEP) == 42 + 18
+    cases = {k: resolve(k, cus) for k in SWEEP}
+    assert all(cases.values()), [k for k, c in cases.items() if c is None]
+    plans = {k: claims_hold(c, cus) for k, c in cases.items()}
+    claimed = lambda name: sorted(c.claims[name] for c in cases.values() if name in c.claims)  # noqa: E731
+    # the claims are of rows of their own: one row less and a value is claimed once less
+    assert claimed("PC") == [64] * 7 + [80, 80, 96, 96, 112, 112, 128, 128, 128, 256]
+    assert sorted(set(claimed("lgT") + claimed("ilgT"))) == list(range(4, LG_MAX + 1))
+    assert claimed("lgT") == [4, 5, 6, 7, 7, 7, 7, 9, 9, 10, 10, 10, 11, 12] and claimed("ilgT") == [8, 8, 8, 8, 9, 9, 9, 10, 11]
+    assert claimed("last") == [1, 1, 17, 40, 40, 63, 63, 63, 64, 64, 88, 88, 128, 128]
+    assert claimed("split") == [False] * 4 + [True] * 5
+    assert sorted(g for G in claimed_groups(cases) for g in G) == [1] * 4 + [3] * 15 + [5, 5, 7, 7, 7, 11, 31, 31, 31, 63, 63]
+    # the thresholds: R = 64 against 65 at one frame count; 2 * CUs - 1 frames against 2 * CUs at R = 256
+    a, b = cases["pc0_r64"], cases["pc64_r65"]
+    assert (a.R, b.R) == (64, 65) and a[2:5] == b[2:5] and plans["pc0_r64"][1].PC == 64 == a.R and plans["pc64_r65"][1].PC == 64 < b.R
+    a, b = cases["pc128_r256_below_2cus"], cases["pc0_r256_at_2cus"]
+    assert (a.nfull, b.nfull) == (2 * cus - 1, 2 * cus) and a.R == b.R == 256 and a.B == b.B
+    assert plans["pc128_r256_below_2cus"][1].grid_fast == 2 * a.nfull and plans["pc0_r256_at_2cus"][1].grid_fast == b.nfull
+    # a range's rows leave in pieces of 16: the ranges of the tile rows keep more than one tile a frame and a ragged last one
+    for k, c in cases.items():
+        if k.endswith("_tiles"):
+            T = 1 << plans[k][1].lgT
+            assert c.B == 2 * T + 48 and c.nfull < 2 * cus and c.R > 64
+        assert c.B % 16 == 0 and c.nfull * c.R * c.B + tail_bytes(c) <= 110 << 20, c   # (the largest buffer: about 100 MB)
+
+
+def claimed_groups(cases):
+    return [[g for g in c.claims["G"] if g is not None] for c in cases.values() if "G" in c.claims]
+
+
+def test_plan_budgets_for_every_record_size(rx):
+    """For every R in 2 .. 256, block sizes either side of every tile size and frame counts on both sides of the CU counts:
+    the tile fits the LDS array, the inverse's items fit their array, PC is R or a multiple of 16 of at least 64, a range
+    never outnumbers the columns, and the grids are what the header promises."""
+    from redux_amd import api
+    for cus in (256, 8):
+        for R in range(2, 257):
+            for B in (16, 48, 64, 1008, 4096, 4112, 1 << 16, (1 << 22) + 16):
+                for nfull in (1, 3, cus - 1, 2 * cus - 1, 2 * cus, 8 * cus + 37):
+                    for delta in (False, True):
+                        fwd = api.record_plan(nfull * R * B, B, R, delta, False, cus)
+                        inv = api.record_plan(nfull * R * B, B, R, delta, True, cus)
+                        at = (cus, R, B, nfull)
+                        for p in (fwd, inv):
+                            assert 4 <= p.lgT <= LG_MAX and (p.lgT == 4 or 1 << (p.lgT - 1) < B) and p.grid_bytes == 0, (at, p)
+                        T = 1 << fwd.lgT
+                        assert fwd.PC == R and tile_bytes(T, R) <= LDS_BYTES and fwd.grid_fast == min(nfull * -(-B // T), 8 * cus), (at, fwd)
+                        assert fwd.lgT == LG_MAX or T >= B or tile_bytes(2 * T, R) > LDS_BYTES, (at, fwd)     # no tile smaller than need be
+                        T, PC = 1 << inv.lgT, inv.PC
+                        assert PC == R or (PC % 16 == 0 and 64 <= PC < R and R > 64 and nfull < 2 * cus), (at, inv)
+                        nr = -(-R // PC)
+                        assert inv.grid_fast == min(nfull, 8 * cus) * nr and (nr - 1) * PC < R, (at, inv)
+                        assert tile_bytes(T, PC) <= LDS_BYTES and min(PC, R) * (T // 16) <= ITEMS, (at, inv)
+                        if nfull >= 2 * cus or R <= 64:
+                            assert PC == R, (at, inv)
+                        elif PC > 64:  # no narrower than it takes to give every CU two workgroups' worth
+                            assert nfull * -(-R // (PC - 16)) >= 2 * cus or -(-R // (PC - 16)) == nr, (at, inv)
+    # the byte kernels: a thread a byte, at most 8192 workgroups; the delta inverse a thread per (frame, column)
+    for R, B, L in ((4, 4100, 3 * 4 * 4100 + 5), (23, 4096, 23 * 4096 - 1), (4, 4100, 1 << 32), (256, 100, 7 * 25600 + 3)):
+        nfr = -(-L // (R * B))
+        for delta in (False, True):
+            assert api.record_plan(L, B, R, delta, False, 256) == (4, R, 0, min(-(-L // 256), 8192))
+            assert api.record_plan(L, B, R, delta, True, 256) == (4, R, 0, min(-(-(nfr * R if delta else L) // 256), 8192))
+    p = api.record_plan(2 * 23 * 4096 + 100, 4096, 23, True, True, 256)     # full frames, then a short one
+    assert p.grid_fast == 2 and p.grid_bytes == 1 and api.record_plan(2 * 23 * 4096 + 100, 4096, 23, False, True, 256).grid_bytes == 1
+    assert api.record_plan(0, 4096, 23) == (4, 23, 0, 0)
+    L = 3 * 255 * 4096   # cus = 0: the current device's CU count, whatever it is (256 without a device)
+    assert api.record_plan(L, 4096, 255, inverse=True) in {api.record_plan(L, 4096, 255, inverse=True, cus=c) for c in range(1, 1025)}
+    for kw in (dict(block_size=0, record_size=23), dict(block_size=64, record_size=1), dict(block_size=64, record_size=257)):
+        with pytest.raises(rx.InvalidInput):
+            api.record_plan(4096, **kw)
+
+
+def test_record_div_is_exact_for_every_divisor_and_dividend_the_kernels_pass():
+    """record_div(n, d, record_magic(d)) of redux_record.hpp, restated: m = 0xFFFFFFFF // d + 1 and n * m >> 32 (d = 1: n
+    itself).  The kernels divide chunk indices c < Gn * R <= 256 * 256 by the row width and piece indices it < Tn * npc <= 4096 * 16
+    by the pieces a row: every n below 2^16, every d in 1 .. 256."""
+    n = np.arange(1 << 16, dtype=np.uint64)
+    for d in range(1, 257):
+        m = np.uint64(0xFFFFFFFF // d + 1)
+        got = (n * m) >> np.uint64(32) if d > 1 else n
+        assert np.array_equal(got, n // np.uint64(d)), d
+        assert m < 1 << 32 or d == 1                    # the reciprocal is a 32-bit value (and unused for d = 1)
+    assert 256 * 256 <= 1 << 16 and 4096 * 16 <= 1 << 16 and (LDS_BYTES // 16) * 16 == LDS_BYTES

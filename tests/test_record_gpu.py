@@ -2,7 +2,11 @@
 two, odd sizes, either side of a 16-byte chunk and the maximum, the byte-plane kernels at R = 2, 4, 8, more frames than
 workgroups, a frame whose tiles all need carries, wrapping extremes, the streams of every layer against the CPU oracle on the
 transformed bytes, the host pipeline over chunks that are whole frames but not whole waves, a damaged stream, and the device
-coder objects with their range reads, the container and the CLI end to end, and the C++ mirror."""
+coder objects with their range reads, the container and the CLI end to end, and the C++ mirror.  Then the shapes of the
+launch plan (SWEEP of test_record_cpu.py, each asserted by redux_record_plan before it runs): group counts that are no power
+of two, ragged last tiles behind full ones, column ranges of every width with last ranges of 1 to 128 columns, the thresholds
+of the cut, a very large block; more frames than workgroups with several tiles a frame; buffers aligned to 16 bytes and no
+more; R = 2, 4, 8 with the delta."""
 import ctypes as C
 import zlib
 
@@ -12,7 +16,7 @@ import pytest
 from oracle import cbind as ox
 from test_lag_order_gpu import FRONT, first_difference, poison_intact, poisoned
 from test_planes_gpu import FILL, guarded, guards_intact, split
-from test_record_cpu import generated_tables, record_ref
+from test_record_cpu import SWEEP, claims_hold, generated_tables, plan_of, record_ref, resolve, tail_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -156,6 +160,127 @@ def test_record_kernels_on_extremes(rx, R):
             assert intact and np.array_equal(y, record_ref(x, R, B, True)), (R, B, name)
             back, intact, _ = run_dev(torch, y, R, B, True, True)
             assert intact and np.array_equal(back, x), (R, B, name)
+
+
+# ---- the shapes of the launch plan --------------------------------------------------------------------------------------
+def where_wrong(got, want, R, B, inverse):
+    """the first wrong byte as (frame, column, record): the inverse writes records, the forward call byte columns"""
+    at = int(np.nonzero(got != want)[0][0])
+    f, o = divmod(at, R * B)
+    N = min(len(got) - f * R * B, R * B) // R
+    if o >= N * R:
+        return f"first wrong byte {at}: frame {f}, trailing byte {o - N * R}"
+    p, i = (o % R, o // R) if inverse else (o // N, o % N)
+    return f"first wrong byte {at}: frame {f}, column {p}, record {i} of {N}"
+
+
+def cu_count(torch):
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def check_both_ways(torch, x, R, B, names, so=0, do=0):
+    """forward and inverse, with and without the delta, of x against the restatement, between poison and guards"""
+    for delta in (False, True):
+        want = record_ref(x, R, B, delta)
+        for inverse, a, b in ((False, x, want), (True, want, x)):
+            got, intact, name = run_dev(torch, a, R, B, delta, inverse, so, do)
+            assert name == names[inverse], (R, B, inverse, name)
+            assert np.array_equal(got, b), (R, B, "inverse" if inverse else "forward", "delta" if delta else "plain", so, do,
+                                            where_wrong(got, b, R, B, inverse))
+            assert intact, (R, B, inverse, delta, so, do)
+
+
+@pytest.mark.parametrize("key", sorted(SWEEP))
+def test_the_sweep_of_the_launch_plan(rx, key):
+    """SWEEP of test_record_cpu.py on the device: group counts that are no power of two, ragged last tiles behind full ones,
+    every width of a column range with last ranges of 1 to 128 columns, both sides of R > 64 and of nfull < 2 * CUs, a very
+    large block.  Each row first asserts, by redux_record_plan for this device, that it reaches what it is there for."""
+    import torch
+    cus = cu_count(torch)
+    c = resolve(key, cus)
+    if c is None:
+        pytest.skip("no frame count gives the inverse PC = %d on a device of %d CUs (pinned for 256 CUs on the CPU)" % (SWEEP[key][2][1], cus))
+    fwd, inv = claims_hold(c, 0)
+    tail = tail_bytes(c)
+    assert (fwd, inv) == (plan_of(c.nfull, c.R, c.B, False, cus, tail=tail), plan_of(c.nfull, c.R, c.B, True, cus, tail=tail))
+    x = np.random.default_rng(len(key) + c.R * 7 + c.B).integers(0, 256, c.nfull * c.R * c.B + tail, dtype=np.uint8)
+    check_both_ways(torch, x, c.R, c.B, {i: FAST[i] + (" + " + BYTES[i] if tail else "") for i in (False, True)})
+
+
+def run_dev_tensor(torch, d_x, R, B, delta, inverse):
+    """run_dev for an input that is on the device already -> (result on the device, guards intact)"""
+    from redux_amd import api
+    from test_planes_gpu import GUARD
+    L = d_x.numel()
+    ts = torch.full((FRONT + L + GUARD + 16,), FILL, dtype=torch.uint8, device="cuda:0")
+    src = ts[FRONT: FRONT + L]
+    src.copy_(d_x)
+    td, dst = guarded(torch, L)
+    api.record_planes(src, R, B, delta=delta, inverse=inverse, out=dst)
+    torch.cuda.synchronize()
+    assert api.record_kernel_name(L, B, R, inverse, d_src=src, d_dst=dst) == FAST[inverse]
+    intact = all(bool((t == FILL).all()) for t in (ts[:FRONT], ts[FRONT + L:], td[:GUARD], td[GUARD + L:])) and torch.equal(src, d_x)
+    return dst, intact
+
+
+@pytest.mark.parametrize("R, add", [(23, 48), (255, 16)])
+def test_more_frames_than_workgroups_with_several_tiles_a_frame(rx, R, add):
+    """8 * CUs + 37 frames of B = 2 * T + 48 (R = 23: three tiles, the last of 3 groups) and 2 * T + 16 (R = 255) records: some
+    workgroups of the inverse walk on to a second frame of several tiles with the carries, their parity and the LDS tile the
+    first left, others do not; the forward kernel's tile stride wraps.  The frames are drawn on the device from four
+    distinct ones, so the restatement is of four frames."""
+    import torch
+    from redux_amd import api
+    cus = cu_count(torch)
+    nfull = 8 * cus + 37
+    T = 1 << plan_of(nfull, R, 1 << 16, True, cus).lgT
+    B = 2 * T + add
+    fwd, inv = api.record_plan(nfull * R * B, B, R, True, False), api.record_plan(nfull * R * B, B, R, True, True)
+    assert inv == (T.bit_length() - 1, R, 8 * cus, 0) and inv.grid_fast < nfull < 2 * inv.grid_fast
+    assert fwd.grid_fast == 8 * cus and fwd.grid_bytes == 0 and -(-B // (1 << fwd.lgT)) >= 3 and B % (1 << fwd.lgT) == add
+    assert B % T == add and nfull * R * B < 256 << 20
+    rng = np.random.default_rng(R)
+    x4 = rng.integers(0, 256, (4, R * B), dtype=np.uint8)
+    pick = torch.from_numpy(rng.integers(0, 4, nfull)).cuda()
+    assert len(set(pick[:37].tolist()) | set(pick[8 * cus:].tolist())) > 1
+    d_x = torch.from_numpy(x4).cuda()[pick].reshape(-1)
+    for delta in (False, True):
+        want4 = record_ref(x4.reshape(-1), R, B, delta).reshape(4, R * B)
+        assert not np.array_equal(want4, x4)
+        d_want = torch.from_numpy(want4).cuda()[pick].reshape(-1)
+        for inverse, a, b in ((False, d_x, d_want), (True, d_want, d_x)):
+            got, intact = run_dev_tensor(torch, a, R, B, delta, inverse)
+            if not torch.equal(got, b):
+                raise AssertionError((R, B, "inverse" if inverse else "forward", "delta" if delta else "plain",
+                                      where_wrong(got.cpu().numpy(), b.cpu().numpy(), R, B, inverse)))
+            assert intact, (R, B, inverse, delta)
+
+
+@pytest.mark.parametrize("R", [5, 16])
+def test_buffers_that_are_16_byte_aligned_and_no_more(rx, R):
+    """source and destination 16 and 48 bytes off a 256-byte boundary, in every combination: the fast kernels, whose 16-byte
+    accesses are then aligned to 16 bytes and nothing more; 8 bytes off: the byte kernels"""
+    import torch
+    B = 4112
+    x = np.random.default_rng(R).integers(0, 256, 2 * R * B + (B // 3 + 1) * R + R - 1, dtype=np.uint8)
+    p = plan_of(2, R, B, True, 0, tail=(B // 3 + 1) * R + R - 1)
+    assert p.grid_fast == 2 and p.grid_bytes and B > 1 << p.lgT
+    for so in (16, 48):
+        for do in (16, 48):
+            check_both_ways(torch, x, R, B, {i: FAST[i] + " + " + BYTES[i] for i in (False, True)}, so, do)
+    for so, do in ((8, 0), (0, 8), (8, 8), (16, 8)):
+        check_both_ways(torch, x, R, B, BYTES, so, do)
+
+
+@pytest.mark.parametrize("R", [2, 4, 8])
+def test_small_power_of_two_records_with_the_delta(rx, R):
+    """R = 2, 4, 8 at 3 and 63 groups a frame against the restatement, the delta included (test_record_layout_equals_byte_plane_kernels
+    compares them with the byte-plane kernels, which have no delta)"""
+    import torch
+    for B in (48, 1008):
+        x = np.random.default_rng(R + B).integers(0, 256, 2 * R * B + (B // 3 + 1) * R + R - 1, dtype=np.uint8)
+        assert plan_of(2, R, B, True, 0).PC == R
+        check_both_ways(torch, x, R, B, {i: FAST[i] + " + " + BYTES[i] for i in (False, True)})
 
 
 def test_record_planes_dev_rejects_bad_arguments(rx, lib):
