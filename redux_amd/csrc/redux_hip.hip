@@ -14,8 +14,8 @@
 //   redux_planes.hpp   k_planes: the byte-plane layout of typed data, a byte transform in front of the coder
 //   redux_delta.hpp    k_delta_planes / k_delta_unplanes: the delta filter for integer series, fused with the layout
 //   redux_zigzag.hpp   the zigzag fold: k_delta_*<E, true> is the delta filter with folded differences, for signed series
-//   redux_lag.hpp      k_lag_planes / k_lag_unplanes: the lagged delta filter for interleaved channels, the predecessor S elements back
-//   redux_lag_order.hpp k_lag_order_planes / k_lag_order_unplanes: higher-order lagged differences, the lag filter applied K times
+//   redux_lag.hpp      k_lag_planes / k_lag_unplanes: the lagged delta filter for interleaved channels, the predecessor S elements back;
+//                      k_lag_order_planes / k_lag_order_unplanes: its higher orders, the filter applied K times, from the same bodies
 //   redux_record.hpp   k_record_planes / k_record_unplanes: the record layout for fixed-width structs, R bytes a record, with a byte delta
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_base_sub.hpp BaseSubFold: the base filter's folded difference, the same kernels under another operation
@@ -27,8 +27,8 @@
 //   redux_const.hpp    k_const_select / k_const_table / k_const_fill: constant blocks, one byte for a block of equal bytes
 //   redux_cost.hpp     k_block_cost / k_table_cost: size estimates, a block's cost under a model from its counts
 //   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
-//   redux_lag_cost.hpp  k_lag_cost: the adaptive cost of every block behind the lagged delta filter, for a list of lags
-//   redux_lag_order_cost.hpp  k_lag_order_cost: the same behind higher-order lagged differences, for (lag, order) candidates
+//   redux_lag_cost.hpp  k_lag_cost: the adaptive cost of every block behind the lagged delta filter, for a list of lags;
+//                      k_lag_order_cost: the same behind its higher orders, for (lag, order) candidates, from the same bodies
 //   redux_mixed.hpp    k_mixed_choose / k_mixed_planes: a layout per unit of 8 blocks, chosen from those costs on the device
 //   redux_range.hpp    k_segment_copy: range reads, the plan of the covered granules and the segmented byte copy
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
@@ -52,7 +52,6 @@
 #include "redux_delta.hpp"
 #include "redux_zigzag.hpp"
 #include "redux_lag.hpp"
-#include "redux_lag_order.hpp"
 #include "redux_record.hpp"
 #include "redux_base.hpp"
 #include "redux_base_sub.hpp"
@@ -66,7 +65,6 @@
 #include "redux_cost.hpp"
 #include "redux_layout_cost.hpp"
 #include "redux_lag_cost.hpp"
-#include "redux_lag_order_cost.hpp"
 #include "redux_lag_order_cost_list.hpp"
 #include "redux_mixed.hpp"
 #include "redux_range.hpp"
@@ -607,10 +605,14 @@ static int launch_planes(const void *d_src, void *d_dst, uint64_t len, uint32_t 
     return REDUX_OK;
 }
 
-// the delta filter, its differences folded (FOLD: the zigzag-folded filter) or not: forward as the layout; the inverse a
-// workgroup per frame (a frame's running sum)
-template <int E, bool FOLD>
-static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, bool inverse, hipStream_t s)
+// the filters with a running sum per frame -- the delta filter, its differences plain or folded (redux_delta.hpp,
+// redux_zigzag.hpp), the lagged delta filter and its higher orders (redux_lag.hpp) -- through a filter's four kernels:
+// forward as the layout, the inverse a workgroup per frame, the byte kernels for the rest.  extra: the kernels' arguments
+// after PlanesArgs (the lag, the order)
+template <int E, typename... T>
+static int launch_filter(void (*planes)(PlanesArgs, T...), void (*unplanes)(PlanesArgs, T...), void (*planes_bytes)(PlanesArgs, T...),
+                         void (*unplanes_bytes)(PlanesArgs, T...), const void *d_src, void *d_dst, uint64_t len, uint32_t block_size,
+                         bool inverse, hipStream_t s, T... extra)
 {
     const uint64_t   frame = (uint64_t)E * block_size;
     const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
@@ -618,70 +620,17 @@ static int launch_delta(const void *d_src, void *d_dst, uint64_t len, uint32_t b
     if (f.nfull) {
         uint32_t grid;
         if (inverse)
-            k_delta_unplanes<E, FOLD><<<grid_frames(f.nfull), 256, 0, s>>>(a);
+            unplanes<<<grid_frames(f.nfull), 256, 0, s>>>(a, extra...);
         else if (!grid_tiles((a.groups + 255) / 256, &grid))
             return REDUX_UNSUPPORTED;
         else
-            k_delta_planes<E, FOLD><<<grid, 256, 0, s>>>(a);
+            planes<<<grid, 256, 0, s>>>(a, extra...);
     }
     if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
         if (inverse)
-            k_delta_unplanes_bytes<E, FOLD><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a);
+            unplanes_bytes<<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a, extra...);
         else
-            k_delta_planes_bytes<E, FOLD><<<grid_bytes(len - f.rest), 256, 0, s>>>(a);
-    }
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
-}
-
-// the lagged delta filter (redux_lag.hpp): the split and the grids of launch_delta, the lag a kernel argument
-template <int E>
-static int launch_lag(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t lag, bool inverse, hipStream_t s)
-{
-    const uint64_t   frame = (uint64_t)E * block_size;
-    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
-    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
-    if (f.nfull) {
-        uint32_t grid;
-        if (inverse)
-            k_lag_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a, lag);
-        else if (!grid_tiles((a.groups + 255) / 256, &grid))
-            return REDUX_UNSUPPORTED;
-        else
-            k_lag_planes<E><<<grid, 256, 0, s>>>(a, lag);
-    }
-    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
-        if (inverse)
-            k_lag_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a, lag);
-        else
-            k_lag_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a, lag);
-    }
-    HIP_TRY(hipGetLastError());
-    return REDUX_OK;
-}
-
-// higher-order lagged differences (redux_lag_order.hpp): launch_lag with the order a second kernel argument
-template <int E>
-static int launch_lag_order(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t lag, uint32_t order,
-                            bool inverse, hipStream_t s)
-{
-    const uint64_t   frame = (uint64_t)E * block_size;
-    const FastSplit  f = fast_split(len, frame, block_size, {d_src, d_dst});
-    const PlanesArgs a = planes_args(d_src, d_dst, len, block_size, f);
-    if (f.nfull) {
-        uint32_t grid;
-        if (inverse)
-            k_lag_order_unplanes<E><<<grid_frames(f.nfull), 256, 0, s>>>(a, lag, order);
-        else if (!grid_tiles((a.groups + 255) / 256, &grid))
-            return REDUX_UNSUPPORTED;
-        else
-            k_lag_order_planes<E><<<grid, 256, 0, s>>>(a, lag, order);
-    }
-    if (f.rest < len) { // the short last frame, or everything the fused kernels cannot take
-        if (inverse)
-            k_lag_order_unplanes_bytes<E><<<grid_frames((len - f.rest + frame - 1) / frame), 256, 0, s>>>(a, lag, order);
-        else
-            k_lag_order_planes_bytes<E><<<grid_bytes(len - f.rest), 256, 0, s>>>(a, lag, order);
+            planes_bytes<<<grid_bytes(len - f.rest), 256, 0, s>>>(a, extra...);
     }
     HIP_TRY(hipGetLastError());
     return REDUX_OK;
@@ -830,8 +779,8 @@ static int for_element_size(uint32_t element_size, F &&f)
 }
 
 // The filter in front of the byte-plane layout: none; the delta filter, its differences plain or folded (redux_delta.hpp,
-// redux_zigzag.hpp); the lagged delta filter, whose lag travels next to the value (redux_lag.hpp), and its higher orders,
-// whose order travels there too (redux_lag_order.hpp); the base filter, the XOR or the folded difference (redux_base.hpp,
+// redux_zigzag.hpp); the lagged delta filter, whose lag travels next to the value, and its higher orders,
+// whose order travels there too (redux_lag.hpp); the base filter, the XOR or the folded difference (redux_base.hpp,
 // redux_base_sub.hpp).  The one name a filter has from the C entry points down to
 // the kernel launch: a new filter is a new value here.
 // RecordDelta is the byte delta of the record layout (redux_record.hpp) and goes with a record size only; the record layout
@@ -875,10 +824,18 @@ static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t
         switch (filter) {
         case Filter::BaseSub: return launch_base<E, true>(d_src, d_base, used, d_dst, len, block_size, inv, s);
         case Filter::BaseXor: return launch_base<E, false>(d_src, d_base, used, d_dst, len, block_size, inv, s);
-        case Filter::LagOrder: return launch_lag_order<E>(d_src, d_dst, len, block_size, lag, order, inv, s);
-        case Filter::Lag: return launch_lag<E>(d_src, d_dst, len, block_size, lag, inv, s);
-        case Filter::Zigzag: return launch_delta<E, true>(d_src, d_dst, len, block_size, inv, s);
-        case Filter::Delta: return launch_delta<E, false>(d_src, d_dst, len, block_size, inv, s);
+        case Filter::LagOrder:
+            return launch_filter<E>(k_lag_order_planes<E>, k_lag_order_unplanes<E>, k_lag_order_planes_bytes<E>,
+                                    k_lag_order_unplanes_bytes<E>, d_src, d_dst, len, block_size, inv, s, lag, order);
+        case Filter::Lag:
+            return launch_filter<E>(k_lag_planes<E>, k_lag_unplanes<E>, k_lag_planes_bytes<E>, k_lag_unplanes_bytes<E>, d_src, d_dst,
+                                    len, block_size, inv, s, lag);
+        case Filter::Zigzag:
+            return launch_filter<E>(k_delta_planes<E, true>, k_delta_unplanes<E, true>, k_delta_planes_bytes<E, true>,
+                                    k_delta_unplanes_bytes<E, true>, d_src, d_dst, len, block_size, inv, s);
+        case Filter::Delta:
+            return launch_filter<E>(k_delta_planes<E, false>, k_delta_unplanes<E, false>, k_delta_planes_bytes<E, false>,
+                                    k_delta_unplanes_bytes<E, false>, d_src, d_dst, len, block_size, inv, s);
         case Filter::RecordDelta: // (refused above)
         case Filter::None: break;
         }
@@ -1088,7 +1045,7 @@ static int launch_layout_cost(const void *d_in, uint64_t in_len, uint32_t block_
     return REDUX_OK;
 }
 
-// ---- lag estimates (redux_lag_cost.hpp) -------------------------------------------------------------------------------
+// ---- lag and order estimates (redux_lag_cost.hpp) ---------------------------------------------------------------------
 // the selected frames (0, T, 2T, ...) of an input of nblocks blocks, and the blocks they have: all but the last E each
 static uint64_t lag_cost_selected(uint64_t nblocks, uint32_t E, uint32_t frame_step, uint64_t *row_blocks)
 {
@@ -1098,42 +1055,11 @@ static uint64_t lag_cost_selected(uint64_t nblocks, uint32_t E, uint32_t frame_s
     return nsel;
 }
 
+// the lag and the order estimates: the fast kernel for the selected full frames, the byte kernel for the rest of a row.
+// a.lags and a.orders (and a.ncand) are filled by the caller: redux_lag_cost_dev, redux_lag_order_cost_dev
 template <int E>
-static int launch_lag_cost(const void *d_in, uint64_t in_len, uint32_t block_size, const uint32_t *lags, uint32_t nlags,
-                           uint32_t frame_step, double *bits, hipStream_t s)
-{
-    LagCostArgs a;
-    a.in         = (const uint8_t *)d_in;
-    a.in_len     = in_len;
-    a.nblocks    = redux_block_count(in_len, block_size);
-    a.bits       = bits;
-    a.block_size = block_size;
-    a.frame_step = frame_step;
-    a.nlags      = nlags;
-    lag_cost_selected(a.nblocks, E, frame_step, &a.row_blocks);
-    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
-    a.nsel_fast  = (nfull + frame_step - 1) / frame_step;
-    for (uint32_t j = 0; j < REDUX_LAG_MAX; j++) // (the list travels in the kernel's arguments: consumed before the call returns)
-        a.lags[j] = (uint16_t)(j < nlags ? lags[j] : 0);
-    if (a.nsel_fast) { // one workgroup of four waves per CU: 160 KiB of LDS
-        const uint64_t jobs = a.nsel_fast * ((nlags + kLagCostWaves - 1) / kLagCostWaves), cap = cu_count();
-        k_lag_cost<E><<<(uint32_t)(jobs < cap ? jobs : cap), 64 * kLagCostWaves, 0, s>>>(a);
-        HIP_TRY(hipGetLastError());
-    }
-    const uint64_t nrest = a.row_blocks - a.nsel_fast * E;
-    if (nrest) { // a selected short last frame, or everything the fast kernel cannot take
-        const uint64_t work = nrest * nlags, cap = (uint64_t)kHistWgsPerCu * cu_count();
-        k_lag_cost_bytes<E><<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
-        HIP_TRY(hipGetLastError());
-    }
-    return REDUX_OK;
-}
-
-// ---- order estimates (redux_lag_order_cost.hpp) -------------------------------------------------------------------------
-// (a.lags and a.orders are filled by the caller: redux_lag_order_cost_dev)
-template <int E>
-static int launch_lag_order_cost(LagOrderCostArgs &a, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t ncand,
-                                 uint32_t frame_step, double *bits, hipStream_t s)
+static int launch_lag_cost(void (*fast)(LagCostArgs), void (*bytes)(LagCostArgs), LagCostArgs &a, const void *d_in, uint64_t in_len,
+                           uint32_t block_size, uint32_t frame_step, double *bits, hipStream_t s)
 {
     a.in         = (const uint8_t *)d_in;
     a.in_len     = in_len;
@@ -1141,19 +1067,18 @@ static int launch_lag_order_cost(LagOrderCostArgs &a, const void *d_in, uint64_t
     a.bits       = bits;
     a.block_size = block_size;
     a.frame_step = frame_step;
-    a.ncand      = ncand;
     lag_cost_selected(a.nblocks, E, frame_step, &a.row_blocks);
     const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
     a.nsel_fast  = (nfull + frame_step - 1) / frame_step;
     if (a.nsel_fast) { // one workgroup of four waves per CU: 160 KiB of LDS
-        const uint64_t jobs = a.nsel_fast * ((ncand + kLagCostWaves - 1) / kLagCostWaves), cap = cu_count();
-        k_lag_order_cost<E><<<(uint32_t)(jobs < cap ? jobs : cap), 64 * kLagCostWaves, 0, s>>>(a);
+        const uint64_t jobs = a.nsel_fast * ((a.ncand + kLagCostWaves - 1) / kLagCostWaves), cap = cu_count();
+        fast<<<(uint32_t)(jobs < cap ? jobs : cap), 64 * kLagCostWaves, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
     }
     const uint64_t nrest = a.row_blocks - a.nsel_fast * E;
     if (nrest) { // a selected short last frame, or everything the fast kernel cannot take
-        const uint64_t work = nrest * ncand, cap = (uint64_t)kHistWgsPerCu * cu_count();
-        k_lag_order_cost_bytes<E><<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
+        const uint64_t work = nrest * a.ncand, cap = (uint64_t)kHistWgsPerCu * cu_count();
+        bytes<<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
     }
     return REDUX_OK;
@@ -2518,8 +2443,8 @@ int redux_static_decode_blocks(const redux_params *p, const uint32_t *cum, const
 }
 
 // ---- the layered adaptive calls: byte-plane layout, delta, zigzag, lag, lag_order, base and base_sub ------------------
-// Seven families of eight entry points (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_lag.hpp,
-// redux_lag_order.hpp, redux_base.hpp, redux_base_sub.hpp), one Filter each: every body below the shared functions is one call into them.
+// Seven families of eight entry points (redux_planes.hpp, redux_delta.hpp, redux_zigzag.hpp, redux_lag.hpp twice,
+// redux_base.hpp, redux_base_sub.hpp), one Filter each: every body below the shared functions is one call into them.
 int redux_planes_check(uint32_t element_size)
 {
     return (element_size == 1 || element_size == 2 || element_size == 4 || element_size == 8) ? REDUX_OK : REDUX_INVALID_INPUT;
@@ -4835,10 +4760,26 @@ int redux_lag_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len,
     const int st = adaptive_cost_check(p, block_size);
     if (st != REDUX_OK)
         return st;
+    LagCostArgs a = {}; // (the list travels in the kernels' arguments: consumed before the call returns)
+    a.ncand = nlags;
+    for (uint32_t j = 0; j < nlags; j++)
+        a.lags[j] = (uint16_t)lags[j];
     return for_element_size(element_size, [&](auto e) -> int {
-        return launch_lag_cost<decltype(e)::value>(d_in, in_len, block_size, lags, nlags, frame_step, (double *)d_bits,
-                                                   (hipStream_t)stream);
+        constexpr int E = decltype(e)::value;
+        return launch_lag_cost<E>(k_lag_cost<E>, k_lag_cost_bytes<E>, a, d_in, in_len, block_size, frame_step, (double *)d_bits,
+                                  (hipStream_t)stream);
     });
+}
+
+// what launch_lag_cost launches, from a family's names for E = 1, 2, 4, 8: {fast, both, bytes}
+static const char *lag_cost_kernel_name(const char *const (&names)[4][3], const void *d_in, uint64_t in_len, uint32_t block_size,
+                                        uint32_t element_size)
+{
+    if (block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK)
+        return "";
+    const uint32_t E = element_size, e = E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : 3;
+    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
+    return names[e][nfull == 0 ? 2 : nfull * E < redux_block_count(in_len, block_size) ? 1 : 0];
 }
 
 const char *redux_lag_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size)
@@ -4849,11 +4790,7 @@ const char *redux_lag_cost_kernel_name_at(const void *d_in, uint64_t in_len, uin
         {"k_lag_cost<4>", "k_lag_cost<4> + k_lag_cost_bytes<4>", "k_lag_cost_bytes<4>"},
         {"k_lag_cost<8>", "k_lag_cost<8> + k_lag_cost_bytes<8>", "k_lag_cost_bytes<8>"},
     };
-    if (block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK)
-        return "";
-    const uint32_t E = element_size, e = E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : 3;
-    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
-    return names[e][nfull == 0 ? 2 : nfull * E < redux_block_count(in_len, block_size) ? 1 : 0];
+    return lag_cost_kernel_name(names, d_in, in_len, block_size, element_size);
 }
 
 const char *redux_lag_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size)
@@ -4868,15 +4805,17 @@ int redux_lag_order_cost_dev(const redux_params *p, const void *d_in, uint64_t i
     if (!p || block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK || frame_step == 0 ||
         !d_bits || (in_len && !d_in))
         return REDUX_INVALID_INPUT;
-    LagOrderCostArgs a; // (the lists travel in the kernels' arguments: consumed before the call returns)
+    LagCostArgs a; // (the lists travel in the kernels' arguments: consumed before the call returns)
     if (!lag_order_cost_list(element_size, lags, orders, ncand, REDUX_LAG_ORDER_COST_MAX, a.lags, a.orders, redux_lag_order_check))
         return REDUX_INVALID_INPUT;
+    a.ncand = ncand;
     const int st = adaptive_cost_check(p, block_size);
     if (st != REDUX_OK)
         return st;
     return for_element_size(element_size, [&](auto e) -> int {
-        return launch_lag_order_cost<decltype(e)::value>(a, d_in, in_len, block_size, ncand, frame_step, (double *)d_bits,
-                                                         (hipStream_t)stream);
+        constexpr int E = decltype(e)::value;
+        return launch_lag_cost<E>(k_lag_order_cost<E>, k_lag_order_cost_bytes<E>, a, d_in, in_len, block_size, frame_step,
+                                  (double *)d_bits, (hipStream_t)stream);
     });
 }
 
@@ -4888,11 +4827,7 @@ const char *redux_lag_order_cost_kernel_name_at(const void *d_in, uint64_t in_le
         {"k_lag_order_cost<4>", "k_lag_order_cost<4> + k_lag_order_cost_bytes<4>", "k_lag_order_cost_bytes<4>"},
         {"k_lag_order_cost<8>", "k_lag_order_cost<8> + k_lag_order_cost_bytes<8>", "k_lag_order_cost_bytes<8>"},
     };
-    if (block_size == 0 || block_size > (1u << 30) || redux_planes_check(element_size) != REDUX_OK)
-        return "";
-    const uint32_t E = element_size, e = E == 1 ? 0 : E == 2 ? 1 : E == 4 ? 2 : 3;
-    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, E);
-    return names[e][nfull == 0 ? 2 : nfull * E < redux_block_count(in_len, block_size) ? 1 : 0];
+    return lag_cost_kernel_name(names, d_in, in_len, block_size, element_size);
 }
 
 const char *redux_lag_order_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size)

@@ -79,6 +79,9 @@ for _E in (1, 2, 4, 8):
         # the counter fold inside a block: one byte value, 16 bytes above the bound of kLayoutFoldRows
         (_E, _above_fold(_E), _E * _above_fold(_E), 0, "one", [1, 2]),
     ]
+# E = 1, B = 5120: five rows of 64 groups, no multiple of the eight rows of a step; one, four and five lags (one wave of a
+# workgroup, all four, and one of a second job)
+CASES += [(1, 5120, 3 * 5120 + 100, 0, "walk", _l) for _l in ([3], [1, 3, 2, 256], [3, 1, 17, 2, 255])]
 
 
 def _place(a, shift):

@@ -57,15 +57,21 @@ def run_dev(rx, torch, x, E, B, S, inverse, so=0, do=0, zigzag=False):
 # ---- the kernels ----------------------------------------------------------------------------------------------------
 # B = 64: 4 groups a frame, most lags beyond a frame's 64 elements; 4096: exactly one row of the inverse; 4112: 257 groups, a
 # second row of one group: the carry and, for lags that do not divide 4096, the moving chain phase; 12304: three rows and a
-# group; 100 and 4099: the byte kernels.  Three full frames, a short one and trailing bytes each.
+# group; 8192: two full rows; 100 and 4099: the byte kernels.  Three full frames, a short one and trailing bytes each; at
+# 4099 also a short frame of E * B - 1 bytes, one byte less than a full one.
 @pytest.mark.parametrize("E", [1, 2, 4, 8])
-@pytest.mark.parametrize("B", [64, 4096, 4112, 12304, 100, 4099])
+@pytest.mark.parametrize("B", [64, 4096, 4112, 8192, 12304, 100, 4099])
 def test_lag_planes_dev_matches_restatement(rx, E, B):
     import torch
     rng = np.random.default_rng(E * 7 + B)
     L = 3 * E * B + (B // 3 + 1) * E + (E - 1)
     x = rng.integers(0, 256, L, dtype=np.uint8)
     for S in LAGS:
+        if B == 4099 and S in (1, 3, 255, 256):
+            xs = x[: 3 * E * B - 1]
+            for inverse in (False, True):
+                got, intact = run_dev(rx, torch, xs, E, B, S, inverse, 1, 0)
+                assert intact and np.array_equal(got, lag_planes_ref(xs, E, B, S, inverse=inverse)), (E, B, S, inverse)
         want = {inverse: lag_planes_ref(x, E, B, S, inverse=inverse) for inverse in (False, True)}
         for so, do in ((0, 0), (1, 0), (0, 1)):  # aligned; source, destination off by a byte: everything on the byte path
             for inverse in (False, True):

@@ -65,11 +65,12 @@ def run_dev(torch, x, E, B, S, K, inverse, so=0, do=0, lag_only=False):
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------
 # B = 64: 4 groups a frame, N = 64; 4096: exactly one row of the inverse; 4112: a row and a group: the per-level carries;
-# 12304: three rows and a group: the carries again and, for lags that do not divide 4096, the moving chain phase; 100 and 4099:
-# the byte kernels, the buffers also one byte off.  Two full frames, a short one and trailing bytes each.
+# 8192: two full rows; 12304: three rows and a group: the carries again and, for lags that do not divide 4096, the moving chain
+# phase; 100 and 4099: the byte kernels, the buffers also one byte off.  Two full frames, a short one and trailing bytes each;
+# at 4099 also a short frame of E * B - 1 bytes, one byte less than a full one.
 @pytest.mark.parametrize("K", [1, 2, 3])
 @pytest.mark.parametrize("E", [1, 2, 4, 8])
-@pytest.mark.parametrize("B", [64, 4096, 4112, 12304, 100, 4099])
+@pytest.mark.parametrize("B", [64, 4096, 4112, 8192, 12304, 100, 4099])
 def test_lag_order_planes_dev_matches_restatement(rx, E, B, K):
     import torch
     rng = np.random.default_rng(E * 7 + B + K)
@@ -77,6 +78,11 @@ def test_lag_order_planes_dev_matches_restatement(rx, E, B, K):
     x = rng.integers(0, 256, L, dtype=np.uint8)
     offsets = ((0, 0), (1, 0), (0, 1)) if B in (100, 4099) else ((0, 0),)
     for S in LAGS:
+        if B == 4099 and S in (1, 3, 255, 256):
+            xs = x[: 3 * E * B - 1]
+            for inverse in (False, True):
+                got, intact = run_dev(torch, xs, E, B, S, K, inverse, 1, 0)
+                assert intact and np.array_equal(got, lag_order_planes_ref(xs, E, B, S, K, inverse=inverse)), (E, B, S, K, inverse)
         want = {inverse: lag_order_planes_ref(x, E, B, S, K, inverse=inverse) for inverse in (False, True)}
         for so, do in offsets:
             for inverse in (False, True):
