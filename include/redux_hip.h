@@ -1208,6 +1208,46 @@ int         redux_lag_order_cost_dev(const redux_params *p, const void *d_in, ui
 const char *redux_lag_order_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size);
 const char *redux_lag_order_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size);
 
+/* ---- record estimates -----------------------------------------------------------------------------------
+ * The adaptive model's cost of every block of the input behind the record layout, for a list of candidates (R, F): R a
+ * record size redux_record_check accepts, F the byte delta (0 or 1).  bits[c][b] is what redux_block_cost_dev gives for
+ * block b of what redux_record_planes_dev writes for candidate c, counted from the untransformed bytes: no transformed copy
+ * and no workspace.  The fresh start of every frame of R * block_size bytes, the short last frame with its trailing bytes,
+ * and in_len == 0 (one empty block per row) are part of the rule.
+ *
+ * Frame sampling.  Candidates have frames of different sizes, so the call takes sample_blocks Q in place of a frame step.
+ * Q == 0 costs every frame.  For Q > 0, with nframes = max(1, ceil(in_len / (R * block_size))) and want = ceil(Q / R), the
+ * step is T = 1 if nframes <= want and ceil(nframes / want) otherwise, and frames 0, T, 2T, ... are costed.  A candidate's
+ * row is compact: the blocks of its selected frames in order, R per full frame, and what it has of a selected short last
+ * frame.  Every row has the stride redux_block_count(in_len, block_size); entries past a row's own count are not written.
+ *
+ * redux_record_cost_frame_step       T for this candidate.  Host only, no GPU.  0 for a block_size outside 1 .. 2^30, a
+ *                                    record size redux_record_check refuses, or a T above 2^32 - 1.
+ * redux_record_cost_block_count      the blocks of the candidate's row.  Host only, no GPU.  0 for the same arguments.
+ * redux_record_cost_dev              d_bits is f64[ncand][redux_block_count(in_len, block_size)] on the device.  records,
+ *                                    deltas: ncand values each on the HOST, consumed before the call returns (they travel
+ *                                    in the kernels' arguments); repeated candidates are legal, rows are independent, any
+ *                                    order of the list is right.  Full frames go to k_record_cost when block_size and d_in
+ *                                    are multiples of 16, everything else (the short last frame included) to
+ *                                    k_record_cost_bytes, which is right for any alignment and block size but slow.
+ *                                    INVALID_INPUT, with nothing written, for a block_size outside 1 .. 2^30, ncand == 0
+ *                                    or above REDUX_RECORD_COST_MAX, a null list or d_bits, or a pair redux_record_check
+ *                                    refuses; UNSUPPORTED as redux_block_cost_dev.  Stream-ordered, no workspace, no host
+ *                                    synchronisation.
+ * redux_record_cost_kernel_name      the kernels such a call with sample_blocks 0 runs on a 16-byte aligned d_in:
+ *                                    "k_record_cost", "k_record_cost_bytes", or both joined by " + " when full frames are
+ *                                    followed by a short one.  "" for a block_size or record size out of range.
+ * redux_record_cost_kernel_name_at   the same for this d_in, which contributes its alignment only. */
+#define REDUX_RECORD_COST_MAX 256   /* candidates of one call */
+uint32_t    redux_record_cost_frame_step(uint64_t in_len, uint32_t block_size, uint32_t record_size, uint32_t sample_blocks);
+uint64_t    redux_record_cost_block_count(uint64_t in_len, uint32_t block_size, uint32_t record_size, uint32_t sample_blocks);
+int         redux_record_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size,
+                                  const uint32_t *records /* host, ncand */, const uint8_t *deltas /* host, ncand */,
+                                  uint32_t ncand, uint32_t sample_blocks, void *d_bits /* f64[ncand][block_count] */,
+                                  void *stream);
+const char *redux_record_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t record_size);
+const char *redux_record_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t record_size);
+
 /* ---- mixed layouts --------------------------------------------------------------------------------------
  * One layout per UNIT of the input instead of one per input, for files that hold several element types (bf16 weights next to
  * fp32 state, int64 indices and text): the eight layouts of "layout estimates" above, chosen for every unit on its own.

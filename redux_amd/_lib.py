@@ -155,6 +155,12 @@ SIGNATURES = {
     "redux_lag_order_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _V, _V, _U32, _U32, _V, _V]),
     "redux_lag_order_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
     "redux_lag_order_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
+    # record estimates: the cost behind the record layout for (record size, delta) candidates
+    "redux_record_cost_frame_step": (_U32, [_U64, _U32, _U32, _U32]),
+    "redux_record_cost_block_count": (_U64, [_U64, _U32, _U32, _U32]),
+    "redux_record_cost_dev": (C.c_int, [_PP, _V, _U64, _U32, _V, _V, _U32, _U32, _V, _V]),
+    "redux_record_cost_kernel_name": (C.c_char_p, [_U64, _U32, _U32]),
+    "redux_record_cost_kernel_name_at": (C.c_char_p, [_V, _U64, _U32, _U32]),
     # mixed layouts: a layout per unit of 8 blocks
     "redux_mixed_unit_count": (_U64, [_U64, _U32]),
     "redux_mixed_choose_dev": (C.c_int, [_V, _U64, _U32, _V, _V, _V]),

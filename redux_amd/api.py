@@ -2602,6 +2602,208 @@ def choose_lag_order(data, element_size, block_size, lag=None, params=(8, 30, 32
     return best_lag_order(est), est
 
 
+# ---- record estimates (include/redux_hip.h, "record estimates") ------------------------------------
+RECORD_COST_MAX = 256      # REDUX_RECORD_COST_MAX: the candidates of one call
+RECORD_SAMPLE_BLOCKS = 64  # choose_record's first stage costs about this many blocks of every candidate
+RECORD_FINALISTS = 4       # and its second stage the candidates with the smallest sampled rates, this many
+
+
+def record_candidates():
+    """all 510 candidates (R, filter): R in 2 .. RECORD_MAX, filter None then "delta" """
+    return [(R, f) for R in range(2, RECORD_MAX + 1) for f in (None, "delta")]
+
+
+def _record_candidate_list(candidates, cap=RECORD_COST_MAX):
+    """1 to cap (R, filter) pairs, R an int in 2 .. RECORD_MAX, filter None or "delta" (False / True and 0 / 1 are taken for
+    them), repeats allowed -> list of (int, None or "delta")"""
+    try:
+        cands = [tuple(c) for c in candidates]
+    except TypeError:
+        raise InvalidInput()
+    if not 1 <= len(cands) <= cap:
+        raise InvalidInput()
+    out = []
+    for c in cands:
+        if len(c) != 2 or isinstance(c[0], bool) or not isinstance(c[0], (int, np.integer)) or not 2 <= c[0] <= RECORD_MAX:
+            raise InvalidInput()
+        f = c[1]
+        if f is None or (isinstance(f, (bool, int, np.integer)) and int(f) == 0):
+            f = None
+        elif (isinstance(f, str) and f == "delta") or (isinstance(f, (bool, int, np.integer)) and int(f) == 1):
+            f = "delta"
+        else:
+            raise InvalidInput()
+        out.append((int(c[0]), f))
+    return out
+
+
+def _record_cost_args(block_size, sample_blocks):
+    """the argument checks of the record estimates, on the arguments alone -> (B, Q)"""
+    if isinstance(block_size, bool) or not isinstance(block_size, (int, np.integer)) or not 0 < block_size <= 1 << 30 \
+            or isinstance(sample_blocks, bool) or not isinstance(sample_blocks, (int, np.integer)) or not 0 <= sample_blocks < 1 << 32:
+        raise InvalidInput()
+    return int(block_size), int(sample_blocks)
+
+
+def record_cost_sample(nbytes, block_size, record_size, sample_blocks=0):
+    """The frame sampling of the record estimates (include/redux_hip.h, "record estimates"), in Python and on the arguments
+    alone -> (T, blocks of the row, input bytes costed): frames 0, T, 2T, ... of record_size * block_size bytes."""
+    frame = record_size * block_size
+    nframes = max(1, -(-nbytes // frame))
+    T = 1
+    if sample_blocks:
+        want = -(-sample_blocks // record_size)
+        if nframes > want:
+            T = -(-nframes // want)
+    nsel = (nframes - 1) // T + 1
+    last = (nsel - 1) * T  # the last selected frame
+    nblocks = max(1, -(-nbytes // block_size))
+    row = (nsel - 1) * record_size + min(record_size, nblocks - last * record_size)
+    return T, row, (nsel - 1) * frame + min(frame, nbytes - last * frame)
+
+
+def _device_record_cost(torch, L, cp, d, B, cands, Q, fill=None):
+    """-> (float64 device tensor [len(cands), redux_block_count], the rows' own block counts); both lists are consumed by
+    the call.  fill: what the entries past a row's count hold (None: nothing is written there)"""
+    n = d.numel()
+    shape = (len(cands), L.redux_block_count(n, B))
+    d_bits = torch.empty(shape, dtype=torch.float64, device=d.device) if fill is None \
+        else torch.full(shape, fill, dtype=torch.float64, device=d.device)
+    h_records = np.asarray([R for R, _ in cands], dtype=np.uint32)
+    h_deltas = np.asarray([f is not None for _, f in cands], dtype=np.uint8)
+    _raise(L.redux_record_cost_dev(C.byref(cp), C.c_void_p(d.data_ptr()) if n else None, n, B, h_records.ctypes.data,
+                                   h_deltas.ctypes.data, len(cands), Q, C.c_void_p(d_bits.data_ptr()), _stream_ptr(torch)))
+    return d_bits, [int(L.redux_record_cost_block_count(n, B, R, Q)) for R, _ in cands]
+
+
+def record_cost(data, candidates, block_size=65536, params=(8, 30, 32), sample_blocks=0):
+    """The adaptive model's ideal code length in bits, EOF included, of every block of `data` behind the record layout
+    (record_size=R, filter=) for each (R, filter) of `candidates` (1 to RECORD_COST_MAX pairs, R in 2 .. RECORD_MAX, filter
+    None or "delta", repeats allowed), counted from the bytes as they are, with no transformed copy (redux_record_cost_dev:
+    k_record_cost on torch's current stream, one read-back) -> np.float64[len(candidates), block_count]: row c is
+    block_cost(record_planes(data, R, block_size, delta)).  sample_blocks Q > 0 costs about Q blocks of every candidate --
+    every T-th frame of R * block_size bytes, T the candidate's own (record_cost_sample) -- and returns a list of rows, each
+    the blocks of its candidate's selected frames in order.  A uint8 device tensor is read where it lies; host data is
+    uploaded once."""
+    B, Q = _record_cost_args(block_size, sample_blocks)  # (before the library is touched)
+    cands = _record_candidate_list(candidates)
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        bits, counts = _device_record_cost(torch, _lib.lib(), P._c(), d, B, cands, Q)
+        bits = bits.cpu().numpy()
+    return bits if Q == 0 else [bits[c, :n].copy() for c, n in enumerate(counts)]
+
+
+def _record_estimates(torch, L, cp, d, B, cands, Q):
+    out = {}
+    for at in range(0, len(cands), RECORD_COST_MAX):
+        part = cands[at:at + RECORD_COST_MAX]
+        bits, counts = _device_record_cost(torch, L, cp, d, B, part, Q, fill=0.0)
+        sums = bits.sum(dim=1).cpu().numpy()
+        for j, c in enumerate(part):
+            out.setdefault(c, int(np.ceil(float(sums[j]) / 8 + TERMINATION_BYTES * counts[j])))
+    return out
+
+
+def estimate_records(data, block_size, candidates=None, params=(8, 30, 32), sample_blocks=0):
+    """-> {(R, filter): estimated payload bytes}: what the streams of compress_blocks(..., record_size=R, filter=) would add
+    up to for each pair of `candidates` (up to 510; None: all 510 of record_candidates(); in calls of at most RECORD_COST_MAX), without
+    transforming or coding anything: record_cost, then ceil(sum bits / 8 + TERMINATION_BYTES * blocks) as estimate_payload,
+    over the blocks of the selected frames (sample_blocks 0: all of them; a repeated candidate keeps its first row)."""
+    B, Q = _record_cost_args(block_size, sample_blocks)  # (before the library is touched)
+    cands = record_candidates() if candidates is None else _record_candidate_list(candidates, 2 * (RECORD_MAX - 1))
+    P = _params_of(params)
+    torch = _torch()
+    d = _device_u8(torch, data)
+    with torch.cuda.device(d.device):
+        return _record_estimates(torch, _lib.lib(), P._c(), d, B, cands, Q)
+
+
+def _record_rank(c):
+    """ties among candidates: the smaller R, then no filter"""
+    return (c[0], c[1] is not None)
+
+
+def record_finalists(estimates, costed=None):
+    """the candidates of choose_record's second stage: the RECORD_FINALISTS smallest of `estimates` {(R, filter): bytes}, by
+    bytes per costed input byte where costed {(R, filter): bytes of the input} is given (candidates sample different
+    amounts); ties go to the smaller R, then to no filter"""
+    def rate(c):
+        return estimates[c] / max(1, costed[c]) if costed is not None else estimates[c]
+    return sorted((c for c in estimates if c is not None), key=lambda c: (rate(c), _record_rank(c)))[:RECORD_FINALISTS]
+
+
+def best_record(estimates):
+    """The key of {(R, filter) or None: bytes} with the smallest estimate.  None, the plain bytes, wins every tie; among
+    candidates ties go to the smaller R, then to no filter."""
+    return min(estimates, key=lambda c: (estimates[c], (0, 0, False) if c is None else (1,) + _record_rank(c)))
+
+
+RECORD_NOISE_SIGMAS = 6.4  # choose_record: a layout must beat the plain bytes by this many standard deviations of the noise
+
+
+def record_noise_bytes(bits, nfull=None):
+    """The standard deviation, in bytes, that an estimate over these blocks shows on data WITHOUT record structure, from the
+    plain bytes' own block costs `bits` (block_cost's).  On such data the blocks are draws of one source, the sample
+    deviation s of their costs is the noise of one block, a sum of n independent blocks has s * sqrt(n), and a candidate of
+    the record layout is the same bytes dealt into other blocks: another such sum.  Data that drifts from block to block
+    makes it larger, which errs towards the plain bytes.  nfull: the leading blocks of full size (None: all); a short last
+    block costs less for being short, which is no noise, so s is taken over the full ones.  0 for fewer than two of them."""
+    bits = np.asarray(bits, dtype=np.float64).reshape(-1)
+    full = bits if nfull is None else bits[:nfull]
+    if len(full) < 2:
+        return 0.0
+    return float(np.std(full, ddof=1)) * float(np.sqrt(len(bits))) / 8
+
+
+def choose_record(data, block_size, params=(8, 30, 32), estimate=None):
+    """-> ((R, filter) or None, {key: estimated payload bytes}): the record size and the filter of the record layout with
+    the smallest estimate, or None where the plain bytes are estimated no larger, counted on the GPU and never guessed.
+    Stage 1: all 510 candidates on about RECORD_SAMPLE_BLOCKS (64) blocks each, ranked by sampled bytes per costed input
+    byte.  Stage 2: one exact pass over the RECORD_FINALISTS (4) best, and block_cost of the plain bytes under the key None,
+    which wins ties: the choice is never estimated above the plain container.  Where stage 1 was exact for every candidate
+    (an input of few frames), its figures stand and only the plain cost is added.  The dict holds the exact estimates.
+    The smallest of 510 estimates lies below the plain one on any data, by noise: on iid bytes every candidate is the same
+    bytes in other blocks, the smallest of 510 such draws lies about 3.1 standard deviations below their mean with a spread
+    of 0.4, and the plain estimate is one more draw, so a gain of 3.1 +- 1.1 deviations says nothing.  A candidate is chosen
+    only where it beats the plain bytes by more than RECORD_NOISE_SIGMAS (6.4 = 3.1 + 3 * 1.1) times record_noise_bytes of
+    the plain bytes' block costs; else None.
+    estimate: the rule alone, for a caller with costs of its own: a function (candidates, sample_blocks) -> {key: bytes} in
+    place of the device, where candidates is a list of (R, filter), or None for the plain bytes: {None: bytes}, and under
+    the key "noise" the deviation in bytes (record_noise_bytes), without which it is 0 and only ties go to None."""
+    B, _ = _record_cost_args(block_size, 0)  # (before the library is touched)
+    if estimate is None:
+        P = _params_of(params)
+        torch = _torch()
+        d = _device_u8(torch, data)
+        L, cp = _lib.lib(), P._c()
+        nbytes = d.numel()
+
+        def estimate(cands, Q):
+            with torch.cuda.device(d.device):
+                if cands is None:
+                    bits = _device_block_cost(torch, L, cp, d, B).cpu().numpy()
+                    return {None: int(np.ceil(float(bits.sum()) / 8 + TERMINATION_BYTES * len(bits))), "noise": record_noise_bytes(bits, nbytes // B)}
+                return _record_estimates(torch, L, cp, d, B, cands, Q)
+    else:
+        nbytes = len(data)
+    cands = record_candidates()
+    est = estimate(cands, RECORD_SAMPLE_BLOCKS)
+    samples = {c: record_cost_sample(nbytes, B, c[0], RECORD_SAMPLE_BLOCKS) for c in cands}
+    if any(samples[c][0] > 1 for c in cands):
+        est = estimate(record_finalists(est, {c: samples[c][2] for c in cands}), 0)
+    est = dict(est)
+    plain = dict(estimate(None, 0))
+    noise = plain.pop("noise", 0.0)
+    est.update(plain)
+    best = best_record(est)
+    if best is not None and est[None] - est[best] <= RECORD_NOISE_SIGMAS * noise:
+        best = None  # (a gain that the smallest of 510 draws of noise explains)
+    return best, est
+
+
 # ---- synthetic workloads (BASELINE.json configs 2 and 5) ------------------------------------
 def gen_iid(nbytes, seed=0x5EED0001, first_byte=0, device="cuda:0", out=None):
     torch = _torch()

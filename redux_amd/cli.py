@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--order-auto] [--record-size R] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--order-auto] [--record-size R|auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -124,11 +124,19 @@ The usage errors are those of `--layout auto`.
 for fixed-width structs: a packed C struct dump, a numpy structured array, a row-major table.  Every block then holds one byte
 column of block-size records of R bytes, and `--filter delta` with it is the byte delta against the record before, not the
 integer delta filter.  On generated tables of 23- and 20-byte structs, layout and delta together come out at
-about 0.74 to 0.75 of the best of plain, planes and `--filter lag`; nothing chooses R or the filter for you.  The output is
+about 0.74 to 0.75 of the best of plain, planes and `--filter lag`.  The output is
 container version 15, which records both: -d and -d `--range` read it with no flag.  `--record-size` with -d, with
 `--block-size 0`, an `--element-size` other than 1, `--stored`, a `--model` other than adaptive, `--filter zigzag` or `lag`,
-`--lag`, `--order`, `--order-auto`, `--base`, `--skip-constant` or `--layout`, and an R that is not a decimal from 2 to 256, is
-a usage error.
+`--lag`, `--order`, `--order-auto`, `--base`, `--skip-constant` or `--layout`, and an R that is neither a decimal from 2 to 256 nor
+`auto`, is a usage error.
+`--record-size auto` (with -c and a block size; `--checksum` is allowed) counts R and the filter for a struct dump of unknown
+width (redux_amd/api.py: choose_record): all 510 candidates, R from 2 to 256 with and without the byte delta, are
+costed on the GPU from the bytes as they are -- about 64 blocks of each first, then every frame for the four best and for the
+plain bytes -- and the smallest estimate codes the data, unless its gain over the plain bytes is one that the smallest of 510
+draws of noise explains.  The output is that choice's ordinary container, version 15, or the
+plain version 1 container where the layout is estimated to cost bytes: nothing new for -d.  On the generated tables above it
+finds 23 and 20 with the delta; no recorded table was measured.  `--record-size auto` with `--filter`, and with everything
+`--record-size R` is a usage error with, is a usage error.
 `--range START:LENGTH` (with -d; both decimal, START + LENGTH at most the length of the data) writes only the bytes
 [START, START + LENGTH) of the original data, and decodes only the blocks that hold them (redux_amd/container.py: Reader;
 DESIGN.md 6o): one tensor out of a checkpoint.  With `-i FILE` the file is not read as a whole: the header and the tables are,
@@ -143,7 +151,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--order-auto] [--record-size <2..256>] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--order-auto] [--record-size <2..256>|auto] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -198,9 +206,12 @@ def parse(argv):
                     return None
                 opts["order"] = int(val)
             elif arg == "--record-size":
-                if not (val.isascii() and val.isdigit()) or not 2 <= int(val) <= 256:
+                if val == "auto":
+                    opts["record_size"] = val
+                elif not (val.isascii() and val.isdigit()) or not 2 <= int(val) <= 256:
                     return None
-                opts["record_size"] = int(val)
+                else:
+                    opts["record_size"] = int(val)
             elif arg == "--base":
                 opts["base"] = val
             elif arg == "--base-op":
@@ -274,6 +285,8 @@ def parse(argv):
                                   or opts.get("filter", "delta") != "delta" or "order" in opts or "base" in opts
                                   or opts.get("skip_constant") or "layout" in opts):
         return None  # the record layout is recorded in the container; it stands in place of an element size, and its one filter is the byte delta
+    if opts.get("record_size") == "auto" and "filter" in opts:
+        return None  # the filter is counted with the record size, not given
     if "range" in opts and opts["compress"] is not False:
         return None  # a range is read, not written
     return None if opts["compress"] is None else opts

@@ -771,6 +771,18 @@ def estimate_lag_order_bytes(data, element_size, block_size=65536, candidates=((
     return {c: payload[c] + over for c in payload}
 
 
+def estimate_record_bytes(data, block_size=65536, candidates=None, params=(8, 30, 32), checksum=False, sample_blocks=0):
+    """-> {(R, filter): estimated container bytes} for the adaptive model behind the record layout for each pair of
+    `candidates` (None: all 510): api.estimate_records' estimate of the payloads (counted from the bytes as they are on the
+    GPU; nothing is transformed or coded) plus overhead_bytes(..., record_size=R), which is exact: version 15 records the layout in
+    the header's reserved word, so it is the plain container's overhead and the figures compare directly with
+    estimate_bytes(...)["adaptive"].  sample_blocks above 0 estimates the selected frames' payload only, under the whole
+    container's overhead."""
+    payload = api.estimate_records(data, block_size, candidates, params, sample_blocks)
+    nb = max(1, -(-len(data) // block_size))
+    return {c: payload[c] + overhead_bytes("adaptive", nb, checksum=checksum, filter=c[1], record_size=c[0]) for c in payload}
+
+
 def choose_layout(estimates):
     """The (element_size, filter) with the smallest estimate; ties go to the earlier of LAYOUT_ORDER."""
     return min(estimates, key=lambda k: (estimates[k], LAYOUT_ORDER.index(k)))
@@ -831,12 +843,28 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     "sub", unrelated ones "xor", and a caller cannot know in advance.
     record_size R, 2 .. 256 (element_size 1, model "adaptive", filter None or "delta", and none of stored, segment_blocks,
     base, skip_constant, layout, lag and order): the record layout for fixed-width structs, every block one byte column of
-    block_size records of R bytes; filter "delta" is then the byte delta against the record before.  Version 15, kind 1."""
+    block_size records of R bytes; filter "delta" is then the byte delta against the record before.  Version 15, kind 1.
+    record_size "auto" (the exclusions of a record size, and no filter; here only, not in the block calls or the device
+    coders): the record size and the filter with the smallest estimate code the data (api.choose_record: all 510 candidates
+    counted on the GPU from the bytes as they are, on a sample first, then exactly for the finalists and for the plain bytes,
+which also keep every gain that noise among 510 candidates explains),
+    and the container is that choice's ordinary one, version 15 -- or version 1 where the plain bytes are estimated no
+    larger: nothing new to decode."""
+    auto_record = isinstance(record_size, str) and record_size == "auto"  # (the choice is made below, once nothing refuses the call)
+    if auto_record:
+        if filter is not None:
+            raise api.InvalidInput()
+        record_size = 2  # (until then it is refused where a record size is)
     if record_size is not None:
         if layout is not None or model != "adaptive" or stored or segment_blocks is not None or skip_constant or base_op != "xor" \
                 or not 0 < block_size <= MAX_BLOCK_SIZE:
             raise api.InvalidInput()
         api._resolve_front(None, element_size, filter, base, lag=lag, order=order, record_size=record_size)
+        if auto_record:
+            choice = api.choose_record(data, block_size, params)[0]
+            if choice is None:  # the layout is estimated to cost bytes: the plain container
+                return compress_bytes(data, block_size, params, checksum=checksum)
+            record_size, filter = choice
         crc = np.zeros(max(1, -(-len(data) // block_size)), dtype=np.uint32) if checksum else None
         out, offs, _ = api.compress_blocks(data, block_size, params, block_crc=crc, filter=filter, record_size=record_size)
         return pack(out, offs, params, block_size, len(data), block_crc=crc, filter=filter, record_size=record_size)

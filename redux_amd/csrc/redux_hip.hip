@@ -29,6 +29,7 @@
 //   redux_layout_cost.hpp  k_layout_cost: the adaptive cost of every block of the eight layouts, from the untransformed bytes
 //   redux_lag_cost.hpp  k_lag_cost: the adaptive cost of every block behind the lagged delta filter, for a list of lags;
 //                      k_lag_order_cost: the same behind its higher orders, for (lag, order) candidates, from the same bodies
+//   redux_record_cost.hpp  k_record_cost: the adaptive cost of every block behind the record layout, for (record size, delta) candidates
 //   redux_mixed.hpp    k_mixed_choose / k_mixed_planes: a layout per unit of 8 blocks, chosen from those costs on the device
 //   redux_range.hpp    k_segment_copy: range reads, the plan of the covered granules and the segmented byte copy
 // This file holds the general-parameter kernels' launch shims, the workspace geometry and the
@@ -66,6 +67,7 @@
 #include "redux_layout_cost.hpp"
 #include "redux_lag_cost.hpp"
 #include "redux_lag_order_cost_list.hpp"
+#include "redux_record_cost.hpp"
 #include "redux_mixed.hpp"
 #include "redux_range.hpp"
 
@@ -1079,6 +1081,44 @@ static int launch_lag_cost(void (*fast)(LagCostArgs), void (*bytes)(LagCostArgs)
     if (nrest) { // a selected short last frame, or everything the fast kernel cannot take
         const uint64_t work = nrest * a.ncand, cap = (uint64_t)kHistWgsPerCu * cu_count();
         bytes<<<(uint32_t)(work < cap ? work : cap), 64, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    return REDUX_OK;
+}
+
+// ---- record estimates (redux_record_cost.hpp) --------------------------------------------------------------------------
+// a.records, a.deltas and a.ncand are filled by the caller.  k_record_cost takes the selected full frames of every candidate,
+// k_record_cost_bytes the rest of every row; each gets the running count of its own jobs.
+static int launch_record_cost(RecordCostArgs &a, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t sample_blocks,
+                              double *bits, hipStream_t s)
+{
+    a.in            = (const uint8_t *)d_in;
+    a.in_len        = in_len;
+    a.stride        = redux_block_count(in_len, block_size);
+    a.bits          = bits;
+    a.block_size    = block_size;
+    a.sample_blocks = sample_blocks;
+    a.fast          = block_size % 16 == 0 && ((uintptr_t)d_in & 15) == 0;
+    for (int pass = 0; pass < 2; pass++) { // 0: the fast kernel, 1: the byte kernel
+        uint64_t jobs = 0;
+        for (uint32_t c = 0; c <= REDUX_RECORD_COST_MAX; c++) {
+            a.jobs[c] = jobs;
+            if (c >= a.ncand)
+                continue;
+            const uint32_t         R  = a.records[c];
+            const RecordCostSample sm = record_cost_sample(in_len, block_size, R, sample_blocks);
+            const uint64_t         nf = record_cost_fast_frames(in_len, block_size, R, a.fast, sm);
+            jobs += pass ? sm.row_blocks - nf * R : nf * (R > kRecordCostPC ? (R + kRecordCostPC - 1) / kRecordCostPC : 1);
+        }
+        if (!jobs)
+            continue;
+        if (pass == 0) {
+            const uint64_t cap = (uint64_t)kRecordCostWgsPerCu * cu_count();
+            k_record_cost<<<(uint32_t)(jobs < cap ? jobs : cap), 256, 0, s>>>(a);
+        } else {
+            const uint64_t cap = (uint64_t)kHistWgsPerCu * cu_count();
+            k_record_cost_bytes<<<(uint32_t)(jobs < cap ? jobs : cap), 64, 0, s>>>(a);
+        }
         HIP_TRY(hipGetLastError());
     }
     return REDUX_OK;
@@ -4833,6 +4873,50 @@ const char *redux_lag_order_cost_kernel_name_at(const void *d_in, uint64_t in_le
 const char *redux_lag_order_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t element_size)
 {
     return redux_lag_order_cost_kernel_name_at(nullptr, in_len, block_size, element_size);
+}
+
+uint32_t redux_record_cost_frame_step(uint64_t in_len, uint32_t block_size, uint32_t record_size, uint32_t sample_blocks)
+{
+    if (block_size == 0 || block_size > (1u << 30) || redux_record_check(record_size, 0) != REDUX_OK)
+        return 0;
+    const uint64_t step = record_cost_sample(in_len, block_size, record_size, sample_blocks).step;
+    return step > 0xFFFFFFFFull ? 0 : (uint32_t)step;
+}
+
+uint64_t redux_record_cost_block_count(uint64_t in_len, uint32_t block_size, uint32_t record_size, uint32_t sample_blocks)
+{
+    if (block_size == 0 || block_size > (1u << 30) || redux_record_check(record_size, 0) != REDUX_OK)
+        return 0;
+    return record_cost_sample(in_len, block_size, record_size, sample_blocks).row_blocks;
+}
+
+int redux_record_cost_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, const uint32_t *records,
+                          const uint8_t *deltas, uint32_t ncand, uint32_t sample_blocks, void *d_bits, void *stream)
+{
+    if (!p || block_size == 0 || block_size > (1u << 30) || !d_bits || (in_len && !d_in))
+        return REDUX_INVALID_INPUT;
+    RecordCostArgs a; // (the lists travel in the kernels' arguments: consumed before the call returns)
+    if (!record_cost_list(records, deltas, ncand, REDUX_RECORD_COST_MAX, a.records, a.deltas, redux_record_check))
+        return REDUX_INVALID_INPUT;
+    a.ncand = ncand;
+    const int st = adaptive_cost_check(p, block_size);
+    if (st != REDUX_OK)
+        return st;
+    return launch_record_cost(a, d_in, in_len, block_size, sample_blocks, (double *)d_bits, (hipStream_t)stream);
+}
+
+const char *redux_record_cost_kernel_name_at(const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t record_size)
+{
+    static const char *const names[3] = {"k_record_cost", "k_record_cost + k_record_cost_bytes", "k_record_cost_bytes"};
+    if (block_size == 0 || block_size > (1u << 30) || redux_record_check(record_size, 0) != REDUX_OK)
+        return "";
+    const uint64_t nfull = layout_cost_full_frames(d_in, in_len, block_size, record_size);
+    return names[nfull == 0 ? 2 : nfull * record_size < redux_block_count(in_len, block_size) ? 1 : 0];
+}
+
+const char *redux_record_cost_kernel_name(uint64_t in_len, uint32_t block_size, uint32_t record_size)
+{
+    return redux_record_cost_kernel_name_at(nullptr, in_len, block_size, record_size);
 }
 
 int redux_table_cost_dev(const void *d_counts, const void *d_cum, uint64_t n, void *d_bits, void *stream)

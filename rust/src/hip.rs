@@ -135,6 +135,18 @@ extern "C" {
     fn redux_lag_order_cost_kernel_name(in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
     #[allow(dead_code)]
     fn redux_lag_order_cost_kernel_name_at(d_in: *const c_void, in_len: u64, block_size: u32, element_size: u32) -> *const c_char;
+    // record estimates: the cost behind the record layout for a list of (record size, delta) candidates, with its sampling
+    #[allow(dead_code)]
+    fn redux_record_cost_frame_step(in_len: u64, block_size: u32, record_size: u32, sample_blocks: u32) -> u32;
+    #[allow(dead_code)]
+    fn redux_record_cost_block_count(in_len: u64, block_size: u32, record_size: u32, sample_blocks: u32) -> u64;
+    #[allow(dead_code)]
+    fn redux_record_cost_dev(p: *const ReduxParams, d_in: *const c_void, in_len: u64, block_size: u32, records: *const u32,
+                             deltas: *const u8, ncand: u32, sample_blocks: u32, d_bits: *mut c_void, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn redux_record_cost_kernel_name(in_len: u64, block_size: u32, record_size: u32) -> *const c_char;
+    #[allow(dead_code)]
+    fn redux_record_cost_kernel_name_at(d_in: *const c_void, in_len: u64, block_size: u32, record_size: u32) -> *const c_char;
     fn redux_static_table_check(p: *const ReduxParams, cum: *const u32) -> c_int;
     fn redux_static_encode_bound(p: *const ReduxParams, in_len: u64, block_size: u32) -> u64;
     fn redux_static_table_from_counts(p: *const ReduxParams, counts: *const u64, total: u32, cum: *mut u32) -> c_int;
