@@ -722,6 +722,63 @@ int redux_decode_blocks_base_sub(const redux_params *p, const uint8_t *in, const
                                  uint64_t base_len, uint64_t out_len, uint32_t block_size, uint32_t element_size, uint8_t *out,
                                  uint32_t *out_sizes, int32_t *block_status, uint32_t *block_crc);
 
+/* ---- snapshot-stride filter for time series of fields ---------------------------------------------
+ * One buffer of T snapshots of the same S elements -- a trajectory [frame, atom, xyz], a field [time, lat, lon], a stack of
+ * sensor frames, a tensor logged every step -- predicts an element best by the same element one snapshot back: a distance of
+ * thousands to millions of elements, out of REDUX_LAG_MAX's reach, and within the base filter's only by cutting the buffer
+ * into T files.  These calls are the folded difference of the base filter with the second operand taken from the input
+ * itself, S elements back.  Strictly opt-in: on unrelated snapshots it costs bytes, and no call chooses it.
+ *   - E = element_size (1, 2, 4 or 8), B = block_size, S >= 1 the stride in elements (a u64), x = the input of len bytes,
+ *     n = len / E whole little-endian elements counted from byte 0 of the WHOLE buffer, not per frame.
+ *   - z[i] = x[i] for i < S; for S <= i < n: d = x[i] - x[i - S] mod 2^(8E), z[i] = (d << 1) ^ (0 - (d >> (8E - 1))), the fold
+ *     of the zigzag filter.  The len - n*E trailing bytes are unchanged.  The byte-plane layout of E (frames of E*B bytes; none
+ *     for E = 1) is applied to z.  S >= n is legal and is the layout alone.
+ *   - The inverse undoes the layout; then, for i from S upward, x[i] = ((z[i] >> 1) ^ (0 - (z[i] & 1))) + x[i - S].
+ *   - stream_stride_E_S(x)[b] == redux_encode_blocks(planes_E(stride_E_S(x)))[b].
+ * This is the first filter whose predecessor lies outside the frame: the inverse of a block needs the blocks before it in its
+ * columns.  So there are no range reads behind it, and the host-pointer pair does not run on the chunk pipeline: it stages
+ * the WHOLE buffer on the first device of the host context (the current device, or the first of redux_host_set_devices) and
+ * runs the _dev call there.  Its output therefore depends on neither the chunk size nor the devices, and block_crc is over the
+ * ORIGINAL bytes; redux_host_chunk_plan does not describe it.
+ *
+ * Every call is the shape of its lag namesake with `stride`, a u64, where the lag is, except:
+ *   - the inverse's second stage cuts time into segments where S is small (no launch holds a serial chain proportional to
+ *     len) and keeps the segments' sums in a workspace: redux_stride_planes_dev takes (d_workspace, workspace_bytes) in front
+ *     of the stream, at least redux_stride_workspace_bytes(len, element_size, stride) bytes for inverse != 0 (0: none needed;
+ *     forward takes none, and null is fine then), REDUX_OUTPUT_TOO_SMALL with nothing written otherwise;
+ *   - redux_decode_stride_workspace_bytes takes the stride too, for the same reason.
+ * Bad arguments -- an element size outside {1, 2, 4, 8}, stride 0, overlapping d_src / d_dst -- are REDUX_INVALID_INPUT with
+ * nothing written.  redux_decode_stride_dev writes no byte outside d_out[0 .. out_len), for damaged streams too; a block that
+ * is not OK says so in its status, and the bytes at and after it in its columns are unspecified.  redux_stride_planes_dev
+ * reads no byte before d_src.  redux_stride_kernel_name names what a transform call runs for these arguments and pointers
+ * (their alignment counts; null: aligned), joined by " + ": "k_stride_planes", "k_stride_planes_bytes" forward; the layout's
+ * inverse ("k_planes", "k_planes_bytes", "copy" for E = 1) and then "k_stride_sum", with "k_stride_totals" and
+ * "k_stride_scan" in front of it where time is cut into segments, each with "_bytes" where a column is one element, and
+ * "k_stride_sum_tail"; "" for arguments the call refuses and for len 0. */
+int      redux_stride_check(uint32_t element_size, uint64_t stride);
+uint64_t redux_stride_workspace_bytes(uint64_t len, uint32_t element_size, uint64_t stride);
+int      redux_stride_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size,
+                                 uint64_t stride, int inverse, void *d_workspace, uint64_t workspace_bytes, void *stream);
+uint64_t redux_encode_stride_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size);
+uint64_t redux_decode_stride_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                                             uint64_t stride);
+int redux_encode_stride_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            uint64_t stride, void *d_out, uint64_t out_cap, void *d_out_offsets /* u64[nblocks+1] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] or NULL */, void *d_workspace,
+                            uint64_t workspace_bytes, void *stream);
+int redux_decode_stride_dev(const redux_params *p, const void *d_in, const void *d_in_offsets /* u64[nblocks+1] */, uint64_t out_len,
+                            uint32_t block_size, uint32_t element_size, uint64_t stride, void *d_out, void *d_out_sizes /* u32[nblocks] */,
+                            void *d_block_status /* i32[nblocks] */, void *d_summary /* i32[2] or NULL */, void *d_workspace,
+                            uint64_t workspace_bytes, void *stream);
+int redux_encode_blocks_stride(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size,
+                               uint32_t element_size, uint64_t stride, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets,
+                               int32_t *block_status, uint32_t *block_crc);
+int redux_decode_blocks_stride(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint64_t stride, uint8_t *out, uint32_t *out_sizes,
+                               int32_t *block_status, uint32_t *block_crc);
+const char *redux_stride_kernel_name(uint64_t len, uint32_t block_size, uint32_t element_size, uint64_t stride, int inverse,
+                                     const void *d_src, const void *d_dst);
+
 /* ---- stored blocks -----------------------------------------------------------------------------
  * A block whose stream does not shrink it can travel as its raw bytes instead (zstd raw blocks, deflate stored blocks).
  * Block b has L_b = min(B, len - b*B) bytes of coder input x' (the input for element_size 1, its byte-plane layout for

@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     lag_cost, estimate_lags, choose_lag,
     lag_order_cost, estimate_lag_orders, choose_lag_order,
     record_planes, record_kernel_name, record_plan, RECORD_MAX,
+    stride_planes, stride_kernel_name,
     record_cost, estimate_records, choose_record, RECORD_COST_MAX,
     range_plan, segment_copy, segment_tiles, SEGMENT_DTYPE,
 )

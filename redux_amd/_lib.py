@@ -253,6 +253,20 @@ SIGNATURES.update({
     "redux_record_kernel_name_at": (C.c_char_p, [_V, _V, _U64, _U32, _U32, C.c_int]),
     "redux_record_plan": (C.c_int, [_U64, _U32, _U32, C.c_int, C.c_int, _U32, C.POINTER(_U32)]),
 })
+# the snapshot-stride filter: the lag family with the stride, a u64, where the lag is; the transform takes a workspace in
+# front of its stream and the decode workspace size takes the stride
+SIGNATURES.update({
+    "redux_stride_check": (C.c_int, [_U32, _U64]),
+    "redux_stride_workspace_bytes": (_U64, [_U64, _U32, _U64]),
+    "redux_stride_planes_dev": (C.c_int, [_V, _V, _U64, _U32, _U32, _U64, C.c_int, _V, _U64, _V]),
+    "redux_encode_stride_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32]),
+    "redux_decode_stride_workspace_bytes": (_U64, [_PP, _U64, _U32, _U32, _U64]),
+    "redux_encode_stride_dev": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U64, _V, _U64, _V, _V, _V, _V, _U64, _V]),
+    "redux_decode_stride_dev": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U64, _V, _V, _V, _V, _V, _U64, _V]),
+    "redux_encode_blocks_stride": (C.c_int, [_PP, _V, _U64, _U32, _U32, _U64, _V, _U64, _V, _V, _V]),
+    "redux_decode_blocks_stride": (C.c_int, [_PP, _V, _V, _U64, _U32, _U32, _U64, _V, _V, _V, _V]),
+    "redux_stride_kernel_name": (C.c_char_p, [_U64, _U32, _U32, _U64, C.c_int, _V, _V]),
+})
 
 _LIB = None
 

@@ -513,7 +513,9 @@ def _check_element_size(element_size):
 # delta filter, which its entry points take behind the element size; None for every other front.  order: the order of
 # higher-order lagged differences, which their entry points take behind the lag; None for every other front.  record: the
 # (record size, delta flag) of the record layout, which its entry points take in place of the element size; None elsewhere.
-_Front = namedtuple("_Front", "infix takes_base needs_length lag order record", defaults=(None, None, None))
+# stride: the stride of the snapshot-stride filter, which its entry points take where the lag filter's take the lag (and its
+# decode workspace size and its transform take more: _ws_tail, stride_planes); None for every other front.
+_Front = namedtuple("_Front", "infix takes_base needs_length lag order record stride", defaults=(None, None, None, None))
 _PLANES = _Front("planes", False, False)                                 # no filter: the layout alone (none for element size 1)
 _FILTERS = {"delta": _Front("delta", False, True),                       # filter="delta": the delta filter for integer series
             "zigzag": _Front("zigzag", False, True),                     # filter="zigzag": the same with folded differences
@@ -523,6 +525,7 @@ LAG_MAX = 256  # REDUX_LAG_MAX
 LAG_ORDER_MAX = 3  # REDUX_LAG_ORDER_MAX
 _RECORD = _Front("record", False, True)                                  # record_size=R: the record layout; filter="delta": its byte delta
 RECORD_MAX = 256  # REDUX_RECORD_MAX
+_STRIDE = _Front("stride", False, True)                                  # filter="stride", stride=S: the same element one snapshot back
 _BASE_OPS = {"xor": _Front("base", True, True),                          # base=: the XOR against the base
              "sub": _Front("base_sub", True, True)}                      # base=, base_op="sub": the folded difference
 
@@ -533,7 +536,7 @@ _STATIC_MODELS = (StaticModel, PlaneStaticModel, SegmentStaticModel, ContextStat
 
 
 def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor", constant=None, stored=None, unit_layouts=None,
-                   device=False, record_size=None, lag=None, order=None):
+                   device=False, stride=None, record_size=None, lag=None, order=None):
     """The one place that says which of filter=, base=, base_op=, constant=, stored=, unit_layouts= and the model's kind go
     together; anything else is InvalidInput.  A check on the arguments alone: it touches neither the library nor torch,
     so it comes before any call into either.  -> _Resolved.
@@ -550,8 +553,18 @@ def _resolve_front(params, element_size=1, filter=None, base=None, base_op="xor"
     constant-block option and the mixed layouts look at the model's kind there.
     record_size: None, or the record layout (include/redux_hip.h, "record layout"): an int in 2 .. RECORD_MAX; adaptive
     model only, element size 1, filter None or "delta" (the byte delta against the record before), and none of lag=,
-    order=, base=, constant=, stored= or unit_layouts=; the _Front returned carries (record size, delta flag)."""
+    order=, base=, constant=, stored= or unit_layouts=; the _Front returned carries (record size, delta flag).
+    stride: with filter="stride" and only with it (include/redux_hip.h, "snapshot-stride filter"): an int of at least 1 (and
+    below 2^64); adaptive model only, any element size, and none of stored=, base=, constant=, unit_layouts=, record_size=,
+    lag= or order=; the _Front returned carries it."""
     static = isinstance(params, _STATIC_MODELS)
+    if stride is not None or (isinstance(filter, str) and filter == "stride"):
+        if stride is None or not (isinstance(filter, str) and filter == "stride") or isinstance(stride, bool) \
+                or not isinstance(stride, (int, np.integer)) or not 1 <= stride < 1 << 64 or static \
+                or any(x is not None for x in (stored, base, unit_layouts, record_size, lag, order)) \
+                or not (constant is None or constant is False):
+            raise InvalidInput()
+        return _Resolved(_STRIDE._replace(stride=int(stride)), False, False)
     if record_size is not None:
         if isinstance(record_size, bool) or not isinstance(record_size, (int, np.integer)) or not 2 <= record_size <= RECORD_MAX \
                 or static or not isinstance(element_size, (int, np.integer)) or isinstance(element_size, bool) or element_size != 1 \
@@ -598,6 +611,8 @@ def _no_front(filter=None, constant=None):
 def _lag_arg(front):
     """what a _Front's entry points take behind the element size: the lag of the lagged delta filter, the lag and the order
     of higher-order lagged differences, or nothing"""
+    if front.stride is not None:  # (the snapshot-stride filter's stride stands where the lag does)
+        return (front.stride,)
     return () if front.lag is None else (front.lag,) if front.order is None else (front.lag, front.order)
 
 
@@ -697,7 +712,7 @@ def _decompress_blocks_mixed(streams, offsets, block_size, params, check, length
 
 def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_crc=None, stored=None,
                     store_ratio=STORE_RATIO, filter=None, base=None, constant=None, unit_layouts=None, layouts=None,
-                    record_size=None, lag=None, order=None, base_op="xor"):
+                    stride=None, record_size=None, lag=None, order=None, base_op="xor"):
     """Per-block redux::compress on the GPU.  Returns (dense streams as uint8 array,
     offsets uint64[nblocks+1], status int32[nblocks]); raises on the first non-OK block.
     element_size 2, 4 or 8: the byte-plane layout of typed data is applied first (include/redux_hip.h, "byte-plane
@@ -745,9 +760,13 @@ def compress_blocks(data, block_size, params=(8, 30, 32), element_size=1, block_
     redux_encode_blocks_record): every block then holds one byte column of B records of R bytes.  filter="delta" with it is
     the byte delta against the record before (not the integer delta filter).  Adaptive model only, element_size 1, and with
     none of lag=, order=, base=, constant=, stored= or unit_layouts=; decompress_blocks(..., length, record_size=R, filter=)
-    undoes it."""
+    undoes it.
+    filter="stride", stride=S (1 or more): the snapshot-stride filter for one buffer of T snapshots of the same S elements
+    (include/redux_hip.h, "snapshot-stride filter": redux_encode_blocks_stride): every element is predicted by the one S
+    elements back, however far that is.  Adaptive model only, any element_size, and with none of the other options; the
+    whole input is staged on one device.  decompress_blocks(..., element_size, length, filter="stride", stride=S) undoes it."""
     front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                         order=order, record_size=record_size)
+                                         order=order, record_size=record_size, stride=stride)
     if mixed:
         return _compress_blocks_mixed(data, block_size, params, unit_layouts, layouts, block_crc)
     if layouts is not None:
@@ -826,7 +845,7 @@ def _offsets_in(offsets, nbytes):
 
 
 def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=True, element_size=1, length=None,
-                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, record_size=None, lag=None,
+                      block_crc=None, stored=None, filter=None, base=None, constant=None, unit_layouts=None, stride=None, record_size=None, lag=None,
                       order=None, base_op="xor"):
     """Per-block redux::decompress on the GPU.  Returns (out uint8[nblocks*block_size],
     sizes uint32[nblocks], status int32[nblocks]); block b occupies out[b*block_size:][:sizes[b]].
@@ -857,9 +876,12 @@ def decompress_blocks(streams, offsets, block_size, params=(8, 30, 32), check=Tr
     required, and out is the original bytes.  Adaptive model only, and with none of the options above but block_crc.
     base_op: "sub" for the streams of compress_blocks(..., base=, base_op="sub") (redux_decode_blocks_base_sub).
     record_size=R, with the filter= the streams were made with: the streams are compress_blocks(..., record_size=R)'s
-    (redux_decode_blocks_record); length is required, and out is the original bytes."""
+    (redux_decode_blocks_record); length is required, and out is the original bytes.
+    filter="stride", stride=S: the streams are compress_blocks(..., filter="stride", stride=S)'s
+    (redux_decode_blocks_stride); length is required.  A block that does not decode leaves the bytes at and after it in its
+    columns undefined, not only its frame's."""
     front, const, mixed = _resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                         order=order, record_size=record_size)
+                                         order=order, record_size=record_size, stride=stride)
     if mixed:
         return _decompress_blocks_mixed(streams, offsets, block_size, params, check, length, unit_layouts, block_crc)
     static, plane = isinstance(params, StaticModel), isinstance(params, PlaneStaticModel)
@@ -1302,14 +1324,15 @@ class DeviceEncoder(_DeviceCoder):
     base"); not together with constant=True.  filter="lag", lag=S: the lagged delta filter (include/redux_hip.h, "lagged delta
     filter"), where filter="zigzag" may stand; order=K (1 .. 3) with it: the difference applied K times (include/redux_hip.h,
     "higher-order lagged differences").  record_size=R: the record layout for fixed-width structs (include/redux_hip.h, "record
-    layout"), with filter=None or "delta", its byte delta; element size 1 and none of the other options."""
+    layout"), with filter=None or "delta", its byte delta; element size 1 and none of the other options.  filter="stride",
+    stride=S: the snapshot-stride filter (include/redux_hip.h, "snapshot-stride filter"), with none of the other options."""
 
     def __init__(self, params, block_size, max_in_len, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, layouts=None, record_size=None, lag=None, order=None, base_op="xor"):
+                 mixed=False, layouts=None, stride=None, record_size=None, lag=None, order=None, base_op="xor"):
         # (mixed: with the adaptive model and nothing else; `layouts`: what encode() chooses among, None = all eight)
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
                                                                unit_layouts=True if mixed else None, device=True, lag=lag,
-                                                               order=order, record_size=record_size)
+                                                               order=order, record_size=record_size, stride=stride)
         if self.mixed:
             self.mixed_mask = _layout_mask(layouts)
         elif layouts is not None:
@@ -1410,14 +1433,15 @@ class DeviceDecoder(_DeviceCoder):
     base_op="sub": the streams are DeviceEncoder(..., base=, base_op="sub")'s.  filter="lag", lag=S: the streams are
     DeviceEncoder(..., filter="lag", lag=S)'s; as filter="zigzag"; order=K: the encoder's order.  record_size=R (with the
     encoder's filter=): the streams are DeviceEncoder(..., record_size=R)'s; decode needs the length, and decode_ranges reads
-    whole frames of R blocks."""
+    whole frames of R blocks.  filter="stride", stride=S: the streams are DeviceEncoder(..., filter="stride", stride=S)'s;
+    decode needs the length, and decode_ranges raises Unsupported."""
 
     def __init__(self, params, block_size, max_blocks, device="cuda:0", element_size=1, filter=None, base=None, constant=False,
-                 mixed=False, record_size=None, lag=None, order=None, base_op="xor"):
+                 mixed=False, stride=None, record_size=None, lag=None, order=None, base_op="xor"):
         # (mixed: the streams are DeviceEncoder(..., mixed=True)'s: decode(..., length, unit_layouts=table))
         self.front, self.constant, self.mixed = _resolve_front(params, element_size, filter, base, base_op, constant,
                                                                unit_layouts=True if mixed else None, device=True, lag=lag,
-                                                               order=order, record_size=record_size)
+                                                               order=order, record_size=record_size, stride=stride)
         torch = _torch()
         self.base = _device_base(torch, base, device)
         P = _params_of(params)
@@ -1450,7 +1474,11 @@ class DeviceDecoder(_DeviceCoder):
         return self.out, self.sizes, self.status, self.summary
 
     def _layout_ws_bytes(self, nbytes):
-        """the workspace of the entry points that undo the layout, for an input of nbytes"""
+        """the workspace of the entry points that undo the layout, for an input of nbytes (the snapshot-stride filter's second
+        stage has a share of its own, which never falls as nbytes grows)"""
+        if self.front.stride is not None:
+            return _lib.lib().redux_decode_stride_workspace_bytes(C.byref(self.cp), nbytes, self.block_size, self.element_size,
+                                                                  self.front.stride)
         return _lib.lib().redux_decode_planes_workspace_bytes(C.byref(self.cp), nbytes, self.block_size, self.element_size)
 
     _takes_base = False  # (the entry points of base= and constant=True take a (base, base_len) pair, whole or gathered)
@@ -1537,7 +1565,10 @@ class DeviceDecoder(_DeviceCoder):
         out: a contiguous uint8 device tensor of sum(n) bytes at any alignment (a view into a larger one is fine); None: a
         new one.  Returns (out, [where each range begins in out]).  A covered block that does not decode raises its status
         (the decoder's summary is read: a synchronisation); ranges that leave [0, length], and covered granules of more than
-        max_blocks * block_size bytes, are InvalidInput.  Ranges without bytes make no GPU call."""
+        max_blocks * block_size bytes, are InvalidInput.  Ranges without bytes make no GPU call.  A decoder made with
+        filter="stride" raises Unsupported: an element of that filter needs every snapshot before it."""
+        if self.front.stride is not None:
+            raise Unsupported()
         torch = _torch()
         L = _lib.lib()
         B = self.block_size
@@ -1856,9 +1887,14 @@ def _transform(front, d_src, element_size, block_size, inverse, out, d_base=None
     t = out if out is not None else torch.empty(n, dtype=torch.uint8, device=d_src.device)
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n and t.device == d_src.device
     base = _base_pair(d_base) if front.takes_base else ()
+    ws = ()
+    if front.stride is not None:  # (its inverse keeps the time segments' sums in a workspace, in front of the stream)
+        need = _lib.lib().redux_stride_workspace_bytes(n, E, front.stride) if inverse else 0
+        d_ws = torch.empty(need, dtype=torch.uint8, device=t.device) if need else None
+        ws = (d_ws.data_ptr() if need else None, need)
     with torch.cuda.device(t.device):
         _raise(getattr(_lib.lib(), name)(d_src.data_ptr(), *base, t.data_ptr(), n, block_size, *_elem_args(front, E),
-                                         1 if inverse else 0, _stream_ptr(torch)))
+                                         1 if inverse else 0, *ws, _stream_ptr(torch)))
     return t
 
 
@@ -1894,6 +1930,25 @@ def lag_order_planes(d_src, element_size, block_size, lag, order, inverse=False,
         raise InvalidInput()
     _resolve_front(None, filter="lag", lag=lag, order=order)
     return _transform(_LAG_ORDER._replace(lag=int(lag), order=int(order)), d_src, element_size, block_size, inverse, out)
+
+
+def stride_planes(d_src, element_size, block_size, stride, inverse=False, out=None):
+    """The snapshot-stride filter followed by the byte-plane layout (include/redux_hip.h, "snapshot-stride filter") of a uint8
+    device tensor, or their inverse: redux_stride_planes_dev on torch's current stream.  stride: 1 or more, in elements.  The
+    inverse's workspace (redux_stride_workspace_bytes) is allocated here; torch's allocator keeps it alive for the stream.
+    out: as for planes()."""
+    return _transform(_resolve_front(None, filter="stride", stride=stride).front, d_src, element_size, block_size, inverse, out)
+
+
+def stride_kernel_name(nbytes, block_size, element_size, stride, inverse=False, d_src=None, d_dst=None):
+    """The kernels stride_planes runs for nbytes bytes (redux_stride_kernel_name; d_src and d_dst, device tensors: their
+    alignment counts; None: aligned), joined by " + "; "" for arguments the call refuses."""
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 0 <= stride < 1 << 64 \
+            or not isinstance(element_size, (int, np.integer)) or not 0 <= element_size < 1 << 32:
+        return ""
+    return _lib.lib().redux_stride_kernel_name(int(nbytes), int(block_size), int(element_size), int(stride), 1 if inverse else 0,
+                                               None if d_src is None else d_src.data_ptr(),
+                                               None if d_dst is None else d_dst.data_ptr()).decode()
 
 
 def record_planes(d_src, record_size, block_size, delta=False, inverse=False, out=None):

@@ -3,7 +3,7 @@
     python -m redux_amd.cli (-c | -d) [-i <input file>] [-o <output file>] [--block-size N] [--element-size E]
                             [--model adaptive|static|plane-static|segment-static|context-static|auto] [--segment-blocks G] [--checksum]
                             [--stored]
-                            [--filter delta|zigzag|lag] [--lag S|auto] [--order K] [--order-auto] [--record-size R|auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
+                            [--filter delta|zigzag|lag|stride] [--lag S|auto] [--stride S] [--order K] [--order-auto] [--record-size R|auto] [--base <base file>] [--skip-constant] [--layout auto|mixed]
                             [--range START:LENGTH] [--base-op xor|sub|auto]
 
 Same flags, same fixed Parameters::new(8, 30, 32) (main.rs:108), same exit codes (1 usage,
@@ -137,6 +137,17 @@ draws of noise explains.  The output is that choice's ordinary container, versio
 plain version 1 container where the layout is estimated to cost bytes: nothing new for -d.  On the generated tables above it
 finds 23 and 20 with the delta; no recorded table was measured.  `--record-size auto` with `--filter`, and with everything
 `--record-size R` is a usage error with, is a usage error.
+`--filter stride --stride S [--element-size E]` (with -c and a block size; S a decimal number of elements from 1 to 2^64 - 1;
+`--checksum` is allowed) is for ONE file of T snapshots of the same S elements -- a trajectory [frame, atom, xyz], a field
+[time, lat, lon], a stack of sensor frames, a tensor logged every step: every element is coded as its folded difference to the
+same element one snapshot back, S elements earlier in the file however far that is (`--lag` ends at 256, and `--base` needs the
+earlier snapshot as a second file).  On generated trajectories and sensor frames it comes out at 0.53 to 0.67 of the best of
+plain, planes, zigzag and lag; on unrelated snapshots it costs about 2 %, so nothing chooses it for the caller.  The output is
+container version 15, kind 2, which records S: -d reads it with no flag.  It has no range reads -- an element needs every
+snapshot before it -- so -d `--range` on such a container is a usage error with a message saying so.  `--stride` without
+`--filter stride`, `--filter stride` without `--stride`, an S that is no such number, and either with -d, `--block-size 0`,
+`--stored`, `--lag`, `--order`, `--order-auto`, `--record-size`, `--base`, `--skip-constant`, `--layout` or a `--model` other than
+adaptive are usage errors.
 `--range START:LENGTH` (with -d; both decimal, START + LENGTH at most the length of the data) writes only the bytes
 [START, START + LENGTH) of the original data, and decodes only the blocks that hold them (redux_amd/container.py: Reader;
 DESIGN.md 6o): one tensor out of a checkpoint.  With `-i FILE` the file is not read as a whole: the header and the tables are,
@@ -151,7 +162,7 @@ import sys
 
 USAGE = ("Usage: redux (-c | -d) [-i <input file>] [-o <output file>] [--block-size <bytes>] [--element-size <1|2|4|8>] "
          "[--model <adaptive|static|plane-static|segment-static|context-static|auto>] [--segment-blocks <G>] [--checksum] [--stored] "
-         "[--filter <delta|zigzag|lag>] [--lag <1..256|auto>] [--order <1|2|3>] [--order-auto] [--record-size <2..256>|auto] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
+         "[--filter <delta|zigzag|lag|stride>] [--lag <1..256|auto>] [--stride <S>] [--order <1|2|3>] [--order-auto] [--record-size <2..256>|auto] [--base <base file>] [--skip-constant] [--layout <auto|mixed>] [--range <start>:<length>] "
          "[--base-op <xor|sub|auto>]")
 
 
@@ -174,7 +185,7 @@ def parse(argv):
                 return None  # the order is given or counted, not both
             opts["order"] = "auto"
         elif arg in ("-i", "-o", "--block-size", "--element-size", "--model", "--segment-blocks", "--filter", "--base", "--layout", "--range",
-                     "--base-op", "--lag", "--order", "--record-size"):
+                     "--base-op", "--lag", "--order", "--record-size", "--stride"):
             val = next(it, None)
             if val is None:
                 return None
@@ -191,7 +202,7 @@ def parse(argv):
                     return None
                 opts["model"] = val
             elif arg == "--filter":
-                if val not in ("delta", "zigzag", "lag"):
+                if val not in ("delta", "zigzag", "lag", "stride"):
                     return None
                 opts["filter"] = val
             elif arg == "--lag":
@@ -201,6 +212,10 @@ def parse(argv):
                     return None
                 else:
                     opts["lag"] = int(val)
+            elif arg == "--stride":
+                if not (val.isascii() and val.isdigit()) or not 1 <= int(val) < 1 << 64:
+                    return None
+                opts["stride"] = int(val)
             elif arg == "--order":
                 if val not in ("1", "2", "3") or "order" in opts and opts["order"] == "auto":
                     return None
@@ -285,6 +300,11 @@ def parse(argv):
                                   or opts.get("filter", "delta") != "delta" or "order" in opts or "base" in opts
                                   or opts.get("skip_constant") or "layout" in opts):
         return None  # the record layout is recorded in the container; it stands in place of an element size, and its one filter is the byte delta
+    if ("stride" in opts) != (opts.get("filter") == "stride"):
+        return None  # the stride is the stride filter's, and that filter has no default for it
+    if "stride" in opts and (not opts["compress"] or "order" in opts or "record_size" in opts or "base" in opts
+                             or opts.get("skip_constant") or "layout" in opts):
+        return None  # the stride is recorded in the container, and the filter stands alone in front of the layout
     if opts.get("record_size") == "auto" and "filter" in opts:
         return None  # the filter is counted with the record size, not given
     if "range" in opts and opts["compress"] is not False:
@@ -335,7 +355,8 @@ def main(argv=None):
                                                 opts.get("element_size", None if "layout" in opts else 1),
                                                 opts.get("model", "adaptive"), opts.get("checksum", False),
                                                 opts.get("stored", False), opts.get("segment_blocks"), opts.get("filter"), base,
-                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("record_size"),
+                                                opts.get("skip_constant", False), opts.get("layout"), opts.get("stride"),
+                                                opts.get("record_size"),
                                                 opts.get("lag"), opts.get("order"), opts.get("base_op", "xor"))
                 sink.write(blob)
                 i_n, o_n = len(data), len(blob)
@@ -343,6 +364,11 @@ def main(argv=None):
         elif "range" in opts:
             # (a raw reference stream has no random access: what is no container fails the header's checks here)
             reader = container.Reader(data, base)
+            if reader.stride is not None:  # (known only once the header is read: a usage error all the same)
+                print("--range: a container of --filter stride has no range reads (an element needs every snapshot before "
+                      "it); decode it whole with -d", file=sys.stderr)
+                print(USAGE, file=sys.stderr)
+                return 1
             out = reader.read(*opts["range"])
             sink.write(out)
             i_n, o_n = reader.bytes_read, len(out)

@@ -13,7 +13,8 @@ Layout (little-endian):
            per unit of 8 blocks; 11 = zigzag-folded delta filter in front of the byte-plane layout; 12 = folded difference
            against a base in front of the byte-plane layout; 13 = lagged delta filter in front of the byte-plane layout;
            14 = higher-order lagged differences in front of the byte-plane layout; 15 = further layouts, told apart by a kind
-           field in the word at offset 12: kind 1 = record layout for fixed-width structs)
+           field in the word at offset 12: kind 1 = record layout for fixed-width structs; kind 2 = snapshot-stride filter
+           in front of the byte-plane layout)
     5   3  symbol_bits, freq_bits, code_bits      (Parameters::new arguments, src/model/mod.rs:63)
     8   4  block_size
    12   4  versions 1 and 3: reserved (0); version 2: element size E, one of 2, 4, 8; version 4: E in the low 16 bits and
@@ -25,10 +26,11 @@ Layout (little-endian):
            version 13: 0xD0000000 | S << 4 | E with E one of 1, 2, 4, 8 and the lag S, 1 <= S <= 256;
            version 14: 0xE0000000 | K << 16 | S << 4 | E with E and S as in version 13 and the order K, 2 <= K <= 3;
            version 15: 0xF0000000 | kind << 24 | F << 12 | R with kind 1, the record size R, 2 <= R <= 256, in bits 0 to 8 and
-           F 1 for the byte delta, else 0
+           F 1 for the byte delta, else 0; or 0xF0000000 | 2 << 24 | E with kind 2, E one of 1, 2, 4, 8 and every other bit 0
    16   8  nblocks
    24   8  total uncompressed length
    (versions 8 and 12, and version 9 with F = 1) 12  the base record: u64 base_used = min(len(base), total), u32 zlib.crc32(base[:base_used])
+   (version 15 kind 2 only) 8  the stride record: u64 S, the stride in elements, at least 1
    (version 3 only) 4*258  the static table cum[0..=257], u32
    (version 4 only) E*4*258  the E static tables, table t (blocks b with b mod E == t) first to last
    (version 5 only) nseg*E*4*258  the static tables, u32[nseg][E][258], nseg = max(1, ceil(nblocks / (64 E k)))
@@ -130,6 +132,15 @@ B records -- behind the byte delta against the record before when F is set, and 
 version takes that word, and version 15 takes no other.  It has no stored blocks (no 0x4F / 0x5F).  Without a record size the
 writers emit exactly the bytes they emitted before the version existed.
 
+Kind 2 of version 15 holds streams of the adaptive coder behind the snapshot-stride filter for time series of fields
+(include/redux_hip.h, "snapshot-stride filter"): every element against the element S back, counted over the whole buffer,
+in front of the byte-plane layout of E.  The word is 0xF0000000 | 2 << 24 | E with E one of 1, 2, 4, 8 in bits 0 to 3 and
+EVERY other bit zero; S does not fit a word and travels as a little-endian u64 record directly behind the header, where
+version 8 keeps its base record; the remaining sections are version 2's.  Any other bit, E outside the set or S = 0 is
+InvalidInput, a truncated record Eof; no other version takes the word.  It has no stored blocks, and no range reads: an
+element needs every snapshot before it, and the container keeps no keyframes (Reader.read raises Unsupported).  Without
+filter="stride" the writers emit exactly the bytes they emitted before the kind existed.
+
 Bit 0x10 of the version byte (versions 0x11 to 0x1F: versions 1 to 15 with checksums) means a table of nblocks
 CRC-32 values follows the size table: crc[b] = zlib.crc32 of block b's ORIGINAL bytes, x[b*B .. min((b+1)*B, total)), for
 every layout (include/redux_hip.h, "per-block CRC-32 checksums").  decompress_bytes checks every block against it: a
@@ -169,6 +180,8 @@ VERSION_LAG_ORDER = 14
 VERSION_KINDS = 15
 KINDS_MARK = 0xF0000000  # version 15's word at offset 12: KINDS_MARK | kind << 24 | what the kind records
 KIND_RECORD = 1  # the record layout: KINDS_MARK | KIND_RECORD << 24 | F << 12 | R
+KIND_STRIDE = 2  # the snapshot-stride filter: KINDS_MARK | KIND_STRIDE << 24 | E, every other bit zero; S in STRIDE_RECORD
+STRIDE_RECORD = struct.Struct("<Q")  # version 15 kind 2, after the header: the stride S in elements, at least 1
 RECORD_MAX = api.RECORD_MAX  # the largest record size R (REDUX_RECORD_MAX)
 LAG_ORDER_MARK = 0xE0000000  # version 14's word at offset 12: LAG_ORDER_MARK | K << 16 | S << 4 | E
 LAG_ORDER_MAX = api.LAG_ORDER_MAX  # the largest order K (REDUX_LAG_ORDER_MAX); version 14 records 2 .. LAG_ORDER_MAX
@@ -230,8 +243,16 @@ def _record_word(res):
     return R, bool(F)
 
 
+def _stride_word(res):
+    """E of a well-formed version 15 word of kind 2, else None"""
+    E = res & 0xF
+    if res != (KINDS_MARK | KIND_STRIDE << 24 | E) or E not in (1,) + ELEMENT_SIZES:
+        return None
+    return E
+
+
 def pack(streams, offsets, params, block_size, total_len, element_size=1, block_crc=None, stored=None, filter=None, base=None,
-         constant=None, unit_layouts=None, record_size=None, lag=None, order=None, base_op="xor"):
+         constant=None, unit_layouts=None, stride=None, record_size=None, lag=None, order=None, base_op="xor"):
     """streams: dense uint8 array; offsets: uint64[nblocks+1]; element_size: 1, or 2 / 4 / 8 for streams of the
     byte-plane layout (version 2).  params a StaticModel: streams of the static-table model (version 3, element size 1).
     params a PlaneStaticModel: streams of plane-static coding (version 4; element_size 1, the default, or the model's).
@@ -254,9 +275,11 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     base_op "sub" (with base, not with constant): streams of compress_blocks(..., base=y, base_op="sub") (version 12, as
     version 8).
     record_size R (with filter None or "delta" only): streams of compress_blocks(..., record_size=R, filter=) (version 15,
-    kind 1; adaptive model, element_size 1 and none of the other options)."""
+    kind 1; adaptive model, element_size 1 and none of the other options).
+    filter "stride" with stride S: streams of compress_blocks(..., filter="stride", stride=S) (version 15, kind 2, any
+    element_size, S as a u64 record behind the header; adaptive model and none of the other options)."""
     front, const, mixed = api._resolve_front(params, element_size, filter, base, base_op, constant, stored, unit_layouts, lag=lag,
-                                             order=order, record_size=record_size)
+                                             order=order, record_size=record_size, stride=stride)
     xbase = front.takes_base
     static, plane = isinstance(params, api.StaticModel), isinstance(params, api.PlaneStaticModel)
     segment = isinstance(params, api.SegmentStaticModel)
@@ -290,6 +313,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
         ver, res = VERSION_CONTEXT_STATIC, CONTEXT_MARK
     if front.record is not None:
         ver, res = VERSION_KINDS, KINDS_MARK | KIND_RECORD << 24 | front.record[1] << 12 | front.record[0]
+    elif front.stride is not None:
+        ver, res = VERSION_KINDS, KINDS_MARK | KIND_STRIDE << 24 | element_size
     elif filter is not None or xbase:
         ver = VERSION_LAG_ORDER if front.order else _VERSION_OF_FILTER[filter, base_op if xbase else None]
         res = FILTER_VERSIONS[ver].mark << 28 | (front.order or 0) << 16 | (front.lag or 0) << 4 | element_size
@@ -326,6 +351,8 @@ def pack(streams, offsets, params, block_size, total_len, element_size=1, block_
     head = HEADER.pack(MAGIC, ver, P.symbol_bits, P.freq_bits, P.code_bits, block_size, res, len(sizes), total_len)
     if xbase:
         head += BASE_RECORD.pack(base_used, base_crc)
+    if front.stride is not None:
+        head += STRIDE_RECORD.pack(front.stride)
     if static:
         head += params.cum.astype("<u4").tobytes()
     if plane or segment:
@@ -399,7 +426,7 @@ def _version_ok(ver, res):
         or (layout == VERSION_CONTEXT_STATIC and not ver & STORED_FLAG and res == CONTEXT_MARK) \
         or (layout == VERSION_CONST and not ver & STORED_FLAG and res >> 28 == 9 and res & 0x0FFFFFEF in (1,) + ELEMENT_SIZES) \
         or (layout == VERSION_MIXED and not ver & STORED_FLAG and res == MIXED_MARK) \
-        or (layout == VERSION_KINDS and not ver & STORED_FLAG and _record_word(res) is not None)
+        or (layout == VERSION_KINDS and not ver & STORED_FLAG and (_record_word(res) is not None or _stride_word(res) is not None))
 
 
 def _has_base_record(ver, res):
@@ -417,9 +444,10 @@ def _has_base_record(ver, res):
 # there is a record, else None.  constant: uint8[nblocks] of 0 / 1
 # for version 9, else None.  unit_layouts: uint8[ceil(nblocks / 8)] of 0 .. 7 for version 10, else None; element_size is then
 # None, as the table holds it unit by unit.  lag: the lag S of version 13 or 14, else None.  order: the order K of version 14,
-# else None.  record: (R, delta) of version 15's record layout, else None; element_size is then 1 and filter None.
+# else None.  record: (R, delta) of version 15's record layout, else None; element_size is then 1 and filter None.  stride: the
+# stride S of version 15's snapshot-stride filter (kind 2), else None; filter is then "stride".
 _Container = namedtuple("_Container", "params block_size total element_size static offsets payload crcs stored filter base constant"
-                        " unit_layouts base_op lag order record", defaults=(None, None, None, None, None))
+                        " unit_layouts base_op lag order record stride", defaults=(None, None, None, None, None, None))
 
 
 def _header(b):
@@ -435,7 +463,7 @@ def _header(b):
         raise api.InvalidInput()
     layout = _layout(ver)
     E = res & 0xF if layout in FILTER_VERSIONS or layout in (VERSION_SEGMENT_STATIC, VERSION_CONST) \
-        else res & 0xFFFF if layout == VERSION_PLANE_STATIC else 1
+        else res & 0xFFFF if layout == VERSION_PLANE_STATIC else _stride_word(res) or 1 if layout == VERSION_KINDS else 1
     return ver, P, block_size, E, nblocks, total
 
 
@@ -457,8 +485,15 @@ def _parse_index(b):
     _Container without its payload, where the payload begins).  Malformed containers raise InvalidInput, truncated ones Eof
     (src/lib.rs:57-64)."""
     ver, P, block_size, E, nblocks, total = _header(b)
-    static = crcs = stored = base = constant = units = None
+    static = crcs = stored = base = constant = units = stride = None
     at = HEADER.size
+    if _layout(ver) == VERSION_KINDS and _stride_word(HEADER.unpack_from(b, 0)[6]) is not None:  # where version 8 keeps its record
+        if len(b) < at + STRIDE_RECORD.size:
+            raise api.Eof()
+        stride, = STRIDE_RECORD.unpack_from(b, at)
+        at += STRIDE_RECORD.size
+        if stride == 0:
+            raise api.InvalidInput()
     if _has_base_record(ver, HEADER.unpack_from(b, 0)[6]):
         if len(b) < at + BASE_RECORD.size:
             raise api.Eof()
@@ -524,10 +559,11 @@ def _parse_index(b):
             raise api.InvalidInput()
         E = None
     row = FILTER_VERSIONS.get(_layout(ver))  # (version 9's record, where it has one, is the XOR's)
-    return _Container(P, block_size, total, E, static, offsets, None, crcs, stored, row.filter if row else None, base, constant,
+    return _Container(P, block_size, total, E, static, offsets, None, crcs, stored,
+                      row.filter if row else "stride" if stride is not None else None, base, constant,
                       units, row.base_op if row else None if base is None else "xor",
                       *(_lag_word(row, HEADER.unpack_from(b, 0)[6]) if row and row.has_lag else (None, None)),
-                      _record_word(HEADER.unpack_from(b, 0)[6]) if _layout(ver) == VERSION_KINDS else None), at
+                      _record_word(HEADER.unpack_from(b, 0)[6]) if _layout(ver) == VERSION_KINDS else None, stride), at
 
 
 def _parse(buf):
@@ -587,6 +623,13 @@ def record(buf):
     the byte delta against the record before was applied; None for every other container.  Malformed containers raise
     InvalidInput, truncated ones Eof."""
     return _parse(buf).record
+
+
+def stride(buf):
+    """(E, S) of a version 15 container of kind 2 (the snapshot-stride filter): the element size and the stride in elements;
+    None for every other container.  Malformed containers raise InvalidInput, truncated ones Eof."""
+    c = _parse(buf)
+    return None if c.stride is None else (c.element_size, c.stride)
 
 
 def base(buf):
@@ -665,7 +708,13 @@ def overhead_bytes(model, nblocks, element_size=1, segment_blocks=None, context_
     filter, not stored): version 10, whose unit table adds a byte per 8 blocks.  base (adaptive model, no filter, not stored, not
     mixed): version 8 or 12, whose base record adds 12 bytes whatever the operation.  record_size (adaptive model, element size 1,
     filter None or "delta", not stored, not mixed, no base): version 15, which records the layout in the header's reserved word
-    and adds no bytes."""
+    and adds no bytes.  filter "stride" (adaptive model, any element size, not stored, not mixed, no base, no record size):
+    version 15 kind 2, whose stride record adds 8 bytes."""
+    if isinstance(filter, str) and filter == "stride":
+        if model != "adaptive" or stored or mixed or base or record_size is not None or nblocks < 1:
+            raise api.InvalidInput()
+        api._check_element_size(element_size)
+        return HEADER.size + STRIDE_RECORD.size + 4 * nblocks + (4 * nblocks if checksum else 0)
     if record_size is not None:
         if model != "adaptive" or stored or mixed or base:
             raise api.InvalidInput()
@@ -794,7 +843,7 @@ def choose_base_op(estimates):
 
 
 def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, model="adaptive", checksum=False,
-                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, record_size=None, lag=None,
+                   stored=False, segment_blocks=None, filter=None, base=None, skip_constant=False, layout=None, stride=None, record_size=None, lag=None,
                    order=None, base_op="xor"):
     """bytes -> container bytes (every block coded on the GPU); element_size 2 / 4 / 8: byte-plane layout, version 2.
     model "static": the static table of the data (api.static_table, default total) codes every block, version 3.
@@ -849,7 +898,20 @@ def compress_bytes(data, block_size=65536, params=(8, 30, 32), element_size=1, m
     counted on the GPU from the bytes as they are, on a sample first, then exactly for the finalists and for the plain bytes,
 which also keep every gain that noise among 510 candidates explains),
     and the container is that choice's ordinary one, version 15 -- or version 1 where the plain bytes are estimated no
-    larger: nothing new to decode."""
+    larger: nothing new to decode.
+    filter "stride" with stride S, 1 or more (any element_size, model "adaptive", and none of stored, segment_blocks, base,
+    skip_constant, layout, record_size, lag and order): the snapshot-stride filter for one buffer of T snapshots of the same S
+    elements, every element against the same element one snapshot back.  Version 15, kind 2, which records S; the container has
+    no range reads.  A stride without the filter is InvalidInput, and so is the filter without one."""
+    if stride is not None or (isinstance(filter, str) and filter == "stride"):
+        if layout is not None or model != "adaptive" or stored or segment_blocks is not None or skip_constant or base_op != "xor" \
+                or not 0 < block_size <= MAX_BLOCK_SIZE:
+            raise api.InvalidInput()
+        api._resolve_front(None, element_size, filter, base, lag=lag, order=order, record_size=record_size, stride=stride)
+        crc = np.zeros(max(1, -(-len(data) // block_size)), dtype=np.uint32) if checksum else None
+        out, offs, _ = api.compress_blocks(data, block_size, params, element_size=element_size, block_crc=crc, filter=filter,
+                                           stride=stride)
+        return pack(out, offs, params, block_size, len(data), element_size, block_crc=crc, filter=filter, stride=stride)
     auto_record = isinstance(record_size, str) and record_size == "auto"  # (the choice is made below, once nothing refuses the call)
     if auto_record:
         if filter is not None:
@@ -964,7 +1026,7 @@ def _decode_parsed(c, base):
     segment = isinstance(c.static, api.SegmentStaticModel)
     mixed = c.unit_layouts is not None
     exact = mixed or c.element_size > 1 or c.stored is not None or segment or c.filter is not None or c.base is not None \
-        or c.constant is not None or c.record is not None
+        or c.constant is not None or c.record is not None  # (c.filter: "stride" of version 15 kind 2 included)
     cap = max(1, min(c.block_size, c.total))  # one short block never needs block_size bytes of capacity
     try:
         if mixed:
@@ -977,7 +1039,7 @@ def _decode_parsed(c, base):
                                                        stored=c.stored, base=base, constant=c.constant,
                                                        filter="delta" if c.record is not None and c.record[1] else c.filter,
                                                        base_op=c.base_op or "xor", lag=c.lag, order=c.order,
-                                                       record_size=None if c.record is None else c.record[0])
+                                                       record_size=None if c.record is None else c.record[0], stride=c.stride)
         else:  # (straight into out[b * cap ..], no plane buffer)
             out, sizes, status = api.decompress_blocks(c.payload, c.offsets, cap, c.static or c.params, block_crc=got)
     except MemoryError:  # a header can declare far more output than this machine holds: malformed for our purposes
@@ -1049,6 +1111,8 @@ class Reader:
         res = HEADER.unpack_from(head, 0)[6]
         layout = _layout(ver)
         tables = BASE_RECORD.size if _has_base_record(ver, res) else 0
+        if layout == VERSION_KINDS and _stride_word(res) is not None:
+            tables += STRIDE_RECORD.size
         if layout == VERSION_STATIC:
             tables += TABLE
         elif layout == VERSION_PLANE_STATIC:
@@ -1067,6 +1131,7 @@ class Reader:
         self.version, self.total, self.block_size, self.nblocks = ver, c.total, c.block_size, nblocks
         self.filter, self.base_op, self.lag, self.order = c.filter, c.base_op, c.lag, c.order
         self.record = c.record
+        self.stride = c.stride
         self.granule_blocks = MIXED_UNIT_BLOCKS if c.unit_layouts is not None \
             else c.static.segment_blocks if isinstance(c.static, api.SegmentStaticModel) \
             else c.record[0] if c.record is not None else c.element_size
@@ -1084,7 +1149,10 @@ class Reader:
         """-> [the bytes of each (start, length) of `ranges`], which may come in any order, overlap and repeat: the granules
         they cover are decoded once, in one decompress_blocks call (none when no range has bytes), with every check
         decompress_bytes makes applied to the covered blocks.  A range that leaves [0, total] is InvalidInput; a source that
-        ends inside a covered stream is Eof."""
+        ends inside a covered stream is Eof.  A container of the snapshot-stride filter (version 15, kind 2) raises Unsupported:
+        an element there needs every snapshot before it, and the container keeps no keyframes."""
+        if self.stride is not None:
+            raise api.Unsupported()
         c, g, B = self._c, self.granule_blocks, self.block_size
         ranges = list(ranges)
         runs, virt_off, virt_len = api.range_plan(c.total, B, g, ranges)

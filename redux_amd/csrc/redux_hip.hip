@@ -19,6 +19,7 @@
 //   redux_record.hpp   k_record_planes / k_record_unplanes: the record layout for fixed-width structs, R bytes a record, with a byte delta
 //   redux_base.hpp     k_base_planes / k_base_unplanes: the XOR-against-base filter for snapshot series, fused with the layout
 //   redux_base_sub.hpp BaseSubFold: the base filter's folded difference, the same kernels under another operation
+//   redux_stride.hpp k_stride_planes / k_stride_sum: the snapshot-stride filter, the folded difference S elements back
 //   redux_hist.hpp     k_byte_hist / k_static_table: semi-static coding, the static table built from the data
 //   redux_plane_static.hpp  k_plane_hist, the tables and their check: the static coder with one table per byte plane
 //   redux_segment_static.hpp  k_segment_hist / k_static_tables / k_*_segment_static*: E tables per range of blocks, or for all
@@ -56,6 +57,7 @@
 #include "redux_record.hpp"
 #include "redux_base.hpp"
 #include "redux_base_sub.hpp"
+#include "redux_stride.hpp"
 #include "redux_hist.hpp"
 #include "redux_plane_static.hpp"
 #include "redux_segment_static.hpp"
@@ -787,14 +789,16 @@ static int for_element_size(uint32_t element_size, F &&f)
 // the kernel launch: a new filter is a new value here.
 // RecordDelta is the byte delta of the record layout (redux_record.hpp) and goes with a record size only; the record layout
 // without it is Filter::None with a record size.
-enum class Filter { None, Delta, Zigzag, Lag, LagOrder, BaseXor, BaseSub, RecordDelta };
+// Stride is the snapshot-stride filter (redux_stride.hpp): its stride is a u64 and its inverse takes a workspace, so it has a
+// transform of its own (stride_transform_dev) and never reaches transform_dev.
+enum class Filter { None, Delta, Zigzag, Lag, LagOrder, BaseXor, BaseSub, RecordDelta, Stride };
 
 static bool filter_has_base(Filter f) { return f == Filter::BaseXor || f == Filter::BaseSub; }
 
 // the element size's check, and the lag's and the order's where the filter has them
 static int filter_check(Filter f, uint32_t element_size, uint32_t lag, uint32_t order)
 {
-    return f == Filter::RecordDelta ? REDUX_INVALID_INPUT // (no element-size layout has it)
+    return f == Filter::RecordDelta || f == Filter::Stride ? REDUX_INVALID_INPUT // (no element-size layout has it; its own check)
            : f == Filter::LagOrder ? redux_lag_order_check(element_size, lag, order)
            : f == Filter::Lag    ? redux_lag_check(element_size, lag)
                                  : redux_planes_check(element_size);
@@ -839,6 +843,7 @@ static int transform_dev(Filter filter, const void *d_src, void *d_dst, uint64_t
             return launch_filter<E>(k_delta_planes<E, false>, k_delta_unplanes<E, false>, k_delta_planes_bytes<E, false>,
                                     k_delta_unplanes_bytes<E, false>, d_src, d_dst, len, block_size, inv, s);
         case Filter::RecordDelta: // (refused above)
+        case Filter::Stride:
         case Filter::None: break;
         }
         if constexpr (E == 1) { // the layout of single bytes is the identity
@@ -864,6 +869,118 @@ static int record_transform_dev(const void *d_src, void *d_dst, uint64_t len, ui
     return launch_record(d_src, d_dst, len, block_size, record_size, delta != 0, inverse != 0, (hipStream_t)stream);
 }
 
+// the snapshot-stride filter (redux_stride.hpp).  Forward: the fused kernel takes the full frames, the byte kernel the rest, as
+// the layout does.  Inverse: the layout's own inverse into the destination (a copy for E = 1), then the running sums in place,
+// in the shape stride_plan (redux_stride_host.hpp) gives them.  The one decision: the launches below and
+// redux_stride_kernel_name both read StrideShape.
+struct StrideShape {
+    FastSplit  f;    // the layout's split, either direction
+    StridePlan p;    // inverse: stage two
+    int        form; // inverse: 0 chunks, 1 elements, 2 elements byte by byte
+};
+
+static StrideShape stride_shape(const void *d_src, const void *d_dst, uint64_t len, uint32_t block_size, uint32_t E, uint64_t S, bool inverse)
+{
+    StrideShape h;
+    h.f    = fast_split(len, (uint64_t)E * block_size, block_size, {d_src, d_dst});
+    h.p    = inverse ? stride_plan(len, E, S, ((uintptr_t)d_dst & 15) == 0) : StridePlan{};
+    h.form = h.p.chunks ? 0 : (uintptr_t)d_dst % E == 0 ? 1 : 2;
+    return h;
+}
+
+template <int E, int FORM>
+static void launch_stride_sum(const StrideSumArgs &a, hipStream_t s)
+{
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((a.segs * a.cols + 255) / 256, 1u << 22); // (the threads stride over the rest)
+    if (a.segs > 1) {
+        k_stride_totals<E, FORM><<<grid, 256, 0, s>>>(a);
+        k_stride_scan<E, FORM><<<(uint32_t)std::min<uint64_t>(a.cols, 1u << 16), 256, 0, s>>>(a);
+    }
+    k_stride_sum<E, FORM><<<grid, 256, 0, s>>>(a);
+}
+
+template <int E>
+static int launch_stride(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint64_t S, bool inverse, void *d_ws,
+                         uint64_t ws_bytes, hipStream_t s)
+{
+    const StrideShape h = stride_shape(d_src, d_dst, len, block_size, E, S, inverse);
+    if (!inverse) {
+        StrideArgs a;
+        a.src          = (const uint8_t *)d_src;
+        a.dst          = (uint8_t *)d_dst;
+        a.block_size   = block_size;
+        a.frame_groups = block_size / 16;
+        a.groups       = h.f.nfull * (E == 1 ? block_size / 16 : a.frame_groups);
+        a.first        = h.f.rest;
+        a.len          = len;
+        a.S            = S;
+        a.D            = S >= len / E ? ~0ull : S * E;
+        if (h.f.nfull) {
+            uint32_t grid;
+            if (!grid_tiles((a.groups + 255) / 256, &grid))
+                return REDUX_UNSUPPORTED;
+            k_stride_planes<E><<<grid, 256, 0, s>>>(a);
+        }
+        if (h.f.rest < len)
+            k_stride_planes_bytes<E><<<grid_bytes(len - h.f.rest), 256, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+        return REDUX_OK;
+    }
+    // (the workspace first: a call that cannot run writes nothing)
+    uint8_t *ws = (uint8_t *)(((uintptr_t)d_ws + 15) & ~(uintptr_t)15);
+    if (h.p.ws_bytes && (!d_ws || ws_bytes < h.p.ws_bytes + (uint64_t)(ws - (uint8_t *)d_ws)))
+        return REDUX_OUTPUT_TOO_SMALL;
+    if constexpr (E == 1) {
+        HIP_TRY(hipMemcpyAsync(d_dst, d_src, len, hipMemcpyDeviceToDevice, s));
+    } else {
+        const int st = launch_planes<E>(d_src, d_dst, len, block_size, true, s);
+        if (st != REDUX_OK)
+            return st;
+    }
+    if (!h.p.run)
+        return REDUX_OK;
+    StrideSumArgs a;
+    a.dst       = (uint8_t *)d_dst;
+    a.ws        = ws;
+    a.cols      = h.p.cols;
+    a.rows      = h.p.rows;
+    a.segs      = h.p.segs;
+    a.steps     = h.p.steps;
+    a.row_bytes = S * E;
+    a.head      = h.p.head;
+    a.S         = S;
+    a.n         = h.p.n;
+    if (h.p.rows >= 2) {
+        if (h.form == 0)
+            launch_stride_sum<E, 0>(a, s);
+        else if (h.form == 1)
+            launch_stride_sum<E, 1>(a, s);
+        else
+            launch_stride_sum<E, 2>(a, s);
+    }
+    if (h.p.chunks && h.p.head < h.p.n * E)
+        k_stride_sum_tail<E><<<1, 64, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return REDUX_OK;
+}
+
+// redux_stride_planes_dev: transform_dev's checks for the snapshot-stride filter, then its launch
+static int stride_transform_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, uint64_t stride,
+                                int inverse, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    if (redux_stride_check(element_size, stride) != REDUX_OK || block_size == 0 || (len && (!d_src || !d_dst)))
+        return REDUX_INVALID_INPUT;
+    if (len == 0)
+        return REDUX_OK;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + len && d0 < s0 + len) // (not in place: the forward reads bytes another thread would have written)
+        return REDUX_INVALID_INPUT;
+    return for_element_size(element_size, [&](auto e) -> int {
+        return launch_stride<decltype(e)::value>(d_src, d_dst, len, block_size, stride, inverse != 0, d_workspace, workspace_bytes,
+                                                 (hipStream_t)stream);
+    });
+}
+
 // ---- the layout stage of the layered calls ---------------------------------------------------------------------------
 // What runs between the caller's bytes and a coder: the byte-plane layout for elements of E bytes, with a filter in front
 // of it or none.  The layout of single bytes is the identity; a filter over single bytes is not.
@@ -875,9 +992,15 @@ struct Layout {
     uint32_t    lag      = 0;       // the lagged delta filter's lag
     uint32_t    order    = 0;       // the order of higher-order lagged differences
     uint32_t    record   = 0;       // the record layout's record size (E is 1 then, and does not say how many blocks a frame has)
+    uint64_t    stride   = 0;       // the snapshot-stride filter's stride, in elements
+    void       *d_ws     = nullptr; // and the workspace of its inverse's second stage, d_ws[0 .. ws_bytes)
+    uint64_t    ws_bytes = 0;
     bool        record_delta() const { return filter == Filter::RecordDelta; }
+    bool        is_stride() const { return filter == Filter::Stride; }
     int         check() const
     {
+        if (is_stride())
+            return record ? REDUX_INVALID_INPUT : redux_stride_check(E, stride);
         if (record)
             return E == 1 && (filter == Filter::None || record_delta()) ? redux_record_check(record, record_delta()) : REDUX_INVALID_INPUT;
         return filter_check(filter, E, lag, order);
@@ -890,6 +1013,8 @@ struct Layout {
     {
         if (record)
             return record_transform_dev(d_src, d_dst, len, block_size, record, record_delta(), inv, stream);
+        if (is_stride())
+            return stride_transform_dev(d_src, d_dst, len, block_size, E, stride, inv, d_ws, ws_bytes, stream);
         return transform_dev(filter, d_src, d_dst, len, block_size, E, inv, stream, d_base, base_len, lag, order);
     }
     int forward(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, void *stream) const
@@ -2555,11 +2680,19 @@ static int decode_layout_dev(Layout L, const redux_params *p, const void *d_in, 
         return REDUX_INVALID_INPUT;
     const uint64_t nblocks = redux_block_count(out_len, block_size);
     const uint64_t copy    = planes_copy_bytes(nblocks * (uint64_t)block_size);
-    if (workspace_bytes < redux_decode_planes_workspace_bytes(p, out_len, block_size, L.E))
+    // (the snapshot-stride filter's inverse has a workspace of its own, behind the decoder's)
+    const uint64_t coder_ws = redux_decode_planes_workspace_bytes(p, out_len, block_size, L.E);
+    const uint64_t sum_ws   = L.is_stride() ? stride_workspace_bytes(out_len, L.E, L.stride) : 0;
+    if (workspace_bytes < (sum_ws ? align_up(coder_ws, 256) + sum_ws : coder_ws))
         return REDUX_OUTPUT_TOO_SMALL;
     uint8_t *t = (uint8_t *)d_workspace;
+    if (sum_ws) {
+        L.d_ws     = t + align_up(coder_ws, 256);
+        L.ws_bytes = sum_ws;
+    }
     st = decode_blocks_dev_impl(p, d_in, d_in_offsets, nblocks, block_size, t, nblocks * (uint64_t)block_size, d_out_sizes,
-                                d_block_status, d_summary, t + copy, workspace_bytes - copy, stream, nullptr, BlockTable{});
+                                d_block_status, d_summary, t + copy, (sum_ws ? coder_ws : workspace_bytes) - copy, stream, nullptr,
+                                BlockTable{});
     if (st != REDUX_OK)
         return st;
     return layout_decode_tail(L, t, d_out, out_len, block_size, d_out_sizes, d_block_status, d_summary, TailSummary::InSizes, stream);
@@ -2594,12 +2727,26 @@ static host::EncodeCoder layout_encoder(const redux_params *p, uint32_t block_si
 // decodes exactly the chunk's share of out_len
 static host::DecodeCoder layout_decoder(const redux_params *p, uint32_t block_size, Layout L)
 {
-    return {[=](uint64_t cb) { return redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, L.E); },
+    return {[=](uint64_t cb) {
+                const uint64_t ws = redux_decode_planes_workspace_bytes(p, cb * (uint64_t)block_size, block_size, L.E);
+                return L.is_stride() ? align_up(ws, 256) + stride_workspace_bytes(cb * (uint64_t)block_size, L.E, L.stride) : ws;
+            },
             [=](host::Slot &s, uint64_t, uint64_t out_bytes, void *, void *ws, uint64_t ws_bytes, hipStream_t st) {
                 return decode_layout_dev(layout_of_slot(L, s), p, s.d_in.p, s.d_off.p, out_bytes, block_size, s.d_out.p, s.d_sz.p, s.d_st.p,
                                          s.d_sum.p, ws, ws_bytes, st);
             },
             true};
+}
+
+// The snapshot-stride filter's predecessor lies S elements back, wherever that is: a chunk cut would put the inverse's
+// predecessors in another chunk.  Its host pair therefore runs as ONE chunk, which the chunk loop hands to the call's first
+// context: frames of as many blocks as the call has make it so (host::chunk_blocks_framed).
+static bool stride_one_chunk(uint64_t nblocks, uint32_t *frame_blocks)
+{
+    if (nblocks > 0xFFFFFFFFull)
+        return false;
+    *frame_blocks = nblocks > 1 ? (uint32_t)nblocks : 1;
+    return true;
 }
 
 // the host-pointer calls (redux_host.hpp); base[0 .. base_len): a base filter's base, the chunks take their shares of it
@@ -2614,8 +2761,11 @@ static int encode_blocks_layout(Layout L, const redux_params *p, const uint8_t *
         (L.has_base() && base_len && !base))
         return REDUX_INVALID_INPUT;
     const host::EncodeCoder coder = L.identity() ? adaptive_encoder(p, block_size) : layout_encoder(p, block_size, L);
+    uint32_t frame_blocks = L.record;
+    if (L.is_stride() && !stride_one_chunk(redux_block_count(in_len, block_size), &frame_blocks))
+        return REDUX_UNSUPPORTED;
     return host::encode_blocks(in, in_len, block_size, out, out_cap, out_offsets, block_status, coder, block_crc, nullptr, {},
-                               host::BaseIo{base, base_len, L.has_base()}, {}, L.record);
+                               host::BaseIo{base, base_len, L.has_base()}, {}, frame_blocks);
 }
 
 static int encode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, uint64_t in_len, const uint8_t *base,
@@ -2634,9 +2784,12 @@ static int decode_blocks_layout(Layout L, const redux_params *p, const uint8_t *
     int st = check_params(p);
     if (st == REDUX_OK && (L.check() != REDUX_OK || (L.has_base() && base_len && !base)))
         st = REDUX_INVALID_INPUT;
+    uint32_t frame_blocks = L.record;
+    if (st == REDUX_OK && block_size && L.is_stride() && !stride_one_chunk(redux_block_count(out_len, block_size), &frame_blocks))
+        st = REDUX_UNSUPPORTED;
     return decode_blocks_host(st, in, in_offsets, redux_block_count(out_len, block_size), block_size, out, out_len, out_len, out_sizes,
                               block_status, nullptr, layout_decoder(p, block_size, L), block_crc, nullptr, {},
-                              host::BaseIo{base, base_len, L.has_base()}, {}, L.record);
+                              host::BaseIo{base, base_len, L.has_base()}, {}, frame_blocks);
 }
 
 static int decode_blocks_layout(Filter f, const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, const uint8_t *base,
@@ -3082,6 +3235,114 @@ int redux_decode_blocks_base_sub(const redux_params *p, const uint8_t *in, const
 {
     return decode_blocks_layout(Filter::BaseSub, p, in, in_offsets, base, base_len, out_len, block_size, element_size, out, out_sizes,
                                 block_status, block_crc);
+}
+
+// -- snapshot-stride filter (redux_stride.hpp): the stride, a u64, behind the element size; the inverse takes a workspace
+int redux_stride_check(uint32_t element_size, uint64_t stride) { return stride_args_ok(element_size, stride) ? REDUX_OK : REDUX_INVALID_INPUT; }
+
+uint64_t redux_stride_workspace_bytes(uint64_t len, uint32_t element_size, uint64_t stride)
+{
+    return stride_workspace_bytes(len, element_size, stride); // (0 for bad arguments too)
+}
+
+int redux_stride_planes_dev(const void *d_src, void *d_dst, uint64_t len, uint32_t block_size, uint32_t element_size, uint64_t stride,
+                            int inverse, void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return stride_transform_dev(d_src, d_dst, len, block_size, element_size, stride, inverse, d_workspace, workspace_bytes, stream);
+}
+
+uint64_t redux_encode_stride_workspace_bytes(const redux_params *p, uint64_t in_len, uint32_t block_size, uint32_t element_size)
+{
+    return encode_layout_workspace_bytes(Filter::Stride, p, in_len, block_size, element_size);
+}
+
+uint64_t redux_decode_stride_workspace_bytes(const redux_params *p, uint64_t out_len, uint32_t block_size, uint32_t element_size,
+                                             uint64_t stride)
+{
+    if (redux_stride_check(element_size, stride) != REDUX_OK)
+        return 0;
+    const uint64_t ws = redux_decode_planes_workspace_bytes(p, out_len, block_size, element_size);
+    return ws ? align_up(ws, 256) + stride_workspace_bytes(out_len, element_size, stride) : 0;
+}
+
+static Layout stride_layout(uint32_t element_size, uint64_t stride)
+{
+    Layout L{element_size, Filter::Stride};
+    L.stride = stride;
+    return L;
+}
+
+int redux_encode_stride_dev(const redux_params *p, const void *d_in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                            uint64_t stride, void *d_out, uint64_t out_cap, void *d_out_offsets, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return encode_layout_dev(stride_layout(element_size, stride), p, d_in, in_len, block_size, d_out, out_cap, d_out_offsets,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_decode_stride_dev(const redux_params *p, const void *d_in, const void *d_in_offsets, uint64_t out_len, uint32_t block_size,
+                            uint32_t element_size, uint64_t stride, void *d_out, void *d_out_sizes, void *d_block_status, void *d_summary,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream)
+{
+    return decode_layout_dev(stride_layout(element_size, stride), p, d_in, d_in_offsets, out_len, block_size, d_out, d_out_sizes,
+                             d_block_status, d_summary, d_workspace, workspace_bytes, stream);
+}
+
+int redux_encode_blocks_stride(const redux_params *p, const uint8_t *in, uint64_t in_len, uint32_t block_size, uint32_t element_size,
+                               uint64_t stride, uint8_t *out, uint64_t out_cap, uint64_t *out_offsets, int32_t *block_status,
+                               uint32_t *block_crc)
+{
+    return encode_blocks_layout(stride_layout(element_size, stride), p, in, in_len, nullptr, 0, block_size, out, out_cap, out_offsets,
+                                block_status, block_crc);
+}
+
+int redux_decode_blocks_stride(const redux_params *p, const uint8_t *in, const uint64_t *in_offsets, uint64_t out_len,
+                               uint32_t block_size, uint32_t element_size, uint64_t stride, uint8_t *out, uint32_t *out_sizes,
+                               int32_t *block_status, uint32_t *block_crc)
+{
+    return decode_blocks_layout(stride_layout(element_size, stride), p, in, in_offsets, nullptr, 0, out_len, block_size, out, out_sizes,
+                                block_status, block_crc);
+}
+
+const char *redux_stride_kernel_name(uint64_t len, uint32_t block_size, uint32_t element_size, uint64_t stride, int inverse,
+                                     const void *d_src, const void *d_dst)
+{
+    static thread_local std::string name;
+    name.clear();
+    if (block_size == 0 || redux_stride_check(element_size, stride) != REDUX_OK || len == 0)
+        return "";
+    const StrideShape h = stride_shape(d_src, d_dst, len, block_size, element_size, stride, inverse != 0);
+    auto add = [&](const char *s) {
+        if (!name.empty())
+            name += " + ";
+        name += s;
+    };
+    if (!inverse) {
+        if (h.f.nfull)
+            add("k_stride_planes");
+        if (h.f.rest < len)
+            add("k_stride_planes_bytes");
+        return name.c_str();
+    }
+    if (element_size == 1)
+        add("copy");
+    else {
+        if (h.f.nfull)
+            add("k_planes");
+        if (h.f.rest < len)
+            add("k_planes_bytes");
+    }
+    if (h.p.run && h.p.rows >= 2) {
+        const bool bytes = h.form != 0;
+        if (h.p.segs > 1) {
+            add(bytes ? "k_stride_totals_bytes" : "k_stride_totals");
+            add(bytes ? "k_stride_scan_bytes" : "k_stride_scan");
+        }
+        add(bytes ? "k_stride_sum_bytes" : "k_stride_sum");
+    }
+    if (h.p.run && h.p.chunks && h.p.head < h.p.n * element_size)
+        add("k_stride_sum_tail");
+    return name.c_str();
 }
 
 // ---- plane-static coding (redux_plane_static.hpp) ------------------------------------------------

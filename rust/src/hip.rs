@@ -92,6 +92,15 @@ extern "C" {
     fn redux_decode_blocks_record(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
                                   block_size: u32, record_size: u32, delta: c_int, out: *mut u8, out_sizes: *mut u32,
                                   block_status: *mut i32, block_crc: *mut u32) -> c_int;
+    // snapshot-stride filter for time series of fields: the lag calls' shape with the stride, a u64, where the lag is.  The pair
+    // stages the whole buffer on one device (include/redux_hip.h, "snapshot-stride filter")
+    fn redux_stride_check(element_size: u32, stride: u64) -> c_int;
+    fn redux_encode_blocks_stride(p: *const ReduxParams, input: *const u8, in_len: u64, block_size: u32, element_size: u32,
+                                  stride: u64, out: *mut u8, out_cap: u64, out_offsets: *mut u64, block_status: *mut i32,
+                                  block_crc: *mut u32) -> c_int;
+    fn redux_decode_blocks_stride(p: *const ReduxParams, input: *const u8, in_offsets: *const u64, out_len: u64,
+                                  block_size: u32, element_size: u32, stride: u64, out: *mut u8, out_sizes: *mut u32,
+                                  block_status: *mut i32, block_crc: *mut u32) -> c_int;
     // XOR-against-base filter for series of snapshots, in front of the byte-plane layout (base null only with base_len 0;
     // block_crc may be null)
     fn redux_encode_blocks_base(p: *const ReduxParams, input: *const u8, in_len: u64, base: *const u8, base_len: u64,
