@@ -495,9 +495,15 @@ __device__ __forceinline__ void spec_end(EncState &S, const SpecCarry &C)
     S.ihigh = C.ih & 0x7FFFFFFFu;
 }
 
-template <bool FIXUP, bool CB32, int ST = 4>
-__device__ __forceinline__ uint32_t encode_symbol_spec(EncState &S, SpecCarry &C, uint32_t lo, uint32_t hi, uint32_t c,
-                                                       double rc, uint32_t sh_, uint8_t *wbase)
+// What one symbol appends: the m-bit number topk + run (< 2^m whenever m <= 32; m = 0: both terms are 0).
+struct SpecBits {
+    uint32_t m, topk, run;
+};
+
+// The narrowing half of encode_symbol_spec: the new interval (S.low, C.ih, C.r1), S.pend, and the symbol's append.
+template <bool FIXUP, bool CB32>
+__device__ __forceinline__ SpecBits spec_narrow(EncState &S, SpecCarry &C, uint32_t lo, uint32_t hi, uint32_t c, double rc,
+                                                uint32_t sh_)
 {
     const uint32_t sh = CB32 ? 0u : sh_;
     const uint32_t R1 = C.r1 >> sh;
@@ -537,11 +543,20 @@ __device__ __forceinline__ uint32_t encode_symbol_spec(EncState &S, SpecCarry &C
     const uint32_t m  = k + Pz;
     uint32_t run;
     asm("v_bfm_b32 %0, %1, %2" : "=v"(run) : "v"(Pz), "v"(km1));
+    return SpecBits{m, topk, run};
+}
+
+template <bool FIXUP, bool CB32, int ST = 4>
+__device__ __forceinline__ uint32_t encode_symbol_spec(EncState &S, SpecCarry &C, uint32_t lo, uint32_t hi, uint32_t c,
+                                                       double rc, uint32_t sh_, uint8_t *wbase)
+{
+    const SpecBits B    = spec_narrow<FIXUP, CB32>(S, C, lo, hi, c, rc, sh_);
+    const uint32_t m    = B.m;
     // acc = (acc << m) | (topk + run): the low m bits of the shifted accumulator are zero and
     // topk + run < 2^m, so the OR is an addition and the three terms are one v_add3_u32
     // (the & 63 is what v_lshlrev_b64 does anyway: no instruction)
     const uint64_t sa = S.acc << (m & 63u);
-    S.acc = (sa & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)sa + topk + run);
+    S.acc = (sa & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)sa + B.topk + B.run);
     // nbm = (bits in the accumulator) - 32, in [-32, -1] between symbols: its sign is the "a dword
     // is complete" test, its value the shift that extracts the dword, and OR-ing -32 takes the 32
     // stored bits off again (a lane that raised the flag has garbage here; everything stays bounded)
@@ -553,6 +568,45 @@ __device__ __forceinline__ uint32_t encode_symbol_spec(EncState &S, SpecCarry &C
     }
     C.nbm = nb | 0xFFFFFFE0u;
     return m; // the caller raises the flag if any m of the half exceeds 32
+}
+
+// encode_symbol_spec for two consecutive symbols a, b (each {lo, hi}; counts ca, cb; reciprocals rca, rcb) with ONE append
+// and ONE store region.  The intervals, pend, and each symbol's m, topk, run are formed exactly as above (spec_narrow);
+// with val = topk + run of each symbol the pair appends
+//     V = (val_a << m_b) + val_b    in    M = m_a + m_b bits.
+// Returns M; the caller raises the flag if any M of the half exceeds 32 (the m are non-negative and far below 2^31, so
+// this covers "some m exceeds 32"), and then redoes the half from its saved state with encode_symbol, symbol by symbol.
+//   * M <= 32: val_a < 2^m_a and val_b < 2^m_b give V <= (2^m_a - 1) 2^m_b + 2^m_b - 1 < 2^M <= 2^32: no carry is lost in 32
+//     bits.  (m_b == 32 leaves m_a == 0 and val_a == 0, so that the hardware takes the shift mod 32 does not matter.)
+//     The low M bits of acc << M are zero, so the OR is again an addition: a v_lshl_add and a v_add3.  Fewer than 32
+//     bits were waiting and at most 32 arrive: at most ONE dword completes, and the accumulator's 64 bits hold it all.
+//     The stored dwords and the waiting bits are those of two single appends: (acc << m_a | val_a) << m_b | val_b.
+//   * Stray stores of a pair with M > 32 (garbage in acc from there on, in that lane).  nbm is always formed as
+//     (nbm + M) | -32, so nbm + 32 stays in [0, 31] and congruent mod 32 to the true number of bits appended since the
+//     half began: it IS the true number of waiting bits, in every lane, flagged or not.  The store region is entered
+//     exactly when waiting + M >= 32, i.e. exactly when the true coder completes at least one dword in this pair, and
+//     then advances off by ONE dword where the true coder advances by one or more.  By induction over the pairs of the
+//     half, off never exceeds the true coder's offset before the same pair, and a stray store lands at an offset that
+//     the true coder writes during this pair or later: the redo, which starts from the saved off and writes every dword
+//     up to the true final offset, overwrites it.
+//   * The caller's chunk budget assumes at most one dword per SYMBOL and lane; here it is at most one per pair.
+template <bool FIXUP, bool CB32, int ST = 4>
+__device__ __forceinline__ uint32_t encode_pair_spec(EncState &S, SpecCarry &C, uint2 a, uint2 b, uint32_t ca, uint32_t cb,
+                                                     double rca, double rcb, uint32_t sh_, uint8_t *wbase)
+{
+    const SpecBits A = spec_narrow<FIXUP, CB32>(S, C, a.x, a.y, ca, rca, sh_);
+    const SpecBits B = spec_narrow<FIXUP, CB32>(S, C, b.x, b.y, cb, rcb, sh_);
+    const uint32_t M = A.m + B.m;
+    const uint32_t V = ((A.topk + A.run) << (B.m & 31u)) + B.topk; // (+ B.run in the v_add3 below)
+    const uint64_t sa = S.acc << (M & 63u);
+    S.acc = (sa & 0xFFFFFFFF00000000ull) | (uint32_t)((uint32_t)sa + V + B.run);
+    const uint32_t nb = C.nbm + M; // as encode_symbol_spec from here on
+    if ((int32_t)nb >= 0) {
+        *reinterpret_cast<uint32_t *>(wbase + S.off) = stream_dword<ST>((uint32_t)(S.acc >> (nb & 63u)));
+        asm volatile("v_add_u32 %0, %1, %0" : "+v"(S.off) : "i"(stride_of<ST>) : "memory");
+    }
+    C.nbm = nb | 0xFFFFFFE0u;
+    return M;
 }
 
 // The EOF tail (codec.rs:91-99) + flush_bits (bitio/mod.rs:183-198).  `shifts` is what

@@ -561,22 +561,25 @@ __device__ __forceinline__ void coder_chunk(EncState &S, uint2 *ring, uint32_t l
             for (int i = 0; i < 8; i++)
                 rn[i] = nb[i];
         }
-        // Eight symbols straight-line; the rare symbol whose pending run needs more than one
-        // 32-bit append only raises a flag, and the half is then redone from the saved state
-        // with the general encode_symbol (no per-symbol branch, no merge of two state versions).
+        // Eight symbols straight-line, two to an append (encode_pair_spec: four store regions per half, a dword
+        // completes once per four symbols at 8 bits a symbol).  The rare pair that appends more than 32 bits -- a long
+        // pending run, or two long shared prefixes in a row -- only raises a flag, and the half is then redone from the
+        // saved state with the general encode_symbol, symbol by symbol (no per-symbol branch, no merge of two state
+        // versions).  kChunkBudget (at most one dword per symbol and lane) now has a factor of two to spare.
         const EncState S0  = S;
         SpecCarry      C   = spec_begin(S);
-        uint32_t       mx  = 0;          // largest append of the half (pairs of symbols fold into one v_max3_u32)
+        uint32_t       mx  = 0;          // largest append of the half
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
+        for (int i = 0; i < 8; i += 2) {
             const uint32_t nup = MODE == 0 ? p + h * 8 + i : nfreeze;
             // keeps ISel from turning (u64 >> 32) -> f64 into a 64-bit conversion (+1 v_add_f64); converting
             // as signed avoids that too, but v_cvt_f64_i32 measured 9 % slower for the whole kernel.
             // Applied to the ring value in place: on a copy it costs a v_mov per symbol, because the redo below reads lh[i] again.
             asm volatile("" : "+v"(lh[i].y));
-            const uint32_t hi = lh[i].y;
-            const uint32_t m = encode_symbol_spec<FIXUP, CB32, kPairStride>(S, C, lh[i].x, hi, 257u + nup, MODE == 0 ? r[i] : rc[nfreeze], sh, wdst);
-            mx               = m > mx ? m : mx;
+            asm volatile("" : "+v"(lh[i + 1].y));
+            const uint32_t M = encode_pair_spec<FIXUP, CB32, kPairStride>(S, C, lh[i], lh[i + 1], 257u + nup, 257u + nup + (MODE == 0 ? 1u : 0u),
+                                                                          MODE == 0 ? r[i] : rc[nfreeze], MODE == 0 ? r[i + 1] : rc[nfreeze], sh, wdst);
+            mx               = M > mx ? M : mx;
         }
         spec_end(S, C);
         const uint64_t bad = __builtin_amdgcn_ballot_w64(mx > 32u);
